@@ -1,6 +1,6 @@
 """bench.py -- the headline metric of BASELINE.json on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]         (N > 1: launches its own N ranks over 127.0.0.1)
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]   (N > 1: launches its own N ranks over 127.0.0.1)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 Workload (config.workload): MaxSim late-interaction retrieval, 32 query vectors x 1,000,000 chunk
@@ -36,7 +36,10 @@ Extra objects in the JSON line (rank 0; all but `roofline` at N = 1 only):
   configs       BASELINE.json configs 1-5 on one GPU (scripts/bench_configs.py), outside the headline's timed region
   raglite_shaped  the headline pipeline on unit-norm fp16-rounded and on clustered corpora (what RAGLite stores): throughput,
                 candidates per query, fallback, float64 parity at 1e-4 absolute
+                (configs and raglite_shaped: their scalars only; the whole records are one `{"side_workloads": ...}` line on stderr)
   candidates_per_query / fallback_steps  what the bound-filtered pipeline did on the headline's own data
+
+--dump-outputs DIR: after the timed steps, what the last one returned (scores.npy, chunk_ids.npy; see dump_outputs).
 """
 
 from __future__ import annotations
@@ -142,6 +145,16 @@ def vendor_gemm_calibration(dev, n_rows: int, iters: int = 20) -> dict:
     return out
 
 
+def dump_outputs(out_dir: Path, last) -> None:
+    """What the last timed step handed its caller, one row per query of the step: the top-k scores (float32) and the global chunk
+    ordinals (float64, exact for any int32).  The corpus, its chunks and the queries are seeded, so with the same arguments two builds
+    of the project can be compared output for output."""
+    scores, chunks = (x.cpu().numpy() for x in last)
+    out_dir.mkdir(parents=True, exist_ok=True)
+    np.save(out_dir / "scores.npy", scores.astype(np.float32))
+    np.save(out_dir / "chunk_ids.npy", chunks.astype(np.float64))
+
+
 def main() -> None:
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -165,7 +178,10 @@ def main() -> None:
                     help="route option set as a process-wide default before any index exists (A/B runs; see include/raglite_hip.h 'options')")
     ap.add_argument("--same-gpu", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--backend", default="nccl", help=argparse.SUPPRESS)
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the last timed step returned as DIR/<name>.npy (see dump_outputs)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # `python bench.py --gpus N` on its own: become N ranks (one process per GPU) through torch.distributed.run, exactly the
@@ -278,6 +294,8 @@ def main() -> None:
         return elapsed, ev0.elapsed_time(ev1), out
 
     elapsed, region_ms, last = timed_steps(args.steps, args.warmup)
+    if args.dump_outputs and rank == 0:  # (every rank holds the same merged result)
+        dump_outputs(Path(args.dump_outputs), last)
 
     # How the data decided the bound-filtered pipeline (outside the timed region: reading the counters synchronises).  The steps cycle
     # through n_batches distinct query batches, so one more run of each tells what every timed step did.
@@ -816,11 +834,29 @@ def fraction_violations(node, path: str = "") -> list[str]:
     return bad
 
 
+# The side workloads' whole records (BASELINE configs 1-5, RAGLite-shaped corpora: 14 KB of a 23 KB line in round 6, when the recorded
+# runs stopped parsing the line) leave on stderr as one JSON line of their own; the result line keeps their scalars (~10 KB in all).
+SIDE_BLOCKS = ("configs", "raglite_shaped")
+
+
+def _scalars(block: dict) -> dict:
+    out = {key: val for key, val in block.items() if not isinstance(val, (dict, list)) and not (isinstance(val, str) and len(val) > 80)}
+    if "error" in block:  # a failing side workload still says so in the line
+        out["error"] = str(block["error"])[:200]
+    return out
+
+
 def _finish(result: dict) -> str:
+    """The result line.  Fractions are checked over the whole record, side workloads included, before those are cut to their scalars."""
     _add_score_tolerance(result)
     result["bench_schema"] = BENCH_SCHEMA
     bad = fraction_violations(result)
     result["fraction_check"] = "ok: every frac / *_frac in (0, 1]" if not bad else {"violations": bad}
+    side = {key: result[key] for key in SIDE_BLOCKS if key in result}
+    if side:
+        print(json.dumps({"side_workloads": side}), file=sys.stderr, flush=True)
+        for key, blocks in side.items():
+            result[key] = {name: _scalars(block) for name, block in blocks.items()}
     return json.dumps(result)
 
 

@@ -45,6 +45,45 @@ def test_checker_rules():
     assert bench.fraction_violations({"cfg2": {"roofline": dict(named, frac=1.2)}})
 
 
+def test_side_workloads_leave_the_line_for_stderr(capsys):
+    """Round 6's whole record (a 23 KB line): the result line keeps the side workloads' scalars and stays short, their whole records
+    are the JSON line on stderr, and the checks that read them (fractions, the unit-norm score bar) still see all of them."""
+    full = json.loads((ROOT / "profiles" / "r06_end_bench.json").read_text())
+    for key in ("score_tolerance", "bench_schema", "fraction_check"):
+        full.pop(key)
+    line = bench._finish(json.loads(json.dumps(full)))  # noqa: SLF001
+    side = json.loads(capsys.readouterr().err.strip().splitlines()[-1])["side_workloads"]
+    assert side == {key: full[key] for key in bench.SIDE_BLOCKS}
+    out = json.loads(line)
+    assert len(line) < 12_000 and "\n" not in line
+    assert out["ms_per_step"] == full["ms_per_step"] and out["steps"] == full["steps"]
+    assert out["configs"]["cfg2"]["value"] == full["configs"]["cfg2"]["value"] and "roofline" not in out["configs"]["cfg2"]
+    assert out["fraction_check"].startswith("ok") and out["score_tolerance"]["pass_abs_on_unit_norm"] is True
+    bad = dict(full, configs={"cfg1": {"roofline": {"frac": 6.08}}, "cfg2": {"error": "RuntimeError: " + "x" * 500}})
+    out = json.loads(bench._finish(bad))  # noqa: SLF001
+    assert out["fraction_check"] == {"violations": ["configs.cfg1.roofline.frac = 6.08 is not in (0, 1]"]}
+    assert out["configs"]["cfg2"]["error"].startswith("RuntimeError: ")
+
+
+def test_dump_outputs_writes_the_step_result(tmp_path):
+    import numpy as np
+    import torch
+
+    scores = torch.rand(128, 100)
+    chunks = torch.randint(0, 2**31 - 1, (128, 100), dtype=torch.int32)
+    bench.dump_outputs(tmp_path / "dump", (scores, chunks))
+    assert sorted(p.name for p in (tmp_path / "dump").iterdir()) == ["chunk_ids.npy", "scores.npy"]
+    s, c = np.load(tmp_path / "dump" / "scores.npy"), np.load(tmp_path / "dump" / "chunk_ids.npy")
+    assert s.dtype == np.float32 and np.array_equal(s, scores.numpy())
+    assert c.dtype == np.float64 and np.array_equal(c.astype(np.int64), chunks.numpy())
+
+
+@pytest.mark.parametrize("argv", [["--steps", "0"], ["--warmup", "-1"]])
+def test_bench_rejects_steps_it_cannot_time(argv):
+    res = subprocess.run([sys.executable, str(ROOT / "bench.py"), *argv], capture_output=True, text=True, timeout=120)
+    assert res.returncode == 2 and "--steps must be at least 1" in res.stderr
+
+
 def _recorded_lines():
     out = []
     for path in sorted((ROOT / "profiles").glob("r*bench*.json")) + sorted(ROOT.glob("BENCH_r*.json")):
