@@ -3,7 +3,9 @@
 #include <cstdlib>
 #include <cstring>
 #include <limits>
+#include <memory>
 #include <mutex>
+#include <utility>
 #include <vector>
 
 #include "common.h"
@@ -115,14 +117,37 @@ struct DevBuf {
     T* as() const { return reinterpret_cast<T*>(p); }
 };
 
-// Growable device buffer owned by an index (never shrinks; no allocation in steady state).
+// RL_HIP for the lifecycle calls, whose HIP errors name the entry point ("rl_index_append: out of memory").
+int hip_status(hipError_t e, const char* who) {
+    if (e == hipSuccess) return RL_OK;
+    return fail(e == hipErrorOutOfMemory ? RL_ERR_NOMEM : RL_ERR_HIP, std::string(who) + ": " + hipGetErrorString(e));
+}
+
+// Device memory owned by an index: freed with its owner, move-only (one owner per block).  As scratch it grows: reserve() never
+// shrinks, frees the old block before it allocates and does not keep the contents (no allocation in steady state).
 struct Pool {
     void* p = nullptr;
     size_t cap = 0;
+    Pool() = default;
+    Pool(const Pool&) = delete;
+    Pool& operator=(const Pool&) = delete;
+    Pool(Pool&& o) noexcept : p(o.p), cap(o.cap) { o.p = nullptr; o.cap = 0; }
+    Pool& operator=(Pool&& o) noexcept {  // (frees what this held right away)
+        if (this != &o) { release(); std::swap(p, o.p); std::swap(cap, o.cap); }
+        return *this;
+    }
+    ~Pool() { release(); }
     int reserve(size_t bytes) {
         if (bytes <= cap) return RL_OK;
-        if (p) { (void)hipFree(p); p = nullptr; cap = 0; }
+        release();
         RL_HIP(hipMalloc(&p, bytes));
+        cap = bytes;
+        return RL_OK;
+    }
+    // A fresh block of exactly `bytes` (the buffers a lifecycle call builds before it commits them to the index); frees what it held.
+    int alloc(size_t bytes, const char* who) {
+        release();
+        RL_TRY(hip_status(hipMalloc(&p, bytes), who));
         cap = bytes;
         return RL_OK;
     }
@@ -133,6 +158,11 @@ struct Pool {
     }
     template <class T>
     T* as() const { return reinterpret_cast<T*>(p); }
+};
+// A Pool that reads as the T* the kernels take: the index' fixed-size device arrays.
+template <class T>
+struct DevArray : Pool {
+    operator T*() const { return as<T>(); }
 };
 
 // Input staging: returns a device pointer for `src` (copying when it is a host pointer).
@@ -226,22 +256,46 @@ bool option_value_ok(int key, int64_t value) {
     }
 }
 
+// The three derived images of the rows (IMG_* bits): a block, the scale it was built with (0 = no image) and the rows it covers.
+struct Image {
+    Pool buf;
+    float scale = 0.f;
+    int64_t rows = 0;
+    void drop() {
+        buf.release();
+        scale = 0.f;
+        rows = 0;
+    }
+    bool covers(float at, int64_t n_rows) const { return scale > 0.f && scale == at && rows == n_rows && n_rows > 0; }
+};
+// max |e|, max |e_lo|, max |e_lo| / |e|, min |e| over the rows (e_lo: what the HI halves drop), the split scale they were computed at and
+// the rows folded in so far: what the error bounds of the half-bytes routes are made of.  min |e| is never raised by deletions (conservative).
+struct NormStats {
+    float max_row_norm = 0.f, max_lo_norm = 0.f, max_lo_ratio = 0.f;
+    float min_row_norm = std::numeric_limits<float>::infinity();
+    float max_row_norm_scale = 0.f;
+    int64_t max_row_norm_rows = 0;
+    void reset() { *this = NormStats(); }
+    bool measured(int64_t n_rows) const { return max_row_norm_rows == n_rows && max_row_norm > 0.f; }
+};
+
 }  // namespace
 }  // namespace rl
 
 struct rl_index {
     const float* E = nullptr;       // fp32 storage ...
-    const uint16_t* E16 = nullptr;  // ... or IEEE fp16 storage (rl_index_create_f16); exactly one is set
-    bool owns_E = false;
+    const uint16_t* E16 = nullptr;  // ... or IEEE fp16 storage (rl_index_create_f16); exactly one is set: the caller's rows or `owned_rows`
+    rl::Pool owned_rows;            // the rows when the index owns them (copied from the host, appended to, compacted)
+    bool owns_E() const { return owned_rows.p != nullptr; }
     int64_t n_rows = 0;
     int32_t dim = 0;
     int64_t n_chunks = 0;
     int metric = RL_COSINE;
     bool has_empty_chunk = false;
-    int64_t* offsets = nullptr;       // device [n_chunks + 1]
-    int32_t* row_to_chunk = nullptr;  // device [n_rows + 65]
-    float* norm = nullptr;            // device [n_rows]  (cosine)
-    float* sumsq = nullptr;           // device [n_rows]  (l2)
+    rl::DevArray<int64_t> offsets;       // device [n_chunks + 1]
+    rl::DevArray<int32_t> row_to_chunk;  // device [n_rows + 65]
+    rl::DevArray<float> norm;            // device [n_rows]  (cosine)
+    rl::DevArray<float> sumsq;           // device [n_rows]  (l2)
     int n_cu = 256;
     std::mutex mu;
     rl::SelectWorkspace ws;
@@ -253,20 +307,21 @@ struct rl_index {
     int64_t cap_chunks = 0;               // chunks the device CSR can hold
     std::vector<int64_t> h_offsets;       // host copy of the CSR
     std::vector<uint32_t> h_live;         // host bitset over chunks: 1 = live (empty until the first delete)
-    uint32_t* live_chunk_bits = nullptr;  // device copy of h_live (nullptr: every chunk is live)
-    uint32_t* live_row_bits = nullptr;    // the same expanded to rows
+    rl::DevArray<uint32_t> live_chunk_bits;  // device copy of h_live (empty: every chunk is live)
+    rl::DevArray<uint32_t> live_row_bits;    // the same expanded to rows
     int64_t n_dead_chunks = 0, n_dead_rows = 0;
     rl::Pool maskbuf;                     // per-call effective row mask
     rl::Pool qsplit;                      // fp16 (hi, lo) query fragments of a MaxSim batch (maxsim_stream.hip)
     // SPLIT arithmetic of the stream kernel (fp32 storage only): range of the row norms, and what follows from it
-    uint32_t* d_range = nullptr;          // device scratch of launch_row_range
+    rl::DevArray<uint32_t> d_range;       // device scratch of launch_row_range
     float max_abs = 0.f, min_row_max = std::numeric_limits<float>::infinity();  // over rows that are not all zero
     bool nonfinite = false;
     int arithmetic = RL_ARITH_AUTO;
     float split_scale = 0.f;              // > 0: power of two applied to the corpus inside the kernel; 0: exact fp32 MFMAs
     // Pre-split corpus image of maxsim_gemm.hip (fp16 hi | lo planes in the kernel's LDS layout, 4 B per element) and
     // the "last row of its chunk" bitmap; built with the index, extended on append, rebuilt when split_scale changes.
-    rl::Pool planes, ends, qplanes;
+    rl::Image planes;
+    rl::Pool ends, qplanes;
     rl::Pool q32;                         // rl_maxsim_topk_batch_f16: the fp16 queries widened to fp32 (what the query-side kernels read)
     rl::Pool cand;                        // rl_maxsim_rerank: sanitised candidate ordinals
     rl::Pool fused;                       // fused batched top-k: sample scores, thresholds, candidate lists, counters
@@ -274,26 +329,18 @@ struct rl_index {
     rl::Pool rankbuf;                     // rank cut (order-first-then-filter): histogram levels + tie counts
     // HI plane (round 2): fp16(e * split_scale) rounded to nearest (toward zero until round 3), row-major [n_rows x dim] -- the hi halves of the fp16
     // split as a matrix of their own, 2 B per element: what the single-query search streams (search_rows_hi).
-    rl::Pool hiplane, hibuf;
-    float hi_scale = 0.f;                 // the scale the plane was built with; 0 = no plane
-    int64_t hi_rows = 0;                  // rows it covers
+    rl::Image hiplane;
+    rl::Pool hibuf;
     // ... and the same halves in the one-plane IMAGE layout (maxsim_gemm.hip HALF): what the approximate MaxSim pass of a
-    // batch multiplies (maxsim_batch_hi); max_row_norm = max |e| over the rows, for its error bound
-    rl::Pool hi_image;
-    float hi_image_scale = 0.f;
-    int64_t hi_image_rows = 0;
-    float max_row_norm = 0.f, max_lo_norm = 0.f, max_lo_ratio = 0.f;  // max |e|, max |e_lo|, max |e_lo| / |e| (e_lo: what the HI halves drop)
-    float min_row_norm = std::numeric_limits<float>::infinity();  // min |e| over the rows folded in so far (never raised by deletions: conservative)
-    float max_row_norm_scale = 0.f;       // the split scale they were computed at
-    uint32_t* d_norms = nullptr;          // device scratch of launch_max_row_norm (4 words)
-    int64_t max_row_norm_rows = 0;        // rows folded into them
+    // batch multiplies (maxsim_batch_hi); the row-norm statistics are for the error bounds of both
+    rl::Image hi_image;
+    rl::NormStats norm_stats;
+    rl::DevArray<uint32_t> d_norms;       // device scratch of launch_max_row_norm (4 words)
     // The scratch above is shared by all calls on this handle; `mu` serialises only their host side.  Device-mode calls are
     // asynchronous, so a call arriving on a DIFFERENT stream than the previous one first waits for that stream.
     hipStream_t last_stream = nullptr;
     bool last_stream_set = false;
     int64_t ends_rows = -1;               // rows the `ends` bitmap covers (-1: not built); kept by both images
-    float planes_scale = 0.f;             // the scale the image was built with; 0 = no image
-    int64_t planes_rows = 0;              // rows the image covers
     // What the last bound-filtered search on this handle left behind (rl_index_filter_stats): per-query candidate counters and the
     // device flag its guarded full-precision fallback waits on.  Pointers into the scratch above, valid until the next call.
     // rl_rank_cut_*: the staged rank cut of a SHARDED corpus keeps its queries and scores here between the calls
@@ -311,7 +358,7 @@ struct rl_index {
     // ... and a pinned host word every bound-filtered MaxSim batch copies its fallback flag to when it is done (asynchronously): a batch
     // that finds the previous one fell back asks for the pre-split image, so that an index whose data keeps defeating the bound runs its
     // full-precision passes through the eight-query kernel instead of the streaming kernels (3-4 x faster) from the second batch on
-    uint32_t* h_fell_back = nullptr;
+    std::unique_ptr<uint32_t, hipError_t (*)(void*)> h_fell_back{nullptr, hipHostFree};
     uint32_t* d_fell_back = nullptr;  // the device's view of that word (written by guarded_select_kernel)
     // rl_time_kernel kind 8: what the candidate pass of the last fused-HI row search ran with (pointers into misc / fused / pp_work: valid
     // while those pools have not been re-reserved, which `pools` pins down)
@@ -320,6 +367,7 @@ struct rl_index {
         const float* thr1 = nullptr; int64_t round1_tiles = 0;  // two-round candidate pass: the first round's thresholds and tiles
         const void* pools[3] = {nullptr, nullptr, nullptr};
     } replay;
+    ~rl_index() { rl::select_workspace_free(ws); }  // (every other member frees itself)
 };
 
 namespace {
@@ -356,7 +404,7 @@ void update_split_scale(rl_index* idx) {
 // Folds the magnitude range of rows [first, first + n) into the index (synchronises the stream: build / append only).
 int scan_row_range(rl_index* idx, int64_t first, int64_t n, hipStream_t s) {
     if (idx->E16 || !idx->E || idx->dim % 4) return RL_OK;
-    if (!idx->d_range) RL_HIP(hipMalloc(&idx->d_range, 16));
+    RL_TRY(idx->d_range.reserve(16));
     RL_TRY(rl::launch_row_range(idx->E + (size_t)first * idx->dim, n, idx->dim, idx->d_range, s));
     uint32_t h[3];
     RL_HIP(hipMemcpyAsync(h, idx->d_range, sizeof(h), hipMemcpyDeviceToHost, s));
@@ -374,11 +422,40 @@ int scan_row_range(rl_index* idx, int64_t first, int64_t n, hipStream_t s) {
 // Scale of the corpus image the index should have: the split scale of an fp32 corpus, 1 for an fp16-stored one (its image is
 // the stored halves, permuted), 0 = no image.
 float image_scale(const rl_index* idx) { return idx->E16 ? 1.0f : idx->split_scale; }
-// Which of the three images may exist right now: all of them, or -- lazy images -- those some call has asked for (demand_images)
+// Which of the three images (the records `planes`, `hi_image`, `hiplane`) may exist right now: all of them, or -- lazy images -- those some
+// call has asked for (demand_images)
 enum : uint32_t { IMG_PLANES = 1u, IMG_HI_IMAGE = 2u, IMG_HI_PLANE = 4u, IMG_ALL = 7u };
 uint32_t image_need(const rl_index* idx) { return idx->opt.on(RL_OPT_LAZY_IMAGES) ? idx->demanded : IMG_ALL; }
-bool image_valid(const rl_index* idx) {
-    return idx->planes_scale > 0.f && idx->planes_scale == image_scale(idx) && idx->planes_rows == idx->n_rows && idx->n_rows > 0;
+rl::Image& image_record(rl_index* idx, uint32_t bit) {
+    return bit == IMG_PLANES ? idx->planes : bit == IMG_HI_IMAGE ? idx->hi_image : idx->hiplane;
+}
+
+// The dims the half-bytes routes take: any multiple of 32 up to 1024; beyond -- the 1536- to 4096-wide embedders the reference also accepts
+// (src/raglite/_embed.py:155-158) -- multiples of 128 (round 6: the exact re-scoring kernels walk wider queries in 128-column windows).
+constexpr int32_t HI_MAX_DIM = 4096;
+bool hi_dim_ok(int32_t d) { return d % 32 == 0 && d >= 32 && (d <= 1024 || (d <= HI_MAX_DIM && d % 128 == 0)); }
+// The dims of the fp16 stream kernel; wider embedders -- round 6 -- go through the packed scan (scan16.hip)
+bool stream16_dim_ok(int32_t d) { return d == 128 || d == 256 || d == 384 || d == 512 || d == 768 || d == 1024 || (d > 1024 && hi_dim_ok(d)); }
+// The rounding term of every half-bytes bound: an fp32 sum of `dim` products is off by at most dim 2^-24 of sum |products| <= |q| |e|, once in
+// the approximate pass and once in the exact one, + the query's 2^-22 split: 2^-12 |q| |e| per started 1024 terms (twice what it takes).
+float sum_eps(int32_t d) { return 0x1p-12f * (float)((d + 1023) / 1024); }
+bool big_corpus(const rl_index* idx) { return (int64_t)idx->n_rows * idx->dim >= (int64_t(64) << 20); }
+
+bool image_valid(const rl_index* idx) { return idx->planes.covers(image_scale(idx), idx->n_rows); }
+bool hi_valid(const rl_index* idx) { return idx->hiplane.covers(idx->split_scale, idx->n_rows); }
+bool hi_image_valid(const rl_index* idx) { return idx->hi_image.covers(idx->split_scale, idx->n_rows) && idx->norm_stats.measured(idx->n_rows); }
+// What the approximate MaxSim pass of a batch multiplies at ONE fp16 product per multiply: the image of the hi halves of an fp32 corpus --
+// or the image of an fp16-STORED corpus itself (the stored halves ARE the corpus: the pass then drops only the queries' lo halves, the
+// bound has no e_lo term, and the candidates are re-scored over the stored rows).  Same size gate for both (>= 64 M elements).
+bool approx_image_valid(const rl_index* idx) {
+    if (!idx->E16) return hi_image_valid(idx);
+    return image_valid(idx) && big_corpus(idx) && hi_dim_ok(idx->dim) && idx->norm_stats.measured(idx->n_rows);
+}
+const void* approx_image(const rl_index* idx) { return idx->E16 ? idx->planes.buf.p : idx->hi_image.buf.p; }
+float approx_scale(const rl_index* idx) { return idx->E16 ? 1.0f : idx->split_scale; }
+// IMG_* bits of the images that cover the current rows
+uint32_t images_built(const rl_index* idx) {
+    return (image_valid(idx) ? IMG_PLANES : 0u) | (hi_image_valid(idx) ? IMG_HI_IMAGE : 0u) | (hi_valid(idx) ? IMG_HI_PLANE : 0u);
 }
 
 // The images are optional accelerators (pre-split image 4 B, HI image 2 B, HI plane 2 B per element next to the rows): one is only
@@ -399,230 +476,131 @@ bool image_fits(const rl_index* idx, const rl::Pool& pool, size_t need) {
     if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) { (void)hipGetLastError(); return true; }
     return free_b + pool.cap >= need + image_headroom(idx);  // (reserve() frees the old block before it allocates)
 }
+// Rows the images are sized for: the owned buffers' capacity, so that an append into spare capacity extends them in place
+int64_t image_cap_rows(const rl_index* idx) { return std::max<int64_t>(idx->n_rows, idx->owns_E() ? idx->cap_rows : idx->n_rows); }
 
-// Builds / extends the corpus image so that it covers rows [0, idx->n_rows) at image_scale(idx).  Not having the image is
-// never an error (the streaming kernels read the stored rows): an allocation failure or a device too full just leaves it absent.
-
-int refresh_row_norm16(rl_index* idx, hipStream_t s);
 // "last row of its chunk" bitmap over the current rows: what the batch kernels over either image find chunk ends with (125 KB per 1 M rows)
 int refresh_ends(rl_index* idx, hipStream_t s) {
     if (idx->ends_rows == idx->n_rows && idx->ends.p) return RL_OK;
-    const int64_t cap = std::max<int64_t>(idx->n_rows, idx->owns_E ? idx->cap_rows : idx->n_rows);
-    RL_TRY(idx->ends.reserve(rl::chunk_ends_words(cap) * sizeof(uint32_t)));
+    RL_TRY(idx->ends.reserve(rl::chunk_ends_words(image_cap_rows(idx)) * sizeof(uint32_t)));
     RL_TRY(rl::launch_chunk_ends(idx->row_to_chunk, idx->n_rows, idx->ends.as<uint32_t>(), s));
     idx->ends_rows = idx->n_rows;
     return RL_OK;
 }
-int refresh_planes(rl_index* idx, hipStream_t s) {
-    const bool half = idx->E16 != nullptr;
-    const bool want = idx->opt.on(RL_OPT_KEEP_IMAGE) && (idx->E16 || idx->E) && image_scale(idx) > 0.f && idx->dim % 32 == 0 && idx->dim >= 32 &&
-                      idx->n_rows > 0 && (image_need(idx) & IMG_PLANES);
-    idx->ends_rows = -1;  // (rows or chunk structure may have changed: whoever needs the bitmap rebuilds it)
-    if (!want) {
-        idx->planes.release();
-        idx->planes_scale = 0.f;
-        idx->planes_rows = 0;
-        return RL_OK;
-    }
-    const int64_t cap = std::max<int64_t>(idx->n_rows, idx->owns_E ? idx->cap_rows : idx->n_rows);
-    const size_t need = rl::planes_bytes(cap, idx->dim, half);
-    int64_t first = idx->planes_scale == image_scale(idx) ? (idx->planes_rows & ~int64_t(15)) : 0;
-    if (idx->planes.cap < need) first = 0;  // Pool::reserve does not keep the contents
-    // (an exactly sized image is "already paid for" and must survive an append into spare capacity however full the device has become)
-    if (!image_fits(idx, idx->planes, need) || idx->planes.reserve(need) != RL_OK) {
-        (void)hipGetLastError();
-        idx->no_room |= IMG_PLANES;
-        idx->planes.release();
-        idx->planes_scale = 0.f;
-        idx->planes_rows = 0;
-        return RL_OK;
-    }
-    const int st = half ? rl::launch_preformat_rows16(idx->E16, first, idx->n_rows, idx->dim, idx->planes.p, s)
-                        : rl::launch_presplit_rows(idx->E, first, idx->n_rows, idx->dim, idx->split_scale, idx->planes.p, s);
-    if (st == RL_ERR_UNSUPPORTED) {  // e.g. caller-owned rows that are not 16-byte aligned: no image, the streaming kernels serve
-        idx->planes.release();
-        idx->planes_scale = 0.f;
-        idx->planes_rows = 0;
-        return RL_OK;
-    }
-    RL_TRY(st);
-    if (refresh_ends(idx, s) != RL_OK) {  // (the bitmap could not be allocated: no image either -- "never an error", as above)
-        (void)hipGetLastError();
-        idx->planes.release();
-        idx->planes_scale = 0.f;
-        idx->planes_rows = 0;
-        return RL_OK;
-    }
-    idx->planes_scale = image_scale(idx);
-    idx->planes_rows = idx->n_rows;
-    if (half) RL_TRY(refresh_row_norm16(idx, s));
-    return RL_OK;
-}
 
-// The HI plane follows the corpus like the image does: built for big fp32 corpora in split arithmetic whose dim the fp16
-// stream kernel takes; RAGLITE_NO_HI_PLANE=1 disables it (2 B per element of extra HBM).
-// The dims the half-bytes routes take: any multiple of 32 up to 1024; beyond -- the 1536- to 4096-wide embedders the reference also accepts
-// (src/raglite/_embed.py:155-158) -- multiples of 128 (round 6: the exact re-scoring kernels walk wider queries in 128-column windows).
-constexpr int32_t HI_MAX_DIM = 4096;
-bool hi_dim_ok(int32_t d) { return d % 32 == 0 && d >= 32 && (d <= 1024 || (d <= HI_MAX_DIM && d % 128 == 0)); }
-// The rounding term of every half-bytes bound: an fp32 sum of `dim` products is off by at most dim 2^-24 of sum |products| <= |q| |e|, once in
-// the approximate pass and once in the exact one, + the query's 2^-22 split: 2^-12 |q| |e| per started 1024 terms (twice what it takes).
-float sum_eps(int32_t d) { return 0x1p-12f * (float)((d + 1023) / 1024); }
-bool hi_valid(const rl_index* idx) {
-    return idx->hi_scale > 0.f && idx->hi_scale == idx->split_scale && idx->hi_rows == idx->n_rows && idx->n_rows > 0;
-}
-bool hi_image_valid(const rl_index* idx) {
-    return idx->hi_image_scale > 0.f && idx->hi_image_scale == idx->split_scale && idx->hi_image_rows == idx->n_rows && idx->n_rows > 0 &&
-           idx->max_row_norm_rows == idx->n_rows && idx->max_row_norm > 0.f;
-}
-// What the approximate MaxSim pass of a batch multiplies at ONE fp16 product per multiply: the image of the hi halves of an fp32 corpus --
-// or the image of an fp16-STORED corpus itself (the stored halves ARE the corpus: the pass then drops only the queries' lo halves, the
-// bound has no e_lo term, and the candidates are re-scored over the stored rows).  Same size gate for both (>= 64 M elements).
-bool approx_image_valid(const rl_index* idx) {
-    if (!idx->E16) return hi_image_valid(idx);
-    return image_valid(idx) && (int64_t)idx->n_rows * idx->dim >= (int64_t(64) << 20) && hi_dim_ok(idx->dim) && idx->max_row_norm_rows == idx->n_rows &&
-           idx->max_row_norm > 0.f;
-}
-const void* approx_image(const rl_index* idx) { return idx->E16 ? idx->planes.p : idx->hi_image.p; }
-float approx_scale(const rl_index* idx) { return idx->E16 ? 1.0f : idx->split_scale; }
-
-// max |e| over the rows of an fp16-stored corpus, folded in as rows arrive (synchronises the stream: build / append / compact only)
-int refresh_row_norm16(rl_index* idx, hipStream_t s) {
-    const bool off = !idx->opt.on(RL_OPT_KEEP_HI);  // (the switch of the half-bytes paths)
-    if (!idx->E16 || off || !image_valid(idx) || (int64_t)idx->n_rows * idx->dim < (int64_t(64) << 20)) {
-        if (idx->E16) { idx->max_row_norm = 0.f; idx->max_row_norm_rows = 0; }
-        return RL_OK;
-    }
-    if (idx->max_row_norm_rows > idx->n_rows) { idx->max_row_norm = 0.f; idx->max_row_norm_rows = 0; }  // (compacted: start over)
-    if (idx->max_row_norm_rows == idx->n_rows) return RL_OK;
-    const int64_t from = idx->max_row_norm_rows;
-    if (!idx->d_norms) RL_HIP(hipMalloc(&idx->d_norms, 16));
-    uint32_t bits[4] = {0, 0, 0, 0};
-    std::memcpy(&bits[0], &idx->max_row_norm, 4);
-    RL_HIP(hipMemcpyAsync(idx->d_norms, bits, 16, hipMemcpyHostToDevice, s));
-    RL_TRY(rl::launch_max_row_norm16(idx->E16 + (size_t)from * idx->dim, idx->n_rows - from, idx->dim, idx->d_norms, s));
-    RL_HIP(hipMemcpyAsync(bits, idx->d_norms, 16, hipMemcpyDeviceToHost, s));
+// Folds rows [from, n_rows) into the row-norm statistics: their four words make one round trip through d_norms around a pass of the row-norm
+// kernel (the fp16 one updates the first word only).  Synchronises the stream.
+int fold_row_norms(rl_index* idx, int64_t from, hipStream_t s) {
+    rl::NormStats& ns = idx->norm_stats;
+    RL_TRY(idx->d_norms.reserve(16));
+    float w[4] = {ns.max_row_norm, ns.max_lo_norm, ns.max_lo_ratio, ns.min_row_norm};
+    RL_HIP(hipMemcpyAsync(idx->d_norms, w, sizeof(w), hipMemcpyHostToDevice, s));
+    const size_t at = (size_t)from * idx->dim;
+    RL_TRY(idx->E16 ? rl::launch_max_row_norm16(idx->E16 + at, idx->n_rows - from, idx->dim, idx->d_norms, s)
+                    : rl::launch_max_row_norm(idx->E + at, idx->n_rows - from, idx->dim, idx->split_scale, idx->d_norms, s));
+    RL_HIP(hipMemcpyAsync(w, idx->d_norms, sizeof(w), hipMemcpyDeviceToHost, s));
     RL_HIP(hipStreamSynchronize(s));
-    std::memcpy(&idx->max_row_norm, &bits[0], 4);
-    idx->max_lo_norm = idx->max_lo_ratio = 0.f;
-    idx->max_row_norm_rows = idx->n_rows;
-    idx->max_row_norm_scale = 1.0f;
+    ns.max_row_norm = w[0];
+    ns.max_lo_norm = w[1];
+    ns.max_lo_ratio = w[2];
+    ns.min_row_norm = w[3];
+    ns.max_row_norm_rows = idx->n_rows;
+    ns.max_row_norm_scale = image_scale(idx);
     return RL_OK;
+}
+
+// max |e| over the rows of an fp16-stored corpus (its stored halves drop nothing: max |e_lo| and the ratio stay 0), folded in as rows arrive
+// (build / append / compact only)
+int refresh_row_norm16(rl_index* idx, hipStream_t s) {
+    rl::NormStats& ns = idx->norm_stats;
+    const bool off = !idx->opt.on(RL_OPT_KEEP_HI);  // (the switch of the half-bytes paths)
+    if (!idx->E16 || off || !image_valid(idx) || !big_corpus(idx)) {
+        if (idx->E16) ns.reset();
+        return RL_OK;
+    }
+    if (ns.max_row_norm_rows > idx->n_rows) ns.reset();  // (compacted: start over)
+    if (ns.max_row_norm_rows == idx->n_rows) return RL_OK;
+    return fold_row_norms(idx, ns.max_row_norm_rows, s);
 }
 
 // max |e|, max |e_lo|, max |e_lo| / |e|, min |e| over the rows at the current split scale: what the error bounds of BOTH half-bytes routes are
-// made of (the HI image's and the HI plane's), folded in as rows arrive (synchronises the stream: image builds only)
+// made of (the HI image's and the HI plane's), folded in as rows arrive (image builds only)
 int refresh_hi_norms(rl_index* idx, hipStream_t s) {
-    if (idx->max_row_norm_rows != idx->n_rows || idx->max_row_norm_scale != idx->split_scale) {  // fold the new rows' norms in
-        if (idx->max_row_norm_scale != idx->split_scale) {  // (the dropped halves depend on the scale: start over)
-            idx->max_row_norm = idx->max_lo_norm = idx->max_lo_ratio = 0.f;
-            idx->min_row_norm = std::numeric_limits<float>::infinity();
-            idx->max_row_norm_rows = 0;
-        }
-        const int64_t from = std::min<int64_t>(idx->max_row_norm_rows, idx->n_rows);
-        if (!idx->d_norms) RL_HIP(hipMalloc(&idx->d_norms, 16));
-        uint32_t bits[4] = {0, 0, 0, 0};
-        std::memcpy(&bits[0], &idx->max_row_norm, 4);
-        std::memcpy(&bits[1], &idx->max_lo_norm, 4);
-        std::memcpy(&bits[2], &idx->max_lo_ratio, 4);
-        std::memcpy(&bits[3], &idx->min_row_norm, 4);
-        RL_HIP(hipMemcpyAsync(idx->d_norms, bits, 16, hipMemcpyHostToDevice, s));
-        RL_TRY(rl::launch_max_row_norm(idx->E + (size_t)from * idx->dim, idx->n_rows - from, idx->dim, idx->split_scale, idx->d_norms, s));
-        RL_HIP(hipMemcpyAsync(bits, idx->d_norms, 16, hipMemcpyDeviceToHost, s));
-        RL_HIP(hipStreamSynchronize(s));
-        std::memcpy(&idx->max_row_norm, &bits[0], 4);
-        std::memcpy(&idx->max_lo_norm, &bits[1], 4);
-        std::memcpy(&idx->max_lo_ratio, &bits[2], 4);
-        std::memcpy(&idx->min_row_norm, &bits[3], 4);
-        idx->max_row_norm_rows = idx->n_rows;
-        idx->max_row_norm_scale = idx->split_scale;
-    }
-    return RL_OK;
+    rl::NormStats& ns = idx->norm_stats;
+    if (ns.max_row_norm_rows == idx->n_rows && ns.max_row_norm_scale == idx->split_scale) return RL_OK;
+    if (ns.max_row_norm_scale != idx->split_scale) ns.reset();  // (the dropped halves depend on the scale: start over)
+    return fold_row_norms(idx, std::min<int64_t>(ns.max_row_norm_rows, idx->n_rows), s);
 }
-// The HI halves in image layout + the largest row norm (synchronises the stream: build / append / compact only).
-int refresh_hi_image(rl_index* idx, hipStream_t s) {
-    const bool off = !idx->opt.on(RL_OPT_KEEP_HI);  // (shared with the row-major plane)
-    // (round 4: independent of the pre-split image -- an index with RL_OPT_KEEP_IMAGE = 0 keeps rows + HI image, 1.5 x the corpus, and its
-    // MaxSim batches fall back to the streaming kernels over the rows)
-    const bool want = !off && !idx->E16 && idx->E && idx->split_scale > 0.f && hi_dim_ok(idx->dim) &&
-                      (int64_t)idx->n_rows * idx->dim >= (int64_t(64) << 20) && (image_need(idx) & IMG_HI_IMAGE);
-    if (!want) {
-        idx->hi_image.release();
-        idx->hi_image_scale = 0.f;
-        idx->hi_image_rows = 0;
-        return RL_OK;
-    }
-    const int64_t cap = std::max<int64_t>(idx->n_rows, idx->owns_E ? idx->cap_rows : idx->n_rows);
-    const size_t need = rl::planes_bytes(cap, idx->dim, true);
-    int64_t first = idx->hi_image_scale == idx->split_scale ? (idx->hi_image_rows & ~int64_t(15)) : 0;
-    if (idx->hi_image.cap < need) first = 0;
-    if (!image_fits(idx, idx->hi_image, need) || idx->hi_image.reserve(need) != RL_OK) {
-        (void)hipGetLastError();
-        idx->no_room |= IMG_HI_IMAGE;
-        idx->hi_image.release();
-        idx->hi_image_scale = 0.f;
-        idx->hi_image_rows = 0;
-        return RL_OK;
-    }
-    const int st = rl::launch_presplit_hi_rows(idx->E, first, idx->n_rows, idx->dim, idx->split_scale, idx->hi_image.p, s);
-    if (st == RL_ERR_UNSUPPORTED) {
-        idx->hi_image.release();
-        idx->hi_image_scale = 0.f;
-        idx->hi_image_rows = 0;
-        return RL_OK;
-    }
-    RL_TRY(st);
-    if (refresh_ends(idx, s) != RL_OK) {  // (as for the pre-split image: without the bitmap the image is just absent)
-        (void)hipGetLastError();
-        idx->hi_image.release();
-        idx->hi_image_scale = 0.f;
-        idx->hi_image_rows = 0;
-        return RL_OK;
-    }
-    idx->hi_image_scale = idx->split_scale;
-    idx->hi_image_rows = idx->n_rows;
-    RL_TRY(refresh_hi_norms(idx, s));
-    return RL_OK;
-}
-int refresh_hi_plane(rl_index* idx, hipStream_t s) {
-    RL_TRY(refresh_hi_image(idx, s));
-    const bool off = !idx->opt.on(RL_OPT_KEEP_HI) || !idx->opt.on(RL_OPT_KEEP_HI_PLANE);
+
+// Whether an image should cover the rows now: allowed by the options, the storage and the shape, and asked for (image_need).
+bool image_wanted(const rl_index* idx, uint32_t bit) {
     const int32_t d = idx->dim;
-    // (the stream kernel's dims; wider embedders -- round 6 -- go through the packed scan, scan16.hip)
-    const bool dim_ok = d == 128 || d == 256 || d == 384 || d == 512 || d == 768 || d == 1024 || (d > 1024 && hi_dim_ok(d));
-    const bool want = !off && !idx->E16 && idx->E && idx->split_scale > 0.f && dim_ok &&
-                      (int64_t)idx->n_rows * d >= (int64_t(64) << 20) && (idx->metric == RL_COSINE || idx->metric == RL_DOT || idx->metric == RL_L2) &&
-                      (image_need(idx) & IMG_HI_PLANE);
-    if (!want) {
-        idx->hiplane.release();
-        idx->hi_scale = 0.f;
-        idx->hi_rows = 0;
+    if (!(image_need(idx) & bit) || idx->n_rows <= 0) return false;
+    if (bit == IMG_PLANES) return idx->opt.on(RL_OPT_KEEP_IMAGE) && (idx->E16 || idx->E) && image_scale(idx) > 0.f && d % 32 == 0 && d >= 32;
+    // Both HI images: big fp32 corpora in split arithmetic.  (round 4: independent of the pre-split image -- an index with RL_OPT_KEEP_IMAGE = 0
+    // keeps rows + HI image, 1.5 x the corpus, and its MaxSim batches fall back to the streaming kernels over the rows)
+    const bool hi = idx->opt.on(RL_OPT_KEEP_HI) && !idx->E16 && idx->E && idx->split_scale > 0.f && big_corpus(idx);
+    if (bit == IMG_HI_IMAGE) return hi && hi_dim_ok(d);
+    // The HI plane follows the corpus like the images do, for the dims the fp16 stream kernel takes; RL_OPT_KEEP_HI_PLANE = 0 disables it
+    // (2 B per element of extra HBM).
+    return hi && idx->opt.on(RL_OPT_KEEP_HI_PLANE) && stream16_dim_ok(d) &&
+           (idx->metric == RL_COSINE || idx->metric == RL_DOT || idx->metric == RL_L2);
+}
+
+// Builds / extends one image so that it covers rows [0, idx->n_rows) at image_scale(idx) (the HI images exist for fp32 rows only, where that
+// is the split scale), or releases it when it is not wanted.  Not having an image is never an error (the streaming kernels read the stored
+// rows): a device too full, an allocation failure, a launch that does not take the rows or a missing `ends` bitmap just leave it absent --
+// and only the first two mark it `no_room` (demand_images asks again later).  Synchronises the stream: build / append / compact only.
+int refresh_image(rl_index* idx, uint32_t bit, hipStream_t s) {
+    rl::Image& im = image_record(idx, bit);
+    const bool tiled = bit != IMG_HI_PLANE;  // the two IMAGE-layout images: 16-row tiles, read with the `ends` bitmap
+    const int64_t n = idx->n_rows;
+    const int32_t d = idx->dim;
+    if (bit == IMG_PLANES) idx->ends_rows = -1;  // (rows or chunk structure may have changed: whoever needs the bitmap rebuilds it)
+    if (!image_wanted(idx, bit)) {
+        im.drop();
         return RL_OK;
     }
-    const int64_t cap = std::max<int64_t>(idx->n_rows, idx->owns_E ? idx->cap_rows : idx->n_rows);
-    const size_t need = (size_t)cap * d * sizeof(uint16_t);
-    int64_t first = idx->hi_scale == idx->split_scale ? idx->hi_rows : 0;
-    if (idx->hiplane.cap < need) first = 0;  // Pool::reserve does not keep the contents
-    if (!image_fits(idx, idx->hiplane, need) || idx->hiplane.reserve(need) != RL_OK) {
+    const float scale = image_scale(idx);
+    const int64_t cap = image_cap_rows(idx);
+    const size_t need = tiled ? rl::planes_bytes(cap, d, bit == IMG_HI_IMAGE || idx->E16) : (size_t)cap * d * sizeof(uint16_t);
+    int64_t first = im.scale == scale ? (tiled ? im.rows & ~int64_t(15) : im.rows) : 0;
+    if (im.buf.cap < need) first = 0;  // Pool::reserve does not keep the contents
+    // (an exactly sized image is "already paid for" and must survive an append into spare capacity however full the device has become)
+    if (!image_fits(idx, im.buf, need) || im.buf.reserve(need) != RL_OK) {
         (void)hipGetLastError();
-        idx->no_room |= IMG_HI_PLANE;
-        idx->hiplane.release();
-        idx->hi_scale = 0.f;
-        idx->hi_rows = 0;
+        idx->no_room |= bit;
+        im.drop();
         return RL_OK;
     }
-    const int st = rl::launch_cast_f16_scaled(idx->E + (size_t)first * d, idx->hiplane.as<uint16_t>() + (size_t)first * d,
-                                           (idx->n_rows - first) * d, idx->split_scale, s);
-    if (st == RL_ERR_UNSUPPORTED) {  // caller-owned rows that are not 16-byte aligned
-        idx->hiplane.release();
-        idx->hi_scale = 0.f;
-        idx->hi_rows = 0;
+    const int st = bit == IMG_HI_PLANE ? rl::launch_cast_f16_scaled(idx->E + (size_t)first * d, im.buf.as<uint16_t>() + (size_t)first * d,
+                                                                    (n - first) * d, scale, s)
+                   : bit == IMG_HI_IMAGE ? rl::launch_presplit_hi_rows(idx->E, first, n, d, scale, im.buf.p, s)
+                   : idx->E16 ? rl::launch_preformat_rows16(idx->E16, first, n, d, im.buf.p, s)
+                              : rl::launch_presplit_rows(idx->E, first, n, d, scale, im.buf.p, s);
+    if (st == RL_ERR_UNSUPPORTED) {  // e.g. caller-owned rows that are not 16-byte aligned
+        im.drop();
         return RL_OK;
     }
     RL_TRY(st);
-    RL_TRY(refresh_hi_norms(idx, s));  // (the plane's bound needs them whether or not the HI image exists)
-    idx->hi_scale = idx->split_scale;
-    idx->hi_rows = idx->n_rows;
+    if (tiled && refresh_ends(idx, s) != RL_OK) {  // (the bitmap could not be allocated)
+        (void)hipGetLastError();
+        im.drop();
+        return RL_OK;
+    }
+    // The row-norm statistics: the HI plane's bound needs them whether or not the HI image exists; fp16 storage has a max |e| of its own
+    // (which asks image_valid: the record comes first there)
+    if (bit == IMG_HI_PLANE) RL_TRY(refresh_hi_norms(idx, s));
+    im.scale = scale;
+    im.rows = n;
+    if (bit == IMG_HI_IMAGE) return refresh_hi_norms(idx, s);
+    if (bit == IMG_PLANES && idx->E16) return refresh_row_norm16(idx, s);
+    return RL_OK;
+}
+// The images of `which`, in their build order (the HI image before the HI plane).
+int refresh_images(rl_index* idx, hipStream_t s, uint32_t which = IMG_ALL) {
+    for (const uint32_t bit : {IMG_PLANES, IMG_HI_IMAGE, IMG_HI_PLANE})
+        if (which & bit) RL_TRY(refresh_image(idx, bit, s));
     return RL_OK;
 }
 
@@ -636,8 +614,8 @@ int demand_images(rl_index* idx, uint32_t bits, hipStream_t s) {
     if ((fresh & idx->no_room) && idx->scratch_epoch < idx->no_room_retry_epoch && !(fresh & ~idx->no_room)) return RL_OK;  // (asked recently, no room then)
     idx->demanded |= bits;
     idx->no_room &= ~fresh;
-    if (fresh & IMG_PLANES) RL_TRY(refresh_planes(idx, s));
-    if (fresh & (IMG_HI_IMAGE | IMG_HI_PLANE)) RL_TRY(refresh_hi_plane(idx, s));
+    // (the two HI images are refreshed together)
+    RL_TRY(refresh_images(idx, s, (fresh & IMG_PLANES) | (fresh & (IMG_HI_IMAGE | IMG_HI_PLANE) ? IMG_HI_IMAGE | IMG_HI_PLANE : 0u)));
     // An image that was NOT built because the device was too full at this moment (scratch pools and the caller's allocator have grown
     // since the index was created) must not leave the route on its slow path for good: its demand bit is cleared again, and a later
     // call -- at most one in 64, a hipMemGetInfo each -- asks again.  (An image the options / the shape do not allow stays "demanded".)
@@ -809,34 +787,6 @@ int rl_adapter_apply(const float* A, const float* queries, int32_t n_queries, in
 // ---- index ---------------------------------------------------------------------------------------------
 int rl_index_destroy(rl_index* idx) {
     if (!idx) return RL_OK;
-    if (idx->owns_E && idx->E) (void)hipFree(const_cast<float*>(idx->E));
-    if (idx->owns_E && idx->E16) (void)hipFree(const_cast<uint16_t*>(idx->E16));
-    if (idx->offsets) (void)hipFree(idx->offsets);
-    if (idx->row_to_chunk) (void)hipFree(idx->row_to_chunk);
-    if (idx->norm) (void)hipFree(idx->norm);
-    if (idx->sumsq) (void)hipFree(idx->sumsq);
-    if (idx->d_range) (void)hipFree(idx->d_range);
-    if (idx->d_norms) (void)hipFree(idx->d_norms);
-    if (idx->live_chunk_bits) (void)hipFree(idx->live_chunk_bits);
-    if (idx->live_row_bits) (void)hipFree(idx->live_row_bits);
-    idx->maskbuf.release();
-    idx->qsplit.release();
-    idx->planes.release();
-    idx->ends.release();
-    idx->qplanes.release();
-    idx->q32.release();
-    if (idx->h_fell_back) (void)hipHostFree(idx->h_fell_back);
-    idx->cand.release();
-    idx->fused.release();
-    idx->pp_work.release();
-    idx->rankbuf.release();
-    idx->hiplane.release();
-    idx->hibuf.release();
-    idx->hi_image.release();
-    select_workspace_free(idx->ws);
-    idx->scores.release();
-    idx->hits.release();
-    idx->misc.release();
     delete idx;
     return RL_OK;
 }
@@ -851,7 +801,7 @@ static int index_create_any(rl_index** out, const void* embeddings, bool f16, in
     if (scan_mode(metric) < 0) return fail(RL_ERR_INVALID, "rl_index_create: unknown metric");
     if (dim > 4096) return fail(RL_ERR_UNSUPPORTED, "rl_index_create: dim must be <= 4096");
     // (the stream kernels' dims; wider -- round 6 -- through the packed scan, the sixteen-query pass and the wide re-scoring kernel)
-    if (f16 && dim != 128 && dim != 256 && dim != 384 && dim != 512 && dim != 768 && dim != 1024 && !(dim > 1024 && hi_dim_ok(dim)))
+    if (f16 && !stream16_dim_ok(dim))
         return fail(RL_ERR_UNSUPPORTED, "rl_index_create_f16: dim must be one of 128, 256, 384, 512, 768, 1024, or a multiple of 128 up to 4096");
     if (f16 && mem == RL_MEM_DEVICE && (reinterpret_cast<uintptr_t>(embeddings) & 15))
         return fail(RL_ERR_INVALID, "rl_index_create_f16: device embeddings must be 16-byte aligned");
@@ -873,7 +823,7 @@ static int index_create_any(rl_index** out, const void* embeddings, bool f16, in
         chunk_offsets = host_offsets.data();
     }
     hipStream_t s = as_stream(stream);
-    rl_index* idx = new rl_index();
+    std::unique_ptr<rl_index> idx(new rl_index());
     {   // route options: the process-wide defaults as they are now
         std::lock_guard<std::mutex> lock(g_default_opts_mu);
         idx->opt = g_default_opts;
@@ -887,41 +837,34 @@ static int index_create_any(rl_index** out, const void* embeddings, bool f16, in
     idx->h_offsets.assign(chunk_offsets, chunk_offsets + n_chunks + 1);
     idx->cap_rows = n_rows;
     idx->cap_chunks = n_chunks;
-    auto bail = [&](int code) { rl_index_destroy(idx); return code; };
-#define RL_IDX(expr) do { int _s = (expr); if (_s != RL_OK) return bail(_s); } while (0)
-#define RL_IDX_HIP(expr) do { hipError_t _e = (expr); if (_e != hipSuccess) return bail(fail(_e == hipErrorOutOfMemory ? RL_ERR_NOMEM : RL_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(_e))); } while (0)
+    // (an early error return destroys the index and with it whatever it holds so far)
+    const char* who = "rl_index_create";
     int dev = 0;
-    RL_IDX_HIP(hipGetDevice(&dev));
+    RL_HIP(hipGetDevice(&dev));
     hipDeviceProp_t prop;
-    RL_IDX_HIP(hipGetDeviceProperties(&prop, dev));
+    RL_HIP(hipGetDeviceProperties(&prop, dev));
     idx->n_cu = prop.multiProcessorCount;
     const size_t elt = f16 ? sizeof(uint16_t) : sizeof(float);
     const void* dev_rows = embeddings;
     if (mem == RL_MEM_HOST) {
-        void* d = nullptr;
-        RL_IDX_HIP(hipMalloc(&d, std::max<size_t>((size_t)n_rows * dim * elt, 16)));
-        idx->owns_E = true;
-        dev_rows = d;
-        (f16 ? (const void*&)idx->E16 : (const void*&)idx->E) = d;  // owned from here on (bail() frees it)
-        if (n_rows) RL_IDX_HIP(hipMemcpyAsync(d, embeddings, (size_t)n_rows * dim * elt, hipMemcpyHostToDevice, s));
+        RL_TRY(idx->owned_rows.alloc(std::max<size_t>((size_t)n_rows * dim * elt, 16), who));
+        dev_rows = idx->owned_rows.p;
+        if (n_rows) RL_HIP(hipMemcpyAsync(idx->owned_rows.p, embeddings, (size_t)n_rows * dim * elt, hipMemcpyHostToDevice, s));
     }
     if (f16) idx->E16 = static_cast<const uint16_t*>(dev_rows); else idx->E = static_cast<const float*>(dev_rows);
-    RL_IDX_HIP(hipMalloc(&idx->offsets, (size_t)(n_chunks + 1) * sizeof(int64_t)));
-    RL_IDX_HIP(hipMemcpyAsync(idx->offsets, chunk_offsets, (size_t)(n_chunks + 1) * sizeof(int64_t), hipMemcpyHostToDevice, s));
-    RL_IDX_HIP(hipMalloc(&idx->row_to_chunk, (size_t)(n_rows + 65) * sizeof(int32_t)));  // +1 terminator, +64 pad
-    RL_IDX(launch_row_to_chunk(idx->offsets, n_chunks, n_rows, idx->row_to_chunk, s));
-    if (metric == RL_COSINE) RL_IDX_HIP(hipMalloc(&idx->norm, (size_t)n_rows * sizeof(float) + 64));  // (+ 64 B: a 16-row block's norms are readable with one scalar load)
-    if (metric == RL_L2) RL_IDX_HIP(hipMalloc(&idx->sumsq, std::max<size_t>((size_t)n_rows * sizeof(float), 16)));
+    RL_TRY(idx->offsets.alloc((size_t)(n_chunks + 1) * sizeof(int64_t), who));
+    RL_HIP(hipMemcpyAsync(idx->offsets, chunk_offsets, (size_t)(n_chunks + 1) * sizeof(int64_t), hipMemcpyHostToDevice, s));
+    RL_TRY(idx->row_to_chunk.alloc((size_t)(n_rows + 65) * sizeof(int32_t), who));  // +1 terminator, +64 pad
+    RL_TRY(launch_row_to_chunk(idx->offsets, n_chunks, n_rows, idx->row_to_chunk, s));
+    if (metric == RL_COSINE) RL_TRY(idx->norm.alloc((size_t)n_rows * sizeof(float) + 64, who));  // (+ 64 B: a 16-row block's norms are readable with one scalar load)
+    if (metric == RL_L2) RL_TRY(idx->sumsq.alloc(std::max<size_t>((size_t)n_rows * sizeof(float), 16), who));
     if (idx->norm || idx->sumsq)
-        RL_IDX(f16 ? launch_row_norms16(idx->E16, n_rows, dim, idx->norm, idx->sumsq, s)
+        RL_TRY(f16 ? launch_row_norms16(idx->E16, n_rows, dim, idx->norm, idx->sumsq, s)
                    : launch_row_norms(idx->E, n_rows, dim, idx->norm, idx->sumsq, s));
-    RL_IDX(scan_row_range(idx, 0, n_rows, s));
-    RL_IDX(refresh_planes(idx, s));
-    RL_IDX(refresh_hi_plane(idx, s));
-    RL_IDX_HIP(hipStreamSynchronize(s));  // host_offsets / caller buffers may go away after return
-#undef RL_IDX
-#undef RL_IDX_HIP
-    *out = idx;
+    RL_TRY(scan_row_range(idx.get(), 0, n_rows, s));
+    RL_TRY(refresh_images(idx.get(), s));
+    RL_HIP(hipStreamSynchronize(s));  // host_offsets / caller buffers may go away after return
+    *out = idx.release();
     return RL_OK;
 }
 
@@ -937,18 +880,22 @@ int rl_index_create_f16(rl_index** out, const uint16_t* embeddings_f16, int64_t 
 
 // ---- lifecycle: append / delete -------------------------------------------------
 namespace {
-// (Re)build the device live bitsets from idx->h_live.
+// (Re)build the device live bitsets from idx->h_live (none while it is empty: every chunk is live).  Both or neither exist.  The old
+// ones go first, so that a failure below leaves none rather than bitsets sized for fewer chunks and rows than the index has by then (an
+// append reaches this after it has grown the index): the kernels that read them would read past their end.
 int upload_live_bits(rl_index* idx, hipStream_t s) {
+    idx->live_chunk_bits = DevArray<uint32_t>();
+    idx->live_row_bits = DevArray<uint32_t>();
     if (idx->h_live.empty()) return RL_OK;
     const size_t cw = (size_t)(idx->n_chunks + 31) / 32, rw = (size_t)(idx->n_rows + 31) / 32;
-    if (idx->live_chunk_bits) (void)hipFree(idx->live_chunk_bits);
-    if (idx->live_row_bits) (void)hipFree(idx->live_row_bits);
-    idx->live_chunk_bits = idx->live_row_bits = nullptr;
-    RL_HIP(hipMalloc(&idx->live_chunk_bits, std::max<size_t>(cw * 4, 16)));
-    RL_HIP(hipMalloc(&idx->live_row_bits, std::max<size_t>(rw * 4, 16)));
-    RL_HIP(hipMemcpyAsync(idx->live_chunk_bits, idx->h_live.data(), cw * 4, hipMemcpyHostToDevice, s));
-    RL_TRY(launch_expand_chunk_bits(idx->live_chunk_bits, idx->row_to_chunk, idx->n_rows, nullptr, idx->live_row_bits, s));
+    DevArray<uint32_t> chunk_bits, row_bits;
+    RL_TRY(chunk_bits.reserve(std::max<size_t>(cw * 4, 16)));
+    RL_TRY(row_bits.reserve(std::max<size_t>(rw * 4, 16)));
+    RL_HIP(hipMemcpyAsync(chunk_bits, idx->h_live.data(), cw * 4, hipMemcpyHostToDevice, s));
+    RL_TRY(launch_expand_chunk_bits(chunk_bits, idx->row_to_chunk, idx->n_rows, nullptr, row_bits, s));
     RL_HIP(hipStreamSynchronize(s));
+    idx->live_chunk_bits = std::move(chunk_bits);
+    idx->live_row_bits = std::move(row_bits);
     return RL_OK;
 }
 }  // namespace
@@ -1039,69 +986,50 @@ int rl_index_compact(rl_index* idx, int64_t* out_remap, int64_t* new_n_rows, int
     const bool f16 = idx->E16 != nullptr;
     const size_t row_bytes = (size_t)idx->dim * (f16 ? sizeof(uint16_t) : sizeof(float));
     if (row_bytes % 4) return fail(RL_ERR_UNSUPPORTED, "rl_index_compact: an odd dim of fp16 rows is not supported");
-    // ---- all-or-nothing: every new buffer exists before the index is touched ------------------------------------------------
-    void *e = nullptr, *map = nullptr;
-    float *nn = nullptr, *ns = nullptr;
-    int32_t* r2c = nullptr;
-    int64_t* o = nullptr;
-    auto undo = [&](int code) {
-        for (void* p : {e, map, (void*)nn, (void*)ns, (void*)r2c, (void*)o}) if (p) (void)hipFree(p);
-        return code;
-    };
-#define RL_CMP(expr) do { hipError_t _e = (expr); if (_e != hipSuccess) return undo(fail(_e == hipErrorOutOfMemory ? RL_ERR_NOMEM : RL_ERR_HIP, std::string("rl_index_compact: ") + hipGetErrorString(_e))); } while (0)
-    RL_CMP(hipMalloc(&e, std::max<size_t>((size_t)new_n * row_bytes, 16)));
-    RL_CMP(hipMalloc(&map, std::max<size_t>((size_t)new_n * sizeof(int64_t), 16)));
-    if (idx->norm) RL_CMP(hipMalloc(&nn, (size_t)new_n * sizeof(float) + 64));
-    if (idx->sumsq) RL_CMP(hipMalloc(&ns, std::max<size_t>((size_t)new_n * sizeof(float), 16)));
-    RL_CMP(hipMalloc(&r2c, (size_t)(new_n + 65) * sizeof(int32_t)));
-    RL_CMP(hipMalloc(&o, (size_t)(new_c + 1) * sizeof(int64_t)));
-    if (new_n) RL_CMP(hipMemcpyAsync(map, old_row.data(), (size_t)new_n * sizeof(int64_t), hipMemcpyHostToDevice, s));
-    RL_CMP(hipMemcpyAsync(o, new_off.data(), (size_t)(new_c + 1) * sizeof(int64_t), hipMemcpyHostToDevice, s));
-    {
-        const void* src = f16 ? (const void*)idx->E16 : (const void*)idx->E;
-        const int st = launch_compact_rows(src, (int64_t)row_bytes, static_cast<const int64_t*>(map), new_n, e, s);
-        if (st != RL_OK) return undo(st);
-        if (nn) { const int st2 = launch_compact_rows(idx->norm, 4, static_cast<const int64_t*>(map), new_n, nn, s); if (st2 != RL_OK) return undo(st2); }
-        if (ns) { const int st2 = launch_compact_rows(idx->sumsq, 4, static_cast<const int64_t*>(map), new_n, ns, s); if (st2 != RL_OK) return undo(st2); }
-    }
-    RL_CMP(hipStreamSynchronize(s));
-#undef RL_CMP
+    // ---- all-or-nothing: every new buffer exists before the index is touched (an early return frees them) --------------------
+    const char* who = "rl_index_compact";
+    Pool e, map;
+    DevArray<float> nn, ns;
+    DevArray<int32_t> r2c;
+    DevArray<int64_t> o;
+    RL_TRY(e.alloc(std::max<size_t>((size_t)new_n * row_bytes, 16), who));
+    RL_TRY(map.alloc(std::max<size_t>((size_t)new_n * sizeof(int64_t), 16), who));
+    if (idx->norm) RL_TRY(nn.alloc((size_t)new_n * sizeof(float) + 64, who));
+    if (idx->sumsq) RL_TRY(ns.alloc(std::max<size_t>((size_t)new_n * sizeof(float), 16), who));
+    RL_TRY(r2c.alloc((size_t)(new_n + 65) * sizeof(int32_t), who));
+    RL_TRY(o.alloc((size_t)(new_c + 1) * sizeof(int64_t), who));
+    if (new_n) RL_TRY(hip_status(hipMemcpyAsync(map.p, old_row.data(), (size_t)new_n * sizeof(int64_t), hipMemcpyHostToDevice, s), who));
+    RL_TRY(hip_status(hipMemcpyAsync(o, new_off.data(), (size_t)(new_c + 1) * sizeof(int64_t), hipMemcpyHostToDevice, s), who));
+    const void* src = f16 ? (const void*)idx->E16 : (const void*)idx->E;
+    RL_TRY(launch_compact_rows(src, (int64_t)row_bytes, map.as<int64_t>(), new_n, e.p, s));
+    if (nn) RL_TRY(launch_compact_rows(idx->norm, 4, map.as<int64_t>(), new_n, nn, s));
+    if (ns) RL_TRY(launch_compact_rows(idx->sumsq, 4, map.as<int64_t>(), new_n, ns, s));
+    RL_TRY(hip_status(hipStreamSynchronize(s), who));
     // ---- commit -----------------------------------------------------------------------------------------------------------------
-    if (idx->owns_E) (void)hipFree(const_cast<void*>(f16 ? (const void*)idx->E16 : (const void*)idx->E));
-    if (f16) idx->E16 = static_cast<const uint16_t*>(e); else idx->E = static_cast<const float*>(e);
-    idx->owns_E = true;
-    (void)hipFree(map);
-    if (idx->norm) { (void)hipFree(idx->norm); idx->norm = nn; }
-    if (idx->sumsq) { (void)hipFree(idx->sumsq); idx->sumsq = ns; }
-    (void)hipFree(idx->row_to_chunk);
-    idx->row_to_chunk = r2c;
-    (void)hipFree(idx->offsets);
-    idx->offsets = o;
+    idx->owned_rows = std::move(e);
+    if (f16) idx->E16 = idx->owned_rows.as<uint16_t>(); else idx->E = idx->owned_rows.as<float>();
+    map.release();  // (before the images are rebuilt: image_fits asks the device what is free)
+    idx->norm = std::move(nn);
+    idx->sumsq = std::move(ns);
+    idx->row_to_chunk = std::move(r2c);
+    idx->offsets = std::move(o);
     idx->n_rows = idx->cap_rows = new_n;
     idx->n_chunks = idx->cap_chunks = new_c;
     idx->h_offsets = std::move(new_off);
     idx->has_empty_chunk = has_empty;
     idx->h_live.clear();
-    if (idx->live_chunk_bits) { (void)hipFree(idx->live_chunk_bits); idx->live_chunk_bits = nullptr; }
-    if (idx->live_row_bits) { (void)hipFree(idx->live_row_bits); idx->live_row_bits = nullptr; }
+    RL_TRY(upload_live_bits(idx, s));  // (drops them: every chunk is live)
     idx->n_dead_chunks = idx->n_dead_rows = 0;
     RL_TRY(launch_row_to_chunk(idx->offsets, new_c, new_n, idx->row_to_chunk, s));
-    // the magnitude range may only have shrunk: recompute it over the survivors, then the corpus image from scratch
+    // the magnitude range may only have shrunk: recompute it over the survivors, then the images from their first row
     idx->max_abs = 0.f;
     idx->min_row_max = std::numeric_limits<float>::infinity();
     idx->nonfinite = false;
-    idx->planes_rows = 0;
-    idx->planes_scale = 0.f;
-    idx->hi_rows = 0;
-    idx->hi_scale = 0.f;
-    idx->hi_image_rows = 0;
-    idx->hi_image_scale = 0.f;
-    idx->max_row_norm = idx->max_lo_norm = idx->max_lo_ratio = 0.f;
-    idx->min_row_norm = std::numeric_limits<float>::infinity();
-    idx->max_row_norm_rows = 0;
+    idx->planes.scale = idx->hi_image.scale = idx->hiplane.scale = 0.f;  // (their blocks are kept: already paid for)
+    idx->planes.rows = idx->hi_image.rows = idx->hiplane.rows = 0;
+    idx->norm_stats.reset();
     RL_TRY(scan_row_range(idx, 0, new_n, s));
-    RL_TRY(refresh_planes(idx, s));
-    RL_TRY(refresh_hi_plane(idx, s));
+    RL_TRY(refresh_images(idx, s));
     RL_HIP(hipStreamSynchronize(s));
     if (out_remap) std::memcpy(out_remap, remap.data(), (size_t)old_c * sizeof(int64_t));
     if (new_n_rows) *new_n_rows = new_n;
@@ -1117,8 +1045,7 @@ int rl_index_set_arithmetic(rl_index* idx, int mode) {
     idx->arithmetic = mode;
     idx->opt.v[RL_OPT_ARITHMETIC] = mode;
     update_split_scale(idx);
-    RL_TRY(refresh_planes(idx, nullptr));
-    RL_TRY(refresh_hi_plane(idx, nullptr));
+    RL_TRY(refresh_images(idx, nullptr));
     RL_HIP(hipStreamSynchronize(nullptr));
     return RL_OK;
 }
@@ -1151,8 +1078,7 @@ int rl_index_set_option(rl_index* idx, int key, int64_t value) {
             idx->arithmetic = (int)value;
             update_split_scale(idx);
         }
-        RL_TRY(refresh_planes(idx, nullptr));
-        RL_TRY(refresh_hi_plane(idx, nullptr));
+        RL_TRY(refresh_images(idx, nullptr));
         RL_HIP(hipStreamSynchronize(nullptr));
     }
     return RL_OK;
@@ -1198,48 +1124,40 @@ int rl_index_append(rl_index* idx, const float* rows, int64_t n_new_rows, const 
     const void* old_rows = f16 ? (const void*)idx->E16 : (const void*)idx->E;
     // ---- storage: own it, grow geometrically.  All-or-nothing: every new buffer is allocated (and filled) before the
     // index is touched, so a failed allocation leaves the index exactly as it was. -----------------------------------
-    if (!idx->owns_E || new_n > idx->cap_rows || new_c > idx->cap_chunks) {
-        const bool grow_rows = !idx->owns_E || new_n > idx->cap_rows;
+    if (!idx->owns_E() || new_n > idx->cap_rows || new_c > idx->cap_chunks) {
+        const bool grow_rows = !idx->owns_E() || new_n > idx->cap_rows;
         const bool grow_chunks = new_c > idx->cap_chunks;
         const int64_t cap = grow_rows ? std::max<int64_t>(new_n, idx->cap_rows + idx->cap_rows / 2) : idx->cap_rows;
         const int64_t ccap = grow_chunks ? std::max<int64_t>(new_c, idx->cap_chunks + idx->cap_chunks / 2) : idx->cap_chunks;
-        void* e = nullptr;
-        float *nn = nullptr, *ns = nullptr;
-        int32_t* r2c = nullptr;
-        int64_t* o = nullptr;
-        auto undo = [&](int code) {
-            for (void* p : {e, (void*)nn, (void*)ns, (void*)r2c, (void*)o}) if (p) (void)hipFree(p);
-            return code;
-        };
-#define RL_GROW(expr) do { hipError_t _e = (expr); if (_e != hipSuccess) return undo(fail(_e == hipErrorOutOfMemory ? RL_ERR_NOMEM : RL_ERR_HIP, std::string("rl_index_append: ") + hipGetErrorString(_e))); } while (0)
+        const char* who = "rl_index_append";
+        Pool e;
+        DevArray<float> nn, ns;
+        DevArray<int32_t> r2c;
+        DevArray<int64_t> o;
         if (grow_rows) {
-            RL_GROW(hipMalloc(&e, std::max<size_t>((size_t)cap * row_bytes, 16)));
-            if (idx->norm) RL_GROW(hipMalloc(&nn, (size_t)cap * sizeof(float) + 64));
-            if (idx->sumsq) RL_GROW(hipMalloc(&ns, std::max<size_t>((size_t)cap * sizeof(float), 16)));
-            RL_GROW(hipMalloc(&r2c, (size_t)(cap + 65) * sizeof(int32_t)));
+            RL_TRY(e.alloc(std::max<size_t>((size_t)cap * row_bytes, 16), who));
+            if (idx->norm) RL_TRY(nn.alloc((size_t)cap * sizeof(float) + 64, who));
+            if (idx->sumsq) RL_TRY(ns.alloc(std::max<size_t>((size_t)cap * sizeof(float), 16), who));
+            RL_TRY(r2c.alloc((size_t)(cap + 65) * sizeof(int32_t), who));
         }
-        if (grow_chunks) RL_GROW(hipMalloc(&o, (size_t)(ccap + 1) * sizeof(int64_t)));
+        if (grow_chunks) RL_TRY(o.alloc((size_t)(ccap + 1) * sizeof(int64_t), who));
         if (grow_rows && old_n) {
-            RL_GROW(hipMemcpyAsync(e, old_rows, (size_t)old_n * row_bytes, hipMemcpyDeviceToDevice, s));
-            if (nn) RL_GROW(hipMemcpyAsync(nn, idx->norm, (size_t)old_n * sizeof(float), hipMemcpyDeviceToDevice, s));
-            if (ns) RL_GROW(hipMemcpyAsync(ns, idx->sumsq, (size_t)old_n * sizeof(float), hipMemcpyDeviceToDevice, s));
+            RL_TRY(hip_status(hipMemcpyAsync(e.p, old_rows, (size_t)old_n * row_bytes, hipMemcpyDeviceToDevice, s), who));
+            if (nn) RL_TRY(hip_status(hipMemcpyAsync(nn, idx->norm, (size_t)old_n * sizeof(float), hipMemcpyDeviceToDevice, s), who));
+            if (ns) RL_TRY(hip_status(hipMemcpyAsync(ns, idx->sumsq, (size_t)old_n * sizeof(float), hipMemcpyDeviceToDevice, s), who));
         }
-        RL_GROW(hipStreamSynchronize(s));
-#undef RL_GROW
+        RL_TRY(hip_status(hipStreamSynchronize(s), who));
         // commit
         if (grow_rows) {
-            if (idx->owns_E && old_rows) (void)hipFree(const_cast<void*>(old_rows));
-            if (idx->norm) { (void)hipFree(idx->norm); idx->norm = nn; }
-            if (idx->sumsq) { (void)hipFree(idx->sumsq); idx->sumsq = ns; }
-            (void)hipFree(idx->row_to_chunk);
-            if (f16) idx->E16 = static_cast<const uint16_t*>(e); else idx->E = static_cast<const float*>(e);
-            idx->owns_E = true;
-            idx->row_to_chunk = r2c;
+            idx->owned_rows = std::move(e);
+            if (f16) idx->E16 = idx->owned_rows.as<uint16_t>(); else idx->E = idx->owned_rows.as<float>();
+            idx->norm = std::move(nn);
+            idx->sumsq = std::move(ns);
+            idx->row_to_chunk = std::move(r2c);
             idx->cap_rows = cap;
         }
         if (grow_chunks) {
-            (void)hipFree(idx->offsets);
-            idx->offsets = o;
+            idx->offsets = std::move(o);
             idx->cap_chunks = ccap;
         }
     }
@@ -1271,8 +1189,7 @@ int rl_index_append(rl_index* idx, const float* rows, int64_t n_new_rows, const 
                    : launch_row_norms(idx->E + (size_t)old_n * idx->dim, n_new_rows, idx->dim, nn, ns, s));
     }
     RL_TRY(scan_row_range(idx, old_n, n_new_rows, s));
-    RL_TRY(refresh_planes(idx, s));
-    RL_TRY(refresh_hi_plane(idx, s));
+    RL_TRY(refresh_images(idx, s));
     if (!idx->h_live.empty()) {  // new chunks are live
         const size_t cw = (size_t)(new_c + 31) / 32;
         idx->h_live.resize(cw, 0u);
@@ -1299,16 +1216,17 @@ int rl_index_prepare(rl_index* idx, uint32_t images, uint32_t* built, void* stre
     RL_TRY(use_scratch(idx, s));
     idx->no_room_retry_epoch = 0;  // (an explicit request always tries)
     RL_TRY(demand_images(idx, images, s));
-    if (built) *built = (image_valid(idx) ? IMG_PLANES : 0u) | (hi_image_valid(idx) ? IMG_HI_IMAGE : 0u) | (hi_valid(idx) ? IMG_HI_PLANE : 0u);
+    if (built) *built = images_built(idx);
     return RL_OK;
 }
 
 int rl_index_memory(const rl_index* idx, int64_t out[8]) {
     if (!idx || !out) return fail(RL_ERR_INVALID, "rl_index_memory: null argument");
     out[0] = (int64_t)idx->n_rows * idx->dim * (idx->E16 ? 2 : 4);
-    out[1] = image_valid(idx) ? (int64_t)idx->planes.cap : 0;
-    out[2] = hi_image_valid(idx) ? (int64_t)idx->hi_image.cap : 0;
-    out[3] = hi_valid(idx) ? (int64_t)idx->hiplane.cap : 0;
+    const uint32_t built = images_built(idx);
+    out[1] = built & IMG_PLANES ? (int64_t)idx->planes.buf.cap : 0;
+    out[2] = built & IMG_HI_IMAGE ? (int64_t)idx->hi_image.buf.cap : 0;
+    out[3] = built & IMG_HI_PLANE ? (int64_t)idx->hiplane.buf.cap : 0;
     out[4] = (int64_t)(idx->scores.cap + idx->hits.cap + idx->misc.cap + idx->maskbuf.cap + idx->qsplit.cap + idx->qplanes.cap + idx->q32.cap + idx->cand.cap +
                        idx->fused.cap + idx->pp_work.cap + idx->rankbuf.cap + idx->hibuf.cap + idx->ends.cap);
     size_t free_b = 0, total_b = 0;
@@ -1341,7 +1259,7 @@ int score_rows(rl_index* idx, const float* d_q, int32_t nb, int64_t ld, hipStrea
         // its one-plane image): no conversion in the loop
         if (idx->opt.on(RL_OPT_PLANES_GEMM)) {
             RL_TRY(idx->misc.reserve(score_planes_scratch_floats(nb, idx->dim) * sizeof(float)));
-            const int st = launch_score_planes(idx->planes.p, idx->n_rows, idx->dim, d_q, nb, sc, ld, idx->norm, idx->sumsq,
+            const int st = launch_score_planes(idx->planes.buf.p, idx->n_rows, idx->dim, d_q, nb, sc, ld, idx->norm, idx->sumsq,
                                                idx->misc.as<float>(), mode, idx->n_cu, s, image_scale(idx), idx->E16 != nullptr);
             if (st != RL_ERR_UNSUPPORTED) return st;
         }
@@ -1446,19 +1364,19 @@ int search_rows_fused(rl_index* idx, const float* d_q, int32_t B, int32_t k, flo
     // ---- (1) sample pass + its exact top-k --------------------------------------------------------------------------------------
     RL_TRY(launch_score_planes_queries(d_q, B, idx->dim, qs, mode, s));
     // (rows past the corpus in the last sampled tile: the pass writes them as -inf itself)
-    RL_TRY(launch_score_planes_pass(idx->planes.p, n, idx->dim, B, qs, S_s, ld_s, idx->norm, idx->sumsq, mode, stride, nullptr, nullptr,
+    RL_TRY(launch_score_planes_pass(idx->planes.buf.p, n, idx->dim, B, qs, S_s, ld_s, idx->norm, idx->sumsq, mode, stride, nullptr, nullptr,
                                     idx->n_cu, s, img_scale, half));
     RL_TRY(launch_topk(S_s, B, ld_s, ld_s, k, idx->ws, top_s, top_i, s));
     // ---- (2) full pass keeping what reaches the bound ---------------------------------------------------------------------------
     RL_HIP(hipMemsetAsync(cnt, 0, ((size_t)B + 1) * sizeof(uint32_t), s));  // list lengths + the overflow flag; the lists need no fill
     const CandArgs ca{top_s + (k - 1), k, c_s, c_i, cnt, flag, cap};
     idx->filt = {RL_FILTER_ROWS_FUSED, B, cap, cnt, flag};
-    RL_TRY(launch_score_planes_pass(idx->planes.p, n, idx->dim, B, qs, nullptr, 0, idx->norm, idx->sumsq, mode, 1, nullptr, &ca, idx->n_cu, s,
+    RL_TRY(launch_score_planes_pass(idx->planes.buf.p, n, idx->dim, B, qs, nullptr, 0, idx->norm, idx->sumsq, mode, 1, nullptr, &ca, idx->n_cu, s,
                                     img_scale, half));
     // ---- (3) exact ranking of every list ------------------------------------------------------------------------------------------
     RL_TRY(launch_merge_topk(c_s, c_i, 1, B, cap, k, d_scores, d_rows, s, cnt));
     // ---- (4) guarded dense fallback -----------------------------------------------------------------------------------------------
-    RL_TRY(launch_score_planes_pass(idx->planes.p, n, idx->dim, B, qs, sc, ld, idx->norm, idx->sumsq, mode, 1, flag, nullptr, idx->n_cu, s,
+    RL_TRY(launch_score_planes_pass(idx->planes.buf.p, n, idx->dim, B, qs, sc, ld, idx->norm, idx->sumsq, mode, 1, flag, nullptr, idx->n_cu, s,
                                     img_scale, half));
     RL_TRY(launch_guarded_select(sc, B, n, ld, k, nullptr, nullptr, nullptr, 0, SCAN_RAW_DOT, 1.0f, d_scores, d_rows, flag, s));
     return RL_OK;
@@ -1516,7 +1434,7 @@ int search_rows_fused_hi(rl_index* idx, const float* d_q, int32_t B, int32_t k, 
     const float* q_unscale = qs + (size_t)groups * 32 * idx->dim;  // (the layout of launch_score_planes_queries)
     const float* q_sumsq = q_unscale + B + groups;
     float* sc = idx->scores.as<float>();  // [B x ld], reserved by the caller: only the fallback touches it
-    const void* hi = idx->hi_image.p;
+    const void* hi = idx->hi_image.buf.p;
     const float sscale = idx->split_scale;
     // ---- (1) sample pass + its exact top-k ------------------------------------------------------------------------------------
     RL_TRY(launch_score_planes_queries(d_q, B, idx->dim, qs, mode, s, flag));  // (also zeroes the flag)
@@ -1531,8 +1449,9 @@ int search_rows_fused_hi(rl_index* idx, const float* d_q, int32_t B, int32_t k, 
     RL_TRY(st_sample);
     RL_TRY(launch_topk(S_s, B, ld_s, ld_s, k, idx->ws, top_s, top_i, s));
     // ---- (2) thresholds lowered by the error band; candidate pass ---------------------------------------------------------------
-    RL_TRY(launch_row_threshold(top_s, B, k, d_q, idx->dim, mode, hi_only ? q_unscale : nullptr, idx->max_lo_ratio, idx->max_lo_norm, idx->max_row_norm,
-                                thr, window, cnt, cnt2, flag, s, thr1, sum_eps(idx->dim)));  // (thr1: the first round's thresholds, kept for rl_time_kernel's replay)
+    RL_TRY(launch_row_threshold(top_s, B, k, d_q, idx->dim, mode, hi_only ? q_unscale : nullptr, idx->norm_stats.max_lo_ratio, idx->norm_stats.max_lo_norm,
+                                idx->norm_stats.max_row_norm, thr, window, cnt, cnt2, flag, s, thr1, sum_eps(idx->dim)));
+    // (thr1: the first round's thresholds, kept for rl_time_kernel's replay)
     const CandArgs ca{thr, 1, c_s, c_i, cnt, flag, cap};
     idx->filt = {RL_FILTER_ROWS_FUSED_HI, B, cap, cnt, flag};
     // The candidate pass on the sixteen-group tile of maxsim_pp.hip (round 4: 128 rows x 512 queries per workgroup, every operand through
@@ -1552,7 +1471,7 @@ int search_rows_fused_hi(rl_index* idx, const float* d_q, int32_t B, int32_t k, 
         const int64_t Tr = (n + 127) / 128;
         // cosines over rows whose norms span more than a factor of four: the candidate pass tests its hits row by row (maxsim_pp.hip: the
         // ROW-NORM variant) -- the block-wide bound would pass most of a block that holds a short row next to long ones
-        row_test = mode == SCAN_COSINE && !(idx->min_row_norm * 4.0f >= idx->max_row_norm);
+        row_test = mode == SCAN_COSINE && !(idx->norm_stats.min_row_norm * 4.0f >= idx->norm_stats.max_row_norm);
         round1_tiles = (Tr >= 64 && idx->opt.on(RL_OPT_FUSED_TWO_ROUNDS)) ? (3 * Tr) / 16 : 0;  // (small corpora: one round)
         if (round1_tiles > 0) {
             st_pp = launch_pp_rows_pass(hi, n, idx->dim, B, qs, idx->norm, mode, &ca, idx->pp_work.p, log_cap, idx->n_cu, s, sscale, 0, round1_tiles, false,
@@ -1588,7 +1507,7 @@ int search_rows_fused_hi(rl_index* idx, const float* d_q, int32_t B, int32_t k, 
     RL_TRY(launch_row_dots(idx->E, idx->dim, d_q, B, r_i, cnt2, cap2, mode, idx->norm, q_sumsq, r_s, s));
     RL_TRY(launch_merge_topk(r_s, r_i, 1, B, cap2, k, d_scores, d_rows, s, cnt2));
     // ---- (5) guarded dense fallback (full precision, over the pre-split image) ------------------------------------------------------
-    RL_TRY(launch_score_planes_pass(idx->planes.p, n, idx->dim, B, qs, sc, ld, idx->norm, idx->sumsq, mode, 1, flag, nullptr, idx->n_cu, s,
+    RL_TRY(launch_score_planes_pass(idx->planes.buf.p, n, idx->dim, B, qs, sc, ld, idx->norm, idx->sumsq, mode, 1, flag, nullptr, idx->n_cu, s,
                                     image_scale(idx), false));
     // (its selection in ONE guarded launch, a block per query: the three launches of the selection, each a grid of 64 x B workgroups that return
     // at once behind the flag, were 36 us of every 1000-query batch)
@@ -1658,33 +1577,33 @@ int search_rows_hi(rl_index* idx, const float* d_q, int32_t nb, int32_t k, float
     uint64_t* bmax = reinterpret_cast<uint64_t*>((reinterpret_cast<uintptr_t>(es + nc) + 7) & ~uintptr_t(7));  // [nb x 2048] group maxima (pivot route)
     float* sc = idx->scores.as<float>();
     // ---- (1) approximate pass over the HI plane ---------------------------------------------------------------------------------------------
-    int st = wide ? launch_scan_rows16(idx->hiplane.as<uint16_t>(), n, dim, d_q, nb, nullptr, SCAN_RAW_DOT, sc, ld, s)
-                  : launch_maxsim_stream16(idx->hiplane.as<uint16_t>(), n, dim, d_q, nb, idx->row_to_chunk, idx->offsets, idx->n_chunks, 1, sc, ld,
+    int st = wide ? launch_scan_rows16(idx->hiplane.buf.as<uint16_t>(), n, dim, d_q, nb, nullptr, SCAN_RAW_DOT, sc, ld, s)
+                  : launch_maxsim_stream16(idx->hiplane.buf.as<uint16_t>(), n, dim, d_q, nb, idx->row_to_chunk, idx->offsets, idx->n_chunks, 1, sc, ld,
                                            idx->n_cu, s);
     if (st != RL_OK) return st;
     // ---- (2) its exact top-k, and every row that could be in the exact top-k of the full-precision scores ----------------------------------
     // The bound: what the HI halves drop is known exactly per row -- max |e_lo| / |e| (cosine) and max |e_lo| (dot) are kept by the
-    // index (refresh_hi_image) -- plus 2^-12 |e| |q| for the query's own 2^-22 split and twice the worst case of a 1024-term fp32
+    // index (refresh_hi_norms) -- plus 2^-12 |e| |q| for the query's own 2^-22 split and twice the worst case of a 1024-term fp32
     // sum (6e-5).  Without those maxima (no HI image on this index): the a-priori 2^-10 of the truncation, plus 2^-11.
-    const bool measured = idx->max_row_norm_rows == idx->n_rows && idx->max_row_norm_scale == idx->hi_scale && idx->max_row_norm > 0.f;
+    const bool measured = idx->norm_stats.measured(idx->n_rows) && idx->norm_stats.max_row_norm_scale == idx->hiplane.scale;
     bool gathered = false;
     float m_rel = 0x1p-10f + 0x1p-11f, e_bound = std::sqrt((float)dim) * idx->max_abs;
     if (measured) {
-        if (mode == SCAN_COSINE) m_rel = idx->max_lo_ratio + sum_eps(dim);
-        else { m_rel = 1.0f; e_bound = idx->max_lo_norm + sum_eps(idx->dim) * idx->max_row_norm; }
+        if (mode == SCAN_COSINE) m_rel = idx->norm_stats.max_lo_ratio + sum_eps(dim);
+        else { m_rel = 1.0f; e_bound = idx->norm_stats.max_lo_norm + sum_eps(idx->dim) * idx->norm_stats.max_row_norm; }
     }
     if (l2) {
         if (!measured) return RL_ERR_UNSUPPORTED;
         m_rel = sum_eps(dim);  // (l2_delta's arguments: the rounding term, the dot's bound per |q|, max |e|)
     }
     if (d_row_bits) {  // tombstones / metadata filter: masked rows rank -inf, so they reach neither the top-k nor the candidates
-        RL_TRY(launch_transform(sc, nb, n, ld, idx->norm, idx->sumsq, d_q, dim, mode, s, 1.0f / idx->hi_scale));
+        RL_TRY(launch_transform(sc, nb, n, ld, idx->norm, idx->sumsq, d_q, dim, mode, s, 1.0f / idx->hiplane.scale));
         RL_TRY(launch_mask_scores(sc, nb, n, ld, d_row_bits, s));
         int st_sel = RL_ERR_UNSUPPORTED;
         if (l2) st_sel = launch_topk_pivot(sc, nb, n, ld, k, idx->ws, ts, ti, s);  // (crowded scores: see above)
         if (st_sel != RL_OK && st_sel != RL_ERR_UNSUPPORTED) return st_sel;
         if (st_sel == RL_ERR_UNSUPPORTED) RL_TRY(launch_topk(sc, nb, n, ld, k, idx->ws, ts, ti, s));
-        RL_TRY(launch_approx_threshold(ts, nb, k, d_q, dim, mode, m_rel, e_bound, thr, cnt, flag, s, idx->max_row_norm));
+        RL_TRY(launch_approx_threshold(ts, nb, k, d_q, dim, mode, m_rel, e_bound, thr, cnt, flag, s, idx->norm_stats.max_row_norm));
         RL_TRY(launch_collect_above(sc, nb, n, ld, thr, mode == SCAN_COSINE ? idx->norm : nullptr, cap, ci, gn, cnt, flag, s));
     } else {
         // Round 4 (cfg 2: thirteen launches of 4.6 - 9.9 us behind a 0.31 ms pass; now eight): the transform + histogram launch also zeroes
@@ -1692,17 +1611,17 @@ int search_rows_hi(rl_index* idx, const float* d_q, int32_t nb, int32_t k, float
         // than 2 m below the threshold bin, and its final kernel -- which knows the k-th best -- lists every row within 2 m of it: no
         // threshold kernel, no collecting pass over the scores.
         HiBound bound;
-        bound.m_out = mb; bound.m_rel = m_rel; bound.e_norm_bound = e_bound; bound.e_max = idx->max_row_norm;
+        bound.m_out = mb; bound.m_rel = m_rel; bound.e_norm_bound = e_bound; bound.e_max = idx->norm_stats.max_row_norm;
         // Round 6 (option hi_pivot): no approximate RANKING at all -- the candidates are re-scored and ranked exactly anyway, so any lower bound
         // of the k-th best approximate similarity will do for the threshold: the k-th largest of ~500 workgroup maxima (hi_filter.hip:
         // transform_bmax_kernel / pivot_collect_kernel), two launches instead of the selection's three (k <= 512, >= 3 k maxima)
         int st_pv = RL_ERR_UNSUPPORTED;
         if (idx->opt.on(RL_OPT_HI_PIVOT))
-            st_pv = launch_pivot_route(sc, nb, n, ld, k, idx->norm, idx->sumsq, d_q, dim, mode, 1.0f / idx->hi_scale, bmax, cnt, 32, bound, thr, cap, ci, gn,
+            st_pv = launch_pivot_route(sc, nb, n, ld, k, idx->norm, idx->sumsq, d_q, dim, mode, 1.0f / idx->hiplane.scale, bmax, cnt, 32, bound, thr, cap, ci, gn,
                                        cnt, flag, s, idx->E, G, &gathered);
         if (st_pv != RL_OK && st_pv != RL_ERR_UNSUPPORTED) return st_pv;
         if (st_pv == RL_ERR_UNSUPPORTED) {
-            RL_TRY(launch_transform_hist(sc, nb, n, ld, idx->norm, idx->sumsq, d_q, dim, mode, idx->ws, s, 1.0f / idx->hi_scale, nullptr, cnt, 32, &bound));
+            RL_TRY(launch_transform_hist(sc, nb, n, ld, idx->norm, idx->sumsq, d_q, dim, mode, idx->ws, s, 1.0f / idx->hiplane.scale, nullptr, cnt, 32, &bound));
             HiEmit emit;
             emit.m = mb; emit.cap = cap; emit.ids = ci; emit.norms = gn; emit.row_norm = mode == SCAN_COSINE ? idx->norm : nullptr;
             emit.cnt = cnt; emit.flag = flag; emit.thr = thr; emit.l2 = l2 ? 1 : 0;
@@ -2085,14 +2004,14 @@ int gemm_prepare(rl_index* idx, const float* d_q, int32_t nq, int64_t q_stride, 
     // (options that route it through the eight-query kernel, shapes outside the slim batch, or the caller says so: k > 512, timing hooks)
     RL_TRY(demand_images(idx, approx_image_bit(idx), s));
     const bool hi_route = idx->opt.on(RL_OPT_HI_MAXSIM) && idx->opt.v[RL_OPT_HI_PRODUCTS] == 1 && idx->dim >= 256 && idx->opt.on(RL_OPT_PP_PASS);
-    const bool fell_back = idx->h_fell_back && *static_cast<volatile uint32_t*>(idx->h_fell_back) != 0u;  // (the previous batch's flag, if it has arrived)
+    const bool fell_back = idx->h_fell_back && *static_cast<volatile uint32_t*>(idx->h_fell_back.get()) != 0u;  // (the previous batch's flag, if it has arrived)
     if (want_planes || !hi_route || fell_back || (!image_valid(idx) && !slim_batch_ok(idx, d_q))) RL_TRY(demand_images(idx, IMG_PLANES, s));
     if (!(image_valid(idx) || slim_batch_ok(idx, d_q))) return RL_ERR_UNSUPPORTED;
     RL_TRY(idx->qplanes.reserve(query_planes_bytes(idx->dim, n_queries)));
     return launch_query_planes(d_q, idx->dim, nq, q_stride, n_queries, idx->qplanes.p, s, zero_words, zero_words ? 16 : 0);
 }
 int gemm_pass(rl_index* idx, int32_t nq, int32_t n_queries, int32_t first, int32_t n_q, float* d_out, int64_t out_stride, hipStream_t s) {
-    return launch_maxsim_gemm(idx->planes.p, idx->n_rows, idx->dim, idx->qplanes.p, n_queries, first, n_q, nq, idx->row_to_chunk,
+    return launch_maxsim_gemm(idx->planes.buf.p, idx->n_rows, idx->dim, idx->qplanes.p, n_queries, first, n_q, nq, idx->row_to_chunk,
                               idx->offsets, idx->ends.as<uint32_t>(), d_out, out_stride, idx->n_cu, s, image_scale(idx), idx->E16 != nullptr);
 }
 
@@ -2247,7 +2166,7 @@ int hi_batch_approx(rl_index* idx, const float* d_q, int32_t nq, int32_t n_queri
     const int32_t cap = hb.cap;
     // per pair |approx - exact| <= |q_i| |e_lo,j| (what the HI halves drop, measured: max_lo_norm) + 2^-12 |q_i| |e_j| (the
     // query's own 2^-22 split and twice the worst case of a 1024-term fp32 sum, 6e-5)
-    hb.m_abs = idx->max_lo_norm + sum_eps(idx->dim) * idx->max_row_norm;
+    hb.m_abs = idx->norm_stats.max_lo_norm + sum_eps(idx->dim) * idx->norm_stats.max_row_norm;
     hb.q_unscale = reinterpret_cast<const float*>(idx->qplanes.as<char>() + (size_t)n_queries * idx->dim * 128);  // launch_query_planes' meta
     hb.qsum = hb.q_unscale + 2 * (size_t)n_queries;                                                                 // ... and its sums
     if (!flag_zeroed) RL_HIP(hipMemsetAsync(hb.flag, 0, 16 * sizeof(uint32_t), s));  // (else: the query-image kernel did, gemm_prepare)
@@ -2297,7 +2216,7 @@ int hi_batch_rescore(rl_index* idx, const float* d_q, int32_t nq, int32_t n_quer
         RL_TRY(launch_maxsim_pairs(rows, idx->dim, d_q, nq, (int64_t)q_elems, idx->offsets, hb.ti, k, n_gemm, hb.es_top, s, rows16, 0, 0, packed));
         if (m_from_qsum)  // (also fills the lists' tails with -1)
             RL_TRY(launch_exact_threshold(hb.es_top, hb.ti, n_gemm, k, hb.m, hb.cap, hb.thr, hb.cnt, hb.ci, hb.es, hb.flag, s, hb.qsum, hb.m_abs,
-                                          idx->max_row_norm + idx->max_lo_norm, hb.one_product, hb.ts));
+                                          idx->norm_stats.max_row_norm + idx->norm_stats.max_lo_norm, hb.one_product, hb.ts));
         else
             RL_TRY(launch_exact_threshold(hb.es_top, hb.ti, n_gemm, k, hb.m, hb.cap, hb.thr, hb.cnt, hb.ci, hb.es, hb.flag, s, nullptr, 0.f, 0.f, false, hb.ts));
         RL_TRY(launch_collect_above(sc, n_gemm, idx->n_chunks, ld, hb.thr, nullptr, hb.cap, hb.ci, nullptr, hb.cnt, hb.flag, s, hb.ts, hb.ti, k));
@@ -2319,7 +2238,7 @@ int hi_batch_fallback(rl_index* idx, const float* d_q, int32_t nq, int32_t n_que
     // (no pre-split image: the streaming kernels over the rows, one launch with a grid row per query -- the same arithmetic, an order of
     // magnitude slower, and as rare)
     if (image_valid(idx) && !rows_only)
-        RL_TRY(launch_maxsim_gemm(idx->planes.p, idx->n_rows, idx->dim, idx->qplanes.p, n_queries, 0, n_gemm, nq, idx->row_to_chunk, idx->offsets,
+        RL_TRY(launch_maxsim_gemm(idx->planes.buf.p, idx->n_rows, idx->dim, idx->qplanes.p, n_queries, 0, n_gemm, nq, idx->row_to_chunk, idx->offsets,
                                   idx->ends.as<uint32_t>(), sc, ld, idx->n_cu, s, image_scale(idx), idx->E16 != nullptr, hb.flag, false, true));
     else if (idx->dim > 1024)  // (a wide index: no streaming kernel -- the exact re-scoring kernel over EVERY chunk, behind the flag)
         RL_TRY(launch_maxsim_pairs_all_wide(idx->E, idx->dim, d_q, nq, (int64_t)q_elems, idx->offsets, idx->n_chunks, n_gemm, sc, ld, s, hb.flag));
@@ -2334,19 +2253,21 @@ int hi_batch_fallback(rl_index* idx, const float* d_q, int32_t nq, int32_t n_que
     uint32_t* host_word = nullptr;
     if (idx->opt.on(RL_OPT_LAZY_IMAGES) && !image_valid(idx) && !rows_only) {  // (lazy images: let the next batch know whether this one fell back)
         if (!idx->h_fell_back) {  // (no pinned word: no signal -- the fallback then stays on the streaming kernels, results unchanged)
-            if (hipHostMalloc(reinterpret_cast<void**>(&idx->h_fell_back), sizeof(uint32_t), hipHostMallocMapped) == hipSuccess) {
+            void* word = nullptr;
+            if (hipHostMalloc(&word, sizeof(uint32_t), hipHostMallocMapped) == hipSuccess) {
+                idx->h_fell_back.reset(static_cast<uint32_t*>(word));
                 *idx->h_fell_back = 0u;
-                if (hipHostGetDevicePointer(reinterpret_cast<void**>(&idx->d_fell_back), idx->h_fell_back, 0) != hipSuccess) {
+                if (hipHostGetDevicePointer(reinterpret_cast<void**>(&idx->d_fell_back), word, 0) != hipSuccess) {
                     idx->d_fell_back = nullptr;
                     (void)hipGetLastError();
                 }
-            } else { idx->h_fell_back = nullptr; (void)hipGetLastError(); }
+            } else (void)hipGetLastError();
         }
         if (idx->h_fell_back) host_word = idx->d_fell_back;
         // (no device view of the pinned word: a 4-byte copy behind the selection, as before round 6)
         if (idx->h_fell_back && !host_word) {
             RL_TRY(launch_guarded_select(sc, n_gemm, idx->n_chunks, ld, k, nullptr, nullptr, nullptr, 0, SCAN_RAW_DOT, 1.0f, d_s, d_c, hb.flag, s));
-            RL_HIP(hipMemcpyAsync(idx->h_fell_back, hb.flag, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+            RL_HIP(hipMemcpyAsync(idx->h_fell_back.get(), hb.flag, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
             return RL_OK;
         }
     }
@@ -2371,7 +2292,7 @@ int maxsim_few_hi_plane(rl_index* idx, const float* d_q, int32_t nq, int32_t n, 
     if (idx->dim > 1024) return RL_ERR_UNSUPPORTED;  // (the stream kernels' dims: a wide index takes the pass even for one query, gemm_min_queries)
     if (idx->E16 || !idx->E || !(idx->split_scale > 0.f) || idx->has_empty_chunk || idx->n_chunks == 0 || idx->n_rows == 0) return RL_ERR_UNSUPPORTED;
     RL_TRY(demand_images(idx, IMG_HI_PLANE, s));
-    if (!hi_valid(idx) || idx->max_row_norm_rows != idx->n_rows || !(idx->max_row_norm > 0.f)) return RL_ERR_UNSUPPORTED;
+    if (!hi_valid(idx) || !idx->norm_stats.measured(idx->n_rows)) return RL_ERR_UNSUPPORTED;
     if ((reinterpret_cast<uintptr_t>(d_q) & 15) || (reinterpret_cast<uintptr_t>(idx->E) & 15)) return RL_ERR_UNSUPPORTED;
     const int64_t q_elems = (int64_t)nq * idx->dim;
     int st = RL_ERR_UNSUPPORTED;
@@ -2379,11 +2300,11 @@ int maxsim_few_hi_plane(rl_index* idx, const float* d_q, int32_t nq, int32_t n, 
         RL_TRY(idx->qsplit.reserve(query_split_bytes(idx->dim, 2)));
         st = launch_query_split(d_q, idx->dim, nq, q_elems, 2, idx->qsplit.as<char>(), true, s);
         if (st == RL_OK)
-            st = launch_maxsim_stream2(idx->hiplane.p, true, idx->n_rows, idx->dim, idx->qsplit.as<char>(), 2, 0, nq, idx->row_to_chunk, idx->offsets,
+            st = launch_maxsim_stream2(idx->hiplane.buf.p, true, idx->n_rows, idx->dim, idx->qsplit.as<char>(), 2, 0, nq, idx->row_to_chunk, idx->offsets,
                                        idx->n_chunks, sc, ld, idx->n_cu, s, 1.f);
     }
     if (st == RL_ERR_UNSUPPORTED)  // one pass per query, one launch (grid row = query)
-        st = launch_maxsim_stream_batch(idx->hiplane.p, true, idx->n_rows, idx->dim, d_q, nq, q_elems, n, idx->row_to_chunk, idx->offsets,
+        st = launch_maxsim_stream_batch(idx->hiplane.buf.p, true, idx->n_rows, idx->dim, d_q, nq, q_elems, n, idx->row_to_chunk, idx->offsets,
                                         idx->n_chunks, sc, ld, idx->n_cu, s, 0.f, nullptr);
     if (st != RL_OK) return st;
     HiBatch hb;
@@ -2391,7 +2312,7 @@ int maxsim_few_hi_plane(rl_index* idx, const float* d_q, int32_t nq, int32_t n, 
     hb.exact_kth = idx->opt.on(RL_OPT_EXACT_KTH_THRESHOLD);
     RL_TRY(idx->hibuf.reserve(hi_batch_words(n, k) * 4));
     hi_batch_layout(idx, n, k, hb);
-    hb.m_abs = idx->max_lo_norm + sum_eps(idx->dim) * idx->max_row_norm;
+    hb.m_abs = idx->norm_stats.max_lo_norm + sum_eps(idx->dim) * idx->norm_stats.max_row_norm;
     hb.q_unscale = nullptr;
     hb.filter = d_filter;
     // The pivot route (round 6, option hi_pivot; k <= 128, no tombstones): with the chip idle around one query, re-scoring ~2.5 x the candidates
@@ -2422,7 +2343,7 @@ int maxsim_few_hi_plane(rl_index* idx, const float* d_q, int32_t nq, int32_t n, 
     RL_TRY(mask_chunk_scores(idx, sc, n, ld, d_filter, s));  // tombstones / filtered-out chunks never become candidates
     RL_TRY(launch_topk(sc, n, idx->n_chunks, ld, k, idx->ws, hb.ts, hb.ti, s));
     RL_TRY(launch_maxsim_threshold(hb.ts, n, k, d_q, nq, idx->dim, q_elems, 1.0f, hb.m_abs, hb.thr, hb.cnt, hb.flag, s, nullptr,
-                                   idx->max_row_norm + idx->max_lo_norm, hb.m));
+                                   idx->norm_stats.max_row_norm + idx->norm_stats.max_lo_norm, hb.m));
     return hi_batch_rescore(idx, d_q, nq, n, n, k, sc, ld, hb, d_s, d_c, s, true);
 }
 // The device side of rl_maxsim_topk_batch: d_q [n_queries x nq x dim] -> d_s / d_c [n_queries x k]; sc: [n_queries x ld] scratch rows
@@ -2478,7 +2399,7 @@ int maxsim_topk_batch_device(rl_index* idx, const float* d_q, bool q16, int32_t 
                 RL_TRY(hi_batch_approx(idx, d_q, nq, n_queries, n_gemm, k, sc, ld, hb, s, flag_words != nullptr));
                 // (an fp32-STORED corpus whose every element is an fp16 value at the split scale -- what its HI halves drop was measured as
                 // exactly zero when the image was built -- is the same case: RAGLite's embeddings handed over as float32 arrays)
-                if (q16 && (idx->E16 || idx->max_lo_norm == 0.f) && hb.one_product && idx->opt.on(RL_OPT_F16_EXACT)) {
+                if (q16 && (idx->E16 || idx->norm_stats.max_lo_norm == 0.f) && hb.one_product && idx->opt.on(RL_OPT_F16_EXACT)) {
                     // fp16 queries x fp16-stored corpus: q_hi . e IS q . e (products of two fp16 values are exact in fp32; the sums are the
                     // pass's fp32 accumulation) -- its top-k is the result; certified per query, the full-precision passes behind the flag
                     RL_TRY(launch_f16_exact_finish(d_q, nq, idx->dim, (int64_t)q_elems, hb.q_unscale, hb.ts, hb.ti, n_gemm, k, d_s, d_c, hb.cnt, hb.flag, s));
@@ -2489,7 +2410,7 @@ int maxsim_topk_batch_device(rl_index* idx, const float* d_q, bool q16, int32_t 
                     // -- no threshold kernel that reads the queries again: 10 us of every 128-query step)
                     if (hb.exact_kth && k <= hb.cap && hb.qsum) hb.m_ready = false;
                     else RL_TRY(launch_maxsim_threshold(hb.ts, n_gemm, k, d_q, nq, idx->dim, (int64_t)q_elems, 1.0f, hb.m_abs, hb.thr, hb.cnt, hb.flag, s,
-                                                        hb.one_product ? hb.q_unscale : nullptr, idx->max_row_norm + idx->max_lo_norm, hb.m));
+                                                        hb.one_product ? hb.q_unscale : nullptr, idx->norm_stats.max_row_norm + idx->norm_stats.max_lo_norm, hb.m));
                     RL_TRY(hi_batch_rescore(idx, d_q, nq, n_queries, n_gemm, k, sc, ld, hb, d_s, d_c, s));
                 }
                 base = n_gemm;
@@ -2618,7 +2539,7 @@ int rl_maxsim_batch_begin(rl_index* idx, const float* query_vecs, int32_t n_quer
     // this shard's bound m_b: the threshold kernel over a "k-th best" of zero leaves -2 m_b
     RL_HIP(hipMemsetAsync(hb.es, 0, (size_t)n_queries * sizeof(float), s));
     RL_TRY(launch_maxsim_threshold(hb.es, n_queries, 1, d_q, nq, idx->dim, (int64_t)q_elems, 1.0f, hb.m_abs, hb.thr, hb.cnt, hb.flag, s,
-                                   hb.one_product ? hb.q_unscale : nullptr, idx->max_row_norm + idx->max_lo_norm));
+                                   hb.one_product ? hb.q_unscale : nullptr, idx->norm_stats.max_row_norm + idx->norm_stats.max_lo_norm));
     RL_TRY(launch_pack_approx(hb.ts, hb.thr, n_queries, k, d_o, s));
     idx->mb_B = n_queries;
     idx->mb_nq = nq;
@@ -2701,7 +2622,7 @@ int rl_maxsim_approx_scores(rl_index* idx, const float* query_vecs, int32_t n_qu
                                       idx->ends.as<uint32_t>(), d_o + (int64_t)b * ld, ld, idx->n_cu, s, approx_scale(idx), true, nullptr, true));
     }
     if (d_b) {  // the bound of the one-product pass, by the kernel the pipeline computes its thresholds with (k = 1 over a dummy top list)
-        const float m_abs = idx->max_lo_norm + sum_eps(idx->dim) * idx->max_row_norm;
+        const float m_abs = idx->norm_stats.max_lo_norm + sum_eps(idx->dim) * idx->norm_stats.max_row_norm;
         const float* q_unscale = reinterpret_cast<const float*>(idx->qplanes.as<char>() + (size_t)n_queries * idx->dim * 128);
         RL_TRY(idx->hibuf.reserve((size_t)n_queries * 4 * sizeof(float) + 64));
         float* top = idx->hibuf.as<float>();                                     // [n] "k-th best" = 0
@@ -2711,7 +2632,7 @@ int rl_maxsim_approx_scores(rl_index* idx, const float* query_vecs, int32_t n_qu
         RL_HIP(hipMemsetAsync(top, 0, (size_t)n_queries * sizeof(float), s));
         RL_HIP(hipMemsetAsync(flag, 0, 16 * sizeof(uint32_t), s));
         RL_TRY(launch_maxsim_threshold(top, n_queries, 1, d_q, nq, idx->dim, (int64_t)q_elems, 1.0f, m_abs, thr, cnt, flag, s, q_unscale,
-                                       idx->max_row_norm + idx->max_lo_norm));
+                                       idx->norm_stats.max_row_norm + idx->norm_stats.max_lo_norm));
         RL_TRY(launch_scale_f32(thr, d_b, -0.5f, n_queries, s));                // thr = -2 m  ->  m
         idx->filt = {};
     }
@@ -2936,34 +2857,34 @@ int rl_time_kernel(rl_index* idx, int kind, const float* q_dev, int32_t nq, int3
             else if (r.pp && r.round1_tiles > 0) {  // both rounds with the thresholds each of them ran with (the ranking between them is not replayed)
                 CandArgs ca1 = r.ca;
                 ca1.tau = r.thr1;
-                st = launch_pp_rows_pass(idx->hi_image.p, idx->n_rows, idx->dim, r.B, r.qs, idx->norm, r.mode, &ca1, idx->pp_work.p, r.log_cap, idx->n_cu, s,
+                st = launch_pp_rows_pass(idx->hi_image.buf.p, idx->n_rows, idx->dim, r.B, r.qs, idx->norm, r.mode, &ca1, idx->pp_work.p, r.log_cap, idx->n_cu, s,
                                          idx->split_scale, 0, r.round1_tiles, false, r.row_test);
                 if (st == RL_OK)
-                    st = launch_pp_rows_pass(idx->hi_image.p, idx->n_rows, idx->dim, r.B, r.qs, idx->norm, r.mode, &r.ca, idx->pp_work.p, r.log_cap, idx->n_cu, s,
+                    st = launch_pp_rows_pass(idx->hi_image.buf.p, idx->n_rows, idx->dim, r.B, r.qs, idx->norm, r.mode, &r.ca, idx->pp_work.p, r.log_cap, idx->n_cu, s,
                                              idx->split_scale, r.round1_tiles, -1, true, r.row_test);
             }
-            else if (r.pp) st = launch_pp_rows_pass(idx->hi_image.p, idx->n_rows, idx->dim, r.B, r.qs, idx->norm, r.mode, &r.ca, idx->pp_work.p, r.log_cap,
+            else if (r.pp) st = launch_pp_rows_pass(idx->hi_image.buf.p, idx->n_rows, idx->dim, r.B, r.qs, idx->norm, r.mode, &r.ca, idx->pp_work.p, r.log_cap,
                                                     idx->n_cu, s, idx->split_scale, 0, -1, false, r.row_test);
-            else st = launch_score_planes_pass(idx->hi_image.p, idx->n_rows, idx->dim, r.B, r.qs, nullptr, 0, idx->norm, idx->sumsq, r.mode, 1, nullptr, &r.ca,
+            else st = launch_score_planes_pass(idx->hi_image.buf.p, idx->n_rows, idx->dim, r.B, r.qs, nullptr, 0, idx->norm, idx->sumsq, r.mode, 1, nullptr, &r.ca,
                                                idx->n_cu, s, idx->split_scale, true, true);
         }
         else if (kind == 0) st = maxsim_scores_device(idx, q_dev, nq, idx->scores.as<float>(), s);
         else if (kind == 9) st = launch_mfma_f16_rate(idx->scores.as<float>(), idx->n_cu, MFMA_RATE_ITERS, s, nullptr);
         else if (kind == 2) st = pairs_pass(idx, nq / 2, 2, 0, idx->scores.as<float>(), ldc, s);
         else if (kind == 5 || kind == 6) {  // the approximate MaxSim pass of a batch: eight queries over the HI image (5: two MFMA products, 6: one)
-            st = hi_image_valid(idx) ? launch_maxsim_gemm(idx->hi_image.p, idx->n_rows, idx->dim, idx->qplanes.p, GEMM_PASS_QUERIES, 0,
+            st = hi_image_valid(idx) ? launch_maxsim_gemm(idx->hi_image.buf.p, idx->n_rows, idx->dim, idx->qplanes.p, GEMM_PASS_QUERIES, 0,
                                                           GEMM_PASS_QUERIES, nq / GEMM_PASS_QUERIES, idx->row_to_chunk, idx->offsets,
                                                           idx->ends.as<uint32_t>(), idx->scores.as<float>(), ldc, idx->n_cu, s, idx->split_scale, true,
                                                           nullptr, kind == 6)
                                      : fail(RL_ERR_UNSUPPORTED, "rl_time_kernel: the index has no HI image");
         }
         else if (kind == 4) {  // the ranking pass of the half-bytes search: the f16 stream kernel over the HI plane
-            st = hi_valid(idx) ? launch_maxsim_stream16(idx->hiplane.as<uint16_t>(), idx->n_rows, idx->dim, q_dev, nq, idx->row_to_chunk, idx->offsets,
+            st = hi_valid(idx) ? launch_maxsim_stream16(idx->hiplane.buf.as<uint16_t>(), idx->n_rows, idx->dim, q_dev, nq, idx->row_to_chunk, idx->offsets,
                                                         idx->n_chunks, 1, idx->scores.as<float>(), ld, idx->n_cu, s)
                                : fail(RL_ERR_UNSUPPORTED, "rl_time_kernel: the index has no HI plane");
         }
         else if (kind == 10) {  // the approximate pass of the few-queries MaxSim route: ONE query of nq vectors, MaxSim over the HI plane
-            st = hi_valid(idx) && nq <= 32 ? launch_maxsim_stream_batch(idx->hiplane.p, true, idx->n_rows, idx->dim, q_dev, nq, (int64_t)nq * idx->dim, 1,
+            st = hi_valid(idx) && nq <= 32 ? launch_maxsim_stream_batch(idx->hiplane.buf.p, true, idx->n_rows, idx->dim, q_dev, nq, (int64_t)nq * idx->dim, 1,
                                                                         idx->row_to_chunk, idx->offsets, idx->n_chunks, idx->scores.as<float>(), ldc, idx->n_cu, s,
                                                                         0.f, nullptr)
                                            : fail(RL_ERR_UNSUPPORTED, "rl_time_kernel: the index has no HI plane (or nq > 32)");
