@@ -436,6 +436,35 @@ int rl_allgather_u32(rl_comm* comm, const uint32_t* local, int64_t count, uint32
 int rl_topk(const float* scores, int32_t n_queries, int64_t n, int64_t ld, int32_t k,
             float* out_scores, int32_t* out_ids, int mem, void* stream);
 
+/* ---- BM25 keyword search (the keyword half of hybrid search) -------------------------------------
+ * Replaces src/raglite/_search.py:156-230 (DuckDB FTS `match_bm25` over chunk.body, ORDER BY score DESC LIMIT k,
+ * WHERE score IS NOT NULL).  The host analyses the text and computes the statistics (raglite_amd/_keyword.py,
+ * DESIGN.md "Keyword search"); a keyword index holds term-major postings over the SAME chunk ordinals as the
+ * rl_index it sits beside:
+ *   term_off    int64[n_terms + 1], term_off[0] = 0, ascending, term_off[n_terms] = n_postings
+ *   post_chunk  int32[n_postings] chunk ordinals in [0, n_chunks), strictly ascending within a term
+ *   post_tf     int32[n_postings] >= 1, occurrences of the term in the chunk
+ *   post_term   int32[n_postings] the term of each posting (t for every posting of term t)
+ *   idf         f32[n_terms], nrm f32[n_chunks]: ln(1 + (N - df + 0.5) / (df + 0.5)) and k1 (1 - b + b len / avgdl),
+ *               computed in double and rounded to float (k1 = 1.2, b = 0.75)
+ * rl_keyword_index_create checks host postings as stated; device postings are taken as given (kernels skip entries
+ * outside the stated ranges).  Each posting's impact idf * ((tf * 2.2f) / (tf + nrm)) is computed once, in float, rounded
+ * at every step.  post_tf / post_term / idf / nrm are not kept.
+ * rl_keyword_search: query b's term ids are q_terms[q_off[b] .. q_off[b + 1]), ascending and distinct; ids outside
+ * [0, n_terms) are ignored.  A chunk's score is the float sum of the impacts of the query terms it contains, in
+ * ascending term order; chunks with none of them, and chunks whose chunk_filter bit (as in the *_filtered calls;
+ * NULL = none) is clear, are no result.  out_scores / out_chunks [n_queries x k] by (score desc, chunk asc), unfilled
+ * slots (-inf, -1); out_counts [n_queries] (may be NULL) the filled slots.  k <= 2048. */
+typedef struct rl_keyword_index rl_keyword_index;
+int rl_keyword_index_create(rl_keyword_index** out, const int64_t* term_off, int32_t n_terms, const int32_t* post_chunk,
+                            const int32_t* post_tf, const int32_t* post_term, int64_t n_postings, const float* idf,
+                            const float* nrm, int64_t n_chunks, int mem, void* stream);
+int rl_keyword_search(rl_keyword_index* kw, const int64_t* q_off, const int32_t* q_terms, int32_t n_queries, int32_t k,
+                      const uint32_t* chunk_filter, float* out_scores, int32_t* out_chunks, int32_t* out_counts, int mem,
+                      void* stream);
+int rl_keyword_index_info(const rl_keyword_index* kw, int32_t* n_terms, int64_t* n_postings, int64_t* n_chunks);
+int rl_keyword_index_destroy(rl_keyword_index* kw);
+
 /* ---- metadata filter pushed down ---------------------------------------
  * The filter-first branch of the reference's vector search (src/raglite/_search.py:96-119): only
  * rows of chunks that match the metadata filter are ranked.  The caller evaluates the filter on its

@@ -2,7 +2,7 @@
 
 Hand-written HIP (gfx950) kernels behind a C ABI (`include/raglite_hip.h`, `libraglite_hip.so`)
 and a Python host layer that mirrors the reference's own entry points for this path:
-`embed_strings()`, `vector_search()`, `rerank_chunks()` and the `RAGLiteConfig.search_method` /
+`embed_strings()`, `vector_search()`, `keyword_search()`, `hybrid_search()`, `rerank_chunks()` and the `RAGLiteConfig.search_method` /
 `.reranker` plugin objects.  There is no CPU fallback: without the shared library (or a gfx950
 GPU) the calls raise.
 """
@@ -18,6 +18,7 @@ from raglite_amd._embed import (
 )
 from raglite_amd._ops import (
     DeviceIndex,
+    KeywordIndex,
     adapter_apply,
     merge_topk,
     pack_bits,
@@ -31,6 +32,7 @@ from raglite_amd._ops import (
 from raglite_amd._search import (
     GpuIndex,
     hybrid_search,
+    keyword_search,
     reciprocal_rank_fusion,
     GpuVectorSearch,
     MaxSimRanker,
@@ -56,6 +58,8 @@ __all__ = [
     "partition_similarities",
     "split_chunks",
     "hybrid_search",
+    "keyword_search",
+    "KeywordIndex",
     "reciprocal_rank_fusion",
     "update_query_adapter",
     "EncoderShape",

@@ -1,0 +1,236 @@
+"""Host half of BM25 keyword search: the analyzer, the Porter stemmer, the stopword list and the postings builder.
+
+The reference ranks keywords with DuckDB's full-text search over `chunk.body` (`src/raglite/_search.py:156-230`; the index is
+`PRAGMA create_fts_index('chunk', 'id', 'body')` with default settings, `_database.py:618`).  This module restates those defaults
+(DESIGN.md "Keyword search" is the contract):
+
+    index side   strip accents (NFKD, drop combining marks), lowercase, split on `(\\\\.|[^a-z])+`, drop English stopwords,
+                 Porter-stem every token
+    query side   the same without stopword removal, distinct stems; stems outside the vocabulary drop out
+    statistics   over the LIVE chunks: N, avgdl (empty chunks count, length 0), df per stem
+    score        sum over query stems t in chunk c of  idf_t * tf (k1 + 1) / (tf + nrm_c),  k1 = 1.2, b = 0.75,
+                 idf_t = ln(1 + (N - df_t + 0.5) / (df_t + 0.5)),  nrm_c = k1 (1 - b + b len_c / avgdl)
+
+Term ids are the ranks of the stems in the sorted vocabulary.  idf and nrm are computed in float64 and rounded to float32; the
+device (`raglite_amd/csrc/keyword.hip`) does the float32 rest.
+"""
+
+from __future__ import annotations
+
+import functools
+import re
+import unicodedata
+from dataclasses import dataclass
+from pathlib import Path
+from typing import Sequence
+
+import numpy as np
+
+K1 = 1.2
+B = 0.75
+
+STOPWORDS: frozenset[str] = frozenset((Path(__file__).resolve().parent / "stopwords_english.txt").read_text().split())
+
+# DuckDB's default `ignore='(\\.|[^a-z])+'`: a backslash with the character after it, or any character outside a-z, separates tokens
+_SEPARATORS = re.compile(r"(?:\\.|[^a-z])+")
+
+
+def normalize(text: str) -> str:
+    """Strip accents (NFKD, then drop combining marks), then lowercase."""
+    decomposed = unicodedata.normalize("NFKD", text)
+    return "".join(ch for ch in decomposed if not unicodedata.combining(ch)).lower()
+
+
+def tokenize(text: str) -> list[str]:
+    return [tok for tok in _SEPARATORS.split(normalize(text)) if tok]
+
+
+# ---- the Porter stemmer (M. F. Porter, "An algorithm for suffix stripping", Program 14(3), 1980) -----------------------------
+def _consonant(w: str, i: int) -> bool:
+    ch = w[i]
+    if ch in "aeiou":
+        return False
+    if ch == "y":  # y is a consonant at the start of a word and after a vowel, a vowel after a consonant
+        return i == 0 or not _consonant(w, i - 1)
+    return True
+
+
+def _measure(stem: str) -> int:
+    """m of the stem's form [C](VC)^m[V]."""
+    n, i, m = len(stem), 0, 0
+    while i < n and _consonant(stem, i):
+        i += 1
+    while i < n:
+        while i < n and not _consonant(stem, i):
+            i += 1
+        if i == n:
+            break
+        m += 1
+        while i < n and _consonant(stem, i):
+            i += 1
+    return m
+
+
+def _has_vowel(stem: str) -> bool:
+    return any(not _consonant(stem, i) for i in range(len(stem)))
+
+
+def _double_consonant(w: str) -> bool:
+    return len(w) >= 2 and w[-1] == w[-2] and _consonant(w, len(w) - 1)
+
+
+def _cvc(w: str) -> bool:
+    """*o: the stem ends consonant-vowel-consonant, the last consonant not w, x or y."""
+    n = len(w)
+    return n >= 3 and _consonant(w, n - 3) and not _consonant(w, n - 2) and _consonant(w, n - 1) and w[-1] not in "wxy"
+
+
+_STEP2 = {"ational": "ate", "tional": "tion", "enci": "ence", "anci": "ance", "izer": "ize", "abli": "able", "alli": "al", "entli": "ent",
+          "eli": "e", "ousli": "ous", "ization": "ize", "ation": "ate", "ator": "ate", "alism": "al", "iveness": "ive", "fulness": "ful",
+          "ousness": "ous", "aliti": "al", "iviti": "ive", "biliti": "ble"}
+_STEP3 = {"icate": "ic", "ative": "", "alize": "al", "iciti": "ic", "ical": "ic", "ful": "", "ness": ""}
+_STEP4 = ("al", "ance", "ence", "er", "ic", "able", "ible", "ant", "ement", "ment", "ent", "ion", "ou", "ism", "ate", "iti", "ous", "ive",
+          "ize")
+
+
+def _longest(w: str, suffixes) -> str | None:
+    """Of a set of rules only the one with the longest matching suffix is tried (whether or not its condition then holds)."""
+    best = None
+    for suf in suffixes:
+        if w.endswith(suf) and (best is None or len(suf) > len(best)):
+            best = suf
+    return best
+
+
+@functools.lru_cache(maxsize=1 << 18)
+def stem(word: str) -> str:
+    w = word
+    # step 1a
+    if w.endswith("sses") or w.endswith("ies"):
+        w = w[:-2]
+    elif w.endswith("s") and not w.endswith("ss"):
+        w = w[:-1]
+    # step 1b
+    again = False
+    if w.endswith("eed"):
+        if _measure(w[:-3]) > 0:
+            w = w[:-1]
+    elif w.endswith("ed") and _has_vowel(w[:-2]):
+        w, again = w[:-2], True
+    elif w.endswith("ing") and _has_vowel(w[:-3]):
+        w, again = w[:-3], True
+    if again:
+        if w.endswith(("at", "bl", "iz")):
+            w += "e"
+        elif _double_consonant(w) and w[-1] not in "lsz":
+            w = w[:-1]
+        elif _measure(w) == 1 and _cvc(w):
+            w += "e"
+    # step 1c
+    if w.endswith("y") and _has_vowel(w[:-1]):
+        w = w[:-1] + "i"
+    # step 2
+    suf = _longest(w, _STEP2)
+    if suf and _measure(w[: -len(suf)]) > 0:
+        w = w[: -len(suf)] + _STEP2[suf]
+    # step 3
+    suf = _longest(w, _STEP3)
+    if suf and _measure(w[: -len(suf)]) > 0:
+        w = w[: -len(suf)] + _STEP3[suf]
+    # step 4
+    suf = _longest(w, _STEP4)
+    if suf:
+        base = w[: -len(suf)]
+        if _measure(base) > 1 and (suf != "ion" or base.endswith(("s", "t"))):
+            w = base
+    # step 5a
+    if w.endswith("e"):
+        base = w[:-1]
+        m = _measure(base)
+        if m > 1 or (m == 1 and not _cvc(base)):
+            w = base
+    # step 5b
+    if w.endswith("l") and _double_consonant(w) and _measure(w) > 1:
+        w = w[:-1]
+    return w
+
+
+def index_stems(text: str) -> list[str]:
+    """The stems a chunk body contributes to the index, in text order (stopwords removed)."""
+    return [stem(tok) for tok in tokenize(text) if tok not in STOPWORDS]
+
+
+def query_stems(text: str) -> list[str]:
+    """The distinct stems of a query, sorted (no stopword removal: DuckDB's `match_bm25` keeps them)."""
+    return sorted({stem(tok) for tok in tokenize(text)})
+
+
+# ---- postings and statistics --------------------------------------------------------------------------------------------------
+@dataclass
+class Postings:
+    """Term-major CSR over chunk ordinals (what `rl_keyword_index_create` takes) and the statistics behind it."""
+
+    term_off: np.ndarray    # int64 [n_terms + 1]
+    post_chunk: np.ndarray  # int32, ascending within a term
+    post_tf: np.ndarray     # int32 >= 1
+    post_term: np.ndarray   # int32
+    idf: np.ndarray         # float32 [n_terms]
+    nrm: np.ndarray         # float32 [n_chunks] (every ordinal; a dead chunk has no postings)
+    length: np.ndarray      # int64 [n_chunks]: stems per chunk (0 for a dead one)
+    n_live: int             # N
+    avgdl: float            # mean length over the live chunks (float64)
+
+    @property
+    def n_terms(self) -> int:
+        return int(self.term_off.size - 1)
+
+    @property
+    def n_chunks(self) -> int:
+        return int(self.nrm.size)
+
+    @property
+    def df(self) -> np.ndarray:
+        return np.diff(self.term_off)
+
+
+def build_from_term_ids(flat_ids: np.ndarray, offsets: np.ndarray, n_terms: int, live: np.ndarray | None = None) -> Postings:
+    """Postings from pre-tokenised chunks: chunk c holds term ids flat_ids[offsets[c] : offsets[c + 1]] (any order, repeats = tf).
+    `live`: bool per chunk (None = all); dead chunks add nothing and are not counted in N, avgdl or df."""
+    offsets = np.asarray(offsets, dtype=np.int64)
+    n_chunks = int(offsets.size - 1)
+    flat_ids = np.asarray(flat_ids, dtype=np.int64)
+    if flat_ids.size and (flat_ids.min() < 0 or flat_ids.max() >= n_terms):
+        raise ValueError("term id out of range")
+    chunk_of = np.repeat(np.arange(n_chunks, dtype=np.int64), np.diff(offsets))
+    if live is not None:
+        live = np.asarray(live, dtype=bool)
+        keep = live[chunk_of]
+        flat_ids, chunk_of = flat_ids[keep], chunk_of[keep]
+    length = np.bincount(chunk_of, minlength=n_chunks).astype(np.int64)
+    keys, tf = np.unique(flat_ids * max(n_chunks, 1) + chunk_of, return_counts=True)  # sorted: term-major, chunks ascending
+    post_term = keys // max(n_chunks, 1)
+    post_chunk = keys - post_term * max(n_chunks, 1)
+    df = np.bincount(post_term, minlength=n_terms).astype(np.int64)
+    term_off = np.concatenate(([0], np.cumsum(df))).astype(np.int64)
+    n_live = n_chunks if live is None else int(live.sum())
+    avgdl = float(length.sum()) / n_live if n_live else 0.0
+    idf = np.log1p((n_live - df + 0.5) / (df + 0.5))
+    rel = length / avgdl if avgdl > 0 else np.zeros(n_chunks)
+    nrm = K1 * (1.0 - B + B * rel)
+    return Postings(term_off, post_chunk.astype(np.int32), tf.astype(np.int32), post_term.astype(np.int32), idf.astype(np.float32),
+                    nrm.astype(np.float32), length, n_live, avgdl)
+
+
+def build_from_stems(chunk_stems: Sequence[Sequence[str] | None]) -> tuple[list[str], Postings]:
+    """(vocabulary, postings) of chunks given as their index stems; None marks a dead chunk (an ordinal with no text)."""
+    vocab = sorted({s for stems in chunk_stems if stems is not None for s in stems})
+    ids = {s: i for i, s in enumerate(vocab)}
+    sizes = np.fromiter((len(stems) if stems is not None else 0 for stems in chunk_stems), dtype=np.int64, count=len(chunk_stems))
+    flat = np.fromiter((ids[s] for stems in chunk_stems if stems is not None for s in stems), dtype=np.int64, count=int(sizes.sum()))
+    live = np.fromiter((stems is not None for stems in chunk_stems), dtype=bool, count=len(chunk_stems))
+    offsets = np.concatenate(([0], np.cumsum(sizes))).astype(np.int64)
+    return vocab, build_from_term_ids(flat, offsets, len(vocab), None if live.all() else live)
+
+
+def build_from_texts(texts: Sequence[str | None]) -> tuple[list[str], Postings]:
+    return build_from_stems([None if t is None else index_stems(t) for t in texts])

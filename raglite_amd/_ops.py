@@ -670,3 +670,54 @@ class DeviceIndex:
         self._prep(a)
         check(lib().rl_time_kernel(self._handle, kind, p_q, nq, iters, C.byref(ms), a.stream))
         return float(ms.value)
+
+
+class KeywordIndex:
+    """BM25 postings on the device (`rl_keyword_index`): the keyword half of hybrid search, over the chunk ordinals of the
+    `DeviceIndex` it sits beside.  Built from a `raglite_amd._keyword.Postings` (host arrays; the impacts are computed on the device)."""
+
+    def __init__(self, postings) -> None:
+        p = postings
+        arrs = [np.ascontiguousarray(p.term_off, dtype=np.int64), np.ascontiguousarray(p.post_chunk, dtype=np.int32),
+                np.ascontiguousarray(p.post_tf, dtype=np.int32), np.ascontiguousarray(p.post_term, dtype=np.int32),
+                np.ascontiguousarray(p.idf, dtype=np.float32), np.ascontiguousarray(p.nrm, dtype=np.float32)]
+        term_off, post_chunk, post_tf, post_term, idf, nrm = arrs
+        self.n_terms, self.n_postings, self.n_chunks = int(term_off.size - 1), int(post_chunk.size), int(nrm.size)
+        _ensure_init(_current_device())
+        handle = C.c_void_p()
+        check(lib().rl_keyword_index_create(C.byref(handle), term_off.ctypes.data, self.n_terms, post_chunk.ctypes.data,
+                                            post_tf.ctypes.data, post_term.ctypes.data, self.n_postings, idf.ctypes.data,
+                                            nrm.ctypes.data, self.n_chunks, MEM_HOST, None))
+        self._handle = handle
+
+    def close(self) -> None:
+        h, self._handle = getattr(self, "_handle", None), None
+        if h:
+            lib().rl_keyword_index_destroy(h)
+
+    def __del__(self) -> None:  # noqa: D105
+        try:
+            self.close()
+        except Exception:  # noqa: BLE001,S110 - interpreter shutdown
+            pass
+
+    def search(self, query_term_ids, k: int, chunk_filter=None):
+        """BM25 top-k of a batch: `query_term_ids` holds one sequence of term ids per query (duplicates are dropped, order does not
+        matter).  Returns (scores (B,k) float32, chunk ordinals (B,k) int32, counts (B,) int32); unfilled slots are (-inf, -1)."""
+        qs = [np.unique(np.asarray(q, dtype=np.int32)) for q in query_term_ids]
+        q_off = np.concatenate(([0], np.cumsum([q.size for q in qs]))).astype(np.int64)
+        q_terms = np.ascontiguousarray(np.concatenate(qs) if qs else np.zeros(0, np.int32), dtype=np.int32)
+        B = len(qs)
+        scores = np.empty((B, k), np.float32)
+        chunks = np.empty((B, k), np.int32)
+        counts = np.empty(B, np.int32)
+        p_f = None
+        if chunk_filter is not None:
+            bits = pack_bits(chunk_filter)
+            if bits.size != (self.n_chunks + 31) // 32:
+                raise ValueError("chunk_filter must have one entry per chunk")
+            p_f = bits.ctypes.data
+        _ensure_init(_current_device())
+        check(lib().rl_keyword_search(self._handle, q_off.ctypes.data, q_terms.ctypes.data, B, k, p_f, scores.ctypes.data,
+                                      chunks.ctypes.data, counts.ctypes.data, MEM_HOST, None))
+        return scores, chunks, counts

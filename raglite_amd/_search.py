@@ -2,6 +2,9 @@
 
     vector_search(query, *, num_results=3, oversample=4, metadata_filter=None, config=None)
         -> (list[ChunkId], list[float])                                   (`_search.py:36-153`)
+    keyword_search(query, *, num_results=3, metadata_filter=None, config=None)
+        -> (list[ChunkId], list[float])   BM25 on the device               (`_search.py:156-230`)
+    hybrid_search(...)                                                    (`_search.py:255-279`)
     rerank_chunks(query, chunk_ids, *, config=None) -> list[chunk]        (`_search.py:364-397`)
     search_and_rerank_chunks(...)                                         (`_search.py:400-414`)
     GpuVectorSearch   -- a `BasicSearchMethod` (`_typing.py:35-43`) for `RAGLiteConfig.search_method`
@@ -20,7 +23,7 @@ from typing import Any, Callable, Sequence
 
 import numpy as np
 
-from raglite_amd import _ops
+from raglite_amd import _keyword, _ops
 from raglite_amd._config import DEFAULT_CHUNK_MAX_SIZE, HotPathConfig
 from raglite_amd._embed import embed_strings
 
@@ -40,11 +43,20 @@ class GpuIndex:
     metadata         optional list[dict] per chunk for `metadata_filter`
     storage          "f32", or "f16" (the reference's own storage precision)
     exact_fp32       multiply with exact fp32 MFMAs instead of the default fp16 (hi, lo) split of fp32 operands
+    keyword_texts    optional list[str] -- `Chunk.body` per chunk: builds the BM25 keyword side (`keyword_search`, the keyword
+                     half of `hybrid_search`; DESIGN.md "Keyword search"), rebuilt from the live chunks after every change
     """
+
+    # keyword side (class defaults: an index without one): each chunk's index stems (None once deleted), the vocabulary and the device
+    # postings built from them
+    keyword: _ops.KeywordIndex | None = None
+    _kw_stems: list[list[str] | None] | None = None
+    _kw_vocab: dict[str, int] = {}
 
     def __init__(self, chunk_ids: Sequence[ChunkId], chunk_embeddings, *, chunk_offsets=None,
                  metric: str = "cosine", query_adapter=None, docs: Sequence[str] | None = None,
-                 metadata: Sequence[dict] | None = None, storage: str = "f32", exact_fp32: bool = False) -> None:
+                 metadata: Sequence[dict] | None = None, storage: str = "f32", exact_fp32: bool = False,
+                 keyword_texts: Sequence[str] | None = None) -> None:
         if chunk_offsets is None:
             mats = [np.asarray(m, dtype=np.float32).reshape(len(m), -1) for m in chunk_embeddings]
             sizes = np.asarray([len(m) for m in mats], dtype=np.int64)
@@ -65,6 +77,28 @@ class GpuIndex:
         self._doc_to_ordinal = None if docs is None else {d: i for i, d in enumerate(self.docs)}
         self.metadata = None if metadata is None else list(metadata)
         self._id_to_ordinal = {cid: i for i, cid in enumerate(self.chunk_ids)}
+        if keyword_texts is not None:
+            if len(keyword_texts) != len(self.chunk_ids):
+                raise ValueError("one keyword text per chunk is required")
+            self._kw_stems = [_keyword.index_stems(t) for t in keyword_texts]
+            self._rebuild_keywords()
+
+    @property
+    def has_keywords(self) -> bool:
+        return self._kw_stems is not None
+
+    def _rebuild_keywords(self) -> None:
+        """The reference rebuilds its FTS index after every insert and delete (`_insert.py:268`, `_delete.py:173`): N, avgdl and df
+        change, so the postings are rebuilt from the live chunks' cached stems (no text is analysed again)."""
+        vocab, postings = _keyword.build_from_stems(self._kw_stems)
+        new = _ops.KeywordIndex(postings)  # (built before the old one goes: a failure leaves the index as it was)
+        if self.keyword is not None:
+            self.keyword.close()
+        self.keyword, self._kw_vocab = new, {s: i for i, s in enumerate(vocab)}
+
+    def keyword_query_ids(self, query: str) -> list[int]:
+        """Term ids of the query's distinct stems that are in the vocabulary, ascending."""
+        return sorted(self._kw_vocab[s] for s in _keyword.query_stems(query) if s in self._kw_vocab)
 
     def ordinal_of(self, chunk_id: ChunkId) -> int:
         return self._id_to_ordinal[chunk_id]
@@ -76,9 +110,10 @@ class GpuIndex:
 
     # -- lifecycle -------------------------------------------------------------------------
     def insert_chunks(self, chunk_ids: Sequence[ChunkId], chunk_embeddings, *, docs: Sequence[str] | None = None,
-                      metadata: Sequence[dict] | None = None) -> None:
+                      metadata: Sequence[dict] | None = None, keyword_texts: Sequence[str] | None = None) -> None:
         """`insert_documents` on the device image (`src/raglite/_insert.py:247-272`): append the chunks'
-        embedding matrices; existing ordinals keep their meaning."""
+        embedding matrices; existing ordinals keep their meaning.  `keyword_texts` (the chunks' bodies) iff the index has a
+        keyword side."""
         mats = [np.asarray(m, dtype=np.float32).reshape(len(m), -1) for m in chunk_embeddings]
         if len(mats) != len(chunk_ids):
             raise ValueError("one embedding matrix per chunk id is required")
@@ -86,6 +121,10 @@ class GpuIndex:
             raise ValueError("chunk id already present")  # the reference skips existing documents (`_insert.py:184-186`)
         if (self.docs is None) != (docs is None) or (self.metadata is None) != (metadata is None):
             raise ValueError("docs / metadata must be given iff the index was built with them")
+        if self.has_keywords != (keyword_texts is not None):
+            raise ValueError("keyword_texts must be given iff the index was built with them")
+        if keyword_texts is not None and len(keyword_texts) != len(chunk_ids):
+            raise ValueError("one keyword text per chunk id is required")
         if not mats:
             return
         self.index.append(np.vstack(mats), np.asarray([len(m) for m in mats], dtype=np.int64))
@@ -97,6 +136,9 @@ class GpuIndex:
             self._doc_to_ordinal.update({d: base + i for i, d in enumerate(docs)})
         if metadata is not None:
             self.metadata.extend(metadata)
+        if keyword_texts is not None:
+            self._kw_stems.extend(_keyword.index_stems(t) for t in keyword_texts)
+            self._rebuild_keywords()
 
     def delete_chunks(self, chunk_ids: Sequence[ChunkId]) -> int:
         """`delete_documents` on the device image (`src/raglite/_delete.py:148-176`): the chunks never match
@@ -104,15 +146,21 @@ class GpuIndex:
         ords = [self._id_to_ordinal.pop(cid) for cid in chunk_ids if cid in self._id_to_ordinal]
         if ords:
             self.index.delete_chunks(np.asarray(ords, dtype=np.int64))
+            if self.has_keywords:
+                for o in ords:
+                    self._kw_stems[o] = None
+                self._rebuild_keywords()
         return len(ords)
 
     # -- the real store ----------------------------------------------------------------------
     @classmethod
-    def from_store(cls, bind: Any, *, metric: str = "cosine", storage: str = "f32", exact_fp32: bool = False) -> "GpuIndex":
+    def from_store(cls, bind: Any, *, metric: str = "cosine", storage: str = "f32", exact_fp32: bool = False,
+                   keywords: bool = False) -> "GpuIndex":
         """Build the device index from a RAGLite database: `chunk_embedding` rows ordered by (chunk_id, id)
         (`src/raglite/_database.py:403-430`), the chunks' `str(chunk)` text and metadata, and the stored query adapter
         (`:450-462`).  `bind`: SQLAlchemy Engine / Connection / Session or a database URL.  `metric` is the store's
-        `vector_search_distance_metric` (`_config.py:69`).  The index remembers `bind` for `sync()`."""
+        `vector_search_distance_metric` (`_config.py:69`).  `keywords`: also build the BM25 keyword side from `chunk.body`.
+        The index remembers `bind` for `sync()`."""
         from raglite_amd import _store
 
         conn, owned = _store._connection(bind)  # noqa: SLF001
@@ -126,7 +174,7 @@ class GpuIndex:
             raise ValueError("First run `insert_documents()` to insert documents.")  # the reference's wording for an empty store
         off = np.concatenate(([0], np.cumsum(np.asarray(img.sizes, dtype=np.int64)))).astype(np.int64)
         gi = cls(img.chunk_ids, img.matrix(), chunk_offsets=off, metric=metric, query_adapter=adapter, docs=img.docs,
-                 metadata=img.metadata, storage=storage, exact_fp32=exact_fp32)
+                 metadata=img.metadata, storage=storage, exact_fp32=exact_fp32, keyword_texts=img.bodies if keywords else None)
         gi._bind = bind  # noqa: SLF001
         return gi
 
@@ -157,7 +205,8 @@ class GpuIndex:
                 mats.append(np.vstack(img.rows[at : at + size]))
                 at += size
             self.insert_chunks(img.chunk_ids, mats, docs=img.docs if self.docs is not None else None,
-                               metadata=img.metadata if self.metadata is not None else None)
+                               metadata=img.metadata if self.metadata is not None else None,
+                               keyword_texts=img.bodies if self.has_keywords else None)
         live_rows, _ = self.index.live()
         if self.index.n_rows and 1.0 - live_rows / self.index.n_rows > compact_above:
             self.compact()
@@ -176,9 +225,14 @@ class GpuIndex:
             self._doc_to_ordinal = {d: i for i, d in enumerate(self.docs)}
         if self.metadata is not None:
             self.metadata = [self.metadata[i] for i in keep]
+        if self.has_keywords:
+            self._kw_stems = [self._kw_stems[i] for i in keep]
+            self._rebuild_keywords()
 
     def close(self) -> None:
         self.index.close()
+        if self.keyword is not None:
+            self.keyword.close()
 
 
 # config (hashable, like the reference's lru_cache keys) -> GpuIndex
@@ -282,6 +336,40 @@ def _filtered_search(gi: GpuIndex, q, num_hits: int, num_results: int, flt: dict
     return [gi.chunk_ids[c] for c in chunks[:n].tolist()], [float(s) for s in scores[:n]]
 
 
+def keyword_search(query: str, *, num_results: int = 3, metadata_filter: dict | None = None, config: Any | None = None,
+                   index: GpuIndex | None = None) -> tuple[list[ChunkId], list[float]]:
+    """Search chunks with BM25 (`src/raglite/_search.py:156-230`, DuckDB's `match_bm25` over `chunk.body`) on the device.  Chunks
+    that contain no query stem are no result, so fewer than `num_results` may come back; equal scores rank by chunk ordinal."""
+    cfg = config or HotPathConfig()
+    gi = index or _index_for(config)
+    metadata_filter = _adapt_metadata(metadata_filter)
+    if getattr(cfg, "self_query", False) and isinstance(query, str):
+        raise NotImplementedError("self_query needs the LLM stack, which is outside this package")
+    if not gi.has_keywords:
+        raise ValueError("GpuIndex was built without keyword texts: pass keyword_texts= or from_store(..., keywords=True)")
+    if num_results < 1:
+        return [], []
+    if num_results > _ops.K_MAX:
+        raise ValueError(f"keyword_search: num_results={num_results} is more than the {_ops.K_MAX} the exact top-k kernel ranks; "
+                         "lower num_results")
+    ids = gi.keyword_query_ids(query)
+    if not ids:
+        return [], []
+    allowed = None
+    if metadata_filter:
+        if gi.metadata is None:
+            raise ValueError("GpuIndex was built without `metadata`; metadata_filter cannot be applied")
+        allowed = np.fromiter((_matches(m, metadata_filter) for m in gi.metadata), dtype=bool, count=len(gi.metadata))
+        if not allowed.any():
+            return [], []
+    scores, chunks, counts = gi.keyword.search([ids], num_results, chunk_filter=allowed)
+    n = int(counts[0])
+    return [gi.chunk_ids[c] for c in chunks[0, :n].tolist()], [float(x) for x in scores[0, :n]]
+
+
+_device_keyword_search = keyword_search  # (hybrid_search's `keyword_search` argument shadows the name)
+
+
 class GpuVectorSearch:
     """`BasicSearchMethod` for `RAGLiteConfig.search_method` (`src/raglite/_typing.py:35-43`,
     consumed at `src/raglite/_rag.py:53-63`)."""
@@ -320,15 +408,18 @@ def hybrid_search(query: str | np.ndarray, *, num_results: int = 3, oversample: 
                   metadata_filter: dict | None = None, config: Any | None = None, index: GpuIndex | None = None,
                   keyword_search: Callable[..., tuple[list[ChunkId], list[float]]] | None = None,
                   ) -> tuple[list[ChunkId], list[float]]:
-    """`src/raglite/_search.py:255-279`: GPU vector search fused with a keyword ranking by RRF.  The BM25 keyword
-    search lives in the store (`_search.py:156-230`, out of scope): pass the reference's own `keyword_search` (or any
-    callable with its signature) as `keyword_search=`; without one the fusion degenerates to the vector ranking."""
+    """`src/raglite/_search.py:255-279`: GPU vector search fused with a BM25 keyword ranking by RRF.  The keyword ranking
+    comes from `keyword_search=` when given (e.g. the reference's own SQL `keyword_search`), else from this package's
+    `keyword_search` when the index has a keyword side; an index without one and no callable fuses the vector ranking alone."""
     vs_ids, _ = vector_search(query, num_results=oversample * num_results, metadata_filter=metadata_filter,
                               config=config, index=index)
     ks_ids: list[ChunkId] = []
     if keyword_search is not None:
         ks_ids, _ = keyword_search(query, num_results=oversample * num_results, metadata_filter=metadata_filter,
                                    config=config)
+    elif isinstance(query, str) and (gi := index or _index_for(config)).has_keywords:
+        ks_ids, _ = _device_keyword_search(query, num_results=oversample * num_results, metadata_filter=metadata_filter,
+                                           config=config, index=gi)
     ids, scores = reciprocal_rank_fusion([vs_ids, ks_ids], weights=[vector_search_weight, keyword_search_weight])
     return ids[:num_results], scores[:num_results]
 
@@ -474,6 +565,7 @@ def search_and_rerank_chunks(query: str, *, num_results: int = 8, oversample: in
                              search: Callable[..., tuple[list[ChunkId], list[float]]] = vector_search,
                              config: Any | None = None, metadata_filter: dict | None = None,
                              chunk_lookup: Callable[[Sequence[ChunkId]], list[Any]] | None = None) -> list[Any]:
-    """`src/raglite/_search.py:400-414` (default `search` there is hybrid_search, whose keyword half is SQL)."""
+    """`src/raglite/_search.py:400-414` (the default `search` there is hybrid_search; pass `search=hybrid_search` over an index
+    with a keyword side for the same pipeline on the device)."""
     chunk_ids, _ = search(query, num_results=oversample * num_results, metadata_filter=metadata_filter, config=config)
     return rerank_chunks(query, chunk_ids, config=config, chunk_lookup=chunk_lookup)[:num_results]

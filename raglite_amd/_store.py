@@ -79,6 +79,7 @@ class StoreImage:
     docs: list[str] = field(default_factory=list)
     metadata: list[dict] = field(default_factory=list)
     query_adapter: np.ndarray | None = None
+    bodies: list[str] = field(default_factory=list)           # `chunk.body`: what the keyword index analyses (`_database.py:618`)
 
     def matrix(self) -> np.ndarray:
         return np.vstack(self.rows).astype(np.float32, copy=False) if self.rows else np.zeros((0, 1), np.float32)
@@ -122,6 +123,7 @@ def read_chunks(conn, only_chunk_ids: Sequence[str] | None = None) -> StoreImage
     for cid in img.chunk_ids:
         headings, body, md = meta.get(cid, ("", "", {}))
         img.docs.append(chunk_text(headings, body, md))
+        img.bodies.append(body or "")
         img.metadata.append(md)
     return img
 

@@ -2902,3 +2902,177 @@ int rl_time_kernel(rl_index* idx, int kind, const float* q_dev, int32_t nq, int3
 }
 
 }  // extern "C"
+
+// ---- BM25 keyword search (include/raglite_hip.h; kernels in keyword.hip) -------------------------------------------------------
+struct rl_keyword_index {
+    int32_t n_terms = 0;
+    int64_t n_postings = 0;
+    int64_t n_chunks = 0;
+    int n_cu = 256;
+    rl::DevArray<int64_t> term_off;     // [n_terms + 1]
+    rl::DevArray<int32_t> post_chunk;   // [n_postings], ascending within a term
+    rl::DevArray<float> post_impact;    // [n_postings]
+    std::mutex mu;
+    rl::SelectWorkspace ws;
+    rl::Pool scores;                    // [B x ld] chunk scores of a (sub-)batch
+    hipStream_t last_stream = nullptr;
+    bool last_stream_set = false;
+    ~rl_keyword_index() { rl::select_workspace_free(ws); }
+};
+
+namespace rl {
+namespace {
+
+// The host postings as the header states them; device postings are taken as given (the kernels skip what lies outside them).
+int check_host_postings(const int64_t* term_off, int32_t n_terms, const int32_t* post_chunk, const int32_t* post_tf, const int32_t* post_term,
+                        int64_t n_postings, int64_t n_chunks) {
+    const char* who = "rl_keyword_index_create";
+    if (term_off[0] != 0 || term_off[n_terms] != n_postings)
+        return fail(RL_ERR_INVALID, std::string(who) + ": term_off must start at 0 and end at n_postings");
+    for (int32_t t = 0; t < n_terms; ++t) {
+        if (term_off[t + 1] < term_off[t]) return fail(RL_ERR_INVALID, std::string(who) + ": term_off must be ascending");
+        for (int64_t p = term_off[t]; p < term_off[t + 1]; ++p) {
+            if (post_chunk[p] < 0 || post_chunk[p] >= n_chunks) return fail(RL_ERR_INVALID, std::string(who) + ": chunk ordinal out of range");
+            if (p > term_off[t] && post_chunk[p] <= post_chunk[p - 1])
+                return fail(RL_ERR_INVALID, std::string(who) + ": the chunks of a term must be strictly ascending");
+            if (post_tf[p] < 1) return fail(RL_ERR_INVALID, std::string(who) + ": term frequencies must be >= 1");
+            if (post_term[p] != t) return fail(RL_ERR_INVALID, std::string(who) + ": post_term disagrees with term_off");
+        }
+    }
+    return RL_OK;
+}
+
+}  // namespace
+}  // namespace rl
+
+extern "C" {
+
+int rl_keyword_index_create(rl_keyword_index** out, const int64_t* term_off, int32_t n_terms, const int32_t* post_chunk, const int32_t* post_tf,
+                            const int32_t* post_term, int64_t n_postings, const float* idf, const float* nrm, int64_t n_chunks, int mem,
+                            void* stream) {
+    const char* who = "rl_keyword_index_create";
+    if (!out) return fail(RL_ERR_INVALID, "rl_keyword_index_create: null output handle");
+    *out = nullptr;
+    if (n_terms < 0 || n_postings < 0 || n_chunks < 0) return fail(RL_ERR_INVALID, "rl_keyword_index_create: negative size");
+    if (n_chunks >= (int64_t)0x7fffffff - 1) return fail(RL_ERR_UNSUPPORTED, "rl_keyword_index_create: more than 2^31-2 chunks");
+    if (!term_off || (n_postings > 0 && (!post_chunk || !post_tf || !post_term)) || (n_terms > 0 && !idf) || (n_chunks > 0 && !nrm))
+        return fail(RL_ERR_INVALID, "rl_keyword_index_create: null argument");
+    if (mem != RL_MEM_HOST && mem != RL_MEM_DEVICE) return fail(RL_ERR_INVALID, "rl_keyword_index_create: bad mem");
+    if (mem == RL_MEM_HOST) RL_TRY(check_host_postings(term_off, n_terms, post_chunk, post_tf, post_term, n_postings, n_chunks));
+    hipStream_t s = as_stream(stream);
+    std::unique_ptr<rl_keyword_index> kw(new rl_keyword_index());
+    kw->n_terms = n_terms;
+    kw->n_postings = n_postings;
+    kw->n_chunks = n_chunks;
+    {
+        std::lock_guard<std::mutex> lock(g_default_opts_mu);
+        kw->ws.block_route = (int)g_default_opts.v[RL_OPT_TOPK_BLOCK];
+    }
+    int dev = 0;
+    RL_HIP(hipGetDevice(&dev));
+    hipDeviceProp_t prop;
+    RL_HIP(hipGetDeviceProperties(&prop, dev));
+    kw->n_cu = prop.multiProcessorCount;
+    const size_t np = (size_t)n_postings;
+    RL_TRY(kw->term_off.alloc((size_t)(n_terms + 1) * sizeof(int64_t), who));
+    RL_TRY(kw->post_chunk.alloc(std::max<size_t>(np * sizeof(int32_t), 16), who));
+    RL_TRY(kw->post_impact.alloc(std::max<size_t>(np * sizeof(float), 16), who));
+    RL_HIP(hipMemcpyAsync(kw->term_off, term_off, (size_t)(n_terms + 1) * sizeof(int64_t),
+                          mem == RL_MEM_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, s));
+    if (np) RL_HIP(hipMemcpyAsync(kw->post_chunk, post_chunk, np * sizeof(int32_t), mem == RL_MEM_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, s));
+    DevBuf t_tf, t_term, t_idf, t_nrm;
+    const int32_t *d_tf, *d_term;
+    const float *d_idf, *d_nrm;
+    RL_TRY(stage_in(post_tf, np, mem, s, t_tf, &d_tf));
+    RL_TRY(stage_in(post_term, np, mem, s, t_term, &d_term));
+    RL_TRY(stage_in(idf, (size_t)n_terms, mem, s, t_idf, &d_idf));
+    RL_TRY(stage_in(nrm, (size_t)n_chunks, mem, s, t_nrm, &d_nrm));
+    RL_TRY(launch_bm25_impact(kw->post_chunk, d_tf, d_term, d_idf, d_nrm, n_postings, n_terms, n_chunks, kw->post_impact, s));
+    RL_HIP(hipStreamSynchronize(s));  // the staging buffers and the caller's arrays may go away after return
+    g_pinned.drain();
+    *out = kw.release();
+    return RL_OK;
+}
+
+int rl_keyword_index_destroy(rl_keyword_index* kw) {
+    if (!kw) return RL_OK;
+    delete kw;
+    return RL_OK;
+}
+
+int rl_keyword_index_info(const rl_keyword_index* kw, int32_t* n_terms, int64_t* n_postings, int64_t* n_chunks) {
+    if (!kw) return fail(RL_ERR_INVALID, "rl_keyword_index_info: null index");
+    if (n_terms) *n_terms = kw->n_terms;
+    if (n_postings) *n_postings = kw->n_postings;
+    if (n_chunks) *n_chunks = kw->n_chunks;
+    return RL_OK;
+}
+
+int rl_keyword_search(rl_keyword_index* kw, const int64_t* q_off, const int32_t* q_terms, int32_t n_queries, int32_t k,
+                      const uint32_t* chunk_filter, float* out_scores, int32_t* out_chunks, int32_t* out_counts, int mem, void* stream) {
+    if (!kw) return fail(RL_ERR_INVALID, "rl_keyword_search: null index");
+    if (n_queries < 0 || k < 1) return fail(RL_ERR_INVALID, "rl_keyword_search: n_queries must be >= 0 and k >= 1");
+    if (k > K_MAX) return fail(RL_ERR_UNSUPPORTED, "rl_keyword_search: k must be <= 2048");
+    if (n_queries == 0) return RL_OK;
+    if (!q_off) return fail(RL_ERR_INVALID, "rl_keyword_search: null q_off");
+    if (!out_scores || !out_chunks) return fail(RL_ERR_INVALID, "rl_keyword_search: null output");
+    int64_t n_q_terms = 0;
+    if (mem == RL_MEM_HOST) {
+        if (q_off[0] != 0) return fail(RL_ERR_INVALID, "rl_keyword_search: q_off must start at 0");
+        for (int32_t b = 0; b < n_queries; ++b)
+            if (q_off[b + 1] < q_off[b]) return fail(RL_ERR_INVALID, "rl_keyword_search: q_off must be ascending");
+        n_q_terms = q_off[n_queries];
+        if (n_q_terms > 0 && !q_terms) return fail(RL_ERR_INVALID, "rl_keyword_search: null q_terms");
+    } else if (!q_terms) {
+        return fail(RL_ERR_INVALID, "rl_keyword_search: null q_terms");
+    }
+    hipStream_t s = as_stream(stream);
+    std::lock_guard<std::mutex> lock(kw->mu);
+    if (kw->last_stream_set && kw->last_stream != s) RL_HIP(hipStreamSynchronize(kw->last_stream));
+    kw->last_stream = s;
+    kw->last_stream_set = true;
+    const int64_t n = kw->n_chunks;
+    const size_t n_out = (size_t)n_queries * k;
+    DevBuf t_off, t_terms, t_f, t_s, t_c, t_n;
+    const int64_t* d_off;
+    const int32_t* d_terms;
+    const uint32_t* d_f = nullptr;
+    float* d_s;
+    int32_t *d_c, *d_n;
+    RL_TRY(stage_in(q_off, (size_t)n_queries + 1, mem, s, t_off, &d_off));
+    if (mem == RL_MEM_HOST) RL_TRY(stage_in(q_terms, (size_t)n_q_terms, mem, s, t_terms, &d_terms));
+    else d_terms = q_terms;
+    if (chunk_filter) RL_TRY(stage_in(chunk_filter, (size_t)((n + 31) / 32), mem, s, t_f, &d_f));
+    RL_TRY(stage_out_begin(out_scores, n_out, mem, t_s, &d_s));
+    RL_TRY(stage_out_begin(out_chunks, n_out, mem, t_c, &d_c));
+    if (out_counts) RL_TRY(stage_out_begin(out_counts, (size_t)n_queries, mem, t_n, &d_n));
+    else {
+        RL_TRY(t_n.alloc((size_t)n_queries * sizeof(int32_t)));
+        d_n = t_n.as<int32_t>();
+    }
+    if (n == 0) {  // no chunks: every slot is padding
+        RL_TRY(launch_fill_f32(d_s, -std::numeric_limits<float>::infinity(), (int64_t)n_out, s));
+        RL_HIP(hipMemsetAsync(d_c, 0xff, n_out * sizeof(int32_t), s));
+    } else {
+        const int64_t ld = (n + 3) & ~int64_t(3);
+        // (a sub-batch is one grid row per query: at most 65535 of them)
+        const int32_t batch = (int32_t)std::max<int64_t>(1, std::min<int64_t>({(int64_t)n_queries, int64_t(65535),
+                                                                                (int64_t)(SCORE_BATCH_BYTES / ((size_t)ld * 4))}));
+        RL_TRY(kw->scores.reserve((size_t)batch * ld * sizeof(float)));
+        for (int32_t b0 = 0; b0 < n_queries; b0 += batch) {
+            const int32_t nb = std::min<int32_t>(batch, n_queries - b0);
+            RL_TRY(launch_bm25_score(kw->term_off, kw->post_chunk, kw->post_impact, kw->n_terms, n, d_off + b0, d_terms, nb, d_f,
+                                     bm25_tile(n, nb, kw->n_cu), kw->scores.as<float>(), ld, s));
+            RL_TRY(launch_topk(kw->scores.as<float>(), nb, n, ld, k, kw->ws, d_s + (int64_t)b0 * k, d_c + (int64_t)b0 * k, s));
+        }
+        RL_TRY(launch_fix_masked(d_s, d_c, (int64_t)n_out, s));  // chunks without a query term are "no hit": (-inf, -1)
+    }
+    RL_TRY(launch_bm25_count(d_s, n_queries, k, d_n, s));
+    RL_TRY(stage_out_end(out_scores, n_out, mem, s, t_s));
+    RL_TRY(stage_out_end(out_chunks, n_out, mem, s, t_c));
+    if (out_counts) RL_TRY(stage_out_end(out_counts, (size_t)n_queries, mem, s, t_n));
+    if (mem == RL_MEM_DEVICE && !out_counts) RL_HIP(hipStreamSynchronize(s));  // t_n dies with this frame
+    return finish(mem, s);
+}
+
+}  // extern "C"

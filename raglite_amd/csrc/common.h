@@ -312,6 +312,19 @@ int launch_mask_scores(float* scores, int32_t nb, int64_t n, int64_t ld, const u
 int launch_fix_masked(const float* scores, int32_t* ids, int64_t count, hipStream_t s);
 int launch_popcount(const uint32_t* bits, int64_t n, unsigned long long* out_dev, hipStream_t s);
 
+// keyword.hip: BM25 over term-major postings (term_off [n_terms + 1], post_chunk ascending within a term, post_impact)
+constexpr int32_t BM25_TILE_MAX = 8192;  // chunk scores per block, in LDS: 32 KiB, four blocks per CU
+// post_impact[p] = idf[t] * ((tf * 2.2f) / (tf + nrm[c])) for posting p = (t, c, tf), float32 rounded at every step
+int launch_bm25_impact(const int32_t* post_chunk, const int32_t* post_tf, const int32_t* post_term, const float* idf, const float* nrm,
+                       int64_t n_postings, int32_t n_terms, int64_t n_chunks, float* post_impact, hipStream_t s);
+int32_t bm25_tile(int64_t n_chunks, int32_t n_queries, int n_cu);  // the tile launch_bm25_score is given
+// scores[b * ld + c] (c < n_chunks): the BM25 score of chunk c for query b (terms q_terms[q_off[b] .. q_off[b + 1]), ascending),
+// -inf where the chunk has none of them or its filter bit is clear
+int launch_bm25_score(const int64_t* term_off, const int32_t* post_chunk, const float* post_impact, int32_t n_terms, int64_t n_chunks,
+                      const int64_t* q_off, const int32_t* q_terms, int32_t n_queries, const uint32_t* filter, int32_t tile, float* scores,
+                      int64_t ld, hipStream_t s);
+int launch_bm25_count(const float* sel, int32_t n_queries, int32_t k, int32_t* counts, hipStream_t s);  // finite entries per selected row
+
 // adapter_fit.hip: device half of update_query_adapter (best row per (query, chunk), row gather)
 int launch_chunk_best_rows(const void* E, bool f16, int32_t dim, const float* Q, const int64_t* offsets,
                            int64_t n_chunks, const int32_t* cand, int32_t n_cand, int64_t n_items, int32_t* out_rows,
