@@ -256,6 +256,13 @@ typedef enum {
     RL_OPT_F16_EXACT = 21, RL_OPT_LAZY_IMAGES = 22, RL_OPT_FUSED_PP_SAMPLE = 23,
     RL_OPT_LIST_SELECT = 24, RL_OPT_HI_FEW = 25, RL_OPT_TOPK_BLOCK = 26, RL_OPT_HI_PIVOT = 27, RL_OPT_COUNT_ = 28
 } rl_option;
+/* Kernel SCHEDULE switches: keys of the same calls, numbered from 64 on (the route options above stay one contiguous range).  They change
+ * where and when workgroups run, never what they compute: results are bit-identical under every value.
+ *   key                         values (default)   what it schedules
+ *   RL_OPT_PP_SCHEDULE          0 / 1 (1)          the sixteen-query MaxSim pass (maxsim_pp.hip): 1 = the passes over one row range run side by
+ *                                                  side on one XCD, so one HBM read of the corpus serves all of them; 0 = pass after pass, each
+ *                                                  pass streaming the whole HI image (raglite_amd/csrc/pp_schedule.h) */
+enum { RL_OPT_PP_SCHEDULE = 64 };
 int rl_set_default_option(int key, int64_t value);
 int rl_get_default_option(int key, int64_t* value);
 int rl_index_set_option(rl_index* index, int key, int64_t value);

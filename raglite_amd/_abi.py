@@ -29,6 +29,13 @@ OPTIONS = {
     "image_headroom_mb": 15, "arithmetic": 16, "exact_kth_threshold": 17, "fused_two_rounds": 18,
     "keep_hi_plane": 19, "pairs_packed": 20, "f16_exact": 21, "lazy_images": 22, "fused_pp_sample": 23, "list_select": 24, "hi_few": 25, "topk_block": 26, "hi_pivot": 27,
 }
+# kernel schedule switches (include/raglite_hip.h, after rl_option): keys of the same calls, numbered from 64 on; results never depend on them
+SCHEDULE_OPTIONS = {"pp_schedule": 64}
+
+
+def option_key(name: str) -> int:
+    """The key of a route option or of a schedule switch."""
+    return OPTIONS[name] if name in OPTIONS else SCHEDULE_OPTIONS[name]
 
 c_void_p, c_int, c_i32, c_i64, c_u64, c_size_t = C.c_void_p, C.c_int, C.c_int32, C.c_int64, C.c_uint64, C.c_size_t
 c_double, c_char_p = C.c_double, C.c_char_p

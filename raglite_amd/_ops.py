@@ -110,12 +110,12 @@ def set_device(device: int) -> None:
 # ----------------------------------------------------------------------------------------------
 def set_default_option(name: str, value: int) -> None:
     """`rl_set_default_option`: the start value of a route option for every index created AFTERWARDS in this process."""
-    check(lib().rl_set_default_option(_abi.OPTIONS[name], int(value)))
+    check(lib().rl_set_default_option(_abi.option_key(name), int(value)))
 
 
 def get_default_option(name: str) -> int:
     v = C.c_int64(0)
-    check(lib().rl_get_default_option(_abi.OPTIONS[name], C.byref(v)))
+    check(lib().rl_get_default_option(_abi.option_key(name), C.byref(v)))
     return int(v.value)
 
 
@@ -361,11 +361,11 @@ class DeviceIndex:
     def set_option(self, name: str, value: int) -> None:
         """`rl_index_set_option`: choose a route of this index (`_abi.OPTIONS` names the keys; include/raglite_hip.h "options" says what
         each one does).  Results never depend on an option; speed and memory do."""
-        check(lib().rl_index_set_option(self._handle, _abi.OPTIONS[name], int(value)))
+        check(lib().rl_index_set_option(self._handle, _abi.option_key(name), int(value)))
 
     def get_option(self, name: str) -> int:
         v = C.c_int64(0)
-        check(lib().rl_index_get_option(self._handle, _abi.OPTIONS[name], C.byref(v)))
+        check(lib().rl_index_get_option(self._handle, _abi.option_key(name), C.byref(v)))
         return int(v.value)
 
     def options(self, **kv: int):

@@ -225,7 +225,7 @@ constexpr size_t SCORE_BATCH_BYTES = size_t(8) << 30;  // cap of the [B x N] sco
 // Route options (raglite_hip.h "options"): per index, copied from the process-wide defaults when the index is created.  The library
 // reads no environment variable.
 struct Options {
-    int64_t v[RL_OPT_COUNT_];
+    int64_t v[RL_OPT_PP_SCHEDULE + 1];  // (keys 1 .. RL_OPT_COUNT_ - 1, and the schedule switches from 64 on)
     Options() {
         for (auto& x : v) x = 0;
         v[RL_OPT_HI_SEARCH] = v[RL_OPT_HI_MAXSIM] = v[RL_OPT_HI_PRODUCTS] = v[RL_OPT_PP_PASS] = v[RL_OPT_FUSED_TOPK] = v[RL_OPT_FUSED_HI] = 1;
@@ -233,6 +233,7 @@ struct Options {
         v[RL_OPT_EXACT_KTH_THRESHOLD] = v[RL_OPT_FUSED_TWO_ROUNDS] = v[RL_OPT_KEEP_HI_PLANE] = v[RL_OPT_F16_EXACT] = v[RL_OPT_LAZY_IMAGES] = v[RL_OPT_FUSED_PP_SAMPLE] = v[RL_OPT_LIST_SELECT] = v[RL_OPT_HI_FEW] = 1;
         v[RL_OPT_TOPK_BLOCK] = v[RL_OPT_PAIRS_PACKED] = 2;
         v[RL_OPT_HI_PIVOT] = 1;
+        v[RL_OPT_PP_SCHEDULE] = 1;
         v[RL_OPT_IMAGE_HEADROOM_MB] = -1;
         v[RL_OPT_ARITHMETIC] = RL_ARITH_AUTO;
     }
@@ -240,11 +241,13 @@ struct Options {
 };
 std::mutex g_default_opts_mu;
 Options g_default_opts;
+bool option_key_ok(int key) { return (key >= 1 && key < RL_OPT_COUNT_) || key == RL_OPT_PP_SCHEDULE; }
 bool option_value_ok(int key, int64_t value) {
     switch (key) {
         case RL_OPT_HI_SEARCH: case RL_OPT_HI_MAXSIM: case RL_OPT_PP_PASS: case RL_OPT_FUSED_TOPK: case RL_OPT_FUSED_HI: case RL_OPT_FUSED_PP:
         case RL_OPT_GEMM_PASS: case RL_OPT_QUERY_PAIRS: case RL_OPT_PLANES_GEMM: case RL_OPT_KEEP_IMAGE: case RL_OPT_KEEP_HI:
         case RL_OPT_EXACT_KTH_THRESHOLD: case RL_OPT_FUSED_TWO_ROUNDS: case RL_OPT_KEEP_HI_PLANE: case RL_OPT_F16_EXACT: case RL_OPT_LAZY_IMAGES: case RL_OPT_FUSED_PP_SAMPLE: case RL_OPT_LIST_SELECT: case RL_OPT_HI_FEW: case RL_OPT_HI_PIVOT:
+        case RL_OPT_PP_SCHEDULE:
             return value == 0 || value == 1;
         case RL_OPT_TOPK_BLOCK: case RL_OPT_PAIRS_PACKED: return value >= 0 && value <= 2;
         case RL_OPT_HI_PRODUCTS: return value == 1 || value == 2;
@@ -1058,7 +1061,7 @@ int rl_set_default_option(int key, int64_t value) {
 }
 
 int rl_get_default_option(int key, int64_t* value) {
-    if (!value || key < 1 || key >= RL_OPT_COUNT_) return fail(RL_ERR_INVALID, "rl_get_default_option: unknown key");
+    if (!value || !option_key_ok(key)) return fail(RL_ERR_INVALID, "rl_get_default_option: unknown key");
     std::lock_guard<std::mutex> lock(g_default_opts_mu);
     *value = g_default_opts.v[key];
     return RL_OK;
@@ -1085,7 +1088,7 @@ int rl_index_set_option(rl_index* idx, int key, int64_t value) {
 }
 
 int rl_index_get_option(rl_index* idx, int key, int64_t* value) {
-    if (!idx || !value || key < 1 || key >= RL_OPT_COUNT_) return fail(RL_ERR_INVALID, "rl_index_get_option: null argument or unknown key");
+    if (!idx || !value || !option_key_ok(key)) return fail(RL_ERR_INVALID, "rl_index_get_option: null argument or unknown key");
     std::lock_guard<std::mutex> lock(idx->mu);
     *value = idx->opt.v[key];
     return RL_OK;
@@ -2178,7 +2181,8 @@ int hi_batch_approx(rl_index* idx, const float* d_q, int32_t nq, int32_t n_queri
     // (round 4: ONE launch for all of the batch's passes -- grid row = pass -- so that a pass starts on the CUs the previous one leaves)
     if (pp)
         RL_TRY(launch_maxsim_pp(approx_image(idx), idx->n_rows, idx->dim, idx->qplanes.p, n_queries, 0, n_gemm, nq, idx->row_to_chunk,
-                                idx->offsets, idx->ends.as<uint32_t>(), sc, ld, idx->n_cu, s, approx_scale(idx)));
+                                idx->offsets, idx->ends.as<uint32_t>(), sc, ld, idx->n_cu, s, approx_scale(idx), nullptr,
+                                (int)idx->opt.v[RL_OPT_PP_SCHEDULE]));
     for (int32_t b = 0; !pp && b < n_gemm; b += GEMM_PASS_QUERIES) {
         const int32_t n_q = std::min<int32_t>(GEMM_PASS_QUERIES, n_gemm - b);
         RL_TRY(launch_maxsim_gemm(approx_image(idx), idx->n_rows, idx->dim, idx->qplanes.p, n_queries, b, n_q, nq, idx->row_to_chunk,
@@ -2616,7 +2620,8 @@ int rl_maxsim_approx_scores(rl_index* idx, const float* query_vecs, int32_t n_qu
         const int32_t n_q = std::min<int32_t>(per, n_queries - b);
         if (kernel == 0)
             RL_TRY(launch_maxsim_pp(approx_image(idx), idx->n_rows, idx->dim, idx->qplanes.p, n_queries, b, n_q, nq, idx->row_to_chunk, idx->offsets,
-                                    idx->ends.as<uint32_t>(), d_o + (int64_t)b * ld, ld, idx->n_cu, s, approx_scale(idx)));
+                                    idx->ends.as<uint32_t>(), d_o + (int64_t)b * ld, ld, idx->n_cu, s, approx_scale(idx), nullptr,
+                                    (int)idx->opt.v[RL_OPT_PP_SCHEDULE]));
         else
             RL_TRY(launch_maxsim_gemm(approx_image(idx), idx->n_rows, idx->dim, idx->qplanes.p, n_queries, b, n_q, nq, idx->row_to_chunk, idx->offsets,
                                       idx->ends.as<uint32_t>(), d_o + (int64_t)b * ld, ld, idx->n_cu, s, approx_scale(idx), true, nullptr, true));
@@ -2849,7 +2854,7 @@ int rl_time_kernel(rl_index* idx, int kind, const float* q_dev, int32_t nq, int3
     for (int i = 0; i < iters && st == RL_OK; ++i) {
         if (kind == 7) st = launch_maxsim_pp(approx_image(idx), idx->n_rows, idx->dim, idx->qplanes.p, pp_n, 0, pp_n,
                                              pp_vec, idx->row_to_chunk, idx->offsets, idx->ends.as<uint32_t>(), idx->scores.as<float>(), ldc,
-                                             idx->n_cu, s, approx_scale(idx));
+                                             idx->n_cu, s, approx_scale(idx), nullptr, (int)idx->opt.v[RL_OPT_PP_SCHEDULE]);
         else if (kind == 3) st = gemm_pass(idx, nq / GEMM_PASS_QUERIES, GEMM_PASS_QUERIES, 0, GEMM_PASS_QUERIES, idx->scores.as<float>(), ldc, s);
         else if (kind == 8) {
             const auto& r = idx->replay;

@@ -12,7 +12,7 @@
 //   * tile = 128 corpus rows x 512 query vectors (16 queries), K slabs of 32; 8 waves, wave w owns queries 2w and 2w + 1: 128
 //     accumulator registers (2 queries x 2 blocks of 16 vectors x 8 blocks of 16 rows).  The CORPUS block is the A operand of
 //     v_mfma_f32_16x16x32_f16: lane (g, n) of accumulator register u holds row 4 g + u of the block, query vector n of the register's set;
-//   * the CORPUS slabs (8 KiB, `nt`) go through an LDS ring of 8 by `global_load_lds_dwordx4`, one 1-KiB piece per wave and slab, the
+//   * the CORPUS slabs (8 KiB; MODES 1 and 2: `nt`) go through an LDS ring of 8 by `global_load_lds_dwordx4`, one 1-KiB piece per wave and slab, the
 //     pieces of slab g + 6 issued at the top of slab g (slot (g + 6) % 8 is neither slab g's, which a lagging wave may still read, nor
 //     g + 1's);
 //   * the QUERY fragments (32 KiB per slab, L2-resident) go STRAIGHT TO REGISTERS: a wave owns its two queries, nobody else reads their
@@ -51,6 +51,7 @@
 #include <utility>
 
 #include "common.h"
+#include "pp_schedule.h"
 
 namespace rl {
 
@@ -74,11 +75,17 @@ __device__ __forceinline__ int64_t pp_uniform_i64(int64_t v) {
 }
 
 // One 1-KiB piece HBM -> LDS: lane i copies 16 B from src + 16 i to lds + 16 i.  Invisible to the compiler's vmcnt bookkeeping
-// (asynchronous; certified by the explicit waits below).  `nt`: streamed once.
+// (asynchronous; certified by the explicit waits below).  MODE 0 (NT = false): no cache hint -- under the co-scheduled order
+// (pp_schedule.h) the workgroups of the other passes over the same rows, on the same XCD, read the piece again shortly after, and `nt`
+// or `sc1` let it leave the L2 sooner: both measured slower.  MODES 1 and 2 keep `nt` (streamed once per grid row).
+template <bool NT>
 __device__ __forceinline__ void pp_dma(uint32_t lds, const char* src, uint32_t lane16) {
     const uint32_t l = __builtin_amdgcn_readfirstlane(lds);
     const char* const p = reinterpret_cast<const char*>(pp_uniform_i64(reinterpret_cast<int64_t>(src)));
-    asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2 nt" ::"s"(l), "v"(lane16), "s"(p) : "memory", "m0");
+    if constexpr (NT)
+        asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2 nt" ::"s"(l), "v"(lane16), "s"(p) : "memory", "m0");
+    else
+        asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2" ::"s"(l), "v"(lane16), "s"(p) : "memory", "m0");
 }
 
 // One LDS fragment read (64 lanes x 16 B) into 4 VGPRs, invisible to the compiler's lgkmcnt bookkeeping -- its own waits would sit in
@@ -136,7 +143,15 @@ __global__ __launch_bounds__(512, 2) void maxsim_pp_kernel(const char* __restric
     if (run_if && __builtin_amdgcn_readfirstlane((int)*run_if) == 0) return;  // whole grid: a guarded launch that is not needed
     const int lane = threadIdx.x & 63;
     const int wv = wave_id();
-    const int64_t G = gridDim.x, b = blockIdx.x;
+    // MODE 0: row range b of G and pass qt of this workgroup -- pp_schedule.h: blockIdx itself, or the co-scheduled order of a 1-D grid
+    int64_t G = gridDim.x, b = blockIdx.x;
+    int qt = (int)blockIdx.y;
+    if constexpr (!GROUPS) {
+        const PpSlot m = pp_schedule((int32_t)blockIdx.x, (int32_t)blockIdx.y, (int32_t)gridDim.x, (int32_t)gridDim.y, (n_q + PP_QPP - 1) / PP_QPP);
+        G = m.ranges;
+        b = m.range;
+        qt = m.pass;
+    }
     // MODE 0: chunk-aligned row range of this workgroup (as in maxsim_gemm.hip): first chunk boundary at or after n_rows * b / G.
     auto boundary = [&](int64_t t) -> int64_t {
         if (t <= 0) return 0;
@@ -172,9 +187,8 @@ __global__ __launch_bounds__(512, 2) void maxsim_pp_kernel(const char* __restric
             return (org >> 4) + t * PP_NBLK;
         }
     };
-    // query tile: MODE 2 -- 16 groups of 32 queries; MODE 0 -- the launch's passes (16 queries each) as grid rows: ONE launch for a batch's
-    // passes instead of one per pass, so a pass's workgroups start on the CUs the previous pass's leave instead of behind a launch boundary
-    const int qt = (int)blockIdx.y;
+    // query tile: MODE 2 -- 16 groups of 32 queries; MODE 0 -- the pass (16 queries): ONE launch for a batch's passes instead of one per pass,
+    // so a pass's workgroups start on the CUs the previous pass's leave instead of behind a launch boundary (pp_schedule.h: their order)
     const int q_base = GROUPS ? 0 : PP_QPP * qt;  // first query of this workgroup's pass
     const int total = nt * nslab;               // K slabs this workgroup streams
     const int32_t last_blk = (int32_t)((n_rows + 15) >> 4) - 1;
@@ -211,7 +225,7 @@ __global__ __launch_bounds__(512, 2) void maxsim_pp_kernel(const char* __restric
             int32_t blk = SCORES ? tile_blk(t) + wv : blk_org + t * PP_NBLK;
             blk = blk < last_blk ? blk : last_blk;  // past the image: harmless re-read of the last block, never emitted
             const char* src = planes + pp_uniform_i64((int64_t)blk * slab_bytes + (int64_t)fc_s * 1024);
-            pp_dma(lds_base + (uint32_t)(fc_slot * PP_CSLOT + wv * 1024), src, lane16);
+            pp_dma<GROUPS>(lds_base + (uint32_t)(fc_slot * PP_CSLOT + wv * 1024), src, lane16);
         }
         if (++fc_s == nslab) { fc_s = 0; ++fc_r; }
         fc_slot = fc_slot + 1 == PP_DC ? 0 : fc_slot + 1;
@@ -767,14 +781,16 @@ __global__ __launch_bounds__(512, 2) void maxsim_pp_kernel(const char* __restric
 // Sixteen queries per pass over the image; n_q > 16: ceil(n_q / 16) passes in ONE launch (grid rows).
 int launch_maxsim_pp(const void* image, int64_t n_rows, int32_t dim, const void* qbuf, int32_t n_queries, int32_t first, int32_t n_q,
                      int32_t nq, const int32_t* row_to_chunk, const int64_t* chunk_offsets, const uint32_t* ends_bits, float* out,
-                     int64_t out_stride, int n_cu, hipStream_t s, float split_scale, const uint32_t* run_if) {
+                     int64_t out_stride, int n_cu, hipStream_t s, float split_scale, const uint32_t* run_if, int schedule) {
     if (nq < 1 || nq > 32 || n_q < 1 || n_q > PP_QPP * 4096 || n_rows < 1 || first < 0 || first + n_q > n_queries) return RL_ERR_UNSUPPORTED;
     if (dim % 32 || dim < 256 || !(split_scale > 0.f) || !image || !ends_bits) return RL_ERR_UNSUPPORTED;
     const int32_t nslab = dim / 32;
     const char* qfrag = static_cast<const char*>(qbuf) + (size_t)first * nslab * 4096;
     const float* qmeta = reinterpret_cast<const float*>(static_cast<const char*>(qbuf) + (size_t)n_queries * dim * 128) + 2 * (size_t)first;
     const int64_t tiles = (n_rows + PP_RT - 1) / PP_RT;
-    const dim3 grid((unsigned)std::max<int64_t>(1, std::min<int64_t>(n_cu > 0 ? n_cu : 256, tiles)), (unsigned)((n_q + PP_QPP - 1) / PP_QPP)), blk(512);
+    const int64_t gx = std::max<int64_t>(1, std::min<int64_t>(n_cu > 0 ? n_cu : 256, tiles)), passes = (n_q + PP_QPP - 1) / PP_QPP;
+    // schedule 1: the passes over one row range side by side on one XCD (pp_schedule.h); 0: pass-major, grid row = pass
+    const dim3 grid = schedule == 1 ? dim3((unsigned)(gx * passes)) : dim3((unsigned)gx, (unsigned)passes), blk(512);
 #define RL_PP_LAUNCH(DBG_)                                                                                                                 \
     hipLaunchKernelGGL((maxsim_pp_kernel<DBG_, 0, false>), grid, blk, 0, s, static_cast<const char*>(image), n_rows, nslab, qfrag, qmeta, n_q, row_to_chunk, \
                        chunk_offsets, ends_bits, out, out_stride, 1.0f / split_scale, run_if, PpRows{})
