@@ -1,7 +1,12 @@
 """bench.py -- the headline metric of BASELINE.json on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]   (N > 1: launches its own N ranks over 127.0.0.1)
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]   (N > 1: launches its own N ranks over 127.0.0.1)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run does what the headline needs and nothing else: it builds the corpus and the index, runs W untimed and K timed steps,
+writes --dump-outputs and prints the result line (metric, value, unit, ms_per_step, dtype, config, index_memory).  --full adds
+every other measurement and check listed below, after the timed steps; they take minutes (the CPU baseline and the side
+workloads most of it).
 
 Workload (config.workload): MaxSim late-interaction retrieval, 32 query vectors x 1,000,000 chunk
 vectors, d = 1024, fp32, exact top-100 chunks -- the shape `metric` is quoted on.  The corpus is
@@ -24,9 +29,8 @@ its exact local top-k, (QB, k, 2) int32, with the device merge.  value = queries
 N > 1: the 1 M-row corpus is sharded by chunk across the ranks (strong scaling on the metric's own
 shape); every rank receives the same queries.
 
-Extra objects in the JSON line (rank 0; all but `roofline` at N = 1 only):
+Extra objects in the JSON line, --full only (rank 0; all but `roofline` and `rank_split` at N = 1 only):
   roofline      dominant kernel, HIP-event timed on its launch stream; `sustained`: the fp16 MFMA rate of this box measured in the same run
-  fraction_check / bench_schema  every printed fraction verified to lie in (0, 1] before the line leaves (fraction_violations)
   exact_fp32    the same workload with RL_ARITH_FP32_EXACT (v_mfma_f32_16x16x4_f32 chain), >= 5 timed steps
   f16_stored    the same corpus rounded to and stored as fp16 (the reference's pgvector halfvec), own workload name
   f16_queries   ... and the queries as fp16 values too (what embed_strings returns): the one-product pass is exact, its top-k is the result
@@ -38,6 +42,11 @@ Extra objects in the JSON line (rank 0; all but `roofline` at N = 1 only):
                 candidates per query, fallback, float64 parity at 1e-4 absolute
                 (configs and raglite_shaped: their scalars only; the whole records are one `{"side_workloads": ...}` line on stderr)
   candidates_per_query / fallback_steps  what the bound-filtered pipeline did on the headline's own data
+  rank_split    N > 1 (or --split): where a rank's step goes -- passes / other local work / the exchanges
+Every line, plain or --full:
+  fraction_check / bench_schema  every printed fraction verified to lie in (0, 1] before the line leaves (fraction_violations)
+  score_tolerance  the score bar; the measured errors next to it with --full
+  full          whether the line is a --full one
 
 --dump-outputs DIR: after the timed steps, what the last one returned (scores.npy, chunk_ids.npy; see dump_outputs).
 """
@@ -169,19 +178,24 @@ def main() -> None:
     ap.add_argument("--storage", choices=("f32", "f16"), default="f32", help=argparse.SUPPRESS)
     ap.add_argument("--no-f16", action="store_true", help="skip the fp16-stored block (the reference's storage dtype, own workload name)")
     ap.add_argument("--queries-per-step", type=int, default=QUERIES_PER_STEP, help=argparse.SUPPRESS)
-    # A/B: the exact fp32 MFMA chain as the HEADLINE arithmetic (the default run reports it in `exact_fp32` anyway)
+    # A/B: the exact fp32 MFMA chain as the HEADLINE arithmetic (a --full run reports it in `exact_fp32` anyway)
     ap.add_argument("--exact-fp32", action="store_true", help=argparse.SUPPRESS)
     # Test hooks for the N > 1 code path on a ONE-GPU box (scripts/test_multirank_one_gpu.sh): every rank uses cuda:0
     # and the collective runs over gloo.  Never used by the driver.
-    ap.add_argument("--split", action="store_true", help="also at N = 1: per-rank split of a step into passes / other local work / exchange")
+    ap.add_argument("--split", action="store_true", help="with --full, also at N = 1: per-rank split of a step into passes / other local work / exchange")
     ap.add_argument("--opt", action="append", default=[], metavar="NAME=VALUE",
                     help="route option set as a process-wide default before any index exists (A/B runs; see include/raglite_hip.h 'options')")
     ap.add_argument("--same-gpu", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--backend", default="nccl", help=argparse.SUPPRESS)
     ap.add_argument("--dump-outputs", metavar="DIR", help="write what the last timed step returned as DIR/<name>.npy (see dump_outputs)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also every other measurement and check (roofline, filter statistics, exact fp32, fp16 storage, "
+                         "one query per call, recall against the NumPy oracle, CPU baseline, BASELINE configs, RAGLite-shaped corpora, rank_split)")
     args = ap.parse_args()
     if args.steps < 1 or args.warmup < 0:
         ap.error("--steps must be at least 1 and --warmup at least 0")
+    if args.split and not args.full:
+        ap.error("--split is one of the --full measurements: add --full")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # `python bench.py --gpus N` on its own: become N ranks (one process per GPU) through torch.distributed.run, exactly the
@@ -297,26 +311,6 @@ def main() -> None:
     if args.dump_outputs and rank == 0:  # (every rank holds the same merged result)
         dump_outputs(Path(args.dump_outputs), last)
 
-    # How the data decided the bound-filtered pipeline (outside the timed region: reading the counters synchronises).  The steps cycle
-    # through n_batches distinct query batches, so one more run of each tells what every timed step did.
-    filt = []
-    for i in range(min(n_batches, args.steps + args.warmup)):
-        step(i)
-        filt.append(index.filter_stats())
-    fence()
-    if filt and filt[0]["kind"] != "none":
-        fallback_steps = sum(int(filt[i % len(filt)]["fallback"]) for i in range(args.steps))
-        filter_block = {
-            "kind": filt[0]["kind"],
-            "candidates_per_query": {"mean": float(np.mean([f["candidates_per_query_mean"] for f in filt])),
-                                     "max": int(max(f["candidates_per_query_max"] for f in filt))},
-            "list_capacity": filt[0]["list_capacity"], "fallback_steps": fallback_steps, "of_steps": args.steps,
-            "note": "rank 0's shard; chunks whose approximate score is within 2m of the k-th best, re-scored exactly; fallback = the "
-                    "guarded full-precision passes ran (list overflow / unusable bound)",
-        }
-    else:
-        filter_block = {"kind": "none", "fallback_steps": 0, "of_steps": args.steps}
-
     total_queries = args.steps * qps
     exchange = ("no exchange step at N = 1" if world == 1 else
                 f"corpus sharded by chunk over {world} GPUs; per step one all-gather of every rank's k best approximate scores (one candidate threshold for all shards), one of its exact local top-k + device merge, no host sync"
@@ -340,9 +334,7 @@ def main() -> None:
                   "f16_stored": "f16 storage, f16 x f16 -> f32 MFMA"}[arithmetic],
         "data": "synthetic",
         "route_options": {"non_default": args.opt, "note": "none = the shipped defaults; set with --opt NAME=VALUE (rl_set_default_option), never from the environment"},
-        "candidates_per_query": filter_block.get("candidates_per_query"),
-        "fallback_steps": filter_block["fallback_steps"],
-        "filter": filter_block,
+        "full": args.full,
         "config": {
             "workload": f"maxsim_{NQ}x{n_rows}_d{DIM}_top{TOPK}_ragged_chunks_1to15"
                         + ("" if args.storage == "f32" else "_F16_STORED_CORPUS_not_the_baseline_config"),
@@ -360,6 +352,38 @@ def main() -> None:
                                       "--opt lazy_images=0: every image with the index, 3 x)"}
 
     result["index_memory_times_corpus"] = result["index_memory"]["times_corpus"]  # (top-level scalar: the driver's record keeps scalars)
+
+    if not args.full:  # the headline and nothing else
+        if rank == 0:
+            print(_finish(result))
+        index.close()
+        if world > 1:
+            dist.destroy_process_group()
+        return
+
+    # ==== --full: everything below runs after the headline's timed steps and leaves its figures as they are ====================
+
+    # How the data decided the bound-filtered pipeline (outside the timed region: reading the counters synchronises).  The steps cycle
+    # through n_batches distinct query batches, so one more run of each tells what every timed step did.
+    filt = []
+    for i in range(min(n_batches, args.steps + args.warmup)):
+        step(i)
+        filt.append(index.filter_stats())
+    fence()
+    if filt and filt[0]["kind"] != "none":
+        fallback_steps = sum(int(filt[i % len(filt)]["fallback"]) for i in range(args.steps))
+        filter_block = {
+            "kind": filt[0]["kind"],
+            "candidates_per_query": {"mean": float(np.mean([f["candidates_per_query_mean"] for f in filt])),
+                                     "max": int(max(f["candidates_per_query_max"] for f in filt))},
+            "list_capacity": filt[0]["list_capacity"], "fallback_steps": fallback_steps, "of_steps": args.steps,
+            "note": "rank 0's shard; chunks whose approximate score is within 2m of the k-th best, re-scored exactly; fallback = the "
+                    "guarded full-precision passes ran (list overflow / unusable bound)",
+        }
+    else:
+        filter_block = {"kind": "none", "fallback_steps": 0, "of_steps": args.steps}
+    result.update({"candidates_per_query": filter_block.get("candidates_per_query"), "fallback_steps": filter_block["fallback_steps"],
+                   "filter": filter_block})
 
     # ---- roofline of the dominant kernel: HIP events on the launch stream, kernel only -----------------------------
     # One launch = one corpus pass of EIGHT queries through maxsim_gemm_kernel (matrix-pipe-bound).  Big fp32 corpora in split

@@ -3,7 +3,7 @@
 # The whole-job rate of N ranks is at most QUERIES_PER_STEP / (this step's time + the exchange): the scaling the driver's N = 2, 4, 8 runs can show.
 OUT=${1:-gpurun_out/shard_overhead}; mkdir -p "$OUT"
 for rows in 1000000 500000 250000 125000; do
-  timeout 300 python bench.py --rows $rows --steps 20 --warmup 5 --no-cpu-baseline --no-configs --no-f16 > "$OUT/rows_$rows.json" 2> "$OUT/rows_$rows.err"
+  timeout 300 python bench.py --rows $rows --steps 20 --warmup 5 --full --no-cpu-baseline --no-configs --no-f16 > "$OUT/rows_$rows.json" 2> "$OUT/rows_$rows.err"
   python - "$OUT/rows_$rows.json" $rows <<'PY' | tee -a "$OUT/summary.txt"
 import json, sys
 r = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])

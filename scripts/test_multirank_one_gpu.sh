@@ -7,5 +7,5 @@ set -u
 export HSA_ENABLE_IPC_MODE_LEGACY=0
 for N in 2 4; do
   timeout 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node $N --master-addr 127.0.0.1 --master-port $((29500 + N)) \
-      bench.py --gpus $N --steps 4 --warmup 1 --rows 200000 --same-gpu --backend gloo 2>/dev/null | tail -1 | cut -c1-400
+      bench.py --gpus $N --steps 4 --warmup 1 --rows 200000 --same-gpu --backend gloo --full 2>/dev/null | tail -1 | cut -c1-400
 done

@@ -147,3 +147,8 @@ def test_kernel_names_printed_by_the_bench_exist_in_the_library():
     have_n = {norm(re.sub(r"\(anonymous namespace\)::", "", h)) for h in have}
     missing = sorted(w for w in wanted if norm(w) not in have_n)
     assert not missing, f"bench prints kernel names the library does not hold: {missing}"
+
+
+def test_bench_split_is_a_full_measurement():
+    res = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--split"], capture_output=True, text=True, timeout=120)
+    assert res.returncode == 2 and "--full" in res.stderr
