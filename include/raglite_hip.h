@@ -472,6 +472,37 @@ int rl_keyword_search(rl_keyword_index* kw, const int64_t* q_off, const int32_t*
 int rl_keyword_index_info(const rl_keyword_index* kw, int32_t* n_terms, int64_t* n_postings, int64_t* n_chunks);
 int rl_keyword_index_destroy(rl_keyword_index* kw);
 
+/* ---- weighted Reciprocal Rank Fusion and batched hybrid search ---------------------------------------
+ * rl_rrf_fuse replaces src/raglite/_search.py:233-252 (`reciprocal_rank_fusion`) for a batch of queries, bit for bit:
+ *   lists       int32 [n_lists x n_queries x len], 1 <= n_lists <= 4, n_lists * len <= 4096: list r of query b is
+ *               lists[(r * n_queries + b) * len ..]; an entry < 0 is padding (anywhere in the list) and takes no rank
+ *   weights     double[n_lists], ALWAYS host memory (checked before any HIP call): finite, |w| <= 2^1000
+ *   rrf_k       1 .. 2^30 (the reference's `k`, 60 in hybrid_search)
+ * An ordinal's score is the float64 sum of w_r / (rrf_k + i) over its occurrences (i = its 0-based rank among the
+ * results of list r), added from +0.0 in the order the reference's loop meets them -- list 0 first, each list in rank
+ * order, a repeat within a list adding again -- every division and addition rounded to nearest, no contraction.
+ * out_scores double / out_ids int32 [n_queries x k], 1 <= k <= n_lists * len: by score descending, equal scores by first
+ * occurrence in list 0 || list 1 || ... (the reference's stable sort over its dict's insertion order); unfilled slots
+ * (-inf, -1); out_counts [n_queries] (may be NULL) the filled slots.  Host or device pointers per `mem`, like rl_merge_topk.
+ *
+ * rl_hybrid_search replaces src/raglite/_search.py:255-279 (`hybrid_search`: vector search and keyword search, each for
+ * n_each = oversample * num_results results, fused by RRF with weights (vector, keyword)) for n_queries queries at once,
+ * on one stream, with no host copy of the intermediate lists:
+ *   the vector half   rl_search_chunks_ranked(index, queries [n_queries x dim], num_hits, n_each, chunk_filter, rank_limit)
+ *   the keyword half  rl_keyword_search(kw, q_off [n_queries + 1], q_terms, n_each, chunk_filter); kw == NULL: no keyword
+ *                     half, only the vector list is fused (weights[0]); otherwise kw must cover the index' n_chunks
+ *   the fusion        rl_rrf_fuse of (vector list, keyword list) with weights double[1 or 2] (host) and rrf_k -> out_scores
+ *                     double / out_chunks int32 [n_queries x k], out_counts [n_queries], k <= (kw ? 2 : 1) * n_each
+ * Both lists live in scratch the index owns.  Host synchronisation: none of its own beyond the RL_MEM_HOST staging;
+ * the two searches keep theirs -- a call on another stream than the handle's (index or kw) previous one first waits for
+ * that stream, and the first search whose route reads an image the index has not built yet builds it (synchronises). */
+int rl_rrf_fuse(const int32_t* lists, int32_t n_lists, int32_t n_queries, int32_t len, const double* weights, int32_t rrf_k,
+                int32_t k, double* out_scores, int32_t* out_ids, int32_t* out_counts, int mem, void* stream);
+int rl_hybrid_search(rl_index* index, rl_keyword_index* kw, const float* queries, int32_t n_queries, int32_t num_hits,
+                     int32_t n_each, const int64_t* q_off, const int32_t* q_terms, const uint32_t* chunk_filter,
+                     int64_t rank_limit, const double* weights, int32_t rrf_k, int32_t k, double* out_scores,
+                     int32_t* out_chunks, int32_t* out_counts, int mem, void* stream);
+
 /* ---- metadata filter pushed down ---------------------------------------
  * The filter-first branch of the reference's vector search (src/raglite/_search.py:96-119): only
  * rows of chunks that match the metadata filter are ranked.  The caller evaluates the filter on its

@@ -22,6 +22,7 @@ from raglite_amd._ops import (
     adapter_apply,
     merge_topk,
     pack_bits,
+    rrf_fuse,
     get_default_option,
     pool_norm,
     set_default_option,
@@ -32,6 +33,7 @@ from raglite_amd._ops import (
 from raglite_amd._search import (
     GpuIndex,
     hybrid_search,
+    hybrid_search_batch,
     keyword_search,
     reciprocal_rank_fusion,
     GpuVectorSearch,
@@ -58,6 +60,7 @@ __all__ = [
     "partition_similarities",
     "split_chunks",
     "hybrid_search",
+    "hybrid_search_batch",
     "keyword_search",
     "KeywordIndex",
     "reciprocal_rank_fusion",
@@ -68,6 +71,7 @@ __all__ = [
     "TorchCrossEncoderRanker",
     "CrossEncoderShape",
     "pack_bits",
+    "rrf_fuse",
     "Communicator", "DeviceIndex", "GpuIndex", "GpuVectorSearch", "HotPathConfig", "MaxSimRanker", "ShardedIndex",
     "adapter_apply", "attach_index", "detach_index", "embed_strings", "embed_strings_with_late_chunking",
     "embed_strings_without_late_chunking", "embedding_type", "merge_topk", "merge_topk_host", "pool_norm",

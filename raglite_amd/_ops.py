@@ -200,6 +200,39 @@ def merge_topk(scores, ids, k: int):
     return o_s, o_i
 
 
+def rrf_fuse(lists, weights, *, rrf_k: int = 60, k: int):
+    """Weighted Reciprocal Rank Fusion (`rl_rrf_fuse`): the reference's `reciprocal_rank_fusion` (`src/raglite/_search.py:233-252`)
+    for a batch, bit for bit.  `lists`: (R, B, len) chunk ordinals, or a sequence of R (B, len) arrays, R <= 4, R * len <= 4096,
+    padded with entries < 0; `weights`: R finite floats.  Returns (scores (B, k) float64, ordinals (B, k) int32, counts (B,) int32),
+    by score descending, ties by first occurrence; unfilled slots are (-inf, -1)."""
+    if isinstance(lists, (list, tuple)):
+        lists = _torch().stack(list(lists)) if lists and _is_torch(lists[0]) else np.stack([np.asarray(x) for x in lists])
+    a = _Args()
+    p_l = a.inp(lists, np.int32)
+    if a.keep[0].ndim != 3:
+        raise ValueError("lists must be (n_lists, n_queries, len)")
+    R, B, L = (int(v) for v in a.keep[0].shape)
+    w = np.ascontiguousarray(np.asarray(weights, dtype=np.float64).ravel())  # (host memory, whatever side the lists are on)
+    if w.size != R:
+        raise ValueError("one weight per list is required")
+    if not (-(1 << 31) <= int(rrf_k) < (1 << 31)) or not (-(1 << 31) <= int(k) < (1 << 31)):
+        raise ValueError("rrf_k and k must fit in int32")
+    o_s, p_s = a.out((B, k), np.float64)
+    o_i, p_i = a.out((B, k), np.int32)
+    o_n, p_n = a.out((B,), np.int32)
+    a.ensure_device()
+    check(lib().rl_rrf_fuse(p_l, R, B, L, w.ctypes.data, int(rrf_k), int(k), p_s, p_i, p_n, a.mem, a.stream))
+    return o_s, o_i, o_n
+
+
+def _term_csr(query_term_ids) -> tuple[np.ndarray, np.ndarray]:
+    """One sequence of term ids per query -> (q_off int64 [B + 1], q_terms int32), each query's ids ascending and distinct."""
+    qs = [np.unique(np.asarray(q, dtype=np.int32)) for q in query_term_ids]
+    q_off = np.concatenate(([0], np.cumsum([q.size for q in qs]))).astype(np.int64)
+    q_terms = np.ascontiguousarray(np.concatenate(qs) if qs else np.zeros(0, np.int32), dtype=np.int32)
+    return q_off, q_terms
+
+
 def pack_bits(mask) -> np.ndarray:
     """Boolean mask (NumPy / torch, any device) -> little-endian uint32 bitset (bit i of word i // 32)."""
     if _is_torch(mask):
@@ -527,6 +560,36 @@ class DeviceIndex:
                                             a.mem, a.stream))
         return (o_s[0], o_c[0], o_n[0]) if single else (o_s, o_c, o_n)
 
+    def hybrid_search(self, queries, num_hits: int, n_each: int, k: int, *, keyword: "KeywordIndex | None" = None, query_term_ids=None,
+                      weights=(0.75, 0.25), rrf_k: int = 60, chunk_filter=None, rank_limit: int | None = None):
+        """`rl_hybrid_search`: per query the n_each best chunks of the two-stage vector search (as `search_chunks`) and, with `keyword`,
+        the n_each best of BM25 over `query_term_ids` (one sequence per query), fused by weighted RRF on the device; `weights` are
+        (vector,) or (vector, keyword).  Returns (scores (B, k) float64, chunk ordinals (B, k) int32, counts (B,) int32)."""
+        a = _Args()
+        p_q, B, single = self._queries(a, queries)
+        o_s, p_s = a.out((B, k), np.float64)
+        o_c, p_c = a.out((B, k), np.int32)
+        o_n, p_n = a.out((B,), np.int32)
+        p_f = self._filter(a, chunk_filter)
+        w = np.ascontiguousarray(np.asarray(weights, dtype=np.float64).ravel()[: 2 if keyword is not None else 1])
+        p_off = p_terms = None
+        if keyword is not None:
+            if query_term_ids is None or len(query_term_ids) != B:
+                raise ValueError("one sequence of term ids per query is required")
+            q_off, q_terms = _term_csr(query_term_ids)
+            if a.mem == MEM_DEVICE:
+                torch = _torch()
+                q_off = torch.from_numpy(q_off).to(a.device)
+                q_terms = torch.from_numpy(q_terms if q_terms.size else np.zeros(1, np.int32)).to(a.device)
+                p_off, p_terms = q_off.data_ptr(), q_terms.data_ptr()
+            else:
+                p_off, p_terms = q_off.ctypes.data, q_terms.ctypes.data
+            a.keep += [q_off, q_terms]
+        self._prep(a)
+        check(lib().rl_hybrid_search(self._handle, None if keyword is None else keyword._handle, p_q, B, int(num_hits), int(n_each), p_off,
+                                     p_terms, p_f, int(rank_limit or 0), w.ctypes.data, int(rrf_k), int(k), p_s, p_c, p_n, a.mem, a.stream))
+        return (o_s[0], o_c[0], o_n[0]) if single else (o_s, o_c, o_n)
+
     # -- a9 ----------------------------------------------------------------------------------------
     def maxsim_scores(self, query_vecs):
         a = _Args()
@@ -704,10 +767,8 @@ class KeywordIndex:
     def search(self, query_term_ids, k: int, chunk_filter=None):
         """BM25 top-k of a batch: `query_term_ids` holds one sequence of term ids per query (duplicates are dropped, order does not
         matter).  Returns (scores (B,k) float32, chunk ordinals (B,k) int32, counts (B,) int32); unfilled slots are (-inf, -1)."""
-        qs = [np.unique(np.asarray(q, dtype=np.int32)) for q in query_term_ids]
-        q_off = np.concatenate(([0], np.cumsum([q.size for q in qs]))).astype(np.int64)
-        q_terms = np.ascontiguousarray(np.concatenate(qs) if qs else np.zeros(0, np.int32), dtype=np.int32)
-        B = len(qs)
+        q_off, q_terms = _term_csr(query_term_ids)
+        B = int(q_off.size - 1)
         scores = np.empty((B, k), np.float32)
         chunks = np.empty((B, k), np.int32)
         counts = np.empty(B, np.int32)

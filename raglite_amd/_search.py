@@ -5,6 +5,7 @@
     keyword_search(query, *, num_results=3, metadata_filter=None, config=None)
         -> (list[ChunkId], list[float])   BM25 on the device               (`_search.py:156-230`)
     hybrid_search(...)                                                    (`_search.py:255-279`)
+    hybrid_search_batch(queries, ...) -> list of hybrid_search's results, one device round trip for the batch
     rerank_chunks(query, chunk_ids, *, config=None) -> list[chunk]        (`_search.py:364-397`)
     search_and_rerank_chunks(...)                                         (`_search.py:400-414`)
     GpuVectorSearch   -- a `BasicSearchMethod` (`_typing.py:35-43`) for `RAGLiteConfig.search_method`
@@ -273,7 +274,10 @@ def _matches(meta: dict, flt: dict) -> bool:
     return True
 
 
-def vector_search(query: str | np.ndarray, *, num_results: int = 3, oversample: int = 4,
+VECTOR_SEARCH_OVERSAMPLE = 4  # vector_search's default `oversample`: what hybrid_search's vector half runs with (`_search.py:36-41`)
+
+
+def vector_search(query: str | np.ndarray, *, num_results: int = 3, oversample: int = VECTOR_SEARCH_OVERSAMPLE,
                   metadata_filter: dict | None = None, config: Any | None = None,
                   index: GpuIndex | None = None) -> tuple[list[ChunkId], list[float]]:
     """Search chunks with an exact GPU scan (the reference's HNSW search is approximate)."""
@@ -422,6 +426,96 @@ def hybrid_search(query: str | np.ndarray, *, num_results: int = 3, oversample: 
                                            config=config, index=gi)
     ids, scores = reciprocal_rank_fusion([vs_ids, ks_ids], weights=[vector_search_weight, keyword_search_weight])
     return ids[:num_results], scores[:num_results]
+
+
+RRF_K = 60  # reciprocal_rank_fusion's `k` as hybrid_search calls it
+
+
+def _embed_one_by_one(queries: Sequence[str], query_vectors, cfg: Any, gi: GpuIndex) -> np.ndarray:
+    """The (B, dim) float32 query matrix vector_search would build query by query: each string embedded on its own (a list handed
+    to embed_strings is one document's sentences under late chunking), then the query adapter applied per query (its batched route
+    multiplies with other kernels than the single-query one) and cast back to the embedding's dtype."""
+    if query_vectors is not None:
+        if _ops._is_torch(query_vectors):  # noqa: SLF001
+            query_vectors = query_vectors.detach().cpu().numpy()
+        qv = np.asarray(query_vectors)
+        if qv.ndim != 2 or qv.shape[0] != len(queries):
+            raise ValueError("query_vectors must be (len(queries), dim)")
+        rows = list(qv)
+    else:
+        rows = [embed_strings([q], config=cfg)[0, :] for q in queries]
+    if cfg.vector_search_query_adapter and gi.query_adapter is not None:
+        rows = [_ops.adapter_apply(gi.query_adapter, np.asarray(q, dtype=np.float32)).astype(q.dtype) for q in rows]
+    return np.stack([np.asarray(q, dtype=np.float32).ravel() for q in rows])
+
+
+def hybrid_search_batch(queries: Sequence[str], *, num_results: int = 3, oversample: int = 2,
+                        vector_search_weight: float = 0.75, keyword_search_weight: float = 0.25,
+                        metadata_filter: dict | None = None, config: Any | None = None, index: GpuIndex | None = None,
+                        query_vectors=None) -> list[tuple[list[ChunkId], list[float]]]:
+    """`hybrid_search` for a batch of query strings: element b is what `hybrid_search(queries[b], ...)` returns with the same
+    arguments (the same chunk ids, the same float scores).  The vector half, the keyword half and the RRF fusion of all queries run
+    on one stream (`rl_hybrid_search`) and the results are read back once.  `query_vectors` ((B, dim), e.g. embeddings computed
+    elsewhere) skips the embedding; the strings still give the keyword half.  The metadata filter applies to the whole batch; an
+    external `keyword_search=` callable is not part of the batched call (use `hybrid_search`)."""
+    cfg = config or HotPathConfig()
+    gi = index or _index_for(config)
+    queries = list(queries)
+    B = len(queries)
+    if B == 0:
+        return []
+    if getattr(cfg, "self_query", False):
+        raise NotImplementedError("self_query needs the LLM stack, which is outside this package")
+    flt = _adapt_metadata(metadata_filter)
+    n_each = oversample * num_results  # what hybrid_search asks of each half
+    Q = _embed_one_by_one(queries, query_vectors, cfg, gi)
+
+    def allowed_chunks() -> np.ndarray:
+        if gi.metadata is None:
+            raise ValueError("GpuIndex was built without `metadata`; metadata_filter cannot be applied")
+        return np.fromiter((_matches(m, flt) for m in gi.metadata), dtype=bool, count=len(gi.metadata))
+
+    # the vector half, decided as vector_search decides it (same checks, same order)
+    num_hits = round(VECTOR_SEARCH_OVERSAMPLE * cfg.chunk_max_size / DEFAULT_CHUNK_MAX_SIZE) * max(n_each, 10)
+    vector = gi.index.n_rows > 0 and num_hits >= 1 and n_each >= 1
+    allowed, rank_limit = None, None
+    if vector and flt:
+        allowed = allowed_chunks()
+        vector = bool(allowed.any())
+    if vector:
+        _check_limits(num_hits, n_each)
+        if allowed is not None:
+            offsets = gi.index.chunk_offsets
+            rows_per_chunk = np.diff(offsets) if offsets is not None else np.ones(len(allowed), dtype=np.int64)
+            rank_limit = ORDER_FIRST_LIMIT if int(rows_per_chunk[allowed].sum()) > FILTER_FIRST_MAX_ROWS else None
+    # the keyword half, as keyword_search decides it
+    keyword, term_ids = gi.has_keywords and n_each >= 1, None
+    if keyword:
+        if n_each > _ops.K_MAX:
+            raise ValueError(f"keyword_search: num_results={n_each} is more than the {_ops.K_MAX} the exact top-k kernel ranks; "
+                             "lower num_results")
+        term_ids = [gi.keyword_query_ids(q) for q in queries]
+        if flt and any(term_ids):  # (a query without a known stem returns before the filter is looked at)
+            if allowed is None:
+                allowed = allowed_chunks()
+            keyword = bool(allowed.any())
+    if not vector and not keyword:
+        return [([], []) for _ in range(B)]
+    R = int(vector) + int(keyword)
+    k = R * n_each if num_results < 1 else min(num_results, R * n_each)  # (hybrid_search slices the fused list [:num_results])
+    if vector:
+        scores, chunks, counts = gi.index.hybrid_search(Q, num_hits, n_each, k, keyword=gi.keyword if keyword else None,
+                                                        query_term_ids=term_ids, weights=(vector_search_weight, keyword_search_weight),
+                                                        rrf_k=RRF_K, chunk_filter=allowed, rank_limit=rank_limit)
+    else:  # no vector results for any query (an empty index, num_hits < 1): RRF of the keyword list alone is the same fusion
+        _, kw_chunks, _ = gi.keyword.search(term_ids, n_each, chunk_filter=allowed)
+        scores, chunks, counts = _ops.rrf_fuse(kw_chunks[None], [keyword_search_weight], rrf_k=RRF_K, k=k)
+    out = []
+    for b in range(B):
+        n = int(counts[b])
+        ids = [gi.chunk_ids[c] for c in chunks[b, :n].tolist()]
+        out.append((ids[:num_results], [float(x) for x in scores[b, :n]][:num_results]))
+    return out
 
 
 # ---- reranking -------------------------------------------------------------------------------------------

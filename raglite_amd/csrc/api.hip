@@ -330,6 +330,7 @@ struct rl_index {
     rl::Pool fused;                       // fused batched top-k: sample scores, thresholds, candidate lists, counters
     rl::Pool pp_work;                     // ... on the sixteen-group tile: wave-private record logs, block norm ranges (maxsim_pp.hip MODE 2)
     rl::Pool rankbuf;                     // rank cut (order-first-then-filter): histogram levels + tie counts
+    rl::Pool hybrid;                      // rl_hybrid_search: the ranked lists the fusion reads, their scores and counts
     // HI plane (round 2): fp16(e * split_scale) rounded to nearest (toward zero until round 3), row-major [n_rows x dim] -- the hi halves of the fp16
     // split as a matrix of their own, 2 B per element: what the single-query search streams (search_rows_hi).
     rl::Image hiplane;
@@ -1756,6 +1757,20 @@ int check_search_args(const rl_index* idx, const float* q, int32_t B, int32_t k,
     return RL_OK;
 }
 
+// The device half of rl_search_chunks_ranked on device pointers (under idx->mu, after use_scratch): the num_hits best rows per
+// query (filter / rank cut as there), grouped to the k best chunks -> d_s / d_c [B x k], d_n [B]
+int search_chunks_device(rl_index* idx, const float* d_q, int32_t B, int32_t num_hits, int32_t k, const uint32_t* d_f, int64_t rank_limit,
+                         float* d_s, int32_t* d_c, int32_t* d_n, hipStream_t s) {
+    const uint32_t* d_bits = nullptr;
+    RL_TRY(effective_row_mask(idx, d_f, s, &d_bits));
+    RL_TRY(idx->hits.reserve((size_t)B * num_hits * 8));
+    float* h_s = idx->hits.as<float>();
+    int32_t* h_r = reinterpret_cast<int32_t*>(h_s + (size_t)B * num_hits);
+    RL_TRY(search_rows_device(idx, d_q, B, num_hits, h_s, h_r, s, d_bits, rank_limit));
+    RL_TRY(launch_group_chunk_max(h_s, h_r, B, num_hits, idx->offsets, idx->n_chunks, k, d_s, d_c, d_n, s));
+    return RL_OK;
+}
+
 }  // namespace
 
 int rl_search_rows_ranked(rl_index* idx, const float* queries, int32_t B, int32_t k, const uint32_t* chunk_filter,
@@ -1916,18 +1931,12 @@ int rl_search_chunks_ranked(rl_index* idx, const float* queries, int32_t B, int3
     DevBuf t_q, t_s, t_c, t_n, t_f;
     const float* d_q; float* d_s; int32_t* d_c; int32_t* d_n;
     const uint32_t* d_f = nullptr;
-    const uint32_t* d_bits = nullptr;
     if (chunk_filter) RL_TRY(stage_in(chunk_filter, (size_t)((idx->n_chunks + 31) / 32), mem, s, t_f, &d_f));
-    RL_TRY(effective_row_mask(idx, d_f, s, &d_bits));
     RL_TRY(stage_in(queries, (size_t)B * idx->dim, mem, s, t_q, &d_q));
     RL_TRY(stage_out_begin(out_scores, (size_t)B * k, mem, t_s, &d_s));
     RL_TRY(stage_out_begin(out_chunks, (size_t)B * k, mem, t_c, &d_c));
     RL_TRY(stage_out_begin(out_counts, (size_t)B, mem, t_n, &d_n));
-    RL_TRY(idx->hits.reserve((size_t)B * num_hits * 8));
-    float* h_s = idx->hits.as<float>();
-    int32_t* h_r = reinterpret_cast<int32_t*>(h_s + (size_t)B * num_hits);
-    RL_TRY(search_rows_device(idx, d_q, B, num_hits, h_s, h_r, s, d_bits, rank_limit));
-    RL_TRY(launch_group_chunk_max(h_s, h_r, B, num_hits, idx->offsets, idx->n_chunks, k, d_s, d_c, d_n, s));
+    RL_TRY(search_chunks_device(idx, d_q, B, num_hits, k, d_f, rank_limit, d_s, d_c, d_n, s));
     RL_TRY(stage_out_end(out_scores, (size_t)B * k, mem, s, t_s));
     RL_TRY(stage_out_end(out_chunks, (size_t)B * k, mem, s, t_c));
     RL_TRY(stage_out_end(out_counts, (size_t)B, mem, s, t_n));
@@ -2947,6 +2956,62 @@ int check_host_postings(const int64_t* term_off, int32_t n_terms, const int32_t*
     return RL_OK;
 }
 
+// A call on another stream than the handle's previous one first waits for that stream (the handle's scratch is shared).
+int keyword_use_stream(rl_keyword_index* kw, hipStream_t s) {
+    if (kw->last_stream_set && kw->last_stream != s) RL_HIP(hipStreamSynchronize(kw->last_stream));
+    kw->last_stream = s;
+    kw->last_stream_set = true;
+    return RL_OK;
+}
+
+// The device half of rl_keyword_search on device pointers (under kw->mu, after keyword_use_stream): d_s / d_c [B x k], d_n [B]
+int keyword_search_device(rl_keyword_index* kw, const int64_t* d_off, const int32_t* d_terms, int32_t n_queries, int32_t k, const uint32_t* d_f,
+                          float* d_s, int32_t* d_c, int32_t* d_n, hipStream_t s) {
+    const int64_t n = kw->n_chunks;
+    const size_t n_out = (size_t)n_queries * k;
+    if (n == 0) {  // no chunks: every slot is padding
+        RL_TRY(launch_fill_f32(d_s, -std::numeric_limits<float>::infinity(), (int64_t)n_out, s));
+        RL_HIP(hipMemsetAsync(d_c, 0xff, n_out * sizeof(int32_t), s));
+    } else {
+        const int64_t ld = (n + 3) & ~int64_t(3);
+        // (a sub-batch is one grid row per query: at most 65535 of them)
+        const int32_t batch = (int32_t)std::max<int64_t>(1, std::min<int64_t>({(int64_t)n_queries, int64_t(65535),
+                                                                                (int64_t)(SCORE_BATCH_BYTES / ((size_t)ld * 4))}));
+        RL_TRY(kw->scores.reserve((size_t)batch * ld * sizeof(float)));
+        for (int32_t b0 = 0; b0 < n_queries; b0 += batch) {
+            const int32_t nb = std::min<int32_t>(batch, n_queries - b0);
+            RL_TRY(launch_bm25_score(kw->term_off, kw->post_chunk, kw->post_impact, kw->n_terms, n, d_off + b0, d_terms, nb, d_f,
+                                     bm25_tile(n, nb, kw->n_cu), kw->scores.as<float>(), ld, s));
+            RL_TRY(launch_topk(kw->scores.as<float>(), nb, n, ld, k, kw->ws, d_s + (int64_t)b0 * k, d_c + (int64_t)b0 * k, s));
+        }
+        RL_TRY(launch_fix_masked(d_s, d_c, (int64_t)n_out, s));  // chunks without a query term are "no hit": (-inf, -1)
+    }
+    return launch_bm25_count(d_s, n_queries, k, d_n, s);
+}
+
+// q_off as rl_keyword_search states it (host pointers only)
+int check_host_q_off(const int64_t* q_off, const int32_t* q_terms, int32_t n_queries, const char* who) {
+    if (q_off[0] != 0) return fail(RL_ERR_INVALID, std::string(who) + ": q_off must start at 0");
+    for (int32_t b = 0; b < n_queries; ++b)
+        if (q_off[b + 1] < q_off[b]) return fail(RL_ERR_INVALID, std::string(who) + ": q_off must be ascending");
+    if (q_off[n_queries] > 0 && !q_terms) return fail(RL_ERR_INVALID, std::string(who) + ": null q_terms");
+    return RL_OK;
+}
+
+// rl_rrf_fuse's limits (weights: host memory)
+int check_fuse_args(int32_t n_lists, int32_t n_queries, int32_t len, const double* weights, int32_t rrf_k, int32_t k, const char* who) {
+    if (n_lists < 1 || n_lists > RRF_MAX_LISTS) return fail(RL_ERR_INVALID, std::string(who) + ": n_lists must be in [1, 4]");
+    if (n_queries < 0 || len < 1) return fail(RL_ERR_INVALID, std::string(who) + ": n_queries must be >= 0 and len >= 1");
+    if ((int64_t)n_lists * len > RRF_MAX_ENTRIES) return fail(RL_ERR_INVALID, std::string(who) + ": n_lists * len must be <= 4096");
+    if (k < 1 || k > n_lists * len) return fail(RL_ERR_INVALID, std::string(who) + ": k must be in [1, n_lists * len]");
+    if (rrf_k < 1 || rrf_k > RRF_MAX_K) return fail(RL_ERR_INVALID, std::string(who) + ": rrf_k must be in [1, 2^30]");
+    if (!weights) return fail(RL_ERR_INVALID, std::string(who) + ": null weights");
+    for (int32_t r = 0; r < n_lists; ++r)
+        if (!(std::fabs(weights[r]) <= RRF_MAX_WEIGHT))
+            return fail(RL_ERR_INVALID, std::string(who) + ": weights must be finite, of magnitude <= 2^1000");
+    return RL_OK;
+}
+
 }  // namespace
 }  // namespace rl
 
@@ -3023,19 +3088,14 @@ int rl_keyword_search(rl_keyword_index* kw, const int64_t* q_off, const int32_t*
     if (!out_scores || !out_chunks) return fail(RL_ERR_INVALID, "rl_keyword_search: null output");
     int64_t n_q_terms = 0;
     if (mem == RL_MEM_HOST) {
-        if (q_off[0] != 0) return fail(RL_ERR_INVALID, "rl_keyword_search: q_off must start at 0");
-        for (int32_t b = 0; b < n_queries; ++b)
-            if (q_off[b + 1] < q_off[b]) return fail(RL_ERR_INVALID, "rl_keyword_search: q_off must be ascending");
+        RL_TRY(check_host_q_off(q_off, q_terms, n_queries, "rl_keyword_search"));
         n_q_terms = q_off[n_queries];
-        if (n_q_terms > 0 && !q_terms) return fail(RL_ERR_INVALID, "rl_keyword_search: null q_terms");
     } else if (!q_terms) {
         return fail(RL_ERR_INVALID, "rl_keyword_search: null q_terms");
     }
     hipStream_t s = as_stream(stream);
     std::lock_guard<std::mutex> lock(kw->mu);
-    if (kw->last_stream_set && kw->last_stream != s) RL_HIP(hipStreamSynchronize(kw->last_stream));
-    kw->last_stream = s;
-    kw->last_stream_set = true;
+    RL_TRY(keyword_use_stream(kw, s));
     const int64_t n = kw->n_chunks;
     const size_t n_out = (size_t)n_queries * k;
     DevBuf t_off, t_terms, t_f, t_s, t_c, t_n;
@@ -3055,28 +3115,98 @@ int rl_keyword_search(rl_keyword_index* kw, const int64_t* q_off, const int32_t*
         RL_TRY(t_n.alloc((size_t)n_queries * sizeof(int32_t)));
         d_n = t_n.as<int32_t>();
     }
-    if (n == 0) {  // no chunks: every slot is padding
-        RL_TRY(launch_fill_f32(d_s, -std::numeric_limits<float>::infinity(), (int64_t)n_out, s));
-        RL_HIP(hipMemsetAsync(d_c, 0xff, n_out * sizeof(int32_t), s));
-    } else {
-        const int64_t ld = (n + 3) & ~int64_t(3);
-        // (a sub-batch is one grid row per query: at most 65535 of them)
-        const int32_t batch = (int32_t)std::max<int64_t>(1, std::min<int64_t>({(int64_t)n_queries, int64_t(65535),
-                                                                                (int64_t)(SCORE_BATCH_BYTES / ((size_t)ld * 4))}));
-        RL_TRY(kw->scores.reserve((size_t)batch * ld * sizeof(float)));
-        for (int32_t b0 = 0; b0 < n_queries; b0 += batch) {
-            const int32_t nb = std::min<int32_t>(batch, n_queries - b0);
-            RL_TRY(launch_bm25_score(kw->term_off, kw->post_chunk, kw->post_impact, kw->n_terms, n, d_off + b0, d_terms, nb, d_f,
-                                     bm25_tile(n, nb, kw->n_cu), kw->scores.as<float>(), ld, s));
-            RL_TRY(launch_topk(kw->scores.as<float>(), nb, n, ld, k, kw->ws, d_s + (int64_t)b0 * k, d_c + (int64_t)b0 * k, s));
-        }
-        RL_TRY(launch_fix_masked(d_s, d_c, (int64_t)n_out, s));  // chunks without a query term are "no hit": (-inf, -1)
-    }
-    RL_TRY(launch_bm25_count(d_s, n_queries, k, d_n, s));
+    RL_TRY(keyword_search_device(kw, d_off, d_terms, n_queries, k, d_f, d_s, d_c, d_n, s));
     RL_TRY(stage_out_end(out_scores, n_out, mem, s, t_s));
     RL_TRY(stage_out_end(out_chunks, n_out, mem, s, t_c));
     if (out_counts) RL_TRY(stage_out_end(out_counts, (size_t)n_queries, mem, s, t_n));
     if (mem == RL_MEM_DEVICE && !out_counts) RL_HIP(hipStreamSynchronize(s));  // t_n dies with this frame
+    return finish(mem, s);
+}
+
+// ---- weighted Reciprocal Rank Fusion and batched hybrid search (include/raglite_hip.h; the kernel is in fuse.hip) ------------------
+int rl_rrf_fuse(const int32_t* lists, int32_t n_lists, int32_t n_queries, int32_t len, const double* weights, int32_t rrf_k, int32_t k,
+                double* out_scores, int32_t* out_ids, int32_t* out_counts, int mem, void* stream) {
+    RL_TRY(check_fuse_args(n_lists, n_queries, len, weights, rrf_k, k, "rl_rrf_fuse"));
+    if (mem != RL_MEM_HOST && mem != RL_MEM_DEVICE) return fail(RL_ERR_INVALID, "rl_rrf_fuse: bad mem");
+    if (n_queries == 0) return RL_OK;
+    if (!lists || !out_scores || !out_ids) return fail(RL_ERR_INVALID, "rl_rrf_fuse: null argument");
+    hipStream_t s = as_stream(stream);
+    const size_t n_in = (size_t)n_lists * n_queries * len, n_out = (size_t)n_queries * k;
+    DevBuf t_l, t_s, t_i, t_n;
+    const int32_t* d_l;
+    double* d_s;
+    int32_t *d_i, *d_n = nullptr;
+    RL_TRY(stage_in(lists, n_in, mem, s, t_l, &d_l));
+    RL_TRY(stage_out_begin(out_scores, n_out, mem, t_s, &d_s));
+    RL_TRY(stage_out_begin(out_ids, n_out, mem, t_i, &d_i));
+    if (out_counts) RL_TRY(stage_out_begin(out_counts, (size_t)n_queries, mem, t_n, &d_n));
+    RL_TRY(launch_rrf_fuse(d_l, n_lists, n_queries, len, weights, rrf_k, k, d_s, d_i, d_n, s));
+    RL_TRY(stage_out_end(out_scores, n_out, mem, s, t_s));
+    RL_TRY(stage_out_end(out_ids, n_out, mem, s, t_i));
+    if (out_counts) RL_TRY(stage_out_end(out_counts, (size_t)n_queries, mem, s, t_n));
+    return finish(mem, s);
+}
+
+int rl_hybrid_search(rl_index* idx, rl_keyword_index* kw, const float* queries, int32_t n_queries, int32_t num_hits, int32_t n_each,
+                     const int64_t* q_off, const int32_t* q_terms, const uint32_t* chunk_filter, int64_t rank_limit, const double* weights,
+                     int32_t rrf_k, int32_t k, double* out_scores, int32_t* out_chunks, int32_t* out_counts, int mem, void* stream) {
+    const char* who = "rl_hybrid_search";
+    const int32_t B = n_queries, R = kw ? 2 : 1;
+    RL_TRY(check_search_args(idx, queries, B, n_each, who));
+    if (rank_limit < 0) return fail(RL_ERR_INVALID, "rl_hybrid_search: rank_limit must be >= 0 (0 = no cut)");
+    if (num_hits < 1 || num_hits > K_MAX) return fail(RL_ERR_INVALID, "rl_hybrid_search: num_hits must be in [1, 2048]");
+    RL_TRY(check_fuse_args(R, B, n_each, weights, rrf_k, k, who));
+    if (mem != RL_MEM_HOST && mem != RL_MEM_DEVICE) return fail(RL_ERR_INVALID, "rl_hybrid_search: bad mem");
+    if (kw && kw->n_chunks != idx->n_chunks) return fail(RL_ERR_INVALID, "rl_hybrid_search: the keyword index covers another number of chunks");
+    if (B == 0) return RL_OK;
+    if (!out_scores || !out_chunks || !out_counts) return fail(RL_ERR_INVALID, "rl_hybrid_search: null output");
+    int64_t n_q_terms = 0;
+    if (kw) {
+        if (!q_off) return fail(RL_ERR_INVALID, "rl_hybrid_search: null q_off");
+        if (mem == RL_MEM_HOST) {
+            RL_TRY(check_host_q_off(q_off, q_terms, B, who));
+            n_q_terms = q_off[B];
+        } else if (!q_terms) {
+            return fail(RL_ERR_INVALID, "rl_hybrid_search: null q_terms");
+        }
+    }
+    hipStream_t s = as_stream(stream);
+    std::lock_guard<std::mutex> lock(idx->mu);  // (then kw->mu: the only call that holds both, always in this order)
+    RL_TRY(use_scratch(idx, s));
+    std::unique_lock<std::mutex> kw_lock;
+    if (kw) {
+        kw_lock = std::unique_lock<std::mutex>(kw->mu);
+        RL_TRY(keyword_use_stream(kw, s));
+    }
+    const size_t n_list = (size_t)B * n_each, n_out = (size_t)B * k;
+    DevBuf t_q, t_f, t_off, t_terms, t_s, t_c, t_n;
+    const float* d_q;
+    const uint32_t* d_f = nullptr;
+    const int64_t* d_off = nullptr;
+    const int32_t* d_terms = q_terms;
+    double* d_s;
+    int32_t *d_c, *d_n;
+    RL_TRY(stage_in(queries, (size_t)B * idx->dim, mem, s, t_q, &d_q));
+    if (chunk_filter) RL_TRY(stage_in(chunk_filter, (size_t)((idx->n_chunks + 31) / 32), mem, s, t_f, &d_f));
+    if (kw) {
+        RL_TRY(stage_in(q_off, (size_t)B + 1, mem, s, t_off, &d_off));
+        if (mem == RL_MEM_HOST) RL_TRY(stage_in(q_terms, (size_t)n_q_terms, mem, s, t_terms, &d_terms));
+    }
+    RL_TRY(stage_out_begin(out_scores, n_out, mem, t_s, &d_s));
+    RL_TRY(stage_out_begin(out_chunks, n_out, mem, t_c, &d_c));
+    RL_TRY(stage_out_begin(out_counts, (size_t)B, mem, t_n, &d_n));
+    // index-owned scratch: lists [R x B x n_each] int32 (what the fusion reads), the two searches' scores [R x B x n_each] f32 and
+    // counts [R x B] int32 (written, not read)
+    RL_TRY(idx->hybrid.reserve((size_t)R * (2 * n_list + B) * 4));
+    int32_t* lists = idx->hybrid.as<int32_t>();
+    float* list_scores = reinterpret_cast<float*>(lists + (size_t)R * n_list);
+    int32_t* list_counts = reinterpret_cast<int32_t*>(list_scores + (size_t)R * n_list);
+    RL_TRY(search_chunks_device(idx, d_q, B, num_hits, n_each, d_f, rank_limit, list_scores, lists, list_counts, s));
+    if (kw) RL_TRY(keyword_search_device(kw, d_off, d_terms, B, n_each, d_f, list_scores + n_list, lists + n_list, list_counts + B, s));
+    RL_TRY(launch_rrf_fuse(lists, R, B, n_each, weights, rrf_k, k, d_s, d_c, d_n, s));
+    RL_TRY(stage_out_end(out_scores, n_out, mem, s, t_s));
+    RL_TRY(stage_out_end(out_chunks, n_out, mem, s, t_c));
+    RL_TRY(stage_out_end(out_counts, (size_t)B, mem, s, t_n));
     return finish(mem, s);
 }
 

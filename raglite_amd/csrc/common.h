@@ -325,6 +325,15 @@ int launch_bm25_score(const int64_t* term_off, const int32_t* post_chunk, const 
                       int64_t ld, hipStream_t s);
 int launch_bm25_count(const float* sel, int32_t n_queries, int32_t k, int32_t* counts, hipStream_t s);  // finite entries per selected row
 
+// fuse.hip: weighted Reciprocal Rank Fusion of n_lists ranked lists per query (lists [n_lists x n_queries x len] int32, < 0 = padding)
+// -> the top k by (float64 score desc, first occurrence asc), bit for bit the reference's reciprocal_rank_fusion
+constexpr int32_t RRF_MAX_LISTS = 4;
+constexpr int32_t RRF_MAX_ENTRIES = 4096;  // n_lists * len
+constexpr int32_t RRF_MAX_K = 1 << 30;       // rrf_k + rank stays an exact int32 (and double)
+constexpr double RRF_MAX_WEIGHT = 0x1p1000;  // |w| <= 2^1000: no sum of 4096 terms w / (rrf_k + i) overflows
+int launch_rrf_fuse(const int32_t* lists, int32_t n_lists, int32_t n_queries, int32_t len, const double* weights /* host */, int32_t rrf_k,
+                    int32_t k, double* out_scores, int32_t* out_ids, int32_t* out_counts, hipStream_t s);
+
 // adapter_fit.hip: device half of update_query_adapter (best row per (query, chunk), row gather)
 int launch_chunk_best_rows(const void* E, bool f16, int32_t dim, const float* Q, const int64_t* offsets,
                            int64_t n_chunks, const int32_t* cand, int32_t n_cand, int64_t n_items, int32_t* out_rows,
