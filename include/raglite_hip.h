@@ -503,6 +503,26 @@ int rl_hybrid_search(rl_index* index, rl_keyword_index* kw, const float* queries
                      int64_t rank_limit, const double* weights, int32_t rrf_k, int32_t k, double* out_scores,
                      int32_t* out_chunks, int32_t* out_counts, int mem, void* stream);
 
+/* rl_shard_hybrid_fuse: everything after the ONE all-gather of a sharded hybrid batch (raglite_amd/_sharded.py
+ * ShardedIndex.hybrid_search), one workgroup per query, LDS only.  `gathered` int32 [world x n_queries x W] is what the
+ * all-gather returns: rank r's records for query b at ((r * n_queries + b) * W), W = 3 num_hits + (n_lists == 2 ? 2 n_each : 0):
+ *   num_hits row records   (score f32 bits, GLOBAL row, GLOBAL chunk): that rank's rl_search_rows_ranked output
+ *   n_each keyword records (score f32 bits, GLOBAL chunk): that rank's rl_keyword_search output (n_lists == 2 only)
+ * An id < 0 is padding, anywhere.  Per query:
+ *   1. the rows merged by (score desc, row asc; NaN after -inf), the first num_hits real ones: the global top rows;
+ *   2. the first hit of each chunk among them, in that order, up to n_each: the vector list (rl_search_chunks_ranked's);
+ *   3. the keyword records merged by (score desc, chunk asc), the first n_each: the keyword list;
+ *   4. rl_rrf_fuse of (vector list[, keyword list]) with weights double[n_lists] (host) and rrf_k, the same arithmetic and ties.
+ * out_scores double / out_chunks int32 [n_queries x k], out_counts [n_queries] (may be NULL) as rl_hybrid_search returns them:
+ * the same bits as rl_hybrid_search on one index holding the whole corpus.  n_lists == 1: the vector list alone (kw == NULL there).
+ * If any record of a query carries RL_ID_SHARD_MISSING, that query's outputs are poisoned: every score NaN, every id -1, count 0.
+ * Limits: the rl_rrf_fuse ones on (n_lists, n_each, k, weights, rrf_k), checked before any HIP call; world * num_hits <= 4096 and
+ * (n_lists == 2) world * n_each <= 4096, else RL_ERR_UNSUPPORTED (the caller composes rl_merge_topk-style merges + rl_rrf_fuse).
+ * Host or device pointers per `mem`. */
+int rl_shard_hybrid_fuse(const int32_t* gathered, int32_t world, int32_t n_queries, int32_t num_hits, int32_t n_each, int32_t n_lists,
+                         const double* weights, int32_t rrf_k, int32_t k, double* out_scores, int32_t* out_chunks, int32_t* out_counts,
+                         int mem, void* stream);
+
 /* ---- metadata filter pushed down ---------------------------------------
  * The filter-first branch of the reference's vector search (src/raglite/_search.py:96-119): only
  * rows of chunks that match the metadata filter are ranked.  The caller evaluates the filter on its

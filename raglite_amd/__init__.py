@@ -23,6 +23,7 @@ from raglite_amd._ops import (
     merge_topk,
     pack_bits,
     rrf_fuse,
+    shard_hybrid_fuse,
     get_default_option,
     pool_norm,
     set_default_option,
@@ -72,6 +73,7 @@ __all__ = [
     "CrossEncoderShape",
     "pack_bits",
     "rrf_fuse",
+    "shard_hybrid_fuse",
     "Communicator", "DeviceIndex", "GpuIndex", "GpuVectorSearch", "HotPathConfig", "MaxSimRanker", "ShardedIndex",
     "adapter_apply", "attach_index", "detach_index", "embed_strings", "embed_strings_with_late_chunking",
     "embed_strings_without_late_chunking", "embedding_type", "merge_topk", "merge_topk_host", "pool_norm",

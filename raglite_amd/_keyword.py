@@ -193,9 +193,19 @@ class Postings:
         return np.diff(self.term_off)
 
 
-def build_from_term_ids(flat_ids: np.ndarray, offsets: np.ndarray, n_terms: int, live: np.ndarray | None = None) -> Postings:
-    """Postings from pre-tokenised chunks: chunk c holds term ids flat_ids[offsets[c] : offsets[c + 1]] (any order, repeats = tf).
-    `live`: bool per chunk (None = all); dead chunks add nothing and are not counted in N, avgdl or df."""
+def bm25_weights(df: np.ndarray, length: np.ndarray, n_live: int, total_length: int) -> tuple[np.ndarray, np.ndarray, float]:
+    """(idf float32 [n_terms], nrm float32 [n_chunks], avgdl) from the corpus statistics: df per term (int64), N = n_live and the total
+    stem count of the live chunks; `length` holds the stems of the chunks the nrm values are for.  float64, rounded to float32 once.
+    The one statement of the formulas: `build_from_term_ids` passes its own corpus, `build_shard_from_term_ids` the global one."""
+    avgdl = float(total_length) / n_live if n_live else 0.0
+    idf = np.log1p((n_live - df + 0.5) / (df + 0.5))
+    rel = length / avgdl if avgdl > 0 else np.zeros(length.size)
+    nrm = K1 * (1.0 - B + B * rel)
+    return idf.astype(np.float32), nrm.astype(np.float32), avgdl
+
+
+def _postings_csr(flat_ids: np.ndarray, offsets: np.ndarray, n_terms: int, live: np.ndarray | None):
+    """(term_off, post_chunk, post_tf, post_term, length, n_live) of the chunks given (see `build_from_term_ids`)."""
     offsets = np.asarray(offsets, dtype=np.int64)
     n_chunks = int(offsets.size - 1)
     flat_ids = np.asarray(flat_ids, dtype=np.int64)
@@ -213,23 +223,57 @@ def build_from_term_ids(flat_ids: np.ndarray, offsets: np.ndarray, n_terms: int,
     df = np.bincount(post_term, minlength=n_terms).astype(np.int64)
     term_off = np.concatenate(([0], np.cumsum(df))).astype(np.int64)
     n_live = n_chunks if live is None else int(live.sum())
-    avgdl = float(length.sum()) / n_live if n_live else 0.0
-    idf = np.log1p((n_live - df + 0.5) / (df + 0.5))
-    rel = length / avgdl if avgdl > 0 else np.zeros(n_chunks)
-    nrm = K1 * (1.0 - B + B * rel)
-    return Postings(term_off, post_chunk.astype(np.int32), tf.astype(np.int32), post_term.astype(np.int32), idf.astype(np.float32),
-                    nrm.astype(np.float32), length, n_live, avgdl)
+    return term_off, post_chunk.astype(np.int32), tf.astype(np.int32), post_term.astype(np.int32), length, n_live
+
+
+def build_from_term_ids(flat_ids: np.ndarray, offsets: np.ndarray, n_terms: int, live: np.ndarray | None = None) -> Postings:
+    """Postings from pre-tokenised chunks: chunk c holds term ids flat_ids[offsets[c] : offsets[c + 1]] (any order, repeats = tf).
+    `live`: bool per chunk (None = all); dead chunks add nothing and are not counted in N, avgdl or df."""
+    term_off, post_chunk, post_tf, post_term, length, n_live = _postings_csr(flat_ids, offsets, n_terms, live)
+    idf, nrm, avgdl = bm25_weights(np.diff(term_off), length, n_live, int(length.sum()))
+    return Postings(term_off, post_chunk, post_tf, post_term, idf, nrm, length, n_live, avgdl)
+
+
+@dataclass
+class ShardCounts:
+    """What one shard contributes to the corpus statistics (summed over the shards by `ShardedIndex.attach_keywords`)."""
+
+    df: np.ndarray     # int64 [n_terms]: live local chunks holding each (global) term
+    n_live: int        # live local chunks
+    total_length: int  # stems over the live local chunks
+
+
+def shard_counts(flat_ids: np.ndarray, offsets: np.ndarray, n_terms: int, live: np.ndarray | None = None) -> ShardCounts:
+    term_off, _, _, _, length, n_live = _postings_csr(flat_ids, offsets, n_terms, live)
+    return ShardCounts(np.diff(term_off), n_live, int(length.sum()))
+
+
+def build_shard_from_term_ids(flat_ids: np.ndarray, offsets: np.ndarray, n_terms: int, live: np.ndarray | None, corpus: ShardCounts) -> Postings:
+    """One shard's postings over its LOCAL chunk ordinals (term ids global), weighted by the statistics of the WHOLE corpus (`corpus`:
+    df, N and the stem total summed over every shard): its idf, nrm and impacts are bitwise the slice of one build over everything.
+    `n_live` / `avgdl` of the result are the corpus values; `df` (the postings' own) stays local."""
+    term_off, post_chunk, post_tf, post_term, length, _ = _postings_csr(flat_ids, offsets, n_terms, live)
+    df = np.asarray(corpus.df, dtype=np.int64)
+    if df.size != n_terms:
+        raise ValueError("corpus.df must hold one count per term")
+    idf, nrm, avgdl = bm25_weights(df, length, int(corpus.n_live), int(corpus.total_length))
+    return Postings(term_off, post_chunk, post_tf, post_term, idf, nrm, length, int(corpus.n_live), avgdl)
+
+
+def stems_to_term_ids(chunk_stems: Sequence[Sequence[str] | None], ids: dict[str, int]):
+    """(flat term ids, offsets, live or None) of chunks given as index stems (None = a dead chunk) under the vocabulary `ids`."""
+    sizes = np.fromiter((len(stems) if stems is not None else 0 for stems in chunk_stems), dtype=np.int64, count=len(chunk_stems))
+    flat = np.fromiter((ids[s] for stems in chunk_stems if stems is not None for s in stems), dtype=np.int64, count=int(sizes.sum()))
+    live = np.fromiter((stems is not None for stems in chunk_stems), dtype=bool, count=len(chunk_stems))
+    offsets = np.concatenate(([0], np.cumsum(sizes))).astype(np.int64)
+    return flat, offsets, (None if live.all() else live)
 
 
 def build_from_stems(chunk_stems: Sequence[Sequence[str] | None]) -> tuple[list[str], Postings]:
     """(vocabulary, postings) of chunks given as their index stems; None marks a dead chunk (an ordinal with no text)."""
     vocab = sorted({s for stems in chunk_stems if stems is not None for s in stems})
-    ids = {s: i for i, s in enumerate(vocab)}
-    sizes = np.fromiter((len(stems) if stems is not None else 0 for stems in chunk_stems), dtype=np.int64, count=len(chunk_stems))
-    flat = np.fromiter((ids[s] for stems in chunk_stems if stems is not None for s in stems), dtype=np.int64, count=int(sizes.sum()))
-    live = np.fromiter((stems is not None for stems in chunk_stems), dtype=bool, count=len(chunk_stems))
-    offsets = np.concatenate(([0], np.cumsum(sizes))).astype(np.int64)
-    return vocab, build_from_term_ids(flat, offsets, len(vocab), None if live.all() else live)
+    flat, offsets, live = stems_to_term_ids(chunk_stems, {s: i for i, s in enumerate(vocab)})
+    return vocab, build_from_term_ids(flat, offsets, len(vocab), live)
 
 
 def build_from_texts(texts: Sequence[str | None]) -> tuple[list[str], Postings]:

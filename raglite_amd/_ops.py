@@ -225,6 +225,32 @@ def rrf_fuse(lists, weights, *, rrf_k: int = 60, k: int):
     return o_s, o_i, o_n
 
 
+def shard_hybrid_fuse(gathered, *, num_hits: int, n_each: int, keywords: bool, weights, rrf_k: int = 60, k: int):
+    """`rl_shard_hybrid_fuse`: the step after the one all-gather of a sharded hybrid batch.  `gathered`: (world, B, W) int32, what every
+    rank packed -- num_hits row records (score bits, global row, global chunk), then with `keywords` n_each keyword records (score bits,
+    global chunk): W = 3 num_hits (+ 2 n_each).  Returns (scores (B, k) float64, chunk ordinals (B, k) int32, counts (B,) int32) as
+    `DeviceIndex.hybrid_search` does; a query with a SHARD_MISSING record comes back poisoned (NaN, -1, 0).  `UnsupportedError` past
+    world * num_hits or world * n_each > 4096."""
+    a = _Args()
+    p_g = a.inp(gathered, np.int32)
+    if a.keep[0].ndim != 3:
+        raise ValueError("gathered must be (world, n_queries, W)")
+    world, B, W = (int(v) for v in a.keep[0].shape)
+    R = 2 if keywords else 1
+    if W != 3 * int(num_hits) + (2 * int(n_each) if keywords else 0):
+        raise ValueError("gathered: W must be 3 num_hits (+ 2 n_each with keywords)")
+    w = np.ascontiguousarray(np.asarray(weights, dtype=np.float64).ravel()[:R])  # (host memory, whatever side the records are on)
+    if w.size != R:
+        raise ValueError("one weight per list is required")
+    o_s, p_s = a.out((B, k), np.float64)
+    o_c, p_c = a.out((B, k), np.int32)
+    o_n, p_n = a.out((B,), np.int32)
+    a.ensure_device()
+    check(lib().rl_shard_hybrid_fuse(p_g, world, B, int(num_hits), int(n_each), R, w.ctypes.data, int(rrf_k), int(k), p_s, p_c, p_n, a.mem,
+                                     a.stream))
+    return o_s, o_c, o_n
+
+
 def _term_csr(query_term_ids) -> tuple[np.ndarray, np.ndarray]:
     """One sequence of term ids per query -> (q_off int64 [B + 1], q_terms int32), each query's ids ascending and distinct."""
     qs = [np.unique(np.asarray(q, dtype=np.int32)) for q in query_term_ids]

@@ -89,6 +89,54 @@ def group_chunk_max_host(row_scores: np.ndarray, row_chunks: np.ndarray, k: int)
     return out_s, out_c, keep.sum(axis=1).astype(np.int32)
 
 
+def _unpack_hybrid(g: np.ndarray, num_hits: int, n_each: int, keywords: bool):
+    """(world, B, W) packed records of a sharded hybrid batch -> (B, world * num_hits) row scores / rows / chunks and, with keywords,
+    (world, B, n_each) keyword scores / chunks."""
+    world, B, _ = g.shape
+    rows = g[:, :, : 3 * num_hits].reshape(world, B, num_hits, 3)
+
+    def flat(x):
+        return np.ascontiguousarray(np.transpose(x, (1, 0, 2))).reshape(B, world * num_hits)
+
+    rs = flat(np.ascontiguousarray(rows[..., 0]).view(np.float32))
+    rr, rc = flat(rows[..., 1]).astype(np.int64), flat(rows[..., 2]).astype(np.int64)
+    if not keywords:
+        return rs, rr, rc, None, None
+    kw = g[:, :, 3 * num_hits :].reshape(world, B, n_each, 2)
+    return rs, rr, rc, np.ascontiguousarray(kw[..., 0]).view(np.float32), np.ascontiguousarray(kw[..., 1])
+
+
+def compose_hybrid_fuse(gathered, *, num_hits: int, n_each: int, keywords: bool, weights, rrf_k: int = 60, k: int, rrf_fuse=None):
+    """What `rl_shard_hybrid_fuse` computes, composed from the existing pieces (the path past its limits, world * num_hits or
+    world * n_each > 4096): the row merge (`_merge_order`), `group_chunk_max_host`, the keyword merge (`merge_topk_host`), then
+    `rl_rrf_fuse`.  Host work; CUDA records in give CUDA results back."""
+    from . import _ops
+
+    cuda = _is_cuda(gathered)
+    g = _to_numpy(gathered).astype(np.int32, copy=False)
+    world, B, _ = g.shape
+    rs, rr, rc, ks, kc = _unpack_hybrid(g, num_hits, n_each, keywords)
+    order, n_valid = _merge_order(rs, rr, num_hits)  # the global top-num_hits rows of every query
+    real = np.arange(order.shape[1])[None, :] < n_valid[:, None]
+    ms = np.where(real, np.take_along_axis(rs, order, axis=1), -np.inf).astype(np.float32)
+    mc = np.where(real, np.take_along_axis(rc, order, axis=1), -1)
+    lists = [group_chunk_max_host(ms, mc, n_each)[1]]
+    missing = ((rr == SHARD_MISSING) | (rc == SHARD_MISSING)).any(axis=1)
+    if keywords:
+        lists.append(merge_topk_host(ks, kc, n_each)[1])
+        missing |= (kc == SHARD_MISSING).any(axis=(0, 2))
+    R = len(lists)
+    w = np.asarray(weights, dtype=np.float64).ravel()[:R]
+    o_s, o_c, o_n = (rrf_fuse or _ops.rrf_fuse)(np.stack(lists).astype(np.int32), w, rrf_k=rrf_k, k=k)
+    o_s, o_c, o_n = np.array(o_s), np.array(o_c), np.array(o_n)
+    o_s[missing], o_c[missing], o_n[missing] = np.nan, -1, 0  # poisoned, as the kernel does it
+    if cuda:
+        import torch
+
+        return tuple(torch.from_numpy(x).to(gathered.device) for x in (o_s, o_c, o_n))
+    return o_s, o_c, o_n
+
+
 def merge_order_torch(s, i, k: int):
     """`_merge_order` on torch tensors (any device, nothing synchronises with the host): three stable sorts, least significant
     key first -- id asc, score desc, then (padding, NaN) last."""
@@ -537,6 +585,194 @@ class ShardedIndex:
         except Exception as exc:  # noqa: BLE001 - one more collective (the merge) is still ahead of every rank
             self._deferred_error = exc
             return empty_lists()
+
+    # -- the keyword side: BM25 with the statistics of the WHOLE corpus ---------------------------------------------------------
+    keyword = None     # this shard's KeywordIndex (None before attach_keywords, and on a shard without chunks)
+    _kw_vocab = None   # stem -> global term id
+    shard_fuse = None  # None: rl_shard_hybrid_fuse (`_ops.shard_hybrid_fuse`); a callable of the same signature stands in for it
+
+    def _n_local_chunks(self) -> int:
+        return (len(self.local_chunk_offsets) - 1) if self.local_chunk_offsets is not None else int(self.local.n_chunks)
+
+    def _exchange_vocab(self, local_vocab: list[str]) -> list[str]:
+        """The sorted union of every rank's stems: UTF-8, each stem NUL-terminated, packed into int32 words; sizes first."""
+        blob = "".join(st + "\0" for st in local_vocab).encode("utf-8")
+        sizes = self._allgather_host(np.asarray([len(blob)], dtype=np.int32)).reshape(-1).astype(np.int64)
+        buf = np.zeros(4 * max(1, -(-int(sizes.max()) // 4)), dtype=np.uint8)
+        buf[: len(blob)] = np.frombuffer(blob, dtype=np.uint8)
+        g = self._allgather_host(buf.view(np.int32))  # (world, words)
+        union: set[str] = set()
+        for r in range(g.shape[0]):
+            text = np.ascontiguousarray(g[r]).view(np.uint8)[: int(sizes[r])].tobytes().decode("utf-8")
+            union.update(text.split("\0")[:-1])
+        return sorted(union)
+
+    def attach_keywords(self, chunk_stems, *, make_index=None) -> None:
+        """Collective: the BM25 keyword side of this shard, with the statistics of the WHOLE corpus.  `chunk_stems`: the index stems of
+        this shard's chunks in local order (`_keyword.index_stems(body)`; None for a dead chunk), as `GpuIndex._kw_stems` holds them.
+        Every rank (1) agrees on one vocabulary, the sorted union of all live stems -- term ids are the ranks in it, the ids one index
+        over the whole corpus assigns; (2) sums df per term, N and the total stem count over the ranks, the counts exchanged as int64;
+        (3) builds its own postings over local chunk ordinals with idf and nrm from those global values
+        (`_keyword.build_shard_from_term_ids`): every impact is bitwise the one a single index over everything computes.  Inserts and
+        deletes change N and avgdl, so every shard's impacts: call it again on every rank after any.  `make_index` (Postings ->
+        an object with `search(query_term_ids, k, chunk_filter)`): default `raglite_amd.KeywordIndex`."""
+        from . import _keyword, _ops
+
+        stems = list(chunk_stems)
+        if len(stems) != self._n_local_chunks():
+            raise ValueError("attach_keywords needs one entry (stems or None) per local chunk")
+        vocab = self._exchange_vocab(sorted({st for ss in stems if ss is not None for st in ss}))
+        ids = {st: i for i, st in enumerate(vocab)}
+        flat, offsets, live = _keyword.stems_to_term_ids(stems, ids)
+        mine = _keyword.shard_counts(flat, offsets, len(vocab), live)
+        head = np.asarray([mine.n_live, mine.total_length], dtype=np.int64).view(np.int32)  # (int64 counts as two int32 words each)
+        g = self._allgather_host(np.concatenate([head, mine.df.astype(np.int32)]))  # (world, 4 + n_terms)
+        heads = np.ascontiguousarray(g[:, :4]).view(np.int64)  # (world, 2)
+        corpus = _keyword.ShardCounts(g[:, 4:].astype(np.int64).sum(axis=0), int(heads[:, 0].sum()), int(heads[:, 1].sum()))
+        postings = _keyword.build_shard_from_term_ids(flat, offsets, len(vocab), live, corpus)
+        new = (make_index or _ops.KeywordIndex)(postings) if len(stems) else None
+        old, self.keyword, self._kw_vocab = self.keyword, new, ids
+        self._kw_attached = True
+        if old is not None and hasattr(old, "close"):
+            old.close()
+
+    def keyword_query_ids(self, query: str) -> list[int]:
+        """The global term ids of a query (`GpuIndex.keyword_query_ids`: distinct stems, those outside the vocabulary dropped)."""
+        from . import _keyword
+
+        self._require_keywords()
+        return sorted(self._kw_vocab[st] for st in _keyword.query_stems(query) if st in self._kw_vocab)
+
+    def _require_keywords(self) -> None:
+        if not getattr(self, "_kw_attached", False):
+            raise ValueError("ShardedIndex: call attach_keywords (on every rank) first")
+
+    def _local_keyword(self, query_term_ids, k: int, local_filter):
+        """This shard's BM25 top-k, LOCAL chunk ordinals: (scores (B, k) float32, chunks (B, k) int32)."""
+        B = len(query_term_ids)
+        if self.keyword is None:  # (a shard without chunks)
+            return np.full((B, k), -np.inf, np.float32), np.full((B, k), -1, np.int32)
+        s, c, _ = self.keyword.search(query_term_ids, k, chunk_filter=local_filter)
+        return np.asarray(s, np.float32), np.asarray(c, np.int32)
+
+    def keyword_search(self, query_term_ids, k: int, chunk_filter=None):
+        """Global BM25 top-k: (scores (B, k) float32, GLOBAL chunk ordinals (B, k) int32, counts (B,) int32), padded with (-inf, -1) --
+        bit for bit what `KeywordIndex.search` over the whole corpus returns.  `query_term_ids`: one sequence of GLOBAL term ids per query
+        (`keyword_query_ids`); chunk_filter as in `search_rows`.  Each rank searches its shard, ONE all-gather, the host merge by (score
+        desc, chunk asc).  A rank that fails locally still enters the exchange (ids SHARD_MISSING) and raises afterwards; the others get
+        poisoned queries (NaN, -1, count 0) -- and raise too with `check_failures`."""
+        self._require_keywords()
+        local_filter = self._local_filter(chunk_filter)
+        B = len(query_term_ids)
+        self._deferred_error = None
+        try:
+            s, c = self._local_keyword(query_term_ids, k, local_filter)
+        except Exception as exc:  # noqa: BLE001 - the other ranks are about to wait in the all-gather
+            self._deferred_error = exc
+            s, c = np.full((B, k), -np.inf, np.float32), np.full((B, k), SHARD_MISSING, np.int32)
+        gs, gi, _, _ = self._exchange_host(s.reshape(B, k), c.reshape(B, k), self.chunk_base)
+        ms, mi = merge_topk_host(gs, gi, k)
+        mi = mi.astype(np.int32)
+        counts = (mi >= 0).sum(axis=1).astype(np.int32)
+        missing = (gi == SHARD_MISSING).any(axis=(0, 2))
+        ms[missing], mi[missing], counts[missing] = np.nan, -1, 0
+        if self._deferred_error is None and self.check_failures and bool(missing.any()):
+            self._deferred_error = RuntimeError("ShardedIndex.keyword_search: another rank failed in its local step; this merge lacks its shard")
+        self._raise_deferred()
+        return ms, mi, counts
+
+    def hybrid_search(self, queries, query_term_ids, num_hits: int, n_each: int, k: int, *, weights=(0.75, 0.25), rrf_k: int = 60,
+                      chunk_filter=None, rank_limit: int | None = None):
+        """`DeviceIndex.hybrid_search` over the sharded corpus, bit for bit what ONE index plus keyword index over everything returns with
+        the same arguments: (scores (B, k) float64, GLOBAL chunk ordinals (B, k) int32, counts (B,) int32).  `query_term_ids`: one sequence
+        of global term ids per query (`keyword_query_ids`), or None for the vector list alone (weights[0]).  Each rank takes its num_hits
+        rows (`_local_rows_ranked`: with rank_limit the staged GLOBAL cut) and its n_each keyword results; both halves travel in ONE packed
+        int32 all-gather; `rl_shard_hybrid_fuse` merges, groups by chunk and fuses (past its limits `compose_hybrid_fuse`).  CUDA queries:
+        records and results stay on the device.  A rank that fails locally sends SHARD_MISSING ids and raises afterwards; the others get
+        poisoned queries (every score NaN, every id -1) -- and raise too with `check_failures`."""
+        from ._abi import UnsupportedError
+
+        if self.local_chunk_offsets is None:
+            raise ValueError("hybrid_search needs local_chunk_offsets")
+        keywords = query_term_ids is not None
+        if keywords:
+            self._require_keywords()
+        single = getattr(queries, "ndim", 2) == 1
+        B = 1 if single else int(queries.shape[0])
+        if keywords and len(query_term_ids) != B:
+            raise ValueError("one sequence of term ids per query is required")
+        num_hits, n_each = int(num_hits), int(n_each)
+        local_filter = self._local_filter(chunk_filter)
+        cuda = _is_cuda(queries)
+        self._deferred_error = None
+        try:
+            s, r = self._local_rows_ranked(queries, num_hits, chunk_filter, rank_limit)
+        except Exception as exc:  # noqa: BLE001 - the other ranks are about to wait in the all-gather
+            self._deferred_error, s, r = exc, None, None
+        kw = None
+        if keywords:
+            try:
+                kw = self._local_keyword(query_term_ids, n_each, local_filter)
+            except Exception as exc:  # noqa: BLE001
+                self._deferred_error = self._deferred_error or exc
+        failed = self._deferred_error is not None
+        if cuda:
+            import torch
+
+            dev = queries.device
+            if failed:
+                rows = torch.full((B, num_hits, 3), SHARD_MISSING, dtype=torch.int32, device=dev)
+                rows[..., 0] = torch.tensor(float("-inf")).view(torch.int32)
+            else:
+                s2, r2 = s.reshape(B, num_hits), r.reshape(B, num_hits).to(torch.int64)
+                loc = torch.as_tensor(self.local_chunk_offsets, device=dev)
+                cl = torch.searchsorted(loc, r2.clamp(min=0), right=True) - 1
+                gr = torch.where(r2 >= 0, r2 + self.row_base, r2)
+                gc = torch.where(r2 >= 0, cl + self.chunk_base, r2)
+                rows = torch.stack([s2.to(torch.float32).contiguous().view(torch.int32), gr.to(torch.int32), gc.to(torch.int32)], dim=-1)
+            parts = [rows.reshape(B, 3 * num_hits)]
+        else:
+            if failed:
+                rows = np.full((B, num_hits, 3), SHARD_MISSING, dtype=np.int32)
+                rows[..., 0] = np.float32(-np.inf).view(np.int32)
+            else:
+                s2 = _to_numpy(s).astype(np.float32, copy=False).reshape(B, num_hits)
+                r2 = _to_numpy(r).astype(np.int64).reshape(B, num_hits)
+                cl = np.searchsorted(self.local_chunk_offsets, r2, side="right") - 1
+                rows = self._pack(s2, np.where(r2 >= 0, r2 + self.row_base, r2), np.where(r2 >= 0, cl + self.chunk_base, r2))
+            parts = [rows.reshape(B, 3 * num_hits)]
+        if keywords:
+            if failed:
+                ks, kc = np.full((B, n_each), -np.inf, np.float32), np.full((B, n_each), SHARD_MISSING, np.int32)
+            else:
+                ks, kc = kw
+                kc = np.where(kc >= 0, kc.astype(np.int64) + self.chunk_base, kc)
+            kp = self._pack(ks.reshape(B, n_each), kc.reshape(B, n_each)).reshape(B, 2 * n_each)
+            if cuda:
+                import torch
+
+                kp = torch.from_numpy(kp).to(queries.device)
+            parts.append(kp)
+        if cuda:
+            import torch
+
+            packed = torch.cat(parts, dim=1).contiguous()
+        else:
+            packed = np.ascontiguousarray(np.concatenate(parts, axis=1), dtype=np.int32)
+        g = self._allgather_int(packed)  # ONE exchange: (world, B, W)
+        args = dict(num_hits=num_hits, n_each=n_each, keywords=keywords, weights=weights, rrf_k=int(rrf_k), k=int(k))
+        from . import _ops
+
+        try:
+            out = (self.shard_fuse or _ops.shard_hybrid_fuse)(g, **args)
+        except UnsupportedError:  # world * num_hits or world * n_each > 4096
+            out = compose_hybrid_fuse(g, **args)
+        if self._deferred_error is None and self.check_failures and self._world() > 1:
+            lost = (bool(torch.isnan(out[0]).any().item()) if cuda else bool(np.isnan(_to_numpy(out[0])).any()))
+            if lost:
+                self._deferred_error = RuntimeError("ShardedIndex.hybrid_search: another rank failed in its local step; this fusion lacks its shard")
+        self._raise_deferred()
+        return tuple(o[0] for o in out) if single else out
 
     def search_chunks(self, queries, num_hits: int, k: int, chunk_filter=None, rank_limit: int | None = None):
         """Reference two-stage semantics across shards (`src/raglite/_search.py:66-79,143-149`; chunk_filter / rank_limit as in

@@ -3147,6 +3147,37 @@ int rl_rrf_fuse(const int32_t* lists, int32_t n_lists, int32_t n_queries, int32_
     return finish(mem, s);
 }
 
+int rl_shard_hybrid_fuse(const int32_t* gathered, int32_t world, int32_t n_queries, int32_t num_hits, int32_t n_each, int32_t n_lists,
+                         const double* weights, int32_t rrf_k, int32_t k, double* out_scores, int32_t* out_chunks, int32_t* out_counts, int mem,
+                         void* stream) {
+    const char* who = "rl_shard_hybrid_fuse";
+    if (world < 1) return fail(RL_ERR_INVALID, "rl_shard_hybrid_fuse: world must be >= 1");
+    if (n_lists != 1 && n_lists != 2) return fail(RL_ERR_INVALID, "rl_shard_hybrid_fuse: n_lists must be 1 or 2");
+    if (num_hits < 1) return fail(RL_ERR_INVALID, "rl_shard_hybrid_fuse: num_hits must be >= 1");
+    RL_TRY(check_fuse_args(n_lists, n_queries, n_each, weights, rrf_k, k, who));
+    if (mem != RL_MEM_HOST && mem != RL_MEM_DEVICE) return fail(RL_ERR_INVALID, "rl_shard_hybrid_fuse: bad mem");
+    if ((int64_t)world * num_hits > SHARD_FUSE_MAX_ENTRIES || (n_lists == 2 && (int64_t)world * n_each > SHARD_FUSE_MAX_ENTRIES))
+        return fail(RL_ERR_UNSUPPORTED, "rl_shard_hybrid_fuse: world * num_hits and world * n_each must be <= 4096");
+    if (n_queries == 0) return RL_OK;
+    if (!gathered || !out_scores || !out_chunks) return fail(RL_ERR_INVALID, "rl_shard_hybrid_fuse: null argument");
+    hipStream_t s = as_stream(stream);
+    const size_t W = (size_t)3 * num_hits + (n_lists == 2 ? (size_t)2 * n_each : 0);
+    const size_t n_in = (size_t)world * n_queries * W, n_out = (size_t)n_queries * k;
+    DevBuf t_g, t_s, t_c, t_n;
+    const int32_t* d_g;
+    double* d_s;
+    int32_t *d_c, *d_n = nullptr;
+    RL_TRY(stage_in(gathered, n_in, mem, s, t_g, &d_g));
+    RL_TRY(stage_out_begin(out_scores, n_out, mem, t_s, &d_s));
+    RL_TRY(stage_out_begin(out_chunks, n_out, mem, t_c, &d_c));
+    if (out_counts) RL_TRY(stage_out_begin(out_counts, (size_t)n_queries, mem, t_n, &d_n));
+    RL_TRY(launch_shard_hybrid_fuse(d_g, world, n_queries, num_hits, n_each, n_lists, weights, rrf_k, k, d_s, d_c, d_n, s));
+    RL_TRY(stage_out_end(out_scores, n_out, mem, s, t_s));
+    RL_TRY(stage_out_end(out_chunks, n_out, mem, s, t_c));
+    if (out_counts) RL_TRY(stage_out_end(out_counts, (size_t)n_queries, mem, s, t_n));
+    return finish(mem, s);
+}
+
 int rl_hybrid_search(rl_index* idx, rl_keyword_index* kw, const float* queries, int32_t n_queries, int32_t num_hits, int32_t n_each,
                      const int64_t* q_off, const int32_t* q_terms, const uint32_t* chunk_filter, int64_t rank_limit, const double* weights,
                      int32_t rrf_k, int32_t k, double* out_scores, int32_t* out_chunks, int32_t* out_counts, int mem, void* stream) {

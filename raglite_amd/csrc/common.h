@@ -333,6 +333,12 @@ constexpr int32_t RRF_MAX_K = 1 << 30;       // rrf_k + rank stays an exact int3
 constexpr double RRF_MAX_WEIGHT = 0x1p1000;  // |w| <= 2^1000: no sum of 4096 terms w / (rrf_k + i) overflows
 int launch_rrf_fuse(const int32_t* lists, int32_t n_lists, int32_t n_queries, int32_t len, const double* weights /* host */, int32_t rrf_k,
                     int32_t k, double* out_scores, int32_t* out_ids, int32_t* out_counts, hipStream_t s);
+// ... and the step after the one all-gather of a sharded hybrid batch (rl_shard_hybrid_fuse): merge the rows, group them by chunk, merge
+// the keyword lists, then the same fusion; RL_ERR_UNSUPPORTED past world * num_hits or world * n_each > SHARD_FUSE_MAX_ENTRIES
+constexpr int32_t SHARD_FUSE_MAX_ENTRIES = 4096;
+int launch_shard_hybrid_fuse(const int32_t* gathered, int32_t world, int32_t n_queries, int32_t num_hits, int32_t n_each, int32_t n_lists,
+                             const double* weights /* host */, int32_t rrf_k, int32_t k, double* out_scores, int32_t* out_ids,
+                             int32_t* out_counts, hipStream_t s);
 
 // adapter_fit.hip: device half of update_query_adapter (best row per (query, chunk), row gather)
 int launch_chunk_best_rows(const void* E, bool f16, int32_t dim, const float* Q, const int64_t* offsets,
