@@ -556,6 +556,35 @@ int rl_search_chunks_ranked(rl_index* index, const float* queries, int32_t n_que
                             int32_t k, const uint32_t* chunk_filter, int64_t rank_limit, float* out_scores,
                             int32_t* out_chunks, int32_t* out_counts, int mem, void* stream);
 
+/* ---- per-query metadata filters and rank limits in one batch ------------------------------------------
+ * The *_per_query calls are rl_search_chunks_ranked, rl_keyword_search and rl_hybrid_search with a filter SET in place of
+ * chunk_filter and one rank limit per query: query b of the batch gets bit for bit what the single-query call returns for
+ * it alone, with its own filter and limit (the same ids, score bits and count).  The single-filter calls run the same
+ * device path (one filter, every query mapped to it, one limit for all).
+ *   chunk_filters  uint32 [n_filters x (n_chunks + 31) / 32], each row a bitset as in the *_filtered calls; host or
+ *                  device memory per `mem`.  NULL only when n_filters == 0.
+ *   query_filter   int32 [n_queries], ALWAYS host memory: -1 = the query has no filter, else a row of chunk_filters.
+ *                  NULL: no query has a filter.
+ *   rank_limits    int64 [n_queries], ALWAYS host memory (not in the keyword call): each >= 0, as rank_limit of
+ *                  rl_search_rows_ranked -- 0 or a limit at or above the live rows: no cut.  NULL: no cut for any query.
+ * Tombstoned chunks never match, whether or not a query has a filter.  These arguments are checked before the index is
+ * looked at and before any HIP call (RL_ERR_INVALID, naming the argument).  The host plans each sub-batch of queries:
+ * its distinct filters are expanded to row bitsets (index-owned scratch, counted in rl_index_memory out[4]) in one launch,
+ * and a sub-batch with a cut takes the score-matrix route with the cut, as rank_limit does; where every query of a
+ * sub-batch has no filter and no cut, it runs exactly as the unfiltered call. */
+int rl_search_chunks_per_query(rl_index* index, const float* queries, int32_t n_queries, int32_t num_hits, int32_t k,
+                               const uint32_t* chunk_filters, int32_t n_filters, const int32_t* query_filter,
+                               const int64_t* rank_limits, float* out_scores, int32_t* out_chunks, int32_t* out_counts,
+                               int mem, void* stream);
+int rl_keyword_search_per_query(rl_keyword_index* kw, const int64_t* q_off, const int32_t* q_terms, int32_t n_queries,
+                                int32_t k, const uint32_t* chunk_filters, int32_t n_filters, const int32_t* query_filter,
+                                float* out_scores, int32_t* out_chunks, int32_t* out_counts, int mem, void* stream);
+int rl_hybrid_search_per_query(rl_index* index, rl_keyword_index* kw, const float* queries, int32_t n_queries,
+                               int32_t num_hits, int32_t n_each, const int64_t* q_off, const int32_t* q_terms,
+                               const uint32_t* chunk_filters, int32_t n_filters, const int32_t* query_filter,
+                               const int64_t* rank_limits, const double* weights, int32_t rrf_k, int32_t k,
+                               double* out_scores, int32_t* out_chunks, int32_t* out_counts, int mem, void* stream);
+
 /* ---- device half of update_query_adapter ----------------------------------
  * src/raglite/_query_adapter.py:153-205 fits the query adapter from evals: per eval a vector search
  * (rl_search_chunks, batched over all evals), then for every retrieved chunk the row

@@ -36,6 +36,7 @@ from raglite_amd._search import (
     hybrid_search,
     hybrid_search_batch,
     keyword_search,
+    keyword_search_batch,
     reciprocal_rank_fusion,
     GpuVectorSearch,
     MaxSimRanker,
@@ -46,6 +47,7 @@ from raglite_amd._search import (
     select_reranker,
     set_language_detector,
     vector_search,
+    vector_search_batch,
 )
 from raglite_amd._cross_encoder import CrossEncoderShape, TorchCrossEncoderRanker
 from raglite_amd._torch_embedder import EncoderShape, HashTokenizer, SentencePieceTokenizer, TorchTokenEmbedder
@@ -63,6 +65,8 @@ __all__ = [
     "hybrid_search",
     "hybrid_search_batch",
     "keyword_search",
+    "keyword_search_batch",
+    "vector_search_batch",
     "KeywordIndex",
     "reciprocal_rank_fusion",
     "update_query_adapter",

@@ -120,6 +120,12 @@ _SIGNATURES = {
                              c_void_p],
     "rl_hybrid_search": [c_void_p, c_void_p, c_void_p, c_i32, c_i32, c_i32, c_void_p, c_void_p, c_void_p, c_i64, c_void_p, c_i32, c_i32,
                          c_void_p, c_void_p, c_void_p, c_int, c_void_p],
+    "rl_search_chunks_per_query": [c_void_p, c_void_p, c_i32, c_i32, c_i32, c_void_p, c_i32, c_void_p, c_void_p, c_void_p, c_void_p,
+                                   c_void_p, c_int, c_void_p],
+    "rl_keyword_search_per_query": [c_void_p, c_void_p, c_void_p, c_i32, c_i32, c_void_p, c_i32, c_void_p, c_void_p, c_void_p, c_void_p,
+                                    c_int, c_void_p],
+    "rl_hybrid_search_per_query": [c_void_p, c_void_p, c_void_p, c_i32, c_i32, c_i32, c_void_p, c_void_p, c_void_p, c_i32, c_void_p,
+                                   c_void_p, c_void_p, c_i32, c_i32, c_void_p, c_void_p, c_void_p, c_int, c_void_p],
 }
 COMM_ID_BYTES = 128
 _RESTYPES = {"rl_last_error": c_char_p}

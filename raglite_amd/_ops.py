@@ -273,6 +273,51 @@ def pack_bits(mask) -> np.ndarray:
     return np.ascontiguousarray(b).view(np.uint32)
 
 
+def filter_set(query_filters, n_chunks: int, B: int) -> tuple[np.ndarray, np.ndarray]:
+    """Per-query filters (B entries, each None or a bool mask over chunks / packed uint32 bitset) -> (bitsets uint32 [F, words], one per
+    distinct filter -- identical masks are sent once, deduplicated by their packed bits -- and query_filter int32 [B], -1 = no filter)."""
+    filters = list(query_filters)
+    if len(filters) != B:
+        raise ValueError(f"query_filters must have one entry per query ({len(filters)} for {B} queries)")
+    words = (n_chunks + 31) // 32
+    rows: list[np.ndarray] = []
+    seen: dict[tuple, list[int]] = {}  # a cheap fingerprint -> the rows that have it (equal bits are then compared in full)
+    query_filter = np.full(B, -1, np.int32)
+    by_object: dict[int, int] = {}  # (a mask object shared by many queries is packed once)
+    for b, f in enumerate(filters):
+        if f is None:
+            continue
+        if id(f) in by_object:
+            query_filter[b] = by_object[id(f)]
+            continue
+        bits = pack_bits(f)
+        if bits.size != words:
+            raise ValueError("chunk_filter must have one entry per chunk")
+        key = (int(bits.sum(dtype=np.uint64)), int(bits[0]) if words else 0, int(bits[-1]) if words else 0)
+        same = [j for j in seen.get(key, ()) if np.array_equal(rows[j], bits)]
+        if same:
+            j = same[0]
+        else:
+            j = len(rows)
+            seen.setdefault(key, []).append(j)
+            rows.append(bits)
+        query_filter[b] = by_object[id(f)] = j
+    table = np.empty((len(rows), words), np.uint32)
+    for j, r in enumerate(rows):
+        table[j] = r
+    return table, query_filter
+
+
+def _rank_limits(rank_limit, B: int) -> np.ndarray | None:
+    """rank_limit as an int (or None) for every query, or a length-B sequence -> int64 [B] for the *_per_query calls (None: no array)."""
+    if rank_limit is None or np.ndim(rank_limit) == 0:
+        return None if not rank_limit else np.full(B, int(rank_limit), np.int64)
+    lim = np.asarray([0 if r is None else int(r) for r in rank_limit], dtype=np.int64)
+    if lim.size != B:
+        raise ValueError(f"rank_limit must be an int or have one entry per query ({lim.size} for {B} queries)")
+    return lim
+
+
 class DeviceIndex:
     """Device-resident chunk-embedding matrix + chunk CSR: the GPU image of the reference's
     `chunk_embedding` table (`src/raglite/_database.py:403-430`).
@@ -370,6 +415,28 @@ class DeviceIndex:
             return t.data_ptr()
         a.keep.append(bits)
         return bits.ctypes.data
+
+    def _per_query(self, a: _Args, B: int, chunk_filter, query_filters, rank_limit):
+        """The filter arguments of a call that takes per-query filters or limits -> (per_query, args): per_query False keeps the
+        single-filter entry point with args (chunk filter pointer, rank limit); True gives (bitsets pointer, n_filters, query_filter
+        pointer, rank_limits pointer) for the *_per_query one."""
+        if query_filters is None and (rank_limit is None or np.ndim(rank_limit) == 0):
+            return False, (self._filter(a, chunk_filter), int(rank_limit or 0))
+        if query_filters is not None and chunk_filter is not None:
+            raise ValueError("pass chunk_filter (one for the batch) or query_filters (one per query), not both")
+        table, qf = filter_set([chunk_filter] * B if query_filters is None else query_filters, self.n_chunks, B)
+        lim = _rank_limits(rank_limit, B)
+        a.keep += [qf, lim]
+        p_f = None
+        if len(table):
+            if a.mem == MEM_DEVICE:
+                t = _torch().from_numpy(table.view(np.int32)).to(a.device)
+                a.keep.append(t)
+                p_f = t.data_ptr()
+            else:
+                a.keep.append(table)
+                p_f = table.ctypes.data
+        return True, (p_f, len(table), qf.ctypes.data, None if lim is None else lim.ctypes.data)
 
     # -- lifecycle (SURVEY.md 8f-1) ---------------------------------------------------------------
     def append(self, rows, chunk_sizes=None) -> None:
@@ -571,32 +638,38 @@ class DeviceIndex:
         return o_s, o_r
 
     # -- a6 + a7 + a8 ----------------------------------------------------------------------------
-    def search_chunks(self, queries, num_hits: int, k: int, chunk_filter=None, rank_limit: int | None = None):
+    def search_chunks(self, queries, num_hits: int, k: int, chunk_filter=None, rank_limit=None, *, query_filters=None):
         """Reference two-stage semantics (`src/raglite/_search.py:66-79,143-149`; with chunk_filter the
         filter-first branch `:105-119`, with rank_limit the order-first-then-filter branch `:120-141`): returns
-        (scores (B,k), chunk ordinals (B,k), counts (B,))."""
+        (scores (B,k), chunk ordinals (B,k), counts (B,)).  Per query (`rl_search_chunks_per_query`): `query_filters` holds one entry
+        per query, None or a mask / packed bitset, and `rank_limit` may be a length-B sequence (0 or None: no cut); row b is then
+        what the call for query b alone with its own filter and limit returns."""
         a = _Args()
         p_q, B, single = self._queries(a, queries)
         o_s, p_s = a.out((B, k), np.float32)
         o_c, p_c = a.out((B, k), np.int32)
         o_n, p_n = a.out((B,), np.int32)
-        p_f = self._filter(a, chunk_filter)
+        per_query, args = self._per_query(a, B, chunk_filter, query_filters, rank_limit)
         self._prep(a)
-        check(lib().rl_search_chunks_ranked(self._handle, p_q, B, num_hits, k, p_f, int(rank_limit or 0), p_s, p_c, p_n,
-                                            a.mem, a.stream))
+        if per_query:
+            check(lib().rl_search_chunks_per_query(self._handle, p_q, B, num_hits, k, *args, p_s, p_c, p_n, a.mem, a.stream))
+        else:
+            check(lib().rl_search_chunks_ranked(self._handle, p_q, B, num_hits, k, *args, p_s, p_c, p_n, a.mem, a.stream))
         return (o_s[0], o_c[0], o_n[0]) if single else (o_s, o_c, o_n)
 
     def hybrid_search(self, queries, num_hits: int, n_each: int, k: int, *, keyword: "KeywordIndex | None" = None, query_term_ids=None,
-                      weights=(0.75, 0.25), rrf_k: int = 60, chunk_filter=None, rank_limit: int | None = None):
+                      weights=(0.75, 0.25), rrf_k: int = 60, chunk_filter=None, rank_limit=None, query_filters=None):
         """`rl_hybrid_search`: per query the n_each best chunks of the two-stage vector search (as `search_chunks`) and, with `keyword`,
         the n_each best of BM25 over `query_term_ids` (one sequence per query), fused by weighted RRF on the device; `weights` are
-        (vector,) or (vector, keyword).  Returns (scores (B, k) float64, chunk ordinals (B, k) int32, counts (B,) int32)."""
+        (vector,) or (vector, keyword).  Returns (scores (B, k) float64, chunk ordinals (B, k) int32, counts (B,) int32).
+        `query_filters` / a sequence `rank_limit`: per query, as in `search_chunks` (`rl_hybrid_search_per_query`); the keyword half
+        takes the same filters."""
         a = _Args()
         p_q, B, single = self._queries(a, queries)
         o_s, p_s = a.out((B, k), np.float64)
         o_c, p_c = a.out((B, k), np.int32)
         o_n, p_n = a.out((B,), np.int32)
-        p_f = self._filter(a, chunk_filter)
+        per_query, args = self._per_query(a, B, chunk_filter, query_filters, rank_limit)
         w = np.ascontiguousarray(np.asarray(weights, dtype=np.float64).ravel()[: 2 if keyword is not None else 1])
         p_off = p_terms = None
         if keyword is not None:
@@ -612,8 +685,9 @@ class DeviceIndex:
                 p_off, p_terms = q_off.ctypes.data, q_terms.ctypes.data
             a.keep += [q_off, q_terms]
         self._prep(a)
-        check(lib().rl_hybrid_search(self._handle, None if keyword is None else keyword._handle, p_q, B, int(num_hits), int(n_each), p_off,
-                                     p_terms, p_f, int(rank_limit or 0), w.ctypes.data, int(rrf_k), int(k), p_s, p_c, p_n, a.mem, a.stream))
+        fn = lib().rl_hybrid_search_per_query if per_query else lib().rl_hybrid_search
+        check(fn(self._handle, None if keyword is None else keyword._handle, p_q, B, int(num_hits), int(n_each), p_off, p_terms, *args,
+                 w.ctypes.data, int(rrf_k), int(k), p_s, p_c, p_n, a.mem, a.stream))
         return (o_s[0], o_c[0], o_n[0]) if single else (o_s, o_c, o_n)
 
     # -- a9 ----------------------------------------------------------------------------------------
@@ -790,21 +864,30 @@ class KeywordIndex:
         except Exception:  # noqa: BLE001,S110 - interpreter shutdown
             pass
 
-    def search(self, query_term_ids, k: int, chunk_filter=None):
+    def search(self, query_term_ids, k: int, chunk_filter=None, *, query_filters=None):
         """BM25 top-k of a batch: `query_term_ids` holds one sequence of term ids per query (duplicates are dropped, order does not
-        matter).  Returns (scores (B,k) float32, chunk ordinals (B,k) int32, counts (B,) int32); unfilled slots are (-inf, -1)."""
+        matter).  Returns (scores (B,k) float32, chunk ordinals (B,k) int32, counts (B,) int32); unfilled slots are (-inf, -1).
+        `query_filters`: one entry per query, None or a mask / packed bitset (`rl_keyword_search_per_query`)."""
         q_off, q_terms = _term_csr(query_term_ids)
         B = int(q_off.size - 1)
         scores = np.empty((B, k), np.float32)
         chunks = np.empty((B, k), np.int32)
         counts = np.empty(B, np.int32)
+        _ensure_init(_current_device())
+        if query_filters is not None:
+            if chunk_filter is not None:
+                raise ValueError("pass chunk_filter (one for the batch) or query_filters (one per query), not both")
+            table, qf = filter_set(query_filters, self.n_chunks, B)
+            check(lib().rl_keyword_search_per_query(self._handle, q_off.ctypes.data, q_terms.ctypes.data, B, k,
+                                                    table.ctypes.data if len(table) else None, len(table), qf.ctypes.data,
+                                                    scores.ctypes.data, chunks.ctypes.data, counts.ctypes.data, MEM_HOST, None))
+            return scores, chunks, counts
         p_f = None
         if chunk_filter is not None:
             bits = pack_bits(chunk_filter)
             if bits.size != (self.n_chunks + 31) // 32:
                 raise ValueError("chunk_filter must have one entry per chunk")
             p_f = bits.ctypes.data
-        _ensure_init(_current_device())
         check(lib().rl_keyword_search(self._handle, q_off.ctypes.data, q_terms.ctypes.data, B, k, p_f, scores.ctypes.data,
                                       chunks.ctypes.data, counts.ctypes.data, MEM_HOST, None))
         return scores, chunks, counts

@@ -6,6 +6,8 @@
         -> (list[ChunkId], list[float])   BM25 on the device               (`_search.py:156-230`)
     hybrid_search(...)                                                    (`_search.py:255-279`)
     hybrid_search_batch(queries, ...) -> list of hybrid_search's results, one device round trip for the batch
+    vector_search_batch / keyword_search_batch(queries, ...) -> the same for vector_search / keyword_search
+                                                            (the batched searches take one metadata filter per query)
     rerank_chunks(query, chunk_ids, *, config=None) -> list[chunk]        (`_search.py:364-397`)
     search_and_rerank_chunks(...)                                         (`_search.py:400-414`)
     GpuVectorSearch   -- a `BasicSearchMethod` (`_typing.py:35-43`) for `RAGLiteConfig.search_method`
@@ -314,6 +316,15 @@ def _check_limits(num_hits: int, num_results: int) -> None:
                          f"{_ops.K_MAX} the exact top-k kernel ranks; lower num_results or oversample")
 
 
+_NO_METADATA = "GpuIndex was built without `metadata`; metadata_filter cannot be applied"
+_NO_KEYWORDS = "GpuIndex was built without keyword texts: pass keyword_texts= or from_store(..., keywords=True)"
+
+
+def _keyword_limit_message(num_results: int) -> str:
+    return (f"keyword_search: num_results={num_results} is more than the {_ops.K_MAX} the exact top-k kernel ranks; "
+            "lower num_results")
+
+
 FILTER_FIRST_MAX_ROWS = 100_000  # `metadata_count <= 100_000` (`src/raglite/_search.py:105`)
 ORDER_FIRST_LIMIT = 1_000_000    # `.limit(1_000_000)` (`src/raglite/_search.py:124`)
 
@@ -325,7 +336,7 @@ def _filtered_search(gi: GpuIndex, q, num_hits: int, num_results: int, flt: dict
     1 000 000 rows nearest to the query are eligible, then the filter (`:120-141`).  Both branches rank exactly; they
     differ only on a corpus of more than 1 000 000 rows."""
     if gi.metadata is None:
-        raise ValueError("GpuIndex was built without `metadata`; metadata_filter cannot be applied")
+        raise ValueError(_NO_METADATA)
     allowed = np.fromiter((_matches(m, flt) for m in gi.metadata), dtype=bool, count=len(gi.metadata))
     if not allowed.any():
         return [], []
@@ -350,19 +361,18 @@ def keyword_search(query: str, *, num_results: int = 3, metadata_filter: dict | 
     if getattr(cfg, "self_query", False) and isinstance(query, str):
         raise NotImplementedError("self_query needs the LLM stack, which is outside this package")
     if not gi.has_keywords:
-        raise ValueError("GpuIndex was built without keyword texts: pass keyword_texts= or from_store(..., keywords=True)")
+        raise ValueError(_NO_KEYWORDS)
     if num_results < 1:
         return [], []
     if num_results > _ops.K_MAX:
-        raise ValueError(f"keyword_search: num_results={num_results} is more than the {_ops.K_MAX} the exact top-k kernel ranks; "
-                         "lower num_results")
+        raise ValueError(_keyword_limit_message(num_results))
     ids = gi.keyword_query_ids(query)
     if not ids:
         return [], []
     allowed = None
     if metadata_filter:
         if gi.metadata is None:
-            raise ValueError("GpuIndex was built without `metadata`; metadata_filter cannot be applied")
+            raise ValueError(_NO_METADATA)
         allowed = np.fromiter((_matches(m, metadata_filter) for m in gi.metadata), dtype=bool, count=len(gi.metadata))
         if not allowed.any():
             return [], []
@@ -443,21 +453,182 @@ def _embed_one_by_one(queries: Sequence[str], query_vectors, cfg: Any, gi: GpuIn
             raise ValueError("query_vectors must be (len(queries), dim)")
         rows = list(qv)
     else:
-        rows = [embed_strings([q], config=cfg)[0, :] for q in queries]
+        rows = [embed_strings([q], config=cfg)[0, :] if isinstance(q, str) else np.ravel(q) for q in queries]
     if cfg.vector_search_query_adapter and gi.query_adapter is not None:
         rows = [_ops.adapter_apply(gi.query_adapter, np.asarray(q, dtype=np.float32)).astype(q.dtype) for q in rows]
     return np.stack([np.asarray(q, dtype=np.float32).ravel() for q in rows])
 
 
+# ---- batches with one metadata filter per query ------------------------------------------------------------------
+def _batch_filters(metadata_filter, B: int) -> list[dict | None]:
+    """A batch's metadata_filter -- None or one dict for every query, or a sequence of B entries, each None or a dict -- as the B
+    normalised filters (`_adapt_metadata`)."""
+    if metadata_filter is None or isinstance(metadata_filter, dict):
+        return [_adapt_metadata(metadata_filter)] * B
+    filters = list(metadata_filter)
+    if len(filters) != B:
+        raise ValueError(f"metadata_filter must be a dict or have one entry per query ({len(filters)} for {B} queries)")
+    return [_adapt_metadata(f) for f in filters]
+
+
+@dataclass
+class FilterPlan:
+    """The metadata filters of a batch: `allowed[j]` is distinct filter j's bool mask over chunks (None on an index without metadata,
+    where applying a filter raises), `rank_limit[j]` its branch (ORDER_FIRST_LIMIT: order first; 0: filter first) and
+    `query_filter[b]` the filter of query b (-1: none)."""
+
+    allowed: list = field(default_factory=list)
+    rank_limit: list = field(default_factory=list)
+    query_filter: list = field(default_factory=list)
+
+    def of(self, b: int):
+        """(mask, rank limit) of query b: (None, 0) without a filter."""
+        j = self.query_filter[b]
+        return (None, 0) if j < 0 else (self.allowed[j], self.rank_limit[j])
+
+
+def plan_filters(filters: Sequence[dict | None], metadata: Sequence[dict] | None, rows_per_chunk: np.ndarray) -> FilterPlan:
+    """Evaluate each distinct normalised filter against the metadata once (`_matches`, the JSON containment), take its filter-first /
+    order-first decision once (`_search.py:97-141`: more than FILTER_FIRST_MAX_ROWS matching embedding rows -> order first) and map
+    every query to its filter."""
+    plan = FilterPlan()
+    seen: dict[str, int] = {}
+    for flt in filters:
+        if not flt:
+            plan.query_filter.append(-1)
+            continue
+        key = repr(sorted(flt.items(), key=lambda kv: repr(kv[0])))
+        if key not in seen:
+            seen[key] = len(plan.allowed)
+            allowed = None
+            if metadata is not None:
+                allowed = np.fromiter((_matches(m, flt) for m in metadata), dtype=bool, count=len(metadata))
+            plan.allowed.append(allowed)
+            rows = 0 if allowed is None else int(rows_per_chunk[allowed].sum())
+            plan.rank_limit.append(ORDER_FIRST_LIMIT if rows > FILTER_FIRST_MAX_ROWS else 0)
+        plan.query_filter.append(seen[key])
+    return plan
+
+
+def _rows_per_chunk(gi: GpuIndex) -> np.ndarray:
+    offsets = gi.index.chunk_offsets
+    return np.diff(offsets) if offsets is not None else np.ones(len(gi.chunk_ids), dtype=np.int64)
+
+
+def _vector_searches(gi: GpuIndex, flt, allowed, num_hits: int, num_results: int) -> bool:
+    """vector_search's decisions for one embedded query, in its order: True where it searches the device, False where it returns
+    ([], []); raises where it raises."""
+    if gi.index.n_rows == 0 or num_hits < 1 or num_results < 1:
+        return False
+    if flt:
+        if gi.metadata is None:
+            raise ValueError(_NO_METADATA)
+        if not allowed.any():
+            return False
+    _check_limits(num_hits, num_results)
+    return True
+
+
+def _keyword_searches(gi: GpuIndex, flt, allowed, ids, num_results: int) -> bool:
+    """keyword_search's decisions for one query, in its order (as _vector_searches)."""
+    if not gi.has_keywords:
+        raise ValueError(_NO_KEYWORDS)
+    if num_results < 1:
+        return False
+    if num_results > _ops.K_MAX:
+        raise ValueError(_keyword_limit_message(num_results))
+    if not ids:
+        return False
+    if flt:
+        if gi.metadata is None:
+            raise ValueError(_NO_METADATA)
+        if not allowed.any():
+            return False
+    return True
+
+
+def _device_filters(plan: FilterPlan, queries: Sequence[int]):
+    """(query_filters, rank_limit) of one batched device call over `queries`: (None, None) where none of them has a filter, which is
+    the unfiltered call.  A query whose filter matches nothing keeps it: its lists come back empty, as the loop's do."""
+    if all(plan.query_filter[b] < 0 for b in queries):
+        return None, None
+    pairs = [plan.of(b) for b in queries]
+    return [a for a, _ in pairs], [r for _, r in pairs]
+
+
+def _self_query(cfg: Any, queries: Sequence[Any]) -> None:
+    if getattr(cfg, "self_query", False) and any(isinstance(q, str) for q in queries):
+        raise NotImplementedError("self_query needs the LLM stack, which is outside this package")
+
+
+def _collect(gi: GpuIndex, out: list, active: Sequence[int], scores, chunks, counts) -> list:
+    for i, b in enumerate(active):
+        n = int(counts[i])
+        out[b] = ([gi.chunk_ids[c] for c in chunks[i, :n].tolist()], [float(x) for x in scores[i, :n]])
+    return out
+
+
+def vector_search_batch(queries: Sequence[str | np.ndarray], *, num_results: int = 3, oversample: int = VECTOR_SEARCH_OVERSAMPLE,
+                        metadata_filter=None, config: Any | None = None, index: GpuIndex | None = None,
+                        query_vectors=None) -> list[tuple[list[ChunkId], list[float]]]:
+    """`vector_search` for a batch: element b is what `vector_search(queries[b], metadata_filter=<its filter>, ...)` returns with the
+    same arguments (the same chunk ids, the same float scores), from one device call (`rl_search_chunks_per_query`).
+    `metadata_filter`: None or one dict for every query, or one entry (None or a dict) per query; each distinct filter is evaluated
+    once.  `query_vectors` ((B, dim)) skips the embedding.  Raises where the loop would raise for some element, with its message."""
+    cfg = config or HotPathConfig()
+    gi = index or _index_for(config)
+    queries = list(queries)
+    B = len(queries)
+    if B == 0:
+        return []
+    filters = _batch_filters(metadata_filter, B)
+    _self_query(cfg, queries)
+    Q = _embed_one_by_one(queries, query_vectors, cfg, gi)
+    num_hits = round(oversample * cfg.chunk_max_size / DEFAULT_CHUNK_MAX_SIZE) * max(num_results, 10)  # (`_search.py:66-67`)
+    plan = plan_filters(filters, gi.metadata, _rows_per_chunk(gi))
+    active = [b for b in range(B) if _vector_searches(gi, filters[b], plan.of(b)[0], num_hits, num_results)]
+    out: list = [([], []) for _ in range(B)]
+    if active:
+        qf, lim = _device_filters(plan, active)
+        scores, chunks, counts = gi.index.search_chunks(Q[active], num_hits, num_results, query_filters=qf, rank_limit=lim)
+        _collect(gi, out, active, scores, chunks, counts)
+    return out
+
+
+def keyword_search_batch(queries: Sequence[str], *, num_results: int = 3, metadata_filter=None, config: Any | None = None,
+                         index: GpuIndex | None = None) -> list[tuple[list[ChunkId], list[float]]]:
+    """`keyword_search` for a batch: element b is what `keyword_search(queries[b], metadata_filter=<its filter>, ...)` returns, from
+    one device call (`rl_keyword_search_per_query`); `metadata_filter` as in `vector_search_batch`."""
+    cfg = config or HotPathConfig()
+    gi = index or _index_for(config)
+    queries = list(queries)
+    B = len(queries)
+    if B == 0:
+        return []
+    filters = _batch_filters(metadata_filter, B)
+    _self_query(cfg, queries)
+    plan = plan_filters(filters, gi.metadata, _rows_per_chunk(gi))
+    ids = [gi.keyword_query_ids(q) for q in queries] if gi.has_keywords else [[] for _ in queries]
+    active = [b for b in range(B) if _keyword_searches(gi, filters[b], plan.of(b)[0], ids[b], num_results)]
+    out: list = [([], []) for _ in range(B)]
+    if active:
+        qf, _ = _device_filters(plan, active)
+        scores, chunks, counts = gi.keyword.search([ids[b] for b in active], num_results, query_filters=qf)
+        _collect(gi, out, active, scores, chunks, counts)
+    return out
+
+
 def hybrid_search_batch(queries: Sequence[str], *, num_results: int = 3, oversample: int = 2,
                         vector_search_weight: float = 0.75, keyword_search_weight: float = 0.25,
-                        metadata_filter: dict | None = None, config: Any | None = None, index: GpuIndex | None = None,
+                        metadata_filter=None, config: Any | None = None, index: GpuIndex | None = None,
                         query_vectors=None) -> list[tuple[list[ChunkId], list[float]]]:
     """`hybrid_search` for a batch of query strings: element b is what `hybrid_search(queries[b], ...)` returns with the same
     arguments (the same chunk ids, the same float scores).  The vector half, the keyword half and the RRF fusion of all queries run
-    on one stream (`rl_hybrid_search`) and the results are read back once.  `query_vectors` ((B, dim), e.g. embeddings computed
-    elsewhere) skips the embedding; the strings still give the keyword half.  The metadata filter applies to the whole batch; an
-    external `keyword_search=` callable is not part of the batched call (use `hybrid_search`)."""
+    on one stream (`rl_hybrid_search`, `rl_hybrid_search_per_query`) and the results are read back once.  `metadata_filter`: None or
+    one dict for every query, or one entry (None or a dict) per query -- element b is then `hybrid_search(queries[b],
+    metadata_filter=<its entry>, ...)`; each distinct filter is evaluated once.  `query_vectors` ((B, dim), e.g. embeddings computed
+    elsewhere) skips the embedding; the strings still give the keyword half.  An external `keyword_search=` callable is not part of
+    the batched call (use `hybrid_search`)."""
     cfg = config or HotPathConfig()
     gi = index or _index_for(config)
     queries = list(queries)
@@ -466,49 +637,30 @@ def hybrid_search_batch(queries: Sequence[str], *, num_results: int = 3, oversam
         return []
     if getattr(cfg, "self_query", False):
         raise NotImplementedError("self_query needs the LLM stack, which is outside this package")
-    flt = _adapt_metadata(metadata_filter)
+    filters = _batch_filters(metadata_filter, B)
     n_each = oversample * num_results  # what hybrid_search asks of each half
     Q = _embed_one_by_one(queries, query_vectors, cfg, gi)
-
-    def allowed_chunks() -> np.ndarray:
-        if gi.metadata is None:
-            raise ValueError("GpuIndex was built without `metadata`; metadata_filter cannot be applied")
-        return np.fromiter((_matches(m, flt) for m in gi.metadata), dtype=bool, count=len(gi.metadata))
-
-    # the vector half, decided as vector_search decides it (same checks, same order)
     num_hits = round(VECTOR_SEARCH_OVERSAMPLE * cfg.chunk_max_size / DEFAULT_CHUNK_MAX_SIZE) * max(n_each, 10)
-    vector = gi.index.n_rows > 0 and num_hits >= 1 and n_each >= 1
-    allowed, rank_limit = None, None
-    if vector and flt:
-        allowed = allowed_chunks()
-        vector = bool(allowed.any())
-    if vector:
-        _check_limits(num_hits, n_each)
-        if allowed is not None:
-            offsets = gi.index.chunk_offsets
-            rows_per_chunk = np.diff(offsets) if offsets is not None else np.ones(len(allowed), dtype=np.int64)
-            rank_limit = ORDER_FIRST_LIMIT if int(rows_per_chunk[allowed].sum()) > FILTER_FIRST_MAX_ROWS else None
-    # the keyword half, as keyword_search decides it
-    keyword, term_ids = gi.has_keywords and n_each >= 1, None
-    if keyword:
-        if n_each > _ops.K_MAX:
-            raise ValueError(f"keyword_search: num_results={n_each} is more than the {_ops.K_MAX} the exact top-k kernel ranks; "
-                             "lower num_results")
-        term_ids = [gi.keyword_query_ids(q) for q in queries]
-        if flt and any(term_ids):  # (a query without a known stem returns before the filter is looked at)
-            if allowed is None:
-                allowed = allowed_chunks()
-            keyword = bool(allowed.any())
+    plan = plan_filters(filters, gi.metadata, _rows_per_chunk(gi))
+    # (hybrid_search runs the keyword half for query strings only; a query given as a vector has none)
+    term_ids = [gi.keyword_query_ids(q) if isinstance(q, str) else [] for q in queries] if gi.has_keywords else None
+    vector = keyword = False
+    for b in range(B):  # hybrid_search's decisions for each query, in its order: its vector half, then its keyword half
+        allowed = plan.of(b)[0]
+        vector = _vector_searches(gi, filters[b], allowed, num_hits, n_each) or vector
+        if gi.has_keywords and isinstance(queries[b], str):
+            keyword = _keyword_searches(gi, filters[b], allowed, term_ids[b], n_each) or keyword
     if not vector and not keyword:
         return [([], []) for _ in range(B)]
     R = int(vector) + int(keyword)
     k = R * n_each if num_results < 1 else min(num_results, R * n_each)  # (hybrid_search slices the fused list [:num_results])
+    qf, lim = _device_filters(plan, range(B))
     if vector:
         scores, chunks, counts = gi.index.hybrid_search(Q, num_hits, n_each, k, keyword=gi.keyword if keyword else None,
                                                         query_term_ids=term_ids, weights=(vector_search_weight, keyword_search_weight),
-                                                        rrf_k=RRF_K, chunk_filter=allowed, rank_limit=rank_limit)
+                                                        rrf_k=RRF_K, query_filters=qf, rank_limit=lim)
     else:  # no vector results for any query (an empty index, num_hits < 1): RRF of the keyword list alone is the same fusion
-        _, kw_chunks, _ = gi.keyword.search(term_ids, n_each, chunk_filter=allowed)
+        _, kw_chunks, _ = gi.keyword.search(term_ids, n_each, query_filters=qf)
         scores, chunks, counts = _ops.rrf_fuse(kw_chunks[None], [keyword_search_weight], rrf_k=RRF_K, k=k)
     out = []
     for b in range(B):

@@ -313,7 +313,7 @@ struct rl_index {
     rl::DevArray<uint32_t> live_chunk_bits;  // device copy of h_live (empty: every chunk is live)
     rl::DevArray<uint32_t> live_row_bits;    // the same expanded to rows
     int64_t n_dead_chunks = 0, n_dead_rows = 0;
-    rl::Pool maskbuf;                     // per-call effective row mask
+    rl::Pool maskbuf;                     // per-call row masks (the distinct filters of a sub-batch) and the query -> mask map
     rl::Pool qsplit;                      // fp16 (hi, lo) query fragments of a MaxSim batch (maxsim_stream.hip)
     // SPLIT arithmetic of the stream kernel (fp32 storage only): range of the row norms, and what follows from it
     rl::DevArray<uint32_t> d_range;       // device scratch of launch_row_range
@@ -896,7 +896,7 @@ int upload_live_bits(rl_index* idx, hipStream_t s) {
     RL_TRY(chunk_bits.reserve(std::max<size_t>(cw * 4, 16)));
     RL_TRY(row_bits.reserve(std::max<size_t>(rw * 4, 16)));
     RL_HIP(hipMemcpyAsync(chunk_bits, idx->h_live.data(), cw * 4, hipMemcpyHostToDevice, s));
-    RL_TRY(launch_expand_chunk_bits(chunk_bits, idx->row_to_chunk, idx->n_rows, nullptr, row_bits, s));
+    RL_TRY(launch_expand_chunk_bits(chunk_bits, 0, nullptr, 1, idx->row_to_chunk, idx->n_rows, nullptr, row_bits, s));
     RL_HIP(hipStreamSynchronize(s));
     idx->live_chunk_bits = std::move(chunk_bits);
     idx->live_row_bits = std::move(row_bits);
@@ -1317,7 +1317,7 @@ int effective_row_mask(rl_index* idx, const uint32_t* d_chunk_filter, hipStream_
     *out = idx->live_row_bits;
     if (!d_chunk_filter || idx->n_rows == 0) return RL_OK;
     RL_TRY(idx->maskbuf.reserve((size_t)((idx->n_rows + 31) / 32) * sizeof(uint32_t)));
-    RL_TRY(launch_expand_chunk_bits(d_chunk_filter, idx->row_to_chunk, idx->n_rows, idx->live_row_bits,
+    RL_TRY(launch_expand_chunk_bits(d_chunk_filter, 0, nullptr, 1, idx->row_to_chunk, idx->n_rows, idx->live_row_bits,
                                     idx->maskbuf.as<uint32_t>(), s));
     *out = idx->maskbuf.as<uint32_t>();
     return RL_OK;
@@ -1538,7 +1538,7 @@ int search_rows_fused_hi(rl_index* idx, const float* d_q, int32_t B, int32_t k, 
 // re-scoring of 32 x 1024 candidate rows cost more than the half pass saves), k <= 512, with or without a row mask (masked rows rank -inf in the approximate pass: they are never
 // candidates); RL_ERR_UNSUPPORTED otherwise.
 int search_rows_hi(rl_index* idx, const float* d_q, int32_t nb, int32_t k, float* d_scores, int32_t* d_rows, int64_t ld, hipStream_t s,
-                   const uint32_t* d_row_bits) {
+                   const QueryMask& row_mask) {
     if (!idx->opt.on(RL_OPT_HI_SEARCH)) return RL_ERR_UNSUPPORTED;
     const int mode = scan_mode(idx->metric);
     const int64_t n = idx->n_rows;
@@ -1600,9 +1600,10 @@ int search_rows_hi(rl_index* idx, const float* d_q, int32_t nb, int32_t k, float
         if (!measured) return RL_ERR_UNSUPPORTED;
         m_rel = sum_eps(dim);  // (l2_delta's arguments: the rounding term, the dot's bound per |q|, max |e|)
     }
-    if (d_row_bits) {  // tombstones / metadata filter: masked rows rank -inf, so they reach neither the top-k nor the candidates
+    const bool masked = row_mask.any();
+    if (masked) {  // tombstones / metadata filters: masked rows rank -inf, so they reach neither the top-k nor the candidates
         RL_TRY(launch_transform(sc, nb, n, ld, idx->norm, idx->sumsq, d_q, dim, mode, s, 1.0f / idx->hiplane.scale));
-        RL_TRY(launch_mask_scores(sc, nb, n, ld, d_row_bits, s));
+        RL_TRY(launch_mask_scores(sc, nb, n, ld, row_mask, s));
         int st_sel = RL_ERR_UNSUPPORTED;
         if (l2) st_sel = launch_topk_pivot(sc, nb, n, ld, k, idx->ws, ts, ti, s);  // (crowded scores: see above)
         if (st_sel != RL_OK && st_sel != RL_ERR_UNSUPPORTED) return st_sel;
@@ -1657,9 +1658,9 @@ int search_rows_hi(rl_index* idx, const float* d_q, int32_t nb, int32_t k, float
     tr.row_norm = gn; tr.queries = d_q; tr.dim = dim; tr.mode = mode;
     RL_TRY(launch_merge_topk(nb > 1 ? es : xs, ci, 1, nb, cap, k, d_scores, d_rows, s, cnt, l2 ? nullptr : &tr));  // (l2: already similarities)
     // ---- (4b) ... and its selection -------------------------------------------------------------------------------------------------------
-    if (d_row_bits) {  // (the mask needs no guard: applied to scores nobody reads it changes nothing)
+    if (masked) {  // (the mask needs no guard: applied to scores nobody reads it changes nothing)
         if (!l2) RL_TRY(launch_transform(sc, nb, n, ld, idx->norm, idx->sumsq, d_q, dim, mode, s, 1.0f, flag));
-        RL_TRY(launch_mask_scores(sc, nb, n, ld, d_row_bits, s));
+        RL_TRY(launch_mask_scores(sc, nb, n, ld, row_mask, s));
         RL_TRY(launch_topk(sc, nb, n, ld, k, idx->ws, d_scores, d_rows, s, flag));
     } else if (l2) {
         RL_TRY(launch_guarded_select(sc, nb, n, ld, k, nullptr, nullptr, nullptr, 0, SCAN_RAW_DOT, 1.0f, d_scores, d_rows, flag, s));
@@ -1696,10 +1697,65 @@ int select_from_scores(rl_index* idx, const float* d_qb, int32_t nb, int32_t k, 
     return RL_OK;
 }
 
-// rank_limit > 0: the order-first-then-filter branch (src/raglite/_search.py:120-141) -- only the rank_limit nearest LIVE
-// rows of a query are eligible, and among those the rows d_row_bits lets through are ranked.
+// The metadata filters and rank limits of a batch as the host describes them (the chunk bitsets are on the device): query b reads chunk
+// bitset filter_of(b) (-1: none) and cuts at limit_of(b) (n_rows: no cut).  The single-filter entry points give n <= 1 and no arrays.
+struct BatchFilters {
+    const uint32_t* chunk_bits = nullptr;  // device [n x (n_chunks + 31) / 32]
+    int32_t n = 0;
+    const int32_t* qf = nullptr;   // host [B]: each query's bitset (-1: none); nullptr: every query reads bitset 0 (when n > 0)
+    const int64_t* lim = nullptr;  // host [B]: each query's rank limit (0: no cut); nullptr: every query `limit`
+    int64_t limit = 0;
+    int32_t filter_of(int32_t b) const { return n == 0 ? -1 : qf ? qf[b] : 0; }
+    int64_t limit_of(int32_t b, int64_t n_rows) const {
+        const int64_t L = lim ? lim[b] : limit;
+        return L > 0 && L < n_rows ? L : n_rows;
+    }
+};
+
+// One sub-batch of a row search, planned on the host: the distinct chunk bitsets it reads (expanded to row bitsets in idx->maskbuf, one
+// per distinct filter), each query's row bitset among them and its rank limit.  Where all queries of the sub-batch agree, no map goes to
+// the device: a sub-batch whose queries have no filter and no cut is the unfiltered call, one whose queries share one filter and one limit
+// is the single-filter call.
+struct RowPlan {
+    std::vector<int32_t> fids;   // distinct chunk bitsets, in order of first use
+    std::vector<int32_t> set;    // [nb] each query's row bitset (index into fids; -1: none, i.e. the tombstones alone)
+    std::vector<uint32_t> lims;  // [nb] each query's rank limit (n_rows: no cut)
+    bool one_set = true, one_lim = true, cut = false, identity = true;  // identity: fids[j] == j
+};
+
+void plan_rows(const BatchFilters& f, int32_t b0, int32_t nb, int64_t n_rows, RowPlan& p) {
+    p.set.resize((size_t)nb);
+    p.lims.resize((size_t)nb);
+    std::vector<int32_t> slot((size_t)f.n, -1);
+    for (int32_t i = 0; i < nb; ++i) {
+        const int32_t fi = f.filter_of(b0 + i);
+        int32_t j = -1;
+        if (fi >= 0) {
+            if (slot[(size_t)fi] < 0) {
+                slot[(size_t)fi] = (int32_t)p.fids.size();
+                p.identity = p.identity && fi == (int32_t)p.fids.size();
+                p.fids.push_back(fi);
+            }
+            j = slot[(size_t)fi];
+        }
+        p.set[(size_t)i] = j;
+        p.lims[(size_t)i] = (uint32_t)f.limit_of(b0 + i, n_rows);
+        p.one_set = p.one_set && j == p.set[0];
+        p.one_lim = p.one_lim && p.lims[(size_t)i] == p.lims[0];
+        p.cut = p.cut || (int64_t)p.lims[(size_t)i] < n_rows;
+    }
+}
+
+// Host -> device copy of a plan's maps (pageable: the copy has consumed the source when it returns)
+int upload(void* dst, const void* src, size_t bytes, hipStream_t s) {
+    if (bytes) RL_HIP(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, s));
+    return RL_OK;
+}
+
+// Limits below the live rows are the order-first-then-filter branch (src/raglite/_search.py:120-141) -- only the rank_limit nearest
+// LIVE rows of a query are eligible, and among those the rows its filter lets through are ranked.
 int search_rows_device(rl_index* idx, const float* d_q, int32_t B, int32_t k, float* d_scores, int32_t* d_rows,
-                       hipStream_t s, const uint32_t* d_row_bits = nullptr, int64_t rank_limit = 0) {
+                       hipStream_t s, const BatchFilters& f = BatchFilters()) {
     const int64_t n = idx->n_rows;
     const int64_t ld = (n + 3) & ~int64_t(3);
     if (n == 0) {  // empty index: every slot is padding (the reference returns ([], []), tests/test_search.py:76-85)
@@ -1710,42 +1766,80 @@ int search_rows_device(rl_index* idx, const float* d_q, int32_t B, int32_t k, fl
     const int64_t per_query = std::max<int64_t>(ld * 4, 1);
     const int32_t batch = (int32_t)std::max<int64_t>(1, std::min<int64_t>(B, (int64_t)(SCORE_BATCH_BYTES / per_query)));
     RL_TRY(idx->scores.reserve((size_t)batch * ld * sizeof(float)));
+    // every sub-batch's plan first: the mask scratch is reserved once, for the sub-batch with the most distinct filters -- the row bitsets
+    // [most x rw], then the maps (filter ids, query -> bitset, limits)
+    std::vector<RowPlan> plans;
+    size_t most = 0;
+    bool maps = false;
     for (int32_t b0 = 0; b0 < B; b0 += batch) {
+        plans.emplace_back();
+        plan_rows(f, b0, std::min<int32_t>(batch, B - b0), n, plans.back());
+        most = std::max(most, plans.back().fids.size());
+        maps = maps || !plans.back().one_set || !plans.back().one_lim || !plans.back().identity;
+    }
+    const int64_t rw = (n + 31) / 32, cw = (idx->n_chunks + 31) / 32;
+    if (most || maps) RL_TRY(idx->maskbuf.reserve(((size_t)most * rw + most + 2 * (size_t)batch) * sizeof(uint32_t)));
+    uint32_t* row_sets = idx->maskbuf.as<uint32_t>();
+    int32_t* d_map = reinterpret_cast<int32_t*>(row_sets + (size_t)most * rw);
+    const std::vector<int32_t>* expanded = nullptr;  // the filters whose row bitsets maskbuf holds
+    bool any_masked = false;
+    for (int32_t i = 0, b0 = 0; b0 < B; ++i, b0 += batch) {
         const int32_t nb = std::min<int32_t>(batch, B - b0);
-        const bool cut = rank_limit > 0 && rank_limit < n;
+        const RowPlan& p = plans[(size_t)i];
+        const int32_t nf = (int32_t)p.fids.size();
+        // the maps this sub-batch needs, in one copy: [filter ids][query -> bitset][limits]
+        std::vector<int32_t> up;
+        const int32_t* d_fid = nullptr;
+        const int32_t* d_set = nullptr;
+        const uint32_t* d_lim = nullptr;
+        if (!p.identity) { d_fid = d_map; up.insert(up.end(), p.fids.begin(), p.fids.end()); }
+        if (!p.one_set) { d_set = d_map + up.size(); up.insert(up.end(), p.set.begin(), p.set.end()); }
+        if (!p.one_lim) {
+            d_lim = reinterpret_cast<const uint32_t*>(d_map + up.size());
+            for (uint32_t L : p.lims) up.push_back((int32_t)L);
+        }
+        RL_TRY(upload(d_map, up.data(), up.size() * sizeof(int32_t), s));
+        if (nf && (!expanded || *expanded != p.fids)) {  // each distinct filter of the sub-batch, and-ed with the tombstones: one launch
+            RL_TRY(launch_expand_chunk_bits(f.chunk_bits, cw, d_fid, nf, idx->row_to_chunk, n, idx->live_row_bits, row_sets, s));
+            expanded = &p.fids;
+        }
+        const QueryMask mask = p.one_set ? QueryMask(p.set[0] >= 0 ? row_sets + (int64_t)p.set[0] * rw : (const uint32_t*)idx->live_row_bits)
+                                         : QueryMask(row_sets, rw, d_set, idx->live_row_bits);
+        const bool masked = mask.any(), cut = p.cut;
+        any_masked = any_masked || masked || cut;
         // lazy images: the routes below test what the index HAS; ask for what this batch's route reads first
-        if (!d_row_bits && !cut && nb >= rows_gemm_min(idx) && k <= 512 && idx->opt.on(RL_OPT_FUSED_TOPK))
+        if (!masked && !cut && nb >= rows_gemm_min(idx) && k <= 512 && idx->opt.on(RL_OPT_FUSED_TOPK))
             RL_TRY(demand_images(idx, IMG_PLANES | (idx->opt.on(RL_OPT_FUSED_HI) ? IMG_HI_IMAGE : 0u), s));
         if (!cut && nb <= ((idx->dim > 1024 || idx->metric == RL_L2) ? 4 : 16) && k <= 512 && idx->opt.on(RL_OPT_HI_SEARCH))
             RL_TRY(demand_images(idx, IMG_HI_PLANE, s));
-        if (!d_row_bits && !cut) {  // big batches over an index with a HI image: fused top-k at one MFMA product per multiply
+        if (!masked && !cut) {  // big batches over an index with a HI image: fused top-k at one MFMA product per multiply
             const int st = search_rows_fused_hi(idx, d_q + (int64_t)b0 * idx->dim, nb, k, d_scores + (int64_t)b0 * k, d_rows + (int64_t)b0 * k, ld, s);
             if (st == RL_OK) continue;
             if (st != RL_ERR_UNSUPPORTED) return st;
         }
-        if (!d_row_bits && !cut) {  // big batches over the pre-split image: no score matrix at all
+        if (!masked && !cut) {  // big batches over the pre-split image: no score matrix at all
             const int st = search_rows_fused(idx, d_q + (int64_t)b0 * idx->dim, nb, k, d_scores + (int64_t)b0 * k, d_rows + (int64_t)b0 * k, ld, s);
             if (st == RL_OK) continue;
             if (st != RL_ERR_UNSUPPORTED) return st;
         }
         if (!cut && nb <= 16) {  // a few queries over a big fp32 corpus: half the bytes through the HI plane
             const int st = search_rows_hi(idx, d_q + (int64_t)b0 * idx->dim, nb, k, d_scores + (int64_t)b0 * k, d_rows + (int64_t)b0 * k, ld, s,
-                                          d_row_bits);
+                                          mask);
             if (st == RL_OK) continue;
             if (st != RL_ERR_UNSUPPORTED) return st;
         }
         bool hist_done = false;
-        RL_TRY(score_rows(idx, d_q + (int64_t)b0 * idx->dim, nb, ld, s, (d_row_bits || cut) ? nullptr : &hist_done));
+        RL_TRY(score_rows(idx, d_q + (int64_t)b0 * idx->dim, nb, ld, s, (masked || cut) ? nullptr : &hist_done));
         if (cut) {  // tombstoned rows are not in the reference's table at all: out before the cut, then cut + filter
-            if (idx->live_row_bits) RL_TRY(launch_mask_scores(idx->scores.as<float>(), nb, n, ld, idx->live_row_bits, s));
+            if (idx->live_row_bits) RL_TRY(launch_mask_scores(idx->scores.as<float>(), nb, n, ld, QueryMask(idx->live_row_bits), s));
             RL_TRY(idx->rankbuf.reserve(rank_cut_scratch_bytes(nb, n)));
-            RL_TRY(launch_rank_cut(idx->scores.as<float>(), nb, n, ld, rank_limit, d_row_bits, idx->rankbuf.p, s));
-        } else if (d_row_bits) {
-            RL_TRY(launch_mask_scores(idx->scores.as<float>(), nb, n, ld, d_row_bits, s));
+            RL_TRY(launch_rank_cut(idx->scores.as<float>(), nb, n, ld, p.one_lim ? (int64_t)p.lims[0] : 0, d_lim, mask, idx->rankbuf.p, s));
+        } else if (masked) {
+            RL_TRY(launch_mask_scores(idx->scores.as<float>(), nb, n, ld, mask, s));
         }
         RL_TRY(select_from_scores(idx, d_q + (int64_t)b0 * idx->dim, nb, k, d_scores + (int64_t)b0 * k, d_rows + (int64_t)b0 * k, ld, hist_done, s));
     }
-    if (d_row_bits || (rank_limit > 0 && rank_limit < n)) RL_TRY(launch_fix_masked(d_scores, d_rows, (int64_t)B * k, s));  // masked rows are "no hit"
+    if (any_masked) RL_TRY(launch_fix_masked(d_scores, d_rows, (int64_t)B * k, s));  // masked rows are "no hit"
     return RL_OK;
 }
 
@@ -1757,17 +1851,29 @@ int check_search_args(const rl_index* idx, const float* q, int32_t B, int32_t k,
     return RL_OK;
 }
 
-// The device half of rl_search_chunks_ranked on device pointers (under idx->mu, after use_scratch): the num_hits best rows per
-// query (filter / rank cut as there), grouped to the k best chunks -> d_s / d_c [B x k], d_n [B]
-int search_chunks_device(rl_index* idx, const float* d_q, int32_t B, int32_t num_hits, int32_t k, const uint32_t* d_f, int64_t rank_limit,
+// The device half of rl_search_chunks_per_query on device pointers (under idx->mu, after use_scratch): the num_hits best rows per
+// query (its filter / rank cut as there), grouped to the k best chunks -> d_s / d_c [B x k], d_n [B]
+int search_chunks_device(rl_index* idx, const float* d_q, int32_t B, int32_t num_hits, int32_t k, const BatchFilters& f,
                          float* d_s, int32_t* d_c, int32_t* d_n, hipStream_t s) {
-    const uint32_t* d_bits = nullptr;
-    RL_TRY(effective_row_mask(idx, d_f, s, &d_bits));
     RL_TRY(idx->hits.reserve((size_t)B * num_hits * 8));
     float* h_s = idx->hits.as<float>();
     int32_t* h_r = reinterpret_cast<int32_t*>(h_s + (size_t)B * num_hits);
-    RL_TRY(search_rows_device(idx, d_q, B, num_hits, h_s, h_r, s, d_bits, rank_limit));
+    RL_TRY(search_rows_device(idx, d_q, B, num_hits, h_s, h_r, s, f));
     RL_TRY(launch_group_chunk_max(h_s, h_r, B, num_hits, idx->offsets, idx->n_chunks, k, d_s, d_c, d_n, s));
+    return RL_OK;
+}
+
+// The per-query arguments of the *_per_query calls that need no index (include/raglite_hip.h): n_filters, chunk_filters, query_filter
+// (host), rank_limits (host)
+int check_query_filters(int32_t B, const uint32_t* chunk_filters, int32_t n_filters, const int32_t* query_filter, const int64_t* rank_limits,
+                        const char* who) {
+    if (n_filters < 0) return fail(RL_ERR_INVALID, std::string(who) + ": n_filters must be >= 0");
+    if (n_filters > 0 && !chunk_filters) return fail(RL_ERR_INVALID, std::string(who) + ": null chunk_filters with n_filters > 0");
+    for (int32_t b = 0; query_filter && b < B; ++b)
+        if (query_filter[b] < -1 || query_filter[b] >= n_filters)
+            return fail(RL_ERR_INVALID, std::string(who) + ": query_filter[" + std::to_string(b) + "] must be -1 or a row of chunk_filters (< n_filters)");
+    for (int32_t b = 0; rank_limits && b < B; ++b)
+        if (rank_limits[b] < 0) return fail(RL_ERR_INVALID, std::string(who) + ": rank_limits[" + std::to_string(b) + "] must be >= 0 (0 = no cut)");
     return RL_OK;
 }
 
@@ -1784,14 +1890,14 @@ int rl_search_rows_ranked(rl_index* idx, const float* queries, int32_t B, int32_
     RL_TRY(use_scratch(idx, s));
     DevBuf t_q, t_s, t_r, t_f;
     const float* d_q; float* d_s; int32_t* d_r;
-    const uint32_t* d_f = nullptr;
-    const uint32_t* d_bits = nullptr;
-    if (chunk_filter) RL_TRY(stage_in(chunk_filter, (size_t)((idx->n_chunks + 31) / 32), mem, s, t_f, &d_f));
-    RL_TRY(effective_row_mask(idx, d_f, s, &d_bits));
+    BatchFilters f;
+    f.n = chunk_filter ? 1 : 0;
+    f.limit = rank_limit;
+    if (chunk_filter) RL_TRY(stage_in(chunk_filter, (size_t)((idx->n_chunks + 31) / 32), mem, s, t_f, &f.chunk_bits));
     RL_TRY(stage_in(queries, (size_t)B * idx->dim, mem, s, t_q, &d_q));
     RL_TRY(stage_out_begin(out_scores, (size_t)B * k, mem, t_s, &d_s));
     RL_TRY(stage_out_begin(out_rows, (size_t)B * k, mem, t_r, &d_r));
-    RL_TRY(search_rows_device(idx, d_q, B, k, d_s, d_r, s, d_bits, rank_limit));
+    RL_TRY(search_rows_device(idx, d_q, B, k, d_s, d_r, s, f));
     RL_TRY(stage_out_end(out_scores, (size_t)B * k, mem, s, t_s));
     RL_TRY(stage_out_end(out_rows, (size_t)B * k, mem, s, t_r));
     return finish(mem, s);
@@ -1826,7 +1932,7 @@ int rl_rank_cut_begin(rl_index* idx, const float* queries, int32_t B, int mem, v
     RL_TRY(idx->rankbuf.reserve(rank_stage_scratch_bytes(B, std::max<int64_t>(n, 1))));
     if (n > 0) {
         RL_TRY(score_rows(idx, idx->rank_q.as<float>(), B, ld, s, nullptr));
-        if (idx->live_row_bits) RL_TRY(launch_mask_scores(idx->scores.as<float>(), B, n, ld, idx->live_row_bits, s));  // tombstones are not in the table
+        if (idx->live_row_bits) RL_TRY(launch_mask_scores(idx->scores.as<float>(), B, n, ld, QueryMask(idx->live_row_bits), s));  // tombstones are not in the table
     }
     idx->rank_B = B;
     return finish(mem, s);
@@ -1917,30 +2023,53 @@ int rl_rank_cut_finish(rl_index* idx, int64_t rank_limit, const uint32_t* ties_b
 }
 
 // ---- a6 + a7 + a8 --------------------------------------------------------------------------------------
-int rl_search_chunks_ranked(rl_index* idx, const float* queries, int32_t B, int32_t num_hits, int32_t k,
-                            const uint32_t* chunk_filter, int64_t rank_limit, float* out_scores, int32_t* out_chunks,
-                            int32_t* out_counts, int mem, void* stream) {
-    RL_TRY(check_search_args(idx, queries, B, k, "rl_search_chunks"));
-    if (rank_limit < 0) return fail(RL_ERR_INVALID, "rl_search_chunks: rank_limit must be >= 0 (0 = no cut)");
-    if (num_hits < 1 || num_hits > K_MAX) return fail(RL_ERR_INVALID, "rl_search_chunks: num_hits must be in [1, 2048]");
+namespace {
+// rl_search_chunks_ranked and rl_search_chunks_per_query: one device path, the filters and limits as BatchFilters describes them
+int search_chunks_call(rl_index* idx, const float* queries, int32_t B, int32_t num_hits, int32_t k, const uint32_t* chunk_filters,
+                       int32_t n_filters, const int32_t* query_filter, const int64_t* rank_limits, int64_t rank_limit, float* out_scores,
+                       int32_t* out_chunks, int32_t* out_counts, int mem, void* stream, const char* who) {
+    RL_TRY(check_search_args(idx, queries, B, k, who));
+    if (rank_limit < 0) return fail(RL_ERR_INVALID, std::string(who) + ": rank_limit must be >= 0 (0 = no cut)");
+    if (num_hits < 1 || num_hits > K_MAX) return fail(RL_ERR_INVALID, std::string(who) + ": num_hits must be in [1, 2048]");
     if (B == 0) return RL_OK;
-    if (!out_scores || !out_chunks || !out_counts) return fail(RL_ERR_INVALID, "rl_search_chunks: null output");
+    if (!out_scores || !out_chunks || !out_counts) return fail(RL_ERR_INVALID, std::string(who) + ": null output");
     hipStream_t s = as_stream(stream);
     std::lock_guard<std::mutex> lock(idx->mu);
     RL_TRY(use_scratch(idx, s));
     DevBuf t_q, t_s, t_c, t_n, t_f;
     const float* d_q; float* d_s; int32_t* d_c; int32_t* d_n;
-    const uint32_t* d_f = nullptr;
-    if (chunk_filter) RL_TRY(stage_in(chunk_filter, (size_t)((idx->n_chunks + 31) / 32), mem, s, t_f, &d_f));
+    BatchFilters f;
+    f.n = n_filters;
+    f.qf = query_filter;
+    f.lim = rank_limits;
+    f.limit = rank_limit;
+    if (n_filters) RL_TRY(stage_in(chunk_filters, (size_t)n_filters * ((idx->n_chunks + 31) / 32), mem, s, t_f, &f.chunk_bits));
     RL_TRY(stage_in(queries, (size_t)B * idx->dim, mem, s, t_q, &d_q));
     RL_TRY(stage_out_begin(out_scores, (size_t)B * k, mem, t_s, &d_s));
     RL_TRY(stage_out_begin(out_chunks, (size_t)B * k, mem, t_c, &d_c));
     RL_TRY(stage_out_begin(out_counts, (size_t)B, mem, t_n, &d_n));
-    RL_TRY(search_chunks_device(idx, d_q, B, num_hits, k, d_f, rank_limit, d_s, d_c, d_n, s));
+    RL_TRY(search_chunks_device(idx, d_q, B, num_hits, k, f, d_s, d_c, d_n, s));
     RL_TRY(stage_out_end(out_scores, (size_t)B * k, mem, s, t_s));
     RL_TRY(stage_out_end(out_chunks, (size_t)B * k, mem, s, t_c));
     RL_TRY(stage_out_end(out_counts, (size_t)B, mem, s, t_n));
     return finish(mem, s);
+}
+}  // namespace
+
+int rl_search_chunks_ranked(rl_index* idx, const float* queries, int32_t B, int32_t num_hits, int32_t k,
+                            const uint32_t* chunk_filter, int64_t rank_limit, float* out_scores, int32_t* out_chunks,
+                            int32_t* out_counts, int mem, void* stream) {
+    return search_chunks_call(idx, queries, B, num_hits, k, chunk_filter, chunk_filter ? 1 : 0, nullptr, nullptr, rank_limit, out_scores,
+                              out_chunks, out_counts, mem, stream, "rl_search_chunks");
+}
+
+int rl_search_chunks_per_query(rl_index* idx, const float* queries, int32_t B, int32_t num_hits, int32_t k, const uint32_t* chunk_filters,
+                               int32_t n_filters, const int32_t* query_filter, const int64_t* rank_limits, float* out_scores,
+                               int32_t* out_chunks, int32_t* out_counts, int mem, void* stream) {
+    const char* who = "rl_search_chunks_per_query";
+    RL_TRY(check_query_filters(B, chunk_filters, n_filters, query_filter, rank_limits, who));
+    return search_chunks_call(idx, queries, B, num_hits, k, chunk_filters, query_filter ? n_filters : 0, query_filter, rank_limits, 0,
+                              out_scores, out_chunks, out_counts, mem, stream, who);
 }
 
 int rl_search_chunks_filtered(rl_index* idx, const float* queries, int32_t B, int32_t num_hits, int32_t k,
@@ -1962,7 +2091,7 @@ namespace {
 int mask_chunk_scores(rl_index* idx, float* d_scores, int32_t nb, int64_t ld, const uint32_t* d_chunk_filter,
                       hipStream_t s) {
     if (d_chunk_filter) RL_TRY(launch_mask_scores(d_scores, nb, idx->n_chunks, ld, d_chunk_filter, s));
-    if (idx->live_chunk_bits) RL_TRY(launch_mask_scores(d_scores, nb, idx->n_chunks, ld, idx->live_chunk_bits, s));
+    if (idx->live_chunk_bits) RL_TRY(launch_mask_scores(d_scores, nb, idx->n_chunks, ld, QueryMask(idx->live_chunk_bits), s));
     return RL_OK;
 }
 
@@ -2929,6 +3058,7 @@ struct rl_keyword_index {
     std::mutex mu;
     rl::SelectWorkspace ws;
     rl::Pool scores;                    // [B x ld] chunk scores of a (sub-)batch
+    rl::Pool qmap;                      // [B] the chunk bitset of each query of a per-query filtered call
     hipStream_t last_stream = nullptr;
     bool last_stream_set = false;
     ~rl_keyword_index() { rl::select_workspace_free(ws); }
@@ -2965,7 +3095,7 @@ int keyword_use_stream(rl_keyword_index* kw, hipStream_t s) {
 }
 
 // The device half of rl_keyword_search on device pointers (under kw->mu, after keyword_use_stream): d_s / d_c [B x k], d_n [B]
-int keyword_search_device(rl_keyword_index* kw, const int64_t* d_off, const int32_t* d_terms, int32_t n_queries, int32_t k, const uint32_t* d_f,
+int keyword_search_device(rl_keyword_index* kw, const int64_t* d_off, const int32_t* d_terms, int32_t n_queries, int32_t k, const QueryMask& d_f,
                           float* d_s, int32_t* d_c, int32_t* d_n, hipStream_t s) {
     const int64_t n = kw->n_chunks;
     const size_t n_out = (size_t)n_queries * k;
@@ -2980,13 +3110,31 @@ int keyword_search_device(rl_keyword_index* kw, const int64_t* d_off, const int3
         RL_TRY(kw->scores.reserve((size_t)batch * ld * sizeof(float)));
         for (int32_t b0 = 0; b0 < n_queries; b0 += batch) {
             const int32_t nb = std::min<int32_t>(batch, n_queries - b0);
-            RL_TRY(launch_bm25_score(kw->term_off, kw->post_chunk, kw->post_impact, kw->n_terms, n, d_off + b0, d_terms, nb, d_f,
+            RL_TRY(launch_bm25_score(kw->term_off, kw->post_chunk, kw->post_impact, kw->n_terms, n, d_off + b0, d_terms, nb, d_f.from(b0),
                                      bm25_tile(n, nb, kw->n_cu), kw->scores.as<float>(), ld, s));
             RL_TRY(launch_topk(kw->scores.as<float>(), nb, n, ld, k, kw->ws, d_s + (int64_t)b0 * k, d_c + (int64_t)b0 * k, s));
         }
         RL_TRY(launch_fix_masked(d_s, d_c, (int64_t)n_out, s));  // chunks without a query term are "no hit": (-inf, -1)
     }
     return launch_bm25_count(d_s, n_queries, k, d_n, s);
+}
+
+// The chunk bitset each query of a keyword search reads (d_filters [n_filters x (n_chunks + 31) / 32] on the device; query_filter: host,
+// nullptr: every query reads bitset 0 when n_filters > 0).  Where every query reads the same bitset, no map goes to the device.
+int keyword_mask(rl_keyword_index* kw, const uint32_t* d_filters, int32_t n_filters, const int32_t* query_filter, int32_t B, hipStream_t s,
+                 QueryMask* out) {
+    *out = QueryMask();
+    if (n_filters == 0 || B == 0) return RL_OK;
+    if (!query_filter) { *out = QueryMask(d_filters); return RL_OK; }
+    const int64_t cw = (kw->n_chunks + 31) / 32;
+    if (std::all_of(query_filter, query_filter + B, [&](int32_t f) { return f == query_filter[0]; })) {
+        if (query_filter[0] >= 0) *out = QueryMask(d_filters + (int64_t)query_filter[0] * cw);
+        return RL_OK;
+    }
+    RL_TRY(kw->qmap.reserve((size_t)B * sizeof(int32_t)));
+    RL_HIP(hipMemcpyAsync(kw->qmap.p, query_filter, (size_t)B * sizeof(int32_t), hipMemcpyHostToDevice, s));  // (pageable: consumed on return)
+    *out = QueryMask(d_filters, cw, kw->qmap.as<int32_t>(), nullptr);
+    return RL_OK;
 }
 
 // q_off as rl_keyword_search states it (host pointers only)
@@ -3078,20 +3226,25 @@ int rl_keyword_index_info(const rl_keyword_index* kw, int32_t* n_terms, int64_t*
     return RL_OK;
 }
 
-int rl_keyword_search(rl_keyword_index* kw, const int64_t* q_off, const int32_t* q_terms, int32_t n_queries, int32_t k,
-                      const uint32_t* chunk_filter, float* out_scores, int32_t* out_chunks, int32_t* out_counts, int mem, void* stream) {
-    if (!kw) return fail(RL_ERR_INVALID, "rl_keyword_search: null index");
-    if (n_queries < 0 || k < 1) return fail(RL_ERR_INVALID, "rl_keyword_search: n_queries must be >= 0 and k >= 1");
-    if (k > K_MAX) return fail(RL_ERR_UNSUPPORTED, "rl_keyword_search: k must be <= 2048");
+}  // extern "C"
+
+namespace {
+// rl_keyword_search and rl_keyword_search_per_query: one device path
+int keyword_search_call(rl_keyword_index* kw, const int64_t* q_off, const int32_t* q_terms, int32_t n_queries, int32_t k,
+                        const uint32_t* chunk_filters, int32_t n_filters, const int32_t* query_filter, float* out_scores, int32_t* out_chunks,
+                        int32_t* out_counts, int mem, void* stream, const char* who) {
+    if (!kw) return fail(RL_ERR_INVALID, std::string(who) + ": null index");
+    if (n_queries < 0 || k < 1) return fail(RL_ERR_INVALID, std::string(who) + ": n_queries must be >= 0 and k >= 1");
+    if (k > K_MAX) return fail(RL_ERR_UNSUPPORTED, std::string(who) + ": k must be <= 2048");
     if (n_queries == 0) return RL_OK;
-    if (!q_off) return fail(RL_ERR_INVALID, "rl_keyword_search: null q_off");
-    if (!out_scores || !out_chunks) return fail(RL_ERR_INVALID, "rl_keyword_search: null output");
+    if (!q_off) return fail(RL_ERR_INVALID, std::string(who) + ": null q_off");
+    if (!out_scores || !out_chunks) return fail(RL_ERR_INVALID, std::string(who) + ": null output");
     int64_t n_q_terms = 0;
     if (mem == RL_MEM_HOST) {
-        RL_TRY(check_host_q_off(q_off, q_terms, n_queries, "rl_keyword_search"));
+        RL_TRY(check_host_q_off(q_off, q_terms, n_queries, who));
         n_q_terms = q_off[n_queries];
     } else if (!q_terms) {
-        return fail(RL_ERR_INVALID, "rl_keyword_search: null q_terms");
+        return fail(RL_ERR_INVALID, std::string(who) + ": null q_terms");
     }
     hipStream_t s = as_stream(stream);
     std::lock_guard<std::mutex> lock(kw->mu);
@@ -3107,7 +3260,9 @@ int rl_keyword_search(rl_keyword_index* kw, const int64_t* q_off, const int32_t*
     RL_TRY(stage_in(q_off, (size_t)n_queries + 1, mem, s, t_off, &d_off));
     if (mem == RL_MEM_HOST) RL_TRY(stage_in(q_terms, (size_t)n_q_terms, mem, s, t_terms, &d_terms));
     else d_terms = q_terms;
-    if (chunk_filter) RL_TRY(stage_in(chunk_filter, (size_t)((n + 31) / 32), mem, s, t_f, &d_f));
+    if (n_filters) RL_TRY(stage_in(chunk_filters, (size_t)n_filters * ((n + 31) / 32), mem, s, t_f, &d_f));
+    QueryMask mask;
+    RL_TRY(keyword_mask(kw, d_f, n_filters, query_filter, n_queries, s, &mask));
     RL_TRY(stage_out_begin(out_scores, n_out, mem, t_s, &d_s));
     RL_TRY(stage_out_begin(out_chunks, n_out, mem, t_c, &d_c));
     if (out_counts) RL_TRY(stage_out_begin(out_counts, (size_t)n_queries, mem, t_n, &d_n));
@@ -3115,12 +3270,30 @@ int rl_keyword_search(rl_keyword_index* kw, const int64_t* q_off, const int32_t*
         RL_TRY(t_n.alloc((size_t)n_queries * sizeof(int32_t)));
         d_n = t_n.as<int32_t>();
     }
-    RL_TRY(keyword_search_device(kw, d_off, d_terms, n_queries, k, d_f, d_s, d_c, d_n, s));
+    RL_TRY(keyword_search_device(kw, d_off, d_terms, n_queries, k, mask, d_s, d_c, d_n, s));
     RL_TRY(stage_out_end(out_scores, n_out, mem, s, t_s));
     RL_TRY(stage_out_end(out_chunks, n_out, mem, s, t_c));
     if (out_counts) RL_TRY(stage_out_end(out_counts, (size_t)n_queries, mem, s, t_n));
     if (mem == RL_MEM_DEVICE && !out_counts) RL_HIP(hipStreamSynchronize(s));  // t_n dies with this frame
     return finish(mem, s);
+}
+}  // namespace
+
+extern "C" {
+
+int rl_keyword_search(rl_keyword_index* kw, const int64_t* q_off, const int32_t* q_terms, int32_t n_queries, int32_t k,
+                      const uint32_t* chunk_filter, float* out_scores, int32_t* out_chunks, int32_t* out_counts, int mem, void* stream) {
+    return keyword_search_call(kw, q_off, q_terms, n_queries, k, chunk_filter, chunk_filter ? 1 : 0, nullptr, out_scores, out_chunks,
+                               out_counts, mem, stream, "rl_keyword_search");
+}
+
+int rl_keyword_search_per_query(rl_keyword_index* kw, const int64_t* q_off, const int32_t* q_terms, int32_t n_queries, int32_t k,
+                                const uint32_t* chunk_filters, int32_t n_filters, const int32_t* query_filter, float* out_scores,
+                                int32_t* out_chunks, int32_t* out_counts, int mem, void* stream) {
+    const char* who = "rl_keyword_search_per_query";
+    RL_TRY(check_query_filters(n_queries, chunk_filters, n_filters, query_filter, nullptr, who));
+    return keyword_search_call(kw, q_off, q_terms, n_queries, k, chunk_filters, query_filter ? n_filters : 0, query_filter, out_scores,
+                               out_chunks, out_counts, mem, stream, who);
 }
 
 // ---- weighted Reciprocal Rank Fusion and batched hybrid search (include/raglite_hip.h; the kernel is in fuse.hip) ------------------
@@ -3178,27 +3351,31 @@ int rl_shard_hybrid_fuse(const int32_t* gathered, int32_t world, int32_t n_queri
     return finish(mem, s);
 }
 
-int rl_hybrid_search(rl_index* idx, rl_keyword_index* kw, const float* queries, int32_t n_queries, int32_t num_hits, int32_t n_each,
-                     const int64_t* q_off, const int32_t* q_terms, const uint32_t* chunk_filter, int64_t rank_limit, const double* weights,
-                     int32_t rrf_k, int32_t k, double* out_scores, int32_t* out_chunks, int32_t* out_counts, int mem, void* stream) {
-    const char* who = "rl_hybrid_search";
+}  // extern "C"
+
+namespace {
+// rl_hybrid_search and rl_hybrid_search_per_query: one device path
+int hybrid_search_call(rl_index* idx, rl_keyword_index* kw, const float* queries, int32_t n_queries, int32_t num_hits, int32_t n_each,
+                       const int64_t* q_off, const int32_t* q_terms, const uint32_t* chunk_filters, int32_t n_filters, const int32_t* query_filter,
+                       const int64_t* rank_limits, int64_t rank_limit, const double* weights, int32_t rrf_k, int32_t k, double* out_scores,
+                       int32_t* out_chunks, int32_t* out_counts, int mem, void* stream, const char* who) {
     const int32_t B = n_queries, R = kw ? 2 : 1;
     RL_TRY(check_search_args(idx, queries, B, n_each, who));
-    if (rank_limit < 0) return fail(RL_ERR_INVALID, "rl_hybrid_search: rank_limit must be >= 0 (0 = no cut)");
-    if (num_hits < 1 || num_hits > K_MAX) return fail(RL_ERR_INVALID, "rl_hybrid_search: num_hits must be in [1, 2048]");
+    if (rank_limit < 0) return fail(RL_ERR_INVALID, std::string(who) + ": rank_limit must be >= 0 (0 = no cut)");
+    if (num_hits < 1 || num_hits > K_MAX) return fail(RL_ERR_INVALID, std::string(who) + ": num_hits must be in [1, 2048]");
     RL_TRY(check_fuse_args(R, B, n_each, weights, rrf_k, k, who));
-    if (mem != RL_MEM_HOST && mem != RL_MEM_DEVICE) return fail(RL_ERR_INVALID, "rl_hybrid_search: bad mem");
-    if (kw && kw->n_chunks != idx->n_chunks) return fail(RL_ERR_INVALID, "rl_hybrid_search: the keyword index covers another number of chunks");
+    if (mem != RL_MEM_HOST && mem != RL_MEM_DEVICE) return fail(RL_ERR_INVALID, std::string(who) + ": bad mem");
+    if (kw && kw->n_chunks != idx->n_chunks) return fail(RL_ERR_INVALID, std::string(who) + ": the keyword index covers another number of chunks");
     if (B == 0) return RL_OK;
-    if (!out_scores || !out_chunks || !out_counts) return fail(RL_ERR_INVALID, "rl_hybrid_search: null output");
+    if (!out_scores || !out_chunks || !out_counts) return fail(RL_ERR_INVALID, std::string(who) + ": null output");
     int64_t n_q_terms = 0;
     if (kw) {
-        if (!q_off) return fail(RL_ERR_INVALID, "rl_hybrid_search: null q_off");
+        if (!q_off) return fail(RL_ERR_INVALID, std::string(who) + ": null q_off");
         if (mem == RL_MEM_HOST) {
             RL_TRY(check_host_q_off(q_off, q_terms, B, who));
             n_q_terms = q_off[B];
         } else if (!q_terms) {
-            return fail(RL_ERR_INVALID, "rl_hybrid_search: null q_terms");
+            return fail(RL_ERR_INVALID, std::string(who) + ": null q_terms");
         }
     }
     hipStream_t s = as_stream(stream);
@@ -3212,13 +3389,17 @@ int rl_hybrid_search(rl_index* idx, rl_keyword_index* kw, const float* queries, 
     const size_t n_list = (size_t)B * n_each, n_out = (size_t)B * k;
     DevBuf t_q, t_f, t_off, t_terms, t_s, t_c, t_n;
     const float* d_q;
-    const uint32_t* d_f = nullptr;
     const int64_t* d_off = nullptr;
     const int32_t* d_terms = q_terms;
     double* d_s;
     int32_t *d_c, *d_n;
+    BatchFilters f;
+    f.n = n_filters;
+    f.qf = query_filter;
+    f.lim = rank_limits;
+    f.limit = rank_limit;
     RL_TRY(stage_in(queries, (size_t)B * idx->dim, mem, s, t_q, &d_q));
-    if (chunk_filter) RL_TRY(stage_in(chunk_filter, (size_t)((idx->n_chunks + 31) / 32), mem, s, t_f, &d_f));
+    if (n_filters) RL_TRY(stage_in(chunk_filters, (size_t)n_filters * ((idx->n_chunks + 31) / 32), mem, s, t_f, &f.chunk_bits));
     if (kw) {
         RL_TRY(stage_in(q_off, (size_t)B + 1, mem, s, t_off, &d_off));
         if (mem == RL_MEM_HOST) RL_TRY(stage_in(q_terms, (size_t)n_q_terms, mem, s, t_terms, &d_terms));
@@ -3232,13 +3413,37 @@ int rl_hybrid_search(rl_index* idx, rl_keyword_index* kw, const float* queries, 
     int32_t* lists = idx->hybrid.as<int32_t>();
     float* list_scores = reinterpret_cast<float*>(lists + (size_t)R * n_list);
     int32_t* list_counts = reinterpret_cast<int32_t*>(list_scores + (size_t)R * n_list);
-    RL_TRY(search_chunks_device(idx, d_q, B, num_hits, n_each, d_f, rank_limit, list_scores, lists, list_counts, s));
-    if (kw) RL_TRY(keyword_search_device(kw, d_off, d_terms, B, n_each, d_f, list_scores + n_list, lists + n_list, list_counts + B, s));
+    RL_TRY(search_chunks_device(idx, d_q, B, num_hits, n_each, f, list_scores, lists, list_counts, s));
+    if (kw) {
+        QueryMask mask;
+        RL_TRY(keyword_mask(kw, f.chunk_bits, n_filters, query_filter, B, s, &mask));
+        RL_TRY(keyword_search_device(kw, d_off, d_terms, B, n_each, mask, list_scores + n_list, lists + n_list, list_counts + B, s));
+    }
     RL_TRY(launch_rrf_fuse(lists, R, B, n_each, weights, rrf_k, k, d_s, d_c, d_n, s));
     RL_TRY(stage_out_end(out_scores, n_out, mem, s, t_s));
     RL_TRY(stage_out_end(out_chunks, n_out, mem, s, t_c));
     RL_TRY(stage_out_end(out_counts, (size_t)B, mem, s, t_n));
     return finish(mem, s);
+}
+}  // namespace
+
+extern "C" {
+
+int rl_hybrid_search(rl_index* idx, rl_keyword_index* kw, const float* queries, int32_t n_queries, int32_t num_hits, int32_t n_each,
+                     const int64_t* q_off, const int32_t* q_terms, const uint32_t* chunk_filter, int64_t rank_limit, const double* weights,
+                     int32_t rrf_k, int32_t k, double* out_scores, int32_t* out_chunks, int32_t* out_counts, int mem, void* stream) {
+    return hybrid_search_call(idx, kw, queries, n_queries, num_hits, n_each, q_off, q_terms, chunk_filter, chunk_filter ? 1 : 0, nullptr, nullptr,
+                              rank_limit, weights, rrf_k, k, out_scores, out_chunks, out_counts, mem, stream, "rl_hybrid_search");
+}
+
+int rl_hybrid_search_per_query(rl_index* idx, rl_keyword_index* kw, const float* queries, int32_t n_queries, int32_t num_hits, int32_t n_each,
+                               const int64_t* q_off, const int32_t* q_terms, const uint32_t* chunk_filters, int32_t n_filters,
+                               const int32_t* query_filter, const int64_t* rank_limits, const double* weights, int32_t rrf_k, int32_t k,
+                               double* out_scores, int32_t* out_chunks, int32_t* out_counts, int mem, void* stream) {
+    const char* who = "rl_hybrid_search_per_query";
+    RL_TRY(check_query_filters(n_queries, chunk_filters, n_filters, query_filter, rank_limits, who));
+    return hybrid_search_call(idx, kw, queries, n_queries, num_hits, n_each, q_off, q_terms, chunk_filters, query_filter ? n_filters : 0,
+                              query_filter, rank_limits, 0, weights, rrf_k, k, out_scores, out_chunks, out_counts, mem, stream, who);
 }
 
 }  // extern "C"

@@ -218,6 +218,30 @@ int launch_merge_topk(const float* in_scores, const int32_t* in_ids, int32_t n_l
                       const uint32_t* counts = nullptr,  // counts (n_lists == 1): records list q really holds
                       const MergeTransform* transform = nullptr);
 
+// The bitset each query of a batch is masked with (mask.hip, select.hip, keyword.hip): query b reads sets + set[b] * ld, or `none` where
+// set[b] < 0; set == nullptr: every query reads `sets`.  A query whose bitset is nullptr is not masked.  A plain pointer converts to
+// the mask every query shares.
+struct QueryMask {
+    const uint32_t* sets = nullptr;
+    int64_t ld = 0;                  // words per bitset
+    const int32_t* set = nullptr;    // device [n_queries]
+    const uint32_t* none = nullptr;
+    QueryMask() = default;
+    QueryMask(const uint32_t* bits) : sets(bits) {}  // NOLINT(google-explicit-constructor)
+    QueryMask(const uint32_t* sets_, int64_t ld_, const int32_t* set_, const uint32_t* none_) : sets(sets_), ld(ld_), set(set_), none(none_) {}
+    __host__ __device__ const uint32_t* of(int64_t b) const {
+        if (!set) return sets;
+        const int32_t f = set[b];
+        return f >= 0 ? sets + (int64_t)f * ld : none;
+    }
+    bool any() const { return sets || none; }  // (host) some query of the batch is masked
+    QueryMask from(int32_t b0) const {         // the mask of the sub-batch that starts at query b0
+        QueryMask m = *this;
+        if (m.set) m.set += b0;
+        return m;
+    }
+};
+
 // select.hip, rank cut (order-first-then-filter, src/raglite/_search.py:120-141): rows outside the rank_limit best of their
 // query, and rows whose keep bit is clear, become -inf
 // the cut in stages (a corpus sharded over several indexes sums each level's histogram over the shards between them)
@@ -230,7 +254,8 @@ int launch_rank_stage_ties(const float* scores, int32_t n_queries, int64_t n, in
 int launch_rank_stage_apply(float* scores, int32_t n_queries, int64_t n, int64_t ld, int64_t rank_limit, const uint32_t* keep_bits,
                             void* scratch, const uint32_t* tie_base, hipStream_t s);
 size_t rank_cut_scratch_bytes(int32_t n_queries, int64_t n);
-int launch_rank_cut(float* scores, int32_t n_queries, int64_t n, int64_t ld, int64_t rank_limit, const uint32_t* keep_bits,
+// limits != nullptr: query b cuts at limits[b] instead of rank_limit (device [n_queries]; >= n: no cut, only its keep bits)
+int launch_rank_cut(float* scores, int32_t n_queries, int64_t n, int64_t ld, int64_t rank_limit, const uint32_t* limits, const QueryMask& keep,
                     void* scratch, hipStream_t s);
 
 // hi_filter.hip: helpers of the half-bytes single-query search (api.hip: search_rows_hi)
@@ -306,9 +331,11 @@ int launch_list_raise_threshold(const float* in_scores, const int32_t* in_ids, i
                                 const float* window, float* thr, hipStream_t s);
 
 // mask.hip: validity bitsets (metadata filter pushed down to the device, tombstones of deleted chunks)
-int launch_expand_chunk_bits(const uint32_t* chunk_bits, const int32_t* row_to_chunk, int64_t n_rows,
-                             const uint32_t* and_rows, uint32_t* row_bits, hipStream_t s);
-int launch_mask_scores(float* scores, int32_t nb, int64_t n, int64_t ld, const uint32_t* bits, hipStream_t s);
+// n_sets chunk bitsets -> row bitsets in one launch: row_bits [n_sets x (n_rows + 31) / 32] from chunk_bits + fid[j] * chunk_ld (fid
+// nullptr: bitset j), each and-ed with and_rows when given
+int launch_expand_chunk_bits(const uint32_t* chunk_bits, int64_t chunk_ld, const int32_t* fid, int32_t n_sets, const int32_t* row_to_chunk,
+                             int64_t n_rows, const uint32_t* and_rows, uint32_t* row_bits, hipStream_t s);
+int launch_mask_scores(float* scores, int32_t nb, int64_t n, int64_t ld, const QueryMask& bits, hipStream_t s);
 int launch_fix_masked(const float* scores, int32_t* ids, int64_t count, hipStream_t s);
 int launch_popcount(const uint32_t* bits, int64_t n, unsigned long long* out_dev, hipStream_t s);
 
@@ -321,7 +348,7 @@ int32_t bm25_tile(int64_t n_chunks, int32_t n_queries, int n_cu);  // the tile l
 // scores[b * ld + c] (c < n_chunks): the BM25 score of chunk c for query b (terms q_terms[q_off[b] .. q_off[b + 1]), ascending),
 // -inf where the chunk has none of them or its filter bit is clear
 int launch_bm25_score(const int64_t* term_off, const int32_t* post_chunk, const float* post_impact, int32_t n_terms, int64_t n_chunks,
-                      const int64_t* q_off, const int32_t* q_terms, int32_t n_queries, const uint32_t* filter, int32_t tile, float* scores,
+                      const int64_t* q_off, const int32_t* q_terms, int32_t n_queries, const QueryMask& filter, int32_t tile, float* scores,
                       int64_t ld, hipStream_t s);
 int launch_bm25_count(const float* sel, int32_t n_queries, int32_t k, int32_t* counts, hipStream_t s);  // finite entries per selected row
 

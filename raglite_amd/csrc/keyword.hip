@@ -60,11 +60,11 @@ __device__ __forceinline__ int64_t lower_bound_32(const int32_t* __restrict__ ar
 
 // grid (chunk tiles, queries); block KW_THREADS; dynamic LDS: `tile` floats (the tile's scores).
 // q_off [B + 1] / q_terms: each query's term ids, ascending and distinct (ids outside [0, n_terms) are skipped).
-// filter (may be null): bit c of the chunk bitset cleared -> -inf.  Writes scores[b * ld + c] for c < n_chunks.
+// filter: query b's chunk bitset (none: no filter), bit c cleared -> -inf.  Writes scores[b * ld + c] for c < n_chunks.
 __global__ __launch_bounds__(KW_THREADS) void bm25_score_kernel(const int64_t* __restrict__ term_off, const int32_t* __restrict__ post_chunk,
                                                                 const float* __restrict__ post_impact, int32_t n_terms, int64_t n_chunks,
                                                                 const int64_t* __restrict__ q_off, const int32_t* __restrict__ q_terms,
-                                                                const uint32_t* __restrict__ filter, int32_t tile, float* __restrict__ scores,
+                                                                QueryMask filter_of, int32_t tile, float* __restrict__ scores,
                                                                 int64_t ld) {
     extern __shared__ float s[];
     __shared__ int64_t range[KW_TERM_GROUP][2];
@@ -115,6 +115,7 @@ __global__ __launch_bounds__(KW_THREADS) void bm25_score_kernel(const int64_t* _
         }
     }
     float* out = scores + (int64_t)b * ld + lo;
+    const uint32_t* __restrict__ filter = filter_of.of(b);
     for (int i = threadIdx.x; i < width; i += KW_THREADS) {
         float v = s[i];
         if (filter) {
@@ -153,7 +154,7 @@ int32_t bm25_tile(int64_t n_chunks, int32_t n_queries, int n_cu) {
 }
 
 int launch_bm25_score(const int64_t* term_off, const int32_t* post_chunk, const float* post_impact, int32_t n_terms, int64_t n_chunks,
-                      const int64_t* q_off, const int32_t* q_terms, int32_t n_queries, const uint32_t* filter, int32_t tile, float* scores,
+                      const int64_t* q_off, const int32_t* q_terms, int32_t n_queries, const QueryMask& filter, int32_t tile, float* scores,
                       int64_t ld, hipStream_t s) {
     if (n_queries <= 0 || n_chunks <= 0) return RL_OK;
     if (tile < 256 || tile > BM25_TILE_MAX || (tile & 255)) return fail(RL_ERR_INVALID, "launch_bm25_score: bad tile");

@@ -8,34 +8,39 @@
 namespace rl {
 namespace {
 
-// row_bits[w] = bits of rows 32w .. 32w+31: chunk_bits[row_to_chunk[r]] (all ones when chunk_bits == nullptr),
-// and-ed with and_rows[w] when given.
-__global__ __launch_bounds__(256) void expand_chunk_bits_kernel(const uint32_t* __restrict__ chunk_bits,
+// Bitset j of a batch (grid y): row_bits[j][w] = bits of rows 32w .. 32w+31: chunk_bits[fid[j]][row_to_chunk[r]] (all ones when
+// chunk_bits == nullptr), and-ed with and_rows[w] when given.
+__global__ __launch_bounds__(256) void expand_chunk_bits_kernel(const uint32_t* __restrict__ chunk_bits, int64_t chunk_ld,
+                                                                 const int32_t* __restrict__ fid,
                                                                  const int32_t* __restrict__ row_to_chunk,
                                                                  int64_t n_rows,
                                                                  const uint32_t* __restrict__ and_rows,
                                                                  uint32_t* __restrict__ row_bits) {
     const int64_t r = (int64_t)blockIdx.x * 256 + threadIdx.x;  // one lane per row, one ballot per 64 rows
+    const int64_t words = (n_rows + 31) >> 5;
+    const uint32_t* cb = chunk_bits ? chunk_bits + (int64_t)(fid ? fid[blockIdx.y] : (int32_t)blockIdx.y) * chunk_ld : nullptr;
     bool on = false;
     if (r < n_rows) {
         on = true;
-        if (chunk_bits) {
+        if (cb) {
             const int32_t c = row_to_chunk[r];
-            on = (chunk_bits[c >> 5] >> (c & 31)) & 1u;
+            on = (cb[c >> 5] >> (c & 31)) & 1u;
         }
     }
     const uint64_t b = __builtin_amdgcn_ballot_w64(on);
     const int lane = threadIdx.x & 63;
     const int64_t w = r >> 5;
-    if ((lane & 31) == 0 && w < ((n_rows + 31) >> 5)) {  // lanes 0 and 32 own one 32-row word each
+    if ((lane & 31) == 0 && w < words) {  // lanes 0 and 32 own one 32-row word each
         uint32_t word = (uint32_t)(lane ? (b >> 32) : b);
         if (and_rows) word &= and_rows[w];
-        row_bits[w] = word;
+        row_bits[(int64_t)blockIdx.y * words + w] = word;
     }
 }
 
-__global__ __launch_bounds__(256) void mask_scores_kernel(float* __restrict__ scores, int64_t n, int64_t ld,
-                                                           const uint32_t* __restrict__ bits) {
+// Query blockIdx.y's elements whose bit is clear in its bitset -> -inf (a query without a bitset is left as it is)
+__global__ __launch_bounds__(256) void mask_scores_kernel(float* __restrict__ scores, int64_t n, int64_t ld, QueryMask m) {
+    const uint32_t* __restrict__ bits = m.of(blockIdx.y);
+    if (!bits) return;
     float* s = scores + (int64_t)blockIdx.y * ld;
     const int64_t stride = (int64_t)gridDim.x * 256;
     const int64_t words = (n + 31) >> 5;
@@ -73,18 +78,18 @@ __global__ __launch_bounds__(256) void popcount_kernel(const uint32_t* __restric
 }
 }  // namespace
 
-int launch_expand_chunk_bits(const uint32_t* chunk_bits, const int32_t* row_to_chunk, int64_t n_rows,
-                             const uint32_t* and_rows, uint32_t* row_bits, hipStream_t s) {
-    if (n_rows <= 0) return RL_OK;
+int launch_expand_chunk_bits(const uint32_t* chunk_bits, int64_t chunk_ld, const int32_t* fid, int32_t n_sets, const int32_t* row_to_chunk,
+                             int64_t n_rows, const uint32_t* and_rows, uint32_t* row_bits, hipStream_t s) {
+    if (n_rows <= 0 || n_sets <= 0) return RL_OK;
     const int64_t padded = (n_rows + 63) & ~int64_t(63);
-    hipLaunchKernelGGL(expand_chunk_bits_kernel, dim3((unsigned)((padded + 255) / 256)), dim3(256), 0, s, chunk_bits,
-                       row_to_chunk, n_rows, and_rows, row_bits);
+    hipLaunchKernelGGL(expand_chunk_bits_kernel, dim3((unsigned)((padded + 255) / 256), (unsigned)n_sets), dim3(256), 0, s, chunk_bits,
+                       chunk_ld, fid, row_to_chunk, n_rows, and_rows, row_bits);
     RL_HIP(hipGetLastError());
     return RL_OK;
 }
 
-int launch_mask_scores(float* scores, int32_t nb, int64_t n, int64_t ld, const uint32_t* bits, hipStream_t s) {
-    if (n <= 0 || nb <= 0) return RL_OK;
+int launch_mask_scores(float* scores, int32_t nb, int64_t n, int64_t ld, const QueryMask& bits, hipStream_t s) {
+    if (n <= 0 || nb <= 0 || !bits.any()) return RL_OK;
     const int64_t words = (n + 31) >> 5;
     const int bx = (int)std::max<int64_t>(1, std::min<int64_t>((words + 255) / 256, 1024));
     hipLaunchKernelGGL(mask_scores_kernel, dim3(bx, nb), dim3(256), 0, s, scores, n, ld, bits);

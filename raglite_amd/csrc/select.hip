@@ -1002,13 +1002,18 @@ __device__ __forceinline__ void rank_prefix(const uint32_t* __restrict__ hq, int
 
 // LEVEL 0: histogram of the key's top 11 bits; LEVEL 1: of bits [20:10] among keys whose top 11 bits are the level-0
 // threshold bin; LEVEL 2: of bits [9:0] among keys matching the 22-bit prefix.
+// Lq != nullptr: query q's limit is Lq[q] (>= n: it has no cut), else L (which may exceed n in a staged cut over shards).
 template <int LEVEL>
 __global__ __launch_bounds__(256) void rank_level_kernel(const float* __restrict__ scores, int64_t n, int64_t ld, uint32_t L,
-                                                          uint32_t* __restrict__ hists) {
+                                                          const uint32_t* __restrict__ Lq, uint32_t* __restrict__ hists) {
     __shared__ uint32_t h[HIST_BINS];
     __shared__ uint32_t scratch[8];
     __shared__ uint32_t thr[2];
     const int q = blockIdx.y;
+    if (Lq) {
+        L = Lq[q];
+        if ((int64_t)L >= n) return;
+    }
     uint32_t* hq = hists + (int64_t)q * 3 * HIST_BINS;
     uint32_t prefix, need;
     rank_prefix(hq, LEVEL, L, h, scratch, thr, prefix, need);
@@ -1028,11 +1033,16 @@ __global__ __launch_bounds__(256) void rank_level_kernel(const float* __restrict
 
 // Keys equal to the threshold T in this block's RANK_CHUNK rows -> tie_counts[q][block].
 __global__ __launch_bounds__(256) void rank_tie_count_kernel(const float* __restrict__ scores, int64_t n, int64_t ld, uint32_t L,
-                                                              const uint32_t* __restrict__ hists, uint32_t* __restrict__ tie_counts) {
+                                                              const uint32_t* __restrict__ Lq, const uint32_t* __restrict__ hists,
+                                                              uint32_t* __restrict__ tie_counts) {
     __shared__ uint32_t h[HIST_BINS];
     __shared__ uint32_t scratch[8];
     __shared__ uint32_t thr[2];
     const int q = blockIdx.y;
+    if (Lq) {
+        L = Lq[q];
+        if ((int64_t)L >= n) return;  // (no cut: rank_cut_kernel reads none of this query's counts)
+    }
     uint32_t T, need_eq;
     rank_prefix(hists + (int64_t)q * 3 * HIST_BINS, 3, L, h, scratch, thr, T, need_eq);
     const float* s = scores + (int64_t)q * ld;
@@ -1047,15 +1057,28 @@ __global__ __launch_bounds__(256) void rank_tie_count_kernel(const float* __rest
     if (threadIdx.x == 0) tie_counts[(int64_t)q * gridDim.x + blockIdx.x] = total;
 }
 
-// scores[i] = -inf unless row i is among the L best of its query (ties on T: the need_eq lowest rows) AND, with keep_bits,
-// its bit is set (the metadata filter expanded to rows, tombstones included).
+// scores[i] = -inf unless row i is among the L best of its query (ties on T: the need_eq lowest rows) AND, with a keep bitset,
+// its bit is set (the metadata filter expanded to rows, tombstones included).  A query whose limit is >= n: its keep bits alone.
 __global__ __launch_bounds__(256) void rank_cut_kernel(float* __restrict__ scores, int64_t n, int64_t ld, uint32_t L,
-                                                        const uint32_t* __restrict__ hists, const uint32_t* __restrict__ tie_counts,
-                                                        const uint32_t* __restrict__ keep_bits, const uint32_t* __restrict__ tie_base) {
+                                                        const uint32_t* __restrict__ Lq, const uint32_t* __restrict__ hists,
+                                                        const uint32_t* __restrict__ tie_counts, QueryMask keep_mask,
+                                                        const uint32_t* __restrict__ tie_base) {
     __shared__ uint32_t h[HIST_BINS];
     __shared__ uint32_t scratch[8];
     __shared__ uint32_t thr[2];
     const int q = blockIdx.y;
+    const uint32_t* __restrict__ keep_bits = keep_mask.of(q);
+    float* s = scores + (int64_t)q * ld;
+    const int64_t base = (int64_t)blockIdx.x * RANK_CHUNK;
+    if (Lq) L = Lq[q];
+    if (Lq && (int64_t)L >= n) {  // (a staged cut's L may exceed this shard's n: its cut still applies)
+        if (!keep_bits) return;
+        for (int it = 0; it < RANK_CHUNK / 256; ++it) {
+            const int64_t i = base + it * 256 + threadIdx.x;
+            if (i < n && !((keep_bits[i >> 5] >> (i & 31)) & 1u)) s[i] = -INFINITY;
+        }
+        return;
+    }
     uint32_t T, need_eq;
     rank_prefix(hists + (int64_t)q * 3 * HIST_BINS, 3, L, h, scratch, thr, T, need_eq);
     uint32_t before = (tie_base && threadIdx.x == 0) ? tie_base[q] : 0u;  // ties in the shards before this one (sharded cut), then in the blocks before this one
@@ -1063,8 +1086,6 @@ __global__ __launch_bounds__(256) void rank_cut_kernel(float* __restrict__ score
     uint32_t running;
     (void)block_inclusive_scan(before, scratch, running);
     __syncthreads();
-    float* s = scores + (int64_t)q * ld;
-    const int64_t base = (int64_t)blockIdx.x * RANK_CHUNK;
     for (int it = 0; it < RANK_CHUNK / 256; ++it) {
         const int64_t i = base + it * 256 + threadIdx.x;
         const uint32_t key = i < n ? score_key(s[i]) : 0u;
@@ -1083,25 +1104,26 @@ size_t rank_cut_scratch_bytes(int32_t nq, int64_t n) {
     return (size_t)nq * (3 * HIST_BINS + (size_t)((n + RANK_CHUNK - 1) / RANK_CHUNK)) * sizeof(uint32_t);
 }
 
-// The cut + filter, in place on scores [nq x ld] (elements that do not take part already -inf).  rank_limit >= n: only the
-// filter.  scratch: rank_cut_scratch_bytes(nq, n).
-int launch_rank_cut(float* scores, int32_t nq, int64_t n, int64_t ld, int64_t rank_limit, const uint32_t* keep_bits, void* scratch,
-                    hipStream_t s) {
+// The cut + filter, in place on scores [nq x ld] (elements that do not take part already -inf).  limits == nullptr: every query cuts at
+// rank_limit (>= n: only the filter); else query q at limits[q] (>= n: only its filter).  scratch: rank_cut_scratch_bytes(nq, n).
+int launch_rank_cut(float* scores, int32_t nq, int64_t n, int64_t ld, int64_t rank_limit, const uint32_t* limits, const QueryMask& keep,
+                    void* scratch, hipStream_t s) {
     if (nq <= 0 || n <= 0) return RL_OK;
-    if (rank_limit < 1) return fail(RL_ERR_INVALID, "rank cut: rank_limit must be >= 1");
-    if (rank_limit >= n) return keep_bits ? launch_mask_scores(scores, nq, n, ld, keep_bits, s) : RL_OK;
+    if (!limits && rank_limit < 1) return fail(RL_ERR_INVALID, "rank cut: rank_limit must be >= 1");
+    if (!limits && rank_limit >= n) return launch_mask_scores(scores, nq, n, ld, keep, s);
     if (n >= (int64_t)0x7fffffff) return fail(RL_ERR_UNSUPPORTED, "rank cut: more than 2^31-2 elements per query");
     uint32_t* hists = static_cast<uint32_t*>(scratch);
     uint32_t* ties = hists + (size_t)nq * 3 * HIST_BINS;
     const int nblk = (int)((n + RANK_CHUNK - 1) / RANK_CHUNK);
-    const uint32_t L = (uint32_t)rank_limit;
+    const uint32_t L = limits ? 0u : (uint32_t)rank_limit;
     RL_HIP(hipMemsetAsync(hists, 0, (size_t)nq * 3 * HIST_BINS * sizeof(uint32_t), s));
     const int bx = (int)std::max<int64_t>(1, std::min<int64_t>((n + 4095) / 4096, nq >= 64 ? 64 : 512));
-    hipLaunchKernelGGL(rank_level_kernel<0>, dim3(bx, nq), dim3(256), 0, s, scores, n, ld, L, hists);
-    hipLaunchKernelGGL(rank_level_kernel<1>, dim3(bx, nq), dim3(256), 0, s, scores, n, ld, L, hists);
-    hipLaunchKernelGGL(rank_level_kernel<2>, dim3(bx, nq), dim3(256), 0, s, scores, n, ld, L, hists);
-    hipLaunchKernelGGL(rank_tie_count_kernel, dim3(nblk, nq), dim3(256), 0, s, scores, n, ld, L, hists, ties);
-    hipLaunchKernelGGL(rank_cut_kernel, dim3(nblk, nq), dim3(256), 0, s, scores, n, ld, L, hists, ties, keep_bits, nullptr);
+    hipLaunchKernelGGL(rank_level_kernel<0>, dim3(bx, nq), dim3(256), 0, s, scores, n, ld, L, limits, hists);
+    hipLaunchKernelGGL(rank_level_kernel<1>, dim3(bx, nq), dim3(256), 0, s, scores, n, ld, L, limits, hists);
+    hipLaunchKernelGGL(rank_level_kernel<2>, dim3(bx, nq), dim3(256), 0, s, scores, n, ld, L, limits, hists);
+    hipLaunchKernelGGL(rank_tie_count_kernel, dim3(nblk, nq), dim3(256), 0, s, scores, n, ld, L, limits, hists, ties);
+    hipLaunchKernelGGL(rank_cut_kernel, dim3(nblk, nq), dim3(256), 0, s, scores, n, ld, L, limits, hists, ties, keep,
+                       (const uint32_t*)nullptr);
     RL_HIP(hipGetLastError());
     return RL_OK;
 }
@@ -1140,9 +1162,9 @@ int launch_rank_stage_level(const float* scores, int32_t nq, int64_t n, int64_t 
     if (level == 0) RL_HIP(hipMemsetAsync(hists, 0, (size_t)nq * 3 * HIST_BINS * sizeof(uint32_t), s));
     if (n > 0) {
         const int bx = (int)std::max<int64_t>(1, std::min<int64_t>((n + 4095) / 4096, nq >= 64 ? 64 : 512));
-        if (level == 0) hipLaunchKernelGGL(rank_level_kernel<0>, dim3(bx, nq), dim3(256), 0, s, scores, n, ld, L, hists);
-        else if (level == 1) hipLaunchKernelGGL(rank_level_kernel<1>, dim3(bx, nq), dim3(256), 0, s, scores, n, ld, L, hists);
-        else hipLaunchKernelGGL(rank_level_kernel<2>, dim3(bx, nq), dim3(256), 0, s, scores, n, ld, L, hists);
+        if (level == 0) hipLaunchKernelGGL(rank_level_kernel<0>, dim3(bx, nq), dim3(256), 0, s, scores, n, ld, L, (const uint32_t*)nullptr, hists);
+        else if (level == 1) hipLaunchKernelGGL(rank_level_kernel<1>, dim3(bx, nq), dim3(256), 0, s, scores, n, ld, L, (const uint32_t*)nullptr, hists);
+        else hipLaunchKernelGGL(rank_level_kernel<2>, dim3(bx, nq), dim3(256), 0, s, scores, n, ld, L, (const uint32_t*)nullptr, hists);
     }
     hipLaunchKernelGGL(rank_level_copy_kernel, dim3(nq), dim3(256), 0, s, hists, level, level_out, 1);
     RL_HIP(hipGetLastError());
@@ -1163,7 +1185,7 @@ int launch_rank_stage_ties(const float* scores, int32_t nq, int64_t n, int64_t l
     uint32_t* ties = hists + (size_t)nq * 3 * HIST_BINS;
     const int nblk = (int)std::max<int64_t>(1, (n + RANK_CHUNK - 1) / RANK_CHUNK);
     const uint32_t L = (uint32_t)std::min<int64_t>(rank_limit, 0xffffffffll);
-    hipLaunchKernelGGL(rank_tie_count_kernel, dim3(nblk, nq), dim3(256), 0, s, scores, n, ld, L, hists, ties);
+    hipLaunchKernelGGL(rank_tie_count_kernel, dim3(nblk, nq), dim3(256), 0, s, scores, n, ld, L, (const uint32_t*)nullptr, hists, ties);
     hipLaunchKernelGGL(rank_tie_total_kernel, dim3(nq), dim3(256), 0, s, ties, nblk, totals_out);
     RL_HIP(hipGetLastError());
     return RL_OK;
@@ -1176,7 +1198,7 @@ int launch_rank_stage_apply(float* scores, int32_t nq, int64_t n, int64_t ld, in
     uint32_t* ties = hists + (size_t)nq * 3 * HIST_BINS;
     const int nblk = (int)((n + RANK_CHUNK - 1) / RANK_CHUNK);
     const uint32_t L = (uint32_t)std::min<int64_t>(rank_limit, 0xffffffffll);
-    hipLaunchKernelGGL(rank_cut_kernel, dim3(nblk, nq), dim3(256), 0, s, scores, n, ld, L, hists, ties, keep_bits, tie_base);
+    hipLaunchKernelGGL(rank_cut_kernel, dim3(nblk, nq), dim3(256), 0, s, scores, n, ld, L, (const uint32_t*)nullptr, hists, ties, QueryMask(keep_bits), tie_base);
     RL_HIP(hipGetLastError());
     return RL_OK;
 }
