@@ -261,8 +261,12 @@ typedef enum {
  *   key                         values (default)   what it schedules
  *   RL_OPT_PP_SCHEDULE          0 / 1 (1)          the sixteen-query MaxSim pass (maxsim_pp.hip): 1 = the passes over one row range run side by
  *                                                  side on one XCD, so one HBM read of the corpus serves all of them; 0 = pass after pass, each
- *                                                  pass streaming the whole HI image (raglite_amd/csrc/pp_schedule.h) */
-enum { RL_OPT_PP_SCHEDULE = 64 };
+ *                                                  pass streaming the whole HI image (raglite_amd/csrc/pp_schedule.h)
+ *   RL_OPT_PP_XCD_PASSES        8 / 4 / 2 / 1 (2)  read only with RL_OPT_PP_SCHEDULE = 1: how many passes of a block of eight share an XCD at a
+ *                                                  time.  8 = the co-scheduled order above (a few row ranges x all passes per XCD); 4, 2, 1 =
+ *                                                  the XCD-affine order: an XCD serves that many passes for the whole launch, so their query
+ *                                                  image stays in its L2, and the XCDs walk the row ranges in step (pp_schedule_affine) */
+enum { RL_OPT_PP_SCHEDULE = 64, RL_OPT_PP_XCD_PASSES = 65 };
 int rl_set_default_option(int key, int64_t value);
 int rl_get_default_option(int key, int64_t* value);
 int rl_index_set_option(rl_index* index, int key, int64_t value);

@@ -225,7 +225,7 @@ constexpr size_t SCORE_BATCH_BYTES = size_t(8) << 30;  // cap of the [B x N] sco
 // Route options (raglite_hip.h "options"): per index, copied from the process-wide defaults when the index is created.  The library
 // reads no environment variable.
 struct Options {
-    int64_t v[RL_OPT_PP_SCHEDULE + 1];  // (keys 1 .. RL_OPT_COUNT_ - 1, and the schedule switches from 64 on)
+    int64_t v[RL_OPT_PP_XCD_PASSES + 1];  // (keys 1 .. RL_OPT_COUNT_ - 1, and the schedule switches from 64 on)
     Options() {
         for (auto& x : v) x = 0;
         v[RL_OPT_HI_SEARCH] = v[RL_OPT_HI_MAXSIM] = v[RL_OPT_HI_PRODUCTS] = v[RL_OPT_PP_PASS] = v[RL_OPT_FUSED_TOPK] = v[RL_OPT_FUSED_HI] = 1;
@@ -234,6 +234,7 @@ struct Options {
         v[RL_OPT_TOPK_BLOCK] = v[RL_OPT_PAIRS_PACKED] = 2;
         v[RL_OPT_HI_PIVOT] = 1;
         v[RL_OPT_PP_SCHEDULE] = 1;
+        v[RL_OPT_PP_XCD_PASSES] = 2;  // (measured: DESIGN.md 4.1)
         v[RL_OPT_IMAGE_HEADROOM_MB] = -1;
         v[RL_OPT_ARITHMETIC] = RL_ARITH_AUTO;
     }
@@ -241,7 +242,7 @@ struct Options {
 };
 std::mutex g_default_opts_mu;
 Options g_default_opts;
-bool option_key_ok(int key) { return (key >= 1 && key < RL_OPT_COUNT_) || key == RL_OPT_PP_SCHEDULE; }
+bool option_key_ok(int key) { return (key >= 1 && key < RL_OPT_COUNT_) || key == RL_OPT_PP_SCHEDULE || key == RL_OPT_PP_XCD_PASSES; }
 bool option_value_ok(int key, int64_t value) {
     switch (key) {
         case RL_OPT_HI_SEARCH: case RL_OPT_HI_MAXSIM: case RL_OPT_PP_PASS: case RL_OPT_FUSED_TOPK: case RL_OPT_FUSED_HI: case RL_OPT_FUSED_PP:
@@ -249,6 +250,7 @@ bool option_value_ok(int key, int64_t value) {
         case RL_OPT_EXACT_KTH_THRESHOLD: case RL_OPT_FUSED_TWO_ROUNDS: case RL_OPT_KEEP_HI_PLANE: case RL_OPT_F16_EXACT: case RL_OPT_LAZY_IMAGES: case RL_OPT_FUSED_PP_SAMPLE: case RL_OPT_LIST_SELECT: case RL_OPT_HI_FEW: case RL_OPT_HI_PIVOT:
         case RL_OPT_PP_SCHEDULE:
             return value == 0 || value == 1;
+        case RL_OPT_PP_XCD_PASSES: return value == 8 || value == 4 || value == 2 || value == 1;
         case RL_OPT_TOPK_BLOCK: case RL_OPT_PAIRS_PACKED: return value >= 0 && value <= 2;
         case RL_OPT_HI_PRODUCTS: return value == 1 || value == 2;
         case RL_OPT_FUSED_TOPK_CAP: return value >= 0 && value <= MERGE_CAP;
@@ -2320,7 +2322,7 @@ int hi_batch_approx(rl_index* idx, const float* d_q, int32_t nq, int32_t n_queri
     if (pp)
         RL_TRY(launch_maxsim_pp(approx_image(idx), idx->n_rows, idx->dim, idx->qplanes.p, n_queries, 0, n_gemm, nq, idx->row_to_chunk,
                                 idx->offsets, idx->ends.as<uint32_t>(), sc, ld, idx->n_cu, s, approx_scale(idx), nullptr,
-                                (int)idx->opt.v[RL_OPT_PP_SCHEDULE]));
+                                (int)idx->opt.v[RL_OPT_PP_SCHEDULE], (int)idx->opt.v[RL_OPT_PP_XCD_PASSES]));
     for (int32_t b = 0; !pp && b < n_gemm; b += GEMM_PASS_QUERIES) {
         const int32_t n_q = std::min<int32_t>(GEMM_PASS_QUERIES, n_gemm - b);
         RL_TRY(launch_maxsim_gemm(approx_image(idx), idx->n_rows, idx->dim, idx->qplanes.p, n_queries, b, n_q, nq, idx->row_to_chunk,
@@ -2759,7 +2761,7 @@ int rl_maxsim_approx_scores(rl_index* idx, const float* query_vecs, int32_t n_qu
         if (kernel == 0)
             RL_TRY(launch_maxsim_pp(approx_image(idx), idx->n_rows, idx->dim, idx->qplanes.p, n_queries, b, n_q, nq, idx->row_to_chunk, idx->offsets,
                                     idx->ends.as<uint32_t>(), d_o + (int64_t)b * ld, ld, idx->n_cu, s, approx_scale(idx), nullptr,
-                                    (int)idx->opt.v[RL_OPT_PP_SCHEDULE]));
+                                    (int)idx->opt.v[RL_OPT_PP_SCHEDULE], (int)idx->opt.v[RL_OPT_PP_XCD_PASSES]));
         else
             RL_TRY(launch_maxsim_gemm(approx_image(idx), idx->n_rows, idx->dim, idx->qplanes.p, n_queries, b, n_q, nq, idx->row_to_chunk, idx->offsets,
                                       idx->ends.as<uint32_t>(), d_o + (int64_t)b * ld, ld, idx->n_cu, s, approx_scale(idx), true, nullptr, true));
@@ -2992,7 +2994,7 @@ int rl_time_kernel(rl_index* idx, int kind, const float* q_dev, int32_t nq, int3
     for (int i = 0; i < iters && st == RL_OK; ++i) {
         if (kind == 7) st = launch_maxsim_pp(approx_image(idx), idx->n_rows, idx->dim, idx->qplanes.p, pp_n, 0, pp_n,
                                              pp_vec, idx->row_to_chunk, idx->offsets, idx->ends.as<uint32_t>(), idx->scores.as<float>(), ldc,
-                                             idx->n_cu, s, approx_scale(idx), nullptr, (int)idx->opt.v[RL_OPT_PP_SCHEDULE]);
+                                             idx->n_cu, s, approx_scale(idx), nullptr, (int)idx->opt.v[RL_OPT_PP_SCHEDULE], (int)idx->opt.v[RL_OPT_PP_XCD_PASSES]);
         else if (kind == 3) st = gemm_pass(idx, nq / GEMM_PASS_QUERIES, GEMM_PASS_QUERIES, 0, GEMM_PASS_QUERIES, idx->scores.as<float>(), ldc, s);
         else if (kind == 8) {
             const auto& r = idx->replay;

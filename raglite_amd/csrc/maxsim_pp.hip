@@ -75,14 +75,26 @@ __device__ __forceinline__ int64_t pp_uniform_i64(int64_t v) {
 }
 
 // One 1-KiB piece HBM -> LDS: lane i copies 16 B from src + 16 i to lds + 16 i.  Invisible to the compiler's vmcnt bookkeeping
-// (asynchronous; certified by the explicit waits below).  MODE 0 (NT = false): no cache hint -- under the co-scheduled order
-// (pp_schedule.h) the workgroups of the other passes over the same rows, on the same XCD, read the piece again shortly after, and `nt`
-// or `sc1` let it leave the L2 sooner: both measured slower.  MODES 1 and 2 keep `nt` (streamed once per grid row).
+// (asynchronous; certified by the explicit waits below).  MODE 0 (NT = false): no cache hint under any workgroup order (pp_schedule.h).
+// Under the co-scheduled order the workgroups of the other passes over the same rows, on the same XCD, read the piece again shortly after,
+// and `nt` or `sc1` let it leave the L2 sooner; under the XCD-affine orders no hint is fastest or level with `sc1` at 2 and 1 passes per
+// XCD, and `sc1` gains 1.3 % at 4 -- less than a hint chosen at run time costs: a wave-uniform branch around this instruction in the K loop
+// cost the step 4-5 %.  MODES 1 and 2 keep `nt` (streamed once per grid row).
+// Experiment builds: `hint` (PP_HINT_*, from RAGLITE_PP_HINT) overrides MODE 0's choice, for timing the hints against each other.
+enum { PP_HINT_NONE = 0, PP_HINT_NT = 1, PP_HINT_SC1 = 2 };
 template <bool NT>
-__device__ __forceinline__ void pp_dma(uint32_t lds, const char* src, uint32_t lane16) {
+__device__ __forceinline__ void pp_dma(uint32_t lds, const char* src, uint32_t lane16, int hint) {
     const uint32_t l = __builtin_amdgcn_readfirstlane(lds);
     const char* const p = reinterpret_cast<const char*>(pp_uniform_i64(reinterpret_cast<int64_t>(src)));
+#ifdef RAGLITE_EXPERIMENTS
+    if (!NT && hint == PP_HINT_SC1) {
+        asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2 sc1" ::"s"(l), "v"(lane16), "s"(p) : "memory", "m0");
+        return;
+    }
+    if (NT || hint == PP_HINT_NT)
+#else
     if constexpr (NT)
+#endif
         asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2 nt" ::"s"(l), "v"(lane16), "s"(p) : "memory", "m0");
     else
         asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2" ::"s"(l), "v"(lane16), "s"(p) : "memory", "m0");
@@ -113,7 +125,8 @@ __device__ __forceinline__ h16x8 pp_h(const f32x4& v) {
 }
 }  // namespace
 
-// MODE 2 arguments (see the header comment).  Queries come in groups of 32 (n_q = groups); a query tile is 16 groups.
+// MODE 2 arguments (see the header comment).  Queries come in groups of 32 (n_q = groups); a query tile is 16 groups.  The last two
+// fields are MODE 0's: its workgroup order reaches the kernel as an argument, so that every order runs the same kernel.
 struct PpRows {
     const float* tau;                     // [B] threshold on the similarity of query q (row_threshold_kernel: k-th of the sample - window)
     const float* q_unscale;               // [B] 2^(ex - 14) per query
@@ -127,6 +140,9 @@ struct PpRows {
     // MODE 1 (the SAMPLE pass of the fused top-k): scores of every `stride`-th 256-row tile, S[q * ld_s + 256 j + r] = similarity of query q with
     // row 256 stride j + r (rows past the corpus: -inf); tile_count = 2 x the sampled 256-row tiles (a launch tile has 128 rows)
     float* S; int64_t ld_s; int32_t stride;
+    // MODE 0, 1-D grid: passes that share an XCD at a time (RL_OPT_PP_XCD_PASSES; pp_schedule_affine); experiment builds: the corpus
+    // DMAs' PP_HINT_*
+    int32_t xcd_passes, dma_hint;
 };
 
 // DBG: timing skeletons (experiment builds only, -DRAGLITE_EXPERIMENTS + RAGLITE_PP_DBG / RAGLITE_PP_ROWS_DBG; WRONG results):
@@ -143,14 +159,16 @@ __global__ __launch_bounds__(512, 2) void maxsim_pp_kernel(const char* __restric
     if (run_if && __builtin_amdgcn_readfirstlane((int)*run_if) == 0) return;  // whole grid: a guarded launch that is not needed
     const int lane = threadIdx.x & 63;
     const int wv = wave_id();
-    // MODE 0: row range b of G and pass qt of this workgroup -- pp_schedule.h: blockIdx itself, or the co-scheduled order of a 1-D grid
+    // MODE 0: row range b of G and pass qt of this workgroup -- pp_schedule.h: blockIdx itself, or the co-scheduled / XCD-affine order of a 1-D grid
     int64_t G = gridDim.x, b = blockIdx.x;
     int qt = (int)blockIdx.y;
     if constexpr (!GROUPS) {
-        const PpSlot m = pp_schedule((int32_t)blockIdx.x, (int32_t)blockIdx.y, (int32_t)gridDim.x, (int32_t)gridDim.y, (n_q + PP_QPP - 1) / PP_QPP);
-        G = m.ranges;
-        b = m.range;
-        qt = m.pass;
+        const int32_t passes = (n_q + PP_QPP - 1) / PP_QPP;
+        const PpSlot m = gridDim.y > 1 ? pp_schedule((int32_t)blockIdx.x, (int32_t)blockIdx.y, (int32_t)gridDim.x, (int32_t)gridDim.y, passes)
+                                       : pp_schedule_affine((int32_t)blockIdx.x, (int32_t)gridDim.x, passes, rs.xcd_passes);
+        G = __builtin_amdgcn_readfirstlane(m.ranges);  // (uniform by construction; the divisions above leave them in vector registers)
+        b = __builtin_amdgcn_readfirstlane(m.range);
+        qt = __builtin_amdgcn_readfirstlane(m.pass);
     }
     // MODE 0: chunk-aligned row range of this workgroup (as in maxsim_gemm.hip): first chunk boundary at or after n_rows * b / G.
     auto boundary = [&](int64_t t) -> int64_t {
@@ -217,6 +235,7 @@ __global__ __launch_bounds__(512, 2) void maxsim_pp_kernel(const char* __restric
     };
     // ---- feeder duty: every wave fetches corpus block wv of slab g + PP_LC during slab g ------------------------------------------------
     int fc_s = 0, fc_r = 0, fc_slot = 0;  // K slab and tile of the NEXT fetch, its ring slot
+    const int dma_hint = GROUPS ? 0 : rs.dma_hint;  // (MODE 0; a kernel argument: wave-uniform)
     const int32_t blk_org = (org >> 4) + wv;
     const int64_t slab_bytes = (int64_t)nslab * 1024;
     auto issue_c = [&]() __attribute__((always_inline)) {
@@ -225,7 +244,7 @@ __global__ __launch_bounds__(512, 2) void maxsim_pp_kernel(const char* __restric
             int32_t blk = SCORES ? tile_blk(t) + wv : blk_org + t * PP_NBLK;
             blk = blk < last_blk ? blk : last_blk;  // past the image: harmless re-read of the last block, never emitted
             const char* src = planes + pp_uniform_i64((int64_t)blk * slab_bytes + (int64_t)fc_s * 1024);
-            pp_dma<GROUPS>(lds_base + (uint32_t)(fc_slot * PP_CSLOT + wv * 1024), src, lane16);
+            pp_dma<GROUPS>(lds_base + (uint32_t)(fc_slot * PP_CSLOT + wv * 1024), src, lane16, dma_hint);
         }
         if (++fc_s == nslab) { fc_s = 0; ++fc_r; }
         fc_slot = fc_slot + 1 == PP_DC ? 0 : fc_slot + 1;
@@ -781,7 +800,7 @@ __global__ __launch_bounds__(512, 2) void maxsim_pp_kernel(const char* __restric
 // Sixteen queries per pass over the image; n_q > 16: ceil(n_q / 16) passes in ONE launch (grid rows).
 int launch_maxsim_pp(const void* image, int64_t n_rows, int32_t dim, const void* qbuf, int32_t n_queries, int32_t first, int32_t n_q,
                      int32_t nq, const int32_t* row_to_chunk, const int64_t* chunk_offsets, const uint32_t* ends_bits, float* out,
-                     int64_t out_stride, int n_cu, hipStream_t s, float split_scale, const uint32_t* run_if, int schedule) {
+                     int64_t out_stride, int n_cu, hipStream_t s, float split_scale, const uint32_t* run_if, int schedule, int xcd_passes) {
     if (nq < 1 || nq > 32 || n_q < 1 || n_q > PP_QPP * 4096 || n_rows < 1 || first < 0 || first + n_q > n_queries) return RL_ERR_UNSUPPORTED;
     if (dim % 32 || dim < 256 || !(split_scale > 0.f) || !image || !ends_bits) return RL_ERR_UNSUPPORTED;
     const int32_t nslab = dim / 32;
@@ -789,13 +808,19 @@ int launch_maxsim_pp(const void* image, int64_t n_rows, int32_t dim, const void*
     const float* qmeta = reinterpret_cast<const float*>(static_cast<const char*>(qbuf) + (size_t)n_queries * dim * 128) + 2 * (size_t)first;
     const int64_t tiles = (n_rows + PP_RT - 1) / PP_RT;
     const int64_t gx = std::max<int64_t>(1, std::min<int64_t>(n_cu > 0 ? n_cu : 256, tiles)), passes = (n_q + PP_QPP - 1) / PP_QPP;
-    // schedule 1: the passes over one row range side by side on one XCD (pp_schedule.h); 0: pass-major, grid row = pass
+    // schedule 1: a 1-D grid in the co-scheduled order (xcd_passes = 8: the passes over one row range side by side on one XCD) or the
+    // XCD-affine order (4, 2, 1: that many passes per XCD for the whole launch) of pp_schedule.h; 0: pass-major, grid row = pass
     const dim3 grid = schedule == 1 ? dim3((unsigned)(gx * passes)) : dim3((unsigned)gx, (unsigned)passes), blk(512);
+    PpRows rs{};
+    rs.xcd_passes = schedule == 1 ? xcd_passes : 8;
 #define RL_PP_LAUNCH(DBG_)                                                                                                                 \
     hipLaunchKernelGGL((maxsim_pp_kernel<DBG_, 0, false>), grid, blk, 0, s, static_cast<const char*>(image), n_rows, nslab, qfrag, qmeta, n_q, row_to_chunk, \
-                       chunk_offsets, ends_bits, out, out_stride, 1.0f / split_scale, run_if, PpRows{})
+                       chunk_offsets, ends_bits, out, out_stride, 1.0f / split_scale, run_if, rs)
 #ifdef RAGLITE_EXPERIMENTS
-    // Experiment builds only (libraglite_hip_exp.so, scripts/gpu_calls/): timing skeletons that skip parts of the kernel -- WRONG results.
+    // Experiment builds only (libraglite_hip_exp.so, scripts/gpu_calls/): timing skeletons that skip parts of the kernel -- WRONG results;
+    // RAGLITE_PP_HINT = 0 / 1 / 2 (none / nt / sc1), read at every launch, sets the corpus DMAs' cache hint (same results).
+    const int force_hint = std::getenv("RAGLITE_PP_HINT") ? std::atoi(std::getenv("RAGLITE_PP_HINT")) : -1;
+    if (force_hint >= PP_HINT_NONE && force_hint <= PP_HINT_SC1) rs.dma_hint = force_hint;
     static const int dbg = std::getenv("RAGLITE_PP_DBG") ? std::atoi(std::getenv("RAGLITE_PP_DBG")) : 0;
     if (dbg == 2) RL_PP_LAUNCH(2);
     else if (dbg == 128) RL_PP_LAUNCH(128);
