@@ -589,6 +589,37 @@ int rl_hybrid_search_per_query(rl_index* index, rl_keyword_index* kw, const floa
                                const int64_t* rank_limits, const double* weights, int32_t rrf_k, int32_t k,
                                double* out_scores, int32_t* out_chunks, int32_t* out_counts, int mem, void* stream);
 
+/* ---- batched search-and-rerank (src/raglite/_search.py:364-414, `search_and_rerank_chunks` with a MaxSim reranker) ----------
+ * rl_rerank_order orders each query's reranked candidates as raglite_amd's MaxSimRanker.rank does on the host
+ * (np.lexsort((arange, -key)), key = where(isnan(s), -inf, s)):
+ *   scores      f32   [n_queries x n_cand], e.g. rl_maxsim_rerank's output
+ *   candidates  int32 [n_queries x n_cand]; an entry < 0 is padding (anywhere in the list): it comes after every real
+ *               candidate and is not counted.  1 <= k <= n_cand <= 4096 (one workgroup's LDS, as rl_rrf_fuse's limit).
+ * The real candidates rank by score descending, NaN as -inf, -0.0 equal to +0.0, equal keys by position (stable).
+ * out_scores f32 / out_chunks int32 / out_pos int32 [n_queries x k]: the input score's own bits (a NaN stays that NaN,
+ * -0.0 stays -0.0), the candidate, and its position in the input list (what the reference reads as `result.doc_id`);
+ * unfilled slots (-inf, -1, -1); out_counts [n_queries] the real candidates among the first k.  Sizes and `mem` are
+ * checked before any HIP call (RL_ERR_INVALID); n_queries == 0 returns RL_OK.  Host or device pointers per `mem`.
+ *
+ * rl_search_rerank_per_query is the whole pipeline for n_queries queries on one stream, nothing read back in between:
+ *   1. rl_hybrid_search_per_query (the same arguments, checks, locks and routes) with k = n_cand <= (kw ? 2 : 1) * n_each:
+ *      the fused candidates [n_queries x n_cand] stay in scratch the index owns.  kw == NULL: the vector list alone,
+ *      which for distinct chunks is rl_search_chunks_per_query's list;
+ *   2. rl_maxsim_rerank of those candidates against query_vecs f32 [n_queries x nq x dim] (its shapes: on an fp16-stored
+ *      index nq <= 32 and dim % 16 == 0, else RL_ERR_UNSUPPORTED); padding, tombstoned and out-of-range candidates
+ *      score -inf;
+ *   3. rl_rerank_order, the first k <= n_cand: out_scores f32 (the MaxSim scores) / out_chunks int32 [n_queries x k],
+ *      best first, out_counts [n_queries].
+ * nq >= 1 and 1 <= k <= n_cand <= 4096 are checked before the index is looked at. */
+int rl_rerank_order(const float* scores, const int32_t* candidates, int32_t n_queries, int32_t n_cand, int32_t k,
+                    float* out_scores, int32_t* out_chunks, int32_t* out_pos, int32_t* out_counts, int mem, void* stream);
+int rl_search_rerank_per_query(rl_index* index, rl_keyword_index* kw, const float* queries, int32_t n_queries,
+                               int32_t num_hits, int32_t n_each, const int64_t* q_off, const int32_t* q_terms,
+                               const uint32_t* chunk_filters, int32_t n_filters, const int32_t* query_filter,
+                               const int64_t* rank_limits, const double* weights, int32_t rrf_k, int32_t n_cand,
+                               const float* query_vecs, int32_t nq, int32_t k, float* out_scores, int32_t* out_chunks,
+                               int32_t* out_counts, int mem, void* stream);
+
 /* ---- device half of update_query_adapter ----------------------------------
  * src/raglite/_query_adapter.py:153-205 fits the query adapter from evals: per eval a vector search
  * (rl_search_chunks, batched over all evals), then for every retrieved chunk the row

@@ -22,6 +22,7 @@ from raglite_amd._ops import (
     adapter_apply,
     merge_topk,
     pack_bits,
+    rerank_order,
     rrf_fuse,
     shard_hybrid_fuse,
     get_default_option,
@@ -43,7 +44,9 @@ from raglite_amd._search import (
     attach_index,
     detach_index,
     rerank_chunks,
+    rerank_chunks_batch,
     search_and_rerank_chunks,
+    search_and_rerank_chunks_batch,
     select_reranker,
     set_language_detector,
     vector_search,
@@ -77,6 +80,9 @@ __all__ = [
     "CrossEncoderShape",
     "pack_bits",
     "rrf_fuse",
+    "rerank_order",
+    "rerank_chunks_batch",
+    "search_and_rerank_chunks_batch",
     "shard_hybrid_fuse",
     "Communicator", "DeviceIndex", "GpuIndex", "GpuVectorSearch", "HotPathConfig", "MaxSimRanker", "ShardedIndex",
     "adapter_apply", "attach_index", "detach_index", "embed_strings", "embed_strings_with_late_chunking",

@@ -126,6 +126,10 @@ _SIGNATURES = {
                                     c_int, c_void_p],
     "rl_hybrid_search_per_query": [c_void_p, c_void_p, c_void_p, c_i32, c_i32, c_i32, c_void_p, c_void_p, c_void_p, c_i32, c_void_p,
                                    c_void_p, c_void_p, c_i32, c_i32, c_void_p, c_void_p, c_void_p, c_int, c_void_p],
+    "rl_rerank_order": [c_void_p, c_void_p, c_i32, c_i32, c_i32, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p],
+    "rl_search_rerank_per_query": [c_void_p, c_void_p, c_void_p, c_i32, c_i32, c_i32, c_void_p, c_void_p, c_void_p, c_i32, c_void_p,
+                                   c_void_p, c_void_p, c_i32, c_i32, c_void_p, c_i32, c_i32, c_void_p, c_void_p, c_void_p, c_int,
+                                   c_void_p],
 }
 COMM_ID_BYTES = 128
 _RESTYPES = {"rl_last_error": c_char_p}

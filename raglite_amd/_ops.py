@@ -225,6 +225,33 @@ def rrf_fuse(lists, weights, *, rrf_k: int = 60, k: int):
     return o_s, o_i, o_n
 
 
+RERANK_MAX_ENTRIES = 4096  # candidates per query that rl_rerank_order sorts (one workgroup's LDS)
+
+
+def rerank_order(scores, candidates, k: int):
+    """`rl_rerank_order`: `MaxSimRanker.rank`'s order for a batch.  `scores` (B, n_cand) float32 and `candidates` (B, n_cand) int32, an
+    entry < 0 being padding; per query the real candidates by score descending, NaN as -inf, -0.0 equal to +0.0, equal scores by
+    position, padding last.  Returns (scores (B, k) float32 -- the input's bits --, candidates (B, k) int32, positions (B, k) int32 in
+    the input list, counts (B,) int32); unfilled slots are (-inf, -1, -1).  1 <= k <= n_cand <= 4096."""
+    a = _Args()
+    p_s = a.inp(scores, np.float32)
+    sv = a.keep[-1]
+    p_c = a.inp(candidates, np.int32)
+    cv = a.keep[-1]
+    if sv.ndim != 2 or cv.ndim != 2 or tuple(sv.shape) != tuple(cv.shape):
+        raise ValueError("scores and candidates must both be (n_queries, n_cand)")
+    B, n_cand = int(sv.shape[0]), int(sv.shape[1])
+    if not 1 <= int(k) <= n_cand <= RERANK_MAX_ENTRIES:
+        raise ValueError(f"rerank_order: need 1 <= k <= n_cand <= {RERANK_MAX_ENTRIES} (k={k}, n_cand={n_cand})")
+    o_s, p_os = a.out((B, int(k)), np.float32)
+    o_c, p_oc = a.out((B, int(k)), np.int32)
+    o_p, p_op = a.out((B, int(k)), np.int32)
+    o_n, p_on = a.out((B,), np.int32)
+    a.ensure_device()
+    check(lib().rl_rerank_order(p_s, p_c, B, n_cand, int(k), p_os, p_oc, p_op, p_on, a.mem, a.stream))
+    return o_s, o_c, o_p, o_n
+
+
 def shard_hybrid_fuse(gathered, *, num_hits: int, n_each: int, keywords: bool, weights, rrf_k: int = 60, k: int):
     """`rl_shard_hybrid_fuse`: the step after the one all-gather of a sharded hybrid batch.  `gathered`: (world, B, W) int32, what every
     rank packed -- num_hits row records (score bits, global row, global chunk), then with `keywords` n_each keyword records (score bits,
@@ -689,6 +716,54 @@ class DeviceIndex:
         check(fn(self._handle, None if keyword is None else keyword._handle, p_q, B, int(num_hits), int(n_each), p_off, p_terms, *args,
                  w.ctypes.data, int(rrf_k), int(k), p_s, p_c, p_n, a.mem, a.stream))
         return (o_s[0], o_c[0], o_n[0]) if single else (o_s, o_c, o_n)
+
+    def search_rerank(self, queries, num_hits: int, n_each: int, n_cand: int, query_vecs, k: int, *,
+                      keyword: "KeywordIndex | None" = None, query_term_ids=None, weights=(0.75, 0.25), rrf_k: int = 60, chunk_filter=None,
+                      rank_limit=None, query_filters=None):
+        """`rl_search_rerank_per_query`: `hybrid_search(queries, num_hits, n_each, k=n_cand, ...)`, then `maxsim_rerank` of each query's
+        fused candidates against `query_vecs` (B, nq, dim), then `rerank_order`'s first k, all on one stream with nothing read back in
+        between.  Returns (MaxSim scores (B, k) float32, chunk ordinals (B, k) int32 best first, counts (B,) int32).  Without
+        `keyword` the candidates are the vector search's list alone.  The filter arguments are `hybrid_search`'s."""
+        a = _Args()
+        p_q, B, single = self._queries(a, queries)
+        if single:
+            raise ValueError("queries must be (n_queries, dim)")
+        p_v = a.inp(query_vecs, np.float32)
+        qv = a.keep[-1]
+        if qv.ndim != 3 or int(qv.shape[0]) != B or int(qv.shape[2]) != self.dim:
+            raise ValueError("query_vecs must be (n_queries, nq, dim)")
+        nq = int(qv.shape[1])
+        o_s, p_s = a.out((B, int(k)), np.float32)
+        o_c, p_c = a.out((B, int(k)), np.int32)
+        o_n, p_n = a.out((B,), np.int32)
+        if query_filters is None and (rank_limit is None or np.ndim(rank_limit) == 0):  # (one filter for the batch: every query maps to it)
+            query_filters = None if chunk_filter is None else [chunk_filter] * B
+            chunk_filter = None
+            if query_filters is None and rank_limit:
+                query_filters = [None] * B
+        if query_filters is None:
+            args = (None, 0, None, None)
+        else:
+            _, args = self._per_query(a, B, chunk_filter, query_filters, rank_limit)
+        w = np.ascontiguousarray(np.asarray(weights, dtype=np.float64).ravel()[: 2 if keyword is not None else 1])
+        p_off = p_terms = None
+        if keyword is not None:
+            if query_term_ids is None or len(query_term_ids) != B:
+                raise ValueError("one sequence of term ids per query is required")
+            q_off, q_terms = _term_csr(query_term_ids)
+            if a.mem == MEM_DEVICE:
+                torch = _torch()
+                q_off = torch.from_numpy(q_off).to(a.device)
+                q_terms = torch.from_numpy(q_terms if q_terms.size else np.zeros(1, np.int32)).to(a.device)
+                p_off, p_terms = q_off.data_ptr(), q_terms.data_ptr()
+            else:
+                p_off, p_terms = q_off.ctypes.data, q_terms.ctypes.data
+            a.keep += [q_off, q_terms]
+        self._prep(a)
+        check(lib().rl_search_rerank_per_query(self._handle, None if keyword is None else keyword._handle, p_q, B, int(num_hits), int(n_each),
+                                               p_off, p_terms, *args, w.ctypes.data, int(rrf_k), int(n_cand), p_v, nq, int(k), p_s, p_c,
+                                               p_n, a.mem, a.stream))
+        return o_s, o_c, o_n
 
     # -- a9 ----------------------------------------------------------------------------------------
     def maxsim_scores(self, query_vecs):

@@ -10,6 +10,9 @@
                                                             (the batched searches take one metadata filter per query)
     rerank_chunks(query, chunk_ids, *, config=None) -> list[chunk]        (`_search.py:364-397`)
     search_and_rerank_chunks(...)                                         (`_search.py:400-414`)
+    search_and_rerank_chunks_batch(queries, ...) -> list of search_and_rerank_chunks's results: search, fusion, MaxSim rerank and
+                                                    ordering of the whole batch in one device call
+    rerank_chunks_batch(queries, chunk_ids_per_query, ...) -> the MaxSim rerank of given lists, one launch per distinct nq
     GpuVectorSearch   -- a `BasicSearchMethod` (`_typing.py:35-43`) for `RAGLiteConfig.search_method`
     MaxSimRanker      -- a duck-typed `rerankers.BaseRanker` for `RAGLiteConfig.reranker`
                          (`.rank(query=, docs=)` -> `.results[*].doc_id`, `_search.py:394-396`)
@@ -568,6 +571,19 @@ def _collect(gi: GpuIndex, out: list, active: Sequence[int], scores, chunks, cou
     return out
 
 
+def _plan_vector_batch(gi: GpuIndex, cfg: Any, queries: list, num_results: int, oversample: int, metadata_filter, query_vectors):
+    """The host decisions of a batch of vector searches (B >= 1), in vector_search's order: (query matrix, num_hits, filter plan, the
+    queries that search the device -- the others return ([], [])); raises where the loop would raise."""
+    B = len(queries)
+    filters = _batch_filters(metadata_filter, B)
+    _self_query(cfg, queries)
+    Q = _embed_one_by_one(queries, query_vectors, cfg, gi)
+    num_hits = round(oversample * cfg.chunk_max_size / DEFAULT_CHUNK_MAX_SIZE) * max(num_results, 10)  # (`_search.py:66-67`)
+    plan = plan_filters(filters, gi.metadata, _rows_per_chunk(gi))
+    active = [b for b in range(B) if _vector_searches(gi, filters[b], plan.of(b)[0], num_hits, num_results)]
+    return Q, num_hits, plan, active
+
+
 def vector_search_batch(queries: Sequence[str | np.ndarray], *, num_results: int = 3, oversample: int = VECTOR_SEARCH_OVERSAMPLE,
                         metadata_filter=None, config: Any | None = None, index: GpuIndex | None = None,
                         query_vectors=None) -> list[tuple[list[ChunkId], list[float]]]:
@@ -581,12 +597,7 @@ def vector_search_batch(queries: Sequence[str | np.ndarray], *, num_results: int
     B = len(queries)
     if B == 0:
         return []
-    filters = _batch_filters(metadata_filter, B)
-    _self_query(cfg, queries)
-    Q = _embed_one_by_one(queries, query_vectors, cfg, gi)
-    num_hits = round(oversample * cfg.chunk_max_size / DEFAULT_CHUNK_MAX_SIZE) * max(num_results, 10)  # (`_search.py:66-67`)
-    plan = plan_filters(filters, gi.metadata, _rows_per_chunk(gi))
-    active = [b for b in range(B) if _vector_searches(gi, filters[b], plan.of(b)[0], num_hits, num_results)]
+    Q, num_hits, plan, active = _plan_vector_batch(gi, cfg, queries, num_results, oversample, metadata_filter, query_vectors)
     out: list = [([], []) for _ in range(B)]
     if active:
         qf, lim = _device_filters(plan, active)
@@ -618,6 +629,46 @@ def keyword_search_batch(queries: Sequence[str], *, num_results: int = 3, metada
     return out
 
 
+@dataclass
+class HybridPlan:
+    """The host decisions of a batch of hybrid searches: what each half is asked for (`n_each`, `num_hits`), which halves run for at
+    least one query (`vector`, `keyword`; R of them), the fused list's length `k`, the query matrix, term ids and filter plan."""
+
+    Q: np.ndarray
+    n_each: int
+    num_hits: int
+    plan: FilterPlan
+    term_ids: list | None
+    vector: bool
+    keyword: bool
+    R: int
+    k: int
+
+
+def _plan_hybrid_batch(gi: GpuIndex, cfg: Any, queries: list, num_results: int, oversample: int, metadata_filter,
+                       query_vectors) -> HybridPlan:
+    """hybrid_search's decisions for every query of a batch (B >= 1), in its order; raises where the loop would raise."""
+    B = len(queries)
+    if getattr(cfg, "self_query", False):
+        raise NotImplementedError("self_query needs the LLM stack, which is outside this package")
+    filters = _batch_filters(metadata_filter, B)
+    n_each = oversample * num_results  # what hybrid_search asks of each half
+    Q = _embed_one_by_one(queries, query_vectors, cfg, gi)
+    num_hits = round(VECTOR_SEARCH_OVERSAMPLE * cfg.chunk_max_size / DEFAULT_CHUNK_MAX_SIZE) * max(n_each, 10)
+    plan = plan_filters(filters, gi.metadata, _rows_per_chunk(gi))
+    # (hybrid_search runs the keyword half for query strings only; a query given as a vector has none)
+    term_ids = [gi.keyword_query_ids(q) if isinstance(q, str) else [] for q in queries] if gi.has_keywords else None
+    vector = keyword = False
+    for b in range(B):  # hybrid_search's decisions for each query, in its order: its vector half, then its keyword half
+        allowed = plan.of(b)[0]
+        vector = _vector_searches(gi, filters[b], allowed, num_hits, n_each) or vector
+        if gi.has_keywords and isinstance(queries[b], str):
+            keyword = _keyword_searches(gi, filters[b], allowed, term_ids[b], n_each) or keyword
+    R = int(vector) + int(keyword)
+    k = R * n_each if num_results < 1 else min(num_results, R * n_each)  # (hybrid_search slices the fused list [:num_results])
+    return HybridPlan(Q, n_each, num_hits, plan, term_ids, vector, keyword, R, k)
+
+
 def hybrid_search_batch(queries: Sequence[str], *, num_results: int = 3, oversample: int = 2,
                         vector_search_weight: float = 0.75, keyword_search_weight: float = 0.25,
                         metadata_filter=None, config: Any | None = None, index: GpuIndex | None = None,
@@ -635,33 +686,17 @@ def hybrid_search_batch(queries: Sequence[str], *, num_results: int = 3, oversam
     B = len(queries)
     if B == 0:
         return []
-    if getattr(cfg, "self_query", False):
-        raise NotImplementedError("self_query needs the LLM stack, which is outside this package")
-    filters = _batch_filters(metadata_filter, B)
-    n_each = oversample * num_results  # what hybrid_search asks of each half
-    Q = _embed_one_by_one(queries, query_vectors, cfg, gi)
-    num_hits = round(VECTOR_SEARCH_OVERSAMPLE * cfg.chunk_max_size / DEFAULT_CHUNK_MAX_SIZE) * max(n_each, 10)
-    plan = plan_filters(filters, gi.metadata, _rows_per_chunk(gi))
-    # (hybrid_search runs the keyword half for query strings only; a query given as a vector has none)
-    term_ids = [gi.keyword_query_ids(q) if isinstance(q, str) else [] for q in queries] if gi.has_keywords else None
-    vector = keyword = False
-    for b in range(B):  # hybrid_search's decisions for each query, in its order: its vector half, then its keyword half
-        allowed = plan.of(b)[0]
-        vector = _vector_searches(gi, filters[b], allowed, num_hits, n_each) or vector
-        if gi.has_keywords and isinstance(queries[b], str):
-            keyword = _keyword_searches(gi, filters[b], allowed, term_ids[b], n_each) or keyword
-    if not vector and not keyword:
+    hp = _plan_hybrid_batch(gi, cfg, queries, num_results, oversample, metadata_filter, query_vectors)
+    if hp.R == 0:
         return [([], []) for _ in range(B)]
-    R = int(vector) + int(keyword)
-    k = R * n_each if num_results < 1 else min(num_results, R * n_each)  # (hybrid_search slices the fused list [:num_results])
-    qf, lim = _device_filters(plan, range(B))
-    if vector:
-        scores, chunks, counts = gi.index.hybrid_search(Q, num_hits, n_each, k, keyword=gi.keyword if keyword else None,
-                                                        query_term_ids=term_ids, weights=(vector_search_weight, keyword_search_weight),
+    qf, lim = _device_filters(hp.plan, range(B))
+    if hp.vector:
+        scores, chunks, counts = gi.index.hybrid_search(hp.Q, hp.num_hits, hp.n_each, hp.k, keyword=gi.keyword if hp.keyword else None,
+                                                        query_term_ids=hp.term_ids, weights=(vector_search_weight, keyword_search_weight),
                                                         rrf_k=RRF_K, query_filters=qf, rank_limit=lim)
     else:  # no vector results for any query (an empty index, num_hits < 1): RRF of the keyword list alone is the same fusion
-        _, kw_chunks, _ = gi.keyword.search(term_ids, n_each, query_filters=qf)
-        scores, chunks, counts = _ops.rrf_fuse(kw_chunks[None], [keyword_search_weight], rrf_k=RRF_K, k=k)
+        _, kw_chunks, _ = gi.keyword.search(hp.term_ids, hp.n_each, query_filters=qf)
+        scores, chunks, counts = _ops.rrf_fuse(kw_chunks[None], [keyword_search_weight], rrf_k=RRF_K, k=hp.k)
     out = []
     for b in range(B):
         n = int(counts[b])
@@ -688,6 +723,14 @@ class RankedResults:
 
     def top_k(self, k: int) -> list[Result]:
         return self.results[:k]
+
+
+def _groups_by_nq(vecs: Sequence[np.ndarray]) -> list[list[int]]:
+    """The queries grouped by their number of token vectors, each group in query order (ColBERT's fixed query length gives one)."""
+    groups: dict[int, list[int]] = {}
+    for b, v in enumerate(vecs):
+        groups.setdefault(int(v.shape[0]), []).append(b)
+    return list(groups.values())
 
 
 class MaxSimRanker:
@@ -723,6 +766,58 @@ class MaxSimRanker:
         qv = qv.reshape(1, *qv.shape) if qv.ndim == 2 else qv.reshape(1, 1, -1)
         cand = np.asarray(ordinals, dtype=np.int32).reshape(1, -1)
         return np.asarray(self.index.index.maxsim_rerank(qv, cand))[0]
+
+    def _token_vectors(self, queries: Sequence[Any], query_token_vectors=None) -> list[np.ndarray]:
+        """Each query's (nq, dim) float32 token vectors: `query_token_vectors[b]` when given, else `query_encoder(queries[b])`, one
+        query at a time (the encoder is host code)."""
+        if query_token_vectors is not None and len(query_token_vectors) != len(queries):
+            raise ValueError("query_token_vectors must have one (nq, dim) matrix per query")
+        out = []
+        for b, q in enumerate(queries):
+            v = query_token_vectors[b] if query_token_vectors is not None else self.query_encoder(q)
+            if _ops._is_torch(v):  # noqa: SLF001
+                v = v.detach().cpu().numpy()
+            v = np.asarray(v, dtype=np.float32)
+            out.append(v if v.ndim == 2 else v.reshape(1, -1))
+        return out
+
+    def _score_and_order(self, vecs: Sequence[np.ndarray], ordinals: Sequence[Sequence[int]]):
+        """Per query (its candidates' scores in list order, their positions best first): one `rl_maxsim_rerank` and one
+        `rl_rerank_order` per distinct nq.  Short lists are padded with -1; short queries are NOT padded with zero vectors (that
+        could change the summation order and so the score bits)."""
+        lists = [np.asarray(o, dtype=np.int32).ravel() for o in ordinals]
+        if len(lists) != len(vecs):
+            raise ValueError("one list of candidates per query is required")
+        out: list = [(np.zeros(0, np.float32), np.zeros(0, np.int32)) for _ in lists]
+        for group in _groups_by_nq(vecs):
+            n_cand = max(len(lists[b]) for b in group)
+            if n_cand == 0:
+                continue
+            if n_cand > _ops.RERANK_MAX_ENTRIES:
+                raise ValueError(f"MaxSimRanker: at most {_ops.RERANK_MAX_ENTRIES} candidates per query can be ordered on the device")
+            cand = np.full((len(group), n_cand), -1, dtype=np.int32)
+            for i, b in enumerate(group):
+                cand[i, : len(lists[b])] = lists[b]
+            scores = np.asarray(self.index.index.maxsim_rerank(np.stack([vecs[b] for b in group]), cand))
+            _, _, pos, counts = _ops.rerank_order(scores, cand, n_cand)
+            for i, b in enumerate(group):
+                out[b] = (scores[i, : len(lists[b])], pos[i, : int(counts[i])])
+        return out
+
+    def score_batch(self, queries: Sequence[str], ordinals: Sequence[Sequence[int]], *, query_token_vectors=None) -> list[np.ndarray]:
+        """`score(queries[b], ordinals[b])` for every b (ragged lists), one `rl_maxsim_rerank` per distinct nq."""
+        return [s for s, _ in self._score_and_order(self._token_vectors(queries, query_token_vectors), ordinals)]
+
+    def rank_batch(self, queries: Sequence[str], docs_per_query: Sequence[Sequence[Any]], *, query_token_vectors=None) -> list[RankedResults]:
+        """`rank(query=queries[b], docs=docs_per_query[b])` for every b: the same `RankedResults`, from one `rl_maxsim_rerank` and one
+        `rl_rerank_order` per distinct nq instead of one call and one host sort per query."""
+        queries, docs_per_query = list(queries), [list(d) for d in docs_per_query]
+        if len(queries) != len(docs_per_query):
+            raise ValueError("one list of docs per query is required")
+        ordinals = [[self.index.ordinal_of_doc(d if isinstance(d, str) else str(d)) for d in docs] for docs in docs_per_query]
+        ranked = self._score_and_order(self._token_vectors(queries, query_token_vectors), ordinals)
+        return [RankedResults([Result(doc_id=int(i), score=float(scores[i]), rank=r + 1, text=str(docs[i])) for r, i in enumerate(order)], q)
+                for q, docs, (scores, order) in zip(queries, docs_per_query, ranked)]
 
     def rank(self, query: str, docs: Sequence[Any], doc_ids: Sequence[int] | None = None, **_: Any) -> RankedResults:
         docs = list(docs)
@@ -815,3 +910,121 @@ def search_and_rerank_chunks(query: str, *, num_results: int = 8, oversample: in
     with a keyword side for the same pipeline on the device)."""
     chunk_ids, _ = search(query, num_results=oversample * num_results, metadata_filter=metadata_filter, config=config)
     return rerank_chunks(query, chunk_ids, config=config, chunk_lookup=chunk_lookup)[:num_results]
+
+
+def _device_ranker(cfg: Any, gi: GpuIndex) -> "MaxSimRanker | None":
+    """`cfg.reranker` when it is a MaxSimRanker over the searched index: the case the device pipeline covers."""
+    reranker = getattr(cfg, "reranker", None)
+    return reranker if isinstance(reranker, MaxSimRanker) and reranker.index is gi else None
+
+
+def rerank_chunks_batch(queries: Sequence[str], chunk_ids_per_query: Sequence[Sequence[ChunkId]], *, config: Any,
+                        index: GpuIndex | None = None, query_token_vectors=None) -> list[tuple[list[ChunkId], list[float]]]:
+    """MaxSim-rerank a batch of (ragged) chunk id lists: element b is (ids best first, their MaxSim scores), the order
+    `config.reranker.rank(queries[b], <those chunks' docs>)` gives.  `config.reranker` must be a `MaxSimRanker` over `index`; one
+    `rl_maxsim_rerank` and one `rl_rerank_order` per distinct query length.  `query_token_vectors`: one (nq, dim) matrix per query,
+    skips the ranker's query encoder."""
+    gi = index or _index_for(config)
+    ranker = _device_ranker(config, gi)
+    if ranker is None:
+        raise ValueError("rerank_chunks_batch needs config.reranker to be a MaxSimRanker over the index")
+    queries, id_lists = list(queries), [list(ids) for ids in chunk_ids_per_query]
+    if len(queries) != len(id_lists):
+        raise ValueError("one list of chunk ids per query is required")
+    ordinals = [[gi.ordinal_of(cid) for cid in ids] for ids in id_lists]
+    ranked = ranker._score_and_order(ranker._token_vectors(queries, query_token_vectors), ordinals)  # noqa: SLF001
+    return [([ids[i] for i in order.tolist()], [float(scores[i]) for i in order.tolist()]) for ids, (scores, order) in zip(id_lists, ranked)]
+
+
+_SEARCHES = {"hybrid": "hybrid", "vector": "vector", hybrid_search: "hybrid", vector_search: "vector"}
+
+
+def search_and_rerank_chunks_batch(queries: Sequence[str], *, num_results: int = 8, oversample: int = 4, search: Any = "hybrid",
+                                   config: Any | None = None, metadata_filter=None, index: GpuIndex | None = None, query_vectors=None,
+                                   query_token_vectors=None,
+                                   chunk_lookup: Callable[[Sequence[ChunkId]], list[Any]] | None = None) -> list[list[Any]]:
+    """`search_and_rerank_chunks` for a batch: element b is what `search_and_rerank_chunks(queries[b], search=hybrid_search |
+    vector_search, metadata_filter=<its filter>, ...)` returns with the same arguments -- the same chunks in the same order -- as
+    chunk ids, or as `chunk_lookup(ids)` per query when a lookup is given.  `search`: "hybrid" or "vector" (or those two functions).
+
+    With `config.reranker` a `MaxSimRanker` over the searched index, the searches, the RRF fusion, the MaxSim scoring of every query's
+    `oversample * num_results` candidates and their ordering run on one stream in one device call per distinct query length
+    (`rl_search_rerank_per_query`), nothing is read back in between, and the best `num_results` are read back once.  Query token
+    vectors come from the ranker's `query_encoder`, one query at a time, or from `query_token_vectors` (one (nq, dim) matrix per query).
+    Without a reranker the batched search's results are returned truncated.  Any other reranker (a dict by language, a cross-encoder)
+    is outside the device path: the batched search runs, then `rerank_chunks` per query.  `metadata_filter` and `query_vectors` as in
+    `hybrid_search_batch`.  Raises where the loop would raise for some element, with its message."""
+    cfg = config or HotPathConfig()
+    gi = index or _index_for(config)
+    queries = list(queries)
+    B = len(queries)
+    if search not in _SEARCHES:
+        raise ValueError("search must be 'hybrid' or 'vector'")
+    kind = _SEARCHES[search]
+    if B == 0:
+        return []
+    n_cand = oversample * num_results  # what search_and_rerank_chunks asks of its search
+    ranker = _device_ranker(cfg, gi)
+    found: list[list[ChunkId]]
+    if ranker is None:
+        batch = hybrid_search_batch if kind == "hybrid" else vector_search_batch
+        found = [ids for ids, _ in batch(queries, num_results=n_cand, metadata_filter=metadata_filter, config=cfg, index=gi,
+                                         query_vectors=query_vectors)]
+        if getattr(cfg, "reranker", None) and any(found):
+            return [rerank_chunks(q, ids, config=cfg, chunk_lookup=chunk_lookup)[:num_results] for q, ids in zip(queries, found)]
+    elif kind == "hybrid":
+        found = _hybrid_rerank_device(gi, cfg, ranker, queries, num_results, n_cand, metadata_filter, query_vectors, query_token_vectors)
+    else:
+        found = _vector_rerank_device(gi, cfg, ranker, queries, num_results, n_cand, metadata_filter, query_vectors, query_token_vectors)
+    found = [ids[:num_results] for ids in found]
+    return [chunk_lookup(ids) if chunk_lookup is not None and ids else ids for ids in found]
+
+
+def _ids_of(gi: GpuIndex, out: list, group: Sequence[int], chunks, counts) -> None:
+    for i, b in enumerate(group):
+        out[b] = [gi.chunk_ids[c] for c in chunks[i, : int(counts[i])].tolist()]
+
+
+def _hybrid_rerank_device(gi, cfg, ranker, queries, num_results, n_cand, metadata_filter, query_vectors, query_token_vectors) -> list:
+    """The device path of search_and_rerank_chunks_batch over hybrid_search: its host decisions are hybrid_search_batch's."""
+    B = len(queries)
+    hp = _plan_hybrid_batch(gi, cfg, queries, n_cand, 2, metadata_filter, query_vectors)  # (hybrid_search's own oversample: 2)
+    out: list = [[] for _ in range(B)]
+    if hp.R == 0:
+        return out
+    k = min(num_results, hp.k)
+    vecs = ranker._token_vectors(queries, query_token_vectors)  # noqa: SLF001
+    for group in _groups_by_nq(vecs):
+        qf, lim = _device_filters(hp.plan, group)
+        V = np.stack([vecs[b] for b in group])
+        terms = None if hp.term_ids is None else [hp.term_ids[b] for b in group]
+        if hp.vector:
+            _, chunks, counts = gi.index.search_rerank(hp.Q[group], hp.num_hits, hp.n_each, hp.k, V, k, keyword=gi.keyword if hp.keyword else None,
+                                                       query_term_ids=terms, weights=(0.75, 0.25), rrf_k=RRF_K, query_filters=qf,
+                                                       rank_limit=lim)
+        else:  # no vector results for any query: the keyword list alone, fused, scored and ordered by separate calls
+            _, kw_chunks, _ = gi.keyword.search(terms, hp.n_each, query_filters=qf)
+            _, fused, _ = _ops.rrf_fuse(kw_chunks[None], [0.25], rrf_k=RRF_K, k=hp.k)
+            _, chunks, _, counts = _ops.rerank_order(gi.index.maxsim_rerank(V, fused), fused, k)
+        _ids_of(gi, out, group, chunks, counts)
+    return out
+
+
+def _vector_rerank_device(gi, cfg, ranker, queries, num_results, n_cand, metadata_filter, query_vectors, query_token_vectors) -> list:
+    """The device path over vector_search: its host decisions are vector_search_batch's; the pipeline call without a keyword index
+    fuses the vector list alone, which keeps its order."""
+    B = len(queries)
+    Q, num_hits, plan, active = _plan_vector_batch(gi, cfg, queries, n_cand, VECTOR_SEARCH_OVERSAMPLE, metadata_filter, query_vectors)
+    out: list = [[] for _ in range(B)]
+    if not active:
+        return out
+    k = min(num_results, n_cand)
+    vecs = ranker._token_vectors([queries[b] for b in active],  # noqa: SLF001
+                                 None if query_token_vectors is None else [query_token_vectors[b] for b in active])
+    for group in _groups_by_nq(vecs):
+        members = [active[i] for i in group]
+        qf, lim = _device_filters(plan, members)
+        _, chunks, counts = gi.index.search_rerank(Q[members], num_hits, n_cand, n_cand, np.stack([vecs[i] for i in group]), k, weights=(1.0,),
+                                                   rrf_k=RRF_K, query_filters=qf, rank_limit=lim)
+        _ids_of(gi, out, members, chunks, counts)
+    return out

@@ -333,6 +333,7 @@ struct rl_index {
     rl::Pool pp_work;                     // ... on the sixteen-group tile: wave-private record logs, block norm ranges (maxsim_pp.hip MODE 2)
     rl::Pool rankbuf;                     // rank cut (order-first-then-filter): histogram levels + tie counts
     rl::Pool hybrid;                      // rl_hybrid_search: the ranked lists the fusion reads, their scores and counts
+    rl::Pool rerank;                      // rl_search_rerank_per_query: the fused candidates, their fused and MaxSim scores, positions
     // HI plane (round 2): fp16(e * split_scale) rounded to nearest (toward zero until round 3), row-major [n_rows x dim] -- the hi halves of the fp16
     // split as a matrix of their own, 2 B per element: what the single-query search streams (search_rows_hi).
     rl::Image hiplane;
@@ -2786,6 +2787,34 @@ int rl_maxsim_approx_scores(rl_index* idx, const float* query_vecs, int32_t n_qu
     return finish(mem, s);
 }
 
+}  // extern "C"
+
+namespace {
+// The device half of rl_maxsim_rerank on device pointers (under idx->mu, after use_scratch): d_q [n_queries x nq x dim],
+// d_c [n_queries x n_cand] -> d_o [n_queries x n_cand]
+int maxsim_rerank_device(rl_index* idx, const float* d_q, int32_t n_queries, int32_t nq, const int32_t* d_c, int32_t n_cand, float* d_o,
+                         hipStream_t s) {
+    {   // ordinals that cannot be scored (device callers are not validated above; -1 pads of a search result; tombstones) -> -inf
+        const int64_t n_items = (int64_t)n_queries * n_cand;
+        RL_TRY(idx->cand.reserve((size_t)n_items * sizeof(int32_t)));
+        RL_TRY(launch_sanitize_candidates(d_c, n_items, idx->n_chunks, idx->live_chunk_bits, idx->cand.as<int32_t>(), s));
+        d_c = idx->cand.as<int32_t>();
+    }
+    int st = idx->E16 ? launch_maxsim_cand16(idx->E16, idx->dim, d_q, nq, idx->offsets, d_c, n_cand, n_queries, d_o, s)
+                      : launch_maxsim_cand(idx->E, idx->dim, d_q, nq, idx->offsets, d_c, n_cand, n_queries, d_o, s, idx->split_scale);
+    if (st == RL_ERR_UNSUPPORTED)  // other dims: the fp32-MFMA pairs kernels (dim % 16 == 0 up to 1024, % 128 up to 4096, nq <= 32; fp16 rows widened on the way in) ...
+        st = launch_maxsim_pairs(idx->E16 ? reinterpret_cast<const float*>(idx->E16) : idx->E, idx->dim, d_q, nq, (int64_t)nq * idx->dim, idx->offsets, d_c,
+                                 n_cand, n_queries, d_o, s, idx->E16 != nullptr, 0, 0, (int)idx->opt.v[RL_OPT_PAIRS_PACKED]);
+    if (st == RL_ERR_UNSUPPORTED && idx->E16) return fail(st, "rl_maxsim_rerank: unsupported shape for an fp16-stored index");
+    if (st == RL_ERR_UNSUPPORTED && !idx->E16)  // ... and the VALU backstop for everything else
+        st = launch_maxsim_generic(idx->E, idx->dim, d_q, nq, (int64_t)nq * idx->dim, idx->offsets, d_c, n_cand,
+                                   n_queries, d_o, s);
+    return st;
+}
+}  // namespace
+
+extern "C" {
+
 int rl_maxsim_rerank(rl_index* idx, const float* query_vecs, int32_t n_queries, int32_t nq, const int32_t* candidates,
                      int32_t n_cand, float* out_scores, int mem, void* stream) {
     if (!idx) return fail(RL_ERR_INVALID, "rl_maxsim_rerank: null index");
@@ -2807,22 +2836,7 @@ int rl_maxsim_rerank(rl_index* idx, const float* query_vecs, int32_t n_queries, 
     RL_TRY(stage_in(query_vecs, (size_t)n_queries * nq * idx->dim, mem, s, t_q, &d_q));
     RL_TRY(stage_in(candidates, (size_t)n_queries * n_cand, mem, s, t_c, &d_c));
     RL_TRY(stage_out_begin(out_scores, (size_t)n_queries * n_cand, mem, t_o, &d_o));
-    {   // ordinals that cannot be scored (device callers are not validated above; -1 pads of a search result; tombstones) -> -inf
-        const int64_t n_items = (int64_t)n_queries * n_cand;
-        RL_TRY(idx->cand.reserve((size_t)n_items * sizeof(int32_t)));
-        RL_TRY(launch_sanitize_candidates(d_c, n_items, idx->n_chunks, idx->live_chunk_bits, idx->cand.as<int32_t>(), s));
-        d_c = idx->cand.as<int32_t>();
-    }
-    int st = idx->E16 ? launch_maxsim_cand16(idx->E16, idx->dim, d_q, nq, idx->offsets, d_c, n_cand, n_queries, d_o, s)
-                      : launch_maxsim_cand(idx->E, idx->dim, d_q, nq, idx->offsets, d_c, n_cand, n_queries, d_o, s, idx->split_scale);
-    if (st == RL_ERR_UNSUPPORTED)  // other dims: the fp32-MFMA pairs kernels (dim % 16 == 0 up to 1024, % 128 up to 4096, nq <= 32; fp16 rows widened on the way in) ...
-        st = launch_maxsim_pairs(idx->E16 ? reinterpret_cast<const float*>(idx->E16) : idx->E, idx->dim, d_q, nq, (int64_t)nq * idx->dim, idx->offsets, d_c,
-                                 n_cand, n_queries, d_o, s, idx->E16 != nullptr, 0, 0, (int)idx->opt.v[RL_OPT_PAIRS_PACKED]);
-    if (st == RL_ERR_UNSUPPORTED && idx->E16) return fail(st, "rl_maxsim_rerank: unsupported shape for an fp16-stored index");
-    if (st == RL_ERR_UNSUPPORTED && !idx->E16)  // ... and the VALU backstop for everything else
-        st = launch_maxsim_generic(idx->E, idx->dim, d_q, nq, (int64_t)nq * idx->dim, idx->offsets, d_c, n_cand,
-                                   n_queries, d_o, s);
-    RL_TRY(st);
+    RL_TRY(maxsim_rerank_device(idx, d_q, n_queries, nq, d_c, n_cand, d_o, s));
     RL_TRY(stage_out_end(out_scores, (size_t)n_queries * n_cand, mem, s, t_o));
     return finish(mem, s);
 }
@@ -3356,20 +3370,33 @@ int rl_shard_hybrid_fuse(const int32_t* gathered, int32_t world, int32_t n_queri
 }  // extern "C"
 
 namespace {
-// rl_hybrid_search and rl_hybrid_search_per_query: one device path
-int hybrid_search_call(rl_index* idx, rl_keyword_index* kw, const float* queries, int32_t n_queries, int32_t num_hits, int32_t n_each,
-                       const int64_t* q_off, const int32_t* q_terms, const uint32_t* chunk_filters, int32_t n_filters, const int32_t* query_filter,
-                       const int64_t* rank_limits, int64_t rank_limit, const double* weights, int32_t rrf_k, int32_t k, double* out_scores,
-                       int32_t* out_chunks, int32_t* out_counts, int mem, void* stream, const char* who) {
-    const int32_t B = n_queries, R = kw ? 2 : 1;
+// What every hybrid call needs before its device work: the arguments checked, both handles locked on the stream, the inputs staged.
+struct HybridCall {
+    std::unique_lock<std::mutex> idx_lock, kw_lock;  // (idx->mu, then kw->mu: always in this order)
+    DevBuf t_q, t_f, t_off, t_terms;
+    const float* d_q = nullptr;
+    const int64_t* d_off = nullptr;
+    const int32_t* d_terms = nullptr;
+    BatchFilters f;
+    int32_t n_filters = 0;
+    const int32_t* query_filter = nullptr;
+    bool empty = false;  // n_queries == 0: nothing to do
+};
+
+// The checks of rl_hybrid_search (k: the fusion's), the locks and the staging-in
+int hybrid_search_begin(rl_index* idx, rl_keyword_index* kw, const float* queries, int32_t B, int32_t num_hits, int32_t n_each,
+                        const int64_t* q_off, const int32_t* q_terms, const uint32_t* chunk_filters, int32_t n_filters,
+                        const int32_t* query_filter, const int64_t* rank_limits, int64_t rank_limit, const double* weights, int32_t rrf_k,
+                        int32_t k, bool outputs, int mem, hipStream_t s, const char* who, HybridCall* c) {
+    const int32_t R = kw ? 2 : 1;
     RL_TRY(check_search_args(idx, queries, B, n_each, who));
     if (rank_limit < 0) return fail(RL_ERR_INVALID, std::string(who) + ": rank_limit must be >= 0 (0 = no cut)");
     if (num_hits < 1 || num_hits > K_MAX) return fail(RL_ERR_INVALID, std::string(who) + ": num_hits must be in [1, 2048]");
     RL_TRY(check_fuse_args(R, B, n_each, weights, rrf_k, k, who));
     if (mem != RL_MEM_HOST && mem != RL_MEM_DEVICE) return fail(RL_ERR_INVALID, std::string(who) + ": bad mem");
     if (kw && kw->n_chunks != idx->n_chunks) return fail(RL_ERR_INVALID, std::string(who) + ": the keyword index covers another number of chunks");
-    if (B == 0) return RL_OK;
-    if (!out_scores || !out_chunks || !out_counts) return fail(RL_ERR_INVALID, std::string(who) + ": null output");
+    if (B == 0) { c->empty = true; return RL_OK; }
+    if (!outputs) return fail(RL_ERR_INVALID, std::string(who) + ": null output");
     int64_t n_q_terms = 0;
     if (kw) {
         if (!q_off) return fail(RL_ERR_INVALID, std::string(who) + ": null q_off");
@@ -3380,48 +3407,67 @@ int hybrid_search_call(rl_index* idx, rl_keyword_index* kw, const float* queries
             return fail(RL_ERR_INVALID, std::string(who) + ": null q_terms");
         }
     }
-    hipStream_t s = as_stream(stream);
-    std::lock_guard<std::mutex> lock(idx->mu);  // (then kw->mu: the only call that holds both, always in this order)
+    c->idx_lock = std::unique_lock<std::mutex>(idx->mu);  // (then kw->mu: the only calls that hold both, always in this order)
     RL_TRY(use_scratch(idx, s));
-    std::unique_lock<std::mutex> kw_lock;
     if (kw) {
-        kw_lock = std::unique_lock<std::mutex>(kw->mu);
+        c->kw_lock = std::unique_lock<std::mutex>(kw->mu);
         RL_TRY(keyword_use_stream(kw, s));
     }
-    const size_t n_list = (size_t)B * n_each, n_out = (size_t)B * k;
-    DevBuf t_q, t_f, t_off, t_terms, t_s, t_c, t_n;
-    const float* d_q;
-    const int64_t* d_off = nullptr;
-    const int32_t* d_terms = q_terms;
-    double* d_s;
-    int32_t *d_c, *d_n;
-    BatchFilters f;
-    f.n = n_filters;
-    f.qf = query_filter;
-    f.lim = rank_limits;
-    f.limit = rank_limit;
-    RL_TRY(stage_in(queries, (size_t)B * idx->dim, mem, s, t_q, &d_q));
-    if (n_filters) RL_TRY(stage_in(chunk_filters, (size_t)n_filters * ((idx->n_chunks + 31) / 32), mem, s, t_f, &f.chunk_bits));
+    c->d_terms = q_terms;
+    c->n_filters = n_filters;
+    c->query_filter = query_filter;
+    c->f.n = n_filters;
+    c->f.qf = query_filter;
+    c->f.lim = rank_limits;
+    c->f.limit = rank_limit;
+    RL_TRY(stage_in(queries, (size_t)B * idx->dim, mem, s, c->t_q, &c->d_q));
+    if (n_filters) RL_TRY(stage_in(chunk_filters, (size_t)n_filters * ((idx->n_chunks + 31) / 32), mem, s, c->t_f, &c->f.chunk_bits));
     if (kw) {
-        RL_TRY(stage_in(q_off, (size_t)B + 1, mem, s, t_off, &d_off));
-        if (mem == RL_MEM_HOST) RL_TRY(stage_in(q_terms, (size_t)n_q_terms, mem, s, t_terms, &d_terms));
+        RL_TRY(stage_in(q_off, (size_t)B + 1, mem, s, c->t_off, &c->d_off));
+        if (mem == RL_MEM_HOST) RL_TRY(stage_in(q_terms, (size_t)n_q_terms, mem, s, c->t_terms, &c->d_terms));
     }
-    RL_TRY(stage_out_begin(out_scores, n_out, mem, t_s, &d_s));
-    RL_TRY(stage_out_begin(out_chunks, n_out, mem, t_c, &d_c));
-    RL_TRY(stage_out_begin(out_counts, (size_t)B, mem, t_n, &d_n));
+    return RL_OK;
+}
+
+// The two searches and the fusion on device pointers (after hybrid_search_begin): d_s / d_c [B x k], d_n [B]
+int hybrid_search_device(rl_index* idx, rl_keyword_index* kw, const HybridCall& c, int32_t B, int32_t num_hits, int32_t n_each,
+                         const double* weights, int32_t rrf_k, int32_t k, double* d_s, int32_t* d_c, int32_t* d_n, hipStream_t s) {
+    const int32_t R = kw ? 2 : 1;
+    const size_t n_list = (size_t)B * n_each;
     // index-owned scratch: lists [R x B x n_each] int32 (what the fusion reads), the two searches' scores [R x B x n_each] f32 and
     // counts [R x B] int32 (written, not read)
     RL_TRY(idx->hybrid.reserve((size_t)R * (2 * n_list + B) * 4));
     int32_t* lists = idx->hybrid.as<int32_t>();
     float* list_scores = reinterpret_cast<float*>(lists + (size_t)R * n_list);
     int32_t* list_counts = reinterpret_cast<int32_t*>(list_scores + (size_t)R * n_list);
-    RL_TRY(search_chunks_device(idx, d_q, B, num_hits, n_each, f, list_scores, lists, list_counts, s));
+    RL_TRY(search_chunks_device(idx, c.d_q, B, num_hits, n_each, c.f, list_scores, lists, list_counts, s));
     if (kw) {
         QueryMask mask;
-        RL_TRY(keyword_mask(kw, f.chunk_bits, n_filters, query_filter, B, s, &mask));
-        RL_TRY(keyword_search_device(kw, d_off, d_terms, B, n_each, mask, list_scores + n_list, lists + n_list, list_counts + B, s));
+        RL_TRY(keyword_mask(kw, c.f.chunk_bits, c.n_filters, c.query_filter, B, s, &mask));
+        RL_TRY(keyword_search_device(kw, c.d_off, c.d_terms, B, n_each, mask, list_scores + n_list, lists + n_list, list_counts + B, s));
     }
-    RL_TRY(launch_rrf_fuse(lists, R, B, n_each, weights, rrf_k, k, d_s, d_c, d_n, s));
+    return launch_rrf_fuse(lists, R, B, n_each, weights, rrf_k, k, d_s, d_c, d_n, s);
+}
+
+// rl_hybrid_search and rl_hybrid_search_per_query: one device path
+int hybrid_search_call(rl_index* idx, rl_keyword_index* kw, const float* queries, int32_t n_queries, int32_t num_hits, int32_t n_each,
+                       const int64_t* q_off, const int32_t* q_terms, const uint32_t* chunk_filters, int32_t n_filters, const int32_t* query_filter,
+                       const int64_t* rank_limits, int64_t rank_limit, const double* weights, int32_t rrf_k, int32_t k, double* out_scores,
+                       int32_t* out_chunks, int32_t* out_counts, int mem, void* stream, const char* who) {
+    const int32_t B = n_queries;
+    hipStream_t s = as_stream(stream);
+    HybridCall c;
+    RL_TRY(hybrid_search_begin(idx, kw, queries, B, num_hits, n_each, q_off, q_terms, chunk_filters, n_filters, query_filter, rank_limits,
+                               rank_limit, weights, rrf_k, k, out_scores && out_chunks && out_counts, mem, s, who, &c));
+    if (c.empty) return RL_OK;
+    const size_t n_out = (size_t)B * k;
+    DevBuf t_s, t_c, t_n;
+    double* d_s;
+    int32_t *d_c, *d_n;
+    RL_TRY(stage_out_begin(out_scores, n_out, mem, t_s, &d_s));
+    RL_TRY(stage_out_begin(out_chunks, n_out, mem, t_c, &d_c));
+    RL_TRY(stage_out_begin(out_counts, (size_t)B, mem, t_n, &d_n));
+    RL_TRY(hybrid_search_device(idx, kw, c, B, num_hits, n_each, weights, rrf_k, k, d_s, d_c, d_n, s));
     RL_TRY(stage_out_end(out_scores, n_out, mem, s, t_s));
     RL_TRY(stage_out_end(out_chunks, n_out, mem, s, t_c));
     RL_TRY(stage_out_end(out_counts, (size_t)B, mem, s, t_n));
@@ -3446,6 +3492,81 @@ int rl_hybrid_search_per_query(rl_index* idx, rl_keyword_index* kw, const float*
     RL_TRY(check_query_filters(n_queries, chunk_filters, n_filters, query_filter, rank_limits, who));
     return hybrid_search_call(idx, kw, queries, n_queries, num_hits, n_each, q_off, q_terms, chunk_filters, query_filter ? n_filters : 0,
                               query_filter, rank_limits, 0, weights, rrf_k, k, out_scores, out_chunks, out_counts, mem, stream, who);
+}
+
+// ---- batched search-and-rerank (include/raglite_hip.h; the ordering kernel is in rerank.hip) -----------------------------------------
+int rl_rerank_order(const float* scores, const int32_t* candidates, int32_t n_queries, int32_t n_cand, int32_t k, float* out_scores,
+                    int32_t* out_chunks, int32_t* out_pos, int32_t* out_counts, int mem, void* stream) {
+    if (n_queries < 0) return fail(RL_ERR_INVALID, "rl_rerank_order: n_queries must be >= 0");
+    if (n_cand < 1 || n_cand > RERANK_MAX_ENTRIES) return fail(RL_ERR_INVALID, "rl_rerank_order: n_cand must be in [1, 4096]");
+    if (k < 1 || k > n_cand) return fail(RL_ERR_INVALID, "rl_rerank_order: k must be in [1, n_cand]");
+    if (mem != RL_MEM_HOST && mem != RL_MEM_DEVICE) return fail(RL_ERR_INVALID, "rl_rerank_order: bad mem");
+    if (n_queries == 0) return RL_OK;
+    if (!scores || !candidates || !out_scores || !out_chunks || !out_pos || !out_counts)
+        return fail(RL_ERR_INVALID, "rl_rerank_order: null argument");
+    hipStream_t s = as_stream(stream);
+    const size_t n_in = (size_t)n_queries * n_cand, n_out = (size_t)n_queries * k;
+    DevBuf t_sc, t_ca, t_s, t_c, t_p, t_n;
+    const float* d_sc;
+    const int32_t* d_ca;
+    float* d_s;
+    int32_t *d_c, *d_p, *d_n;
+    RL_TRY(stage_in(scores, n_in, mem, s, t_sc, &d_sc));
+    RL_TRY(stage_in(candidates, n_in, mem, s, t_ca, &d_ca));
+    RL_TRY(stage_out_begin(out_scores, n_out, mem, t_s, &d_s));
+    RL_TRY(stage_out_begin(out_chunks, n_out, mem, t_c, &d_c));
+    RL_TRY(stage_out_begin(out_pos, n_out, mem, t_p, &d_p));
+    RL_TRY(stage_out_begin(out_counts, (size_t)n_queries, mem, t_n, &d_n));
+    RL_TRY(launch_rerank_order(d_sc, d_ca, n_queries, n_cand, k, d_s, d_c, d_p, d_n, s));
+    RL_TRY(stage_out_end(out_scores, n_out, mem, s, t_s));
+    RL_TRY(stage_out_end(out_chunks, n_out, mem, s, t_c));
+    RL_TRY(stage_out_end(out_pos, n_out, mem, s, t_p));
+    RL_TRY(stage_out_end(out_counts, (size_t)n_queries, mem, s, t_n));
+    return finish(mem, s);
+}
+
+int rl_search_rerank_per_query(rl_index* idx, rl_keyword_index* kw, const float* queries, int32_t n_queries, int32_t num_hits, int32_t n_each,
+                               const int64_t* q_off, const int32_t* q_terms, const uint32_t* chunk_filters, int32_t n_filters,
+                               const int32_t* query_filter, const int64_t* rank_limits, const double* weights, int32_t rrf_k, int32_t n_cand,
+                               const float* query_vecs, int32_t nq, int32_t k, float* out_scores, int32_t* out_chunks, int32_t* out_counts,
+                               int mem, void* stream) {
+    const char* who = "rl_search_rerank_per_query";
+    const int32_t B = n_queries;
+    if (nq < 1) return fail(RL_ERR_INVALID, std::string(who) + ": nq must be >= 1");
+    if (n_cand < 1 || n_cand > RERANK_MAX_ENTRIES) return fail(RL_ERR_INVALID, std::string(who) + ": n_cand must be in [1, 4096]");
+    if (k < 1 || k > n_cand) return fail(RL_ERR_INVALID, std::string(who) + ": k must be in [1, n_cand]");
+    RL_TRY(check_query_filters(B, chunk_filters, n_filters, query_filter, rank_limits, who));
+    if (idx && idx->E16 && (nq > 32 || idx->dim % 16))
+        return fail(RL_ERR_UNSUPPORTED, std::string(who) + ": MaxSim reranking on an fp16-stored index needs nq <= 32 and dim % 16 == 0");
+    hipStream_t s = as_stream(stream);
+    HybridCall c;
+    RL_TRY(hybrid_search_begin(idx, kw, queries, B, num_hits, n_each, q_off, q_terms, chunk_filters, query_filter ? n_filters : 0, query_filter,
+                               rank_limits, 0, weights, rrf_k, n_cand, query_vecs && out_scores && out_chunks && out_counts, mem, s, who, &c));
+    if (c.empty) return RL_OK;
+    const size_t n_list = (size_t)B * n_cand, n_out = (size_t)B * k;
+    DevBuf t_v, t_s, t_c, t_n;
+    const float* d_v;
+    float* d_s;
+    int32_t *d_c, *d_n;
+    RL_TRY(stage_in(query_vecs, (size_t)B * nq * idx->dim, mem, s, t_v, &d_v));
+    RL_TRY(stage_out_begin(out_scores, n_out, mem, t_s, &d_s));
+    RL_TRY(stage_out_begin(out_chunks, n_out, mem, t_c, &d_c));
+    RL_TRY(stage_out_begin(out_counts, (size_t)B, mem, t_n, &d_n));
+    // index-owned scratch: the fused scores [B x n_cand] f64 (written, not read), the fused candidates [B x n_cand] int32, their
+    // MaxSim scores [B x n_cand] f32, the fusion's counts [B] and the positions of the first k [B x k] int32 (written, not read)
+    RL_TRY(idx->rerank.reserve(n_list * 16 + (size_t)B * 4 + n_out * 4));
+    double* fused_scores = idx->rerank.as<double>();
+    int32_t* fused = reinterpret_cast<int32_t*>(fused_scores + n_list);
+    float* maxsim = reinterpret_cast<float*>(fused + n_list);
+    int32_t* fused_counts = reinterpret_cast<int32_t*>(maxsim + n_list);
+    int32_t* pos = fused_counts + B;
+    RL_TRY(hybrid_search_device(idx, kw, c, B, num_hits, n_each, weights, rrf_k, n_cand, fused_scores, fused, fused_counts, s));
+    RL_TRY(maxsim_rerank_device(idx, d_v, B, nq, fused, n_cand, maxsim, s));
+    RL_TRY(launch_rerank_order(maxsim, fused, B, n_cand, k, d_s, d_c, pos, d_n, s));
+    RL_TRY(stage_out_end(out_scores, n_out, mem, s, t_s));
+    RL_TRY(stage_out_end(out_chunks, n_out, mem, s, t_c));
+    RL_TRY(stage_out_end(out_counts, (size_t)B, mem, s, t_n));
+    return finish(mem, s);
 }
 
 }  // extern "C"

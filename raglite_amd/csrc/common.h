@@ -367,6 +367,12 @@ int launch_shard_hybrid_fuse(const int32_t* gathered, int32_t world, int32_t n_q
                              const double* weights /* host */, int32_t rrf_k, int32_t k, double* out_scores, int32_t* out_ids,
                              int32_t* out_counts, hipStream_t s);
 
+// rerank.hip: the order of reranked candidates (scores / candidates [n_queries x n_cand], candidate < 0 = padding) -> the first k by
+// (score desc, NaN as -inf, -0.0 == +0.0; position asc), padding last: MaxSimRanker.rank's lexsort.  out_counts may be nullptr.
+constexpr int32_t RERANK_MAX_ENTRIES = 4096;  // n_cand: one workgroup's LDS, as RRF_MAX_ENTRIES
+int launch_rerank_order(const float* scores, const int32_t* candidates, int32_t n_queries, int32_t n_cand, int32_t k, float* out_scores,
+                        int32_t* out_chunks, int32_t* out_pos, int32_t* out_counts, hipStream_t s);
+
 // adapter_fit.hip: device half of update_query_adapter (best row per (query, chunk), row gather)
 int launch_chunk_best_rows(const void* E, bool f16, int32_t dim, const float* Q, const int64_t* offsets,
                            int64_t n_chunks, const int32_t* cand, int32_t n_cand, int64_t n_items, int32_t* out_rows,
