@@ -620,6 +620,55 @@ int rl_search_rerank_per_query(rl_index* index, rl_keyword_index* kw, const floa
                                const float* query_vecs, int32_t nq, int32_t k, float* out_scores, int32_t* out_chunks,
                                int32_t* out_counts, int mem, void* stream);
 
+/* ---- chunk spans (src/raglite/_search.py:302-361, `retrieve_chunk_spans`; :417-433, `search_and_rerank_chunk_spans`) ---------
+ * A span table sits beside an rl_index as a keyword index does: it covers the SAME chunk ordinals, is immutable, and is built
+ * again from the live chunks after every change of the index.
+ *   doc   int32[n_chunks] (host) the dense number of the chunk's document: the place of its `Chunk.document_id` among the
+ *         distinct ids in ascending string order (what the reference's sort key compares); < 0: the chunk has no position
+ *         (a tombstoned chunk), it is never kept and never a neighbour
+ *   pos   int32[n_chunks] (host) `Chunk.index`, >= 0 where doc >= 0; two chunks with the same (doc, pos): RL_ERR_INVALID
+ * rl_span_table_create sorts the chunks that have a position by (doc, pos) on the host and uploads ordinal -> rank,
+ * rank -> (doc, pos) as one 64-bit key, and rank -> ordinal.  rl_span_table_info: the chunks covered, those with a position, and
+ * the device bytes held (each pointer may be NULL).
+ *
+ * rl_chunk_spans replaces `_search.py:323-361` for n_queries lists of chunk ordinals:
+ *   chunks   int32 [n_queries x n_in], each query's chunks best first.  An entry < 0, >= the table's n_chunks or without a
+ *            position is skipped and takes no rank (what `retrieve_chunks` does to unknown ids before `:324` enumerates); kept
+ *            entry number i (from 0) scores 1.0 / (i + 1) in double; of a chunk that appears twice the LAST score stands (`:324`)
+ *   offsets  int32 [n_off] in HOST memory whatever `mem` says; may be empty, hold 0 and repeat values.  Every kept entry adds the
+ *            chunk at (doc, pos + offset) where the table holds one (`:328-340`); pos + offset is taken in 64 bits
+ *   E = n_in * (1 + n_off) <= 4096, n_in >= 1, 0 <= n_off <= 64: checked with `mem` and the table before any HIP call
+ *   (RL_ERR_INVALID); n_queries == 0 returns RL_OK.
+ * The distinct chunks are ordered by (doc, pos) (`:342`); a chunk continues the span of the one before it iff it has the same doc
+ * and the next pos (`:345-353`).  A span's score is the IEEE double sum of its members' scores, a neighbour that is no entry
+ * counting 0.0, added left to right in ascending pos from 0.0 (`:356-358`; Python's sum() before 3.12).  Spans are ordered by score
+ * descending, equal scores by the (doc, pos) of their first chunk (`:355-360`, a stable sort).
+ *   out_chunks      int32 [n_queries x E] the distinct chunks, span after span in that order, ascending pos within a span; then -1
+ *   out_span_len    int32 [n_queries x E] the chunks of each span; 0 beyond the last span
+ *   out_span_scores f64   [n_queries x E] the spans' scores; 0.0 beyond the last span
+ *   out_n_spans / out_n_chunks int32 [n_queries]
+ *
+ * rl_search_rerank_spans_per_query replaces `_search.py:417-433` with a MaxSim reranker: rl_search_rerank_per_query (its
+ * arguments, checks, locks and routes) into scratch the index owns, then rl_chunk_spans of each query's reranked first k on the
+ * same stream, nothing read back in between.  k * (1 + n_off) <= 4096 and the table are checked first.  out_top_chunks
+ * int32 [n_queries x k] / out_top_counts [n_queries] are rl_search_rerank_per_query's out_chunks / out_counts; the span outputs
+ * are rl_chunk_spans' with n_in = k. */
+typedef struct rl_span_table rl_span_table;
+int rl_span_table_create(rl_span_table** out, const int32_t* doc, const int32_t* pos, int64_t n_chunks);
+int rl_span_table_info(const rl_span_table* table, int64_t* n_chunks, int64_t* n_live, int64_t* device_bytes);
+int rl_span_table_destroy(rl_span_table* table);
+int rl_chunk_spans(const rl_span_table* table, const int32_t* chunks, int32_t n_queries, int32_t n_in, const int32_t* offsets,
+                   int32_t n_off, int32_t* out_chunks, int32_t* out_span_len, double* out_span_scores, int32_t* out_n_spans,
+                   int32_t* out_n_chunks, int mem, void* stream);
+int rl_search_rerank_spans_per_query(rl_index* index, rl_keyword_index* kw, const float* queries, int32_t n_queries,
+                                     int32_t num_hits, int32_t n_each, const int64_t* q_off, const int32_t* q_terms,
+                                     const uint32_t* chunk_filters, int32_t n_filters, const int32_t* query_filter,
+                                     const int64_t* rank_limits, const double* weights, int32_t rrf_k, int32_t n_cand,
+                                     const float* query_vecs, int32_t nq, int32_t k, const rl_span_table* table,
+                                     const int32_t* offsets, int32_t n_off, int32_t* out_top_chunks, int32_t* out_top_counts,
+                                     int32_t* out_chunks, int32_t* out_span_len, double* out_span_scores, int32_t* out_n_spans,
+                                     int32_t* out_n_chunks, int mem, void* stream);
+
 /* ---- device half of update_query_adapter ----------------------------------
  * src/raglite/_query_adapter.py:153-205 fits the query adapter from evals: per eval a vector search
  * (rl_search_chunks, batched over all evals), then for every retrieved chunk the row

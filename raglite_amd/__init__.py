@@ -23,6 +23,7 @@ from raglite_amd._ops import (
     merge_topk,
     pack_bits,
     rerank_order,
+    SpanTable,
     rrf_fuse,
     shard_hybrid_fuse,
     get_default_option,
@@ -47,6 +48,12 @@ from raglite_amd._search import (
     rerank_chunks_batch,
     search_and_rerank_chunks,
     search_and_rerank_chunks_batch,
+    ChunkSpan,
+    retrieve_chunk_spans,
+    retrieve_chunk_spans_batch,
+    search_and_rerank_chunk_spans,
+    search_and_rerank_chunk_spans_batch,
+    retrieve_context,
     select_reranker,
     set_language_detector,
     vector_search,
@@ -83,6 +90,8 @@ __all__ = [
     "rerank_order",
     "rerank_chunks_batch",
     "search_and_rerank_chunks_batch",
+    "ChunkSpan", "SpanTable", "retrieve_chunk_spans", "retrieve_chunk_spans_batch", "search_and_rerank_chunk_spans",
+    "search_and_rerank_chunk_spans_batch", "retrieve_context",
     "shard_hybrid_fuse",
     "Communicator", "DeviceIndex", "GpuIndex", "GpuVectorSearch", "HotPathConfig", "MaxSimRanker", "ShardedIndex",
     "adapter_apply", "attach_index", "detach_index", "embed_strings", "embed_strings_with_late_chunking",

@@ -130,6 +130,13 @@ _SIGNATURES = {
     "rl_search_rerank_per_query": [c_void_p, c_void_p, c_void_p, c_i32, c_i32, c_i32, c_void_p, c_void_p, c_void_p, c_i32, c_void_p,
                                    c_void_p, c_void_p, c_i32, c_i32, c_void_p, c_i32, c_i32, c_void_p, c_void_p, c_void_p, c_int,
                                    c_void_p],
+    "rl_span_table_create": [C.POINTER(c_void_p), c_void_p, c_void_p, c_i64],
+    "rl_span_table_info": [c_void_p, C.POINTER(c_i64), C.POINTER(c_i64), C.POINTER(c_i64)],
+    "rl_span_table_destroy": [c_void_p],
+    "rl_chunk_spans": [c_void_p, c_void_p, c_i32, c_i32, c_void_p, c_i32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p],
+    "rl_search_rerank_spans_per_query": [c_void_p, c_void_p, c_void_p, c_i32, c_i32, c_i32, c_void_p, c_void_p, c_void_p, c_i32, c_void_p,
+                                         c_void_p, c_void_p, c_i32, c_i32, c_void_p, c_i32, c_i32, c_void_p, c_void_p, c_i32, c_void_p,
+                                         c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p],
 }
 COMM_ID_BYTES = 128
 _RESTYPES = {"rl_last_error": c_char_p}

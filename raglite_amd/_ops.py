@@ -252,6 +252,80 @@ def rerank_order(scores, candidates, k: int):
     return o_s, o_c, o_p, o_n
 
 
+SPANS_MAX_ENTRIES = 4096  # n_in * (1 + n_off) per query that rl_chunk_spans handles (one workgroup's LDS)
+SPANS_MAX_OFFSETS = 64
+
+
+def _span_offsets(neighbors) -> np.ndarray:
+    offs = np.ascontiguousarray(np.asarray(() if neighbors is None else tuple(neighbors), dtype=np.int64).ravel())
+    if offs.size > SPANS_MAX_OFFSETS:
+        raise ValueError(f"at most {SPANS_MAX_OFFSETS} neighbour offsets are supported")
+    if offs.size and (offs.min() < -(1 << 31) or offs.max() >= (1 << 31)):
+        raise ValueError("neighbour offsets must fit in int32")
+    return offs.astype(np.int32)
+
+
+class SpanTable:
+    """Where every chunk sits in its document (`rl_span_table`): `doc` and `pos` int32 per chunk ordinal of the `DeviceIndex` it sits
+    beside, `doc` the dense number of the chunk's document id in sorted order (< 0: the chunk has no position), `pos` its
+    `Chunk.index`."""
+
+    def __init__(self, doc, pos) -> None:
+        doc = np.ascontiguousarray(doc, dtype=np.int32).ravel()
+        pos = np.ascontiguousarray(pos, dtype=np.int32).ravel()
+        if doc.size != pos.size:
+            raise ValueError("one (doc, pos) per chunk is required")
+        self.n_chunks = int(doc.size)
+        _ensure_init(_current_device())
+        handle = C.c_void_p()
+        check(lib().rl_span_table_create(C.byref(handle), doc.ctypes.data, pos.ctypes.data, self.n_chunks))
+        self._handle = handle
+
+    def info(self) -> tuple[int, int, int]:
+        """(chunks covered, chunks with a position, device bytes held)."""
+        n, live, nbytes = C.c_int64(0), C.c_int64(0), C.c_int64(0)
+        check(lib().rl_span_table_info(self._handle, C.byref(n), C.byref(live), C.byref(nbytes)))
+        return int(n.value), int(live.value), int(nbytes.value)
+
+    def close(self) -> None:
+        h, self._handle = getattr(self, "_handle", None), None
+        if h:
+            lib().rl_span_table_destroy(h)
+
+    def __del__(self) -> None:  # noqa: D105
+        try:
+            self.close()
+        except Exception:  # noqa: BLE001,S110 - interpreter shutdown
+            pass
+
+    def chunk_spans(self, chunks, neighbors=(-1, 1)):
+        """`rl_chunk_spans`: the reference's `retrieve_chunk_spans` (`src/raglite/_search.py:323-361`) on ordinals for a batch.  `chunks`
+        (B, n_in) int32, each query's chunks best first; entries < 0, out of range or without a position are skipped and take no rank.
+        `neighbors`: the offsets (None or () for none).  With E = n_in * (1 + len(neighbors)) <= 4096, returns (chunks (B, E) int32 --
+        the distinct chunks span after span, best span first, ascending index within a span, padded with -1 --, span lengths (B, E)
+        int32, span scores (B, E) float64, number of spans (B,) int32, number of chunks (B,) int32)."""
+        offs = _span_offsets(neighbors)
+        a = _Args()
+        p_c = a.inp(chunks, np.int32)
+        cv = a.keep[-1]
+        if cv.ndim != 2:
+            raise ValueError("chunks must be (n_queries, n_in)")
+        B, n_in = int(cv.shape[0]), int(cv.shape[1])
+        E = n_in * (1 + int(offs.size))
+        if n_in < 1 or E > SPANS_MAX_ENTRIES:
+            raise ValueError(f"chunk_spans: need n_in >= 1 and n_in * (1 + len(neighbors)) <= {SPANS_MAX_ENTRIES} (n_in={n_in}, "
+                             f"{offs.size} offsets)")
+        o_c, p_oc = a.out((B, E), np.int32)
+        o_l, p_ol = a.out((B, E), np.int32)
+        o_s, p_os = a.out((B, E), np.float64)
+        o_ns, p_ns = a.out((B,), np.int32)
+        o_nc, p_nc = a.out((B,), np.int32)
+        a.ensure_device()
+        check(lib().rl_chunk_spans(self._handle, p_c, B, n_in, offs.ctypes.data if offs.size else None, int(offs.size), p_oc, p_ol, p_os,
+                                   p_ns, p_nc, a.mem, a.stream))
+        return o_c, o_l, o_s, o_ns, o_nc
+
+
 def shard_hybrid_fuse(gathered, *, num_hits: int, n_each: int, keywords: bool, weights, rrf_k: int = 60, k: int):
     """`rl_shard_hybrid_fuse`: the step after the one all-gather of a sharded hybrid batch.  `gathered`: (world, B, W) int32, what every
     rank packed -- num_hits row records (score bits, global row, global chunk), then with `keywords` n_each keyword records (score bits,
@@ -717,14 +791,9 @@ class DeviceIndex:
                  w.ctypes.data, int(rrf_k), int(k), p_s, p_c, p_n, a.mem, a.stream))
         return (o_s[0], o_c[0], o_n[0]) if single else (o_s, o_c, o_n)
 
-    def search_rerank(self, queries, num_hits: int, n_each: int, n_cand: int, query_vecs, k: int, *,
-                      keyword: "KeywordIndex | None" = None, query_term_ids=None, weights=(0.75, 0.25), rrf_k: int = 60, chunk_filter=None,
-                      rank_limit=None, query_filters=None):
-        """`rl_search_rerank_per_query`: `hybrid_search(queries, num_hits, n_each, k=n_cand, ...)`, then `maxsim_rerank` of each query's
-        fused candidates against `query_vecs` (B, nq, dim), then `rerank_order`'s first k, all on one stream with nothing read back in
-        between.  Returns (MaxSim scores (B, k) float32, chunk ordinals (B, k) int32 best first, counts (B,) int32).  Without
-        `keyword` the candidates are the vector search's list alone.  The filter arguments are `hybrid_search`'s."""
-        a = _Args()
+    def _search_rerank_args(self, a, queries, query_vecs, keyword, query_term_ids, weights, chunk_filter, rank_limit, query_filters):
+        """The arguments `rl_search_rerank_per_query` and `rl_search_rerank_spans_per_query` share, up to `weights`: (B, nq, the pointers
+        in call order after `n_each`, the weights array)."""
         p_q, B, single = self._queries(a, queries)
         if single:
             raise ValueError("queries must be (n_queries, dim)")
@@ -733,9 +802,6 @@ class DeviceIndex:
         if qv.ndim != 3 or int(qv.shape[0]) != B or int(qv.shape[2]) != self.dim:
             raise ValueError("query_vecs must be (n_queries, nq, dim)")
         nq = int(qv.shape[1])
-        o_s, p_s = a.out((B, int(k)), np.float32)
-        o_c, p_c = a.out((B, int(k)), np.int32)
-        o_n, p_n = a.out((B,), np.int32)
         if query_filters is None and (rank_limit is None or np.ndim(rank_limit) == 0):  # (one filter for the batch: every query maps to it)
             query_filters = None if chunk_filter is None else [chunk_filter] * B
             chunk_filter = None
@@ -759,11 +825,53 @@ class DeviceIndex:
             else:
                 p_off, p_terms = q_off.ctypes.data, q_terms.ctypes.data
             a.keep += [q_off, q_terms]
+        return p_q, B, p_v, nq, p_off, p_terms, args, w
+
+    def search_rerank(self, queries, num_hits: int, n_each: int, n_cand: int, query_vecs, k: int, *,
+                      keyword: "KeywordIndex | None" = None, query_term_ids=None, weights=(0.75, 0.25), rrf_k: int = 60, chunk_filter=None,
+                      rank_limit=None, query_filters=None):
+        """`rl_search_rerank_per_query`: `hybrid_search(queries, num_hits, n_each, k=n_cand, ...)`, then `maxsim_rerank` of each query's
+        fused candidates against `query_vecs` (B, nq, dim), then `rerank_order`'s first k, all on one stream with nothing read back in
+        between.  Returns (MaxSim scores (B, k) float32, chunk ordinals (B, k) int32 best first, counts (B,) int32).  Without
+        `keyword` the candidates are the vector search's list alone.  The filter arguments are `hybrid_search`'s."""
+        a = _Args()
+        p_q, B, p_v, nq, p_off, p_terms, args, w = self._search_rerank_args(a, queries, query_vecs, keyword, query_term_ids, weights,
+                                                                            chunk_filter, rank_limit, query_filters)
+        o_s, p_s = a.out((B, int(k)), np.float32)
+        o_c, p_c = a.out((B, int(k)), np.int32)
+        o_n, p_n = a.out((B,), np.int32)
         self._prep(a)
         check(lib().rl_search_rerank_per_query(self._handle, None if keyword is None else keyword._handle, p_q, B, int(num_hits), int(n_each),
                                                p_off, p_terms, *args, w.ctypes.data, int(rrf_k), int(n_cand), p_v, nq, int(k), p_s, p_c,
                                                p_n, a.mem, a.stream))
         return o_s, o_c, o_n
+
+    def search_rerank_spans(self, queries, num_hits: int, n_each: int, n_cand: int, query_vecs, k: int, spans: "SpanTable",
+                            neighbors=(-1, 1), *, keyword: "KeywordIndex | None" = None, query_term_ids=None, weights=(0.75, 0.25),
+                            rrf_k: int = 60, chunk_filter=None, rank_limit=None, query_filters=None):
+        """`rl_search_rerank_spans_per_query`: `search_rerank`'s pipeline, then `spans.chunk_spans` of each query's reranked first k on
+        the same stream, nothing read back in between.  Returns (top chunk ordinals (B, k) int32, their counts (B,) int32) followed by
+        `SpanTable.chunk_spans`'s five results with n_in = k."""
+        offs = _span_offsets(neighbors)
+        E = int(k) * (1 + int(offs.size))
+        if int(k) < 1 or E > SPANS_MAX_ENTRIES:
+            raise ValueError(f"search_rerank_spans: need k >= 1 and k * (1 + len(neighbors)) <= {SPANS_MAX_ENTRIES}")
+        a = _Args()
+        p_q, B, p_v, nq, p_off, p_terms, args, w = self._search_rerank_args(a, queries, query_vecs, keyword, query_term_ids, weights,
+                                                                            chunk_filter, rank_limit, query_filters)
+        o_tc, p_tc = a.out((B, int(k)), np.int32)
+        o_tn, p_tn = a.out((B,), np.int32)
+        o_c, p_oc = a.out((B, E), np.int32)
+        o_l, p_ol = a.out((B, E), np.int32)
+        o_s, p_os = a.out((B, E), np.float64)
+        o_ns, p_ns = a.out((B,), np.int32)
+        o_nc, p_nc = a.out((B,), np.int32)
+        self._prep(a)
+        check(lib().rl_search_rerank_spans_per_query(self._handle, None if keyword is None else keyword._handle, p_q, B, int(num_hits),
+                                                     int(n_each), p_off, p_terms, *args, w.ctypes.data, int(rrf_k), int(n_cand), p_v, nq,
+                                                     int(k), spans._handle, offs.ctypes.data if offs.size else None, int(offs.size), p_tc,
+                                                     p_tn, p_oc, p_ol, p_os, p_ns, p_nc, a.mem, a.stream))
+        return o_tc, o_tn, o_c, o_l, o_s, o_ns, o_nc
 
     # -- a9 ----------------------------------------------------------------------------------------
     def maxsim_scores(self, query_vecs):

@@ -13,6 +13,12 @@
     search_and_rerank_chunks_batch(queries, ...) -> list of search_and_rerank_chunks's results: search, fusion, MaxSim rerank and
                                                     ordering of the whole batch in one device call
     rerank_chunks_batch(queries, chunk_ids_per_query, ...) -> the MaxSim rerank of given lists, one launch per distinct nq
+    retrieve_chunk_spans(chunk_ids, *, neighbors=(-1, 1), config=None) -> list[ChunkSpan]      (`_search.py:302-361`)
+    retrieve_chunk_spans_batch(chunk_ids_per_query, ...) -> the same for ragged lists, one device call
+    search_and_rerank_chunk_spans(...)                                    (`_search.py:417-433`)
+    search_and_rerank_chunk_spans_batch(queries, ...) -> search, fusion, MaxSim rerank, ordering and spans of the whole batch in one
+                                                        device call
+    retrieve_context(query, *, config=None) -> list[ChunkSpan]            (`_rag.py:43-64`)
     GpuVectorSearch   -- a `BasicSearchMethod` (`_typing.py:35-43`) for `RAGLiteConfig.search_method`
     MaxSimRanker      -- a duck-typed `rerankers.BaseRanker` for `RAGLiteConfig.reranker`
                          (`.rank(query=, docs=)` -> `.results[*].doc_id`, `_search.py:394-396`)
@@ -25,6 +31,7 @@ store, ORM and HNSW index are out of scope.
 from __future__ import annotations
 
 from dataclasses import dataclass, field
+from functools import partial
 from typing import Any, Callable, Sequence
 
 import numpy as np
@@ -51,6 +58,9 @@ class GpuIndex:
     exact_fp32       multiply with exact fp32 MFMAs instead of the default fp16 (hi, lo) split of fp32 operands
     keyword_texts    optional list[str] -- `Chunk.body` per chunk: builds the BM25 keyword side (`keyword_search`, the keyword
                      half of `hybrid_search`; DESIGN.md "Keyword search"), rebuilt from the live chunks after every change
+    positions        optional list of (document_id: str, index: int) -- `Chunk.document_id` / `Chunk.index` per chunk
+                     (`_database.py:207-224`; None: the chunk has no position): builds the span table (`retrieve_chunk_spans`;
+                     DESIGN.md 4.11), rebuilt from the live chunks after every change
     """
 
     # keyword side (class defaults: an index without one): each chunk's index stems (None once deleted), the vocabulary and the device
@@ -58,11 +68,14 @@ class GpuIndex:
     keyword: _ops.KeywordIndex | None = None
     _kw_stems: list[list[str] | None] | None = None
     _kw_vocab: dict[str, int] = {}
+    # span side (class defaults: an index without one): each chunk's (document_id, index) (None once deleted) and the device table
+    positions: list | None = None
+    spans: _ops.SpanTable | None = None
 
     def __init__(self, chunk_ids: Sequence[ChunkId], chunk_embeddings, *, chunk_offsets=None,
                  metric: str = "cosine", query_adapter=None, docs: Sequence[str] | None = None,
                  metadata: Sequence[dict] | None = None, storage: str = "f32", exact_fp32: bool = False,
-                 keyword_texts: Sequence[str] | None = None) -> None:
+                 keyword_texts: Sequence[str] | None = None, positions: Sequence[tuple[str, int] | None] | None = None) -> None:
         if chunk_offsets is None:
             mats = [np.asarray(m, dtype=np.float32).reshape(len(m), -1) for m in chunk_embeddings]
             sizes = np.asarray([len(m) for m in mats], dtype=np.int64)
@@ -88,10 +101,41 @@ class GpuIndex:
                 raise ValueError("one keyword text per chunk is required")
             self._kw_stems = [_keyword.index_stems(t) for t in keyword_texts]
             self._rebuild_keywords()
+        if positions is not None:
+            if len(positions) != len(self.chunk_ids):
+                raise ValueError("one (document_id, index) position per chunk is required")
+            self._rebuild_spans(list(positions))
 
     @property
     def has_keywords(self) -> bool:
         return self._kw_stems is not None
+
+    @property
+    def has_positions(self) -> bool:
+        return self.positions is not None
+
+    def _rebuild_spans(self, positions: list) -> None:
+        """The span table of `positions` (one per chunk ordinal; None: no position): documents are numbered in sorted(document_id)
+        order, Python's string comparison, which is what the reference's `sorted(..., key=(document_id, index))` compares
+        (`_search.py:342`).  Built before the old table goes, and `self.positions` changes only then: a failure leaves the index as
+        it was."""
+        self._check_positions(positions)
+        doc_no = {d: i for i, d in enumerate(sorted({p[0] for p in positions if p is not None}))}
+        doc = np.full(len(positions), -1, dtype=np.int32)
+        pos = np.zeros(len(positions), dtype=np.int32)
+        for o, p in enumerate(positions):
+            if p is not None:
+                doc[o], pos[o] = doc_no[p[0]], int(p[1])
+        new = _ops.SpanTable(doc, pos)
+        if self.spans is not None:
+            self.spans.close()
+        self.spans, self.positions = new, positions
+
+    def span_table(self) -> "_ops.SpanTable":
+        if self.spans is None:
+            raise ValueError("GpuIndex was built without `positions`: pass positions= (one (document_id, index) per chunk) or use "
+                             "from_store(); chunk spans need them")
+        return self.spans
 
     def _rebuild_keywords(self) -> None:
         """The reference rebuilds its FTS index after every insert and delete (`_insert.py:268`, `_delete.py:173`): N, avgdl and df
@@ -116,10 +160,11 @@ class GpuIndex:
 
     # -- lifecycle -------------------------------------------------------------------------
     def insert_chunks(self, chunk_ids: Sequence[ChunkId], chunk_embeddings, *, docs: Sequence[str] | None = None,
-                      metadata: Sequence[dict] | None = None, keyword_texts: Sequence[str] | None = None) -> None:
+                      metadata: Sequence[dict] | None = None, keyword_texts: Sequence[str] | None = None,
+                      positions: Sequence[tuple[str, int] | None] | None = None) -> None:
         """`insert_documents` on the device image (`src/raglite/_insert.py:247-272`): append the chunks'
         embedding matrices; existing ordinals keep their meaning.  `keyword_texts` (the chunks' bodies) iff the index has a
-        keyword side."""
+        keyword side; `positions` iff it was built with them."""
         mats = [np.asarray(m, dtype=np.float32).reshape(len(m), -1) for m in chunk_embeddings]
         if len(mats) != len(chunk_ids):
             raise ValueError("one embedding matrix per chunk id is required")
@@ -131,8 +176,14 @@ class GpuIndex:
             raise ValueError("keyword_texts must be given iff the index was built with them")
         if keyword_texts is not None and len(keyword_texts) != len(chunk_ids):
             raise ValueError("one keyword text per chunk id is required")
+        if self.has_positions != (positions is not None):
+            raise ValueError("positions must be given iff the index was built with them")
+        if positions is not None and len(positions) != len(chunk_ids):
+            raise ValueError("one (document_id, index) position per chunk id is required")
         if not mats:
             return
+        if positions is not None:  # (checked before the index changes: two live chunks at one position raise here)
+            self._check_positions(self.positions + list(positions))
         self.index.append(np.vstack(mats), np.asarray([len(m) for m in mats], dtype=np.int64))
         base = len(self.chunk_ids)
         self.chunk_ids.extend(chunk_ids)
@@ -145,6 +196,19 @@ class GpuIndex:
         if keyword_texts is not None:
             self._kw_stems.extend(_keyword.index_stems(t) for t in keyword_texts)
             self._rebuild_keywords()
+        if positions is not None:
+            self._rebuild_spans(self.positions + list(positions))
+
+    @staticmethod
+    def _check_positions(positions: list) -> None:
+        """Every position is None or (document_id: str, index: int in [0, 2^31)), and no two live chunks share one."""
+        live = [(p[0], int(p[1])) for p in positions if p is not None]
+        if any(not isinstance(d, str) or not 0 <= i < (1 << 31) for d, i in live):
+            raise ValueError("positions: document_id must be a str and index an int in [0, 2^31)")
+        if len(set(live)) != len(live):
+            seen: set = set()
+            dup = next(p for p in live if p in seen or seen.add(p))
+            raise ValueError(f"positions: two live chunks are at (document_id={dup[0]!r}, index={dup[1]})")
 
     def delete_chunks(self, chunk_ids: Sequence[ChunkId]) -> int:
         """`delete_documents` on the device image (`src/raglite/_delete.py:148-176`): the chunks never match
@@ -156,6 +220,9 @@ class GpuIndex:
                 for o in ords:
                     self._kw_stems[o] = None
                 self._rebuild_keywords()
+            if self.has_positions:
+                gone = set(ords)
+                self._rebuild_spans([None if o in gone else p for o, p in enumerate(self.positions)])
         return len(ords)
 
     # -- the real store ----------------------------------------------------------------------
@@ -180,7 +247,8 @@ class GpuIndex:
             raise ValueError("First run `insert_documents()` to insert documents.")  # the reference's wording for an empty store
         off = np.concatenate(([0], np.cumsum(np.asarray(img.sizes, dtype=np.int64)))).astype(np.int64)
         gi = cls(img.chunk_ids, img.matrix(), chunk_offsets=off, metric=metric, query_adapter=adapter, docs=img.docs,
-                 metadata=img.metadata, storage=storage, exact_fp32=exact_fp32, keyword_texts=img.bodies if keywords else None)
+                 metadata=img.metadata, storage=storage, exact_fp32=exact_fp32, keyword_texts=img.bodies if keywords else None,
+                 positions=img.positions)
         gi._bind = bind  # noqa: SLF001
         return gi
 
@@ -212,7 +280,8 @@ class GpuIndex:
                 at += size
             self.insert_chunks(img.chunk_ids, mats, docs=img.docs if self.docs is not None else None,
                                metadata=img.metadata if self.metadata is not None else None,
-                               keyword_texts=img.bodies if self.has_keywords else None)
+                               keyword_texts=img.bodies if self.has_keywords else None,
+                               positions=img.positions if self.has_positions else None)
         live_rows, _ = self.index.live()
         if self.index.n_rows and 1.0 - live_rows / self.index.n_rows > compact_above:
             self.compact()
@@ -234,11 +303,15 @@ class GpuIndex:
         if self.has_keywords:
             self._kw_stems = [self._kw_stems[i] for i in keep]
             self._rebuild_keywords()
+        if self.has_positions:
+            self._rebuild_spans([self.positions[i] for i in keep])
 
     def close(self) -> None:
         self.index.close()
         if self.keyword is not None:
             self.keyword.close()
+        if self.spans is not None:
+            self.spans.close()
 
 
 # config (hashable, like the reference's lru_cache keys) -> GpuIndex
@@ -985,8 +1058,10 @@ def _ids_of(gi: GpuIndex, out: list, group: Sequence[int], chunks, counts) -> No
         out[b] = [gi.chunk_ids[c] for c in chunks[i, : int(counts[i])].tolist()]
 
 
-def _hybrid_rerank_device(gi, cfg, ranker, queries, num_results, n_cand, metadata_filter, query_vectors, query_token_vectors) -> list:
-    """The device path of search_and_rerank_chunks_batch over hybrid_search: its host decisions are hybrid_search_batch's."""
+def _hybrid_rerank_device(gi, cfg, ranker, queries, num_results, n_cand, metadata_filter, query_vectors, query_token_vectors,
+                          spans: "_SpanRequest | None" = None) -> list:
+    """The device path of search_and_rerank_chunks_batch over hybrid_search: its host decisions are hybrid_search_batch's.  With
+    `spans` each group's call is the span pipeline and the result is every query's spans."""
     B = len(queries)
     hp = _plan_hybrid_batch(gi, cfg, queries, n_cand, 2, metadata_filter, query_vectors)  # (hybrid_search's own oversample: 2)
     out: list = [[] for _ in range(B)]
@@ -998,6 +1073,12 @@ def _hybrid_rerank_device(gi, cfg, ranker, queries, num_results, n_cand, metadat
         qf, lim = _device_filters(hp.plan, group)
         V = np.stack([vecs[b] for b in group])
         terms = None if hp.term_ids is None else [hp.term_ids[b] for b in group]
+        if hp.vector and spans is not None:
+            res = gi.index.search_rerank_spans(hp.Q[group], hp.num_hits, hp.n_each, hp.k, V, k, spans.table, spans.neighbors,
+                                               keyword=gi.keyword if hp.keyword else None, query_term_ids=terms, weights=(0.75, 0.25),
+                                               rrf_k=RRF_K, query_filters=qf, rank_limit=lim)
+            _spans_of(gi, out, group, *res[2:6])
+            continue
         if hp.vector:
             _, chunks, counts = gi.index.search_rerank(hp.Q[group], hp.num_hits, hp.n_each, hp.k, V, k, keyword=gi.keyword if hp.keyword else None,
                                                        query_term_ids=terms, weights=(0.75, 0.25), rrf_k=RRF_K, query_filters=qf,
@@ -1006,13 +1087,17 @@ def _hybrid_rerank_device(gi, cfg, ranker, queries, num_results, n_cand, metadat
             _, kw_chunks, _ = gi.keyword.search(terms, hp.n_each, query_filters=qf)
             _, fused, _ = _ops.rrf_fuse(kw_chunks[None], [0.25], rrf_k=RRF_K, k=hp.k)
             _, chunks, _, counts = _ops.rerank_order(gi.index.maxsim_rerank(V, fused), fused, k)
-        _ids_of(gi, out, group, chunks, counts)
+        if spans is not None:  # (the ordered list is padded with -1 past its count)
+            _spans_of(gi, out, group, *spans.table.chunk_spans(chunks, spans.neighbors)[:4])
+        else:
+            _ids_of(gi, out, group, chunks, counts)
     return out
 
 
-def _vector_rerank_device(gi, cfg, ranker, queries, num_results, n_cand, metadata_filter, query_vectors, query_token_vectors) -> list:
+def _vector_rerank_device(gi, cfg, ranker, queries, num_results, n_cand, metadata_filter, query_vectors, query_token_vectors,
+                          spans: "_SpanRequest | None" = None) -> list:
     """The device path over vector_search: its host decisions are vector_search_batch's; the pipeline call without a keyword index
-    fuses the vector list alone, which keeps its order."""
+    fuses the vector list alone, which keeps its order.  `spans` as in _hybrid_rerank_device."""
     B = len(queries)
     Q, num_hits, plan, active = _plan_vector_batch(gi, cfg, queries, n_cand, VECTOR_SEARCH_OVERSAMPLE, metadata_filter, query_vectors)
     out: list = [[] for _ in range(B)]
@@ -1024,7 +1109,161 @@ def _vector_rerank_device(gi, cfg, ranker, queries, num_results, n_cand, metadat
     for group in _groups_by_nq(vecs):
         members = [active[i] for i in group]
         qf, lim = _device_filters(plan, members)
+        if spans is not None:
+            res = gi.index.search_rerank_spans(Q[members], num_hits, n_cand, n_cand, np.stack([vecs[i] for i in group]), k, spans.table,
+                                               spans.neighbors, weights=(1.0,), rrf_k=RRF_K, query_filters=qf, rank_limit=lim)
+            _spans_of(gi, out, members, *res[2:6])
+            continue
         _, chunks, counts = gi.index.search_rerank(Q[members], num_hits, n_cand, n_cand, np.stack([vecs[i] for i in group]), k, weights=(1.0,),
                                                    rrf_k=RRF_K, query_filters=qf, rank_limit=lim)
         _ids_of(gi, out, members, chunks, counts)
     return out
+
+
+# ---- chunk spans ---------------------------------------------------------------------------------------
+@dataclass
+class ChunkSpan:
+    """A run of consecutive chunks of one document (the reference's `ChunkSpan`, `_database.py`, without its ORM objects):
+    the chunks' ids in ascending `Chunk.index`, their document's id, and the span's score -- the sum of its chunks' reciprocal
+    ranks, which is what `retrieve_chunk_spans` orders the spans by (`_search.py:355-360`)."""
+
+    chunk_ids: list[ChunkId]
+    document_id: str
+    score: float
+
+
+@dataclass
+class _SpanRequest:
+    table: Any      # _ops.SpanTable
+    neighbors: Any  # the offsets as given: a tuple of ints, () or None
+
+
+def _spans_of(gi: GpuIndex, out: list, group: Sequence[int], chunks, span_len, span_scores, n_spans) -> None:
+    """The spans of each query of a device call, from rl_chunk_spans' outputs (host arrays; turned into lists once: per-row NumPy
+    slicing would cost more than the device call)."""
+    rows, lens, scores, counts = chunks.tolist(), span_len.tolist(), span_scores.tolist(), n_spans.tolist()
+    ids, positions = gi.chunk_ids, gi.positions
+    for i, b in enumerate(group):
+        row, at, spans = rows[i], 0, []
+        for s in range(counts[i]):
+            ords = row[at : at + lens[i][s]]
+            at += lens[i][s]
+            spans.append(ChunkSpan([ids[c] for c in ords], positions[ords[0]][0], scores[i][s]))
+        out[b] = spans
+
+
+def retrieve_chunk_spans_batch(chunk_ids_per_query: Sequence[Sequence[Any]], *, neighbors: Sequence[int] | None = (-1, 1),
+                               config: Any | None = None, index: GpuIndex | None = None) -> list[list[ChunkSpan]]:
+    """`retrieve_chunk_spans` for a batch of (ragged) lists: element b is `retrieve_chunk_spans(chunk_ids_per_query[b], ...)`, from one
+    device call (`rl_chunk_spans`; short lists are padded with -1, which takes no rank)."""
+    gi = index or _index_for(config)
+    lists = [list(ids) for ids in chunk_ids_per_query]
+    out: list = [[] for _ in lists]
+    if not any(lists):
+        return out
+    table = gi.span_table()
+    ordinals = []
+    for ids in lists:
+        if all(isinstance(c, ChunkId) for c in ids):
+            # ids: `retrieve_chunks` (`_search.py:282-299`) returns each stored chunk once, in the order of its first occurrence
+            ordinals.append([gi._id_to_ordinal[c] for c in dict.fromkeys(ids) if c in gi._id_to_ordinal])  # noqa: SLF001
+        else:
+            # chunk objects are taken as they come (`:321`): of one that comes twice the last rank stands (`:324`)
+            ordinals.append([gi._id_to_ordinal.get(getattr(c, "id", c), -1) for c in ids])  # noqa: SLF001
+    n_in = max(len(o) for o in ordinals)
+    if n_in == 0:
+        return out
+    chunks = np.full((len(lists), n_in), -1, dtype=np.int32)
+    for b, o in enumerate(ordinals):
+        chunks[b, : len(o)] = o
+    _spans_of(gi, out, range(len(lists)), *table.chunk_spans(chunks, neighbors)[:4])
+    return out
+
+
+def retrieve_chunk_spans(chunk_ids: Sequence[Any], *, neighbors: Sequence[int] | None = (-1, 1), config: Any | None = None,
+                         index: GpuIndex | None = None) -> list[ChunkSpan]:
+    """Group chunks into spans of consecutive chunks and order the spans by the summed reciprocal ranks of their chunks
+    (`src/raglite/_search.py:302-361`), on the device (`rl_chunk_spans`).  `chunk_ids`: chunk ids, best first -- de-duplicated to
+    their first occurrence, unknown ids dropped, as the reference's `retrieve_chunks` does -- or chunk objects with an `.id`.
+    `neighbors`: the offsets in `Chunk.index` of the chunks to add (None or (): none).  Chunks that have no embedding are not in the
+    index and so are never neighbours here."""
+    if not chunk_ids:
+        return []
+    return retrieve_chunk_spans_batch([chunk_ids], neighbors=neighbors, config=config, index=index)[0]
+
+
+@dataclass
+class _ChunkRef:
+    """What a reranker outside the device path sees of a chunk: `str()` is its text; `.id` leads back to it."""
+
+    id: ChunkId
+    text: str
+
+    def __str__(self) -> str:
+        return self.text
+
+
+def _ref_lookup(gi: GpuIndex) -> Callable[[Sequence[ChunkId]], list[Any]]:
+    return lambda ids: [_ChunkRef(c, gi.docs[gi.ordinal_of(c)] if gi.docs is not None else c) for c in ids]
+
+
+def search_and_rerank_chunk_spans(query: str, *, num_results: int = 8, oversample: int = 4, neighbors: Sequence[int] | None = (-1, 1),
+                                  search: Callable[..., tuple[list[ChunkId], list[float]]] = hybrid_search, config: Any | None = None,
+                                  metadata_filter: dict | None = None, index: GpuIndex | None = None) -> list[ChunkSpan]:
+    """`src/raglite/_search.py:417-433`: search, rerank, keep the best `num_results`, collate them into chunk spans."""
+    gi = index or _index_for(config)
+    gi.span_table()
+    if index is not None:  # (the search looks its index up by config unless told)
+        search = partial(search, index=index)
+    chunks = search_and_rerank_chunks(query, num_results=num_results, oversample=oversample, search=search, config=config,
+                                      metadata_filter=metadata_filter, chunk_lookup=_ref_lookup(gi))
+    return retrieve_chunk_spans(chunks, neighbors=neighbors, config=config, index=gi)
+
+
+def search_and_rerank_chunk_spans_batch(queries: Sequence[str], *, num_results: int = 8, oversample: int = 4,
+                                        neighbors: Sequence[int] | None = (-1, 1), search: Any = "hybrid", config: Any | None = None,
+                                        metadata_filter=None, index: GpuIndex | None = None, query_vectors=None,
+                                        query_token_vectors=None) -> list[list[ChunkSpan]]:
+    """`search_and_rerank_chunk_spans` for a batch: element b is what `search_and_rerank_chunk_spans(queries[b], search=hybrid_search |
+    vector_search, metadata_filter=<its filter>, ...)` returns with the same arguments.  The planning, the grouping by query length,
+    the filters and the fallbacks are `search_and_rerank_chunks_batch`'s.  With `config.reranker` a `MaxSimRanker` over the searched
+    index, everything from the searches to the ordered spans runs on one stream in one device call per distinct query length
+    (`rl_search_rerank_spans_per_query`) and is read back once.  Otherwise the batched search runs, then the rerank path of
+    `search_and_rerank_chunks_batch`, then one `rl_chunk_spans` for the batch."""
+    cfg = config or HotPathConfig()
+    gi = index or _index_for(config)
+    queries = list(queries)
+    if search not in _SEARCHES:
+        raise ValueError("search must be 'hybrid' or 'vector'")
+    if not queries:
+        return []
+    request = _SpanRequest(gi.span_table(), neighbors)
+    ranker = _device_ranker(cfg, gi)
+    if ranker is None:
+        found = search_and_rerank_chunks_batch(queries, num_results=num_results, oversample=oversample, search=search, config=cfg,
+                                               metadata_filter=metadata_filter, index=gi, query_vectors=query_vectors,
+                                               chunk_lookup=_ref_lookup(gi))
+        return retrieve_chunk_spans_batch([[c.id for c in chunks] for chunks in found], neighbors=neighbors, index=gi)
+    device = _hybrid_rerank_device if _SEARCHES[search] == "hybrid" else _vector_rerank_device
+    return device(gi, cfg, ranker, queries, num_results, oversample * num_results, metadata_filter, query_vectors, query_token_vectors,
+                  spans=request)
+
+
+def retrieve_context(query: str, *, num_chunks: int = 10, metadata_filter: dict | None = None, config: Any | None = None,
+                     index: GpuIndex | None = None) -> list[ChunkSpan]:
+    """Retrieve context for RAG (`src/raglite/_rag.py:43-64`): call `config.search_method` and turn what it returns into chunk spans
+    as `:57-63` does -- an (ids, scores) tuple and a list of chunk ids (or of chunk objects with an `.id`) go through
+    `retrieve_chunk_spans`, a list of `ChunkSpan` is returned as it is, anything else gives no spans."""
+    cfg = config or HotPathConfig()
+    search_method = getattr(cfg, "search_method", None)
+    if search_method is None:
+        raise ValueError("retrieve_context needs config.search_method (e.g. GpuVectorSearch, or a function returning chunk spans)")
+    results = search_method(query, num_results=num_chunks, metadata_filter=metadata_filter, config=config)
+    if isinstance(results, tuple):
+        return retrieve_chunk_spans(results[0], config=config, index=index)
+    results = list(results)
+    if all(isinstance(r, ChunkSpan) for r in results):
+        return results
+    if all(isinstance(r, ChunkId) or hasattr(r, "id") for r in results):
+        return retrieve_chunk_spans(results, config=config, index=index)
+    return []

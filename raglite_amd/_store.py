@@ -80,6 +80,7 @@ class StoreImage:
     metadata: list[dict] = field(default_factory=list)
     query_adapter: np.ndarray | None = None
     bodies: list[str] = field(default_factory=list)           # `chunk.body`: what the keyword index analyses (`_database.py:618`)
+    positions: list[tuple[str, int] | None] = field(default_factory=list)  # (`Chunk.document_id`, `Chunk.index`) (`_database.py:207-224`)
 
     def matrix(self) -> np.ndarray:
         return np.vstack(self.rows).astype(np.float32, copy=False) if self.rows else np.zeros((0, 1), np.float32)
@@ -108,9 +109,10 @@ def read_chunks(conn, only_chunk_ids: Sequence[str] | None = None) -> StoreImage
             img.sizes[-1] += 1
             img.rows.append(decode_embedding(value))
         meta = {}
-        rows = conn.execute(sa.text(f'SELECT id, headings, body, metadata FROM chunk {where.replace("chunk_id", "id")}'), params)
-        for cid, headings, body, md in rows:
-            meta[cid] = (headings, body, _as_dict(md))
+        rows = conn.execute(sa.text(f'SELECT id, headings, body, metadata, document_id, "index" FROM chunk {where.replace("chunk_id", "id")}'),
+                            params)
+        for cid, headings, body, md, document_id, index in rows:
+            meta[cid] = (headings, body, _as_dict(md), document_id, index)
         return meta
 
     if only_chunk_ids is None:
@@ -121,10 +123,12 @@ def read_chunks(conn, only_chunk_ids: Sequence[str] | None = None) -> StoreImage
             names = {f"c{i}": cid for i, cid in enumerate(batch)}
             meta.update(fetch("WHERE chunk_id IN (" + ", ".join(f":{n}" for n in names) + ")", names))
     for cid in img.chunk_ids:
-        headings, body, md = meta.get(cid, ("", "", {}))
+        headings, body, md, document_id, index = meta.get(cid, ("", "", {}, None, None))
         img.docs.append(chunk_text(headings, body, md))
         img.bodies.append(body or "")
         img.metadata.append(md)
+        # (an embedding row without its chunk row, or a chunk without an index, has no position: it is in no span)
+        img.positions.append(None if document_id is None or index is None else (str(document_id), int(index)))
     return img
 
 

@@ -3525,6 +3525,110 @@ int rl_rerank_order(const float* scores, const int32_t* candidates, int32_t n_qu
     return finish(mem, s);
 }
 
+}  // extern "C"
+
+// ---- chunk spans (include/raglite_hip.h; the kernel is in spans.hip) -------------------------------------------------------------------
+// Immutable after rl_span_table_create: calls on any stream may share it without a lock.
+struct rl_span_table {
+    int64_t n_chunks = 0;
+    int64_t n_live = 0;                 // chunks with a position
+    rl::DevArray<int32_t> rank_of;      // [n_chunks] the chunk's rank in (doc, pos) order, -1: no position
+    rl::DevArray<uint64_t> tab_key;     // [n_live] doc << 32 | pos, ascending
+    rl::DevArray<int32_t> tab_ord;      // [n_live] the chunk ordinal at that rank
+};
+
+namespace {
+// What rl_search_rerank_per_query and rl_search_rerank_spans_per_query need before their device work: hybrid_search_begin's, and the
+// query token vectors staged.
+struct RerankCall {
+    HybridCall c;
+    DevBuf t_v;
+    const float* d_v = nullptr;
+};
+
+// The checks of rl_search_rerank_per_query, the locks and the staging-in
+int search_rerank_begin(rl_index* idx, rl_keyword_index* kw, const float* queries, int32_t B, int32_t num_hits, int32_t n_each,
+                        const int64_t* q_off, const int32_t* q_terms, const uint32_t* chunk_filters, int32_t n_filters,
+                        const int32_t* query_filter, const int64_t* rank_limits, const double* weights, int32_t rrf_k, int32_t n_cand,
+                        const float* query_vecs, int32_t nq, int32_t k, bool outputs, int mem, hipStream_t s, const char* who, RerankCall* rc) {
+    if (nq < 1) return fail(RL_ERR_INVALID, std::string(who) + ": nq must be >= 1");
+    if (n_cand < 1 || n_cand > RERANK_MAX_ENTRIES) return fail(RL_ERR_INVALID, std::string(who) + ": n_cand must be in [1, 4096]");
+    if (k < 1 || k > n_cand) return fail(RL_ERR_INVALID, std::string(who) + ": k must be in [1, n_cand]");
+    RL_TRY(check_query_filters(B, chunk_filters, n_filters, query_filter, rank_limits, who));
+    if (idx && idx->E16 && (nq > 32 || idx->dim % 16))
+        return fail(RL_ERR_UNSUPPORTED, std::string(who) + ": MaxSim reranking on an fp16-stored index needs nq <= 32 and dim % 16 == 0");
+    RL_TRY(hybrid_search_begin(idx, kw, queries, B, num_hits, n_each, q_off, q_terms, chunk_filters, query_filter ? n_filters : 0, query_filter,
+                               rank_limits, 0, weights, rrf_k, n_cand, query_vecs && outputs, mem, s, who, &rc->c));
+    if (rc->c.empty) return RL_OK;
+    return stage_in(query_vecs, (size_t)B * nq * idx->dim, mem, s, rc->t_v, &rc->d_v);
+}
+
+// The searches, the fusion, the MaxSim rerank and the ordering on device pointers (after search_rerank_begin): d_c [B x k], d_n [B];
+// d_s [B x k], or nullptr: the scores stay in the index's scratch
+int search_rerank_device(rl_index* idx, rl_keyword_index* kw, const RerankCall& rc, int32_t B, int32_t num_hits, int32_t n_each,
+                         const double* weights, int32_t rrf_k, int32_t n_cand, int32_t nq, int32_t k, float* d_s, int32_t* d_c, int32_t* d_n,
+                         hipStream_t s) {
+    const size_t n_list = (size_t)B * n_cand, n_out = (size_t)B * k;
+    // index-owned scratch: the fused scores [B x n_cand] f64 (written, not read), the fused candidates [B x n_cand] int32, their
+    // MaxSim scores [B x n_cand] f32, the fusion's counts [B] and the positions of the first k [B x k] int32 (written, not read);
+    // without d_s the scores of the first k [B x k] f32 (written, not read)
+    RL_TRY(idx->rerank.reserve(n_list * 16 + (size_t)B * 4 + n_out * 4 + (d_s ? 0 : n_out * 4)));
+    double* fused_scores = idx->rerank.as<double>();
+    int32_t* fused = reinterpret_cast<int32_t*>(fused_scores + n_list);
+    float* maxsim = reinterpret_cast<float*>(fused + n_list);
+    int32_t* fused_counts = reinterpret_cast<int32_t*>(maxsim + n_list);
+    int32_t* pos = fused_counts + B;
+    if (!d_s) d_s = reinterpret_cast<float*>(pos + n_out);
+    RL_TRY(hybrid_search_device(idx, kw, rc.c, B, num_hits, n_each, weights, rrf_k, n_cand, fused_scores, fused, fused_counts, s));
+    RL_TRY(maxsim_rerank_device(idx, rc.d_v, B, nq, fused, n_cand, maxsim, s));
+    return launch_rerank_order(maxsim, fused, B, n_cand, k, d_s, d_c, pos, d_n, s);
+}
+
+// rl_chunk_spans' limits
+int check_span_args(const rl_span_table* table, int32_t n_queries, int32_t n_in, const int32_t* offsets, int32_t n_off, int mem,
+                    const char* who) {
+    if (!table) return fail(RL_ERR_INVALID, std::string(who) + ": null span table");
+    if (n_queries < 0) return fail(RL_ERR_INVALID, std::string(who) + ": n_queries must be >= 0");
+    if (n_off < 0 || n_off > SPANS_MAX_OFFSETS) return fail(RL_ERR_INVALID, std::string(who) + ": n_off must be in [0, 64]");
+    if (n_in < 1 || (int64_t)n_in * (1 + n_off) > SPANS_MAX_ENTRIES)
+        return fail(RL_ERR_INVALID, std::string(who) + ": need n_in >= 1 and n_in * (1 + n_off) <= 4096");
+    if (n_off > 0 && !offsets) return fail(RL_ERR_INVALID, std::string(who) + ": null offsets");
+    if (mem != RL_MEM_HOST && mem != RL_MEM_DEVICE) return fail(RL_ERR_INVALID, std::string(who) + ": bad mem");
+    return RL_OK;
+}
+
+// The five outputs of the span kernel for a batch, staged for host callers
+struct SpanOutputs {
+    DevBuf t_c, t_l, t_s, t_ns, t_nc;
+    int32_t *d_c = nullptr, *d_l = nullptr, *d_ns = nullptr, *d_nc = nullptr;
+    double* d_s = nullptr;
+    int begin(int32_t* out_chunks, int32_t* out_span_len, double* out_span_scores, int32_t* out_n_spans, int32_t* out_n_chunks, size_t n,
+              size_t B, int mem) {
+        RL_TRY(stage_out_begin(out_chunks, n, mem, t_c, &d_c));
+        RL_TRY(stage_out_begin(out_span_len, n, mem, t_l, &d_l));
+        RL_TRY(stage_out_begin(out_span_scores, n, mem, t_s, &d_s));
+        RL_TRY(stage_out_begin(out_n_spans, B, mem, t_ns, &d_ns));
+        return stage_out_begin(out_n_chunks, B, mem, t_nc, &d_nc);
+    }
+    int end(int32_t* out_chunks, int32_t* out_span_len, double* out_span_scores, int32_t* out_n_spans, int32_t* out_n_chunks, size_t n,
+            size_t B, int mem, hipStream_t s) {
+        RL_TRY(stage_out_end(out_chunks, n, mem, s, t_c));
+        RL_TRY(stage_out_end(out_span_len, n, mem, s, t_l));
+        RL_TRY(stage_out_end(out_span_scores, n, mem, s, t_s));
+        RL_TRY(stage_out_end(out_n_spans, B, mem, s, t_ns));
+        return stage_out_end(out_n_chunks, B, mem, s, t_nc);
+    }
+};
+
+int spans_device(const rl_span_table* t, const int32_t* d_in, int32_t B, int32_t n_in, const int32_t* offsets, int32_t n_off,
+                 const SpanOutputs& o, hipStream_t s) {
+    return launch_chunk_spans(t->rank_of, t->tab_key, t->tab_ord, (int32_t)t->n_chunks, (int32_t)t->n_live, d_in, B, n_in, offsets, n_off,
+                              o.d_c, o.d_l, o.d_s, o.d_ns, o.d_nc, s);
+}
+}  // namespace
+
+extern "C" {
+
 int rl_search_rerank_per_query(rl_index* idx, rl_keyword_index* kw, const float* queries, int32_t n_queries, int32_t num_hits, int32_t n_each,
                                const int64_t* q_off, const int32_t* q_terms, const uint32_t* chunk_filters, int32_t n_filters,
                                const int32_t* query_filter, const int64_t* rank_limits, const double* weights, int32_t rrf_k, int32_t n_cand,
@@ -3532,40 +3636,127 @@ int rl_search_rerank_per_query(rl_index* idx, rl_keyword_index* kw, const float*
                                int mem, void* stream) {
     const char* who = "rl_search_rerank_per_query";
     const int32_t B = n_queries;
-    if (nq < 1) return fail(RL_ERR_INVALID, std::string(who) + ": nq must be >= 1");
-    if (n_cand < 1 || n_cand > RERANK_MAX_ENTRIES) return fail(RL_ERR_INVALID, std::string(who) + ": n_cand must be in [1, 4096]");
-    if (k < 1 || k > n_cand) return fail(RL_ERR_INVALID, std::string(who) + ": k must be in [1, n_cand]");
-    RL_TRY(check_query_filters(B, chunk_filters, n_filters, query_filter, rank_limits, who));
-    if (idx && idx->E16 && (nq > 32 || idx->dim % 16))
-        return fail(RL_ERR_UNSUPPORTED, std::string(who) + ": MaxSim reranking on an fp16-stored index needs nq <= 32 and dim % 16 == 0");
     hipStream_t s = as_stream(stream);
-    HybridCall c;
-    RL_TRY(hybrid_search_begin(idx, kw, queries, B, num_hits, n_each, q_off, q_terms, chunk_filters, query_filter ? n_filters : 0, query_filter,
-                               rank_limits, 0, weights, rrf_k, n_cand, query_vecs && out_scores && out_chunks && out_counts, mem, s, who, &c));
-    if (c.empty) return RL_OK;
-    const size_t n_list = (size_t)B * n_cand, n_out = (size_t)B * k;
-    DevBuf t_v, t_s, t_c, t_n;
-    const float* d_v;
+    RerankCall rc;
+    RL_TRY(search_rerank_begin(idx, kw, queries, B, num_hits, n_each, q_off, q_terms, chunk_filters, n_filters, query_filter, rank_limits, weights,
+                               rrf_k, n_cand, query_vecs, nq, k, out_scores && out_chunks && out_counts, mem, s, who, &rc));
+    if (rc.c.empty) return RL_OK;
+    const size_t n_out = (size_t)B * k;
+    DevBuf t_s, t_c, t_n;
     float* d_s;
     int32_t *d_c, *d_n;
-    RL_TRY(stage_in(query_vecs, (size_t)B * nq * idx->dim, mem, s, t_v, &d_v));
     RL_TRY(stage_out_begin(out_scores, n_out, mem, t_s, &d_s));
     RL_TRY(stage_out_begin(out_chunks, n_out, mem, t_c, &d_c));
     RL_TRY(stage_out_begin(out_counts, (size_t)B, mem, t_n, &d_n));
-    // index-owned scratch: the fused scores [B x n_cand] f64 (written, not read), the fused candidates [B x n_cand] int32, their
-    // MaxSim scores [B x n_cand] f32, the fusion's counts [B] and the positions of the first k [B x k] int32 (written, not read)
-    RL_TRY(idx->rerank.reserve(n_list * 16 + (size_t)B * 4 + n_out * 4));
-    double* fused_scores = idx->rerank.as<double>();
-    int32_t* fused = reinterpret_cast<int32_t*>(fused_scores + n_list);
-    float* maxsim = reinterpret_cast<float*>(fused + n_list);
-    int32_t* fused_counts = reinterpret_cast<int32_t*>(maxsim + n_list);
-    int32_t* pos = fused_counts + B;
-    RL_TRY(hybrid_search_device(idx, kw, c, B, num_hits, n_each, weights, rrf_k, n_cand, fused_scores, fused, fused_counts, s));
-    RL_TRY(maxsim_rerank_device(idx, d_v, B, nq, fused, n_cand, maxsim, s));
-    RL_TRY(launch_rerank_order(maxsim, fused, B, n_cand, k, d_s, d_c, pos, d_n, s));
+    RL_TRY(search_rerank_device(idx, kw, rc, B, num_hits, n_each, weights, rrf_k, n_cand, nq, k, d_s, d_c, d_n, s));
     RL_TRY(stage_out_end(out_scores, n_out, mem, s, t_s));
     RL_TRY(stage_out_end(out_chunks, n_out, mem, s, t_c));
     RL_TRY(stage_out_end(out_counts, (size_t)B, mem, s, t_n));
+    return finish(mem, s);
+}
+
+int rl_span_table_create(rl_span_table** out, const int32_t* doc, const int32_t* pos, int64_t n_chunks) {
+    const char* who = "rl_span_table_create";
+    if (!out) return fail(RL_ERR_INVALID, std::string(who) + ": null output handle");
+    *out = nullptr;
+    if (n_chunks < 0) return fail(RL_ERR_INVALID, std::string(who) + ": negative size");
+    if (n_chunks >= (int64_t)0x7fffffff - 1) return fail(RL_ERR_UNSUPPORTED, std::string(who) + ": more than 2^31-2 chunks");
+    if (n_chunks > 0 && (!doc || !pos)) return fail(RL_ERR_INVALID, std::string(who) + ": null argument");
+    std::vector<std::pair<uint64_t, int32_t>> live;  // (doc << 32 | pos, ordinal)
+    for (int64_t c = 0; c < n_chunks; ++c) {
+        if (doc[c] < 0) continue;
+        if (pos[c] < 0) return fail(RL_ERR_INVALID, std::string(who) + ": pos must be >= 0");
+        live.emplace_back(((uint64_t)(uint32_t)doc[c] << 32) | (uint32_t)pos[c], (int32_t)c);
+    }
+    std::sort(live.begin(), live.end());
+    for (size_t r = 1; r < live.size(); ++r)
+        if (live[r].first == live[r - 1].first) return fail(RL_ERR_INVALID, std::string(who) + ": two chunks share a (doc, pos)");
+    std::vector<int32_t> rank_of((size_t)n_chunks, -1), tab_ord(live.size());
+    std::vector<uint64_t> tab_key(live.size());
+    for (size_t r = 0; r < live.size(); ++r) {
+        tab_key[r] = live[r].first;
+        tab_ord[r] = live[r].second;
+        rank_of[(size_t)live[r].second] = (int32_t)r;
+    }
+    std::unique_ptr<rl_span_table> t(new rl_span_table());
+    t->n_chunks = n_chunks;
+    t->n_live = (int64_t)live.size();
+    RL_TRY(t->rank_of.alloc(std::max<size_t>(rank_of.size() * sizeof(int32_t), 16), who));
+    RL_TRY(t->tab_key.alloc(std::max<size_t>(tab_key.size() * sizeof(uint64_t), 16), who));
+    RL_TRY(t->tab_ord.alloc(std::max<size_t>(tab_ord.size() * sizeof(int32_t), 16), who));
+    if (n_chunks) RL_HIP(hipMemcpy(t->rank_of, rank_of.data(), rank_of.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+    if (!live.empty()) {
+        RL_HIP(hipMemcpy(t->tab_key, tab_key.data(), tab_key.size() * sizeof(uint64_t), hipMemcpyHostToDevice));
+        RL_HIP(hipMemcpy(t->tab_ord, tab_ord.data(), tab_ord.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+    }
+    *out = t.release();
+    return RL_OK;
+}
+
+int rl_span_table_destroy(rl_span_table* table) {
+    if (!table) return RL_OK;
+    delete table;
+    return RL_OK;
+}
+
+int rl_span_table_info(const rl_span_table* table, int64_t* n_chunks, int64_t* n_live, int64_t* device_bytes) {
+    if (!table) return fail(RL_ERR_INVALID, "rl_span_table_info: null span table");
+    if (n_chunks) *n_chunks = table->n_chunks;
+    if (n_live) *n_live = table->n_live;
+    if (device_bytes) *device_bytes = (int64_t)(table->rank_of.cap + table->tab_key.cap + table->tab_ord.cap);
+    return RL_OK;
+}
+
+int rl_chunk_spans(const rl_span_table* table, const int32_t* chunks, int32_t n_queries, int32_t n_in, const int32_t* offsets, int32_t n_off,
+                   int32_t* out_chunks, int32_t* out_span_len, double* out_span_scores, int32_t* out_n_spans, int32_t* out_n_chunks, int mem,
+                   void* stream) {
+    const char* who = "rl_chunk_spans";
+    RL_TRY(check_span_args(table, n_queries, n_in, offsets, n_off, mem, who));
+    if (n_queries == 0) return RL_OK;
+    if (!chunks || !out_chunks || !out_span_len || !out_span_scores || !out_n_spans || !out_n_chunks)
+        return fail(RL_ERR_INVALID, std::string(who) + ": null argument");
+    hipStream_t s = as_stream(stream);
+    const size_t B = (size_t)n_queries, n_out = B * n_in * (1 + n_off);
+    DevBuf t_in;
+    const int32_t* d_in;
+    SpanOutputs o;
+    RL_TRY(stage_in(chunks, B * n_in, mem, s, t_in, &d_in));
+    RL_TRY(o.begin(out_chunks, out_span_len, out_span_scores, out_n_spans, out_n_chunks, n_out, B, mem));
+    RL_TRY(spans_device(table, d_in, n_queries, n_in, offsets, n_off, o, s));
+    RL_TRY(o.end(out_chunks, out_span_len, out_span_scores, out_n_spans, out_n_chunks, n_out, B, mem, s));
+    return finish(mem, s);
+}
+
+int rl_search_rerank_spans_per_query(rl_index* idx, rl_keyword_index* kw, const float* queries, int32_t n_queries, int32_t num_hits,
+                                     int32_t n_each, const int64_t* q_off, const int32_t* q_terms, const uint32_t* chunk_filters,
+                                     int32_t n_filters, const int32_t* query_filter, const int64_t* rank_limits, const double* weights,
+                                     int32_t rrf_k, int32_t n_cand, const float* query_vecs, int32_t nq, int32_t k, const rl_span_table* table,
+                                     const int32_t* offsets, int32_t n_off, int32_t* out_top_chunks, int32_t* out_top_counts,
+                                     int32_t* out_chunks, int32_t* out_span_len, double* out_span_scores, int32_t* out_n_spans,
+                                     int32_t* out_n_chunks, int mem, void* stream) {
+    const char* who = "rl_search_rerank_spans_per_query";
+    const int32_t B = n_queries;
+    RL_TRY(check_span_args(table, B, k, offsets, n_off, mem, who));  // (k * (1 + n_off) <= 4096)
+    if (idx && table->n_chunks != idx->n_chunks) return fail(RL_ERR_INVALID, std::string(who) + ": the span table covers another number of chunks");
+    hipStream_t s = as_stream(stream);
+    RerankCall rc;
+    RL_TRY(search_rerank_begin(idx, kw, queries, B, num_hits, n_each, q_off, q_terms, chunk_filters, n_filters, query_filter, rank_limits, weights,
+                               rrf_k, n_cand, query_vecs, nq, k,
+                               out_top_chunks && out_top_counts && out_chunks && out_span_len && out_span_scores && out_n_spans && out_n_chunks,
+                               mem, s, who, &rc));
+    if (rc.c.empty) return RL_OK;
+    const size_t n_top = (size_t)B * k, n_out = n_top * (1 + n_off);
+    DevBuf t_c, t_n;
+    int32_t *d_c, *d_n;
+    SpanOutputs o;
+    RL_TRY(stage_out_begin(out_top_chunks, n_top, mem, t_c, &d_c));
+    RL_TRY(stage_out_begin(out_top_counts, (size_t)B, mem, t_n, &d_n));
+    RL_TRY(o.begin(out_chunks, out_span_len, out_span_scores, out_n_spans, out_n_chunks, n_out, (size_t)B, mem));
+    RL_TRY(search_rerank_device(idx, kw, rc, B, num_hits, n_each, weights, rrf_k, n_cand, nq, k, nullptr, d_c, d_n, s));
+    RL_TRY(spans_device(table, d_c, B, k, offsets, n_off, o, s));
+    RL_TRY(stage_out_end(out_top_chunks, n_top, mem, s, t_c));
+    RL_TRY(stage_out_end(out_top_counts, (size_t)B, mem, s, t_n));
+    RL_TRY(o.end(out_chunks, out_span_len, out_span_scores, out_n_spans, out_n_chunks, n_out, (size_t)B, mem, s));
     return finish(mem, s);
 }
 

@@ -373,6 +373,16 @@ constexpr int32_t RERANK_MAX_ENTRIES = 4096;  // n_cand: one workgroup's LDS, as
 int launch_rerank_order(const float* scores, const int32_t* candidates, int32_t n_queries, int32_t n_cand, int32_t k, float* out_scores,
                         int32_t* out_chunks, int32_t* out_pos, int32_t* out_counts, hipStream_t s);
 
+// spans.hip: retrieve_chunk_spans on ordinals.  rank_of [n_chunks] (-1: no position), tab_key [n_live] = doc << 32 | pos ascending,
+// tab_ord [n_live]: the span table's device arrays; chunks [n_queries x n_in] best first; offsets: host, n_off of them.
+// E = n_in * (1 + n_off): out_chunks / out_span_len / out_span_scores [n_queries x E], out_n_spans / out_n_chunks [n_queries].
+constexpr int32_t SPANS_MAX_ENTRIES = 4096;  // E: one workgroup's LDS, as RERANK_MAX_ENTRIES
+constexpr int32_t SPANS_MAX_OFFSETS = 64;
+int launch_chunk_spans(const int32_t* rank_of, const uint64_t* tab_key, const int32_t* tab_ord, int32_t n_chunks, int32_t n_live,
+                       const int32_t* chunks, int32_t n_queries, int32_t n_in, const int32_t* offsets /* host */, int32_t n_off,
+                       int32_t* out_chunks, int32_t* out_span_len, double* out_span_scores, int32_t* out_n_spans, int32_t* out_n_chunks,
+                       hipStream_t s);
+
 // adapter_fit.hip: device half of update_query_adapter (best row per (query, chunk), row gather)
 int launch_chunk_best_rows(const void* E, bool f16, int32_t dim, const float* Q, const int64_t* offsets,
                            int64_t n_chunks, const int32_t* cand, int32_t n_cand, int64_t n_items, int32_t* out_rows,
