@@ -475,6 +475,41 @@ int rl_keyword_search(rl_keyword_index* kw, const int64_t* q_off, const int32_t*
                       void* stream);
 int rl_keyword_index_info(const rl_keyword_index* kw, int32_t* n_terms, int64_t* n_postings, int64_t* n_chunks);
 int rl_keyword_index_destroy(rl_keyword_index* kw);
+/* The three arrays the handle keeps, copied out (host or device pointers by `mem`; NULL skips one): term_off [n_terms + 1],
+ * post_chunk and post_impact [n_postings]. */
+int rl_keyword_index_read(const rl_keyword_index* kw, int64_t* term_off, int32_t* post_chunk, float* post_impact, int mem,
+                          void* stream);
+
+/* ---- keyword store: the postings built on the device -------------------------------------------------
+ * A keyword store holds, on the device, each chunk's term ids for the chunk ordinals of the rl_index it sits beside:
+ *   tok_off   int64[n_chunks + 1]; tok_term int32[n_tokens]: STABLE term ids (they never change once stored), in any order
+ *   inside a chunk, a repeated id is a term frequency; and a live flag per chunk.
+ * rl_keyword_store_append adds n_new_chunks chunks (offsets [n_new_chunks + 1] starting at 0, ascending; term ids >= 0) with
+ * amortised capacity; rl_keyword_store_delete (host ordinals) clears live flags -- a dead chunk again is a no-op -- and the
+ * tokens stay.  rl_keyword_store_count builds the term-major postings of the live chunks without the host touching a
+ * token: term t of the postings is term_rank[id] (term_rank: a permutation of [0, n_terms), NULL = the ids themselves;
+ * checked when it is host memory), by a stable radix sort of (term, chunk) on the term and a run-length encode.  It
+ * returns the statistics idf and nrm are made of: out_df [n_terms] (live chunks per term), out_length [n_chunks] (tokens
+ * of a live chunk, 0 of a dead one), out_totals = (n_live, total_length, n_postings); any may be NULL.  Every stored id
+ * must be < n_terms.  rl_keyword_store_build computes the impacts of the counted postings from idf [n_terms] and
+ * nrm [n_chunks] (as rl_keyword_index_create states them: the host computes them, or sums the counts of several shards
+ * first) and moves the postings into a fresh rl_keyword_index; it needs a count since the last append, delete or build.
+ * The store keeps the scratch of its counts (about 24 B per live token, grown by a quarter beyond need) so that the count after
+ * an insert allocates nothing; rl_keyword_store_info reports it in device_bytes, rl_keyword_store_destroy frees it.
+ * A store with no chunks or no live tokens counts zeros and builds what rl_keyword_index_create builds from empty arrays.
+ * The index is bit for bit the one rl_keyword_index_create makes from the host postings of the same chunks. */
+typedef struct rl_keyword_store rl_keyword_store;
+int rl_keyword_store_create(rl_keyword_store** out);
+int rl_keyword_store_destroy(rl_keyword_store* s);
+int rl_keyword_store_info(const rl_keyword_store* s, int64_t* n_chunks, int64_t* n_live, int64_t* n_tokens,
+                          int64_t* device_bytes);
+int rl_keyword_store_append(rl_keyword_store* s, const int32_t* term_ids, const int64_t* offsets, int64_t n_new_chunks,
+                            int mem, void* stream);
+int rl_keyword_store_delete(rl_keyword_store* s, const int64_t* chunk_ordinals, int64_t n, void* stream);
+int rl_keyword_store_count(rl_keyword_store* s, const int32_t* term_rank, int32_t n_terms, int64_t* out_df,
+                           int64_t* out_length, int64_t out_totals[3], int mem, void* stream);
+int rl_keyword_store_build(rl_keyword_store* s, const float* idf, const float* nrm, rl_keyword_index** out, int mem,
+                           void* stream);
 
 /* ---- weighted Reciprocal Rank Fusion and batched hybrid search ---------------------------------------
  * rl_rrf_fuse replaces src/raglite/_search.py:233-252 (`reciprocal_rank_fusion`) for a batch of queries, bit for bit:

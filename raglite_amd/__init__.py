@@ -19,6 +19,7 @@ from raglite_amd._embed import (
 from raglite_amd._ops import (
     DeviceIndex,
     KeywordIndex,
+    KeywordStore,
     adapter_apply,
     merge_topk,
     pack_bits,
@@ -78,6 +79,7 @@ __all__ = [
     "keyword_search_batch",
     "vector_search_batch",
     "KeywordIndex",
+    "KeywordStore",
     "reciprocal_rank_fusion",
     "update_query_adapter",
     "EncoderShape",

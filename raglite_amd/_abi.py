@@ -115,6 +115,14 @@ _SIGNATURES = {
     "rl_keyword_search": [c_void_p, c_void_p, c_void_p, c_i32, c_i32, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p],
     "rl_keyword_index_info": [c_void_p, C.POINTER(c_i32), C.POINTER(c_i64), C.POINTER(c_i64)],
     "rl_keyword_index_destroy": [c_void_p],
+    "rl_keyword_index_read": [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p],
+    "rl_keyword_store_create": [C.POINTER(c_void_p)],
+    "rl_keyword_store_destroy": [c_void_p],
+    "rl_keyword_store_info": [c_void_p, C.POINTER(c_i64), C.POINTER(c_i64), C.POINTER(c_i64), C.POINTER(c_i64)],
+    "rl_keyword_store_append": [c_void_p, c_void_p, c_void_p, c_i64, c_int, c_void_p],
+    "rl_keyword_store_delete": [c_void_p, c_void_p, c_i64, c_void_p],
+    "rl_keyword_store_count": [c_void_p, c_void_p, c_i32, c_void_p, c_void_p, c_void_p, c_int, c_void_p],
+    "rl_keyword_store_build": [c_void_p, c_void_p, c_void_p, C.POINTER(c_void_p), c_int, c_void_p],
     "rl_rrf_fuse": [c_void_p, c_i32, c_i32, c_i32, c_void_p, c_i32, c_i32, c_void_p, c_void_p, c_void_p, c_int, c_void_p],
     "rl_shard_hybrid_fuse": [c_void_p, c_i32, c_i32, c_i32, c_i32, c_i32, c_void_p, c_i32, c_i32, c_void_p, c_void_p, c_void_p, c_int,
                              c_void_p],

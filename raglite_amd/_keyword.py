@@ -278,3 +278,66 @@ def build_from_stems(chunk_stems: Sequence[Sequence[str] | None]) -> tuple[list[
 
 def build_from_texts(texts: Sequence[str | None]) -> tuple[list[str], Postings]:
     return build_from_stems([None if t is None else index_stems(t) for t in texts])
+
+
+class Vocabulary:
+    """Stable term ids for the device token store (`raglite_amd.KeywordStore`): a stem gets the next id the first time it is stored and
+    keeps it, so the tokens on the device never have to be rewritten.  The postings' terms are the RANKS of the stems in the sorted
+    vocabulary (`ranks()`, the permutation `KeywordStore.count` applies on the device).  Ranks are taken over every stem ever stored: a
+    stem that lives only in dead chunks keeps its rank with df = 0, and the live stems keep the relative order the sorted live
+    vocabulary gives them, so a score sums its impacts in the same order either way.  Host only."""
+
+    def __init__(self) -> None:
+        self._ids: dict[str, int] = {}
+        self._stems: list[str] = []
+        self._ranks = np.zeros(0, dtype=np.int32)
+
+    def __len__(self) -> int:
+        return len(self._stems)
+
+    def __contains__(self, stem_: str) -> bool:
+        return stem_ in self._ids
+
+    @property
+    def stems(self) -> list[str]:
+        """The stems in id order."""
+        return list(self._stems)
+
+    def add(self, stems: Sequence[str]) -> np.ndarray:
+        """The ids (int32) of `stems`, in their order; stems not seen before get the next ids in order of first appearance."""
+        ids = self._ids
+        out = np.empty(len(stems), dtype=np.int32)
+        for i, s in enumerate(stems):
+            t = ids.get(s)
+            if t is None:
+                t = ids[s] = len(self._stems)
+                self._stems.append(s)
+            out[i] = t
+        return out
+
+    def ranks(self) -> np.ndarray:
+        """int32 [len(self)]: rank[id] = the position of the stem in the sorted vocabulary (recomputed only after growth)."""
+        n = len(self._stems)
+        if self._ranks.size != n:
+            order = sorted(range(n), key=self._stems.__getitem__)
+            ranks = np.empty(n, dtype=np.int32)
+            ranks[np.asarray(order, dtype=np.int64)] = np.arange(n, dtype=np.int32)
+            self._ranks = ranks
+        return self._ranks
+
+    def query_ranks(self, stems: Sequence[str], ranks: np.ndarray | None = None) -> list[int]:
+        """The ranks of the distinct stems that are in the vocabulary, ascending (the term ids a query searches with).  `ranks`: an
+        earlier result of `ranks()` -- the numbering of the index that was built with it; stems added since then are unknown to it."""
+        if ranks is None:
+            ranks = self.ranks()
+        ids = self._ids
+        return sorted({int(ranks[ids[s]]) for s in stems if s in ids and ids[s] < ranks.size})
+
+
+def stems_to_store_ids(chunk_stems: Sequence[Sequence[str] | None], vocab: Vocabulary):
+    """(flat int32 ids, int64 offsets, ordinals of the dead chunks) of chunks given as index stems (None = dead: no tokens), every
+    stem added to `vocab`: what `KeywordStore.append` and `.delete` take."""
+    sizes = np.fromiter((len(stems) if stems is not None else 0 for stems in chunk_stems), dtype=np.int64, count=len(chunk_stems))
+    flat = vocab.add([s for stems in chunk_stems if stems is not None for s in stems])
+    dead = np.asarray([i for i, stems in enumerate(chunk_stems) if stems is None], dtype=np.int64)
+    return flat, np.concatenate(([0], np.cumsum(sizes))).astype(np.int64), dead

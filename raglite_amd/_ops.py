@@ -1036,6 +1036,25 @@ class KeywordIndex:
                                             nrm.ctypes.data, self.n_chunks, MEM_HOST, None))
         self._handle = handle
 
+    @classmethod
+    def _from_handle(cls, handle) -> "KeywordIndex":
+        """Wraps an `rl_keyword_index` the library built (`KeywordStore.build`); the object owns it."""
+        self = cls.__new__(cls)
+        n_terms, n_postings, n_chunks = C.c_int32(0), C.c_int64(0), C.c_int64(0)
+        self._handle = handle
+        check(lib().rl_keyword_index_info(handle, C.byref(n_terms), C.byref(n_postings), C.byref(n_chunks)))
+        self.n_terms, self.n_postings, self.n_chunks = n_terms.value, n_postings.value, n_chunks.value
+        return self
+
+    def read(self):
+        """(term_off int64 [n_terms + 1], post_chunk int32 [n_postings], post_impact float32 [n_postings]): the arrays the device holds."""
+        term_off = np.empty(self.n_terms + 1, np.int64)
+        post_chunk = np.empty(self.n_postings, np.int32)
+        post_impact = np.empty(self.n_postings, np.float32)
+        _ensure_init(_current_device())
+        check(lib().rl_keyword_index_read(self._handle, term_off.ctypes.data, post_chunk.ctypes.data, post_impact.ctypes.data, MEM_HOST, None))
+        return term_off, post_chunk, post_impact
+
     def close(self) -> None:
         h, self._handle = getattr(self, "_handle", None), None
         if h:
@@ -1074,3 +1093,85 @@ class KeywordIndex:
         check(lib().rl_keyword_search(self._handle, q_off.ctypes.data, q_terms.ctypes.data, B, k, p_f, scores.ctypes.data,
                                       chunks.ctypes.data, counts.ctypes.data, MEM_HOST, None))
         return scores, chunks, counts
+
+
+class KeywordStore:
+    """Each chunk's term ids on the device (`rl_keyword_store`), beside the `DeviceIndex` whose chunk ordinals it follows: the BM25
+    postings are built from it on the device (`count`, then `build`), so an insert or a delete uploads only what is new.  Term ids are
+    stable (`raglite_amd._keyword.Vocabulary`); `count` takes the permutation that turns them into ranks in the sorted vocabulary."""
+
+    def __init__(self) -> None:
+        _ensure_init(_current_device())
+        handle = C.c_void_p()
+        check(lib().rl_keyword_store_create(C.byref(handle)))
+        self._handle = handle
+
+    def close(self) -> None:
+        h, self._handle = getattr(self, "_handle", None), None
+        if h:
+            lib().rl_keyword_store_destroy(h)
+
+    def __del__(self) -> None:  # noqa: D105
+        try:
+            self.close()
+        except Exception:  # noqa: BLE001,S110 - interpreter shutdown
+            pass
+
+    def info(self) -> dict:
+        vals = [C.c_int64(0) for _ in range(4)]
+        check(lib().rl_keyword_store_info(self._handle, *(C.byref(v) for v in vals)))
+        return dict(zip(("n_chunks", "n_live", "n_tokens", "device_bytes"), (v.value for v in vals)))
+
+    def append(self, flat_ids, offsets) -> None:
+        """New chunks at the end: chunk i holds term ids flat_ids[offsets[i] : offsets[i + 1]] (any order, repeats = tf)."""
+        offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+        flat = np.asarray(flat_ids)
+        if flat.size and (flat.min() < 0 or flat.max() > np.iinfo(np.int32).max):
+            raise ValueError("KeywordStore.append: term ids must be in [0, 2^31)")
+        flat = np.ascontiguousarray(flat, dtype=np.int32)
+        if offsets.ndim != 1 or offsets.size < 1 or flat.ndim != 1 or int(offsets[-1]) != flat.size:
+            raise ValueError("KeywordStore.append: offsets must hold one entry per chunk plus one and end at len(flat_ids)")
+        _ensure_init(_current_device())
+        check(lib().rl_keyword_store_append(self._handle, flat.ctypes.data, offsets.ctypes.data, int(offsets.size - 1), MEM_HOST, None))
+        if offsets.size > 1:
+            self._counted = None
+
+    def delete(self, ordinals) -> None:
+        """The chunks never count again (their tokens stay until the store is rebuilt); an ordinal that is dead already is skipped."""
+        ords = np.ascontiguousarray(ordinals, dtype=np.int64).reshape(-1)
+        _ensure_init(_current_device())
+        check(lib().rl_keyword_store_delete(self._handle, ords.ctypes.data, int(ords.size), None))
+        if ords.size:
+            self._counted = None
+
+    def count(self, n_terms: int, term_rank=None):
+        """Builds the postings of the live chunks on the device; term t of them is term_rank[id] (None: the ids themselves).  Returns
+        (df int64 [n_terms], length int64 [n_chunks], n_live, total_length, n_postings): what `_keyword.bm25_weights` takes."""
+        n_chunks = self.info()["n_chunks"]
+        p_rank = None
+        if term_rank is not None:
+            rank = np.ascontiguousarray(term_rank, dtype=np.int32)
+            if rank.shape != (n_terms,):
+                raise ValueError("KeywordStore.count: term_rank must hold one rank per term")
+            p_rank = rank.ctypes.data
+        df = np.zeros(n_terms, np.int64)
+        length = np.zeros(n_chunks, np.int64)
+        totals = np.zeros(3, np.int64)
+        self._counted = None
+        check(lib().rl_keyword_store_count(self._handle, p_rank, n_terms, df.ctypes.data, length.ctypes.data, totals.ctypes.data, MEM_HOST, None))
+        self._counted = (n_terms, n_chunks)
+        return df, length, int(totals[0]), int(totals[1]), int(totals[2])
+
+    def build(self, idf, nrm) -> "KeywordIndex":
+        """The `KeywordIndex` of the counted postings with these weights (float32 [n_terms], [n_chunks]); needs a `count` since the last
+        change, and uses it up."""
+        idf = np.ascontiguousarray(idf, dtype=np.float32)
+        nrm = np.ascontiguousarray(nrm, dtype=np.float32)
+        counted = getattr(self, "_counted", None)  # (n_terms, n_chunks) of the last count; the library refuses a build without one
+        if counted is not None and counted != (idf.size, nrm.size):
+            raise ValueError("KeywordStore.build: idf / nrm must hold one weight per counted term / chunk")
+        handle = C.c_void_p()
+        check(lib().rl_keyword_store_build(self._handle, idf.ctypes.data if counted else None, nrm.ctypes.data if counted else None,
+                                           C.byref(handle), MEM_HOST, None))
+        self._counted = None
+        return KeywordIndex._from_handle(handle)  # noqa: SLF001

@@ -58,6 +58,9 @@ class GpuIndex:
     exact_fp32       multiply with exact fp32 MFMAs instead of the default fp16 (hi, lo) split of fp32 operands
     keyword_texts    optional list[str] -- `Chunk.body` per chunk: builds the BM25 keyword side (`keyword_search`, the keyword
                      half of `hybrid_search`; DESIGN.md "Keyword search"), rebuilt from the live chunks after every change
+    keyword_build    "device" (the default): the chunks' term ids stay on the device (`KeywordStore`) and every rebuild of the postings
+                     runs there; "host": the postings are rebuilt on the host and uploaded (the oracle of the device
+                     build, and its A/B path).  Every result is the same either way.
     positions        optional list of (document_id: str, index: int) -- `Chunk.document_id` / `Chunk.index` per chunk
                      (`_database.py:207-224`; None: the chunk has no position): builds the span table (`retrieve_chunk_spans`;
                      DESIGN.md 4.11), rebuilt from the live chunks after every change
@@ -68,6 +71,11 @@ class GpuIndex:
     keyword: _ops.KeywordIndex | None = None
     _kw_stems: list[list[str] | None] | None = None
     _kw_vocab: dict[str, int] = {}
+    # keyword_build="device": the stable term ids (host) and the chunks' ids on the device; the postings are built from them there
+    keyword_build: str = "device"
+    _kw_vocabulary: _keyword.Vocabulary | None = None
+    _kw_store: _ops.KeywordStore | None = None
+    _kw_built_ranks: np.ndarray | None = None  # `_kw_vocabulary.ranks()` as of the build of `keyword`
     # span side (class defaults: an index without one): each chunk's (document_id, index) (None once deleted) and the device table
     positions: list | None = None
     spans: _ops.SpanTable | None = None
@@ -75,7 +83,11 @@ class GpuIndex:
     def __init__(self, chunk_ids: Sequence[ChunkId], chunk_embeddings, *, chunk_offsets=None,
                  metric: str = "cosine", query_adapter=None, docs: Sequence[str] | None = None,
                  metadata: Sequence[dict] | None = None, storage: str = "f32", exact_fp32: bool = False,
-                 keyword_texts: Sequence[str] | None = None, positions: Sequence[tuple[str, int] | None] | None = None) -> None:
+                 keyword_texts: Sequence[str] | None = None, positions: Sequence[tuple[str, int] | None] | None = None,
+                 keyword_build: str = "device") -> None:
+        if keyword_build not in ("device", "host"):
+            raise ValueError('keyword_build must be "device" or "host"')
+        self.keyword_build = keyword_build
         if chunk_offsets is None:
             mats = [np.asarray(m, dtype=np.float32).reshape(len(m), -1) for m in chunk_embeddings]
             sizes = np.asarray([len(m) for m in mats], dtype=np.int64)
@@ -100,7 +112,10 @@ class GpuIndex:
             if len(keyword_texts) != len(self.chunk_ids):
                 raise ValueError("one keyword text per chunk is required")
             self._kw_stems = [_keyword.index_stems(t) for t in keyword_texts]
-            self._rebuild_keywords()
+            if keyword_build == "device":
+                self._reset_keyword_store()
+            else:
+                self._rebuild_keywords()
         if positions is not None:
             if len(positions) != len(self.chunk_ids):
                 raise ValueError("one (document_id, index) position per chunk is required")
@@ -146,8 +161,41 @@ class GpuIndex:
             self.keyword.close()
         self.keyword, self._kw_vocab = new, {s: i for i, s in enumerate(vocab)}
 
+    def _reset_keyword_store(self) -> None:
+        """keyword_build="device": a fresh vocabulary and token store from `_kw_stems`, by one upload of every chunk's ids (the
+        constructor, and `compact` -- a rare operation, which renumbers the chunks), then the postings."""
+        vocab, store = _keyword.Vocabulary(), _ops.KeywordStore()
+        old = (self._kw_vocabulary, self._kw_store, self._kw_built_ranks)
+        try:
+            flat, offsets, dead = _keyword.stems_to_store_ids(self._kw_stems, vocab)
+            store.append(flat, offsets)
+            store.delete(dead)
+            self._kw_vocabulary, self._kw_store = vocab, store
+            self._build_keywords_on_device()
+        except Exception:
+            self._kw_vocabulary, self._kw_store, self._kw_built_ranks = old
+            store.close()
+            raise
+        if old[1] is not None:
+            old[1].close()
+
+    def _build_keywords_on_device(self) -> None:
+        """What `_rebuild_keywords` does, without the host touching a token: the store counts the postings of the live chunks
+        (`rl_keyword_store_count`), `_keyword.bm25_weights` turns the statistics into idf and nrm, the store builds the index."""
+        vocab, store = self._kw_vocabulary, self._kw_store
+        ranks = vocab.ranks()
+        df, length, n_live, total_length, _ = store.count(len(vocab), ranks)
+        idf, nrm, _ = _keyword.bm25_weights(df, length, n_live, total_length)
+        new = store.build(idf, nrm)  # (built before the old one goes: a failure leaves the keyword index as it was)
+        if self.keyword is not None:
+            self.keyword.close()
+        # queries are numbered by the ranks the index was BUILT with: the vocabulary may grow before a later build succeeds
+        self.keyword, self._kw_built_ranks = new, ranks
+
     def keyword_query_ids(self, query: str) -> list[int]:
         """Term ids of the query's distinct stems that are in the vocabulary, ascending."""
+        if self._kw_vocabulary is not None:  # (the device build's terms are ranks over every stem ever stored)
+            return self._kw_vocabulary.query_ranks(_keyword.query_stems(query), self._kw_built_ranks)
         return sorted(self._kw_vocab[s] for s in _keyword.query_stems(query) if s in self._kw_vocab)
 
     def ordinal_of(self, chunk_id: ChunkId) -> int:
@@ -194,8 +242,14 @@ class GpuIndex:
         if metadata is not None:
             self.metadata.extend(metadata)
         if keyword_texts is not None:
-            self._kw_stems.extend(_keyword.index_stems(t) for t in keyword_texts)
-            self._rebuild_keywords()
+            stems = [_keyword.index_stems(t) for t in keyword_texts]
+            self._kw_stems.extend(stems)
+            if self._kw_store is not None:  # only the new chunks' ids go to the device
+                flat, offsets, _ = _keyword.stems_to_store_ids(stems, self._kw_vocabulary)
+                self._kw_store.append(flat, offsets)
+                self._build_keywords_on_device()
+            else:
+                self._rebuild_keywords()
         if positions is not None:
             self._rebuild_spans(self.positions + list(positions))
 
@@ -219,7 +273,11 @@ class GpuIndex:
             if self.has_keywords:
                 for o in ords:
                     self._kw_stems[o] = None
-                self._rebuild_keywords()
+                if self._kw_store is not None:
+                    self._kw_store.delete(np.asarray(ords, dtype=np.int64))
+                    self._build_keywords_on_device()
+                else:
+                    self._rebuild_keywords()
             if self.has_positions:
                 gone = set(ords)
                 self._rebuild_spans([None if o in gone else p for o, p in enumerate(self.positions)])
@@ -228,11 +286,12 @@ class GpuIndex:
     # -- the real store ----------------------------------------------------------------------
     @classmethod
     def from_store(cls, bind: Any, *, metric: str = "cosine", storage: str = "f32", exact_fp32: bool = False,
-                   keywords: bool = False) -> "GpuIndex":
+                   keywords: bool = False, keyword_build: str = "device") -> "GpuIndex":
         """Build the device index from a RAGLite database: `chunk_embedding` rows ordered by (chunk_id, id)
         (`src/raglite/_database.py:403-430`), the chunks' `str(chunk)` text and metadata, and the stored query adapter
         (`:450-462`).  `bind`: SQLAlchemy Engine / Connection / Session or a database URL.  `metric` is the store's
-        `vector_search_distance_metric` (`_config.py:69`).  `keywords`: also build the BM25 keyword side from `chunk.body`.
+        `vector_search_distance_metric` (`_config.py:69`).  `keywords`: also build the BM25 keyword side from `chunk.body`
+        (`keyword_build` as in the constructor).
         The index remembers `bind` for `sync()`."""
         from raglite_amd import _store
 
@@ -248,7 +307,7 @@ class GpuIndex:
         off = np.concatenate(([0], np.cumsum(np.asarray(img.sizes, dtype=np.int64)))).astype(np.int64)
         gi = cls(img.chunk_ids, img.matrix(), chunk_offsets=off, metric=metric, query_adapter=adapter, docs=img.docs,
                  metadata=img.metadata, storage=storage, exact_fp32=exact_fp32, keyword_texts=img.bodies if keywords else None,
-                 positions=img.positions)
+                 positions=img.positions, keyword_build=keyword_build)
         gi._bind = bind  # noqa: SLF001
         return gi
 
@@ -302,7 +361,10 @@ class GpuIndex:
             self.metadata = [self.metadata[i] for i in keep]
         if self.has_keywords:
             self._kw_stems = [self._kw_stems[i] for i in keep]
-            self._rebuild_keywords()
+            if self._kw_store is not None:  # (the ordinals changed: one upload of the kept chunks' ids)
+                self._reset_keyword_store()
+            else:
+                self._rebuild_keywords()
         if self.has_positions:
             self._rebuild_spans([self.positions[i] for i in keep])
 
@@ -310,6 +372,8 @@ class GpuIndex:
         self.index.close()
         if self.keyword is not None:
             self.keyword.close()
+        if self._kw_store is not None:
+            self._kw_store.close()
         if self.spans is not None:
             self.spans.close()
 

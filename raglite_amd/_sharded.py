@@ -609,13 +609,16 @@ class ShardedIndex:
 
     def attach_keywords(self, chunk_stems, *, make_index=None) -> None:
         """Collective: the BM25 keyword side of this shard, with the statistics of the WHOLE corpus.  `chunk_stems`: the index stems of
-        this shard's chunks in local order (`_keyword.index_stems(body)`; None for a dead chunk), as `GpuIndex._kw_stems` holds them.
+        this shard's chunks in local order (`_keyword.index_stems(body)`; None for a dead chunk): `GpuIndex._kw_stems` is that list.
         Every rank (1) agrees on one vocabulary, the sorted union of all live stems -- term ids are the ranks in it, the ids one index
         over the whole corpus assigns; (2) sums df per term, N and the total stem count over the ranks, the counts exchanged as int64;
-        (3) builds its own postings over local chunk ordinals with idf and nrm from those global values
-        (`_keyword.build_shard_from_term_ids`): every impact is bitwise the one a single index over everything computes.  Inserts and
-        deletes change N and avgdl, so every shard's impacts: call it again on every rank after any.  `make_index` (Postings ->
-        an object with `search(query_term_ids, k, chunk_filter)`): default `raglite_amd.KeywordIndex`."""
+        (3) builds its own postings over local chunk ordinals with idf and nrm from those global values: every impact is bitwise the
+        one a single index over everything computes.  The postings are built on the device: the shard's ids go to a `KeywordStore`
+        (they are global ranks already, so no permutation), its `count` supplies the shard's df, N and stem total for the all-gather,
+        `_keyword.bm25_weights` runs over the sums and `build` makes the index.  Inserts and deletes change N and avgdl, so every
+        shard's impacts: call it again on every rank after any.  `make_index` (Postings -> an object with
+        `search(query_term_ids, k, chunk_filter)`): the postings are built on the host (`_keyword.build_shard_from_term_ids`) and
+        handed to it."""
         from . import _keyword, _ops
 
         stems = list(chunk_stems)
@@ -624,13 +627,29 @@ class ShardedIndex:
         vocab = self._exchange_vocab(sorted({st for ss in stems if ss is not None for st in ss}))
         ids = {st: i for i, st in enumerate(vocab)}
         flat, offsets, live = _keyword.stems_to_term_ids(stems, ids)
-        mine = _keyword.shard_counts(flat, offsets, len(vocab), live)
-        head = np.asarray([mine.n_live, mine.total_length], dtype=np.int64).view(np.int32)  # (int64 counts as two int32 words each)
-        g = self._allgather_host(np.concatenate([head, mine.df.astype(np.int32)]))  # (world, 4 + n_terms)
-        heads = np.ascontiguousarray(g[:, :4]).view(np.int64)  # (world, 2)
-        corpus = _keyword.ShardCounts(g[:, 4:].astype(np.int64).sum(axis=0), int(heads[:, 0].sum()), int(heads[:, 1].sum()))
-        postings = _keyword.build_shard_from_term_ids(flat, offsets, len(vocab), live, corpus)
-        new = (make_index or _ops.KeywordIndex)(postings) if len(stems) else None
+        store = _ops.KeywordStore() if make_index is None else None
+        try:
+            if store is not None:
+                store.append(flat, offsets)
+                if live is not None:
+                    store.delete(np.nonzero(~live)[0])
+                df, length, n_live, total_length, _ = store.count(len(vocab))
+                mine = _keyword.ShardCounts(df, n_live, total_length)
+            else:
+                mine = _keyword.shard_counts(flat, offsets, len(vocab), live)
+            head = np.asarray([mine.n_live, mine.total_length], dtype=np.int64).view(np.int32)  # (int64 counts as two int32 words each)
+            g = self._allgather_host(np.concatenate([head, mine.df.astype(np.int32)]))  # (world, 4 + n_terms)
+            heads = np.ascontiguousarray(g[:, :4]).view(np.int64)  # (world, 2)
+            corpus = _keyword.ShardCounts(g[:, 4:].astype(np.int64).sum(axis=0), int(heads[:, 0].sum()), int(heads[:, 1].sum()))
+            if store is not None:
+                idf, nrm, _ = _keyword.bm25_weights(corpus.df, length, corpus.n_live, corpus.total_length)
+                new = store.build(idf, nrm) if len(stems) else None
+            else:
+                postings = _keyword.build_shard_from_term_ids(flat, offsets, len(vocab), live, corpus)
+                new = make_index(postings) if len(stems) else None
+        finally:
+            if store is not None:
+                store.close()
         old, self.keyword, self._kw_vocab = self.keyword, new, ids
         self._kw_attached = True
         if old is not None and hasattr(old, "close"):

@@ -3162,6 +3162,25 @@ int check_host_q_off(const int64_t* q_off, const int32_t* q_terms, int32_t n_que
     return RL_OK;
 }
 
+// A fresh handle with its sizes, the default top-k route and the device's CU count; the arrays are the caller's to fill.
+int new_keyword_index(int32_t n_terms, int64_t n_postings, int64_t n_chunks, std::unique_ptr<rl_keyword_index>* out) {
+    std::unique_ptr<rl_keyword_index> kw(new rl_keyword_index());
+    kw->n_terms = n_terms;
+    kw->n_postings = n_postings;
+    kw->n_chunks = n_chunks;
+    {
+        std::lock_guard<std::mutex> lock(g_default_opts_mu);
+        kw->ws.block_route = (int)g_default_opts.v[RL_OPT_TOPK_BLOCK];
+    }
+    int dev = 0;
+    RL_HIP(hipGetDevice(&dev));
+    hipDeviceProp_t prop;
+    RL_HIP(hipGetDeviceProperties(&prop, dev));
+    kw->n_cu = prop.multiProcessorCount;
+    *out = std::move(kw);
+    return RL_OK;
+}
+
 // rl_rrf_fuse's limits (weights: host memory)
 int check_fuse_args(int32_t n_lists, int32_t n_queries, int32_t len, const double* weights, int32_t rrf_k, int32_t k, const char* who) {
     if (n_lists < 1 || n_lists > RRF_MAX_LISTS) return fail(RL_ERR_INVALID, std::string(who) + ": n_lists must be in [1, 4]");
@@ -3194,19 +3213,8 @@ int rl_keyword_index_create(rl_keyword_index** out, const int64_t* term_off, int
     if (mem != RL_MEM_HOST && mem != RL_MEM_DEVICE) return fail(RL_ERR_INVALID, "rl_keyword_index_create: bad mem");
     if (mem == RL_MEM_HOST) RL_TRY(check_host_postings(term_off, n_terms, post_chunk, post_tf, post_term, n_postings, n_chunks));
     hipStream_t s = as_stream(stream);
-    std::unique_ptr<rl_keyword_index> kw(new rl_keyword_index());
-    kw->n_terms = n_terms;
-    kw->n_postings = n_postings;
-    kw->n_chunks = n_chunks;
-    {
-        std::lock_guard<std::mutex> lock(g_default_opts_mu);
-        kw->ws.block_route = (int)g_default_opts.v[RL_OPT_TOPK_BLOCK];
-    }
-    int dev = 0;
-    RL_HIP(hipGetDevice(&dev));
-    hipDeviceProp_t prop;
-    RL_HIP(hipGetDeviceProperties(&prop, dev));
-    kw->n_cu = prop.multiProcessorCount;
+    std::unique_ptr<rl_keyword_index> kw;
+    RL_TRY(new_keyword_index(n_terms, n_postings, n_chunks, &kw));
     const size_t np = (size_t)n_postings;
     RL_TRY(kw->term_off.alloc((size_t)(n_terms + 1) * sizeof(int64_t), who));
     RL_TRY(kw->post_chunk.alloc(std::max<size_t>(np * sizeof(int32_t), 16), who));
@@ -3239,6 +3247,312 @@ int rl_keyword_index_info(const rl_keyword_index* kw, int32_t* n_terms, int64_t*
     if (n_terms) *n_terms = kw->n_terms;
     if (n_postings) *n_postings = kw->n_postings;
     if (n_chunks) *n_chunks = kw->n_chunks;
+    return RL_OK;
+}
+
+int rl_keyword_index_read(const rl_keyword_index* kw, int64_t* term_off, int32_t* post_chunk, float* post_impact, int mem, void* stream) {
+    if (!kw) return fail(RL_ERR_INVALID, "rl_keyword_index_read: null index");
+    if (mem != RL_MEM_HOST && mem != RL_MEM_DEVICE) return fail(RL_ERR_INVALID, "rl_keyword_index_read: bad mem");
+    hipStream_t s = as_stream(stream);
+    const hipMemcpyKind kind = mem == RL_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
+    const size_t np = (size_t)kw->n_postings;
+    if (term_off) RL_HIP(hipMemcpyAsync(term_off, kw->term_off, (size_t)(kw->n_terms + 1) * sizeof(int64_t), kind, s));
+    if (post_chunk && np) RL_HIP(hipMemcpyAsync(post_chunk, kw->post_chunk, np * sizeof(int32_t), kind, s));
+    if (post_impact && np) RL_HIP(hipMemcpyAsync(post_impact, kw->post_impact, np * sizeof(float), kind, s));
+    if (mem == RL_MEM_HOST) RL_HIP(hipStreamSynchronize(s));
+    return RL_OK;
+}
+
+}  // extern "C"
+
+// ---- keyword store: the chunks' term ids on the device, and the postings built from them (kernels in keyword_build.hip) -------------
+struct rl_keyword_store {
+    int64_t n_chunks = 0, n_tokens = 0, n_live = 0;
+    int64_t cap_off = 0, cap_live = 0, cap_tokens = 0;  // items the three arrays can hold
+    int32_t max_id = -1;                  // the largest term id ever stored
+    rl::DevArray<int64_t> tok_off;        // [n_chunks + 1]
+    rl::DevArray<int32_t> tok_term;       // [n_tokens]
+    rl::DevArray<uint8_t> live;           // [n_chunks]: 1 = live
+    std::vector<uint8_t> h_live;          // host copy of `live`
+    std::mutex mu;
+    // what rl_keyword_store_count left for rl_keyword_store_build (dropped by an append or a delete)
+    bool counted = false;
+    int32_t c_terms = 0;
+    int64_t c_postings = 0, c_chunks = 0;
+    rl::DevArray<int64_t> term_off;       // fresh per count: these two become the index' own
+    rl::DevArray<int32_t> post_chunk;
+    rl::DevArray<int32_t> post_term, post_tf;  // [c_postings], kept with the scratch below
+    // Scratch of count, kept between calls with amortised capacity (an insert changes every size a little, and allocating ~24 B per
+    // token afresh costs more than the kernels: DESIGN.md 4.12): lengths, their scan, the scan levels, the (key, value) planes of the
+    // sort, its (digit, block) table, the head counts and positions, df
+    rl::Pool lens, offs, scan_scratch, sortbuf, table, heads, head_pos, df;
+    void drop_count() {
+        counted = false;
+        term_off.release();
+        post_chunk.release();
+    }
+    size_t device_bytes() const {
+        return tok_off.cap + tok_term.cap + live.cap + term_off.cap + post_term.cap + post_chunk.cap + post_tf.cap + lens.cap + offs.cap +
+               scan_scratch.cap + sortbuf.cap + table.cap + heads.cap + head_pos.cap + df.cap;
+    }
+};
+
+namespace rl {
+namespace {
+
+// Room for `need` items in an array that holds `used`: a fresh block of amortised capacity, the contents copied on the device.
+// Scratch that grows by a quarter more than asked for, so that the next few inserts fit (Pool::reserve keeps a block that is large enough).
+int reserve_amortised(Pool& pool, size_t bytes, const char* who) {
+    if (bytes <= pool.cap) return RL_OK;
+    return pool.alloc(bytes + bytes / 4, who);
+}
+
+template <class T>
+int store_grow(DevArray<T>& arr, int64_t* cap, int64_t used, int64_t need, hipStream_t s, const char* who) {
+    if (need <= *cap) return RL_OK;
+    const int64_t want = std::max<int64_t>({need, *cap + *cap / 2, 1024});
+    DevArray<T> bigger;
+    RL_TRY(bigger.alloc((size_t)want * sizeof(T), who));
+    if (used > 0) RL_TRY(hip_status(hipMemcpyAsync(bigger.p, arr.p, (size_t)used * sizeof(T), hipMemcpyDeviceToDevice, s), who));
+    RL_TRY(hip_status(hipStreamSynchronize(s), who));  // (the old block goes now)
+    arr = std::move(bigger);
+    *cap = want;
+    return RL_OK;
+}
+
+}  // namespace
+}  // namespace rl
+
+extern "C" {
+
+int rl_keyword_store_create(rl_keyword_store** out) {
+    if (!out) return fail(RL_ERR_INVALID, "rl_keyword_store_create: null output handle");
+    *out = new rl_keyword_store();
+    return RL_OK;
+}
+
+int rl_keyword_store_destroy(rl_keyword_store* st) {
+    if (!st) return RL_OK;
+    delete st;
+    return RL_OK;
+}
+
+int rl_keyword_store_info(const rl_keyword_store* st, int64_t* n_chunks, int64_t* n_live, int64_t* n_tokens, int64_t* device_bytes) {
+    if (!st) return fail(RL_ERR_INVALID, "rl_keyword_store_info: null store");
+    std::lock_guard<std::mutex> lock(const_cast<rl_keyword_store*>(st)->mu);
+    if (n_chunks) *n_chunks = st->n_chunks;
+    if (n_live) *n_live = st->n_live;
+    if (n_tokens) *n_tokens = st->n_tokens;
+    if (device_bytes) *device_bytes = (int64_t)st->device_bytes();
+    return RL_OK;
+}
+
+int rl_keyword_store_append(rl_keyword_store* st, const int32_t* term_ids, const int64_t* offsets, int64_t n_new_chunks, int mem, void* stream) {
+    const char* who = "rl_keyword_store_append";
+    if (!st) return fail(RL_ERR_INVALID, std::string(who) + ": null store");
+    if (n_new_chunks < 0) return fail(RL_ERR_INVALID, std::string(who) + ": negative size");
+    if (mem != RL_MEM_HOST && mem != RL_MEM_DEVICE) return fail(RL_ERR_INVALID, std::string(who) + ": bad mem");
+    if (n_new_chunks == 0) return RL_OK;
+    if (!offsets) return fail(RL_ERR_INVALID, std::string(who) + ": null offsets");
+    hipStream_t s = as_stream(stream);
+    const hipMemcpyKind in_kind = mem == RL_MEM_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice;
+    std::vector<int64_t> h_off((size_t)n_new_chunks + 1);
+    if (mem == RL_MEM_HOST) std::memcpy(h_off.data(), offsets, h_off.size() * sizeof(int64_t));
+    else {
+        RL_TRY(hip_status(hipMemcpyAsync(h_off.data(), offsets, h_off.size() * sizeof(int64_t), hipMemcpyDeviceToHost, s), who));
+        RL_TRY(hip_status(hipStreamSynchronize(s), who));
+    }
+    if (h_off[0] != 0) return fail(RL_ERR_INVALID, std::string(who) + ": offsets must start at 0");
+    for (int64_t c = 0; c < n_new_chunks; ++c)
+        if (h_off[c + 1] < h_off[c]) return fail(RL_ERR_INVALID, std::string(who) + ": offsets must be ascending");
+    const int64_t n_add = h_off[n_new_chunks];
+    if (n_add > 0 && !term_ids) return fail(RL_ERR_INVALID, std::string(who) + ": null term_ids");
+    int32_t range[2] = {std::numeric_limits<int32_t>::max(), std::numeric_limits<int32_t>::min()};  // min, max of the new ids
+    if (mem == RL_MEM_HOST) {
+        for (int64_t i = 0; i < n_add; ++i) {
+            range[0] = std::min(range[0], term_ids[i]);
+            range[1] = std::max(range[1], term_ids[i]);
+        }
+    } else if (n_add > 0) {
+        DevBuf t_range;
+        RL_TRY(t_range.alloc(sizeof(range)));
+        RL_TRY(hip_status(hipMemcpyAsync(t_range.p, range, sizeof(range), hipMemcpyHostToDevice, s), who));
+        RL_TRY(launch_kb_minmax(term_ids, n_add, t_range.as<int32_t>(), s));
+        RL_TRY(hip_status(hipMemcpyAsync(range, t_range.p, sizeof(range), hipMemcpyDeviceToHost, s), who));
+        RL_TRY(hip_status(hipStreamSynchronize(s), who));
+    }
+    if (n_add > 0 && range[0] < 0) return fail(RL_ERR_INVALID, std::string(who) + ": negative term id");
+    std::lock_guard<std::mutex> lock(st->mu);
+    if (st->n_chunks + n_new_chunks >= (int64_t)0x7fffffff - 1) return fail(RL_ERR_UNSUPPORTED, std::string(who) + ": more than 2^31-2 chunks");
+    RL_TRY(store_grow(st->tok_off, &st->cap_off, st->n_chunks ? st->n_chunks + 1 : 0, st->n_chunks + n_new_chunks + 1, s, who));
+    RL_TRY(store_grow(st->live, &st->cap_live, st->n_chunks, st->n_chunks + n_new_chunks, s, who));
+    RL_TRY(store_grow(st->tok_term, &st->cap_tokens, st->n_tokens, st->n_tokens + n_add, s, who));
+    for (int64_t& o : h_off) o += st->n_tokens;  // (h_off[0] is what tok_off[n_chunks] holds already, or the first 0)
+    RL_TRY(hip_status(hipMemcpyAsync(st->tok_off + st->n_chunks, h_off.data(), h_off.size() * sizeof(int64_t), hipMemcpyHostToDevice, s), who));
+    if (n_add > 0) RL_TRY(hip_status(hipMemcpyAsync(st->tok_term + st->n_tokens, term_ids, (size_t)n_add * sizeof(int32_t), in_kind, s), who));
+    RL_TRY(hip_status(hipMemsetAsync(st->live + st->n_chunks, 1, (size_t)n_new_chunks, s), who));
+    RL_TRY(hip_status(hipStreamSynchronize(s), who));  // the caller's arrays and h_off may go away after return
+    st->h_live.resize((size_t)(st->n_chunks + n_new_chunks), 1);
+    st->n_chunks += n_new_chunks;
+    st->n_live += n_new_chunks;
+    st->n_tokens += n_add;
+    if (n_add > 0) st->max_id = std::max(st->max_id, range[1]);
+    st->drop_count();
+    return RL_OK;
+}
+
+int rl_keyword_store_delete(rl_keyword_store* st, const int64_t* chunk_ordinals, int64_t n, void* stream) {
+    const char* who = "rl_keyword_store_delete";
+    if (!st) return fail(RL_ERR_INVALID, std::string(who) + ": null store");
+    if (n < 0 || (n > 0 && !chunk_ordinals)) return fail(RL_ERR_INVALID, std::string(who) + ": bad ordinals");
+    hipStream_t s = as_stream(stream);
+    std::lock_guard<std::mutex> lock(st->mu);
+    for (int64_t i = 0; i < n; ++i)
+        if (chunk_ordinals[i] < 0 || chunk_ordinals[i] >= st->n_chunks) return fail(RL_ERR_INVALID, std::string(who) + ": chunk ordinal out of range");
+    if (n == 0) return RL_OK;
+    st->drop_count();  // (any delete, even of dead chunks alone, asks for a new count)
+    // the touched range of the live bytes goes up before the host copy changes: a failure leaves the store as it was
+    int64_t lo = st->n_chunks, hi = -1, gone = 0;
+    for (int64_t i = 0; i < n; ++i) {  // (deleting a dead chunk is a no-op, as in rl_index_delete_chunks)
+        if (!st->h_live[(size_t)chunk_ordinals[i]]) continue;
+        lo = std::min(lo, chunk_ordinals[i]);
+        hi = std::max(hi, chunk_ordinals[i]);
+    }
+    if (hi < 0) return RL_OK;
+    std::vector<uint8_t> range(st->h_live.begin() + lo, st->h_live.begin() + hi + 1);
+    for (int64_t i = 0; i < n; ++i) {
+        if (chunk_ordinals[i] < lo || chunk_ordinals[i] > hi) continue;  // (dead already: every live one lies in [lo, hi])
+        uint8_t& flag = range[(size_t)(chunk_ordinals[i] - lo)];
+        gone += flag;
+        flag = 0;
+    }
+    RL_TRY(hip_status(hipMemcpyAsync(st->live + lo, range.data(), range.size(), hipMemcpyHostToDevice, s), who));
+    RL_TRY(hip_status(hipStreamSynchronize(s), who));
+    std::copy(range.begin(), range.end(), st->h_live.begin() + lo);
+    st->n_live -= gone;
+    return RL_OK;
+}
+
+int rl_keyword_store_count(rl_keyword_store* st, const int32_t* term_rank, int32_t n_terms, int64_t* out_df, int64_t* out_length,
+                           int64_t out_totals[3], int mem, void* stream) {
+    const char* who = "rl_keyword_store_count";
+    if (!st) return fail(RL_ERR_INVALID, std::string(who) + ": null store");
+    if (n_terms < 0) return fail(RL_ERR_INVALID, std::string(who) + ": negative size");
+    if (mem != RL_MEM_HOST && mem != RL_MEM_DEVICE) return fail(RL_ERR_INVALID, std::string(who) + ": bad mem");
+    hipStream_t s = as_stream(stream);
+    std::lock_guard<std::mutex> lock(st->mu);
+    if ((int64_t)st->max_id >= (int64_t)n_terms) return fail(RL_ERR_INVALID, std::string(who) + ": the store holds a term id >= n_terms");
+    if (term_rank && mem == RL_MEM_HOST) {
+        std::vector<bool> seen((size_t)n_terms, false);
+        for (int32_t t = 0; t < n_terms; ++t) {
+            if (term_rank[t] < 0 || term_rank[t] >= n_terms || seen[(size_t)term_rank[t]])
+                return fail(RL_ERR_INVALID, std::string(who) + ": term_rank must be a permutation of [0, n_terms)");
+            seen[(size_t)term_rank[t]] = true;
+        }
+    }
+    st->drop_count();
+    const hipMemcpyKind out_kind = mem == RL_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
+    const int64_t n = st->n_chunks;
+    int64_t m = 0, np = 0;  // live tokens, postings
+    Pool &lens = st->lens, &offs = st->offs, &scan_scratch = st->scan_scratch;  // (kept by the store: see its declaration)
+    if (n > 0) {
+        RL_TRY(reserve_amortised(lens, (size_t)n * sizeof(int64_t), who));
+        RL_TRY(reserve_amortised(offs, (size_t)n * sizeof(int64_t), who));
+        RL_TRY(reserve_amortised(scan_scratch, kb_scan_scratch_items(n) * sizeof(int64_t), who));
+        RL_TRY(launch_kb_lengths(st->tok_off, st->live, n, lens.as<int64_t>(), s));
+        RL_HIP(hipMemcpyAsync(offs.p, lens.p, (size_t)n * sizeof(int64_t), hipMemcpyDeviceToDevice, s));
+        const int64_t* d_total;
+        RL_TRY(launch_kb_exclusive_scan(offs.as<int64_t>(), n, scan_scratch.as<int64_t>(), &d_total, s));
+        RL_HIP(hipMemcpyAsync(&m, d_total, sizeof(int64_t), hipMemcpyDeviceToHost, s));
+        RL_HIP(hipStreamSynchronize(s));
+        if (m < 0 || m > st->n_tokens) return fail(RL_ERR_HIP, std::string(who) + ": inconsistent token count");
+    }
+    DevArray<int64_t> term_off;
+    DevArray<int32_t> post_chunk;
+    DevArray<int32_t>&post_term = st->post_term, &post_tf = st->post_tf;
+    Pool& df = st->df;
+    RL_TRY(term_off.alloc((size_t)(n_terms + 1) * sizeof(int64_t), who));
+    RL_TRY(reserve_amortised(df, std::max<size_t>((size_t)n_terms * sizeof(int64_t), 16), who));
+    if (m > 0) {
+        Pool &sortbuf = st->sortbuf, &table = st->table, &heads = st->heads, &head_pos = st->head_pos;
+        DevBuf t_rank;
+        const int32_t* d_rank = nullptr;
+        if (term_rank) RL_TRY(stage_in(term_rank, (size_t)n_terms, mem, s, t_rank, &d_rank));
+        const size_t plane = ((size_t)m * 4 + 255) & ~size_t(255);
+        RL_TRY(reserve_amortised(sortbuf, 4 * plane, who));  // keys and values, twice: the passes go back and forth
+        uint32_t* keys[2] = {reinterpret_cast<uint32_t*>(sortbuf.as<char>()), reinterpret_cast<uint32_t*>(sortbuf.as<char>() + 2 * plane)};
+        int32_t* vals[2] = {reinterpret_cast<int32_t*>(sortbuf.as<char>() + plane), reinterpret_cast<int32_t*>(sortbuf.as<char>() + 3 * plane)};
+        const int64_t table_items = 256 * kb_sort_blocks(m);
+        RL_TRY(reserve_amortised(table, (size_t)table_items * sizeof(int64_t), who));
+        RL_TRY(reserve_amortised(scan_scratch, std::max(kb_scan_scratch_items(table_items), kb_scan_scratch_items(kb_rle_blocks(m))) * sizeof(int64_t), who));
+        RL_TRY(launch_kb_emit(st->tok_off, st->tok_term, st->live, offs.as<int64_t>(), d_rank, n_terms, n, st->n_tokens, m, keys[0], vals[0], s));
+        int at = 0;
+        for (int pass = 0; pass < kb_sort_passes(n_terms); ++pass, at ^= 1)
+            RL_TRY(launch_kb_sort_pass(keys[at], vals[at], m, pass, table.as<int64_t>(), scan_scratch.as<int64_t>(), keys[at ^ 1], vals[at ^ 1], s));
+        RL_TRY(reserve_amortised(heads, (size_t)kb_rle_blocks(m) * sizeof(int64_t), who));
+        RL_TRY(launch_kb_rle_count(keys[at], vals[at], m, heads.as<int64_t>(), s));
+        const int64_t* d_total;
+        RL_TRY(launch_kb_exclusive_scan(heads.as<int64_t>(), kb_rle_blocks(m), scan_scratch.as<int64_t>(), &d_total, s));
+        RL_HIP(hipMemcpyAsync(&np, d_total, sizeof(int64_t), hipMemcpyDeviceToHost, s));
+        RL_HIP(hipStreamSynchronize(s));
+        if (np < 1 || np > m) return fail(RL_ERR_HIP, std::string(who) + ": inconsistent posting count");
+        RL_TRY(reserve_amortised(post_term, (size_t)np * sizeof(int32_t), who));
+        RL_TRY(post_chunk.alloc((size_t)np * sizeof(int32_t), who));
+        RL_TRY(reserve_amortised(post_tf, (size_t)np * sizeof(int32_t), who));
+        RL_TRY(reserve_amortised(head_pos, (size_t)np * sizeof(int64_t), who));
+        RL_TRY(launch_kb_rle_write(keys[at], vals[at], m, heads.as<int64_t>(), np, post_term, post_chunk, post_tf, head_pos.as<int64_t>(), s));
+        RL_TRY(launch_kb_term_off(post_term, np, n_terms, term_off, df.as<int64_t>(), s));
+        RL_HIP(hipStreamSynchronize(s));  // t_rank goes with this scope
+        g_pinned.drain();
+    } else {  // no chunks, or no live tokens: what rl_keyword_index_create holds for empty arrays
+        RL_TRY(reserve_amortised(post_term, 16, who));
+        RL_TRY(post_chunk.alloc(16, who));
+        RL_TRY(reserve_amortised(post_tf, 16, who));
+        RL_HIP(hipMemsetAsync(term_off.p, 0, (size_t)(n_terms + 1) * sizeof(int64_t), s));
+        RL_HIP(hipMemsetAsync(df.p, 0, std::max<size_t>((size_t)n_terms * sizeof(int64_t), 16), s));
+    }
+    if (out_df && n_terms > 0) RL_HIP(hipMemcpyAsync(out_df, df.p, (size_t)n_terms * sizeof(int64_t), out_kind, s));
+    if (out_length && n > 0) RL_HIP(hipMemcpyAsync(out_length, lens.p, (size_t)n * sizeof(int64_t), out_kind, s));
+    const int64_t totals[3] = {st->n_live, m, np};
+    if (out_totals) {
+        if (mem == RL_MEM_HOST) std::memcpy(out_totals, totals, sizeof(totals));
+        else RL_HIP(hipMemcpyAsync(out_totals, totals, sizeof(totals), hipMemcpyHostToDevice, s));
+    }
+    RL_HIP(hipStreamSynchronize(s));  // `totals` goes with this frame
+    st->term_off = std::move(term_off);
+    st->post_chunk = std::move(post_chunk);
+    st->c_terms = n_terms;
+    st->c_postings = np;
+    st->c_chunks = n;
+    st->counted = true;
+    return RL_OK;
+}
+
+int rl_keyword_store_build(rl_keyword_store* st, const float* idf, const float* nrm, rl_keyword_index** out, int mem, void* stream) {
+    const char* who = "rl_keyword_store_build";
+    if (!out) return fail(RL_ERR_INVALID, std::string(who) + ": null output handle");
+    *out = nullptr;
+    if (!st) return fail(RL_ERR_INVALID, std::string(who) + ": null store");
+    if (mem != RL_MEM_HOST && mem != RL_MEM_DEVICE) return fail(RL_ERR_INVALID, std::string(who) + ": bad mem");
+    hipStream_t s = as_stream(stream);
+    std::lock_guard<std::mutex> lock(st->mu);
+    if (!st->counted)
+        return fail(RL_ERR_INVALID, std::string(who) + ": no rl_keyword_store_count since the store was created, appended to, deleted from or built");
+    if ((st->c_terms > 0 && !idf) || (st->c_chunks > 0 && !nrm)) return fail(RL_ERR_INVALID, std::string(who) + ": null argument");
+    std::unique_ptr<rl_keyword_index> kw;
+    RL_TRY(new_keyword_index(st->c_terms, st->c_postings, st->c_chunks, &kw));
+    RL_TRY(kw->post_impact.alloc(std::max<size_t>((size_t)st->c_postings * sizeof(float), 16), who));
+    DevBuf t_idf, t_nrm;
+    const float *d_idf, *d_nrm;
+    RL_TRY(stage_in(idf, (size_t)st->c_terms, mem, s, t_idf, &d_idf));
+    RL_TRY(stage_in(nrm, (size_t)st->c_chunks, mem, s, t_nrm, &d_nrm));
+    RL_TRY(launch_bm25_impact(st->post_chunk, st->post_tf, st->post_term, d_idf, d_nrm, st->c_postings, st->c_terms, st->c_chunks, kw->post_impact, s));
+    RL_HIP(hipStreamSynchronize(s));  // the staging buffers and the caller's arrays may go away after return
+    g_pinned.drain();
+    kw->term_off = std::move(st->term_off);  // the counted postings become the index: no copy
+    kw->post_chunk = std::move(st->post_chunk);
+    st->drop_count();
+    *out = kw.release();
     return RL_OK;
 }
 

@@ -352,6 +352,28 @@ int launch_bm25_score(const int64_t* term_off, const int32_t* post_chunk, const 
                       int64_t ld, hipStream_t s);
 int launch_bm25_count(const float* sel, int32_t n_queries, int32_t k, int32_t* counts, hipStream_t s);  // finite entries per selected row
 
+// keyword_build.hip: the postings of a device token store (rl_keyword_store_count drives these in this order)
+int launch_kb_minmax(const int32_t* ids, int64_t n, int32_t* out /* [2]: min, max; folded into what they hold */, hipStream_t s);
+int launch_kb_lengths(const int64_t* tok_off, const uint8_t* live, int64_t n_chunks, int64_t* length, hipStream_t s);
+// data [n] (n >= 1) -> its exclusive scan, in place; scratch: kb_scan_scratch_items(n) int64; *total: where the sum of all lands (device)
+size_t kb_scan_scratch_items(int64_t n);
+int launch_kb_exclusive_scan(int64_t* data, int64_t n, int64_t* scratch, const int64_t** total, hipStream_t s);
+// keys / vals [m]: (term_rank[tok_term] or tok_term itself, chunk) of the live chunks' tokens in token order; out_off: scanned lengths
+int launch_kb_emit(const int64_t* tok_off, const int32_t* tok_term, const uint8_t* live, const int64_t* out_off, const int32_t* term_rank,
+                   int32_t n_terms, int64_t n_chunks, int64_t n_tokens, int64_t m, uint32_t* keys, int32_t* vals, hipStream_t s);
+int kb_sort_passes(int32_t n_terms);  // 8-bit digits that cover n_terms - 1, at least one
+int64_t kb_sort_blocks(int64_t m);    // blocks of a sort pass; its table holds 256 * that many int64
+// one stable pass on digit `pass` of the keys: histogram, scan of the (digit, block) table, scatter
+int launch_kb_sort_pass(const uint32_t* keys_in, const int32_t* vals_in, int64_t m, int pass, int64_t* table, int64_t* scan_scratch,
+                        uint32_t* keys_out, int32_t* vals_out, hipStream_t s);
+int64_t kb_rle_blocks(int64_t m);
+int launch_kb_rle_count(const uint32_t* keys, const int32_t* vals, int64_t m, int64_t* heads /* [kb_rle_blocks(m)] */, hipStream_t s);
+// heads: scanned; post_term / post_chunk / post_tf [n_postings]; head_pos [n_postings]: scratch
+int launch_kb_rle_write(const uint32_t* keys, const int32_t* vals, int64_t m, const int64_t* heads, int64_t n_postings, int32_t* post_term,
+                        int32_t* post_chunk, int32_t* post_tf, int64_t* head_pos, hipStream_t s);
+int launch_kb_term_off(const int32_t* post_term, int64_t n_postings, int32_t n_terms, int64_t* term_off /* [n_terms + 1] */,
+                       int64_t* df /* [n_terms] or null */, hipStream_t s);
+
 // fuse.hip: weighted Reciprocal Rank Fusion of n_lists ranked lists per query (lists [n_lists x n_queries x len] int32, < 0 = padding)
 // -> the top k by (float64 score desc, first occurrence asc), bit for bit the reference's reciprocal_rank_fusion
 constexpr int32_t RRF_MAX_LISTS = 4;
