@@ -38,6 +38,10 @@ typedef enum {
 } rl_status;
 
 typedef enum { RL_MEM_HOST = 0, RL_MEM_DEVICE = 1 } rl_mem;
+/* A flag or-ed into `mem` of the calls that take `chunk_filter` / `chunk_filters`: that argument ALONE is a device pointer,
+ * read in place and not copied (e.g. rl_filter_set_bits' table); every other pointer follows `mem & 1`.  The work is
+ * enqueued on `stream` after whatever that stream holds, so a table written on the same stream is complete when it is read. */
+#define RL_MEM_FILTERS_DEVICE 2
 /* How an index multiplies queries with its corpus in the MFMA streaming kernel (rl_index_set_arithmetic). */
 typedef enum {
     RL_ARITH_AUTO = 0,       /* request: RL_ARITH_F16_SPLIT where the corpus allows it, else RL_ARITH_FP32_EXACT */
@@ -601,7 +605,8 @@ int rl_search_chunks_ranked(rl_index* index, const float* queries, int32_t n_que
  * it alone, with its own filter and limit (the same ids, score bits and count).  The single-filter calls run the same
  * device path (one filter, every query mapped to it, one limit for all).
  *   chunk_filters  uint32 [n_filters x (n_chunks + 31) / 32], each row a bitset as in the *_filtered calls; host or
- *                  device memory per `mem`.  NULL only when n_filters == 0.
+ *                  device memory per `mem` (device memory whatever the rest is with RL_MEM_FILTERS_DEVICE or-ed into
+ *                  `mem`).  NULL only when n_filters == 0.
  *   query_filter   int32 [n_queries], ALWAYS host memory: -1 = the query has no filter, else a row of chunk_filters.
  *                  NULL: no query has a filter.
  *   rank_limits    int64 [n_queries], ALWAYS host memory (not in the keyword call): each >= 0, as rank_limit of
@@ -703,6 +708,41 @@ int rl_search_rerank_spans_per_query(rl_index* index, rl_keyword_index* kw, cons
                                      const int32_t* offsets, int32_t n_off, int32_t* out_top_chunks, int32_t* out_top_counts,
                                      int32_t* out_chunks, int32_t* out_span_len, double* out_span_scores, int32_t* out_n_spans,
                                      int32_t* out_n_chunks, int mem, void* stream);
+
+/* ---- metadata filters on the device ---------------------------------------------------------------------------------------
+ * The reference's metadata filter is JSON containment (src/raglite/_search.py:82-94): a chunk matches when, for every key of
+ * the filter, every wanted value occurs among the chunk's values.  The host numbers the (key, value) pairs ("tags",
+ * raglite_amd/_metadata.py); an rl_metadata_store holds every chunk's tags beside the rl_index whose chunk ordinals it follows,
+ * as a CSR: tag_off int64 [n_chunks + 1] from 0, ascending, and tags int32 [tag_off[n_chunks]], each chunk's list ASCENDING
+ * and free of duplicates (fewer than 2^31 tags in all).  rl_metadata_store_append adds n_new chunks at the end (tag_off
+ * [n_new + 1] from 0) with amortised capacity.  Deleting chunks needs no call: tombstoned chunks are evaluated like any other
+ * (the searches and-in the live rows); after rl_index_compact the store is made anew.  rl_metadata_store_memory: out[0] the
+ * bytes the two arrays use, out[1] the bytes reserved.  The arrays are host or device memory per `mem`; create and append
+ * synchronise the stream.
+ *
+ * rl_metadata_filters evaluates n_filters filters in one launch.  Filter j is the tags f_tags[f_off[j] .. f_off[j + 1])
+ * (f_off int64 [n_filters + 1] from 0, ascending; any order; host or device per `mem`) and matches the chunks whose list
+ * holds every one of them: a filter without tags matches every chunk, a tag that no chunk carries -- INT32_MAX is never a
+ * chunk's tag -- matches none.  The results stay on the device in *inout_set (NULL: a new set; else reused, grown if too small,
+ * so a warm call allocates nothing): rl_filter_set_bits gives the table uint32 [n_filters x (n_chunks + 31) / 32] in the layout
+ * of `chunk_filters`, the bits past n_chunks zero, which the *_per_query calls read in place under RL_MEM_FILTERS_DEVICE.
+ * out_chunks[j] is the number of matching chunks and out_rows[j] the sum of their embedding rows (the index's chunk offsets):
+ * what decides filter first or order first.  Both count tombstoned chunks, as the bits do, and are exact (integer atomics).
+ * store->n_chunks != index->n_chunks is RL_ERR_INVALID.  Arguments that need no handle are checked first.  With RL_MEM_HOST the
+ * call returns after the counts have arrived; with RL_MEM_DEVICE everything is enqueued on `stream`. */
+typedef struct rl_metadata_store rl_metadata_store;
+typedef struct rl_filter_set rl_filter_set;
+int rl_metadata_store_create(rl_metadata_store** out, const int64_t* tag_off, const int32_t* tags, int64_t n_chunks, int mem,
+                             void* stream);
+int rl_metadata_store_append(rl_metadata_store* store, const int64_t* tag_off, const int32_t* tags, int64_t n_new, int mem,
+                             void* stream);
+int rl_metadata_store_memory(const rl_metadata_store* store, int64_t out[2]);
+int rl_metadata_store_destroy(rl_metadata_store* store);
+int rl_metadata_filters(rl_metadata_store* store, rl_index* index, const int64_t* f_off, const int32_t* f_tags, int32_t n_filters,
+                        rl_filter_set** inout_set, int64_t* out_chunks, int64_t* out_rows, int mem, void* stream);
+int rl_filter_set_bits(const rl_filter_set* set, const uint32_t** out_device_bits, int32_t* out_n_filters, int64_t* out_words);
+int rl_filter_set_read(const rl_filter_set* set, uint32_t* out, int mem, void* stream); /* a copy of the table (tests, tools) */
+int rl_filter_set_destroy(rl_filter_set* set);
 
 /* ---- device half of update_query_adapter ----------------------------------
  * src/raglite/_query_adapter.py:153-205 fits the query adapter from evals: per eval a vector search

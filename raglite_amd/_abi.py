@@ -20,6 +20,7 @@ LIB_PATH = Path(os.environ.get("RAGLITE_HIP_LIB") or Path(__file__).resolve().pa
 
 RL_OK, RL_ERR_INVALID, RL_ERR_HIP, RL_ERR_UNSUPPORTED, RL_ERR_NOMEM = 0, -1, -2, -3, -4
 MEM_HOST, MEM_DEVICE = 0, 1
+MEM_FILTERS_DEVICE = 2  # RL_MEM_FILTERS_DEVICE, or-ed into `mem`: the filter table alone is a device pointer
 METRICS = {"cosine": 0, "dot": 1, "l2": 2}
 SYNTH_KINDS = {"uniform": 0, "small_int": 1}
 # rl_option (include/raglite_hip.h "options"): route switches of an index; the library reads no environment variable
@@ -145,6 +146,14 @@ _SIGNATURES = {
     "rl_search_rerank_spans_per_query": [c_void_p, c_void_p, c_void_p, c_i32, c_i32, c_i32, c_void_p, c_void_p, c_void_p, c_i32, c_void_p,
                                          c_void_p, c_void_p, c_i32, c_i32, c_void_p, c_i32, c_i32, c_void_p, c_void_p, c_i32, c_void_p,
                                          c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p],
+    "rl_metadata_store_create": [C.POINTER(c_void_p), c_void_p, c_void_p, c_i64, c_int, c_void_p],
+    "rl_metadata_store_append": [c_void_p, c_void_p, c_void_p, c_i64, c_int, c_void_p],
+    "rl_metadata_store_memory": [c_void_p, C.POINTER(c_i64)],
+    "rl_metadata_store_destroy": [c_void_p],
+    "rl_metadata_filters": [c_void_p, c_void_p, c_void_p, c_void_p, c_i32, C.POINTER(c_void_p), c_void_p, c_void_p, c_int, c_void_p],
+    "rl_filter_set_bits": [c_void_p, C.POINTER(c_void_p), C.POINTER(c_i32), C.POINTER(c_i64)],
+    "rl_filter_set_read": [c_void_p, c_void_p, c_int, c_void_p],
+    "rl_filter_set_destroy": [c_void_p],
 }
 COMM_ID_BYTES = 128
 _RESTYPES = {"rl_last_error": c_char_p}

@@ -15,7 +15,7 @@ from typing import Any
 import numpy as np
 
 from raglite_amd import _abi
-from raglite_amd._abi import MEM_DEVICE, MEM_HOST, METRICS, SYNTH_KINDS, check, lib
+from raglite_amd._abi import MEM_DEVICE, MEM_FILTERS_DEVICE, MEM_HOST, METRICS, SYNTH_KINDS, check, lib
 
 K_MAX = 2048
 
@@ -44,6 +44,12 @@ class _Args:
         self.mem: int | None = None
         self.device = None
         self.keep: list[Any] = []
+        self.filters_flag = 0  # MEM_FILTERS_DEVICE once the call's filter table is a `FilterSet` (device memory whatever the rest is)
+
+    @property
+    def call_mem(self) -> int:
+        """`mem` of a call that takes filters."""
+        return self.mem | self.filters_flag
 
     def _side(self, mem: int, device=None) -> None:
         if self.mem is None:
@@ -419,6 +425,127 @@ def _rank_limits(rank_limit, B: int) -> np.ndarray | None:
     return lim
 
 
+class FilterSet:
+    """Chunk bitsets on the device (`rl_filter_set`): what `MetadataStore.filters` writes and the *_per_query searches read in place
+    (RL_MEM_FILTERS_DEVICE).  `n_filters` rows of `words` uint32 in the layout of `chunk_filters`.  `query_filter` (int32 per query,
+    -1: none) maps a batch's queries to rows: `select` gives the set with a map, which `DeviceIndex.search_chunks(query_filters=)` and
+    its kin and `KeywordIndex.search(query_filters=)` take in place of a list of masks.  Reused across calls it grows and never
+    shrinks, so a warm call allocates nothing."""
+
+    def __init__(self) -> None:
+        self._handle = C.c_void_p()  # (null until the first `MetadataStore.filters`)
+        self._owner: FilterSet | None = None
+        self.n_filters, self.words = 0, 0
+        self.query_filter: np.ndarray | None = None
+
+    def select(self, query_filter) -> "FilterSet":
+        """This set (not a copy: the same device table) with `query_filter` as its map."""
+        view = FilterSet()
+        view._owner = self._owner or self  # (the handle stays the owner's: a view of a closed set is an error, not a stale pointer)
+        view.n_filters, view.words = self.n_filters, self.words
+        view.query_filter = np.ascontiguousarray(query_filter, dtype=np.int32).ravel()
+        return view
+
+    def _bits(self) -> int | None:
+        p, n, w = C.c_void_p(), C.c_int32(0), C.c_int64(0)
+        check(lib().rl_filter_set_bits((self._owner or self)._handle, C.byref(p), C.byref(n), C.byref(w)))
+        if (int(n.value), int(w.value)) != (self.n_filters, self.words):
+            raise ValueError("FilterSet: the set was written again after this view of it was taken")
+        return p.value
+
+    def call_args(self, n_chunks: int, B: int):
+        """(device pointer of the table, n_filters, query_filter int32 [B]) for a *_per_query call over `n_chunks` chunks."""
+        qf = self.query_filter
+        if qf is None or qf.size != B:
+            raise ValueError(f"FilterSet.query_filter must have one entry per query ({0 if qf is None else qf.size} for {B} queries)")
+        if self.n_filters and self.words != (n_chunks + 31) // 32:
+            raise ValueError("chunk_filter must have one entry per chunk")
+        if qf.size and (qf.min() < -1 or qf.max() >= self.n_filters):
+            raise ValueError("FilterSet.query_filter entries must be -1 or a row of the set")
+        return (self._bits() if self.n_filters else None), self.n_filters, qf
+
+    def read(self) -> np.ndarray:
+        """A host copy of the table, uint32 [n_filters x words]."""
+        out = np.zeros((self.n_filters, self.words), np.uint32)
+        if out.size:
+            check(lib().rl_filter_set_read((self._owner or self)._handle, out.ctypes.data, MEM_HOST, None))
+        return out
+
+    def close(self) -> None:
+        h, self._handle = getattr(self, "_handle", None), C.c_void_p()
+        if h and getattr(self, "_owner", None) is None:
+            lib().rl_filter_set_destroy(h)
+        self.n_filters = self.words = 0
+
+    def __del__(self) -> None:  # noqa: D105
+        try:
+            self.close()
+        except Exception:  # noqa: BLE001,S110 - interpreter shutdown
+            pass
+
+
+class MetadataStore:
+    """Every chunk's metadata tags on the device (`rl_metadata_store`), beside the `DeviceIndex` whose chunk ordinals it follows:
+    `tag_off` int64 [n_chunks + 1] and `tags` int32, each chunk's ids ascending and free of duplicates
+    (`raglite_amd._metadata.TagVocabulary.encode_chunks`).  Deleting chunks needs no call; after a compaction the store is made anew."""
+
+    def __init__(self, tag_off, tags) -> None:
+        tag_off, tags = self._csr(tag_off, tags)
+        _ensure_init(_current_device())
+        handle = C.c_void_p()
+        check(lib().rl_metadata_store_create(C.byref(handle), tag_off.ctypes.data, tags.ctypes.data, int(tag_off.size - 1), MEM_HOST, None))
+        self._handle = handle
+        self.n_chunks = int(tag_off.size - 1)
+
+    @staticmethod
+    def _csr(tag_off, tags) -> tuple[np.ndarray, np.ndarray]:
+        tag_off = np.ascontiguousarray(tag_off, dtype=np.int64)
+        tags = np.ascontiguousarray(tags, dtype=np.int32)
+        if tag_off.ndim != 1 or tag_off.size < 1 or tags.ndim != 1 or int(tag_off[-1]) != tags.size:
+            raise ValueError("MetadataStore: tag_off must hold one entry per chunk plus one and end at len(tags)")
+        return tag_off, tags
+
+    def append(self, tag_off, tags) -> None:
+        """New chunks at the end (`tag_off` from 0)."""
+        tag_off, tags = self._csr(tag_off, tags)
+        _ensure_init(_current_device())
+        check(lib().rl_metadata_store_append(self._handle, tag_off.ctypes.data, tags.ctypes.data, int(tag_off.size - 1), MEM_HOST, None))
+        self.n_chunks += int(tag_off.size - 1)
+
+    def memory(self) -> tuple[int, int]:
+        """(device bytes used, device bytes reserved)."""
+        out = (C.c_int64 * 2)()
+        check(lib().rl_metadata_store_memory(self._handle, out))
+        return int(out[0]), int(out[1])
+
+    def filters(self, index: "DeviceIndex", f_off, f_tags, filter_set: FilterSet | None = None):
+        """`rl_metadata_filters`: filter j wants the tags f_tags[f_off[j] : f_off[j + 1]].  Returns (the `FilterSet` holding the F
+        bitsets -- `filter_set` reused, or a new one --, matching chunks int64 [F], their embedding rows int64 [F]); tombstoned chunks
+        count like any other.  One launch and one read-back of 16 bytes per filter."""
+        f_off, f_tags = self._csr(f_off, f_tags)
+        F = int(f_off.size - 1)
+        fs = filter_set if filter_set is not None else FilterSet()
+        if fs._owner is not None:  # noqa: SLF001
+            raise ValueError("MetadataStore.filters writes a FilterSet itself, not a view of one")
+        chunks, rows = np.zeros(F, np.int64), np.zeros(F, np.int64)
+        _ensure_init(_current_device())
+        check(lib().rl_metadata_filters(self._handle, index._handle, f_off.ctypes.data, f_tags.ctypes.data, F, C.byref(fs._handle),  # noqa: SLF001
+                                        chunks.ctypes.data, rows.ctypes.data, MEM_HOST, None))
+        fs.n_filters, fs.words = F, (self.n_chunks + 31) // 32
+        return fs, chunks, rows
+
+    def close(self) -> None:
+        h, self._handle = getattr(self, "_handle", None), None
+        if h:
+            lib().rl_metadata_store_destroy(h)
+
+    def __del__(self) -> None:  # noqa: D105
+        try:
+            self.close()
+        except Exception:  # noqa: BLE001,S110 - interpreter shutdown
+            pass
+
+
 class DeviceIndex:
     """Device-resident chunk-embedding matrix + chunk CSR: the GPU image of the reference's
     `chunk_embedding` table (`src/raglite/_database.py:403-430`).
@@ -525,6 +652,12 @@ class DeviceIndex:
             return False, (self._filter(a, chunk_filter), int(rank_limit or 0))
         if query_filters is not None and chunk_filter is not None:
             raise ValueError("pass chunk_filter (one for the batch) or query_filters (one per query), not both")
+        if isinstance(query_filters, FilterSet):  # the table is on the device already: its pointer goes in as it is, with the flag
+            p_f, n_filters, qf = query_filters.call_args(self.n_chunks, B)
+            lim = _rank_limits(rank_limit, B)
+            a.keep += [query_filters, qf, lim]
+            a.filters_flag = MEM_FILTERS_DEVICE
+            return True, (p_f, n_filters, qf.ctypes.data, None if lim is None else lim.ctypes.data)
         table, qf = filter_set([chunk_filter] * B if query_filters is None else query_filters, self.n_chunks, B)
         lim = _rank_limits(rank_limit, B)
         a.keep += [qf, lim]
@@ -753,7 +886,7 @@ class DeviceIndex:
         per_query, args = self._per_query(a, B, chunk_filter, query_filters, rank_limit)
         self._prep(a)
         if per_query:
-            check(lib().rl_search_chunks_per_query(self._handle, p_q, B, num_hits, k, *args, p_s, p_c, p_n, a.mem, a.stream))
+            check(lib().rl_search_chunks_per_query(self._handle, p_q, B, num_hits, k, *args, p_s, p_c, p_n, a.call_mem, a.stream))
         else:
             check(lib().rl_search_chunks_ranked(self._handle, p_q, B, num_hits, k, *args, p_s, p_c, p_n, a.mem, a.stream))
         return (o_s[0], o_c[0], o_n[0]) if single else (o_s, o_c, o_n)
@@ -788,7 +921,7 @@ class DeviceIndex:
         self._prep(a)
         fn = lib().rl_hybrid_search_per_query if per_query else lib().rl_hybrid_search
         check(fn(self._handle, None if keyword is None else keyword._handle, p_q, B, int(num_hits), int(n_each), p_off, p_terms, *args,
-                 w.ctypes.data, int(rrf_k), int(k), p_s, p_c, p_n, a.mem, a.stream))
+                 w.ctypes.data, int(rrf_k), int(k), p_s, p_c, p_n, a.call_mem if per_query else a.mem, a.stream))
         return (o_s[0], o_c[0], o_n[0]) if single else (o_s, o_c, o_n)
 
     def _search_rerank_args(self, a, queries, query_vecs, keyword, query_term_ids, weights, chunk_filter, rank_limit, query_filters):
@@ -843,7 +976,7 @@ class DeviceIndex:
         self._prep(a)
         check(lib().rl_search_rerank_per_query(self._handle, None if keyword is None else keyword._handle, p_q, B, int(num_hits), int(n_each),
                                                p_off, p_terms, *args, w.ctypes.data, int(rrf_k), int(n_cand), p_v, nq, int(k), p_s, p_c,
-                                               p_n, a.mem, a.stream))
+                                               p_n, a.call_mem, a.stream))
         return o_s, o_c, o_n
 
     def search_rerank_spans(self, queries, num_hits: int, n_each: int, n_cand: int, query_vecs, k: int, spans: "SpanTable",
@@ -870,7 +1003,7 @@ class DeviceIndex:
         check(lib().rl_search_rerank_spans_per_query(self._handle, None if keyword is None else keyword._handle, p_q, B, int(num_hits),
                                                      int(n_each), p_off, p_terms, *args, w.ctypes.data, int(rrf_k), int(n_cand), p_v, nq,
                                                      int(k), spans._handle, offs.ctypes.data if offs.size else None, int(offs.size), p_tc,
-                                                     p_tn, p_oc, p_ol, p_os, p_ns, p_nc, a.mem, a.stream))
+                                                     p_tn, p_oc, p_ol, p_os, p_ns, p_nc, a.call_mem, a.stream))
         return o_tc, o_tn, o_c, o_l, o_s, o_ns, o_nc
 
     # -- a9 ----------------------------------------------------------------------------------------
@@ -1079,10 +1212,14 @@ class KeywordIndex:
         if query_filters is not None:
             if chunk_filter is not None:
                 raise ValueError("pass chunk_filter (one for the batch) or query_filters (one per query), not both")
-            table, qf = filter_set(query_filters, self.n_chunks, B)
-            check(lib().rl_keyword_search_per_query(self._handle, q_off.ctypes.data, q_terms.ctypes.data, B, k,
-                                                    table.ctypes.data if len(table) else None, len(table), qf.ctypes.data,
-                                                    scores.ctypes.data, chunks.ctypes.data, counts.ctypes.data, MEM_HOST, None))
+            if isinstance(query_filters, FilterSet):
+                p_f, n_filters, qf = query_filters.call_args(self.n_chunks, B)
+                mem = MEM_HOST | MEM_FILTERS_DEVICE
+            else:
+                table, qf = filter_set(query_filters, self.n_chunks, B)
+                p_f, n_filters, mem = table.ctypes.data if len(table) else None, len(table), MEM_HOST
+            check(lib().rl_keyword_search_per_query(self._handle, q_off.ctypes.data, q_terms.ctypes.data, B, k, p_f, n_filters,
+                                                    qf.ctypes.data, scores.ctypes.data, chunks.ctypes.data, counts.ctypes.data, mem, None))
             return scores, chunks, counts
         p_f = None
         if chunk_filter is not None:

@@ -30,13 +30,14 @@ store, ORM and HNSW index are out of scope.
 
 from __future__ import annotations
 
+import threading
 from dataclasses import dataclass, field
 from functools import partial
 from typing import Any, Callable, Sequence
 
 import numpy as np
 
-from raglite_amd import _keyword, _ops
+from raglite_amd import _keyword, _metadata, _ops
 from raglite_amd._config import DEFAULT_CHUNK_MAX_SIZE, HotPathConfig
 from raglite_amd._embed import embed_strings
 
@@ -61,6 +62,10 @@ class GpuIndex:
     keyword_build    "device" (the default): the chunks' term ids stay on the device (`KeywordStore`) and every rebuild of the postings
                      runs there; "host": the postings are rebuilt on the host and uploaded (the oracle of the device
                      build, and its A/B path).  Every result is the same either way.
+    metadata_filters "device" (the default): the chunks' metadata stays on the device as tag lists (`MetadataStore`) and every
+                     `metadata_filter` is evaluated there, its bitset handed to the search without a trip through the host (DESIGN.md
+                     4.13); "host": the filters are evaluated by a Python loop over `metadata` (the oracle of the device evaluation,
+                     and its A/B path).  Every result is the same either way.
     positions        optional list of (document_id: str, index: int) -- `Chunk.document_id` / `Chunk.index` per chunk
                      (`_database.py:207-224`; None: the chunk has no position): builds the span table (`retrieve_chunk_spans`;
                      DESIGN.md 4.11), rebuilt from the live chunks after every change
@@ -79,15 +84,22 @@ class GpuIndex:
     # span side (class defaults: an index without one): each chunk's (document_id, index) (None once deleted) and the device table
     positions: list | None = None
     spans: _ops.SpanTable | None = None
+    # metadata_filters="device": the stable tag ids (host) and the chunks' tag lists on the device
+    metadata_filters: str = "device"
+    _meta_vocab: _metadata.TagVocabulary | None = None
+    _meta_store: _ops.MetadataStore | None = None
 
     def __init__(self, chunk_ids: Sequence[ChunkId], chunk_embeddings, *, chunk_offsets=None,
                  metric: str = "cosine", query_adapter=None, docs: Sequence[str] | None = None,
                  metadata: Sequence[dict] | None = None, storage: str = "f32", exact_fp32: bool = False,
                  keyword_texts: Sequence[str] | None = None, positions: Sequence[tuple[str, int] | None] | None = None,
-                 keyword_build: str = "device") -> None:
+                 keyword_build: str = "device", metadata_filters: str = "device") -> None:
         if keyword_build not in ("device", "host"):
             raise ValueError('keyword_build must be "device" or "host"')
+        if metadata_filters not in ("device", "host"):
+            raise ValueError('metadata_filters must be "device" or "host"')
         self.keyword_build = keyword_build
+        self.metadata_filters = metadata_filters
         if chunk_offsets is None:
             mats = [np.asarray(m, dtype=np.float32).reshape(len(m), -1) for m in chunk_embeddings]
             sizes = np.asarray([len(m) for m in mats], dtype=np.int64)
@@ -108,6 +120,7 @@ class GpuIndex:
         self._doc_to_ordinal = None if docs is None else {d: i for i, d in enumerate(self.docs)}
         self.metadata = None if metadata is None else list(metadata)
         self._id_to_ordinal = {cid: i for i, cid in enumerate(self.chunk_ids)}
+        self._reset_metadata_store()
         if keyword_texts is not None:
             if len(keyword_texts) != len(self.chunk_ids):
                 raise ValueError("one keyword text per chunk is required")
@@ -128,6 +141,19 @@ class GpuIndex:
     @property
     def has_positions(self) -> bool:
         return self.positions is not None
+
+    def _reset_metadata_store(self) -> None:
+        """metadata_filters="device": a fresh tag vocabulary and store from `metadata`, by one upload of every chunk's tags (the
+        constructor, and `compact`, which renumbers the chunks).  Metadata that does not cover the chunks one to one has no store: the
+        host path answers, as before."""
+        old = self._meta_store
+        self._meta_vocab = self._meta_store = None
+        if self.metadata_filters == "device" and self.metadata is not None and len(self.metadata) == len(self.chunk_ids):
+            vocab = _metadata.TagVocabulary()
+            store = _ops.MetadataStore(*vocab.encode_chunks(self.metadata))
+            self._meta_vocab, self._meta_store = vocab, store
+        if old is not None:
+            old.close()
 
     def _rebuild_spans(self, positions: list) -> None:
         """The span table of `positions` (one per chunk ordinal; None: no position): documents are numbered in sorted(document_id)
@@ -241,6 +267,11 @@ class GpuIndex:
             self._doc_to_ordinal.update({d: base + i for i, d in enumerate(docs)})
         if metadata is not None:
             self.metadata.extend(metadata)
+            if self._meta_store is not None:  # only the new chunks' tags go to the device
+                if len(metadata) == len(mats):
+                    self._meta_store.append(*self._meta_vocab.encode_chunks(metadata))
+                else:
+                    self._reset_metadata_store()
         if keyword_texts is not None:
             stems = [_keyword.index_stems(t) for t in keyword_texts]
             self._kw_stems.extend(stems)
@@ -286,12 +317,12 @@ class GpuIndex:
     # -- the real store ----------------------------------------------------------------------
     @classmethod
     def from_store(cls, bind: Any, *, metric: str = "cosine", storage: str = "f32", exact_fp32: bool = False,
-                   keywords: bool = False, keyword_build: str = "device") -> "GpuIndex":
+                   keywords: bool = False, keyword_build: str = "device", metadata_filters: str = "device") -> "GpuIndex":
         """Build the device index from a RAGLite database: `chunk_embedding` rows ordered by (chunk_id, id)
         (`src/raglite/_database.py:403-430`), the chunks' `str(chunk)` text and metadata, and the stored query adapter
         (`:450-462`).  `bind`: SQLAlchemy Engine / Connection / Session or a database URL.  `metric` is the store's
         `vector_search_distance_metric` (`_config.py:69`).  `keywords`: also build the BM25 keyword side from `chunk.body`
-        (`keyword_build` as in the constructor).
+        (`keyword_build` as in the constructor).  `metadata_filters` as in the constructor.
         The index remembers `bind` for `sync()`."""
         from raglite_amd import _store
 
@@ -307,7 +338,7 @@ class GpuIndex:
         off = np.concatenate(([0], np.cumsum(np.asarray(img.sizes, dtype=np.int64)))).astype(np.int64)
         gi = cls(img.chunk_ids, img.matrix(), chunk_offsets=off, metric=metric, query_adapter=adapter, docs=img.docs,
                  metadata=img.metadata, storage=storage, exact_fp32=exact_fp32, keyword_texts=img.bodies if keywords else None,
-                 positions=img.positions, keyword_build=keyword_build)
+                 positions=img.positions, keyword_build=keyword_build, metadata_filters=metadata_filters)
         gi._bind = bind  # noqa: SLF001
         return gi
 
@@ -359,6 +390,7 @@ class GpuIndex:
             self._doc_to_ordinal = {d: i for i, d in enumerate(self.docs)}
         if self.metadata is not None:
             self.metadata = [self.metadata[i] for i in keep]
+            self._reset_metadata_store()  # (the ordinals changed: one upload of the kept chunks' tags)
         if self.has_keywords:
             self._kw_stems = [self._kw_stems[i] for i in keep]
             if self._kw_store is not None:  # (the ordinals changed: one upload of the kept chunks' ids)
@@ -376,6 +408,9 @@ class GpuIndex:
             self._kw_store.close()
         if self.spans is not None:
             self.spans.close()
+        if self._meta_store is not None:
+            self._meta_store.close()
+            self._meta_store = None
 
 
 # config (hashable, like the reference's lru_cache keys) -> GpuIndex
@@ -414,6 +449,36 @@ def _matches(meta: dict, flt: dict) -> bool:
         if any(w not in have for w in wanted):
             return False
     return True
+
+
+_filter_sets = threading.local()  # one `_ops.FilterSet` per thread, reused across calls: a warm evaluation allocates nothing
+
+
+class _DeviceMask:
+    """Stands where a filter's bool mask stands when its bitset is on the device: `n` chunks match (`any()` is what the searches'
+    decisions ask of a mask)."""
+
+    __slots__ = ("n",)
+
+    def __init__(self, n: int) -> None:
+        self.n = n
+
+    def any(self) -> bool:
+        return self.n > 0
+
+
+def _filters_on_device(gi: GpuIndex, filters: Sequence[dict]):
+    """Evaluate a call's distinct normalised filters on the device (`rl_metadata_filters`, one call): (the thread's `FilterSet` with
+    filter j's bitset in row j, matching chunks [F], their embedding rows [F]).  None where the host path must answer: the index keeps
+    no device metadata, or a filter is not encodable.  Tombstoned chunks count like any other, as in the loop over `gi.metadata`."""
+    if gi._meta_store is None or not filters:  # noqa: SLF001
+        return None
+    encoded = gi._meta_vocab.encode_filters(filters)  # noqa: SLF001
+    if encoded is None:
+        return None
+    fs, chunks, rows = gi._meta_store.filters(gi.index, *encoded, filter_set=getattr(_filter_sets, "set", None))  # noqa: SLF001
+    _filter_sets.set = fs
+    return fs, chunks, rows
 
 
 VECTOR_SEARCH_OVERSAMPLE = 4  # vector_search's default `oversample`: what hybrid_search's vector half runs with (`_search.py:36-41`)
@@ -477,6 +542,17 @@ def _filtered_search(gi: GpuIndex, q, num_hits: int, num_results: int, flt: dict
     differ only on a corpus of more than 1 000 000 rows."""
     if gi.metadata is None:
         raise ValueError(_NO_METADATA)
+    on_device = _filters_on_device(gi, [flt])
+    if on_device is not None:  # the same decisions from the device's counts; the bitset goes to the search where it is
+        fs, n_chunks, n_rows = on_device
+        if n_chunks[0] == 0:
+            return [], []
+        _check_limits(num_hits, num_results)
+        rank_limit = ORDER_FIRST_LIMIT if int(n_rows[0]) > FILTER_FIRST_MAX_ROWS else 0
+        scores, chunks, count = gi.index.search_chunks(np.asarray(q, dtype=np.float32), num_hits, num_results,
+                                                       query_filters=fs.select([0]), rank_limit=[rank_limit])
+        n = int(count)
+        return [gi.chunk_ids[c] for c in chunks[:n].tolist()], [float(s) for s in scores[:n]]
     allowed = np.fromiter((_matches(m, flt) for m in gi.metadata), dtype=bool, count=len(gi.metadata))
     if not allowed.any():
         return [], []
@@ -513,6 +589,13 @@ def keyword_search(query: str, *, num_results: int = 3, metadata_filter: dict | 
     if metadata_filter:
         if gi.metadata is None:
             raise ValueError(_NO_METADATA)
+        on_device = _filters_on_device(gi, [metadata_filter])
+        if on_device is not None:
+            if on_device[1][0] == 0:
+                return [], []
+            scores, chunks, counts = gi.keyword.search([ids], num_results, query_filters=on_device[0].select([0]))
+            n = int(counts[0])
+            return [gi.chunk_ids[c] for c in chunks[0, :n].tolist()], [float(x) for x in scores[0, :n]]
         allowed = np.fromiter((_matches(m, metadata_filter) for m in gi.metadata), dtype=bool, count=len(gi.metadata))
         if not allowed.any():
             return [], []
@@ -615,11 +698,13 @@ def _batch_filters(metadata_filter, B: int) -> list[dict | None]:
 class FilterPlan:
     """The metadata filters of a batch: `allowed[j]` is distinct filter j's bool mask over chunks (None on an index without metadata,
     where applying a filter raises), `rank_limit[j]` its branch (ORDER_FIRST_LIMIT: order first; 0: filter first) and
-    `query_filter[b]` the filter of query b (-1: none)."""
+    `query_filter[b]` the filter of query b (-1: none).  Evaluated on the device, `filter_set` holds filter j's bitset in row j and
+    `allowed[j]` only says whether any chunk matches (`_DeviceMask`)."""
 
     allowed: list = field(default_factory=list)
     rank_limit: list = field(default_factory=list)
     query_filter: list = field(default_factory=list)
+    filter_set: Any = None  # _ops.FilterSet
 
     def of(self, b: int):
         """(mask, rank limit) of query b: (None, 0) without a filter."""
@@ -627,26 +712,37 @@ class FilterPlan:
         return (None, 0) if j < 0 else (self.allowed[j], self.rank_limit[j])
 
 
-def plan_filters(filters: Sequence[dict | None], metadata: Sequence[dict] | None, rows_per_chunk: np.ndarray) -> FilterPlan:
-    """Evaluate each distinct normalised filter against the metadata once (`_matches`, the JSON containment), take its filter-first /
-    order-first decision once (`_search.py:97-141`: more than FILTER_FIRST_MAX_ROWS matching embedding rows -> order first) and map
-    every query to its filter."""
+def plan_filters(filters: Sequence[dict | None], metadata: Sequence[dict] | None, rows_per_chunk: np.ndarray,
+                 index: GpuIndex | None = None) -> FilterPlan:
+    """Evaluate each distinct normalised filter against the metadata once, take its filter-first / order-first decision once
+    (`_search.py:97-141`: more than FILTER_FIRST_MAX_ROWS matching embedding rows -> order first) and map every query to its filter.
+    With `index` (a GpuIndex that keeps its metadata on the device) all distinct filters are evaluated there by one call, unless one
+    of them is not encodable; else by `_matches`, the JSON containment, chunk by chunk."""
     plan = FilterPlan()
     seen: dict[str, int] = {}
+    distinct: list[dict] = []
     for flt in filters:
         if not flt:
             plan.query_filter.append(-1)
             continue
         key = repr(sorted(flt.items(), key=lambda kv: repr(kv[0])))
         if key not in seen:
-            seen[key] = len(plan.allowed)
-            allowed = None
-            if metadata is not None:
-                allowed = np.fromiter((_matches(m, flt) for m in metadata), dtype=bool, count=len(metadata))
-            plan.allowed.append(allowed)
-            rows = 0 if allowed is None else int(rows_per_chunk[allowed].sum())
-            plan.rank_limit.append(ORDER_FIRST_LIMIT if rows > FILTER_FIRST_MAX_ROWS else 0)
+            seen[key] = len(distinct)
+            distinct.append(flt)
         plan.query_filter.append(seen[key])
+    on_device = None if index is None or metadata is None else _filters_on_device(index, distinct)
+    if on_device is not None:
+        plan.filter_set, n_chunks, n_rows = on_device
+        plan.allowed = [_DeviceMask(int(n)) for n in n_chunks]
+        plan.rank_limit = [ORDER_FIRST_LIMIT if int(r) > FILTER_FIRST_MAX_ROWS else 0 for r in n_rows]
+        return plan
+    for flt in distinct:
+        allowed = None
+        if metadata is not None:
+            allowed = np.fromiter((_matches(m, flt) for m in metadata), dtype=bool, count=len(metadata))
+        plan.allowed.append(allowed)
+        rows = 0 if allowed is None else int(rows_per_chunk[allowed].sum())
+        plan.rank_limit.append(ORDER_FIRST_LIMIT if rows > FILTER_FIRST_MAX_ROWS else 0)
     return plan
 
 
@@ -692,6 +788,8 @@ def _device_filters(plan: FilterPlan, queries: Sequence[int]):
     the unfiltered call.  A query whose filter matches nothing keeps it: its lists come back empty, as the loop's do."""
     if all(plan.query_filter[b] < 0 for b in queries):
         return None, None
+    if plan.filter_set is not None:  # the bitsets are on the device: the set with these queries' rows, no mask goes through the host
+        return plan.filter_set.select([plan.query_filter[b] for b in queries]), [plan.of(b)[1] for b in queries]
     pairs = [plan.of(b) for b in queries]
     return [a for a, _ in pairs], [r for _, r in pairs]
 
@@ -716,7 +814,7 @@ def _plan_vector_batch(gi: GpuIndex, cfg: Any, queries: list, num_results: int, 
     _self_query(cfg, queries)
     Q = _embed_one_by_one(queries, query_vectors, cfg, gi)
     num_hits = round(oversample * cfg.chunk_max_size / DEFAULT_CHUNK_MAX_SIZE) * max(num_results, 10)  # (`_search.py:66-67`)
-    plan = plan_filters(filters, gi.metadata, _rows_per_chunk(gi))
+    plan = plan_filters(filters, gi.metadata, _rows_per_chunk(gi), gi)
     active = [b for b in range(B) if _vector_searches(gi, filters[b], plan.of(b)[0], num_hits, num_results)]
     return Q, num_hits, plan, active
 
@@ -755,7 +853,7 @@ def keyword_search_batch(queries: Sequence[str], *, num_results: int = 3, metada
         return []
     filters = _batch_filters(metadata_filter, B)
     _self_query(cfg, queries)
-    plan = plan_filters(filters, gi.metadata, _rows_per_chunk(gi))
+    plan = plan_filters(filters, gi.metadata, _rows_per_chunk(gi), gi)
     ids = [gi.keyword_query_ids(q) for q in queries] if gi.has_keywords else [[] for _ in queries]
     active = [b for b in range(B) if _keyword_searches(gi, filters[b], plan.of(b)[0], ids[b], num_results)]
     out: list = [([], []) for _ in range(B)]
@@ -792,7 +890,7 @@ def _plan_hybrid_batch(gi: GpuIndex, cfg: Any, queries: list, num_results: int, 
     n_each = oversample * num_results  # what hybrid_search asks of each half
     Q = _embed_one_by_one(queries, query_vectors, cfg, gi)
     num_hits = round(VECTOR_SEARCH_OVERSAMPLE * cfg.chunk_max_size / DEFAULT_CHUNK_MAX_SIZE) * max(n_each, 10)
-    plan = plan_filters(filters, gi.metadata, _rows_per_chunk(gi))
+    plan = plan_filters(filters, gi.metadata, _rows_per_chunk(gi), gi)
     # (hybrid_search runs the keyword half for query strings only; a query given as a vector has none)
     term_ids = [gi.keyword_query_ids(q) if isinstance(q, str) else [] for q in queries] if gi.has_keywords else None
     vector = keyword = False

@@ -211,6 +211,11 @@ int finish(int mem, hipStream_t s) {
     return RL_OK;
 }
 
+// RL_MEM_FILTERS_DEVICE or-ed into `mem`: the filter table alone is a device pointer, read in place; every other pointer follows the
+// rest of `mem`.  Each entry that takes filters splits `mem` once, into where its filters live and where everything else does.
+int filters_mem(int mem) { return (mem & RL_MEM_FILTERS_DEVICE) ? RL_MEM_DEVICE : mem; }
+int args_mem(int mem) { return mem & ~RL_MEM_FILTERS_DEVICE; }
+
 int scan_mode(int metric) {
     switch (metric) {
         case RL_COSINE: return SCAN_COSINE;
@@ -1888,6 +1893,8 @@ int rl_search_rows_ranked(rl_index* idx, const float* queries, int32_t B, int32_
     if (rank_limit < 0) return fail(RL_ERR_INVALID, "rl_search_rows: rank_limit must be >= 0 (0 = no cut)");
     if (B == 0) return RL_OK;
     if (!out_scores || !out_rows) return fail(RL_ERR_INVALID, "rl_search_rows: null output");
+    const int fmem = filters_mem(mem);
+    mem = args_mem(mem);
     hipStream_t s = as_stream(stream);
     std::lock_guard<std::mutex> lock(idx->mu);
     RL_TRY(use_scratch(idx, s));
@@ -1896,7 +1903,7 @@ int rl_search_rows_ranked(rl_index* idx, const float* queries, int32_t B, int32_
     BatchFilters f;
     f.n = chunk_filter ? 1 : 0;
     f.limit = rank_limit;
-    if (chunk_filter) RL_TRY(stage_in(chunk_filter, (size_t)((idx->n_chunks + 31) / 32), mem, s, t_f, &f.chunk_bits));
+    if (chunk_filter) RL_TRY(stage_in(chunk_filter, (size_t)((idx->n_chunks + 31) / 32), fmem, s, t_f, &f.chunk_bits));
     RL_TRY(stage_in(queries, (size_t)B * idx->dim, mem, s, t_q, &d_q));
     RL_TRY(stage_out_begin(out_scores, (size_t)B * k, mem, t_s, &d_s));
     RL_TRY(stage_out_begin(out_rows, (size_t)B * k, mem, t_r, &d_r));
@@ -2036,6 +2043,8 @@ int search_chunks_call(rl_index* idx, const float* queries, int32_t B, int32_t n
     if (num_hits < 1 || num_hits > K_MAX) return fail(RL_ERR_INVALID, std::string(who) + ": num_hits must be in [1, 2048]");
     if (B == 0) return RL_OK;
     if (!out_scores || !out_chunks || !out_counts) return fail(RL_ERR_INVALID, std::string(who) + ": null output");
+    const int fmem = filters_mem(mem);
+    mem = args_mem(mem);
     hipStream_t s = as_stream(stream);
     std::lock_guard<std::mutex> lock(idx->mu);
     RL_TRY(use_scratch(idx, s));
@@ -2046,7 +2055,7 @@ int search_chunks_call(rl_index* idx, const float* queries, int32_t B, int32_t n
     f.qf = query_filter;
     f.lim = rank_limits;
     f.limit = rank_limit;
-    if (n_filters) RL_TRY(stage_in(chunk_filters, (size_t)n_filters * ((idx->n_chunks + 31) / 32), mem, s, t_f, &f.chunk_bits));
+    if (n_filters) RL_TRY(stage_in(chunk_filters, (size_t)n_filters * ((idx->n_chunks + 31) / 32), fmem, s, t_f, &f.chunk_bits));
     RL_TRY(stage_in(queries, (size_t)B * idx->dim, mem, s, t_q, &d_q));
     RL_TRY(stage_out_begin(out_scores, (size_t)B * k, mem, t_s, &d_s));
     RL_TRY(stage_out_begin(out_chunks, (size_t)B * k, mem, t_c, &d_c));
@@ -3569,6 +3578,8 @@ int keyword_search_call(rl_keyword_index* kw, const int64_t* q_off, const int32_
     if (n_queries == 0) return RL_OK;
     if (!q_off) return fail(RL_ERR_INVALID, std::string(who) + ": null q_off");
     if (!out_scores || !out_chunks) return fail(RL_ERR_INVALID, std::string(who) + ": null output");
+    const int fmem = filters_mem(mem);
+    mem = args_mem(mem);
     int64_t n_q_terms = 0;
     if (mem == RL_MEM_HOST) {
         RL_TRY(check_host_q_off(q_off, q_terms, n_queries, who));
@@ -3590,7 +3601,7 @@ int keyword_search_call(rl_keyword_index* kw, const int64_t* q_off, const int32_
     RL_TRY(stage_in(q_off, (size_t)n_queries + 1, mem, s, t_off, &d_off));
     if (mem == RL_MEM_HOST) RL_TRY(stage_in(q_terms, (size_t)n_q_terms, mem, s, t_terms, &d_terms));
     else d_terms = q_terms;
-    if (n_filters) RL_TRY(stage_in(chunk_filters, (size_t)n_filters * ((n + 31) / 32), mem, s, t_f, &d_f));
+    if (n_filters) RL_TRY(stage_in(chunk_filters, (size_t)n_filters * ((n + 31) / 32), fmem, s, t_f, &d_f));
     QueryMask mask;
     RL_TRY(keyword_mask(kw, d_f, n_filters, query_filter, n_queries, s, &mask));
     RL_TRY(stage_out_begin(out_scores, n_out, mem, t_s, &d_s));
@@ -3702,6 +3713,8 @@ int hybrid_search_begin(rl_index* idx, rl_keyword_index* kw, const float* querie
                         const int64_t* q_off, const int32_t* q_terms, const uint32_t* chunk_filters, int32_t n_filters,
                         const int32_t* query_filter, const int64_t* rank_limits, int64_t rank_limit, const double* weights, int32_t rrf_k,
                         int32_t k, bool outputs, int mem, hipStream_t s, const char* who, HybridCall* c) {
+    const int fmem = filters_mem(mem);  // (`mem` as the caller of the entry point gave it; the callers go on with args_mem(mem))
+    mem = args_mem(mem);
     const int32_t R = kw ? 2 : 1;
     RL_TRY(check_search_args(idx, queries, B, n_each, who));
     if (rank_limit < 0) return fail(RL_ERR_INVALID, std::string(who) + ": rank_limit must be >= 0 (0 = no cut)");
@@ -3735,7 +3748,7 @@ int hybrid_search_begin(rl_index* idx, rl_keyword_index* kw, const float* querie
     c->f.lim = rank_limits;
     c->f.limit = rank_limit;
     RL_TRY(stage_in(queries, (size_t)B * idx->dim, mem, s, c->t_q, &c->d_q));
-    if (n_filters) RL_TRY(stage_in(chunk_filters, (size_t)n_filters * ((idx->n_chunks + 31) / 32), mem, s, c->t_f, &c->f.chunk_bits));
+    if (n_filters) RL_TRY(stage_in(chunk_filters, (size_t)n_filters * ((idx->n_chunks + 31) / 32), fmem, s, c->t_f, &c->f.chunk_bits));
     if (kw) {
         RL_TRY(stage_in(q_off, (size_t)B + 1, mem, s, c->t_off, &c->d_off));
         if (mem == RL_MEM_HOST) RL_TRY(stage_in(q_terms, (size_t)n_q_terms, mem, s, c->t_terms, &c->d_terms));
@@ -3774,6 +3787,7 @@ int hybrid_search_call(rl_index* idx, rl_keyword_index* kw, const float* queries
     RL_TRY(hybrid_search_begin(idx, kw, queries, B, num_hits, n_each, q_off, q_terms, chunk_filters, n_filters, query_filter, rank_limits,
                                rank_limit, weights, rrf_k, k, out_scores && out_chunks && out_counts, mem, s, who, &c));
     if (c.empty) return RL_OK;
+    mem = args_mem(mem);
     const size_t n_out = (size_t)B * k;
     DevBuf t_s, t_c, t_n;
     double* d_s;
@@ -3874,7 +3888,7 @@ int search_rerank_begin(rl_index* idx, rl_keyword_index* kw, const float* querie
     RL_TRY(hybrid_search_begin(idx, kw, queries, B, num_hits, n_each, q_off, q_terms, chunk_filters, query_filter ? n_filters : 0, query_filter,
                                rank_limits, 0, weights, rrf_k, n_cand, query_vecs && outputs, mem, s, who, &rc->c));
     if (rc->c.empty) return RL_OK;
-    return stage_in(query_vecs, (size_t)B * nq * idx->dim, mem, s, rc->t_v, &rc->d_v);
+    return stage_in(query_vecs, (size_t)B * nq * idx->dim, args_mem(mem), s, rc->t_v, &rc->d_v);
 }
 
 // The searches, the fusion, the MaxSim rerank and the ordering on device pointers (after search_rerank_begin): d_c [B x k], d_n [B];
@@ -3955,6 +3969,7 @@ int rl_search_rerank_per_query(rl_index* idx, rl_keyword_index* kw, const float*
     RL_TRY(search_rerank_begin(idx, kw, queries, B, num_hits, n_each, q_off, q_terms, chunk_filters, n_filters, query_filter, rank_limits, weights,
                                rrf_k, n_cand, query_vecs, nq, k, out_scores && out_chunks && out_counts, mem, s, who, &rc));
     if (rc.c.empty) return RL_OK;
+    mem = args_mem(mem);
     const size_t n_out = (size_t)B * k;
     DevBuf t_s, t_c, t_n;
     float* d_s;
@@ -4050,7 +4065,7 @@ int rl_search_rerank_spans_per_query(rl_index* idx, rl_keyword_index* kw, const 
                                      int32_t* out_n_chunks, int mem, void* stream) {
     const char* who = "rl_search_rerank_spans_per_query";
     const int32_t B = n_queries;
-    RL_TRY(check_span_args(table, B, k, offsets, n_off, mem, who));  // (k * (1 + n_off) <= 4096)
+    RL_TRY(check_span_args(table, B, k, offsets, n_off, args_mem(mem), who));  // (k * (1 + n_off) <= 4096)
     if (idx && table->n_chunks != idx->n_chunks) return fail(RL_ERR_INVALID, std::string(who) + ": the span table covers another number of chunks");
     hipStream_t s = as_stream(stream);
     RerankCall rc;
@@ -4059,6 +4074,7 @@ int rl_search_rerank_spans_per_query(rl_index* idx, rl_keyword_index* kw, const 
                                out_top_chunks && out_top_counts && out_chunks && out_span_len && out_span_scores && out_n_spans && out_n_chunks,
                                mem, s, who, &rc));
     if (rc.c.empty) return RL_OK;
+    mem = args_mem(mem);
     const size_t n_top = (size_t)B * k, n_out = n_top * (1 + n_off);
     DevBuf t_c, t_n;
     int32_t *d_c, *d_n;
@@ -4072,6 +4088,183 @@ int rl_search_rerank_spans_per_query(rl_index* idx, rl_keyword_index* kw, const 
     RL_TRY(stage_out_end(out_top_counts, (size_t)B, mem, s, t_n));
     RL_TRY(o.end(out_chunks, out_span_len, out_span_scores, out_n_spans, out_n_chunks, n_out, (size_t)B, mem, s));
     return finish(mem, s);
+}
+
+}  // extern "C"
+
+// ---- metadata filters on the device (include/raglite_hip.h; the kernel is in metadata.hip) --------------------------------------------
+struct rl_metadata_store {
+    int64_t n_chunks = 0, n_tags = 0;
+    int64_t cap_off = 0, cap_tags = 0;  // items the two arrays can hold
+    rl::DevArray<int64_t> tag_off;      // [n_chunks + 1]
+    rl::DevArray<int32_t> tags;         // [n_tags]
+    std::mutex mu;
+};
+
+// What rl_metadata_filters leaves on the device: the bitsets [n_filters x words] and the counts [2 x n_filters].  Grown, never shrunk.
+struct rl_filter_set {
+    rl::Pool bits, counts, f_off, f_tags;  // (the last two: the filters' own CSR, staged for host callers)
+    int32_t n_filters = 0;
+    int64_t words = 0;
+};
+
+namespace {
+
+// A CSR handed in by the caller, read on the host: from 0, ascending; returns its last entry in *total
+int check_csr(const int64_t* off, int64_t n, int mem, hipStream_t s, const char* who, const char* name, std::vector<int64_t>* h_off,
+              int64_t* total) {
+    h_off->resize((size_t)n + 1);
+    if (mem == RL_MEM_HOST) std::memcpy(h_off->data(), off, h_off->size() * sizeof(int64_t));
+    else {
+        RL_TRY(hip_status(hipMemcpyAsync(h_off->data(), off, h_off->size() * sizeof(int64_t), hipMemcpyDeviceToHost, s), who));
+        RL_TRY(hip_status(hipStreamSynchronize(s), who));
+    }
+    if ((*h_off)[0] != 0) return fail(RL_ERR_INVALID, std::string(who) + ": " + name + " must start at 0");
+    for (int64_t i = 0; i < n; ++i)
+        if ((*h_off)[(size_t)i + 1] < (*h_off)[(size_t)i]) return fail(RL_ERR_INVALID, std::string(who) + ": " + name + " must be ascending");
+    *total = (*h_off)[(size_t)n];
+    return RL_OK;
+}
+
+// rl_metadata_store_append, and the one append of rl_metadata_store_create
+int metadata_append(rl_metadata_store* st, const int64_t* tag_off, const int32_t* tags, int64_t n_new, int mem, void* stream, const char* who) {
+    if (n_new < 0) return fail(RL_ERR_INVALID, std::string(who) + ": negative size");
+    if (mem != RL_MEM_HOST && mem != RL_MEM_DEVICE) return fail(RL_ERR_INVALID, std::string(who) + ": bad mem");
+    if (n_new > 0 && !tag_off) return fail(RL_ERR_INVALID, std::string(who) + ": null tag_off");
+    if (!st) return fail(RL_ERR_INVALID, std::string(who) + ": null store");
+    if (n_new == 0) return RL_OK;
+    hipStream_t s = as_stream(stream);
+    std::vector<int64_t> h_off;
+    int64_t n_add = 0;
+    RL_TRY(check_csr(tag_off, n_new, mem, s, who, "tag_off", &h_off, &n_add));
+    if (n_add > 0 && !tags) return fail(RL_ERR_INVALID, std::string(who) + ": null tags");
+    std::lock_guard<std::mutex> lock(st->mu);
+    if (st->n_chunks + n_new >= (int64_t)0x7fffffff - 1) return fail(RL_ERR_UNSUPPORTED, std::string(who) + ": more than 2^31-2 chunks");
+    if (st->n_tags + n_add >= (int64_t)0x7fffffff) return fail(RL_ERR_UNSUPPORTED, std::string(who) + ": 2^31 tags or more");
+    RL_TRY(store_grow(st->tag_off, &st->cap_off, st->n_chunks ? st->n_chunks + 1 : 0, st->n_chunks + n_new + 1, s, who));
+    RL_TRY(store_grow(st->tags, &st->cap_tags, st->n_tags, st->n_tags + n_add, s, who));
+    for (int64_t& o : h_off) o += st->n_tags;  // (h_off[0] is what tag_off[n_chunks] holds already, or the first 0)
+    RL_TRY(hip_status(hipMemcpyAsync(st->tag_off + st->n_chunks, h_off.data(), h_off.size() * sizeof(int64_t), hipMemcpyHostToDevice, s), who));
+    if (n_add > 0)
+        RL_TRY(hip_status(hipMemcpyAsync(st->tags + st->n_tags, tags, (size_t)n_add * sizeof(int32_t),
+                                         mem == RL_MEM_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, s), who));
+    RL_TRY(hip_status(hipStreamSynchronize(s), who));  // the caller's arrays and h_off may go away after return
+    st->n_chunks += n_new;
+    st->n_tags += n_add;
+    return RL_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int rl_metadata_store_append(rl_metadata_store* st, const int64_t* tag_off, const int32_t* tags, int64_t n_new, int mem, void* stream) {
+    return metadata_append(st, tag_off, tags, n_new, mem, stream, "rl_metadata_store_append");
+}
+
+int rl_metadata_store_create(rl_metadata_store** out, const int64_t* tag_off, const int32_t* tags, int64_t n_chunks, int mem, void* stream) {
+    const char* who = "rl_metadata_store_create";
+    if (!out) return fail(RL_ERR_INVALID, std::string(who) + ": null output handle");
+    *out = nullptr;
+    if (n_chunks < 0) return fail(RL_ERR_INVALID, std::string(who) + ": negative size");
+    if (mem != RL_MEM_HOST && mem != RL_MEM_DEVICE) return fail(RL_ERR_INVALID, std::string(who) + ": bad mem");
+    if (n_chunks > 0 && !tag_off) return fail(RL_ERR_INVALID, std::string(who) + ": null tag_off");
+    std::unique_ptr<rl_metadata_store> st(new rl_metadata_store());
+    RL_TRY(metadata_append(st.get(), tag_off, tags, n_chunks, mem, stream, who));
+    *out = st.release();
+    return RL_OK;
+}
+
+int rl_metadata_store_memory(const rl_metadata_store* st, int64_t out[2]) {
+    if (!st || !out) return fail(RL_ERR_INVALID, "rl_metadata_store_memory: null argument");
+    std::lock_guard<std::mutex> lock(const_cast<rl_metadata_store*>(st)->mu);
+    out[0] = (st->n_chunks ? (st->n_chunks + 1) * (int64_t)sizeof(int64_t) : 0) + st->n_tags * (int64_t)sizeof(int32_t);
+    out[1] = (int64_t)(st->tag_off.cap + st->tags.cap);
+    return RL_OK;
+}
+
+int rl_metadata_store_destroy(rl_metadata_store* st) {
+    delete st;
+    return RL_OK;
+}
+
+int rl_metadata_filters(rl_metadata_store* st, rl_index* idx, const int64_t* f_off, const int32_t* f_tags, int32_t n_filters,
+                        rl_filter_set** inout_set, int64_t* out_chunks, int64_t* out_rows, int mem, void* stream) {
+    const char* who = "rl_metadata_filters";
+    if (n_filters < 0) return fail(RL_ERR_INVALID, std::string(who) + ": n_filters must be >= 0");
+    if (n_filters > MF_GROUP * 65535) return fail(RL_ERR_UNSUPPORTED, std::string(who) + ": more than 64 * 65535 filters");
+    if (mem != RL_MEM_HOST && mem != RL_MEM_DEVICE) return fail(RL_ERR_INVALID, std::string(who) + ": bad mem");
+    if (!inout_set) return fail(RL_ERR_INVALID, std::string(who) + ": null inout_set");
+    if (n_filters > 0 && (!f_off || !out_chunks || !out_rows)) return fail(RL_ERR_INVALID, std::string(who) + ": null f_off or output");
+    if (!st) return fail(RL_ERR_INVALID, std::string(who) + ": null store");
+    if (!idx) return fail(RL_ERR_INVALID, std::string(who) + ": null index");
+    hipStream_t s = as_stream(stream);
+    std::vector<int64_t> h_off;
+    int64_t n_ftags = 0;
+    if (n_filters > 0) RL_TRY(check_csr(f_off, n_filters, mem, s, who, "f_off", &h_off, &n_ftags));
+    if (n_ftags >= (int64_t)0x7fffffff) return fail(RL_ERR_UNSUPPORTED, std::string(who) + ": 2^31 filter tags or more");
+    if (n_ftags > 0 && !f_tags) return fail(RL_ERR_INVALID, std::string(who) + ": null f_tags");
+    std::lock_guard<std::mutex> idx_lock(idx->mu);  // (idx->mu, then the store's: the chunk offsets must not move under the launch)
+    std::lock_guard<std::mutex> lock(st->mu);
+    if (st->n_chunks != idx->n_chunks) return fail(RL_ERR_INVALID, std::string(who) + ": the metadata store covers another number of chunks");
+    std::unique_ptr<rl_filter_set> fresh;
+    rl_filter_set* set = *inout_set;
+    if (!set) {
+        fresh.reset(new rl_filter_set());
+        set = fresh.get();
+    }
+    const int64_t n = st->n_chunks, words = (n + 31) / 32;
+    set->n_filters = 0;  // (until the launch is enqueued)
+    RL_TRY(set->bits.reserve(std::max<size_t>((size_t)n_filters * (size_t)words * sizeof(uint32_t), 16)));  // (never null: an empty index)
+    RL_TRY(set->counts.reserve((size_t)2 * n_filters * sizeof(unsigned long long)));
+    const int64_t* d_off = f_off;
+    const int32_t* d_tags = f_tags;
+    if (mem == RL_MEM_HOST && n_filters > 0) {
+        RL_TRY(set->f_off.reserve(h_off.size() * sizeof(int64_t)));
+        RL_TRY(set->f_tags.reserve((size_t)std::max<int64_t>(n_ftags, 1) * sizeof(int32_t)));
+        RL_HIP(hipMemcpyAsync(set->f_off.p, h_off.data(), h_off.size() * sizeof(int64_t), hipMemcpyHostToDevice, s));
+        if (n_ftags) RL_HIP(hipMemcpyAsync(set->f_tags.p, f_tags, (size_t)n_ftags * sizeof(int32_t), hipMemcpyHostToDevice, s));
+        d_off = set->f_off.as<int64_t>();
+        d_tags = set->f_tags.as<int32_t>();
+    }
+    unsigned long long* counts = set->counts.as<unsigned long long>();
+    RL_TRY(launch_metadata_filters(st->tag_off, st->tags, n, idx->offsets, d_off, d_tags, n_filters, set->bits.as<uint32_t>(), counts, s));
+    if (n_filters > 0) {
+        const hipMemcpyKind kind = mem == RL_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
+        RL_HIP(hipMemcpyAsync(out_chunks, counts, (size_t)n_filters * sizeof(int64_t), kind, s));
+        RL_HIP(hipMemcpyAsync(out_rows, counts + n_filters, (size_t)n_filters * sizeof(int64_t), kind, s));
+    }
+    if (mem == RL_MEM_HOST) RL_HIP(hipStreamSynchronize(s));
+    set->n_filters = n_filters;
+    set->words = words;
+    if (fresh) *inout_set = fresh.release();
+    return RL_OK;
+}
+
+int rl_filter_set_bits(const rl_filter_set* set, const uint32_t** out_device_bits, int32_t* out_n_filters, int64_t* out_words) {
+    if (!set) return fail(RL_ERR_INVALID, "rl_filter_set_bits: null filter set");
+    if (out_device_bits) *out_device_bits = set->bits.as<uint32_t>();
+    if (out_n_filters) *out_n_filters = set->n_filters;
+    if (out_words) *out_words = set->words;
+    return RL_OK;
+}
+
+int rl_filter_set_read(const rl_filter_set* set, uint32_t* out, int mem, void* stream) {
+    const char* who = "rl_filter_set_read";
+    if (mem != RL_MEM_HOST && mem != RL_MEM_DEVICE) return fail(RL_ERR_INVALID, std::string(who) + ": bad mem");
+    if (!set) return fail(RL_ERR_INVALID, std::string(who) + ": null filter set");
+    const size_t bytes = (size_t)set->n_filters * (size_t)set->words * sizeof(uint32_t);
+    if (bytes == 0) return RL_OK;
+    if (!out) return fail(RL_ERR_INVALID, std::string(who) + ": null output");
+    hipStream_t s = as_stream(stream);
+    RL_HIP(hipMemcpyAsync(out, set->bits.p, bytes, mem == RL_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, s));
+    if (mem == RL_MEM_HOST) RL_HIP(hipStreamSynchronize(s));
+    return RL_OK;
+}
+
+int rl_filter_set_destroy(rl_filter_set* set) {
+    delete set;
+    return RL_OK;
 }
 
 }  // extern "C"

@@ -405,6 +405,16 @@ int launch_chunk_spans(const int32_t* rank_of, const uint64_t* tab_key, const in
                        int32_t* out_chunks, int32_t* out_span_len, double* out_span_scores, int32_t* out_n_spans, int32_t* out_n_chunks,
                        hipStream_t s);
 
+// metadata.hip: metadata filters as tag containment.  tag_off [n_chunks + 1] / tags: every chunk's ascending, duplicate-free tag ids;
+// row_off [n_chunks + 1]: the index's chunk offsets; f_off [n_filters + 1] / f_tags: the filters' tags.  bits [n_filters x words],
+// words = (n_chunks + 31) / 32, every word written; counts [2 x n_filters] (matching chunks, then their rows), zeroed here.
+constexpr int32_t MF_BLOCK = 256;         // chunks per workgroup, one lane each
+constexpr int32_t MF_STAGE_TAGS = 4096;   // chunk tags a workgroup stages in LDS (16 KiB); a chunk whose list ends past them reads HBM
+constexpr int32_t MF_FILTER_TAGS = 1024;  // filter tags per LDS piece (4 KiB); a single filter with more reads HBM
+constexpr int32_t MF_GROUP = 64;          // filters per blockIdx.y
+int launch_metadata_filters(const int64_t* tag_off, const int32_t* tags, int64_t n_chunks, const int64_t* row_off, const int64_t* f_off,
+                            const int32_t* f_tags, int32_t n_filters, uint32_t* bits, unsigned long long* counts, hipStream_t s);
+
 // adapter_fit.hip: device half of update_query_adapter (best row per (query, chunk), row gather)
 int launch_chunk_best_rows(const void* E, bool f16, int32_t dim, const float* Q, const int64_t* offsets,
                            int64_t n_chunks, const int32_t* cand, int32_t n_cand, int64_t n_items, int32_t* out_rows,
