@@ -759,7 +759,9 @@ int rl_gather_rows(rl_index* index, const int32_t* rows, int64_t n, float* out, 
 
 /* ---- semantic-chunking similarities ---------------------------------------
  * src/raglite/_split_chunks.py:54-72, the consumer of the pooled chunklet embeddings and the cost
- * vector of the chunk-partition MILP (which stays on the host), batched over documents:
+ * vector of the chunk partition, batched over documents.  The partition itself no longer has to
+ * stay on the host: rl_partition_chunks below solves the reference's integer programme exactly on
+ * the device, and rl_split_chunks chains the two without a repack.
  *   X            [n x dim] f32 chunklet embeddings of all documents, concatenated (nonzero rows)
  *   doc_offsets  int64[n_docs + 1] CSR over those rows (same side as X); NULL = one document
  *   nonoutlying  uint8[n], nonzero = chunklet size within the document's 15 %..85 % quantiles
@@ -768,6 +770,37 @@ int rl_gather_rows(rl_index* index, const int32_t* rows, int64_t n, float* out, 
  *                discourse-free rows (:59-72); 0 for the last row of a document. */
 int rl_partition_similarity(const float* X, int64_t n, int32_t dim, const int64_t* doc_offsets, int64_t n_docs,
                             const uint8_t* nonoutlying, float* out, int mem, void* stream);
+
+/* ---- chunk partition on the device --------------------------------------
+ * src/raglite/_split_chunks.py:87-113 minimises cost . x over binary x (x[j] = split after chunklet j)
+ * such that every window of chunklets that overflows max_size holds a split.  The windows' ends
+ * ascend with their starts, so the optimum is a shortest path over split positions: exact, float64,
+ * one document per wave, no limit on a document's length.  Ties: no predecessor before an equal
+ * predecessor, then the smallest position (raglite_amd._chunking.partition_dp states the same
+ * recurrence on the host; the two agree bit for bit).
+ *   cost         f32[n], the layout rl_partition_similarity writes: cost[i] = price of a split after
+ *                chunklet i; the entry at every document's last chunklet is ignored
+ *   sizes        int64[n] chunklet string lengths (>= 0)
+ *   doc_offsets  int64[n_docs + 1] CSR over the chunklets (starts at 0, ascends, ends at n)
+ *   cut          uint8[n]: 1 = a split after chunklet i (never at a document's last chunklet)
+ *   objective    f64[n_docs] (nullable): the cost of the chosen cuts; 0 without cuts; NaN with status != 0
+ *   status       int32[n_docs]: 0 = ok; 1 = a chunklet larger than max_size (the reference's "Chunklet
+ *                larger than chunk max_size detected."); 2 = a non-finite cost -- or, from
+ *                rl_split_chunks, an embedding row of zero or NaN norm (the reference's "Chunklet
+ *                embeddings with zero norm detected.").  Such a document gets no cuts.
+ * RL_ERR_INVALID before any HIP call: n < 0, max_size < 1, n > 0 with n_docs < 1 or a null pointer,
+ * and for RL_MEM_HOST offsets that do not start at 0 / ascend / end at n, or a negative size.  n == 0
+ * returns RL_OK and writes nothing.
+ *
+ * rl_split_chunks = rl_partition_similarity (X, nonoutlying as there) -> the Markdown-heading
+ * adjustments of :73-86 (is_heading uint8[n], nonzero = the chunklet is a heading; NULL = none) ->
+ * rl_partition_chunks, on one stream, nothing through the host, one read-back for host callers.
+ * cost_out f32[n] (nullable): the adjusted costs.  dim > 4096: RL_ERR_UNSUPPORTED. */
+int rl_partition_chunks(const float* cost, const int64_t* sizes, const int64_t* doc_offsets, int64_t n, int64_t n_docs,
+                        int64_t max_size, uint8_t* cut, double* objective, int32_t* status, int mem, void* stream);
+int rl_split_chunks(const float* X, int64_t n, int32_t dim, const int64_t* doc_offsets, int64_t n_docs,
+                    const uint8_t* nonoutlying, const uint8_t* is_heading, const int64_t* sizes, int64_t max_size,
+                    uint8_t* cut, float* cost_out, double* objective, int32_t* status, int mem, void* stream);
 
 /* What the last bound-filtered search on this index did (diagnostic; bench.py reports it next to every timed number that depends
  * on it).  The searches that rank on approximate scores and re-score what a rigorous bound cannot rule out -- rl_maxsim_topk_batch

@@ -7,7 +7,14 @@ and a Python host layer that mirrors the reference's own entry points for this p
 GPU) the calls raise.
 """
 
-from raglite_amd._chunking import partition_cost, partition_similarities, split_chunks
+from raglite_amd._chunking import (
+    partition_chunks,
+    partition_cost,
+    partition_similarities,
+    solve_partition_dp,
+    split_chunks,
+    split_chunks_batch,
+)
 from raglite_amd._config import HotPathConfig
 from raglite_amd._embed import (
     embed_strings,
@@ -73,6 +80,9 @@ __all__ = [
     "partition_cost",
     "partition_similarities",
     "split_chunks",
+    "split_chunks_batch",
+    "partition_chunks",
+    "solve_partition_dp",
     "hybrid_search",
     "hybrid_search_batch",
     "keyword_search",

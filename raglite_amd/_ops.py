@@ -1312,3 +1312,66 @@ class KeywordStore:
                                            C.byref(handle), MEM_HOST, None))
         self._counted = None
         return KeywordIndex._from_handle(handle)  # noqa: SLF001
+
+
+# ----------------------------------------------------------------------------------------------
+def _same_side(a: _Args, x: Any, dtype: np.dtype) -> int:
+    """`a.inp` for the small host-derived arrays of a call (offsets, sizes, flags): NumPy input follows the call to the device."""
+    if a.mem == MEM_DEVICE and not _is_torch(x):
+        x = _torch().from_numpy(np.ascontiguousarray(x, dtype=dtype)).to(a.device)
+    return a.inp(x, dtype)
+
+
+def partition_chunks(cost: Any, sizes: Any, doc_offsets: Any, max_size: int) -> tuple[Any, Any, Any]:
+    """`rl_partition_chunks`: the optimal cuts of many documents in one call.  cost float32[n] (the layout `rl_partition_similarity`
+    writes), sizes int64[n], doc_offsets int64[n_docs + 1] -> (cut uint8[n], objective float64[n_docs], status int32[n_docs]) on the
+    side of `cost`."""
+    a = _Args()
+    p_cost = a.inp(cost, np.float32)
+    n = int(a.keep[0].shape[0])
+    p_sizes = _same_side(a, sizes, np.int64)
+    p_off = _same_side(a, doc_offsets, np.int64)
+    n_docs = int(a.keep[-1].shape[0]) - 1
+    if int(a.keep[-2].shape[0]) != n:
+        raise ValueError("partition_chunks: cost and sizes differ in length")
+    cut, p_cut = a.out((n,), np.uint8)
+    obj, p_obj = a.out((max(n_docs, 0),), np.float64)
+    status, p_status = a.out((max(n_docs, 0),), np.int32)
+    if n == 0 and n_docs >= 0:  # the call writes nothing: no document has a cut
+        obj[...] = 0.0
+        status[...] = 0
+        return cut, obj, status
+    a.ensure_device()
+    check(lib().rl_partition_chunks(p_cost, p_sizes, p_off, n, n_docs, int(max_size), p_cut, p_obj, p_status, a.mem, a.stream))
+    return cut, obj, status
+
+
+def split_chunks_call(embeddings: Any, doc_offsets: Any, nonoutlying: Any, is_heading: Any, sizes: Any, max_size: int,
+                      want_cost: bool = False) -> tuple[Any, Any, Any, Any]:
+    """`rl_split_chunks`: similarities -> heading adjustments -> partition for many documents in one call.  embeddings (n, dim);
+    nonoutlying / is_heading uint8[n] or None -> (cut, cost or None, objective, status) on the side of `embeddings`."""
+    a = _Args()
+    p_x = a.inp(embeddings, np.float32)
+    x = a.keep[0]
+    if x.ndim != 2:
+        raise ValueError("split_chunks_call: embeddings must be (n, dim)")
+    n, dim = int(x.shape[0]), int(x.shape[1])
+    p_off = _same_side(a, doc_offsets, np.int64)
+    n_docs = int(a.keep[-1].shape[0]) - 1
+    p_sel = _same_side(a, nonoutlying, np.uint8) if nonoutlying is not None else None
+    p_head = _same_side(a, is_heading, np.uint8) if is_heading is not None else None
+    p_sizes = _same_side(a, sizes, np.int64)
+    if int(a.keep[-1].shape[0]) != n or any(v is not None and len(v) != n for v in (nonoutlying, is_heading)):
+        raise ValueError("split_chunks_call: sizes / flags do not match the embedding rows")
+    cut, p_cut = a.out((n,), np.uint8)
+    cost, p_cost = a.out((n,), np.float32) if want_cost else (None, None)
+    obj, p_obj = a.out((max(n_docs, 0),), np.float64)
+    status, p_status = a.out((max(n_docs, 0),), np.int32)
+    if n == 0 and n_docs >= 0:
+        obj[...] = 0.0
+        status[...] = 0
+        return cut, cost, obj, status
+    a.ensure_device()
+    check(lib().rl_split_chunks(p_x, n, dim, p_off, n_docs, p_sel, p_head, p_sizes, int(max_size), p_cut, p_cost, p_obj, p_status,
+                                a.mem, a.stream))
+    return cut, cost, obj, status

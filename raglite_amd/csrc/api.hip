@@ -2927,6 +2927,91 @@ int rl_partition_similarity(const float* X, int64_t n, int32_t dim, const int64_
     return sync_and_drain(s);  // the scratch dies with this frame
 }
 
+// Argument checks shared by rl_partition_chunks and rl_split_chunks; all of them return before the first HIP call.
+static int partition_args(const char* who, const int64_t* sizes, const int64_t* doc_offsets, int64_t n, int64_t n_docs, const uint8_t* cut,
+                          const int32_t* status, int mem) {
+    const std::string w(who);
+    if (n_docs < 1) return fail(RL_ERR_INVALID, w + ": n_docs must be >= 1");
+    if (!sizes) return fail(RL_ERR_INVALID, w + ": sizes is null");
+    if (!doc_offsets) return fail(RL_ERR_INVALID, w + ": doc_offsets is null");
+    if (!cut) return fail(RL_ERR_INVALID, w + ": cut is null");
+    if (!status) return fail(RL_ERR_INVALID, w + ": status is null");
+    if (mem == RL_MEM_HOST) {
+        if (doc_offsets[0] != 0) return fail(RL_ERR_INVALID, w + ": doc_offsets must start at 0");
+        for (int64_t d = 0; d < n_docs; ++d)
+            if (doc_offsets[d + 1] < doc_offsets[d]) return fail(RL_ERR_INVALID, w + ": doc_offsets must be ascending");
+        if (doc_offsets[n_docs] != n) return fail(RL_ERR_INVALID, w + ": doc_offsets must end at n");
+        for (int64_t i = 0; i < n; ++i)
+            if (sizes[i] < 0) return fail(RL_ERR_INVALID, w + ": sizes must be >= 0");
+    }
+    return RL_OK;
+}
+
+int rl_partition_chunks(const float* cost, const int64_t* sizes, const int64_t* doc_offsets, int64_t n, int64_t n_docs, int64_t max_size,
+                        uint8_t* cut, double* objective, int32_t* status, int mem, void* stream) {
+    if (n < 0) return fail(RL_ERR_INVALID, "rl_partition_chunks: n must be >= 0");
+    if (max_size < 1) return fail(RL_ERR_INVALID, "rl_partition_chunks: max_size must be >= 1");
+    if (mem != RL_MEM_HOST && mem != RL_MEM_DEVICE) return fail(RL_ERR_INVALID, "rl_partition_chunks: bad mem");
+    if (n == 0) return RL_OK;
+    if (!cost) return fail(RL_ERR_INVALID, "rl_partition_chunks: cost is null");
+    RL_TRY(partition_args("rl_partition_chunks", sizes, doc_offsets, n, n_docs, cut, status, mem));
+    hipStream_t s = as_stream(stream);
+    DevBuf t_c, t_sz, t_off, t_cut, t_obj, t_st, t_scr;
+    const float* d_c; const int64_t* d_sz; const int64_t* d_off; uint8_t* d_cut; double* d_obj; int32_t* d_st;
+    RL_TRY(stage_in(cost, (size_t)n, mem, s, t_c, &d_c));
+    RL_TRY(stage_in(sizes, (size_t)n, mem, s, t_sz, &d_sz));
+    RL_TRY(stage_in(doc_offsets, (size_t)n_docs + 1, mem, s, t_off, &d_off));
+    RL_TRY(stage_out_begin(cut, (size_t)n, mem, t_cut, &d_cut));
+    RL_TRY(stage_out_begin(objective, (size_t)n_docs, mem, t_obj, &d_obj));
+    RL_TRY(stage_out_begin(status, (size_t)n_docs, mem, t_st, &d_st));
+    RL_TRY(t_scr.alloc(partition_dp_scratch_bytes(n)));
+    RL_TRY(launch_partition_dp(d_c, d_sz, nullptr, d_off, n, n_docs, max_size, d_cut, d_obj, d_st, t_scr.p, s));
+    RL_TRY(stage_out_end(cut, (size_t)n, mem, s, t_cut));
+    RL_TRY(stage_out_end(objective, (size_t)n_docs, mem, s, t_obj));
+    RL_TRY(stage_out_end(status, (size_t)n_docs, mem, s, t_st));
+    return sync_and_drain(s);  // the scratch dies with this frame
+}
+
+int rl_split_chunks(const float* X, int64_t n, int32_t dim, const int64_t* doc_offsets, int64_t n_docs, const uint8_t* nonoutlying,
+                    const uint8_t* is_heading, const int64_t* sizes, int64_t max_size, uint8_t* cut, float* cost_out, double* objective,
+                    int32_t* status, int mem, void* stream) {
+    if (n < 0 || dim <= 0) return fail(RL_ERR_INVALID, "rl_split_chunks: bad shape (n, dim)");
+    if (max_size < 1) return fail(RL_ERR_INVALID, "rl_split_chunks: max_size must be >= 1");
+    if (mem != RL_MEM_HOST && mem != RL_MEM_DEVICE) return fail(RL_ERR_INVALID, "rl_split_chunks: bad mem");
+    if (n == 0) return RL_OK;
+    if (!X) return fail(RL_ERR_INVALID, "rl_split_chunks: X is null");
+    RL_TRY(partition_args("rl_split_chunks", sizes, doc_offsets, n, n_docs, cut, status, mem));
+    if (dim > 4096) return fail(RL_ERR_UNSUPPORTED, "rl_split_chunks: dim must be <= 4096");
+    hipStream_t s = as_stream(stream);
+    DevBuf t_x, t_sz, t_off, t_sel, t_head, t_cut, t_cost, t_obj, t_st, t_scr, t_dp;
+    const float* d_x; const int64_t* d_sz; const int64_t* d_off; const uint8_t* d_sel = nullptr; const uint8_t* d_head = nullptr;
+    uint8_t* d_cut; float* d_cost; double* d_obj; int32_t* d_st;
+    RL_TRY(stage_in(X, (size_t)n * dim, mem, s, t_x, &d_x));
+    RL_TRY(stage_in(sizes, (size_t)n, mem, s, t_sz, &d_sz));
+    RL_TRY(stage_in(doc_offsets, (size_t)n_docs + 1, mem, s, t_off, &d_off));
+    if (nonoutlying) RL_TRY(stage_in(nonoutlying, (size_t)n, mem, s, t_sel, &d_sel));
+    if (is_heading) RL_TRY(stage_in(is_heading, (size_t)n, mem, s, t_head, &d_head));
+    RL_TRY(stage_out_begin(cut, (size_t)n, mem, t_cut, &d_cut));
+    RL_TRY(stage_out_begin(objective, (size_t)n_docs, mem, t_obj, &d_obj));
+    RL_TRY(stage_out_begin(status, (size_t)n_docs, mem, t_st, &d_st));
+    if (cost_out) {
+        RL_TRY(stage_out_begin(cost_out, (size_t)n, mem, t_cost, &d_cost));
+    } else {
+        RL_TRY(t_cost.alloc((size_t)n * sizeof(float)));
+        d_cost = t_cost.as<float>();
+    }
+    RL_TRY(t_scr.alloc(partition_sim_scratch_bytes(n, n_docs, dim)));
+    RL_TRY(t_dp.alloc(partition_dp_scratch_bytes(n)));
+    RL_TRY(launch_partition_similarity(d_x, n, dim, d_off, n_docs, d_sel, d_cost, t_scr.p, s));
+    if (d_head) RL_TRY(launch_partition_headings(d_cost, d_head, d_off, n_docs, n, s));  // in place: entry i reads sim[i] alone
+    RL_TRY(launch_partition_dp(d_cost, d_sz, t_scr.as<float>() /* 1 / |x_i| */, d_off, n, n_docs, max_size, d_cut, d_obj, d_st, t_dp.p, s));
+    RL_TRY(stage_out_end(cut, (size_t)n, mem, s, t_cut));
+    if (cost_out) RL_TRY(stage_out_end(cost_out, (size_t)n, mem, s, t_cost));
+    RL_TRY(stage_out_end(objective, (size_t)n_docs, mem, s, t_obj));
+    RL_TRY(stage_out_end(status, (size_t)n_docs, mem, s, t_st));
+    return sync_and_drain(s);  // the scratch dies with this frame
+}
+
 int rl_chunk_best_rows(rl_index* idx, const float* queries, int32_t B, const int32_t* candidates, int32_t n_cand,
                        int32_t* out_rows, int mem, void* stream) {
     if (!idx) return fail(RL_ERR_INVALID, "rl_chunk_best_rows: null index");

@@ -434,6 +434,15 @@ size_t partition_sim_scratch_bytes(int64_t n, int64_t n_docs, int32_t dim);
 int launch_partition_similarity(const float* X, int64_t n, int32_t dim, const int64_t* doc_off, int64_t n_docs,
                                 const uint8_t* sel, float* out, void* scratch, hipStream_t s);
 
+// partition_dp.hip: the chunk partition as a shortest path over split positions (`_split_chunks.py:87-113` without the MILP solver),
+// batched over documents.  cost: the layout launch_partition_similarity writes; inv_norm (optional): 1 / |x_i| per row, a row where it
+// is inf or NaN gives its document status 2.  cut [n] is zeroed here.
+size_t partition_dp_scratch_bytes(int64_t n);
+int launch_partition_headings(float* cost /* in: the similarities */, const uint8_t* heading, const int64_t* doc_off, int64_t n_docs,
+                              int64_t n, hipStream_t s);
+int launch_partition_dp(const float* cost, const int64_t* sizes, const float* inv_norm, const int64_t* doc_off, int64_t n, int64_t n_docs,
+                        int64_t max_size, uint8_t* cut, double* objective, int32_t* status, void* scratch, hipStream_t s);
+
 // maxsim*.hip
 int launch_row_to_chunk(const int64_t* chunk_offsets, int64_t n_chunks, int64_t n_rows, int32_t* row_to_chunk,
                         hipStream_t s);

@@ -124,7 +124,8 @@ __global__ __launch_bounds__(256) void ps_choose_kernel(const float* __restrict_
 }
 }  // namespace
 
-// scratch: float[2 * n + n + n_docs * dim] + int32[2 * n_docs]  (see partition_sim_scratch_bytes)
+// scratch: float[2 * n + n + n_docs * dim] + int32[2 * n_docs]  (see partition_sim_scratch_bytes); its first n floats hold 1 / |x_i| once
+// the launches have run (rl_split_chunks reads them for its zero-norm status)
 size_t partition_sim_scratch_bytes(int64_t n, int64_t n_docs, int32_t dim) {
     return (size_t)(3 * n + n_docs * (int64_t)dim) * sizeof(float) + (size_t)(2 * n_docs) * sizeof(int32_t) + 64;
 }
