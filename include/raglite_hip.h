@@ -757,6 +757,32 @@ int rl_chunk_best_rows(rl_index* index, const float* queries, int32_t n_queries,
                        int32_t n_cand, int32_t* out_rows, int mem, void* stream);
 int rl_gather_rows(rl_index* index, const int32_t* rows, int64_t n, float* out, int mem, void* stream);
 
+/* ---- the target vectors of update_query_adapter (src/raglite/_query_adapter.py:20-38) ---------------
+ * Per eval the reference solves t* = argmin |q + D^T mu|^2 over mu >= 0 with D = P_i - (1 + gap) N_j over
+ * the eval's positive rows P and negative rows N (an NNLS on the host).  t* is the projection of the
+ * origin onto q + cone(D): unique, and an active-set iteration on the Gram matrix of the eval's example
+ * rows finds it exactly.  rl_query_targets does that for every eval in one call; the rows are read in
+ * place from the index by ordinal (no rl_gather_rows).
+ *   queries    [B x dim] f32
+ *   rows       [B x n_examples] int32 row ordinals (rl_chunk_best_rows' output), -1 = no example in
+ *              this slot (anywhere in the list)
+ *   relevant   [B x n_examples] uint8, nonzero = the slot's row is a positive example
+ *   n_examples 2 .. RL_QT_MAX_EXAMPLES;  gap >= 0 (optimize_gap, :48)
+ *   targets    [B x dim] f64: t = q + sum_i a_i P_i - (1 + gap) sum_j b_j N_j   (NaN for status 1, 2)
+ *   weights    [B x n_examples] f64 by slot: the non-negative marginals a_i = sum_j mu_ij of a positive,
+ *              b_j = sum_i mu_ij of a negative; 0 for an empty slot
+ *   objective  [B] f64: |t|^2 (NaN for status 1, 2)
+ *   status     [B]: 0 ok; 1 no positive or no negative example (the eval does not qualify, :169);
+ *              2 a non-finite query / example row, or a row ordinal outside the index (never read);
+ *              3 zero target, |t| <= 1e-9 |q| (the constraints cannot be met; the reference would divide
+ *              by |t| = 0); 4 the cap of 4 (p + n) entering steps was reached without status 3
+ *   iterations [B]: entering steps taken
+ * An eval's status never affects its neighbours.  Same bits run to run and for host and device pointers. */
+#define RL_QT_MAX_EXAMPLES 64
+int rl_query_targets(rl_index* index, const float* queries, int32_t n_queries, const int32_t* rows, const uint8_t* relevant,
+                     int32_t n_examples, double gap, double* targets, double* weights, double* objective, int32_t* status,
+                     int32_t* iterations, int mem, void* stream);
+
 /* ---- semantic-chunking similarities ---------------------------------------
  * src/raglite/_split_chunks.py:54-72, the consumer of the pooled chunklet embeddings and the cost
  * vector of the chunk partition, batched over documents.  The partition itself no longer has to

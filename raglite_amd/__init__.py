@@ -69,7 +69,7 @@ from raglite_amd._search import (
 )
 from raglite_amd._cross_encoder import CrossEncoderShape, TorchCrossEncoderRanker
 from raglite_amd._torch_embedder import EncoderShape, HashTokenizer, SentencePieceTokenizer, TorchTokenEmbedder
-from raglite_amd._query_adapter import update_query_adapter
+from raglite_amd._query_adapter import optimize_query_target_active_set, optimize_query_targets, update_query_adapter
 from raglite_amd._comm import Communicator
 from raglite_amd._sharded import ShardedIndex, merge_topk_host, shard_bounds_by_chunk
 
@@ -91,6 +91,8 @@ __all__ = [
     "KeywordIndex",
     "KeywordStore",
     "reciprocal_rank_fusion",
+    "optimize_query_target_active_set",
+    "optimize_query_targets",
     "update_query_adapter",
     "EncoderShape",
     "HashTokenizer",

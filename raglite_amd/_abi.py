@@ -69,6 +69,8 @@ _SIGNATURES = {
                         c_void_p, c_int, c_void_p],
     "rl_chunk_best_rows": [c_void_p, c_void_p, c_i32, c_void_p, c_i32, c_void_p, c_int, c_void_p],
     "rl_gather_rows": [c_void_p, c_void_p, c_i64, c_void_p, c_int, c_void_p],
+    "rl_query_targets": [c_void_p, c_void_p, c_i32, c_void_p, c_void_p, c_i32, c_double, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                         c_int, c_void_p],
     "rl_index_create_f16": [C.POINTER(c_void_p), c_void_p, c_i64, c_i32, c_void_p, c_i64, c_int, c_int, c_void_p],
     "rl_index_append": [c_void_p, c_void_p, c_i64, c_void_p, c_i64, c_int, c_void_p],
     "rl_index_delete_chunks": [c_void_p, c_void_p, c_i64, c_void_p],

@@ -1139,6 +1139,27 @@ class DeviceIndex:
         check(lib().rl_gather_rows(self._handle, p_r, n, p_o, a.mem, a.stream))
         return o
 
+    def query_targets(self, queries, rows, relevant, gap: float = 0.05):
+        """`rl_query_targets`: the exact NNLS target of every eval in one call.  queries (B, dim), rows (B, n_examples) int32 row ordinals
+        (-1 = none), relevant (B, n_examples) nonzero = positive -> (targets float64 (B, dim), weights float64 (B, n_examples),
+        objective float64 (B,), status int32 (B,), iterations int32 (B,)) on the side of `queries`."""
+        a = _Args()
+        p_q, B, _ = self._queries(a, queries)
+        p_r = _same_side(a, rows, np.int32)
+        r = a.keep[-1]
+        p_rel = _same_side(a, relevant, np.uint8)
+        if r.ndim != 2 or int(r.shape[0]) != B or tuple(a.keep[-1].shape) != tuple(r.shape):
+            raise ValueError("query_targets: rows and relevant must be (n_queries, n_examples)")
+        k = int(r.shape[1])
+        T, p_t = a.out((B, self.dim), np.float64)  # noqa: N806
+        w, p_w = a.out((B, k), np.float64)
+        obj, p_o = a.out((B,), np.float64)
+        status, p_s = a.out((B,), np.int32)
+        iters, p_i = a.out((B,), np.int32)
+        self._prep(a)
+        check(lib().rl_query_targets(self._handle, p_q, B, p_r, p_rel, k, float(gap), p_t, p_w, p_o, p_s, p_i, a.mem, a.stream))
+        return T, w, obj, status, iters
+
     def time_kernel(self, kind: int, query_vecs_cuda, iters: int) -> float:
         """Milliseconds (HIP events on the launch stream) for `iters` launches of the dominant kernel."""
         a = _Args()

@@ -1,7 +1,8 @@
 // 8f-3: the device half of `update_query_adapter` (src/raglite/_query_adapter.py:153-205).  The batched vector
 // search is rl_search_chunks; what is left on the device is, for every (eval, retrieved chunk), the row
 //     np.argmax(chunk.embedding_matrix @ q)                                  (_query_adapter.py:174,180)
-// and fetching those rows for the host's NNLS / Procrustes step (fp64 LAPACK, stays on the host).
+// and fetching those rows for the host's NNLS (targets="nnls"; query_targets.hip solves it on the device for targets="device", reading
+// the rows in place) and Procrustes step (fp64 LAPACK, stays on the host).
 #include "common.h"
 
 namespace rl {

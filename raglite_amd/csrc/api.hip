@@ -3050,6 +3050,46 @@ int rl_gather_rows(rl_index* idx, const int32_t* rows, int64_t n, float* out, in
     return finish(mem, s);
 }
 
+int rl_query_targets(rl_index* idx, const float* queries, int32_t B, const int32_t* rows, const uint8_t* relevant, int32_t k, double gap,
+                     double* targets, double* weights, double* objective, int32_t* status, int32_t* iterations, int mem, void* stream) {
+    if (!idx) return fail(RL_ERR_INVALID, "rl_query_targets: index is null");
+    if (B < 1) return fail(RL_ERR_INVALID, "rl_query_targets: n_queries must be >= 1");
+    if (k < 2 || k > RL_QT_MAX_EXAMPLES) return fail(RL_ERR_INVALID, "rl_query_targets: n_examples must be 2 .. 64");
+    if (!(gap >= 0.0) || !std::isfinite(gap)) return fail(RL_ERR_INVALID, "rl_query_targets: gap must be finite and >= 0");
+    if (mem != RL_MEM_HOST && mem != RL_MEM_DEVICE) return fail(RL_ERR_INVALID, "rl_query_targets: bad mem");
+    if (!queries) return fail(RL_ERR_INVALID, "rl_query_targets: queries is null");
+    if (!rows) return fail(RL_ERR_INVALID, "rl_query_targets: rows is null");
+    if (!relevant) return fail(RL_ERR_INVALID, "rl_query_targets: relevant is null");
+    if (!targets) return fail(RL_ERR_INVALID, "rl_query_targets: targets is null");
+    if (!weights) return fail(RL_ERR_INVALID, "rl_query_targets: weights is null");
+    if (!objective) return fail(RL_ERR_INVALID, "rl_query_targets: objective is null");
+    if (!status) return fail(RL_ERR_INVALID, "rl_query_targets: status is null");
+    if (!iterations) return fail(RL_ERR_INVALID, "rl_query_targets: iterations is null");
+    hipStream_t s = as_stream(stream);
+    std::lock_guard<std::mutex> lock(idx->mu);
+    RL_TRY(use_scratch(idx, s));
+    const size_t dim = (size_t)idx->dim, n = (size_t)B * k;
+    DevBuf t_q, t_r, t_rel, t_t, t_w, t_o, t_st, t_it, t_scr;
+    const float* d_q; const int32_t* d_r; const uint8_t* d_rel; double* d_t; double* d_w; double* d_o; int32_t* d_st; int32_t* d_it;
+    RL_TRY(stage_in(queries, (size_t)B * dim, mem, s, t_q, &d_q));
+    RL_TRY(stage_in(rows, n, mem, s, t_r, &d_r));
+    RL_TRY(stage_in(relevant, n, mem, s, t_rel, &d_rel));
+    RL_TRY(stage_out_begin(targets, (size_t)B * dim, mem, t_t, &d_t));
+    RL_TRY(stage_out_begin(weights, n, mem, t_w, &d_w));
+    RL_TRY(stage_out_begin(objective, (size_t)B, mem, t_o, &d_o));
+    RL_TRY(stage_out_begin(status, (size_t)B, mem, t_st, &d_st));
+    RL_TRY(stage_out_begin(iterations, (size_t)B, mem, t_it, &d_it));
+    RL_TRY(t_scr.alloc(query_targets_scratch_bytes(B, k)));
+    RL_TRY(launch_query_targets(idx->E16 ? (const void*)idx->E16 : (const void*)idx->E, idx->E16 != nullptr, idx->dim, idx->n_rows, d_q, B,
+                                d_r, d_rel, k, gap, d_t, d_w, d_o, d_st, d_it, t_scr.p, s));
+    RL_TRY(stage_out_end(targets, (size_t)B * dim, mem, s, t_t));
+    RL_TRY(stage_out_end(weights, n, mem, s, t_w));
+    RL_TRY(stage_out_end(objective, (size_t)B, mem, s, t_o));
+    RL_TRY(stage_out_end(status, (size_t)B, mem, s, t_st));
+    RL_TRY(stage_out_end(iterations, (size_t)B, mem, s, t_it));
+    return sync_and_drain(s);  // the scratch dies with this frame
+}
+
 int rl_time_kernel(rl_index* idx, int kind, const float* q_dev, int32_t nq, int32_t iters, float* out_ms_total,
                    void* stream) {
     if (!idx || !q_dev || !out_ms_total || iters < 1 || nq < 1) return fail(RL_ERR_INVALID, "rl_time_kernel: bad arguments");

@@ -429,6 +429,12 @@ int launch_gather_rows(const void* E, bool f16, int32_t dim, int64_t n_rows, con
                        hipStream_t s, const uint32_t* counts = nullptr, int32_t cap = 0);
 int launch_compact_rows(const void* src, int64_t row_bytes, const int64_t* old_row, int64_t n, void* dst, hipStream_t s);
 
+// query_targets.hip: the exact NNLS targets of update_query_adapter, batched over evals (Gram, solve, target: three launches)
+size_t query_targets_scratch_bytes(int32_t B, int32_t k);
+int launch_query_targets(const void* E, bool f16, int32_t dim, int64_t n_rows, const float* Q, int32_t B, const int32_t* rows,
+                         const uint8_t* relevant, int32_t k, double gap, double* targets, double* weights, double* objective,
+                         int32_t* status, int32_t* iterations, void* scratch, hipStream_t s);
+
 // partition_sim.hip: semantic-chunking similarities (src/raglite/_split_chunks.py:54-72), batched over documents
 size_t partition_sim_scratch_bytes(int64_t n, int64_t n_docs, int32_t dim);
 int launch_partition_similarity(const float* X, int64_t n, int32_t dim, const int64_t* doc_off, int64_t n_docs,
