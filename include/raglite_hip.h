@@ -828,6 +828,35 @@ int rl_split_chunks(const float* X, int64_t n, int32_t dim, const int64_t* doc_o
                     const uint8_t* nonoutlying, const uint8_t* is_heading, const int64_t* sizes, int64_t max_size,
                     uint8_t* cut, float* cost_out, double* objective, int32_t* status, int mem, void* stream);
 
+/* ---- chunklet partition on the device -----------------------------------
+ * src/raglite/_split_chunklets.py:136-178 cuts a document's sentences into chunklets by an exact
+ * shortest path over split positions in float64:
+ *   dp[i] = min over j in [lo(i), i) of dp[j] + cost(j, i),   lo(i) = smallest j with chars(j..i) <= max_size
+ *   cost(j, i) = ((1.0 - p[j]) + (pb[i] - pb[j+1])) + (s - 3.0)^2 / sqrt(max(s, 1e-6)) / 2.0,  s = ps[i] - ps[j]
+ * (pb, ps: prefix sums of boundary and statements, summed strictly left to right per document).  One
+ * document per wave, no limit on a document's length, no atomics, same bits run to run and for host
+ * and device pointers.  Ties: the smallest j; +inf takes part in ties and NaN never wins, so behind a
+ * sentence longer than max_size the partition is still the reference's.  The square is x * x, where
+ * the reference's NumPy scalar `** 2` calls libm pow (a last-bit difference for about one value in a
+ * thousand): raglite_amd._chunklets.chunklet_dp states the same recurrence on the host and the two
+ * agree bit for bit; against the reference the partitions agree.
+ *   boundary     f64[n] Markdown boundary probability of every sentence (markdown_chunklet_boundaries)
+ *   statements   f64[n] statement count of every sentence (compute_num_statements)
+ *   lengths      int64[n] sentence string lengths (>= 0)
+ *   doc_offsets  int64[n_docs + 1] CSR over the sentences (starts at 0, ascends, ends at n)
+ *   cut          uint8[n]: 1 = a chunklet ends after sentence i (never at a document's last sentence)
+ *   objective    f64[n_docs] (nullable): dp[n_d]; 0 for an empty document; may be +inf (status 1);
+ *                NaN with status 2
+ *   status       int32[n_docs]: 0 = ok; 1 = a sentence longer than max_size (the reference does not
+ *                raise there, the cuts are its cuts); 2 = a non-finite boundary or statements value
+ *                (no cuts; it wins over 1)
+ * RL_ERR_INVALID before any HIP call: n < 0, max_size < 1, n > 0 with n_docs < 1 or a null pointer,
+ * and for RL_MEM_HOST offsets that do not start at 0 / ascend / end at n, or a negative length.  n == 0
+ * returns RL_OK and writes nothing. */
+int rl_partition_chunklets(const double* boundary, const double* statements, const int64_t* lengths,
+                           const int64_t* doc_offsets, int64_t n, int64_t n_docs, int64_t max_size,
+                           uint8_t* cut, double* objective, int32_t* status, int mem, void* stream);
+
 /* What the last bound-filtered search on this index did (diagnostic; bench.py reports it next to every timed number that depends
  * on it).  The searches that rank on approximate scores and re-score what a rigorous bound cannot rule out -- rl_maxsim_topk_batch
  * over the HI image, rl_search_rows for B <= 16 over the HI plane, the fused top-k of B >= 96 -- keep per-query candidate lists of a

@@ -15,6 +15,15 @@ from raglite_amd._chunking import (
     split_chunks,
     split_chunks_batch,
 )
+from raglite_amd._chunklets import (
+    chunklet_dp,
+    compute_num_statements,
+    markdown_chunklet_boundaries,
+    partition_chunklets,
+    split_chunklets,
+    split_chunklets_batch,
+    split_documents_batch,
+)
 from raglite_amd._config import HotPathConfig
 from raglite_amd._embed import (
     embed_strings,
@@ -83,6 +92,8 @@ __all__ = [
     "split_chunks_batch",
     "partition_chunks",
     "solve_partition_dp",
+    "split_chunklets", "split_chunklets_batch", "split_documents_batch", "partition_chunklets", "chunklet_dp",
+    "markdown_chunklet_boundaries", "compute_num_statements",
     "hybrid_search",
     "hybrid_search_batch",
     "keyword_search",

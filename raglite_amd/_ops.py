@@ -1367,6 +1367,33 @@ def partition_chunks(cost: Any, sizes: Any, doc_offsets: Any, max_size: int) -> 
     return cut, obj, status
 
 
+def partition_chunklets(boundary: Any, statements: Any, lengths: Any, doc_offsets: Any, max_size: int,
+                        want_objective: bool = True) -> tuple[Any, Any, Any]:
+    """`rl_partition_chunklets`: the chunklet cuts of many documents in one call.  boundary / statements float64[n], lengths int64[n],
+    doc_offsets int64[n_docs + 1] -> (cut uint8[n], objective float64[n_docs] or None, status int32[n_docs]) on the side of
+    `boundary`."""
+    a = _Args()
+    p_b = a.inp(boundary, np.float64)
+    n = int(a.keep[0].shape[0])
+    p_s = _same_side(a, statements, np.float64)
+    p_len = _same_side(a, lengths, np.int64)
+    if int(a.keep[-1].shape[0]) != n or int(a.keep[-2].shape[0]) != n:
+        raise ValueError("partition_chunklets: boundary, statements and lengths differ in length")
+    p_off = _same_side(a, doc_offsets, np.int64)
+    n_docs = int(a.keep[-1].shape[0]) - 1
+    cut, p_cut = a.out((n,), np.uint8)
+    obj, p_obj = a.out((max(n_docs, 0),), np.float64) if want_objective else (None, None)
+    status, p_status = a.out((max(n_docs, 0),), np.int32)
+    if n == 0 and n_docs >= 0:  # the call writes nothing: every document is empty
+        if obj is not None:
+            obj[...] = 0.0
+        status[...] = 0
+        return cut, obj, status
+    a.ensure_device()
+    check(lib().rl_partition_chunklets(p_b, p_s, p_len, p_off, n, n_docs, int(max_size), p_cut, p_obj, p_status, a.mem, a.stream))
+    return cut, obj, status
+
+
 def split_chunks_call(embeddings: Any, doc_offsets: Any, nonoutlying: Any, is_heading: Any, sizes: Any, max_size: int,
                       want_cost: bool = False) -> tuple[Any, Any, Any, Any]:
     """`rl_split_chunks`: similarities -> heading adjustments -> partition for many documents in one call.  embeddings (n, dim);

@@ -3012,6 +3012,33 @@ int rl_split_chunks(const float* X, int64_t n, int32_t dim, const int64_t* doc_o
     return sync_and_drain(s);  // the scratch dies with this frame
 }
 
+int rl_partition_chunklets(const double* boundary, const double* statements, const int64_t* lengths, const int64_t* doc_offsets, int64_t n,
+                           int64_t n_docs, int64_t max_size, uint8_t* cut, double* objective, int32_t* status, int mem, void* stream) {
+    if (n < 0) return fail(RL_ERR_INVALID, "rl_partition_chunklets: n must be >= 0");
+    if (max_size < 1) return fail(RL_ERR_INVALID, "rl_partition_chunklets: max_size must be >= 1");
+    if (mem != RL_MEM_HOST && mem != RL_MEM_DEVICE) return fail(RL_ERR_INVALID, "rl_partition_chunklets: bad mem");
+    if (n == 0) return RL_OK;
+    if (!boundary) return fail(RL_ERR_INVALID, "rl_partition_chunklets: boundary is null");
+    if (!statements) return fail(RL_ERR_INVALID, "rl_partition_chunklets: statements is null");
+    RL_TRY(partition_args("rl_partition_chunklets", lengths, doc_offsets, n, n_docs, cut, status, mem));
+    hipStream_t s = as_stream(stream);
+    DevBuf t_b, t_st, t_len, t_off, t_cut, t_obj, t_status, t_scr;
+    const double* d_b; const double* d_s; const int64_t* d_len; const int64_t* d_off; uint8_t* d_cut; double* d_obj; int32_t* d_status;
+    RL_TRY(stage_in(boundary, (size_t)n, mem, s, t_b, &d_b));
+    RL_TRY(stage_in(statements, (size_t)n, mem, s, t_st, &d_s));
+    RL_TRY(stage_in(lengths, (size_t)n, mem, s, t_len, &d_len));
+    RL_TRY(stage_in(doc_offsets, (size_t)n_docs + 1, mem, s, t_off, &d_off));
+    RL_TRY(stage_out_begin(cut, (size_t)n, mem, t_cut, &d_cut));
+    RL_TRY(stage_out_begin(objective, (size_t)n_docs, mem, t_obj, &d_obj));
+    RL_TRY(stage_out_begin(status, (size_t)n_docs, mem, t_status, &d_status));
+    RL_TRY(t_scr.alloc(chunklet_dp_scratch_bytes(n, n_docs)));
+    RL_TRY(launch_chunklet_dp(d_b, d_s, d_len, d_off, n, n_docs, max_size, d_cut, d_obj, d_status, t_scr.p, s));
+    RL_TRY(stage_out_end(cut, (size_t)n, mem, s, t_cut));
+    RL_TRY(stage_out_end(objective, (size_t)n_docs, mem, s, t_obj));
+    RL_TRY(stage_out_end(status, (size_t)n_docs, mem, s, t_status));
+    return sync_and_drain(s);  // the scratch dies with this frame
+}
+
 int rl_chunk_best_rows(rl_index* idx, const float* queries, int32_t B, const int32_t* candidates, int32_t n_cand,
                        int32_t* out_rows, int mem, void* stream) {
     if (!idx) return fail(RL_ERR_INVALID, "rl_chunk_best_rows: null index");

@@ -449,6 +449,12 @@ int launch_partition_headings(float* cost /* in: the similarities */, const uint
 int launch_partition_dp(const float* cost, const int64_t* sizes, const float* inv_norm, const int64_t* doc_off, int64_t n, int64_t n_docs,
                         int64_t max_size, uint8_t* cut, double* objective, int32_t* status, void* scratch, hipStream_t s);
 
+// chunklet_dp.hip: the chunklet partition of `_split_chunklets.py:136-178` (an exact shortest path over split positions in float64),
+// batched over documents.  boundary / statements: one value per sentence; lengths: the sentences' characters.  cut [n] is zeroed here.
+size_t chunklet_dp_scratch_bytes(int64_t n, int64_t n_docs);
+int launch_chunklet_dp(const double* boundary, const double* statements, const int64_t* lengths, const int64_t* doc_off, int64_t n,
+                       int64_t n_docs, int64_t max_size, uint8_t* cut, double* objective, int32_t* status, void* scratch, hipStream_t s);
+
 // maxsim*.hip
 int launch_row_to_chunk(const int64_t* chunk_offsets, int64_t n_chunks, int64_t n_rows, int32_t* row_to_chunk,
                         hipStream_t s);
