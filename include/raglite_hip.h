@@ -857,6 +857,36 @@ int rl_partition_chunklets(const double* boundary, const double* statements, con
                            const int64_t* doc_offsets, int64_t n, int64_t n_docs, int64_t max_size,
                            uint8_t* cut, double* objective, int32_t* status, int mem, void* stream);
 
+/* ---- sentence partition on the device -----------------------------------
+ * src/raglite/_split_sentences.py:183-218: what the reference does with its model's boundary
+ * probability per character.  Known boundaries override the prediction; white space is made to trail
+ * a sentence (per run of white space behind a character: the minimum up to the penultimate position,
+ * the maximum at the last); a dynamic programme in float64 picks the boundaries that maximise the sum
+ * of (probability - 0.25) with no sentence shorter than min_len (phase 1: the earliest of equal
+ * predecessors wins); every resulting sentence longer than max_len is solved again under max_len
+ * (phase 2: the latest of equal predecessors in the window wins).  One document per wave, no atomics,
+ * same bits run to run and for host and device pointers; raglite_amd._sentences.sentence_partition
+ * states the same computation on the host and the two agree bit for bit.
+ *   codepoints   uint32[n] the characters (UTF-32); the white-space class is Python's str.isspace
+ *   probas       f32[n] (probas_f64 == 0) or f64[n]: the subtraction of 0.25 is done in that type
+ *   known        f64[n] or NULL: a finite value replaces the prediction (cast to the type of probas)
+ *   doc_offsets  int64[n_docs + 1] CSR over the characters (starts at 0, ascends, ends at n)
+ *   min_len      >= 1;  max_len  0 = none
+ *   cut          uint8[n]: 1 = character i is the last of a sentence (never a document's last one)
+ *   objective    f64[n_docs] (nullable): the phase-1 best score; 0.0 with no boundary; NaN with status 2
+ *   status       int32[n_docs]: 0 = ok; 1 = some sentence is longer than max_len (one longer than
+ *                max_len but shorter than 2 * min_len comes back unsplit, as in the reference; the
+ *                cuts are its cuts); 2 = a non-finite probability after the override (no cuts);
+ *                3 = no valid split under max_len (no cuts; the reference raises).  2 wins over 3,
+ *                3 over 1.
+ * RL_ERR_INVALID before any HIP call: n < 0, min_len < 1, max_len < 0, n > 0 with n_docs < 1 or a
+ * null codepoints / probas / doc_offsets / cut / status, a document of 2^31 characters or more, and
+ * for RL_MEM_HOST offsets that do not start at 0 / ascend / end at n.  n == 0 returns RL_OK and
+ * writes nothing. */
+int rl_partition_sentences(const uint32_t* codepoints, const void* probas, int probas_f64, const double* known,
+                           const int64_t* doc_offsets, int64_t n, int64_t n_docs, int64_t min_len, int64_t max_len,
+                           uint8_t* cut, double* objective, int32_t* status, int mem, void* stream);
+
 /* What the last bound-filtered search on this index did (diagnostic; bench.py reports it next to every timed number that depends
  * on it).  The searches that rank on approximate scores and re-score what a rigorous bound cannot rule out -- rl_maxsim_topk_batch
  * over the HI image, rl_search_rows for B <= 16 over the HI plane, the fused top-k of B >= 96 -- keep per-query candidate lists of a

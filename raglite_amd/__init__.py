@@ -24,6 +24,17 @@ from raglite_amd._chunklets import (
     split_chunklets_batch,
     split_documents_batch,
 )
+from raglite_amd._sentences import (
+    markdown_sentence_boundaries,
+    partition_sentences,
+    propagate_whitespace,
+    sentence_dp,
+    sentence_partition,
+    split_sentences,
+    split_sentences_batch,
+    split_texts_batch,
+    whitespace_mask,
+)
 from raglite_amd._config import HotPathConfig
 from raglite_amd._embed import (
     embed_strings,
@@ -94,6 +105,8 @@ __all__ = [
     "solve_partition_dp",
     "split_chunklets", "split_chunklets_batch", "split_documents_batch", "partition_chunklets", "chunklet_dp",
     "markdown_chunklet_boundaries", "compute_num_statements",
+    "split_sentences", "split_sentences_batch", "split_texts_batch", "partition_sentences", "sentence_dp", "sentence_partition",
+    "markdown_sentence_boundaries", "whitespace_mask", "propagate_whitespace",
     "hybrid_search",
     "hybrid_search_batch",
     "keyword_search",

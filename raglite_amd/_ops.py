@@ -1394,6 +1394,47 @@ def partition_chunklets(boundary: Any, statements: Any, lengths: Any, doc_offset
     return cut, obj, status
 
 
+def partition_sentences(codepoints: Any, probas: Any, doc_offsets: Any, min_len: int = 4, max_len: int | None = None,
+                        known: Any | None = None, want_objective: bool = True) -> tuple[Any, Any, Any]:
+    """`rl_partition_sentences`: the sentence cuts of many documents in one call.  codepoints uint32[n] (a CUDA tensor: uint32 or
+    int32, the same bits), probas float32[n] or float64[n] (other dtypes are widened to float64), doc_offsets int64[n_docs + 1],
+    known float64[n] or None -> (cut uint8[n], objective float64[n_docs] or None, status int32[n_docs]) on the side of `probas`."""
+    if min_len < 1 or (max_len is not None and max_len < 1):
+        raise ValueError("partition_sentences: min_len >= 1 and max_len >= 1 (or None) are required")
+    a = _Args()
+    if _is_torch(probas):
+        f64 = probas.dtype != _torch().float32
+    else:
+        probas = np.asarray(probas)
+        f64 = probas.dtype != np.float32
+    p_p = a.inp(probas, np.float64 if f64 else np.float32)
+    n = int(a.keep[0].shape[0])
+    if _is_torch(codepoints):
+        torch = _torch()
+        if codepoints.dtype not in (torch.int32, torch.uint32):
+            codepoints = codepoints.to(torch.int32)  # code points are below 2^21
+        p_cp = a.inp(codepoints.view(torch.int32), np.int32)
+    else:
+        p_cp = _same_side(a, np.ascontiguousarray(codepoints, dtype=np.uint32).view(np.int32), np.int32)
+    p_known = _same_side(a, known, np.float64) if known is not None else None
+    if any(int(x.shape[0]) != n for x in a.keep[1:]):
+        raise ValueError("partition_sentences: codepoints, probas and known differ in length")
+    p_off = _same_side(a, doc_offsets, np.int64)
+    n_docs = int(a.keep[-1].shape[0]) - 1
+    cut, p_cut = a.out((n,), np.uint8)
+    obj, p_obj = a.out((max(n_docs, 0),), np.float64) if want_objective else (None, None)
+    status, p_status = a.out((max(n_docs, 0),), np.int32)
+    if n == 0 and n_docs >= 0:  # the call writes nothing: every document is empty
+        if obj is not None:
+            obj[...] = 0.0
+        status[...] = 0
+        return cut, obj, status
+    a.ensure_device()
+    check(lib().rl_partition_sentences(p_cp, p_p, int(f64), p_known, p_off, n, n_docs, int(min_len), int(max_len or 0), p_cut, p_obj,
+                                       p_status, a.mem, a.stream))
+    return cut, obj, status
+
+
 def split_chunks_call(embeddings: Any, doc_offsets: Any, nonoutlying: Any, is_heading: Any, sizes: Any, max_size: int,
                       want_cost: bool = False) -> tuple[Any, Any, Any, Any]:
     """`rl_split_chunks`: similarities -> heading adjustments -> partition for many documents in one call.  embeddings (n, dim);

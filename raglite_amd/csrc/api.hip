@@ -3039,6 +3039,49 @@ int rl_partition_chunklets(const double* boundary, const double* statements, con
     return sync_and_drain(s);  // the scratch dies with this frame
 }
 
+int rl_partition_sentences(const uint32_t* codepoints, const void* probas, int probas_f64, const double* known, const int64_t* doc_offsets,
+                           int64_t n, int64_t n_docs, int64_t min_len, int64_t max_len, uint8_t* cut, double* objective, int32_t* status,
+                           int mem, void* stream) {
+    if (n < 0) return fail(RL_ERR_INVALID, "rl_partition_sentences: n must be >= 0");
+    if (min_len < 1) return fail(RL_ERR_INVALID, "rl_partition_sentences: min_len must be >= 1");
+    if (max_len < 0) return fail(RL_ERR_INVALID, "rl_partition_sentences: max_len must be >= 0 (0: none)");
+    if (mem != RL_MEM_HOST && mem != RL_MEM_DEVICE) return fail(RL_ERR_INVALID, "rl_partition_sentences: bad mem");
+    if (n == 0) return RL_OK;
+    if (n_docs < 1) return fail(RL_ERR_INVALID, "rl_partition_sentences: n_docs must be >= 1");
+    if (!codepoints) return fail(RL_ERR_INVALID, "rl_partition_sentences: codepoints is null");
+    if (!probas) return fail(RL_ERR_INVALID, "rl_partition_sentences: probas is null");
+    if (!doc_offsets) return fail(RL_ERR_INVALID, "rl_partition_sentences: doc_offsets is null");
+    if (!cut) return fail(RL_ERR_INVALID, "rl_partition_sentences: cut is null");
+    if (!status) return fail(RL_ERR_INVALID, "rl_partition_sentences: status is null");
+    const int64_t doc_max = (int64_t)1 << 31;  // back-pointers are int32
+    if (n_docs == 1 && n >= doc_max) return fail(RL_ERR_INVALID, "rl_partition_sentences: a document must be shorter than 2^31 characters");
+    if (mem == RL_MEM_HOST) {
+        if (doc_offsets[0] != 0) return fail(RL_ERR_INVALID, "rl_partition_sentences: doc_offsets must start at 0");
+        for (int64_t d = 0; d < n_docs; ++d) {
+            if (doc_offsets[d + 1] < doc_offsets[d]) return fail(RL_ERR_INVALID, "rl_partition_sentences: doc_offsets must be ascending");
+            if (doc_offsets[d + 1] - doc_offsets[d] >= doc_max)
+                return fail(RL_ERR_INVALID, "rl_partition_sentences: a document must be shorter than 2^31 characters");
+        }
+        if (doc_offsets[n_docs] != n) return fail(RL_ERR_INVALID, "rl_partition_sentences: doc_offsets must end at n");
+    }
+    hipStream_t s = as_stream(stream);
+    DevBuf t_cp, t_p, t_k, t_off, t_cut, t_obj, t_status, t_scr;
+    const uint32_t* d_cp; const uint8_t* d_p; const double* d_k = nullptr; const int64_t* d_off; uint8_t* d_cut; double* d_obj; int32_t* d_status;
+    RL_TRY(stage_in(codepoints, (size_t)n, mem, s, t_cp, &d_cp));
+    RL_TRY(stage_in(static_cast<const uint8_t*>(probas), (size_t)n * (probas_f64 ? 8 : 4), mem, s, t_p, &d_p));
+    if (known) RL_TRY(stage_in(known, (size_t)n, mem, s, t_k, &d_k));
+    RL_TRY(stage_in(doc_offsets, (size_t)n_docs + 1, mem, s, t_off, &d_off));
+    RL_TRY(stage_out_begin(cut, (size_t)n, mem, t_cut, &d_cut));
+    RL_TRY(stage_out_begin(objective, (size_t)n_docs, mem, t_obj, &d_obj));
+    RL_TRY(stage_out_begin(status, (size_t)n_docs, mem, t_status, &d_status));
+    RL_TRY(t_scr.alloc(sentence_dp_scratch_bytes(n, n_docs)));
+    RL_TRY(launch_sentence_dp(d_cp, d_p, probas_f64, d_k, d_off, n, n_docs, min_len, max_len, d_cut, d_obj, d_status, t_scr.p, s));
+    RL_TRY(stage_out_end(cut, (size_t)n, mem, s, t_cut));
+    RL_TRY(stage_out_end(objective, (size_t)n_docs, mem, s, t_obj));
+    RL_TRY(stage_out_end(status, (size_t)n_docs, mem, s, t_status));
+    return sync_and_drain(s);  // the scratch dies with this frame
+}
+
 int rl_chunk_best_rows(rl_index* idx, const float* queries, int32_t B, const int32_t* candidates, int32_t n_cand,
                        int32_t* out_rows, int mem, void* stream) {
     if (!idx) return fail(RL_ERR_INVALID, "rl_chunk_best_rows: null index");

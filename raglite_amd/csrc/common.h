@@ -455,6 +455,14 @@ size_t chunklet_dp_scratch_bytes(int64_t n, int64_t n_docs);
 int launch_chunklet_dp(const double* boundary, const double* statements, const int64_t* lengths, const int64_t* doc_off, int64_t n,
                        int64_t n_docs, int64_t max_size, uint8_t* cut, double* objective, int32_t* status, void* scratch, hipStream_t s);
 
+// sentence_dp.hip: the sentence partition of `_split_sentences.py:183-218` (override, white-space propagation, the dynamic programme
+// without and with a maximum length in float64), batched over documents.  codepoints / probas / known: one value per character.
+// cut [n] is zeroed here.
+size_t sentence_dp_scratch_bytes(int64_t n, int64_t n_docs);
+int launch_sentence_dp(const uint32_t* codepoints, const void* probas, int probas_f64, const double* known, const int64_t* doc_off,
+                       int64_t n, int64_t n_docs, int64_t min_len, int64_t max_len, uint8_t* cut, double* objective, int32_t* status,
+                       void* scratch, hipStream_t s);
+
 // maxsim*.hip
 int launch_row_to_chunk(const int64_t* chunk_offsets, int64_t n_chunks, int64_t n_rows, int32_t* row_to_chunk,
                         hipStream_t s);
