@@ -515,6 +515,46 @@ int rl_keyword_store_count(rl_keyword_store* s, const int32_t* term_rank, int32_
 int rl_keyword_store_build(rl_keyword_store* s, const float* idf, const float* nrm, rl_keyword_index** out, int mem,
                            void* stream);
 
+/* ---- keyword analyzer: chunk bodies to stable term ids on the device --------
+ * What raglite_amd._keyword.index_stems does per chunk and stems_to_store_ids per token, for many chunk bodies in one call:
+ * fold (NFKD, drop combining marks, lowercase), split on DuckDB's `(\\.|[^a-z])+`, drop stopwords, Porter-stem, and number
+ * the stems.  The library embeds neither Unicode data nor a word list: rl_keyword_analyzer_create takes
+ *   fold_table  uint32[n_table] (host; n_table <= 2^21, 0x110000 covers Unicode): the image of each code point under the
+ *               fold, up to six symbols in fields of 5 bits from bit 0, field = symbol + 1, 0 = no further symbol; symbols
+ *               0 .. 25 = a .. z, 26 = a separator (a run of them may be given as one), 27 = a backslash, 28 = a newline.
+ *               An empty image is no symbol at all.  A code point >= n_table is a separator.
+ *   stopwords   the words' bytes back to back, stop_off int64[n_stop + 1] into them (host); words with a byte outside a-z
+ *               can equal no token and are dropped
+ *   hash_bits   0 = the full 64-bit hash of a stem; b > 0 = only its b low bits (for tests: forces stems to collide)
+ * rl_keyword_analyze_begin takes codepoints uint32[n] (UTF-32) and text_off int64[n_texts + 1] (a CSR over them; starts at
+ * 0, ascends, ends at n: checked when it is host memory), host or device pointers by `mem`.  Nothing carries from one text
+ * to the next: neither a token nor an escape crosses a text boundary.  It leaves the call's distinct stems on the device,
+ * numbered by first appearance (text order, then token order, stopwords not counted), and returns
+ *   out_counts = (n_tokens: the non-stopword tokens, n_distinct, stem_bytes: the letters of all distinct stems, n_symbols:
+ *   the length of the folded stream, n_all_tokens: stopwords included).
+ * rl_keyword_analyze_stems copies them out (NULL skips one): stem_bytes [stem_bytes] ASCII letters, stem_off [n_distinct + 1],
+ * first_pos [n_distinct] the index among the call's n_tokens of each stem's first token (ascending).  A stem may be empty
+ * (the token `s`, unless it is a stopword).  The caller owns the vocabulary: rl_keyword_analyze_finish takes
+ * ids int32[n_distinct] >= 0, one per distinct stem in that order, and writes, in device memory the analyzer owns until its
+ * next begin or its destruction,
+ *   term_ids int32[n_tokens]: the id of every kept token in text order;  offsets int64[n_texts + 1]: text c holds
+ *   term_ids[offsets[c] .. offsets[c + 1]) -- what rl_keyword_store_append takes with RL_MEM_DEVICE.
+ * rl_keyword_analyze_result copies both out.  Stems are made distinct by an open-addressing table of token numbers
+ * (64-bit integer compare-and-swap and min, bytes compared on every hit: exact under hash collisions); nothing in the
+ * outputs depends on the order in which lanes arrive, so they are the same bytes run to run.  Positions are 64-bit; one
+ * call takes fewer than 2^40 code points.  The calls on one analyzer are serialised; each returns synchronised. */
+typedef struct rl_keyword_analyzer rl_keyword_analyzer;
+int rl_keyword_analyzer_create(rl_keyword_analyzer** out, const uint32_t* fold_table, int64_t n_table, const char* stopwords,
+                               const int64_t* stop_off, int32_t n_stop, int32_t hash_bits);
+int rl_keyword_analyzer_destroy(rl_keyword_analyzer* a);
+int rl_keyword_analyze_begin(rl_keyword_analyzer* a, const uint32_t* codepoints, const int64_t* text_off, int64_t n,
+                             int64_t n_texts, int64_t out_counts[5], int mem, void* stream);
+int rl_keyword_analyze_stems(rl_keyword_analyzer* a, uint8_t* stem_bytes, int64_t* stem_off, int64_t* first_pos, int mem,
+                             void* stream);
+int rl_keyword_analyze_finish(rl_keyword_analyzer* a, const int32_t* ids, int mem, const int32_t** term_ids,
+                              const int64_t** offsets, void* stream);
+int rl_keyword_analyze_result(rl_keyword_analyzer* a, int32_t* term_ids, int64_t* offsets, int mem, void* stream);
+
 /* ---- weighted Reciprocal Rank Fusion and batched hybrid search ---------------------------------------
  * rl_rrf_fuse replaces src/raglite/_search.py:233-252 (`reciprocal_rank_fusion`) for a batch of queries, bit for bit:
  *   lists       int32 [n_lists x n_queries x len], 1 <= n_lists <= 4, n_lists * len <= 4096: list r of query b is

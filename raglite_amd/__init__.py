@@ -45,6 +45,7 @@ from raglite_amd._embed import (
 )
 from raglite_amd._ops import (
     DeviceIndex,
+    KeywordAnalyzer,
     KeywordIndex,
     KeywordStore,
     adapter_apply,
@@ -61,6 +62,7 @@ from raglite_amd._ops import (
     synth_fill,
     topk,
 )
+from raglite_amd._keyword import analyze_texts_batch
 from raglite_amd._search import (
     GpuIndex,
     hybrid_search,
@@ -112,8 +114,10 @@ __all__ = [
     "keyword_search",
     "keyword_search_batch",
     "vector_search_batch",
+    "KeywordAnalyzer",
     "KeywordIndex",
     "KeywordStore",
+    "analyze_texts_batch",
     "reciprocal_rank_fusion",
     "optimize_query_target_active_set",
     "optimize_query_targets",

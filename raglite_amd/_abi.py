@@ -132,6 +132,12 @@ _SIGNATURES = {
     "rl_keyword_store_delete": [c_void_p, c_void_p, c_i64, c_void_p],
     "rl_keyword_store_count": [c_void_p, c_void_p, c_i32, c_void_p, c_void_p, c_void_p, c_int, c_void_p],
     "rl_keyword_store_build": [c_void_p, c_void_p, c_void_p, C.POINTER(c_void_p), c_int, c_void_p],
+    "rl_keyword_analyzer_create": [C.POINTER(c_void_p), c_void_p, c_i64, c_void_p, c_void_p, c_i32, c_i32],
+    "rl_keyword_analyzer_destroy": [c_void_p],
+    "rl_keyword_analyze_begin": [c_void_p, c_void_p, c_void_p, c_i64, c_i64, c_void_p, c_int, c_void_p],
+    "rl_keyword_analyze_stems": [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p],
+    "rl_keyword_analyze_finish": [c_void_p, c_void_p, c_int, C.POINTER(c_void_p), C.POINTER(c_void_p), c_void_p],
+    "rl_keyword_analyze_result": [c_void_p, c_void_p, c_void_p, c_int, c_void_p],
     "rl_rrf_fuse": [c_void_p, c_i32, c_i32, c_i32, c_void_p, c_i32, c_i32, c_void_p, c_void_p, c_void_p, c_int, c_void_p],
     "rl_shard_hybrid_fuse": [c_void_p, c_i32, c_i32, c_i32, c_i32, c_i32, c_void_p, c_i32, c_i32, c_void_p, c_void_p, c_void_p, c_int,
                              c_void_p],

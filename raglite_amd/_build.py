@@ -20,7 +20,7 @@ LIB_DIR = PKG / "_lib"
 LIB_PATH = LIB_DIR / "libraglite_hip.so"
 SOURCES = ["api.hip", "synth.hip", "pool_norm.hip", "scan.hip", "select.hip", "maxsim_stream.hip", "maxsim_generic.hip",
            "maxsim_gemm.hip", "maxsim_pp.hip", "score_gemm.hip", "mask.hip", "scan16.hip", "adapter_fit.hip", "query_targets.hip", "partition_sim.hip", "partition_dp.hip", "chunklet_dp.hip", "sentence_dp.hip", "comm.hip", "hi_filter.hip",
-           "keyword.hip", "keyword_build.hip", "fuse.hip", "rerank.hip", "spans.hip", "metadata.hip"]
+           "keyword.hip", "keyword_build.hip", "keyword_analyze.hip", "fuse.hip", "rerank.hip", "spans.hip", "metadata.hip"]
 # No -ffast-math: parity relies on IEEE fp32 divide / sqrt and on un-fused, un-reassociated sums.
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function",
          f"-I{INCLUDE}", f"-I{CSRC}"]

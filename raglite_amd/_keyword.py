@@ -165,6 +165,166 @@ def query_stems(text: str) -> list[str]:
     return sorted({stem(tok) for tok in tokenize(text)})
 
 
+# ---- the analyzer as a table and a rule: what the device runs (`raglite_amd/csrc/keyword_analyze.hip`) --------------
+# `tokenize` only ever compares tokens, so `normalize` can be applied per code point: a code point's image is a short sequence over
+# {a-z, separator, backslash, newline}.  Symbols: 0 .. 25 = a .. z, then
+SYM_SEPARATOR, SYM_BACKSLASH, SYM_NEWLINE = 26, 27, 28
+FOLD_IMAGE_MAX = 6  # symbols per image (U+33AF, `rad/s2`, has six once its separator runs are collapsed)
+FOLD_TABLE_SIZE = 0x110000
+
+
+def _image_symbols(cp: int) -> list[int]:
+    """The symbols of `normalize(chr(cp))`, a run of separators given as one."""
+    out: list[int] = []
+    for ch in normalize(chr(cp)):
+        if "a" <= ch <= "z":
+            out.append(ord(ch) - 97)
+        elif ch == "\\":
+            out.append(SYM_BACKSLASH)
+        elif ch == "\n":
+            out.append(SYM_NEWLINE)
+        elif not out or out[-1] != SYM_SEPARATOR:
+            out.append(SYM_SEPARATOR)
+    return out
+
+
+@functools.lru_cache(maxsize=1)
+def fold_table() -> np.ndarray:
+    """uint32 [0x110000]: the image of every code point under `normalize` (surrogates included: they are separators), built from
+    `normalize` itself so the two cannot drift.  Up to FOLD_IMAGE_MAX fields of 5 bits from bit 0, field = symbol + 1, 0 = no further
+    symbol; an empty image is 0.  What `rl_keyword_analyzer_create` takes."""
+    table = np.empty(FOLD_TABLE_SIZE, dtype=np.uint32)
+    for cp in range(FOLD_TABLE_SIZE):
+        symbols = _image_symbols(cp)
+        if len(symbols) > FOLD_IMAGE_MAX:
+            raise ValueError(f"U+{cp:04X} folds to {len(symbols)} symbols; the table holds {FOLD_IMAGE_MAX}")
+        entry = 0
+        for j, s in enumerate(symbols):
+            entry |= (s + 1) << (5 * j)
+        table[cp] = entry
+    table.setflags(write=False)
+    return table
+
+
+@functools.lru_cache(maxsize=1)
+def _fold_entries() -> list[int]:
+    return fold_table().tolist()
+
+
+def fold_symbols(text: str) -> list[int]:
+    """The folded stream of one text: the images of its code points, back to back (an empty image adds nothing)."""
+    entries = _fold_entries()
+    out: list[int] = []
+    for ch in text:
+        e = entries[ord(ch)]
+        while e:
+            out.append((e & 31) - 1)
+            e >>= 5
+    return out
+
+
+def tokenize_by_table(text: str) -> list[str]:
+    """`tokenize` restated without `unicodedata` or a regex, as the device runs it: fold through the table, then scan the symbols of the
+    text from the left.  A backslash that is not itself consumed consumes the next symbol unless that is a newline; a consumed letter
+    separates like anything else outside a-z.  So a symbol behind a run of r backslashes is consumed iff r is odd and it is no newline:
+    the backslashes pair up from the left.  Nothing carries over from another text."""
+    tokens: list[str] = []
+    cur: list[str] = []
+    run = 0  # backslashes directly in front of this symbol
+    for s in fold_symbols(text):
+        if s == SYM_BACKSLASH:
+            run += 1
+            letter = False
+        else:
+            letter = s < SYM_SEPARATOR and not (run & 1)  # (a newline is never consumed, and is no letter either way)
+            run = 0
+        if letter:
+            cur.append(chr(97 + s))
+        elif cur:
+            tokens.append("".join(cur))
+            cur = []
+    if cur:
+        tokens.append("".join(cur))
+    return tokens
+
+
+@functools.lru_cache(maxsize=1)
+def default_analyzer():
+    """The process-wide device analyzer over `fold_table()` and STOPWORDS (created on first use on the current device)."""
+    from raglite_amd import _ops
+
+    return _ops.KeywordAnalyzer(fold_table(), sorted(STOPWORDS))
+
+
+DEFAULT_MAX_CHARS_PER_CALL = 1 << 24  # code points per device call: about 0.6 GB of device scratch at 6 letters per token
+
+
+def analyze_texts_device(texts: Sequence[str | None], vocab: "Vocabulary", *, analyzer=None,
+                         max_chars_per_call: int = DEFAULT_MAX_CHARS_PER_CALL, timings: dict | None = None):
+    """Yields one `_ops.DeviceTermIds` per device call over consecutive runs of `texts` (None = a dead chunk: no tokens) of at most
+    `max_chars_per_call` code points each (a longer text goes alone), every new stem added to `vocab` in order of first appearance.
+    Each result is valid until the next one is asked for.  `timings`: seconds added up under encode / begin / vocabulary / finish, and the sizes of every call under calls."""
+    import time
+
+    if max_chars_per_call < 1:
+        raise ValueError("max_chars_per_call must be >= 1")
+    if analyzer is None:
+        analyzer = default_analyzer()
+    clock = time.perf_counter
+    at, n_texts = 0, len(texts)
+    while at < n_texts:
+        t0 = clock()
+        end, chars = at, 0
+        while end < n_texts:
+            size = len(texts[end]) if texts[end] is not None else 0
+            if end > at and chars + size > max_chars_per_call:
+                break
+            chars += size
+            end += 1
+        run = texts[at:end]
+        sizes = np.fromiter((len(t) if t is not None else 0 for t in run), dtype=np.int64, count=len(run))
+        text_off = np.concatenate(([0], np.cumsum(sizes))).astype(np.int64)
+        # (surrogatepass: a lone surrogate is a separator to `normalize`, and must not stop the encoder)
+        codepoints = np.frombuffer("".join(t for t in run if t is not None).encode("utf-32-le", "surrogatepass"), dtype=np.uint32)
+        t1 = clock()
+        _, stems, _ = analyzer.begin(codepoints, text_off)
+        t2 = clock()
+        ids = vocab.add(stems)
+        t3 = clock()
+        result = analyzer.finish(ids)
+        t4 = clock()
+        if timings is not None:
+            for key, dt in (("encode", t1 - t0), ("begin", t2 - t1), ("vocabulary", t3 - t2), ("finish", t4 - t3)):
+                timings[key] = timings.get(key, 0.0) + dt
+            timings.setdefault("calls", []).append(getattr(analyzer, "last_sizes", None))
+        yield result
+        at = end
+
+
+def analyze_texts_batch(texts: Sequence[str | None], vocab: "Vocabulary", *, analyzer=None,
+                        max_chars_per_call: int = DEFAULT_MAX_CHARS_PER_CALL, return_dead: bool = False, timings: dict | None = None):
+    """(flat int32 ids, int64 offsets) of many chunk bodies, analyzed on the device: what
+    `stems_to_store_ids([index_stems(t) for t in texts], vocab)` gives, with the same growth of `vocab` (None = a dead chunk: no
+    tokens; `return_dead` adds the ordinals of those as a third value).  A bulk load is split into calls of at most
+    `max_chars_per_call` code points; the vocabulary carries across them."""
+    import time
+
+    flats, offs, base = [], [np.zeros(1, dtype=np.int64)], 0
+    for result in analyze_texts_device(texts, vocab, analyzer=analyzer, max_chars_per_call=max_chars_per_call, timings=timings):
+        t0 = time.perf_counter()
+        flat, offsets = result.read()
+        if timings is not None:
+            timings["read"] = timings.get("read", 0.0) + time.perf_counter() - t0
+        flats.append(flat)
+        offs.append(offsets[1:] + base)
+        base += int(offsets[-1])
+    flat = np.concatenate(flats) if flats else np.zeros(0, dtype=np.int32)
+    offsets = np.concatenate(offs)
+    if return_dead:
+        return flat, offsets, np.asarray([i for i, t in enumerate(texts) if t is None], dtype=np.int64)
+    return flat, offsets
+
+
 # ---- postings and statistics --------------------------------------------------------------------------------------------------
 @dataclass
 class Postings:

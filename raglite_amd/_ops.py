@@ -1253,6 +1253,104 @@ class KeywordIndex:
         return scores, chunks, counts
 
 
+class DeviceTermIds:
+    """The result of one analyzer call, in device memory the analyzer owns: term ids int32 [n_tokens] and offsets int64 [n_chunks + 1].
+    It is valid until the analyzer's next `begin` (or its `close`); `KeywordStore.append` takes it, `read` copies it out."""
+
+    def __init__(self, analyzer: "KeywordAnalyzer", serial: int, p_ids: int, p_off: int, n_chunks: int, n_tokens: int) -> None:
+        self._analyzer, self._serial, self._p_ids, self._p_off = analyzer, serial, p_ids, p_off
+        self.n_chunks, self.n_tokens = n_chunks, n_tokens
+
+    def _check(self) -> None:
+        if self._analyzer._handle is None or self._analyzer._serial != self._serial:  # noqa: SLF001
+            raise ValueError("DeviceTermIds: the analyzer has moved on to another call (or was closed); this result is gone")
+
+    def pointers(self) -> tuple[int | None, int]:
+        self._check()
+        return self._p_ids or None, self._p_off
+
+    def read(self) -> tuple[np.ndarray, np.ndarray]:
+        """(flat int32 [n_tokens], offsets int64 [n_chunks + 1]) on the host."""
+        self._check()
+        flat = np.empty(self.n_tokens, dtype=np.int32)
+        offsets = np.empty(self.n_chunks + 1, dtype=np.int64)
+        check(lib().rl_keyword_analyze_result(self._analyzer._handle, flat.ctypes.data, offsets.ctypes.data, MEM_HOST, None))  # noqa: SLF001
+        return flat, offsets
+
+
+class KeywordAnalyzer:
+    """The BM25 index analyzer on the device (`rl_keyword_analyzer`): fold, tokenize, drop stopwords, Porter-stem and number the stems
+    of many chunk bodies in one call, with the results `raglite_amd._keyword.index_stems` + `stems_to_store_ids` give.
+    fold_table: uint32 [0x110000] (`_keyword.fold_table()`); stopwords: the words; hash_bits: 0, or the low bits of the stem hash to keep
+    (tests force collisions with it).  One call is `begin` (the distinct stems come back, in order of first appearance), the caller's
+    vocabulary step, then `finish` (one id per distinct stem goes in, the term ids stay on the device)."""
+
+    def __init__(self, fold_table, stopwords, hash_bits: int = 0) -> None:
+        _ensure_init(_current_device())
+        table = np.ascontiguousarray(fold_table, dtype=np.uint32)
+        words = [w.encode("utf-8") for w in stopwords]
+        blob = b"".join(words)
+        stop_off = np.concatenate(([0], np.cumsum([len(w) for w in words], dtype=np.int64))).astype(np.int64)
+        handle = C.c_void_p()
+        self._handle = None
+        check(lib().rl_keyword_analyzer_create(C.byref(handle), table.ctypes.data, int(table.size), blob, stop_off.ctypes.data, len(words),
+                                               int(hash_bits)))
+        self._handle = handle
+        self._serial = 0
+        self._counts = None
+
+    def close(self) -> None:
+        h, self._handle = getattr(self, "_handle", None), None
+        if h:
+            lib().rl_keyword_analyzer_destroy(h)
+
+    def __del__(self) -> None:  # noqa: D105
+        try:
+            self.close()
+        except Exception:  # noqa: BLE001,S110 - interpreter shutdown
+            pass
+
+    def begin(self, codepoints, text_off) -> tuple[int, list[str], np.ndarray]:
+        """Step one over codepoints uint32 [n] (UTF-32) and text_off int64 [n_texts + 1]: (n_tokens, the distinct stems in order of
+        first appearance, first_pos int64: the index of each stem's first token among the call's non-stopword tokens)."""
+        cp = np.ascontiguousarray(codepoints, dtype=np.uint32)
+        off = np.ascontiguousarray(text_off, dtype=np.int64)
+        if cp.ndim != 1 or off.ndim != 1 or off.size < 1:
+            raise ValueError("KeywordAnalyzer.begin: codepoints [n] and text_off [n_texts + 1] are required")
+        _ensure_init(_current_device())
+        counts = np.zeros(5, dtype=np.int64)
+        self._serial += 1
+        self._counts = None
+        check(lib().rl_keyword_analyze_begin(self._handle, cp.ctypes.data if cp.size else None, off.ctypes.data, int(cp.size), int(off.size - 1),
+                                             counts.ctypes.data, MEM_HOST, None))
+        n_tokens, n_distinct, n_bytes = int(counts[0]), int(counts[1]), int(counts[2])
+        blob = np.empty(n_bytes, dtype=np.uint8)
+        stem_off = np.zeros(n_distinct + 1, dtype=np.int64)
+        first_pos = np.empty(n_distinct, dtype=np.int64)
+        check(lib().rl_keyword_analyze_stems(self._handle, blob.ctypes.data if n_bytes else None, stem_off.ctypes.data,
+                                             first_pos.ctypes.data if n_distinct else None, MEM_HOST, None))
+        text = blob.tobytes().decode("ascii")
+        bounds = stem_off.tolist()
+        stems = [text[bounds[i] : bounds[i + 1]] for i in range(n_distinct)]
+        self._counts = (int(off.size - 1), n_tokens, n_distinct, int(counts[3]))
+        self.last_sizes = {"code_points": int(cp.size), "texts": int(off.size - 1), "symbols": int(counts[3]), "all_tokens": int(counts[4]),
+                           "tokens": n_tokens, "distinct": n_distinct, "stem_bytes": n_bytes}  # (of the last begin: what the benchmark sizes its bounds by)
+        return n_tokens, stems, first_pos
+
+    def finish(self, ids) -> DeviceTermIds:
+        """Step two: ids int32 [n_distinct], one per distinct stem of `begin` in its order -> the term ids and offsets on the device."""
+        if self._counts is None:
+            raise ValueError("KeywordAnalyzer.finish: no begin before it")
+        n_texts, n_tokens, n_distinct, _ = self._counts
+        ids = np.ascontiguousarray(ids, dtype=np.int32)
+        if ids.shape != (n_distinct,):
+            raise ValueError("KeywordAnalyzer.finish: one id per distinct stem is required")
+        p_ids, p_off = C.c_void_p(), C.c_void_p()
+        check(lib().rl_keyword_analyze_finish(self._handle, ids.ctypes.data if n_distinct else None, MEM_HOST, C.byref(p_ids), C.byref(p_off),
+                                              None))
+        return DeviceTermIds(self, self._serial, p_ids.value or 0, p_off.value or 0, n_texts, n_tokens)
+
+
 class KeywordStore:
     """Each chunk's term ids on the device (`rl_keyword_store`), beside the `DeviceIndex` whose chunk ordinals it follows: the BM25
     postings are built from it on the device (`count`, then `build`), so an insert or a delete uploads only what is new.  Term ids are
@@ -1280,8 +1378,20 @@ class KeywordStore:
         check(lib().rl_keyword_store_info(self._handle, *(C.byref(v) for v in vals)))
         return dict(zip(("n_chunks", "n_live", "n_tokens", "device_bytes"), (v.value for v in vals)))
 
-    def append(self, flat_ids, offsets) -> None:
-        """New chunks at the end: chunk i holds term ids flat_ids[offsets[i] : offsets[i + 1]] (any order, repeats = tf)."""
+    def append(self, flat_ids, offsets=None) -> None:
+        """New chunks at the end: chunk i holds term ids flat_ids[offsets[i] : offsets[i + 1]] (any order, repeats = tf).  A
+        `DeviceTermIds` (what `KeywordAnalyzer.finish` left on the device) is appended device to device, `offsets` then stays None."""
+        if isinstance(flat_ids, DeviceTermIds):
+            if offsets is not None:
+                raise ValueError("KeywordStore.append: a DeviceTermIds carries its own offsets")
+            p_ids, p_off = flat_ids.pointers()
+            _ensure_init(_current_device())
+            check(lib().rl_keyword_store_append(self._handle, p_ids, p_off, flat_ids.n_chunks, MEM_DEVICE, None))
+            if flat_ids.n_chunks:
+                self._counted = None
+            return
+        if offsets is None:
+            raise ValueError("KeywordStore.append: offsets are required with host term ids")
         offsets = np.ascontiguousarray(offsets, dtype=np.int64)
         flat = np.asarray(flat_ids)
         if flat.size and (flat.min() < 0 or flat.max() > np.iinfo(np.int32).max):

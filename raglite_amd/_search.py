@@ -62,6 +62,11 @@ class GpuIndex:
     keyword_build    "device" (the default): the chunks' term ids stay on the device (`KeywordStore`) and every rebuild of the postings
                      runs there; "host": the postings are rebuilt on the host and uploaded (the oracle of the device
                      build, and its A/B path).  Every result is the same either way.
+    keyword_analyzer "host" (the default): every chunk body is analyzed by `_keyword.index_stems` in Python; "device" (needs
+                     keyword_build="device"): the bodies of a build, an insert or a sync are folded, tokenized, Porter-stemmed and
+                     numbered on the device in one call per batch (`_keyword.analyze_texts_device`) and appended to
+                     the `KeywordStore` device to device; the index then keeps each chunk's int32 term ids on the host instead of
+                     its stems.  Queries are analyzed on the host either way, and every result is the same either way.
     metadata_filters "device" (the default): the chunks' metadata stays on the device as tag lists (`MetadataStore`) and every
                      `metadata_filter` is evaluated there, its bitset handed to the search without a trip through the host (DESIGN.md
                      4.13); "host": the filters are evaluated by a Python loop over `metadata` (the oracle of the device evaluation,
@@ -74,10 +79,11 @@ class GpuIndex:
     # keyword side (class defaults: an index without one): each chunk's index stems (None once deleted), the vocabulary and the device
     # postings built from them
     keyword: _ops.KeywordIndex | None = None
-    _kw_stems: list[list[str] | None] | None = None
+    _kw_stems: list | None = None  # per chunk: its stems, or (keyword_analyzer="device") its int32 term ids; None once deleted
     _kw_vocab: dict[str, int] = {}
     # keyword_build="device": the stable term ids (host) and the chunks' ids on the device; the postings are built from them there
     keyword_build: str = "device"
+    keyword_analyzer: str = "host"
     _kw_vocabulary: _keyword.Vocabulary | None = None
     _kw_store: _ops.KeywordStore | None = None
     _kw_built_ranks: np.ndarray | None = None  # `_kw_vocabulary.ranks()` as of the build of `keyword`
@@ -93,9 +99,14 @@ class GpuIndex:
                  metric: str = "cosine", query_adapter=None, docs: Sequence[str] | None = None,
                  metadata: Sequence[dict] | None = None, storage: str = "f32", exact_fp32: bool = False,
                  keyword_texts: Sequence[str] | None = None, positions: Sequence[tuple[str, int] | None] | None = None,
-                 keyword_build: str = "device", metadata_filters: str = "device") -> None:
+                 keyword_build: str = "device", metadata_filters: str = "device", keyword_analyzer: str = "host") -> None:
         if keyword_build not in ("device", "host"):
             raise ValueError('keyword_build must be "device" or "host"')
+        if keyword_analyzer not in ("device", "host"):
+            raise ValueError('keyword_analyzer must be "device" or "host"')
+        if keyword_analyzer == "device" and keyword_build != "device":
+            raise ValueError('keyword_analyzer="device" needs keyword_build="device": the term ids it makes stay on the device')
+        self.keyword_analyzer = keyword_analyzer
         if metadata_filters not in ("device", "host"):
             raise ValueError('metadata_filters must be "device" or "host"')
         self.keyword_build = keyword_build
@@ -124,10 +135,13 @@ class GpuIndex:
         if keyword_texts is not None:
             if len(keyword_texts) != len(self.chunk_ids):
                 raise ValueError("one keyword text per chunk is required")
-            self._kw_stems = [_keyword.index_stems(t) for t in keyword_texts]
-            if keyword_build == "device":
+            if keyword_analyzer == "device":
+                self._reset_keyword_store(list(keyword_texts))
+            elif keyword_build == "device":
+                self._kw_stems = [_keyword.index_stems(t) for t in keyword_texts]
                 self._reset_keyword_store()
             else:
+                self._kw_stems = [_keyword.index_stems(t) for t in keyword_texts]
                 self._rebuild_keywords()
         if positions is not None:
             if len(positions) != len(self.chunk_ids):
@@ -187,15 +201,43 @@ class GpuIndex:
             self.keyword.close()
         self.keyword, self._kw_vocab = new, {s: i for i, s in enumerate(vocab)}
 
-    def _reset_keyword_store(self) -> None:
+    @staticmethod
+    def _analyze_into_store(texts: Sequence[str | None], vocab: "_keyword.Vocabulary", store: "_ops.KeywordStore") -> list:
+        """keyword_analyzer="device": the bodies analyzed on the device and appended to `store` device to device; returns each chunk's
+        int32 term ids (a host copy: what `compact` uploads again), None for a dead chunk."""
+        first = store.info()["n_chunks"]
+        ids: list = []
+        for result in _keyword.analyze_texts_device(texts, vocab):
+            store.append(result)
+            flat, offsets = result.read()
+            ids.extend(np.split(flat, offsets[1:-1]))
+        dead = [i for i, t in enumerate(texts) if t is None]
+        for i in dead:
+            ids[i] = None
+        store.delete(np.asarray(dead, dtype=np.int64) + first)
+        return ids
+
+    def _reset_keyword_store(self, texts: list | None = None) -> None:
         """keyword_build="device": a fresh vocabulary and token store from `_kw_stems`, by one upload of every chunk's ids (the
-        constructor, and `compact` -- a rare operation, which renumbers the chunks), then the postings."""
-        vocab, store = _keyword.Vocabulary(), _ops.KeywordStore()
+        constructor, and `compact` -- a rare operation, which renumbers the chunks), then the postings.  keyword_analyzer="device":
+        the constructor hands in the bodies (`texts`) and they are analyzed on the device; `compact` uploads the kept chunks' ids
+        under the SAME vocabulary -- stable ids stay valid, and a stem that lived only in dropped chunks keeps its rank with df = 0."""
+        on_device = self.keyword_analyzer == "device"
+        vocab = self._kw_vocabulary if on_device and texts is None else _keyword.Vocabulary()
+        store = _ops.KeywordStore()
         old = (self._kw_vocabulary, self._kw_store, self._kw_built_ranks)
         try:
-            flat, offsets, dead = _keyword.stems_to_store_ids(self._kw_stems, vocab)
-            store.append(flat, offsets)
-            store.delete(dead)
+            if on_device and texts is not None:
+                self._kw_stems = self._analyze_into_store(texts, vocab, store)
+            elif on_device:
+                sizes = np.fromiter((0 if ids is None else len(ids) for ids in self._kw_stems), dtype=np.int64, count=len(self._kw_stems))
+                kept = [ids for ids in self._kw_stems if ids is not None and len(ids)]
+                store.append(np.concatenate(kept) if kept else np.zeros(0, dtype=np.int32), np.concatenate(([0], np.cumsum(sizes))))
+                store.delete(np.asarray([i for i, ids in enumerate(self._kw_stems) if ids is None], dtype=np.int64))
+            else:
+                flat, offsets, dead = _keyword.stems_to_store_ids(self._kw_stems, vocab)
+                store.append(flat, offsets)
+                store.delete(dead)
             self._kw_vocabulary, self._kw_store = vocab, store
             self._build_keywords_on_device()
         except Exception:
@@ -272,7 +314,10 @@ class GpuIndex:
                     self._meta_store.append(*self._meta_vocab.encode_chunks(metadata))
                 else:
                     self._reset_metadata_store()
-        if keyword_texts is not None:
+        if keyword_texts is not None and self.keyword_analyzer == "device":  # the new bodies are analyzed where their ids stay
+            self._kw_stems.extend(self._analyze_into_store(list(keyword_texts), self._kw_vocabulary, self._kw_store))
+            self._build_keywords_on_device()
+        elif keyword_texts is not None:
             stems = [_keyword.index_stems(t) for t in keyword_texts]
             self._kw_stems.extend(stems)
             if self._kw_store is not None:  # only the new chunks' ids go to the device
@@ -317,12 +362,13 @@ class GpuIndex:
     # -- the real store ----------------------------------------------------------------------
     @classmethod
     def from_store(cls, bind: Any, *, metric: str = "cosine", storage: str = "f32", exact_fp32: bool = False,
-                   keywords: bool = False, keyword_build: str = "device", metadata_filters: str = "device") -> "GpuIndex":
+                   keywords: bool = False, keyword_build: str = "device", metadata_filters: str = "device",
+                   keyword_analyzer: str = "host") -> "GpuIndex":
         """Build the device index from a RAGLite database: `chunk_embedding` rows ordered by (chunk_id, id)
         (`src/raglite/_database.py:403-430`), the chunks' `str(chunk)` text and metadata, and the stored query adapter
         (`:450-462`).  `bind`: SQLAlchemy Engine / Connection / Session or a database URL.  `metric` is the store's
         `vector_search_distance_metric` (`_config.py:69`).  `keywords`: also build the BM25 keyword side from `chunk.body`
-        (`keyword_build` as in the constructor).  `metadata_filters` as in the constructor.
+        (`keyword_build` and `keyword_analyzer` as in the constructor).  `metadata_filters` as in the constructor.
         The index remembers `bind` for `sync()`."""
         from raglite_amd import _store
 
@@ -338,7 +384,8 @@ class GpuIndex:
         off = np.concatenate(([0], np.cumsum(np.asarray(img.sizes, dtype=np.int64)))).astype(np.int64)
         gi = cls(img.chunk_ids, img.matrix(), chunk_offsets=off, metric=metric, query_adapter=adapter, docs=img.docs,
                  metadata=img.metadata, storage=storage, exact_fp32=exact_fp32, keyword_texts=img.bodies if keywords else None,
-                 positions=img.positions, keyword_build=keyword_build, metadata_filters=metadata_filters)
+                 positions=img.positions, keyword_build=keyword_build, metadata_filters=metadata_filters,
+                 keyword_analyzer=keyword_analyzer)
         gi._bind = bind  # noqa: SLF001
         return gi
 

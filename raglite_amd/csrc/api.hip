@@ -3762,6 +3762,269 @@ int rl_keyword_store_build(rl_keyword_store* st, const float* idf, const float* 
 
 }  // extern "C"
 
+// ---- keyword analyzer: chunk bodies -> stable term ids on the device (kernels in keyword_analyze.hip) ----------------------------------
+struct rl_keyword_analyzer {
+    std::mutex mu;
+    int hash_bits = 0;
+    int64_t n_table = 0;
+    int32_t n_stop = 0, stop_max_len = 0;
+    rl::DevArray<uint32_t> table;      // [n_table] the fold table
+    rl::DevArray<uint8_t> stop_bytes;  // the stopwords, sorted, as symbols 0 .. 25
+    rl::DevArray<int32_t> stop_off;    // [n_stop + 1]
+    // what the last rl_keyword_analyze_begin left (sizes 0 until then)
+    bool begun = false, finished = false;
+    int64_t n_texts = 0, m = 0, n_tok = 0, n_kept = 0, n_distinct = 0, n_bytes = 0, cap = 0;
+    // device arrays of a call, kept between calls with amortised capacity
+    rl::Pool count, scan_scratch, sym, start, letter, stem, head, ftext_off, tok_pos, tok_len, tok_hash, tok_slot, slots, kept, first, dist_tok,
+        dist_first, dist_len, dist_bytes, term_ids, offsets;
+};
+
+namespace rl {
+namespace {
+
+// the exclusive scan of data [n] in place and its total, copied to *total_host (valid after the next synchronisation of `s`)
+int ka_scan(rl_keyword_analyzer* a, int64_t* data, int64_t n, int64_t* total_host, hipStream_t s, const char* who) {
+    RL_TRY(reserve_amortised(a->scan_scratch, kb_scan_scratch_items(n) * sizeof(int64_t), who));
+    const int64_t* total = nullptr;
+    RL_TRY(launch_kb_exclusive_scan(data, n, a->scan_scratch.as<int64_t>(), &total, s));
+    RL_TRY(hip_status(hipMemcpyAsync(total_host, total, sizeof(int64_t), hipMemcpyDeviceToHost, s), who));
+    return RL_OK;
+}
+
+}  // namespace
+}  // namespace rl
+
+extern "C" {
+
+int rl_keyword_analyzer_create(rl_keyword_analyzer** out, const uint32_t* fold_table, int64_t n_table, const char* stopwords,
+                               const int64_t* stop_off, int32_t n_stop, int32_t hash_bits) {
+    const char* who = "rl_keyword_analyzer_create";
+    if (!out) return fail(RL_ERR_INVALID, std::string(who) + ": null output handle");
+    *out = nullptr;
+    if (!fold_table || n_table < 1 || n_table > (int64_t(1) << 21)) return fail(RL_ERR_INVALID, std::string(who) + ": bad fold table");
+    if (n_stop < 0 || (n_stop > 0 && (!stopwords || !stop_off))) return fail(RL_ERR_INVALID, std::string(who) + ": bad stopword list");
+    if (hash_bits < 0 || hash_bits > 64) return fail(RL_ERR_INVALID, std::string(who) + ": hash_bits must be 0 .. 64");
+    for (int64_t i = 0; i < n_table; ++i) {  // every field a symbol + 1 (<= 29), no symbol behind an empty field, nothing above the fields
+        uint32_t e = fold_table[i];
+        bool ended = false;
+        for (int j = 0; j < KA_IMAGE_MAX; ++j, e >>= 5) {
+            const uint32_t f = e & 31u;
+            if (f > 29u || (ended && f)) return fail(RL_ERR_INVALID, std::string(who) + ": malformed fold table entry");
+            ended |= f == 0;
+        }
+        if (e) return fail(RL_ERR_INVALID, std::string(who) + ": malformed fold table entry");
+    }
+    // the words that a token can equal (a-z only, non-empty), sorted and distinct, as symbols
+    std::vector<std::string> words;
+    for (int32_t i = 0; i < n_stop; ++i) {
+        if (stop_off[i] < 0 || stop_off[i + 1] < stop_off[i]) return fail(RL_ERR_INVALID, std::string(who) + ": stopword offsets must ascend from 0");
+        std::string w(stopwords + stop_off[i], (size_t)(stop_off[i + 1] - stop_off[i]));
+        bool ok = !w.empty();
+        for (char& c : w) {
+            ok = ok && c >= 'a' && c <= 'z';
+            c = (char)(c - 'a');
+        }
+        if (ok) words.push_back(std::move(w));
+    }
+    std::sort(words.begin(), words.end());
+    words.erase(std::unique(words.begin(), words.end()), words.end());
+    std::vector<int32_t> h_off(words.size() + 1, 0);
+    std::string h_bytes;
+    size_t longest = 0;
+    for (size_t i = 0; i < words.size(); ++i) {
+        h_bytes += words[i];
+        h_off[i + 1] = (int32_t)h_bytes.size();
+        longest = std::max(longest, words[i].size());
+    }
+    std::unique_ptr<rl_keyword_analyzer> a(new rl_keyword_analyzer());
+    a->hash_bits = hash_bits == 64 ? 0 : hash_bits;
+    a->n_table = n_table;
+    a->n_stop = (int32_t)words.size();
+    a->stop_max_len = (int32_t)longest;
+    RL_TRY(a->table.alloc((size_t)n_table * sizeof(uint32_t), who));
+    RL_TRY(a->stop_bytes.alloc(std::max<size_t>(h_bytes.size(), 16), who));
+    RL_TRY(a->stop_off.alloc(h_off.size() * sizeof(int32_t), who));
+    RL_TRY(hip_status(hipMemcpy(a->table.p, fold_table, (size_t)n_table * sizeof(uint32_t), hipMemcpyHostToDevice), who));
+    if (!h_bytes.empty()) RL_TRY(hip_status(hipMemcpy(a->stop_bytes.p, h_bytes.data(), h_bytes.size(), hipMemcpyHostToDevice), who));
+    RL_TRY(hip_status(hipMemcpy(a->stop_off.p, h_off.data(), h_off.size() * sizeof(int32_t), hipMemcpyHostToDevice), who));
+    *out = a.release();
+    return RL_OK;
+}
+
+int rl_keyword_analyzer_destroy(rl_keyword_analyzer* a) {
+    if (!a) return RL_OK;
+    delete a;
+    return RL_OK;
+}
+
+int rl_keyword_analyze_begin(rl_keyword_analyzer* a, const uint32_t* codepoints, const int64_t* text_off, int64_t n, int64_t n_texts,
+                             int64_t out_counts[5], int mem, void* stream) {
+    const char* who = "rl_keyword_analyze_begin";
+    if (!a) return fail(RL_ERR_INVALID, std::string(who) + ": null analyzer");
+    if (n < 0 || n_texts < 0) return fail(RL_ERR_INVALID, std::string(who) + ": negative size");
+    if (mem != RL_MEM_HOST && mem != RL_MEM_DEVICE) return fail(RL_ERR_INVALID, std::string(who) + ": bad mem");
+    if (!text_off) return fail(RL_ERR_INVALID, std::string(who) + ": null text_off");
+    if (n > 0 && !codepoints) return fail(RL_ERR_INVALID, std::string(who) + ": null codepoints");
+    if (n > 0 && n_texts < 1) return fail(RL_ERR_INVALID, std::string(who) + ": code points without a text");
+    if (n >= (int64_t(1) << 40)) return fail(RL_ERR_UNSUPPORTED, std::string(who) + ": more than 2^40 code points in one call");
+    if (mem == RL_MEM_HOST) {
+        if (text_off[0] != 0) return fail(RL_ERR_INVALID, std::string(who) + ": text_off must start at 0");
+        for (int64_t t = 0; t < n_texts; ++t)
+            if (text_off[t + 1] < text_off[t]) return fail(RL_ERR_INVALID, std::string(who) + ": text_off must be ascending");
+        if (text_off[n_texts] != n) return fail(RL_ERR_INVALID, std::string(who) + ": text_off must end at n");
+    }
+    hipStream_t s = as_stream(stream);
+    std::lock_guard<std::mutex> lock(a->mu);
+    a->begun = a->finished = false;
+    a->n_texts = n_texts;
+    a->m = a->n_tok = a->n_kept = a->n_distinct = a->n_bytes = a->cap = 0;
+    DevBuf t_cp, t_off;
+    const uint32_t* d_cp;
+    const int64_t* d_off;
+    RL_TRY(stage_in(codepoints, (size_t)n, mem, s, t_cp, &d_cp));
+    RL_TRY(stage_in(text_off, (size_t)n_texts + 1, mem, s, t_off, &d_off));
+    // 1. fold
+    RL_TRY(reserve_amortised(a->count, (size_t)(n + 1) * sizeof(int64_t), who));
+    RL_TRY(launch_ka_fold_count(d_cp, n, a->table, a->n_table, a->count.as<int64_t>(), s));
+    int64_t m = 0, n_tok = 0, n_kept = 0, n_distinct = 0, n_bytes = 0;
+    RL_TRY(ka_scan(a, a->count.as<int64_t>(), n + 1, &m, s, who));
+    RL_TRY(hip_status(hipStreamSynchronize(s), who));
+    const int64_t* sym_off = a->count.as<int64_t>();
+    const size_t m_bytes = std::max<size_t>((size_t)m, 16);
+    RL_TRY(reserve_amortised(a->sym, m_bytes, who));
+    RL_TRY(reserve_amortised(a->start, m_bytes, who));
+    RL_TRY(reserve_amortised(a->letter, m_bytes, who));
+    RL_TRY(reserve_amortised(a->stem, m_bytes, who));
+    RL_TRY(reserve_amortised(a->head, (size_t)(m + 1) * sizeof(int64_t), who));
+    RL_TRY(reserve_amortised(a->ftext_off, (size_t)(n_texts + 1) * sizeof(int64_t), who));
+    RL_TRY(hip_status(hipMemsetAsync(a->start.p, 0, m_bytes, s), who));
+    RL_TRY(launch_ka_fold_write(d_cp, n, a->table, a->n_table, sym_off, m, a->sym.as<uint8_t>(), s));
+    RL_TRY(launch_ka_text_starts(d_off, n_texts, n, sym_off, m, a->ftext_off.as<int64_t>(), a->start.as<uint8_t>(), s));
+    // 2. tokenize
+    RL_TRY(launch_ka_heads(a->sym.as<uint8_t>(), a->start.as<uint8_t>(), m, a->letter.as<uint8_t>(), a->head.as<int64_t>(), s));
+    RL_TRY(ka_scan(a, a->head.as<int64_t>(), m + 1, &n_tok, s, who));
+    RL_TRY(hip_status(hipStreamSynchronize(s), who));
+    if (n_tok > 0) {
+        // 3. stem
+        const int64_t cap = ka_table_slots(n_tok);
+        RL_TRY(reserve_amortised(a->tok_pos, (size_t)n_tok * sizeof(int64_t), who));
+        RL_TRY(reserve_amortised(a->tok_len, (size_t)n_tok * sizeof(int64_t), who));
+        RL_TRY(reserve_amortised(a->tok_hash, (size_t)n_tok * sizeof(uint64_t), who));
+        RL_TRY(reserve_amortised(a->tok_slot, (size_t)n_tok * sizeof(int64_t), who));
+        RL_TRY(reserve_amortised(a->kept, (size_t)(n_tok + 1) * sizeof(int64_t), who));
+        RL_TRY(reserve_amortised(a->first, (size_t)(n_tok + 1) * sizeof(int64_t), who));
+        RL_TRY(reserve_amortised(a->slots, (size_t)cap * sizeof(uint64_t), who));
+        RL_TRY(launch_ka_stem(a->sym.as<uint8_t>(), a->letter.as<uint8_t>(), a->start.as<uint8_t>(), a->head.as<int64_t>(), m, n_tok, a->stop_bytes,
+                              a->stop_off, a->n_stop, a->stop_max_len, a->hash_bits, a->tok_pos.as<int64_t>(), a->stem.as<uint8_t>(),
+                              a->tok_len.as<int64_t>(), a->tok_hash.as<uint64_t>(), s));
+        // 4. distinct
+        RL_TRY(launch_ka_distinct(a->stem.as<uint8_t>(), a->tok_pos.as<int64_t>(), a->tok_len.as<int64_t>(), a->tok_hash.as<uint64_t>(), n_tok,
+                                  a->slots.as<uint64_t>(), cap, a->tok_slot.as<int64_t>(), a->kept.as<int64_t>(), a->first.as<int64_t>(), s));
+        RL_TRY(ka_scan(a, a->kept.as<int64_t>(), n_tok + 1, &n_kept, s, who));
+        RL_TRY(ka_scan(a, a->first.as<int64_t>(), n_tok + 1, &n_distinct, s, who));
+        RL_TRY(hip_status(hipStreamSynchronize(s), who));
+        RL_TRY(reserve_amortised(a->dist_tok, std::max<size_t>((size_t)n_distinct * sizeof(int64_t), 16), who));
+        RL_TRY(reserve_amortised(a->dist_first, std::max<size_t>((size_t)n_distinct * sizeof(int64_t), 16), who));
+        RL_TRY(reserve_amortised(a->dist_len, (size_t)(n_distinct + 1) * sizeof(int64_t), who));
+        RL_TRY(launch_ka_distinct_out(a->tok_len.as<int64_t>(), a->tok_slot.as<int64_t>(), a->slots.as<uint64_t>(), cap, n_tok, a->kept.as<int64_t>(),
+                                      a->first.as<int64_t>(), n_distinct, a->dist_tok.as<int64_t>(), a->dist_first.as<int64_t>(),
+                                      a->dist_len.as<int64_t>(), s));
+        RL_TRY(ka_scan(a, a->dist_len.as<int64_t>(), n_distinct + 1, &n_bytes, s, who));
+        RL_TRY(hip_status(hipStreamSynchronize(s), who));
+        RL_TRY(reserve_amortised(a->dist_bytes, std::max<size_t>((size_t)n_bytes, 16), who));
+        RL_TRY(launch_ka_distinct_bytes(a->stem.as<uint8_t>(), a->tok_pos.as<int64_t>(), a->tok_len.as<int64_t>(), a->dist_tok.as<int64_t>(),
+                                        a->dist_len.as<int64_t>(), n_distinct, n_bytes, a->dist_bytes.as<uint8_t>(), s));
+        RL_TRY(hip_status(hipStreamSynchronize(s), who));
+        a->cap = cap;
+    }
+    g_pinned.drain();
+    a->m = m;
+    a->n_tok = n_tok;
+    a->n_kept = n_kept;
+    a->n_distinct = n_distinct;
+    a->n_bytes = n_bytes;
+    a->begun = true;
+    if (out_counts) {
+        out_counts[0] = n_kept;
+        out_counts[1] = n_distinct;
+        out_counts[2] = n_bytes;
+        out_counts[3] = m;
+        out_counts[4] = n_tok;
+    }
+    return RL_OK;
+}
+
+int rl_keyword_analyze_stems(rl_keyword_analyzer* a, uint8_t* stem_bytes, int64_t* stem_off, int64_t* first_pos, int mem, void* stream) {
+    const char* who = "rl_keyword_analyze_stems";
+    if (!a) return fail(RL_ERR_INVALID, std::string(who) + ": null analyzer");
+    if (mem != RL_MEM_HOST && mem != RL_MEM_DEVICE) return fail(RL_ERR_INVALID, std::string(who) + ": bad mem");
+    hipStream_t s = as_stream(stream);
+    std::lock_guard<std::mutex> lock(a->mu);
+    if (!a->begun) return fail(RL_ERR_INVALID, std::string(who) + ": no rl_keyword_analyze_begin before it");
+    const hipMemcpyKind kind = mem == RL_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
+    const size_t nd = (size_t)a->n_distinct;
+    if (a->n_tok == 0) {  // (no token: the device arrays were not written)
+        if (stem_off && mem == RL_MEM_HOST) stem_off[0] = 0;
+        else if (stem_off) RL_TRY(hip_status(hipMemsetAsync(stem_off, 0, sizeof(int64_t), s), who));
+    } else {
+        if (stem_bytes && a->n_bytes) RL_TRY(hip_status(hipMemcpyAsync(stem_bytes, a->dist_bytes.p, (size_t)a->n_bytes, kind, s), who));
+        if (stem_off) RL_TRY(hip_status(hipMemcpyAsync(stem_off, a->dist_len.p, (nd + 1) * sizeof(int64_t), kind, s), who));
+        if (first_pos && nd) RL_TRY(hip_status(hipMemcpyAsync(first_pos, a->dist_first.p, nd * sizeof(int64_t), kind, s), who));
+    }
+    RL_TRY(hip_status(hipStreamSynchronize(s), who));
+    return RL_OK;
+}
+
+int rl_keyword_analyze_finish(rl_keyword_analyzer* a, const int32_t* ids, int mem, const int32_t** term_ids, const int64_t** offsets, void* stream) {
+    const char* who = "rl_keyword_analyze_finish";
+    if (!a) return fail(RL_ERR_INVALID, std::string(who) + ": null analyzer");
+    if (mem != RL_MEM_HOST && mem != RL_MEM_DEVICE) return fail(RL_ERR_INVALID, std::string(who) + ": bad mem");
+    hipStream_t s = as_stream(stream);
+    std::lock_guard<std::mutex> lock(a->mu);
+    if (!a->begun) return fail(RL_ERR_INVALID, std::string(who) + ": no rl_keyword_analyze_begin before it");
+    if (a->n_distinct > 0 && !ids) return fail(RL_ERR_INVALID, std::string(who) + ": null ids");
+    if (mem == RL_MEM_HOST)
+        for (int64_t d = 0; d < a->n_distinct; ++d)
+            if (ids[d] < 0) return fail(RL_ERR_INVALID, std::string(who) + ": negative term id");
+    a->finished = false;
+    RL_TRY(reserve_amortised(a->term_ids, std::max<size_t>((size_t)a->n_kept * sizeof(int32_t), 16), who));
+    RL_TRY(reserve_amortised(a->offsets, (size_t)(a->n_texts + 1) * sizeof(int64_t), who));
+    DevBuf t_ids;
+    const int32_t* d_ids;
+    RL_TRY(stage_in(ids, (size_t)a->n_distinct, mem, s, t_ids, &d_ids));
+    if (a->n_tok > 0) {
+        // 5. emit
+        RL_TRY(launch_ka_emit(a->tok_len.as<int64_t>(), a->tok_slot.as<int64_t>(), a->slots.as<uint64_t>(), a->cap, a->n_tok, a->kept.as<int64_t>(),
+                              a->first.as<int64_t>(), d_ids, a->n_distinct, a->n_kept, a->term_ids.as<int32_t>(), s));
+        RL_TRY(launch_ka_offsets(a->ftext_off.as<int64_t>(), a->n_texts, a->head.as<int64_t>(), a->m, a->kept.as<int64_t>(), a->n_tok,
+                                 a->offsets.as<int64_t>(), s));
+    } else {
+        RL_TRY(hip_status(hipMemsetAsync(a->offsets.p, 0, (size_t)(a->n_texts + 1) * sizeof(int64_t), s), who));
+    }
+    RL_TRY(hip_status(hipStreamSynchronize(s), who));  // the staging buffer and the caller's ids may go away after return
+    g_pinned.drain();
+    a->finished = true;
+    if (term_ids) *term_ids = a->term_ids.as<int32_t>();
+    if (offsets) *offsets = a->offsets.as<int64_t>();
+    return RL_OK;
+}
+
+int rl_keyword_analyze_result(rl_keyword_analyzer* a, int32_t* term_ids, int64_t* offsets, int mem, void* stream) {
+    const char* who = "rl_keyword_analyze_result";
+    if (!a) return fail(RL_ERR_INVALID, std::string(who) + ": null analyzer");
+    if (mem != RL_MEM_HOST && mem != RL_MEM_DEVICE) return fail(RL_ERR_INVALID, std::string(who) + ": bad mem");
+    hipStream_t s = as_stream(stream);
+    std::lock_guard<std::mutex> lock(a->mu);
+    if (!a->finished) return fail(RL_ERR_INVALID, std::string(who) + ": no rl_keyword_analyze_finish before it");
+    const hipMemcpyKind kind = mem == RL_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
+    if (term_ids && a->n_kept) RL_TRY(hip_status(hipMemcpyAsync(term_ids, a->term_ids.p, (size_t)a->n_kept * sizeof(int32_t), kind, s), who));
+    if (offsets) RL_TRY(hip_status(hipMemcpyAsync(offsets, a->offsets.p, (size_t)(a->n_texts + 1) * sizeof(int64_t), kind, s), who));
+    RL_TRY(hip_status(hipStreamSynchronize(s), who));
+    return RL_OK;
+}
+
+}  // extern "C"
+
 namespace {
 // rl_keyword_search and rl_keyword_search_per_query: one device path
 int keyword_search_call(rl_keyword_index* kw, const int64_t* q_off, const int32_t* q_terms, int32_t n_queries, int32_t k,

@@ -374,6 +374,37 @@ int launch_kb_rle_write(const uint32_t* keys, const int32_t* vals, int64_t m, co
 int launch_kb_term_off(const int32_t* post_term, int64_t n_postings, int32_t n_terms, int64_t* term_off /* [n_terms + 1] */,
                        int64_t* df /* [n_terms] or null */, hipStream_t s);
 
+// keyword_analyze.hip: chunk bodies -> stable term ids (rl_keyword_analyze_begin / _finish drive these in this order; the scans
+// between them are launch_kb_exclusive_scan's).  cp [n] UTF-32; table [n_table]: a code point's image, KA_IMAGE_MAX fields of 5 bits
+// (symbol + 1; 0 ends it); symbols: 0 .. 25 = a .. z, 26 separator, 27 backslash, 28 newline.
+constexpr int KA_IMAGE_MAX = 6;
+int launch_ka_fold_count(const uint32_t* cp, int64_t n, const uint32_t* table, int64_t n_table, int64_t* count /* [n + 1] */, hipStream_t s);
+int launch_ka_fold_write(const uint32_t* cp, int64_t n, const uint32_t* table, int64_t n_table, const int64_t* sym_off, int64_t m, uint8_t* sym,
+                         hipStream_t s);
+// ftext_off [n_texts + 1]: the texts' offsets in the folded stream; start [m] (zero on entry): 1 where a text begins
+int launch_ka_text_starts(const int64_t* text_off, int64_t n_texts, int64_t n, const int64_t* sym_off, int64_t m, int64_t* ftext_off, uint8_t* start,
+                          hipStream_t s);
+// letter [m]: 1 = a letter no backslash consumes; head [m + 1]: 1 where a token begins (to be scanned: tok_idx)
+int launch_ka_heads(const uint8_t* sym, const uint8_t* start, int64_t m, uint8_t* letter, int64_t* head, hipStream_t s);
+// per token: tok_pos, tok_len (-1: a stopword, else its stem's length), the stem's letters at stem[tok_pos ..], tok_hash (hash_bits > 0:
+// only that many low bits)
+int launch_ka_stem(const uint8_t* sym, const uint8_t* letter, const uint8_t* start, const int64_t* tok_idx, int64_t m, int64_t n_tok,
+                   const uint8_t* stop_bytes, const int32_t* stop_off, int32_t n_stop, int32_t stop_max_len, int hash_bits, int64_t* tok_pos,
+                   uint8_t* stem, int64_t* tok_len, uint64_t* tok_hash, hipStream_t s);
+int64_t ka_table_slots(int64_t n_tok);  // slots of the distinct table: a power of two >= 2 n_tok
+// slots [cap]: set here; tok_slot [n_tok]; kept / first [n_tok + 1]: the flags to be scanned (kept_scan, rank)
+int launch_ka_distinct(const uint8_t* stem, const int64_t* tok_pos, const int64_t* tok_len, const uint64_t* tok_hash, int64_t n_tok, uint64_t* slots,
+                       int64_t cap, int64_t* tok_slot, int64_t* kept, int64_t* first, hipStream_t s);
+int launch_ka_distinct_out(const int64_t* tok_len, const int64_t* tok_slot, const uint64_t* slots, int64_t cap, int64_t n_tok, const int64_t* kept_scan,
+                           const int64_t* rank, int64_t n_distinct, int64_t* dist_tok, int64_t* dist_first, int64_t* dist_len /* [n_distinct + 1] */,
+                           hipStream_t s);
+int launch_ka_distinct_bytes(const uint8_t* stem, const int64_t* tok_pos, const int64_t* tok_len, const int64_t* dist_tok, const int64_t* dist_off,
+                             int64_t n_distinct, int64_t n_bytes, uint8_t* bytes, hipStream_t s);
+int launch_ka_emit(const int64_t* tok_len, const int64_t* tok_slot, const uint64_t* slots, int64_t cap, int64_t n_tok, const int64_t* kept_scan,
+                   const int64_t* rank, const int32_t* ids, int64_t n_distinct, int64_t n_kept, int32_t* term_ids, hipStream_t s);
+int launch_ka_offsets(const int64_t* ftext_off, int64_t n_texts, const int64_t* tok_idx, int64_t m, const int64_t* kept_scan, int64_t n_tok,
+                      int64_t* offsets /* [n_texts + 1] */, hipStream_t s);
+
 // fuse.hip: weighted Reciprocal Rank Fusion of n_lists ranked lists per query (lists [n_lists x n_queries x len] int32, < 0 = padding)
 // -> the top k by (float64 score desc, first occurrence asc), bit for bit the reference's reciprocal_rank_fusion
 constexpr int32_t RRF_MAX_LISTS = 4;
