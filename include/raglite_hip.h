@@ -829,7 +829,8 @@ int rl_query_targets(rl_index* index, const float* queries, int32_t n_queries, c
  * stay on the host: rl_partition_chunks below solves the reference's integer programme exactly on
  * the device, and rl_split_chunks chains the two without a repack.
  *   X            [n x dim] f32 chunklet embeddings of all documents, concatenated (nonzero rows)
- *   doc_offsets  int64[n_docs + 1] CSR over those rows (same side as X); NULL = one document
+ *   doc_offsets  int64[n_docs + 1] CSR over those rows (same side as X; starts at 0, ascends, ends at n:
+ *                RL_ERR_INVALID for RL_MEM_HOST offsets that do not); NULL = one document
  *   nonoutlying  uint8[n], nonzero = chunklet size within the document's 15 %..85 % quantiles
  *                (:57-58, computed on the host from string lengths); NULL = no discourse removal
  *   out          f32[n]: out[i] = max((x_i . x_{i+1} + 1) / 2, sqrt(eps)) on the normalised,

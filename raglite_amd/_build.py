@@ -52,7 +52,7 @@ def build(force: bool = False, verbose: bool = False, experiments: bool = False)
     obj_dir.mkdir(exist_ok=True)
     lib_path = EXP_LIB_PATH if experiments else LIB_PATH
     flags = FLAGS + (["-DRAGLITE_EXPERIMENTS"] if experiments else [])
-    headers = [CSRC / "common.h", CSRC / "pp_schedule.h", INCLUDE / "raglite_hip.h"]
+    headers = [*sorted(CSRC.glob("*.h")), INCLUDE / "raglite_hip.h"]  # every object depends on every header: none can go stale
     hipcc = _hipcc()
 
     def compile_one(src: str) -> Path:

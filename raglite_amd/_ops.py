@@ -1453,6 +1453,22 @@ def _same_side(a: _Args, x: Any, dtype: np.dtype) -> int:
     return a.inp(x, dtype)
 
 
+def _partition_outputs(a: _Args, n: int, n_docs: int, want_objective: bool = True) -> tuple[tuple[Any, Any, Any], tuple | None]:
+    """The outputs of a document-batched partition call on the side of `a`: (cut uint8[n], objective float64[n_docs] or None, status
+    int32[n_docs]) and their pointers.  The pointers are None when n == 0: the call would write nothing (every document is empty and
+    has no cut), so the outputs are filled here and the caller returns them as they are."""
+    cut, p_cut = a.out((n,), np.uint8)
+    obj, p_obj = a.out((max(n_docs, 0),), np.float64) if want_objective else (None, None)
+    status, p_status = a.out((max(n_docs, 0),), np.int32)
+    if n == 0 and n_docs >= 0:
+        if obj is not None:
+            obj[...] = 0.0
+        status[...] = 0
+        return (cut, obj, status), None
+    a.ensure_device()
+    return (cut, obj, status), (p_cut, p_obj, p_status)
+
+
 def partition_chunks(cost: Any, sizes: Any, doc_offsets: Any, max_size: int) -> tuple[Any, Any, Any]:
     """`rl_partition_chunks`: the optimal cuts of many documents in one call.  cost float32[n] (the layout `rl_partition_similarity`
     writes), sizes int64[n], doc_offsets int64[n_docs + 1] -> (cut uint8[n], objective float64[n_docs], status int32[n_docs]) on the
@@ -1465,16 +1481,10 @@ def partition_chunks(cost: Any, sizes: Any, doc_offsets: Any, max_size: int) -> 
     n_docs = int(a.keep[-1].shape[0]) - 1
     if int(a.keep[-2].shape[0]) != n:
         raise ValueError("partition_chunks: cost and sizes differ in length")
-    cut, p_cut = a.out((n,), np.uint8)
-    obj, p_obj = a.out((max(n_docs, 0),), np.float64)
-    status, p_status = a.out((max(n_docs, 0),), np.int32)
-    if n == 0 and n_docs >= 0:  # the call writes nothing: no document has a cut
-        obj[...] = 0.0
-        status[...] = 0
-        return cut, obj, status
-    a.ensure_device()
-    check(lib().rl_partition_chunks(p_cost, p_sizes, p_off, n, n_docs, int(max_size), p_cut, p_obj, p_status, a.mem, a.stream))
-    return cut, obj, status
+    out, ptrs = _partition_outputs(a, n, n_docs)
+    if ptrs is not None:
+        check(lib().rl_partition_chunks(p_cost, p_sizes, p_off, n, n_docs, int(max_size), *ptrs, a.mem, a.stream))
+    return out
 
 
 def partition_chunklets(boundary: Any, statements: Any, lengths: Any, doc_offsets: Any, max_size: int,
@@ -1491,17 +1501,10 @@ def partition_chunklets(boundary: Any, statements: Any, lengths: Any, doc_offset
         raise ValueError("partition_chunklets: boundary, statements and lengths differ in length")
     p_off = _same_side(a, doc_offsets, np.int64)
     n_docs = int(a.keep[-1].shape[0]) - 1
-    cut, p_cut = a.out((n,), np.uint8)
-    obj, p_obj = a.out((max(n_docs, 0),), np.float64) if want_objective else (None, None)
-    status, p_status = a.out((max(n_docs, 0),), np.int32)
-    if n == 0 and n_docs >= 0:  # the call writes nothing: every document is empty
-        if obj is not None:
-            obj[...] = 0.0
-        status[...] = 0
-        return cut, obj, status
-    a.ensure_device()
-    check(lib().rl_partition_chunklets(p_b, p_s, p_len, p_off, n, n_docs, int(max_size), p_cut, p_obj, p_status, a.mem, a.stream))
-    return cut, obj, status
+    out, ptrs = _partition_outputs(a, n, n_docs, want_objective)
+    if ptrs is not None:
+        check(lib().rl_partition_chunklets(p_b, p_s, p_len, p_off, n, n_docs, int(max_size), *ptrs, a.mem, a.stream))
+    return out
 
 
 def partition_sentences(codepoints: Any, probas: Any, doc_offsets: Any, min_len: int = 4, max_len: int | None = None,
@@ -1531,18 +1534,11 @@ def partition_sentences(codepoints: Any, probas: Any, doc_offsets: Any, min_len:
         raise ValueError("partition_sentences: codepoints, probas and known differ in length")
     p_off = _same_side(a, doc_offsets, np.int64)
     n_docs = int(a.keep[-1].shape[0]) - 1
-    cut, p_cut = a.out((n,), np.uint8)
-    obj, p_obj = a.out((max(n_docs, 0),), np.float64) if want_objective else (None, None)
-    status, p_status = a.out((max(n_docs, 0),), np.int32)
-    if n == 0 and n_docs >= 0:  # the call writes nothing: every document is empty
-        if obj is not None:
-            obj[...] = 0.0
-        status[...] = 0
-        return cut, obj, status
-    a.ensure_device()
-    check(lib().rl_partition_sentences(p_cp, p_p, int(f64), p_known, p_off, n, n_docs, int(min_len), int(max_len or 0), p_cut, p_obj,
-                                       p_status, a.mem, a.stream))
-    return cut, obj, status
+    out, ptrs = _partition_outputs(a, n, n_docs, want_objective)
+    if ptrs is not None:
+        check(lib().rl_partition_sentences(p_cp, p_p, int(f64), p_known, p_off, n, n_docs, int(min_len), int(max_len or 0), *ptrs,
+                                           a.mem, a.stream))
+    return out
 
 
 def split_chunks_call(embeddings: Any, doc_offsets: Any, nonoutlying: Any, is_heading: Any, sizes: Any, max_size: int,
@@ -1562,15 +1558,9 @@ def split_chunks_call(embeddings: Any, doc_offsets: Any, nonoutlying: Any, is_he
     p_sizes = _same_side(a, sizes, np.int64)
     if int(a.keep[-1].shape[0]) != n or any(v is not None and len(v) != n for v in (nonoutlying, is_heading)):
         raise ValueError("split_chunks_call: sizes / flags do not match the embedding rows")
-    cut, p_cut = a.out((n,), np.uint8)
     cost, p_cost = a.out((n,), np.float32) if want_cost else (None, None)
-    obj, p_obj = a.out((max(n_docs, 0),), np.float64)
-    status, p_status = a.out((max(n_docs, 0),), np.int32)
-    if n == 0 and n_docs >= 0:
-        obj[...] = 0.0
-        status[...] = 0
-        return cut, cost, obj, status
-    a.ensure_device()
-    check(lib().rl_split_chunks(p_x, n, dim, p_off, n_docs, p_sel, p_head, p_sizes, int(max_size), p_cut, p_cost, p_obj, p_status,
-                                a.mem, a.stream))
+    (cut, obj, status), ptrs = _partition_outputs(a, n, n_docs)
+    if ptrs is not None:
+        check(lib().rl_split_chunks(p_x, n, dim, p_off, n_docs, p_sel, p_head, p_sizes, int(max_size), ptrs[0], p_cost, *ptrs[1:],
+                                    a.mem, a.stream))
     return cut, cost, obj, status

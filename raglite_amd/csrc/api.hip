@@ -2897,7 +2897,44 @@ int rl_topk(const float* scores, int32_t n_queries, int64_t n, int64_t ld, int32
     return st == RL_OK ? sy : st;
 }
 
-// ---- timing hook for bench.py ------------------------------------------------------------------------------
+// ---- document-batched ingestion: similarities, chunk / chunklet / sentence partitions (kernels in partition_sim.hip, partition_dp.hip,
+// ---- chunklet_dp.hip, sentence_dp.hip; the offset conventions in doc_batch.h) ---------------------------------------------------------
+// Host offsets are checked here, before the first HIP call; device offsets are clamped by the kernels (doc_batch.h).  doc_max > 0:
+// every document must be shorter than that many rows; its one caller is rl_partition_sentences with 2^31, which the text names.
+static int check_doc_offsets(const char* who, const int64_t* off, int64_t n, int64_t n_docs, int mem, int64_t doc_max) {
+    if (mem != RL_MEM_HOST) return RL_OK;
+    const std::string w(who);
+    if (off[0] != 0) return fail(RL_ERR_INVALID, w + ": doc_offsets must start at 0");
+    for (int64_t d = 0; d < n_docs; ++d) {
+        if (off[d + 1] < off[d]) return fail(RL_ERR_INVALID, w + ": doc_offsets must be ascending");
+        if (doc_max > 0 && off[d + 1] - off[d] >= doc_max) return fail(RL_ERR_INVALID, w + ": a document must be shorter than 2^31 characters");
+    }
+    if (off[n_docs] != n) return fail(RL_ERR_INVALID, w + ": doc_offsets must end at n");
+    return RL_OK;
+}
+
+// The three outputs of a partition call (cut per row; objective, optional, and status per document), staged out and back.
+struct PartitionOut {
+    DevBuf t_cut, t_obj, t_status;
+    uint8_t *h_cut, *cut = nullptr;
+    double *h_obj, *objective = nullptr;
+    int32_t *h_status, *status = nullptr;
+    size_t n, n_docs;
+    int mem;
+    PartitionOut(uint8_t* cut_, double* obj_, int32_t* status_, int64_t n_, int64_t n_docs_, int mem_)
+        : h_cut(cut_), h_obj(obj_), h_status(status_), n((size_t)n_), n_docs((size_t)n_docs_), mem(mem_) {}
+    int begin() {
+        RL_TRY(stage_out_begin(h_cut, n, mem, t_cut, &cut));
+        RL_TRY(stage_out_begin(h_obj, n_docs, mem, t_obj, &objective));
+        return stage_out_begin(h_status, n_docs, mem, t_status, &status);
+    }
+    int end(hipStream_t s) {
+        RL_TRY(stage_out_end(h_cut, n, mem, s, t_cut));
+        RL_TRY(stage_out_end(h_obj, n_docs, mem, s, t_obj));
+        return stage_out_end(h_status, n_docs, mem, s, t_status);
+    }
+};
+
 int rl_partition_similarity(const float* X, int64_t n, int32_t dim, const int64_t* doc_offsets, int64_t n_docs,
                             const uint8_t* nonoutlying, float* out, int mem, void* stream) {
     if (n < 0 || dim <= 0) return fail(RL_ERR_INVALID, "rl_partition_similarity: bad shape");
@@ -2906,6 +2943,7 @@ int rl_partition_similarity(const float* X, int64_t n, int32_t dim, const int64_
     if (dim > 4096) return fail(RL_ERR_UNSUPPORTED, "rl_partition_similarity: dim must be <= 4096");
     if (!doc_offsets) n_docs = 1;
     if (n_docs < 1) return fail(RL_ERR_INVALID, "rl_partition_similarity: need at least one document");
+    if (doc_offsets) RL_TRY(check_doc_offsets("rl_partition_similarity", doc_offsets, n, n_docs, mem, 0));
     hipStream_t s = as_stream(stream);
     DevBuf t_x, t_off, t_sel, t_out, t_scr, t_one;
     const float* d_x; const int64_t* d_off; const uint8_t* d_sel = nullptr; float* d_out;
@@ -2927,7 +2965,7 @@ int rl_partition_similarity(const float* X, int64_t n, int32_t dim, const int64_
     return sync_and_drain(s);  // the scratch dies with this frame
 }
 
-// Argument checks shared by rl_partition_chunks and rl_split_chunks; all of them return before the first HIP call.
+// Argument checks shared by rl_partition_chunks, rl_split_chunks and rl_partition_chunklets; all of them return before the first HIP call.
 static int partition_args(const char* who, const int64_t* sizes, const int64_t* doc_offsets, int64_t n, int64_t n_docs, const uint8_t* cut,
                           const int32_t* status, int mem) {
     const std::string w(who);
@@ -2936,11 +2974,8 @@ static int partition_args(const char* who, const int64_t* sizes, const int64_t* 
     if (!doc_offsets) return fail(RL_ERR_INVALID, w + ": doc_offsets is null");
     if (!cut) return fail(RL_ERR_INVALID, w + ": cut is null");
     if (!status) return fail(RL_ERR_INVALID, w + ": status is null");
+    RL_TRY(check_doc_offsets(who, doc_offsets, n, n_docs, mem, 0));
     if (mem == RL_MEM_HOST) {
-        if (doc_offsets[0] != 0) return fail(RL_ERR_INVALID, w + ": doc_offsets must start at 0");
-        for (int64_t d = 0; d < n_docs; ++d)
-            if (doc_offsets[d + 1] < doc_offsets[d]) return fail(RL_ERR_INVALID, w + ": doc_offsets must be ascending");
-        if (doc_offsets[n_docs] != n) return fail(RL_ERR_INVALID, w + ": doc_offsets must end at n");
         for (int64_t i = 0; i < n; ++i)
             if (sizes[i] < 0) return fail(RL_ERR_INVALID, w + ": sizes must be >= 0");
     }
@@ -2956,19 +2991,16 @@ int rl_partition_chunks(const float* cost, const int64_t* sizes, const int64_t* 
     if (!cost) return fail(RL_ERR_INVALID, "rl_partition_chunks: cost is null");
     RL_TRY(partition_args("rl_partition_chunks", sizes, doc_offsets, n, n_docs, cut, status, mem));
     hipStream_t s = as_stream(stream);
-    DevBuf t_c, t_sz, t_off, t_cut, t_obj, t_st, t_scr;
-    const float* d_c; const int64_t* d_sz; const int64_t* d_off; uint8_t* d_cut; double* d_obj; int32_t* d_st;
+    DevBuf t_c, t_sz, t_off, t_scr;
+    PartitionOut o(cut, objective, status, n, n_docs, mem);
+    const float* d_c; const int64_t* d_sz; const int64_t* d_off;
     RL_TRY(stage_in(cost, (size_t)n, mem, s, t_c, &d_c));
     RL_TRY(stage_in(sizes, (size_t)n, mem, s, t_sz, &d_sz));
     RL_TRY(stage_in(doc_offsets, (size_t)n_docs + 1, mem, s, t_off, &d_off));
-    RL_TRY(stage_out_begin(cut, (size_t)n, mem, t_cut, &d_cut));
-    RL_TRY(stage_out_begin(objective, (size_t)n_docs, mem, t_obj, &d_obj));
-    RL_TRY(stage_out_begin(status, (size_t)n_docs, mem, t_st, &d_st));
+    RL_TRY(o.begin());
     RL_TRY(t_scr.alloc(partition_dp_scratch_bytes(n)));
-    RL_TRY(launch_partition_dp(d_c, d_sz, nullptr, d_off, n, n_docs, max_size, d_cut, d_obj, d_st, t_scr.p, s));
-    RL_TRY(stage_out_end(cut, (size_t)n, mem, s, t_cut));
-    RL_TRY(stage_out_end(objective, (size_t)n_docs, mem, s, t_obj));
-    RL_TRY(stage_out_end(status, (size_t)n_docs, mem, s, t_st));
+    RL_TRY(launch_partition_dp(d_c, d_sz, nullptr, d_off, n, n_docs, max_size, o.cut, o.objective, o.status, t_scr.p, s));
+    RL_TRY(o.end(s));
     return sync_and_drain(s);  // the scratch dies with this frame
 }
 
@@ -2983,17 +3015,16 @@ int rl_split_chunks(const float* X, int64_t n, int32_t dim, const int64_t* doc_o
     RL_TRY(partition_args("rl_split_chunks", sizes, doc_offsets, n, n_docs, cut, status, mem));
     if (dim > 4096) return fail(RL_ERR_UNSUPPORTED, "rl_split_chunks: dim must be <= 4096");
     hipStream_t s = as_stream(stream);
-    DevBuf t_x, t_sz, t_off, t_sel, t_head, t_cut, t_cost, t_obj, t_st, t_scr, t_dp;
+    DevBuf t_x, t_sz, t_off, t_sel, t_head, t_cost, t_scr, t_dp;
+    PartitionOut o(cut, objective, status, n, n_docs, mem);
     const float* d_x; const int64_t* d_sz; const int64_t* d_off; const uint8_t* d_sel = nullptr; const uint8_t* d_head = nullptr;
-    uint8_t* d_cut; float* d_cost; double* d_obj; int32_t* d_st;
+    float* d_cost;
     RL_TRY(stage_in(X, (size_t)n * dim, mem, s, t_x, &d_x));
     RL_TRY(stage_in(sizes, (size_t)n, mem, s, t_sz, &d_sz));
     RL_TRY(stage_in(doc_offsets, (size_t)n_docs + 1, mem, s, t_off, &d_off));
     if (nonoutlying) RL_TRY(stage_in(nonoutlying, (size_t)n, mem, s, t_sel, &d_sel));
     if (is_heading) RL_TRY(stage_in(is_heading, (size_t)n, mem, s, t_head, &d_head));
-    RL_TRY(stage_out_begin(cut, (size_t)n, mem, t_cut, &d_cut));
-    RL_TRY(stage_out_begin(objective, (size_t)n_docs, mem, t_obj, &d_obj));
-    RL_TRY(stage_out_begin(status, (size_t)n_docs, mem, t_st, &d_st));
+    RL_TRY(o.begin());
     if (cost_out) {
         RL_TRY(stage_out_begin(cost_out, (size_t)n, mem, t_cost, &d_cost));
     } else {
@@ -3004,11 +3035,10 @@ int rl_split_chunks(const float* X, int64_t n, int32_t dim, const int64_t* doc_o
     RL_TRY(t_dp.alloc(partition_dp_scratch_bytes(n)));
     RL_TRY(launch_partition_similarity(d_x, n, dim, d_off, n_docs, d_sel, d_cost, t_scr.p, s));
     if (d_head) RL_TRY(launch_partition_headings(d_cost, d_head, d_off, n_docs, n, s));  // in place: entry i reads sim[i] alone
-    RL_TRY(launch_partition_dp(d_cost, d_sz, t_scr.as<float>() /* 1 / |x_i| */, d_off, n, n_docs, max_size, d_cut, d_obj, d_st, t_dp.p, s));
-    RL_TRY(stage_out_end(cut, (size_t)n, mem, s, t_cut));
-    if (cost_out) RL_TRY(stage_out_end(cost_out, (size_t)n, mem, s, t_cost));
-    RL_TRY(stage_out_end(objective, (size_t)n_docs, mem, s, t_obj));
-    RL_TRY(stage_out_end(status, (size_t)n_docs, mem, s, t_st));
+    RL_TRY(launch_partition_dp(d_cost, d_sz, t_scr.as<float>() /* 1 / |x_i| */, d_off, n, n_docs, max_size, o.cut, o.objective, o.status,
+                               t_dp.p, s));
+    RL_TRY(o.end(s));
+    if (cost_out) RL_TRY(stage_out_end(cost_out, (size_t)n, mem, s, t_cost));  // independent copies: their order does not matter
     return sync_and_drain(s);  // the scratch dies with this frame
 }
 
@@ -3022,20 +3052,17 @@ int rl_partition_chunklets(const double* boundary, const double* statements, con
     if (!statements) return fail(RL_ERR_INVALID, "rl_partition_chunklets: statements is null");
     RL_TRY(partition_args("rl_partition_chunklets", lengths, doc_offsets, n, n_docs, cut, status, mem));
     hipStream_t s = as_stream(stream);
-    DevBuf t_b, t_st, t_len, t_off, t_cut, t_obj, t_status, t_scr;
-    const double* d_b; const double* d_s; const int64_t* d_len; const int64_t* d_off; uint8_t* d_cut; double* d_obj; int32_t* d_status;
+    DevBuf t_b, t_st, t_len, t_off, t_scr;
+    PartitionOut o(cut, objective, status, n, n_docs, mem);
+    const double* d_b; const double* d_s; const int64_t* d_len; const int64_t* d_off;
     RL_TRY(stage_in(boundary, (size_t)n, mem, s, t_b, &d_b));
     RL_TRY(stage_in(statements, (size_t)n, mem, s, t_st, &d_s));
     RL_TRY(stage_in(lengths, (size_t)n, mem, s, t_len, &d_len));
     RL_TRY(stage_in(doc_offsets, (size_t)n_docs + 1, mem, s, t_off, &d_off));
-    RL_TRY(stage_out_begin(cut, (size_t)n, mem, t_cut, &d_cut));
-    RL_TRY(stage_out_begin(objective, (size_t)n_docs, mem, t_obj, &d_obj));
-    RL_TRY(stage_out_begin(status, (size_t)n_docs, mem, t_status, &d_status));
+    RL_TRY(o.begin());
     RL_TRY(t_scr.alloc(chunklet_dp_scratch_bytes(n, n_docs)));
-    RL_TRY(launch_chunklet_dp(d_b, d_s, d_len, d_off, n, n_docs, max_size, d_cut, d_obj, d_status, t_scr.p, s));
-    RL_TRY(stage_out_end(cut, (size_t)n, mem, s, t_cut));
-    RL_TRY(stage_out_end(objective, (size_t)n_docs, mem, s, t_obj));
-    RL_TRY(stage_out_end(status, (size_t)n_docs, mem, s, t_status));
+    RL_TRY(launch_chunklet_dp(d_b, d_s, d_len, d_off, n, n_docs, max_size, o.cut, o.objective, o.status, t_scr.p, s));
+    RL_TRY(o.end(s));
     return sync_and_drain(s);  // the scratch dies with this frame
 }
 
@@ -3055,33 +3082,23 @@ int rl_partition_sentences(const uint32_t* codepoints, const void* probas, int p
     if (!status) return fail(RL_ERR_INVALID, "rl_partition_sentences: status is null");
     const int64_t doc_max = (int64_t)1 << 31;  // back-pointers are int32
     if (n_docs == 1 && n >= doc_max) return fail(RL_ERR_INVALID, "rl_partition_sentences: a document must be shorter than 2^31 characters");
-    if (mem == RL_MEM_HOST) {
-        if (doc_offsets[0] != 0) return fail(RL_ERR_INVALID, "rl_partition_sentences: doc_offsets must start at 0");
-        for (int64_t d = 0; d < n_docs; ++d) {
-            if (doc_offsets[d + 1] < doc_offsets[d]) return fail(RL_ERR_INVALID, "rl_partition_sentences: doc_offsets must be ascending");
-            if (doc_offsets[d + 1] - doc_offsets[d] >= doc_max)
-                return fail(RL_ERR_INVALID, "rl_partition_sentences: a document must be shorter than 2^31 characters");
-        }
-        if (doc_offsets[n_docs] != n) return fail(RL_ERR_INVALID, "rl_partition_sentences: doc_offsets must end at n");
-    }
+    RL_TRY(check_doc_offsets("rl_partition_sentences", doc_offsets, n, n_docs, mem, doc_max));
     hipStream_t s = as_stream(stream);
-    DevBuf t_cp, t_p, t_k, t_off, t_cut, t_obj, t_status, t_scr;
-    const uint32_t* d_cp; const uint8_t* d_p; const double* d_k = nullptr; const int64_t* d_off; uint8_t* d_cut; double* d_obj; int32_t* d_status;
+    DevBuf t_cp, t_p, t_k, t_off, t_scr;
+    PartitionOut o(cut, objective, status, n, n_docs, mem);
+    const uint32_t* d_cp; const uint8_t* d_p; const double* d_k = nullptr; const int64_t* d_off;
     RL_TRY(stage_in(codepoints, (size_t)n, mem, s, t_cp, &d_cp));
     RL_TRY(stage_in(static_cast<const uint8_t*>(probas), (size_t)n * (probas_f64 ? 8 : 4), mem, s, t_p, &d_p));
     if (known) RL_TRY(stage_in(known, (size_t)n, mem, s, t_k, &d_k));
     RL_TRY(stage_in(doc_offsets, (size_t)n_docs + 1, mem, s, t_off, &d_off));
-    RL_TRY(stage_out_begin(cut, (size_t)n, mem, t_cut, &d_cut));
-    RL_TRY(stage_out_begin(objective, (size_t)n_docs, mem, t_obj, &d_obj));
-    RL_TRY(stage_out_begin(status, (size_t)n_docs, mem, t_status, &d_status));
+    RL_TRY(o.begin());
     RL_TRY(t_scr.alloc(sentence_dp_scratch_bytes(n, n_docs)));
-    RL_TRY(launch_sentence_dp(d_cp, d_p, probas_f64, d_k, d_off, n, n_docs, min_len, max_len, d_cut, d_obj, d_status, t_scr.p, s));
-    RL_TRY(stage_out_end(cut, (size_t)n, mem, s, t_cut));
-    RL_TRY(stage_out_end(objective, (size_t)n_docs, mem, s, t_obj));
-    RL_TRY(stage_out_end(status, (size_t)n_docs, mem, s, t_status));
+    RL_TRY(launch_sentence_dp(d_cp, d_p, probas_f64, d_k, d_off, n, n_docs, min_len, max_len, o.cut, o.objective, o.status, t_scr.p, s));
+    RL_TRY(o.end(s));
     return sync_and_drain(s);  // the scratch dies with this frame
 }
 
+// ---- query adapter fit (kernels in adapter_fit.hip and query_targets.hip) ---------------------------------------------------------------
 int rl_chunk_best_rows(rl_index* idx, const float* queries, int32_t B, const int32_t* candidates, int32_t n_cand,
                        int32_t* out_rows, int mem, void* stream) {
     if (!idx) return fail(RL_ERR_INVALID, "rl_chunk_best_rows: null index");
@@ -3160,6 +3177,7 @@ int rl_query_targets(rl_index* idx, const float* queries, int32_t B, const int32
     return sync_and_drain(s);  // the scratch dies with this frame
 }
 
+// ---- timing hook for bench.py ------------------------------------------------------------------------------
 int rl_time_kernel(rl_index* idx, int kind, const float* q_dev, int32_t nq, int32_t iters, float* out_ms_total,
                    void* stream) {
     if (!idx || !q_dev || !out_ms_total || iters < 1 || nq < 1) return fail(RL_ERR_INVALID, "rl_time_kernel: bad arguments");

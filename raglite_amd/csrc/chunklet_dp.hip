@@ -9,20 +9,21 @@
 // statement of the same recurrence, and the two agree bit for bit.  The square is x * x (the reference's NumPy scalar `** 2` goes
 // through libm pow, which differs from x * x in the last bit for about one value in a thousand): objectives are pinned against the
 // statement, partitions against the reference.
-// Batched over documents (doc_offsets CSR over the concatenated sentences), every phase its own launch, no atomics:
+// Batched over documents (doc_batch.h), every phase its own launch, no atomics:
 //   cd_prefix_kernel  one wave per document: the character prefix by a wave scan (integers: any order gives the same sum); the two
 //                     float64 prefixes by ONE running sum that every lane carries through the 64 values of a block in order
 //                     (a scan would re-associate); status (2: a non-finite input, else 1: a sentence longer than max_size)
 //   cd_lo_kernel      one lane per sentence: lo(i) by binary search over the character prefix
 //   chunklet_dp_kernel  one wave per document: the recurrence (lanes stride over the window), the backtrack (lane 0)
-// Prefix arrays hold n_d + 1 entries per document: document d (rows [b, e)) owns entries [b + d, e + d] of each.  Scratch per entry:
+// Prefix arrays hold n_d + 1 entries per document: document d (rows [b, e)) owns entries [b + d, e + d] of each, and e <= n keeps
+// entry e + d inside their n + n_docs.  Scratch per entry:
 // pc, lo, back int64 + pb, ps, dp float64 (48 bytes).  dp lives in global memory (L2-resident for the window a step reads): an LDS
 // ring over the window would cap the window's width, and the kernel has no per-document limit.
 //
 // Bits: no operation in this file may be fused or re-associated.  `#pragma clang fp contract(off)` below covers every expression of
 // the file (hipcc's default contracts a * b + c into an fma across statements); the build has no -ffast-math, so `/` and sqrt are the
 // IEEE double operations.
-#include "common.h"
+#include "doc_batch.h"
 
 #include <cmath>
 #include <limits>
@@ -34,23 +35,6 @@ namespace {
 
 constexpr long long CD_NONE = std::numeric_limits<long long>::max();
 
-__device__ __forceinline__ int64_t cd_doc_of(const int64_t* __restrict__ off, int64_t n_docs, int64_t row) {
-    int64_t lo = 0, hi = n_docs;  // off[lo] <= row < off[hi]   (partition_dp.hip: pd_doc_of)
-    while (hi - lo > 1) {
-        const int64_t mid = (lo + hi) >> 1;
-        if (off[mid] <= row) lo = mid; else hi = mid;
-    }
-    return lo;
-}
-
-// Rows [b, e) of a document, forced into [0, n]: device callers' offsets are not validated, and no kernel here may index past n
-// (the prefix arrays: past n + n_docs; entry e + d <= n + n_docs - 1).
-__device__ __forceinline__ void cd_doc_rows(const int64_t* __restrict__ off, int64_t doc, int64_t n, int64_t* b, int64_t* e) {
-    const int64_t lo = off[doc], hi = off[doc + 1];
-    *b = lo < 0 ? 0 : (lo > n ? n : lo);
-    *e = hi < *b ? *b : (hi > n ? n : hi);
-}
-
 __global__ __launch_bounds__(256) void cd_prefix_kernel(const double* __restrict__ boundary, const double* __restrict__ statements,
                                                          const int64_t* __restrict__ lengths, const int64_t* __restrict__ off,
                                                          int64_t n_docs, int64_t n, int64_t max_size, int64_t* __restrict__ pc,
@@ -59,7 +43,7 @@ __global__ __launch_bounds__(256) void cd_prefix_kernel(const double* __restrict
     const int64_t wave0 = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6), n_waves = (int64_t)gridDim.x * 4;
     for (int64_t doc = wave0; doc < n_docs; doc += n_waves) {
         int64_t b, e;
-        cd_doc_rows(off, doc, n, &b, &e);
+        doc_rows(off, doc, n, &b, &e);
         const int64_t base = b + doc;
         if (lane == 0) { pc[base] = 0; pb[base] = 0.0; ps[base] = 0.0; }
         long long carry = 0;
@@ -74,11 +58,7 @@ __global__ __launch_bounds__(256) void cd_prefix_kernel(const double* __restrict
                 if (x > max_size) bad |= 1;
                 if (!isfinite(vb) || !isfinite(vs)) bad |= 2;
             }
-#pragma unroll
-            for (int o = 1; o < 64; o <<= 1) {
-                const long long t = __shfl_up(x, o, 64);
-                if (lane >= o) x += t;
-            }
+            const long long incl = wave_prefix_step(x, lane, &carry);
             double mine_b = 0.0, mine_s = 0.0;
 #pragma unroll 1  // unrolled, the 64 broadcast values fill the register file (256 VGPRs, spilled SGPRs)
             for (int k = 0; k < 64; ++k) {  // left to right; np.cumsum starts from the first element itself, not from 0.0 + it
@@ -89,11 +69,10 @@ __global__ __launch_bounds__(256) void cd_prefix_kernel(const double* __restrict
                 if (lane == k) { mine_b = run_b; mine_s = run_s; }
             }
             if (ok) {
-                pc[base + (i - b) + 1] = carry + x;
+                pc[base + (i - b) + 1] = incl;
                 pb[base + (i - b) + 1] = mine_b;
                 ps[base + (i - b) + 1] = mine_s;
             }
-            carry += __shfl(x, 63, 64);
         }
         const int any1 = __any(bad & 1), any2 = __any(bad & 2);
         if (lane == 0) status[doc] = any2 ? 2 : (any1 ? 1 : 0);
@@ -105,8 +84,8 @@ __global__ __launch_bounds__(256) void cd_lo_kernel(const int64_t* __restrict__ 
     const int64_t r = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (r >= n) return;
     int64_t b, e;
-    const int64_t doc = cd_doc_of(off, n_docs, r);
-    cd_doc_rows(off, doc, n, &b, &e);
+    const int64_t doc = doc_of(off, n_docs, r);
+    doc_rows(off, doc, n, &b, &e);
     if (r < b || r >= e) return;
     const int64_t base = b + doc, i = r - b + 1;  // position i in 1 .. n_d
     const int64_t pci = pc[base + i];
@@ -127,7 +106,7 @@ __global__ __launch_bounds__(256) void chunklet_dp_kernel(const double* __restri
     const int64_t wave0 = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6), n_waves = (int64_t)gridDim.x * 4;
     for (int64_t doc = wave0; doc < n_docs; doc += n_waves) {
         int64_t b, e;
-        cd_doc_rows(off, doc, n, &b, &e);
+        doc_rows(off, doc, n, &b, &e);
         const int64_t nd = e - b, base = b + doc;
         if (status[doc] == 2) {
             if (lane == 0 && objective) objective[doc] = NAN;
@@ -195,7 +174,7 @@ int launch_chunklet_dp(const double* boundary, const double* statements, const i
     double* ps = pb + m;
     double* dp = ps + m;
     RL_HIP(hipMemsetAsync(cut, 0, (size_t)n, s));
-    const int wblocks = (int)std::max<int64_t>(1, std::min<int64_t>((n_docs + 3) / 4, 256 * 16));
+    const int wblocks = wave_per_item_blocks(n_docs);
     hipLaunchKernelGGL(cd_prefix_kernel, dim3(wblocks), dim3(256), 0, s, boundary, statements, lengths, doc_off, n_docs, n, max_size, pc,
                        pb, ps, status);
     hipLaunchKernelGGL(cd_lo_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, pc, doc_off, n_docs, n, max_size, lo);

@@ -6,14 +6,14 @@
 // when window 0 reaches past j.  The admissible p are the range [lo(j), j - 1] with lo non-decreasing.  Ties: "no predecessor"
 // beats an equal g[p]; among predecessors, and among last cuts, the smallest p wins.  raglite_amd/_chunking.py: partition_dp is
 // the host statement of the same recurrence, and the two agree bit for bit.
-// Batched over documents (doc_offsets CSR over the concatenated chunklets), every phase its own launch:
+// Batched over documents (doc_batch.h), every phase its own launch:
 //   pd_prefix_kernel  one wave per document: inclusive prefix sums of the sizes, status (1: a size > max_size; 2: a non-finite cost
 //                     or, from rl_split_chunks, a row of zero / NaN norm)
 //   pd_ends_kernel    one lane per chunklet: end[i] = #{k : csum[k] <= start[i] + max_size} by binary search
 //   ps_headings_kernel  (rl_split_chunks only) the Markdown-heading adjustments of :73-86, elementwise
 //   partition_dp_kernel  one wave per document: W, the recurrence, the last cut, the backtrack
 // Scratch per chunklet: csum, end, prev int64 + g float64 (32 bytes).  No per-document length limit.
-#include "common.h"
+#include "doc_batch.h"
 
 #include <cmath>
 #include <limits>
@@ -23,22 +23,6 @@ namespace {
 
 constexpr int64_t I64_MAX = std::numeric_limits<int64_t>::max();
 
-__device__ __forceinline__ int64_t pd_doc_of(const int64_t* __restrict__ off, int64_t n_docs, int64_t row) {
-    int64_t lo = 0, hi = n_docs;  // off[lo] <= row < off[hi]   (partition_sim.hip: doc_of)
-    while (hi - lo > 1) {
-        const int64_t mid = (lo + hi) >> 1;
-        if (off[mid] <= row) lo = mid; else hi = mid;
-    }
-    return lo;
-}
-
-// Rows [b, e) of a document, forced into [0, n]: device callers' offsets are not validated, and no kernel here may index past n.
-__device__ __forceinline__ void pd_doc_rows(const int64_t* __restrict__ off, int64_t doc, int64_t n, int64_t* b, int64_t* e) {
-    const int64_t lo = off[doc], hi = off[doc + 1];
-    *b = lo < 0 ? 0 : (lo > n ? n : lo);
-    *e = hi < *b ? *b : (hi > n ? n : hi);
-}
-
 __global__ __launch_bounds__(256) void pd_prefix_kernel(const int64_t* __restrict__ sizes, const float* __restrict__ cost,
                                                          const float* __restrict__ inv_norm, const int64_t* __restrict__ off,
                                                          int64_t n_docs, int64_t n, int64_t max_size, int64_t* __restrict__ csum,
@@ -47,7 +31,7 @@ __global__ __launch_bounds__(256) void pd_prefix_kernel(const int64_t* __restric
     const int64_t wave0 = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6), n_waves = (int64_t)gridDim.x * 4;
     for (int64_t doc = wave0; doc < n_docs; doc += n_waves) {
         int64_t b, e;
-        pd_doc_rows(off, doc, n, &b, &e);
+        doc_rows(off, doc, n, &b, &e);
         long long carry = 0;
         int bad = 0;
         for (int64_t base = b; base < e; base += 64) {
@@ -59,13 +43,8 @@ __global__ __launch_bounds__(256) void pd_prefix_kernel(const int64_t* __restric
                 if (i + 1 < e && !isfinite(cost[i])) bad |= 2;
                 if (inv_norm && !(inv_norm[i] < INFINITY)) bad |= 2;  // 1 / |x_i|: inf for a zero row, NaN for a NaN row
             }
-#pragma unroll
-            for (int o = 1; o < 64; o <<= 1) {
-                const long long t = __shfl_up(x, o, 64);
-                if (lane >= o) x += t;
-            }
-            if (ok) csum[i] = carry + x;
-            carry += __shfl(x, 63, 64);
+            const long long incl = wave_prefix_step(x, lane, &carry);
+            if (ok) csum[i] = incl;
         }
         const int any1 = __any(bad & 1), any2 = __any(bad & 2);
         if (lane == 0) status[doc] = any1 ? 1 : (any2 ? 2 : 0);
@@ -77,7 +56,7 @@ __global__ __launch_bounds__(256) void pd_ends_kernel(const int64_t* __restrict_
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
     int64_t b, e;
-    pd_doc_rows(off, pd_doc_of(off, n_docs, i), n, &b, &e);
+    doc_rows(off, doc_of(off, n_docs, i), n, &b, &e);
     if (i < b || i >= e) { end[i] = 0; return; }
     const int64_t start = i > b ? csum[i - 1] : 0;
     const int64_t target = start > I64_MAX - max_size ? I64_MAX : start + max_size;
@@ -98,7 +77,7 @@ __global__ __launch_bounds__(256) void ps_headings_kernel(float* __restrict__ co
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
     int64_t b, e;
-    pd_doc_rows(off, pd_doc_of(off, n_docs, i), n, &b, &e);
+    doc_rows(off, doc_of(off, n_docs, i), n, &b, &e);
     if (i < b || i + 1 >= e) return;  // i <= n_doc - 2 only
     if (heading[i]) cost[i] = 1.0f;
     else if (i + 2 < e && heading[i + 1]) cost[i] = cost[i] / 4;
@@ -139,7 +118,7 @@ __global__ __launch_bounds__(256) void partition_dp_kernel(const float* __restri
     const int64_t wave0 = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6), n_waves = (int64_t)gridDim.x * 4;
     for (int64_t doc = wave0; doc < n_docs; doc += n_waves) {
         int64_t b, e;
-        pd_doc_rows(off, doc, n, &b, &e);
+        doc_rows(off, doc, n, &b, &e);
         const int64_t nd = e - b, m = nd - 1;  // m split positions
         if (status[doc] != 0) {
             if (lane == 0 && objective) objective[doc] = NAN;
@@ -204,7 +183,7 @@ int launch_partition_dp(const float* cost, const int64_t* sizes, const float* in
     int64_t* prev = end + n;
     double* g = reinterpret_cast<double*>(prev + n);
     RL_HIP(hipMemsetAsync(cut, 0, (size_t)n, s));
-    const int wblocks = (int)std::max<int64_t>(1, std::min<int64_t>((n_docs + 3) / 4, 256 * 16));
+    const int wblocks = wave_per_item_blocks(n_docs);
     hipLaunchKernelGGL(pd_prefix_kernel, dim3(wblocks), dim3(256), 0, s, sizes, cost, inv_norm, doc_off, n_docs, n, max_size, csum, status);
     hipLaunchKernelGGL(pd_ends_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, csum, doc_off, n_docs, n, max_size, end);
     hipLaunchKernelGGL(partition_dp_kernel, dim3(wblocks), dim3(256), 0, s, cost, doc_off, n_docs, n, end, status, g, prev, cut, objective);

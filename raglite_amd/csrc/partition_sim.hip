@@ -4,24 +4,15 @@
 //   d      = normalised mean of the normalised rows flagged `nonoutlying`           (:57-61)
 //   X_mod  = X - (X . d) d, re-normalised, used unless some ||X_mod row|| <= eps    (:62-65)
 //   sim[i] = max((X[i] . X[i+1] + 1) / 2, sqrt(eps))   for consecutive rows of one document (:68-72)
-// Batched over documents (doc_offsets CSR over the concatenated rows); fp32 like the reference.  Three small
-// HBM-bound kernels: row norms -> per-document discourse vector -> per-row-pair similarities (+ the per-document
-// "degenerate" flag) -> choice.  sim[last row of a document] = 0 (unused).
-#include "common.h"
+// Batched over documents (doc_batch.h); fp32 like the reference.  Three small HBM-bound kernels: row norms ->
+// per-document discourse vector -> per-row-pair similarities (+ the per-document "degenerate" flag) -> choice.
+// sim[last row of a document] = 0 (unused).
+#include "doc_batch.h"
 
 namespace rl {
 namespace {
 
 constexpr float EPS32 = 1.1920928955078125e-07f;  // np.finfo(np.float32).eps
-
-__device__ __forceinline__ int doc_of(const int64_t* __restrict__ off, int64_t n_docs, int64_t row) {
-    int64_t lo = 0, hi = n_docs;  // off[lo] <= row < off[hi]
-    while (hi - lo > 1) {
-        const int64_t mid = (lo + hi) >> 1;
-        if (off[mid] <= row) lo = mid; else hi = mid;
-    }
-    return (int)lo;
-}
 
 // inv_norm[i] = 1 / ||x_i||   (one wave per row)
 __global__ __launch_bounds__(256) void ps_norms_kernel(const float* __restrict__ X, int64_t n, int dim,
@@ -39,12 +30,13 @@ __global__ __launch_bounds__(256) void ps_norms_kernel(const float* __restrict__
 // d[doc] = normalise(mean over selected rows of x_hat); has_d[doc] = any row selected.  One block per document,
 // thread t owns columns t, t+256, ...: coalesced row reads, fixed row order (deterministic).
 __global__ __launch_bounds__(256) void ps_discourse_kernel(const float* __restrict__ X, const float* __restrict__ inv_norm,
-                                                            const int64_t* __restrict__ doc_off, int dim,
+                                                            const int64_t* __restrict__ doc_off, int64_t n, int dim,
                                                             const uint8_t* __restrict__ sel, float* __restrict__ dvec,
                                                             int32_t* __restrict__ has_d) {
     __shared__ float part[4];
     const int doc = blockIdx.x;
-    const int64_t b = doc_off[doc], e = doc_off[doc + 1];
+    int64_t b, e;
+    doc_rows(doc_off, doc, n, &b, &e);
     int cnt = 0;
     float ss = 0.f;
     for (int k0 = 0; k0 < dim; k0 += 256) {
@@ -78,8 +70,10 @@ __global__ __launch_bounds__(256) void ps_pairs_kernel(const float* __restrict__
     const int lane = threadIdx.x & 63;
     const int64_t wave0 = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6), n_waves = (int64_t)gridDim.x * 4;
     for (int64_t r = wave0; r < n; r += n_waves) {
-        const int doc = doc_of(doc_off, n_docs, r);
-        const bool last = r + 1 >= doc_off[doc + 1];
+        const int64_t doc = doc_of(doc_off, n_docs, r);
+        int64_t doc_b, doc_e;
+        doc_rows(doc_off, doc, n, &doc_b, &doc_e);
+        const bool last = r + 1 >= doc_e;
         const int64_t r1 = last ? r : r + 1;
         float a[NV], b[NV], d[NV];
         const float ia = inv_norm[r], ib = inv_norm[r1];
@@ -90,7 +84,7 @@ __global__ __launch_bounds__(256) void ps_pairs_kernel(const float* __restrict__
             const bool ok = k < dim;
             a[v] = ok ? X[r * (int64_t)dim + k] * ia : 0.f;
             b[v] = ok ? X[r1 * (int64_t)dim + k] * ib : 0.f;
-            d[v] = ok ? dvec[(int64_t)doc * dim + k] : 0.f;
+            d[v] = ok ? dvec[doc * dim + k] : 0.f;
             pa = fmaf(a[v], d[v], pa);
             pb = fmaf(b[v], d[v], pb);
             dot = fmaf(a[v], b[v], dot);
@@ -117,8 +111,10 @@ __global__ __launch_bounds__(256) void ps_choose_kernel(const float* __restrict_
                                                          const int32_t* __restrict__ degenerate, float* __restrict__ out) {
     const int64_t r = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (r >= n) return;
-    const int doc = doc_of(doc_off, n_docs, r);
-    if (r + 1 >= doc_off[doc + 1]) { out[r] = 0.f; return; }
+    const int64_t doc = doc_of(doc_off, n_docs, r);
+    int64_t b, e;
+    doc_rows(doc_off, doc, n, &b, &e);
+    if (r + 1 >= e) { out[r] = 0.f; return; }
     const float s = (has_d[doc] && !degenerate[doc]) ? mod[r] : plain[r];
     out[r] = fmaxf((s + 1.0f) / 2.0f, sqrtf(EPS32));
 }
@@ -141,10 +137,10 @@ int launch_partition_similarity(const float* X, int64_t n, int32_t dim, const in
     int32_t* has_d = reinterpret_cast<int32_t*>(dvec + n_docs * (int64_t)dim);
     int32_t* degenerate = has_d + n_docs;
     RL_HIP(hipMemsetAsync(degenerate, 0, (size_t)n_docs * sizeof(int32_t), s));
-    const int wblocks = (int)std::max<int64_t>(1, std::min<int64_t>((n + 3) / 4, 256 * 16));
+    const int wblocks = wave_per_item_blocks(n);
     hipLaunchKernelGGL(ps_norms_kernel, dim3(wblocks), dim3(256), 0, s, X, n, (int)dim, inv_norm);
-    hipLaunchKernelGGL(ps_discourse_kernel, dim3((unsigned)n_docs), dim3(256), 0, s, X, inv_norm, doc_off, (int)dim, sel,
-                       dvec, has_d);
+    hipLaunchKernelGGL(ps_discourse_kernel, dim3((unsigned)n_docs), dim3(256), 0, s, X, inv_norm, doc_off, n, (int)dim,
+                       sel, dvec, has_d);
 #define RL_PS(NV) hipLaunchKernelGGL((ps_pairs_kernel<NV>), dim3(wblocks), dim3(256), 0, s, X, inv_norm, doc_off, n_docs, n, \
                                      (int)dim, dvec, plain, mod, degenerate)
     const int nv = (dim + 63) / 64;

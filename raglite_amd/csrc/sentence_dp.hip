@@ -1,5 +1,5 @@
 // The sentence partition of src/raglite/_split_sentences.py:183-218: everything the reference does with the
-// model's boundary probability per character, batched over documents (doc_offsets CSR over the concatenated characters).
+// model's boundary probability per character, batched over documents (doc_batch.h).
 //   override     probas[k] = known[k] where known[k] is finite, cast to the dtype of probas (:185-186)
 //   propagation  a range [i, j): i a non-space character followed by a space, j the first non-space character after that run;
 //                probas[i : j-1] = min(probas[i : j]), probas[j-1] = max(probas[i : j]) (:188-196).  A run without a character before
@@ -30,7 +30,7 @@
 //                        (a table, a line without punctuation); the price is that one document's long sentences are solved in series.
 // Scratch per character: the propagated probability float64, dp float64, back int32 (relative to the document in phase 1, to the
 // sentence in phase 2), the space byte; per document the bad word.  dp lives in global memory, as in chunklet_dp.hip.
-#include "common.h"
+#include "doc_batch.h"
 
 #include <cmath>
 #include <limits>
@@ -40,25 +40,7 @@
 namespace rl {
 namespace {
 
-constexpr int64_t SD_DOC_MAX = 2147483647;  // back is int32
-
-__device__ __forceinline__ int64_t sd_doc_of(const int64_t* __restrict__ off, int64_t n_docs, int64_t row) {
-    int64_t lo = 0, hi = n_docs;  // off[lo] <= row < off[hi]: the last such document, so empty ones in front are skipped
-    while (hi - lo > 1) {
-        const int64_t mid = (lo + hi) >> 1;
-        if (off[mid] <= row) lo = mid; else hi = mid;
-    }
-    return lo;
-}
-
-// Characters [b, e) of a document, forced into [0, n] and to fewer than 2^31: device callers' offsets are not validated, and no
-// kernel here may index past n.
-__device__ __forceinline__ void sd_doc_rows(const int64_t* __restrict__ off, int64_t doc, int64_t n, int64_t* b, int64_t* e) {
-    const int64_t lo = off[doc], hi = off[doc + 1];
-    *b = lo < 0 ? 0 : (lo > n ? n : lo);
-    *e = hi < *b ? *b : (hi > n ? n : hi);
-    if (*e - *b > SD_DOC_MAX) *e = *b + SD_DOC_MAX;
-}
+constexpr int64_t SD_DOC_MAX = 2147483647;  // back is int32: the cap every doc_rows of this file passes
 
 __device__ __forceinline__ bool sd_is_space(uint32_t c) {  // str.isspace
     return (c >= 0x0009u && c <= 0x000Du) || (c >= 0x001Cu && c <= 0x0020u) || c == 0x0085u || c == 0x00A0u || c == 0x1680u ||
@@ -95,8 +77,8 @@ __global__ __launch_bounds__(256) void sd_classify_kernel(const uint32_t* __rest
         P[i] = p;
         if (!isfinite(p)) {
             int64_t b, e;
-            const int64_t doc = sd_doc_of(off, n_docs, i);
-            sd_doc_rows(off, doc, n, &b, &e);
+            const int64_t doc = doc_of(off, n_docs, i);
+            doc_rows(off, doc, n, &b, &e, SD_DOC_MAX);
             if (i >= b && i < e) bad[doc] = 1;
         }
     }
@@ -108,8 +90,8 @@ __global__ __launch_bounds__(256) void sd_propagate_kernel(const uint8_t* __rest
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += stride) {
         if (SP[i] || i + 1 >= n || !SP[i + 1]) continue;  // a range starts at a non-space character followed by a space
         int64_t b, e;
-        const int64_t doc = sd_doc_of(off, n_docs, i);
-        sd_doc_rows(off, doc, n, &b, &e);
+        const int64_t doc = doc_of(off, n_docs, i);
+        doc_rows(off, doc, n, &b, &e, SD_DOC_MAX);
         if (i < b || i + 1 >= e) continue;
         double lo = P[i], hi = lo;
         int64_t j = i + 1;
@@ -132,7 +114,7 @@ __global__ __launch_bounds__(256) void sd_phase1_kernel(const double* __restrict
     const int64_t wave0 = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6), n_waves = (int64_t)gridDim.x * 4;
     for (int64_t doc = wave0; doc < n_docs; doc += n_waves) {
         int64_t b, e;
-        sd_doc_rows(off, doc, n, &b, &e);
+        doc_rows(off, doc, n, &b, &e, SD_DOC_MAX);
         if (bad[doc]) {
             if (lane == 0) {
                 status[doc] = 2;
@@ -244,7 +226,7 @@ __global__ __launch_bounds__(256) void sd_phase2_kernel(const double* __restrict
     const int64_t wave0 = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6), n_waves = (int64_t)gridDim.x * 4;
     for (int64_t doc = wave0; doc < n_docs; doc += n_waves) {
         int64_t b, e;
-        sd_doc_rows(off, doc, n, &b, &e);
+        doc_rows(off, doc, n, &b, &e, SD_DOC_MAX);
         const int64_t nd = e - b;
         if (nd <= max_len || status[doc] == 2) continue;
         int st = 0;
@@ -288,7 +270,7 @@ int launch_sentence_dp(const uint32_t* codepoints, const void* probas, int proba
     RL_HIP(hipMemsetAsync(cut, 0, (size_t)n, s));
     RL_HIP(hipMemsetAsync(bad, 0, (size_t)n_docs * sizeof(int32_t), s));
     const int cblocks = (int)std::max<int64_t>(1, std::min<int64_t>((n + 255) / 256, 256 * 64));
-    const int wblocks = (int)std::max<int64_t>(1, std::min<int64_t>((n_docs + 3) / 4, 256 * 16));
+    const int wblocks = wave_per_item_blocks(n_docs);
     hipLaunchKernelGGL(sd_classify_kernel, dim3(cblocks), dim3(256), 0, s, codepoints, probas, f32, known, doc_off, n_docs, n, P, SP, bad);
     hipLaunchKernelGGL(sd_propagate_kernel, dim3(cblocks), dim3(256), 0, s, SP, doc_off, n_docs, n, P);
     hipLaunchKernelGGL(sd_phase1_kernel, dim3(wblocks), dim3(256), 0, s, P, f32, doc_off, n_docs, n, min_len, bad, dp, back, cut, objective,

@@ -244,4 +244,10 @@ def test_c_entries_reject_bad_arguments_before_any_hip_call():
     assert split(X=None) == _abi.RL_ERR_INVALID and "X" in _abi.last_error()
     assert split(dim=0) == _abi.RL_ERR_INVALID
     assert split(X=np.ones((n, 4097), np.float32), dim=4097) == _abi.RL_ERR_UNSUPPORTED
-    assert np.all(cut == 0) and np.all(status == 0)
+    sim_out = np.zeros(n, np.float32)
+    for bad_off, word in ((np.asarray([1, 2, 4], np.int64), "start at 0"), (np.asarray([0, 3, 2], np.int64), "ascending"),
+                          (np.asarray([0, 2, 3], np.int64), "end at n")):
+        assert lib.rl_partition_similarity(p(X), n, dim, p(bad_off), 2, p(sel), p(sim_out), _abi.MEM_HOST, None) == _abi.RL_ERR_INVALID, word
+        err = _abi.last_error()
+        assert "rl_partition_similarity" in err and word in err, (word, err)
+    assert np.all(cut == 0) and np.all(status == 0) and np.all(sim_out == 0)
