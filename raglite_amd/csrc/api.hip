@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "common.h"
+#include "staging.h"
 
 namespace rl {
 
@@ -22,106 +23,6 @@ int fail(int code, const std::string& msg) {
 namespace {
 
 hipStream_t as_stream(void* s) { return reinterpret_cast<hipStream_t>(s); }
-
-// Per-thread cache of small device blocks: RL_MEM_HOST calls stage a query in and a handful of results out, and a
-// hipMalloc + hipFree pair per staging buffer costs more than a 10 k-row search (measured: 121 us per host-argument
-// search_chunks against 39 us with device arguments).  Blocks up to 4 MiB are recycled, larger ones are not kept.
-struct BlockCache {
-    struct Block { void* p; size_t bytes; int device; };
-    std::vector<Block> free_blocks;
-    static constexpr size_t MAX_BLOCK = size_t(4) << 20;
-    static constexpr size_t MAX_BLOCKS = 32;
-    void* take(size_t bytes, int device, size_t* got) {
-        for (size_t i = 0; i < free_blocks.size(); ++i) {
-            Block b = free_blocks[i];
-            if (b.device == device && b.bytes >= bytes && b.bytes <= 4 * bytes + 4096) {
-                free_blocks.erase(free_blocks.begin() + (long)i);
-                *got = b.bytes;
-                return b.p;
-            }
-        }
-        return nullptr;
-    }
-    void give(void* p, size_t bytes, int device) {
-        if (bytes > MAX_BLOCK || free_blocks.size() >= MAX_BLOCKS) { (void)hipFree(p); return; }
-        free_blocks.push_back({p, bytes, device});
-    }
-    ~BlockCache() {
-        for (const Block& b : free_blocks) (void)hipFree(b.p);  // at thread exit; errors during runtime teardown are moot
-    }
-};
-thread_local BlockCache g_blocks;
-
-// Per-thread pinned bounce buffer for the small host <-> device copies of RL_MEM_HOST calls (a query in, k results
-// out).  A hipMemcpyAsync from / to pageable memory is synchronous and goes through the driver's own staging; through
-// pinned memory the copies are truly asynchronous and the call needs ONE synchronisation: results are copied out of
-// the pinned buffer after it (drain()).  Entries are keyed by the DevBuf they belong to, so that an early error
-// return, which destroys its DevBufs without draining, can never copy stale data into a caller's buffer later.
-struct PinnedBounce {
-    static constexpr size_t CAP = size_t(1) << 20, SMALL = size_t(256) << 10;
-    char* base = nullptr;
-    size_t used = 0;
-    struct Pending { const void* owner; const void* src; void* dst; size_t bytes; };
-    std::vector<Pending> pending;
-    void* take(size_t bytes) {
-        if (bytes == 0 || bytes > SMALL) return nullptr;
-        if (!base && hipHostMalloc(reinterpret_cast<void**>(&base), CAP, hipHostMallocDefault) != hipSuccess) {
-            base = nullptr;
-            (void)hipGetLastError();
-            return nullptr;
-        }
-        const size_t at = (used + 63) & ~size_t(63);
-        if (at + bytes > CAP) return nullptr;
-        used = at + bytes;
-        return base + at;
-    }
-    void drain() {  // after the stream has been synchronised
-        for (const Pending& p : pending) std::memcpy(p.dst, p.src, p.bytes);
-        pending.clear();
-        used = 0;
-    }
-    void drop(const void* owner) {
-        for (size_t i = pending.size(); i-- > 0;)
-            if (pending[i].owner == owner) pending.erase(pending.begin() + (long)i);
-    }
-    ~PinnedBounce() { if (base) (void)hipHostFree(base); }
-};
-thread_local PinnedBounce g_pinned;
-
-// Device scratch that returns itself to the thread's block cache; used for RL_MEM_HOST staging and per-call
-// temporaries.  Callers synchronise the stream before the buffer goes out of scope whenever the device may still
-// be using it (finish() for host calls), so a recycled block is never in flight.
-struct DevBuf {
-    void* p = nullptr;
-    size_t bytes = 0;
-    int device = 0;
-    ~DevBuf() { release(); }
-    void release() {
-        g_pinned.drop(this);
-        if (p) g_blocks.give(p, bytes, device);
-        p = nullptr;
-    }
-    int alloc(size_t want) {
-        release();
-        if (want == 0) want = 16;
-        RL_HIP(hipGetDevice(&device));
-        size_t got = 0;
-        p = g_blocks.take(want, device, &got);
-        if (p) { bytes = got; return RL_OK; }
-        const size_t rounded = (want + 255) & ~size_t(255);
-        RL_HIP(hipMalloc(&p, rounded));
-        bytes = rounded;
-        return RL_OK;
-    }
-    template <class T>
-    T* as() const { return reinterpret_cast<T*>(p); }
-};
-
-// RL_HIP for the lifecycle calls, whose HIP errors name the entry point ("rl_index_append: out of memory").
-int hip_status(hipError_t e, const char* who) {
-    if (e == hipSuccess) return RL_OK;
-    return fail(e == hipErrorOutOfMemory ? RL_ERR_NOMEM : RL_ERR_HIP, std::string(who) + ": " + hipGetErrorString(e));
-}
 
 // Device memory owned by an index: freed with its owner, move-only (one owner per block).  As scratch it grows: reserve() never
 // shrinks, frees the old block before it allocates and does not keep the contents (no allocation in steady state).
@@ -164,52 +65,6 @@ template <class T>
 struct DevArray : Pool {
     operator T*() const { return as<T>(); }
 };
-
-// Input staging: returns a device pointer for `src` (copying when it is a host pointer).
-template <class T>
-int stage_in(const T* src, size_t count, int mem, hipStream_t s, DevBuf& tmp, const T** out) {
-    if (mem == RL_MEM_DEVICE) { *out = src; return RL_OK; }
-    RL_TRY(tmp.alloc(count * sizeof(T)));
-    if (count) {
-        const void* from = src;
-        if (void* pin = g_pinned.take(count * sizeof(T))) {
-            std::memcpy(pin, src, count * sizeof(T));
-            from = pin;
-        }
-        RL_HIP(hipMemcpyAsync(tmp.p, from, count * sizeof(T), hipMemcpyHostToDevice, s));
-    }
-    *out = tmp.as<T>();
-    return RL_OK;
-}
-// Output staging: a device pointer to write to; stage_out copies back for host callers.
-template <class T>
-int stage_out_begin(T* dst, size_t count, int mem, DevBuf& tmp, T** out) {
-    if (mem == RL_MEM_DEVICE || dst == nullptr) { *out = dst; return RL_OK; }
-    RL_TRY(tmp.alloc(count * sizeof(T)));
-    *out = tmp.as<T>();
-    return RL_OK;
-}
-template <class T>
-int stage_out_end(T* dst, size_t count, int mem, hipStream_t s, const DevBuf& tmp) {
-    if (mem == RL_MEM_DEVICE || dst == nullptr || count == 0) return RL_OK;
-    if (void* pin = g_pinned.take(count * sizeof(T))) {
-        RL_HIP(hipMemcpyAsync(pin, tmp.p, count * sizeof(T), hipMemcpyDeviceToHost, s));
-        g_pinned.pending.push_back({&tmp, pin, dst, count * sizeof(T)});
-        return RL_OK;
-    }
-    RL_HIP(hipMemcpyAsync(dst, tmp.p, count * sizeof(T), hipMemcpyDeviceToHost, s));
-    return RL_OK;
-}
-// Synchronise and hand the bounced results to the caller's buffers.
-int sync_and_drain(hipStream_t s) {
-    RL_HIP(hipStreamSynchronize(s));
-    g_pinned.drain();
-    return RL_OK;
-}
-int finish(int mem, hipStream_t s) {
-    if (mem == RL_MEM_HOST) return sync_and_drain(s);
-    return RL_OK;
-}
 
 // RL_MEM_FILTERS_DEVICE or-ed into `mem`: the filter table alone is a device pointer, read in place; every other pointer follows the
 // rest of `mem`.  Each entry that takes filters splits `mem` once, into where its filters live and where everything else does.
@@ -727,18 +582,16 @@ int rl_pool_norm(const float* tokens, int64_t n_token_rows, int32_t dim, const i
             if (span_begin[i] < 0 || span_end[i] < span_begin[i] || span_end[i] > n_token_rows)
                 return fail(RL_ERR_INVALID, "rl_pool_norm: span outside the token matrix");
     }
-    DevBuf t_tok, t_b, t_e, t_o32, t_o16;
+    Staging st(mem, s);
     const float* d_tok; const int64_t* d_b; const int64_t* d_e;
-    RL_TRY(stage_in(tokens, (size_t)n_token_rows * dim, mem, s, t_tok, &d_tok));
-    RL_TRY(stage_in(span_begin, (size_t)n_spans, mem, s, t_b, &d_b));
-    RL_TRY(stage_in(span_end, (size_t)n_spans, mem, s, t_e, &d_e));
+    RL_TRY(st.in(tokens, (size_t)n_token_rows * dim, &d_tok));
+    RL_TRY(st.in(span_begin, (size_t)n_spans, &d_b));
+    RL_TRY(st.in(span_end, (size_t)n_spans, &d_e));
     float* d_o32; uint16_t* d_o16;
-    RL_TRY(stage_out_begin(out_f32, (size_t)n_spans * dim, mem, t_o32, &d_o32));
-    RL_TRY(stage_out_begin(out_f16, (size_t)n_spans * dim, mem, t_o16, &d_o16));
+    RL_TRY(st.out(out_f32, (size_t)n_spans * dim, &d_o32));
+    RL_TRY(st.out(out_f16, (size_t)n_spans * dim, &d_o16));
     RL_TRY(launch_pool_norm(d_tok, dim, d_b, d_e, n_spans, normalize, eps, d_o32, d_o16, s));
-    RL_TRY(stage_out_end(out_f32, (size_t)n_spans * dim, mem, s, t_o32));
-    RL_TRY(stage_out_end(out_f16, (size_t)n_spans * dim, mem, s, t_o16));
-    return finish(mem, s);
+    return st.finish();
 }
 
 // Below this many queries the stream kernel's per-32-query corpus passes (HBM-bound) beat a 128-query GEMM tile.
@@ -755,18 +608,13 @@ int rl_adapter_apply(const float* A, const float* queries, int32_t n_queries, in
     if (!out_f32 && !out_f16) return fail(RL_ERR_INVALID, "rl_adapter_apply: no output requested");
     if (n_queries == 0) return RL_OK;
     hipStream_t s = as_stream(stream);
-    DevBuf t_a, t_q, t_o32, t_o16, t_tmp;
+    Staging st(mem, s);
     const float* d_a; const float* d_q;
-    RL_TRY(stage_in(A, (size_t)dim * dim, mem, s, t_a, &d_a));
-    RL_TRY(stage_in(queries, (size_t)n_queries * dim, mem, s, t_q, &d_q));
-    float* d_o32; uint16_t* d_o16;
-    RL_TRY(stage_out_begin(out_f32, (size_t)n_queries * dim, mem, t_o32, &d_o32));
-    RL_TRY(stage_out_begin(out_f16, (size_t)n_queries * dim, mem, t_o16, &d_o16));
-    float* d_res = d_o32;
-    if (!d_res) {  // fp16-only output still needs the fp32 result first
-        RL_TRY(t_tmp.alloc((size_t)n_queries * dim * sizeof(float)));
-        d_res = t_tmp.as<float>();
-    }
+    RL_TRY(st.in(A, (size_t)dim * dim, &d_a));
+    RL_TRY(st.in(queries, (size_t)n_queries * dim, &d_q));
+    float* d_res; uint16_t* d_o16;
+    RL_TRY(st.out_or_temp(out_f32, (size_t)n_queries * dim, &d_res));  // fp16-only output still needs the fp32 result first
+    RL_TRY(st.out(out_f16, (size_t)n_queries * dim, &d_o16));
     // out[b][r] = sum_c A[r][c] q[b][c]: a similarity scan over the rows of A in raw-dot mode.  Batches go
     // through the MFMA tile kernel (32 queries per pass over A, which stays L2-resident), single queries and
     // other dims through the VALU scan.
@@ -790,10 +638,7 @@ int rl_adapter_apply(const float* A, const float* queries, int32_t n_queries, in
     }
     if (!done) RL_TRY(launch_scan_rows(d_a, dim, dim, d_q, n_queries, nullptr, SCAN_RAW_DOT, d_res, dim, s));
     if (d_o16) RL_TRY(launch_cast_f16(d_res, d_o16, (int64_t)n_queries * dim, s));
-    RL_TRY(stage_out_end(out_f32, (size_t)n_queries * dim, mem, s, t_o32));
-    RL_TRY(stage_out_end(out_f16, (size_t)n_queries * dim, mem, s, t_o16));
-    if (mem == RL_MEM_DEVICE && !out_f32) RL_HIP(hipStreamSynchronize(s));  // t_tmp dies with this frame
-    return finish(mem, s);
+    return st.finish();
 }
 
 // ---- index ---------------------------------------------------------------------------------------------
@@ -1174,13 +1019,13 @@ int rl_index_append(rl_index* idx, const float* rows, int64_t n_new_rows, const 
         }
     }
     // ---- new rows, CSR, ordinals, norms ------------------------------------------------------------------
-    DevBuf t_rows;
+    Staging st(mem, s);
     if (n_new_rows && !f16)
         RL_HIP(hipMemcpyAsync(const_cast<float*>(idx->E) + (size_t)old_n * idx->dim, rows, (size_t)n_new_rows * row_bytes,
                               mem == RL_MEM_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, s));
     if (n_new_rows && f16) {  // fp32 rows in, rounded to nearest even into the fp16 store (the reference's astype(float16))
         const float* d_rows;
-        RL_TRY(stage_in(rows, (size_t)n_new_rows * idx->dim, mem, s, t_rows, &d_rows));
+        RL_TRY(st.in(rows, (size_t)n_new_rows * idx->dim, &d_rows));
         RL_TRY(launch_cast_f16(d_rows, const_cast<uint16_t*>(idx->E16) + (size_t)old_n * idx->dim,
                                n_new_rows * (int64_t)idx->dim, s));
     }
@@ -1208,7 +1053,7 @@ int rl_index_append(rl_index* idx, const float* rows, int64_t n_new_rows, const 
         for (int64_t c = old_c; c < new_c; ++c) idx->h_live[(size_t)(c >> 5)] |= 1u << (c & 31);
         RL_TRY(upload_live_bits(idx, s));
     }
-    return sync_and_drain(s);  // the caller's buffers may go away after return
+    return st.finish_synced();  // the caller's buffers may go away after return
 }
 
 int rl_index_info(const rl_index* idx, int64_t* n_rows, int32_t* dim, int64_t* n_chunks, int* metric) {
@@ -1898,19 +1743,17 @@ int rl_search_rows_ranked(rl_index* idx, const float* queries, int32_t B, int32_
     hipStream_t s = as_stream(stream);
     std::lock_guard<std::mutex> lock(idx->mu);
     RL_TRY(use_scratch(idx, s));
-    DevBuf t_q, t_s, t_r, t_f;
+    Staging st(mem, s);
     const float* d_q; float* d_s; int32_t* d_r;
     BatchFilters f;
     f.n = chunk_filter ? 1 : 0;
     f.limit = rank_limit;
-    if (chunk_filter) RL_TRY(stage_in(chunk_filter, (size_t)((idx->n_chunks + 31) / 32), fmem, s, t_f, &f.chunk_bits));
-    RL_TRY(stage_in(queries, (size_t)B * idx->dim, mem, s, t_q, &d_q));
-    RL_TRY(stage_out_begin(out_scores, (size_t)B * k, mem, t_s, &d_s));
-    RL_TRY(stage_out_begin(out_rows, (size_t)B * k, mem, t_r, &d_r));
+    if (chunk_filter) RL_TRY(st.in(chunk_filter, (size_t)((idx->n_chunks + 31) / 32), &f.chunk_bits, fmem));
+    RL_TRY(st.in(queries, (size_t)B * idx->dim, &d_q));
+    RL_TRY(st.out(out_scores, (size_t)B * k, &d_s));
+    RL_TRY(st.out(out_rows, (size_t)B * k, &d_r));
     RL_TRY(search_rows_device(idx, d_q, B, k, d_s, d_r, s, f));
-    RL_TRY(stage_out_end(out_scores, (size_t)B * k, mem, s, t_s));
-    RL_TRY(stage_out_end(out_rows, (size_t)B * k, mem, s, t_r));
-    return finish(mem, s);
+    return st.finish();
 }
 
 int rl_search_rows_filtered(rl_index* idx, const float* queries, int32_t B, int32_t k, const uint32_t* chunk_filter,
@@ -1933,9 +1776,9 @@ int rl_rank_cut_begin(rl_index* idx, const float* queries, int32_t B, int mem, v
     idx->rank_B = 0;
     const int64_t n = idx->n_rows, ld = std::max<int64_t>((n + 3) & ~int64_t(3), 4);
     if ((int64_t)B * ld * 4 > (int64_t)SCORE_BATCH_BYTES) return fail(RL_ERR_UNSUPPORTED, "rl_rank_cut_begin: too many queries for one score batch (split the batch)");
-    DevBuf t_q;
+    Staging st(mem, s);
     const float* d_q;
-    RL_TRY(stage_in(queries, (size_t)B * idx->dim, mem, s, t_q, &d_q));
+    RL_TRY(st.in(queries, (size_t)B * idx->dim, &d_q));
     RL_TRY(idx->rank_q.reserve((size_t)B * idx->dim * sizeof(float)));
     RL_HIP(hipMemcpyAsync(idx->rank_q.p, d_q, (size_t)B * idx->dim * sizeof(float), hipMemcpyDeviceToDevice, s));
     RL_TRY(idx->scores.reserve((size_t)B * ld * sizeof(float)));
@@ -1945,7 +1788,7 @@ int rl_rank_cut_begin(rl_index* idx, const float* queries, int32_t B, int mem, v
         if (idx->live_row_bits) RL_TRY(launch_mask_scores(idx->scores.as<float>(), B, n, ld, QueryMask(idx->live_row_bits), s));  // tombstones are not in the table
     }
     idx->rank_B = B;
-    return finish(mem, s);
+    return st.finish();
 }
 
 namespace {
@@ -1960,15 +1803,14 @@ int rl_rank_cut_level(rl_index* idx, int level, int64_t rank_limit, uint32_t* ou
     if (idx->rank_B < 1) return fail(RL_ERR_INVALID, "rl_rank_cut_level: no rl_rank_cut_begin in progress on this index");
     if (level < 0 || level > 2 || rank_limit < 1) return fail(RL_ERR_INVALID, "rl_rank_cut_level: level must be 0..2 and rank_limit >= 1");
     const int64_t n = idx->n_rows, ld = std::max<int64_t>((n + 3) & ~int64_t(3), 4);
-    DevBuf t_o;
+    Staging st(mem, s);
     uint32_t* d_o;
     const size_t words = (size_t)idx->rank_B * HIST_BINS;
-    RL_TRY(stage_out_begin(out_hist, words, mem, t_o, &d_o));
+    RL_TRY(st.out(out_hist, words, &d_o));
     uint32_t* lvl = mem == RL_MEM_DEVICE ? d_o : rank_level_buf(idx);
     RL_TRY(launch_rank_stage_level(idx->scores.as<float>(), idx->rank_B, n, ld, rank_limit, level, idx->rankbuf.p, lvl, s));
     if (lvl != d_o) RL_HIP(hipMemcpyAsync(d_o, lvl, words * sizeof(uint32_t), hipMemcpyDeviceToDevice, s));
-    RL_TRY(stage_out_end(out_hist, words, mem, s, t_o));
-    return finish(mem, s);
+    return st.finish();
 }
 
 int rl_rank_cut_level_done(rl_index* idx, int level, const uint32_t* hist_sum, int mem, void* stream) {
@@ -1978,11 +1820,11 @@ int rl_rank_cut_level_done(rl_index* idx, int level, const uint32_t* hist_sum, i
     RL_TRY(use_scratch(idx, s));
     if (idx->rank_B < 1) return fail(RL_ERR_INVALID, "rl_rank_cut_level_done: no rl_rank_cut_begin in progress on this index");
     if (level < 0 || level > 2) return fail(RL_ERR_INVALID, "rl_rank_cut_level_done: level must be 0..2");
-    DevBuf t_i;
+    Staging st(mem, s);
     const uint32_t* d_i;
-    RL_TRY(stage_in(hist_sum, (size_t)idx->rank_B * HIST_BINS, mem, s, t_i, &d_i));
+    RL_TRY(st.in(hist_sum, (size_t)idx->rank_B * HIST_BINS, &d_i));
     RL_TRY(launch_rank_stage_set_level(idx->rank_B, level, idx->rankbuf.p, d_i, s));
-    return finish(mem, s);
+    return st.finish();
 }
 
 int rl_rank_cut_ties(rl_index* idx, int64_t rank_limit, uint32_t* out_ties, int mem, void* stream) {
@@ -1992,12 +1834,11 @@ int rl_rank_cut_ties(rl_index* idx, int64_t rank_limit, uint32_t* out_ties, int 
     RL_TRY(use_scratch(idx, s));
     if (idx->rank_B < 1 || rank_limit < 1) return fail(RL_ERR_INVALID, "rl_rank_cut_ties: no rl_rank_cut_begin in progress on this index");
     const int64_t n = idx->n_rows, ld = std::max<int64_t>((n + 3) & ~int64_t(3), 4);
-    DevBuf t_o;
+    Staging st(mem, s);
     uint32_t* d_o;
-    RL_TRY(stage_out_begin(out_ties, (size_t)idx->rank_B, mem, t_o, &d_o));
+    RL_TRY(st.out(out_ties, (size_t)idx->rank_B, &d_o));
     RL_TRY(launch_rank_stage_ties(idx->scores.as<float>(), idx->rank_B, n, ld, rank_limit, idx->rankbuf.p, d_o, s));
-    RL_TRY(stage_out_end(out_ties, (size_t)idx->rank_B, mem, s, t_o));
-    return finish(mem, s);
+    return st.finish();
 }
 
 int rl_rank_cut_finish(rl_index* idx, int64_t rank_limit, const uint32_t* ties_before, const uint32_t* chunk_filter, int32_t k,
@@ -2011,14 +1852,14 @@ int rl_rank_cut_finish(rl_index* idx, int64_t rank_limit, const uint32_t* ties_b
     if (B < 1) return fail(RL_ERR_INVALID, "rl_rank_cut_finish: no rl_rank_cut_begin in progress on this index");
     idx->rank_B = 0;
     const int64_t n = idx->n_rows, ld = std::max<int64_t>((n + 3) & ~int64_t(3), 4);
-    DevBuf t_b, t_f, t_s, t_r;
+    Staging st(mem, s);
     const uint32_t* d_b; const uint32_t* d_f = nullptr; const uint32_t* d_bits = nullptr;
     float* d_s; int32_t* d_r;
-    RL_TRY(stage_in(ties_before, (size_t)B, mem, s, t_b, &d_b));
-    if (chunk_filter) RL_TRY(stage_in(chunk_filter, (size_t)((idx->n_chunks + 31) / 32), mem, s, t_f, &d_f));
+    RL_TRY(st.in(ties_before, (size_t)B, &d_b));
+    if (chunk_filter) RL_TRY(st.in(chunk_filter, (size_t)((idx->n_chunks + 31) / 32), &d_f));
     RL_TRY(effective_row_mask(idx, d_f, s, &d_bits));
-    RL_TRY(stage_out_begin(out_scores, (size_t)B * k, mem, t_s, &d_s));
-    RL_TRY(stage_out_begin(out_rows, (size_t)B * k, mem, t_r, &d_r));
+    RL_TRY(st.out(out_scores, (size_t)B * k, &d_s));
+    RL_TRY(st.out(out_rows, (size_t)B * k, &d_r));
     if (n == 0) {
         RL_TRY(launch_fill_f32(d_s, -std::numeric_limits<float>::infinity(), (int64_t)B * k, s));
         RL_HIP(hipMemsetAsync(d_r, 0xff, (size_t)B * k * sizeof(int32_t), s));
@@ -2027,9 +1868,7 @@ int rl_rank_cut_finish(rl_index* idx, int64_t rank_limit, const uint32_t* ties_b
         RL_TRY(select_from_scores(idx, idx->rank_q.as<float>(), B, k, d_s, d_r, ld, false, s));
         RL_TRY(launch_fix_masked(d_s, d_r, (int64_t)B * k, s));  // rows outside the cut / the filter are "no hit"
     }
-    RL_TRY(stage_out_end(out_scores, (size_t)B * k, mem, s, t_s));
-    RL_TRY(stage_out_end(out_rows, (size_t)B * k, mem, s, t_r));
-    return finish(mem, s);
+    return st.finish();
 }
 
 // ---- a6 + a7 + a8 --------------------------------------------------------------------------------------
@@ -2048,23 +1887,20 @@ int search_chunks_call(rl_index* idx, const float* queries, int32_t B, int32_t n
     hipStream_t s = as_stream(stream);
     std::lock_guard<std::mutex> lock(idx->mu);
     RL_TRY(use_scratch(idx, s));
-    DevBuf t_q, t_s, t_c, t_n, t_f;
+    Staging st(mem, s);
     const float* d_q; float* d_s; int32_t* d_c; int32_t* d_n;
     BatchFilters f;
     f.n = n_filters;
     f.qf = query_filter;
     f.lim = rank_limits;
     f.limit = rank_limit;
-    if (n_filters) RL_TRY(stage_in(chunk_filters, (size_t)n_filters * ((idx->n_chunks + 31) / 32), fmem, s, t_f, &f.chunk_bits));
-    RL_TRY(stage_in(queries, (size_t)B * idx->dim, mem, s, t_q, &d_q));
-    RL_TRY(stage_out_begin(out_scores, (size_t)B * k, mem, t_s, &d_s));
-    RL_TRY(stage_out_begin(out_chunks, (size_t)B * k, mem, t_c, &d_c));
-    RL_TRY(stage_out_begin(out_counts, (size_t)B, mem, t_n, &d_n));
+    if (n_filters) RL_TRY(st.in(chunk_filters, (size_t)n_filters * ((idx->n_chunks + 31) / 32), &f.chunk_bits, fmem));
+    RL_TRY(st.in(queries, (size_t)B * idx->dim, &d_q));
+    RL_TRY(st.out(out_scores, (size_t)B * k, &d_s));
+    RL_TRY(st.out(out_chunks, (size_t)B * k, &d_c));
+    RL_TRY(st.out(out_counts, (size_t)B, &d_n));
     RL_TRY(search_chunks_device(idx, d_q, B, num_hits, k, f, d_s, d_c, d_n, s));
-    RL_TRY(stage_out_end(out_scores, (size_t)B * k, mem, s, t_s));
-    RL_TRY(stage_out_end(out_chunks, (size_t)B * k, mem, s, t_c));
-    RL_TRY(stage_out_end(out_counts, (size_t)B, mem, s, t_n));
-    return finish(mem, s);
+    return st.finish();
 }
 }  // namespace
 
@@ -2212,15 +2048,39 @@ int rl_maxsim_scores(rl_index* idx, const float* query_vecs, int32_t nq, float* 
     hipStream_t s = as_stream(stream);
     std::lock_guard<std::mutex> lock(idx->mu);
     RL_TRY(use_scratch(idx, s));
-    DevBuf t_q, t_o;
+    Staging st(mem, s);
     const float* d_q; float* d_o;
-    RL_TRY(stage_in(query_vecs, (size_t)nq * idx->dim, mem, s, t_q, &d_q));
-    RL_TRY(stage_out_begin(out_scores, (size_t)idx->n_chunks, mem, t_o, &d_o));
+    RL_TRY(st.in(query_vecs, (size_t)nq * idx->dim, &d_q));
+    RL_TRY(st.out(out_scores, (size_t)idx->n_chunks, &d_o));
     RL_TRY(maxsim_scores_device(idx, d_q, nq, d_o, s));
     RL_TRY(mask_chunk_scores(idx, d_o, 1, idx->n_chunks, nullptr, s));  // deleted chunks score -inf
-    RL_TRY(stage_out_end(out_scores, (size_t)idx->n_chunks, mem, s, t_o));
-    return finish(mem, s);
+    return st.finish();
 }
+
+namespace {
+// rl_maxsim_topk_filtered on device pointers: d_s / d_c [k], d_f the chunk filter or nullptr
+int maxsim_topk_one_device(rl_index* idx, const float* d_q, int32_t nq, int32_t k, const uint32_t* d_f, float* d_s, int32_t* d_c, hipStream_t s) {
+    RL_TRY(idx->scores.reserve(std::max<size_t>((size_t)idx->n_chunks * sizeof(float), 16)));
+    const int64_t ld1 = std::max<int64_t>((idx->n_chunks + 3) & ~int64_t(3), 4);
+    if (idx->dim > 1024) {  // a WIDE index: the batch's routes (the bound-filtered pipeline where the index keeps a HI image), batch of one
+        RL_TRY(idx->scores.reserve((size_t)ld1 * sizeof(float)));
+        return maxsim_topk_batch_device(idx, d_q, false, 1, nq, k, idx->scores.as<float>(), ld1, d_s, d_c, s, d_f);
+    }
+    {   // one user query at a time: the half-width route over the HI plane where the index has (or may build) one -- with a metadata filter too
+        // (round 6: the filtered-out chunks rank -inf in the approximate scores, like tombstones)
+        RL_TRY(idx->scores.reserve((size_t)ld1 * sizeof(float)));
+        const int st = maxsim_few_hi_plane(idx, d_q, nq, 1, k, idx->scores.as<float>(), ld1, d_s, d_c, s, d_f);
+        if (st == RL_OK && (idx->live_chunk_bits || d_f)) return launch_fix_masked(d_s, d_c, k, s);
+        if (st != RL_ERR_UNSUPPORTED) return st;
+    }
+    RL_TRY(maxsim_scores_device(idx, d_q, nq, idx->scores.as<float>(), s));
+    const bool masked = d_f || idx->live_chunk_bits;
+    RL_TRY(mask_chunk_scores(idx, idx->scores.as<float>(), 1, idx->n_chunks, d_f, s));
+    RL_TRY(launch_topk(idx->scores.as<float>(), 1, idx->n_chunks, idx->n_chunks, k, idx->ws, d_s, d_c, s));
+    if (masked) RL_TRY(launch_fix_masked(d_s, d_c, k, s));
+    return RL_OK;
+}
+}  // namespace
 
 int rl_maxsim_topk_filtered(rl_index* idx, const float* query_vecs, int32_t nq, int32_t k, const uint32_t* chunk_filter,
                             float* out_scores, int32_t* out_chunks, int mem, void* stream) {
@@ -2232,43 +2092,15 @@ int rl_maxsim_topk_filtered(rl_index* idx, const float* query_vecs, int32_t nq, 
     hipStream_t s = as_stream(stream);
     std::lock_guard<std::mutex> lock(idx->mu);
     RL_TRY(use_scratch(idx, s));
-    DevBuf t_q, t_s, t_c, t_f;
+    Staging st(mem, s);
     const float* d_q; float* d_s; int32_t* d_c;
     const uint32_t* d_f = nullptr;
-    if (chunk_filter) RL_TRY(stage_in(chunk_filter, (size_t)((idx->n_chunks + 31) / 32), mem, s, t_f, &d_f));
-    RL_TRY(stage_in(query_vecs, (size_t)nq * idx->dim, mem, s, t_q, &d_q));
-    RL_TRY(stage_out_begin(out_scores, (size_t)k, mem, t_s, &d_s));
-    RL_TRY(stage_out_begin(out_chunks, (size_t)k, mem, t_c, &d_c));
-    RL_TRY(idx->scores.reserve(std::max<size_t>((size_t)idx->n_chunks * sizeof(float), 16)));
-    if (idx->dim > 1024) {  // a WIDE index: the batch's routes (the bound-filtered pipeline where the index keeps a HI image), batch of one
-        const int64_t ld1 = std::max<int64_t>((idx->n_chunks + 3) & ~int64_t(3), 4);
-        RL_TRY(idx->scores.reserve((size_t)ld1 * sizeof(float)));
-        RL_TRY(maxsim_topk_batch_device(idx, d_q, false, 1, nq, k, idx->scores.as<float>(), ld1, d_s, d_c, s, d_f));
-        RL_TRY(stage_out_end(out_scores, (size_t)k, mem, s, t_s));
-        RL_TRY(stage_out_end(out_chunks, (size_t)k, mem, s, t_c));
-        return finish(mem, s);
-    }
-    {   // one user query at a time: the half-width route over the HI plane where the index has (or may build) one -- with a metadata filter too
-        // (round 6: the filtered-out chunks rank -inf in the approximate scores, like tombstones)
-        const int64_t ld1 = std::max<int64_t>((idx->n_chunks + 3) & ~int64_t(3), 4);
-        RL_TRY(idx->scores.reserve((size_t)ld1 * sizeof(float)));
-        const int st = maxsim_few_hi_plane(idx, d_q, nq, 1, k, idx->scores.as<float>(), ld1, d_s, d_c, s, d_f);
-        if (st == RL_OK) {
-            if (idx->live_chunk_bits || d_f) RL_TRY(launch_fix_masked(d_s, d_c, k, s));
-            RL_TRY(stage_out_end(out_scores, (size_t)k, mem, s, t_s));
-            RL_TRY(stage_out_end(out_chunks, (size_t)k, mem, s, t_c));
-            return finish(mem, s);
-        }
-        if (st != RL_ERR_UNSUPPORTED) return st;
-    }
-    RL_TRY(maxsim_scores_device(idx, d_q, nq, idx->scores.as<float>(), s));
-    const bool masked = d_f || idx->live_chunk_bits;
-    RL_TRY(mask_chunk_scores(idx, idx->scores.as<float>(), 1, idx->n_chunks, d_f, s));
-    RL_TRY(launch_topk(idx->scores.as<float>(), 1, idx->n_chunks, idx->n_chunks, k, idx->ws, d_s, d_c, s));
-    if (masked) RL_TRY(launch_fix_masked(d_s, d_c, k, s));
-    RL_TRY(stage_out_end(out_scores, (size_t)k, mem, s, t_s));
-    RL_TRY(stage_out_end(out_chunks, (size_t)k, mem, s, t_c));
-    return finish(mem, s);
+    if (chunk_filter) RL_TRY(st.in(chunk_filter, (size_t)((idx->n_chunks + 31) / 32), &d_f));
+    RL_TRY(st.in(query_vecs, (size_t)nq * idx->dim, &d_q));
+    RL_TRY(st.out(out_scores, (size_t)k, &d_s));
+    RL_TRY(st.out(out_chunks, (size_t)k, &d_c));
+    RL_TRY(maxsim_topk_one_device(idx, d_q, nq, k, d_f, d_s, d_c, s));
+    return st.finish();
 }
 
 int rl_maxsim_topk(rl_index* idx, const float* query_vecs, int32_t nq, int32_t k, float* out_scores,
@@ -2623,29 +2455,27 @@ static int maxsim_topk_batch_any(rl_index* idx, const void* query_vecs, bool q16
     hipStream_t s = as_stream(stream);
     std::lock_guard<std::mutex> lock(idx->mu);
     RL_TRY(use_scratch(idx, s));
-    DevBuf t_q, t_s, t_c;
+    Staging st(mem, s);
     const float* d_q; float* d_s; int32_t* d_c;
     const size_t q_elems = (size_t)nq * idx->dim;
     if (q16) {
         const uint16_t* d_q16;
-        RL_TRY(stage_in(static_cast<const uint16_t*>(query_vecs), (size_t)n_queries * q_elems, mem, s, t_q, &d_q16));
+        RL_TRY(st.in(static_cast<const uint16_t*>(query_vecs), (size_t)n_queries * q_elems, &d_q16));
         RL_TRY(idx->q32.reserve((size_t)n_queries * q_elems * sizeof(float)));
         const int st_w = launch_widen_f16(d_q16, idx->q32.as<float>(), (int64_t)n_queries * (int64_t)q_elems, s);
         if (st_w == RL_ERR_UNSUPPORTED) return fail(RL_ERR_INVALID, "rl_maxsim_topk_batch_f16: query_vecs_f16 must be 2-byte aligned");
         RL_TRY(st_w);  // (a launch failure stays what it is)
         d_q = idx->q32.as<float>();
     } else {
-        RL_TRY(stage_in(static_cast<const float*>(query_vecs), (size_t)n_queries * q_elems, mem, s, t_q, &d_q));
+        RL_TRY(st.in(static_cast<const float*>(query_vecs), (size_t)n_queries * q_elems, &d_q));
     }
-    RL_TRY(stage_out_begin(out_scores, (size_t)n_queries * k, mem, t_s, &d_s));
-    RL_TRY(stage_out_begin(out_chunks, (size_t)n_queries * k, mem, t_c, &d_c));
+    RL_TRY(st.out(out_scores, (size_t)n_queries * k, &d_s));
+    RL_TRY(st.out(out_chunks, (size_t)n_queries * k, &d_c));
     const int64_t ld = std::max<int64_t>((idx->n_chunks + 3) & ~int64_t(3), 4);
     RL_TRY(idx->scores.reserve((size_t)n_queries * ld * sizeof(float)));
     float* sc = idx->scores.as<float>();
     RL_TRY(maxsim_topk_batch_device(idx, d_q, q16, n_queries, nq, k, sc, ld, d_s, d_c, s));
-    RL_TRY(stage_out_end(out_scores, (size_t)n_queries * k, mem, s, t_s));
-    RL_TRY(stage_out_end(out_chunks, (size_t)n_queries * k, mem, s, t_c));
-    return finish(mem, s);
+    return st.finish();
 }
 
 int rl_maxsim_topk_batch(rl_index* idx, const float* query_vecs, int32_t n_queries, int32_t nq, int32_t k,
@@ -2673,11 +2503,11 @@ int rl_maxsim_batch_begin(rl_index* idx, const float* query_vecs, int32_t n_quer
     const bool whole = n_queries % GEMM_PASS_QUERIES == 0 || n_queries % GEMM_PASS_QUERIES >= gemm_min_queries(idx);
     if (hi_off || !whole || n_queries < gemm_min_queries(idx) || k > 512 || nq > 32)
         return fail(RL_ERR_UNSUPPORTED, "rl_maxsim_batch_begin: needs >= 3 queries (n % 8 == 0 or n % 8 >= 3), nq <= 32 and k <= 512");
-    DevBuf t_q, t_o;
+    Staging st(mem, s);
     const float* d_q; float* d_o;
     const size_t q_elems = (size_t)nq * idx->dim;
-    RL_TRY(stage_in(query_vecs, (size_t)n_queries * q_elems, mem, s, t_q, &d_q));
-    RL_TRY(stage_out_begin(out_approx, (size_t)n_queries * (k + 1), mem, t_o, &d_o));
+    RL_TRY(st.in(query_vecs, (size_t)n_queries * q_elems, &d_q));
+    RL_TRY(st.out(out_approx, (size_t)n_queries * (k + 1), &d_o));
     const int64_t ld = std::max<int64_t>((idx->n_chunks + 3) & ~int64_t(3), 4);
     RL_TRY(idx->scores.reserve((size_t)n_queries * ld * sizeof(float)));
     float* sc = idx->scores.as<float>();
@@ -2699,8 +2529,7 @@ int rl_maxsim_batch_begin(rl_index* idx, const float* query_vecs, int32_t n_quer
     idx->mb_nq = nq;
     idx->mb_k = k;
     idx->mb_epoch = idx->scratch_epoch;
-    RL_TRY(stage_out_end(out_approx, (size_t)n_queries * (k + 1), mem, s, t_o));
-    return finish(mem, s);
+    return st.finish();
 }
 
 int rl_maxsim_batch_finish(rl_index* idx, const float* query_vecs, const float* all_approx, int32_t world, int32_t rank, float* out_scores,
@@ -2718,13 +2547,13 @@ int rl_maxsim_batch_finish(rl_index* idx, const float* query_vecs, const float* 
     }
     const int32_t n_queries = idx->mb_B, nq = idx->mb_nq, k = idx->mb_k;
     idx->mb_B = 0;
-    DevBuf t_q, t_a, t_s, t_c;
+    Staging st(mem, s);
     const float* d_q; const float* d_a; float* d_s; int32_t* d_c;
     const size_t q_elems = (size_t)nq * idx->dim;
-    RL_TRY(stage_in(query_vecs, (size_t)n_queries * q_elems, mem, s, t_q, &d_q));
-    RL_TRY(stage_in(all_approx, (size_t)world * n_queries * (k + 1), mem, s, t_a, &d_a));
-    RL_TRY(stage_out_begin(out_scores, (size_t)n_queries * k, mem, t_s, &d_s));
-    RL_TRY(stage_out_begin(out_chunks, (size_t)n_queries * k, mem, t_c, &d_c));
+    RL_TRY(st.in(query_vecs, (size_t)n_queries * q_elems, &d_q));
+    RL_TRY(st.in(all_approx, (size_t)world * n_queries * (k + 1), &d_a));
+    RL_TRY(st.out(out_scores, (size_t)n_queries * k, &d_s));
+    RL_TRY(st.out(out_chunks, (size_t)n_queries * k, &d_c));
     const int64_t ld = std::max<int64_t>((idx->n_chunks + 3) & ~int64_t(3), 4);
     float* sc = idx->scores.as<float>();
     HiBatch hb;  // the layout of rl_maxsim_batch_begin (same sizes: nothing is reallocated, the approximate scores are still in `sc`)
@@ -2736,9 +2565,7 @@ int rl_maxsim_batch_finish(rl_index* idx, const float* query_vecs, const float* 
     RL_TRY(launch_global_threshold(d_a, world, n_queries, k, rank, hb.thr, hb.cnt, hb.flag, s));
     RL_TRY(hi_batch_rescore(idx, d_q, nq, n_queries, n_queries, k, sc, ld, hb, d_s, d_c, s));
     if (idx->live_chunk_bits) RL_TRY(launch_fix_masked(d_s, d_c, (int64_t)n_queries * k, s));
-    RL_TRY(stage_out_end(out_scores, (size_t)n_queries * k, mem, s, t_s));
-    RL_TRY(stage_out_end(out_chunks, (size_t)n_queries * k, mem, s, t_c));
-    return finish(mem, s);
+    return st.finish();
 }
 
 int rl_maxsim_approx_scores(rl_index* idx, const float* query_vecs, int32_t n_queries, int32_t nq, int kernel, float* out_scores,
@@ -2756,13 +2583,13 @@ int rl_maxsim_approx_scores(rl_index* idx, const float* query_vecs, int32_t n_qu
     RL_TRY(demand_images(idx, approx_image_bit(idx), s));
     if (!approx_image_valid(idx) || nq > 32 || (kernel == 0 && idx->dim < 256))
         return fail(RL_ERR_UNSUPPORTED, "rl_maxsim_approx_scores: this index keeps no HI image (or nq > 32 / dim < 256)");
-    DevBuf t_q, t_o, t_b;
+    Staging st(mem, s);
     const float* d_q; float* d_o; float* d_b = nullptr;
     const size_t q_elems = (size_t)nq * idx->dim;
     const int64_t ld = idx->n_chunks;
-    RL_TRY(stage_in(query_vecs, (size_t)n_queries * q_elems, mem, s, t_q, &d_q));
-    RL_TRY(stage_out_begin(out_scores, (size_t)n_queries * ld, mem, t_o, &d_o));
-    if (out_bound) RL_TRY(stage_out_begin(out_bound, (size_t)n_queries, mem, t_b, &d_b));
+    RL_TRY(st.in(query_vecs, (size_t)n_queries * q_elems, &d_q));
+    RL_TRY(st.out(out_scores, (size_t)n_queries * ld, &d_o));
+    RL_TRY(st.out(out_bound, (size_t)n_queries, &d_b));  // (optional)
     RL_TRY(idx->qplanes.reserve(query_planes_bytes(idx->dim, n_queries)));
     RL_TRY(launch_query_planes(d_q, idx->dim, nq, (int64_t)q_elems, n_queries, idx->qplanes.p, s));
     const int32_t per = kernel == 0 ? n_queries : GEMM_PASS_QUERIES;  // (the sixteen-query kernel takes all its passes in one launch)
@@ -2791,9 +2618,7 @@ int rl_maxsim_approx_scores(rl_index* idx, const float* query_vecs, int32_t n_qu
         RL_TRY(launch_scale_f32(thr, d_b, -0.5f, n_queries, s));                // thr = -2 m  ->  m
         idx->filt = {};
     }
-    RL_TRY(stage_out_end(out_scores, (size_t)n_queries * ld, mem, s, t_o));
-    if (out_bound) RL_TRY(stage_out_end(out_bound, (size_t)n_queries, mem, s, t_b));
-    return finish(mem, s);
+    return st.finish();
 }
 
 }  // extern "C"
@@ -2840,14 +2665,13 @@ int rl_maxsim_rerank(rl_index* idx, const float* query_vecs, int32_t n_queries, 
     hipStream_t s = as_stream(stream);
     std::lock_guard<std::mutex> lock(idx->mu);
     RL_TRY(use_scratch(idx, s));
-    DevBuf t_q, t_c, t_o;
+    Staging st(mem, s);
     const float* d_q; const int32_t* d_c; float* d_o;
-    RL_TRY(stage_in(query_vecs, (size_t)n_queries * nq * idx->dim, mem, s, t_q, &d_q));
-    RL_TRY(stage_in(candidates, (size_t)n_queries * n_cand, mem, s, t_c, &d_c));
-    RL_TRY(stage_out_begin(out_scores, (size_t)n_queries * n_cand, mem, t_o, &d_o));
+    RL_TRY(st.in(query_vecs, (size_t)n_queries * nq * idx->dim, &d_q));
+    RL_TRY(st.in(candidates, (size_t)n_queries * n_cand, &d_c));
+    RL_TRY(st.out(out_scores, (size_t)n_queries * n_cand, &d_o));
     RL_TRY(maxsim_rerank_device(idx, d_q, n_queries, nq, d_c, n_cand, d_o, s));
-    RL_TRY(stage_out_end(out_scores, (size_t)n_queries * n_cand, mem, s, t_o));
-    return finish(mem, s);
+    return st.finish();
 }
 
 // ---- section 8e + generic selection ----------------------------------------------------------------------
@@ -2859,16 +2683,14 @@ int rl_merge_topk(const float* in_scores, const int32_t* in_ids, int32_t n_lists
     if (!in_scores || !in_ids || !out_scores || !out_ids) return fail(RL_ERR_INVALID, "rl_merge_topk: null argument");
     hipStream_t s = as_stream(stream);
     const size_t n_in = (size_t)n_lists * n_queries * k_in, n_out = (size_t)n_queries * k;
-    DevBuf t_is, t_ii, t_os, t_oi;
+    Staging st(mem, s);
     const float* d_is; const int32_t* d_ii; float* d_os; int32_t* d_oi;
-    RL_TRY(stage_in(in_scores, n_in, mem, s, t_is, &d_is));
-    RL_TRY(stage_in(in_ids, n_in, mem, s, t_ii, &d_ii));
-    RL_TRY(stage_out_begin(out_scores, n_out, mem, t_os, &d_os));
-    RL_TRY(stage_out_begin(out_ids, n_out, mem, t_oi, &d_oi));
+    RL_TRY(st.in(in_scores, n_in, &d_is));
+    RL_TRY(st.in(in_ids, n_in, &d_ii));
+    RL_TRY(st.out(out_scores, n_out, &d_os));
+    RL_TRY(st.out(out_ids, n_out, &d_oi));
     RL_TRY(launch_merge_topk(d_is, d_ii, n_lists, n_queries, k_in, k, d_os, d_oi, s));
-    RL_TRY(stage_out_end(out_scores, n_out, mem, s, t_os));
-    RL_TRY(stage_out_end(out_ids, n_out, mem, s, t_oi));
-    return finish(mem, s);
+    return st.finish();
 }
 
 int rl_topk(const float* scores, int32_t n_queries, int64_t n, int64_t ld, int32_t k, float* out_scores,
@@ -2879,22 +2701,20 @@ int rl_topk(const float* scores, int32_t n_queries, int64_t n, int64_t ld, int32
     if ((n > 0 && !scores) || !out_scores || !out_ids) return fail(RL_ERR_INVALID, "rl_topk: null argument");
     hipStream_t s = as_stream(stream);
     const size_t n_in = (size_t)n_queries * ld, n_out = (size_t)n_queries * k;
-    DevBuf t_in, t_os, t_oi;
+    Staging st(mem, s);
     const float* d_in; float* d_os; int32_t* d_oi;
-    RL_TRY(stage_in(scores, n_in, mem, s, t_in, &d_in));
-    RL_TRY(stage_out_begin(out_scores, n_out, mem, t_os, &d_os));
-    RL_TRY(stage_out_begin(out_ids, n_out, mem, t_oi, &d_oi));
+    RL_TRY(st.in(scores, n_in, &d_in));
+    RL_TRY(st.out(out_scores, n_out, &d_os));
+    RL_TRY(st.out(out_ids, n_out, &d_oi));
     SelectWorkspace ws;  // one-off workspace: this entry point is for tests / external scorers
     {
         std::lock_guard<std::mutex> lock(g_default_opts_mu);
         ws.block_route = (int)g_default_opts.v[RL_OPT_TOPK_BLOCK];
     }
-    int st = launch_topk(d_in, n_queries, n, ld, k, ws, d_os, d_oi, s);
-    if (st == RL_OK) st = stage_out_end(out_scores, n_out, mem, s, t_os);
-    if (st == RL_OK) st = stage_out_end(out_ids, n_out, mem, s, t_oi);
-    const int sy = sync_and_drain(s);  // the workspace is freed below; bounced results reach the caller here
+    const int rc = launch_topk(d_in, n_queries, n, ld, k, ws, d_os, d_oi, s);
+    const int sy = rc == RL_OK ? st.finish_synced() : st.sync();  // the workspace is freed below, after an error too
     select_workspace_free(ws);
-    return st == RL_OK ? sy : st;
+    return rc == RL_OK ? sy : rc;
 }
 
 // ---- document-batched ingestion: similarities, chunk / chunklet / sentence partitions (kernels in partition_sim.hip, partition_dp.hip,
@@ -2913,28 +2733,6 @@ static int check_doc_offsets(const char* who, const int64_t* off, int64_t n, int
     return RL_OK;
 }
 
-// The three outputs of a partition call (cut per row; objective, optional, and status per document), staged out and back.
-struct PartitionOut {
-    DevBuf t_cut, t_obj, t_status;
-    uint8_t *h_cut, *cut = nullptr;
-    double *h_obj, *objective = nullptr;
-    int32_t *h_status, *status = nullptr;
-    size_t n, n_docs;
-    int mem;
-    PartitionOut(uint8_t* cut_, double* obj_, int32_t* status_, int64_t n_, int64_t n_docs_, int mem_)
-        : h_cut(cut_), h_obj(obj_), h_status(status_), n((size_t)n_), n_docs((size_t)n_docs_), mem(mem_) {}
-    int begin() {
-        RL_TRY(stage_out_begin(h_cut, n, mem, t_cut, &cut));
-        RL_TRY(stage_out_begin(h_obj, n_docs, mem, t_obj, &objective));
-        return stage_out_begin(h_status, n_docs, mem, t_status, &status);
-    }
-    int end(hipStream_t s) {
-        RL_TRY(stage_out_end(h_cut, n, mem, s, t_cut));
-        RL_TRY(stage_out_end(h_obj, n_docs, mem, s, t_obj));
-        return stage_out_end(h_status, n_docs, mem, s, t_status);
-    }
-};
-
 int rl_partition_similarity(const float* X, int64_t n, int32_t dim, const int64_t* doc_offsets, int64_t n_docs,
                             const uint8_t* nonoutlying, float* out, int mem, void* stream) {
     if (n < 0 || dim <= 0) return fail(RL_ERR_INVALID, "rl_partition_similarity: bad shape");
@@ -2945,24 +2743,18 @@ int rl_partition_similarity(const float* X, int64_t n, int32_t dim, const int64_
     if (n_docs < 1) return fail(RL_ERR_INVALID, "rl_partition_similarity: need at least one document");
     if (doc_offsets) RL_TRY(check_doc_offsets("rl_partition_similarity", doc_offsets, n, n_docs, mem, 0));
     hipStream_t s = as_stream(stream);
-    DevBuf t_x, t_off, t_sel, t_out, t_scr, t_one;
+    Staging st(mem, s);
     const float* d_x; const int64_t* d_off; const uint8_t* d_sel = nullptr; float* d_out;
-    RL_TRY(stage_in(X, (size_t)n * dim, mem, s, t_x, &d_x));
-    if (doc_offsets) {
-        RL_TRY(stage_in(doc_offsets, (size_t)n_docs + 1, mem, s, t_off, &d_off));
-    } else {
-        const int64_t one[2] = {0, n};
-        RL_TRY(t_one.alloc(sizeof(one)));
-        RL_HIP(hipMemcpyAsync(t_one.p, one, sizeof(one), hipMemcpyHostToDevice, s));
-        RL_HIP(hipStreamSynchronize(s));  // `one` lives on this stack frame
-        d_off = t_one.as<int64_t>();
-    }
-    if (nonoutlying) RL_TRY(stage_in(nonoutlying, (size_t)n, mem, s, t_sel, &d_sel));
-    RL_TRY(stage_out_begin(out, (size_t)n, mem, t_out, &d_out));
-    RL_TRY(t_scr.alloc(partition_sim_scratch_bytes(n, n_docs, dim)));
-    RL_TRY(launch_partition_similarity(d_x, n, dim, d_off, n_docs, d_sel, d_out, t_scr.p, s));
-    RL_TRY(stage_out_end(out, (size_t)n, mem, s, t_out));
-    return sync_and_drain(s);  // the scratch dies with this frame
+    RL_TRY(st.in(X, (size_t)n * dim, &d_x));
+    const int64_t one[2] = {0, n};  // one document: offsets made here (outlives the copy: the call ends synchronised)
+    if (doc_offsets) RL_TRY(st.in(doc_offsets, (size_t)n_docs + 1, &d_off));
+    else RL_TRY(st.in(one, 2, &d_off, RL_MEM_HOST));
+    if (nonoutlying) RL_TRY(st.in(nonoutlying, (size_t)n, &d_sel));
+    RL_TRY(st.out(out, (size_t)n, &d_out));
+    void* d_scr;
+    RL_TRY(st.temp(partition_sim_scratch_bytes(n, n_docs, dim), &d_scr));
+    RL_TRY(launch_partition_similarity(d_x, n, dim, d_off, n_docs, d_sel, d_out, d_scr, s));
+    return st.finish();
 }
 
 // Argument checks shared by rl_partition_chunks, rl_split_chunks and rl_partition_chunklets; all of them return before the first HIP call.
@@ -2991,17 +2783,19 @@ int rl_partition_chunks(const float* cost, const int64_t* sizes, const int64_t* 
     if (!cost) return fail(RL_ERR_INVALID, "rl_partition_chunks: cost is null");
     RL_TRY(partition_args("rl_partition_chunks", sizes, doc_offsets, n, n_docs, cut, status, mem));
     hipStream_t s = as_stream(stream);
-    DevBuf t_c, t_sz, t_off, t_scr;
-    PartitionOut o(cut, objective, status, n, n_docs, mem);
+    Staging st(mem, s);
     const float* d_c; const int64_t* d_sz; const int64_t* d_off;
-    RL_TRY(stage_in(cost, (size_t)n, mem, s, t_c, &d_c));
-    RL_TRY(stage_in(sizes, (size_t)n, mem, s, t_sz, &d_sz));
-    RL_TRY(stage_in(doc_offsets, (size_t)n_docs + 1, mem, s, t_off, &d_off));
-    RL_TRY(o.begin());
-    RL_TRY(t_scr.alloc(partition_dp_scratch_bytes(n)));
-    RL_TRY(launch_partition_dp(d_c, d_sz, nullptr, d_off, n, n_docs, max_size, o.cut, o.objective, o.status, t_scr.p, s));
-    RL_TRY(o.end(s));
-    return sync_and_drain(s);  // the scratch dies with this frame
+    RL_TRY(st.in(cost, (size_t)n, &d_c));
+    RL_TRY(st.in(sizes, (size_t)n, &d_sz));
+    RL_TRY(st.in(doc_offsets, (size_t)n_docs + 1, &d_off));
+    uint8_t* d_cut; double* d_obj; int32_t* d_status;
+    RL_TRY(st.out(cut, (size_t)n, &d_cut));
+    RL_TRY(st.out(objective, (size_t)n_docs, &d_obj));  // (optional)
+    RL_TRY(st.out(status, (size_t)n_docs, &d_status));
+    void* d_scr;
+    RL_TRY(st.temp(partition_dp_scratch_bytes(n), &d_scr));
+    RL_TRY(launch_partition_dp(d_c, d_sz, nullptr, d_off, n, n_docs, max_size, d_cut, d_obj, d_status, d_scr, s));
+    return st.finish();
 }
 
 int rl_split_chunks(const float* X, int64_t n, int32_t dim, const int64_t* doc_offsets, int64_t n_docs, const uint8_t* nonoutlying,
@@ -3015,31 +2809,28 @@ int rl_split_chunks(const float* X, int64_t n, int32_t dim, const int64_t* doc_o
     RL_TRY(partition_args("rl_split_chunks", sizes, doc_offsets, n, n_docs, cut, status, mem));
     if (dim > 4096) return fail(RL_ERR_UNSUPPORTED, "rl_split_chunks: dim must be <= 4096");
     hipStream_t s = as_stream(stream);
-    DevBuf t_x, t_sz, t_off, t_sel, t_head, t_cost, t_scr, t_dp;
-    PartitionOut o(cut, objective, status, n, n_docs, mem);
+    Staging st(mem, s);
     const float* d_x; const int64_t* d_sz; const int64_t* d_off; const uint8_t* d_sel = nullptr; const uint8_t* d_head = nullptr;
     float* d_cost;
-    RL_TRY(stage_in(X, (size_t)n * dim, mem, s, t_x, &d_x));
-    RL_TRY(stage_in(sizes, (size_t)n, mem, s, t_sz, &d_sz));
-    RL_TRY(stage_in(doc_offsets, (size_t)n_docs + 1, mem, s, t_off, &d_off));
-    if (nonoutlying) RL_TRY(stage_in(nonoutlying, (size_t)n, mem, s, t_sel, &d_sel));
-    if (is_heading) RL_TRY(stage_in(is_heading, (size_t)n, mem, s, t_head, &d_head));
-    RL_TRY(o.begin());
-    if (cost_out) {
-        RL_TRY(stage_out_begin(cost_out, (size_t)n, mem, t_cost, &d_cost));
-    } else {
-        RL_TRY(t_cost.alloc((size_t)n * sizeof(float)));
-        d_cost = t_cost.as<float>();
-    }
-    RL_TRY(t_scr.alloc(partition_sim_scratch_bytes(n, n_docs, dim)));
-    RL_TRY(t_dp.alloc(partition_dp_scratch_bytes(n)));
-    RL_TRY(launch_partition_similarity(d_x, n, dim, d_off, n_docs, d_sel, d_cost, t_scr.p, s));
+    RL_TRY(st.in(X, (size_t)n * dim, &d_x));
+    RL_TRY(st.in(sizes, (size_t)n, &d_sz));
+    RL_TRY(st.in(doc_offsets, (size_t)n_docs + 1, &d_off));
+    if (nonoutlying) RL_TRY(st.in(nonoutlying, (size_t)n, &d_sel));
+    if (is_heading) RL_TRY(st.in(is_heading, (size_t)n, &d_head));
+    uint8_t* d_cut; double* d_obj; int32_t* d_status;
+    RL_TRY(st.out(cut, (size_t)n, &d_cut));
+    RL_TRY(st.out(objective, (size_t)n_docs, &d_obj));  // (optional)
+    RL_TRY(st.out(status, (size_t)n_docs, &d_status));
+    RL_TRY(st.out_or_temp(cost_out, (size_t)n, &d_cost));
+    void* d_scr;
+    RL_TRY(st.temp(partition_sim_scratch_bytes(n, n_docs, dim), &d_scr));
+    void* d_dp;
+    RL_TRY(st.temp(partition_dp_scratch_bytes(n), &d_dp));
+    RL_TRY(launch_partition_similarity(d_x, n, dim, d_off, n_docs, d_sel, d_cost, d_scr, s));
     if (d_head) RL_TRY(launch_partition_headings(d_cost, d_head, d_off, n_docs, n, s));  // in place: entry i reads sim[i] alone
-    RL_TRY(launch_partition_dp(d_cost, d_sz, t_scr.as<float>() /* 1 / |x_i| */, d_off, n, n_docs, max_size, o.cut, o.objective, o.status,
-                               t_dp.p, s));
-    RL_TRY(o.end(s));
-    if (cost_out) RL_TRY(stage_out_end(cost_out, (size_t)n, mem, s, t_cost));  // independent copies: their order does not matter
-    return sync_and_drain(s);  // the scratch dies with this frame
+    RL_TRY(launch_partition_dp(d_cost, d_sz, static_cast<float*>(d_scr) /* 1 / |x_i| */, d_off, n, n_docs, max_size, d_cut, d_obj, d_status,
+                               d_dp, s));
+    return st.finish();
 }
 
 int rl_partition_chunklets(const double* boundary, const double* statements, const int64_t* lengths, const int64_t* doc_offsets, int64_t n,
@@ -3052,18 +2843,20 @@ int rl_partition_chunklets(const double* boundary, const double* statements, con
     if (!statements) return fail(RL_ERR_INVALID, "rl_partition_chunklets: statements is null");
     RL_TRY(partition_args("rl_partition_chunklets", lengths, doc_offsets, n, n_docs, cut, status, mem));
     hipStream_t s = as_stream(stream);
-    DevBuf t_b, t_st, t_len, t_off, t_scr;
-    PartitionOut o(cut, objective, status, n, n_docs, mem);
+    Staging st(mem, s);
     const double* d_b; const double* d_s; const int64_t* d_len; const int64_t* d_off;
-    RL_TRY(stage_in(boundary, (size_t)n, mem, s, t_b, &d_b));
-    RL_TRY(stage_in(statements, (size_t)n, mem, s, t_st, &d_s));
-    RL_TRY(stage_in(lengths, (size_t)n, mem, s, t_len, &d_len));
-    RL_TRY(stage_in(doc_offsets, (size_t)n_docs + 1, mem, s, t_off, &d_off));
-    RL_TRY(o.begin());
-    RL_TRY(t_scr.alloc(chunklet_dp_scratch_bytes(n, n_docs)));
-    RL_TRY(launch_chunklet_dp(d_b, d_s, d_len, d_off, n, n_docs, max_size, o.cut, o.objective, o.status, t_scr.p, s));
-    RL_TRY(o.end(s));
-    return sync_and_drain(s);  // the scratch dies with this frame
+    RL_TRY(st.in(boundary, (size_t)n, &d_b));
+    RL_TRY(st.in(statements, (size_t)n, &d_s));
+    RL_TRY(st.in(lengths, (size_t)n, &d_len));
+    RL_TRY(st.in(doc_offsets, (size_t)n_docs + 1, &d_off));
+    uint8_t* d_cut; double* d_obj; int32_t* d_status;
+    RL_TRY(st.out(cut, (size_t)n, &d_cut));
+    RL_TRY(st.out(objective, (size_t)n_docs, &d_obj));  // (optional)
+    RL_TRY(st.out(status, (size_t)n_docs, &d_status));
+    void* d_scr;
+    RL_TRY(st.temp(chunklet_dp_scratch_bytes(n, n_docs), &d_scr));
+    RL_TRY(launch_chunklet_dp(d_b, d_s, d_len, d_off, n, n_docs, max_size, d_cut, d_obj, d_status, d_scr, s));
+    return st.finish();
 }
 
 int rl_partition_sentences(const uint32_t* codepoints, const void* probas, int probas_f64, const double* known, const int64_t* doc_offsets,
@@ -3084,18 +2877,20 @@ int rl_partition_sentences(const uint32_t* codepoints, const void* probas, int p
     if (n_docs == 1 && n >= doc_max) return fail(RL_ERR_INVALID, "rl_partition_sentences: a document must be shorter than 2^31 characters");
     RL_TRY(check_doc_offsets("rl_partition_sentences", doc_offsets, n, n_docs, mem, doc_max));
     hipStream_t s = as_stream(stream);
-    DevBuf t_cp, t_p, t_k, t_off, t_scr;
-    PartitionOut o(cut, objective, status, n, n_docs, mem);
+    Staging st(mem, s);
     const uint32_t* d_cp; const uint8_t* d_p; const double* d_k = nullptr; const int64_t* d_off;
-    RL_TRY(stage_in(codepoints, (size_t)n, mem, s, t_cp, &d_cp));
-    RL_TRY(stage_in(static_cast<const uint8_t*>(probas), (size_t)n * (probas_f64 ? 8 : 4), mem, s, t_p, &d_p));
-    if (known) RL_TRY(stage_in(known, (size_t)n, mem, s, t_k, &d_k));
-    RL_TRY(stage_in(doc_offsets, (size_t)n_docs + 1, mem, s, t_off, &d_off));
-    RL_TRY(o.begin());
-    RL_TRY(t_scr.alloc(sentence_dp_scratch_bytes(n, n_docs)));
-    RL_TRY(launch_sentence_dp(d_cp, d_p, probas_f64, d_k, d_off, n, n_docs, min_len, max_len, o.cut, o.objective, o.status, t_scr.p, s));
-    RL_TRY(o.end(s));
-    return sync_and_drain(s);  // the scratch dies with this frame
+    RL_TRY(st.in(codepoints, (size_t)n, &d_cp));
+    RL_TRY(st.in(static_cast<const uint8_t*>(probas), (size_t)n * (probas_f64 ? 8 : 4), &d_p));
+    if (known) RL_TRY(st.in(known, (size_t)n, &d_k));
+    RL_TRY(st.in(doc_offsets, (size_t)n_docs + 1, &d_off));
+    uint8_t* d_cut; double* d_obj; int32_t* d_status;
+    RL_TRY(st.out(cut, (size_t)n, &d_cut));
+    RL_TRY(st.out(objective, (size_t)n_docs, &d_obj));  // (optional)
+    RL_TRY(st.out(status, (size_t)n_docs, &d_status));
+    void* d_scr;
+    RL_TRY(st.temp(sentence_dp_scratch_bytes(n, n_docs), &d_scr));
+    RL_TRY(launch_sentence_dp(d_cp, d_p, probas_f64, d_k, d_off, n, n_docs, min_len, max_len, d_cut, d_obj, d_status, d_scr, s));
+    return st.finish();
 }
 
 // ---- query adapter fit (kernels in adapter_fit.hip and query_targets.hip) ---------------------------------------------------------------
@@ -3108,15 +2903,14 @@ int rl_chunk_best_rows(rl_index* idx, const float* queries, int32_t B, const int
     hipStream_t s = as_stream(stream);
     std::lock_guard<std::mutex> lock(idx->mu);
     RL_TRY(use_scratch(idx, s));
-    DevBuf t_q, t_c, t_o;
+    Staging st(mem, s);
     const float* d_q; const int32_t* d_c; int32_t* d_o;
-    RL_TRY(stage_in(queries, (size_t)B * idx->dim, mem, s, t_q, &d_q));
-    RL_TRY(stage_in(candidates, (size_t)B * n_cand, mem, s, t_c, &d_c));
-    RL_TRY(stage_out_begin(out_rows, (size_t)B * n_cand, mem, t_o, &d_o));
+    RL_TRY(st.in(queries, (size_t)B * idx->dim, &d_q));
+    RL_TRY(st.in(candidates, (size_t)B * n_cand, &d_c));
+    RL_TRY(st.out(out_rows, (size_t)B * n_cand, &d_o));
     RL_TRY(launch_chunk_best_rows(idx->E16 ? (const void*)idx->E16 : (const void*)idx->E, idx->E16 != nullptr, idx->dim,
                                   d_q, idx->offsets, idx->n_chunks, d_c, n_cand, (int64_t)B * n_cand, d_o, s));
-    RL_TRY(stage_out_end(out_rows, (size_t)B * n_cand, mem, s, t_o));
-    return finish(mem, s);
+    return st.finish();
 }
 
 int rl_gather_rows(rl_index* idx, const int32_t* rows, int64_t n, float* out, int mem, void* stream) {
@@ -3127,14 +2921,13 @@ int rl_gather_rows(rl_index* idx, const int32_t* rows, int64_t n, float* out, in
     hipStream_t s = as_stream(stream);
     std::lock_guard<std::mutex> lock(idx->mu);
     RL_TRY(use_scratch(idx, s));
-    DevBuf t_r, t_o;
+    Staging st(mem, s);
     const int32_t* d_r; float* d_o;
-    RL_TRY(stage_in(rows, (size_t)n, mem, s, t_r, &d_r));
-    RL_TRY(stage_out_begin(out, (size_t)n * idx->dim, mem, t_o, &d_o));
+    RL_TRY(st.in(rows, (size_t)n, &d_r));
+    RL_TRY(st.out(out, (size_t)n * idx->dim, &d_o));
     RL_TRY(launch_gather_rows(idx->E16 ? (const void*)idx->E16 : (const void*)idx->E, idx->E16 != nullptr, idx->dim,
                               idx->n_rows, d_r, n, d_o, s));
-    RL_TRY(stage_out_end(out, (size_t)n * idx->dim, mem, s, t_o));
-    return finish(mem, s);
+    return st.finish();
 }
 
 int rl_query_targets(rl_index* idx, const float* queries, int32_t B, const int32_t* rows, const uint8_t* relevant, int32_t k, double gap,
@@ -3156,25 +2949,21 @@ int rl_query_targets(rl_index* idx, const float* queries, int32_t B, const int32
     std::lock_guard<std::mutex> lock(idx->mu);
     RL_TRY(use_scratch(idx, s));
     const size_t dim = (size_t)idx->dim, n = (size_t)B * k;
-    DevBuf t_q, t_r, t_rel, t_t, t_w, t_o, t_st, t_it, t_scr;
+    Staging st(mem, s);
     const float* d_q; const int32_t* d_r; const uint8_t* d_rel; double* d_t; double* d_w; double* d_o; int32_t* d_st; int32_t* d_it;
-    RL_TRY(stage_in(queries, (size_t)B * dim, mem, s, t_q, &d_q));
-    RL_TRY(stage_in(rows, n, mem, s, t_r, &d_r));
-    RL_TRY(stage_in(relevant, n, mem, s, t_rel, &d_rel));
-    RL_TRY(stage_out_begin(targets, (size_t)B * dim, mem, t_t, &d_t));
-    RL_TRY(stage_out_begin(weights, n, mem, t_w, &d_w));
-    RL_TRY(stage_out_begin(objective, (size_t)B, mem, t_o, &d_o));
-    RL_TRY(stage_out_begin(status, (size_t)B, mem, t_st, &d_st));
-    RL_TRY(stage_out_begin(iterations, (size_t)B, mem, t_it, &d_it));
-    RL_TRY(t_scr.alloc(query_targets_scratch_bytes(B, k)));
+    RL_TRY(st.in(queries, (size_t)B * dim, &d_q));
+    RL_TRY(st.in(rows, n, &d_r));
+    RL_TRY(st.in(relevant, n, &d_rel));
+    RL_TRY(st.out(targets, (size_t)B * dim, &d_t));
+    RL_TRY(st.out(weights, n, &d_w));
+    RL_TRY(st.out(objective, (size_t)B, &d_o));
+    RL_TRY(st.out(status, (size_t)B, &d_st));
+    RL_TRY(st.out(iterations, (size_t)B, &d_it));
+    void* d_scr;
+    RL_TRY(st.temp(query_targets_scratch_bytes(B, k), &d_scr));
     RL_TRY(launch_query_targets(idx->E16 ? (const void*)idx->E16 : (const void*)idx->E, idx->E16 != nullptr, idx->dim, idx->n_rows, d_q, B,
-                                d_r, d_rel, k, gap, d_t, d_w, d_o, d_st, d_it, t_scr.p, s));
-    RL_TRY(stage_out_end(targets, (size_t)B * dim, mem, s, t_t));
-    RL_TRY(stage_out_end(weights, n, mem, s, t_w));
-    RL_TRY(stage_out_end(objective, (size_t)B, mem, s, t_o));
-    RL_TRY(stage_out_end(status, (size_t)B, mem, s, t_st));
-    RL_TRY(stage_out_end(iterations, (size_t)B, mem, s, t_it));
-    return sync_and_drain(s);  // the scratch dies with this frame
+                                d_r, d_rel, k, gap, d_t, d_w, d_o, d_st, d_it, d_scr, s));
+    return st.finish();
 }
 
 // ---- timing hook for bench.py ------------------------------------------------------------------------------
@@ -3444,16 +3233,15 @@ int rl_keyword_index_create(rl_keyword_index** out, const int64_t* term_off, int
     RL_HIP(hipMemcpyAsync(kw->term_off, term_off, (size_t)(n_terms + 1) * sizeof(int64_t),
                           mem == RL_MEM_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, s));
     if (np) RL_HIP(hipMemcpyAsync(kw->post_chunk, post_chunk, np * sizeof(int32_t), mem == RL_MEM_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, s));
-    DevBuf t_tf, t_term, t_idf, t_nrm;
+    Staging st(mem, s);
     const int32_t *d_tf, *d_term;
     const float *d_idf, *d_nrm;
-    RL_TRY(stage_in(post_tf, np, mem, s, t_tf, &d_tf));
-    RL_TRY(stage_in(post_term, np, mem, s, t_term, &d_term));
-    RL_TRY(stage_in(idf, (size_t)n_terms, mem, s, t_idf, &d_idf));
-    RL_TRY(stage_in(nrm, (size_t)n_chunks, mem, s, t_nrm, &d_nrm));
+    RL_TRY(st.in(post_tf, np, &d_tf));
+    RL_TRY(st.in(post_term, np, &d_term));
+    RL_TRY(st.in(idf, (size_t)n_terms, &d_idf));
+    RL_TRY(st.in(nrm, (size_t)n_chunks, &d_nrm));
     RL_TRY(launch_bm25_impact(kw->post_chunk, d_tf, d_term, d_idf, d_nrm, n_postings, n_terms, n_chunks, kw->post_impact, s));
-    RL_HIP(hipStreamSynchronize(s));  // the staging buffers and the caller's arrays may go away after return
-    g_pinned.drain();
+    RL_TRY(st.sync());  // the staging buffers and the caller's arrays may go away after return
     *out = kw.release();
     return RL_OK;
 }
@@ -3596,12 +3384,13 @@ int rl_keyword_store_append(rl_keyword_store* st, const int32_t* term_ids, const
             range[1] = std::max(range[1], term_ids[i]);
         }
     } else if (n_add > 0) {
-        DevBuf t_range;
-        RL_TRY(t_range.alloc(sizeof(range)));
-        RL_TRY(hip_status(hipMemcpyAsync(t_range.p, range, sizeof(range), hipMemcpyHostToDevice, s), who));
-        RL_TRY(launch_kb_minmax(term_ids, n_add, t_range.as<int32_t>(), s));
-        RL_TRY(hip_status(hipMemcpyAsync(range, t_range.p, sizeof(range), hipMemcpyDeviceToHost, s), who));
+        Staging up(RL_MEM_HOST, s);
+        const int32_t* d_range;
+        RL_TRY(up.in(range, 2, &d_range));
+        RL_TRY(launch_kb_minmax(term_ids, n_add, const_cast<int32_t*>(d_range), s));  // (folds the ids into the staged copy, which is this call's own)
+        RL_TRY(hip_status(hipMemcpyAsync(range, d_range, sizeof(range), hipMemcpyDeviceToHost, s), who));
         RL_TRY(hip_status(hipStreamSynchronize(s), who));
+        up.drain();
     }
     if (n_add > 0 && range[0] < 0) return fail(RL_ERR_INVALID, std::string(who) + ": negative term id");
     std::lock_guard<std::mutex> lock(st->mu);
@@ -3697,9 +3486,9 @@ int rl_keyword_store_count(rl_keyword_store* st, const int32_t* term_rank, int32
     RL_TRY(reserve_amortised(df, std::max<size_t>((size_t)n_terms * sizeof(int64_t), 16), who));
     if (m > 0) {
         Pool &sortbuf = st->sortbuf, &table = st->table, &heads = st->heads, &head_pos = st->head_pos;
-        DevBuf t_rank;
+        Staging up(mem, s);
         const int32_t* d_rank = nullptr;
-        if (term_rank) RL_TRY(stage_in(term_rank, (size_t)n_terms, mem, s, t_rank, &d_rank));
+        if (term_rank) RL_TRY(up.in(term_rank, (size_t)n_terms, &d_rank));
         const size_t plane = ((size_t)m * 4 + 255) & ~size_t(255);
         RL_TRY(reserve_amortised(sortbuf, 4 * plane, who));  // keys and values, twice: the passes go back and forth
         uint32_t* keys[2] = {reinterpret_cast<uint32_t*>(sortbuf.as<char>()), reinterpret_cast<uint32_t*>(sortbuf.as<char>() + 2 * plane)};
@@ -3724,8 +3513,7 @@ int rl_keyword_store_count(rl_keyword_store* st, const int32_t* term_rank, int32
         RL_TRY(reserve_amortised(head_pos, (size_t)np * sizeof(int64_t), who));
         RL_TRY(launch_kb_rle_write(keys[at], vals[at], m, heads.as<int64_t>(), np, post_term, post_chunk, post_tf, head_pos.as<int64_t>(), s));
         RL_TRY(launch_kb_term_off(post_term, np, n_terms, term_off, df.as<int64_t>(), s));
-        RL_HIP(hipStreamSynchronize(s));  // t_rank goes with this scope
-        g_pinned.drain();
+        RL_TRY(up.sync());  // the staged term_rank goes with this scope
     } else {  // no chunks, or no live tokens: what rl_keyword_index_create holds for empty arrays
         RL_TRY(reserve_amortised(post_term, 16, who));
         RL_TRY(post_chunk.alloc(16, who));
@@ -3764,13 +3552,12 @@ int rl_keyword_store_build(rl_keyword_store* st, const float* idf, const float* 
     std::unique_ptr<rl_keyword_index> kw;
     RL_TRY(new_keyword_index(st->c_terms, st->c_postings, st->c_chunks, &kw));
     RL_TRY(kw->post_impact.alloc(std::max<size_t>((size_t)st->c_postings * sizeof(float), 16), who));
-    DevBuf t_idf, t_nrm;
+    Staging up(mem, s);
     const float *d_idf, *d_nrm;
-    RL_TRY(stage_in(idf, (size_t)st->c_terms, mem, s, t_idf, &d_idf));
-    RL_TRY(stage_in(nrm, (size_t)st->c_chunks, mem, s, t_nrm, &d_nrm));
+    RL_TRY(up.in(idf, (size_t)st->c_terms, &d_idf));
+    RL_TRY(up.in(nrm, (size_t)st->c_chunks, &d_nrm));
     RL_TRY(launch_bm25_impact(st->post_chunk, st->post_tf, st->post_term, d_idf, d_nrm, st->c_postings, st->c_terms, st->c_chunks, kw->post_impact, s));
-    RL_HIP(hipStreamSynchronize(s));  // the staging buffers and the caller's arrays may go away after return
-    g_pinned.drain();
+    RL_TRY(up.sync());  // the staging buffers and the caller's arrays may go away after return
     kw->term_off = std::move(st->term_off);  // the counted postings become the index: no copy
     kw->post_chunk = std::move(st->post_chunk);
     st->drop_count();
@@ -3896,11 +3683,11 @@ int rl_keyword_analyze_begin(rl_keyword_analyzer* a, const uint32_t* codepoints,
     a->begun = a->finished = false;
     a->n_texts = n_texts;
     a->m = a->n_tok = a->n_kept = a->n_distinct = a->n_bytes = a->cap = 0;
-    DevBuf t_cp, t_off;
+    Staging st(mem, s);
     const uint32_t* d_cp;
     const int64_t* d_off;
-    RL_TRY(stage_in(codepoints, (size_t)n, mem, s, t_cp, &d_cp));
-    RL_TRY(stage_in(text_off, (size_t)n_texts + 1, mem, s, t_off, &d_off));
+    RL_TRY(st.in(codepoints, (size_t)n, &d_cp));
+    RL_TRY(st.in(text_off, (size_t)n_texts + 1, &d_off));
     // 1. fold
     RL_TRY(reserve_amortised(a->count, (size_t)(n + 1) * sizeof(int64_t), who));
     RL_TRY(launch_ka_fold_count(d_cp, n, a->table, a->n_table, a->count.as<int64_t>(), s));
@@ -3955,7 +3742,7 @@ int rl_keyword_analyze_begin(rl_keyword_analyzer* a, const uint32_t* codepoints,
         RL_TRY(hip_status(hipStreamSynchronize(s), who));
         a->cap = cap;
     }
-    g_pinned.drain();
+    st.drain();  // (the stream has been synchronised above)
     a->m = m;
     a->n_tok = n_tok;
     a->n_kept = n_kept;
@@ -4007,9 +3794,9 @@ int rl_keyword_analyze_finish(rl_keyword_analyzer* a, const int32_t* ids, int me
     a->finished = false;
     RL_TRY(reserve_amortised(a->term_ids, std::max<size_t>((size_t)a->n_kept * sizeof(int32_t), 16), who));
     RL_TRY(reserve_amortised(a->offsets, (size_t)(a->n_texts + 1) * sizeof(int64_t), who));
-    DevBuf t_ids;
+    Staging st(mem, s);
     const int32_t* d_ids;
-    RL_TRY(stage_in(ids, (size_t)a->n_distinct, mem, s, t_ids, &d_ids));
+    RL_TRY(st.in(ids, (size_t)a->n_distinct, &d_ids));
     if (a->n_tok > 0) {
         // 5. emit
         RL_TRY(launch_ka_emit(a->tok_len.as<int64_t>(), a->tok_slot.as<int64_t>(), a->slots.as<uint64_t>(), a->cap, a->n_tok, a->kept.as<int64_t>(),
@@ -4020,7 +3807,7 @@ int rl_keyword_analyze_finish(rl_keyword_analyzer* a, const int32_t* ids, int me
         RL_TRY(hip_status(hipMemsetAsync(a->offsets.p, 0, (size_t)(a->n_texts + 1) * sizeof(int64_t), s), who));
     }
     RL_TRY(hip_status(hipStreamSynchronize(s), who));  // the staging buffer and the caller's ids may go away after return
-    g_pinned.drain();
+    st.drain();
     a->finished = true;
     if (term_ids) *term_ids = a->term_ids.as<int32_t>();
     if (offsets) *offsets = a->offsets.as<int64_t>();
@@ -4068,31 +3855,23 @@ int keyword_search_call(rl_keyword_index* kw, const int64_t* q_off, const int32_
     RL_TRY(keyword_use_stream(kw, s));
     const int64_t n = kw->n_chunks;
     const size_t n_out = (size_t)n_queries * k;
-    DevBuf t_off, t_terms, t_f, t_s, t_c, t_n;
+    Staging st(mem, s);
     const int64_t* d_off;
     const int32_t* d_terms;
     const uint32_t* d_f = nullptr;
     float* d_s;
     int32_t *d_c, *d_n;
-    RL_TRY(stage_in(q_off, (size_t)n_queries + 1, mem, s, t_off, &d_off));
-    if (mem == RL_MEM_HOST) RL_TRY(stage_in(q_terms, (size_t)n_q_terms, mem, s, t_terms, &d_terms));
+    RL_TRY(st.in(q_off, (size_t)n_queries + 1, &d_off));
+    if (mem == RL_MEM_HOST) RL_TRY(st.in(q_terms, (size_t)n_q_terms, &d_terms));
     else d_terms = q_terms;
-    if (n_filters) RL_TRY(stage_in(chunk_filters, (size_t)n_filters * ((n + 31) / 32), fmem, s, t_f, &d_f));
+    if (n_filters) RL_TRY(st.in(chunk_filters, (size_t)n_filters * ((n + 31) / 32), &d_f, fmem));
     QueryMask mask;
     RL_TRY(keyword_mask(kw, d_f, n_filters, query_filter, n_queries, s, &mask));
-    RL_TRY(stage_out_begin(out_scores, n_out, mem, t_s, &d_s));
-    RL_TRY(stage_out_begin(out_chunks, n_out, mem, t_c, &d_c));
-    if (out_counts) RL_TRY(stage_out_begin(out_counts, (size_t)n_queries, mem, t_n, &d_n));
-    else {
-        RL_TRY(t_n.alloc((size_t)n_queries * sizeof(int32_t)));
-        d_n = t_n.as<int32_t>();
-    }
+    RL_TRY(st.out(out_scores, n_out, &d_s));
+    RL_TRY(st.out(out_chunks, n_out, &d_c));
+    RL_TRY(st.out_or_temp(out_counts, (size_t)n_queries, &d_n));
     RL_TRY(keyword_search_device(kw, d_off, d_terms, n_queries, k, mask, d_s, d_c, d_n, s));
-    RL_TRY(stage_out_end(out_scores, n_out, mem, s, t_s));
-    RL_TRY(stage_out_end(out_chunks, n_out, mem, s, t_c));
-    if (out_counts) RL_TRY(stage_out_end(out_counts, (size_t)n_queries, mem, s, t_n));
-    if (mem == RL_MEM_DEVICE && !out_counts) RL_HIP(hipStreamSynchronize(s));  // t_n dies with this frame
-    return finish(mem, s);
+    return st.finish();
 }
 }  // namespace
 
@@ -4122,19 +3901,16 @@ int rl_rrf_fuse(const int32_t* lists, int32_t n_lists, int32_t n_queries, int32_
     if (!lists || !out_scores || !out_ids) return fail(RL_ERR_INVALID, "rl_rrf_fuse: null argument");
     hipStream_t s = as_stream(stream);
     const size_t n_in = (size_t)n_lists * n_queries * len, n_out = (size_t)n_queries * k;
-    DevBuf t_l, t_s, t_i, t_n;
+    Staging st(mem, s);
     const int32_t* d_l;
     double* d_s;
     int32_t *d_i, *d_n = nullptr;
-    RL_TRY(stage_in(lists, n_in, mem, s, t_l, &d_l));
-    RL_TRY(stage_out_begin(out_scores, n_out, mem, t_s, &d_s));
-    RL_TRY(stage_out_begin(out_ids, n_out, mem, t_i, &d_i));
-    if (out_counts) RL_TRY(stage_out_begin(out_counts, (size_t)n_queries, mem, t_n, &d_n));
+    RL_TRY(st.in(lists, n_in, &d_l));
+    RL_TRY(st.out(out_scores, n_out, &d_s));
+    RL_TRY(st.out(out_ids, n_out, &d_i));
+    RL_TRY(st.out(out_counts, (size_t)n_queries, &d_n));  // (optional)
     RL_TRY(launch_rrf_fuse(d_l, n_lists, n_queries, len, weights, rrf_k, k, d_s, d_i, d_n, s));
-    RL_TRY(stage_out_end(out_scores, n_out, mem, s, t_s));
-    RL_TRY(stage_out_end(out_ids, n_out, mem, s, t_i));
-    if (out_counts) RL_TRY(stage_out_end(out_counts, (size_t)n_queries, mem, s, t_n));
-    return finish(mem, s);
+    return st.finish();
 }
 
 int rl_shard_hybrid_fuse(const int32_t* gathered, int32_t world, int32_t n_queries, int32_t num_hits, int32_t n_each, int32_t n_lists,
@@ -4153,19 +3929,16 @@ int rl_shard_hybrid_fuse(const int32_t* gathered, int32_t world, int32_t n_queri
     hipStream_t s = as_stream(stream);
     const size_t W = (size_t)3 * num_hits + (n_lists == 2 ? (size_t)2 * n_each : 0);
     const size_t n_in = (size_t)world * n_queries * W, n_out = (size_t)n_queries * k;
-    DevBuf t_g, t_s, t_c, t_n;
+    Staging st(mem, s);
     const int32_t* d_g;
     double* d_s;
     int32_t *d_c, *d_n = nullptr;
-    RL_TRY(stage_in(gathered, n_in, mem, s, t_g, &d_g));
-    RL_TRY(stage_out_begin(out_scores, n_out, mem, t_s, &d_s));
-    RL_TRY(stage_out_begin(out_chunks, n_out, mem, t_c, &d_c));
-    if (out_counts) RL_TRY(stage_out_begin(out_counts, (size_t)n_queries, mem, t_n, &d_n));
+    RL_TRY(st.in(gathered, n_in, &d_g));
+    RL_TRY(st.out(out_scores, n_out, &d_s));
+    RL_TRY(st.out(out_chunks, n_out, &d_c));
+    RL_TRY(st.out(out_counts, (size_t)n_queries, &d_n));  // (optional)
     RL_TRY(launch_shard_hybrid_fuse(d_g, world, n_queries, num_hits, n_each, n_lists, weights, rrf_k, k, d_s, d_c, d_n, s));
-    RL_TRY(stage_out_end(out_scores, n_out, mem, s, t_s));
-    RL_TRY(stage_out_end(out_chunks, n_out, mem, s, t_c));
-    if (out_counts) RL_TRY(stage_out_end(out_counts, (size_t)n_queries, mem, s, t_n));
-    return finish(mem, s);
+    return st.finish();
 }
 
 }  // extern "C"
@@ -4174,7 +3947,7 @@ namespace {
 // What every hybrid call needs before its device work: the arguments checked, both handles locked on the stream, the inputs staged.
 struct HybridCall {
     std::unique_lock<std::mutex> idx_lock, kw_lock;  // (idx->mu, then kw->mu: always in this order)
-    DevBuf t_q, t_f, t_off, t_terms;
+    Staging st;                                      // (after the locks: its buffers are released while they are held)
     const float* d_q = nullptr;
     const int64_t* d_off = nullptr;
     const int32_t* d_terms = nullptr;
@@ -4182,6 +3955,7 @@ struct HybridCall {
     int32_t n_filters = 0;
     const int32_t* query_filter = nullptr;
     bool empty = false;  // n_queries == 0: nothing to do
+    HybridCall(int mem, hipStream_t s) : st(args_mem(mem), s) {}  // (`mem` as the caller of the entry point gave it)
 };
 
 // The checks of rl_hybrid_search (k: the fusion's), the locks and the staging-in
@@ -4223,11 +3997,11 @@ int hybrid_search_begin(rl_index* idx, rl_keyword_index* kw, const float* querie
     c->f.qf = query_filter;
     c->f.lim = rank_limits;
     c->f.limit = rank_limit;
-    RL_TRY(stage_in(queries, (size_t)B * idx->dim, mem, s, c->t_q, &c->d_q));
-    if (n_filters) RL_TRY(stage_in(chunk_filters, (size_t)n_filters * ((idx->n_chunks + 31) / 32), fmem, s, c->t_f, &c->f.chunk_bits));
+    RL_TRY(c->st.in(queries, (size_t)B * idx->dim, &c->d_q));
+    if (n_filters) RL_TRY(c->st.in(chunk_filters, (size_t)n_filters * ((idx->n_chunks + 31) / 32), &c->f.chunk_bits, fmem));
     if (kw) {
-        RL_TRY(stage_in(q_off, (size_t)B + 1, mem, s, c->t_off, &c->d_off));
-        if (mem == RL_MEM_HOST) RL_TRY(stage_in(q_terms, (size_t)n_q_terms, mem, s, c->t_terms, &c->d_terms));
+        RL_TRY(c->st.in(q_off, (size_t)B + 1, &c->d_off));
+        if (mem == RL_MEM_HOST) RL_TRY(c->st.in(q_terms, (size_t)n_q_terms, &c->d_terms));
     }
     return RL_OK;
 }
@@ -4259,23 +4033,19 @@ int hybrid_search_call(rl_index* idx, rl_keyword_index* kw, const float* queries
                        int32_t* out_chunks, int32_t* out_counts, int mem, void* stream, const char* who) {
     const int32_t B = n_queries;
     hipStream_t s = as_stream(stream);
-    HybridCall c;
+    HybridCall c(mem, s);
     RL_TRY(hybrid_search_begin(idx, kw, queries, B, num_hits, n_each, q_off, q_terms, chunk_filters, n_filters, query_filter, rank_limits,
                                rank_limit, weights, rrf_k, k, out_scores && out_chunks && out_counts, mem, s, who, &c));
     if (c.empty) return RL_OK;
-    mem = args_mem(mem);
+    Staging& st = c.st;
     const size_t n_out = (size_t)B * k;
-    DevBuf t_s, t_c, t_n;
     double* d_s;
     int32_t *d_c, *d_n;
-    RL_TRY(stage_out_begin(out_scores, n_out, mem, t_s, &d_s));
-    RL_TRY(stage_out_begin(out_chunks, n_out, mem, t_c, &d_c));
-    RL_TRY(stage_out_begin(out_counts, (size_t)B, mem, t_n, &d_n));
+    RL_TRY(st.out(out_scores, n_out, &d_s));
+    RL_TRY(st.out(out_chunks, n_out, &d_c));
+    RL_TRY(st.out(out_counts, (size_t)B, &d_n));
     RL_TRY(hybrid_search_device(idx, kw, c, B, num_hits, n_each, weights, rrf_k, k, d_s, d_c, d_n, s));
-    RL_TRY(stage_out_end(out_scores, n_out, mem, s, t_s));
-    RL_TRY(stage_out_end(out_chunks, n_out, mem, s, t_c));
-    RL_TRY(stage_out_end(out_counts, (size_t)B, mem, s, t_n));
-    return finish(mem, s);
+    return st.finish();
 }
 }  // namespace
 
@@ -4310,23 +4080,19 @@ int rl_rerank_order(const float* scores, const int32_t* candidates, int32_t n_qu
         return fail(RL_ERR_INVALID, "rl_rerank_order: null argument");
     hipStream_t s = as_stream(stream);
     const size_t n_in = (size_t)n_queries * n_cand, n_out = (size_t)n_queries * k;
-    DevBuf t_sc, t_ca, t_s, t_c, t_p, t_n;
+    Staging st(mem, s);
     const float* d_sc;
     const int32_t* d_ca;
     float* d_s;
     int32_t *d_c, *d_p, *d_n;
-    RL_TRY(stage_in(scores, n_in, mem, s, t_sc, &d_sc));
-    RL_TRY(stage_in(candidates, n_in, mem, s, t_ca, &d_ca));
-    RL_TRY(stage_out_begin(out_scores, n_out, mem, t_s, &d_s));
-    RL_TRY(stage_out_begin(out_chunks, n_out, mem, t_c, &d_c));
-    RL_TRY(stage_out_begin(out_pos, n_out, mem, t_p, &d_p));
-    RL_TRY(stage_out_begin(out_counts, (size_t)n_queries, mem, t_n, &d_n));
+    RL_TRY(st.in(scores, n_in, &d_sc));
+    RL_TRY(st.in(candidates, n_in, &d_ca));
+    RL_TRY(st.out(out_scores, n_out, &d_s));
+    RL_TRY(st.out(out_chunks, n_out, &d_c));
+    RL_TRY(st.out(out_pos, n_out, &d_p));
+    RL_TRY(st.out(out_counts, (size_t)n_queries, &d_n));
     RL_TRY(launch_rerank_order(d_sc, d_ca, n_queries, n_cand, k, d_s, d_c, d_p, d_n, s));
-    RL_TRY(stage_out_end(out_scores, n_out, mem, s, t_s));
-    RL_TRY(stage_out_end(out_chunks, n_out, mem, s, t_c));
-    RL_TRY(stage_out_end(out_pos, n_out, mem, s, t_p));
-    RL_TRY(stage_out_end(out_counts, (size_t)n_queries, mem, s, t_n));
-    return finish(mem, s);
+    return st.finish();
 }
 
 }  // extern "C"
@@ -4346,8 +4112,8 @@ namespace {
 // query token vectors staged.
 struct RerankCall {
     HybridCall c;
-    DevBuf t_v;
     const float* d_v = nullptr;
+    RerankCall(int mem, hipStream_t s) : c(mem, s) {}
 };
 
 // The checks of rl_search_rerank_per_query, the locks and the staging-in
@@ -4364,7 +4130,7 @@ int search_rerank_begin(rl_index* idx, rl_keyword_index* kw, const float* querie
     RL_TRY(hybrid_search_begin(idx, kw, queries, B, num_hits, n_each, q_off, q_terms, chunk_filters, query_filter ? n_filters : 0, query_filter,
                                rank_limits, 0, weights, rrf_k, n_cand, query_vecs && outputs, mem, s, who, &rc->c));
     if (rc->c.empty) return RL_OK;
-    return stage_in(query_vecs, (size_t)B * nq * idx->dim, args_mem(mem), s, rc->t_v, &rc->d_v);
+    return rc->c.st.in(query_vecs, (size_t)B * nq * idx->dim, &rc->d_v);
 }
 
 // The searches, the fusion, the MaxSim rerank and the ordering on device pointers (after search_rerank_begin): d_c [B x k], d_n [B];
@@ -4401,31 +4167,23 @@ int check_span_args(const rl_span_table* table, int32_t n_queries, int32_t n_in,
     return RL_OK;
 }
 
-// The five outputs of the span kernel for a batch, staged for host callers
-struct SpanOutputs {
-    DevBuf t_c, t_l, t_s, t_ns, t_nc;
+// The five outputs of the span kernel for a batch, as the kernel takes them ...
+struct SpanPtrs {
     int32_t *d_c = nullptr, *d_l = nullptr, *d_ns = nullptr, *d_nc = nullptr;
     double* d_s = nullptr;
-    int begin(int32_t* out_chunks, int32_t* out_span_len, double* out_span_scores, int32_t* out_n_spans, int32_t* out_n_chunks, size_t n,
-              size_t B, int mem) {
-        RL_TRY(stage_out_begin(out_chunks, n, mem, t_c, &d_c));
-        RL_TRY(stage_out_begin(out_span_len, n, mem, t_l, &d_l));
-        RL_TRY(stage_out_begin(out_span_scores, n, mem, t_s, &d_s));
-        RL_TRY(stage_out_begin(out_n_spans, B, mem, t_ns, &d_ns));
-        return stage_out_begin(out_n_chunks, B, mem, t_nc, &d_nc);
-    }
-    int end(int32_t* out_chunks, int32_t* out_span_len, double* out_span_scores, int32_t* out_n_spans, int32_t* out_n_chunks, size_t n,
-            size_t B, int mem, hipStream_t s) {
-        RL_TRY(stage_out_end(out_chunks, n, mem, s, t_c));
-        RL_TRY(stage_out_end(out_span_len, n, mem, s, t_l));
-        RL_TRY(stage_out_end(out_span_scores, n, mem, s, t_s));
-        RL_TRY(stage_out_end(out_n_spans, B, mem, s, t_ns));
-        return stage_out_end(out_n_chunks, B, mem, s, t_nc);
-    }
 };
+// ... registered on a call's frame: [n] chunks, span lengths and span scores, [B] span and chunk counts
+int span_outputs(Staging& st, int32_t* out_chunks, int32_t* out_span_len, double* out_span_scores, int32_t* out_n_spans, int32_t* out_n_chunks,
+                 size_t n, size_t B, SpanPtrs* o) {
+    RL_TRY(st.out(out_chunks, n, &o->d_c));
+    RL_TRY(st.out(out_span_len, n, &o->d_l));
+    RL_TRY(st.out(out_span_scores, n, &o->d_s));
+    RL_TRY(st.out(out_n_spans, B, &o->d_ns));
+    return st.out(out_n_chunks, B, &o->d_nc);
+}
 
 int spans_device(const rl_span_table* t, const int32_t* d_in, int32_t B, int32_t n_in, const int32_t* offsets, int32_t n_off,
-                 const SpanOutputs& o, hipStream_t s) {
+                 const SpanPtrs& o, hipStream_t s) {
     return launch_chunk_spans(t->rank_of, t->tab_key, t->tab_ord, (int32_t)t->n_chunks, (int32_t)t->n_live, d_in, B, n_in, offsets, n_off,
                               o.d_c, o.d_l, o.d_s, o.d_ns, o.d_nc, s);
 }
@@ -4441,23 +4199,19 @@ int rl_search_rerank_per_query(rl_index* idx, rl_keyword_index* kw, const float*
     const char* who = "rl_search_rerank_per_query";
     const int32_t B = n_queries;
     hipStream_t s = as_stream(stream);
-    RerankCall rc;
+    RerankCall rc(mem, s);
     RL_TRY(search_rerank_begin(idx, kw, queries, B, num_hits, n_each, q_off, q_terms, chunk_filters, n_filters, query_filter, rank_limits, weights,
                                rrf_k, n_cand, query_vecs, nq, k, out_scores && out_chunks && out_counts, mem, s, who, &rc));
     if (rc.c.empty) return RL_OK;
-    mem = args_mem(mem);
+    Staging& st = rc.c.st;
     const size_t n_out = (size_t)B * k;
-    DevBuf t_s, t_c, t_n;
     float* d_s;
     int32_t *d_c, *d_n;
-    RL_TRY(stage_out_begin(out_scores, n_out, mem, t_s, &d_s));
-    RL_TRY(stage_out_begin(out_chunks, n_out, mem, t_c, &d_c));
-    RL_TRY(stage_out_begin(out_counts, (size_t)B, mem, t_n, &d_n));
+    RL_TRY(st.out(out_scores, n_out, &d_s));
+    RL_TRY(st.out(out_chunks, n_out, &d_c));
+    RL_TRY(st.out(out_counts, (size_t)B, &d_n));
     RL_TRY(search_rerank_device(idx, kw, rc, B, num_hits, n_each, weights, rrf_k, n_cand, nq, k, d_s, d_c, d_n, s));
-    RL_TRY(stage_out_end(out_scores, n_out, mem, s, t_s));
-    RL_TRY(stage_out_end(out_chunks, n_out, mem, s, t_c));
-    RL_TRY(stage_out_end(out_counts, (size_t)B, mem, s, t_n));
-    return finish(mem, s);
+    return st.finish();
 }
 
 int rl_span_table_create(rl_span_table** out, const int32_t* doc, const int32_t* pos, int64_t n_chunks) {
@@ -4522,14 +4276,13 @@ int rl_chunk_spans(const rl_span_table* table, const int32_t* chunks, int32_t n_
         return fail(RL_ERR_INVALID, std::string(who) + ": null argument");
     hipStream_t s = as_stream(stream);
     const size_t B = (size_t)n_queries, n_out = B * n_in * (1 + n_off);
-    DevBuf t_in;
+    Staging st(mem, s);
     const int32_t* d_in;
-    SpanOutputs o;
-    RL_TRY(stage_in(chunks, B * n_in, mem, s, t_in, &d_in));
-    RL_TRY(o.begin(out_chunks, out_span_len, out_span_scores, out_n_spans, out_n_chunks, n_out, B, mem));
+    SpanPtrs o;
+    RL_TRY(st.in(chunks, B * n_in, &d_in));
+    RL_TRY(span_outputs(st, out_chunks, out_span_len, out_span_scores, out_n_spans, out_n_chunks, n_out, B, &o));
     RL_TRY(spans_device(table, d_in, n_queries, n_in, offsets, n_off, o, s));
-    RL_TRY(o.end(out_chunks, out_span_len, out_span_scores, out_n_spans, out_n_chunks, n_out, B, mem, s));
-    return finish(mem, s);
+    return st.finish();
 }
 
 int rl_search_rerank_spans_per_query(rl_index* idx, rl_keyword_index* kw, const float* queries, int32_t n_queries, int32_t num_hits,
@@ -4544,26 +4297,22 @@ int rl_search_rerank_spans_per_query(rl_index* idx, rl_keyword_index* kw, const 
     RL_TRY(check_span_args(table, B, k, offsets, n_off, args_mem(mem), who));  // (k * (1 + n_off) <= 4096)
     if (idx && table->n_chunks != idx->n_chunks) return fail(RL_ERR_INVALID, std::string(who) + ": the span table covers another number of chunks");
     hipStream_t s = as_stream(stream);
-    RerankCall rc;
+    RerankCall rc(mem, s);
     RL_TRY(search_rerank_begin(idx, kw, queries, B, num_hits, n_each, q_off, q_terms, chunk_filters, n_filters, query_filter, rank_limits, weights,
                                rrf_k, n_cand, query_vecs, nq, k,
                                out_top_chunks && out_top_counts && out_chunks && out_span_len && out_span_scores && out_n_spans && out_n_chunks,
                                mem, s, who, &rc));
     if (rc.c.empty) return RL_OK;
-    mem = args_mem(mem);
+    Staging& st = rc.c.st;
     const size_t n_top = (size_t)B * k, n_out = n_top * (1 + n_off);
-    DevBuf t_c, t_n;
     int32_t *d_c, *d_n;
-    SpanOutputs o;
-    RL_TRY(stage_out_begin(out_top_chunks, n_top, mem, t_c, &d_c));
-    RL_TRY(stage_out_begin(out_top_counts, (size_t)B, mem, t_n, &d_n));
-    RL_TRY(o.begin(out_chunks, out_span_len, out_span_scores, out_n_spans, out_n_chunks, n_out, (size_t)B, mem));
+    SpanPtrs o;
+    RL_TRY(st.out(out_top_chunks, n_top, &d_c));
+    RL_TRY(st.out(out_top_counts, (size_t)B, &d_n));
+    RL_TRY(span_outputs(st, out_chunks, out_span_len, out_span_scores, out_n_spans, out_n_chunks, n_out, (size_t)B, &o));
     RL_TRY(search_rerank_device(idx, kw, rc, B, num_hits, n_each, weights, rrf_k, n_cand, nq, k, nullptr, d_c, d_n, s));
     RL_TRY(spans_device(table, d_c, B, k, offsets, n_off, o, s));
-    RL_TRY(stage_out_end(out_top_chunks, n_top, mem, s, t_c));
-    RL_TRY(stage_out_end(out_top_counts, (size_t)B, mem, s, t_n));
-    RL_TRY(o.end(out_chunks, out_span_len, out_span_scores, out_n_spans, out_n_chunks, n_out, (size_t)B, mem, s));
-    return finish(mem, s);
+    return st.finish();
 }
 
 }  // extern "C"
