@@ -18,9 +18,16 @@ CSRC = PKG / "csrc"
 INCLUDE = PKG.parent / "include"
 LIB_DIR = PKG / "_lib"
 LIB_PATH = LIB_DIR / "libraglite_hip.so"
-SOURCES = ["api.hip", "synth.hip", "pool_norm.hip", "scan.hip", "select.hip", "maxsim_stream.hip", "maxsim_generic.hip",
-           "maxsim_gemm.hip", "maxsim_pp.hip", "score_gemm.hip", "mask.hip", "scan16.hip", "adapter_fit.hip", "query_targets.hip", "partition_sim.hip", "partition_dp.hip", "chunklet_dp.hip", "sentence_dp.hip", "comm.hip", "hi_filter.hip",
-           "keyword.hip", "keyword_build.hip", "keyword_analyze.hip", "fuse.hip", "rerank.hip", "spans.hip", "metadata.hip"]
+SOURCES = [
+    "api.hip", "api_ingest.hip", "api_keyword.hip", "api_retrieval.hip",  # the C ABI (host code only)
+    "synth.hip", "scan.hip", "scan16.hip", "select.hip", "mask.hip", "score_gemm.hip", "hi_filter.hip",  # row and chunk search
+    "maxsim_stream.hip", "maxsim_generic.hip", "maxsim_gemm.hip", "maxsim_pp.hip",  # MaxSim
+    "pool_norm.hip", "partition_sim.hip", "partition_dp.hip", "chunklet_dp.hip", "sentence_dp.hip",  # ingestion
+    "adapter_fit.hip", "query_targets.hip",  # query adapter
+    "keyword.hip", "keyword_build.hip", "keyword_analyze.hip",  # BM25
+    "fuse.hip", "rerank.hip", "spans.hip", "metadata.hip",  # fusion, rerank order, spans, metadata filters
+    "comm.hip",  # sharding
+]
 # No -ffast-math: parity relies on IEEE fp32 divide / sqrt and on un-fused, un-reassociated sums.
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function",
          f"-I{INCLUDE}", f"-I{CSRC}"]

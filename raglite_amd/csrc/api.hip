@@ -8,8 +8,7 @@
 #include <utility>
 #include <vector>
 
-#include "common.h"
-#include "staging.h"
+#include "handles.h"
 
 namespace rl {
 
@@ -22,55 +21,6 @@ int fail(int code, const std::string& msg) {
 
 namespace {
 
-hipStream_t as_stream(void* s) { return reinterpret_cast<hipStream_t>(s); }
-
-// Device memory owned by an index: freed with its owner, move-only (one owner per block).  As scratch it grows: reserve() never
-// shrinks, frees the old block before it allocates and does not keep the contents (no allocation in steady state).
-struct Pool {
-    void* p = nullptr;
-    size_t cap = 0;
-    Pool() = default;
-    Pool(const Pool&) = delete;
-    Pool& operator=(const Pool&) = delete;
-    Pool(Pool&& o) noexcept : p(o.p), cap(o.cap) { o.p = nullptr; o.cap = 0; }
-    Pool& operator=(Pool&& o) noexcept {  // (frees what this held right away)
-        if (this != &o) { release(); std::swap(p, o.p); std::swap(cap, o.cap); }
-        return *this;
-    }
-    ~Pool() { release(); }
-    int reserve(size_t bytes) {
-        if (bytes <= cap) return RL_OK;
-        release();
-        RL_HIP(hipMalloc(&p, bytes));
-        cap = bytes;
-        return RL_OK;
-    }
-    // A fresh block of exactly `bytes` (the buffers a lifecycle call builds before it commits them to the index); frees what it held.
-    int alloc(size_t bytes, const char* who) {
-        release();
-        RL_TRY(hip_status(hipMalloc(&p, bytes), who));
-        cap = bytes;
-        return RL_OK;
-    }
-    void release() {
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        cap = 0;
-    }
-    template <class T>
-    T* as() const { return reinterpret_cast<T*>(p); }
-};
-// A Pool that reads as the T* the kernels take: the index' fixed-size device arrays.
-template <class T>
-struct DevArray : Pool {
-    operator T*() const { return as<T>(); }
-};
-
-// RL_MEM_FILTERS_DEVICE or-ed into `mem`: the filter table alone is a device pointer, read in place; every other pointer follows the
-// rest of `mem`.  Each entry that takes filters splits `mem` once, into where its filters live and where everything else does.
-int filters_mem(int mem) { return (mem & RL_MEM_FILTERS_DEVICE) ? RL_MEM_DEVICE : mem; }
-int args_mem(int mem) { return mem & ~RL_MEM_FILTERS_DEVICE; }
-
 int scan_mode(int metric) {
     switch (metric) {
         case RL_COSINE: return SCAN_COSINE;
@@ -80,26 +30,7 @@ int scan_mode(int metric) {
     }
 }
 
-constexpr size_t SCORE_BATCH_BYTES = size_t(8) << 30;  // cap of the [B x N] score scratch per sub-batch
-
-// Route options (raglite_hip.h "options"): per index, copied from the process-wide defaults when the index is created.  The library
-// reads no environment variable.
-struct Options {
-    int64_t v[RL_OPT_PP_XCD_PASSES + 1];  // (keys 1 .. RL_OPT_COUNT_ - 1, and the schedule switches from 64 on)
-    Options() {
-        for (auto& x : v) x = 0;
-        v[RL_OPT_HI_SEARCH] = v[RL_OPT_HI_MAXSIM] = v[RL_OPT_HI_PRODUCTS] = v[RL_OPT_PP_PASS] = v[RL_OPT_FUSED_TOPK] = v[RL_OPT_FUSED_HI] = 1;
-        v[RL_OPT_FUSED_PP] = v[RL_OPT_GEMM_PASS] = v[RL_OPT_QUERY_PAIRS] = v[RL_OPT_PLANES_GEMM] = v[RL_OPT_KEEP_IMAGE] = v[RL_OPT_KEEP_HI] = 1;
-        v[RL_OPT_EXACT_KTH_THRESHOLD] = v[RL_OPT_FUSED_TWO_ROUNDS] = v[RL_OPT_KEEP_HI_PLANE] = v[RL_OPT_F16_EXACT] = v[RL_OPT_LAZY_IMAGES] = v[RL_OPT_FUSED_PP_SAMPLE] = v[RL_OPT_LIST_SELECT] = v[RL_OPT_HI_FEW] = 1;
-        v[RL_OPT_TOPK_BLOCK] = v[RL_OPT_PAIRS_PACKED] = 2;
-        v[RL_OPT_HI_PIVOT] = 1;
-        v[RL_OPT_PP_SCHEDULE] = 1;
-        v[RL_OPT_PP_XCD_PASSES] = 2;  // (measured: DESIGN.md 4.1)
-        v[RL_OPT_IMAGE_HEADROOM_MB] = -1;
-        v[RL_OPT_ARITHMETIC] = RL_ARITH_AUTO;
-    }
-    bool on(int key) const { return v[key] != 0; }
-};
+// The process-wide defaults of the route options: what an index is created with (handles.h: Options).
 std::mutex g_default_opts_mu;
 Options g_default_opts;
 bool option_key_ok(int key) { return (key >= 1 && key < RL_OPT_COUNT_) || key == RL_OPT_PP_SCHEDULE || key == RL_OPT_PP_XCD_PASSES; }
@@ -121,123 +52,13 @@ bool option_value_ok(int key, int64_t value) {
     }
 }
 
-// The three derived images of the rows (IMG_* bits): a block, the scale it was built with (0 = no image) and the rows it covers.
-struct Image {
-    Pool buf;
-    float scale = 0.f;
-    int64_t rows = 0;
-    void drop() {
-        buf.release();
-        scale = 0.f;
-        rows = 0;
-    }
-    bool covers(float at, int64_t n_rows) const { return scale > 0.f && scale == at && rows == n_rows && n_rows > 0; }
-};
-// max |e|, max |e_lo|, max |e_lo| / |e|, min |e| over the rows (e_lo: what the HI halves drop), the split scale they were computed at and
-// the rows folded in so far: what the error bounds of the half-bytes routes are made of.  min |e| is never raised by deletions (conservative).
-struct NormStats {
-    float max_row_norm = 0.f, max_lo_norm = 0.f, max_lo_ratio = 0.f;
-    float min_row_norm = std::numeric_limits<float>::infinity();
-    float max_row_norm_scale = 0.f;
-    int64_t max_row_norm_rows = 0;
-    void reset() { *this = NormStats(); }
-    bool measured(int64_t n_rows) const { return max_row_norm_rows == n_rows && max_row_norm > 0.f; }
-};
-
 }  // namespace
-}  // namespace rl
 
-struct rl_index {
-    const float* E = nullptr;       // fp32 storage ...
-    const uint16_t* E16 = nullptr;  // ... or IEEE fp16 storage (rl_index_create_f16); exactly one is set: the caller's rows or `owned_rows`
-    rl::Pool owned_rows;            // the rows when the index owns them (copied from the host, appended to, compacted)
-    bool owns_E() const { return owned_rows.p != nullptr; }
-    int64_t n_rows = 0;
-    int32_t dim = 0;
-    int64_t n_chunks = 0;
-    int metric = RL_COSINE;
-    bool has_empty_chunk = false;
-    rl::DevArray<int64_t> offsets;       // device [n_chunks + 1]
-    rl::DevArray<int32_t> row_to_chunk;  // device [n_rows + 65]
-    rl::DevArray<float> norm;            // device [n_rows]  (cosine)
-    rl::DevArray<float> sumsq;           // device [n_rows]  (l2)
-    int n_cu = 256;
-    std::mutex mu;
-    rl::SelectWorkspace ws;
-    rl::Pool scores;                  // [B x ld] similarity scratch / chunk scores
-    rl::Pool hits;                    // search_chunks: [B x num_hits] (score, row)
-    rl::Pool misc;
-    // lifecycle (append / delete / filter)
-    int64_t cap_rows = 0;                 // rows the owned buffers (E, norm, sumsq, row_to_chunk) can hold
-    int64_t cap_chunks = 0;               // chunks the device CSR can hold
-    std::vector<int64_t> h_offsets;       // host copy of the CSR
-    std::vector<uint32_t> h_live;         // host bitset over chunks: 1 = live (empty until the first delete)
-    rl::DevArray<uint32_t> live_chunk_bits;  // device copy of h_live (empty: every chunk is live)
-    rl::DevArray<uint32_t> live_row_bits;    // the same expanded to rows
-    int64_t n_dead_chunks = 0, n_dead_rows = 0;
-    rl::Pool maskbuf;                     // per-call row masks (the distinct filters of a sub-batch) and the query -> mask map
-    rl::Pool qsplit;                      // fp16 (hi, lo) query fragments of a MaxSim batch (maxsim_stream.hip)
-    // SPLIT arithmetic of the stream kernel (fp32 storage only): range of the row norms, and what follows from it
-    rl::DevArray<uint32_t> d_range;       // device scratch of launch_row_range
-    float max_abs = 0.f, min_row_max = std::numeric_limits<float>::infinity();  // over rows that are not all zero
-    bool nonfinite = false;
-    int arithmetic = RL_ARITH_AUTO;
-    float split_scale = 0.f;              // > 0: power of two applied to the corpus inside the kernel; 0: exact fp32 MFMAs
-    // Pre-split corpus image of maxsim_gemm.hip (fp16 hi | lo planes in the kernel's LDS layout, 4 B per element) and
-    // the "last row of its chunk" bitmap; built with the index, extended on append, rebuilt when split_scale changes.
-    rl::Image planes;
-    rl::Pool ends, qplanes;
-    rl::Pool q32;                         // rl_maxsim_topk_batch_f16: the fp16 queries widened to fp32 (what the query-side kernels read)
-    rl::Pool cand;                        // rl_maxsim_rerank: sanitised candidate ordinals
-    rl::Pool fused;                       // fused batched top-k: sample scores, thresholds, candidate lists, counters
-    rl::Pool pp_work;                     // ... on the sixteen-group tile: wave-private record logs, block norm ranges (maxsim_pp.hip MODE 2)
-    rl::Pool rankbuf;                     // rank cut (order-first-then-filter): histogram levels + tie counts
-    rl::Pool hybrid;                      // rl_hybrid_search: the ranked lists the fusion reads, their scores and counts
-    rl::Pool rerank;                      // rl_search_rerank_per_query: the fused candidates, their fused and MaxSim scores, positions
-    // HI plane (round 2): fp16(e * split_scale) rounded to nearest (toward zero until round 3), row-major [n_rows x dim] -- the hi halves of the fp16
-    // split as a matrix of their own, 2 B per element: what the single-query search streams (search_rows_hi).
-    rl::Image hiplane;
-    rl::Pool hibuf;
-    // ... and the same halves in the one-plane IMAGE layout (maxsim_gemm.hip HALF): what the approximate MaxSim pass of a
-    // batch multiplies (maxsim_batch_hi); the row-norm statistics are for the error bounds of both
-    rl::Image hi_image;
-    rl::NormStats norm_stats;
-    rl::DevArray<uint32_t> d_norms;       // device scratch of launch_max_row_norm (4 words)
-    // The scratch above is shared by all calls on this handle; `mu` serialises only their host side.  Device-mode calls are
-    // asynchronous, so a call arriving on a DIFFERENT stream than the previous one first waits for that stream.
-    hipStream_t last_stream = nullptr;
-    bool last_stream_set = false;
-    int64_t ends_rows = -1;               // rows the `ends` bitmap covers (-1: not built); kept by both images
-    // What the last bound-filtered search on this handle left behind (rl_index_filter_stats): per-query candidate counters and the
-    // device flag its guarded full-precision fallback waits on.  Pointers into the scratch above, valid until the next call.
-    // rl_rank_cut_*: the staged rank cut of a SHARDED corpus keeps its queries and scores here between the calls
-    int32_t rank_B = 0;                   // queries of the running rl_rank_cut_begin (0: none)
-    int32_t mb_B = 0, mb_nq = 0, mb_k = 0;  // rl_maxsim_batch_begin in progress: queries, vectors per query, k (0: none)
-    uint64_t scratch_epoch = 0, mb_epoch = 0;  // calls that used the scratch so far; the value right after that rl_maxsim_batch_begin
-    rl::Pool rank_q;                      // their device copy (the l2 re-scoring of rl_rank_cut_finish needs them)
-    struct FilterRecord { int kind = 0; int32_t n = 0, cap = 0; const uint32_t* cnt = nullptr; const uint32_t* flag = nullptr; } filt;
-    rl::Options opt;                      // route options (rl_index_set_option)
-    // RL_OPT_LAZY_IMAGES (round 5, the default): an image is built by the first call whose route reads it -- which images this index
-    // has been asked for so far (IMG_* bits); with the option off every image the KEEP_* options allow is built with the index
-    uint32_t demanded = 0;
-    uint32_t no_room = 0;                 // IMG_* bits whose last build was skipped because it would not have left the headroom free
-    uint64_t no_room_retry_epoch = 0;     // ... and the scratch epoch from which demand_images asks for them again
-    // ... and a pinned host word every bound-filtered MaxSim batch copies its fallback flag to when it is done (asynchronously): a batch
-    // that finds the previous one fell back asks for the pre-split image, so that an index whose data keeps defeating the bound runs its
-    // full-precision passes through the eight-query kernel instead of the streaming kernels (3-4 x faster) from the second batch on
-    std::unique_ptr<uint32_t, hipError_t (*)(void*)> h_fell_back{nullptr, hipHostFree};
-    uint32_t* d_fell_back = nullptr;  // the device's view of that word (written by guarded_select_kernel)
-    // rl_time_kernel kind 8: what the candidate pass of the last fused-HI row search ran with (pointers into misc / fused / pp_work: valid
-    // while those pools have not been re-reserved, which `pools` pins down)
-    struct FusedReplay {
-        bool valid = false, pp = false, row_test = false; int32_t B = 0, log_cap = 0; int mode = 0; float* qs = nullptr; rl::CandArgs ca{}; uint32_t* cnt = nullptr;
-        const float* thr1 = nullptr; int64_t round1_tiles = 0;  // two-round candidate pass: the first round's thresholds and tiles
-        const void* pools[3] = {nullptr, nullptr, nullptr};
-    } replay;
-    ~rl_index() { rl::select_workspace_free(ws); }  // (every other member frees itself)
-};
+int64_t default_option(int key) {
+    std::lock_guard<std::mutex> lock(g_default_opts_mu);
+    return g_default_opts.v[key];
+}
 
-namespace {
 // Called (under idx->mu) by every entry point that uses the index' shared scratch: a call on another stream than the
 // previous one waits for the previous stream's work on this handle (host-side; the rare case).
 int use_scratch(rl_index* idx, hipStream_t s) {
@@ -245,12 +66,12 @@ int use_scratch(rl_index* idx, hipStream_t s) {
     idx->filt = {};        // its pointers go into scratch this call may re-reserve: whoever filters next records itself again
     idx->ws.block_route = (int)idx->opt.v[RL_OPT_TOPK_BLOCK];
     idx->replay.valid = false;  // likewise: a later search overwrites the queries / thresholds the record points at (rl_time_kernel restores it for itself)
-    if (idx->last_stream_set && idx->last_stream != s) RL_HIP(hipStreamSynchronize(idx->last_stream));
-    idx->last_stream = s;
-    idx->last_stream_set = true;
-    return RL_OK;
+    return idx->last_stream.use(s);
 }
 
+}  // namespace rl
+
+namespace {
 // The stream kernel multiplies an fp32 corpus either with the exact fp32 MFMA chain or -- 10 % faster, HBM-bound instead
 // of matrix-pipe-bound -- as fp16 (hi, lo) pairs (maxsim_stream.hip, SPLIT).  After scaling the largest element to
 // [2^13, 2^14) a pair keeps 22 significant bits of every element down to 2^-3, fewer below (lo goes subnormal), which
@@ -567,33 +388,6 @@ int rl_synth_fill(float* dst, int64_t start, int64_t count, uint64_t seed, int k
     return launch_synth(dst, start, count, seed, kind, as_stream(stream));
 }
 
-// ---- a1 + a2 + a3 ----------------------------------------------------------------------------------
-int rl_pool_norm(const float* tokens, int64_t n_token_rows, int32_t dim, const int64_t* span_begin,
-                 const int64_t* span_end, int64_t n_spans, int32_t normalize, double eps, float* out_f32,
-                 uint16_t* out_f16, int mem, void* stream) {
-    if (dim <= 0 || n_token_rows < 0 || n_spans < 0) return fail(RL_ERR_INVALID, "rl_pool_norm: negative size");
-    if (n_spans > 0 && (!span_begin || !span_end)) return fail(RL_ERR_INVALID, "rl_pool_norm: null spans");
-    if (!out_f32 && !out_f16) return fail(RL_ERR_INVALID, "rl_pool_norm: no output requested");
-    if (!(eps >= 0.0)) return fail(RL_ERR_INVALID, "rl_pool_norm: eps must be >= 0");
-    if (n_spans == 0) return RL_OK;
-    hipStream_t s = as_stream(stream);
-    if (mem == RL_MEM_HOST) {  // validate the spans the host handed over (device callers own their spans)
-        for (int64_t i = 0; i < n_spans; ++i)
-            if (span_begin[i] < 0 || span_end[i] < span_begin[i] || span_end[i] > n_token_rows)
-                return fail(RL_ERR_INVALID, "rl_pool_norm: span outside the token matrix");
-    }
-    Staging st(mem, s);
-    const float* d_tok; const int64_t* d_b; const int64_t* d_e;
-    RL_TRY(st.in(tokens, (size_t)n_token_rows * dim, &d_tok));
-    RL_TRY(st.in(span_begin, (size_t)n_spans, &d_b));
-    RL_TRY(st.in(span_end, (size_t)n_spans, &d_e));
-    float* d_o32; uint16_t* d_o16;
-    RL_TRY(st.out(out_f32, (size_t)n_spans * dim, &d_o32));
-    RL_TRY(st.out(out_f16, (size_t)n_spans * dim, &d_o16));
-    RL_TRY(launch_pool_norm(d_tok, dim, d_b, d_e, n_spans, normalize, eps, d_o32, d_o16, s));
-    return st.finish();
-}
-
 // Below this many queries the stream kernel's per-32-query corpus passes (HBM-bound) beat a 128-query GEMM tile.
 constexpr int32_t GEMM_MIN_QUERIES = 96;
 // (a WIDE index -- dim > 1024 -- has no 32-queries-per-pass streaming kernel between the few-queries routes and the GEMM-shaped ones: its scan takes ONE
@@ -696,11 +490,7 @@ static int index_create_any(rl_index** out, const void* embeddings, bool f16, in
     idx->cap_chunks = n_chunks;
     // (an early error return destroys the index and with it whatever it holds so far)
     const char* who = "rl_index_create";
-    int dev = 0;
-    RL_HIP(hipGetDevice(&dev));
-    hipDeviceProp_t prop;
-    RL_HIP(hipGetDeviceProperties(&prop, dev));
-    idx->n_cu = prop.multiProcessorCount;
+    RL_TRY(device_cu_count(&idx->n_cu));
     const size_t elt = f16 ? sizeof(uint16_t) : sizeof(float);
     const void* dev_rows = embeddings;
     if (mem == RL_MEM_HOST) {
@@ -916,8 +706,7 @@ int rl_set_default_option(int key, int64_t value) {
 
 int rl_get_default_option(int key, int64_t* value) {
     if (!value || !option_key_ok(key)) return fail(RL_ERR_INVALID, "rl_get_default_option: unknown key");
-    std::lock_guard<std::mutex> lock(g_default_opts_mu);
-    *value = g_default_opts.v[key];
+    *value = default_option(key);
     return RL_OK;
 }
 
@@ -1550,21 +1339,6 @@ int select_from_scores(rl_index* idx, const float* d_qb, int32_t nb, int32_t k, 
     return RL_OK;
 }
 
-// The metadata filters and rank limits of a batch as the host describes them (the chunk bitsets are on the device): query b reads chunk
-// bitset filter_of(b) (-1: none) and cuts at limit_of(b) (n_rows: no cut).  The single-filter entry points give n <= 1 and no arrays.
-struct BatchFilters {
-    const uint32_t* chunk_bits = nullptr;  // device [n x (n_chunks + 31) / 32]
-    int32_t n = 0;
-    const int32_t* qf = nullptr;   // host [B]: each query's bitset (-1: none); nullptr: every query reads bitset 0 (when n > 0)
-    const int64_t* lim = nullptr;  // host [B]: each query's rank limit (0: no cut); nullptr: every query `limit`
-    int64_t limit = 0;
-    int32_t filter_of(int32_t b) const { return n == 0 ? -1 : qf ? qf[b] : 0; }
-    int64_t limit_of(int32_t b, int64_t n_rows) const {
-        const int64_t L = lim ? lim[b] : limit;
-        return L > 0 && L < n_rows ? L : n_rows;
-    }
-};
-
 // One sub-batch of a row search, planned on the host: the distinct chunk bitsets it reads (expanded to row bitsets in idx->maskbuf, one
 // per distinct filter), each query's row bitset among them and its rank limit.  Where all queries of the sub-batch agree, no map goes to
 // the device: a sub-batch whose queries have no filter and no cut is the unfiltered call, one whose queries share one filter and one limit
@@ -1696,6 +1470,10 @@ int search_rows_device(rl_index* idx, const float* d_q, int32_t B, int32_t k, fl
     return RL_OK;
 }
 
+}  // namespace
+}  // extern "C"
+
+namespace rl {
 int check_search_args(const rl_index* idx, const float* q, int32_t B, int32_t k, const char* who) {
     if (!idx) return fail(RL_ERR_INVALID, std::string(who) + ": null index");
     if (B < 0 || k < 1) return fail(RL_ERR_INVALID, std::string(who) + ": n_queries must be >= 0 and k >= 1");
@@ -1729,8 +1507,9 @@ int check_query_filters(int32_t B, const uint32_t* chunk_filters, int32_t n_filt
         if (rank_limits[b] < 0) return fail(RL_ERR_INVALID, std::string(who) + ": rank_limits[" + std::to_string(b) + "] must be >= 0 (0 = no cut)");
     return RL_OK;
 }
+}  // namespace rl
 
-}  // namespace
+extern "C" {
 
 int rl_search_rows_ranked(rl_index* idx, const float* queries, int32_t B, int32_t k, const uint32_t* chunk_filter,
                           int64_t rank_limit, float* out_scores, int32_t* out_rows, int mem, void* stream) {
@@ -2623,7 +2402,7 @@ int rl_maxsim_approx_scores(rl_index* idx, const float* query_vecs, int32_t n_qu
 
 }  // extern "C"
 
-namespace {
+namespace rl {
 // The device half of rl_maxsim_rerank on device pointers (under idx->mu, after use_scratch): d_q [n_queries x nq x dim],
 // d_c [n_queries x n_cand] -> d_o [n_queries x n_cand]
 int maxsim_rerank_device(rl_index* idx, const float* d_q, int32_t n_queries, int32_t nq, const int32_t* d_c, int32_t n_cand, float* d_o,
@@ -2645,7 +2424,7 @@ int maxsim_rerank_device(rl_index* idx, const float* d_q, int32_t n_queries, int
                                    n_queries, d_o, s);
     return st;
 }
-}  // namespace
+}  // namespace rl
 
 extern "C" {
 
@@ -2707,190 +2486,11 @@ int rl_topk(const float* scores, int32_t n_queries, int64_t n, int64_t ld, int32
     RL_TRY(st.out(out_scores, n_out, &d_os));
     RL_TRY(st.out(out_ids, n_out, &d_oi));
     SelectWorkspace ws;  // one-off workspace: this entry point is for tests / external scorers
-    {
-        std::lock_guard<std::mutex> lock(g_default_opts_mu);
-        ws.block_route = (int)g_default_opts.v[RL_OPT_TOPK_BLOCK];
-    }
+    ws.block_route = (int)default_option(RL_OPT_TOPK_BLOCK);
     const int rc = launch_topk(d_in, n_queries, n, ld, k, ws, d_os, d_oi, s);
     const int sy = rc == RL_OK ? st.finish_synced() : st.sync();  // the workspace is freed below, after an error too
     select_workspace_free(ws);
     return rc == RL_OK ? sy : rc;
-}
-
-// ---- document-batched ingestion: similarities, chunk / chunklet / sentence partitions (kernels in partition_sim.hip, partition_dp.hip,
-// ---- chunklet_dp.hip, sentence_dp.hip; the offset conventions in doc_batch.h) ---------------------------------------------------------
-// Host offsets are checked here, before the first HIP call; device offsets are clamped by the kernels (doc_batch.h).  doc_max > 0:
-// every document must be shorter than that many rows; its one caller is rl_partition_sentences with 2^31, which the text names.
-static int check_doc_offsets(const char* who, const int64_t* off, int64_t n, int64_t n_docs, int mem, int64_t doc_max) {
-    if (mem != RL_MEM_HOST) return RL_OK;
-    const std::string w(who);
-    if (off[0] != 0) return fail(RL_ERR_INVALID, w + ": doc_offsets must start at 0");
-    for (int64_t d = 0; d < n_docs; ++d) {
-        if (off[d + 1] < off[d]) return fail(RL_ERR_INVALID, w + ": doc_offsets must be ascending");
-        if (doc_max > 0 && off[d + 1] - off[d] >= doc_max) return fail(RL_ERR_INVALID, w + ": a document must be shorter than 2^31 characters");
-    }
-    if (off[n_docs] != n) return fail(RL_ERR_INVALID, w + ": doc_offsets must end at n");
-    return RL_OK;
-}
-
-int rl_partition_similarity(const float* X, int64_t n, int32_t dim, const int64_t* doc_offsets, int64_t n_docs,
-                            const uint8_t* nonoutlying, float* out, int mem, void* stream) {
-    if (n < 0 || dim <= 0) return fail(RL_ERR_INVALID, "rl_partition_similarity: bad shape");
-    if (n == 0) return RL_OK;
-    if (!X || !out) return fail(RL_ERR_INVALID, "rl_partition_similarity: null argument");
-    if (dim > 4096) return fail(RL_ERR_UNSUPPORTED, "rl_partition_similarity: dim must be <= 4096");
-    if (!doc_offsets) n_docs = 1;
-    if (n_docs < 1) return fail(RL_ERR_INVALID, "rl_partition_similarity: need at least one document");
-    if (doc_offsets) RL_TRY(check_doc_offsets("rl_partition_similarity", doc_offsets, n, n_docs, mem, 0));
-    hipStream_t s = as_stream(stream);
-    Staging st(mem, s);
-    const float* d_x; const int64_t* d_off; const uint8_t* d_sel = nullptr; float* d_out;
-    RL_TRY(st.in(X, (size_t)n * dim, &d_x));
-    const int64_t one[2] = {0, n};  // one document: offsets made here (outlives the copy: the call ends synchronised)
-    if (doc_offsets) RL_TRY(st.in(doc_offsets, (size_t)n_docs + 1, &d_off));
-    else RL_TRY(st.in(one, 2, &d_off, RL_MEM_HOST));
-    if (nonoutlying) RL_TRY(st.in(nonoutlying, (size_t)n, &d_sel));
-    RL_TRY(st.out(out, (size_t)n, &d_out));
-    void* d_scr;
-    RL_TRY(st.temp(partition_sim_scratch_bytes(n, n_docs, dim), &d_scr));
-    RL_TRY(launch_partition_similarity(d_x, n, dim, d_off, n_docs, d_sel, d_out, d_scr, s));
-    return st.finish();
-}
-
-// Argument checks shared by rl_partition_chunks, rl_split_chunks and rl_partition_chunklets; all of them return before the first HIP call.
-static int partition_args(const char* who, const int64_t* sizes, const int64_t* doc_offsets, int64_t n, int64_t n_docs, const uint8_t* cut,
-                          const int32_t* status, int mem) {
-    const std::string w(who);
-    if (n_docs < 1) return fail(RL_ERR_INVALID, w + ": n_docs must be >= 1");
-    if (!sizes) return fail(RL_ERR_INVALID, w + ": sizes is null");
-    if (!doc_offsets) return fail(RL_ERR_INVALID, w + ": doc_offsets is null");
-    if (!cut) return fail(RL_ERR_INVALID, w + ": cut is null");
-    if (!status) return fail(RL_ERR_INVALID, w + ": status is null");
-    RL_TRY(check_doc_offsets(who, doc_offsets, n, n_docs, mem, 0));
-    if (mem == RL_MEM_HOST) {
-        for (int64_t i = 0; i < n; ++i)
-            if (sizes[i] < 0) return fail(RL_ERR_INVALID, w + ": sizes must be >= 0");
-    }
-    return RL_OK;
-}
-
-int rl_partition_chunks(const float* cost, const int64_t* sizes, const int64_t* doc_offsets, int64_t n, int64_t n_docs, int64_t max_size,
-                        uint8_t* cut, double* objective, int32_t* status, int mem, void* stream) {
-    if (n < 0) return fail(RL_ERR_INVALID, "rl_partition_chunks: n must be >= 0");
-    if (max_size < 1) return fail(RL_ERR_INVALID, "rl_partition_chunks: max_size must be >= 1");
-    if (mem != RL_MEM_HOST && mem != RL_MEM_DEVICE) return fail(RL_ERR_INVALID, "rl_partition_chunks: bad mem");
-    if (n == 0) return RL_OK;
-    if (!cost) return fail(RL_ERR_INVALID, "rl_partition_chunks: cost is null");
-    RL_TRY(partition_args("rl_partition_chunks", sizes, doc_offsets, n, n_docs, cut, status, mem));
-    hipStream_t s = as_stream(stream);
-    Staging st(mem, s);
-    const float* d_c; const int64_t* d_sz; const int64_t* d_off;
-    RL_TRY(st.in(cost, (size_t)n, &d_c));
-    RL_TRY(st.in(sizes, (size_t)n, &d_sz));
-    RL_TRY(st.in(doc_offsets, (size_t)n_docs + 1, &d_off));
-    uint8_t* d_cut; double* d_obj; int32_t* d_status;
-    RL_TRY(st.out(cut, (size_t)n, &d_cut));
-    RL_TRY(st.out(objective, (size_t)n_docs, &d_obj));  // (optional)
-    RL_TRY(st.out(status, (size_t)n_docs, &d_status));
-    void* d_scr;
-    RL_TRY(st.temp(partition_dp_scratch_bytes(n), &d_scr));
-    RL_TRY(launch_partition_dp(d_c, d_sz, nullptr, d_off, n, n_docs, max_size, d_cut, d_obj, d_status, d_scr, s));
-    return st.finish();
-}
-
-int rl_split_chunks(const float* X, int64_t n, int32_t dim, const int64_t* doc_offsets, int64_t n_docs, const uint8_t* nonoutlying,
-                    const uint8_t* is_heading, const int64_t* sizes, int64_t max_size, uint8_t* cut, float* cost_out, double* objective,
-                    int32_t* status, int mem, void* stream) {
-    if (n < 0 || dim <= 0) return fail(RL_ERR_INVALID, "rl_split_chunks: bad shape (n, dim)");
-    if (max_size < 1) return fail(RL_ERR_INVALID, "rl_split_chunks: max_size must be >= 1");
-    if (mem != RL_MEM_HOST && mem != RL_MEM_DEVICE) return fail(RL_ERR_INVALID, "rl_split_chunks: bad mem");
-    if (n == 0) return RL_OK;
-    if (!X) return fail(RL_ERR_INVALID, "rl_split_chunks: X is null");
-    RL_TRY(partition_args("rl_split_chunks", sizes, doc_offsets, n, n_docs, cut, status, mem));
-    if (dim > 4096) return fail(RL_ERR_UNSUPPORTED, "rl_split_chunks: dim must be <= 4096");
-    hipStream_t s = as_stream(stream);
-    Staging st(mem, s);
-    const float* d_x; const int64_t* d_sz; const int64_t* d_off; const uint8_t* d_sel = nullptr; const uint8_t* d_head = nullptr;
-    float* d_cost;
-    RL_TRY(st.in(X, (size_t)n * dim, &d_x));
-    RL_TRY(st.in(sizes, (size_t)n, &d_sz));
-    RL_TRY(st.in(doc_offsets, (size_t)n_docs + 1, &d_off));
-    if (nonoutlying) RL_TRY(st.in(nonoutlying, (size_t)n, &d_sel));
-    if (is_heading) RL_TRY(st.in(is_heading, (size_t)n, &d_head));
-    uint8_t* d_cut; double* d_obj; int32_t* d_status;
-    RL_TRY(st.out(cut, (size_t)n, &d_cut));
-    RL_TRY(st.out(objective, (size_t)n_docs, &d_obj));  // (optional)
-    RL_TRY(st.out(status, (size_t)n_docs, &d_status));
-    RL_TRY(st.out_or_temp(cost_out, (size_t)n, &d_cost));
-    void* d_scr;
-    RL_TRY(st.temp(partition_sim_scratch_bytes(n, n_docs, dim), &d_scr));
-    void* d_dp;
-    RL_TRY(st.temp(partition_dp_scratch_bytes(n), &d_dp));
-    RL_TRY(launch_partition_similarity(d_x, n, dim, d_off, n_docs, d_sel, d_cost, d_scr, s));
-    if (d_head) RL_TRY(launch_partition_headings(d_cost, d_head, d_off, n_docs, n, s));  // in place: entry i reads sim[i] alone
-    RL_TRY(launch_partition_dp(d_cost, d_sz, static_cast<float*>(d_scr) /* 1 / |x_i| */, d_off, n, n_docs, max_size, d_cut, d_obj, d_status,
-                               d_dp, s));
-    return st.finish();
-}
-
-int rl_partition_chunklets(const double* boundary, const double* statements, const int64_t* lengths, const int64_t* doc_offsets, int64_t n,
-                           int64_t n_docs, int64_t max_size, uint8_t* cut, double* objective, int32_t* status, int mem, void* stream) {
-    if (n < 0) return fail(RL_ERR_INVALID, "rl_partition_chunklets: n must be >= 0");
-    if (max_size < 1) return fail(RL_ERR_INVALID, "rl_partition_chunklets: max_size must be >= 1");
-    if (mem != RL_MEM_HOST && mem != RL_MEM_DEVICE) return fail(RL_ERR_INVALID, "rl_partition_chunklets: bad mem");
-    if (n == 0) return RL_OK;
-    if (!boundary) return fail(RL_ERR_INVALID, "rl_partition_chunklets: boundary is null");
-    if (!statements) return fail(RL_ERR_INVALID, "rl_partition_chunklets: statements is null");
-    RL_TRY(partition_args("rl_partition_chunklets", lengths, doc_offsets, n, n_docs, cut, status, mem));
-    hipStream_t s = as_stream(stream);
-    Staging st(mem, s);
-    const double* d_b; const double* d_s; const int64_t* d_len; const int64_t* d_off;
-    RL_TRY(st.in(boundary, (size_t)n, &d_b));
-    RL_TRY(st.in(statements, (size_t)n, &d_s));
-    RL_TRY(st.in(lengths, (size_t)n, &d_len));
-    RL_TRY(st.in(doc_offsets, (size_t)n_docs + 1, &d_off));
-    uint8_t* d_cut; double* d_obj; int32_t* d_status;
-    RL_TRY(st.out(cut, (size_t)n, &d_cut));
-    RL_TRY(st.out(objective, (size_t)n_docs, &d_obj));  // (optional)
-    RL_TRY(st.out(status, (size_t)n_docs, &d_status));
-    void* d_scr;
-    RL_TRY(st.temp(chunklet_dp_scratch_bytes(n, n_docs), &d_scr));
-    RL_TRY(launch_chunklet_dp(d_b, d_s, d_len, d_off, n, n_docs, max_size, d_cut, d_obj, d_status, d_scr, s));
-    return st.finish();
-}
-
-int rl_partition_sentences(const uint32_t* codepoints, const void* probas, int probas_f64, const double* known, const int64_t* doc_offsets,
-                           int64_t n, int64_t n_docs, int64_t min_len, int64_t max_len, uint8_t* cut, double* objective, int32_t* status,
-                           int mem, void* stream) {
-    if (n < 0) return fail(RL_ERR_INVALID, "rl_partition_sentences: n must be >= 0");
-    if (min_len < 1) return fail(RL_ERR_INVALID, "rl_partition_sentences: min_len must be >= 1");
-    if (max_len < 0) return fail(RL_ERR_INVALID, "rl_partition_sentences: max_len must be >= 0 (0: none)");
-    if (mem != RL_MEM_HOST && mem != RL_MEM_DEVICE) return fail(RL_ERR_INVALID, "rl_partition_sentences: bad mem");
-    if (n == 0) return RL_OK;
-    if (n_docs < 1) return fail(RL_ERR_INVALID, "rl_partition_sentences: n_docs must be >= 1");
-    if (!codepoints) return fail(RL_ERR_INVALID, "rl_partition_sentences: codepoints is null");
-    if (!probas) return fail(RL_ERR_INVALID, "rl_partition_sentences: probas is null");
-    if (!doc_offsets) return fail(RL_ERR_INVALID, "rl_partition_sentences: doc_offsets is null");
-    if (!cut) return fail(RL_ERR_INVALID, "rl_partition_sentences: cut is null");
-    if (!status) return fail(RL_ERR_INVALID, "rl_partition_sentences: status is null");
-    const int64_t doc_max = (int64_t)1 << 31;  // back-pointers are int32
-    if (n_docs == 1 && n >= doc_max) return fail(RL_ERR_INVALID, "rl_partition_sentences: a document must be shorter than 2^31 characters");
-    RL_TRY(check_doc_offsets("rl_partition_sentences", doc_offsets, n, n_docs, mem, doc_max));
-    hipStream_t s = as_stream(stream);
-    Staging st(mem, s);
-    const uint32_t* d_cp; const uint8_t* d_p; const double* d_k = nullptr; const int64_t* d_off;
-    RL_TRY(st.in(codepoints, (size_t)n, &d_cp));
-    RL_TRY(st.in(static_cast<const uint8_t*>(probas), (size_t)n * (probas_f64 ? 8 : 4), &d_p));
-    if (known) RL_TRY(st.in(known, (size_t)n, &d_k));
-    RL_TRY(st.in(doc_offsets, (size_t)n_docs + 1, &d_off));
-    uint8_t* d_cut; double* d_obj; int32_t* d_status;
-    RL_TRY(st.out(cut, (size_t)n, &d_cut));
-    RL_TRY(st.out(objective, (size_t)n_docs, &d_obj));  // (optional)
-    RL_TRY(st.out(status, (size_t)n_docs, &d_status));
-    void* d_scr;
-    RL_TRY(st.temp(sentence_dp_scratch_bytes(n, n_docs), &d_scr));
-    RL_TRY(launch_sentence_dp(d_cp, d_p, probas_f64, d_k, d_off, n, n_docs, min_len, max_len, d_cut, d_obj, d_status, d_scr, s));
-    return st.finish();
 }
 
 // ---- query adapter fit (kernels in adapter_fit.hip and query_targets.hip) ---------------------------------------------------------------
@@ -2936,7 +2536,7 @@ int rl_query_targets(rl_index* idx, const float* queries, int32_t B, const int32
     if (B < 1) return fail(RL_ERR_INVALID, "rl_query_targets: n_queries must be >= 1");
     if (k < 2 || k > RL_QT_MAX_EXAMPLES) return fail(RL_ERR_INVALID, "rl_query_targets: n_examples must be 2 .. 64");
     if (!(gap >= 0.0) || !std::isfinite(gap)) return fail(RL_ERR_INVALID, "rl_query_targets: gap must be finite and >= 0");
-    if (mem != RL_MEM_HOST && mem != RL_MEM_DEVICE) return fail(RL_ERR_INVALID, "rl_query_targets: bad mem");
+    RL_TRY(check_mem(mem, "rl_query_targets"));
     if (!queries) return fail(RL_ERR_INVALID, "rl_query_targets: queries is null");
     if (!rows) return fail(RL_ERR_INVALID, "rl_query_targets: rows is null");
     if (!relevant) return fail(RL_ERR_INVALID, "rl_query_targets: relevant is null");
@@ -3069,1427 +2669,6 @@ int rl_time_kernel(rl_index* idx, int kind, const float* q_dev, int32_t nq, int3
     (void)hipEventDestroy(e1);
     *out_ms_total = ms;
     return st;
-}
-
-}  // extern "C"
-
-// ---- BM25 keyword search (include/raglite_hip.h; kernels in keyword.hip) -------------------------------------------------------
-struct rl_keyword_index {
-    int32_t n_terms = 0;
-    int64_t n_postings = 0;
-    int64_t n_chunks = 0;
-    int n_cu = 256;
-    rl::DevArray<int64_t> term_off;     // [n_terms + 1]
-    rl::DevArray<int32_t> post_chunk;   // [n_postings], ascending within a term
-    rl::DevArray<float> post_impact;    // [n_postings]
-    std::mutex mu;
-    rl::SelectWorkspace ws;
-    rl::Pool scores;                    // [B x ld] chunk scores of a (sub-)batch
-    rl::Pool qmap;                      // [B] the chunk bitset of each query of a per-query filtered call
-    hipStream_t last_stream = nullptr;
-    bool last_stream_set = false;
-    ~rl_keyword_index() { rl::select_workspace_free(ws); }
-};
-
-namespace rl {
-namespace {
-
-// The host postings as the header states them; device postings are taken as given (the kernels skip what lies outside them).
-int check_host_postings(const int64_t* term_off, int32_t n_terms, const int32_t* post_chunk, const int32_t* post_tf, const int32_t* post_term,
-                        int64_t n_postings, int64_t n_chunks) {
-    const char* who = "rl_keyword_index_create";
-    if (term_off[0] != 0 || term_off[n_terms] != n_postings)
-        return fail(RL_ERR_INVALID, std::string(who) + ": term_off must start at 0 and end at n_postings");
-    for (int32_t t = 0; t < n_terms; ++t) {
-        if (term_off[t + 1] < term_off[t]) return fail(RL_ERR_INVALID, std::string(who) + ": term_off must be ascending");
-        for (int64_t p = term_off[t]; p < term_off[t + 1]; ++p) {
-            if (post_chunk[p] < 0 || post_chunk[p] >= n_chunks) return fail(RL_ERR_INVALID, std::string(who) + ": chunk ordinal out of range");
-            if (p > term_off[t] && post_chunk[p] <= post_chunk[p - 1])
-                return fail(RL_ERR_INVALID, std::string(who) + ": the chunks of a term must be strictly ascending");
-            if (post_tf[p] < 1) return fail(RL_ERR_INVALID, std::string(who) + ": term frequencies must be >= 1");
-            if (post_term[p] != t) return fail(RL_ERR_INVALID, std::string(who) + ": post_term disagrees with term_off");
-        }
-    }
-    return RL_OK;
-}
-
-// A call on another stream than the handle's previous one first waits for that stream (the handle's scratch is shared).
-int keyword_use_stream(rl_keyword_index* kw, hipStream_t s) {
-    if (kw->last_stream_set && kw->last_stream != s) RL_HIP(hipStreamSynchronize(kw->last_stream));
-    kw->last_stream = s;
-    kw->last_stream_set = true;
-    return RL_OK;
-}
-
-// The device half of rl_keyword_search on device pointers (under kw->mu, after keyword_use_stream): d_s / d_c [B x k], d_n [B]
-int keyword_search_device(rl_keyword_index* kw, const int64_t* d_off, const int32_t* d_terms, int32_t n_queries, int32_t k, const QueryMask& d_f,
-                          float* d_s, int32_t* d_c, int32_t* d_n, hipStream_t s) {
-    const int64_t n = kw->n_chunks;
-    const size_t n_out = (size_t)n_queries * k;
-    if (n == 0) {  // no chunks: every slot is padding
-        RL_TRY(launch_fill_f32(d_s, -std::numeric_limits<float>::infinity(), (int64_t)n_out, s));
-        RL_HIP(hipMemsetAsync(d_c, 0xff, n_out * sizeof(int32_t), s));
-    } else {
-        const int64_t ld = (n + 3) & ~int64_t(3);
-        // (a sub-batch is one grid row per query: at most 65535 of them)
-        const int32_t batch = (int32_t)std::max<int64_t>(1, std::min<int64_t>({(int64_t)n_queries, int64_t(65535),
-                                                                                (int64_t)(SCORE_BATCH_BYTES / ((size_t)ld * 4))}));
-        RL_TRY(kw->scores.reserve((size_t)batch * ld * sizeof(float)));
-        for (int32_t b0 = 0; b0 < n_queries; b0 += batch) {
-            const int32_t nb = std::min<int32_t>(batch, n_queries - b0);
-            RL_TRY(launch_bm25_score(kw->term_off, kw->post_chunk, kw->post_impact, kw->n_terms, n, d_off + b0, d_terms, nb, d_f.from(b0),
-                                     bm25_tile(n, nb, kw->n_cu), kw->scores.as<float>(), ld, s));
-            RL_TRY(launch_topk(kw->scores.as<float>(), nb, n, ld, k, kw->ws, d_s + (int64_t)b0 * k, d_c + (int64_t)b0 * k, s));
-        }
-        RL_TRY(launch_fix_masked(d_s, d_c, (int64_t)n_out, s));  // chunks without a query term are "no hit": (-inf, -1)
-    }
-    return launch_bm25_count(d_s, n_queries, k, d_n, s);
-}
-
-// The chunk bitset each query of a keyword search reads (d_filters [n_filters x (n_chunks + 31) / 32] on the device; query_filter: host,
-// nullptr: every query reads bitset 0 when n_filters > 0).  Where every query reads the same bitset, no map goes to the device.
-int keyword_mask(rl_keyword_index* kw, const uint32_t* d_filters, int32_t n_filters, const int32_t* query_filter, int32_t B, hipStream_t s,
-                 QueryMask* out) {
-    *out = QueryMask();
-    if (n_filters == 0 || B == 0) return RL_OK;
-    if (!query_filter) { *out = QueryMask(d_filters); return RL_OK; }
-    const int64_t cw = (kw->n_chunks + 31) / 32;
-    if (std::all_of(query_filter, query_filter + B, [&](int32_t f) { return f == query_filter[0]; })) {
-        if (query_filter[0] >= 0) *out = QueryMask(d_filters + (int64_t)query_filter[0] * cw);
-        return RL_OK;
-    }
-    RL_TRY(kw->qmap.reserve((size_t)B * sizeof(int32_t)));
-    RL_HIP(hipMemcpyAsync(kw->qmap.p, query_filter, (size_t)B * sizeof(int32_t), hipMemcpyHostToDevice, s));  // (pageable: consumed on return)
-    *out = QueryMask(d_filters, cw, kw->qmap.as<int32_t>(), nullptr);
-    return RL_OK;
-}
-
-// q_off as rl_keyword_search states it (host pointers only)
-int check_host_q_off(const int64_t* q_off, const int32_t* q_terms, int32_t n_queries, const char* who) {
-    if (q_off[0] != 0) return fail(RL_ERR_INVALID, std::string(who) + ": q_off must start at 0");
-    for (int32_t b = 0; b < n_queries; ++b)
-        if (q_off[b + 1] < q_off[b]) return fail(RL_ERR_INVALID, std::string(who) + ": q_off must be ascending");
-    if (q_off[n_queries] > 0 && !q_terms) return fail(RL_ERR_INVALID, std::string(who) + ": null q_terms");
-    return RL_OK;
-}
-
-// A fresh handle with its sizes, the default top-k route and the device's CU count; the arrays are the caller's to fill.
-int new_keyword_index(int32_t n_terms, int64_t n_postings, int64_t n_chunks, std::unique_ptr<rl_keyword_index>* out) {
-    std::unique_ptr<rl_keyword_index> kw(new rl_keyword_index());
-    kw->n_terms = n_terms;
-    kw->n_postings = n_postings;
-    kw->n_chunks = n_chunks;
-    {
-        std::lock_guard<std::mutex> lock(g_default_opts_mu);
-        kw->ws.block_route = (int)g_default_opts.v[RL_OPT_TOPK_BLOCK];
-    }
-    int dev = 0;
-    RL_HIP(hipGetDevice(&dev));
-    hipDeviceProp_t prop;
-    RL_HIP(hipGetDeviceProperties(&prop, dev));
-    kw->n_cu = prop.multiProcessorCount;
-    *out = std::move(kw);
-    return RL_OK;
-}
-
-// rl_rrf_fuse's limits (weights: host memory)
-int check_fuse_args(int32_t n_lists, int32_t n_queries, int32_t len, const double* weights, int32_t rrf_k, int32_t k, const char* who) {
-    if (n_lists < 1 || n_lists > RRF_MAX_LISTS) return fail(RL_ERR_INVALID, std::string(who) + ": n_lists must be in [1, 4]");
-    if (n_queries < 0 || len < 1) return fail(RL_ERR_INVALID, std::string(who) + ": n_queries must be >= 0 and len >= 1");
-    if ((int64_t)n_lists * len > RRF_MAX_ENTRIES) return fail(RL_ERR_INVALID, std::string(who) + ": n_lists * len must be <= 4096");
-    if (k < 1 || k > n_lists * len) return fail(RL_ERR_INVALID, std::string(who) + ": k must be in [1, n_lists * len]");
-    if (rrf_k < 1 || rrf_k > RRF_MAX_K) return fail(RL_ERR_INVALID, std::string(who) + ": rrf_k must be in [1, 2^30]");
-    if (!weights) return fail(RL_ERR_INVALID, std::string(who) + ": null weights");
-    for (int32_t r = 0; r < n_lists; ++r)
-        if (!(std::fabs(weights[r]) <= RRF_MAX_WEIGHT))
-            return fail(RL_ERR_INVALID, std::string(who) + ": weights must be finite, of magnitude <= 2^1000");
-    return RL_OK;
-}
-
-}  // namespace
-}  // namespace rl
-
-extern "C" {
-
-int rl_keyword_index_create(rl_keyword_index** out, const int64_t* term_off, int32_t n_terms, const int32_t* post_chunk, const int32_t* post_tf,
-                            const int32_t* post_term, int64_t n_postings, const float* idf, const float* nrm, int64_t n_chunks, int mem,
-                            void* stream) {
-    const char* who = "rl_keyword_index_create";
-    if (!out) return fail(RL_ERR_INVALID, "rl_keyword_index_create: null output handle");
-    *out = nullptr;
-    if (n_terms < 0 || n_postings < 0 || n_chunks < 0) return fail(RL_ERR_INVALID, "rl_keyword_index_create: negative size");
-    if (n_chunks >= (int64_t)0x7fffffff - 1) return fail(RL_ERR_UNSUPPORTED, "rl_keyword_index_create: more than 2^31-2 chunks");
-    if (!term_off || (n_postings > 0 && (!post_chunk || !post_tf || !post_term)) || (n_terms > 0 && !idf) || (n_chunks > 0 && !nrm))
-        return fail(RL_ERR_INVALID, "rl_keyword_index_create: null argument");
-    if (mem != RL_MEM_HOST && mem != RL_MEM_DEVICE) return fail(RL_ERR_INVALID, "rl_keyword_index_create: bad mem");
-    if (mem == RL_MEM_HOST) RL_TRY(check_host_postings(term_off, n_terms, post_chunk, post_tf, post_term, n_postings, n_chunks));
-    hipStream_t s = as_stream(stream);
-    std::unique_ptr<rl_keyword_index> kw;
-    RL_TRY(new_keyword_index(n_terms, n_postings, n_chunks, &kw));
-    const size_t np = (size_t)n_postings;
-    RL_TRY(kw->term_off.alloc((size_t)(n_terms + 1) * sizeof(int64_t), who));
-    RL_TRY(kw->post_chunk.alloc(std::max<size_t>(np * sizeof(int32_t), 16), who));
-    RL_TRY(kw->post_impact.alloc(std::max<size_t>(np * sizeof(float), 16), who));
-    RL_HIP(hipMemcpyAsync(kw->term_off, term_off, (size_t)(n_terms + 1) * sizeof(int64_t),
-                          mem == RL_MEM_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, s));
-    if (np) RL_HIP(hipMemcpyAsync(kw->post_chunk, post_chunk, np * sizeof(int32_t), mem == RL_MEM_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, s));
-    Staging st(mem, s);
-    const int32_t *d_tf, *d_term;
-    const float *d_idf, *d_nrm;
-    RL_TRY(st.in(post_tf, np, &d_tf));
-    RL_TRY(st.in(post_term, np, &d_term));
-    RL_TRY(st.in(idf, (size_t)n_terms, &d_idf));
-    RL_TRY(st.in(nrm, (size_t)n_chunks, &d_nrm));
-    RL_TRY(launch_bm25_impact(kw->post_chunk, d_tf, d_term, d_idf, d_nrm, n_postings, n_terms, n_chunks, kw->post_impact, s));
-    RL_TRY(st.sync());  // the staging buffers and the caller's arrays may go away after return
-    *out = kw.release();
-    return RL_OK;
-}
-
-int rl_keyword_index_destroy(rl_keyword_index* kw) {
-    if (!kw) return RL_OK;
-    delete kw;
-    return RL_OK;
-}
-
-int rl_keyword_index_info(const rl_keyword_index* kw, int32_t* n_terms, int64_t* n_postings, int64_t* n_chunks) {
-    if (!kw) return fail(RL_ERR_INVALID, "rl_keyword_index_info: null index");
-    if (n_terms) *n_terms = kw->n_terms;
-    if (n_postings) *n_postings = kw->n_postings;
-    if (n_chunks) *n_chunks = kw->n_chunks;
-    return RL_OK;
-}
-
-int rl_keyword_index_read(const rl_keyword_index* kw, int64_t* term_off, int32_t* post_chunk, float* post_impact, int mem, void* stream) {
-    if (!kw) return fail(RL_ERR_INVALID, "rl_keyword_index_read: null index");
-    if (mem != RL_MEM_HOST && mem != RL_MEM_DEVICE) return fail(RL_ERR_INVALID, "rl_keyword_index_read: bad mem");
-    hipStream_t s = as_stream(stream);
-    const hipMemcpyKind kind = mem == RL_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
-    const size_t np = (size_t)kw->n_postings;
-    if (term_off) RL_HIP(hipMemcpyAsync(term_off, kw->term_off, (size_t)(kw->n_terms + 1) * sizeof(int64_t), kind, s));
-    if (post_chunk && np) RL_HIP(hipMemcpyAsync(post_chunk, kw->post_chunk, np * sizeof(int32_t), kind, s));
-    if (post_impact && np) RL_HIP(hipMemcpyAsync(post_impact, kw->post_impact, np * sizeof(float), kind, s));
-    if (mem == RL_MEM_HOST) RL_HIP(hipStreamSynchronize(s));
-    return RL_OK;
-}
-
-}  // extern "C"
-
-// ---- keyword store: the chunks' term ids on the device, and the postings built from them (kernels in keyword_build.hip) -------------
-struct rl_keyword_store {
-    int64_t n_chunks = 0, n_tokens = 0, n_live = 0;
-    int64_t cap_off = 0, cap_live = 0, cap_tokens = 0;  // items the three arrays can hold
-    int32_t max_id = -1;                  // the largest term id ever stored
-    rl::DevArray<int64_t> tok_off;        // [n_chunks + 1]
-    rl::DevArray<int32_t> tok_term;       // [n_tokens]
-    rl::DevArray<uint8_t> live;           // [n_chunks]: 1 = live
-    std::vector<uint8_t> h_live;          // host copy of `live`
-    std::mutex mu;
-    // what rl_keyword_store_count left for rl_keyword_store_build (dropped by an append or a delete)
-    bool counted = false;
-    int32_t c_terms = 0;
-    int64_t c_postings = 0, c_chunks = 0;
-    rl::DevArray<int64_t> term_off;       // fresh per count: these two become the index' own
-    rl::DevArray<int32_t> post_chunk;
-    rl::DevArray<int32_t> post_term, post_tf;  // [c_postings], kept with the scratch below
-    // Scratch of count, kept between calls with amortised capacity (an insert changes every size a little, and allocating ~24 B per
-    // token afresh costs more than the kernels: DESIGN.md 4.12): lengths, their scan, the scan levels, the (key, value) planes of the
-    // sort, its (digit, block) table, the head counts and positions, df
-    rl::Pool lens, offs, scan_scratch, sortbuf, table, heads, head_pos, df;
-    void drop_count() {
-        counted = false;
-        term_off.release();
-        post_chunk.release();
-    }
-    size_t device_bytes() const {
-        return tok_off.cap + tok_term.cap + live.cap + term_off.cap + post_term.cap + post_chunk.cap + post_tf.cap + lens.cap + offs.cap +
-               scan_scratch.cap + sortbuf.cap + table.cap + heads.cap + head_pos.cap + df.cap;
-    }
-};
-
-namespace rl {
-namespace {
-
-// Room for `need` items in an array that holds `used`: a fresh block of amortised capacity, the contents copied on the device.
-// Scratch that grows by a quarter more than asked for, so that the next few inserts fit (Pool::reserve keeps a block that is large enough).
-int reserve_amortised(Pool& pool, size_t bytes, const char* who) {
-    if (bytes <= pool.cap) return RL_OK;
-    return pool.alloc(bytes + bytes / 4, who);
-}
-
-template <class T>
-int store_grow(DevArray<T>& arr, int64_t* cap, int64_t used, int64_t need, hipStream_t s, const char* who) {
-    if (need <= *cap) return RL_OK;
-    const int64_t want = std::max<int64_t>({need, *cap + *cap / 2, 1024});
-    DevArray<T> bigger;
-    RL_TRY(bigger.alloc((size_t)want * sizeof(T), who));
-    if (used > 0) RL_TRY(hip_status(hipMemcpyAsync(bigger.p, arr.p, (size_t)used * sizeof(T), hipMemcpyDeviceToDevice, s), who));
-    RL_TRY(hip_status(hipStreamSynchronize(s), who));  // (the old block goes now)
-    arr = std::move(bigger);
-    *cap = want;
-    return RL_OK;
-}
-
-}  // namespace
-}  // namespace rl
-
-extern "C" {
-
-int rl_keyword_store_create(rl_keyword_store** out) {
-    if (!out) return fail(RL_ERR_INVALID, "rl_keyword_store_create: null output handle");
-    *out = new rl_keyword_store();
-    return RL_OK;
-}
-
-int rl_keyword_store_destroy(rl_keyword_store* st) {
-    if (!st) return RL_OK;
-    delete st;
-    return RL_OK;
-}
-
-int rl_keyword_store_info(const rl_keyword_store* st, int64_t* n_chunks, int64_t* n_live, int64_t* n_tokens, int64_t* device_bytes) {
-    if (!st) return fail(RL_ERR_INVALID, "rl_keyword_store_info: null store");
-    std::lock_guard<std::mutex> lock(const_cast<rl_keyword_store*>(st)->mu);
-    if (n_chunks) *n_chunks = st->n_chunks;
-    if (n_live) *n_live = st->n_live;
-    if (n_tokens) *n_tokens = st->n_tokens;
-    if (device_bytes) *device_bytes = (int64_t)st->device_bytes();
-    return RL_OK;
-}
-
-int rl_keyword_store_append(rl_keyword_store* st, const int32_t* term_ids, const int64_t* offsets, int64_t n_new_chunks, int mem, void* stream) {
-    const char* who = "rl_keyword_store_append";
-    if (!st) return fail(RL_ERR_INVALID, std::string(who) + ": null store");
-    if (n_new_chunks < 0) return fail(RL_ERR_INVALID, std::string(who) + ": negative size");
-    if (mem != RL_MEM_HOST && mem != RL_MEM_DEVICE) return fail(RL_ERR_INVALID, std::string(who) + ": bad mem");
-    if (n_new_chunks == 0) return RL_OK;
-    if (!offsets) return fail(RL_ERR_INVALID, std::string(who) + ": null offsets");
-    hipStream_t s = as_stream(stream);
-    const hipMemcpyKind in_kind = mem == RL_MEM_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice;
-    std::vector<int64_t> h_off((size_t)n_new_chunks + 1);
-    if (mem == RL_MEM_HOST) std::memcpy(h_off.data(), offsets, h_off.size() * sizeof(int64_t));
-    else {
-        RL_TRY(hip_status(hipMemcpyAsync(h_off.data(), offsets, h_off.size() * sizeof(int64_t), hipMemcpyDeviceToHost, s), who));
-        RL_TRY(hip_status(hipStreamSynchronize(s), who));
-    }
-    if (h_off[0] != 0) return fail(RL_ERR_INVALID, std::string(who) + ": offsets must start at 0");
-    for (int64_t c = 0; c < n_new_chunks; ++c)
-        if (h_off[c + 1] < h_off[c]) return fail(RL_ERR_INVALID, std::string(who) + ": offsets must be ascending");
-    const int64_t n_add = h_off[n_new_chunks];
-    if (n_add > 0 && !term_ids) return fail(RL_ERR_INVALID, std::string(who) + ": null term_ids");
-    int32_t range[2] = {std::numeric_limits<int32_t>::max(), std::numeric_limits<int32_t>::min()};  // min, max of the new ids
-    if (mem == RL_MEM_HOST) {
-        for (int64_t i = 0; i < n_add; ++i) {
-            range[0] = std::min(range[0], term_ids[i]);
-            range[1] = std::max(range[1], term_ids[i]);
-        }
-    } else if (n_add > 0) {
-        Staging up(RL_MEM_HOST, s);
-        const int32_t* d_range;
-        RL_TRY(up.in(range, 2, &d_range));
-        RL_TRY(launch_kb_minmax(term_ids, n_add, const_cast<int32_t*>(d_range), s));  // (folds the ids into the staged copy, which is this call's own)
-        RL_TRY(hip_status(hipMemcpyAsync(range, d_range, sizeof(range), hipMemcpyDeviceToHost, s), who));
-        RL_TRY(hip_status(hipStreamSynchronize(s), who));
-        up.drain();
-    }
-    if (n_add > 0 && range[0] < 0) return fail(RL_ERR_INVALID, std::string(who) + ": negative term id");
-    std::lock_guard<std::mutex> lock(st->mu);
-    if (st->n_chunks + n_new_chunks >= (int64_t)0x7fffffff - 1) return fail(RL_ERR_UNSUPPORTED, std::string(who) + ": more than 2^31-2 chunks");
-    RL_TRY(store_grow(st->tok_off, &st->cap_off, st->n_chunks ? st->n_chunks + 1 : 0, st->n_chunks + n_new_chunks + 1, s, who));
-    RL_TRY(store_grow(st->live, &st->cap_live, st->n_chunks, st->n_chunks + n_new_chunks, s, who));
-    RL_TRY(store_grow(st->tok_term, &st->cap_tokens, st->n_tokens, st->n_tokens + n_add, s, who));
-    for (int64_t& o : h_off) o += st->n_tokens;  // (h_off[0] is what tok_off[n_chunks] holds already, or the first 0)
-    RL_TRY(hip_status(hipMemcpyAsync(st->tok_off + st->n_chunks, h_off.data(), h_off.size() * sizeof(int64_t), hipMemcpyHostToDevice, s), who));
-    if (n_add > 0) RL_TRY(hip_status(hipMemcpyAsync(st->tok_term + st->n_tokens, term_ids, (size_t)n_add * sizeof(int32_t), in_kind, s), who));
-    RL_TRY(hip_status(hipMemsetAsync(st->live + st->n_chunks, 1, (size_t)n_new_chunks, s), who));
-    RL_TRY(hip_status(hipStreamSynchronize(s), who));  // the caller's arrays and h_off may go away after return
-    st->h_live.resize((size_t)(st->n_chunks + n_new_chunks), 1);
-    st->n_chunks += n_new_chunks;
-    st->n_live += n_new_chunks;
-    st->n_tokens += n_add;
-    if (n_add > 0) st->max_id = std::max(st->max_id, range[1]);
-    st->drop_count();
-    return RL_OK;
-}
-
-int rl_keyword_store_delete(rl_keyword_store* st, const int64_t* chunk_ordinals, int64_t n, void* stream) {
-    const char* who = "rl_keyword_store_delete";
-    if (!st) return fail(RL_ERR_INVALID, std::string(who) + ": null store");
-    if (n < 0 || (n > 0 && !chunk_ordinals)) return fail(RL_ERR_INVALID, std::string(who) + ": bad ordinals");
-    hipStream_t s = as_stream(stream);
-    std::lock_guard<std::mutex> lock(st->mu);
-    for (int64_t i = 0; i < n; ++i)
-        if (chunk_ordinals[i] < 0 || chunk_ordinals[i] >= st->n_chunks) return fail(RL_ERR_INVALID, std::string(who) + ": chunk ordinal out of range");
-    if (n == 0) return RL_OK;
-    st->drop_count();  // (any delete, even of dead chunks alone, asks for a new count)
-    // the touched range of the live bytes goes up before the host copy changes: a failure leaves the store as it was
-    int64_t lo = st->n_chunks, hi = -1, gone = 0;
-    for (int64_t i = 0; i < n; ++i) {  // (deleting a dead chunk is a no-op, as in rl_index_delete_chunks)
-        if (!st->h_live[(size_t)chunk_ordinals[i]]) continue;
-        lo = std::min(lo, chunk_ordinals[i]);
-        hi = std::max(hi, chunk_ordinals[i]);
-    }
-    if (hi < 0) return RL_OK;
-    std::vector<uint8_t> range(st->h_live.begin() + lo, st->h_live.begin() + hi + 1);
-    for (int64_t i = 0; i < n; ++i) {
-        if (chunk_ordinals[i] < lo || chunk_ordinals[i] > hi) continue;  // (dead already: every live one lies in [lo, hi])
-        uint8_t& flag = range[(size_t)(chunk_ordinals[i] - lo)];
-        gone += flag;
-        flag = 0;
-    }
-    RL_TRY(hip_status(hipMemcpyAsync(st->live + lo, range.data(), range.size(), hipMemcpyHostToDevice, s), who));
-    RL_TRY(hip_status(hipStreamSynchronize(s), who));
-    std::copy(range.begin(), range.end(), st->h_live.begin() + lo);
-    st->n_live -= gone;
-    return RL_OK;
-}
-
-int rl_keyword_store_count(rl_keyword_store* st, const int32_t* term_rank, int32_t n_terms, int64_t* out_df, int64_t* out_length,
-                           int64_t out_totals[3], int mem, void* stream) {
-    const char* who = "rl_keyword_store_count";
-    if (!st) return fail(RL_ERR_INVALID, std::string(who) + ": null store");
-    if (n_terms < 0) return fail(RL_ERR_INVALID, std::string(who) + ": negative size");
-    if (mem != RL_MEM_HOST && mem != RL_MEM_DEVICE) return fail(RL_ERR_INVALID, std::string(who) + ": bad mem");
-    hipStream_t s = as_stream(stream);
-    std::lock_guard<std::mutex> lock(st->mu);
-    if ((int64_t)st->max_id >= (int64_t)n_terms) return fail(RL_ERR_INVALID, std::string(who) + ": the store holds a term id >= n_terms");
-    if (term_rank && mem == RL_MEM_HOST) {
-        std::vector<bool> seen((size_t)n_terms, false);
-        for (int32_t t = 0; t < n_terms; ++t) {
-            if (term_rank[t] < 0 || term_rank[t] >= n_terms || seen[(size_t)term_rank[t]])
-                return fail(RL_ERR_INVALID, std::string(who) + ": term_rank must be a permutation of [0, n_terms)");
-            seen[(size_t)term_rank[t]] = true;
-        }
-    }
-    st->drop_count();
-    const hipMemcpyKind out_kind = mem == RL_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
-    const int64_t n = st->n_chunks;
-    int64_t m = 0, np = 0;  // live tokens, postings
-    Pool &lens = st->lens, &offs = st->offs, &scan_scratch = st->scan_scratch;  // (kept by the store: see its declaration)
-    if (n > 0) {
-        RL_TRY(reserve_amortised(lens, (size_t)n * sizeof(int64_t), who));
-        RL_TRY(reserve_amortised(offs, (size_t)n * sizeof(int64_t), who));
-        RL_TRY(reserve_amortised(scan_scratch, kb_scan_scratch_items(n) * sizeof(int64_t), who));
-        RL_TRY(launch_kb_lengths(st->tok_off, st->live, n, lens.as<int64_t>(), s));
-        RL_HIP(hipMemcpyAsync(offs.p, lens.p, (size_t)n * sizeof(int64_t), hipMemcpyDeviceToDevice, s));
-        const int64_t* d_total;
-        RL_TRY(launch_kb_exclusive_scan(offs.as<int64_t>(), n, scan_scratch.as<int64_t>(), &d_total, s));
-        RL_HIP(hipMemcpyAsync(&m, d_total, sizeof(int64_t), hipMemcpyDeviceToHost, s));
-        RL_HIP(hipStreamSynchronize(s));
-        if (m < 0 || m > st->n_tokens) return fail(RL_ERR_HIP, std::string(who) + ": inconsistent token count");
-    }
-    DevArray<int64_t> term_off;
-    DevArray<int32_t> post_chunk;
-    DevArray<int32_t>&post_term = st->post_term, &post_tf = st->post_tf;
-    Pool& df = st->df;
-    RL_TRY(term_off.alloc((size_t)(n_terms + 1) * sizeof(int64_t), who));
-    RL_TRY(reserve_amortised(df, std::max<size_t>((size_t)n_terms * sizeof(int64_t), 16), who));
-    if (m > 0) {
-        Pool &sortbuf = st->sortbuf, &table = st->table, &heads = st->heads, &head_pos = st->head_pos;
-        Staging up(mem, s);
-        const int32_t* d_rank = nullptr;
-        if (term_rank) RL_TRY(up.in(term_rank, (size_t)n_terms, &d_rank));
-        const size_t plane = ((size_t)m * 4 + 255) & ~size_t(255);
-        RL_TRY(reserve_amortised(sortbuf, 4 * plane, who));  // keys and values, twice: the passes go back and forth
-        uint32_t* keys[2] = {reinterpret_cast<uint32_t*>(sortbuf.as<char>()), reinterpret_cast<uint32_t*>(sortbuf.as<char>() + 2 * plane)};
-        int32_t* vals[2] = {reinterpret_cast<int32_t*>(sortbuf.as<char>() + plane), reinterpret_cast<int32_t*>(sortbuf.as<char>() + 3 * plane)};
-        const int64_t table_items = 256 * kb_sort_blocks(m);
-        RL_TRY(reserve_amortised(table, (size_t)table_items * sizeof(int64_t), who));
-        RL_TRY(reserve_amortised(scan_scratch, std::max(kb_scan_scratch_items(table_items), kb_scan_scratch_items(kb_rle_blocks(m))) * sizeof(int64_t), who));
-        RL_TRY(launch_kb_emit(st->tok_off, st->tok_term, st->live, offs.as<int64_t>(), d_rank, n_terms, n, st->n_tokens, m, keys[0], vals[0], s));
-        int at = 0;
-        for (int pass = 0; pass < kb_sort_passes(n_terms); ++pass, at ^= 1)
-            RL_TRY(launch_kb_sort_pass(keys[at], vals[at], m, pass, table.as<int64_t>(), scan_scratch.as<int64_t>(), keys[at ^ 1], vals[at ^ 1], s));
-        RL_TRY(reserve_amortised(heads, (size_t)kb_rle_blocks(m) * sizeof(int64_t), who));
-        RL_TRY(launch_kb_rle_count(keys[at], vals[at], m, heads.as<int64_t>(), s));
-        const int64_t* d_total;
-        RL_TRY(launch_kb_exclusive_scan(heads.as<int64_t>(), kb_rle_blocks(m), scan_scratch.as<int64_t>(), &d_total, s));
-        RL_HIP(hipMemcpyAsync(&np, d_total, sizeof(int64_t), hipMemcpyDeviceToHost, s));
-        RL_HIP(hipStreamSynchronize(s));
-        if (np < 1 || np > m) return fail(RL_ERR_HIP, std::string(who) + ": inconsistent posting count");
-        RL_TRY(reserve_amortised(post_term, (size_t)np * sizeof(int32_t), who));
-        RL_TRY(post_chunk.alloc((size_t)np * sizeof(int32_t), who));
-        RL_TRY(reserve_amortised(post_tf, (size_t)np * sizeof(int32_t), who));
-        RL_TRY(reserve_amortised(head_pos, (size_t)np * sizeof(int64_t), who));
-        RL_TRY(launch_kb_rle_write(keys[at], vals[at], m, heads.as<int64_t>(), np, post_term, post_chunk, post_tf, head_pos.as<int64_t>(), s));
-        RL_TRY(launch_kb_term_off(post_term, np, n_terms, term_off, df.as<int64_t>(), s));
-        RL_TRY(up.sync());  // the staged term_rank goes with this scope
-    } else {  // no chunks, or no live tokens: what rl_keyword_index_create holds for empty arrays
-        RL_TRY(reserve_amortised(post_term, 16, who));
-        RL_TRY(post_chunk.alloc(16, who));
-        RL_TRY(reserve_amortised(post_tf, 16, who));
-        RL_HIP(hipMemsetAsync(term_off.p, 0, (size_t)(n_terms + 1) * sizeof(int64_t), s));
-        RL_HIP(hipMemsetAsync(df.p, 0, std::max<size_t>((size_t)n_terms * sizeof(int64_t), 16), s));
-    }
-    if (out_df && n_terms > 0) RL_HIP(hipMemcpyAsync(out_df, df.p, (size_t)n_terms * sizeof(int64_t), out_kind, s));
-    if (out_length && n > 0) RL_HIP(hipMemcpyAsync(out_length, lens.p, (size_t)n * sizeof(int64_t), out_kind, s));
-    const int64_t totals[3] = {st->n_live, m, np};
-    if (out_totals) {
-        if (mem == RL_MEM_HOST) std::memcpy(out_totals, totals, sizeof(totals));
-        else RL_HIP(hipMemcpyAsync(out_totals, totals, sizeof(totals), hipMemcpyHostToDevice, s));
-    }
-    RL_HIP(hipStreamSynchronize(s));  // `totals` goes with this frame
-    st->term_off = std::move(term_off);
-    st->post_chunk = std::move(post_chunk);
-    st->c_terms = n_terms;
-    st->c_postings = np;
-    st->c_chunks = n;
-    st->counted = true;
-    return RL_OK;
-}
-
-int rl_keyword_store_build(rl_keyword_store* st, const float* idf, const float* nrm, rl_keyword_index** out, int mem, void* stream) {
-    const char* who = "rl_keyword_store_build";
-    if (!out) return fail(RL_ERR_INVALID, std::string(who) + ": null output handle");
-    *out = nullptr;
-    if (!st) return fail(RL_ERR_INVALID, std::string(who) + ": null store");
-    if (mem != RL_MEM_HOST && mem != RL_MEM_DEVICE) return fail(RL_ERR_INVALID, std::string(who) + ": bad mem");
-    hipStream_t s = as_stream(stream);
-    std::lock_guard<std::mutex> lock(st->mu);
-    if (!st->counted)
-        return fail(RL_ERR_INVALID, std::string(who) + ": no rl_keyword_store_count since the store was created, appended to, deleted from or built");
-    if ((st->c_terms > 0 && !idf) || (st->c_chunks > 0 && !nrm)) return fail(RL_ERR_INVALID, std::string(who) + ": null argument");
-    std::unique_ptr<rl_keyword_index> kw;
-    RL_TRY(new_keyword_index(st->c_terms, st->c_postings, st->c_chunks, &kw));
-    RL_TRY(kw->post_impact.alloc(std::max<size_t>((size_t)st->c_postings * sizeof(float), 16), who));
-    Staging up(mem, s);
-    const float *d_idf, *d_nrm;
-    RL_TRY(up.in(idf, (size_t)st->c_terms, &d_idf));
-    RL_TRY(up.in(nrm, (size_t)st->c_chunks, &d_nrm));
-    RL_TRY(launch_bm25_impact(st->post_chunk, st->post_tf, st->post_term, d_idf, d_nrm, st->c_postings, st->c_terms, st->c_chunks, kw->post_impact, s));
-    RL_TRY(up.sync());  // the staging buffers and the caller's arrays may go away after return
-    kw->term_off = std::move(st->term_off);  // the counted postings become the index: no copy
-    kw->post_chunk = std::move(st->post_chunk);
-    st->drop_count();
-    *out = kw.release();
-    return RL_OK;
-}
-
-}  // extern "C"
-
-// ---- keyword analyzer: chunk bodies -> stable term ids on the device (kernels in keyword_analyze.hip) ----------------------------------
-struct rl_keyword_analyzer {
-    std::mutex mu;
-    int hash_bits = 0;
-    int64_t n_table = 0;
-    int32_t n_stop = 0, stop_max_len = 0;
-    rl::DevArray<uint32_t> table;      // [n_table] the fold table
-    rl::DevArray<uint8_t> stop_bytes;  // the stopwords, sorted, as symbols 0 .. 25
-    rl::DevArray<int32_t> stop_off;    // [n_stop + 1]
-    // what the last rl_keyword_analyze_begin left (sizes 0 until then)
-    bool begun = false, finished = false;
-    int64_t n_texts = 0, m = 0, n_tok = 0, n_kept = 0, n_distinct = 0, n_bytes = 0, cap = 0;
-    // device arrays of a call, kept between calls with amortised capacity
-    rl::Pool count, scan_scratch, sym, start, letter, stem, head, ftext_off, tok_pos, tok_len, tok_hash, tok_slot, slots, kept, first, dist_tok,
-        dist_first, dist_len, dist_bytes, term_ids, offsets;
-};
-
-namespace rl {
-namespace {
-
-// the exclusive scan of data [n] in place and its total, copied to *total_host (valid after the next synchronisation of `s`)
-int ka_scan(rl_keyword_analyzer* a, int64_t* data, int64_t n, int64_t* total_host, hipStream_t s, const char* who) {
-    RL_TRY(reserve_amortised(a->scan_scratch, kb_scan_scratch_items(n) * sizeof(int64_t), who));
-    const int64_t* total = nullptr;
-    RL_TRY(launch_kb_exclusive_scan(data, n, a->scan_scratch.as<int64_t>(), &total, s));
-    RL_TRY(hip_status(hipMemcpyAsync(total_host, total, sizeof(int64_t), hipMemcpyDeviceToHost, s), who));
-    return RL_OK;
-}
-
-}  // namespace
-}  // namespace rl
-
-extern "C" {
-
-int rl_keyword_analyzer_create(rl_keyword_analyzer** out, const uint32_t* fold_table, int64_t n_table, const char* stopwords,
-                               const int64_t* stop_off, int32_t n_stop, int32_t hash_bits) {
-    const char* who = "rl_keyword_analyzer_create";
-    if (!out) return fail(RL_ERR_INVALID, std::string(who) + ": null output handle");
-    *out = nullptr;
-    if (!fold_table || n_table < 1 || n_table > (int64_t(1) << 21)) return fail(RL_ERR_INVALID, std::string(who) + ": bad fold table");
-    if (n_stop < 0 || (n_stop > 0 && (!stopwords || !stop_off))) return fail(RL_ERR_INVALID, std::string(who) + ": bad stopword list");
-    if (hash_bits < 0 || hash_bits > 64) return fail(RL_ERR_INVALID, std::string(who) + ": hash_bits must be 0 .. 64");
-    for (int64_t i = 0; i < n_table; ++i) {  // every field a symbol + 1 (<= 29), no symbol behind an empty field, nothing above the fields
-        uint32_t e = fold_table[i];
-        bool ended = false;
-        for (int j = 0; j < KA_IMAGE_MAX; ++j, e >>= 5) {
-            const uint32_t f = e & 31u;
-            if (f > 29u || (ended && f)) return fail(RL_ERR_INVALID, std::string(who) + ": malformed fold table entry");
-            ended |= f == 0;
-        }
-        if (e) return fail(RL_ERR_INVALID, std::string(who) + ": malformed fold table entry");
-    }
-    // the words that a token can equal (a-z only, non-empty), sorted and distinct, as symbols
-    std::vector<std::string> words;
-    for (int32_t i = 0; i < n_stop; ++i) {
-        if (stop_off[i] < 0 || stop_off[i + 1] < stop_off[i]) return fail(RL_ERR_INVALID, std::string(who) + ": stopword offsets must ascend from 0");
-        std::string w(stopwords + stop_off[i], (size_t)(stop_off[i + 1] - stop_off[i]));
-        bool ok = !w.empty();
-        for (char& c : w) {
-            ok = ok && c >= 'a' && c <= 'z';
-            c = (char)(c - 'a');
-        }
-        if (ok) words.push_back(std::move(w));
-    }
-    std::sort(words.begin(), words.end());
-    words.erase(std::unique(words.begin(), words.end()), words.end());
-    std::vector<int32_t> h_off(words.size() + 1, 0);
-    std::string h_bytes;
-    size_t longest = 0;
-    for (size_t i = 0; i < words.size(); ++i) {
-        h_bytes += words[i];
-        h_off[i + 1] = (int32_t)h_bytes.size();
-        longest = std::max(longest, words[i].size());
-    }
-    std::unique_ptr<rl_keyword_analyzer> a(new rl_keyword_analyzer());
-    a->hash_bits = hash_bits == 64 ? 0 : hash_bits;
-    a->n_table = n_table;
-    a->n_stop = (int32_t)words.size();
-    a->stop_max_len = (int32_t)longest;
-    RL_TRY(a->table.alloc((size_t)n_table * sizeof(uint32_t), who));
-    RL_TRY(a->stop_bytes.alloc(std::max<size_t>(h_bytes.size(), 16), who));
-    RL_TRY(a->stop_off.alloc(h_off.size() * sizeof(int32_t), who));
-    RL_TRY(hip_status(hipMemcpy(a->table.p, fold_table, (size_t)n_table * sizeof(uint32_t), hipMemcpyHostToDevice), who));
-    if (!h_bytes.empty()) RL_TRY(hip_status(hipMemcpy(a->stop_bytes.p, h_bytes.data(), h_bytes.size(), hipMemcpyHostToDevice), who));
-    RL_TRY(hip_status(hipMemcpy(a->stop_off.p, h_off.data(), h_off.size() * sizeof(int32_t), hipMemcpyHostToDevice), who));
-    *out = a.release();
-    return RL_OK;
-}
-
-int rl_keyword_analyzer_destroy(rl_keyword_analyzer* a) {
-    if (!a) return RL_OK;
-    delete a;
-    return RL_OK;
-}
-
-int rl_keyword_analyze_begin(rl_keyword_analyzer* a, const uint32_t* codepoints, const int64_t* text_off, int64_t n, int64_t n_texts,
-                             int64_t out_counts[5], int mem, void* stream) {
-    const char* who = "rl_keyword_analyze_begin";
-    if (!a) return fail(RL_ERR_INVALID, std::string(who) + ": null analyzer");
-    if (n < 0 || n_texts < 0) return fail(RL_ERR_INVALID, std::string(who) + ": negative size");
-    if (mem != RL_MEM_HOST && mem != RL_MEM_DEVICE) return fail(RL_ERR_INVALID, std::string(who) + ": bad mem");
-    if (!text_off) return fail(RL_ERR_INVALID, std::string(who) + ": null text_off");
-    if (n > 0 && !codepoints) return fail(RL_ERR_INVALID, std::string(who) + ": null codepoints");
-    if (n > 0 && n_texts < 1) return fail(RL_ERR_INVALID, std::string(who) + ": code points without a text");
-    if (n >= (int64_t(1) << 40)) return fail(RL_ERR_UNSUPPORTED, std::string(who) + ": more than 2^40 code points in one call");
-    if (mem == RL_MEM_HOST) {
-        if (text_off[0] != 0) return fail(RL_ERR_INVALID, std::string(who) + ": text_off must start at 0");
-        for (int64_t t = 0; t < n_texts; ++t)
-            if (text_off[t + 1] < text_off[t]) return fail(RL_ERR_INVALID, std::string(who) + ": text_off must be ascending");
-        if (text_off[n_texts] != n) return fail(RL_ERR_INVALID, std::string(who) + ": text_off must end at n");
-    }
-    hipStream_t s = as_stream(stream);
-    std::lock_guard<std::mutex> lock(a->mu);
-    a->begun = a->finished = false;
-    a->n_texts = n_texts;
-    a->m = a->n_tok = a->n_kept = a->n_distinct = a->n_bytes = a->cap = 0;
-    Staging st(mem, s);
-    const uint32_t* d_cp;
-    const int64_t* d_off;
-    RL_TRY(st.in(codepoints, (size_t)n, &d_cp));
-    RL_TRY(st.in(text_off, (size_t)n_texts + 1, &d_off));
-    // 1. fold
-    RL_TRY(reserve_amortised(a->count, (size_t)(n + 1) * sizeof(int64_t), who));
-    RL_TRY(launch_ka_fold_count(d_cp, n, a->table, a->n_table, a->count.as<int64_t>(), s));
-    int64_t m = 0, n_tok = 0, n_kept = 0, n_distinct = 0, n_bytes = 0;
-    RL_TRY(ka_scan(a, a->count.as<int64_t>(), n + 1, &m, s, who));
-    RL_TRY(hip_status(hipStreamSynchronize(s), who));
-    const int64_t* sym_off = a->count.as<int64_t>();
-    const size_t m_bytes = std::max<size_t>((size_t)m, 16);
-    RL_TRY(reserve_amortised(a->sym, m_bytes, who));
-    RL_TRY(reserve_amortised(a->start, m_bytes, who));
-    RL_TRY(reserve_amortised(a->letter, m_bytes, who));
-    RL_TRY(reserve_amortised(a->stem, m_bytes, who));
-    RL_TRY(reserve_amortised(a->head, (size_t)(m + 1) * sizeof(int64_t), who));
-    RL_TRY(reserve_amortised(a->ftext_off, (size_t)(n_texts + 1) * sizeof(int64_t), who));
-    RL_TRY(hip_status(hipMemsetAsync(a->start.p, 0, m_bytes, s), who));
-    RL_TRY(launch_ka_fold_write(d_cp, n, a->table, a->n_table, sym_off, m, a->sym.as<uint8_t>(), s));
-    RL_TRY(launch_ka_text_starts(d_off, n_texts, n, sym_off, m, a->ftext_off.as<int64_t>(), a->start.as<uint8_t>(), s));
-    // 2. tokenize
-    RL_TRY(launch_ka_heads(a->sym.as<uint8_t>(), a->start.as<uint8_t>(), m, a->letter.as<uint8_t>(), a->head.as<int64_t>(), s));
-    RL_TRY(ka_scan(a, a->head.as<int64_t>(), m + 1, &n_tok, s, who));
-    RL_TRY(hip_status(hipStreamSynchronize(s), who));
-    if (n_tok > 0) {
-        // 3. stem
-        const int64_t cap = ka_table_slots(n_tok);
-        RL_TRY(reserve_amortised(a->tok_pos, (size_t)n_tok * sizeof(int64_t), who));
-        RL_TRY(reserve_amortised(a->tok_len, (size_t)n_tok * sizeof(int64_t), who));
-        RL_TRY(reserve_amortised(a->tok_hash, (size_t)n_tok * sizeof(uint64_t), who));
-        RL_TRY(reserve_amortised(a->tok_slot, (size_t)n_tok * sizeof(int64_t), who));
-        RL_TRY(reserve_amortised(a->kept, (size_t)(n_tok + 1) * sizeof(int64_t), who));
-        RL_TRY(reserve_amortised(a->first, (size_t)(n_tok + 1) * sizeof(int64_t), who));
-        RL_TRY(reserve_amortised(a->slots, (size_t)cap * sizeof(uint64_t), who));
-        RL_TRY(launch_ka_stem(a->sym.as<uint8_t>(), a->letter.as<uint8_t>(), a->start.as<uint8_t>(), a->head.as<int64_t>(), m, n_tok, a->stop_bytes,
-                              a->stop_off, a->n_stop, a->stop_max_len, a->hash_bits, a->tok_pos.as<int64_t>(), a->stem.as<uint8_t>(),
-                              a->tok_len.as<int64_t>(), a->tok_hash.as<uint64_t>(), s));
-        // 4. distinct
-        RL_TRY(launch_ka_distinct(a->stem.as<uint8_t>(), a->tok_pos.as<int64_t>(), a->tok_len.as<int64_t>(), a->tok_hash.as<uint64_t>(), n_tok,
-                                  a->slots.as<uint64_t>(), cap, a->tok_slot.as<int64_t>(), a->kept.as<int64_t>(), a->first.as<int64_t>(), s));
-        RL_TRY(ka_scan(a, a->kept.as<int64_t>(), n_tok + 1, &n_kept, s, who));
-        RL_TRY(ka_scan(a, a->first.as<int64_t>(), n_tok + 1, &n_distinct, s, who));
-        RL_TRY(hip_status(hipStreamSynchronize(s), who));
-        RL_TRY(reserve_amortised(a->dist_tok, std::max<size_t>((size_t)n_distinct * sizeof(int64_t), 16), who));
-        RL_TRY(reserve_amortised(a->dist_first, std::max<size_t>((size_t)n_distinct * sizeof(int64_t), 16), who));
-        RL_TRY(reserve_amortised(a->dist_len, (size_t)(n_distinct + 1) * sizeof(int64_t), who));
-        RL_TRY(launch_ka_distinct_out(a->tok_len.as<int64_t>(), a->tok_slot.as<int64_t>(), a->slots.as<uint64_t>(), cap, n_tok, a->kept.as<int64_t>(),
-                                      a->first.as<int64_t>(), n_distinct, a->dist_tok.as<int64_t>(), a->dist_first.as<int64_t>(),
-                                      a->dist_len.as<int64_t>(), s));
-        RL_TRY(ka_scan(a, a->dist_len.as<int64_t>(), n_distinct + 1, &n_bytes, s, who));
-        RL_TRY(hip_status(hipStreamSynchronize(s), who));
-        RL_TRY(reserve_amortised(a->dist_bytes, std::max<size_t>((size_t)n_bytes, 16), who));
-        RL_TRY(launch_ka_distinct_bytes(a->stem.as<uint8_t>(), a->tok_pos.as<int64_t>(), a->tok_len.as<int64_t>(), a->dist_tok.as<int64_t>(),
-                                        a->dist_len.as<int64_t>(), n_distinct, n_bytes, a->dist_bytes.as<uint8_t>(), s));
-        RL_TRY(hip_status(hipStreamSynchronize(s), who));
-        a->cap = cap;
-    }
-    st.drain();  // (the stream has been synchronised above)
-    a->m = m;
-    a->n_tok = n_tok;
-    a->n_kept = n_kept;
-    a->n_distinct = n_distinct;
-    a->n_bytes = n_bytes;
-    a->begun = true;
-    if (out_counts) {
-        out_counts[0] = n_kept;
-        out_counts[1] = n_distinct;
-        out_counts[2] = n_bytes;
-        out_counts[3] = m;
-        out_counts[4] = n_tok;
-    }
-    return RL_OK;
-}
-
-int rl_keyword_analyze_stems(rl_keyword_analyzer* a, uint8_t* stem_bytes, int64_t* stem_off, int64_t* first_pos, int mem, void* stream) {
-    const char* who = "rl_keyword_analyze_stems";
-    if (!a) return fail(RL_ERR_INVALID, std::string(who) + ": null analyzer");
-    if (mem != RL_MEM_HOST && mem != RL_MEM_DEVICE) return fail(RL_ERR_INVALID, std::string(who) + ": bad mem");
-    hipStream_t s = as_stream(stream);
-    std::lock_guard<std::mutex> lock(a->mu);
-    if (!a->begun) return fail(RL_ERR_INVALID, std::string(who) + ": no rl_keyword_analyze_begin before it");
-    const hipMemcpyKind kind = mem == RL_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
-    const size_t nd = (size_t)a->n_distinct;
-    if (a->n_tok == 0) {  // (no token: the device arrays were not written)
-        if (stem_off && mem == RL_MEM_HOST) stem_off[0] = 0;
-        else if (stem_off) RL_TRY(hip_status(hipMemsetAsync(stem_off, 0, sizeof(int64_t), s), who));
-    } else {
-        if (stem_bytes && a->n_bytes) RL_TRY(hip_status(hipMemcpyAsync(stem_bytes, a->dist_bytes.p, (size_t)a->n_bytes, kind, s), who));
-        if (stem_off) RL_TRY(hip_status(hipMemcpyAsync(stem_off, a->dist_len.p, (nd + 1) * sizeof(int64_t), kind, s), who));
-        if (first_pos && nd) RL_TRY(hip_status(hipMemcpyAsync(first_pos, a->dist_first.p, nd * sizeof(int64_t), kind, s), who));
-    }
-    RL_TRY(hip_status(hipStreamSynchronize(s), who));
-    return RL_OK;
-}
-
-int rl_keyword_analyze_finish(rl_keyword_analyzer* a, const int32_t* ids, int mem, const int32_t** term_ids, const int64_t** offsets, void* stream) {
-    const char* who = "rl_keyword_analyze_finish";
-    if (!a) return fail(RL_ERR_INVALID, std::string(who) + ": null analyzer");
-    if (mem != RL_MEM_HOST && mem != RL_MEM_DEVICE) return fail(RL_ERR_INVALID, std::string(who) + ": bad mem");
-    hipStream_t s = as_stream(stream);
-    std::lock_guard<std::mutex> lock(a->mu);
-    if (!a->begun) return fail(RL_ERR_INVALID, std::string(who) + ": no rl_keyword_analyze_begin before it");
-    if (a->n_distinct > 0 && !ids) return fail(RL_ERR_INVALID, std::string(who) + ": null ids");
-    if (mem == RL_MEM_HOST)
-        for (int64_t d = 0; d < a->n_distinct; ++d)
-            if (ids[d] < 0) return fail(RL_ERR_INVALID, std::string(who) + ": negative term id");
-    a->finished = false;
-    RL_TRY(reserve_amortised(a->term_ids, std::max<size_t>((size_t)a->n_kept * sizeof(int32_t), 16), who));
-    RL_TRY(reserve_amortised(a->offsets, (size_t)(a->n_texts + 1) * sizeof(int64_t), who));
-    Staging st(mem, s);
-    const int32_t* d_ids;
-    RL_TRY(st.in(ids, (size_t)a->n_distinct, &d_ids));
-    if (a->n_tok > 0) {
-        // 5. emit
-        RL_TRY(launch_ka_emit(a->tok_len.as<int64_t>(), a->tok_slot.as<int64_t>(), a->slots.as<uint64_t>(), a->cap, a->n_tok, a->kept.as<int64_t>(),
-                              a->first.as<int64_t>(), d_ids, a->n_distinct, a->n_kept, a->term_ids.as<int32_t>(), s));
-        RL_TRY(launch_ka_offsets(a->ftext_off.as<int64_t>(), a->n_texts, a->head.as<int64_t>(), a->m, a->kept.as<int64_t>(), a->n_tok,
-                                 a->offsets.as<int64_t>(), s));
-    } else {
-        RL_TRY(hip_status(hipMemsetAsync(a->offsets.p, 0, (size_t)(a->n_texts + 1) * sizeof(int64_t), s), who));
-    }
-    RL_TRY(hip_status(hipStreamSynchronize(s), who));  // the staging buffer and the caller's ids may go away after return
-    st.drain();
-    a->finished = true;
-    if (term_ids) *term_ids = a->term_ids.as<int32_t>();
-    if (offsets) *offsets = a->offsets.as<int64_t>();
-    return RL_OK;
-}
-
-int rl_keyword_analyze_result(rl_keyword_analyzer* a, int32_t* term_ids, int64_t* offsets, int mem, void* stream) {
-    const char* who = "rl_keyword_analyze_result";
-    if (!a) return fail(RL_ERR_INVALID, std::string(who) + ": null analyzer");
-    if (mem != RL_MEM_HOST && mem != RL_MEM_DEVICE) return fail(RL_ERR_INVALID, std::string(who) + ": bad mem");
-    hipStream_t s = as_stream(stream);
-    std::lock_guard<std::mutex> lock(a->mu);
-    if (!a->finished) return fail(RL_ERR_INVALID, std::string(who) + ": no rl_keyword_analyze_finish before it");
-    const hipMemcpyKind kind = mem == RL_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
-    if (term_ids && a->n_kept) RL_TRY(hip_status(hipMemcpyAsync(term_ids, a->term_ids.p, (size_t)a->n_kept * sizeof(int32_t), kind, s), who));
-    if (offsets) RL_TRY(hip_status(hipMemcpyAsync(offsets, a->offsets.p, (size_t)(a->n_texts + 1) * sizeof(int64_t), kind, s), who));
-    RL_TRY(hip_status(hipStreamSynchronize(s), who));
-    return RL_OK;
-}
-
-}  // extern "C"
-
-namespace {
-// rl_keyword_search and rl_keyword_search_per_query: one device path
-int keyword_search_call(rl_keyword_index* kw, const int64_t* q_off, const int32_t* q_terms, int32_t n_queries, int32_t k,
-                        const uint32_t* chunk_filters, int32_t n_filters, const int32_t* query_filter, float* out_scores, int32_t* out_chunks,
-                        int32_t* out_counts, int mem, void* stream, const char* who) {
-    if (!kw) return fail(RL_ERR_INVALID, std::string(who) + ": null index");
-    if (n_queries < 0 || k < 1) return fail(RL_ERR_INVALID, std::string(who) + ": n_queries must be >= 0 and k >= 1");
-    if (k > K_MAX) return fail(RL_ERR_UNSUPPORTED, std::string(who) + ": k must be <= 2048");
-    if (n_queries == 0) return RL_OK;
-    if (!q_off) return fail(RL_ERR_INVALID, std::string(who) + ": null q_off");
-    if (!out_scores || !out_chunks) return fail(RL_ERR_INVALID, std::string(who) + ": null output");
-    const int fmem = filters_mem(mem);
-    mem = args_mem(mem);
-    int64_t n_q_terms = 0;
-    if (mem == RL_MEM_HOST) {
-        RL_TRY(check_host_q_off(q_off, q_terms, n_queries, who));
-        n_q_terms = q_off[n_queries];
-    } else if (!q_terms) {
-        return fail(RL_ERR_INVALID, std::string(who) + ": null q_terms");
-    }
-    hipStream_t s = as_stream(stream);
-    std::lock_guard<std::mutex> lock(kw->mu);
-    RL_TRY(keyword_use_stream(kw, s));
-    const int64_t n = kw->n_chunks;
-    const size_t n_out = (size_t)n_queries * k;
-    Staging st(mem, s);
-    const int64_t* d_off;
-    const int32_t* d_terms;
-    const uint32_t* d_f = nullptr;
-    float* d_s;
-    int32_t *d_c, *d_n;
-    RL_TRY(st.in(q_off, (size_t)n_queries + 1, &d_off));
-    if (mem == RL_MEM_HOST) RL_TRY(st.in(q_terms, (size_t)n_q_terms, &d_terms));
-    else d_terms = q_terms;
-    if (n_filters) RL_TRY(st.in(chunk_filters, (size_t)n_filters * ((n + 31) / 32), &d_f, fmem));
-    QueryMask mask;
-    RL_TRY(keyword_mask(kw, d_f, n_filters, query_filter, n_queries, s, &mask));
-    RL_TRY(st.out(out_scores, n_out, &d_s));
-    RL_TRY(st.out(out_chunks, n_out, &d_c));
-    RL_TRY(st.out_or_temp(out_counts, (size_t)n_queries, &d_n));
-    RL_TRY(keyword_search_device(kw, d_off, d_terms, n_queries, k, mask, d_s, d_c, d_n, s));
-    return st.finish();
-}
-}  // namespace
-
-extern "C" {
-
-int rl_keyword_search(rl_keyword_index* kw, const int64_t* q_off, const int32_t* q_terms, int32_t n_queries, int32_t k,
-                      const uint32_t* chunk_filter, float* out_scores, int32_t* out_chunks, int32_t* out_counts, int mem, void* stream) {
-    return keyword_search_call(kw, q_off, q_terms, n_queries, k, chunk_filter, chunk_filter ? 1 : 0, nullptr, out_scores, out_chunks,
-                               out_counts, mem, stream, "rl_keyword_search");
-}
-
-int rl_keyword_search_per_query(rl_keyword_index* kw, const int64_t* q_off, const int32_t* q_terms, int32_t n_queries, int32_t k,
-                                const uint32_t* chunk_filters, int32_t n_filters, const int32_t* query_filter, float* out_scores,
-                                int32_t* out_chunks, int32_t* out_counts, int mem, void* stream) {
-    const char* who = "rl_keyword_search_per_query";
-    RL_TRY(check_query_filters(n_queries, chunk_filters, n_filters, query_filter, nullptr, who));
-    return keyword_search_call(kw, q_off, q_terms, n_queries, k, chunk_filters, query_filter ? n_filters : 0, query_filter, out_scores,
-                               out_chunks, out_counts, mem, stream, who);
-}
-
-// ---- weighted Reciprocal Rank Fusion and batched hybrid search (include/raglite_hip.h; the kernel is in fuse.hip) ------------------
-int rl_rrf_fuse(const int32_t* lists, int32_t n_lists, int32_t n_queries, int32_t len, const double* weights, int32_t rrf_k, int32_t k,
-                double* out_scores, int32_t* out_ids, int32_t* out_counts, int mem, void* stream) {
-    RL_TRY(check_fuse_args(n_lists, n_queries, len, weights, rrf_k, k, "rl_rrf_fuse"));
-    if (mem != RL_MEM_HOST && mem != RL_MEM_DEVICE) return fail(RL_ERR_INVALID, "rl_rrf_fuse: bad mem");
-    if (n_queries == 0) return RL_OK;
-    if (!lists || !out_scores || !out_ids) return fail(RL_ERR_INVALID, "rl_rrf_fuse: null argument");
-    hipStream_t s = as_stream(stream);
-    const size_t n_in = (size_t)n_lists * n_queries * len, n_out = (size_t)n_queries * k;
-    Staging st(mem, s);
-    const int32_t* d_l;
-    double* d_s;
-    int32_t *d_i, *d_n = nullptr;
-    RL_TRY(st.in(lists, n_in, &d_l));
-    RL_TRY(st.out(out_scores, n_out, &d_s));
-    RL_TRY(st.out(out_ids, n_out, &d_i));
-    RL_TRY(st.out(out_counts, (size_t)n_queries, &d_n));  // (optional)
-    RL_TRY(launch_rrf_fuse(d_l, n_lists, n_queries, len, weights, rrf_k, k, d_s, d_i, d_n, s));
-    return st.finish();
-}
-
-int rl_shard_hybrid_fuse(const int32_t* gathered, int32_t world, int32_t n_queries, int32_t num_hits, int32_t n_each, int32_t n_lists,
-                         const double* weights, int32_t rrf_k, int32_t k, double* out_scores, int32_t* out_chunks, int32_t* out_counts, int mem,
-                         void* stream) {
-    const char* who = "rl_shard_hybrid_fuse";
-    if (world < 1) return fail(RL_ERR_INVALID, "rl_shard_hybrid_fuse: world must be >= 1");
-    if (n_lists != 1 && n_lists != 2) return fail(RL_ERR_INVALID, "rl_shard_hybrid_fuse: n_lists must be 1 or 2");
-    if (num_hits < 1) return fail(RL_ERR_INVALID, "rl_shard_hybrid_fuse: num_hits must be >= 1");
-    RL_TRY(check_fuse_args(n_lists, n_queries, n_each, weights, rrf_k, k, who));
-    if (mem != RL_MEM_HOST && mem != RL_MEM_DEVICE) return fail(RL_ERR_INVALID, "rl_shard_hybrid_fuse: bad mem");
-    if ((int64_t)world * num_hits > SHARD_FUSE_MAX_ENTRIES || (n_lists == 2 && (int64_t)world * n_each > SHARD_FUSE_MAX_ENTRIES))
-        return fail(RL_ERR_UNSUPPORTED, "rl_shard_hybrid_fuse: world * num_hits and world * n_each must be <= 4096");
-    if (n_queries == 0) return RL_OK;
-    if (!gathered || !out_scores || !out_chunks) return fail(RL_ERR_INVALID, "rl_shard_hybrid_fuse: null argument");
-    hipStream_t s = as_stream(stream);
-    const size_t W = (size_t)3 * num_hits + (n_lists == 2 ? (size_t)2 * n_each : 0);
-    const size_t n_in = (size_t)world * n_queries * W, n_out = (size_t)n_queries * k;
-    Staging st(mem, s);
-    const int32_t* d_g;
-    double* d_s;
-    int32_t *d_c, *d_n = nullptr;
-    RL_TRY(st.in(gathered, n_in, &d_g));
-    RL_TRY(st.out(out_scores, n_out, &d_s));
-    RL_TRY(st.out(out_chunks, n_out, &d_c));
-    RL_TRY(st.out(out_counts, (size_t)n_queries, &d_n));  // (optional)
-    RL_TRY(launch_shard_hybrid_fuse(d_g, world, n_queries, num_hits, n_each, n_lists, weights, rrf_k, k, d_s, d_c, d_n, s));
-    return st.finish();
-}
-
-}  // extern "C"
-
-namespace {
-// What every hybrid call needs before its device work: the arguments checked, both handles locked on the stream, the inputs staged.
-struct HybridCall {
-    std::unique_lock<std::mutex> idx_lock, kw_lock;  // (idx->mu, then kw->mu: always in this order)
-    Staging st;                                      // (after the locks: its buffers are released while they are held)
-    const float* d_q = nullptr;
-    const int64_t* d_off = nullptr;
-    const int32_t* d_terms = nullptr;
-    BatchFilters f;
-    int32_t n_filters = 0;
-    const int32_t* query_filter = nullptr;
-    bool empty = false;  // n_queries == 0: nothing to do
-    HybridCall(int mem, hipStream_t s) : st(args_mem(mem), s) {}  // (`mem` as the caller of the entry point gave it)
-};
-
-// The checks of rl_hybrid_search (k: the fusion's), the locks and the staging-in
-int hybrid_search_begin(rl_index* idx, rl_keyword_index* kw, const float* queries, int32_t B, int32_t num_hits, int32_t n_each,
-                        const int64_t* q_off, const int32_t* q_terms, const uint32_t* chunk_filters, int32_t n_filters,
-                        const int32_t* query_filter, const int64_t* rank_limits, int64_t rank_limit, const double* weights, int32_t rrf_k,
-                        int32_t k, bool outputs, int mem, hipStream_t s, const char* who, HybridCall* c) {
-    const int fmem = filters_mem(mem);  // (`mem` as the caller of the entry point gave it; the callers go on with args_mem(mem))
-    mem = args_mem(mem);
-    const int32_t R = kw ? 2 : 1;
-    RL_TRY(check_search_args(idx, queries, B, n_each, who));
-    if (rank_limit < 0) return fail(RL_ERR_INVALID, std::string(who) + ": rank_limit must be >= 0 (0 = no cut)");
-    if (num_hits < 1 || num_hits > K_MAX) return fail(RL_ERR_INVALID, std::string(who) + ": num_hits must be in [1, 2048]");
-    RL_TRY(check_fuse_args(R, B, n_each, weights, rrf_k, k, who));
-    if (mem != RL_MEM_HOST && mem != RL_MEM_DEVICE) return fail(RL_ERR_INVALID, std::string(who) + ": bad mem");
-    if (kw && kw->n_chunks != idx->n_chunks) return fail(RL_ERR_INVALID, std::string(who) + ": the keyword index covers another number of chunks");
-    if (B == 0) { c->empty = true; return RL_OK; }
-    if (!outputs) return fail(RL_ERR_INVALID, std::string(who) + ": null output");
-    int64_t n_q_terms = 0;
-    if (kw) {
-        if (!q_off) return fail(RL_ERR_INVALID, std::string(who) + ": null q_off");
-        if (mem == RL_MEM_HOST) {
-            RL_TRY(check_host_q_off(q_off, q_terms, B, who));
-            n_q_terms = q_off[B];
-        } else if (!q_terms) {
-            return fail(RL_ERR_INVALID, std::string(who) + ": null q_terms");
-        }
-    }
-    c->idx_lock = std::unique_lock<std::mutex>(idx->mu);  // (then kw->mu: the only calls that hold both, always in this order)
-    RL_TRY(use_scratch(idx, s));
-    if (kw) {
-        c->kw_lock = std::unique_lock<std::mutex>(kw->mu);
-        RL_TRY(keyword_use_stream(kw, s));
-    }
-    c->d_terms = q_terms;
-    c->n_filters = n_filters;
-    c->query_filter = query_filter;
-    c->f.n = n_filters;
-    c->f.qf = query_filter;
-    c->f.lim = rank_limits;
-    c->f.limit = rank_limit;
-    RL_TRY(c->st.in(queries, (size_t)B * idx->dim, &c->d_q));
-    if (n_filters) RL_TRY(c->st.in(chunk_filters, (size_t)n_filters * ((idx->n_chunks + 31) / 32), &c->f.chunk_bits, fmem));
-    if (kw) {
-        RL_TRY(c->st.in(q_off, (size_t)B + 1, &c->d_off));
-        if (mem == RL_MEM_HOST) RL_TRY(c->st.in(q_terms, (size_t)n_q_terms, &c->d_terms));
-    }
-    return RL_OK;
-}
-
-// The two searches and the fusion on device pointers (after hybrid_search_begin): d_s / d_c [B x k], d_n [B]
-int hybrid_search_device(rl_index* idx, rl_keyword_index* kw, const HybridCall& c, int32_t B, int32_t num_hits, int32_t n_each,
-                         const double* weights, int32_t rrf_k, int32_t k, double* d_s, int32_t* d_c, int32_t* d_n, hipStream_t s) {
-    const int32_t R = kw ? 2 : 1;
-    const size_t n_list = (size_t)B * n_each;
-    // index-owned scratch: lists [R x B x n_each] int32 (what the fusion reads), the two searches' scores [R x B x n_each] f32 and
-    // counts [R x B] int32 (written, not read)
-    RL_TRY(idx->hybrid.reserve((size_t)R * (2 * n_list + B) * 4));
-    int32_t* lists = idx->hybrid.as<int32_t>();
-    float* list_scores = reinterpret_cast<float*>(lists + (size_t)R * n_list);
-    int32_t* list_counts = reinterpret_cast<int32_t*>(list_scores + (size_t)R * n_list);
-    RL_TRY(search_chunks_device(idx, c.d_q, B, num_hits, n_each, c.f, list_scores, lists, list_counts, s));
-    if (kw) {
-        QueryMask mask;
-        RL_TRY(keyword_mask(kw, c.f.chunk_bits, c.n_filters, c.query_filter, B, s, &mask));
-        RL_TRY(keyword_search_device(kw, c.d_off, c.d_terms, B, n_each, mask, list_scores + n_list, lists + n_list, list_counts + B, s));
-    }
-    return launch_rrf_fuse(lists, R, B, n_each, weights, rrf_k, k, d_s, d_c, d_n, s);
-}
-
-// rl_hybrid_search and rl_hybrid_search_per_query: one device path
-int hybrid_search_call(rl_index* idx, rl_keyword_index* kw, const float* queries, int32_t n_queries, int32_t num_hits, int32_t n_each,
-                       const int64_t* q_off, const int32_t* q_terms, const uint32_t* chunk_filters, int32_t n_filters, const int32_t* query_filter,
-                       const int64_t* rank_limits, int64_t rank_limit, const double* weights, int32_t rrf_k, int32_t k, double* out_scores,
-                       int32_t* out_chunks, int32_t* out_counts, int mem, void* stream, const char* who) {
-    const int32_t B = n_queries;
-    hipStream_t s = as_stream(stream);
-    HybridCall c(mem, s);
-    RL_TRY(hybrid_search_begin(idx, kw, queries, B, num_hits, n_each, q_off, q_terms, chunk_filters, n_filters, query_filter, rank_limits,
-                               rank_limit, weights, rrf_k, k, out_scores && out_chunks && out_counts, mem, s, who, &c));
-    if (c.empty) return RL_OK;
-    Staging& st = c.st;
-    const size_t n_out = (size_t)B * k;
-    double* d_s;
-    int32_t *d_c, *d_n;
-    RL_TRY(st.out(out_scores, n_out, &d_s));
-    RL_TRY(st.out(out_chunks, n_out, &d_c));
-    RL_TRY(st.out(out_counts, (size_t)B, &d_n));
-    RL_TRY(hybrid_search_device(idx, kw, c, B, num_hits, n_each, weights, rrf_k, k, d_s, d_c, d_n, s));
-    return st.finish();
-}
-}  // namespace
-
-extern "C" {
-
-int rl_hybrid_search(rl_index* idx, rl_keyword_index* kw, const float* queries, int32_t n_queries, int32_t num_hits, int32_t n_each,
-                     const int64_t* q_off, const int32_t* q_terms, const uint32_t* chunk_filter, int64_t rank_limit, const double* weights,
-                     int32_t rrf_k, int32_t k, double* out_scores, int32_t* out_chunks, int32_t* out_counts, int mem, void* stream) {
-    return hybrid_search_call(idx, kw, queries, n_queries, num_hits, n_each, q_off, q_terms, chunk_filter, chunk_filter ? 1 : 0, nullptr, nullptr,
-                              rank_limit, weights, rrf_k, k, out_scores, out_chunks, out_counts, mem, stream, "rl_hybrid_search");
-}
-
-int rl_hybrid_search_per_query(rl_index* idx, rl_keyword_index* kw, const float* queries, int32_t n_queries, int32_t num_hits, int32_t n_each,
-                               const int64_t* q_off, const int32_t* q_terms, const uint32_t* chunk_filters, int32_t n_filters,
-                               const int32_t* query_filter, const int64_t* rank_limits, const double* weights, int32_t rrf_k, int32_t k,
-                               double* out_scores, int32_t* out_chunks, int32_t* out_counts, int mem, void* stream) {
-    const char* who = "rl_hybrid_search_per_query";
-    RL_TRY(check_query_filters(n_queries, chunk_filters, n_filters, query_filter, rank_limits, who));
-    return hybrid_search_call(idx, kw, queries, n_queries, num_hits, n_each, q_off, q_terms, chunk_filters, query_filter ? n_filters : 0,
-                              query_filter, rank_limits, 0, weights, rrf_k, k, out_scores, out_chunks, out_counts, mem, stream, who);
-}
-
-// ---- batched search-and-rerank (include/raglite_hip.h; the ordering kernel is in rerank.hip) -----------------------------------------
-int rl_rerank_order(const float* scores, const int32_t* candidates, int32_t n_queries, int32_t n_cand, int32_t k, float* out_scores,
-                    int32_t* out_chunks, int32_t* out_pos, int32_t* out_counts, int mem, void* stream) {
-    if (n_queries < 0) return fail(RL_ERR_INVALID, "rl_rerank_order: n_queries must be >= 0");
-    if (n_cand < 1 || n_cand > RERANK_MAX_ENTRIES) return fail(RL_ERR_INVALID, "rl_rerank_order: n_cand must be in [1, 4096]");
-    if (k < 1 || k > n_cand) return fail(RL_ERR_INVALID, "rl_rerank_order: k must be in [1, n_cand]");
-    if (mem != RL_MEM_HOST && mem != RL_MEM_DEVICE) return fail(RL_ERR_INVALID, "rl_rerank_order: bad mem");
-    if (n_queries == 0) return RL_OK;
-    if (!scores || !candidates || !out_scores || !out_chunks || !out_pos || !out_counts)
-        return fail(RL_ERR_INVALID, "rl_rerank_order: null argument");
-    hipStream_t s = as_stream(stream);
-    const size_t n_in = (size_t)n_queries * n_cand, n_out = (size_t)n_queries * k;
-    Staging st(mem, s);
-    const float* d_sc;
-    const int32_t* d_ca;
-    float* d_s;
-    int32_t *d_c, *d_p, *d_n;
-    RL_TRY(st.in(scores, n_in, &d_sc));
-    RL_TRY(st.in(candidates, n_in, &d_ca));
-    RL_TRY(st.out(out_scores, n_out, &d_s));
-    RL_TRY(st.out(out_chunks, n_out, &d_c));
-    RL_TRY(st.out(out_pos, n_out, &d_p));
-    RL_TRY(st.out(out_counts, (size_t)n_queries, &d_n));
-    RL_TRY(launch_rerank_order(d_sc, d_ca, n_queries, n_cand, k, d_s, d_c, d_p, d_n, s));
-    return st.finish();
-}
-
-}  // extern "C"
-
-// ---- chunk spans (include/raglite_hip.h; the kernel is in spans.hip) -------------------------------------------------------------------
-// Immutable after rl_span_table_create: calls on any stream may share it without a lock.
-struct rl_span_table {
-    int64_t n_chunks = 0;
-    int64_t n_live = 0;                 // chunks with a position
-    rl::DevArray<int32_t> rank_of;      // [n_chunks] the chunk's rank in (doc, pos) order, -1: no position
-    rl::DevArray<uint64_t> tab_key;     // [n_live] doc << 32 | pos, ascending
-    rl::DevArray<int32_t> tab_ord;      // [n_live] the chunk ordinal at that rank
-};
-
-namespace {
-// What rl_search_rerank_per_query and rl_search_rerank_spans_per_query need before their device work: hybrid_search_begin's, and the
-// query token vectors staged.
-struct RerankCall {
-    HybridCall c;
-    const float* d_v = nullptr;
-    RerankCall(int mem, hipStream_t s) : c(mem, s) {}
-};
-
-// The checks of rl_search_rerank_per_query, the locks and the staging-in
-int search_rerank_begin(rl_index* idx, rl_keyword_index* kw, const float* queries, int32_t B, int32_t num_hits, int32_t n_each,
-                        const int64_t* q_off, const int32_t* q_terms, const uint32_t* chunk_filters, int32_t n_filters,
-                        const int32_t* query_filter, const int64_t* rank_limits, const double* weights, int32_t rrf_k, int32_t n_cand,
-                        const float* query_vecs, int32_t nq, int32_t k, bool outputs, int mem, hipStream_t s, const char* who, RerankCall* rc) {
-    if (nq < 1) return fail(RL_ERR_INVALID, std::string(who) + ": nq must be >= 1");
-    if (n_cand < 1 || n_cand > RERANK_MAX_ENTRIES) return fail(RL_ERR_INVALID, std::string(who) + ": n_cand must be in [1, 4096]");
-    if (k < 1 || k > n_cand) return fail(RL_ERR_INVALID, std::string(who) + ": k must be in [1, n_cand]");
-    RL_TRY(check_query_filters(B, chunk_filters, n_filters, query_filter, rank_limits, who));
-    if (idx && idx->E16 && (nq > 32 || idx->dim % 16))
-        return fail(RL_ERR_UNSUPPORTED, std::string(who) + ": MaxSim reranking on an fp16-stored index needs nq <= 32 and dim % 16 == 0");
-    RL_TRY(hybrid_search_begin(idx, kw, queries, B, num_hits, n_each, q_off, q_terms, chunk_filters, query_filter ? n_filters : 0, query_filter,
-                               rank_limits, 0, weights, rrf_k, n_cand, query_vecs && outputs, mem, s, who, &rc->c));
-    if (rc->c.empty) return RL_OK;
-    return rc->c.st.in(query_vecs, (size_t)B * nq * idx->dim, &rc->d_v);
-}
-
-// The searches, the fusion, the MaxSim rerank and the ordering on device pointers (after search_rerank_begin): d_c [B x k], d_n [B];
-// d_s [B x k], or nullptr: the scores stay in the index's scratch
-int search_rerank_device(rl_index* idx, rl_keyword_index* kw, const RerankCall& rc, int32_t B, int32_t num_hits, int32_t n_each,
-                         const double* weights, int32_t rrf_k, int32_t n_cand, int32_t nq, int32_t k, float* d_s, int32_t* d_c, int32_t* d_n,
-                         hipStream_t s) {
-    const size_t n_list = (size_t)B * n_cand, n_out = (size_t)B * k;
-    // index-owned scratch: the fused scores [B x n_cand] f64 (written, not read), the fused candidates [B x n_cand] int32, their
-    // MaxSim scores [B x n_cand] f32, the fusion's counts [B] and the positions of the first k [B x k] int32 (written, not read);
-    // without d_s the scores of the first k [B x k] f32 (written, not read)
-    RL_TRY(idx->rerank.reserve(n_list * 16 + (size_t)B * 4 + n_out * 4 + (d_s ? 0 : n_out * 4)));
-    double* fused_scores = idx->rerank.as<double>();
-    int32_t* fused = reinterpret_cast<int32_t*>(fused_scores + n_list);
-    float* maxsim = reinterpret_cast<float*>(fused + n_list);
-    int32_t* fused_counts = reinterpret_cast<int32_t*>(maxsim + n_list);
-    int32_t* pos = fused_counts + B;
-    if (!d_s) d_s = reinterpret_cast<float*>(pos + n_out);
-    RL_TRY(hybrid_search_device(idx, kw, rc.c, B, num_hits, n_each, weights, rrf_k, n_cand, fused_scores, fused, fused_counts, s));
-    RL_TRY(maxsim_rerank_device(idx, rc.d_v, B, nq, fused, n_cand, maxsim, s));
-    return launch_rerank_order(maxsim, fused, B, n_cand, k, d_s, d_c, pos, d_n, s);
-}
-
-// rl_chunk_spans' limits
-int check_span_args(const rl_span_table* table, int32_t n_queries, int32_t n_in, const int32_t* offsets, int32_t n_off, int mem,
-                    const char* who) {
-    if (!table) return fail(RL_ERR_INVALID, std::string(who) + ": null span table");
-    if (n_queries < 0) return fail(RL_ERR_INVALID, std::string(who) + ": n_queries must be >= 0");
-    if (n_off < 0 || n_off > SPANS_MAX_OFFSETS) return fail(RL_ERR_INVALID, std::string(who) + ": n_off must be in [0, 64]");
-    if (n_in < 1 || (int64_t)n_in * (1 + n_off) > SPANS_MAX_ENTRIES)
-        return fail(RL_ERR_INVALID, std::string(who) + ": need n_in >= 1 and n_in * (1 + n_off) <= 4096");
-    if (n_off > 0 && !offsets) return fail(RL_ERR_INVALID, std::string(who) + ": null offsets");
-    if (mem != RL_MEM_HOST && mem != RL_MEM_DEVICE) return fail(RL_ERR_INVALID, std::string(who) + ": bad mem");
-    return RL_OK;
-}
-
-// The five outputs of the span kernel for a batch, as the kernel takes them ...
-struct SpanPtrs {
-    int32_t *d_c = nullptr, *d_l = nullptr, *d_ns = nullptr, *d_nc = nullptr;
-    double* d_s = nullptr;
-};
-// ... registered on a call's frame: [n] chunks, span lengths and span scores, [B] span and chunk counts
-int span_outputs(Staging& st, int32_t* out_chunks, int32_t* out_span_len, double* out_span_scores, int32_t* out_n_spans, int32_t* out_n_chunks,
-                 size_t n, size_t B, SpanPtrs* o) {
-    RL_TRY(st.out(out_chunks, n, &o->d_c));
-    RL_TRY(st.out(out_span_len, n, &o->d_l));
-    RL_TRY(st.out(out_span_scores, n, &o->d_s));
-    RL_TRY(st.out(out_n_spans, B, &o->d_ns));
-    return st.out(out_n_chunks, B, &o->d_nc);
-}
-
-int spans_device(const rl_span_table* t, const int32_t* d_in, int32_t B, int32_t n_in, const int32_t* offsets, int32_t n_off,
-                 const SpanPtrs& o, hipStream_t s) {
-    return launch_chunk_spans(t->rank_of, t->tab_key, t->tab_ord, (int32_t)t->n_chunks, (int32_t)t->n_live, d_in, B, n_in, offsets, n_off,
-                              o.d_c, o.d_l, o.d_s, o.d_ns, o.d_nc, s);
-}
-}  // namespace
-
-extern "C" {
-
-int rl_search_rerank_per_query(rl_index* idx, rl_keyword_index* kw, const float* queries, int32_t n_queries, int32_t num_hits, int32_t n_each,
-                               const int64_t* q_off, const int32_t* q_terms, const uint32_t* chunk_filters, int32_t n_filters,
-                               const int32_t* query_filter, const int64_t* rank_limits, const double* weights, int32_t rrf_k, int32_t n_cand,
-                               const float* query_vecs, int32_t nq, int32_t k, float* out_scores, int32_t* out_chunks, int32_t* out_counts,
-                               int mem, void* stream) {
-    const char* who = "rl_search_rerank_per_query";
-    const int32_t B = n_queries;
-    hipStream_t s = as_stream(stream);
-    RerankCall rc(mem, s);
-    RL_TRY(search_rerank_begin(idx, kw, queries, B, num_hits, n_each, q_off, q_terms, chunk_filters, n_filters, query_filter, rank_limits, weights,
-                               rrf_k, n_cand, query_vecs, nq, k, out_scores && out_chunks && out_counts, mem, s, who, &rc));
-    if (rc.c.empty) return RL_OK;
-    Staging& st = rc.c.st;
-    const size_t n_out = (size_t)B * k;
-    float* d_s;
-    int32_t *d_c, *d_n;
-    RL_TRY(st.out(out_scores, n_out, &d_s));
-    RL_TRY(st.out(out_chunks, n_out, &d_c));
-    RL_TRY(st.out(out_counts, (size_t)B, &d_n));
-    RL_TRY(search_rerank_device(idx, kw, rc, B, num_hits, n_each, weights, rrf_k, n_cand, nq, k, d_s, d_c, d_n, s));
-    return st.finish();
-}
-
-int rl_span_table_create(rl_span_table** out, const int32_t* doc, const int32_t* pos, int64_t n_chunks) {
-    const char* who = "rl_span_table_create";
-    if (!out) return fail(RL_ERR_INVALID, std::string(who) + ": null output handle");
-    *out = nullptr;
-    if (n_chunks < 0) return fail(RL_ERR_INVALID, std::string(who) + ": negative size");
-    if (n_chunks >= (int64_t)0x7fffffff - 1) return fail(RL_ERR_UNSUPPORTED, std::string(who) + ": more than 2^31-2 chunks");
-    if (n_chunks > 0 && (!doc || !pos)) return fail(RL_ERR_INVALID, std::string(who) + ": null argument");
-    std::vector<std::pair<uint64_t, int32_t>> live;  // (doc << 32 | pos, ordinal)
-    for (int64_t c = 0; c < n_chunks; ++c) {
-        if (doc[c] < 0) continue;
-        if (pos[c] < 0) return fail(RL_ERR_INVALID, std::string(who) + ": pos must be >= 0");
-        live.emplace_back(((uint64_t)(uint32_t)doc[c] << 32) | (uint32_t)pos[c], (int32_t)c);
-    }
-    std::sort(live.begin(), live.end());
-    for (size_t r = 1; r < live.size(); ++r)
-        if (live[r].first == live[r - 1].first) return fail(RL_ERR_INVALID, std::string(who) + ": two chunks share a (doc, pos)");
-    std::vector<int32_t> rank_of((size_t)n_chunks, -1), tab_ord(live.size());
-    std::vector<uint64_t> tab_key(live.size());
-    for (size_t r = 0; r < live.size(); ++r) {
-        tab_key[r] = live[r].first;
-        tab_ord[r] = live[r].second;
-        rank_of[(size_t)live[r].second] = (int32_t)r;
-    }
-    std::unique_ptr<rl_span_table> t(new rl_span_table());
-    t->n_chunks = n_chunks;
-    t->n_live = (int64_t)live.size();
-    RL_TRY(t->rank_of.alloc(std::max<size_t>(rank_of.size() * sizeof(int32_t), 16), who));
-    RL_TRY(t->tab_key.alloc(std::max<size_t>(tab_key.size() * sizeof(uint64_t), 16), who));
-    RL_TRY(t->tab_ord.alloc(std::max<size_t>(tab_ord.size() * sizeof(int32_t), 16), who));
-    if (n_chunks) RL_HIP(hipMemcpy(t->rank_of, rank_of.data(), rank_of.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-    if (!live.empty()) {
-        RL_HIP(hipMemcpy(t->tab_key, tab_key.data(), tab_key.size() * sizeof(uint64_t), hipMemcpyHostToDevice));
-        RL_HIP(hipMemcpy(t->tab_ord, tab_ord.data(), tab_ord.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-    }
-    *out = t.release();
-    return RL_OK;
-}
-
-int rl_span_table_destroy(rl_span_table* table) {
-    if (!table) return RL_OK;
-    delete table;
-    return RL_OK;
-}
-
-int rl_span_table_info(const rl_span_table* table, int64_t* n_chunks, int64_t* n_live, int64_t* device_bytes) {
-    if (!table) return fail(RL_ERR_INVALID, "rl_span_table_info: null span table");
-    if (n_chunks) *n_chunks = table->n_chunks;
-    if (n_live) *n_live = table->n_live;
-    if (device_bytes) *device_bytes = (int64_t)(table->rank_of.cap + table->tab_key.cap + table->tab_ord.cap);
-    return RL_OK;
-}
-
-int rl_chunk_spans(const rl_span_table* table, const int32_t* chunks, int32_t n_queries, int32_t n_in, const int32_t* offsets, int32_t n_off,
-                   int32_t* out_chunks, int32_t* out_span_len, double* out_span_scores, int32_t* out_n_spans, int32_t* out_n_chunks, int mem,
-                   void* stream) {
-    const char* who = "rl_chunk_spans";
-    RL_TRY(check_span_args(table, n_queries, n_in, offsets, n_off, mem, who));
-    if (n_queries == 0) return RL_OK;
-    if (!chunks || !out_chunks || !out_span_len || !out_span_scores || !out_n_spans || !out_n_chunks)
-        return fail(RL_ERR_INVALID, std::string(who) + ": null argument");
-    hipStream_t s = as_stream(stream);
-    const size_t B = (size_t)n_queries, n_out = B * n_in * (1 + n_off);
-    Staging st(mem, s);
-    const int32_t* d_in;
-    SpanPtrs o;
-    RL_TRY(st.in(chunks, B * n_in, &d_in));
-    RL_TRY(span_outputs(st, out_chunks, out_span_len, out_span_scores, out_n_spans, out_n_chunks, n_out, B, &o));
-    RL_TRY(spans_device(table, d_in, n_queries, n_in, offsets, n_off, o, s));
-    return st.finish();
-}
-
-int rl_search_rerank_spans_per_query(rl_index* idx, rl_keyword_index* kw, const float* queries, int32_t n_queries, int32_t num_hits,
-                                     int32_t n_each, const int64_t* q_off, const int32_t* q_terms, const uint32_t* chunk_filters,
-                                     int32_t n_filters, const int32_t* query_filter, const int64_t* rank_limits, const double* weights,
-                                     int32_t rrf_k, int32_t n_cand, const float* query_vecs, int32_t nq, int32_t k, const rl_span_table* table,
-                                     const int32_t* offsets, int32_t n_off, int32_t* out_top_chunks, int32_t* out_top_counts,
-                                     int32_t* out_chunks, int32_t* out_span_len, double* out_span_scores, int32_t* out_n_spans,
-                                     int32_t* out_n_chunks, int mem, void* stream) {
-    const char* who = "rl_search_rerank_spans_per_query";
-    const int32_t B = n_queries;
-    RL_TRY(check_span_args(table, B, k, offsets, n_off, args_mem(mem), who));  // (k * (1 + n_off) <= 4096)
-    if (idx && table->n_chunks != idx->n_chunks) return fail(RL_ERR_INVALID, std::string(who) + ": the span table covers another number of chunks");
-    hipStream_t s = as_stream(stream);
-    RerankCall rc(mem, s);
-    RL_TRY(search_rerank_begin(idx, kw, queries, B, num_hits, n_each, q_off, q_terms, chunk_filters, n_filters, query_filter, rank_limits, weights,
-                               rrf_k, n_cand, query_vecs, nq, k,
-                               out_top_chunks && out_top_counts && out_chunks && out_span_len && out_span_scores && out_n_spans && out_n_chunks,
-                               mem, s, who, &rc));
-    if (rc.c.empty) return RL_OK;
-    Staging& st = rc.c.st;
-    const size_t n_top = (size_t)B * k, n_out = n_top * (1 + n_off);
-    int32_t *d_c, *d_n;
-    SpanPtrs o;
-    RL_TRY(st.out(out_top_chunks, n_top, &d_c));
-    RL_TRY(st.out(out_top_counts, (size_t)B, &d_n));
-    RL_TRY(span_outputs(st, out_chunks, out_span_len, out_span_scores, out_n_spans, out_n_chunks, n_out, (size_t)B, &o));
-    RL_TRY(search_rerank_device(idx, kw, rc, B, num_hits, n_each, weights, rrf_k, n_cand, nq, k, nullptr, d_c, d_n, s));
-    RL_TRY(spans_device(table, d_c, B, k, offsets, n_off, o, s));
-    return st.finish();
-}
-
-}  // extern "C"
-
-// ---- metadata filters on the device (include/raglite_hip.h; the kernel is in metadata.hip) --------------------------------------------
-struct rl_metadata_store {
-    int64_t n_chunks = 0, n_tags = 0;
-    int64_t cap_off = 0, cap_tags = 0;  // items the two arrays can hold
-    rl::DevArray<int64_t> tag_off;      // [n_chunks + 1]
-    rl::DevArray<int32_t> tags;         // [n_tags]
-    std::mutex mu;
-};
-
-// What rl_metadata_filters leaves on the device: the bitsets [n_filters x words] and the counts [2 x n_filters].  Grown, never shrunk.
-struct rl_filter_set {
-    rl::Pool bits, counts, f_off, f_tags;  // (the last two: the filters' own CSR, staged for host callers)
-    int32_t n_filters = 0;
-    int64_t words = 0;
-};
-
-namespace {
-
-// A CSR handed in by the caller, read on the host: from 0, ascending; returns its last entry in *total
-int check_csr(const int64_t* off, int64_t n, int mem, hipStream_t s, const char* who, const char* name, std::vector<int64_t>* h_off,
-              int64_t* total) {
-    h_off->resize((size_t)n + 1);
-    if (mem == RL_MEM_HOST) std::memcpy(h_off->data(), off, h_off->size() * sizeof(int64_t));
-    else {
-        RL_TRY(hip_status(hipMemcpyAsync(h_off->data(), off, h_off->size() * sizeof(int64_t), hipMemcpyDeviceToHost, s), who));
-        RL_TRY(hip_status(hipStreamSynchronize(s), who));
-    }
-    if ((*h_off)[0] != 0) return fail(RL_ERR_INVALID, std::string(who) + ": " + name + " must start at 0");
-    for (int64_t i = 0; i < n; ++i)
-        if ((*h_off)[(size_t)i + 1] < (*h_off)[(size_t)i]) return fail(RL_ERR_INVALID, std::string(who) + ": " + name + " must be ascending");
-    *total = (*h_off)[(size_t)n];
-    return RL_OK;
-}
-
-// rl_metadata_store_append, and the one append of rl_metadata_store_create
-int metadata_append(rl_metadata_store* st, const int64_t* tag_off, const int32_t* tags, int64_t n_new, int mem, void* stream, const char* who) {
-    if (n_new < 0) return fail(RL_ERR_INVALID, std::string(who) + ": negative size");
-    if (mem != RL_MEM_HOST && mem != RL_MEM_DEVICE) return fail(RL_ERR_INVALID, std::string(who) + ": bad mem");
-    if (n_new > 0 && !tag_off) return fail(RL_ERR_INVALID, std::string(who) + ": null tag_off");
-    if (!st) return fail(RL_ERR_INVALID, std::string(who) + ": null store");
-    if (n_new == 0) return RL_OK;
-    hipStream_t s = as_stream(stream);
-    std::vector<int64_t> h_off;
-    int64_t n_add = 0;
-    RL_TRY(check_csr(tag_off, n_new, mem, s, who, "tag_off", &h_off, &n_add));
-    if (n_add > 0 && !tags) return fail(RL_ERR_INVALID, std::string(who) + ": null tags");
-    std::lock_guard<std::mutex> lock(st->mu);
-    if (st->n_chunks + n_new >= (int64_t)0x7fffffff - 1) return fail(RL_ERR_UNSUPPORTED, std::string(who) + ": more than 2^31-2 chunks");
-    if (st->n_tags + n_add >= (int64_t)0x7fffffff) return fail(RL_ERR_UNSUPPORTED, std::string(who) + ": 2^31 tags or more");
-    RL_TRY(store_grow(st->tag_off, &st->cap_off, st->n_chunks ? st->n_chunks + 1 : 0, st->n_chunks + n_new + 1, s, who));
-    RL_TRY(store_grow(st->tags, &st->cap_tags, st->n_tags, st->n_tags + n_add, s, who));
-    for (int64_t& o : h_off) o += st->n_tags;  // (h_off[0] is what tag_off[n_chunks] holds already, or the first 0)
-    RL_TRY(hip_status(hipMemcpyAsync(st->tag_off + st->n_chunks, h_off.data(), h_off.size() * sizeof(int64_t), hipMemcpyHostToDevice, s), who));
-    if (n_add > 0)
-        RL_TRY(hip_status(hipMemcpyAsync(st->tags + st->n_tags, tags, (size_t)n_add * sizeof(int32_t),
-                                         mem == RL_MEM_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, s), who));
-    RL_TRY(hip_status(hipStreamSynchronize(s), who));  // the caller's arrays and h_off may go away after return
-    st->n_chunks += n_new;
-    st->n_tags += n_add;
-    return RL_OK;
-}
-
-}  // namespace
-
-extern "C" {
-
-int rl_metadata_store_append(rl_metadata_store* st, const int64_t* tag_off, const int32_t* tags, int64_t n_new, int mem, void* stream) {
-    return metadata_append(st, tag_off, tags, n_new, mem, stream, "rl_metadata_store_append");
-}
-
-int rl_metadata_store_create(rl_metadata_store** out, const int64_t* tag_off, const int32_t* tags, int64_t n_chunks, int mem, void* stream) {
-    const char* who = "rl_metadata_store_create";
-    if (!out) return fail(RL_ERR_INVALID, std::string(who) + ": null output handle");
-    *out = nullptr;
-    if (n_chunks < 0) return fail(RL_ERR_INVALID, std::string(who) + ": negative size");
-    if (mem != RL_MEM_HOST && mem != RL_MEM_DEVICE) return fail(RL_ERR_INVALID, std::string(who) + ": bad mem");
-    if (n_chunks > 0 && !tag_off) return fail(RL_ERR_INVALID, std::string(who) + ": null tag_off");
-    std::unique_ptr<rl_metadata_store> st(new rl_metadata_store());
-    RL_TRY(metadata_append(st.get(), tag_off, tags, n_chunks, mem, stream, who));
-    *out = st.release();
-    return RL_OK;
-}
-
-int rl_metadata_store_memory(const rl_metadata_store* st, int64_t out[2]) {
-    if (!st || !out) return fail(RL_ERR_INVALID, "rl_metadata_store_memory: null argument");
-    std::lock_guard<std::mutex> lock(const_cast<rl_metadata_store*>(st)->mu);
-    out[0] = (st->n_chunks ? (st->n_chunks + 1) * (int64_t)sizeof(int64_t) : 0) + st->n_tags * (int64_t)sizeof(int32_t);
-    out[1] = (int64_t)(st->tag_off.cap + st->tags.cap);
-    return RL_OK;
-}
-
-int rl_metadata_store_destroy(rl_metadata_store* st) {
-    delete st;
-    return RL_OK;
-}
-
-int rl_metadata_filters(rl_metadata_store* st, rl_index* idx, const int64_t* f_off, const int32_t* f_tags, int32_t n_filters,
-                        rl_filter_set** inout_set, int64_t* out_chunks, int64_t* out_rows, int mem, void* stream) {
-    const char* who = "rl_metadata_filters";
-    if (n_filters < 0) return fail(RL_ERR_INVALID, std::string(who) + ": n_filters must be >= 0");
-    if (n_filters > MF_GROUP * 65535) return fail(RL_ERR_UNSUPPORTED, std::string(who) + ": more than 64 * 65535 filters");
-    if (mem != RL_MEM_HOST && mem != RL_MEM_DEVICE) return fail(RL_ERR_INVALID, std::string(who) + ": bad mem");
-    if (!inout_set) return fail(RL_ERR_INVALID, std::string(who) + ": null inout_set");
-    if (n_filters > 0 && (!f_off || !out_chunks || !out_rows)) return fail(RL_ERR_INVALID, std::string(who) + ": null f_off or output");
-    if (!st) return fail(RL_ERR_INVALID, std::string(who) + ": null store");
-    if (!idx) return fail(RL_ERR_INVALID, std::string(who) + ": null index");
-    hipStream_t s = as_stream(stream);
-    std::vector<int64_t> h_off;
-    int64_t n_ftags = 0;
-    if (n_filters > 0) RL_TRY(check_csr(f_off, n_filters, mem, s, who, "f_off", &h_off, &n_ftags));
-    if (n_ftags >= (int64_t)0x7fffffff) return fail(RL_ERR_UNSUPPORTED, std::string(who) + ": 2^31 filter tags or more");
-    if (n_ftags > 0 && !f_tags) return fail(RL_ERR_INVALID, std::string(who) + ": null f_tags");
-    std::lock_guard<std::mutex> idx_lock(idx->mu);  // (idx->mu, then the store's: the chunk offsets must not move under the launch)
-    std::lock_guard<std::mutex> lock(st->mu);
-    if (st->n_chunks != idx->n_chunks) return fail(RL_ERR_INVALID, std::string(who) + ": the metadata store covers another number of chunks");
-    std::unique_ptr<rl_filter_set> fresh;
-    rl_filter_set* set = *inout_set;
-    if (!set) {
-        fresh.reset(new rl_filter_set());
-        set = fresh.get();
-    }
-    const int64_t n = st->n_chunks, words = (n + 31) / 32;
-    set->n_filters = 0;  // (until the launch is enqueued)
-    RL_TRY(set->bits.reserve(std::max<size_t>((size_t)n_filters * (size_t)words * sizeof(uint32_t), 16)));  // (never null: an empty index)
-    RL_TRY(set->counts.reserve((size_t)2 * n_filters * sizeof(unsigned long long)));
-    const int64_t* d_off = f_off;
-    const int32_t* d_tags = f_tags;
-    if (mem == RL_MEM_HOST && n_filters > 0) {
-        RL_TRY(set->f_off.reserve(h_off.size() * sizeof(int64_t)));
-        RL_TRY(set->f_tags.reserve((size_t)std::max<int64_t>(n_ftags, 1) * sizeof(int32_t)));
-        RL_HIP(hipMemcpyAsync(set->f_off.p, h_off.data(), h_off.size() * sizeof(int64_t), hipMemcpyHostToDevice, s));
-        if (n_ftags) RL_HIP(hipMemcpyAsync(set->f_tags.p, f_tags, (size_t)n_ftags * sizeof(int32_t), hipMemcpyHostToDevice, s));
-        d_off = set->f_off.as<int64_t>();
-        d_tags = set->f_tags.as<int32_t>();
-    }
-    unsigned long long* counts = set->counts.as<unsigned long long>();
-    RL_TRY(launch_metadata_filters(st->tag_off, st->tags, n, idx->offsets, d_off, d_tags, n_filters, set->bits.as<uint32_t>(), counts, s));
-    if (n_filters > 0) {
-        const hipMemcpyKind kind = mem == RL_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
-        RL_HIP(hipMemcpyAsync(out_chunks, counts, (size_t)n_filters * sizeof(int64_t), kind, s));
-        RL_HIP(hipMemcpyAsync(out_rows, counts + n_filters, (size_t)n_filters * sizeof(int64_t), kind, s));
-    }
-    if (mem == RL_MEM_HOST) RL_HIP(hipStreamSynchronize(s));
-    set->n_filters = n_filters;
-    set->words = words;
-    if (fresh) *inout_set = fresh.release();
-    return RL_OK;
-}
-
-int rl_filter_set_bits(const rl_filter_set* set, const uint32_t** out_device_bits, int32_t* out_n_filters, int64_t* out_words) {
-    if (!set) return fail(RL_ERR_INVALID, "rl_filter_set_bits: null filter set");
-    if (out_device_bits) *out_device_bits = set->bits.as<uint32_t>();
-    if (out_n_filters) *out_n_filters = set->n_filters;
-    if (out_words) *out_words = set->words;
-    return RL_OK;
-}
-
-int rl_filter_set_read(const rl_filter_set* set, uint32_t* out, int mem, void* stream) {
-    const char* who = "rl_filter_set_read";
-    if (mem != RL_MEM_HOST && mem != RL_MEM_DEVICE) return fail(RL_ERR_INVALID, std::string(who) + ": bad mem");
-    if (!set) return fail(RL_ERR_INVALID, std::string(who) + ": null filter set");
-    const size_t bytes = (size_t)set->n_filters * (size_t)set->words * sizeof(uint32_t);
-    if (bytes == 0) return RL_OK;
-    if (!out) return fail(RL_ERR_INVALID, std::string(who) + ": null output");
-    hipStream_t s = as_stream(stream);
-    RL_HIP(hipMemcpyAsync(out, set->bits.p, bytes, mem == RL_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, s));
-    if (mem == RL_MEM_HOST) RL_HIP(hipStreamSynchronize(s));
-    return RL_OK;
-}
-
-int rl_filter_set_destroy(rl_filter_set* set) {
-    delete set;
-    return RL_OK;
 }
 
 }  // extern "C"

@@ -1,7 +1,7 @@
 // What the document-batched kernels share (partition_sim.hip, partition_dp.hip, chunklet_dp.hip, sentence_dp.hip; DESIGN.md
 // section 4.13b): a batch is n rows and a CSR `off` of n_docs + 1 offsets, document d owning rows [off[d], off[d + 1]).
 //
-// Host callers' offsets are checked before the first HIP call (api.hip: check_doc_offsets).  Device callers' offsets cannot be read
+// Host callers' offsets are checked before the first HIP call (api_ingest.hip: check_doc_offsets).  Device callers' offsets cannot be read
 // without a synchronisation, so they are not validated: every kernel takes a document's rows from doc_rows, which forces them into
 // [0, n], and doc_of returns a document in [0, n_docs) for any row.  With malformed offsets the results are unspecified, but no kernel
 // indexes past n.

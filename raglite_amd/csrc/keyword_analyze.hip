@@ -1,4 +1,4 @@
-// The BM25 index analyzer on the device (rl_keyword_analyze_begin / _finish; driven from api.hip): what
+// The BM25 index analyzer on the device (rl_keyword_analyze_begin / _finish; driven from api_keyword.hip): what
 // raglite_amd._keyword.index_stems + stems_to_store_ids do for many chunk bodies, on their UTF-32 code points.
 //   1. fold      every code point has an image of 0 .. KA_IMAGE_MAX symbols over {a-z, separator, backslash, newline} (the host builds
 //                the table from _keyword.normalize): count, exclusive scan, write -> the folded stream, one byte per symbol

@@ -1,4 +1,4 @@
-// Building the BM25 postings on the device (rl_keyword_store_count; driven from api.hip).  The store keeps each chunk's term ids
+// Building the BM25 postings on the device (rl_keyword_store_count; driven from api_keyword.hip).  The store keeps each chunk's term ids
 // chunk-major (tok_off / tok_term); the postings are term-major.  The transposition is
 //   1. emit     (key = term_rank[tok_term], value = chunk) for the tokens of live chunks, in token order
 //   2. sort     stable LSD radix sort on the key alone, 8-bit digits: per pass a per-block digit histogram, an exclusive scan of the

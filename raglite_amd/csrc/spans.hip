@@ -2,7 +2,7 @@
 // batch of queries, on chunk ordinals: score the chunks by their place in the list, add their neighbours, deduplicate, order by
 // (document, index), cut into runs of consecutive indices, sum each run's scores and order the runs by that sum.
 //
-// The span table (rl_span_table, api.hip) holds the live chunks sorted by (doc, pos), doc being the dense number of the chunk's
+// The span table (rl_span_table, api_retrieval.hip) holds the live chunks sorted by (doc, pos), doc being the dense number of the chunk's
 // document_id in sorted order: rank_of[ordinal] (-1: no position), tab_key[rank] = doc << 32 | pos and tab_ord[rank].
 //
 // Per query b there are n_in entries, best first, and n_off offsets; E = n_in * (1 + n_off) <= 4096 slots.

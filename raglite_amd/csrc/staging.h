@@ -15,6 +15,14 @@ inline int hip_status(hipError_t e, const char* who) {
     return fail(e == hipErrorOutOfMemory ? RL_ERR_NOMEM : RL_ERR_HIP, std::string(who) + ": " + hipGetErrorString(e));
 }
 
+// The two arguments every entry point ends with: `stream` as the C ABI passes it, and `mem`, which is one of the two once an entry
+// that takes filters has split RL_MEM_FILTERS_DEVICE off.
+inline hipStream_t as_stream(void* s) { return reinterpret_cast<hipStream_t>(s); }
+inline int check_mem(int mem, const char* who) {
+    if (mem != RL_MEM_HOST && mem != RL_MEM_DEVICE) return fail(RL_ERR_INVALID, std::string(who) + ": bad mem");
+    return RL_OK;
+}
+
 // The per-thread state below is `inline thread_local`, so every translation unit that includes this header shares one instance per
 // thread, and hidden: the library keeps it to itself, which lets the compiler reach it without a call through the PLT per access
 // (host-argument calls are latency-bound and touch it some thirty times).
