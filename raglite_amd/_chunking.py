@@ -42,20 +42,12 @@ def partition_similarities(embeddings: Any, doc_offsets: np.ndarray, chunklet_si
     sel = np.concatenate([_nonoutlying(sizes[off[d] : off[d + 1]]) if off[d + 1] > off[d] else np.zeros(0, np.uint8)
                           for d in range(len(off) - 1)]) if len(off) > 1 else np.zeros(0, np.uint8)
     a = _ops._Args()  # noqa: SLF001
-    p_x = a.inp(embeddings, np.float32)
-    x = a.keep[0]
+    x, p_x = a.inp(embeddings, np.float32)
     n, dim = int(x.shape[0]), int(x.shape[1])
     if n != int(off[-1]) or len(sel) != n:
         raise ValueError("doc_offsets / chunklet_sizes do not match the embedding rows")
-    if a.mem == _ops.MEM_DEVICE:
-        torch = _ops._torch()  # noqa: SLF001
-        t_off = torch.from_numpy(off).to(a.device)
-        t_sel = torch.from_numpy(sel).to(a.device)
-        a.keep += [t_off, t_sel]
-        p_off, p_sel = t_off.data_ptr(), t_sel.data_ptr()
-    else:
-        a.keep += [off, sel]
-        p_off, p_sel = off.ctypes.data, sel.ctypes.data
+    _, p_off = a.same_side(off, np.int64)
+    _, p_sel = a.same_side(sel, np.uint8)
     out, p_out = a.out((n,), np.float32)
     a.ensure_device()
     check(lib().rl_partition_similarity(p_x, n, dim, p_off, len(off) - 1, p_sel, p_out, a.mem, a.stream))

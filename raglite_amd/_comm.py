@@ -18,9 +18,12 @@ import numpy as np
 
 from raglite_amd import _ops
 from raglite_amd._abi import COMM_ID_BYTES, check, lib
+from raglite_amd._ops_frame import _Handle
 
 
-class Communicator:
+class Communicator(_Handle):
+    _destroy = "rl_comm_destroy"
+
     def __init__(self, rank: int, world: int, unique_id: bytes) -> None:
         if len(unique_id) != COMM_ID_BYTES:
             raise ValueError(f"unique_id must be {COMM_ID_BYTES} bytes")
@@ -28,7 +31,7 @@ class Communicator:
         handle = C.c_void_p()
         buf = C.create_string_buffer(bytes(unique_id), COMM_ID_BYTES)
         check(lib().rl_comm_init(C.byref(handle), int(rank), int(world), buf))
-        self._handle: C.c_void_p | None = handle
+        self._handle = handle
         self.rank, self.world = int(rank), int(world)
 
     @staticmethod
@@ -87,25 +90,13 @@ class Communicator:
             return None, err
         return comm, None
 
-    def close(self) -> None:
-        if self._handle is not None:
-            check(lib().rl_comm_destroy(self._handle))
-            self._handle = None
-
-    def __del__(self) -> None:  # noqa: D105
-        try:
-            self.close()
-        except Exception:  # noqa: BLE001 - interpreter teardown
-            pass
-
     def _args(self, scores, ids):
         a = _ops._Args()
-        p_s = a.inp(scores, np.float32)
-        p_i = a.inp(ids, np.int32)
+        s, p_s = a.inp(scores, np.float32)
+        i, p_i = a.inp(ids, np.int32)
         if a.mem != _ops.MEM_DEVICE:
             raise ValueError("the RCCL exchange moves device memory: pass CUDA tensors")
-        s = a.keep[0]
-        if s.dim() != 2 or tuple(a.keep[1].shape) != tuple(s.shape):
+        if s.dim() != 2 or tuple(i.shape) != tuple(s.shape):
             raise ValueError("scores and ids must both be (n_queries, k)")
         a.ensure_device()
         return a, p_s, p_i, int(s.shape[0]), int(s.shape[1])

@@ -80,9 +80,9 @@ def _partition_case():
 def _partition_chunks(cost, sizes, off, max_size, want_objective):
     """raglite_amd.partition_chunks with the objective optional: the wrapper's own steps (it always asks for the objective)."""
     a = _ops._Args()
-    p_cost = a.inp(cost, np.float32)
-    p_sizes = _ops._same_side(a, sizes, np.int64)
-    p_off = _ops._same_side(a, off, np.int64)
+    _, p_cost = a.inp(cost, np.float32)
+    _, p_sizes = _ops._same_side(a, sizes, np.int64)
+    _, p_off = _ops._same_side(a, off, np.int64)
     n, n_docs = int(cost.shape[0]), int(off.shape[0]) - 1
     out, ptrs = _ops._partition_outputs(a, n, n_docs, want_objective)
     _ops.check(_ops.lib().rl_partition_chunks(p_cost, p_sizes, p_off, n, n_docs, int(max_size), *ptrs, a.mem, a.stream))
