@@ -834,7 +834,12 @@ int rl_query_targets(rl_index* index, const float* queries, int32_t n_queries, c
  *   nonoutlying  uint8[n], nonzero = chunklet size within the document's 15 %..85 % quantiles
  *                (:57-58, computed on the host from string lengths); NULL = no discourse removal
  *   out          f32[n]: out[i] = max((x_i . x_{i+1} + 1) / 2, sqrt(eps)) on the normalised,
- *                discourse-free rows (:59-72); 0 for the last row of a document. */
+ *                discourse-free rows (:59-72); 0 for the last row of a document.
+ * A document with exactly ONE nonoutlying row keeps its plain similarities (no discourse removal):
+ * its discourse vector IS that row, so the row's residual is zero in exact arithmetic, which is the
+ * reference's own "would zero a row" case (:62-65).  The reference decides it by fp32 rounding (a
+ * residual norm of 0 .. 2.5e-7 against eps = 1.19e-7); before this rule the device did too, and 25 /
+ * 23 / 20 / 9 of 200 such documents at dim 64 / 128 / 256 / 1024 got arbitrary similarities. */
 int rl_partition_similarity(const float* X, int64_t n, int32_t dim, const int64_t* doc_offsets, int64_t n_docs,
                             const uint8_t* nonoutlying, float* out, int mem, void* stream);
 

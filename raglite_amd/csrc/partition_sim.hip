@@ -7,6 +7,14 @@
 // Batched over documents (doc_batch.h); fp32 like the reference.  Three small HBM-bound kernels: row norms ->
 // per-document discourse vector -> per-row-pair similarities (+ the per-document "degenerate" flag) -> choice.
 // sim[last row of a document] = 0 (unused).
+//
+// The one-selected-row rule.  A document with exactly ONE `nonoutlying` row has d equal to that row, so that row's X_mod is zero in exact
+// arithmetic: the document is degenerate and keeps its plain similarities.  In fp32 the residual norm lands between 0 and ~2.5e-7 against
+// the threshold eps = 1.19e-7, so the test of :62-65 would be decided by rounding (as it is in the reference), and where it fails the
+// row is re-normalised noise and both of its similarities are arbitrary.  Here the count decides: one selected row -> no discourse
+// vector (ps_discourse_kernel clears has_d), the exact-arithmetic result.  Measured on an MI355X before the rule, 200 documents of three
+// rows with the middle one selected: 25 / 23 / 20 / 9 documents off the plain values at dim 64 / 128 / 256 / 1024
+// (profiles/partition_sim_error.txt).  Documents whose SEVERAL selected rows are all identical sit on the same threshold and are left to it.
 #include "doc_batch.h"
 
 namespace rl {
@@ -27,8 +35,9 @@ __global__ __launch_bounds__(256) void ps_norms_kernel(const float* __restrict__
     }
 }
 
-// d[doc] = normalise(mean over selected rows of x_hat); has_d[doc] = any row selected.  One block per document,
-// thread t owns columns t, t+256, ...: coalesced row reads, fixed row order (deterministic).
+// d[doc] = normalise(mean over selected rows of x_hat); has_d[doc] = two or more rows selected (none: nothing to remove; one: the
+// one-selected-row rule above).  One block per document, thread t owns columns t, t+256, ...: coalesced row reads, fixed row order
+// (deterministic).
 __global__ __launch_bounds__(256) void ps_discourse_kernel(const float* __restrict__ X, const float* __restrict__ inv_norm,
                                                             const int64_t* __restrict__ doc_off, int64_t n, int dim,
                                                             const uint8_t* __restrict__ sel, float* __restrict__ dvec,
@@ -56,7 +65,7 @@ __global__ __launch_bounds__(256) void ps_discourse_kernel(const float* __restri
     __syncthreads();
     const float inv = 1.0f / sqrtf((part[0] + part[1]) + (part[2] + part[3]));
     for (int k = threadIdx.x; k < dim; k += 256) dvec[(int64_t)doc * dim + k] *= inv;
-    if (threadIdx.x == 0) has_d[doc] = (sel != nullptr && cnt > 0) ? 1 : 0;
+    if (threadIdx.x == 0) has_d[doc] = (sel != nullptr && cnt > 1) ? 1 : 0;
 }
 
 // For row i (one wave): plain[i] = x_hat_i . x_hat_{i+1};  mod[i] = the same on the discourse-free, re-normalised
