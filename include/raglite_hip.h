@@ -87,7 +87,8 @@ int rl_synth_fill(float* dst, int64_t start, int64_t count, uint64_t seed, int k
  *   eps         0  -> unguarded divide (:139);  >0 -> divide by max(norm, eps) (:160-163)
  *   out_f32     [S x dim] f32 or NULL;  out_f16 [S x dim] IEEE half bits or NULL
  * Accumulation is fp64 (the reference pools float64 arrays), the cast rounds to nearest even.
- * An empty span produces NaN, as np.mean of zero rows does. */
+ * An empty span produces NaN, as np.mean of zero rows does.  Sums start from +0.0, so a column
+ * whose rows are all -0.0 pools to +0.0 where np.mean gives -0.0: zeros compare equal, not bitwise. */
 int rl_pool_norm(const float* tokens, int64_t n_token_rows, int32_t dim,
                  const int64_t* span_begin, const int64_t* span_end, int64_t n_spans,
                  int32_t normalize, double eps, float* out_f32, uint16_t* out_f16,

@@ -36,7 +36,8 @@ struct VecLoad<1> {
 // VALU work than the sums.  Instead: fp64 -> fp32 rounded TO ODD (v_cvt_f32_f64 rounds to nearest; when that was inexact,
 // of the two floats around x take the one with the odd significand), then v_cvt_f16_f32: with 13 spare significand bits the
 // second rounding of a round-to-odd intermediate equals the direct rounding (Boldo & Melquiond 2008) -- bit-identical for
-// every input (checked against numpy on all fp16 midpoints and their fp64 neighbours), NaN stays NaN.
+// every input (tests/test_gpu_pool_norm.py::test_cast_on_every_fp16_midpoint: all fp16 midpoints and fp64 values either side, against
+// numpy), NaN stays NaN.
 __device__ __forceinline__ uint16_t f64_to_f16_bits(double x) {
     const float f = (float)x;
     const double back = (double)f;  // exact
