@@ -109,7 +109,11 @@ int rl_adapter_apply(const float* A, const float* queries, int32_t n_queries, in
  *   chunk_offsets  [n_chunks + 1] int64 ascending CSR, chunk_offsets[0]==0, [n_chunks]==n_rows
  *                  (always a HOST pointer); NULL -> every row is its own chunk.
  *   metric         rl_metric used by rl_search_rows / rl_search_chunks.
- * Precomputes ||e|| per row (cosine) or ||e||^2 (l2): 4 B/row extra. */
+ * Precomputes ||e|| per row (cosine) or ||e||^2 (l2): 4 B/row extra.
+ * Widths: 1 <= dim <= 4096.  Up to 2048 any dim and any 4-byte aligned device pointer (a dim that is no multiple of 4, or rows that are
+ * not 16-byte aligned, are scanned with scalar loads).  Above 2048 dim must be a multiple of 4 and borrowed device rows 16-byte aligned,
+ * whatever the metric: RL_ERR_UNSUPPORTED otherwise.  Device QUERIES of a search over an index wider than 2048 must be 16-byte aligned
+ * too (the search reports RL_ERR_UNSUPPORTED; host queries are staged aligned). */
 int rl_index_create(rl_index** out, const float* embeddings, int64_t n_rows, int32_t dim,
                     const int64_t* chunk_offsets, int64_t n_chunks, int metric, int mem, void* stream);
 /* fp16-STORED index.  The reference stores its embeddings as float16

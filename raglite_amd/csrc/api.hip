@@ -451,6 +451,10 @@ static int index_create_any(rl_index** out, const void* embeddings, bool f16, in
     if (n_rows >= (int64_t)0x7fffffff - 1) return fail(RL_ERR_UNSUPPORTED, "rl_index_create: more than 2^31-2 rows");
     if (scan_mode(metric) < 0) return fail(RL_ERR_INVALID, "rl_index_create: unknown metric");
     if (dim > 4096) return fail(RL_ERR_UNSUPPORTED, "rl_index_create: dim must be <= 4096");
+    // (scan.hip: beyond 2048 only the 16-byte loads reach -- a lane of the scalar family would keep more than 32 elements per row in registers.
+    // Refused here, for every metric: no index may exist that no search can answer)
+    if (!f16 && dim > 2048 && (dim % 4 != 0 || (mem == RL_MEM_DEVICE && (reinterpret_cast<uintptr_t>(embeddings) & 15))))
+        return fail(RL_ERR_UNSUPPORTED, "rl_index_create: dim above 2048 must be a multiple of 4, device embeddings 16-byte aligned");
     // (the stream kernels' dims; wider -- round 6 -- through the packed scan, the sixteen-query pass and the wide re-scoring kernel)
     if (f16 && !stream16_dim_ok(dim))
         return fail(RL_ERR_UNSUPPORTED, "rl_index_create_f16: dim must be one of 128, 256, 384, 512, 768, 1024, or a multiple of 128 up to 4096");
@@ -899,6 +903,7 @@ int score_rows(rl_index* idx, const float* d_q, int32_t nb, int64_t ld, hipStrea
     };
     const int mode = scan_mode(idx->metric);
     float* sc = idx->scores.as<float>();
+    idx->scores_direct = false;  // (set where the VALU scan answers: its l2 needs no re-scoring, select_from_scores)
     if (nb >= rows_gemm_min(idx) && idx->opt.on(RL_OPT_PLANES_GEMM)) RL_TRY(demand_images(idx, IMG_PLANES, s));
     if (nb >= rows_gemm_min(idx) && image_valid(idx)) {
         // the row-score GEMM over the corpus image (maxsim_gemm.hip MODE 1; fp32 corpus: pre-split planes, fp16-stored corpus:
@@ -917,8 +922,10 @@ int score_rows(rl_index* idx, const float* d_q, int32_t nb, int64_t ld, hipStrea
         // near-duplicate's small distance to cancellation (the reference's nearest neighbour IS often a near-duplicate).
         // A WIDE fp16-stored index (dim > 1024, round 6): the packed scan in every metric, up to four queries per pass -- no stream kernel
         // covers it; batches of five and more took the GEMM over its image above (rows_gemm_min).
-        if ((nb <= 4 && mode == SCAN_L2) || idx->dim > 1024)
+        if ((nb <= 4 && mode == SCAN_L2) || idx->dim > 1024) {
+            idx->scores_direct = true;
             return launch_scan_rows16(idx->E16, idx->n_rows, idx->dim, d_q, nb, idx->norm, mode, sc, ld, s);
+        }
         for (int32_t b0 = 0; b0 < nb; b0 += 32) {
             const int32_t nq = std::min<int32_t>(32, nb - b0);
             RL_TRY(launch_maxsim_stream16(idx->E16, idx->n_rows, idx->dim, d_q + (int64_t)b0 * idx->dim, nq,
@@ -951,6 +958,7 @@ int score_rows(rl_index* idx, const float* d_q, int32_t nb, int64_t ld, hipStrea
         }
         if (ok) return transform(sc, mode);
     }
+    idx->scores_direct = true;
     return launch_scan_rows(idx->E, idx->n_rows, idx->dim, d_q, nb, idx->norm, mode, sc, ld, s);
 }
 
@@ -1322,9 +1330,12 @@ int select_from_scores(rl_index* idx, const float* d_qb, int32_t nb, int32_t k, 
         st_pv = launch_topk_pivot(idx->scores.as<float>(), nb, n, ld, k, idx->ws, o_s, o_r, s);
     if (st_pv != RL_OK && st_pv != RL_ERR_UNSUPPORTED) return st_pv;
     if (st_pv == RL_ERR_UNSUPPORTED) RL_TRY(launch_topk(idx->scores.as<float>(), nb, n, ld, k, idx->ws, o_s, o_r, s, nullptr, hist_done));
-    if (idx->metric == RL_L2 && (nb > 4)) {
+    if (idx->metric == RL_L2 && !idx->scores_direct) {
         // The batched paths rank by |e|^2 + |q|^2 - 2 e.q; re-score the k hits of every query with the exact
-        // sum (e - q)^2 and re-sort them (near-duplicates would otherwise report a cancelled distance).
+        // sum (e - q)^2 and re-sort them (near-duplicates would otherwise report a cancelled distance).  Not behind the VALU scan (every
+        // batch size of a width no MFMA kernel takes, a wide fp16-stored index): its scores ARE that sum, and re-scoring them in this
+        // kernel's other order of summation changed their last bits with the batch size and re-sorted equal scores by their earlier rank
+        // instead of by row (tests/test_gpu_scan.py).
         const int64_t items = (int64_t)nb * k;
         RL_TRY(idx->misc.reserve((size_t)items * (sizeof(float) + 2 * sizeof(int32_t))));
         float* re = idx->misc.as<float>();

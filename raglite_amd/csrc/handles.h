@@ -164,6 +164,7 @@ struct rl_index {
     // device flag its guarded full-precision fallback waits on.  Pointers into the scratch above, valid until the next call.
     // rl_rank_cut_*: the staged rank cut of a SHARDED corpus keeps its queries and scores here between the calls
     int32_t rank_B = 0;                   // queries of the running rl_rank_cut_begin (0: none)
+    bool scores_direct = false;           // the scores score_rows left in `scores` came from the VALU scan: l2 summed (e - q)^2 directly (select_from_scores)
     int32_t mb_B = 0, mb_nq = 0, mb_k = 0;  // rl_maxsim_batch_begin in progress: queries, vectors per query, k (0: none)
     uint64_t scratch_epoch = 0, mb_epoch = 0;  // calls that used the scratch so far; the value right after that rl_maxsim_batch_begin
     rl::Pool rank_q;                      // their device copy (the l2 re-scoring of rl_rank_cut_finish needs them)
