@@ -1004,15 +1004,11 @@ int search_rows_fused(rl_index* idx, const float* d_q, int32_t B, int32_t k, flo
     if (ld_s < k) return RL_ERR_UNSUPPORTED;
     // ---- scratch ------------------------------------------------------------------------------------------------------------
     RL_TRY(idx->misc.reserve(score_planes_scratch_floats(B, idx->dim) * sizeof(float)));
-    const size_t n_sample = (size_t)B * ld_s, n_top = (size_t)B * k, n_cand = (size_t)B * cap;
-    RL_TRY(idx->fused.reserve((n_sample + 2 * n_top + 2 * n_cand + (size_t)B + 16) * 4));
-    float* S_s = idx->fused.as<float>();
-    float* top_s = S_s + n_sample;
-    int32_t* top_i = reinterpret_cast<int32_t*>(top_s + n_top);
-    float* c_s = reinterpret_cast<float*>(top_i + n_top);
-    int32_t* c_i = reinterpret_cast<int32_t*>(c_s + n_cand);
-    uint32_t* cnt = reinterpret_cast<uint32_t*>(c_i + n_cand);
-    uint32_t* flag = cnt + B;
+    FusedRows L;
+    RL_TRY(carve(idx->fused, L, B, ld_s, k, cap));
+    float *const S_s = L.S_s, *const top_s = L.top_s, *const c_s = L.c_s;
+    int32_t *const top_i = L.top_i, *const c_i = L.c_i;
+    uint32_t *const cnt = L.cnt, *const flag = L.flag;
     float* qs = idx->misc.as<float>();
     float* sc = idx->scores.as<float>();  // [B x ld], reserved by the caller: only the fallback touches it
     // ---- (1) sample pass + its exact top-k --------------------------------------------------------------------------------------
@@ -1068,25 +1064,15 @@ int search_rows_fused_hi(rl_index* idx, const float* d_q, int32_t B, int32_t k, 
     if (ld_s < k) return RL_ERR_UNSUPPORTED;
     // ---- scratch ------------------------------------------------------------------------------------------------------------
     RL_TRY(idx->misc.reserve(score_planes_scratch_floats(B, idx->dim) * sizeof(float)));
-    const size_t n_sample = (size_t)B * ld_s, n_top = (size_t)B * k, n_cand = (size_t)B * cap, n_c2 = (size_t)B * cap2;
-    RL_TRY(idx->fused.reserve((n_sample + 2 * n_top + 2 * n_cand + 2 * n_c2 + 5 * (size_t)B + 16) * 4));
-    float* S_s = idx->fused.as<float>();
-    float* top_s = S_s + n_sample;
-    int32_t* top_i = reinterpret_cast<int32_t*>(top_s + n_top);
-    float* c_s = reinterpret_cast<float*>(top_i + n_top);
-    int32_t* c_i = reinterpret_cast<int32_t*>(c_s + n_cand);
-    int32_t* r_i = c_i + n_cand;                                   // [B x cap2] rows to re-score
-    float* r_s = reinterpret_cast<float*>(r_i + n_c2);             // [B x cap2] their exact similarities
-    float* thr = r_s + n_c2;                                       // [B]
-    float* window = thr + B;                                       // [B]
-    float* thr1 = window + B;                                      // [B] the first round's thresholds (two-round candidate pass)
-    uint32_t* cnt = reinterpret_cast<uint32_t*>(thr1 + B);         // [B]
-    uint32_t* cnt2 = cnt + B;                                      // [B]
-    uint32_t* flag = cnt2 + B;
+    FusedHiRows L;
+    RL_TRY(carve(idx->fused, L, B, ld_s, k, cap, cap2));
+    float *const S_s = L.S_s, *const top_s = L.top_s, *const c_s = L.c_s, *const r_s = L.r_s, *const thr = L.thr, *const window = L.window, *const thr1 = L.thr1;
+    int32_t *const top_i = L.top_i, *const c_i = L.c_i, *const r_i = L.r_i;
+    uint32_t *const cnt = L.cnt, *const cnt2 = L.cnt2, *const flag = L.flag;
     float* qs = idx->misc.as<float>();
-    const int32_t groups = (B + 31) / 32;
-    const float* q_unscale = qs + (size_t)groups * 32 * idx->dim;  // (the layout of launch_score_planes_queries)
-    const float* q_sumsq = q_unscale + B + groups;
+    ScoreQueries Q;  // (what launch_score_planes_queries leaves in qs)
+    Q.lay(Carver(qs), B, idx->dim);
+    const float *const q_unscale = Q.unscale, *const q_sumsq = Q.q_sumsq;
     float* sc = idx->scores.as<float>();  // [B x ld], reserved by the caller: only the fallback touches it
     const void* hi = idx->hi_image.buf.p;
     const float sscale = idx->split_scale;
@@ -1118,8 +1104,8 @@ int search_rows_fused_hi(rl_index* idx, const float* d_q, int32_t B, int32_t k, 
     int st_pp = RL_ERR_UNSUPPORTED;
     int64_t round1_tiles = 0;
     bool row_test = false;
+    int32_t log_cap = 0;
     if (idx->opt.on(RL_OPT_FUSED_PP) && idx->dim % 32 == 0 && idx->dim >= 256) {
-        int32_t log_cap = 0;
         const size_t work_bytes = pp_rows_scratch_bytes(n, B, idx->n_cu, (int32_t)std::min<int64_t>((int64_t)k * stride, cap), &log_cap);
         RL_TRY(idx->pp_work.reserve(work_bytes));
         const int64_t Tr = (n + 127) / 128;
@@ -1151,9 +1137,7 @@ int search_rows_fused_hi(rl_index* idx, const float* d_q, int32_t B, int32_t k, 
         auto& r = idx->replay;
         r.valid = true; r.pp = st_pp == RL_OK; r.B = B; r.mode = mode; r.qs = qs; r.ca = ca; r.cnt = cnt; r.thr1 = thr1; r.round1_tiles = round1_tiles; r.row_test = row_test;
         r.pools[0] = idx->misc.p; r.pools[1] = idx->fused.p; r.pools[2] = idx->pp_work.p;
-        int32_t lc = 0;
-        (void)pp_rows_scratch_bytes(n, B, idx->n_cu, (int32_t)std::min<int64_t>((int64_t)k * stride, cap), &lc);
-        r.log_cap = lc;
+        r.log_cap = log_cap;
     }
     // ---- (3) the rows within the band of each list's k-th entry; (4) their exact similarities, ranked -----------------------------
     if (idx->opt.on(RL_OPT_LIST_SELECT)) RL_TRY(launch_list_select(c_s, c_i, B, cap, k, cnt, window, cap2, r_i, cnt2, flag, s));
@@ -1212,23 +1196,15 @@ int search_rows_hi(rl_index* idx, const float* d_q, int32_t nb, int32_t k, float
     const int64_t nc = (int64_t)nb * cap, ldx = nc;
     // ---- scratch: approximate top-k scores (+ unused ids), thresholds, counters + flag, candidate rows, their norms, the
     // gathered rows, the exact score block and its diagonal -------------------------------------------------------------------------
-    const size_t words = (size_t)nb * k * 2 + 32 + 32 + (size_t)nc * 2 + 4 + (size_t)nc * dim + (size_t)nb * ldx + (size_t)nc + 2 + 2 * pivot_scratch_words(nb);
-    RL_TRY(idx->hibuf.reserve(words * 4));
-    float* ts = idx->hibuf.as<float>();                        // [nb x k]
-    int32_t* ti = reinterpret_cast<int32_t*>(ts + (size_t)nb * k);
-    float* thr = reinterpret_cast<float*>(ti + (size_t)nb * k);  // [nb] (16 words)
-    float* mb = thr + 16;                                        // [nb] (16 words) the error bound of each query
-    uint32_t* cnt = reinterpret_cast<uint32_t*>(mb + 16);        // [nb] counters, then the flag at cnt[16]
-    uint32_t* flag = cnt + 16;
-    int32_t* ci = reinterpret_cast<int32_t*>(cnt + 32);        // [nb x cap]
-    float* gn = reinterpret_cast<float*>(ci + nc);             // [nb x cap]
-    // (16-byte aligned whatever the parity of nb * k: the kernels that score the gathered rows take 16-byte loads -- misaligned, the stream kernel
-    // DECLINED after the approximate pass had run, every search with an odd nb * k paying for both routes, and the scan fell back to scalar loads,
-    // whose other order of summation costs the last bit of parity with the full pass; found by scripts/soak_pivot.py with l2 in, round 6)
-    float* G = reinterpret_cast<float*>((reinterpret_cast<uintptr_t>(gn + nc) + 15) & ~uintptr_t(15));  // [nb * cap x dim]
-    float* xs = G + (size_t)nc * dim;                          // [nb x nb * cap]
-    float* es = xs + (size_t)nb * ldx;                         // [nb x cap]
-    uint64_t* bmax = reinterpret_cast<uint64_t*>((reinterpret_cast<uintptr_t>(es + nc) + 7) & ~uintptr_t(7));  // [nb x 2048] group maxima (pivot route)
+    // (G is 16-byte aligned whatever the parity of nb * k: misaligned, the stream kernel DECLINED after the approximate pass had run, every search
+    // with an odd nb * k paying for both routes, and the scan's scalar loads cost the last bit of parity with the full pass; found by
+    // scripts/soak_pivot.py with l2 in, round 6 -- now every take is, tests/test_scratch_layout_host.py)
+    HiRows L;
+    RL_TRY(carve(idx->hibuf, L, nb, k, dim, cap, pivot_scratch_words(nb)));
+    float *const ts = L.ts, *const thr = L.thr, *const mb = L.mb, *const gn = L.gn, *const G = L.G, *const xs = L.xs, *const es = L.es;
+    int32_t *const ti = L.ti, *const ci = L.ci;
+    uint32_t *const cnt = L.cnt, *const flag = L.flag;
+    uint64_t* const bmax = L.bmax;
     float* sc = idx->scores.as<float>();
     // ---- (1) approximate pass over the HI plane ---------------------------------------------------------------------------------------------
     int st = wide ? launch_scan_rows16(idx->hiplane.buf.as<uint16_t>(), n, dim, d_q, nb, nullptr, SCAN_RAW_DOT, sc, ld, s)
@@ -1337,10 +1313,10 @@ int select_from_scores(rl_index* idx, const float* d_qb, int32_t nb, int32_t k, 
         // kernel's other order of summation changed their last bits with the batch size and re-sorted equal scores by their earlier rank
         // instead of by row (tests/test_gpu_scan.py).
         const int64_t items = (int64_t)nb * k;
-        RL_TRY(idx->misc.reserve((size_t)items * (sizeof(float) + 2 * sizeof(int32_t))));
-        float* re = idx->misc.as<float>();
-        int32_t* pos = reinterpret_cast<int32_t*>(re + items);
-        int32_t* tmp_rows = pos + items;
+        L2Rescore L;
+        RL_TRY(carve(idx->misc, L, items));
+        float* const re = L.re;
+        int32_t *const pos = L.pos, *const tmp_rows = L.tmp_rows;
         RL_TRY(launch_rescore_l2(idx->E16 ? (const void*)idx->E16 : (const void*)idx->E, idx->E16 != nullptr, idx->dim, d_qb, o_r, o_s, k, items,
                                  re, s));
         RL_HIP(hipMemcpyAsync(tmp_rows, o_r, (size_t)items * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
@@ -1416,9 +1392,10 @@ int search_rows_device(rl_index* idx, const float* d_q, int32_t B, int32_t k, fl
         maps = maps || !plans.back().one_set || !plans.back().one_lim || !plans.back().identity;
     }
     const int64_t rw = (n + 31) / 32, cw = (idx->n_chunks + 31) / 32;
-    if (most || maps) RL_TRY(idx->maskbuf.reserve(((size_t)most * rw + most + 2 * (size_t)batch) * sizeof(uint32_t)));
-    uint32_t* row_sets = idx->maskbuf.as<uint32_t>();
-    int32_t* d_map = reinterpret_cast<int32_t*>(row_sets + (size_t)most * rw);
+    RowMasks M{};
+    if (most || maps) RL_TRY(carve(idx->maskbuf, M, most, rw, batch));
+    uint32_t* const row_sets = M.row_sets;
+    int32_t* const d_map = M.d_map;
     const std::vector<int32_t>* expanded = nullptr;  // the filters whose row bitsets maskbuf holds
     bool any_masked = false;
     for (int32_t i = 0, b0 = 0; b0 < B; ++i, b0 += batch) {
@@ -1902,48 +1879,32 @@ namespace {
 // The bound-filtered MaxSim batch in two halves, so that a SHARDED corpus can put one exchange between them
 // (rl_maxsim_batch_begin / _finish): (a) approximate passes + the local top-k of the approximate scores, (b) given thr[] / cnt[] = 0:
 // candidate collection, exact re-scoring, ranking, and the guarded full-precision fallback.
-struct HiBatch {
-    float* ts; int32_t* ti; float* thr; uint32_t* cnt; uint32_t* flag; int32_t* ci; float* es;
-    float* m; float* es_top;  // [n] the bound m_b of every query; [n x k] exact scores of the approximate top-k (second threshold)
-    int32_t cap; bool one_product; float m_abs; const float* q_unscale;
-    uint64_t* bmax = nullptr;     // group maxima of the pivot route (one or two queries)
+struct HiBatch : HiBatchScratch {  // (the scratch of the batch: scratch_layout.h)
+    int32_t cap = 2048;  // (the benchmark corpus needs ~300 -- 1 150 with the a-priori bound: score spread sigma ~ 34, window 2 m = 15..34)
+    bool one_product; float m_abs; const float* q_unscale;
     const float* qsum = nullptr;  // [2 n] sum_i |q_i|, sum_i |q_lo,i| of every query where the query image carries them (launch_query_planes)
     bool m_ready = true;          // hb.m holds the bounds (a threshold kernel ran); false: exact_threshold_kernel computes them from qsum
     bool exact_kth;           // second, tighter threshold from the exact scores of the approximate top-k (RL_OPT_EXACT_KTH_THRESHOLD)
     const uint32_t* filter = nullptr;  // chunk bitset of a metadata-filtered call: masked chunks rank -inf in the approximate scores, so they are
                                        // neither in their top-k nor among the candidates (the bound's argument runs over the chunks that remain)
+    // The scratch of a batch of n queries in hibuf (the same n and k give the same layout in every call that works on the batch)
+    size_t lay(Carver c, int32_t n, int32_t k) { return HiBatchScratch::lay(c, n, k, cap, pivot_scratch_words(std::min<int32_t>(n, 2))); }
 };
-// The scratch layout of a bound-filtered MaxSim batch of n queries (the same in every call that works on the batch)
-void hi_batch_layout(rl_index* idx, int32_t n, int32_t k, HiBatch& hb) {
-    hb.cap = 2048;  // (the benchmark corpus needs ~300 -- 1 150 with the a-priori bound: score spread sigma ~ 34, window 2 m = 15..34)
-    hb.ts = idx->hibuf.as<float>();                                        // [n x k] approximate top-k scores
-    hb.ti = reinterpret_cast<int32_t*>(hb.ts + (size_t)n * k);
-    hb.thr = reinterpret_cast<float*>(hb.ti + (size_t)n * k);              // [n]
-    hb.cnt = reinterpret_cast<uint32_t*>(hb.thr + n);                      // [n]
-    hb.flag = hb.cnt + n;                                                  // (16 words)
-    hb.ci = reinterpret_cast<int32_t*>(hb.flag + 16);                      // [n x cap] candidate chunks
-    hb.es = reinterpret_cast<float*>(hb.ci + (size_t)n * hb.cap);          // [n x cap] their exact scores
-    hb.m = hb.es + (size_t)n * hb.cap;                                     // [n]
-    hb.es_top = hb.m + n;                                                  // [n x k]
-    hb.bmax = reinterpret_cast<uint64_t*>((reinterpret_cast<uintptr_t>(hb.es_top + (size_t)n * k) + 7) & ~uintptr_t(7));  // [min(n, 2) x 2048] (few-queries pivot route)
-}
-size_t hi_batch_words(int32_t n, int32_t k) {
-    return (size_t)n * k * 3 + (size_t)n * 3 + 16 + (size_t)n * 2048 * 2 + 2 + 2 * pivot_scratch_words(std::min<int32_t>(n, 2));
-}
 int hi_batch_approx(rl_index* idx, const float* d_q, int32_t nq, int32_t n_queries, int32_t n_gemm, int32_t k, float* sc, int64_t ld, HiBatch& hb,
                     hipStream_t s, bool flag_zeroed = false) {
     // ONE product per multiply -- q_hi.e_hi only, a plain fp16 GEMM -- with the bound widened by what the queries' hi halves drop,
     // (max|e| + max|e_lo|) sum_i |q_lo,i| (measured per query by the threshold kernel).  RL_OPT_HI_PRODUCTS = 2: two products.
     hb.one_product = idx->opt.v[RL_OPT_HI_PRODUCTS] == 1;
     hb.exact_kth = idx->opt.on(RL_OPT_EXACT_KTH_THRESHOLD);
-    RL_TRY(idx->hibuf.reserve(hi_batch_words(n_gemm, k) * 4));
-    hi_batch_layout(idx, n_gemm, k, hb);
+    RL_TRY(carve(idx->hibuf, hb, n_gemm, k));
     const int32_t cap = hb.cap;
     // per pair |approx - exact| <= |q_i| |e_lo,j| (what the HI halves drop, measured: max_lo_norm) + 2^-12 |q_i| |e_j| (the
     // query's own 2^-22 split and twice the worst case of a 1024-term fp32 sum, 6e-5)
     hb.m_abs = idx->norm_stats.max_lo_norm + sum_eps(idx->dim) * idx->norm_stats.max_row_norm;
-    hb.q_unscale = reinterpret_cast<const float*>(idx->qplanes.as<char>() + (size_t)n_queries * idx->dim * 128);  // launch_query_planes' meta
-    hb.qsum = hb.q_unscale + 2 * (size_t)n_queries;                                                                 // ... and its sums
+    QueryPlanes qp;  // (what launch_query_planes left in qplanes: its meta and its sums)
+    qp.lay(Carver(idx->qplanes.p), n_queries, idx->dim);
+    hb.q_unscale = qp.meta;
+    hb.qsum = qp.qsum;
     if (!flag_zeroed) RL_HIP(hipMemsetAsync(hb.flag, 0, 16 * sizeof(uint32_t), s));  // (else: the query-image kernel did, gemm_prepare)
     // (the candidate lists' unused slots -- -1 = "no chunk" -- are filled where the lists are started: hi_batch_rescore)
     (void)cap;
@@ -2086,8 +2047,7 @@ int maxsim_few_hi_plane(rl_index* idx, const float* d_q, int32_t nq, int32_t n, 
     HiBatch hb;
     hb.one_product = false;  // q_hi . e_hi + q_lo . e_hi: nothing of the query is dropped
     hb.exact_kth = idx->opt.on(RL_OPT_EXACT_KTH_THRESHOLD);
-    RL_TRY(idx->hibuf.reserve(hi_batch_words(n, k) * 4));
-    hi_batch_layout(idx, n, k, hb);
+    RL_TRY(carve(idx->hibuf, hb, n, k));
     hb.m_abs = idx->norm_stats.max_lo_norm + sum_eps(idx->dim) * idx->norm_stats.max_row_norm;
     hb.q_unscale = nullptr;
     hb.filter = d_filter;
@@ -2146,9 +2106,8 @@ int maxsim_topk_batch_device(rl_index* idx, const float* d_q, bool q16, int32_t 
         // kernel can zero it on its way -- one memset launch less per batch)
         uint32_t* flag_words = nullptr;
         if (n_gemm > 0 && k <= 512) {
-            RL_TRY(idx->hibuf.reserve(hi_batch_words(n_gemm, k) * 4));
             HiBatch pre;
-            hi_batch_layout(idx, n_gemm, k, pre);
+            RL_TRY(carve(idx->hibuf, pre, n_gemm, k));
             flag_words = pre.flag;
         }
         const int st = gemm_prepare(idx, d_q, nq, (int64_t)q_elems, n_queries, s, k > 512, flag_words);
@@ -2347,7 +2306,7 @@ int rl_maxsim_batch_finish(rl_index* idx, const float* query_vecs, const float* 
     const int64_t ld = std::max<int64_t>((idx->n_chunks + 3) & ~int64_t(3), 4);
     float* sc = idx->scores.as<float>();
     HiBatch hb;  // the layout of rl_maxsim_batch_begin (same sizes: nothing is reallocated, the approximate scores are still in `sc`)
-    hi_batch_layout(idx, n_queries, k, hb);
+    hb.lay(Carver(idx->hibuf.p), n_queries, k);
     hb.one_product = idx->opt.v[RL_OPT_HI_PRODUCTS] == 1;
     hb.exact_kth = false;  // (the shards' ONE threshold comes from the exchange of their approximate lists)
     hb.m_abs = 0.f;
@@ -2395,12 +2354,13 @@ int rl_maxsim_approx_scores(rl_index* idx, const float* query_vecs, int32_t n_qu
     }
     if (d_b) {  // the bound of the one-product pass, by the kernel the pipeline computes its thresholds with (k = 1 over a dummy top list)
         const float m_abs = idx->norm_stats.max_lo_norm + sum_eps(idx->dim) * idx->norm_stats.max_row_norm;
-        const float* q_unscale = reinterpret_cast<const float*>(idx->qplanes.as<char>() + (size_t)n_queries * idx->dim * 128);
-        RL_TRY(idx->hibuf.reserve((size_t)n_queries * 4 * sizeof(float) + 64));
-        float* top = idx->hibuf.as<float>();                                     // [n] "k-th best" = 0
-        float* thr = top + n_queries;                                            // [n] 0 - 2 m
-        uint32_t* cnt = reinterpret_cast<uint32_t*>(thr + n_queries);            // [n]
-        uint32_t* flag = cnt + n_queries;
+        QueryPlanes qp;
+        qp.lay(Carver(idx->qplanes.p), n_queries, idx->dim);
+        const float* q_unscale = qp.meta;
+        ApproxBound L;
+        RL_TRY(carve(idx->hibuf, L, n_queries));
+        float *const top = L.top, *const thr = L.thr;
+        uint32_t *const cnt = L.cnt, *const flag = L.flag;
         RL_HIP(hipMemsetAsync(top, 0, (size_t)n_queries * sizeof(float), s));
         RL_HIP(hipMemsetAsync(flag, 0, 16 * sizeof(uint32_t), s));
         RL_TRY(launch_maxsim_threshold(top, n_queries, 1, d_q, nq, idx->dim, (int64_t)q_elems, 1.0f, m_abs, thr, cnt, flag, s, q_unscale,

@@ -151,10 +151,10 @@ int hybrid_search_device(rl_index* idx, rl_keyword_index* kw, const HybridCall& 
     const size_t n_list = (size_t)B * n_each;
     // index-owned scratch: lists [R x B x n_each] int32 (what the fusion reads), the two searches' scores [R x B x n_each] f32 and
     // counts [R x B] int32 (written, not read)
-    RL_TRY(idx->hybrid.reserve((size_t)R * (2 * n_list + B) * 4));
-    int32_t* lists = idx->hybrid.as<int32_t>();
-    float* list_scores = reinterpret_cast<float*>(lists + (size_t)R * n_list);
-    int32_t* list_counts = reinterpret_cast<int32_t*>(list_scores + (size_t)R * n_list);
+    HybridLists L;
+    RL_TRY(carve(idx->hybrid, L, R, B, n_each));
+    int32_t *const lists = L.lists, *const list_counts = L.counts;
+    float* const list_scores = L.scores;
     RL_TRY(search_chunks_device(idx, c.d_q, B, num_hits, n_each, c.f, list_scores, lists, list_counts, s));
     if (kw) {
         QueryMask mask;
@@ -276,20 +276,15 @@ int search_rerank_begin(rl_index* idx, rl_keyword_index* kw, const float* querie
 int search_rerank_device(rl_index* idx, rl_keyword_index* kw, const RerankCall& rc, int32_t B, int32_t num_hits, int32_t n_each,
                          const double* weights, int32_t rrf_k, int32_t n_cand, int32_t nq, int32_t k, float* d_s, int32_t* d_c, int32_t* d_n,
                          hipStream_t s) {
-    const size_t n_list = (size_t)B * n_cand, n_out = (size_t)B * k;
     // index-owned scratch: the fused scores [B x n_cand] f64 (written, not read), the fused candidates [B x n_cand] int32, their
     // MaxSim scores [B x n_cand] f32, the fusion's counts [B] and the positions of the first k [B x k] int32 (written, not read);
     // without d_s the scores of the first k [B x k] f32 (written, not read)
-    RL_TRY(idx->rerank.reserve(n_list * 16 + (size_t)B * 4 + n_out * 4 + (d_s ? 0 : n_out * 4)));
-    double* fused_scores = idx->rerank.as<double>();
-    int32_t* fused = reinterpret_cast<int32_t*>(fused_scores + n_list);
-    float* maxsim = reinterpret_cast<float*>(fused + n_list);
-    int32_t* fused_counts = reinterpret_cast<int32_t*>(maxsim + n_list);
-    int32_t* pos = fused_counts + B;
-    if (!d_s) d_s = reinterpret_cast<float*>(pos + n_out);
-    RL_TRY(hybrid_search_device(idx, kw, rc.c, B, num_hits, n_each, weights, rrf_k, n_cand, fused_scores, fused, fused_counts, s));
-    RL_TRY(maxsim_rerank_device(idx, rc.d_v, B, nq, fused, n_cand, maxsim, s));
-    return launch_rerank_order(maxsim, fused, B, n_cand, k, d_s, d_c, pos, d_n, s);
+    RerankScratch L;
+    RL_TRY(carve(idx->rerank, L, B, n_cand, k, !d_s));
+    if (!d_s) d_s = L.own_scores;
+    RL_TRY(hybrid_search_device(idx, kw, rc.c, B, num_hits, n_each, weights, rrf_k, n_cand, L.fused_scores, L.fused, L.fused_counts, s));
+    RL_TRY(maxsim_rerank_device(idx, rc.d_v, B, nq, L.fused, n_cand, L.maxsim, s));
+    return launch_rerank_order(L.maxsim, L.fused, B, n_cand, k, d_s, d_c, L.pos, d_n, s);
 }
 
 // rl_chunk_spans' limits

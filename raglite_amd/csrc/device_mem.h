@@ -2,6 +2,7 @@
 #pragma once
 #include <utility>
 
+#include "scratch_layout.h"
 #include "staging.h"
 
 namespace rl {
@@ -47,6 +48,14 @@ template <class T>
 struct DevArray : Pool {
     operator T*() const { return as<T>(); }
 };
+
+// Size, reserve, lay out (scratch_layout.h): the layout's sizing walk says what to reserve, the same walk over the block fills its pointers.
+template <class L, class... A>
+int carve(Pool& pool, L& layout, A... sizes) {
+    RL_TRY(pool.reserve(layout.lay(Carver(), sizes...)));
+    layout.lay(Carver(pool.p), sizes...);
+    return RL_OK;
+}
 
 // Scratch that grows by a quarter more than asked for, so that the next few inserts fit (Pool::reserve keeps a block that is large enough).
 inline int reserve_amortised(Pool& pool, size_t bytes, const char* who) {

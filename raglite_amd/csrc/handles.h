@@ -1,5 +1,6 @@
 // What the api*.hip files share: the two handle types that more than one of them reads, what those are made of, and
 // the prototypes of the functions that cross a file boundary.  Every other handle type is private to the file of its entry points.
+// Through device_mem.h also: memory ownership (Pool, DevArray) and how the routes cut a scratch pool into sub-buffers (scratch_layout.h).
 #pragma once
 #include <limits>
 #include <memory>

@@ -36,6 +36,7 @@
 #include <cstdlib>
 
 #include "common.h"
+#include "scratch_layout.h"
 
 namespace rl {
 
@@ -300,17 +301,17 @@ __global__ __launch_bounds__(1024) void query_planes_kernel(const float* __restr
     }
 }
 
-size_t query_planes_bytes(int32_t dim, int32_t n_queries) { return (size_t)n_queries * ((size_t)dim * 128 + 16) + 64; }
+size_t query_planes_bytes(int32_t dim, int32_t n_queries) { return QueryPlanes().lay(Carver(), n_queries, dim); }
 
 int launch_query_planes(const float* Q, int32_t dim, int32_t nq, int64_t q_stride, int32_t n_queries, void* buf, hipStream_t s, uint32_t* zero_words,
                         int n_zero) {
     if (n_zero < 0 || n_zero > 1024 || (n_zero > 0 && !zero_words)) return RL_ERR_INVALID;
     if (nq < 1 || nq > 32 || n_queries < 1 || dim % 32 || dim < 32) return RL_ERR_UNSUPPORTED;
     if ((reinterpret_cast<uintptr_t>(Q) & 15) || (q_stride & 3)) return RL_ERR_UNSUPPORTED;
-    uint4* frag = static_cast<uint4*>(buf);
-    float* meta = reinterpret_cast<float*>(static_cast<char*>(buf) + (size_t)n_queries * dim * 128);
-    float* qsum = meta + 2 * (size_t)n_queries;  // (query_planes_qsum)
-    hipLaunchKernelGGL(query_planes_kernel, dim3((unsigned)n_queries), dim3(1024), 0, s, Q, (int)nq, (int)dim, q_stride, frag, meta, qsum, zero_words, n_zero);
+    QueryPlanes L;
+    L.lay(Carver(buf), n_queries, dim);
+    hipLaunchKernelGGL(query_planes_kernel, dim3((unsigned)n_queries), dim3(1024), 0, s, Q, (int)nq, (int)dim, q_stride, reinterpret_cast<uint4*>(L.frag),
+                       L.meta, L.qsum, zero_words, n_zero);
     RL_HIP(hipGetLastError());
     return RL_OK;
 }
@@ -974,7 +975,9 @@ int launch_maxsim_gemm(const void* planes, int64_t n_rows, int32_t dim, const vo
     if (dim % 32 || dim < 32 || !(split_scale > 0.f) || !planes || !ends_bits) return RL_ERR_UNSUPPORTED;
     const int32_t nslab = dim / 32;
     const char* qfrag = static_cast<const char*>(qbuf) + (size_t)first * nslab * 4096;
-    const float* qmeta = reinterpret_cast<const float*>(static_cast<const char*>(qbuf) + (size_t)n_queries * dim * 128) + 2 * (size_t)first;
+    QueryPlanes L;  // (const in, const out: the launch only reads the image)
+    L.lay(Carver(const_cast<void*>(qbuf)), n_queries, dim);
+    const float* qmeta = L.meta + 2 * (size_t)first;
     const int64_t tiles = (n_rows + MG_TM - 1) / MG_TM;
     const dim3 grid((unsigned)std::max<int64_t>(1, std::min<int64_t>(n_cu > 0 ? n_cu : 256, tiles)), (unsigned)((n_q + MG_WAVES - 1) / MG_WAVES)), blk(512);
     static const int dbg_env = exp_env("RAGLITE_GEMM_DBG") ? std::atoi(exp_env("RAGLITE_GEMM_DBG")) : 0;  // timing experiments only
@@ -1088,11 +1091,8 @@ __global__ __launch_bounds__(1024) void query_rows_planes_kernel(const float* __
     if (threadIdx.x == 0) anylo[grp] = any_lo_sh ? 1.f : 0.f;
 }
 
-// floats of scratch for `nb` queries: fragments (dim * 32 per group of 32), unscale[nb], anylo[groups], q_sumsq[nb]
-size_t score_planes_scratch_floats(int32_t nb, int32_t dim) {
-    const size_t groups = ((size_t)nb + 31) / 32;
-    return groups * 32 * (size_t)dim + 2 * (size_t)nb + groups + 64;
-}
+// floats of scratch for `nb` queries: the sizing walk of ScoreQueries (scratch_layout.h)
+size_t score_planes_scratch_floats(int32_t nb, int32_t dim) { return ScoreQueries().lay(Carver(), nb, dim) / sizeof(float); }
 
 int launch_query_sumsq(const float* Q, int32_t nb, int32_t dim, float* out, hipStream_t s);  // score_gemm.hip
 
@@ -1102,10 +1102,9 @@ int launch_score_planes_queries(const float* Q, int32_t nb, int32_t dim, float* 
     if (nb < 1 || dim % 32 || dim < 32) return RL_ERR_UNSUPPORTED;
     if ((reinterpret_cast<uintptr_t>(Q) & 15) || (reinterpret_cast<uintptr_t>(scratch) & 15)) return RL_ERR_UNSUPPORTED;
     const int32_t groups = (nb + 31) / 32;
-    float* frag = scratch;
-    float* unscale = frag + (size_t)groups * 32 * dim;
-    float* anylo = unscale + nb;
-    float* qss = anylo + groups;
+    ScoreQueries L;
+    L.lay(Carver(scratch), nb, dim);
+    float *const frag = L.frag, *const unscale = L.unscale, *const anylo = L.anylo, *const qss = L.q_sumsq;
     hipLaunchKernelGGL(query_rows_planes_kernel, dim3((unsigned)groups), dim3(1024), 0, s, Q, (int)nb, (int)dim, reinterpret_cast<uint4*>(frag), unscale,
                        anylo, zero_word);
     RL_HIP(hipGetLastError());
@@ -1122,10 +1121,9 @@ int launch_score_planes_pass(const void* planes, int64_t n_rows, int32_t dim, in
     if (nb < 1 || n_rows < 1 || dim % 32 || dim < 32 || !(split_scale > 0.f) || !planes || tile_stride < 1) return RL_ERR_UNSUPPORTED;
     if ((mode == SCAN_COSINE && !row_norm) || (mode == SCAN_L2 && !row_sumsq)) return RL_ERR_INVALID;
     const int32_t nslab = dim / 32, groups = (nb + 31) / 32;
-    float* frag = scratch;
-    float* unscale = frag + (size_t)groups * 32 * dim;
-    float* anylo = unscale + nb;
-    float* qss = anylo + groups;
+    ScoreQueries L;  // (as launch_score_planes_queries left it)
+    L.lay(Carver(scratch), nb, dim);
+    float *const frag = L.frag, *const unscale = L.unscale, *const anylo = L.anylo, *const qss = L.q_sumsq;
     RowScoreArgs rs{};
     rs.S = scores; rs.ld = ld; rs.row_norm = mode == SCAN_COSINE ? row_norm : row_sumsq; rs.q_sumsq = qss; rs.q_unscale = unscale;
     rs.q_anylo = anylo; rs.B = nb; rs.QT = (groups + MG_WAVES - 1) / MG_WAVES; rs.metric = mode; rs.tile_stride = tile_stride;

@@ -52,6 +52,7 @@
 
 #include "common.h"
 #include "pp_schedule.h"
+#include "scratch_layout.h"
 
 namespace rl {
 
@@ -805,7 +806,9 @@ int launch_maxsim_pp(const void* image, int64_t n_rows, int32_t dim, const void*
     if (dim % 32 || dim < 256 || !(split_scale > 0.f) || !image || !ends_bits) return RL_ERR_UNSUPPORTED;
     const int32_t nslab = dim / 32;
     const char* qfrag = static_cast<const char*>(qbuf) + (size_t)first * nslab * 4096;
-    const float* qmeta = reinterpret_cast<const float*>(static_cast<const char*>(qbuf) + (size_t)n_queries * dim * 128) + 2 * (size_t)first;
+    QueryPlanes L;  // (launch_query_planes' image; the launch only reads it)
+    L.lay(Carver(const_cast<void*>(qbuf)), n_queries, dim);
+    const float* qmeta = L.meta + 2 * (size_t)first;
     const int64_t tiles = (n_rows + PP_RT - 1) / PP_RT;
     const int64_t gx = std::max<int64_t>(1, std::min<int64_t>(n_cu > 0 ? n_cu : 256, tiles)), passes = (n_q + PP_QPP - 1) / PP_QPP;
     // schedule 1: a 1-D grid in the co-scheduled order (xcd_passes = 8: the passes over one row range side by side on one XCD) or the
@@ -862,10 +865,9 @@ int launch_pp_rows_sample(const void* image, int64_t n_rows, int32_t dim, int32_
     if (mode == SCAN_COSINE && !row_norm) return RL_ERR_INVALID;
     if ((ld_s & 255) || (reinterpret_cast<uintptr_t>(S) & 15)) return RL_ERR_UNSUPPORTED;
     const int32_t nslab = dim / 32, groups = (nb + 31) / 32;
-    float* frag = scratch;  // the layout of launch_score_planes_queries
-    float* unscale = frag + (size_t)groups * 32 * dim;
-    float* anylo = unscale + nb;
-    float* qss = anylo + groups;
+    ScoreQueries L;  // (as launch_score_planes_queries left it)
+    L.lay(Carver(scratch), nb, dim);
+    float *const frag = L.frag, *const unscale = L.unscale, *const qss = L.q_sumsq;
     const int64_t grid_cu = n_cu > 0 ? n_cu : 256;
     const int64_t T256 = (n_rows + 255) / 256, Tv = (T256 + stride - 1) / stride;
     if (Tv * 256 != ld_s) return RL_ERR_INVALID;
@@ -905,10 +907,9 @@ int launch_pp_rows_pass(const void* image, int64_t n_rows, int32_t dim, int32_t 
     if (mode == SCAN_COSINE && !row_norm) return RL_ERR_INVALID;
     if (cand->tau_stride != 1) return RL_ERR_UNSUPPORTED;
     const int32_t nslab = dim / 32, groups = (nb + 31) / 32;
-    float* frag = scratch;  // the layout of launch_score_planes_queries
-    float* unscale = frag + (size_t)groups * 32 * dim;
-    float* anylo = unscale + nb;
-    float* qss = anylo + groups;
+    ScoreQueries L;  // (as launch_score_planes_queries left it)
+    L.lay(Carver(scratch), nb, dim);
+    float *const frag = L.frag, *const unscale = L.unscale, *const qss = L.q_sumsq;
     const int64_t grid_cu = n_cu > 0 ? n_cu : 256;
     const int64_t Tr_all = (n_rows + PP_RT - 1) / PP_RT;
     if (tile_count < 0) tile_count = Tr_all - tile_begin;

@@ -46,6 +46,27 @@ def test_fused_equals_dense_path_bitwise(metric, n, dim, B, k):
     idx.close()
 
 
+@pytest.mark.parametrize("B,k", [(97, 7), (96, 8)])
+def test_fused_odd_and_even_scratch_layouts_equal_the_dense_path_bitwise(B, k):
+    """The route's scratch (csrc/scratch_layout.h: FusedRows) at an odd B and B k -- every sub-buffer behind the sample scores then starts on
+    a boundary of its own, and the flag word sits behind 97 counters -- and at its even twin.  8192 rows of 256: the smallest corpus the
+    route takes here (32 row tiles: sample stride 4)."""
+    n, dim = 8192, 256
+    E = oracle.synth_matrix(7900, n, dim)
+    Q = oracle.synth_matrix(7901, B, dim)
+    idx = raglite_amd.DeviceIndex(E, metric="cosine")
+    S, R = idx.search_rows(Q, k)
+    st = idx.filter_stats()
+    assert st["kind"] == "rows_fused" and not st["fallback"], st
+    with idx.options(fused_topk=0):
+        S0, R0 = idx.search_rows(Q, k)
+        assert idx.filter_stats()["kind"] != "rows_fused"
+    assert np.array_equal(R, R0) and np.array_equal(S.view(np.uint32), S0.view(np.uint32))
+    for b in (0, B - 1):
+        assert_topk_close(S[b], R[b], oracle.similarity(E, Q[b], "cosine"), k, TOL)
+    idx.close()
+
+
 @pytest.mark.parametrize("metric", ["cosine", "dot"])
 def test_fused_integer_ties_bit_exact(metric):
     """Small-integer data: thousands of rows share every score, the bound itself is a tie value -- ties resolve to the lowest
@@ -174,6 +195,35 @@ def test_fused_hi_float_data(metric):
         assert_topk_close(S[b], R[b], oracle.similarity(E, Q[b], metric), k, tol)
         assert len(set(R[b].tolist()) ^ set(R0[b].tolist())) <= 2  # (scores within an ulp of the k-th may swap at the boundary)
         np.testing.assert_allclose(S[b], S0[b], rtol=0, atol=2 * tol)
+    idx.close()
+
+
+@pytest.mark.parametrize("B,k", [(97, 7), (96, 8)])
+def test_fused_hi_odd_and_even_scratch_layouts(B, k):
+    """The same pair over the HI image (csrc/scratch_layout.h: FusedHiRows).  262 144 rows of 256: the smallest corpus of that width that
+    keeps a HI image (64 Mi elements).  Compared like test_fused_hi_float_data, against the dense path."""
+    import torch
+
+    raglite_amd.set_device(0)
+    n, dim = 262_144, 256
+    E = torch.empty((n, dim), dtype=torch.float32, device="cuda")
+    raglite_amd.synth_fill(E, seed=7950)
+    Q = torch.empty((B, dim), dtype=torch.float32, device="cuda")
+    raglite_amd.synth_fill(Q, seed=7951)
+    idx = raglite_amd.DeviceIndex(E, metric="cosine")
+    S, R = idx.search_rows(Q, k)
+    st = idx.filter_stats()
+    assert st["kind"] == "rows_fused_hi" and not st["fallback"], st
+    with idx.options(fused_topk=0):
+        S0, R0 = idx.search_rows(Q, k)
+        assert not idx.filter_stats()["kind"].startswith("rows_fused")
+    S, R, S0, R0 = (t.cpu().numpy() for t in (S, R, S0, R0))
+    Eh, Qh = E.cpu().numpy(), Q.cpu().numpy()
+    for b in range(B):
+        assert len(set(R[b].tolist()) ^ set(R0[b].tolist())) <= 2  # (scores within an ulp of the k-th may swap at the boundary)
+        np.testing.assert_allclose(S[b], S0[b], rtol=0, atol=2 * TOL)
+    for b in (0, B - 1):
+        assert_topk_close(S[b], R[b], oracle.similarity(Eh, Qh[b], "cosine"), k, TOL)
     idx.close()
 
 

@@ -40,6 +40,29 @@ def test_hi_maxsim_integer_bit_exact(nq, n_queries, k):
     idx.close()
 
 
+@pytest.mark.parametrize("n_queries", [3, 5])
+def test_odd_batch_scratch_layout_integer_bit_exact(n_queries):
+    """The batch's scratch (csrc/scratch_layout.h: HiBatchScratch) at odd sizes throughout -- 3 and 5 queries of 3 vectors, k = 5: every list
+    of n k or n words ends off a 16-byte boundary, and the 16 flag words sit behind 3 or 5 counters.  A few thousand chunks of 256-wide rows
+    (262 144 of them: the smallest index of that width that keeps a HI image); the same bits as the full-precision passes."""
+    n, dim, nq, k = 262_144, 256, 3, 5
+    rng = np.random.default_rng(n_queries)
+    off = ragged_offsets(rng, n, 33, 95)
+    E = oracle.synth_matrix(10_150, n, dim, "small_int")
+    Qb = np.stack([oracle.synth_matrix(10_160 + i, nq, dim, "small_int") for i in range(n_queries)])
+    idx = raglite_amd.DeviceIndex(E, off, metric="dot")
+    bs, bc = idx.maxsim_topk_batch(Qb, k)
+    assert idx.filter_stats()["kind"] == "maxsim_batch_hi", idx.filter_stats()
+    with idx.options(hi_maxsim=0):
+        fs, fc = idx.maxsim_topk_batch(Qb, k)
+        assert idx.filter_stats()["kind"] != "maxsim_batch_hi"
+    assert np.array_equal(bc, fc) and np.array_equal(bs.view(np.uint32), fs.view(np.uint32))
+    for i in (0, n_queries - 1):
+        ws, wc = oracle.maxsim_topk(E, off, Qb[i], k, np.float32)
+        assert np.array_equal(bc[i], wc) and np.array_equal(bs[i], ws)
+    idx.close()
+
+
 def test_hi_maxsim_float_data_tombstones_and_switch():
     rng = np.random.default_rng(5)
     off = ragged_offsets(rng, N, 1, 15)

@@ -184,6 +184,26 @@ def test_without_keyword_side_and_after_lifecycle(torch_cuda, fake_embedder):
         gi.close()
 
 
+def test_three_queries_of_five_hits_equal_single_query_calls(torch_cuda, fake_embedder):
+    """The scratch of hybrid_search (csrc/scratch_layout.h: HybridLists) at odd sizes -- B = 3, n_each = 5, k = 3: lists of 15 and counts of
+    3 words per search -- with the keyword side (two lists per query) and without."""
+    rng = np.random.default_rng(15)
+    gi = _index(rng, 2000)
+    try:
+        queries = _queries(rng, 3)
+        Q = np.stack([raglite_amd.embed_strings([q], config=fake_embedder)[0, :] for q in queries]).astype(np.float32)
+        terms = [gi.keyword_query_ids(q) for q in queries]
+        for keyword in (gi.keyword, None):
+            s, c, n = gi.index.hybrid_search(Q, 20, 5, 3, keyword=keyword, query_term_ids=terms)
+            assert (n[:2] == 3).all()
+            for b in range(3):
+                s1, c1, n1 = gi.index.hybrid_search(Q[b:b + 1], 20, 5, 3, keyword=keyword, query_term_ids=terms[b:b + 1])
+                assert np.array_equal(c[b], c1[0]) and n[b] == n1[0]
+                assert np.array_equal(s[b].view(np.uint64), s1[0].view(np.uint64))
+    finally:
+        gi.close()
+
+
 def test_device_tensors_equal_host_arrays(torch_cuda, fake_embedder):
     rng = np.random.default_rng(14)
     gi = _index(rng, 2000)

@@ -1132,6 +1132,22 @@ def test_l2_batched_near_duplicates_are_rescored(storage, B):
     idx.close()
 
 
+def test_l2_five_queries_of_seven_hits_are_rescored_behind_the_stream_kernel():
+    """The re-scoring's scratch (csrc/scratch_layout.h: L2Rescore) at an odd size: 5 queries x 7 hits = 35 items per array.  dim 128 and 203
+    rows: the narrowest width at which five queries leave the scan for an MFMA route (the stream kernel; api.hip: score_rows) -- the re-scoring
+    runs only behind those -- over the row count of the scan's own tests."""
+    n, dim, B, k = 203, 128, 5, 7
+    E = (3.0 * oracle.synth_matrix(123, n, dim)).astype(np.float16).astype(np.float32)
+    picks = np.random.default_rng(17).choice(n, B, replace=False)
+    Q = E[picks] + (1e-3 * oracle.synth_matrix(124, B, dim)).astype(np.float32)  # near-duplicates: the ranking formula alone would cancel
+    idx = raglite_amd.DeviceIndex(E, metric="l2")
+    S, R = idx.search_rows(Q, k)
+    for b in range(B):
+        assert R[b, 0] == picks[b]
+        assert_topk_close(S[b], R[b], oracle.similarity(E, Q[b], "l2"), k, TOL)
+    idx.close()
+
+
 @pytest.mark.parametrize("storage", ["f32", "f16"])
 def test_lifecycle_random_operation_sequences(storage):
     """Random interleavings of append / delete / filtered and unfiltered searches against a NumPy mirror of the table

@@ -129,6 +129,19 @@ def test_search_rerank_equals_the_composition(corpus, B, nq):
     assert not set(range(0, 3000, 7)).intersection(c[c >= 0].tolist())  # no tombstoned chunk comes back
 
 
+@pytest.mark.parametrize("keyword", [True, False])
+def test_search_rerank_at_odd_sizes_equals_the_composition(corpus, keyword):
+    """The scratch of search_rerank (csrc/scratch_layout.h: RerankScratch over HybridLists) at odd sizes: B = 3, nq = 3, n_each = 5, k = 3;
+    n_cand = 5 from the vector search alone, 10 with the keyword list."""
+    rng = np.random.default_rng(77)
+    B, nq = 3, 3
+    Q, V = _ints(rng, (B, DIM)), _ints(rng, (B, nq, DIM))
+    terms = [corpus.keyword_query_ids(q) for q in _queries(rng, B)]
+    c, n, _ = _check_pipeline(corpus, Q, V, terms, keyword, 3, n_each=5, num_hits=20)
+    assert (n == 3).all() and c.shape == (B, 3)
+    _check_pipeline(corpus, Q, V, terms, keyword, 3, n_each=5, num_hits=20, device=True)
+
+
 def test_search_rerank_on_an_fp16_stored_index_of_dim_1024(torch_cuda):
     rng = np.random.default_rng(3)
     gi = _index(rng, n=400, dim=1024, storage="f16")

@@ -222,6 +222,19 @@ def test_search_rerank_spans_equal_the_composition(corpus, B, nq):
     assert not dead.intersection(got[2][got[2] >= 0].tolist())  # no tombstoned chunk is a neighbour
 
 
+@pytest.mark.parametrize("keyword", [True, False])
+def test_search_rerank_spans_at_odd_sizes_equal_the_composition(corpus, keyword):
+    """This call takes no MaxSim scores back, so the scores of the first k stay in the index's scratch (csrc/scratch_layout.h: RerankScratch
+    with own_scores) -- at odd sizes: B = 3, nq = 3, n_each = 5, k = 3; n_cand = 5 from the vector search alone, 10 with the keyword list."""
+    rng = np.random.default_rng(78)
+    B, nq = 3, 3
+    Q, V = _ints(rng, (B, DIM)), _ints(rng, (B, nq, DIM))
+    terms = [corpus.keyword_query_ids(q) for q in _queries(rng, B)]
+    got = _check_pipeline(corpus, Q, V, terms, keyword, 3, n_each=5, num_hits=20)
+    assert (got[1] == 3).all()
+    _check_pipeline(corpus, Q, V, terms, keyword, 3, n_each=5, num_hits=20, device=True)
+
+
 def test_search_rerank_spans_on_an_fp16_stored_index_of_dim_1024(torch_cuda):
     rng = np.random.default_rng(3)
     gi = _index(rng, n=400, dim=1024, storage="f16")
