@@ -94,6 +94,33 @@ int rl_pool_norm(const float* tokens, int64_t n_token_rows, int32_t dim,
                  int32_t normalize, double eps, float* out_f32, uint16_t* out_f16,
                  int mem, void* stream);
 
+/* ---- variable-length attention forward (the packed encoder's attention) --------
+ * Non-causal softmax attention over a PACKED batch: the sequences of a call are concatenated along the token axis and every token
+ * attends to the tokens of its own sequence only,
+ *     out[t, h, :] = softmax_j(scale * q[t,h] . k[j,h]) . v[j,h],   seq_offsets[s] <= t, j < seq_offsets[s + 1].
+ *   qkv          [n_tokens x 3 x heads x head_dim] bf16 or fp16: the fused QKV projection, read in place (token row stride
+ *                3 * heads * head_dim elements; q, k, v of head h at element offsets h * head_dim, (heads + h) * head_dim,
+ *                (2 * heads + h) * head_dim); 16-byte aligned
+ *   seq_offsets  int32[n_seqs + 1] on the device: ascending, from 0 to n_tokens; empty sequences are allowed
+ *   max_len      at least every sequence length (a host scalar: it sizes the grid, nothing waits for the device); a sequence longer than
+ *                max_len gets its first max_len rows (rounded up to the query tile) only
+ *   dtype        RL_ATTN_BF16 or RL_ATTN_F16, of qkv and of out
+ *   out          [n_tokens x heads x head_dim], 8-byte aligned
+ * Scores, the online softmax, the row sums and the output accumulate in f32; `scale` multiplies f32 scores; the probabilities are
+ * rounded to `dtype` only as the operand of P.V (in bf16 as two operands, the rounded value and the rounded remainder); the output is rounded to nearest even.  No atomics: the same bits run to run, and a
+ * sequence's bits depend neither on the rest of the pack nor on max_len.  Error against exact arithmetic on the rounded inputs: at most
+ * (2 u + 2^-12) * sum_j w_j |v_j| per element, u = 2^-9 (bf16) or 2^-11 (fp16), w the exact softmax weights (|scaled score| <= 64).
+ * Device offsets are not validated: every token index the kernel forms is clamped into [0, n_tokens), so offsets that break the
+ * contract give wrong numbers but never an access outside qkv or out.
+ * Device pointers only (mem != RL_MEM_DEVICE: RL_ERR_UNSUPPORTED; bf16 has no host array type in the binding); everything is enqueued on
+ * `stream`.  Checked before any HIP call: RL_ERR_INVALID for a null qkv / seq_offsets / out or a misaligned qkv / out with n_tokens > 0,
+ * n_seqs < 0, n_tokens < 0 or >= 2^31, max_len < 0, heads < 1 or > 65535, n_seqs > 65535 (the grid's z axis), a non-finite scale, an
+ * unknown dtype; RL_ERR_UNSUPPORTED for head_dim outside {32, 64}.  n_tokens == 0 returns RL_OK and writes nothing. */
+#define RL_ATTN_BF16 0
+#define RL_ATTN_F16 1
+int rl_attention_varlen(const void* qkv, const int32_t* seq_offsets, int32_t n_seqs, int64_t n_tokens, int32_t max_len,
+                        int32_t heads, int32_t head_dim, int32_t dtype, float scale, void* out, int mem, void* stream);
+
 /* ---- a5: query adapter -----------------------------------------------------------------------
  * Replaces src/raglite/_search.py:62  `(Q @ q).astype(q.dtype)`; out[b] = A @ q[b].
  *   A [dim x dim] f32, queries [B x dim] f32, out_f32 [B x dim] or NULL, out_f16 or NULL. */

@@ -23,6 +23,7 @@ MEM_HOST, MEM_DEVICE = 0, 1
 MEM_FILTERS_DEVICE = 2  # RL_MEM_FILTERS_DEVICE, or-ed into `mem`: the filter table alone is a device pointer
 METRICS = {"cosine": 0, "dot": 1, "l2": 2}
 SYNTH_KINDS = {"uniform": 0, "small_int": 1}
+ATTN_DTYPES = {"bfloat16": 0, "float16": 1}  # RL_ATTN_BF16 / RL_ATTN_F16
 # rl_option (include/raglite_hip.h "options"): route switches of an index; the library reads no environment variable
 OPTIONS = {
     "hi_search": 1, "hi_maxsim": 2, "hi_products": 3, "pp_pass": 4, "fused_topk": 5, "fused_hi": 6, "fused_pp": 7, "fused_topk_cap": 8,
@@ -57,6 +58,7 @@ _SIGNATURES = {
     "rl_synth_fill": [c_void_p, c_i64, c_i64, c_u64, c_int, c_void_p],
     "rl_pool_norm": [c_void_p, c_i64, c_i32, c_void_p, c_void_p, c_i64, c_i32, c_double, c_void_p, c_void_p,
                      c_int, c_void_p],
+    "rl_attention_varlen": [c_void_p, c_void_p, c_i32, c_i64, c_i32, c_i32, c_i32, c_i32, C.c_float, c_void_p, c_int, c_void_p],
     "rl_adapter_apply": [c_void_p, c_void_p, c_i32, c_i32, c_void_p, c_void_p, c_int, c_void_p],
     "rl_index_create": [C.POINTER(c_void_p), c_void_p, c_i64, c_i32, c_void_p, c_i64, c_int, c_int, c_void_p],
     "rl_index_destroy": [c_void_p],

@@ -23,6 +23,7 @@ SOURCES = [
     "synth.hip", "scan.hip", "scan16.hip", "select.hip", "mask.hip", "score_gemm.hip", "hi_filter.hip",  # row and chunk search
     "maxsim_stream.hip", "maxsim_generic.hip", "maxsim_gemm.hip", "maxsim_pp.hip",  # MaxSim
     "pool_norm.hip", "partition_sim.hip", "partition_dp.hip", "chunklet_dp.hip", "sentence_dp.hip",  # ingestion
+    "attention_varlen.hip",  # the packed encoder's attention
     "adapter_fit.hip", "query_targets.hip",  # query adapter
     "keyword.hip", "keyword_build.hip", "keyword_analyze.hip",  # BM25
     "fuse.hip", "rerank.hip", "spans.hip", "metadata.hip",  # fusion, rerank order, spans, metadata filters

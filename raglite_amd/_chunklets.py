@@ -237,15 +237,21 @@ def split_chunklets(sentences: list[str], boundary_cost: Callable[[np.ndarray], 
 
 
 def split_documents_batch(documents: Sequence[Sequence[str]], *, config: Any | None = None,
-                          embedder: Any | None = None) -> list[tuple[list[str], list[Any]]]:
+                          embedder: Any | None = None, embed: str = "loop") -> list[tuple[list[str], list[Any]]]:
     """Sentences -> chunklets -> chunklet embeddings -> chunks for MANY documents (`_insert.py:95-101`): `split_chunklets_batch`,
-    `embed_strings` one document at a time (as `_insert.py:96` does), `split_chunks_batch`.  Returns per document
-    (chunks, chunk_embeddings), ready for `GpuIndex.insert_chunks`."""
+    the chunklet embeddings, `split_chunks_batch`.  embed="loop" (default): `embed_strings` one document at a time (as `_insert.py:96`
+    does); embed="batch": `embed_strings_batch`, which shares encoder forwards and the pooling launch across documents.  Returns per
+    document (chunks, chunk_embeddings), ready for `GpuIndex.insert_chunks`."""
     from raglite_amd._chunking import split_chunks_batch
     from raglite_amd._config import HotPathConfig
-    from raglite_amd._embed import embed_strings
+    from raglite_amd._embed import embed_strings, embed_strings_batch
 
+    if embed not in ("loop", "batch"):
+        raise ValueError('embed must be "loop" or "batch"')
     config = config or HotPathConfig()
     chunklets = split_chunklets_batch(documents, max_size=config.chunk_max_size)
-    embeddings = [embed_strings(c, config=config, embedder=embedder) for c in chunklets]
+    if embed == "batch":
+        embeddings = embed_strings_batch(chunklets, config=config, embedder=embedder)
+    else:
+        embeddings = [embed_strings(c, config=config, embedder=embedder) for c in chunklets]
     return split_chunks_batch(chunklets, embeddings, max_size=config.chunk_max_size)

@@ -25,7 +25,8 @@ from __future__ import annotations
 from dataclasses import dataclass
 from typing import Any, Sequence
 
-from raglite_amd._torch_embedder import EncoderShape, HashTokenizer, _build_encoder, native_state_from_hf
+from raglite_amd._torch_embedder import (BATCHING_MODES, EncoderShape, HashTokenizer, _build_encoder, native_state_from_hf, pack_runs,
+                                         packed_inputs)
 
 
 @dataclass(frozen=True)
@@ -70,9 +71,17 @@ class TorchCrossEncoderRanker:
     """`rank(query=, docs=)` of the `rerankers.BaseRanker` surface the reference calls, on the GPU."""
 
     def __init__(self, shape: CrossEncoderShape | None = None, *, tokenizer: Any | None = None, device: str = "cuda",
-                 dtype: Any | None = None, seed: int = 0, max_length: int | None = None, pairs_per_batch: int = 128) -> None:
+                 dtype: Any | None = None, seed: int = 0, max_length: int | None = None, pairs_per_batch: int = 128,
+                 batching: str = "padded", pack_tokens: int = 16384) -> None:
+        """batching "padded" (default): length-sorted padded batches of `pairs_per_batch` pairs; "packed": the pairs in input order in
+        unpadded packs of at most `pack_tokens` tokens (`Encoder.forward_packed`; `pairs_per_batch` is ignored)."""
         import torch
 
+        if batching not in BATCHING_MODES:
+            raise ValueError('batching must be "padded" or "packed"')
+        if pack_tokens < 1:
+            raise ValueError("pack_tokens must be >= 1")
+        self.batching, self.pack_tokens = batching, int(pack_tokens)
         self.shape = shape or CrossEncoderShape()
         if not self.shape.classifier:
             raise ValueError("a cross-encoder needs shape.classifier = True")
@@ -111,6 +120,14 @@ class TorchCrossEncoderRanker:
 
         pairs = self.encode_pairs(query, docs)
         out = torch.empty(len(pairs), dtype=torch.float32, device=self.device)
+        if self.batching == "packed":
+            for lo, hi in pack_runs([len(p[0]) for p in pairs], self.pack_tokens):
+                rows = [p[0] for p in pairs[lo:hi]]
+                types = [[0] * first + [1] * (len(r) - first) for r, (_, first) in zip(rows, pairs[lo:hi])]
+                ids, off, lens, type_ids = packed_inputs(rows, self.device, types)
+                with torch.inference_mode():
+                    out[lo:hi] = self.encoder.forward_packed(ids, off, lens, type_ids).float()
+            return out
         order = sorted(range(len(pairs)), key=lambda i: len(pairs[i][0]))  # length-sorted batches: little padding
         for lo in range(0, len(order), self.pairs_per_batch):
             sel = order[lo : lo + self.pairs_per_batch]

@@ -7,7 +7,9 @@ Same entry points, argument meaning and return contract as the reference:
     embed_strings_without_late_chunking(strings, *, config=None)   (`_embed.py:168-184`)
     embedding_type(*, config=None)                                 (`_embed.py:187-190`)
 
-all returning a float16 matrix with one row per input string (`tests/test_embed.py:19-26`).
+all returning a float16 matrix with one row per input string (`tests/test_embed.py:19-26`); plus `embed_strings_batch(documents)`,
+which the reference has no counterpart of: many documents per call, their late-chunking segments grouped across documents into
+shared encoder forwards and pooled in one launch, one such matrix per document.
 
 What stays on the host (integer bookkeeping, a few hundred values per document): sentinel-based
 token counting, the 38.2 % / 61.8 % preamble/content segment plan, the largest-remainder split of a
@@ -19,12 +21,13 @@ reference, `_embed.py:64-66,119`) is reached through `embedder_for(config)`.
 
 from __future__ import annotations
 
-from typing import Any, Callable, Literal
+from typing import Any, Callable, Literal, Sequence
 
 import numpy as np
 
 from raglite_amd import _ops
 from raglite_amd._config import HotPathConfig
+from raglite_amd._torch_embedder import pack_runs
 
 SENTINEL = "⊕"  # `_embed.py:70`
 _BATCH = 96  # `_embed.py:173`
@@ -225,3 +228,46 @@ def embed_strings(strings: list[str], *, config: Any | None = None, embedder: An
     if embedding_type(config=config) == "late_chunking":
         return embed_strings_with_late_chunking(strings, config=config, embedder=embedder)
     return embed_strings_without_late_chunking(strings, config=config, embedder=embedder)
+
+
+def embed_strings_batch(documents: Sequence[list[str]], *, config: Any | None = None, embedder: Any | None = None) -> list[np.ndarray]:
+    """`embed_strings` for MANY documents: one float16 matrix per document, each with `embed_strings(document)`'s contract.
+
+    Late chunking: token counts and the segment plan per document, as `plan_document` makes them; then consecutive segments ACROSS
+    documents go to `embedder.embed(list_of_segment_texts)` in groups of at most `embedder.pack_tokens` tokens (`embedder.n_batch` for
+    an embedder without that attribute; a segment over the bound goes alone), so a short document no longer costs an encoder forward of
+    its own; the token rows are apportioned per segment, ONE `rl_pool_norm` pools every document's spans, and the result is sliced per
+    document.  Any llama-like embedder whose `embed(list)` returns a list works; a `TorchTokenEmbedder(batching="packed")` runs each
+    group as one unpadded forward.  The token rows of all documents are resident at once (they are on the device with a GPU embedder):
+    callers bound the documents per call.  Standard embedders: the strings of all documents through
+    `embed_strings_without_late_chunking`, sliced.  An empty document raises ValueError, as `embed_strings` does; no documents: []."""
+    config = config or HotPathConfig()
+    docs = [d if isinstance(d, list) else list(d) for d in documents]
+    if not docs:
+        return []
+    if any(len(d) == 0 for d in docs):
+        raise ValueError("need at least one sentence")
+    bounds = np.concatenate(([0], np.cumsum([len(d) for d in docs])))
+    if embedding_type(config=config) != "late_chunking":
+        flat = embed_strings_without_late_chunking([s for d in docs for s in d], config=config, embedder=embedder)
+        return [flat[bounds[i] : bounds[i + 1]] for i in range(len(docs))]
+    embedder = embedder or embedder_for(config)
+    segments = []  # (text, token counts of its sentences, index of its first content sentence)
+    for sentences in docs:
+        num_tokens = count_sentence_tokens(sentences, embedder)
+        for seg_start, content_start, seg_end in plan_segments(num_tokens, embedder.n_ctx(), embedder.n_batch):
+            segments.append(("".join(sentences[seg_start:seg_end]), num_tokens[seg_start:seg_end], content_start - seg_start))
+    token_blocks, begins, ends = [], [], []
+    base = 0
+    for lo, hi in pack_runs([int(s[1].sum()) for s in segments], int(getattr(embedder, "pack_tokens", embedder.n_batch))):
+        mats = embedder.embed([s[0] for s in segments[lo:hi]])
+        for (_, seg_tokens, first), mat in zip(segments[lo:hi], mats):
+            tokens = _token_matrix(mat)
+            edges = base + np.concatenate(([0], np.cumsum(split_rows(len(tokens), seg_tokens))))
+            begins.append(edges[first:-1])
+            ends.append(edges[first + 1 :])
+            token_blocks.append(tokens)
+            base += len(tokens)
+    pooled = _pool(_stack(token_blocks), np.concatenate(begins).astype(np.int64), np.concatenate(ends).astype(np.int64),
+                   normalize=bool(config.embedder_normalize), eps=0.0)
+    return [pooled[bounds[i] : bounds[i + 1]] for i in range(len(docs))]

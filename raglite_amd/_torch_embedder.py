@@ -9,7 +9,9 @@ surface `_embed.py` touches (`n_ctx()`, `n_batch`, `tokenize`, `detokenize`, `em
 
 makes `embed_strings()` run tokenise -> encoder -> late-chunking pool (`rl_pool_norm`) without the token matrix ever
 leaving HBM.  PyTorch is plumbing here (GEMMs through hipBLASLt, attention through SDPA); the kernels this package
-owns start at the pooling seam.
+owns start at the pooling seam -- and, with `batching="packed"`, include the attention: the strings of a call are concatenated along
+the token axis (`Encoder.forward_packed`, no pad tokens) and attend block-diagonally through `rl_attention_varlen`
+(`_attention.py`).  The default, `"padded"`, is the route described above.
 
 No checkpoint can be fetched in this environment: weights are random-initialised in the architecture's shape unless a
 state dict is supplied (`load_state_dict`).  Tokenizers: `SentencePieceTokenizer(model_file)` loads a SentencePiece model the way
@@ -22,7 +24,7 @@ from __future__ import annotations
 
 import itertools
 from dataclasses import dataclass
-from typing import Any
+from typing import Any, Sequence
 
 SENTINEL = "⊕"  # `_embed.py:70`
 
@@ -139,10 +141,44 @@ class SentencePieceTokenizer:
         return self.sp.decode([i - self.FAIRSEQ_OFFSET for i in ids if i > self.UNK_ID])
 
 
+BATCHING_MODES = ("padded", "packed")
+
+
+def pack_runs(lengths: Sequence[int], pack_tokens: int) -> list[tuple[int, int]]:
+    """The packs of a packed forward: greedy runs [lo, hi) of consecutive sequences, in input order, whose token total is at most
+    `pack_tokens`; a single sequence longer than that goes alone."""
+    runs, lo, total = [], 0, 0
+    for i, n in enumerate(lengths):
+        if i > lo and total + n > pack_tokens:
+            runs.append((lo, i))
+            lo, total = i, 0
+        total += n
+    if len(lengths) > lo:
+        runs.append((lo, len(lengths)))
+    return runs
+
+
+def packed_inputs(rows: Sequence[Sequence[int]], device: Any, type_rows: Sequence[Sequence[int]] | None = None):  # noqa: ANN201
+    """(ids, seq_offsets, lengths, type_ids or None) of one pack for `Encoder.forward_packed`: the sequences concatenated along the token
+    axis and their int32 offsets, uploaded from pinned memory without blocking; the lengths stay on the host."""
+    import torch
+
+    lens = [len(r) for r in rows]
+    ids = torch.tensor(list(itertools.chain.from_iterable(rows)), dtype=torch.long)
+    off = torch.tensor(list(itertools.accumulate(lens, initial=0)), dtype=torch.int32)
+    typ = None if type_rows is None else torch.tensor(list(itertools.chain.from_iterable(type_rows)), dtype=torch.long)
+    if torch.device(device).type == "cuda":
+        ids, off = ids.pin_memory().to(device, non_blocking=True), off.pin_memory().to(device, non_blocking=True)
+        typ = None if typ is None else typ.pin_memory().to(device, non_blocking=True)
+    return ids, off, lens, typ
+
+
 def _build_encoder(shape: EncoderShape):
     import torch
     from torch import nn
     from torch.nn import functional as F  # noqa: N812
+
+    from raglite_amd._attention import attention_varlen, attention_varlen_supports
 
     class Layer(nn.Module):
         def __init__(self) -> None:
@@ -163,6 +199,23 @@ def _build_encoder(shape: EncoderShape):
                 k, v = k[:, :, :kv_len], v[:, :, :kv_len]
             a = F.scaled_dot_product_attention(q, k, v, attn_mask=mask)
             x = self.ln1(x + self.out(a.transpose(1, 2).reshape(B, T, d)))  # post-LN, like BERT / XLM-R
+            return self.ln2(x + self.down(F.gelu(self.up(x))))
+
+        def forward_packed(self, x, seq_offsets, lengths_host):  # x: (n_tokens, d), the sequences one after another
+            n, d = x.shape
+            h = shape.heads
+            qkv = self.qkv(x)
+            if x.is_cuda and attention_varlen_supports(x.dtype, d // h):  # the gfx950 kernel reads the fused projection in place
+                a = attention_varlen(qkv, seq_offsets, max(lengths_host), h)
+            else:  # CPU, fp32, other head widths: torch's attention per sequence, sliced by the host lengths (no device round trip)
+                q, k, v = qkv.view(n, 3, h, d // h).permute(1, 2, 0, 3)  # each (h, n, d/h)
+                parts, lo = [], 0
+                for ln in lengths_host:
+                    if ln:
+                        parts.append(F.scaled_dot_product_attention(q[None, :, lo:lo + ln], k[None, :, lo:lo + ln], v[None, :, lo:lo + ln])[0])
+                    lo += ln
+                a = torch.cat(parts, dim=1).transpose(0, 1).reshape(n, d)
+            x = self.ln1(x + self.out(a))
             return self.ln2(x + self.down(F.gelu(self.up(x))))
 
     class Encoder(nn.Module):
@@ -213,6 +266,29 @@ def _build_encoder(shape: EncoderShape):
                 return self.head(torch.tanh(self.pooler(x[:, 0])))[:, 0]  # (B,): one relevance logit per pair
             return x  # (B, T, hidden): one embedding per token, pooling NONE
 
+        def forward_packed(self, ids, seq_offsets, lengths_host, type_ids=None):
+            """The same forward over an UNPADDED batch: ids (n_tokens,) holds the sequences one after another, seq_offsets (int32,
+            n_seqs + 1, on ids' device) where each starts, lengths_host their lengths as Python integers.  Embeddings, layer norms, linears
+            and GELU run on (n_tokens, hidden) -- no pad token is computed -- and attention is block-diagonal: `attention_varlen` on a
+            GPU in bf16 / fp16 at a head width it covers, otherwise torch's attention per sequence.  Nothing here waits for the device.
+            Returns (n_tokens, hidden), or one logit per sequence with a classifier head."""
+            n = ids.shape[0]
+            if n == 0 or n != sum(lengths_host):
+                raise ValueError("forward_packed: needs at least one token, and lengths that add up to the number of tokens")
+            lens = torch.tensor(lengths_host, dtype=torch.long)
+            starts = torch.cumsum(lens, 0) - lens
+            pos = torch.arange(n) - torch.repeat_interleave(starts, lens) + shape.position_offset  # t - seq_start + offset, made on the host
+            if ids.is_cuda:
+                pos = pos.pin_memory().to(ids.device, non_blocking=True)
+            typ = self.typ.weight[0] if type_ids is None else self.typ(type_ids)
+            x = self.ln(self.tok(ids) + self.pos(pos) + typ)
+            for layer in self.layers:
+                x = layer.forward_packed(x, seq_offsets, lengths_host)
+            if shape.classifier:
+                first = x[seq_offsets[:-1].long().clamp(max=n - 1)]  # each sequence's first row
+                return self.head(torch.tanh(self.pooler(first)))[:, 0]
+            return x
+
     return Encoder()
 
 
@@ -250,9 +326,17 @@ class TorchTokenEmbedder:
     """llama-like facade over the encoder: the object `embedder_for(config)` is expected to return."""
 
     def __init__(self, shape: EncoderShape | None = None, *, tokenizer: Any | None = None, device: str = "cuda",
-                 dtype: Any | None = None, seed: int = 0, n_batch: int | None = None) -> None:
+                 dtype: Any | None = None, seed: int = 0, n_batch: int | None = None, batching: str = "padded",
+                 pack_tokens: int = 16384) -> None:
+        """batching: how `embed` runs the strings of one call through the encoder -- "padded" (default): one batch padded to the longest,
+        keys masked; "packed": unpadded packs of at most `pack_tokens` tokens (`pack_runs`) through `Encoder.forward_packed`."""
         import torch
 
+        if batching not in BATCHING_MODES:
+            raise ValueError('batching must be "padded" or "packed"')
+        if pack_tokens < 1:
+            raise ValueError("pack_tokens must be >= 1")
+        self.batching, self.pack_tokens = batching, int(pack_tokens)
         self.shape = shape or EncoderShape()
         self.tokenizer = tokenizer or HashTokenizer(self.shape.vocab_size)
         self.device = torch.device(device)
@@ -301,6 +385,9 @@ class TorchTokenEmbedder:
         # Lengths stay on the HOST and the ids go up from pinned memory without blocking: nothing in this call waits for the device, so the
         # caller tokenises the next segment while the GPU is still in this one (a `.to(device)` from pageable memory and `int(tensor)`
         # each waited for the whole forward pass: 8 ms of idle GPU per 7.8 k-token segment)
+        if self.batching == "packed":
+            mats = self._embed_packed(rows)
+            return mats[0] if single else mats
         lens = [len(r) for r in rows]
         T = max(lens)  # noqa: N806
         ids = torch.full((len(rows), T), self.shape.pad_id, dtype=torch.long)
@@ -313,3 +400,16 @@ class TorchTokenEmbedder:
             out = self.encoder(ids, lengths, all_full=min(lens) == T).float()
         mats = [out[i, : lens[i]] for i in range(len(rows))]
         return mats[0] if single else mats
+
+    def _embed_packed(self, rows: list[list[int]]) -> list:
+        """One packed forward per run of `pack_runs`; the pad-queries-to-128 trick of the padded route belongs to torch's attention
+        kernel and is not applied here."""
+        import torch
+
+        mats = []
+        for lo, hi in pack_runs([len(r) for r in rows], self.pack_tokens):
+            ids, off, lens, _ = packed_inputs(rows[lo:hi], self.device)
+            with torch.inference_mode():
+                out = self.encoder.forward_packed(ids, off, lens).float()
+            mats.extend(torch.split(out, lens))
+        return mats

@@ -1,5 +1,5 @@
-// The ingestion entry points of the C ABI, which take no handle: pooling and normalising token embeddings, and the document-batched
-// splitters (include/raglite_hip.h for the contract of each).
+// The ingestion entry points of the C ABI, which take no handle: pooling and normalising token embeddings, the packed
+// encoder's attention, and the document-batched splitters (include/raglite_hip.h for the contract of each).
 #include <string>
 
 #include "staging.h"
@@ -33,6 +33,25 @@ int rl_pool_norm(const float* tokens, int64_t n_token_rows, int32_t dim, const i
     RL_TRY(st.out(out_f16, (size_t)n_spans * dim, &d_o16));
     RL_TRY(launch_pool_norm(d_tok, dim, d_b, d_e, n_spans, normalize, eps, d_o32, d_o16, s));
     return st.finish();
+}
+
+// ---- the packed encoder's attention (attention_varlen.hip) -------------------------------------------------------------------------
+int rl_attention_varlen(const void* qkv, const int32_t* seq_offsets, int32_t n_seqs, int64_t n_tokens, int32_t max_len, int32_t heads,
+                        int32_t head_dim, int32_t dtype, float scale, void* out, int mem, void* stream) {
+    if (n_seqs < 0 || n_tokens < 0 || max_len < 0) return fail(RL_ERR_INVALID, "rl_attention_varlen: negative size");
+    if (heads < 1) return fail(RL_ERR_INVALID, "rl_attention_varlen: heads must be >= 1");
+    if (!(scale - scale == 0.0f)) return fail(RL_ERR_INVALID, "rl_attention_varlen: scale must be finite");
+    if (dtype != RL_ATTN_BF16 && dtype != RL_ATTN_F16) return fail(RL_ERR_INVALID, "rl_attention_varlen: unknown dtype");
+    if (n_seqs > 65535) return fail(RL_ERR_INVALID, "rl_attention_varlen: n_seqs must be <= 65535 (the grid's z axis)");
+    if (heads > 65535) return fail(RL_ERR_INVALID, "rl_attention_varlen: heads must be <= 65535 (the grid's y axis)");
+    if (n_tokens >= ((int64_t)1 << 31)) return fail(RL_ERR_INVALID, "rl_attention_varlen: n_tokens must be < 2^31 (offsets are int32)");
+    if (head_dim != 32 && head_dim != 64) return fail(RL_ERR_UNSUPPORTED, "rl_attention_varlen: head_dim must be 32 or 64");
+    if (mem != RL_MEM_DEVICE) return fail(RL_ERR_UNSUPPORTED, "rl_attention_varlen: device pointers only (mem must be RL_MEM_DEVICE)");
+    if (n_tokens == 0) return RL_OK;
+    if (!qkv || !seq_offsets || !out) return fail(RL_ERR_INVALID, "rl_attention_varlen: null argument");
+    if ((reinterpret_cast<uintptr_t>(qkv) & 15) || (reinterpret_cast<uintptr_t>(out) & 7))
+        return fail(RL_ERR_INVALID, "rl_attention_varlen: qkv must be 16-byte and out 8-byte aligned");
+    return launch_attention_varlen(qkv, seq_offsets, n_seqs, n_tokens, max_len, heads, head_dim, dtype, scale, out, as_stream(stream));
 }
 
 // ---- document-batched ingestion: similarities, chunk / chunklet / sentence partitions (kernels in partition_sim.hip, partition_dp.hip,

@@ -110,6 +110,10 @@ int launch_pool_norm(const float* tokens, int32_t dim, const int64_t* span_begin
                      int64_t n_spans, int normalize, double eps, float* out_f32, uint16_t* out_f16,
                      hipStream_t s);
 
+// attention_varlen.hip: arguments as rl_attention_varlen takes them, already checked
+int launch_attention_varlen(const void* qkv, const int32_t* seq_offsets, int32_t n_seqs, int64_t n_tokens, int32_t max_len, int32_t heads,
+                            int32_t head_dim, int32_t dtype, float scale, void* out, hipStream_t s);
+
 // scan.hip
 enum ScanMode { SCAN_RAW_DOT = 0, SCAN_COSINE = 1, SCAN_DOT = 2, SCAN_L2 = 3 };
 
