@@ -121,6 +121,47 @@ int rl_pool_norm(const float* tokens, int64_t n_token_rows, int32_t dim,
 int rl_attention_varlen(const void* qkv, const int32_t* seq_offsets, int32_t n_seqs, int64_t n_tokens, int32_t max_len,
                         int32_t heads, int32_t head_dim, int32_t dtype, float scale, void* out, int mem, void* stream);
 
+/* ---- native encoder forward for short packs (text queries) --------------------------------------------------------
+ * The forward of a post-LN BERT / XLM-R encoder over a PACKED batch of at most RL_ENCODER_MAX_TOKENS tokens, enqueued by one call:
+ *     x = LN(tok[id] + pos[p] + typ[type]);  per layer:  qkv = x Wqkv^T + b;  a = attention_varlen(qkv);
+ *     x1 = LN1(x + a Wout^T + b);  x = LN2(x1 + gelu_erf(x1 Wup^T + b) Wdown^T + b)
+ * Every sum (embeddings, products, bias, residual, layer norm) is taken in f32 and rounded ONCE to the 16-bit dtype where the next
+ * step reads it: after each layer norm, after the QKV bias and after the GELU.  1 + 7 * layers kernel launches, no allocation, no
+ * synchronisation, no atomics: the same bits run to run, and a sequence's bits depend neither on its place in the pack nor on
+ * what else is in it.
+ *
+ * rl_encoder_create BORROWS every parameter pointer (device memory, `dtype` elements; the caller keeps the tensors alive and
+ * unchanged in place for as long as the handle) and allocates the scratch of RL_ENCODER_MAX_TOKENS rows:
+ *   tok [vocab x hidden], pos [max_positions x hidden], typ [type_vocab x hidden], ln_w / ln_b [hidden]
+ *   layer_params   HOST array of 12 * layers device pointers, per layer: qkv_w [3 hidden x hidden], qkv_b, out_w [hidden x hidden],
+ *                  out_b, ln1_w, ln1_b, up_w [ffn x hidden], up_b, down_w [hidden x ffn], down_b, ln2_w, ln2_b -- the matrices in
+ *                  nn.Linear's own row-major [out x in] layout, read in place
+ *   every parameter pointer 16-byte aligned
+ * Checked before any HIP call: RL_ERR_INVALID for a null argument, a size < 1, hidden % heads != 0, heads > 65535, eps not finite or
+ * negative, an unknown dtype, a misaligned parameter; RL_ERR_UNSUPPORTED for a head width outside {32, 64}, hidden or ffn not a multiple of 32,
+ * hidden > 8192 or ffn > 32768.
+ *
+ * rl_encoder_forward: ids, positions, type_ids (NULL: type 0 everywhere) int32[n_tokens], seq_offsets int32[n_seqs + 1] as
+ * rl_attention_varlen takes them, all on the device; max_len >= every sequence length; out [n_tokens x hidden] in the handle's dtype,
+ * 16-byte aligned.  Ids, positions and type ids are clamped into their tables: a bad id gives a wrong number, never an access
+ * outside a table.  Checked before any HIP call, the handle last: mem != RL_MEM_DEVICE (RL_ERR_UNSUPPORTED), a negative size,
+ * n_seqs > 65535, n_tokens > RL_ENCODER_MAX_TOKENS (RL_ERR_UNSUPPORTED), null or misaligned pointers with n_tokens > 0, a null handle.
+ * n_tokens == 0 returns RL_OK and writes nothing.  Calls on one handle share its scratch (the mutex and stream rule of the header's
+ * conventions).
+ *
+ * rl_encoder_info: max_tokens = RL_ENCODER_MAX_TOKENS; scratch / scratch_bytes: the handle's block; used_bytes: the prefix of it a
+ * forward of n_tokens rows writes (nothing behind it is touched); launches = 1 + 7 * layers.  Every output may be NULL. */
+#define RL_ENCODER_MAX_TOKENS 256
+typedef struct rl_encoder rl_encoder;
+int rl_encoder_create(rl_encoder** out, int32_t vocab, int32_t hidden, int32_t layers, int32_t heads, int32_t ffn, int32_t max_positions,
+                      int32_t type_vocab, float eps, int32_t dtype, const void* tok, const void* pos, const void* typ, const void* ln_w,
+                      const void* ln_b, const void* const* layer_params);
+int rl_encoder_forward(rl_encoder* enc, const int32_t* ids, const int32_t* positions, const int32_t* type_ids, const int32_t* seq_offsets,
+                       int32_t n_seqs, int64_t n_tokens, int32_t max_len, void* out, int mem, void* stream);
+int rl_encoder_info(const rl_encoder* enc, int64_t n_tokens, int32_t* max_tokens, int64_t* scratch_bytes, int64_t* used_bytes,
+                    void** scratch, int32_t* launches);
+int rl_encoder_destroy(rl_encoder* enc);
+
 /* ---- a5: query adapter -----------------------------------------------------------------------
  * Replaces src/raglite/_search.py:62  `(Q @ q).astype(q.dtype)`; out[b] = A @ q[b].
  *   A [dim x dim] f32, queries [B x dim] f32, out_f32 [B x dim] or NULL, out_f16 or NULL. */

@@ -95,6 +95,7 @@ from raglite_amd._torch_embedder import EncoderShape, HashTokenizer, SentencePie
 from raglite_amd._query_adapter import optimize_query_target_active_set, optimize_query_targets, update_query_adapter
 from raglite_amd._comm import Communicator
 from raglite_amd._attention import attention_varlen
+from raglite_amd._encoder import NativeEncoder
 from raglite_amd._sharded import ShardedIndex, merge_topk_host, shard_bounds_by_chunk
 
 __all__ = [
@@ -142,6 +143,6 @@ __all__ = [
     "embed_strings_without_late_chunking", "embedding_type", "merge_topk", "merge_topk_host", "pool_norm",
     "rerank_chunks", "search_and_rerank_chunks", "select_reranker", "set_language_detector", "set_device", "set_embedder_factory", "shard_bounds_by_chunk",
     "synth_fill", "topk", "vector_search",
-    "attention_varlen", "embed_strings_batch",
+    "attention_varlen", "embed_strings_batch", "NativeEncoder",
 ]
 __version__ = "0.1.0"

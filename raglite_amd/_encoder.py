@@ -1,0 +1,149 @@
+"""The native encoder forward for short packs through the C ABI (`rl_encoder_*`, raglite_amd/csrc/encoder.hip): the
+whole forward of `_torch_embedder`'s `Encoder` over a packed batch of at most `MAX_TOKENS` tokens, enqueued by one call -- what a text
+query needs, where the torch route is bound by launches and Python.  CUDA tensors only, like `_attention.py`, which is why the wrapper
+lives here and not among the `_ops*` modules."""
+
+from __future__ import annotations
+
+import ctypes as C
+from typing import Any, Sequence
+
+from raglite_amd._abi import ATTN_DTYPES, ENCODER_MAX_TOKENS, MEM_DEVICE, check, lib
+from raglite_amd._attention import HEAD_DIMS
+from raglite_amd._ops_frame import _Args, _Handle
+
+MAX_TOKENS = ENCODER_MAX_TOKENS
+HIDDEN_MAX, FFN_MAX = 8192, 32768
+_LAYER_PARAMS = ("qkv.weight", "qkv.bias", "out.weight", "out.bias", "ln1.weight", "ln1.bias", "up.weight", "up.bias", "down.weight",
+                 "down.bias", "ln2.weight", "ln2.bias")  # the order of rl_encoder_create's layer_params
+
+
+def _dtype_name(dtype: Any) -> str:
+    return str(dtype).split(".")[-1]
+
+
+class NativeEncoder(_Handle):
+    """`Encoder.forward_packed` without its classifier head, in HIP: `forward` returns the (n_tokens, hidden) rows in the module's
+    16-bit dtype.  The handle borrows the module's parameters; it is made on the first call and made again whenever a parameter's
+    `data_ptr()` or the dtype has changed (`.to(dtype)`, a `load_state_dict` that reallocates).  A parameter rewritten IN PLACE is
+    simply read: the library keeps no copy."""
+
+    _destroy = "rl_encoder_destroy"
+
+    def __init__(self, encoder_module: Any, shape: Any) -> None:
+        self.module, self.shape = encoder_module, shape
+        self._key: tuple | None = None
+        self._held: list = []
+        self._collect()
+
+    def _collect(self) -> None:
+        """The module's Parameter objects in the order of rl_encoder_create.  They are looked up once: `.to(dtype)` and `load_state_dict`
+        swap or rewrite their storage and keep the objects; a conversion that makes new ones (a move between devices) is noticed by
+        `_ensure_handle` on the first and the last of them."""
+        names = ["tok.weight", "pos.weight", "typ.weight", "ln.weight", "ln.bias"]
+        names += [f"layers.{i}.{n}" for i in range(self.shape.layers) for n in _LAYER_PARAMS]
+        params = dict(self.module.named_parameters())
+        self._params = [params[n] for n in names]
+
+    @staticmethod
+    def supports(shape: Any, dtype: Any, n_tokens: int, device: Any = "cuda") -> bool:
+        """Does the native forward take a pack of `n_tokens` tokens of this shape, element type and device?"""
+        import torch
+
+        if torch.device(device).type != "cuda" or _dtype_name(dtype) not in ATTN_DTYPES:
+            return False
+        if shape.heads < 1 or shape.hidden % shape.heads or shape.hidden // shape.heads not in HEAD_DIMS:
+            return False
+        if shape.hidden % 32 or shape.ffn % 32 or shape.hidden > HIDDEN_MAX or shape.ffn > FFN_MAX or shape.layers < 1:
+            return False
+        return 1 <= n_tokens <= MAX_TOKENS
+
+    def _ensure_handle(self) -> None:
+        if self.module.tok.weight is not self._params[0] or self.module.layers[-1].ln2.bias is not self._params[-1]:
+            self._collect()
+        key =(self._params[0].dtype, *(p.data_ptr() for p in self._params))
+        if key == self._key and self._handle:
+            return
+        self.close()
+        sh, tensors = self.shape, [p.data for p in self._params]
+        if any(not t.is_cuda or not t.is_contiguous() or t.dtype != tensors[0].dtype for t in tensors):
+            raise ValueError("NativeEncoder: the encoder's parameters must be contiguous CUDA tensors of one dtype")
+        name = _dtype_name(tensors[0].dtype)
+        if name not in ATTN_DTYPES:
+            raise ValueError("NativeEncoder: the encoder must be bfloat16 or float16")
+        layer_ptrs = (C.c_void_p * (len(tensors) - 5))(*(t.data_ptr() for t in tensors[5:]))
+        h = C.c_void_p()
+        check(lib().rl_encoder_create(C.byref(h), sh.vocab_size, sh.hidden, sh.layers, sh.heads, sh.ffn, sh.max_positions, sh.type_vocab,
+                                      float(sh.layer_norm_eps), ATTN_DTYPES[name], *(t.data_ptr() for t in tensors[:5]), layer_ptrs))
+        self._handle, self._key, self._held = h, key, tensors  # (the storages the handle reads stay alive with it)
+
+    def close(self) -> None:
+        super().close()
+        self._key, self._held = None, []
+
+    def info(self, n_tokens: int = 0) -> dict:
+        """The handle's cap, its scratch block (device pointer and bytes), the prefix a forward of `n_tokens` rows writes, and the kernel
+        launches of a forward."""
+        a = _Args.on(MEM_DEVICE, self._params[0].device)
+        a.ensure_device()
+        self._ensure_handle()
+        cap, launches, total, used, ptr = C.c_int32(), C.c_int32(), C.c_int64(), C.c_int64(), C.c_void_p()
+        check(lib().rl_encoder_info(self._handle, int(n_tokens), C.byref(cap), C.byref(total), C.byref(used), C.byref(ptr), C.byref(launches)))
+        return {"max_tokens": cap.value, "scratch_bytes": total.value, "used_bytes": used.value, "scratch": ptr.value or 0,
+                "launches": launches.value}
+
+    def forward_i32(self, ids: Any, positions: Any, seq_offsets: Any, type_ids: Any | None, n_seqs: int, n_tokens: int, max_len: int,
+                    out: Any | None = None) -> Any:
+        """The C call on int32 CUDA tensors as it takes them (ids, positions, type_ids or None: n_tokens each; seq_offsets: n_seqs + 1),
+        enqueued on torch's current stream; nothing waits for the device."""
+        import torch
+
+        dev = self._params[0].device
+        a = _Args.on(MEM_DEVICE, dev)
+        a.ensure_device()
+        self._ensure_handle()
+        for t in (ids, positions, seq_offsets, type_ids):
+            if t is not None and not (t.is_cuda and t.dtype == torch.int32 and t.is_contiguous()):
+                raise ValueError("NativeEncoder: ids, positions, seq_offsets and type_ids must be contiguous int32 CUDA tensors")
+        if ids.numel() < n_tokens or positions.numel() < n_tokens or seq_offsets.numel() < n_seqs + 1 or (type_ids is not None and type_ids.numel() < n_tokens):
+            raise ValueError("NativeEncoder: an argument is shorter than n_tokens / n_seqs + 1")
+        if out is None:
+            out = torch.empty((n_tokens, self.shape.hidden), dtype=self._params[0].dtype, device=dev)
+        a.hold(ids, positions, seq_offsets, type_ids, out)
+        check(lib().rl_encoder_forward(self._handle, ids.data_ptr(), positions.data_ptr(), type_ids.data_ptr() if type_ids is not None else None,
+                                       seq_offsets.data_ptr(), int(n_seqs), int(n_tokens), int(max_len), out.data_ptr(), MEM_DEVICE, a.stream))
+        return out
+
+    def forward(self, ids: Any, seq_offsets: Any, lengths_host: Sequence[int], type_ids: Any | None = None) -> Any:
+        """`Encoder.forward_packed`'s arguments: ids (n_tokens,) CUDA integers, the sequences one after another; seq_offsets int32
+        (n_seqs + 1) on the device; lengths_host their lengths as Python integers (the positions are made from them on the host)."""
+        import torch
+
+        n = int(ids.shape[0])
+        if n == 0 or n != sum(lengths_host):
+            raise ValueError("NativeEncoder.forward: needs at least one token, and lengths that add up to the number of tokens")
+        if n > MAX_TOKENS:
+            raise ValueError(f"NativeEncoder.forward: at most {MAX_TOKENS} tokens per pack")
+        pos = torch.tensor([t + self.shape.position_offset for ln in lengths_host for t in range(ln)], dtype=torch.int32)
+        pos = pos.pin_memory().to(ids.device, non_blocking=True)
+        typ = None if type_ids is None else type_ids.to(torch.int32).contiguous()
+        return self.forward_i32(ids.to(torch.int32).contiguous(), pos, seq_offsets.to(torch.int32).contiguous(), typ, len(lengths_host), n,
+                                max(lengths_host))
+
+    def forward_rows(self, rows: Sequence[Sequence[int]], type_rows: Sequence[Sequence[int]] | None = None) -> Any:
+        """The forward of token-id lists (each with its `<s>` / `</s>`): ids, positions, type ids and offsets go up in ONE copy from
+        pinned memory."""
+        import itertools
+
+        import torch
+
+        lens = [len(r) for r in rows]
+        n, off = sum(lens), self.shape.position_offset
+        flat = list(itertools.chain.from_iterable(rows))
+        flat += [t + off for ln in lens for t in range(ln)]
+        if type_rows is not None:
+            flat += list(itertools.chain.from_iterable(type_rows))
+        flat += list(itertools.accumulate(lens, initial=0))
+        buf = torch.tensor(flat, dtype=torch.int32).pin_memory().to(self._params[0].device, non_blocking=True)
+        typ = buf[2 * n: 3 * n] if type_rows is not None else None
+        return self.forward_i32(buf[:n], buf[n: 2 * n], buf[(3 if type_rows is not None else 2) * n:], typ, len(lens), n, max(lens))

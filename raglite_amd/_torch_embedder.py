@@ -142,6 +142,7 @@ class SentencePieceTokenizer:
 
 
 BATCHING_MODES = ("padded", "packed")
+SHORT_FORWARD_MODES = ("torch", "native")
 
 
 def pack_runs(lengths: Sequence[int], pack_tokens: int) -> list[tuple[int, int]]:
@@ -327,13 +328,19 @@ class TorchTokenEmbedder:
 
     def __init__(self, shape: EncoderShape | None = None, *, tokenizer: Any | None = None, device: str = "cuda",
                  dtype: Any | None = None, seed: int = 0, n_batch: int | None = None, batching: str = "padded",
-                 pack_tokens: int = 16384) -> None:
+                 pack_tokens: int = 16384, short_forward: str = "torch") -> None:
         """batching: how `embed` runs the strings of one call through the encoder -- "padded" (default): one batch padded to the longest,
-        keys masked; "packed": unpadded packs of at most `pack_tokens` tokens (`pack_runs`) through `Encoder.forward_packed`."""
+        keys masked; "packed": unpadded packs of at most `pack_tokens` tokens (`pack_runs`) through `Encoder.forward_packed`.
+        short_forward: "torch" (default): always that route; "native": a call whose strings together have at most
+        `_encoder.MAX_TOKENS` tokens runs as ONE pack through the HIP forward (`NativeEncoder`) when the encoder is on a
+        GPU in bf16 / fp16 at a head width of 32 or 64 -- every other call takes the `batching` route as before."""
         import torch
 
         if batching not in BATCHING_MODES:
             raise ValueError('batching must be "padded" or "packed"')
+        if short_forward not in SHORT_FORWARD_MODES:
+            raise ValueError('short_forward must be "torch" or "native"')
+        self.short_forward, self._native = short_forward, None
         if pack_tokens < 1:
             raise ValueError("pack_tokens must be >= 1")
         self.batching, self.pack_tokens = batching, int(pack_tokens)
@@ -385,6 +392,10 @@ class TorchTokenEmbedder:
         # Lengths stay on the HOST and the ids go up from pinned memory without blocking: nothing in this call waits for the device, so the
         # caller tokenises the next segment while the GPU is still in this one (a `.to(device)` from pageable memory and `int(tensor)`
         # each waited for the whole forward pass: 8 ms of idle GPU per 7.8 k-token segment)
+        if self.short_forward == "native":
+            mats = self._embed_native(rows)
+            if mats is not None:
+                return mats[0] if single else mats
         if self.batching == "packed":
             mats = self._embed_packed(rows)
             return mats[0] if single else mats
@@ -400,6 +411,22 @@ class TorchTokenEmbedder:
             out = self.encoder(ids, lengths, all_full=min(lens) == T).float()
         mats = [out[i, : lens[i]] for i in range(len(rows))]
         return mats[0] if single else mats
+
+    def _embed_native(self, rows: list[list[int]]) -> list | None:
+        """The strings of a call as one pack through the HIP forward, or None where it does not take them (too many tokens, a CPU,
+        fp32, a head width it does not cover, a classifier head): the caller then goes on as it always did."""
+        import torch
+
+        from raglite_amd._encoder import NativeEncoder
+
+        w = self.encoder.ln.weight
+        if self.shape.classifier or not NativeEncoder.supports(self.shape, w.dtype, sum(len(r) for r in rows), w.device):
+            return None
+        if self._native is None or self._native.module is not self.encoder:
+            self._native = NativeEncoder(self.encoder, self.shape)
+        with torch.inference_mode():
+            out = self._native.forward_rows(rows).float()
+        return list(torch.split(out, [len(r) for r in rows]))
 
     def _embed_packed(self, rows: list[list[int]]) -> list:
         """One packed forward per run of `pack_runs`; the pad-queries-to-128 trick of the padded route belongs to torch's attention

@@ -1,7 +1,10 @@
-// The ingestion entry points of the C ABI, which take no handle: pooling and normalising token embeddings, the packed
-// encoder's attention, and the document-batched splitters (include/raglite_hip.h for the contract of each).
+// The ingestion entry points of the C ABI: pooling and normalising token embeddings, the packed encoder's attention, the native
+// encoder forward for short packs (the one handle here, rl_encoder) and the document-batched splitters (include/raglite_hip.h for
+// the contract of each).
+#include <cmath>
 #include <string>
 
+#include "handles.h"
 #include "staging.h"
 
 using namespace rl;
@@ -52,6 +55,100 @@ int rl_attention_varlen(const void* qkv, const int32_t* seq_offsets, int32_t n_s
     if ((reinterpret_cast<uintptr_t>(qkv) & 15) || (reinterpret_cast<uintptr_t>(out) & 7))
         return fail(RL_ERR_INVALID, "rl_attention_varlen: qkv must be 16-byte and out 8-byte aligned");
     return launch_attention_varlen(qkv, seq_offsets, n_seqs, n_tokens, max_len, heads, head_dim, dtype, scale, out, as_stream(stream));
+}
+
+// ---- the native encoder forward for short packs (encoder.hip) -------------------------------------------------------
+static bool misaligned(const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) != 0; }
+
+int rl_encoder_create(rl_encoder** out, int32_t vocab, int32_t hidden, int32_t layers, int32_t heads, int32_t ffn, int32_t max_positions,
+                      int32_t type_vocab, float eps, int32_t dtype, const void* tok, const void* pos, const void* typ, const void* ln_w,
+                      const void* ln_b, const void* const* layer_params) {
+    if (!out) return fail(RL_ERR_INVALID, "rl_encoder_create: out is null");
+    *out = nullptr;
+    if (vocab < 1 || hidden < 1 || layers < 1 || heads < 1 || ffn < 1 || max_positions < 1 || type_vocab < 1)
+        return fail(RL_ERR_INVALID, "rl_encoder_create: every size must be >= 1");
+    if (hidden % heads) return fail(RL_ERR_INVALID, "rl_encoder_create: hidden must be a multiple of heads");
+    if (!(eps - eps == 0.0f) || eps < 0.0f) return fail(RL_ERR_INVALID, "rl_encoder_create: eps must be finite and >= 0");
+    if (dtype != RL_ATTN_BF16 && dtype != RL_ATTN_F16) return fail(RL_ERR_INVALID, "rl_encoder_create: unknown dtype");
+    if (heads > 65535) return fail(RL_ERR_INVALID, "rl_encoder_create: heads must be <= 65535 (the attention grid's y axis)");
+    if (hidden / heads != 32 && hidden / heads != 64) return fail(RL_ERR_UNSUPPORTED, "rl_encoder_create: head width must be 32 or 64");
+    if (hidden % 32 || ffn % 32) return fail(RL_ERR_UNSUPPORTED, "rl_encoder_create: hidden and ffn must be multiples of 32");
+    if (hidden > ENC_HIDDEN_MAX || ffn > 4 * ENC_HIDDEN_MAX) return fail(RL_ERR_UNSUPPORTED, "rl_encoder_create: hidden must be <= 8192 and ffn <= 32768");
+    if (!tok || !pos || !typ || !ln_w || !ln_b || !layer_params) return fail(RL_ERR_INVALID, "rl_encoder_create: null argument");
+    if (misaligned(tok, 16) || misaligned(pos, 16) || misaligned(typ, 16) || misaligned(ln_w, 16) || misaligned(ln_b, 16))
+        return fail(RL_ERR_INVALID, "rl_encoder_create: the embedding tables and their layer norm must be 16-byte aligned");
+    for (int64_t i = 0; i < (int64_t)12 * layers; ++i) {
+        if (!layer_params[i]) return fail(RL_ERR_INVALID, "rl_encoder_create: null layer parameter");
+        if (misaligned(layer_params[i], 16)) return fail(RL_ERR_INVALID, "rl_encoder_create: every layer parameter must be 16-byte aligned");
+    }
+    std::unique_ptr<rl_encoder> e(new rl_encoder);
+    e->vocab = vocab; e->hidden = hidden; e->layers = layers; e->heads = heads; e->ffn = ffn;
+    e->max_positions = max_positions; e->type_vocab = type_vocab; e->dtype = dtype; e->eps = eps;
+    e->tok = tok; e->pos = pos; e->typ = typ; e->ln_w = ln_w; e->ln_b = ln_b;
+    e->layer.resize((size_t)layers);
+    for (int32_t l = 0; l < layers; ++l) {
+        const void* const* p = layer_params + (size_t)12 * l;
+        e->layer[(size_t)l] = {p[0], p[1], p[2], p[3], p[4], p[5], p[6], p[7], p[8], p[9], p[10], p[11]};
+    }
+    e->ksplit = std::max(encoder_ksplit(hidden, hidden), encoder_ksplit(hidden, ffn));
+    EncoderScratch all;
+    RL_TRY(carve(e->scratch, all, (size_t)RL_ENCODER_MAX_TOKENS, (size_t)hidden, (size_t)ffn, (size_t)e->ksplit));
+    *out = e.release();
+    return RL_OK;
+}
+
+int rl_encoder_destroy(rl_encoder* enc) {
+    delete enc;
+    return RL_OK;
+}
+
+int rl_encoder_info(const rl_encoder* enc, int64_t n_tokens, int32_t* max_tokens, int64_t* scratch_bytes, int64_t* used_bytes,
+                    void** scratch, int32_t* launches) {
+    if (n_tokens < 0 || n_tokens > RL_ENCODER_MAX_TOKENS) return fail(RL_ERR_INVALID, "rl_encoder_info: n_tokens must be in [0, RL_ENCODER_MAX_TOKENS]");
+    if (!enc) return fail(RL_ERR_INVALID, "rl_encoder_info: null handle");
+    if (max_tokens) *max_tokens = RL_ENCODER_MAX_TOKENS;
+    if (scratch_bytes) *scratch_bytes = (int64_t)enc->scratch.cap;
+    if (used_bytes) *used_bytes = (int64_t)EncoderScratch().lay(Carver(), (size_t)n_tokens, (size_t)enc->hidden, (size_t)enc->ffn, (size_t)enc->ksplit);
+    if (scratch) *scratch = enc->scratch.p;
+    if (launches) *launches = 1 + 7 * enc->layers;
+    return RL_OK;
+}
+
+int rl_encoder_forward(rl_encoder* enc, const int32_t* ids, const int32_t* positions, const int32_t* type_ids, const int32_t* seq_offsets,
+                       int32_t n_seqs, int64_t n_tokens, int32_t max_len, void* out, int mem, void* stream) {
+    if (mem != RL_MEM_DEVICE) return fail(RL_ERR_UNSUPPORTED, "rl_encoder_forward: device pointers only (mem must be RL_MEM_DEVICE)");
+    if (n_seqs < 0 || n_tokens < 0 || max_len < 0) return fail(RL_ERR_INVALID, "rl_encoder_forward: negative size");
+    if (n_seqs > 65535) return fail(RL_ERR_INVALID, "rl_encoder_forward: n_seqs must be <= 65535 (the attention grid's z axis)");
+    if (n_tokens > RL_ENCODER_MAX_TOKENS) return fail(RL_ERR_UNSUPPORTED, "rl_encoder_forward: n_tokens must be <= RL_ENCODER_MAX_TOKENS (256)");
+    if (n_tokens > 0) {
+        if (!ids || !positions || !seq_offsets || !out) return fail(RL_ERR_INVALID, "rl_encoder_forward: null argument");
+        if (misaligned(ids, 4) || misaligned(positions, 4) || misaligned(type_ids, 4) || misaligned(seq_offsets, 4) || misaligned(out, 16))
+            return fail(RL_ERR_INVALID, "rl_encoder_forward: the int32 arrays must be 4-byte and out 16-byte aligned");
+    }
+    if (!enc) return fail(RL_ERR_INVALID, "rl_encoder_forward: null handle");
+    if (n_tokens == 0) return RL_OK;
+    hipStream_t s = as_stream(stream);
+    std::lock_guard<std::mutex> lock(enc->mu);
+    RL_TRY(enc->last_stream.use(s));
+    const int32_t M = (int32_t)n_tokens, H = enc->hidden, F = enc->ffn, dt = enc->dtype;
+    EncoderScratch b;  // this call's rows: a prefix of the block reserved for the cap
+    b.lay(Carver(enc->scratch.p), (size_t)M, (size_t)H, (size_t)F, (size_t)enc->ksplit);
+    const int32_t ks_out = encoder_ksplit(H, H), ks_down = encoder_ksplit(H, F);
+    const float scale = 1.0f / sqrtf((float)(H / enc->heads));
+    RL_TRY(launch_encoder_embed(ids, positions, type_ids, M, enc->tok, enc->vocab, enc->pos, enc->max_positions, enc->typ, enc->type_vocab,
+                                enc->ln_w, enc->ln_b, H, enc->eps, dt, enc->layers ? (void*)b.x : out, s));
+    for (int32_t l = 0; l < enc->layers; ++l) {
+        const rl_encoder::Layer& p = enc->layer[(size_t)l];
+        void* x_next = l + 1 < enc->layers ? (void*)b.x : out;  // the last layer writes the caller's rows
+        RL_TRY(launch_encoder_linear(b.x, M, H, p.qkv_w, 3 * H, p.qkv_b, ENC_EPI_BIAS, dt, b.qkv, nullptr, s));
+        RL_TRY(launch_attention_varlen(b.qkv, seq_offsets, n_seqs, M, max_len, enc->heads, H / enc->heads, dt, scale, b.attn, s));
+        RL_TRY(launch_encoder_linear(b.attn, M, H, p.out_w, H, nullptr, ENC_EPI_PARTIAL, dt, nullptr, b.part, s));
+        RL_TRY(launch_encoder_ln(b.part, ks_out, M, H, p.out_b, b.x, p.ln1_w, p.ln1_b, enc->eps, dt, b.x1, s));
+        RL_TRY(launch_encoder_linear(b.x1, M, H, p.up_w, F, p.up_b, ENC_EPI_GELU, dt, b.mid, nullptr, s));
+        RL_TRY(launch_encoder_linear(b.mid, M, F, p.down_w, H, nullptr, ENC_EPI_PARTIAL, dt, nullptr, b.part, s));
+        RL_TRY(launch_encoder_ln(b.part, ks_down, M, H, p.down_b, b.x1, p.ln2_w, p.ln2_b, enc->eps, dt, x_next, s));
+    }
+    return RL_OK;
 }
 
 // ---- document-batched ingestion: similarities, chunk / chunklet / sentence partitions (kernels in partition_sim.hip, partition_dp.hip,

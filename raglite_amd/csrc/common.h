@@ -114,6 +114,24 @@ int launch_pool_norm(const float* tokens, int32_t dim, const int64_t* span_begin
 int launch_attention_varlen(const void* qkv, const int32_t* seq_offsets, int32_t n_seqs, int64_t n_tokens, int32_t max_len, int32_t heads,
                             int32_t head_dim, int32_t dtype, float scale, void* out, hipStream_t s);
 
+// encoder.hip: the kernels of rl_encoder_forward.  dtype: RL_ATTN_BF16 / RL_ATTN_F16, of every `void*` below;
+// M <= RL_ENCODER_MAX_TOKENS rows; hidden, K, N multiples of 32; arguments already checked
+constexpr int32_t ENC_KSPLIT_MAX = 8;
+constexpr int32_t ENC_HIDDEN_MAX = 8192;        // a row of f32 in a workgroup's LDS (the layer norms)
+int32_t encoder_ksplit(int32_t N, int32_t K);  // the K slices of a projection into f32 partials: a function of (N, K) alone
+// out[t] = LN(tok[ids[t]] + pos[positions[t]] + typ[type_ids ? type_ids[t] : 0]), indices clamped into their tables
+int launch_encoder_embed(const int32_t* ids, const int32_t* positions, const int32_t* type_ids, int32_t n_tokens, const void* tok,
+                         int32_t vocab, const void* pos, int32_t max_positions, const void* typ, int32_t type_vocab, const void* ln_w,
+                         const void* ln_b, int32_t hidden, float eps, int32_t dtype, void* out, hipStream_t s);
+enum EncEpilogue { ENC_EPI_BIAS = 0, ENC_EPI_GELU = 1, ENC_EPI_PARTIAL = 2 };
+// x [M x K] . W [N x K]^T: ENC_EPI_BIAS / ENC_EPI_GELU -> out16 [M x N] = (gelu_erf)(. + bias); ENC_EPI_PARTIAL -> part [encoder_ksplit(N, K) x
+// M x N] f32, the raw K slices (bias, residual and their ordered sum belong to launch_encoder_ln)
+int launch_encoder_linear(const void* x, int32_t M, int32_t K, const void* W, int32_t N, const void* bias, int epilogue, int32_t dtype,
+                          void* out16, float* part, hipStream_t s);
+// out[r] = LN(part[0][r] + .. + part[ksplit - 1][r] + bias + resid[r])
+int launch_encoder_ln(const float* part, int32_t ksplit, int32_t M, int32_t hidden, const void* bias, const void* resid, const void* ln_w,
+                      const void* ln_b, float eps, int32_t dtype, void* out, hipStream_t s);
+
 // scan.hip
 enum ScanMode { SCAN_RAW_DOT = 0, SCAN_COSINE = 1, SCAN_DOT = 2, SCAN_L2 = 3 };
 

@@ -208,6 +208,19 @@ struct rl_keyword_index {
     ~rl_keyword_index() { rl::select_workspace_free(ws); }
 };
 
+// ---- native encoder forward (include/raglite_hip.h; kernels in encoder.hip, entry points in api_ingest.hip) -----------------------
+struct rl_encoder {
+    int32_t vocab = 0, hidden = 0, layers = 0, heads = 0, ffn = 0, max_positions = 0, type_vocab = 0, dtype = 0;
+    float eps = 0.f;
+    const void *tok = nullptr, *pos = nullptr, *typ = nullptr, *ln_w = nullptr, *ln_b = nullptr;  // borrowed, like everything in `layer`
+    struct Layer { const void *qkv_w, *qkv_b, *out_w, *out_b, *ln1_w, *ln1_b, *up_w, *up_b, *down_w, *down_b, *ln2_w, *ln2_b; };
+    std::vector<Layer> layer;
+    int32_t ksplit = 1;           // the larger of the out and down projections' K slices: what `part` of the scratch is sized by
+    std::mutex mu;
+    rl::Pool scratch;             // rl::EncoderScratch over RL_ENCODER_MAX_TOKENS rows; every call walks a prefix of it
+    rl::LastStream last_stream;
+};
+
 namespace rl {
 
 // The process-wide default of a route option (api.hip keeps the table and its mutex to itself).
