@@ -26,8 +26,8 @@
 //     re-loaded right after its four MFMAs -- through inline asm, waited for by COUNT (LDS reads return in order);
 //   * ONE workgroup barrier per slab, HALF-WAY through it; waves 4-7 issue every fragment read one MFMA group later than their SIMD
 //     partners (LAG), so one wave's LDS instructions sit beside the partner's MFMAs instead of beside the partner's own;
-//   * tile epilogue in REGISTERS (the comment in front of it has the steps): ~93 VALU instructions per 16-row block, no LDS traffic but
-//     the staged results.
+//   * tile epilogue in REGISTERS (the comment in front of it has the steps): 88 VALU instructions per 16-row block, 71 under the tile
+//     loop of MODE 3 (profiles/pp_tile_loop_isa.txt), no LDS traffic but the staged results.
 // Deterministic (fixed MFMA order per (query vector, row), fixed sum tree over the query vectors; independent of the grid);
 // integer-valued data is exact.  Same products and the same sums over K as maxsim_gemm_kernel's one-product pass; the 32 per-vector maxima
 // are added in another order: scores agree to the last bits, not bit for bit, on float data.  Needs an index without empty chunks (a chunk
@@ -147,8 +147,13 @@ struct PpRows {
 };
 
 // DBG: timing skeletons (experiment builds only, -DRAGLITE_EXPERIMENTS + RAGLITE_PP_DBG / RAGLITE_PP_ROWS_DBG; WRONG results):
-// 2 = no MFMAs, 8 = no LDS fragment reads, 16 = no corpus DMAs, 32 = no query loads, 128 = no block epilogues (the MFMAs stay).
+// 2 = no MFMAs, 8 = no LDS fragment reads, 16 = no corpus DMAs, 32 = no query loads, 128 = no block epilogues (the MFMAs stay); all on
+// MODE 0's slab-counting loop.
 // ROWNORM (MODE 2, cosine): the block-wide bound is only the PREFILTER; a group that passes it is tested row by row against T |e_row|.
+// MODE 3: MODE 0 -- same arguments, same arithmetic in the same order, same bits -- for an EVEN number of K slabs, with the tiles walked by an
+// explicit loop (the comment in front of the main loop): a tile's first slab multiplies into a zero C operand instead of accumulators the
+// epilogue zeroed, the block epilogues exist once per wave role instead of once per slab parity, and a tile's 128 chunk-end bits come by
+// one scalar load.
 template <int DBG, int MODE, bool ROWNORM>
 __global__ __launch_bounds__(512, 2) void maxsim_pp_kernel(const char* __restrict__ planes, int64_t n_rows, int32_t nslab,
                                                            const char* __restrict__ qfrag, const float* __restrict__ qmeta, int32_t n_q,
@@ -156,6 +161,8 @@ __global__ __launch_bounds__(512, 2) void maxsim_pp_kernel(const char* __restric
                                                            const uint32_t* __restrict__ ends_bits, float* __restrict__ out, int64_t out_stride,
                                                            float inv_e_scale, const uint32_t* __restrict__ run_if, PpRows rs) {
     constexpr bool ROWS = MODE == 2, SCORES = MODE == 1, GROUPS = ROWS || SCORES;  // GROUPS: a "query" of the tile is a group of 32 single-vector queries
+    constexpr bool TILES = MODE == 3;  // the explicit tile loop (nslab even)
+    static_assert(!TILES || DBG == 0, "the timing skeletons keep the slab-counting loop");
     __shared__ __attribute__((aligned(16))) char smem[PP_LDS];
     if (run_if && __builtin_amdgcn_readfirstlane((int)*run_if) == 0) return;  // whole grid: a guarded launch that is not needed
     const int lane = threadIdx.x & 63;
@@ -269,9 +276,20 @@ __global__ __launch_bounds__(512, 2) void maxsim_pp_kernel(const char* __restric
         constexpr int a = decltype(A_)::value;
         if constexpr (!(DBG & 8)) pp_read<a * 1024>(ef[a], rd_c + (uint32_t)(c_slot * PP_CSLOT));
     };
-    auto mfma_group = [&](f32x4 (&q)[4], auto A_) __attribute__((always_inline)) {
+    // FIRST: a tile's first slab -- C is the inline constant 0 (0 + x is x bit for bit), what the accumulators held is dead
+    auto mfma_group = [&](f32x4 (&q)[4], auto A_, auto FIRST_) __attribute__((always_inline)) {
         constexpr int A = decltype(A_)::value;
-        if constexpr (!(DBG & 2)) {
+        constexpr bool FIRST = decltype(FIRST_)::value;
+        if constexpr (FIRST && !(DBG & 2)) {
+            // Written out, with the accumulator as an in-out operand it does not read: the builtin with a constant C has a destination of
+            // its own, the allocator then gives a tile's first two slabs other registers than the pair loop, and pays for the moves between
+            // them with 172 bytes of scratch.  Tied like this the accumulators live where MODE 0's do.  Nothing the compiler's hazard
+            // checks would have to see: the operands come from loads (waited for by count), and the results are next read as the C of the
+            // same registers' MFMAs one slab later.
+#pragma unroll
+            for (int c = 0; c < 4; ++c)
+                asm volatile("v_mfma_f32_16x16x32_f16 %0, %1, %2, 0" : "+v"(acc[c >> 1][c & 1][A]) : "v"(ef[A]), "v"(q[c]));
+        } else if constexpr (!(DBG & 2)) {
             acc[0][0][A] = __builtin_amdgcn_mfma_f32_16x16x32_f16(pp_h(ef[A]), pp_h(q[0]), acc[0][0][A], 0, 0, 0);
             acc[0][1][A] = __builtin_amdgcn_mfma_f32_16x16x32_f16(pp_h(ef[A]), pp_h(q[1]), acc[0][1][A], 0, 0, 0);
             acc[1][0][A] = __builtin_amdgcn_mfma_f32_16x16x32_f16(pp_h(ef[A]), pp_h(q[2]), acc[1][0][A], 0, 0, 0);
@@ -313,10 +331,14 @@ __global__ __launch_bounds__(512, 2) void maxsim_pp_kernel(const char* __restric
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // this wave's own LDS writes
             const float* const b0 = reinterpret_cast<const float*>(smem + PP_DC * PP_CSLOT) + (2 * wv) * PP_STAGE;
             float* const g0 = out + (int64_t)(q_base + 2 * wv) * out_stride + ord_lo + own_flushed;
+            int ln = lane;
+            // (MODE 3: an opaque copy -- what the copy loops derive from the plain lane number is invariant in the tile loop, gets hoisted
+            // out of it and spilled)
+            if constexpr (TILES) asm volatile("" : "+v"(ln));
             if (has0)
-                for (int i = lane; i < n; i += 64) g0[i] = b0[i];
+                for (int i = ln; i < n; i += 64) g0[i] = b0[i];
             if (has1)
-                for (int i = lane; i < n; i += 64) g0[out_stride + i] = b0[PP_STAGE + i];
+                for (int i = ln; i < n; i += 64) g0[out_stride + i] = b0[PP_STAGE + i];
             own_flushed = own_cnt;
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // (rare: once per workgroup on RAGLite-shaped chunks)
         }
@@ -339,11 +361,32 @@ __global__ __launch_bounds__(512, 2) void maxsim_pp_kernel(const char* __restric
 #pragma unroll
             for (int qb = 0; qb < 2; ++qb) acc[q][qb][a] = (f32x4){0.f, 0.f, 0.f, 0.f};
     };
+    // MODE 3: the tile's 128 chunk-end bits by ONE scalar load, issued at the top of the tile's first slab (pp_tile_ends), waited for once in
+    // front of the first block epilogue.  A tile starts on a 16-row block, so its bits start at bit 0 or 16 of a word: five words, loaded as
+    // eight.  The bitmap is allocated and written 16 words past the corpus' last (chunk_ends_words), a tile starts inside the corpus, and the
+    // load ends 7 words after the tile's first: inside the bitmap for every tile.  Invisible to the compiler's lgkmcnt bookkeeping like the
+    // fragment reads (a wait of its own making would drain them): scalar loads return out of order, but a counted wait that also counts this
+    // load is only ever STRICTER for the LDS reads in front of it.
+    typedef uint32_t u32x8s __attribute__((ext_vector_type(8)));
+    [[maybe_unused]] u32x8s tile_ends = {};
+    [[maybe_unused]] const uint32_t ends_shift = (uint32_t)org & 16u;  // (the same for every tile of the workgroup)
+    [[maybe_unused]] auto pp_tile_ends = [&](int T) __attribute__((always_inline)) {
+        const uint32_t* const p = reinterpret_cast<const uint32_t*>(pp_uniform_i64(reinterpret_cast<int64_t>(ends_bits + ((org + T * PP_RT) >> 5))));
+        asm volatile("s_load_dwordx8 %0, %1, 0x0" : "=&s"(tile_ends) : "s"(p) : "memory");
+    };
+    // the 16 bits of block a: words w and w + 1 of the tile's eight, moved down by 0 or 16 bits
+    [[maybe_unused]] auto tile_ends_of = [&](auto A_) __attribute__((always_inline)) -> uint32_t {
+        constexpr int a = decltype(A_)::value;
+        const uint64_t pair = ((uint64_t)tile_ends[a / 2 + 1] << 32) | tile_ends[a / 2];
+        return (uint32_t)(pair >> (ends_shift + 16u * (a & 1))) & 0xffffu;
+    };
     [[maybe_unused]] auto block_epilogue_maxsim = [&](auto A_, int T) __attribute__((always_inline)) {
         constexpr int a = decltype(A_)::value;
         const int32_t base = org + T * PP_RT + 16 * a;
         // "last row of its chunk" bits of the block's 16 rows: half a word of the bitmap
-        const uint32_t E = (ends_bits[base >> 5] >> (base & 16)) & 0xffffu;
+        uint32_t E;
+        if constexpr (TILES) E = tile_ends_of(A_);
+        else E = (ends_bits[base >> 5] >> (base & 16)) & 0xffffu;
         float z[16];
 #pragma unroll
         for (int r = 0; r < 16; ++r) z[r] = acc[r >> 3][(r >> 2) & 1][a][r & 3];
@@ -423,7 +466,15 @@ __global__ __launch_bounds__(512, 2) void maxsim_pp_kernel(const char* __restric
             own_cnt += __builtin_popcount(EM);
         }
         ord_run += __builtin_popcount(E);
-        zero_block(A_);
+        if constexpr (!TILES) {
+            zero_block(A_);
+        } else {
+            // The next tile's first slab does not read them.  It names them as in-out operands all the same (mfma_group), and what it is
+            // handed is what the transposes and maxima above left in place: with the accumulators' own values it would be those that stay
+            // live, and every block would begin by copying its sixteen registers out of the way.
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[r >> 3][(r >> 2) & 1][a][r & 3] = z[r];
+        }
     };
 
     // MODE 2: threshold test of every accumulator of the block, records into the wave-private log.  Register (c = 2 q + qb, a, u), lane
@@ -704,9 +755,9 @@ __global__ __launch_bounds__(512, 2) void maxsim_pp_kernel(const char* __restric
             }
         }
     };
-    auto slab = [&](f32x4 (&q)[4], f32x4 (&qn)[4], auto LAG_) __attribute__((always_inline)) {
+    auto slab = [&](f32x4 (&q)[4], f32x4 (&qn)[4], auto LAG_, auto FIRST_) __attribute__((always_inline)) {
         constexpr bool LAG = decltype(LAG_)::value;
-        auto G = [&](auto A_) __attribute__((always_inline)) { mfma_group(q, A_); };
+        auto G = [&](auto A_) __attribute__((always_inline)) { mfma_group(q, A_, FIRST_); };
         auto R = [&](auto A_) __attribute__((always_inline)) { read_slab(A_); };
         // the query fragments of the next slab, then the corpus piece of slab g + PP_LC
         issue_qregs(qn);
@@ -742,8 +793,10 @@ __global__ __launch_bounds__(512, 2) void maxsim_pp_kernel(const char* __restric
             R(PP_I(7)); __builtin_amdgcn_sched_barrier(0);
         }
         c_slot = c_slot + 1 == PP_DC ? 0 : c_slot + 1;
-        tile_end();
-        if (++c_s == nslab) { c_s = 0; ++c_r; }
+        if constexpr (!TILES) {
+            tile_end();
+            if (++c_s == nslab) { c_s = 0; ++c_r; }
+        }
     };
     // LDS reads return in order: with the four reads of blocks 4-7 still outstanding, the four in front of them (blocks 0-3 of slab g + 1)
     // are real values now -- a wait that was served half a slab ago instead of one that exposes an LDS round trip under load at the end of
@@ -758,20 +811,52 @@ __global__ __launch_bounds__(512, 2) void maxsim_pp_kernel(const char* __restric
 
     // ---- prologue: C(0 .. LC - 1) and slab 0's query fragments landed; slab 0's corpus fragments ------------------------------------------
     for (int i = 0; i < PP_LC; ++i) issue_c();
-    issue_qregs(qA);
-    asm volatile("s_waitcnt vmcnt(0)\n\ts_barrier" ::: "memory");
-    [&]<int... A>(std::integer_sequence<int, A...>) { (read_slab(std::integral_constant<int, A>{}), ...); }
-    (std::make_integer_sequence<int, PP_NBLK>{});
-    c_slot = 1;
-    landed(qA);
+    // (the fragments -- MODE 3: inside the wave role, below; loaded in front of the fork they have to be in the same registers for both
+    // roles, and the allocator answers with 48 copies on one side and registers it holds for nothing through that side's whole loop)
+    auto prologue_fragments = [&]() __attribute__((always_inline)) {
+        issue_qregs(qA);
+        asm volatile("s_waitcnt vmcnt(0)\n\ts_barrier" ::: "memory");
+        [&]<int... A>(std::integer_sequence<int, A...>) { (read_slab(std::integral_constant<int, A>{}), ...); }
+        (std::make_integer_sequence<int, PP_NBLK>{});
+        c_slot = 1;
+        landed(qA);
+    };
+    if constexpr (!TILES) prologue_fragments();
     // ---- main loop: two slabs per iteration (two static sets of query fragment registers) -----------------------------------------
+    // MODE 3 (nslab even) walks the tiles instead of counting slabs: the same slabs in the same order with the same waits, but a tile's
+    // first slab stands in straight-line position at the head of the tile loop (no per-slab test selects it: a wave-uniform branch inside
+    // the K loop cost 4-5 %) and its eight block epilogues behind the pair loop -- one copy per wave role, where the
+    // slab-counting loop has one per slab parity and tests `c_s == nslab - 1` every slab.  The two back edges are the only joins.
     auto main_loop = [&](auto LAG_) __attribute__((always_inline)) {
-        for (int g = 0; g < total; g += 2) {
-            slab(qA, qB, LAG_);
-            landed(qB);
-            if (g + 1 < total) {
-                slab(qB, qA, LAG_);
+        if constexpr (TILES) {
+            const int pairs = nslab >> 1;
+            prologue_fragments();
+            for (int t = 0; t < nt; ++t) {
+                pp_tile_ends(t);
+                slab(qA, qB, LAG_, std::true_type{});
+                landed(qB);
+                slab(qB, qA, LAG_, std::false_type{});
                 landed(qA);
+#pragma nounroll
+                for (int p = 1; p < pairs; ++p) {
+                    slab(qA, qB, LAG_, std::false_type{});
+                    landed(qB);
+                    slab(qB, qA, LAG_, std::false_type{});
+                    landed(qA);
+                }
+                asm volatile("s_waitcnt lgkmcnt(0)" : "+s"(tile_ends) : : "memory");  // the tile's chunk-end bits
+                [&]<int... A>(std::integer_sequence<int, A...>) { (block_epilogue_maxsim(std::integral_constant<int, A>{}, t), ...); }
+                (std::make_integer_sequence<int, PP_NBLK>{});
+                if (own_cnt - own_flushed > PP_STAGE - PP_RT) flush_out();  // (a tile finishes at most PP_RT chunks)
+            }
+        } else {
+            for (int g = 0; g < total; g += 2) {
+                slab(qA, qB, LAG_, std::false_type{});
+                landed(qB);
+                if (g + 1 < total) {
+                    slab(qB, qA, LAG_, std::false_type{});
+                    landed(qA);
+                }
             }
         }
     };
@@ -816,26 +901,33 @@ int launch_maxsim_pp(const void* image, int64_t n_rows, int32_t dim, const void*
     const dim3 grid = schedule == 1 ? dim3((unsigned)(gx * passes)) : dim3((unsigned)gx, (unsigned)passes), blk(512);
     PpRows rs{};
     rs.xcd_passes = schedule == 1 ? xcd_passes : 8;
-#define RL_PP_LAUNCH(DBG_)                                                                                                                 \
-    hipLaunchKernelGGL((maxsim_pp_kernel<DBG_, 0, false>), grid, blk, 0, s, static_cast<const char*>(image), n_rows, nslab, qfrag, qmeta, n_q, row_to_chunk, \
+    // an even number of K slabs (dim % 64 == 0): the tile loop (MODE 3); odd: the slab-counting loop (MODE 0).  Same bits.
+#define RL_PP_LAUNCH(DBG_) RL_PP_LAUNCH_MODE(DBG_, 0)
+#define RL_PP_LAUNCH_MODE(DBG_, MODE_)                                                                                                     \
+    hipLaunchKernelGGL((maxsim_pp_kernel<DBG_, MODE_, false>), grid, blk, 0, s, static_cast<const char*>(image), n_rows, nslab, qfrag, qmeta, n_q, row_to_chunk, \
                        chunk_offsets, ends_bits, out, out_stride, 1.0f / split_scale, run_if, rs)
 #ifdef RAGLITE_EXPERIMENTS
     // Experiment builds only (libraglite_hip_exp.so, scripts/gpu_calls/): timing skeletons that skip parts of the kernel -- WRONG results;
     // RAGLITE_PP_HINT = 0 / 1 / 2 (none / nt / sc1), read at every launch, sets the corpus DMAs' cache hint (same results).
     const int force_hint = std::getenv("RAGLITE_PP_HINT") ? std::atoi(std::getenv("RAGLITE_PP_HINT")) : -1;
     if (force_hint >= PP_HINT_NONE && force_hint <= PP_HINT_SC1) rs.dma_hint = force_hint;
-    static const int dbg = std::getenv("RAGLITE_PP_DBG") ? std::atoi(std::getenv("RAGLITE_PP_DBG")) : 0;
+    // RAGLITE_PP_DBG = 1 (same results): the slab-counting loop where the tile loop would run -- read at every launch, so one process can
+    // time the two loops alternated.
+    const int dbg = std::getenv("RAGLITE_PP_DBG") ? std::atoi(std::getenv("RAGLITE_PP_DBG")) : 0;
     if (dbg == 2) RL_PP_LAUNCH(2);
     else if (dbg == 128) RL_PP_LAUNCH(128);
     else if (dbg == 136) RL_PP_LAUNCH(136);
     else if (dbg == 144) RL_PP_LAUNCH(144);
     else if (dbg == 160) RL_PP_LAUNCH(160);
     else if (dbg == 184) RL_PP_LAUNCH(184);
-    else RL_PP_LAUNCH(0);
+    else if (dbg == 1 || nslab % 2) RL_PP_LAUNCH(0);
+    else RL_PP_LAUNCH_MODE(0, 3);
 #else
-    RL_PP_LAUNCH(0);
+    if (nslab % 2) RL_PP_LAUNCH(0);
+    else RL_PP_LAUNCH_MODE(0, 3);
 #endif
 #undef RL_PP_LAUNCH
+#undef RL_PP_LAUNCH_MODE
     RL_HIP(hipGetLastError());
     return RL_OK;
 }
