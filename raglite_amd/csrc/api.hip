@@ -107,9 +107,18 @@ int scan_row_range(rl_index* idx, int64_t first, int64_t n, hipStream_t s) {
     return RL_OK;
 }
 
-// Scale of the corpus image the index should have: the split scale of an fp32 corpus, 1 for an fp16-stored one (its image is
-// the stored halves, permuted), 0 = no image.
-float image_scale(const rl_index* idx) { return idx->E16 ? 1.0f : idx->split_scale; }
+// ---- the index as the launchers see it (common.h: RowsRef, ChunkMap, Launch): the only code that reads these fields for a launch ----------
+// The stored rows.  Their scale is also the scale of the corpus image the index should have: the split scale of an fp32 corpus, 1 for an
+// fp16-stored one (its image is the stored halves, permuted), 0 = no image.
+rl::RowsRef rows(const rl_index* idx) {
+    return {idx->E16 ? (const void*)idx->E16 : (const void*)idx->E, idx->E16 != nullptr, idx->n_rows, idx->dim, idx->E16 ? 1.0f : idx->split_scale};
+}
+rl::RowsRef image(const rl_index* idx) { return {idx->planes.buf.p, idx->E16 != nullptr, idx->n_rows, idx->dim, rows(idx).scale}; }  // hi | lo planes; fp16 storage: one plane
+rl::RowsRef hi_image(const rl_index* idx) { return {idx->hi_image.buf.p, true, idx->n_rows, idx->dim, idx->split_scale}; }  // the hi halves in the image layout
+rl::RowsRef hi_plane(const rl_index* idx) { return {idx->hiplane.buf.p, true, idx->n_rows, idx->dim, idx->split_scale}; }   // ... row-major
+rl::ChunkMap chunks(const rl_index* idx) { return {idx->row_to_chunk, idx->offsets, idx->n_chunks, idx->ends.as<uint32_t>()}; }
+rl::Launch on(const rl_index* idx, hipStream_t s, const uint32_t* run_if = nullptr) { return {idx->n_cu, s, run_if}; }
+rl::RowMetric metric_of(const rl_index* idx, int mode) { return {mode, idx->norm, idx->sumsq}; }
 // Which of the three images (the records `planes`, `hi_image`, `hiplane`) may exist right now: all of them, or -- lazy images -- those some
 // call has asked for (demand_images)
 enum : uint32_t { IMG_PLANES = 1u, IMG_HI_IMAGE = 2u, IMG_HI_PLANE = 4u, IMG_ALL = 7u };
@@ -129,7 +138,7 @@ bool stream16_dim_ok(int32_t d) { return d == 128 || d == 256 || d == 384 || d =
 float sum_eps(int32_t d) { return 0x1p-12f * (float)((d + 1023) / 1024); }
 bool big_corpus(const rl_index* idx) { return (int64_t)idx->n_rows * idx->dim >= (int64_t(64) << 20); }
 
-bool image_valid(const rl_index* idx) { return idx->planes.covers(image_scale(idx), idx->n_rows); }
+bool image_valid(const rl_index* idx) { return idx->planes.covers(rows(idx).scale, idx->n_rows); }
 bool hi_valid(const rl_index* idx) { return idx->hiplane.covers(idx->split_scale, idx->n_rows); }
 bool hi_image_valid(const rl_index* idx) { return idx->hi_image.covers(idx->split_scale, idx->n_rows) && idx->norm_stats.measured(idx->n_rows); }
 // What the approximate MaxSim pass of a batch multiplies at ONE fp16 product per multiply: the image of the hi halves of an fp32 corpus --
@@ -139,8 +148,7 @@ bool approx_image_valid(const rl_index* idx) {
     if (!idx->E16) return hi_image_valid(idx);
     return image_valid(idx) && big_corpus(idx) && hi_dim_ok(idx->dim) && idx->norm_stats.measured(idx->n_rows);
 }
-const void* approx_image(const rl_index* idx) { return idx->E16 ? idx->planes.buf.p : idx->hi_image.buf.p; }
-float approx_scale(const rl_index* idx) { return idx->E16 ? 1.0f : idx->split_scale; }
+rl::RowsRef approx_image(const rl_index* idx) { return idx->E16 ? image(idx) : hi_image(idx); }
 // IMG_* bits of the images that cover the current rows
 uint32_t images_built(const rl_index* idx) {
     return (image_valid(idx) ? IMG_PLANES : 0u) | (hi_image_valid(idx) ? IMG_HI_IMAGE : 0u) | (hi_valid(idx) ? IMG_HI_PLANE : 0u);
@@ -193,7 +201,7 @@ int fold_row_norms(rl_index* idx, int64_t from, hipStream_t s) {
     ns.max_lo_ratio = w[2];
     ns.min_row_norm = w[3];
     ns.max_row_norm_rows = idx->n_rows;
-    ns.max_row_norm_scale = image_scale(idx);
+    ns.max_row_norm_scale = rows(idx).scale;
     return RL_OK;
 }
 
@@ -224,7 +232,7 @@ int refresh_hi_norms(rl_index* idx, hipStream_t s) {
 bool image_wanted(const rl_index* idx, uint32_t bit) {
     const int32_t d = idx->dim;
     if (!(image_need(idx) & bit) || idx->n_rows <= 0) return false;
-    if (bit == IMG_PLANES) return idx->opt.on(RL_OPT_KEEP_IMAGE) && (idx->E16 || idx->E) && image_scale(idx) > 0.f && d % 32 == 0 && d >= 32;
+    if (bit == IMG_PLANES) return idx->opt.on(RL_OPT_KEEP_IMAGE) && (idx->E16 || idx->E) && rows(idx).scale > 0.f && d % 32 == 0 && d >= 32;
     // Both HI images: big fp32 corpora in split arithmetic.  (round 4: independent of the pre-split image -- an index with RL_OPT_KEEP_IMAGE = 0
     // keeps rows + HI image, 1.5 x the corpus, and its MaxSim batches fall back to the streaming kernels over the rows)
     const bool hi = idx->opt.on(RL_OPT_KEEP_HI) && !idx->E16 && idx->E && idx->split_scale > 0.f && big_corpus(idx);
@@ -235,7 +243,7 @@ bool image_wanted(const rl_index* idx, uint32_t bit) {
            (idx->metric == RL_COSINE || idx->metric == RL_DOT || idx->metric == RL_L2);
 }
 
-// Builds / extends one image so that it covers rows [0, idx->n_rows) at image_scale(idx) (the HI images exist for fp32 rows only, where that
+// Builds / extends one image so that it covers rows [0, idx->n_rows) at rows(idx).scale (the HI images exist for fp32 rows only, where that
 // is the split scale), or releases it when it is not wanted.  Not having an image is never an error (the streaming kernels read the stored
 // rows): a device too full, an allocation failure, a launch that does not take the rows or a missing `ends` bitmap just leave it absent --
 // and only the first two mark it `no_room` (demand_images asks again later).  Synchronises the stream: build / append / compact only.
@@ -249,7 +257,7 @@ int refresh_image(rl_index* idx, uint32_t bit, hipStream_t s) {
         im.drop();
         return RL_OK;
     }
-    const float scale = image_scale(idx);
+    const float scale = rows(idx).scale;
     const int64_t cap = image_cap_rows(idx);
     const size_t need = tiled ? rl::planes_bytes(cap, d, bit == IMG_HI_IMAGE || idx->E16) : (size_t)cap * d * sizeof(uint16_t);
     int64_t first = im.scale == scale ? (tiled ? im.rows & ~int64_t(15) : im.rows) : 0;
@@ -263,9 +271,9 @@ int refresh_image(rl_index* idx, uint32_t bit, hipStream_t s) {
     }
     const int st = bit == IMG_HI_PLANE ? rl::launch_cast_f16_scaled(idx->E + (size_t)first * d, im.buf.as<uint16_t>() + (size_t)first * d,
                                                                     (n - first) * d, scale, s)
-                   : bit == IMG_HI_IMAGE ? rl::launch_presplit_hi_rows(idx->E, first, n, d, scale, im.buf.p, s)
-                   : idx->E16 ? rl::launch_preformat_rows16(idx->E16, first, n, d, im.buf.p, s)
-                              : rl::launch_presplit_rows(idx->E, first, n, d, scale, im.buf.p, s);
+                   : bit == IMG_HI_IMAGE ? rl::launch_presplit_hi_rows(rows(idx), first, im.buf.p, s)
+                   : idx->E16 ? rl::launch_preformat_rows16(rows(idx), first, im.buf.p, s)
+                              : rl::launch_presplit_rows(rows(idx), first, im.buf.p, s);
     if (st == RL_ERR_UNSUPPORTED) {  // e.g. caller-owned rows that are not 16-byte aligned
         im.drop();
         return RL_OK;
@@ -416,17 +424,16 @@ int rl_adapter_apply(const float* A, const float* queries, int32_t n_queries, in
     int dev = 0, n_cu = 256;
     RL_HIP(hipGetDevice(&dev));
     RL_HIP(hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev));
+    const RowsRef A_rows{d_a, false, dim, dim, 0.f};  // (the exact fp32 MFMA chain)
     if (n_queries >= GEMM_MIN_QUERIES) {  // cfg 5's B = 1000: one fp32 MFMA GEMM (score_gemm.hip)
-        const int st = launch_score_gemm(d_a, dim, dim, d_q, n_queries, d_res, dim, nullptr, nullptr, nullptr,
-                                         SCAN_RAW_DOT, n_cu, s);
+        const int st = launch_score_gemm(A_rows, d_q, n_queries, {d_res, dim}, RowMetric{}, nullptr, {n_cu, s});
         if (st == RL_OK) done = true; else if (st != RL_ERR_UNSUPPORTED) return st;
     }
     if (!done && n_queries > 4) {
         done = true;
         for (int32_t b0 = 0; b0 < n_queries && done; b0 += 32) {
             const int32_t nq = std::min<int32_t>(32, n_queries - b0);
-            const int st = launch_maxsim_stream(d_a, dim, dim, d_q + (int64_t)b0 * dim, nq, nullptr, nullptr, 0, 1,
-                                                d_res + (int64_t)b0 * dim, dim, n_cu, s);
+            const int st = launch_maxsim_stream(A_rows, {d_q + (int64_t)b0 * dim, nq}, ChunkMap{}, 1, {d_res + (int64_t)b0 * dim, dim}, {n_cu, s});
             if (st == RL_ERR_UNSUPPORTED) done = false; else RL_TRY(st);
         }
     }
@@ -910,8 +917,7 @@ int score_rows(rl_index* idx, const float* d_q, int32_t nb, int64_t ld, hipStrea
         // its one-plane image): no conversion in the loop
         if (idx->opt.on(RL_OPT_PLANES_GEMM)) {
             RL_TRY(idx->misc.reserve(score_planes_scratch_floats(nb, idx->dim) * sizeof(float)));
-            const int st = launch_score_planes(idx->planes.buf.p, idx->n_rows, idx->dim, d_q, nb, sc, ld, idx->norm, idx->sumsq,
-                                               idx->misc.as<float>(), mode, idx->n_cu, s, image_scale(idx), idx->E16 != nullptr);
+            const int st = launch_score_planes(image(idx), d_q, nb, {sc, ld}, metric_of(idx, mode), idx->misc.as<float>(), on(idx, s));
             if (st != RL_ERR_UNSUPPORTED) return st;
         }
     }
@@ -928,16 +934,13 @@ int score_rows(rl_index* idx, const float* d_q, int32_t nb, int64_t ld, hipStrea
         }
         for (int32_t b0 = 0; b0 < nb; b0 += 32) {
             const int32_t nq = std::min<int32_t>(32, nb - b0);
-            RL_TRY(launch_maxsim_stream16(idx->E16, idx->n_rows, idx->dim, d_q + (int64_t)b0 * idx->dim, nq,
-                                          idx->row_to_chunk, idx->offsets, idx->n_chunks, 1, sc + (int64_t)b0 * ld, ld,
-                                          idx->n_cu, s));
+            RL_TRY(launch_maxsim_stream(rows(idx), {d_q + (int64_t)b0 * idx->dim, nq}, chunks(idx), 1, {sc + (int64_t)b0 * ld, ld}, on(idx, s)));
         }
         return transform(sc, mode);
     }
     if (nb >= rows_gemm_min(idx)) {  // MFMA-bound regime: one 128 x 128-tiled GEMM instead of a corpus pass per 32 queries
         RL_TRY(idx->misc.reserve(score_gemm_scratch_floats(nb, idx->dim, idx->split_scale > 0.f) * sizeof(float)));
-        const int st = launch_score_gemm(idx->E, idx->n_rows, idx->dim, d_q, nb, sc, ld, idx->norm, idx->sumsq,
-                                         idx->misc.as<float>(), mode, idx->n_cu, s, idx->split_scale);
+        const int st = launch_score_gemm(rows(idx), d_q, nb, {sc, ld}, metric_of(idx, mode), idx->misc.as<float>(), on(idx, s));
         if (st != RL_ERR_UNSUPPORTED) return st;
     }
     // Small batches too: one LDS-DMA stream pass (16-query variant: half the MFMAs) + the 4-MB transform reads the
@@ -951,9 +954,7 @@ int score_rows(rl_index* idx, const float* d_q, int32_t nb, int64_t ld, hipStrea
         bool ok = true;
         for (int32_t b0 = 0; b0 < nb && ok; b0 += 32) {
             const int32_t nq = std::min<int32_t>(32, nb - b0);
-            const int st = launch_maxsim_stream(idx->E, idx->n_rows, idx->dim, d_q + (int64_t)b0 * idx->dim, nq,
-                                                idx->row_to_chunk, idx->offsets, idx->n_chunks, 1,
-                                                sc + (int64_t)b0 * ld, ld, idx->n_cu, s, idx->split_scale);
+            const int st = launch_maxsim_stream(rows(idx), {d_q + (int64_t)b0 * idx->dim, nq}, chunks(idx), 1, {sc + (int64_t)b0 * ld, ld}, on(idx, s));
             if (st == RL_ERR_UNSUPPORTED) ok = false; else RL_TRY(st);
         }
         if (ok) return transform(sc, mode);
@@ -989,9 +990,8 @@ int search_rows_fused(rl_index* idx, const float* d_q, int32_t B, int32_t k, flo
     const int mode = scan_mode(idx->metric);
     if (off || B < rows_gemm_min(idx) || k > 512 || (mode != SCAN_COSINE && mode != SCAN_DOT)) return RL_ERR_UNSUPPORTED;
     if (!image_valid(idx)) return RL_ERR_UNSUPPORTED;
-    const bool half = idx->E16 != nullptr;
-    const float img_scale = image_scale(idx);
     const int64_t n = idx->n_rows, T = (n + 255) / 256;
+    const RowMetric metric = metric_of(idx, mode);
     const int32_t cap = cap_env > 0 ? std::min(cap_env, MERGE_CAP) : MERGE_CAP;
     // Sample stride: ~k * stride rows per query reach the bound -- a third of a list on average (the fluctuation is
     // ~sqrt(k) * stride) -- and at least 8 sample tiles.  Measured at cfg 5 (same box): stride 27 (this rule) 7.50 ms, 20: 7.67
@@ -1014,20 +1014,17 @@ int search_rows_fused(rl_index* idx, const float* d_q, int32_t B, int32_t k, flo
     // ---- (1) sample pass + its exact top-k --------------------------------------------------------------------------------------
     RL_TRY(launch_score_planes_queries(d_q, B, idx->dim, qs, mode, s));
     // (rows past the corpus in the last sampled tile: the pass writes them as -inf itself)
-    RL_TRY(launch_score_planes_pass(idx->planes.buf.p, n, idx->dim, B, qs, S_s, ld_s, idx->norm, idx->sumsq, mode, stride, nullptr, nullptr,
-                                    idx->n_cu, s, img_scale, half));
+    RL_TRY(launch_score_planes_pass(image(idx), B, qs, {S_s, ld_s}, metric, {stride}, on(idx, s)));
     RL_TRY(launch_topk(S_s, B, ld_s, ld_s, k, idx->ws, top_s, top_i, s));
     // ---- (2) full pass keeping what reaches the bound ---------------------------------------------------------------------------
     RL_HIP(hipMemsetAsync(cnt, 0, ((size_t)B + 1) * sizeof(uint32_t), s));  // list lengths + the overflow flag; the lists need no fill
     const CandArgs ca{top_s + (k - 1), k, c_s, c_i, cnt, flag, cap};
     idx->filt = {RL_FILTER_ROWS_FUSED, B, cap, cnt, flag};
-    RL_TRY(launch_score_planes_pass(idx->planes.buf.p, n, idx->dim, B, qs, nullptr, 0, idx->norm, idx->sumsq, mode, 1, nullptr, &ca, idx->n_cu, s,
-                                    img_scale, half));
+    RL_TRY(launch_score_planes_pass(image(idx), B, qs, Scores{}, metric, {1, &ca}, on(idx, s)));
     // ---- (3) exact ranking of every list ------------------------------------------------------------------------------------------
     RL_TRY(launch_merge_topk(c_s, c_i, 1, B, cap, k, d_scores, d_rows, s, cnt));
     // ---- (4) guarded dense fallback -----------------------------------------------------------------------------------------------
-    RL_TRY(launch_score_planes_pass(idx->planes.buf.p, n, idx->dim, B, qs, sc, ld, idx->norm, idx->sumsq, mode, 1, flag, nullptr, idx->n_cu, s,
-                                    img_scale, half));
+    RL_TRY(launch_score_planes_pass(image(idx), B, qs, {sc, ld}, metric, ScorePass{}, on(idx, s, flag)));
     RL_TRY(launch_guarded_select(sc, B, n, ld, k, nullptr, nullptr, nullptr, 0, SCAN_RAW_DOT, 1.0f, d_scores, d_rows, flag, s));
     return RL_OK;
 }
@@ -1074,18 +1071,17 @@ int search_rows_fused_hi(rl_index* idx, const float* d_q, int32_t B, int32_t k, 
     Q.lay(Carver(qs), B, idx->dim);
     const float *const q_unscale = Q.unscale, *const q_sumsq = Q.q_sumsq;
     float* sc = idx->scores.as<float>();  // [B x ld], reserved by the caller: only the fallback touches it
-    const void* hi = idx->hi_image.buf.p;
-    const float sscale = idx->split_scale;
+    const RowsRef hi = hi_image(idx);
+    const RowMetric metric = metric_of(idx, mode);
     // ---- (1) sample pass + its exact top-k ------------------------------------------------------------------------------------
     RL_TRY(launch_score_planes_queries(d_q, B, idx->dim, qs, mode, s, flag));  // (also zeroes the flag)
     // (round 5: on the sixteen-group tile of maxsim_pp.hip, MODE 1 -- the eight-group kernel gives every workgroup ONE 256 x 256 tile and is
     // start-up bound there; RL_OPT_FUSED_PP_SAMPLE = 0 or shapes outside the tile: the eight-group kernel)
     int st_sample = RL_ERR_UNSUPPORTED;
     if (idx->opt.on(RL_OPT_FUSED_PP) && idx->opt.on(RL_OPT_FUSED_PP_SAMPLE) && hi_only && idx->dim % 32 == 0 && idx->dim >= 256)
-        st_sample = launch_pp_rows_sample(hi, n, idx->dim, B, qs, idx->norm, mode, S_s, ld_s, stride, idx->n_cu, s, sscale);
+        st_sample = launch_pp_rows_sample(hi, B, qs, metric, {S_s, ld_s}, stride, on(idx, s));
     if (st_sample == RL_ERR_UNSUPPORTED)
-        st_sample = launch_score_planes_pass(hi, n, idx->dim, B, qs, S_s, ld_s, idx->norm, idx->sumsq, mode, stride, nullptr, nullptr, idx->n_cu, s, sscale,
-                                             true, hi_only);
+        st_sample = launch_score_planes_pass(hi, B, qs, {S_s, ld_s}, metric, {stride, nullptr, hi_only}, on(idx, s));
     RL_TRY(st_sample);
     RL_TRY(launch_topk(S_s, B, ld_s, ld_s, k, idx->ws, top_s, top_i, s));
     // ---- (2) thresholds lowered by the error band; candidate pass ---------------------------------------------------------------
@@ -1114,8 +1110,7 @@ int search_rows_fused_hi(rl_index* idx, const float* d_q, int32_t B, int32_t k, 
         row_test = mode == SCAN_COSINE && !(idx->norm_stats.min_row_norm * 4.0f >= idx->norm_stats.max_row_norm);
         round1_tiles = (Tr >= 64 && idx->opt.on(RL_OPT_FUSED_TWO_ROUNDS)) ? (3 * Tr) / 16 : 0;  // (small corpora: one round)
         if (round1_tiles > 0) {
-            st_pp = launch_pp_rows_pass(hi, n, idx->dim, B, qs, idx->norm, mode, &ca, idx->pp_work.p, log_cap, idx->n_cu, s, sscale, 0, round1_tiles, false,
-                                        row_test);
+            st_pp = launch_pp_rows_pass(hi, B, qs, metric, &ca, {idx->pp_work.p, log_cap, 0, round1_tiles, false, row_test}, on(idx, s));
             if (st_pp == RL_OK) {
                 if (idx->opt.on(RL_OPT_LIST_SELECT)) {  // (round 5: the k-th best of every list by a radix select, threshold raised in the same launch)
                     RL_TRY(launch_list_raise_threshold(c_s, c_i, B, cap, k, cnt, window, thr, s));
@@ -1123,16 +1118,15 @@ int search_rows_fused_hi(rl_index* idx, const float* d_q, int32_t B, int32_t k, 
                     RL_TRY(launch_merge_topk(c_s, c_i, 1, B, cap, k, top_s, top_i, s, cnt));  // (top_s / top_i: the sample's top-k is not needed any more)
                     RL_TRY(launch_raise_threshold(thr, top_s, B, k, window, s));
                 }
-                st_pp = launch_pp_rows_pass(hi, n, idx->dim, B, qs, idx->norm, mode, &ca, idx->pp_work.p, log_cap, idx->n_cu, s, sscale, round1_tiles,
-                                            Tr - round1_tiles, true, row_test);
+                st_pp = launch_pp_rows_pass(hi, B, qs, metric, &ca, {idx->pp_work.p, log_cap, round1_tiles, Tr - round1_tiles, true, row_test}, on(idx, s));
             }
         } else {
-            st_pp = launch_pp_rows_pass(hi, n, idx->dim, B, qs, idx->norm, mode, &ca, idx->pp_work.p, log_cap, idx->n_cu, s, sscale, 0, -1, false, row_test);
+            st_pp = launch_pp_rows_pass(hi, B, qs, metric, &ca, {idx->pp_work.p, log_cap, 0, -1, false, row_test}, on(idx, s));
         }
         if (st_pp != RL_OK && st_pp != RL_ERR_UNSUPPORTED) return st_pp;
     }
     if (st_pp != RL_OK)
-        RL_TRY(launch_score_planes_pass(hi, n, idx->dim, B, qs, nullptr, 0, idx->norm, idx->sumsq, mode, 1, nullptr, &ca, idx->n_cu, s, sscale, true, hi_only));
+        RL_TRY(launch_score_planes_pass(hi, B, qs, Scores{}, metric, {1, &ca, hi_only}, on(idx, s)));
     {
         auto& r = idx->replay;
         r.valid = true; r.pp = st_pp == RL_OK; r.B = B; r.mode = mode; r.qs = qs; r.ca = ca; r.cnt = cnt; r.thr1 = thr1; r.round1_tiles = round1_tiles; r.row_test = row_test;
@@ -1145,8 +1139,7 @@ int search_rows_fused_hi(rl_index* idx, const float* d_q, int32_t B, int32_t k, 
     RL_TRY(launch_row_dots(idx->E, idx->dim, d_q, B, r_i, cnt2, cap2, mode, idx->norm, q_sumsq, r_s, s));
     RL_TRY(launch_merge_topk(r_s, r_i, 1, B, cap2, k, d_scores, d_rows, s, cnt2));
     // ---- (5) guarded dense fallback (full precision, over the pre-split image) ------------------------------------------------------
-    RL_TRY(launch_score_planes_pass(idx->planes.buf.p, n, idx->dim, B, qs, sc, ld, idx->norm, idx->sumsq, mode, 1, flag, nullptr, idx->n_cu, s,
-                                    image_scale(idx), false));
+    RL_TRY(launch_score_planes_pass(image(idx), B, qs, {sc, ld}, metric, ScorePass{}, on(idx, s, flag)));
     // (its selection in ONE guarded launch, a block per query: the three launches of the selection, each a grid of 64 x B workgroups that return
     // at once behind the flag, were 36 us of every 1000-query batch)
     RL_TRY(launch_guarded_select(sc, B, n, ld, k, nullptr, nullptr, nullptr, 0, SCAN_RAW_DOT, 1.0f, d_scores, d_rows, flag, s));
@@ -1208,8 +1201,7 @@ int search_rows_hi(rl_index* idx, const float* d_q, int32_t nb, int32_t k, float
     float* sc = idx->scores.as<float>();
     // ---- (1) approximate pass over the HI plane ---------------------------------------------------------------------------------------------
     int st = wide ? launch_scan_rows16(idx->hiplane.buf.as<uint16_t>(), n, dim, d_q, nb, nullptr, SCAN_RAW_DOT, sc, ld, s)
-                  : launch_maxsim_stream16(idx->hiplane.buf.as<uint16_t>(), n, dim, d_q, nb, idx->row_to_chunk, idx->offsets, idx->n_chunks, 1, sc, ld,
-                                           idx->n_cu, s);
+                  : launch_maxsim_stream(hi_plane(idx), {d_q, nb}, chunks(idx), 1, {sc, ld}, on(idx, s));
     if (st != RL_OK) return st;
     // ---- (2) its exact top-k, and every row that could be in the exact top-k of the full-precision scores ----------------------------------
     // The bound: what the HI halves drop is known exactly per row -- max |e_lo| / |e| (cosine) and max |e_lo| (dot) are kept by the
@@ -1273,7 +1265,7 @@ int search_rows_hi(rl_index* idx, const float* d_q, int32_t nb, int32_t k, float
         st = launch_scan_rows(G, nc, dim, d_q, nb, nullptr, SCAN_RAW_DOT, xs, ldx, s);
         if (st == RL_OK) st = launch_scan_rows(idx->E, n, dim, d_q, nb, nullptr, SCAN_RAW_DOT, sc, ld, s, flag);
     } else {
-        st = launch_maxsim_stream_two(G, nc, dim, d_q, nb, idx->row_to_chunk, idx->offsets, idx->n_chunks, xs, ldx, idx->n_cu, s, idx->split_scale, full);
+        st = launch_maxsim_stream_two({G, false, nc, dim, idx->split_scale}, {d_q, nb}, chunks(idx), {xs, ldx}, on(idx, s), full);
     }
     if (st != RL_OK) {  // (a late decline: the route did not answer -- whoever does records itself)
         idx->filt = {};
@@ -1721,7 +1713,7 @@ int pairs_prepare(rl_index* idx, const float* d_q, int32_t nq, int64_t q_stride,
     const int32_t d = idx->dim;
     if (d != 128 && d != 256 && d != 384 && d != 512 && d != 768 && d != 1024) return RL_ERR_UNSUPPORTED;
     RL_TRY(idx->qsplit.reserve(query_split_bytes(d, n_queries)));
-    return launch_query_split(d_q, d, nq, q_stride, n_queries, idx->qsplit.as<char>(), idx->E16 != nullptr, s);
+    return launch_query_split({d_q, nq, q_stride, n_queries}, d, idx->qsplit.p, idx->E16 != nullptr, s);
 }
 
 int pairs_pass(rl_index* idx, int32_t nq, int32_t n_queries, int32_t first, float* d_out, int64_t out_stride, hipStream_t s) {
@@ -1729,9 +1721,7 @@ int pairs_pass(rl_index* idx, int32_t nq, int32_t n_queries, int32_t first, floa
         RL_TRY(launch_fill_f32(d_out, -std::numeric_limits<float>::infinity(), idx->n_chunks, s));
         RL_TRY(launch_fill_f32(d_out + out_stride, -std::numeric_limits<float>::infinity(), idx->n_chunks, s));
     }
-    return launch_maxsim_stream2(idx->E16 ? (const void*)idx->E16 : (const void*)idx->E, idx->E16 != nullptr, idx->n_rows, idx->dim,
-                                 idx->qsplit.as<char>(), n_queries, first, nq, idx->row_to_chunk, idx->offsets, idx->n_chunks, d_out,
-                                 out_stride, idx->n_cu, s, idx->split_scale);
+    return launch_maxsim_stream2(rows(idx), {idx->qsplit.p, n_queries, first, 2, nq}, chunks(idx), {d_out, out_stride}, on(idx, s));
 }
 
 // Batched MaxSim over the pre-split corpus image scores EIGHT queries per corpus pass (maxsim_gemm.hip).  gemm_prepare lays
@@ -1764,11 +1754,11 @@ int gemm_prepare(rl_index* idx, const float* d_q, int32_t nq, int64_t q_stride, 
     if (want_planes || !hi_route || fell_back || (!image_valid(idx) && !slim_batch_ok(idx, d_q))) RL_TRY(demand_images(idx, IMG_PLANES, s));
     if (!(image_valid(idx) || slim_batch_ok(idx, d_q))) return RL_ERR_UNSUPPORTED;
     RL_TRY(idx->qplanes.reserve(query_planes_bytes(idx->dim, n_queries)));
-    return launch_query_planes(d_q, idx->dim, nq, q_stride, n_queries, idx->qplanes.p, s, zero_words, zero_words ? 16 : 0);
+    return launch_query_planes({d_q, nq, q_stride, n_queries}, idx->dim, idx->qplanes.p, s, zero_words, zero_words ? 16 : 0);
 }
 int gemm_pass(rl_index* idx, int32_t nq, int32_t n_queries, int32_t first, int32_t n_q, float* d_out, int64_t out_stride, hipStream_t s) {
-    return launch_maxsim_gemm(idx->planes.buf.p, idx->n_rows, idx->dim, idx->qplanes.p, n_queries, first, n_q, nq, idx->row_to_chunk,
-                              idx->offsets, idx->ends.as<uint32_t>(), d_out, out_stride, idx->n_cu, s, image_scale(idx), idx->E16 != nullptr);
+    return launch_maxsim_gemm(image(idx), {idx->qplanes.p, n_queries, first, n_q, nq}, chunks(idx), {d_out, out_stride}, on(idx, s),
+                              /*hi_only*/ false, /*all_passes*/ false);
 }
 
 int maxsim_scores_device(rl_index* idx, const float* d_q, int32_t nq, float* d_out, hipStream_t s) {
@@ -1779,8 +1769,7 @@ int maxsim_scores_device(rl_index* idx, const float* d_q, int32_t nq, float* d_o
     if (idx->n_rows == 0) return RL_OK;
     if (idx->E16 && idx->dim > 1024) {  // a wide fp16-stored index: the exact re-scoring kernel over every chunk (empty chunks: -inf)
         if (nq > 32) return fail(RL_ERR_UNSUPPORTED, "MaxSim over an fp16-stored index wider than 1024 takes up to 32 query vectors");
-        st = launch_maxsim_pairs_all_wide(reinterpret_cast<const float*>(idx->E16), idx->dim, d_q, nq, (int64_t)nq * idx->dim, idx->offsets, idx->n_chunks, 1,
-                                          d_out, idx->n_chunks, s, nullptr, true);
+        st = launch_maxsim_pairs_all_wide(rows(idx), {d_q, nq, (int64_t)nq * idx->dim, 1}, chunks(idx), {d_out, idx->n_chunks}, on(idx, s));
         if (st == RL_ERR_UNSUPPORTED) return fail(st, "MaxSim: query vectors must be 16-byte aligned on an fp16-stored index wider than 1024");
         return st;
     }
@@ -1788,17 +1777,13 @@ int maxsim_scores_device(rl_index* idx, const float* d_q, int32_t nq, float* d_o
     for (int32_t v0 = 0; v0 < nq; v0 += 32) {
         const int32_t nv = std::min<int32_t>(32, nq - v0);
         const float* qv = d_q + (int64_t)v0 * idx->dim;
-        const int64_t accumulate = v0 > 0 ? 1 : 0;
-        st = idx->E16 ? launch_maxsim_stream16(idx->E16, idx->n_rows, idx->dim, qv, nv, idx->row_to_chunk, idx->offsets,
-                                               idx->n_chunks, 0, d_out, accumulate, idx->n_cu, s)
-                      : launch_maxsim_stream(idx->E, idx->n_rows, idx->dim, qv, nv, idx->row_to_chunk, idx->offsets,
-                                             idx->n_chunks, 0, d_out, accumulate, idx->n_cu, s, idx->split_scale);
+        const int64_t accumulate = v0 > 0 ? 1 : 0;  // (mode 0 reads `ld` as: add to what `out` holds)
+        st = launch_maxsim_stream(rows(idx), {qv, nv}, chunks(idx), 0, {d_out, accumulate}, on(idx, s));
         if (st != RL_OK) break;
     }
     if (idx->E16 && st == RL_ERR_UNSUPPORTED) return fail(st, "MaxSim: unsupported shape for an fp16-stored index");
     if (st == RL_ERR_UNSUPPORTED)
-        st = launch_maxsim_generic(idx->E, idx->dim, d_q, nq, (int64_t)nq * idx->dim, idx->offsets, nullptr,
-                                   idx->n_chunks, 1, d_out, s);
+        st = launch_maxsim_generic(rows(idx), {d_q, nq, (int64_t)nq * idx->dim, 1}, chunks(idx), nullptr, idx->n_chunks, d_out, s);
     return st;
 }
 
@@ -1913,14 +1898,12 @@ int hi_batch_approx(rl_index* idx, const float* d_q, int32_t nq, int32_t n_queri
     const bool pp = hb.one_product && idx->dim >= 256 && idx->opt.on(RL_OPT_PP_PASS);
     // (round 4: ONE launch for all of the batch's passes -- grid row = pass -- so that a pass starts on the CUs the previous one leaves)
     if (pp)
-        RL_TRY(launch_maxsim_pp(approx_image(idx), idx->n_rows, idx->dim, idx->qplanes.p, n_queries, 0, n_gemm, nq, idx->row_to_chunk,
-                                idx->offsets, idx->ends.as<uint32_t>(), sc, ld, idx->n_cu, s, approx_scale(idx), nullptr,
+        RL_TRY(launch_maxsim_pp(approx_image(idx), {idx->qplanes.p, n_queries, 0, n_gemm, nq}, chunks(idx), {sc, ld}, on(idx, s),
                                 (int)idx->opt.v[RL_OPT_PP_SCHEDULE], (int)idx->opt.v[RL_OPT_PP_XCD_PASSES]));
     for (int32_t b = 0; !pp && b < n_gemm; b += GEMM_PASS_QUERIES) {
         const int32_t n_q = std::min<int32_t>(GEMM_PASS_QUERIES, n_gemm - b);
-        RL_TRY(launch_maxsim_gemm(approx_image(idx), idx->n_rows, idx->dim, idx->qplanes.p, n_queries, b, n_q, nq, idx->row_to_chunk,
-                                  idx->offsets, idx->ends.as<uint32_t>(), sc + (int64_t)b * ld, ld, idx->n_cu, s, approx_scale(idx), true,
-                                  nullptr, hb.one_product));
+        RL_TRY(launch_maxsim_gemm(approx_image(idx), {idx->qplanes.p, n_queries, b, n_q, nq}, chunks(idx), {sc + (int64_t)b * ld, ld}, on(idx, s),
+                                  /*hi_only*/ hb.one_product, /*all_passes*/ false));
     }
     RL_TRY(mask_chunk_scores(idx, sc, n_gemm, ld, hb.filter, s));  // tombstones (and filtered-out chunks) never become candidates
     // (a handful of queries over more chunks than the one-block selection takes: crowded MaxSim scores send the radix selection down its slow path
@@ -1938,9 +1921,7 @@ int hi_batch_fallback(rl_index* idx, const float* d_q, int32_t nq, int32_t n_que
                       const HiBatch& hb, float* d_s, int32_t* d_c, hipStream_t s, bool rows_only = false);
 int hi_batch_rescore(rl_index* idx, const float* d_q, int32_t nq, int32_t n_queries, int32_t n_gemm, int32_t k, float* sc, int64_t ld,
                      const HiBatch& hb, float* d_s, int32_t* d_c, hipStream_t s, bool rows_only = false) {
-    const size_t q_elems = (size_t)nq * idx->dim;
-    const float* rows = idx->E16 ? reinterpret_cast<const float*>(idx->E16) : idx->E;
-    const bool rows16 = idx->E16 != nullptr;
+    const QueryVecs q{d_q, nq, (int64_t)nq * idx->dim, n_gemm};
     idx->filt = {RL_FILTER_MAXSIM_BATCH, n_gemm, hb.cap, hb.cnt, hb.flag};
     const int packed = (int)idx->opt.v[RL_OPT_PAIRS_PACKED];
     const bool m_from_qsum = !hb.m_ready && hb.qsum != nullptr;
@@ -1950,7 +1931,7 @@ int hi_batch_rescore(rl_index* idx, const float* d_q, int32_t nq, int32_t n_quer
         // exact scores bounds the k-th best overall from below, so a candidate needs approx >= that - m instead of (k-th approx) - 2 m: about
         // half as many chunks beyond the top-k to re-score.  The approximate top-k becomes the head of the list; the collection appends only
         // what ranks below it, and only those entries are scored by the second launch.
-        RL_TRY(launch_maxsim_pairs(rows, idx->dim, d_q, nq, (int64_t)q_elems, idx->offsets, hb.ti, k, n_gemm, hb.es_top, s, rows16, 0, 0, packed));
+        RL_TRY(launch_maxsim_pairs(rows(idx), q, chunks(idx), {hb.ti, k, 0, 0, packed}, hb.es_top, s));
         if (m_from_qsum)  // (also fills the lists' tails with -1)
             RL_TRY(launch_exact_threshold(hb.es_top, hb.ti, n_gemm, k, hb.m, hb.cap, hb.thr, hb.cnt, hb.ci, hb.es, hb.flag, s, hb.qsum, hb.m_abs,
                                           idx->norm_stats.max_row_norm + idx->norm_stats.max_lo_norm, hb.one_product, hb.ts));
@@ -1958,32 +1939,31 @@ int hi_batch_rescore(rl_index* idx, const float* d_q, int32_t nq, int32_t n_quer
             RL_TRY(launch_exact_threshold(hb.es_top, hb.ti, n_gemm, k, hb.m, hb.cap, hb.thr, hb.cnt, hb.ci, hb.es, hb.flag, s, nullptr, 0.f, 0.f, false, hb.ts));
         RL_TRY(launch_collect_above(sc, n_gemm, idx->n_chunks, ld, hb.thr, nullptr, hb.cap, hb.ci, nullptr, hb.cnt, hb.flag, s, hb.ts, hb.ti, k));
         if (hb.cap > k)
-            RL_TRY(launch_maxsim_pairs(rows, idx->dim, d_q, nq, (int64_t)q_elems, idx->offsets, hb.ci, hb.cap - k, n_gemm, hb.es, s, rows16, hb.cap, k, packed));
+            RL_TRY(launch_maxsim_pairs(rows(idx), q, chunks(idx), {hb.ci, hb.cap - k, hb.cap, k, packed}, hb.es, s));
     } else {
         RL_HIP(hipMemsetAsync(hb.ci, 0xff, (size_t)n_gemm * hb.cap * sizeof(int32_t), s));  // unused slots: -1 = "no chunk"
         RL_TRY(launch_collect_above(sc, n_gemm, idx->n_chunks, ld, hb.thr, nullptr, hb.cap, hb.ci, nullptr, hb.cnt, hb.flag, s));
-        RL_TRY(launch_maxsim_pairs(rows, idx->dim, d_q, nq, (int64_t)q_elems, idx->offsets, hb.ci, hb.cap, n_gemm, hb.es, s, rows16, 0, 0, packed));
+        RL_TRY(launch_maxsim_pairs(rows(idx), q, chunks(idx), {hb.ci, hb.cap, 0, 0, packed}, hb.es, s));
     }
     RL_TRY(launch_merge_topk(hb.es, hb.ci, 1, n_gemm, hb.cap, k, d_s, d_c, s, hb.cnt));
     return hi_batch_fallback(idx, d_q, nq, n_queries, n_gemm, k, sc, ld, hb, d_s, d_c, s, rows_only);
 }
 int hi_batch_fallback(rl_index* idx, const float* d_q, int32_t nq, int32_t n_queries, int32_t n_gemm, int32_t k, float* sc, int64_t ld,
                       const HiBatch& hb, float* d_s, int32_t* d_c, hipStream_t s, bool rows_only) {
-    const size_t q_elems = (size_t)nq * idx->dim;
+    const QueryVecs q{d_q, nq, (int64_t)nq * idx->dim, n_gemm};
     // list overflow / unusable bound: the full-precision passes, behind the flag -- ONE launch for all of them (gridDim.y = passes: sixteen
     // guarded launches that return at once were 0.08 ms of every 128-query step)
     // (no pre-split image: the streaming kernels over the rows, one launch with a grid row per query -- the same arithmetic, an order of
     // magnitude slower, and as rare)
     if (image_valid(idx) && !rows_only)
-        RL_TRY(launch_maxsim_gemm(idx->planes.buf.p, idx->n_rows, idx->dim, idx->qplanes.p, n_queries, 0, n_gemm, nq, idx->row_to_chunk, idx->offsets,
-                                  idx->ends.as<uint32_t>(), sc, ld, idx->n_cu, s, image_scale(idx), idx->E16 != nullptr, hb.flag, false, true));
+        RL_TRY(launch_maxsim_gemm(image(idx), {idx->qplanes.p, n_queries, 0, n_gemm, nq}, chunks(idx), {sc, ld}, on(idx, s, hb.flag),
+                                  /*hi_only*/ false, /*all_passes*/ true));
     else if (idx->dim > 1024)  // (a wide index: no streaming kernel -- the exact re-scoring kernel over EVERY chunk, behind the flag)
-        RL_TRY(launch_maxsim_pairs_all_wide(idx->E, idx->dim, d_q, nq, (int64_t)q_elems, idx->offsets, idx->n_chunks, n_gemm, sc, ld, s, hb.flag));
+        RL_TRY(launch_maxsim_pairs_all_wide(rows(idx), q, chunks(idx), {sc, ld}, on(idx, s, hb.flag)));
     else  // (grid row = query: with many queries a grid column of n_cu workgroups per query is 32 k workgroups that return at once behind the
           // flag -- 25 us of every step; n_cu / 8 columns keep the device as full when the passes do run and cost 3 us when they do not)
-        RL_TRY(launch_maxsim_stream_batch(idx->E, false, idx->n_rows, idx->dim, d_q, nq, (int64_t)q_elems, n_gemm, idx->row_to_chunk, idx->offsets,
-                                          idx->n_chunks, sc, ld, std::max(1, idx->n_cu / std::min<int32_t>(8, std::max<int32_t>(1, n_gemm / 4))), s,
-                                          idx->split_scale, hb.flag));
+        RL_TRY(launch_maxsim_stream_batch(rows(idx), q, chunks(idx), {sc, ld},
+                                          {std::max(1, idx->n_cu / std::min<int32_t>(8, std::max<int32_t>(1, n_gemm / 4))), s, hb.flag}));
     RL_TRY(mask_chunk_scores(idx, sc, n_gemm, ld, hb.filter, s));  // (harmless on scores nobody reads)
     // (the exact top-k of the fallback's scores in ONE guarded launch, a block per query -- select.hip: guarded_select_kernel -- instead of the
     // selection's three: what usually returns at once is one launch shorter by two)
@@ -2035,14 +2015,11 @@ int maxsim_few_hi_plane(rl_index* idx, const float* d_q, int32_t nq, int32_t n, 
     int st = RL_ERR_UNSUPPORTED;
     if (n == 2 && nq > 16 && idx->opt.on(RL_OPT_QUERY_PAIRS)) {  // two queries of 17..32 vectors share ONE pass over the plane
         RL_TRY(idx->qsplit.reserve(query_split_bytes(idx->dim, 2)));
-        st = launch_query_split(d_q, idx->dim, nq, q_elems, 2, idx->qsplit.as<char>(), true, s);
-        if (st == RL_OK)
-            st = launch_maxsim_stream2(idx->hiplane.buf.p, true, idx->n_rows, idx->dim, idx->qsplit.as<char>(), 2, 0, nq, idx->row_to_chunk, idx->offsets,
-                                       idx->n_chunks, sc, ld, idx->n_cu, s, 1.f);
+        st = launch_query_split({d_q, nq, q_elems, 2}, idx->dim, idx->qsplit.p, true, s);
+        if (st == RL_OK) st = launch_maxsim_stream2(hi_plane(idx), {idx->qsplit.p, 2, 0, 2, nq}, chunks(idx), {sc, ld}, on(idx, s));
     }
     if (st == RL_ERR_UNSUPPORTED)  // one pass per query, one launch (grid row = query)
-        st = launch_maxsim_stream_batch(idx->hiplane.buf.p, true, idx->n_rows, idx->dim, d_q, nq, q_elems, n, idx->row_to_chunk, idx->offsets,
-                                        idx->n_chunks, sc, ld, idx->n_cu, s, 0.f, nullptr);
+        st = launch_maxsim_stream_batch(hi_plane(idx), {d_q, nq, q_elems, n}, chunks(idx), {sc, ld}, on(idx, s));
     if (st != RL_OK) return st;
     HiBatch hb;
     hb.one_product = false;  // q_hi . e_hi + q_lo . e_hi: nothing of the query is dropped
@@ -2066,8 +2043,8 @@ int maxsim_few_hi_plane(rl_index* idx, const float* d_q, int32_t nq, int32_t n, 
             idx->filt = {RL_FILTER_MAXSIM_BATCH, n, hb.cap, hb.cnt, hb.flag};
             // (one candidate per wave here: the eight-wave kernel's 256-k blocks -- half as many dependent HBM round trips per tile -- suit it better
             // than the sixteen-wave variant's 128-k blocks, which pay when a wave has many tiles to pipeline)
-            RL_TRY(launch_maxsim_pairs(idx->E, idx->dim, d_q, nq, q_elems, idx->offsets, hb.ci, hb.cap, n, hb.es, s, false, 0, 0,
-                                       std::min<int>(1, (int)idx->opt.v[RL_OPT_PAIRS_PACKED])));
+            RL_TRY(launch_maxsim_pairs(rows(idx), {d_q, nq, q_elems, n}, chunks(idx),
+                                       {hb.ci, hb.cap, 0, 0, std::min<int>(1, (int)idx->opt.v[RL_OPT_PAIRS_PACKED])}, hb.es, s));
             RL_TRY(launch_merge_topk(hb.es, hb.ci, 1, n, hb.cap, k, d_s, d_c, s, hb.cnt));
             return hi_batch_fallback(idx, d_q, nq, n, n, k, sc, ld, hb, d_s, d_c, s, true);
         }
@@ -2340,17 +2317,16 @@ int rl_maxsim_approx_scores(rl_index* idx, const float* query_vecs, int32_t n_qu
     RL_TRY(st.out(out_scores, (size_t)n_queries * ld, &d_o));
     RL_TRY(st.out(out_bound, (size_t)n_queries, &d_b));  // (optional)
     RL_TRY(idx->qplanes.reserve(query_planes_bytes(idx->dim, n_queries)));
-    RL_TRY(launch_query_planes(d_q, idx->dim, nq, (int64_t)q_elems, n_queries, idx->qplanes.p, s));
+    RL_TRY(launch_query_planes({d_q, nq, (int64_t)q_elems, n_queries}, idx->dim, idx->qplanes.p, s, nullptr, 0));
     const int32_t per = kernel == 0 ? n_queries : GEMM_PASS_QUERIES;  // (the sixteen-query kernel takes all its passes in one launch)
     for (int32_t b = 0; b < n_queries; b += per) {
-        const int32_t n_q = std::min<int32_t>(per, n_queries - b);
+        const QueryImageRef q{idx->qplanes.p, n_queries, b, std::min<int32_t>(per, n_queries - b), nq};
+        const Scores out{d_o + (int64_t)b * ld, ld};
         if (kernel == 0)
-            RL_TRY(launch_maxsim_pp(approx_image(idx), idx->n_rows, idx->dim, idx->qplanes.p, n_queries, b, n_q, nq, idx->row_to_chunk, idx->offsets,
-                                    idx->ends.as<uint32_t>(), d_o + (int64_t)b * ld, ld, idx->n_cu, s, approx_scale(idx), nullptr,
-                                    (int)idx->opt.v[RL_OPT_PP_SCHEDULE], (int)idx->opt.v[RL_OPT_PP_XCD_PASSES]));
+            RL_TRY(launch_maxsim_pp(approx_image(idx), q, chunks(idx), out, on(idx, s), (int)idx->opt.v[RL_OPT_PP_SCHEDULE],
+                                    (int)idx->opt.v[RL_OPT_PP_XCD_PASSES]));
         else
-            RL_TRY(launch_maxsim_gemm(approx_image(idx), idx->n_rows, idx->dim, idx->qplanes.p, n_queries, b, n_q, nq, idx->row_to_chunk, idx->offsets,
-                                      idx->ends.as<uint32_t>(), d_o + (int64_t)b * ld, ld, idx->n_cu, s, approx_scale(idx), true, nullptr, true));
+            RL_TRY(launch_maxsim_gemm(approx_image(idx), q, chunks(idx), out, on(idx, s), /*hi_only*/ true, /*all_passes*/ false));
     }
     if (d_b) {  // the bound of the one-product pass, by the kernel the pipeline computes its thresholds with (k = 1 over a dummy top list)
         const float m_abs = idx->norm_stats.max_lo_norm + sum_eps(idx->dim) * idx->norm_stats.max_row_norm;
@@ -2384,15 +2360,13 @@ int maxsim_rerank_device(rl_index* idx, const float* d_q, int32_t n_queries, int
         RL_TRY(launch_sanitize_candidates(d_c, n_items, idx->n_chunks, idx->live_chunk_bits, idx->cand.as<int32_t>(), s));
         d_c = idx->cand.as<int32_t>();
     }
-    int st = idx->E16 ? launch_maxsim_cand16(idx->E16, idx->dim, d_q, nq, idx->offsets, d_c, n_cand, n_queries, d_o, s)
-                      : launch_maxsim_cand(idx->E, idx->dim, d_q, nq, idx->offsets, d_c, n_cand, n_queries, d_o, s, idx->split_scale);
+    const QueryVecs q{d_q, nq, (int64_t)nq * idx->dim, n_queries};
+    int st = launch_maxsim_cand(rows(idx), q, chunks(idx), d_c, n_cand, d_o, s);
     if (st == RL_ERR_UNSUPPORTED)  // other dims: the fp32-MFMA pairs kernels (dim % 16 == 0 up to 1024, % 128 up to 4096, nq <= 32; fp16 rows widened on the way in) ...
-        st = launch_maxsim_pairs(idx->E16 ? reinterpret_cast<const float*>(idx->E16) : idx->E, idx->dim, d_q, nq, (int64_t)nq * idx->dim, idx->offsets, d_c,
-                                 n_cand, n_queries, d_o, s, idx->E16 != nullptr, 0, 0, (int)idx->opt.v[RL_OPT_PAIRS_PACKED]);
+        st = launch_maxsim_pairs(rows(idx), q, chunks(idx), {d_c, n_cand, 0, 0, (int)idx->opt.v[RL_OPT_PAIRS_PACKED]}, d_o, s);
     if (st == RL_ERR_UNSUPPORTED && idx->E16) return fail(st, "rl_maxsim_rerank: unsupported shape for an fp16-stored index");
     if (st == RL_ERR_UNSUPPORTED && !idx->E16)  // ... and the VALU backstop for everything else
-        st = launch_maxsim_generic(idx->E, idx->dim, d_q, nq, (int64_t)nq * idx->dim, idx->offsets, d_c, n_cand,
-                                   n_queries, d_o, s);
+        st = launch_maxsim_generic(rows(idx), q, chunks(idx), d_c, n_cand, d_o, s);
     return st;
 }
 }  // namespace rl
@@ -2588,46 +2562,38 @@ int rl_time_kernel(rl_index* idx, int kind, const float* q_dev, int32_t nq, int3
     }
     RL_HIP(hipEventRecord(e0, s));
     for (int i = 0; i < iters && st == RL_OK; ++i) {
-        if (kind == 7) st = launch_maxsim_pp(approx_image(idx), idx->n_rows, idx->dim, idx->qplanes.p, pp_n, 0, pp_n,
-                                             pp_vec, idx->row_to_chunk, idx->offsets, idx->ends.as<uint32_t>(), idx->scores.as<float>(), ldc,
-                                             idx->n_cu, s, approx_scale(idx), nullptr, (int)idx->opt.v[RL_OPT_PP_SCHEDULE], (int)idx->opt.v[RL_OPT_PP_XCD_PASSES]);
+        if (kind == 7) st = launch_maxsim_pp(approx_image(idx), {idx->qplanes.p, pp_n, 0, pp_n, pp_vec}, chunks(idx), {idx->scores.as<float>(), ldc}, on(idx, s),
+                                             (int)idx->opt.v[RL_OPT_PP_SCHEDULE], (int)idx->opt.v[RL_OPT_PP_XCD_PASSES]);
         else if (kind == 3) st = gemm_pass(idx, nq / GEMM_PASS_QUERIES, GEMM_PASS_QUERIES, 0, GEMM_PASS_QUERIES, idx->scores.as<float>(), ldc, s);
         else if (kind == 8) {
             const auto& r = idx->replay;
+            const RowMetric metric = metric_of(idx, r.mode);
             if (hipMemsetAsync(r.cnt, 0, (size_t)r.B * sizeof(uint32_t), s) != hipSuccess) st = RL_ERR_HIP;  // the lists fill up again on every run
             else if (r.pp && r.round1_tiles > 0) {  // both rounds with the thresholds each of them ran with (the ranking between them is not replayed)
                 CandArgs ca1 = r.ca;
                 ca1.tau = r.thr1;
-                st = launch_pp_rows_pass(idx->hi_image.buf.p, idx->n_rows, idx->dim, r.B, r.qs, idx->norm, r.mode, &ca1, idx->pp_work.p, r.log_cap, idx->n_cu, s,
-                                         idx->split_scale, 0, r.round1_tiles, false, r.row_test);
+                st = launch_pp_rows_pass(hi_image(idx), r.B, r.qs, metric, &ca1, {idx->pp_work.p, r.log_cap, 0, r.round1_tiles, false, r.row_test}, on(idx, s));
                 if (st == RL_OK)
-                    st = launch_pp_rows_pass(idx->hi_image.buf.p, idx->n_rows, idx->dim, r.B, r.qs, idx->norm, r.mode, &r.ca, idx->pp_work.p, r.log_cap, idx->n_cu, s,
-                                             idx->split_scale, r.round1_tiles, -1, true, r.row_test);
+                    st = launch_pp_rows_pass(hi_image(idx), r.B, r.qs, metric, &r.ca, {idx->pp_work.p, r.log_cap, r.round1_tiles, -1, true, r.row_test}, on(idx, s));
             }
-            else if (r.pp) st = launch_pp_rows_pass(idx->hi_image.buf.p, idx->n_rows, idx->dim, r.B, r.qs, idx->norm, r.mode, &r.ca, idx->pp_work.p, r.log_cap,
-                                                    idx->n_cu, s, idx->split_scale, 0, -1, false, r.row_test);
-            else st = launch_score_planes_pass(idx->hi_image.buf.p, idx->n_rows, idx->dim, r.B, r.qs, nullptr, 0, idx->norm, idx->sumsq, r.mode, 1, nullptr, &r.ca,
-                                               idx->n_cu, s, idx->split_scale, true, true);
+            else if (r.pp) st = launch_pp_rows_pass(hi_image(idx), r.B, r.qs, metric, &r.ca, {idx->pp_work.p, r.log_cap, 0, -1, false, r.row_test}, on(idx, s));
+            else st = launch_score_planes_pass(hi_image(idx), r.B, r.qs, Scores{}, metric, {1, &r.ca, true}, on(idx, s));
         }
         else if (kind == 0) st = maxsim_scores_device(idx, q_dev, nq, idx->scores.as<float>(), s);
         else if (kind == 9) st = launch_mfma_f16_rate(idx->scores.as<float>(), idx->n_cu, MFMA_RATE_ITERS, s, nullptr);
         else if (kind == 2) st = pairs_pass(idx, nq / 2, 2, 0, idx->scores.as<float>(), ldc, s);
         else if (kind == 5 || kind == 6) {  // the approximate MaxSim pass of a batch: eight queries over the HI image (5: two MFMA products, 6: one)
-            st = hi_image_valid(idx) ? launch_maxsim_gemm(idx->hi_image.buf.p, idx->n_rows, idx->dim, idx->qplanes.p, GEMM_PASS_QUERIES, 0,
-                                                          GEMM_PASS_QUERIES, nq / GEMM_PASS_QUERIES, idx->row_to_chunk, idx->offsets,
-                                                          idx->ends.as<uint32_t>(), idx->scores.as<float>(), ldc, idx->n_cu, s, idx->split_scale, true,
-                                                          nullptr, kind == 6)
+            st = hi_image_valid(idx) ? launch_maxsim_gemm(hi_image(idx), {idx->qplanes.p, GEMM_PASS_QUERIES, 0, GEMM_PASS_QUERIES, nq / GEMM_PASS_QUERIES},
+                                                          chunks(idx), {idx->scores.as<float>(), ldc}, on(idx, s), /*hi_only*/ kind == 6, /*all_passes*/ false)
                                      : fail(RL_ERR_UNSUPPORTED, "rl_time_kernel: the index has no HI image");
         }
         else if (kind == 4) {  // the ranking pass of the half-bytes search: the f16 stream kernel over the HI plane
-            st = hi_valid(idx) ? launch_maxsim_stream16(idx->hiplane.buf.as<uint16_t>(), idx->n_rows, idx->dim, q_dev, nq, idx->row_to_chunk, idx->offsets,
-                                                        idx->n_chunks, 1, idx->scores.as<float>(), ld, idx->n_cu, s)
+            st = hi_valid(idx) ? launch_maxsim_stream(hi_plane(idx), {q_dev, nq}, chunks(idx), 1, {idx->scores.as<float>(), ld}, on(idx, s))
                                : fail(RL_ERR_UNSUPPORTED, "rl_time_kernel: the index has no HI plane");
         }
         else if (kind == 10) {  // the approximate pass of the few-queries MaxSim route: ONE query of nq vectors, MaxSim over the HI plane
-            st = hi_valid(idx) && nq <= 32 ? launch_maxsim_stream_batch(idx->hiplane.buf.p, true, idx->n_rows, idx->dim, q_dev, nq, (int64_t)nq * idx->dim, 1,
-                                                                        idx->row_to_chunk, idx->offsets, idx->n_chunks, idx->scores.as<float>(), ldc, idx->n_cu, s,
-                                                                        0.f, nullptr)
+            st = hi_valid(idx) && nq <= 32 ? launch_maxsim_stream_batch(hi_plane(idx), {q_dev, nq, (int64_t)nq * idx->dim, 1}, chunks(idx),
+                                                                        {idx->scores.as<float>(), ldc}, on(idx, s))
                                            : fail(RL_ERR_UNSUPPORTED, "rl_time_kernel: the index has no HI plane (or nq > 32)");
         }
         else st = score_rows(idx, q_dev, nq, ld, s);

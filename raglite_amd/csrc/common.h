@@ -517,16 +517,57 @@ int launch_sentence_dp(const uint32_t* codepoints, const void* probas, int proba
                        void* scratch, hipStream_t s);
 
 // maxsim*.hip
+// The launchers of this section take what they read and write as a few plain views (nothing owns memory; api.hip builds them from an index
+// in one place: rows(idx), image(idx), chunks(idx), on(idx, s, run_if) ...), then what is their own.
+// A corpus matrix: the stored rows, the row-major HI plane, or an image in the tiled layout of maxsim_gemm.hip.
+struct RowsRef {
+    const void* p = nullptr;
+    bool f16 = false;  // fp16 elements: an fp16-stored corpus, the HI plane; of an image: ONE plane (the `half` layout) instead of hi | lo
+    int64_t n_rows = 0;
+    int32_t dim = 0;
+    // An image or the HI plane: the power of two it was built at (the kernels undo it); that is 1 for an fp16-stored corpus.  fp32 rows:
+    // the split scale the kernel applies (fp32 operands as fp16 hi + lo pairs, three fp16 MFMAs, fp32 accumulation), 0 = the exact fp32
+    // MFMA chain.  Kernels that read fp16 rows directly take no scale.
+    float scale = 0.f;
+};
+struct ChunkMap {  // the chunk structure over those rows
+    const int32_t* row_to_chunk = nullptr;
+    const int64_t* offsets = nullptr;  // [n_chunks + 1]
+    int64_t n_chunks = 0;
+    const uint32_t* ends_bits = nullptr;  // launch_chunk_ends' bitmap (the image passes)
+};
+struct QueryVecs {  // n_queries queries of nq vectors each, q_stride floats apart
+    const float* Q = nullptr;
+    int32_t nq = 0;
+    int64_t q_stride = 0;
+    int32_t n_queries = 1;
+};
+struct QueryImageRef {  // queries first .. first + n_q - 1, nq vectors each, of a launch_query_planes / launch_query_split buffer over n_queries
+    const void* buf = nullptr;
+    int32_t n_queries = 0, first = 0, n_q = 0, nq = 0;
+};
+struct RowMetric {  // the row side of a similarity (scan.hip conventions)
+    int mode = SCAN_RAW_DOT;
+    const float* row_norm = nullptr;   // [n_rows] (cosine)
+    const float* row_sumsq = nullptr;  // [n_rows] (l2)
+};
+struct Scores {  // out[q * ld + row or chunk]
+    float* p = nullptr;
+    int64_t ld = 0;
+};
+struct Launch {
+    int n_cu = 0;
+    hipStream_t s = nullptr;
+    const uint32_t* run_if = nullptr;  // the kernel returns at once unless *run_if != 0 (nullptr: always runs); a launcher whose kernel has no
+                                       // such guard refuses one
+};
+
 int launch_row_to_chunk(const int64_t* chunk_offsets, int64_t n_chunks, int64_t n_rows, int32_t* row_to_chunk,
                         hipStream_t s);
-// Fast path: dim in {128,256,384,512,768,1024}, nq <= 32 (wave-specialised MFMA streaming kernel).  mode 0: chunk MaxSim scores
-// out[n_chunks]; mode 1: raw row dots out[q * ld + row].  Returns RL_ERR_UNSUPPORTED outside the fast path.
-// split_scale > 0: SPLIT arithmetic (fp32 operands as fp16 hi + lo pairs, three fp16 MFMAs, fp32 accumulation) with the
-// corpus scaled by that power of two; 0: the exact fp32 MFMA chain.
-int launch_maxsim_stream(const float* D, int64_t n_rows, int32_t dim, const float* Q, int32_t nq,
-                         const int32_t* row_to_chunk, const int64_t* chunk_offsets, int64_t n_chunks, int mode,
-                         float* out, int64_t ld, int n_cu, hipStream_t s, float split_scale = 0.f,
-                         const uint32_t* run_if = nullptr);  // run_if: the kernel returns at once unless *run_if != 0
+// Fast path: dim in {128,256,384,512,768,1024}, q.nq <= 32 (wave-specialised MFMA streaming kernel; one query, q.n_queries == 1), fp32 or
+// fp16 rows.  mode 0: chunk MaxSim scores out[n_chunks] (out.ld != 0: added to what `out` holds); mode 1: raw row dots out[q * ld + row].
+// RL_ERR_UNSUPPORTED outside the fast path.
+int launch_maxsim_stream(const RowsRef& D, const QueryVecs& q, const ChunkMap& c, int mode, Scores out, const Launch& on);
 struct StreamSecondJob {  // launch_maxsim_stream_two: what grid row 1 runs
     const float* D = nullptr;
     int64_t n_rows = 0;
@@ -534,97 +575,81 @@ struct StreamSecondJob {  // launch_maxsim_stream_two: what grid row 1 runs
     int64_t ld = 0;
     const uint32_t* run_if = nullptr;  // the row returns at once unless *run_if != 0 (nullptr: always runs)
 };
-int launch_maxsim_stream_two(const float* D, int64_t n_rows, int32_t dim, const float* Q, int32_t nq, const int32_t* row_to_chunk,
-                             const int64_t* chunk_offsets, int64_t n_chunks, float* out, int64_t ld, int n_cu, hipStream_t s, float split_scale,
-                             const StreamSecondJob& job2);
-int launch_maxsim_stream_batch(const void* D, bool f16, int64_t n_rows, int32_t dim, const float* Q, int32_t nq, int64_t q_stride,
-                               int32_t n_queries, const int32_t* row_to_chunk, const int64_t* chunk_offsets, int64_t n_chunks, float* out,
-                               int64_t out_stride, int n_cu, hipStream_t s, float split_scale, const uint32_t* run_if = nullptr);
+int launch_maxsim_stream_two(const RowsRef& D, const QueryVecs& q, const ChunkMap& c, Scores out, const Launch& on, const StreamSecondJob& job2);
+int launch_maxsim_stream_batch(const RowsRef& D, const QueryVecs& q, const ChunkMap& c, Scores out, const Launch& on);
 size_t query_split_bytes(int32_t dim, int32_t n_queries);
-int launch_query_split(const float* Q, int32_t dim, int32_t nq, int64_t q_stride, int32_t n_queries, void* buf, bool f16_corpus,
-                       hipStream_t s);
-int launch_maxsim_stream2(const void* D, bool f16, int64_t n_rows, int32_t dim, const void* split_buf, int32_t n_queries,
-                          int32_t first, int32_t nq, const int32_t* row_to_chunk, const int64_t* chunk_offsets, int64_t n_chunks,
-                          float* out, int64_t out_stride, int n_cu, hipStream_t s, float split_scale);
-// maxsim_gemm.hip: eight queries per corpus pass over the pre-split (fp16 hi | lo) corpus image; `half`: the one-plane image of
-// an fp16-stored corpus (split_scale = 1)
+int launch_query_split(const QueryVecs& q, int32_t dim, void* buf, bool f16_corpus, hipStream_t s);
+int launch_maxsim_stream2(const RowsRef& D, const QueryImageRef& q, const ChunkMap& c, Scores out, const Launch& on);  // q.n_q == 2
+// maxsim_gemm.hip: eight queries per corpus pass over the pre-split (fp16 hi | lo) corpus image, or (image.f16) a one-plane image
 size_t planes_bytes(int64_t rows, int32_t dim, bool half = false);
-int launch_presplit_rows(const float* E, int64_t first_row, int64_t n_rows, int32_t dim, float scale, void* planes, hipStream_t s);
-int launch_preformat_rows16(const uint16_t* E, int64_t first_row, int64_t n_rows, int32_t dim, void* planes, hipStream_t s);
-int launch_presplit_hi_rows(const float* E, int64_t first_row, int64_t n_rows, int32_t dim, float scale, void* planes, hipStream_t s);
+// rows [first_row, E.n_rows) of E -> their place in the image `planes`
+int launch_presplit_rows(const RowsRef& E, int64_t first_row, void* planes, hipStream_t s);
+int launch_preformat_rows16(const RowsRef& E, int64_t first_row, void* planes, hipStream_t s);
+int launch_presplit_hi_rows(const RowsRef& E, int64_t first_row, void* planes, hipStream_t s);
 size_t chunk_ends_words(int64_t rows);
 int launch_chunk_ends(const int32_t* row_to_chunk, int64_t n_rows, uint32_t* ends, hipStream_t s);
 size_t query_planes_bytes(int32_t dim, int32_t n_queries);
-int launch_query_planes(const float* Q, int32_t dim, int32_t nq, int64_t q_stride, int32_t n_queries, void* buf, hipStream_t s,
-                        uint32_t* zero_words = nullptr, int n_zero = 0);
-int launch_maxsim_gemm(const void* planes, int64_t n_rows, int32_t dim, const void* qbuf, int32_t n_queries, int32_t first,
-                       int32_t n_q, int32_t nq, const int32_t* row_to_chunk, const int64_t* chunk_offsets, const uint32_t* ends_bits,
-                       float* out, int64_t out_stride, int n_cu, hipStream_t s, float split_scale, bool half = false,
-                       const uint32_t* run_if = nullptr, bool hi_only = false, bool all_passes = false);  // all_passes: n_q > 8 in one launch
+int launch_query_planes(const QueryVecs& q, int32_t dim, void* buf, hipStream_t s, uint32_t* zero_words, int n_zero);
+// hi_only: one product (q_hi . e_hi) per multiply; all_passes: q.n_q > 8 in one launch
+int launch_maxsim_gemm(const RowsRef& image, const QueryImageRef& q, const ChunkMap& c, Scores out, const Launch& on, bool hi_only,
+                       bool all_passes);
 // maxsim_pp.hip: the approximate pass of the headline pipeline -- SIXTEEN queries per pass over a one-plane image, one product
 constexpr int32_t PP_PASS_QUERIES = 16;
-int launch_maxsim_pp(const void* image, int64_t n_rows, int32_t dim, const void* qbuf, int32_t n_queries, int32_t first, int32_t n_q,
-                     int32_t nq, const int32_t* row_to_chunk, const int64_t* chunk_offsets, const uint32_t* ends_bits, float* out,
-                     int64_t out_stride, int n_cu, hipStream_t s, float split_scale, const uint32_t* run_if, int schedule, int xcd_passes);  // RL_OPT_PP_SCHEDULE, RL_OPT_PP_XCD_PASSES
+int launch_maxsim_pp(const RowsRef& image, const QueryImageRef& q, const ChunkMap& c, Scores out, const Launch& on,
+                     int schedule, int xcd_passes);  // RL_OPT_PP_SCHEDULE, RL_OPT_PP_XCD_PASSES
 // the matrix pipe's sustained fp16 rate under the pass kernel's own MFMA stream (no loads, no epilogue): rl_time_kernel kind 9
 constexpr int32_t MFMA_RATE_ITERS = 1000;  // x 32 MFMAs per wave: the MFMA count of a wave over one pass of 1 M rows x 1024
 int launch_mfma_f16_rate(float* out, int n_cu, int32_t iters, hipStream_t s, double* flops);
 // the candidate pass of the fused row top-k on that kernel's tile (MODE 2; see maxsim_pp.hip) -- declared after CandArgs below
 size_t score_planes_scratch_floats(int32_t nb, int32_t dim);
-int launch_score_planes(const void* planes, int64_t n_rows, int32_t dim, const float* Q, int32_t nb, float* scores, int64_t ld,
-                        const float* row_norm, const float* row_sumsq, float* scratch, int mode, int n_cu, hipStream_t s, float split_scale,
-                        bool half = false);
+int launch_score_planes(const RowsRef& image, const float* Q, int32_t nb, Scores out, const RowMetric& m, float* scratch, const Launch& on);
 struct CandArgs { const float* tau; int32_t tau_stride; float* scores; int32_t* ids; uint32_t* cnt; uint32_t* overflow; int32_t cap; };
 int launch_score_planes_queries(const float* Q, int32_t nb, int32_t dim, float* scratch, int mode, hipStream_t s, uint32_t* zero_word = nullptr);
 size_t pp_rows_scratch_bytes(int64_t n_rows, int32_t nb, int n_cu, int32_t expected_per_query, int32_t* log_cap_out);
-// row tiles (of 128 rows) [tile_begin, tile_begin + tile_count) only (tile_count < 0: to the end); norms_ready: the block norm ranges in
-// `work` are those of an earlier launch of the same search
-int launch_pp_rows_pass(const void* image, int64_t n_rows, int32_t dim, int32_t nb, float* scratch, const float* row_norm, int mode,
-                        const CandArgs* cand, void* work, int32_t log_cap, int n_cu, hipStream_t s, float split_scale, int64_t tile_begin = 0,
-                        int64_t tile_count = -1, bool norms_ready = false,
-                        bool row_norm_test = false);  // cosine: test hits row by row against their own norms (wild norm spread)
-// the sample pass of the same search on that tile (MODE 1): S[q * ld_s + 256 j + r] = similarity of query q with row 256 stride j + r
-int launch_pp_rows_sample(const void* image, int64_t n_rows, int32_t dim, int32_t nb, float* scratch, const float* row_norm, int mode, float* S,
-                          int64_t ld_s, int32_t stride, int n_cu, hipStream_t s, float split_scale);
+struct PpRowsPass {
+    void* work = nullptr;  // pp_rows_scratch_bytes bytes, which also gives log_cap
+    int32_t log_cap = 0;
+    int64_t tile_begin = 0, tile_count = -1;  // row tiles (of 128 rows) [tile_begin, tile_begin + tile_count) only (tile_count < 0: to the end)
+    bool norms_ready = false;                 // the block norm ranges in `work` are those of an earlier launch of the same search
+    bool row_norm_test = false;               // cosine: test hits row by row against their own norms (wild norm spread)
+};
+int launch_pp_rows_pass(const RowsRef& image, int32_t nb, float* scratch, const RowMetric& m, const CandArgs* cand, const PpRowsPass& pass,
+                        const Launch& on);
+// the sample pass of the same search on that tile (MODE 1): S[q * ld + 256 j + r] = similarity of query q with row 256 stride j + r
+int launch_pp_rows_sample(const RowsRef& image, int32_t nb, float* scratch, const RowMetric& m, Scores S, int32_t stride, const Launch& on);
 // thr[q] = max(thr[q], kth[q * k + k - 1] - window[q]): the k-th best approximate similarity of ANY subset of the rows bounds the k-th best
 // overall from below (select.hip; the second round of the fused top-k's candidate pass)
 int launch_raise_threshold(float* thr, const float* kth, int32_t nq, int32_t k, const float* window, hipStream_t s);
-int launch_score_planes_pass(const void* planes, int64_t n_rows, int32_t dim, int32_t nb, float* scratch, float* scores, int64_t ld,
-                             const float* row_norm, const float* row_sumsq, int mode, int32_t tile_stride, const uint32_t* run_if,
-                             const CandArgs* cand, int n_cu, hipStream_t s, float split_scale, bool half = false, bool hi_only = false);
+struct ScorePass {
+    int32_t tile_stride = 1;         // > 1: every tile_stride-th 256-row tile only, in compact columns (the sample pass)
+    const CandArgs* cand = nullptr;  // the fused top-k's candidate lists instead of dense scores
+    bool hi_only = false;            // one product per multiply over a one-plane image
+};
+int launch_score_planes_pass(const RowsRef& image, int32_t nb, float* scratch, Scores out, const RowMetric& m, const ScorePass& pass,
+                             const Launch& on);
 // [largest |element|, smallest non-zero row maximum, non-finite flag] of an fp32 corpus, as uint32 bit patterns (device, 3 words)
 int launch_row_range(const float* E, int64_t n_rows, int32_t dim, uint32_t* range, hipStream_t s);
-// Any dim / nq: one wave per chunk (or per candidate), VALU dot products.
-// score_gemm.hip: similarity of many queries at once (fp32 MFMA GEMM, 128 x 128 tiles, fused metric); dim % 32 == 0.
-int launch_score_gemm(const float* E, int64_t n_rows, int32_t dim, const float* Q, int32_t nb, float* scores,
-                      int64_t ld, const float* row_norm, const float* row_sumsq, float* q_sumsq_scratch, int mode,
-                      int n_cu, hipStream_t s, float split_scale = 0.f);
+// score_gemm.hip: similarity of many queries at once (fp32 MFMA GEMM, 128 x 128 tiles, fused metric); dim % 32 == 0; fp32 rows.
+int launch_score_gemm(const RowsRef& E, const float* Q, int32_t nb, Scores out, const RowMetric& m, float* q_sumsq_scratch, const Launch& on);
 size_t score_gemm_scratch_floats(int32_t nb, int32_t dim, bool split);
-// the same over an fp16-stored corpus
-int launch_maxsim_stream16(const uint16_t* D, int64_t n_rows, int32_t dim, const float* Q, int32_t nq,
-                           const int32_t* row_to_chunk, const int64_t* chunk_offsets, int64_t n_chunks, int mode,
-                           float* out, int64_t ld, int n_cu, hipStream_t s);
 // exact MaxSim of (query, candidate chunk) pairs, all queries in one launch: dim % 16 == 0 up to 1024, dim % 128 == 0 up to 4096 (wave-private query
-// windows, maxsim_pairs_wide_kernel), nq <= 32, fp32 MFMA
-int launch_maxsim_pairs(const float* D, int32_t dim, const float* Q, int32_t nq, int64_t q_stride, const int64_t* chunk_offsets,
-                        const int32_t* candidates, int64_t n_items_per_query, int32_t n_queries, float* out, hipStream_t s,
-                        bool rows16 = false,  // rows16: D points at fp16 rows (an fp16-stored corpus)
-                        int64_t item_stride = 0, int64_t first_item = 0,  // lists of `item_stride` (0: n_items_per_query) entries per query, of
-                                                                          // which entries first_item .. first_item + n_items_per_query - 1 are scored
-                        int packed = 1);  // 0: a chunk per tile; 1: rows packed into shared tiles; 2: ... by sixteen waves per workgroup  // dim % 128 == 0: the row-packing kernel (same bits, about half the matrix work on short chunks)
+// windows, maxsim_pairs_wide_kernel), nq <= 32, fp32 MFMA over fp32 or fp16 rows
+struct PairsList {
+    const int32_t* candidates = nullptr;
+    int64_t n_items = 0;                       // entries scored per query
+    int64_t item_stride = 0, first_item = 0;   // lists of `item_stride` (0: n_items) entries per query, of which first_item .. first_item + n_items - 1 are scored
+    int packed = 1;  // 0: a chunk per tile; 1: rows packed into shared tiles; 2: ... by sixteen waves per workgroup  (dim % 128 == 0: same bits, about half the matrix work on short chunks)
+};
+int launch_maxsim_pairs(const RowsRef& D, const QueryVecs& q, const ChunkMap& c, const PairsList& list, float* out, hipStream_t s);
 // 1024 < dim <= 4096 (dim % 128 == 0): launch_maxsim_pairs takes maxsim_pairs_wide_kernel; and the exact scores of EVERY chunk behind a run-if flag
-int launch_maxsim_pairs_all_wide(const float* D, int32_t dim, const float* Q, int32_t nq, int64_t q_stride, const int64_t* offsets, int64_t n_chunks,
-                                 int32_t n_queries, float* out, int64_t out_stride, hipStream_t s, const uint32_t* run_if, bool rows16 = false);
-int launch_maxsim_generic(const float* D, int32_t dim, const float* Q, int32_t nq, int64_t q_stride_queries,
-                          const int64_t* chunk_offsets, const int32_t* candidates, int64_t n_items,
-                          int32_t n_queries, float* out, hipStream_t s);
+int launch_maxsim_pairs_all_wide(const RowsRef& D, const QueryVecs& q, const ChunkMap& c, Scores out, const Launch& on);
+// Any dim / nq: one wave per chunk (or per candidate), VALU dot products; fp32 rows.
+int launch_maxsim_generic(const RowsRef& D, const QueryVecs& q, const ChunkMap& c, const int32_t* candidates, int64_t n_items, float* out,
+                          hipStream_t s);
 int launch_sanitize_candidates(const int32_t* in, int64_t n, int64_t n_chunks, const uint32_t* live_chunk_bits, int32_t* out,
                                hipStream_t s);
-// Rerank fast path: dim == 128, nq <= 32 (MFMA, direct fragment loads).
-int launch_maxsim_cand(const float* D, int32_t dim, const float* Q, int32_t nq, const int64_t* chunk_offsets,
-                       const int32_t* candidates, int32_t n_cand, int32_t n_queries, float* out, hipStream_t s,
-                       float split_scale = 0.f);  // > 0: fp16-split arithmetic, corpus scaled by that power of two
-int launch_maxsim_cand16(const uint16_t* D, int32_t dim, const float* Q, int32_t nq, const int64_t* chunk_offsets,
-                         const int32_t* candidates, int32_t n_cand, int32_t n_queries, float* out, hipStream_t s);
+// Rerank fast path: dim == 128, nq <= 32 (MFMA, direct fragment loads), fp32 or fp16 rows.
+int launch_maxsim_cand(const RowsRef& D, const QueryVecs& q, const ChunkMap& c, const int32_t* candidates, int32_t n_cand, float* out,
+                       hipStream_t s);
 
 }  // namespace rl

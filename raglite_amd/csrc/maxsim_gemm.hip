@@ -93,8 +93,10 @@ __global__ __launch_bounds__(256) void presplit_rows_kernel(const float* __restr
     *reinterpret_cast<h16x8*>(blk + (((4 + kq) ^ sw) << 4)) = lo;
 }
 
-int launch_presplit_rows(const float* E, int64_t first_row, int64_t n_rows, int32_t dim, float scale, void* planes, hipStream_t s) {
-    if (dim % 32 || dim < 32) return RL_ERR_UNSUPPORTED;
+int launch_presplit_rows(const RowsRef& rows, int64_t first_row, void* planes, hipStream_t s) {
+    const auto [p, f16, n_rows, dim, scale] = rows;
+    const float* const E = static_cast<const float*>(p);
+    if (f16 || dim % 32 || dim < 32) return RL_ERR_UNSUPPORTED;
     const int64_t end_row = (n_rows + 15) / 16 * 16;
     if (end_row <= first_row) return RL_OK;
     const int64_t threads = (end_row - first_row) * (dim / 8);
@@ -148,8 +150,10 @@ __global__ __launch_bounds__(256) void presplit_hi_rows_kernel(const float* __re
     *reinterpret_cast<uint4*>(planes + ((row >> 4) * nslab + s) * 1024 + kq * 256 + (row & 15) * 16) = o;
 }
 
-int launch_presplit_hi_rows(const float* E, int64_t first_row, int64_t n_rows, int32_t dim, float scale, void* planes, hipStream_t s) {
-    if (dim % 32 || dim < 32 || (reinterpret_cast<uintptr_t>(E) & 15)) return RL_ERR_UNSUPPORTED;
+int launch_presplit_hi_rows(const RowsRef& rows, int64_t first_row, void* planes, hipStream_t s) {
+    const auto [p, f16, n_rows, dim, scale] = rows;
+    const float* const E = static_cast<const float*>(p);
+    if (f16 || dim % 32 || dim < 32 || (reinterpret_cast<uintptr_t>(E) & 15)) return RL_ERR_UNSUPPORTED;
     const int64_t end_row = (n_rows + 15) / 16 * 16;
     if (end_row <= first_row) return RL_OK;
     const int64_t threads = (end_row - first_row) * (dim / 8);
@@ -159,8 +163,10 @@ int launch_presplit_hi_rows(const float* E, int64_t first_row, int64_t n_rows, i
     return RL_OK;
 }
 
-int launch_preformat_rows16(const uint16_t* E, int64_t first_row, int64_t n_rows, int32_t dim, void* planes, hipStream_t s) {
-    if (dim % 32 || dim < 32 || (reinterpret_cast<uintptr_t>(E) & 15)) return RL_ERR_UNSUPPORTED;
+int launch_preformat_rows16(const RowsRef& rows, int64_t first_row, void* planes, hipStream_t s) {
+    const auto [p, f16, n_rows, dim, scale] = rows;  // (a permutation: no scale)
+    const uint16_t* const E = static_cast<const uint16_t*>(p);
+    if (!f16 || dim % 32 || dim < 32 || (reinterpret_cast<uintptr_t>(E) & 15)) return RL_ERR_UNSUPPORTED;
     const int64_t end_row = (n_rows + 15) / 16 * 16;
     if (end_row <= first_row) return RL_OK;
     const int64_t threads = (end_row - first_row) * (dim / 8);
@@ -303,8 +309,8 @@ __global__ __launch_bounds__(1024) void query_planes_kernel(const float* __restr
 
 size_t query_planes_bytes(int32_t dim, int32_t n_queries) { return QueryPlanes().lay(Carver(), n_queries, dim); }
 
-int launch_query_planes(const float* Q, int32_t dim, int32_t nq, int64_t q_stride, int32_t n_queries, void* buf, hipStream_t s, uint32_t* zero_words,
-                        int n_zero) {
+int launch_query_planes(const QueryVecs& q, int32_t dim, void* buf, hipStream_t s, uint32_t* zero_words, int n_zero) {
+    const auto [Q, nq, q_stride, n_queries] = q;
     if (n_zero < 0 || n_zero > 1024 || (n_zero > 0 && !zero_words)) return RL_ERR_INVALID;
     if (nq < 1 || nq > 32 || n_queries < 1 || dim % 32 || dim < 32) return RL_ERR_UNSUPPORTED;
     if ((reinterpret_cast<uintptr_t>(Q) & 15) || (q_stride & 3)) return RL_ERR_UNSUPPORTED;
@@ -965,11 +971,13 @@ __global__ __launch_bounds__(512, 2) void maxsim_gemm_kernel(const char* __restr
 }
 
 // n_q (1..8) queries `first .. first + n_q - 1` of a launch_query_planes buffer over `n_queries`, each nq (<= 32) vectors:
-// out[q * out_stride + chunk].  Needs an index without empty chunks (the chunk of an end row is found by counting ends).
-int launch_maxsim_gemm(const void* planes, int64_t n_rows, int32_t dim, const void* qbuf, int32_t n_queries, int32_t first,
-                       int32_t n_q, int32_t nq, const int32_t* row_to_chunk, const int64_t* chunk_offsets, const uint32_t* ends_bits,
-                       float* out, int64_t out_stride, int n_cu, hipStream_t s, float split_scale, bool half, const uint32_t* run_if,
-                       bool hi_only, bool all_passes) {
+// out[q * ld + chunk].  Needs an index without empty chunks (the chunk of an end row is found by counting ends).
+int launch_maxsim_gemm(const RowsRef& image, const QueryImageRef& q, const ChunkMap& c, Scores o, const Launch& on, bool hi_only, bool all_passes) {
+    const auto [planes, half, n_rows, dim, split_scale] = image;
+    const auto [qbuf, n_queries, first, n_q, nq] = q;
+    const auto [row_to_chunk, chunk_offsets, n_chunks, ends_bits] = c;
+    const auto [out, out_stride] = o;
+    const auto [n_cu, s, run_if] = on;
     // all_passes: n_q may exceed 8 -- ceil(n_q / 8) passes in ONE launch (gridDim.y), pass y writing out + 8 y out_stride
     if (nq < 1 || nq > 32 || n_q < 1 || (n_q > MG_WAVES && !all_passes) || n_rows < 1 || first < 0 || first + n_q > n_queries) return RL_ERR_UNSUPPORTED;
     if (dim % 32 || dim < 32 || !(split_scale > 0.f) || !planes || !ends_bits) return RL_ERR_UNSUPPORTED;
@@ -1115,9 +1123,13 @@ int launch_score_planes_queries(const float* Q, int32_t nb, int32_t dim, float* 
 // One pass of the row-score GEMM over the pre-split corpus image with the query side prepared by
 // launch_score_planes_queries.  Dense (cand == nullptr): scores[q * ld + row] (or + sampled-tile column with
 // tile_stride > 1).  Fused top-k (cand != nullptr): candidate lists, see RowScoreArgs.
-int launch_score_planes_pass(const void* planes, int64_t n_rows, int32_t dim, int32_t nb, float* scratch, float* scores, int64_t ld,
-                             const float* row_norm, const float* row_sumsq, int mode, int32_t tile_stride, const uint32_t* run_if,
-                             const CandArgs* cand, int n_cu, hipStream_t s, float split_scale, bool half, bool hi_only) {
+int launch_score_planes_pass(const RowsRef& image, int32_t nb, float* scratch, Scores out, const RowMetric& m, const ScorePass& pass,
+                             const Launch& on) {
+    const auto [planes, half, n_rows, dim, split_scale] = image;
+    const auto [scores, ld] = out;
+    const auto [mode, row_norm, row_sumsq] = m;
+    const auto [tile_stride, cand, hi_only] = pass;
+    const auto [n_cu, s, run_if] = on;
     if (nb < 1 || n_rows < 1 || dim % 32 || dim < 32 || !(split_scale > 0.f) || !planes || tile_stride < 1) return RL_ERR_UNSUPPORTED;
     if ((mode == SCAN_COSINE && !row_norm) || (mode == SCAN_L2 && !row_sumsq)) return RL_ERR_INVALID;
     const int32_t nslab = dim / 32, groups = (nb + 31) / 32;
@@ -1155,13 +1167,10 @@ int launch_score_planes_pass(const void* planes, int64_t n_rows, int32_t dim, in
 
 // Similarity (metric `mode`, scan.hip conventions) of nb queries against every row over the pre-split corpus image:
 // scores[q * ld + row].  Same results as launch_score_gemm in split arithmetic up to the summation order over K.
-int launch_score_planes(const void* planes, int64_t n_rows, int32_t dim, const float* Q, int32_t nb, float* scores, int64_t ld,
-                        const float* row_norm, const float* row_sumsq, float* scratch, int mode, int n_cu, hipStream_t s, float split_scale,
-                        bool half) {
-    if (!(split_scale > 0.f) || !planes) return RL_ERR_UNSUPPORTED;
-    RL_TRY(launch_score_planes_queries(Q, nb, dim, scratch, mode, s));
-    return launch_score_planes_pass(planes, n_rows, dim, nb, scratch, scores, ld, row_norm, row_sumsq, mode, 1, nullptr, nullptr, n_cu, s,
-                                    split_scale, half);
+int launch_score_planes(const RowsRef& image, const float* Q, int32_t nb, Scores out, const RowMetric& m, float* scratch, const Launch& on) {
+    if (!(image.scale > 0.f) || !image.p) return RL_ERR_UNSUPPORTED;
+    RL_TRY(launch_score_planes_queries(Q, nb, image.dim, scratch, m.mode, on.s));
+    return launch_score_planes_pass(image, nb, scratch, out, m, ScorePass{}, on);
 }
 
 }  // namespace rl

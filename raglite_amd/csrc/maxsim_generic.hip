@@ -601,9 +601,13 @@ __global__ __launch_bounds__(512) void maxsim_pairs_wide_kernel(const float* __r
     }
 }
 
-int launch_maxsim_pairs(const float* D, int32_t dim, const float* Q, int32_t nq, int64_t q_stride, const int64_t* offsets,
-                        const int32_t* candidates, int64_t n_items_per_query, int32_t n_queries, float* out, hipStream_t s, bool rows16,
-                        int64_t item_stride, int64_t first_item, int packed_mode) {
+int launch_maxsim_pairs(const RowsRef& rows, const QueryVecs& q, const ChunkMap& c, const PairsList& list, float* out, hipStream_t s) {
+    const float* const D = static_cast<const float*>(rows.p);  // fp32 rows, or (rows16) IEEE halves
+    const bool rows16 = rows.f16;
+    const int32_t dim = rows.dim;
+    const auto [Q, nq, q_stride, n_queries] = q;
+    const int64_t* const offsets = c.offsets;
+    auto [candidates, n_items_per_query, item_stride, first_item, packed_mode] = list;
     bool packed = packed_mode != 0;
     if (n_items_per_query <= 0 || n_queries <= 0) return RL_OK;
     if (item_stride <= 0) item_stride = n_items_per_query;
@@ -721,8 +725,14 @@ int launch_maxsim_pairs(const float* D, int32_t dim, const float* Q, int32_t nq,
 
 // Exact MaxSim scores of EVERY chunk for a batch of queries over a wide index (1024 < dim <= 4096, dim % 128 == 0), behind a run-if flag:
 // out[q * out_stride + chunk].  The guarded full-precision fallback of the bound-filtered batch where the index keeps rows + HI image only.
-int launch_maxsim_pairs_all_wide(const float* D, int32_t dim, const float* Q, int32_t nq, int64_t q_stride, const int64_t* offsets, int64_t n_chunks,
-                                 int32_t n_queries, float* out, int64_t out_stride, hipStream_t s, const uint32_t* run_if, bool rows16) {
+int launch_maxsim_pairs_all_wide(const RowsRef& rows, const QueryVecs& q, const ChunkMap& c, Scores o, const Launch& on) {
+    const float* const D = static_cast<const float*>(rows.p);  // fp32 rows, or (rows16) IEEE halves
+    const bool rows16 = rows.f16;
+    const int32_t dim = rows.dim;
+    const auto [Q, nq, q_stride, n_queries] = q;
+    const auto [row_to_chunk, offsets, n_chunks, ends_bits] = c;
+    const auto [out, out_stride] = o;
+    const auto [n_cu, s, run_if] = on;
     if (n_chunks <= 0 || n_queries <= 0) return RL_OK;
     if (nq < 1 || nq > 32 || dim <= 1024 || dim > PAIRS_MAX_DIM || dim % PW_KW) return RL_ERR_UNSUPPORTED;
     if ((reinterpret_cast<uintptr_t>(D) & (rows16 ? 7 : 15)) || (reinterpret_cast<uintptr_t>(Q) & 15) || (q_stride & 3)) return RL_ERR_UNSUPPORTED;
@@ -745,9 +755,13 @@ int launch_maxsim_pairs_all_wide(const float* D, int32_t dim, const float* Q, in
 }
 
 // One launch per query (the generic path is a correctness backstop, not a throughput path).
-int launch_maxsim_generic(const float* D, int32_t dim, const float* Q, int32_t nq, int64_t q_stride,
-                          const int64_t* offsets, const int32_t* candidates, int64_t n_items_per_query,
-                          int32_t n_queries, float* out, hipStream_t s) {
+int launch_maxsim_generic(const RowsRef& rows, const QueryVecs& q, const ChunkMap& c, const int32_t* candidates, int64_t n_items_per_query,
+                          float* out, hipStream_t s) {
+    const float* const D = static_cast<const float*>(rows.p);
+    const int32_t dim = rows.dim;
+    const auto [Q, nq, q_stride, n_queries] = q;
+    const int64_t* const offsets = c.offsets;
+    if (rows.f16) return RL_ERR_UNSUPPORTED;
     if (nq < 1 || nq > GEN_NQ_MAX) return fail(RL_ERR_UNSUPPORTED, "MaxSim: nq must be in [1, 1024]");
     if (n_items_per_query <= 0 || n_queries <= 0) return RL_OK;
     const bool vec4 = (dim % 4 == 0) && ((reinterpret_cast<uintptr_t>(D) & 15) == 0) &&
@@ -1015,16 +1029,11 @@ int launch_sanitize_candidates(const int32_t* in, int64_t n, int64_t n_chunks, c
     return RL_OK;
 }
 
-int launch_maxsim_cand(const float* D, int32_t dim, const float* Q, int32_t nq, const int64_t* offsets,
-                       const int32_t* candidates, int32_t n_cand, int32_t n_queries, float* out, hipStream_t s,
-                       float split_scale) {
-    return launch_cand_any(D, false, dim, Q, nq, offsets, candidates, n_cand, n_queries, out, s, split_scale);
-}
-
-int launch_maxsim_cand16(const uint16_t* D, int32_t dim, const float* Q, int32_t nq, const int64_t* offsets,
-                         const int32_t* candidates, int32_t n_cand, int32_t n_queries, float* out, hipStream_t s) {
-    return launch_cand_any(reinterpret_cast<const float*>(D), true, dim, Q, nq, offsets, candidates, n_cand, n_queries,
-                           out, s);
+// (fp16 rows are multiplied as they are: the kernel takes no scale for them)
+int launch_maxsim_cand(const RowsRef& D, const QueryVecs& q, const ChunkMap& c, const int32_t* candidates, int32_t n_cand, float* out,
+                       hipStream_t s) {
+    return launch_cand_any(static_cast<const float*>(D.p), D.f16, D.dim, q.Q, q.nq, c.offsets, candidates, n_cand, q.n_queries, out, s,
+                           D.f16 ? 0.f : D.scale);
 }
 
 }  // namespace rl

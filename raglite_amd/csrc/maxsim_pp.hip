@@ -884,9 +884,13 @@ __global__ __launch_bounds__(512, 2) void maxsim_pp_kernel(const char* __restric
 // n_q queries `first .. first + n_q - 1` of a launch_query_planes buffer over `n_queries`, each nq (<= 32) vectors, against
 // a one-plane image (fp16 hi halves, or an fp16-stored corpus): out[q * out_stride + chunk], one MFMA product per multiply.
 // Sixteen queries per pass over the image; n_q > 16: ceil(n_q / 16) passes in ONE launch (grid rows).
-int launch_maxsim_pp(const void* image, int64_t n_rows, int32_t dim, const void* qbuf, int32_t n_queries, int32_t first, int32_t n_q,
-                     int32_t nq, const int32_t* row_to_chunk, const int64_t* chunk_offsets, const uint32_t* ends_bits, float* out,
-                     int64_t out_stride, int n_cu, hipStream_t s, float split_scale, const uint32_t* run_if, int schedule, int xcd_passes) {
+int launch_maxsim_pp(const RowsRef& rows, const QueryImageRef& q, const ChunkMap& c, Scores o, const Launch& on, int schedule, int xcd_passes) {
+    const auto [image, one_plane, n_rows, dim, split_scale] = rows;
+    const auto [qbuf, n_queries, first, n_q, nq] = q;
+    const auto [row_to_chunk, chunk_offsets, n_chunks, ends_bits] = c;
+    const auto [out, out_stride] = o;
+    const auto [n_cu, s, run_if] = on;
+    if (!one_plane) return RL_ERR_UNSUPPORTED;
     if (nq < 1 || nq > 32 || n_q < 1 || n_q > PP_QPP * 4096 || n_rows < 1 || first < 0 || first + n_q > n_queries) return RL_ERR_UNSUPPORTED;
     if (dim % 32 || dim < 256 || !(split_scale > 0.f) || !image || !ends_bits) return RL_ERR_UNSUPPORTED;
     const int32_t nslab = dim / 32;
@@ -950,8 +954,12 @@ __global__ __launch_bounds__(256) void block_norm_minmax_kernel(const float* __r
 // The sample pass of the fused top-k on the sixteen-group tile (MODE 1): similarities of every `stride`-th 256-row tile with all nb queries,
 // S[q * ld_s + 256 j + r] (ld_s = 256 x sampled tiles; rows past the corpus: -inf).  `scratch`: the query side as launch_score_planes_queries
 // left it.  cosine / dot; dim % 32 == 0, dim >= 256; the row-norm array must be readable up to the next multiple of 16 rows.
-int launch_pp_rows_sample(const void* image, int64_t n_rows, int32_t dim, int32_t nb, float* scratch, const float* row_norm, int mode, float* S,
-                          int64_t ld_s, int32_t stride, int n_cu, hipStream_t s, float split_scale) {
+int launch_pp_rows_sample(const RowsRef& rows, int32_t nb, float* scratch, const RowMetric& m, Scores out, int32_t stride, const Launch& on) {
+    const auto [image, one_plane, n_rows, dim, split_scale] = rows;
+    const auto [mode, row_norm, row_sumsq] = m;
+    const auto [S, ld_s] = out;
+    const auto [n_cu, s, run_if] = on;
+    if (!one_plane || run_if) return RL_ERR_UNSUPPORTED;
     if (nb < 1 || n_rows < 1 || dim % 32 || dim < 256 || !(split_scale > 0.f) || !image || !S || stride < 1) return RL_ERR_UNSUPPORTED;
     if (mode != SCAN_COSINE && mode != SCAN_DOT) return RL_ERR_UNSUPPORTED;
     if (mode == SCAN_COSINE && !row_norm) return RL_ERR_INVALID;
@@ -991,9 +999,13 @@ size_t pp_rows_scratch_bytes(int64_t n_rows, int32_t nb, int n_cu, int32_t expec
 // The candidate pass of the fused top-k (maxsim_gemm.hip MODE 2 semantics: per-query lists of (similarity, row) for every row whose
 // similarity reaches cand->tau[q]) over a ONE-PLANE image at one product per multiply, on the 128-row x 512-query tile.  `scratch`: the
 // query side as launch_score_planes_queries left it; `work`: pp_rows_scratch_bytes bytes.  cosine / dot; dim % 32 == 0, dim >= 256.
-int launch_pp_rows_pass(const void* image, int64_t n_rows, int32_t dim, int32_t nb, float* scratch, const float* row_norm, int mode,
-                        const CandArgs* cand, void* work, int32_t log_cap, int n_cu, hipStream_t s, float split_scale, int64_t tile_begin,
-                        int64_t tile_count, bool norms_ready, bool row_norm_test) {
+int launch_pp_rows_pass(const RowsRef& rows, int32_t nb, float* scratch, const RowMetric& m, const CandArgs* cand, const PpRowsPass& pass,
+                        const Launch& on) {
+    const auto [image, one_plane, n_rows, dim, split_scale] = rows;
+    const auto [mode, row_norm, row_sumsq] = m;
+    auto [work, log_cap, tile_begin, tile_count, norms_ready, row_norm_test] = pass;
+    const auto [n_cu, s, run_if] = on;
+    if (!one_plane || run_if) return RL_ERR_UNSUPPORTED;
     if (nb < 1 || n_rows < 1 || dim % 32 || dim < 256 || !(split_scale > 0.f) || !image || !cand || !work) return RL_ERR_UNSUPPORTED;
     if (mode != SCAN_COSINE && mode != SCAN_DOT) return RL_ERR_UNSUPPORTED;
     if (mode == SCAN_COSINE && !row_norm) return RL_ERR_INVALID;

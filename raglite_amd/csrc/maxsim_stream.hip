@@ -1078,37 +1078,33 @@ static int launch_stream_any(const float* D, bool f16, int64_t n_rows, int32_t d
     return RL_OK;
 }
 
-int launch_maxsim_stream(const float* D, int64_t n_rows, int32_t dim, const float* Q, int32_t nq,
-                         const int32_t* row_to_chunk, const int64_t* chunk_offsets, int64_t n_chunks, int mode,
-                         float* out, int64_t ld, int n_cu, hipStream_t s, float split_scale, const uint32_t* run_if) {
-    return launch_stream_any(D, false, n_rows, dim, Q, nq, row_to_chunk, chunk_offsets, n_chunks, mode, out, ld, n_cu, s,
-                             split_scale, run_if);
+// (fp16 rows are multiplied as they are: the kernel takes no scale for them)
+int launch_maxsim_stream(const RowsRef& D, const QueryVecs& q, const ChunkMap& c, int mode, Scores out, const Launch& on) {
+    return launch_stream_any(static_cast<const float*>(D.p), D.f16, D.n_rows, D.dim, q.Q, q.nq, c.row_to_chunk, c.offsets, c.n_chunks, mode,
+                             out.p, out.ld, on.n_cu, on.s, D.f16 ? 0.f : D.scale, on.run_if);
 }
 
 // launch_maxsim_stream with a SECOND job in the same launch (grid row 1): the same queries over job2's matrix into job2's output, behind
 // job2's run-if flag.  Mode 1 (row scores) only; fp32 rows.
-int launch_maxsim_stream_two(const float* D, int64_t n_rows, int32_t dim, const float* Q, int32_t nq, const int32_t* row_to_chunk,
-                             const int64_t* chunk_offsets, int64_t n_chunks, float* out, int64_t ld, int n_cu, hipStream_t s, float split_scale,
-                             const StreamSecondJob& job2) {
-    return launch_stream_any(D, false, n_rows, dim, Q, nq, row_to_chunk, chunk_offsets, n_chunks, 1, out, ld, n_cu, s, split_scale, nullptr, 1, 0,
-                             0, &job2);
+int launch_maxsim_stream_two(const RowsRef& D, const QueryVecs& q, const ChunkMap& c, Scores out, const Launch& on, const StreamSecondJob& job2) {
+    if (D.f16 || on.run_if) return RL_ERR_UNSUPPORTED;  // (only the second job is guarded, by job2.run_if)
+    return launch_stream_any(static_cast<const float*>(D.p), false, D.n_rows, D.dim, q.Q, q.nq, c.row_to_chunk, c.offsets, c.n_chunks, 1, out.p,
+                             out.ld, on.n_cu, on.s, D.scale, nullptr, 1, 0, 0, &job2);
 }
 
-// MaxSim chunk scores of a BATCH of queries in one launch (grid row y = query y: Q + y q_stride -> out + y out_stride), fp32 or fp16 rows;
+// MaxSim chunk scores of a BATCH of queries in one launch (grid row y = query y: Q + y q_stride -> out + y ld), fp32 or fp16 rows;
 // what the guarded fallback of a MaxSim batch runs over an index without a pre-split image.  nq <= 32 per query.
-int launch_maxsim_stream_batch(const void* D, bool f16, int64_t n_rows, int32_t dim, const float* Q, int32_t nq, int64_t q_stride,
-                               int32_t n_queries, const int32_t* row_to_chunk, const int64_t* chunk_offsets, int64_t n_chunks, float* out,
-                               int64_t out_stride, int n_cu, hipStream_t s, float split_scale, const uint32_t* run_if) {
-    return launch_stream_any(static_cast<const float*>(D), f16, n_rows, dim, Q, nq, row_to_chunk, chunk_offsets, n_chunks, 0, out, 0, n_cu, s,
-                             f16 ? 0.f : split_scale, run_if, n_queries, q_stride, out_stride);
+int launch_maxsim_stream_batch(const RowsRef& D, const QueryVecs& q, const ChunkMap& c, Scores out, const Launch& on) {
+    return launch_stream_any(static_cast<const float*>(D.p), D.f16, D.n_rows, D.dim, q.Q, q.nq, c.row_to_chunk, c.offsets, c.n_chunks, 0, out.p,
+                             0, on.n_cu, on.s, D.f16 ? 0.f : D.scale, on.run_if, q.n_queries, q.q_stride, out.ld);
 }
 
 // Two queries (17..32 vectors each, q_stride floats apart) per corpus pass over an fp32 corpus in SPLIT arithmetic:
 // out[g * out_stride + chunk], g = 0, 1.  RL_ERR_UNSUPPORTED outside that shape (the caller then makes two passes).
 // SPLIT query fragments for `n_queries` queries of nq (17..32) vectors, q_stride floats apart (see query_split_kernel).
 size_t query_split_bytes(int32_t dim, int32_t n_queries) { return (size_t)n_queries * (4 * 2 * (dim / 128) * 2 * 64 * 16 + 64); }
-int launch_query_split(const float* Q, int32_t dim, int32_t nq, int64_t q_stride, int32_t n_queries, void* buf, bool f16_corpus,
-                       hipStream_t s) {
+int launch_query_split(const QueryVecs& q, int32_t dim, void* buf, bool f16_corpus, hipStream_t s) {
+    const auto [Q, nq, q_stride, n_queries] = q;
     if (nq <= 16 || nq > 32 || n_queries < 1) return RL_ERR_UNSUPPORTED;
     if (dim != 128 && dim != 256 && dim != 384 && dim != 512 && dim != 768 && dim != 1024) return RL_ERR_UNSUPPORTED;
     if ((reinterpret_cast<uintptr_t>(Q) & 15) || (q_stride & 3)) return RL_ERR_UNSUPPORTED;
@@ -1127,12 +1123,16 @@ int launch_query_split(const float* Q, int32_t dim, int32_t nq, int64_t q_stride
 }
 
 // Two queries (17..32 vectors each; queries `first`, `first + 1` of a launch_query_split buffer over `n_queries`) per corpus
-// pass over an fp32 corpus in SPLIT arithmetic: out[g * out_stride + chunk], g = 0, 1.  RL_ERR_UNSUPPORTED outside that
+// pass over an fp32 corpus in SPLIT arithmetic: out[g * ld + chunk], g = 0, 1.  RL_ERR_UNSUPPORTED outside that
 // shape (the caller then makes one pass per query).
-int launch_maxsim_stream2(const void* Dv, bool f16, int64_t n_rows, int32_t dim, const void* split_buf, int32_t n_queries,
-                          int32_t first, int32_t nq, const int32_t* row_to_chunk, const int64_t* chunk_offsets, int64_t n_chunks,
-                          float* out, int64_t out_stride, int n_cu, hipStream_t s, float split_scale) {
-    const float* D = static_cast<const float*>(Dv);  // fp32 rows, or (f16) IEEE halves
+int launch_maxsim_stream2(const RowsRef& rows, const QueryImageRef& q, const ChunkMap& c, Scores o, const Launch& on) {
+    const auto [p, f16, n_rows, dim, split_scale] = rows;
+    const float* D = static_cast<const float*>(p);  // fp32 rows, or (f16) IEEE halves
+    const auto [split_buf, n_queries, first, n_q, nq] = q;
+    const auto [row_to_chunk, chunk_offsets, n_chunks, ends_bits] = c;
+    const auto [out, out_stride] = o;
+    const auto [n_cu, s, run_if] = on;
+    if (n_q != 2 || run_if) return RL_ERR_UNSUPPORTED;
     if (nq <= 16 || nq > 32 || n_rows < 1 || (!f16 && !(split_scale > 0.f)) || first < 0 || first + 2 > n_queries) return RL_ERR_UNSUPPORTED;
     if (dim != 128 && dim != 256 && dim != 384 && dim != 512 && dim != 768 && dim != 1024) return RL_ERR_UNSUPPORTED;
     if (reinterpret_cast<uintptr_t>(D) & 15) return RL_ERR_UNSUPPORTED;
@@ -1177,13 +1177,6 @@ int launch_maxsim_stream2(const void* Dv, bool f16, int64_t n_rows, int32_t dim,
 #undef RL_STREAM2
     RL_HIP(hipGetLastError());
     return RL_OK;
-}
-
-int launch_maxsim_stream16(const uint16_t* D, int64_t n_rows, int32_t dim, const float* Q, int32_t nq,
-                           const int32_t* row_to_chunk, const int64_t* chunk_offsets, int64_t n_chunks, int mode,
-                           float* out, int64_t ld, int n_cu, hipStream_t s) {
-    return launch_stream_any(reinterpret_cast<const float*>(D), true, n_rows, dim, Q, nq, row_to_chunk, chunk_offsets,
-                             n_chunks, mode, out, ld, n_cu, s);
 }
 
 }  // namespace rl

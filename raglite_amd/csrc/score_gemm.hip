@@ -518,9 +518,13 @@ int launch_query_sumsq(const float* Q, int32_t nb, int32_t dim, float* out, hipS
 // split_scale > 0: fp16-split arithmetic with the corpus scaled by that power of two; q_sumsq_scratch then holds
 // score_gemm_scratch_floats(nb, dim) floats: q_sumsq, q_scale and the pre-split queries.
 size_t score_gemm_scratch_floats(int32_t nb, int32_t dim, bool split) { return split ? (size_t)nb * (dim + 8) + 8 : (size_t)nb; }
-int launch_score_gemm(const float* E, int64_t n_rows, int32_t dim, const float* Q, int32_t nb, float* scores,
-                      int64_t ld, const float* row_norm, const float* row_sumsq, float* q_sumsq_scratch, int mode,
-                      int n_cu, hipStream_t s, float split_scale) {
+int launch_score_gemm(const RowsRef& rows, const float* Q, int32_t nb, Scores out, const RowMetric& m, float* q_sumsq_scratch, const Launch& on) {
+    const auto [p, f16, n_rows, dim, split_scale] = rows;
+    const float* const E = static_cast<const float*>(p);
+    const auto [scores, ld] = out;
+    const auto [mode, row_norm, row_sumsq] = m;
+    const auto [n_cu, s, run_if] = on;
+    if (f16 || run_if) return RL_ERR_UNSUPPORTED;
     if (nb < 1 || n_rows < 1 || dim < GK || dim % GK != 0) return RL_ERR_UNSUPPORTED;
     if ((reinterpret_cast<uintptr_t>(E) & 15) || (reinterpret_cast<uintptr_t>(Q) & 15)) return RL_ERR_UNSUPPORTED;
     if ((mode == SCAN_COSINE && !row_norm) || (mode == SCAN_L2 && !row_sumsq)) return RL_ERR_INVALID;

@@ -393,3 +393,34 @@ def test_fused_pp_rows_of_wildly_different_norms_stay_on_the_candidate_pass():
         assert not idx.filter_stats()["fallback"]
     assert torch.equal(R, R0) and torch.equal(S.view(torch.int32), S0.view(torch.int32))
     idx.close()
+
+
+@pytest.mark.parametrize("options", [{}, {"fused_two_rounds": 0}, {"fused_pp": 0}], ids=["two_rounds", "one_round", "eight_group_tile"])
+def test_time_kernel_replays_the_candidate_pass_of_the_last_search(options):
+    """`rl_time_kernel` kind 8 launches the candidate pass of the last fused-HI row search again, with the queries and thresholds it ran
+    with: both rounds of the sixteen-group tile, its single round, or the eight-group tile.  The hook returns a time and nothing else, so:
+    it runs, and the search after it returns the bits of the search before it (and the oracle's rows)."""
+    import torch
+
+    raglite_amd.set_device(0)
+    n, dim, B, k = 140_000, 512, 600, 10
+    E = torch.empty((n, dim), dtype=torch.float32, device="cuda")
+    raglite_amd.synth_fill(E, seed=8600)
+    Q = torch.empty((B, dim), dtype=torch.float32, device="cuda")
+    raglite_amd.synth_fill(Q, seed=8601)
+    idx = raglite_amd.DeviceIndex(E, metric="cosine")
+    with idx.options(**options):
+        S, R = idx.search_rows(Q, k)
+        st = idx.filter_stats()
+        assert st["kind"] == "rows_fused_hi" and not st["fallback"], st
+        ms = idx.time_kernel(8, Q, 2)
+        assert 0.0 < ms < 1e4
+        S1, R1 = idx.search_rows(Q, k)
+        st1 = idx.filter_stats()
+    assert st1 == st
+    assert torch.equal(R, R1) and torch.equal(S.view(torch.int32), S1.view(torch.int32))
+    Eh = E.cpu().numpy()
+    for b in (0, B - 1):
+        qh = Q[b].cpu().numpy()
+        assert_topk_close(S[b].cpu().numpy(), R[b].cpu().numpy(), oracle.similarity(Eh, qh, "cosine"), k, _tol(Eh, qh, "cosine"))
+    idx.close()

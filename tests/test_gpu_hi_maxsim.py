@@ -545,3 +545,29 @@ def test_fewer_live_chunks_than_k_never_returns_a_masked_chunk():
     s1, c1 = idx.maxsim_topk(Qb[0], 100)
     assert np.isin(c1[:37], keep).all() and (c1[37:] == -1).all()
     idx.close()
+
+
+def test_time_kernel_runs_the_passes_over_the_hi_images_outside_a_batch():
+    """`rl_time_kernel` launches single passes outside any search: kind 5 / 6 the eight-query pass over the HI image (two products / one),
+    kind 4 the stream kernel's row dots over the HI plane.  The hook returns a time and nothing else, so: each runs, and the batch after
+    them returns the bits of the batch before them, which are the oracle's (integer data; 19 queries: a sixteen-query pass and three)."""
+    import torch
+
+    n, dim, nq, n_queries, k = 262_144, 256, 5, 19, 10
+    rng = np.random.default_rng(19)
+    off = ragged_offsets(rng, n, 33, 95)
+    E = oracle.synth_matrix(10_170, n, dim, "small_int")
+    Qb = np.stack([oracle.synth_matrix(10_180 + i, nq, dim, "small_int") for i in range(n_queries)])
+    idx = raglite_amd.DeviceIndex(E, off, metric="dot")
+    bs, bc = idx.maxsim_topk_batch(Qb, k)
+    assert idx.filter_stats()["kind"] == "maxsim_batch_hi", idx.filter_stats()
+    qv = torch.as_tensor(Qb[:8].reshape(8 * nq, dim), device="cuda")  # eight queries of nq vectors each; kind 4: seventeen row queries
+    for kind, q in ((5, qv), (6, qv), (4, qv[:17])):
+        ms = idx.time_kernel(kind, q, 2)
+        assert 0.0 < ms < 1e4, (kind, ms)
+    bs1, bc1 = idx.maxsim_topk_batch(Qb, k)
+    assert np.array_equal(bc, bc1) and np.array_equal(bs.view(np.uint32), bs1.view(np.uint32))
+    for i in (0, n_queries - 1):
+        ws, wc = oracle.maxsim_topk(E, off, Qb[i], k, np.float32)
+        assert np.array_equal(bc[i], wc) and np.array_equal(bs[i], ws)
+    idx.close()

@@ -212,6 +212,25 @@ def test_search_rows_gemm_path_integer_bit_exact(metric, n, dim, B):
 
 
 @pytest.mark.parametrize("metric", ["cosine", "dot", "l2"])
+@pytest.mark.parametrize("n,dim,B", [(1003, 256, 97), (1003, 288, 130)])
+def test_search_rows_gemm_over_the_stored_rows_integer_bit_exact(metric, n, dim, B):
+    """With the row-score GEMM over the corpus image switched off (`planes_gemm` = 0, and no fused top-k), B >= 96 over an fp32 index is
+    `launch_score_gemm` over the stored rows -- the route of an index without an image.  One and two query tiles, ragged row tiles, an even
+    and an odd number of 32-wide K steps; integer data: the bits of the fp32 as-computed oracle, ties to the lowest row."""
+    E = oracle.synth_matrix(55, n, dim, "small_int")
+    Q = oracle.synth_matrix(56, B, dim, "small_int")
+    idx = raglite_amd.DeviceIndex(E, metric=metric)
+    k = 10
+    with idx.options(planes_gemm=0, fused_topk=0):
+        S, R = idx.search_rows(Q, k)
+    for b in (0, 1, 63, 64, B // 2, B - 2, B - 1):
+        es, ei = oracle.topk_desc(sim_fp32_exact(E, Q[b], metric), k)
+        assert np.array_equal(R[b], ei), f"query {b}: indices differ"
+        assert np.array_equal(S[b].view(np.uint32), es.astype(np.float32).view(np.uint32)), f"query {b}: scores"
+    idx.close()
+
+
+@pytest.mark.parametrize("metric", ["cosine", "dot", "l2"])
 def test_search_rows_gemm_path_uniform_tolerance(metric):
     n, dim, B = 3001, 1024, 200
     E = oracle.synth_matrix(53, n, dim)
@@ -1523,6 +1542,26 @@ def test_maxsim_rerank_unscorable_candidates_are_minus_inf(torch_cuda, dim):
         assert np.array_equal(got[~mask], want[~mask])
     with pytest.raises(ValueError):
         idx.maxsim_rerank(Q, np.full((3, 4), n_chunks, dtype=np.int32))  # host callers are still validated
+    idx.close()
+
+
+@pytest.mark.parametrize("dim,nq", [(100, 5), (256, 40)])
+def test_maxsim_rerank_generic_backstop_integer_bit_exact(dim, nq):
+    """What neither MFMA rerank kernel takes -- a dim that is no multiple of 16, or more than 32 query vectors -- is scored by the VALU
+    backstop (`launch_maxsim_generic` with a candidate list): two queries, nineteen candidates each out of ~200 ragged chunks (rows !=
+    chunks), integer data: the oracle's scores exactly."""
+    rng = np.random.default_rng(dim + nq)
+    n = 1003
+    off = ragged_offsets(rng, n, 1, 9)
+    n_chunks = len(off) - 1
+    E = oracle.synth_matrix(72, n, dim, "small_int")
+    Q = np.stack([oracle.synth_matrix(73 + i, nq, dim, "small_int") for i in range(2)])
+    idx = raglite_amd.DeviceIndex(E, off, metric="dot")
+    cand = rng.integers(0, n_chunks, size=(2, 19)).astype(np.int32)
+    got = np.asarray(idx.maxsim_rerank(Q, cand))
+    for qi in range(2):
+        want = oracle.maxsim_scores(E, off, Q[qi], np.float64)[cand[qi]]
+        assert np.array_equal(got[qi].astype(np.float64), want), qi
     idx.close()
 
 
