@@ -162,6 +162,40 @@ int rl_encoder_info(const rl_encoder* enc, int64_t n_tokens, int32_t* max_tokens
                     void** scratch, int32_t* launches);
 int rl_encoder_destroy(rl_encoder* enc);
 
+/* The three launches of rl_encoder_forward ONE AT A TIME, on the caller's buffers: the same kernels through the same launchers, for
+ * callers that hold each to a reference of its own (tests/test_gpu_encoder_kernels.py) or chain them by hand.  Device pointers only
+ * (mem must be RL_MEM_DEVICE, else RL_ERR_UNSUPPORTED), no handle, no scratch, nothing allocated; `dtype` (RL_ATTN_BF16 / RL_ATTN_F16) is
+ * that of every `void*`.  M, n_tokens in [0, RL_ENCODER_MAX_TOKENS]: 0 returns RL_OK and writes nothing.  K, N and hidden are positive
+ * multiples of 32, hidden <= 8192 (RL_ERR_UNSUPPORTED above).  Every argument is checked before the first HIP call: RL_ERR_INVALID for
+ * a size outside its range, an unknown dtype or epilogue, an eps that is negative or not finite, a null or misaligned pointer
+ * (matrices and `part`: 16 bytes; 16-bit vectors and 16-bit outputs: 8; int32 arrays: 4).
+ *
+ * rl_encoder_embed: out[t] = LN(tok[ids[t]] + pos[positions[t]] + typ[type_ids ? type_ids[t] : 0]) for t < n_tokens, out
+ *   [n_tokens x hidden]; tok [vocab x hidden], pos [max_positions x hidden], typ [type_vocab x hidden]; every index is clamped into its
+ *   table; type_ids may be NULL.
+ * rl_encoder_linear: x [M x K] . W [N x K]^T (W as nn.Linear keeps it), by `epilogue`:
+ *     RL_ENC_EPI_BIAS     out16 [M x N] = the product + bias, rounded once               (the QKV projection)
+ *     RL_ENC_EPI_GELU     out16 [M x N] = gelu_erf(the product + bias), rounded once     (the up projection)
+ *     RL_ENC_EPI_PARTIAL  part [slices x M x N] f32: the raw sums of the K slices, slices = rl_encoder_linear_slices(N, K); bias is not
+ *                         read (the out and down projections: bias, residual and the slices' sum belong to the layer norm)
+ *   The output the epilogue does not write, and bias under RL_ENC_EPI_PARTIAL, may be NULL and are not looked at; the one it writes must
+ *   be given.  A row's bits depend on (N, K) and its own x row alone, not on M.
+ * rl_encoder_layer_norm: out[r] = LN(part[0][r] + .. + part[slices - 1][r] + bias + resid[r]) for r < M, the sum in that order in f32;
+ *   part [slices x M x hidden] f32, slices in [1, 8]; bias, ln_w, ln_b [hidden], resid and out [M x hidden].
+ * rl_encoder_linear_slices: host only; *slices = the K slices RL_ENC_EPI_PARTIAL uses at (N, K) -- a function of the two alone, in
+ *   [1, 8] -- so that a caller can size `part`. */
+#define RL_ENC_EPI_BIAS 0
+#define RL_ENC_EPI_GELU 1
+#define RL_ENC_EPI_PARTIAL 2
+int rl_encoder_embed(const int32_t* ids, const int32_t* positions, const int32_t* type_ids, int64_t n_tokens, const void* tok, int32_t vocab,
+                     const void* pos, int32_t max_positions, const void* typ, int32_t type_vocab, const void* ln_w, const void* ln_b,
+                     int32_t hidden, float eps, int32_t dtype, void* out, int mem, void* stream);
+int rl_encoder_linear(const void* x, int64_t M, int32_t K, const void* W, int32_t N, const void* bias, int32_t epilogue, int32_t dtype,
+                      void* out16, float* part, int mem, void* stream);
+int rl_encoder_layer_norm(const float* part, int32_t slices, int64_t M, int32_t hidden, const void* bias, const void* resid,
+                          const void* ln_w, const void* ln_b, float eps, int32_t dtype, void* out, int mem, void* stream);
+int rl_encoder_linear_slices(int32_t N, int32_t K, int32_t* slices);
+
 /* ---- a5: query adapter -----------------------------------------------------------------------
  * Replaces src/raglite/_search.py:62  `(Q @ q).astype(q.dtype)`; out[b] = A @ q[b].
  *   A [dim x dim] f32, queries [B x dim] f32, out_f32 [B x dim] or NULL, out_f16 or NULL. */

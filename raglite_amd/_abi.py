@@ -25,6 +25,7 @@ METRICS = {"cosine": 0, "dot": 1, "l2": 2}
 SYNTH_KINDS = {"uniform": 0, "small_int": 1}
 ATTN_DTYPES = {"bfloat16": 0, "float16": 1}  # RL_ATTN_BF16 / RL_ATTN_F16
 ENCODER_MAX_TOKENS = 256  # RL_ENCODER_MAX_TOKENS: the most token rows rl_encoder_forward takes in one pack
+ENCODER_EPILOGUES = {"bias": 0, "gelu": 1, "partial": 2}  # RL_ENC_EPI_*: what rl_encoder_linear does with the product
 # rl_option (include/raglite_hip.h "options"): route switches of an index; the library reads no environment variable
 OPTIONS = {
     "hi_search": 1, "hi_maxsim": 2, "hi_products": 3, "pp_pass": 4, "fused_topk": 5, "fused_hi": 6, "fused_pp": 7, "fused_topk_cap": 8,
@@ -65,6 +66,12 @@ _SIGNATURES = {
     "rl_encoder_forward": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_i32, c_i64, c_i32, c_void_p, c_int, c_void_p],
     "rl_encoder_info": [c_void_p, c_i64, C.POINTER(c_i32), C.POINTER(c_i64), C.POINTER(c_i64), C.POINTER(c_void_p), C.POINTER(c_i32)],
     "rl_encoder_destroy": [c_void_p],
+    "rl_encoder_embed": [c_void_p, c_void_p, c_void_p, c_i64, c_void_p, c_i32, c_void_p, c_i32, c_void_p, c_i32, c_void_p, c_void_p, c_i32,
+                         C.c_float, c_i32, c_void_p, c_int, c_void_p],
+    "rl_encoder_linear": [c_void_p, c_i64, c_i32, c_void_p, c_i32, c_void_p, c_i32, c_i32, c_void_p, c_void_p, c_int, c_void_p],
+    "rl_encoder_layer_norm": [c_void_p, c_i32, c_i64, c_i32, c_void_p, c_void_p, c_void_p, c_void_p, C.c_float, c_i32, c_void_p, c_int,
+                              c_void_p],
+    "rl_encoder_linear_slices": [c_i32, c_i32, C.POINTER(c_i32)],
     "rl_adapter_apply": [c_void_p, c_void_p, c_i32, c_i32, c_void_p, c_void_p, c_int, c_void_p],
     "rl_index_create": [C.POINTER(c_void_p), c_void_p, c_i64, c_i32, c_void_p, c_i64, c_int, c_int, c_void_p],
     "rl_index_destroy": [c_void_p],

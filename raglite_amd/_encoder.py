@@ -8,7 +8,7 @@ from __future__ import annotations
 import ctypes as C
 from typing import Any, Sequence
 
-from raglite_amd._abi import ATTN_DTYPES, ENCODER_MAX_TOKENS, MEM_DEVICE, check, lib
+from raglite_amd._abi import ATTN_DTYPES, ENCODER_EPILOGUES, ENCODER_MAX_TOKENS, MEM_DEVICE, check, lib
 from raglite_amd._attention import HEAD_DIMS
 from raglite_amd._ops_frame import _Args, _Handle
 
@@ -147,3 +147,101 @@ class NativeEncoder(_Handle):
         buf = torch.tensor(flat, dtype=torch.int32).pin_memory().to(self._params[0].device, non_blocking=True)
         typ = buf[2 * n: 3 * n] if type_rows is not None else None
         return self.forward_i32(buf[:n], buf[n: 2 * n], buf[(3 if type_rows is not None else 2) * n:], typ, len(lens), n, max(lens))
+
+
+# ---- the forward's three launches one at a time (rl_encoder_embed / _linear / _layer_norm): the same kernels, on the caller's tensors ----
+def _take(who: str, dtype: Any, *tensors: Any) -> tuple:
+    """(ATTN_DTYPES code, frame) for a call whose 16-bit CUDA tensors are `tensors` (None allowed): all contiguous, of `dtype`."""
+    name = _dtype_name(dtype)
+    if name not in ATTN_DTYPES:
+        raise ValueError(f"{who}: the tensors must be bfloat16 or float16")
+    for t in tensors:
+        if t is not None and not (t.is_cuda and t.is_contiguous() and t.dtype == dtype):
+            raise ValueError(f"{who}: every 16-bit argument must be a contiguous CUDA tensor of one dtype")
+    first = next(t for t in tensors if t is not None)
+    a = _Args.on(MEM_DEVICE, first.device)
+    a.ensure_device()
+    return ATTN_DTYPES[name], a
+
+
+def _ptr(t: Any) -> Any:
+    return None if t is None else t.data_ptr()
+
+
+def encoder_linear_slices(N: int, K: int) -> int:  # noqa: N803 - the header's names
+    """The K slices the partial epilogue of `encoder_linear` writes at (N, K): `part` is (slices, M, N) float32.  Host only."""
+    s = C.c_int32()
+    check(lib().rl_encoder_linear_slices(int(N), int(K), C.byref(s)))
+    return s.value
+
+
+def encoder_linear(x: Any, W: Any, bias: Any | None = None, epilogue: str = "bias", *, out: Any | None = None) -> Any:  # noqa: N803
+    """x (M, K) . W (N, K)^T through the skinny linear kernel.  epilogue "bias" / "gelu": (M, N) in x's dtype, `+ bias` or
+    `gelu_erf(. + bias)` rounded once; "partial": (encoder_linear_slices(N, K), M, N) float32, the raw K slices (bias is not read).
+    `out`, if given, is the tensor written (its shape and dtype as above)."""
+    import torch
+
+    if epilogue not in ENCODER_EPILOGUES:
+        raise ValueError('encoder_linear: epilogue must be "bias", "gelu" or "partial"')
+    partial = epilogue == "partial"
+    if x.dim() != 2 or W.dim() != 2 or x.shape[1] != W.shape[1]:
+        raise ValueError("encoder_linear: x must be (M, K) and W (N, K)")
+    if not partial and (bias is None or tuple(bias.shape) != (W.shape[0],)):
+        raise ValueError("encoder_linear: the bias and GELU epilogues take a bias of N elements")
+    dt, a = _take("encoder_linear", x.dtype, x, W, None if partial else bias)
+    M, K, N = int(x.shape[0]), int(x.shape[1]), int(W.shape[0])  # noqa: N806
+    shape = (encoder_linear_slices(N, K), M, N) if partial else (M, N)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32 if partial else x.dtype, device=x.device)
+    elif not (out.is_cuda and out.is_contiguous() and tuple(out.shape) == shape and out.dtype == (torch.float32 if partial else x.dtype)):
+        raise ValueError(f"encoder_linear: out must be a contiguous CUDA tensor of shape {shape}")
+    a.hold(x, W, bias, out)
+    check(lib().rl_encoder_linear(x.data_ptr(), M, K, W.data_ptr(), N, None if partial else bias.data_ptr(), ENCODER_EPILOGUES[epilogue], dt,
+                                  None if partial else out.data_ptr(), out.data_ptr() if partial else None, MEM_DEVICE, a.stream))
+    return out
+
+
+def encoder_layer_norm(part: Any, bias: Any, resid: Any, ln_w: Any, ln_b: Any, eps: float, *, out: Any | None = None) -> Any:
+    """LN(part[0] + .. + part[slices - 1] + bias + resid) per row: part (slices, M, hidden) float32, resid (M, hidden), the vectors
+    (hidden,), all 16-bit tensors of one dtype; returns (M, hidden) in it."""
+    import torch
+
+    if part.dim() != 3 or part.dtype != torch.float32 or not (part.is_cuda and part.is_contiguous()):
+        raise ValueError("encoder_layer_norm: part must be a contiguous float32 CUDA tensor (slices, M, hidden)")
+    slices, M, hidden = (int(v) for v in part.shape)  # noqa: N806
+    if tuple(resid.shape) != (M, hidden) or any(tuple(v.shape) != (hidden,) for v in (bias, ln_w, ln_b)):
+        raise ValueError("encoder_layer_norm: resid must be (M, hidden) and bias, ln_w, ln_b (hidden,)")
+    dt, a = _take("encoder_layer_norm", resid.dtype, bias, resid, ln_w, ln_b)
+    if out is None:
+        out = torch.empty((M, hidden), dtype=resid.dtype, device=resid.device)
+    elif not (out.is_cuda and out.is_contiguous() and tuple(out.shape) == (M, hidden) and out.dtype == resid.dtype):
+        raise ValueError("encoder_layer_norm: out must be a contiguous CUDA tensor (M, hidden) of resid's dtype")
+    a.hold(part, bias, resid, ln_w, ln_b, out)
+    check(lib().rl_encoder_layer_norm(part.data_ptr(), slices, M, hidden, bias.data_ptr(), resid.data_ptr(), ln_w.data_ptr(), ln_b.data_ptr(),
+                                      float(eps), dt, out.data_ptr(), MEM_DEVICE, a.stream))
+    return out
+
+
+def encoder_embed(ids: Any, positions: Any, type_ids: Any | None, tok: Any, pos: Any, typ: Any, ln_w: Any, ln_b: Any, eps: float, *,
+                  out: Any | None = None) -> Any:
+    """LN(tok[ids] + pos[positions] + typ[type_ids or 0]) per token, every index clamped into its table: ids, positions, type_ids
+    (or None) int32 CUDA tensors of n_tokens; tok, pos, typ (rows, hidden); returns (n_tokens, hidden) in the tables' dtype."""
+    import torch
+
+    n = int(ids.numel())
+    for t in (ids, positions, type_ids):
+        if t is not None and not (t.is_cuda and t.dtype == torch.int32 and t.is_contiguous() and t.numel() == n):
+            raise ValueError("encoder_embed: ids, positions and type_ids must be contiguous int32 CUDA tensors of one length")
+    hidden = int(tok.shape[-1])
+    if any(m.dim() != 2 or m.shape[1] != hidden for m in (tok, pos, typ)) or any(tuple(v.shape) != (hidden,) for v in (ln_w, ln_b)):
+        raise ValueError("encoder_embed: tok, pos, typ must be (rows, hidden) and ln_w, ln_b (hidden,)")
+    dt, a = _take("encoder_embed", tok.dtype, tok, pos, typ, ln_w, ln_b)
+    if out is None:
+        out = torch.empty((n, hidden), dtype=tok.dtype, device=tok.device)
+    elif not (out.is_cuda and out.is_contiguous() and tuple(out.shape) == (n, hidden) and out.dtype == tok.dtype):
+        raise ValueError("encoder_embed: out must be a contiguous CUDA tensor (n_tokens, hidden) of the tables' dtype")
+    a.hold(ids, positions, type_ids, tok, pos, typ, ln_w, ln_b, out)
+    check(lib().rl_encoder_embed(ids.data_ptr(), positions.data_ptr(), _ptr(type_ids), n, tok.data_ptr(), int(tok.shape[0]), pos.data_ptr(),
+                                 int(pos.shape[0]), typ.data_ptr(), int(typ.shape[0]), ln_w.data_ptr(), ln_b.data_ptr(), hidden, float(eps), dt,
+                                 out.data_ptr(), MEM_DEVICE, a.stream))
+    return out

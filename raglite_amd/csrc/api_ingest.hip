@@ -151,6 +151,82 @@ int rl_encoder_forward(rl_encoder* enc, const int32_t* ids, const int32_t* posit
     return RL_OK;
 }
 
+// The forward's three launches one at a time (what tests/test_gpu_encoder_kernels.py holds to float64): every argument checked here, the
+// launchers as rl_encoder_forward calls them.
+static_assert(RL_ENC_EPI_BIAS == ENC_EPI_BIAS && RL_ENC_EPI_GELU == ENC_EPI_GELU && RL_ENC_EPI_PARTIAL == ENC_EPI_PARTIAL,
+              "the header's epilogue names are the launcher's");
+
+static bool bad_width(int32_t n) { return n < 32 || n % 32 != 0; }
+static bool bad_eps(float eps) { return !(eps - eps == 0.0f) || eps < 0.0f; }
+
+int rl_encoder_embed(const int32_t* ids, const int32_t* positions, const int32_t* type_ids, int64_t n_tokens, const void* tok, int32_t vocab,
+                     const void* pos, int32_t max_positions, const void* typ, int32_t type_vocab, const void* ln_w, const void* ln_b,
+                     int32_t hidden, float eps, int32_t dtype, void* out, int mem, void* stream) {
+    if (mem != RL_MEM_DEVICE) return fail(RL_ERR_UNSUPPORTED, "rl_encoder_embed: device pointers only (mem must be RL_MEM_DEVICE)");
+    if (n_tokens < 0 || n_tokens > RL_ENCODER_MAX_TOKENS) return fail(RL_ERR_INVALID, "rl_encoder_embed: n_tokens must be in [0, RL_ENCODER_MAX_TOKENS]");
+    if (vocab < 1 || max_positions < 1 || type_vocab < 1) return fail(RL_ERR_INVALID, "rl_encoder_embed: every table must have at least one row");
+    if (bad_width(hidden)) return fail(RL_ERR_INVALID, "rl_encoder_embed: hidden must be a positive multiple of 32");
+    if (hidden > ENC_HIDDEN_MAX) return fail(RL_ERR_UNSUPPORTED, "rl_encoder_embed: hidden must be <= 8192");
+    if (bad_eps(eps)) return fail(RL_ERR_INVALID, "rl_encoder_embed: eps must be finite and >= 0");
+    if (dtype != RL_ATTN_BF16 && dtype != RL_ATTN_F16) return fail(RL_ERR_INVALID, "rl_encoder_embed: unknown dtype");
+    if (n_tokens == 0) return RL_OK;
+    if (!ids || !positions || !tok || !pos || !typ || !ln_w || !ln_b || !out) return fail(RL_ERR_INVALID, "rl_encoder_embed: null argument");
+    if (misaligned(ids, 4) || misaligned(positions, 4) || misaligned(type_ids, 4))
+        return fail(RL_ERR_INVALID, "rl_encoder_embed: the int32 arrays must be 4-byte aligned");
+    if (misaligned(tok, 16) || misaligned(pos, 16) || misaligned(typ, 16))
+        return fail(RL_ERR_INVALID, "rl_encoder_embed: the embedding tables must be 16-byte aligned");
+    if (misaligned(ln_w, 8) || misaligned(ln_b, 8) || misaligned(out, 8))
+        return fail(RL_ERR_INVALID, "rl_encoder_embed: ln_w, ln_b and out must be 8-byte aligned");
+    return launch_encoder_embed(ids, positions, type_ids, (int32_t)n_tokens, tok, vocab, pos, max_positions, typ, type_vocab, ln_w, ln_b, hidden,
+                                eps, dtype, out, as_stream(stream));
+}
+
+int rl_encoder_linear_slices(int32_t N, int32_t K, int32_t* slices) {
+    if (bad_width(N) || bad_width(K)) return fail(RL_ERR_INVALID, "rl_encoder_linear_slices: N and K must be positive multiples of 32");
+    if (!slices) return fail(RL_ERR_INVALID, "rl_encoder_linear_slices: slices is null");
+    *slices = encoder_ksplit(N, K);
+    return RL_OK;
+}
+
+int rl_encoder_linear(const void* x, int64_t M, int32_t K, const void* W, int32_t N, const void* bias, int32_t epilogue, int32_t dtype,
+                      void* out16, float* part, int mem, void* stream) {
+    if (mem != RL_MEM_DEVICE) return fail(RL_ERR_UNSUPPORTED, "rl_encoder_linear: device pointers only (mem must be RL_MEM_DEVICE)");
+    if (M < 0 || M > RL_ENCODER_MAX_TOKENS) return fail(RL_ERR_INVALID, "rl_encoder_linear: M must be in [0, RL_ENCODER_MAX_TOKENS]");
+    if (bad_width(K) || bad_width(N)) return fail(RL_ERR_INVALID, "rl_encoder_linear: K and N must be positive multiples of 32");
+    if (dtype != RL_ATTN_BF16 && dtype != RL_ATTN_F16) return fail(RL_ERR_INVALID, "rl_encoder_linear: unknown dtype");
+    if (epilogue != RL_ENC_EPI_BIAS && epilogue != RL_ENC_EPI_GELU && epilogue != RL_ENC_EPI_PARTIAL)
+        return fail(RL_ERR_INVALID, "rl_encoder_linear: unknown epilogue");
+    if (M == 0) return RL_OK;
+    const bool partial = epilogue == RL_ENC_EPI_PARTIAL;
+    if (!x || !W) return fail(RL_ERR_INVALID, "rl_encoder_linear: null argument");
+    if (partial && !part) return fail(RL_ERR_INVALID, "rl_encoder_linear: the partial epilogue writes part, which is null");
+    if (!partial && !out16) return fail(RL_ERR_INVALID, "rl_encoder_linear: the bias and GELU epilogues write out16, which is null");
+    if (!partial && !bias) return fail(RL_ERR_INVALID, "rl_encoder_linear: the bias and GELU epilogues read bias, which is null");
+    if (misaligned(x, 16) || misaligned(W, 16) || (partial && misaligned(part, 16)))
+        return fail(RL_ERR_INVALID, "rl_encoder_linear: x, W and part must be 16-byte aligned");
+    if (!partial && (misaligned(bias, 8) || misaligned(out16, 8)))
+        return fail(RL_ERR_INVALID, "rl_encoder_linear: bias and out16 must be 8-byte aligned");
+    return launch_encoder_linear(x, (int32_t)M, K, W, N, partial ? nullptr : bias, epilogue, dtype, partial ? nullptr : out16,
+                                 partial ? part : nullptr, as_stream(stream));
+}
+
+int rl_encoder_layer_norm(const float* part, int32_t slices, int64_t M, int32_t hidden, const void* bias, const void* resid, const void* ln_w,
+                          const void* ln_b, float eps, int32_t dtype, void* out, int mem, void* stream) {
+    if (mem != RL_MEM_DEVICE) return fail(RL_ERR_UNSUPPORTED, "rl_encoder_layer_norm: device pointers only (mem must be RL_MEM_DEVICE)");
+    if (M < 0 || M > RL_ENCODER_MAX_TOKENS) return fail(RL_ERR_INVALID, "rl_encoder_layer_norm: M must be in [0, RL_ENCODER_MAX_TOKENS]");
+    if (slices < 1 || slices > ENC_KSPLIT_MAX) return fail(RL_ERR_INVALID, "rl_encoder_layer_norm: slices must be in [1, 8]");
+    if (bad_width(hidden)) return fail(RL_ERR_INVALID, "rl_encoder_layer_norm: hidden must be a positive multiple of 32");
+    if (hidden > ENC_HIDDEN_MAX) return fail(RL_ERR_UNSUPPORTED, "rl_encoder_layer_norm: hidden must be <= 8192");
+    if (bad_eps(eps)) return fail(RL_ERR_INVALID, "rl_encoder_layer_norm: eps must be finite and >= 0");
+    if (dtype != RL_ATTN_BF16 && dtype != RL_ATTN_F16) return fail(RL_ERR_INVALID, "rl_encoder_layer_norm: unknown dtype");
+    if (M == 0) return RL_OK;
+    if (!part || !bias || !resid || !ln_w || !ln_b || !out) return fail(RL_ERR_INVALID, "rl_encoder_layer_norm: null argument");
+    if (misaligned(part, 16)) return fail(RL_ERR_INVALID, "rl_encoder_layer_norm: part must be 16-byte aligned");
+    if (misaligned(bias, 8) || misaligned(resid, 8) || misaligned(ln_w, 8) || misaligned(ln_b, 8) || misaligned(out, 8))
+        return fail(RL_ERR_INVALID, "rl_encoder_layer_norm: bias, resid, ln_w, ln_b and out must be 8-byte aligned");
+    return launch_encoder_ln(part, slices, (int32_t)M, hidden, bias, resid, ln_w, ln_b, eps, dtype, out, as_stream(stream));
+}
+
 // ---- document-batched ingestion: similarities, chunk / chunklet / sentence partitions (kernels in partition_sim.hip, partition_dp.hip,
 // ---- chunklet_dp.hip, sentence_dp.hip; the offset conventions in doc_batch.h) ---------------------------------------------------------
 // Host offsets are checked here, before the first HIP call; device offsets are clamped by the kernels (doc_batch.h).  doc_max > 0:
