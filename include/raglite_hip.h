@@ -196,11 +196,46 @@ int rl_encoder_layer_norm(const float* part, int32_t slices, int64_t M, int32_t 
                           const void* ln_w, const void* ln_b, float eps, int32_t dtype, void* out, int mem, void* stream);
 int rl_encoder_linear_slices(int32_t N, int32_t K, int32_t* slices);
 
+/* ---- the native forward of a pack larger than one token block (all text queries of a batched search) ----------------
+ * rl_encoder_forward's cap of RL_ENCODER_MAX_TOKENS rows is what ONE workgroup of the linear kernel keeps in accumulators.  Above it
+ * the linear kernel runs one workgroup per TOKEN BLOCK of 256 rows (block z: rows [256 z, min(256 z + 256, M))), each exactly the loop
+ * of a 256-row call: the same chunk order, k-step order, wave-order reduction and slice order.  So a row's bits stay a function of
+ * (N, K) and its own x row -- NOT of M, of the block it falls in, or of its place in the block -- and a sequence's rows out of a pack
+ * of any size are bit for bit the rows rl_encoder_forward gives for that sequence alone, wherever in the pack it lies, block edges
+ * included.  That is what lets a batch of queries share one forward and still return what the single calls return.
+ *
+ * rl_encoder_pack_workspace_bytes: host only; *bytes = the scratch a pack of n_tokens rows needs: the handle's own scratch layout walked
+ *   with that many rows (at RL_ENCODER_MAX_TOKENS: rl_encoder_info's scratch_bytes); monotone in n_tokens.  RL_ERR_INVALID for n_tokens
+ *   outside [0, RL_ENCODER_MAX_PACK_TOKENS], a null `bytes`, a null handle (looked at last).
+ * rl_encoder_forward_pack: rl_encoder_forward's arguments and contract, with n_tokens <= RL_ENCODER_MAX_PACK_TOKENS and the scratch in
+ *   `workspace`, device memory the CALLER owns: 16-byte aligned, workspace_bytes >= rl_encoder_pack_workspace_bytes(n_tokens); nothing
+ *   behind that many bytes is written.  1 + 7 * layers launches on `stream`, no allocation, no synchronisation.  The handle's own
+ *   scratch is not touched, so calls with different workspaces need no ordering among themselves or with rl_encoder_forward; calls
+ *   that share a workspace are ordered by the caller (one stream, or events).  At n_tokens <= RL_ENCODER_MAX_TOKENS the launches are
+ *   rl_encoder_forward's and so are the bits.  Checked before any HIP call, the handle last: everything rl_encoder_forward checks, in
+ *   its order, with n_tokens > RL_ENCODER_MAX_PACK_TOKENS (RL_ERR_UNSUPPORTED) in the place of its cap; then, with n_tokens > 0, a
+ *   null or misaligned workspace and (once the handle is known) one that is too small (RL_ERR_INVALID).
+ * rl_encoder_linear_pack: rl_encoder_linear with M in [0, RL_ENCODER_MAX_PACK_TOKENS] -- the blocked launch on its own. */
+#define RL_ENCODER_MAX_PACK_TOKENS 8192
+int rl_encoder_pack_workspace_bytes(const rl_encoder* enc, int64_t n_tokens, int64_t* bytes);
+int rl_encoder_forward_pack(rl_encoder* enc, const int32_t* ids, const int32_t* positions, const int32_t* type_ids,
+                            const int32_t* seq_offsets, int32_t n_seqs, int64_t n_tokens, int32_t max_len, void* out, void* workspace,
+                            int64_t workspace_bytes, int mem, void* stream);
+int rl_encoder_linear_pack(const void* x, int64_t M, int32_t K, const void* W, int32_t N, const void* bias, int32_t epilogue, int32_t dtype,
+                           void* out16, float* part, int mem, void* stream);
+
 /* ---- a5: query adapter -----------------------------------------------------------------------
  * Replaces src/raglite/_search.py:62  `(Q @ q).astype(q.dtype)`; out[b] = A @ q[b].
  *   A [dim x dim] f32, queries [B x dim] f32, out_f32 [B x dim] or NULL, out_f16 or NULL. */
 int rl_adapter_apply(const float* A, const float* queries, int32_t n_queries, int32_t dim,
                      float* out_f32, uint16_t* out_f16, int mem, void* stream);
+/* rl_adapter_apply picks its kernels by n_queries (a scan up to 4 queries, MFMA tiles above), so a query's bits depend on the size of
+ * the batch it comes in.  rl_adapter_apply_rows takes the same arguments and gives EVERY row the bits rl_adapter_apply gives it at
+ * n_queries = 1 -- the single-query scan's arithmetic, one query per workgroup row of ONE launch -- for callers whose batch must equal
+ * the loop of single calls (the text queries of a batched search).  RL_ERR_UNSUPPORTED for dim > 4096, or > 2048 where
+ * dim is no multiple of 4. */
+int rl_adapter_apply_rows(const float* A, const float* queries, int32_t n_queries, int32_t dim,
+                          float* out_f32, uint16_t* out_f16, int mem, void* stream);
 
 /* ---- index lifecycle -------------------------------------------------------------------------
  * The device-resident equivalent of the `chunk_embedding` table (src/raglite/_database.py:403-430):

@@ -25,6 +25,7 @@ METRICS = {"cosine": 0, "dot": 1, "l2": 2}
 SYNTH_KINDS = {"uniform": 0, "small_int": 1}
 ATTN_DTYPES = {"bfloat16": 0, "float16": 1}  # RL_ATTN_BF16 / RL_ATTN_F16
 ENCODER_MAX_TOKENS = 256  # RL_ENCODER_MAX_TOKENS: the most token rows rl_encoder_forward takes in one pack
+ENCODER_MAX_PACK_TOKENS = 8192  # RL_ENCODER_MAX_PACK_TOKENS: the most token rows rl_encoder_forward_pack takes (32 blocks of 256)
 ENCODER_EPILOGUES = {"bias": 0, "gelu": 1, "partial": 2}  # RL_ENC_EPI_*: what rl_encoder_linear does with the product
 # rl_option (include/raglite_hip.h "options"): route switches of an index; the library reads no environment variable
 OPTIONS = {
@@ -72,7 +73,12 @@ _SIGNATURES = {
     "rl_encoder_layer_norm": [c_void_p, c_i32, c_i64, c_i32, c_void_p, c_void_p, c_void_p, c_void_p, C.c_float, c_i32, c_void_p, c_int,
                               c_void_p],
     "rl_encoder_linear_slices": [c_i32, c_i32, C.POINTER(c_i32)],
+    "rl_encoder_pack_workspace_bytes": [c_void_p, c_i64, C.POINTER(c_i64)],
+    "rl_encoder_forward_pack": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_i32, c_i64, c_i32, c_void_p, c_void_p, c_i64, c_int,
+                                c_void_p],
+    "rl_encoder_linear_pack": [c_void_p, c_i64, c_i32, c_void_p, c_i32, c_void_p, c_i32, c_i32, c_void_p, c_void_p, c_int, c_void_p],
     "rl_adapter_apply": [c_void_p, c_void_p, c_i32, c_i32, c_void_p, c_void_p, c_int, c_void_p],
+    "rl_adapter_apply_rows": [c_void_p, c_void_p, c_i32, c_i32, c_void_p, c_void_p, c_int, c_void_p],
     "rl_index_create": [C.POINTER(c_void_p), c_void_p, c_i64, c_i32, c_void_p, c_i64, c_int, c_int, c_void_p],
     "rl_index_destroy": [c_void_p],
     "rl_index_info": [c_void_p, C.POINTER(c_i64), C.POINTER(c_i32), C.POINTER(c_i64), C.POINTER(c_int)],

@@ -1,18 +1,20 @@
 """The native encoder forward for short packs through the C ABI (`rl_encoder_*`, raglite_amd/csrc/encoder.hip): the
 whole forward of `_torch_embedder`'s `Encoder` over a packed batch of at most `MAX_TOKENS` tokens, enqueued by one call -- what a text
-query needs, where the torch route is bound by launches and Python.  CUDA tensors only, like `_attention.py`, which is why the wrapper
-lives here and not among the `_ops*` modules."""
+query needs, where the torch route is bound by launches and Python -- and, for all text queries of a batched search at once, over a pack of
+up to `MAX_PACK_TOKENS` tokens in token blocks of `MAX_TOKENS` rows (`forward_pack`), every sequence with the bits of a
+call of its own.  CUDA tensors only, like `_attention.py`, which is why the wrapper lives here and not among the `_ops*` modules."""
 
 from __future__ import annotations
 
 import ctypes as C
 from typing import Any, Sequence
 
-from raglite_amd._abi import ATTN_DTYPES, ENCODER_EPILOGUES, ENCODER_MAX_TOKENS, MEM_DEVICE, check, lib
+from raglite_amd._abi import ATTN_DTYPES, ENCODER_EPILOGUES, ENCODER_MAX_PACK_TOKENS, ENCODER_MAX_TOKENS, MEM_DEVICE, check, lib
 from raglite_amd._attention import HEAD_DIMS
 from raglite_amd._ops_frame import _Args, _Handle
 
 MAX_TOKENS = ENCODER_MAX_TOKENS
+MAX_PACK_TOKENS = ENCODER_MAX_PACK_TOKENS  # `forward_pack`: token blocks of MAX_TOKENS rows, a sequence's bits as in a call of its own
 HIDDEN_MAX, FFN_MAX = 8192, 32768
 _LAYER_PARAMS = ("qkv.weight", "qkv.bias", "out.weight", "out.bias", "ln1.weight", "ln1.bias", "up.weight", "up.bias", "down.weight",
                  "down.bias", "ln2.weight", "ln2.bias")  # the order of rl_encoder_create's layer_params
@@ -34,6 +36,8 @@ class NativeEncoder(_Handle):
         self.module, self.shape = encoder_module, shape
         self._key: tuple | None = None
         self._held: list = []
+        self._workspace: Any | None = None  # `forward_pack`'s scratch: a uint8 CUDA tensor, grown when a larger pack arrives
+        self.pack_forwards = 0  # `rl_encoder_forward_pack` calls made (what a batch of text queries should cost: one)
         self._collect()
 
     def _collect(self) -> None:
@@ -57,6 +61,12 @@ class NativeEncoder(_Handle):
         if shape.hidden % 32 or shape.ffn % 32 or shape.hidden > HIDDEN_MAX or shape.ffn > FFN_MAX or shape.layers < 1:
             return False
         return 1 <= n_tokens <= MAX_TOKENS
+
+    @staticmethod
+    def supports_pack(shape: Any, dtype: Any, n_tokens: int, device: Any = "cuda") -> bool:
+        """Does `forward_pack` take a pack of `n_tokens` tokens of this shape, element type and device?  `supports` with the cap of
+        `MAX_PACK_TOKENS`."""
+        return 1 <= n_tokens <= MAX_PACK_TOKENS and NativeEncoder.supports(shape, dtype, 1, device)
 
     def _ensure_handle(self) -> None:
         if self.module.tok.weight is not self._params[0] or self.module.layers[-1].ln2.bias is not self._params[-1]:
@@ -114,6 +124,68 @@ class NativeEncoder(_Handle):
                                        seq_offsets.data_ptr(), int(n_seqs), int(n_tokens), int(max_len), out.data_ptr(), MEM_DEVICE, a.stream))
         return out
 
+    def workspace_bytes(self, n_tokens: int) -> int:
+        """The device bytes `rl_encoder_forward_pack` needs for a pack of `n_tokens` rows (host only once the handle exists)."""
+        a = _Args.on(MEM_DEVICE, self._params[0].device)
+        a.ensure_device()
+        self._ensure_handle()
+        n = C.c_int64()
+        check(lib().rl_encoder_pack_workspace_bytes(self._handle, int(n_tokens), C.byref(n)))
+        return n.value
+
+    def forward_pack_i32(self, ids: Any, positions: Any, seq_offsets: Any, type_ids: Any | None, n_seqs: int, n_tokens: int, max_len: int,
+                         out: Any | None = None, workspace: Any | None = None) -> Any:
+        """`forward_i32` for up to `MAX_PACK_TOKENS` tokens (`rl_encoder_forward_pack`).  `workspace`: a contiguous uint8 CUDA tensor of
+        at least `workspace_bytes(n_tokens)` bytes; None: the one kept on this object, grown when the pack needs more (calls that share
+        it are ordered by torch's current stream, as torch's own allocator expects of a tensor's users)."""
+        import torch
+
+        dev = self._params[0].device
+        a = _Args.on(MEM_DEVICE, dev)
+        a.ensure_device()
+        self._ensure_handle()
+        for t in (ids, positions, seq_offsets, type_ids):
+            if t is not None and not (t.is_cuda and t.dtype == torch.int32 and t.is_contiguous()):
+                raise ValueError("NativeEncoder: ids, positions, seq_offsets and type_ids must be contiguous int32 CUDA tensors")
+        if ids.numel() < n_tokens or positions.numel() < n_tokens or seq_offsets.numel() < n_seqs + 1 or (type_ids is not None and type_ids.numel() < n_tokens):
+            raise ValueError("NativeEncoder: an argument is shorter than n_tokens / n_seqs + 1")
+        if workspace is None:
+            need = self.workspace_bytes(n_tokens) if 0 <= n_tokens <= MAX_PACK_TOKENS else 0  # (past the cap the C call says so)
+            if self._workspace is None or self._workspace.device != dev or self._workspace.numel() < need:
+                self._workspace = torch.empty(need, dtype=torch.uint8, device=dev)
+            workspace = self._workspace
+        elif not (workspace.is_cuda and workspace.dtype == torch.uint8 and workspace.is_contiguous()):
+            raise ValueError("NativeEncoder: workspace must be a contiguous uint8 CUDA tensor")
+        if out is None:
+            out = torch.empty((n_tokens, self.shape.hidden), dtype=self._params[0].dtype, device=dev)
+        a.hold(ids, positions, seq_offsets, type_ids, out, workspace)
+        check(lib().rl_encoder_forward_pack(self._handle, ids.data_ptr(), positions.data_ptr(), type_ids.data_ptr() if type_ids is not None else None,
+                                            seq_offsets.data_ptr(), int(n_seqs), int(n_tokens), int(max_len), out.data_ptr(),
+                                            workspace.data_ptr(), int(workspace.numel()), MEM_DEVICE, a.stream))
+        self.pack_forwards += 1
+        return out
+
+    def forward_pack(self, ids: Any, seq_offsets: Any, lengths_host: Sequence[int], type_ids: Any | None = None) -> Any:
+        """`forward` for a pack of up to `MAX_PACK_TOKENS` tokens: every sequence's rows are bit for bit the rows `forward` gives for
+        that sequence alone."""
+        import torch
+
+        n = int(ids.shape[0])
+        if n == 0 or n != sum(lengths_host):
+            raise ValueError("NativeEncoder.forward_pack: needs at least one token, and lengths that add up to the number of tokens")
+        if n > MAX_PACK_TOKENS:
+            raise ValueError(f"NativeEncoder.forward_pack: at most {MAX_PACK_TOKENS} tokens per pack")
+        pos = torch.tensor([t + self.shape.position_offset for ln in lengths_host for t in range(ln)], dtype=torch.int32)
+        pos = pos.pin_memory().to(ids.device, non_blocking=True)
+        typ = None if type_ids is None else type_ids.to(torch.int32).contiguous()
+        return self.forward_pack_i32(ids.to(torch.int32).contiguous(), pos, seq_offsets.to(torch.int32).contiguous(), typ, len(lengths_host),
+                                     n, max(lengths_host))
+
+    def forward_pack_rows(self, rows: Sequence[Sequence[int]], type_rows: Sequence[Sequence[int]] | None = None) -> Any:
+        """`forward_rows` for up to `MAX_PACK_TOKENS` tokens: still ONE copy from pinned memory."""
+        buf, typ, n, lens = self._upload_rows(rows, type_rows)
+        return self.forward_pack_i32(buf[:n], buf[n: 2 * n], buf[(3 if typ is not None else 2) * n:], typ, len(lens), n, max(lens))
+
     def forward(self, ids: Any, seq_offsets: Any, lengths_host: Sequence[int], type_ids: Any | None = None) -> Any:
         """`Encoder.forward_packed`'s arguments: ids (n_tokens,) CUDA integers, the sequences one after another; seq_offsets int32
         (n_seqs + 1) on the device; lengths_host their lengths as Python integers (the positions are made from them on the host)."""
@@ -133,6 +205,12 @@ class NativeEncoder(_Handle):
     def forward_rows(self, rows: Sequence[Sequence[int]], type_rows: Sequence[Sequence[int]] | None = None) -> Any:
         """The forward of token-id lists (each with its `<s>` / `</s>`): ids, positions, type ids and offsets go up in ONE copy from
         pinned memory."""
+        buf, typ, n, lens = self._upload_rows(rows, type_rows)
+        return self.forward_i32(buf[:n], buf[n: 2 * n], buf[(3 if typ is not None else 2) * n:], typ, len(lens), n, max(lens))
+
+    def _upload_rows(self, rows: Sequence[Sequence[int]], type_rows: Sequence[Sequence[int]] | None) -> tuple:
+        """(the int32 device buffer ids | positions | [type ids] | offsets, its type-id part or None, n_tokens, lengths) of token-id
+        lists: one pinned upload."""
         import itertools
 
         import torch
@@ -145,8 +223,7 @@ class NativeEncoder(_Handle):
             flat += list(itertools.chain.from_iterable(type_rows))
         flat += list(itertools.accumulate(lens, initial=0))
         buf = torch.tensor(flat, dtype=torch.int32).pin_memory().to(self._params[0].device, non_blocking=True)
-        typ = buf[2 * n: 3 * n] if type_rows is not None else None
-        return self.forward_i32(buf[:n], buf[n: 2 * n], buf[(3 if type_rows is not None else 2) * n:], typ, len(lens), n, max(lens))
+        return buf, (buf[2 * n: 3 * n] if type_rows is not None else None), n, lens
 
 
 # ---- the forward's three launches one at a time (rl_encoder_embed / _linear / _layer_norm): the same kernels, on the caller's tensors ----
@@ -179,26 +256,36 @@ def encoder_linear(x: Any, W: Any, bias: Any | None = None, epilogue: str = "bia
     """x (M, K) . W (N, K)^T through the skinny linear kernel.  epilogue "bias" / "gelu": (M, N) in x's dtype, `+ bias` or
     `gelu_erf(. + bias)` rounded once; "partial": (encoder_linear_slices(N, K), M, N) float32, the raw K slices (bias is not read).
     `out`, if given, is the tensor written (its shape and dtype as above)."""
+    return _linear("rl_encoder_linear", "encoder_linear", x, W, bias, epilogue, out)
+
+
+def _linear(entry: str, who: str, x: Any, W: Any, bias: Any | None, epilogue: str, out: Any | None) -> Any:  # noqa: N803
     import torch
 
     if epilogue not in ENCODER_EPILOGUES:
-        raise ValueError('encoder_linear: epilogue must be "bias", "gelu" or "partial"')
+        raise ValueError(f'{who}: epilogue must be "bias", "gelu" or "partial"')
     partial = epilogue == "partial"
     if x.dim() != 2 or W.dim() != 2 or x.shape[1] != W.shape[1]:
-        raise ValueError("encoder_linear: x must be (M, K) and W (N, K)")
+        raise ValueError(f"{who}: x must be (M, K) and W (N, K)")
     if not partial and (bias is None or tuple(bias.shape) != (W.shape[0],)):
-        raise ValueError("encoder_linear: the bias and GELU epilogues take a bias of N elements")
-    dt, a = _take("encoder_linear", x.dtype, x, W, None if partial else bias)
+        raise ValueError(f"{who}: the bias and GELU epilogues take a bias of N elements")
+    dt, a = _take(who, x.dtype, x, W, None if partial else bias)
     M, K, N = int(x.shape[0]), int(x.shape[1]), int(W.shape[0])  # noqa: N806
     shape = (encoder_linear_slices(N, K), M, N) if partial else (M, N)
     if out is None:
         out = torch.empty(shape, dtype=torch.float32 if partial else x.dtype, device=x.device)
     elif not (out.is_cuda and out.is_contiguous() and tuple(out.shape) == shape and out.dtype == (torch.float32 if partial else x.dtype)):
-        raise ValueError(f"encoder_linear: out must be a contiguous CUDA tensor of shape {shape}")
+        raise ValueError(f"{who}: out must be a contiguous CUDA tensor of shape {shape}")
     a.hold(x, W, bias, out)
-    check(lib().rl_encoder_linear(x.data_ptr(), M, K, W.data_ptr(), N, None if partial else bias.data_ptr(), ENCODER_EPILOGUES[epilogue], dt,
+    check(getattr(lib(), entry)(x.data_ptr(), M, K, W.data_ptr(), N, None if partial else bias.data_ptr(), ENCODER_EPILOGUES[epilogue], dt,
                                   None if partial else out.data_ptr(), out.data_ptr() if partial else None, MEM_DEVICE, a.stream))
     return out
+
+
+def encoder_linear_pack(x: Any, W: Any, bias: Any | None = None, epilogue: str = "bias", *, out: Any | None = None) -> Any:  # noqa: N803
+    """`encoder_linear` for M up to `MAX_PACK_TOKENS` rows (`rl_encoder_linear_pack`): above `MAX_TOKENS` one workgroup per token block
+    of 256 rows, every row with the bits `encoder_linear` gives it."""
+    return _linear("rl_encoder_linear_pack", "encoder_linear_pack", x, W, bias, epilogue, out)
 
 
 def encoder_layer_norm(part: Any, bias: Any, resid: Any, ln_w: Any, ln_b: Any, eps: float, *, out: Any | None = None) -> Any:

@@ -71,8 +71,13 @@ def synth_fill(out, seed: int, start: int = 0, kind: str = "uniform"):
     return out
 
 
-def adapter_apply(A, queries, *, want_f16: bool = False):
-    """a5: out[b] = A @ q[b] (`src/raglite/_search.py:62`).  Accepts a vector or a (B, dim) batch."""
+def adapter_apply(A, queries, *, want_f16: bool = False, rows: bool = False):
+    """a5: out[b] = A @ q[b] (`src/raglite/_search.py:62`).  Accepts a vector or a (B, dim) batch.  `rows`: `rl_adapter_apply_rows`,
+    which gives every row of a batch the bits this call gives a single vector (the batched routes multiply with other kernels)."""
+    if rows:
+        from raglite_amd._adapter_rows import adapter_apply_rows  # (its `lib()` call is not one of this module's: see there)
+
+        return adapter_apply_rows(A, queries, want_f16=want_f16)
     a = _Args()
     A, p_a = a.inp(A, np.float32)  # noqa: N806
     q = queries

@@ -37,7 +37,7 @@ from typing import Any, Callable, Sequence
 
 import numpy as np
 
-from raglite_amd import _keyword, _metadata, _ops
+from raglite_amd import _embed, _keyword, _metadata, _ops
 from raglite_amd._config import DEFAULT_CHUNK_MAX_SIZE, HotPathConfig
 from raglite_amd._embed import embed_strings
 
@@ -729,6 +729,86 @@ def _embed_one_by_one(queries: Sequence[str], query_vectors, cfg: Any, gi: GpuIn
     return np.stack([np.asarray(q, dtype=np.float32).ravel() for q in rows])
 
 
+def _config_embedder(cfg: Any) -> Any | None:
+    """`embedder_for(cfg)`, or None where no token-level embedder is installed (the loop then says so, if it gets that far)."""
+    try:
+        return _embed.embedder_for(cfg)
+    except ModuleNotFoundError:
+        return None
+
+
+def _query_pack(queries: Sequence[Any], query_vectors, cfg: Any, embedder: Any | None = None):
+    """The token matrices of a batch's text queries from ONE `embedder.embed_pack` call, as (indices of the string
+    entries, their matrices, the embedder), or None where the batch embeds one by one: `query_vectors` given, no string entry, an
+    embedder other than a late-chunking one with `embed_pack`, or a string whose single call would not be one whole segment (empty, or
+    holding the sentinel: the loop raises for it, and so must the batch)."""
+    if query_vectors is not None:
+        return None
+    at = [b for b, q in enumerate(queries) if isinstance(q, str)]
+    if not at or _embed.embedding_type(config=cfg) != "late_chunking":
+        return None
+    texts = [queries[b] for b in at]
+    if any(not t or _embed.SENTINEL in t for t in texts):
+        return None
+    embedder = embedder if embedder is not None else _config_embedder(cfg)
+    embed_pack = getattr(embedder, "embed_pack", None)
+    if embed_pack is None:
+        return None
+    mats = embed_pack(texts)
+    if mats is None:
+        return None
+    if any(len(embedder.tokenize(t.encode(), add_bos=False)) == 0 for t in texts):  # (no token rows to apportion: the loop's business)
+        return None
+    if len(mats) != len(texts):
+        raise ValueError("embed_pack must return one token matrix per text")
+    return at, list(mats), embedder
+
+
+def _pooled_pack(mats: Sequence[Any], cfg: Any, gi: GpuIndex) -> np.ndarray:
+    """`_embed_one_by_one`'s rows for the strings whose token matrices are `mats`, as (B, dim) float32 with its bits: ONE `rl_pool_norm`
+    over the B spans (a span's result does not depend on the other spans of a call; eps = 0 and the normalisation as
+    `embed_strings_with_late_chunking` has them), the fp16 cast, the single-query adapter arithmetic for all rows in one launch
+    (`rl_adapter_apply_rows`), the cast back to fp16 -- on the device where the matrices are, read back once."""
+    lengths = np.asarray([len(m) for m in mats], dtype=np.int64)
+    ends = np.cumsum(lengths)
+    tokens = _embed._stack([_embed._token_matrix(m) for m in mats])  # noqa: SLF001
+    adapt = cfg.vector_search_query_adapter and gi.query_adapter is not None
+    if _embed._is_device_tensor(tokens):  # noqa: SLF001
+        import torch
+
+        b, e = torch.as_tensor(ends - lengths, device=tokens.device), torch.as_tensor(ends, device=tokens.device)
+        _, pooled = _ops.pool_norm(tokens, b, e, normalize=bool(cfg.embedder_normalize), eps=0.0)
+        if adapt:
+            A = torch.as_tensor(np.ascontiguousarray(gi.query_adapter, dtype=np.float32)).to(tokens.device)  # noqa: N806
+            pooled = _ops.adapter_apply(A, pooled.float(), rows=True)
+        pooled = pooled.cpu().numpy()
+    else:
+        _, pooled = _ops.pool_norm(tokens, ends - lengths, ends, normalize=bool(cfg.embedder_normalize), eps=0.0)
+        if adapt:
+            pooled = _ops.adapter_apply(gi.query_adapter, pooled.astype(np.float32), rows=True)
+    return pooled.astype(np.float16).astype(np.float32)  # (`.astype(q.dtype)`: the embedding's fp16; then the query matrix's float32)
+
+
+def _embed_queries(queries: Sequence[Any], query_vectors, cfg: Any, gi: GpuIndex, pack=None) -> np.ndarray:
+    """`_embed_one_by_one`'s matrix, bit for bit, with the batch's text queries through one packed native forward where the config's
+    embedder offers one (`_query_pack`; `pack`: its result when the caller has made the call already, to share it).  Raw-vector
+    entries, `query_vectors=`, every other embedder and a None from `embed_pack` go through `_embed_one_by_one` as before."""
+    pack = pack if pack is not None else _query_pack(queries, query_vectors, cfg)
+    if pack is None:
+        return _embed_one_by_one(queries, query_vectors, cfg, gi)
+    at, mats, _ = pack
+    pooled = _pooled_pack(mats, cfg, gi)
+    if len(at) == len(queries):
+        return pooled
+    rest = [b for b in range(len(queries)) if not isinstance(queries[b], str)]
+    others = _embed_one_by_one([queries[b] for b in rest], None, cfg, gi)
+    if others.shape[1] != pooled.shape[1]:
+        raise ValueError("all input arrays must have the same shape")  # (np.stack's words in _embed_one_by_one)
+    Q = np.empty((len(queries), pooled.shape[1]), dtype=np.float32)  # noqa: N806
+    Q[at], Q[rest] = pooled, others
+    return Q
+
+
 # ---- batches with one metadata filter per query ------------------------------------------------------------------
 def _batch_filters(metadata_filter, B: int) -> list[dict | None]:
     """A batch's metadata_filter -- None or one dict for every query, or a sequence of B entries, each None or a dict -- as the B
@@ -853,13 +933,14 @@ def _collect(gi: GpuIndex, out: list, active: Sequence[int], scores, chunks, cou
     return out
 
 
-def _plan_vector_batch(gi: GpuIndex, cfg: Any, queries: list, num_results: int, oversample: int, metadata_filter, query_vectors):
+def _plan_vector_batch(gi: GpuIndex, cfg: Any, queries: list, num_results: int, oversample: int, metadata_filter, query_vectors,
+                       pack=None):
     """The host decisions of a batch of vector searches (B >= 1), in vector_search's order: (query matrix, num_hits, filter plan, the
     queries that search the device -- the others return ([], [])); raises where the loop would raise."""
     B = len(queries)
     filters = _batch_filters(metadata_filter, B)
     _self_query(cfg, queries)
-    Q = _embed_one_by_one(queries, query_vectors, cfg, gi)
+    Q = _embed_queries(queries, query_vectors, cfg, gi, pack)
     num_hits = round(oversample * cfg.chunk_max_size / DEFAULT_CHUNK_MAX_SIZE) * max(num_results, 10)  # (`_search.py:66-67`)
     plan = plan_filters(filters, gi.metadata, _rows_per_chunk(gi), gi)
     active = [b for b in range(B) if _vector_searches(gi, filters[b], plan.of(b)[0], num_hits, num_results)]
@@ -928,14 +1009,14 @@ class HybridPlan:
 
 
 def _plan_hybrid_batch(gi: GpuIndex, cfg: Any, queries: list, num_results: int, oversample: int, metadata_filter,
-                       query_vectors) -> HybridPlan:
+                       query_vectors, pack=None) -> HybridPlan:
     """hybrid_search's decisions for every query of a batch (B >= 1), in its order; raises where the loop would raise."""
     B = len(queries)
     if getattr(cfg, "self_query", False):
         raise NotImplementedError("self_query needs the LLM stack, which is outside this package")
     filters = _batch_filters(metadata_filter, B)
     n_each = oversample * num_results  # what hybrid_search asks of each half
-    Q = _embed_one_by_one(queries, query_vectors, cfg, gi)
+    Q = _embed_queries(queries, query_vectors, cfg, gi, pack)
     num_hits = round(VECTOR_SEARCH_OVERSAMPLE * cfg.chunk_max_size / DEFAULT_CHUNK_MAX_SIZE) * max(n_each, 10)
     plan = plan_filters(filters, gi.metadata, _rows_per_chunk(gi), gi)
     # (hybrid_search runs the keyword half for query strings only; a query given as a vector has none)
@@ -1026,6 +1107,10 @@ class MaxSimRanker:
     def __init__(self, index: GpuIndex, query_encoder: Callable[[str], np.ndarray]) -> None:
         self.index = index
         self.query_encoder = query_encoder
+        # set by `from_embedder`: the token-level embedder, and `(queries, mats=None) -> list of (nq, dim) | None`, every query's
+        # `query_encoder` result from one `embedder.embed_pack` call (`mats`: that call's result where the caller made it already)
+        self.embedder: Any | None = None
+        self.query_batch_encoder: Callable[..., list | None] | None = None
 
     @classmethod
     def from_embedder(cls, index: GpuIndex, embedder: Any, *, normalize: bool = True, max_vectors: int = 32) -> "MaxSimRanker":
@@ -1033,15 +1118,34 @@ class MaxSimRanker:
         the query's token embeddings, L2-normalised like the stored chunklet vectors, at most `max_vectors` of them
         (ColBERT's fixed query length; the first tokens are kept)."""
 
-        def encode(query: str) -> np.ndarray:
-            m = embedder.embed(query)
-            m = m.float().cpu().numpy() if hasattr(m, "cpu") else np.asarray(m, dtype=np.float32)
+        def finish(m: np.ndarray) -> np.ndarray:
             m = m[:max_vectors]
             if normalize:
                 m = m / np.maximum(np.linalg.norm(m, axis=1, keepdims=True), np.finfo(np.float32).eps)
             return m.astype(np.float32)
 
-        return cls(index, encode)
+        def encode(query: str) -> np.ndarray:
+            m = embedder.embed(query)
+            return finish(m.float().cpu().numpy() if hasattr(m, "cpu") else np.asarray(m, dtype=np.float32))
+
+        def encode_batch(queries: Sequence[str], mats: Sequence[Any] | None = None) -> list | None:
+            """`encode` of every query from one `embed_pack` call: the same NumPy lines on the same token rows, so the same bits;
+            None where the embedder has no pack route for these queries."""
+            if mats is None:
+                embed_pack = getattr(embedder, "embed_pack", None)
+                mats = embed_pack(list(queries)) if embed_pack is not None else None
+            if mats is None:
+                return None
+            if len(mats) and all(_ops._is_torch(m) for m in mats):  # noqa: SLF001 - one copy to the host, cut there
+                import torch
+
+                host = torch.cat([m.float() for m in mats]).cpu().numpy()
+                mats = np.split(host, np.cumsum([len(m) for m in mats])[:-1])
+            return [finish(np.asarray(m, dtype=np.float32)) for m in mats]
+
+        ranker = cls(index, encode)
+        ranker.embedder, ranker.query_batch_encoder = embedder, encode_batch
+        return ranker
 
     def score(self, query: str, ordinals: Sequence[int]) -> np.ndarray:
         qv = np.asarray(self.query_encoder(query), dtype=np.float32)
@@ -1049,11 +1153,14 @@ class MaxSimRanker:
         cand = np.asarray(ordinals, dtype=np.int32).reshape(1, -1)
         return np.asarray(self.index.index.maxsim_rerank(qv, cand))[0]
 
-    def _token_vectors(self, queries: Sequence[Any], query_token_vectors=None) -> list[np.ndarray]:
-        """Each query's (nq, dim) float32 token vectors: `query_token_vectors[b]` when given, else `query_encoder(queries[b])`, one
-        query at a time (the encoder is host code)."""
+    def _token_vectors(self, queries: Sequence[Any], query_token_vectors=None, mats: Sequence[Any] | None = None) -> list[np.ndarray]:
+        """Each query's (nq, dim) float32 token vectors: `query_token_vectors[b]` when given; else, for a ranker made by `from_embedder`
+        whose embedder packs these queries, all of them from one forward (`query_batch_encoder`; `mats`: the token matrices of that
+        forward where the caller has made it already); else `query_encoder(queries[b])`, one query at a time."""
         if query_token_vectors is not None and len(query_token_vectors) != len(queries):
             raise ValueError("query_token_vectors must have one (nq, dim) matrix per query")
+        if query_token_vectors is None and self.query_batch_encoder is not None and len(queries) and all(isinstance(q, str) for q in queries):
+            query_token_vectors = self.query_batch_encoder(queries, mats)
         out = []
         for b, q in enumerate(queries):
             v = query_token_vectors[b] if query_token_vectors is not None else self.query_encoder(q)
@@ -1262,6 +1369,21 @@ def search_and_rerank_chunks_batch(queries: Sequence[str], *, num_results: int =
     return [chunk_lookup(ids) if chunk_lookup is not None and ids else ids for ids in found]
 
 
+def _shared_pack(cfg: Any, ranker: "MaxSimRanker", queries: Sequence[Any], query_vectors, query_token_vectors):
+    """One forward for both sides of a batched search-and-rerank: where the ranker was made `from_embedder` over the very embedder the
+    config embeds queries with, every query is a string and neither side's vectors are given, (`_query_pack`'s result for the pooled
+    query matrix, the same token matrices for the MaxSim vectors); else (None, None) and each side embeds for itself."""
+    if query_vectors is not None or query_token_vectors is not None or ranker.query_batch_encoder is None:
+        return None, None
+    if not all(isinstance(q, str) for q in queries) or _embed.embedding_type(config=cfg) != "late_chunking":
+        return None, None
+    embedder = _config_embedder(cfg)
+    if embedder is None or embedder is not ranker.embedder:
+        return None, None
+    pack = _query_pack(queries, None, cfg, embedder)
+    return (pack, pack[1]) if pack is not None else (None, None)
+
+
 def _ids_of(gi: GpuIndex, out: list, group: Sequence[int], chunks, counts) -> None:
     for i, b in enumerate(group):
         out[b] = [gi.chunk_ids[c] for c in chunks[i, : int(counts[i])].tolist()]
@@ -1272,12 +1394,13 @@ def _hybrid_rerank_device(gi, cfg, ranker, queries, num_results, n_cand, metadat
     """The device path of search_and_rerank_chunks_batch over hybrid_search: its host decisions are hybrid_search_batch's.  With
     `spans` each group's call is the span pipeline and the result is every query's spans."""
     B = len(queries)
-    hp = _plan_hybrid_batch(gi, cfg, queries, n_cand, 2, metadata_filter, query_vectors)  # (hybrid_search's own oversample: 2)
+    pack, mats = _shared_pack(cfg, ranker, queries, query_vectors, query_token_vectors)
+    hp = _plan_hybrid_batch(gi, cfg, queries, n_cand, 2, metadata_filter, query_vectors, pack)  # (hybrid_search's own oversample: 2)
     out: list = [[] for _ in range(B)]
     if hp.R == 0:
         return out
     k = min(num_results, hp.k)
-    vecs = ranker._token_vectors(queries, query_token_vectors)  # noqa: SLF001
+    vecs = ranker._token_vectors(queries, query_token_vectors, mats)  # noqa: SLF001
     for group in _groups_by_nq(vecs):
         qf, lim = _device_filters(hp.plan, group)
         V = np.stack([vecs[b] for b in group])
@@ -1308,13 +1431,16 @@ def _vector_rerank_device(gi, cfg, ranker, queries, num_results, n_cand, metadat
     """The device path over vector_search: its host decisions are vector_search_batch's; the pipeline call without a keyword index
     fuses the vector list alone, which keeps its order.  `spans` as in _hybrid_rerank_device."""
     B = len(queries)
-    Q, num_hits, plan, active = _plan_vector_batch(gi, cfg, queries, n_cand, VECTOR_SEARCH_OVERSAMPLE, metadata_filter, query_vectors)
+    pack, mats = _shared_pack(cfg, ranker, queries, query_vectors, query_token_vectors)
+    Q, num_hits, plan, active = _plan_vector_batch(gi, cfg, queries, n_cand, VECTOR_SEARCH_OVERSAMPLE, metadata_filter, query_vectors,
+                                                   pack)
     out: list = [[] for _ in range(B)]
     if not active:
         return out
     k = min(num_results, n_cand)
     vecs = ranker._token_vectors([queries[b] for b in active],  # noqa: SLF001
-                                 None if query_token_vectors is None else [query_token_vectors[b] for b in active])
+                                 None if query_token_vectors is None else [query_token_vectors[b] for b in active],
+                                 None if mats is None else [mats[b] for b in active])
     for group in _groups_by_nq(vecs):
         members = [active[i] for i in group]
         qf, lim = _device_filters(plan, members)

@@ -333,7 +333,9 @@ class TorchTokenEmbedder:
         keys masked; "packed": unpadded packs of at most `pack_tokens` tokens (`pack_runs`) through `Encoder.forward_packed`.
         short_forward: "torch" (default): always that route; "native": a call whose strings together have at most
         `_encoder.MAX_TOKENS` tokens runs as ONE pack through the HIP forward (`NativeEncoder`) when the encoder is on a
-        GPU in bf16 / fp16 at a head width of 32 or 64 -- every other call takes the `batching` route as before."""
+        GPU in bf16 / fp16 at a head width of 32 or 64 -- every other call takes the `batching` route as before.  "native" also opens
+        `embed_pack`: many short strings (the text queries of a batched search) through one native forward of up to
+        `_encoder.MAX_PACK_TOKENS` tokens, each with the bits of its own `embed()`."""
         import torch
 
         if batching not in BATCHING_MODES:
@@ -427,6 +429,36 @@ class TorchTokenEmbedder:
         with torch.inference_mode():
             out = self._native.forward_rows(rows).float()
         return list(torch.split(out, [len(r) for r in rows]))
+
+    def embed_pack(self, texts: Sequence[str]) -> list | None:
+        """The token matrices `embed(t)` returns for each text of `texts`, bit for bit, from ONE native forward per run of at most
+        `_encoder.MAX_PACK_TOKENS` tokens (`NativeEncoder.forward_pack_rows`) -- what a batch of text queries needs.
+        Taken only with `short_forward="native"`, where the HIP forward covers the encoder (`NativeEncoder.supports_pack`) and every
+        single text is within `_encoder.MAX_TOKENS` tokens, so that its own `embed()` would have gone native too; otherwise None, and
+        the caller embeds one by one as before.  Counts as one `embed` call."""
+        import torch
+
+        from raglite_amd._encoder import MAX_PACK_TOKENS, MAX_TOKENS, NativeEncoder
+
+        if self.short_forward != "native" or self.shape.classifier:
+            return None
+        texts = list(texts)
+        if not texts:
+            return []
+        rows = [[self.shape.bos_id, *self.tokenizer.encode(t)[: self.shape.n_ctx - 2], self.shape.eos_id] for t in texts]
+        lens = [len(r) for r in rows]
+        w = self.encoder.ln.weight
+        if max(lens) > MAX_TOKENS or not NativeEncoder.supports_pack(self.shape, w.dtype, min(sum(lens), MAX_PACK_TOKENS), w.device):
+            return None
+        if self._native is None or self._native.module is not self.encoder:
+            self._native = NativeEncoder(self.encoder, self.shape)
+        self.embed_calls += 1
+        mats: list = []
+        for lo, hi in pack_runs(lens, MAX_PACK_TOKENS):
+            with torch.inference_mode():
+                out = self._native.forward_pack_rows(rows[lo:hi]).float()
+            mats.extend(torch.split(out, lens[lo:hi]))
+        return mats
 
     def _embed_packed(self, rows: list[list[int]]) -> list:
         """One packed forward per run of `pack_runs`; the pad-queries-to-128 trick of the padded route belongs to torch's attention

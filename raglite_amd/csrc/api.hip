@@ -442,6 +442,26 @@ int rl_adapter_apply(const float* A, const float* queries, int32_t n_queries, in
     return st.finish();
 }
 
+// The same product with the n_queries = 1 route's arithmetic for every row, in one launch (scan.hip: adapter_rows_kernel).
+int rl_adapter_apply_rows(const float* A, const float* queries, int32_t n_queries, int32_t dim, float* out_f32,
+                          uint16_t* out_f16, int mem, void* stream) {
+    if (dim <= 0 || n_queries < 0) return fail(RL_ERR_INVALID, "rl_adapter_apply_rows: bad size");
+    if (!A || (n_queries > 0 && !queries)) return fail(RL_ERR_INVALID, "rl_adapter_apply_rows: null input");
+    if (!out_f32 && !out_f16) return fail(RL_ERR_INVALID, "rl_adapter_apply_rows: no output requested");
+    if (n_queries == 0) return RL_OK;
+    hipStream_t s = as_stream(stream);
+    Staging st(mem, s);
+    const float* d_a; const float* d_q;
+    RL_TRY(st.in(A, (size_t)dim * dim, &d_a));
+    RL_TRY(st.in(queries, (size_t)n_queries * dim, &d_q));
+    float* d_res; uint16_t* d_o16;
+    RL_TRY(st.out_or_temp(out_f32, (size_t)n_queries * dim, &d_res));
+    RL_TRY(st.out(out_f16, (size_t)n_queries * dim, &d_o16));
+    RL_TRY(launch_adapter_rows(d_a, dim, d_q, n_queries, d_res, s));
+    if (d_o16) RL_TRY(launch_cast_f16(d_res, d_o16, (int64_t)n_queries * dim, s));
+    return st.finish();
+}
+
 // ---- index ---------------------------------------------------------------------------------------------
 int rl_index_destroy(rl_index* idx) {
     if (!idx) return RL_OK;

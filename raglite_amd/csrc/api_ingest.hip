@@ -1,6 +1,6 @@
 // The ingestion entry points of the C ABI: pooling and normalising token embeddings, the packed encoder's attention, the native
-// encoder forward for short packs (the one handle here, rl_encoder) and the document-batched splitters (include/raglite_hip.h for
-// the contract of each).
+// encoder forward for short packs and for packs of several token blocks (the one handle here, rl_encoder) and the document-batched
+// splitters (include/raglite_hip.h for the contract of each).
 #include <cmath>
 #include <string>
 
@@ -114,25 +114,30 @@ int rl_encoder_info(const rl_encoder* enc, int64_t n_tokens, int32_t* max_tokens
     return RL_OK;
 }
 
-int rl_encoder_forward(rl_encoder* enc, const int32_t* ids, const int32_t* positions, const int32_t* type_ids, const int32_t* seq_offsets,
-                       int32_t n_seqs, int64_t n_tokens, int32_t max_len, void* out, int mem, void* stream) {
-    if (mem != RL_MEM_DEVICE) return fail(RL_ERR_UNSUPPORTED, "rl_encoder_forward: device pointers only (mem must be RL_MEM_DEVICE)");
-    if (n_seqs < 0 || n_tokens < 0 || max_len < 0) return fail(RL_ERR_INVALID, "rl_encoder_forward: negative size");
-    if (n_seqs > 65535) return fail(RL_ERR_INVALID, "rl_encoder_forward: n_seqs must be <= 65535 (the attention grid's z axis)");
-    if (n_tokens > RL_ENCODER_MAX_TOKENS) return fail(RL_ERR_UNSUPPORTED, "rl_encoder_forward: n_tokens must be <= RL_ENCODER_MAX_TOKENS (256)");
+// The checks rl_encoder_forward and rl_encoder_forward_pack share, in the header's order; `cap` / `cap_name`: the most tokens of `who`.
+// The handle comes after them, in the callers.
+static int check_forward_args(const char* who, int64_t cap, const char* cap_name, const int32_t* ids, const int32_t* positions,
+                              const int32_t* type_ids, const int32_t* seq_offsets, int32_t n_seqs, int64_t n_tokens, int32_t max_len,
+                              const void* out, int mem) {
+    const std::string w(who);
+    if (mem != RL_MEM_DEVICE) return fail(RL_ERR_UNSUPPORTED, w + ": device pointers only (mem must be RL_MEM_DEVICE)");
+    if (n_seqs < 0 || n_tokens < 0 || max_len < 0) return fail(RL_ERR_INVALID, w + ": negative size");
+    if (n_seqs > 65535) return fail(RL_ERR_INVALID, w + ": n_seqs must be <= 65535 (the attention grid's z axis)");
+    if (n_tokens > cap) return fail(RL_ERR_UNSUPPORTED, w + ": n_tokens must be <= " + cap_name + " (" + std::to_string(cap) + ")");
     if (n_tokens > 0) {
-        if (!ids || !positions || !seq_offsets || !out) return fail(RL_ERR_INVALID, "rl_encoder_forward: null argument");
+        if (!ids || !positions || !seq_offsets || !out) return fail(RL_ERR_INVALID, w + ": null argument");
         if (misaligned(ids, 4) || misaligned(positions, 4) || misaligned(type_ids, 4) || misaligned(seq_offsets, 4) || misaligned(out, 16))
-            return fail(RL_ERR_INVALID, "rl_encoder_forward: the int32 arrays must be 4-byte and out 16-byte aligned");
+            return fail(RL_ERR_INVALID, w + ": the int32 arrays must be 4-byte and out 16-byte aligned");
     }
-    if (!enc) return fail(RL_ERR_INVALID, "rl_encoder_forward: null handle");
-    if (n_tokens == 0) return RL_OK;
-    hipStream_t s = as_stream(stream);
-    std::lock_guard<std::mutex> lock(enc->mu);
-    RL_TRY(enc->last_stream.use(s));
-    const int32_t M = (int32_t)n_tokens, H = enc->hidden, F = enc->ffn, dt = enc->dtype;
-    EncoderScratch b;  // this call's rows: a prefix of the block reserved for the cap
-    b.lay(Carver(enc->scratch.p), (size_t)M, (size_t)H, (size_t)F, (size_t)enc->ksplit);
+    return RL_OK;
+}
+
+// The 1 + 7 * layers launches of a forward of M > 0 rows, with `block` as its scratch: at least EncoderScratch's walk over M rows.
+static int encoder_launches(const rl_encoder* enc, const int32_t* ids, const int32_t* positions, const int32_t* type_ids,
+                            const int32_t* seq_offsets, int32_t n_seqs, int32_t M, int32_t max_len, void* out, void* block, hipStream_t s) {
+    const int32_t H = enc->hidden, F = enc->ffn, dt = enc->dtype;
+    EncoderScratch b;  // this call's rows: a prefix of the block
+    b.lay(Carver(block), (size_t)M, (size_t)H, (size_t)F, (size_t)enc->ksplit);
     const int32_t ks_out = encoder_ksplit(H, H), ks_down = encoder_ksplit(H, F);
     const float scale = 1.0f / sqrtf((float)(H / enc->heads));
     RL_TRY(launch_encoder_embed(ids, positions, type_ids, M, enc->tok, enc->vocab, enc->pos, enc->max_positions, enc->typ, enc->type_vocab,
@@ -149,6 +154,49 @@ int rl_encoder_forward(rl_encoder* enc, const int32_t* ids, const int32_t* posit
         RL_TRY(launch_encoder_ln(b.part, ks_down, M, H, p.down_b, b.x1, p.ln2_w, p.ln2_b, enc->eps, dt, x_next, s));
     }
     return RL_OK;
+}
+
+int rl_encoder_forward(rl_encoder* enc, const int32_t* ids, const int32_t* positions, const int32_t* type_ids, const int32_t* seq_offsets,
+                       int32_t n_seqs, int64_t n_tokens, int32_t max_len, void* out, int mem, void* stream) {
+    RL_TRY(check_forward_args("rl_encoder_forward", RL_ENCODER_MAX_TOKENS, "RL_ENCODER_MAX_TOKENS", ids, positions, type_ids, seq_offsets,
+                              n_seqs, n_tokens, max_len, out, mem));
+    if (!enc) return fail(RL_ERR_INVALID, "rl_encoder_forward: null handle");
+    if (n_tokens == 0) return RL_OK;
+    hipStream_t s = as_stream(stream);
+    std::lock_guard<std::mutex> lock(enc->mu);
+    RL_TRY(enc->last_stream.use(s));
+    return encoder_launches(enc, ids, positions, type_ids, seq_offsets, n_seqs, (int32_t)n_tokens, max_len, out, enc->scratch.p, s);
+}
+
+// ---- a pack of several token blocks, on the caller's workspace -----------------------------------------------------
+static size_t pack_workspace_bytes(const rl_encoder* enc, int64_t n_tokens) {  // the handle's layout, walked with the pack's rows
+    return EncoderScratch().lay(Carver(), (size_t)n_tokens, (size_t)enc->hidden, (size_t)enc->ffn, (size_t)enc->ksplit);
+}
+
+int rl_encoder_pack_workspace_bytes(const rl_encoder* enc, int64_t n_tokens, int64_t* bytes) {
+    if (n_tokens < 0 || n_tokens > RL_ENCODER_MAX_PACK_TOKENS)
+        return fail(RL_ERR_INVALID, "rl_encoder_pack_workspace_bytes: n_tokens must be in [0, RL_ENCODER_MAX_PACK_TOKENS]");
+    if (!bytes) return fail(RL_ERR_INVALID, "rl_encoder_pack_workspace_bytes: bytes is null");
+    if (!enc) return fail(RL_ERR_INVALID, "rl_encoder_pack_workspace_bytes: null handle");
+    *bytes = (int64_t)pack_workspace_bytes(enc, n_tokens);
+    return RL_OK;
+}
+
+int rl_encoder_forward_pack(rl_encoder* enc, const int32_t* ids, const int32_t* positions, const int32_t* type_ids,
+                            const int32_t* seq_offsets, int32_t n_seqs, int64_t n_tokens, int32_t max_len, void* out, void* workspace,
+                            int64_t workspace_bytes, int mem, void* stream) {
+    RL_TRY(check_forward_args("rl_encoder_forward_pack", RL_ENCODER_MAX_PACK_TOKENS, "RL_ENCODER_MAX_PACK_TOKENS", ids, positions, type_ids,
+                              seq_offsets, n_seqs, n_tokens, max_len, out, mem));
+    if (n_tokens > 0) {
+        if (!workspace) return fail(RL_ERR_INVALID, "rl_encoder_forward_pack: workspace is null");
+        if (misaligned(workspace, 16)) return fail(RL_ERR_INVALID, "rl_encoder_forward_pack: workspace must be 16-byte aligned");
+    }
+    if (!enc) return fail(RL_ERR_INVALID, "rl_encoder_forward_pack: null handle");
+    if (n_tokens == 0) return RL_OK;
+    if (workspace_bytes < 0 || (uint64_t)workspace_bytes < (uint64_t)pack_workspace_bytes(enc, n_tokens))
+        return fail(RL_ERR_INVALID, "rl_encoder_forward_pack: workspace_bytes is less than rl_encoder_pack_workspace_bytes(n_tokens)");
+    // (the handle's own scratch, its mutex and its stream record are not involved: the workspace is the caller's)
+    return encoder_launches(enc, ids, positions, type_ids, seq_offsets, n_seqs, (int32_t)n_tokens, max_len, out, workspace, as_stream(stream));
 }
 
 // The forward's three launches one at a time (what tests/test_gpu_encoder_kernels.py holds to float64): every argument checked here, the
@@ -188,26 +236,40 @@ int rl_encoder_linear_slices(int32_t N, int32_t K, int32_t* slices) {
     return RL_OK;
 }
 
-int rl_encoder_linear(const void* x, int64_t M, int32_t K, const void* W, int32_t N, const void* bias, int32_t epilogue, int32_t dtype,
-                      void* out16, float* part, int mem, void* stream) {
-    if (mem != RL_MEM_DEVICE) return fail(RL_ERR_UNSUPPORTED, "rl_encoder_linear: device pointers only (mem must be RL_MEM_DEVICE)");
-    if (M < 0 || M > RL_ENCODER_MAX_TOKENS) return fail(RL_ERR_INVALID, "rl_encoder_linear: M must be in [0, RL_ENCODER_MAX_TOKENS]");
-    if (bad_width(K) || bad_width(N)) return fail(RL_ERR_INVALID, "rl_encoder_linear: K and N must be positive multiples of 32");
-    if (dtype != RL_ATTN_BF16 && dtype != RL_ATTN_F16) return fail(RL_ERR_INVALID, "rl_encoder_linear: unknown dtype");
+// rl_encoder_linear and rl_encoder_linear_pack: the same checks and the same launcher; `cap_name` names the most rows of `who`.
+static int linear_entry(const char* who, int64_t cap, const char* cap_name, const void* x, int64_t M, int32_t K, const void* W, int32_t N,
+                        const void* bias, int32_t epilogue, int32_t dtype, void* out16, float* part, int mem, void* stream) {
+    const std::string w(who);
+    if (mem != RL_MEM_DEVICE) return fail(RL_ERR_UNSUPPORTED, w + ": device pointers only (mem must be RL_MEM_DEVICE)");
+    if (M < 0 || M > cap) return fail(RL_ERR_INVALID, w + ": M must be in [0, " + cap_name + "]");
+    if (bad_width(K) || bad_width(N)) return fail(RL_ERR_INVALID, w + ": K and N must be positive multiples of 32");
+    if (dtype != RL_ATTN_BF16 && dtype != RL_ATTN_F16) return fail(RL_ERR_INVALID, w + ": unknown dtype");
     if (epilogue != RL_ENC_EPI_BIAS && epilogue != RL_ENC_EPI_GELU && epilogue != RL_ENC_EPI_PARTIAL)
-        return fail(RL_ERR_INVALID, "rl_encoder_linear: unknown epilogue");
+        return fail(RL_ERR_INVALID, w + ": unknown epilogue");
     if (M == 0) return RL_OK;
     const bool partial = epilogue == RL_ENC_EPI_PARTIAL;
-    if (!x || !W) return fail(RL_ERR_INVALID, "rl_encoder_linear: null argument");
-    if (partial && !part) return fail(RL_ERR_INVALID, "rl_encoder_linear: the partial epilogue writes part, which is null");
-    if (!partial && !out16) return fail(RL_ERR_INVALID, "rl_encoder_linear: the bias and GELU epilogues write out16, which is null");
-    if (!partial && !bias) return fail(RL_ERR_INVALID, "rl_encoder_linear: the bias and GELU epilogues read bias, which is null");
+    if (!x || !W) return fail(RL_ERR_INVALID, w + ": null argument");
+    if (partial && !part) return fail(RL_ERR_INVALID, w + ": the partial epilogue writes part, which is null");
+    if (!partial && !out16) return fail(RL_ERR_INVALID, w + ": the bias and GELU epilogues write out16, which is null");
+    if (!partial && !bias) return fail(RL_ERR_INVALID, w + ": the bias and GELU epilogues read bias, which is null");
     if (misaligned(x, 16) || misaligned(W, 16) || (partial && misaligned(part, 16)))
-        return fail(RL_ERR_INVALID, "rl_encoder_linear: x, W and part must be 16-byte aligned");
+        return fail(RL_ERR_INVALID, w + ": x, W and part must be 16-byte aligned");
     if (!partial && (misaligned(bias, 8) || misaligned(out16, 8)))
-        return fail(RL_ERR_INVALID, "rl_encoder_linear: bias and out16 must be 8-byte aligned");
+        return fail(RL_ERR_INVALID, w + ": bias and out16 must be 8-byte aligned");
     return launch_encoder_linear(x, (int32_t)M, K, W, N, partial ? nullptr : bias, epilogue, dtype, partial ? nullptr : out16,
                                  partial ? part : nullptr, as_stream(stream));
+}
+
+int rl_encoder_linear(const void* x, int64_t M, int32_t K, const void* W, int32_t N, const void* bias, int32_t epilogue, int32_t dtype,
+                      void* out16, float* part, int mem, void* stream) {
+    return linear_entry("rl_encoder_linear", RL_ENCODER_MAX_TOKENS, "RL_ENCODER_MAX_TOKENS", x, M, K, W, N, bias, epilogue, dtype, out16, part,
+                        mem, stream);
+}
+
+int rl_encoder_linear_pack(const void* x, int64_t M, int32_t K, const void* W, int32_t N, const void* bias, int32_t epilogue, int32_t dtype,
+                           void* out16, float* part, int mem, void* stream) {
+    return linear_entry("rl_encoder_linear_pack", RL_ENCODER_MAX_PACK_TOKENS, "RL_ENCODER_MAX_PACK_TOKENS", x, M, K, W, N, bias, epilogue,
+                        dtype, out16, part, mem, stream);
 }
 
 int rl_encoder_layer_norm(const float* part, int32_t slices, int64_t M, int32_t hidden, const void* bias, const void* resid, const void* ln_w,

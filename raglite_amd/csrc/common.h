@@ -115,7 +115,8 @@ int launch_attention_varlen(const void* qkv, const int32_t* seq_offsets, int32_t
                             int32_t head_dim, int32_t dtype, float scale, void* out, hipStream_t s);
 
 // encoder.hip: the kernels of rl_encoder_forward.  dtype: RL_ATTN_BF16 / RL_ATTN_F16, of every `void*` below;
-// M <= RL_ENCODER_MAX_TOKENS rows; hidden, K, N multiples of 32; arguments already checked
+// M, n_tokens <= RL_ENCODER_MAX_PACK_TOKENS rows (the linear kernel takes them in token blocks of RL_ENCODER_MAX_TOKENS, one per
+// blockIdx.z); hidden, K, N multiples of 32; arguments already checked
 constexpr int32_t ENC_KSPLIT_MAX = 8;
 constexpr int32_t ENC_HIDDEN_MAX = 8192;        // a row of f32 in a workgroup's LDS (the layer norms)
 int32_t encoder_ksplit(int32_t N, int32_t K);  // the K slices of a projection into f32 partials: a function of (N, K) alone
@@ -146,6 +147,8 @@ __device__ __forceinline__ float transform_score(float d, int mode, float row_no
 // scores[b * ld + row] for b < nb (nb <= 4 per launch handled inside), rows < n.
 int launch_scan_rows(const float* E, int64_t n, int32_t dim, const float* queries, int32_t nb,
                      const float* row_norm, int mode, float* scores, int64_t ld, hipStream_t s, const uint32_t* run_if = nullptr);
+// out[b] = A @ q[b] for b < nb in one launch, each with the bits of launch_scan_rows(A, dim, dim, q[b], 1, .., SCAN_RAW_DOT, ..)
+int launch_adapter_rows(const float* A, int32_t dim, const float* queries, int32_t nb, float* out, hipStream_t s);
 // scan16.hip: the same over an fp16-stored corpus (dim <= 1024) -- or over the HI plane of a WIDE fp32 index (dim <= 4096, nb <= 4: raw dots)
 int launch_scan_rows16(const uint16_t* E, int64_t n, int32_t dim, const float* queries, int32_t nb,
                        const float* row_norm, int mode, float* scores, int64_t ld, hipStream_t s);

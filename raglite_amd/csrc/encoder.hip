@@ -1,6 +1,7 @@
-// The kernels of the native encoder forward for short packs (rl_encoder_forward): embeddings + layer norm, the skinny
-// linear layer, and the layer norm that closes a projection.  M <= RL_ENCODER_MAX_TOKENS token rows, 16-bit storage (bf16 / fp16), every
-// sum in f32, one rounding per stored value.  Attention is attention_varlen.hip's, on the QKV buffer as the linear kernel leaves it.
+// The kernels of the native encoder forward for short packs (rl_encoder_forward) and for packs of several token
+// blocks (rl_encoder_forward_pack): embeddings + layer norm, the skinny linear layer, and the layer norm that closes a
+// projection.  16-bit storage (bf16 / fp16), every sum in f32, one rounding per stored value.  Attention is attention_varlen.hip's, on
+// the QKV buffer as the linear kernel leaves it.
 //
 // Skinny linear: out[M x N] = epi(x[M x K] . W[N x K]^T).  At these M a projection is a stream of W, not a GEMM: a workgroup owns a slab
 // of 32 output columns -- 32 rows of W, read in place from nn.Linear's [N x K] layout, each byte once -- for ALL M rows, and, where the
@@ -13,8 +14,11 @@
 //   of a chunk from k = chunk + (lane >> 5) * (chunk size / 2) + 8 j: the k order inside an MFMA is free as long as A and B agree, and this
 //   one lets a lane read 64 contiguous bytes of its W row.  K % 64 == 32 ends in a chunk of 32 (two k-steps).
 //   x rows past M are clamped to row M - 1 for the loads and never stored.
+// More than RL_ENCODER_MAX_TOKENS rows: a TOKEN BLOCK per blockIdx.z.  Block z owns the rows [256 z, min(256 z + 256, M)) and runs on them
+// exactly the loop above -- the same chunks to the same waves, the same k-steps, the same reductions -- so W is streamed once per block
+// and a row's sums are the ones it has in a call of its own; `part` is indexed with the global row.
 // The waves' tiles are summed through LDS in wave order, the K slices by launch_encoder_ln in slice order: a row's summation order is a
-// function of (N, K) alone -- not of M, MT, or what else is in the pack -- and there is no atomic anywhere.
+// function of (N, K) alone -- not of M, MT, the token block, the place in it, or what else is in the pack -- and there is no atomic anywhere.
 // Epilogues, in f32 before the single rounding: + bias (QKV); gelu_erf(. + bias) (up); or the raw f32 slice into `part` (out, down),
 // whose bias, residual and layer norm follow in encoder_ln_kernel.
 //
@@ -137,6 +141,7 @@ __global__ __launch_bounds__(LN_THREADS) void encoder_ln_kernel(const float* __r
 constexpr int LIN_SLAB = 32;    // output columns (rows of W) per workgroup
 constexpr int LIN_CHUNK = 64;   // k elements per chunk: 128 bytes of a W row, 64 per lane half
 constexpr int LIN_WAVES = 4;
+constexpr int LIN_BLOCK_ROWS = 256;  // token rows per blockIdx.z: eight tiles of 32, the most a wave keeps in accumulators
 constexpr int LIN_RED_LD = 36;  // floats per token row of a wave's reduction tile (32 + 4: the 16-byte writes of 32 lanes spread over the banks)
 
 __device__ __forceinline__ float gelu_erf(float v) { return 0.5f * v * (1.0f + erff(v * 0.70710678118654752440f)); }
@@ -175,6 +180,7 @@ __global__ __launch_bounds__(WAVE * LIN_WAVES) void encoder_linear_kernel(const 
     const int tid = threadIdx.x, lane = tid & 63, r = lane & 31, h = lane >> 5;
     const int wave = wave_id();
     const int n0 = blockIdx.x * LIN_SLAB, slice = blockIdx.y;
+    const int m0 = blockIdx.z * LIN_BLOCK_ROWS;  // this token block's first row (gridDim.z == 1, m0 == 0 wherever MT < 8)
     const int n_chunks = (K + LIN_CHUNK - 1) / LIN_CHUNK;
     const int c_begin = slice * chunks_per_slice;
     const int c_end = c_begin + chunks_per_slice < n_chunks ? c_begin + chunks_per_slice : n_chunks;
@@ -183,7 +189,7 @@ __global__ __launch_bounds__(WAVE * LIN_WAVES) void encoder_linear_kernel(const 
     const uint16_t* xrow[MT];
 #pragma unroll
     for (int mt = 0; mt < MT; ++mt) {
-        const int m = mt * 32 + r;
+        const int m = m0 + mt * 32 + r;
         xrow[mt] = x + (int64_t)(m < M ? m : M - 1) * K;
     }
     f32x16 acc[MT];
@@ -216,7 +222,7 @@ __global__ __launch_bounds__(WAVE * LIN_WAVES) void encoder_linear_kernel(const 
     const int m_l = tid >> 3, nl = (tid & 7) * 4;
 #pragma unroll
     for (int mt = 0; mt < MT; ++mt) {
-        if (mt * 32 >= M) break;  // (uniform)
+        if (m0 + mt * 32 >= M) break;  // (uniform)
         if (mt) __syncthreads();  // the previous tile has been read
 #pragma unroll
         for (int g = 0; g < 4; ++g)
@@ -226,7 +232,7 @@ __global__ __launch_bounds__(WAVE * LIN_WAVES) void encoder_linear_kernel(const 
         f32x4 v = *reinterpret_cast<const f32x4*>(red + m_l * LIN_RED_LD + nl);
 #pragma unroll
         for (int w = 1; w < LIN_WAVES; ++w) v += *reinterpret_cast<const f32x4*>(red + (w * 32 + m_l) * LIN_RED_LD + nl);
-        const int m = mt * 32 + m_l;
+        const int m = m0 + mt * 32 + m_l;
         if (m >= M) continue;
         if (EPI == ENC_EPI_PARTIAL) {
             *reinterpret_cast<f32x4*>(part + ((int64_t)slice * M + m) * N + n0 + nl) = v;
@@ -251,7 +257,7 @@ int linear_epi(const void* x, int32_t M, int32_t K, const void* W, int32_t N, co
     const int chunks = (K + LIN_CHUNK - 1) / LIN_CHUNK;
     const int slices = epilogue == ENC_EPI_PARTIAL ? encoder_ksplit(N, K) : 1;
     const int per = (chunks + slices - 1) / slices;
-    const dim3 grid((unsigned)(N / LIN_SLAB), (unsigned)slices), block(WAVE * LIN_WAVES);
+    const dim3 grid((unsigned)(N / LIN_SLAB), (unsigned)slices, (unsigned)((M + LIN_BLOCK_ROWS - 1) / LIN_BLOCK_ROWS)), block(WAVE * LIN_WAVES);
     const uint16_t* x16 = static_cast<const uint16_t*>(x);
     const uint16_t* w16 = static_cast<const uint16_t*>(W);
     const uint16_t* b16 = static_cast<const uint16_t*>(bias);
@@ -267,6 +273,7 @@ int linear_epi(const void* x, int32_t M, int32_t K, const void* W, int32_t N, co
 }
 
 // The token tiles a wave keeps are a template argument (the accumulators are registers); a row's arithmetic is the same in all four.
+// Up to 256 rows the grid has one token block; above, ceil(M / 256) blocks of the eight-tile kernel.
 template <class T>
 int linear_t(const void* x, int32_t M, int32_t K, const void* W, int32_t N, const void* bias, int epilogue, void* out16, float* part,
              hipStream_t s) {
@@ -279,6 +286,9 @@ int linear_t(const void* x, int32_t M, int32_t K, const void* W, int32_t N, cons
 }  // namespace
 
 static_assert(RL_ENCODER_MAX_TOKENS == 8 * 32, "the linear kernel keeps at most eight token tiles of 32 in a wave's accumulators");
+static_assert(LIN_BLOCK_ROWS == RL_ENCODER_MAX_TOKENS && RL_ENCODER_MAX_PACK_TOKENS % LIN_BLOCK_ROWS == 0 &&
+                  RL_ENCODER_MAX_PACK_TOKENS / LIN_BLOCK_ROWS <= 65535,
+              "a token block is the rows of one short pack; the pack cap is whole blocks on the grid's z axis");
 
 // Slabs x slices near the CU count, every wave of a slice with at least one chunk of its own, at most ENC_KSPLIT_MAX slices -- and no
 // empty slice: the launcher gives each ceil(chunks / slices) chunks.

@@ -257,6 +257,86 @@ int launch_scan_rows(const float* E, int64_t n, int32_t dim, const float* querie
     return fail(RL_ERR_UNSUPPORTED, "similarity scan: dim must be <= 4096 (multiple of 4) or <= 2048 otherwise");
 }
 
+// The query adapter out[b] = A @ q[b] for MANY queries with the single-query arithmetic (rl_adapter_apply_rows): what
+// scan_rows_kernel<NV, VEC, 1> computes in SCAN_RAW_DOT mode, one query per blockIdx.y in ONE launch.  Per (row of A, query): the same
+// columns to the same lanes, the same fma chain over them, the same butterfly -- so out[b] has the bits of rl_adapter_apply with
+// n_queries = 1 on that query, whatever else is in the batch.  A (dim x dim, 4 MiB at 1024) stays in L2 across the queries.
+template <int NV, int VEC>
+__global__ __launch_bounds__(256) void adapter_rows_kernel(const float* __restrict__ A, int dim, const float* __restrict__ queries,
+                                                            float* __restrict__ out) {
+    const int lane = threadIdx.x & 63;
+    const int wave0 = blockIdx.x * 4 + (threadIdx.x >> 6), n_waves = gridDim.x * 4;
+    const float* qb = queries + (int64_t)blockIdx.y * dim;
+    float* ob = out + (int64_t)blockIdx.y * dim;
+    int col[NV];
+    bool ok[NV];
+    float q[NV][VEC];
+#pragma unroll
+    for (int v = 0; v < NV; ++v) {
+        col[v] = (v * 64 + lane) * VEC;
+        ok[v] = col[v] < dim;
+#pragma unroll
+        for (int j = 0; j < VEC; ++j) q[v][j] = 0.f;
+        if (ok[v]) vload<VEC>(qb + col[v], q[v]);
+    }
+    for (int r = wave0; r < dim; r += n_waves) {
+        float x[NV][VEC];
+        const float* p = A + (int64_t)r * dim;
+#pragma unroll
+        for (int v = 0; v < NV; ++v) {
+#pragma unroll
+            for (int j = 0; j < VEC; ++j) x[v][j] = 0.f;
+            if (ok[v]) vload<VEC>(p + col[v], x[v]);
+        }
+        float s = 0.f;
+#pragma unroll
+        for (int v = 0; v < NV; ++v)
+#pragma unroll
+            for (int j = 0; j < VEC; ++j) s = fmaf(x[v][j], q[v][j], s);
+        s = wave_sum(s);
+        if (lane == 0) ob[r] = s;
+    }
+}
+
+template <int NV, int VEC>
+static int adapter_rows_t(const float* A, int32_t dim, const float* q, int32_t nb, float* out, hipStream_t s) {
+    const unsigned blocks = (unsigned)((dim + 15) / 16);  // four rows of A per wave
+    for (int32_t b0 = 0; b0 < nb; b0 += 65535) {           // (the grid's y axis)
+        const unsigned ny = (unsigned)std::min<int32_t>(65535, nb - b0);
+        hipLaunchKernelGGL((adapter_rows_kernel<NV, VEC>), dim3(blocks, ny), dim3(256), 0, s, A, (int)dim, q + (int64_t)b0 * dim,
+                           out + (int64_t)b0 * dim);
+        RL_HIP(hipGetLastError());
+    }
+    return RL_OK;
+}
+
+// The instantiation by (dim, alignment) is launch_scan_rows': the lane-to-column map is part of the arithmetic.
+int launch_adapter_rows(const float* A, int32_t dim, const float* queries, int32_t nb, float* out, hipStream_t s) {
+    if (dim <= 0 || nb <= 0) return RL_OK;
+    const bool vec4 = (dim % 4 == 0) && aligned16(A) && aligned16(queries);
+#define RL_ADAPT(NV, VEC) return adapter_rows_t<NV, VEC>(A, dim, queries, nb, out, s)
+    if (vec4) {
+        const int nv = (dim + 255) / 256;
+        if (nv <= 1) RL_ADAPT(1, 4);
+        if (nv <= 2) RL_ADAPT(2, 4);
+        if (nv <= 3) RL_ADAPT(3, 4);
+        if (nv <= 4) RL_ADAPT(4, 4);
+        if (nv <= 6) RL_ADAPT(6, 4);
+        if (nv <= 8) RL_ADAPT(8, 4);
+        if (nv <= 16) RL_ADAPT(16, 4);
+    } else {
+        const int nv = (dim + 63) / 64;
+        if (nv <= 1) RL_ADAPT(1, 1);
+        if (nv <= 2) RL_ADAPT(2, 1);
+        if (nv <= 4) RL_ADAPT(4, 1);
+        if (nv <= 8) RL_ADAPT(8, 1);
+        if (nv <= 16) RL_ADAPT(16, 1);
+        if (nv <= 32) RL_ADAPT(32, 1);
+    }
+#undef RL_ADAPT
+    return fail(RL_ERR_UNSUPPORTED, "rl_adapter_apply_rows: dim must be <= 4096 (multiple of 4) or <= 2048 otherwise");
+}
+
 template <int NV, int VEC>
 static int norms_t(const float* E, int64_t n, int32_t dim, float* norm, float* sumsq, hipStream_t s) {
     const int blocks = persistent_grid(row_norms_kernel<NV, VEC>, 256, (n + 3) / 4);

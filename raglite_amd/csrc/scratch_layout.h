@@ -196,7 +196,8 @@ struct RerankScratch {  // search_rerank_device, pool `rerank`
 
 // ---- native encoder forward (api_ingest.hip, encoder.hip) -------------------------------------------------------------------------------
 struct EncoderScratch {  // rl_encoder_forward, the handle's one block: reserved for RL_ENCODER_MAX_TOKENS rows, walked per call with the
-                         // call's own `rows`, so that a call writes a prefix of the block and nothing behind it
+                         // call's own `rows`, so that a call writes a prefix of the block and nothing behind it.  rl_encoder_forward_pack
+                         // walks the same layout over the caller's workspace, with up to RL_ENCODER_MAX_PACK_TOKENS rows
     uint16_t *x, *x1;    // [rows x hidden] a layer's input; the same after the attention half (ln1)
     uint16_t *qkv, *attn, *mid;  // [rows x 3 hidden] fused projection; [rows x hidden] attention output; [rows x ffn] gelu(up)
     float* part;         // [ksplit x rows x hidden] the K slices of the out / down projections, summed in order by the layer norm
