@@ -237,6 +237,28 @@ int rl_adapter_apply(const float* A, const float* queries, int32_t n_queries, in
 int rl_adapter_apply_rows(const float* A, const float* queries, int32_t n_queries, int32_t dim,
                           float* out_f32, uint16_t* out_f16, int mem, void* stream);
 
+/* ---- the dense score GEMMs on the caller's matrices (score_gemm.hip; the row-score mode of maxsim_gemm.hip) --------------------------
+ * What a search of 96 and more queries runs, without an index around it (what tests/test_gpu_score_gemm.py holds to float64):
+ *     out[q * ld + r] = metric(E[r] . Q[q])        r < n_rows, q < n_queries; nothing else of `out` is written
+ *   E [n_rows x dim] f32, Q [n_queries x dim] f32, both 16-byte aligned; dim a multiple of 32 (RL_ERR_UNSUPPORTED otherwise).
+ *   metric        RL_SCORE_RAW: the dot; RL_SCORE_COSINE / _DOT / _L2: the index metrics, formed from the dot and the CALLER's
+ *                 row_norm [n_rows] = |e| (cosine) or row_sumsq [n_rows] = |e|^2 (l2) exactly as a search forms them from the index' own.
+ *   split_scale   0: the exact fp32 MFMA chain; a power of two: RL_ARITH_F16_SPLIT with the rows scaled by it.
+ *   kernel        0: as a search over the stored rows chooses (128 x 256 tiles for more than 128 queries in split arithmetic, else
+ *                 128 x 128); 1: 128 x 128 tiles; 2: 128 x 256 tiles; 3: the GEMM over the pre-split corpus image, which is built from E
+ *                 into a temporary first.  2 and 3 exist in split arithmetic only.
+ *   max_workgroups  the most workgroups of the persistent grid; 0: the device's CUs.  Fewer make each walk more tiles; results do not
+ *                 depend on it.
+ *   out_q_sumsq [n_queries], out_q_scale [n_queries] (both optional; kernels 0 to 2): what the query-side kernels left -- |q|^2 as the
+ *                 epilogue reads it, and the power of two each query was scaled by (split arithmetic only).
+ * RL_ERR_INVALID for a null argument, a size < 1, ld < n_rows, an unknown metric or kernel, cosine without row_norm, l2 without row_sumsq,
+ * kernels 2 and 3 without a split scale, a split scale that is no power of two, out_q_scale without a split scale, a read-back with
+ * kernel 3, device pointers E or Q that are not 16-byte aligned.  Every check comes before the first HIP call. */
+enum { RL_SCORE_RAW = 0, RL_SCORE_COSINE = 1, RL_SCORE_DOT = 2, RL_SCORE_L2 = 3 };
+int rl_score_gemm(const float* E, int64_t n_rows, int32_t dim, const float* Q, int32_t n_queries, int metric, const float* row_norm,
+                  const float* row_sumsq, float split_scale, int32_t kernel, int32_t max_workgroups, float* out, int64_t ld,
+                  float* out_q_sumsq, float* out_q_scale, int mem, void* stream);
+
 /* ---- index lifecycle -------------------------------------------------------------------------
  * The device-resident equivalent of the `chunk_embedding` table (src/raglite/_database.py:403-430):
  * one row per chunklet vector, rows of a chunk contiguous (a4: src/raglite/_split_chunks.py:116-122,

@@ -22,6 +22,7 @@ RL_OK, RL_ERR_INVALID, RL_ERR_HIP, RL_ERR_UNSUPPORTED, RL_ERR_NOMEM = 0, -1, -2,
 MEM_HOST, MEM_DEVICE = 0, 1
 MEM_FILTERS_DEVICE = 2  # RL_MEM_FILTERS_DEVICE, or-ed into `mem`: the filter table alone is a device pointer
 METRICS = {"cosine": 0, "dot": 1, "l2": 2}
+SCORE_METRICS = {"raw": 0, "cosine": 1, "dot": 2, "l2": 3}  # RL_SCORE_*: rl_score_gemm's metric (the dot itself, then the index metrics)
 SYNTH_KINDS = {"uniform": 0, "small_int": 1}
 ATTN_DTYPES = {"bfloat16": 0, "float16": 1}  # RL_ATTN_BF16 / RL_ATTN_F16
 ENCODER_MAX_TOKENS = 256  # RL_ENCODER_MAX_TOKENS: the most token rows rl_encoder_forward takes in one pack
@@ -79,6 +80,8 @@ _SIGNATURES = {
     "rl_encoder_linear_pack": [c_void_p, c_i64, c_i32, c_void_p, c_i32, c_void_p, c_i32, c_i32, c_void_p, c_void_p, c_int, c_void_p],
     "rl_adapter_apply": [c_void_p, c_void_p, c_i32, c_i32, c_void_p, c_void_p, c_int, c_void_p],
     "rl_adapter_apply_rows": [c_void_p, c_void_p, c_i32, c_i32, c_void_p, c_void_p, c_int, c_void_p],
+    "rl_score_gemm": [c_void_p, c_i64, c_i32, c_void_p, c_i32, c_int, c_void_p, c_void_p, C.c_float, c_i32, c_i32, c_void_p, c_i64, c_void_p,
+                      c_void_p, c_int, c_void_p],
     "rl_index_create": [C.POINTER(c_void_p), c_void_p, c_i64, c_i32, c_void_p, c_i64, c_int, c_int, c_void_p],
     "rl_index_destroy": [c_void_p],
     "rl_index_info": [c_void_p, C.POINTER(c_i64), C.POINTER(c_i32), C.POINTER(c_i64), C.POINTER(c_int)],

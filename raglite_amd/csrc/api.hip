@@ -462,6 +462,87 @@ int rl_adapter_apply_rows(const float* A, const float* queries, int32_t n_querie
     return st.finish();
 }
 
+// ---- the dense score GEMMs on the caller's matrices (what tests/test_gpu_score_gemm.py holds to float64) -------------------------------
+// Every argument checked here, the launchers as score_rows calls them: launch_score_gemm over the rows (kernels 0 to 2), or
+// launch_presplit_rows into a temporary and launch_score_planes over it (kernel 3).
+static_assert(RL_SCORE_RAW == SCAN_RAW_DOT && RL_SCORE_COSINE == SCAN_COSINE && RL_SCORE_DOT == SCAN_DOT && RL_SCORE_L2 == SCAN_L2,
+              "the header's score metrics are the scan modes");
+
+int rl_score_gemm(const float* E, int64_t n_rows, int32_t dim, const float* Q, int32_t n_queries, int metric, const float* row_norm,
+                  const float* row_sumsq, float split_scale, int32_t kernel, int32_t max_workgroups, float* out, int64_t ld,
+                  float* out_q_sumsq, float* out_q_scale, int mem, void* stream) {
+    RL_TRY(check_mem(mem, "rl_score_gemm"));
+    if (n_rows < 1 || n_queries < 1 || dim < 1) return fail(RL_ERR_INVALID, "rl_score_gemm: n_rows, dim and n_queries must be >= 1");
+    if (!E || !Q || !out) return fail(RL_ERR_INVALID, "rl_score_gemm: null argument");
+    if (ld < n_rows) return fail(RL_ERR_INVALID, "rl_score_gemm: ld must be >= n_rows");
+    if (metric != RL_SCORE_RAW && metric != RL_SCORE_COSINE && metric != RL_SCORE_DOT && metric != RL_SCORE_L2)
+        return fail(RL_ERR_INVALID, "rl_score_gemm: unknown metric");
+    if (kernel < 0 || kernel > 3) return fail(RL_ERR_INVALID, "rl_score_gemm: kernel must be 0, 1, 2 or 3");
+    if (max_workgroups < 0) return fail(RL_ERR_INVALID, "rl_score_gemm: max_workgroups must be >= 0");
+    if (dim % 32 != 0) return fail(RL_ERR_UNSUPPORTED, "rl_score_gemm: dim must be a multiple of 32");
+    if (metric == RL_SCORE_COSINE && !row_norm) return fail(RL_ERR_INVALID, "rl_score_gemm: cosine reads row_norm, which is null");
+    if (metric == RL_SCORE_L2 && !row_sumsq) return fail(RL_ERR_INVALID, "rl_score_gemm: l2 reads row_sumsq, which is null");
+    const bool split = split_scale != 0.f;
+    if (split) {
+        int ex = 0;
+        if (!(split_scale > 0.f) || !(split_scale < INFINITY) || frexpf(split_scale, &ex) != 0.5f)
+            return fail(RL_ERR_INVALID, "rl_score_gemm: split_scale must be 0 or a power of two");
+    }
+    if (kernel >= 2 && !split) return fail(RL_ERR_INVALID, "rl_score_gemm: kernels 2 and 3 exist in split arithmetic only (split_scale is 0)");
+    if (out_q_scale && !split) return fail(RL_ERR_INVALID, "rl_score_gemm: out_q_scale is written in split arithmetic only (split_scale is 0)");
+    if (kernel == 3 && (out_q_sumsq || out_q_scale)) return fail(RL_ERR_INVALID, "rl_score_gemm: out_q_sumsq and out_q_scale read back kernels 0 to 2");
+    if (kernel == 3 && n_rows > (int64_t)std::numeric_limits<int32_t>::max() - 256)
+        return fail(RL_ERR_UNSUPPORTED, "rl_score_gemm: kernel 3 takes fewer than 2^31 - 256 rows");
+    if (mem == RL_MEM_DEVICE && ((reinterpret_cast<uintptr_t>(E) & 15) || (reinterpret_cast<uintptr_t>(Q) & 15)))
+        return fail(RL_ERR_INVALID, "rl_score_gemm: E and Q must be 16-byte aligned");
+    hipStream_t s = as_stream(stream);
+    int n_cu = max_workgroups;
+    if (n_cu == 0) {
+        int dev = 0;
+        RL_HIP(hipGetDevice(&dev));
+        RL_HIP(hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev));
+    }
+    Staging st(mem, s);
+    const float *d_e, *d_q, *d_norm = nullptr, *d_sumsq = nullptr;
+    RL_TRY(st.in(E, (size_t)n_rows * dim, &d_e));
+    RL_TRY(st.in(Q, (size_t)n_queries * dim, &d_q));
+    if (metric == RL_SCORE_COSINE) RL_TRY(st.in(row_norm, (size_t)n_rows, &d_norm));
+    if (metric == RL_SCORE_L2) RL_TRY(st.in(row_sumsq, (size_t)n_rows, &d_sumsq));
+    // `out` as far as the call owns it: the last query's row ends at n_rows.  Host memory: what lies between the rows goes up first, so
+    // that it comes back as it was.
+    const size_t out_floats = (size_t)(n_queries - 1) * (size_t)ld + (size_t)n_rows;
+    float *d_out, *d_qss, *d_qsc;
+    RL_TRY(st.out(out, out_floats, &d_out));
+    if (mem == RL_MEM_HOST && ld > n_rows) RL_HIP(hipMemcpyAsync(d_out, out, out_floats * sizeof(float), hipMemcpyHostToDevice, s));
+    RL_TRY(st.out(out_q_sumsq, (size_t)n_queries, &d_qss));
+    RL_TRY(st.out(out_q_scale, (size_t)n_queries, &d_qsc));
+    const RowMetric m{metric, d_norm, d_sumsq};
+    const Launch on{n_cu, s};
+    if (kernel == 3) {
+        char* image;
+        float* scratch;
+        RL_TRY(st.temp(planes_bytes(n_rows, dim), &image));
+        RL_TRY(st.temp(score_planes_scratch_floats(n_queries, dim) * sizeof(float), &scratch));
+        RL_TRY(launch_presplit_rows({d_e, false, n_rows, dim, split_scale}, 0, image, s));
+        const int rc = launch_score_planes({image, false, n_rows, dim, split_scale}, d_q, n_queries, {d_out, ld}, m, scratch, on);
+        if (rc == RL_ERR_UNSUPPORTED) return fail(rc, "rl_score_gemm: the image GEMM does not take these arguments");
+        RL_TRY(rc);
+        return st.finish();
+    }
+    float* scratch;  // q_sumsq [n_queries] | q_scale [n_queries] | the pre-split queries (launch_score_gemm's layout)
+    RL_TRY(st.temp(score_gemm_scratch_floats(n_queries, dim, split) * sizeof(float), &scratch));
+    const int rc = launch_score_gemm({d_e, false, n_rows, dim, split ? split_scale : 0.f}, d_q, n_queries, {d_out, ld}, m, scratch, on, kernel);
+    if (rc == RL_ERR_UNSUPPORTED) return fail(rc, "rl_score_gemm: the GEMM does not take these arguments");
+    RL_TRY(rc);
+    if (d_qss) {
+        // (the launcher sums the squares for cosine and l2 only; the same kernel otherwise)
+        if (metric != RL_SCORE_COSINE && metric != RL_SCORE_L2) RL_TRY(launch_query_sumsq(d_q, n_queries, dim, scratch, s));
+        RL_HIP(hipMemcpyAsync(d_qss, scratch, (size_t)n_queries * sizeof(float), hipMemcpyDeviceToDevice, s));
+    }
+    if (d_qsc) RL_HIP(hipMemcpyAsync(d_qsc, scratch + n_queries, (size_t)n_queries * sizeof(float), hipMemcpyDeviceToDevice, s));
+    return st.finish();
+}
+
 // ---- index ---------------------------------------------------------------------------------------------
 int rl_index_destroy(rl_index* idx) {
     if (!idx) return RL_OK;

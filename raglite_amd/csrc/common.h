@@ -633,7 +633,11 @@ int launch_score_planes_pass(const RowsRef& image, int32_t nb, float* scratch, S
 // [largest |element|, smallest non-zero row maximum, non-finite flag] of an fp32 corpus, as uint32 bit patterns (device, 3 words)
 int launch_row_range(const float* E, int64_t n_rows, int32_t dim, uint32_t* range, hipStream_t s);
 // score_gemm.hip: similarity of many queries at once (fp32 MFMA GEMM, 128 x 128 tiles, fused metric); dim % 32 == 0; fp32 rows.
-int launch_score_gemm(const RowsRef& E, const float* Q, int32_t nb, Scores out, const RowMetric& m, float* q_sumsq_scratch, const Launch& on);
+// tile: 0 = the launcher's choice, 1 = 128 x 128, 2 = 128 x 256 (split arithmetic only) -- rl_score_gemm names one
+int launch_score_gemm(const RowsRef& E, const float* Q, int32_t nb, Scores out, const RowMetric& m, float* q_sumsq_scratch, const Launch& on,
+                      int tile = 0);
+// |q|^2 per query as the GEMM epilogues read it (query_sumsq_kernel)
+int launch_query_sumsq(const float* Q, int32_t nb, int32_t dim, float* out, hipStream_t s);
 size_t score_gemm_scratch_floats(int32_t nb, int32_t dim, bool split);
 // exact MaxSim of (query, candidate chunk) pairs, all queries in one launch: dim % 16 == 0 up to 1024, dim % 128 == 0 up to 4096 (wave-private query
 // windows, maxsim_pairs_wide_kernel), nq <= 32, fp32 MFMA over fp32 or fp16 rows

@@ -140,6 +140,7 @@ __global__ __launch_bounds__(384) void score_gemm_kernel(const float* __restrict
                             if (mode == SCAN_COSINE) v[u] = 1.0f - (1.0f - d / (rn[a][u] * qn));
                             else if (mode == SCAN_DOT) v[u] = 1.0f + d;
                             else if (mode == SCAN_L2) v[u] = 1.0f - sqrtf(fmaxf(rn[a][u] + qss - 2.0f * d, 0.f));
+                            else v[u] = d;  // SCAN_RAW_DOT: the dot itself, not the scaled sum of the split arithmetic
                         }
                         if (q < B && r < n_rows) {
                             float* o = S + (int64_t)q * ld + r;
@@ -378,6 +379,7 @@ __global__ __launch_bounds__(704) void score_gemm256_kernel(const float* __restr
                             if (mode == SCAN_COSINE) v[u] = 1.0f - (1.0f - d / (rn * qn));
                             else if (mode == SCAN_DOT) v[u] = 1.0f + d;
                             else if (mode == SCAN_L2) v[u] = 1.0f - sqrtf(fmaxf(rn + qss - 2.0f * d, 0.f));
+                            else v[u] = d;  // SCAN_RAW_DOT
                         }
                         if (q < B && r < n_rows) {
                             float* o = S + (int64_t)q * ld + r;
@@ -518,7 +520,9 @@ int launch_query_sumsq(const float* Q, int32_t nb, int32_t dim, float* out, hipS
 // split_scale > 0: fp16-split arithmetic with the corpus scaled by that power of two; q_sumsq_scratch then holds
 // score_gemm_scratch_floats(nb, dim) floats: q_sumsq, q_scale and the pre-split queries.
 size_t score_gemm_scratch_floats(int32_t nb, int32_t dim, bool split) { return split ? (size_t)nb * (dim + 8) + 8 : (size_t)nb; }
-int launch_score_gemm(const RowsRef& rows, const float* Q, int32_t nb, Scores out, const RowMetric& m, float* q_sumsq_scratch, const Launch& on) {
+// tile: 0 = 128 x 256 tiles for nb > 128 in split arithmetic, else 128 x 128; 1 / 2 name the tile (2: split arithmetic only).
+int launch_score_gemm(const RowsRef& rows, const float* Q, int32_t nb, Scores out, const RowMetric& m, float* q_sumsq_scratch, const Launch& on,
+                      int tile) {
     const auto [p, f16, n_rows, dim, split_scale] = rows;
     const float* const E = static_cast<const float*>(p);
     const auto [scores, ld] = out;
@@ -526,6 +530,7 @@ int launch_score_gemm(const RowsRef& rows, const float* Q, int32_t nb, Scores ou
     const auto [n_cu, s, run_if] = on;
     if (f16 || run_if) return RL_ERR_UNSUPPORTED;
     if (nb < 1 || n_rows < 1 || dim < GK || dim % GK != 0) return RL_ERR_UNSUPPORTED;
+    if (tile < 0 || tile > 2 || (tile == 2 && !(split_scale > 0.f))) return RL_ERR_UNSUPPORTED;
     if ((reinterpret_cast<uintptr_t>(E) & 15) || (reinterpret_cast<uintptr_t>(Q) & 15)) return RL_ERR_UNSUPPORTED;
     if ((mode == SCAN_COSINE && !row_norm) || (mode == SCAN_L2 && !row_sumsq)) return RL_ERR_INVALID;
     const int64_t RT = (n_rows + GN - 1) / GN;
@@ -541,7 +546,7 @@ int launch_score_gemm(const RowsRef& rows, const float* Q, int32_t nb, Scores ou
         if (reinterpret_cast<uintptr_t>(Qs) & 15) return RL_ERR_UNSUPPORTED;
         hipLaunchKernelGGL(query_presplit_kernel, dim3(nb), dim3(256), 0, s, Q, (int)dim, q_scale, reinterpret_cast<uint4*>(Qs));
         static const bool tile128 = exp_env("RAGLITE_GEMM_TILE128") != nullptr;  // A/B switch
-        if (!tile128 && nb > GM) {  // 128 x 256 tiles: 25 % fewer bytes into the CU per flop
+        if (tile == 2 || (tile == 0 && !tile128 && nb > GM)) {  // 128 x 256 tiles: 25 % fewer bytes into the CU per flop
             const int32_t QT2 = (nb + GM2 - 1) / GM2;
             const int64_t n_tiles2 = ((RT + 7) / 8) * 8 * QT2;
             const int grid2 = (int)std::min<int64_t>(n_cu > 0 ? n_cu : 256, n_tiles2);

@@ -89,7 +89,8 @@ def test_fullsize_batched_cosine_mfma_path(corpus):
 
 
 def test_fullsize_gemm_path_cfg5_shape(corpus):
-    """cfg 5's per-GPU shape class: hundreds of queries against the full 1 M x 1024 corpus through score_gemm.hip."""
+    """cfg 5's per-GPU shape class: hundreds of queries against the full 1 M x 1024 corpus through the row-score GEMM over the
+    pre-split corpus image (maxsim_gemm.hip MODE 1, `launch_score_planes`: the default route of 96 and more queries)."""
     torch, E = corpus
     B = 300
     Q = torch.empty((B, D), dtype=torch.float32, device="cuda")
