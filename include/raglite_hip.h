@@ -433,8 +433,11 @@ typedef enum {
  *   RL_OPT_PP_XCD_PASSES        8 / 4 / 2 / 1 (2)  read only with RL_OPT_PP_SCHEDULE = 1: how many passes of a block of eight share an XCD at a
  *                                                  time.  8 = the co-scheduled order above (a few row ranges x all passes per XCD); 4, 2, 1 =
  *                                                  the XCD-affine order: an XCD serves that many passes for the whole launch, so their query
- *                                                  image stays in its L2, and the XCDs walk the row ranges in step (pp_schedule_affine) */
-enum { RL_OPT_PP_SCHEDULE = 64, RL_OPT_PP_XCD_PASSES = 65 };
+ *                                                  image stays in its L2, and the XCDs walk the row ranges in step (pp_schedule_affine)
+ *   RL_OPT_PP_LOOP              0 / 1 (1)          the same pass at an even number of K slabs (dim % 64 == 0): 0 = the tile loop, every wave
+ *                                                  spreads its loads between its own MFMAs; 1 = the alternating loop, a wave's slab is a compute
+ *                                                  and a load segment, and the two waves of a SIMD run half a period apart */
+enum { RL_OPT_PP_SCHEDULE = 64, RL_OPT_PP_XCD_PASSES = 65, RL_OPT_PP_LOOP = 66 };
 int rl_set_default_option(int key, int64_t value);
 int rl_get_default_option(int key, int64_t* value);
 int rl_index_set_option(rl_index* index, int key, int64_t value);

@@ -36,7 +36,7 @@ OPTIONS = {
     "keep_hi_plane": 19, "pairs_packed": 20, "f16_exact": 21, "lazy_images": 22, "fused_pp_sample": 23, "list_select": 24, "hi_few": 25, "topk_block": 26, "hi_pivot": 27,
 }
 # kernel schedule switches (include/raglite_hip.h, after rl_option): keys of the same calls, numbered from 64 on; results never depend on them
-SCHEDULE_OPTIONS = {"pp_schedule": 64, "pp_xcd_passes": 65}
+SCHEDULE_OPTIONS = {"pp_schedule": 64, "pp_xcd_passes": 65, "pp_loop": 66}
 
 
 def option_key(name: str) -> int:

@@ -33,13 +33,13 @@ int scan_mode(int metric) {
 // The process-wide defaults of the route options: what an index is created with (handles.h: Options).
 std::mutex g_default_opts_mu;
 Options g_default_opts;
-bool option_key_ok(int key) { return (key >= 1 && key < RL_OPT_COUNT_) || key == RL_OPT_PP_SCHEDULE || key == RL_OPT_PP_XCD_PASSES; }
+bool option_key_ok(int key) { return (key >= 1 && key < RL_OPT_COUNT_) || key == RL_OPT_PP_SCHEDULE || key == RL_OPT_PP_XCD_PASSES || key == RL_OPT_PP_LOOP; }
 bool option_value_ok(int key, int64_t value) {
     switch (key) {
         case RL_OPT_HI_SEARCH: case RL_OPT_HI_MAXSIM: case RL_OPT_PP_PASS: case RL_OPT_FUSED_TOPK: case RL_OPT_FUSED_HI: case RL_OPT_FUSED_PP:
         case RL_OPT_GEMM_PASS: case RL_OPT_QUERY_PAIRS: case RL_OPT_PLANES_GEMM: case RL_OPT_KEEP_IMAGE: case RL_OPT_KEEP_HI:
         case RL_OPT_EXACT_KTH_THRESHOLD: case RL_OPT_FUSED_TWO_ROUNDS: case RL_OPT_KEEP_HI_PLANE: case RL_OPT_F16_EXACT: case RL_OPT_LAZY_IMAGES: case RL_OPT_FUSED_PP_SAMPLE: case RL_OPT_LIST_SELECT: case RL_OPT_HI_FEW: case RL_OPT_HI_PIVOT:
-        case RL_OPT_PP_SCHEDULE:
+        case RL_OPT_PP_SCHEDULE: case RL_OPT_PP_LOOP:
             return value == 0 || value == 1;
         case RL_OPT_PP_XCD_PASSES: return value == 8 || value == 4 || value == 2 || value == 1;
         case RL_OPT_TOPK_BLOCK: case RL_OPT_PAIRS_PACKED: return value >= 0 && value <= 2;
@@ -2000,7 +2000,7 @@ int hi_batch_approx(rl_index* idx, const float* d_q, int32_t nq, int32_t n_queri
     // (round 4: ONE launch for all of the batch's passes -- grid row = pass -- so that a pass starts on the CUs the previous one leaves)
     if (pp)
         RL_TRY(launch_maxsim_pp(approx_image(idx), {idx->qplanes.p, n_queries, 0, n_gemm, nq}, chunks(idx), {sc, ld}, on(idx, s),
-                                (int)idx->opt.v[RL_OPT_PP_SCHEDULE], (int)idx->opt.v[RL_OPT_PP_XCD_PASSES]));
+                                (int)idx->opt.v[RL_OPT_PP_SCHEDULE], (int)idx->opt.v[RL_OPT_PP_XCD_PASSES], (int)idx->opt.v[RL_OPT_PP_LOOP]));
     for (int32_t b = 0; !pp && b < n_gemm; b += GEMM_PASS_QUERIES) {
         const int32_t n_q = std::min<int32_t>(GEMM_PASS_QUERIES, n_gemm - b);
         RL_TRY(launch_maxsim_gemm(approx_image(idx), {idx->qplanes.p, n_queries, b, n_q, nq}, chunks(idx), {sc + (int64_t)b * ld, ld}, on(idx, s),
@@ -2425,7 +2425,7 @@ int rl_maxsim_approx_scores(rl_index* idx, const float* query_vecs, int32_t n_qu
         const Scores out{d_o + (int64_t)b * ld, ld};
         if (kernel == 0)
             RL_TRY(launch_maxsim_pp(approx_image(idx), q, chunks(idx), out, on(idx, s), (int)idx->opt.v[RL_OPT_PP_SCHEDULE],
-                                    (int)idx->opt.v[RL_OPT_PP_XCD_PASSES]));
+                                    (int)idx->opt.v[RL_OPT_PP_XCD_PASSES], (int)idx->opt.v[RL_OPT_PP_LOOP]));
         else
             RL_TRY(launch_maxsim_gemm(approx_image(idx), q, chunks(idx), out, on(idx, s), /*hi_only*/ true, /*all_passes*/ false));
     }
@@ -2664,7 +2664,7 @@ int rl_time_kernel(rl_index* idx, int kind, const float* q_dev, int32_t nq, int3
     RL_HIP(hipEventRecord(e0, s));
     for (int i = 0; i < iters && st == RL_OK; ++i) {
         if (kind == 7) st = launch_maxsim_pp(approx_image(idx), {idx->qplanes.p, pp_n, 0, pp_n, pp_vec}, chunks(idx), {idx->scores.as<float>(), ldc}, on(idx, s),
-                                             (int)idx->opt.v[RL_OPT_PP_SCHEDULE], (int)idx->opt.v[RL_OPT_PP_XCD_PASSES]);
+                                             (int)idx->opt.v[RL_OPT_PP_SCHEDULE], (int)idx->opt.v[RL_OPT_PP_XCD_PASSES], (int)idx->opt.v[RL_OPT_PP_LOOP]);
         else if (kind == 3) st = gemm_pass(idx, nq / GEMM_PASS_QUERIES, GEMM_PASS_QUERIES, 0, GEMM_PASS_QUERIES, idx->scores.as<float>(), ldc, s);
         else if (kind == 8) {
             const auto& r = idx->replay;

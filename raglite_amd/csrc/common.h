@@ -599,7 +599,7 @@ int launch_maxsim_gemm(const RowsRef& image, const QueryImageRef& q, const Chunk
 // maxsim_pp.hip: the approximate pass of the headline pipeline -- SIXTEEN queries per pass over a one-plane image, one product
 constexpr int32_t PP_PASS_QUERIES = 16;
 int launch_maxsim_pp(const RowsRef& image, const QueryImageRef& q, const ChunkMap& c, Scores out, const Launch& on,
-                     int schedule, int xcd_passes);  // RL_OPT_PP_SCHEDULE, RL_OPT_PP_XCD_PASSES
+                     int schedule, int xcd_passes, int loop);  // RL_OPT_PP_SCHEDULE, RL_OPT_PP_XCD_PASSES, RL_OPT_PP_LOOP
 // the matrix pipe's sustained fp16 rate under the pass kernel's own MFMA stream (no loads, no epilogue): rl_time_kernel kind 9
 constexpr int32_t MFMA_RATE_ITERS = 1000;  // x 32 MFMAs per wave: the MFMA count of a wave over one pass of 1 M rows x 1024
 int launch_mfma_f16_rate(float* out, int n_cu, int32_t iters, hipStream_t s, double* flops);

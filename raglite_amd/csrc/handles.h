@@ -21,7 +21,7 @@ constexpr size_t SCORE_BATCH_BYTES = size_t(8) << 30;  // cap of the [B x N] sco
 // Route options (raglite_hip.h "options"): per index, copied from the process-wide defaults when the index is created.  The library
 // reads no environment variable.
 struct Options {
-    int64_t v[RL_OPT_PP_XCD_PASSES + 1];  // (keys 1 .. RL_OPT_COUNT_ - 1, and the schedule switches from 64 on)
+    int64_t v[RL_OPT_PP_LOOP + 1];  // (keys 1 .. RL_OPT_COUNT_ - 1, and the schedule switches from 64 on)
     Options() {
         for (auto& x : v) x = 0;
         v[RL_OPT_HI_SEARCH] = v[RL_OPT_HI_MAXSIM] = v[RL_OPT_HI_PRODUCTS] = v[RL_OPT_PP_PASS] = v[RL_OPT_FUSED_TOPK] = v[RL_OPT_FUSED_HI] = 1;
@@ -31,6 +31,7 @@ struct Options {
         v[RL_OPT_HI_PIVOT] = 1;
         v[RL_OPT_PP_SCHEDULE] = 1;
         v[RL_OPT_PP_XCD_PASSES] = 2;  // (measured: DESIGN.md 4.1)
+        v[RL_OPT_PP_LOOP] = 1;        // (measured: DESIGN.md 4.1)
         v[RL_OPT_IMAGE_HEADROOM_MB] = -1;
         v[RL_OPT_ARITHMETIC] = RL_ARITH_AUTO;
     }

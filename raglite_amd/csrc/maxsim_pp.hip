@@ -33,6 +33,27 @@
 // are added in another order: scores agree to the last bits, not bit for bit, on float data.  Needs an index without empty chunks (a chunk
 // is found by counting chunk ends), nq <= 32, dim % 32 == 0, dim >= 256.
 //
+// MODE 4 (RL_OPT_PP_LOOP = 1; an even number of K slabs, like MODE 3): the ALTERNATING loop.  Tile, fragment layout, products and their
+// order per accumulator, epilogue, staging and flush are MODE 3's -- the same bits.  What differs is when a wave loads.  Per wave, slab g
+// is two SEGMENTS, each ended by the workgroup barrier:
+//   C_g      the 32 MFMAs of slab g from ef[0..7] and the slab's query set, back to back; no LDS or VMEM instruction;
+//   L_{g+1}  four `global_load_dwordx4`: the query fragments of slab g + 2 into the set C_g just multiplied from; the wave's corpus piece
+//            of slab g + 1 + PP_LC; the eight `ds_read_b128` of slab g + 1 into ef (one set: a slab's reads are issued after its
+//            predecessor's MFMAs); `lgkmcnt(0)`, and `vmcnt(6)`: this wave's VMEM queue is, old -> new, .. C(g - 1 + LC) | Q(g + 1) x4,
+//            C(g + LC) | Q(g + 2) x4, C(g + 1 + LC), so slab g + 1's query set has landed when the six newest are in flight -- a
+//            piece gets two periods to land, as under the other loops.  Never `vmcnt(0)` inside the loop.
+// Waves 0-3 run C | L | C | L ..; waves 4-7 run the SAME program one barrier later (the prologue gives them one barrier more, the tail
+// gives waves 0-3 one more), L | C | L | C ..: in every interval a SIMD has one wave's MFMAs beside the other's loads.  Interval 2g is
+// C_g of waves 0-3 and L_g of waves 4-7, interval 2g + 1 is L_{g+1} of waves 0-3 and C_g of waves 4-7.  Barriers per role: one in the
+// prologue for all, one more for waves 4-7; 2 nslab per tile for both (same code); one at the tail for waves 0-3: equal sums.
+// RING (PP_DC = 8 slots, PP_LC = 6; the prologue issues pieces 0 .. 6): the pieces of slab s are issued in L_{s-6} and certified by their
+// issuer's `vmcnt(6)` at the end of L_{s-4} -- interval 2s - 8 at the latest -- with a barrier behind it; the first read of slab s is
+// L_s of waves 0-3 in interval 2s - 1.  Slot s % 8 is rewritten by the pieces of slab s + 8, issued in L_{s+2}: interval 2s + 3 at the
+// earliest (waves 0-3).  The last reader of slab s is L_s of waves 4-7 in interval 2s, which ends with `lgkmcnt(0)` in front of its
+// barrier: three barriers lie between.  At a tile boundary waves 4-7 issue their L one interval early (the comment there): their reads
+// are then where waves 0-3's are, and their piece overwrites the slot of slab s - 2, last read by their own L_{s-2} three barriers back.
+// The block epilogues of a tile stand in the load segment behind its last C; how the two roles share that boundary: the comment there.
+//
 // MODE 1 (round 5): the SAMPLE pass of the same search on the same tile -- the similarities of every stride-th 256-row tile with all queries,
 // written out (the tile epilogue applies the metric's transform; its stores sit in the wave's in-order VMEM queue in front of the next tile's
 // first query loads, a stall of a few microseconds per 25-us tile that a pass of two or three tiles per workgroup can afford).  Was the
@@ -148,7 +169,7 @@ struct PpRows {
 
 // DBG: timing skeletons (experiment builds only, -DRAGLITE_EXPERIMENTS + RAGLITE_PP_DBG / RAGLITE_PP_ROWS_DBG; WRONG results):
 // 2 = no MFMAs, 8 = no LDS fragment reads, 16 = no corpus DMAs, 32 = no query loads, 128 = no block epilogues (the MFMAs stay); all on
-// MODE 0's slab-counting loop.
+// MODE 0's slab-counting loop; 128 also on MODE 4's alternating loop (RAGLITE_PP_DBG = 132).
 // ROWNORM (MODE 2, cosine): the block-wide bound is only the PREFILTER; a group that passes it is tested row by row against T |e_row|.
 // MODE 3: MODE 0 -- same arguments, same arithmetic in the same order, same bits -- for an EVEN number of K slabs, with the tiles walked by an
 // explicit loop (the comment in front of the main loop): a tile's first slab multiplies into a zero C operand instead of accumulators the
@@ -161,8 +182,9 @@ __global__ __launch_bounds__(512, 2) void maxsim_pp_kernel(const char* __restric
                                                            const uint32_t* __restrict__ ends_bits, float* __restrict__ out, int64_t out_stride,
                                                            float inv_e_scale, const uint32_t* __restrict__ run_if, PpRows rs) {
     constexpr bool ROWS = MODE == 2, SCORES = MODE == 1, GROUPS = ROWS || SCORES;  // GROUPS: a "query" of the tile is a group of 32 single-vector queries
-    constexpr bool TILES = MODE == 3;  // the explicit tile loop (nslab even)
-    static_assert(!TILES || DBG == 0, "the timing skeletons keep the slab-counting loop");
+    constexpr bool ALT = MODE == 4;    // the alternating pair loop (nslab even): compute and load SEGMENTS, the SIMD partners half a period apart
+    constexpr bool TILES = MODE == 3 || ALT;  // the explicit tile loop (nslab even)
+    static_assert(!TILES || DBG == 0 || (ALT && DBG == 128), "the timing skeletons keep the slab-counting loop (but the bare alternating loop)");
     __shared__ __attribute__((aligned(16))) char smem[PP_LDS];
     if (run_if && __builtin_amdgcn_readfirstlane((int)*run_if) == 0) return;  // whole grid: a guarded launch that is not needed
     const int lane = threadIdx.x & 63;
@@ -860,8 +882,104 @@ __global__ __launch_bounds__(512, 2) void maxsim_pp_kernel(const char* __restric
             }
         }
     };
+    // ---- MODE 4: the ALTERNATING loop (the header comment has the schedule and the ring argument).  One program for both roles: waves 4-7
+    // run it one barrier interval behind waves 0-3 (one barrier more in front of it, one fewer behind it).
+    // C_g: the 32 MFMAs of slab g back to back -- no LDS or VMEM instruction -- and the barrier.
+    [[maybe_unused]] auto alt_mfmas = [&](f32x4 (&q)[4], auto FIRST_) __attribute__((always_inline)) {
+        __builtin_amdgcn_sched_barrier(0);
+        [&]<int... A>(std::integer_sequence<int, A...>) { (mfma_group(q, std::integral_constant<int, A>{}, FIRST_), ...); }
+        (std::make_integer_sequence<int, PP_NBLK>{});
+        __builtin_amdgcn_sched_barrier(0);
+    };
+    [[maybe_unused]] auto alt_barrier = [&]() __attribute__((always_inline)) {
+        asm volatile("s_barrier" ::: "memory");
+        __builtin_amdgcn_sched_barrier(0);
+    };
+    [[maybe_unused]] auto alt_compute = [&](f32x4 (&q)[4], auto FIRST_) __attribute__((always_inline)) {
+        alt_mfmas(q, FIRST_);
+        alt_barrier();
+    };
+    // L_{g+1}, first half: the query fragments of slab g + 2 into the set C_g multiplied from, the wave's corpus piece of slab
+    // g + 1 + PP_LC, the eight fragment reads of slab g + 1
+    [[maybe_unused]] auto alt_issue = [&](f32x4 (&qn)[4]) __attribute__((always_inline)) {
+        issue_qregs(qn);
+        issue_c();
+        [&]<int... A>(std::integer_sequence<int, A...>) { (read_slab(std::integral_constant<int, A>{}), ...); }
+        (std::make_integer_sequence<int, PP_NBLK>{});
+        c_slot = c_slot + 1 == PP_DC ? 0 : c_slot + 1;
+        __builtin_amdgcn_sched_barrier(0);
+    };
+    // L_{g+1}, second half: all eight reads; this wave's VMEM queue, old -> new: .. C(g - 1 + LC) | Q(g + 1) x4, C(g + LC) | Q(g + 2) x4,
+    // C(g + 1 + LC): slab g + 1's query set `qc` has landed when the six newest are outstanding -- a piece gets two periods to land
+    [[maybe_unused]] auto alt_wait = [&](f32x4 (&qc)[4]) __attribute__((always_inline)) {
+        __builtin_amdgcn_sched_barrier(0);
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
+        pp_pin(ef[0], ef[1], ef[2], ef[3]);
+        pp_pin(ef[4], ef[5], ef[6], ef[7]);
+        pp_pin(qc[0], qc[1], qc[2], qc[3]);
+        __builtin_amdgcn_sched_barrier(0);
+    };
+    [[maybe_unused]] auto alt_landed = [&](f32x4 (&qc)[4]) __attribute__((always_inline)) {
+        alt_wait(qc);
+        alt_barrier();
+    };
+    [[maybe_unused]] auto alt_loop = [&]() __attribute__((always_inline)) {
+        const int pairs = nslab >> 1;
+        // prologue (C(0 .. LC - 1) are on their way): one piece more -- L_{g+1} fetches slab g + 1 + LC --, the query sets of slabs 0
+        // and 1, slab 0's fragments; then waves 4-7 let one barrier pass: the skew
+        issue_c();
+        issue_qregs(qA);
+        issue_qregs(qB);
+        asm volatile("s_waitcnt vmcnt(0)\n\ts_barrier" ::: "memory");
+        [&]<int... A>(std::integer_sequence<int, A...>) { (read_slab(std::integral_constant<int, A>{}), ...); }
+        (std::make_integer_sequence<int, PP_NBLK>{});
+        c_slot = 1;
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        pp_pin(ef[0], ef[1], ef[2], ef[3]);
+        pp_pin(ef[4], ef[5], ef[6], ef[7]);
+        pp_pin(qA[0], qA[1], qA[2], qA[3]);
+        pp_pin(qB[0], qB[1], qB[2], qB[3]);
+        if (wv >= 4) asm volatile("s_barrier" ::: "memory");
+        for (int t = 0; t < nt; ++t) {
+            if constexpr (!(DBG & 128)) pp_tile_ends(t);
+            alt_compute(qA, std::true_type{});
+#pragma nounroll
+            for (int p = 1; p < pairs; ++p) {
+                alt_issue(qA); alt_landed(qB);
+                alt_compute(qB, std::false_type{});
+                alt_issue(qB); alt_landed(qA);
+                alt_compute(qA, std::false_type{});
+            }
+            alt_issue(qA); alt_landed(qB);
+            // The tile's last C and the load segment behind it: the next tile's first loads on their way, then the eight block epilogues.
+            // Waves 0-3 run them as every other segment pair (barrier | epilogues | barrier): beside the partners' last C.  Waves 4-7
+            // do NOT wait for the barrier behind their last C -- the partners would be 3 900 cycles into their epilogues and they idle
+            // -- but run on into their own epilogues, beside the partners' (as under the tile loop), and take that barrier behind the
+            // seventh block instead: the eighth runs beside the partners' first C of the next tile.  Same number of barriers per tile
+            // for both roles, same order of every wave's own loads and waits; the loads of waves 4-7 move one interval FORWARD (slab
+            // 0 of the next tile landed long ago, and the slot their piece overwrites was last read by themselves, three barriers back).
+            // The chunk-end bits landed with the first load segment's lgkmcnt(0).
+            alt_mfmas(qB, std::false_type{});
+            if (wv < 4) alt_barrier();
+            alt_issue(qB);
+            if constexpr (!(DBG & 128)) {
+                asm volatile("" : "+s"(tile_ends));
+                [&]<int... A>(std::integer_sequence<int, A...>) { (block_epilogue_maxsim(std::integral_constant<int, A>{}, t), ...); }
+                (std::make_integer_sequence<int, PP_NBLK - 1>{});
+            }
+            if (wv >= 4) alt_barrier();
+            if constexpr (!(DBG & 128)) {
+                block_epilogue_maxsim(std::integral_constant<int, PP_NBLK - 1>{}, t);
+                if (own_cnt - own_flushed > PP_STAGE - PP_RT) flush_out();  // (a tile finishes at most PP_RT chunks)
+            }
+            alt_landed(qA);
+        }
+        if (wv < 4) asm volatile("s_barrier" ::: "memory");  // (the skew undone: the partners' last load segment)
+    };
 #undef PP_I
-    if (wv < 4) main_loop(std::false_type{});
+    if constexpr (ALT) alt_loop();
+    else if (wv < 4) main_loop(std::false_type{});
     else main_loop(std::true_type{});
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // look-ahead DMAs must not outlive the workgroup's LDS
     dump_log();
@@ -884,7 +1002,8 @@ __global__ __launch_bounds__(512, 2) void maxsim_pp_kernel(const char* __restric
 // n_q queries `first .. first + n_q - 1` of a launch_query_planes buffer over `n_queries`, each nq (<= 32) vectors, against
 // a one-plane image (fp16 hi halves, or an fp16-stored corpus): out[q * out_stride + chunk], one MFMA product per multiply.
 // Sixteen queries per pass over the image; n_q > 16: ceil(n_q / 16) passes in ONE launch (grid rows).
-int launch_maxsim_pp(const RowsRef& rows, const QueryImageRef& q, const ChunkMap& c, Scores o, const Launch& on, int schedule, int xcd_passes) {
+int launch_maxsim_pp(const RowsRef& rows, const QueryImageRef& q, const ChunkMap& c, Scores o, const Launch& on, int schedule, int xcd_passes,
+                     int loop) {
     const auto [image, one_plane, n_rows, dim, split_scale] = rows;
     const auto [qbuf, n_queries, first, n_q, nq] = q;
     const auto [row_to_chunk, chunk_offsets, n_chunks, ends_bits] = c;
@@ -905,7 +1024,8 @@ int launch_maxsim_pp(const RowsRef& rows, const QueryImageRef& q, const ChunkMap
     const dim3 grid = schedule == 1 ? dim3((unsigned)(gx * passes)) : dim3((unsigned)gx, (unsigned)passes), blk(512);
     PpRows rs{};
     rs.xcd_passes = schedule == 1 ? xcd_passes : 8;
-    // an even number of K slabs (dim % 64 == 0): the tile loop (MODE 3); odd: the slab-counting loop (MODE 0).  Same bits.
+    // an even number of K slabs (dim % 64 == 0): the tile loop (MODE 3) or, loop = 1 (RL_OPT_PP_LOOP), the alternating loop (MODE 4);
+    // odd: the slab-counting loop (MODE 0).  Same bits.
 #define RL_PP_LAUNCH(DBG_) RL_PP_LAUNCH_MODE(DBG_, 0)
 #define RL_PP_LAUNCH_MODE(DBG_, MODE_)                                                                                                     \
     hipLaunchKernelGGL((maxsim_pp_kernel<DBG_, MODE_, false>), grid, blk, 0, s, static_cast<const char*>(image), n_rows, nslab, qfrag, qmeta, n_q, row_to_chunk, \
@@ -924,10 +1044,13 @@ int launch_maxsim_pp(const RowsRef& rows, const QueryImageRef& q, const ChunkMap
     else if (dbg == 144) RL_PP_LAUNCH(144);
     else if (dbg == 160) RL_PP_LAUNCH(160);
     else if (dbg == 184) RL_PP_LAUNCH(184);
+    else if (dbg == 132 && nslab % 2 == 0) RL_PP_LAUNCH_MODE(128, 4);  // (128 + 4: the bare alternating loop, against 128)
     else if (dbg == 1 || nslab % 2) RL_PP_LAUNCH(0);
+    else if (loop == 1) RL_PP_LAUNCH_MODE(0, 4);
     else RL_PP_LAUNCH_MODE(0, 3);
 #else
     if (nslab % 2) RL_PP_LAUNCH(0);
+    else if (loop == 1) RL_PP_LAUNCH_MODE(0, 4);
     else RL_PP_LAUNCH_MODE(0, 3);
 #endif
 #undef RL_PP_LAUNCH
