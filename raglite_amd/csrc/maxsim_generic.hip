@@ -820,9 +820,10 @@ __global__ __launch_bounds__(256) void maxsim_cand_kernel(const float* __restric
     [[maybe_unused]] bool any_lo = false;
     [[maybe_unused]] float q_unscale = 1.f;
     const float* Qq = Q + (int64_t)qi * nq * CD;
-    if constexpr (SPLIT) {
-        // the whole query (nq x 128) scaled to [2^13, 2^14) by one power of two, split into fp16 (hi, lo); MFMA m uses
-        // k = 16 (2m + (u >> 2)) + 4 kq + (u & 3), the positions of A fragments 2m and 2m + 1
+    [[maybe_unused]] float q_scale = 1.f;
+    if constexpr (H) {
+        // the whole query (nq x 128) scaled to [2^13, 2^14) by one power of two before it is split into fp16 (hi, lo), over fp16-stored rows
+        // too: unscaled, the lo half of every element below 2^-2 was subnormal, and the scores of 2^k q were not 2^k times those of q
         float mxq = 0.f;
 #pragma unroll
         for (int h = 0; h < NQT; ++h) {
@@ -838,8 +839,11 @@ __global__ __launch_bounds__(256) void maxsim_cand_kernel(const float* __restric
         for (int o = 32; o > 0; o >>= 1) mxq = fmaxf(mxq, __shfl_xor(mxq, o));
         int ex = 0;
         if (mxq > 0.f && mxq < INFINITY) (void)frexpf(mxq, &ex);
-        const float q_scale = ldexpf(1.f, 14 - ex);
-        q_unscale = ldexpf(1.f, ex - 14) / e_scale;
+        q_scale = ldexpf(1.f, 14 - ex);
+        q_unscale = F16 ? ldexpf(1.f, ex - 14) : ldexpf(1.f, ex - 14) / e_scale;  // stored halves are not rescaled
+    }
+    if constexpr (SPLIT) {
+        // MFMA m uses k = 16 (2m + (u >> 2)) + 4 kq + (u & 3), the positions of A fragments 2m and 2m + 1
 #pragma unroll
         for (int h = 0; h < NQT; ++h) {
             const int qv = 16 * h + fj;
@@ -880,7 +884,7 @@ __global__ __launch_bounds__(256) void maxsim_cand_kernel(const float* __restric
                 const f32x4 v0 = *reinterpret_cast<const f32x4*>(qp), v1 = *reinterpret_cast<const f32x4*>(qp + 4);
 #pragma unroll
                 for (int u = 0; u < 8; ++u) {
-                    const float x = qv < nq ? (u < 4 ? v0[u] : v1[u - 4]) : 0.f;
+                    const float x = qv < nq ? (u < 4 ? v0[u] : v1[u - 4]) * q_scale : 0.f;
                     const _Float16 hi = (_Float16)x;
                     const _Float16 lo = (_Float16)(x - (float)hi);
                     qhi[h][mm][u] = hi;
@@ -964,6 +968,8 @@ __global__ __launch_bounds__(256) void maxsim_cand_kernel(const float* __restric
                         for (int h = 0; h < NQT; ++h)
                             acc[h] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a[mm], qlo[h][mm], acc[h], 0, 0, 0);
                 }
+#pragma unroll
+                for (int h = 0; h < NQT; ++h) acc[h] = acc[h] * q_unscale;
             }
             // C/D: column fj = query, row 4*kq + reg = corpus row r0 + 4*kq + reg
 #pragma unroll
