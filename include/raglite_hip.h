@@ -578,6 +578,22 @@ int rl_maxsim_approx_scores(rl_index* index, const float* query_vecs, int32_t n_
 int rl_maxsim_rerank(rl_index* index, const float* query_vecs, int32_t n_queries, int32_t nq,
                      const int32_t* candidates, int32_t n_cand, float* out_scores, int mem, void* stream);
 
+/* rl_maxsim_rerank_ragged: rl_maxsim_rerank where every query carries its own number of vectors, any number >= 1.
+ *   query_vecs f32 [qv_off[n_queries] x dim]: query b owns rows qv_off[b] .. qv_off[b + 1] - 1
+ *   qv_off     int64 [n_queries + 1] in HOST memory whatever `mem` says: from 0, strictly ascending (no query without vectors)
+ *   candidates / out_scores [n_queries x n_cand] as in rl_maxsim_rerank, -1, tombstoned and out-of-range ordinals likewise
+ * The contract: every query's scores equal, bit for bit, the fp32 sum in slab order (((s_0 + s_1) + s_2) ...) of what
+ * rl_maxsim_rerank returns on this index, with the same options, for each slab of 32 of the query's vectors alone (the last
+ * slab with its own shorter nq).  For a query of at most 32 vectors that is rl_maxsim_rerank itself.  No query's bits depend
+ * on another query of the call.
+ * Routes: dim % 16 == 0, dim <= 1024, dim != 128: one launch for all queries (maxsim_ragged_kernel), over fp32 or fp16-stored
+ * rows.  dim 128, 1024 < dim <= 4096 with dim % 128 == 0, and any other dim of an fp32-stored index: a backstop that calls
+ * rl_maxsim_rerank's own kernels per (query, slab) and adds the slabs in order -- correct, unhurried.  An fp16-stored index with
+ * dim % 16 != 0: RL_ERR_UNSUPPORTED.  The sizes, null pointers and the table are checked before any HIP call (RL_ERR_INVALID);
+ * n_queries == 0 returns RL_OK. */
+int rl_maxsim_rerank_ragged(rl_index* index, const float* query_vecs, const int64_t* qv_off, int32_t n_queries,
+                            const int32_t* candidates, int32_t n_cand, float* out_scores, int mem, void* stream);
+
 /* ---- section 8e: shard merge --------------------------------------------------------------------
  * Merge `n_lists` per-shard top-k lists per query (as produced by an all-gather of each rank's
  * rl_search_rows / rl_maxsim_topk output with GLOBAL ids) into the global top-k by
@@ -857,7 +873,11 @@ int rl_hybrid_search_per_query(rl_index* index, rl_keyword_index* kw, const floa
  *      score -inf;
  *   3. rl_rerank_order, the first k <= n_cand: out_scores f32 (the MaxSim scores) / out_chunks int32 [n_queries x k],
  *      best first, out_counts [n_queries].
- * nq >= 1 and 1 <= k <= n_cand <= 4096 are checked before the index is looked at. */
+ * nq >= 1 and 1 <= k <= n_cand <= 4096 are checked before the index is looked at.
+ *
+ * rl_search_rerank_ragged is that pipeline with (query_vecs f32 [qv_off[n_queries] x dim], qv_off int64 [n_queries + 1] in HOST
+ * memory) in place of (query_vecs, nq): step 2 is rl_maxsim_rerank_ragged, its table, contract and routes; a query may have more
+ * than 32 vectors on either storage.  The sizes, the filters and the table are checked before any HIP call. */
 int rl_rerank_order(const float* scores, const int32_t* candidates, int32_t n_queries, int32_t n_cand, int32_t k,
                     float* out_scores, int32_t* out_chunks, int32_t* out_pos, int32_t* out_counts, int mem, void* stream);
 int rl_search_rerank_per_query(rl_index* index, rl_keyword_index* kw, const float* queries, int32_t n_queries,
@@ -866,6 +886,12 @@ int rl_search_rerank_per_query(rl_index* index, rl_keyword_index* kw, const floa
                                const int64_t* rank_limits, const double* weights, int32_t rrf_k, int32_t n_cand,
                                const float* query_vecs, int32_t nq, int32_t k, float* out_scores, int32_t* out_chunks,
                                int32_t* out_counts, int mem, void* stream);
+int rl_search_rerank_ragged(rl_index* index, rl_keyword_index* kw, const float* queries, int32_t n_queries,
+                            int32_t num_hits, int32_t n_each, const int64_t* q_off, const int32_t* q_terms,
+                            const uint32_t* chunk_filters, int32_t n_filters, const int32_t* query_filter,
+                            const int64_t* rank_limits, const double* weights, int32_t rrf_k, int32_t n_cand,
+                            const float* query_vecs, const int64_t* qv_off, int32_t k, float* out_scores, int32_t* out_chunks,
+                            int32_t* out_counts, int mem, void* stream);
 
 /* ---- chunk spans (src/raglite/_search.py:302-361, `retrieve_chunk_spans`; :417-433, `search_and_rerank_chunk_spans`) ---------
  * A span table sits beside an rl_index as a keyword index does: it covers the SAME chunk ordinals, is immutable, and is built
@@ -899,7 +925,7 @@ int rl_search_rerank_per_query(rl_index* index, rl_keyword_index* kw, const floa
  * arguments, checks, locks and routes) into scratch the index owns, then rl_chunk_spans of each query's reranked first k on the
  * same stream, nothing read back in between.  k * (1 + n_off) <= 4096 and the table are checked first.  out_top_chunks
  * int32 [n_queries x k] / out_top_counts [n_queries] are rl_search_rerank_per_query's out_chunks / out_counts; the span outputs
- * are rl_chunk_spans' with n_in = k. */
+ * are rl_chunk_spans' with n_in = k.  rl_search_rerank_spans_ragged: the same over rl_search_rerank_ragged. */
 typedef struct rl_span_table rl_span_table;
 int rl_span_table_create(rl_span_table** out, const int32_t* doc, const int32_t* pos, int64_t n_chunks);
 int rl_span_table_info(const rl_span_table* table, int64_t* n_chunks, int64_t* n_live, int64_t* device_bytes);
@@ -915,6 +941,14 @@ int rl_search_rerank_spans_per_query(rl_index* index, rl_keyword_index* kw, cons
                                      const int32_t* offsets, int32_t n_off, int32_t* out_top_chunks, int32_t* out_top_counts,
                                      int32_t* out_chunks, int32_t* out_span_len, double* out_span_scores, int32_t* out_n_spans,
                                      int32_t* out_n_chunks, int mem, void* stream);
+int rl_search_rerank_spans_ragged(rl_index* index, rl_keyword_index* kw, const float* queries, int32_t n_queries,
+                                  int32_t num_hits, int32_t n_each, const int64_t* q_off, const int32_t* q_terms,
+                                  const uint32_t* chunk_filters, int32_t n_filters, const int32_t* query_filter,
+                                  const int64_t* rank_limits, const double* weights, int32_t rrf_k, int32_t n_cand,
+                                  const float* query_vecs, const int64_t* qv_off, int32_t k, const rl_span_table* table,
+                                  const int32_t* offsets, int32_t n_off, int32_t* out_top_chunks, int32_t* out_top_counts,
+                                  int32_t* out_chunks, int32_t* out_span_len, double* out_span_scores, int32_t* out_n_spans,
+                                  int32_t* out_n_chunks, int mem, void* stream);
 
 /* ---- metadata filters on the device ---------------------------------------------------------------------------------------
  * The reference's metadata filter is JSON containment (src/raglite/_search.py:82-94): a chunk matches when, for every key of

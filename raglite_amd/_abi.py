@@ -127,6 +127,7 @@ _SIGNATURES = {
     "rl_maxsim_batch_begin": [c_void_p, c_void_p, c_i32, c_i32, c_i32, c_void_p, c_int, c_void_p],
     "rl_maxsim_batch_finish": [c_void_p, c_void_p, c_void_p, c_i32, c_i32, c_void_p, c_void_p, c_int, c_void_p],
     "rl_maxsim_rerank": [c_void_p, c_void_p, c_i32, c_i32, c_void_p, c_i32, c_void_p, c_int, c_void_p],
+    "rl_maxsim_rerank_ragged": [c_void_p, c_void_p, c_void_p, c_i32, c_void_p, c_i32, c_void_p, c_int, c_void_p],
     "rl_merge_topk": [c_void_p, c_void_p, c_i32, c_i32, c_i32, c_i32, c_void_p, c_void_p, c_int, c_void_p],
     "rl_topk": [c_void_p, c_i32, c_i64, c_i64, c_i32, c_void_p, c_void_p, c_int, c_void_p],
     "rl_time_kernel": [c_void_p, c_int, c_void_p, c_i32, c_i32, C.POINTER(C.c_float), c_void_p],
@@ -177,6 +178,9 @@ _SIGNATURES = {
     "rl_search_rerank_per_query": [c_void_p, c_void_p, c_void_p, c_i32, c_i32, c_i32, c_void_p, c_void_p, c_void_p, c_i32, c_void_p,
                                    c_void_p, c_void_p, c_i32, c_i32, c_void_p, c_i32, c_i32, c_void_p, c_void_p, c_void_p, c_int,
                                    c_void_p],
+    "rl_search_rerank_ragged": [c_void_p, c_void_p, c_void_p, c_i32, c_i32, c_i32, c_void_p, c_void_p, c_void_p, c_i32, c_void_p,
+                                c_void_p, c_void_p, c_i32, c_i32, c_void_p, c_void_p, c_i32, c_void_p, c_void_p, c_void_p, c_int,
+                                c_void_p],
     "rl_span_table_create": [C.POINTER(c_void_p), c_void_p, c_void_p, c_i64],
     "rl_span_table_info": [c_void_p, C.POINTER(c_i64), C.POINTER(c_i64), C.POINTER(c_i64)],
     "rl_span_table_destroy": [c_void_p],
@@ -184,6 +188,9 @@ _SIGNATURES = {
     "rl_search_rerank_spans_per_query": [c_void_p, c_void_p, c_void_p, c_i32, c_i32, c_i32, c_void_p, c_void_p, c_void_p, c_i32, c_void_p,
                                          c_void_p, c_void_p, c_i32, c_i32, c_void_p, c_i32, c_i32, c_void_p, c_void_p, c_i32, c_void_p,
                                          c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p],
+    "rl_search_rerank_spans_ragged": [c_void_p, c_void_p, c_void_p, c_i32, c_i32, c_i32, c_void_p, c_void_p, c_void_p, c_i32, c_void_p,
+                                      c_void_p, c_void_p, c_i32, c_i32, c_void_p, c_void_p, c_i32, c_void_p, c_void_p, c_i32, c_void_p,
+                                      c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p],
     "rl_metadata_store_create": [C.POINTER(c_void_p), c_void_p, c_void_p, c_i64, c_int, c_void_p],
     "rl_metadata_store_append": [c_void_p, c_void_p, c_void_p, c_i64, c_int, c_void_p],
     "rl_metadata_store_memory": [c_void_p, C.POINTER(c_i64)],

@@ -21,7 +21,7 @@ LIB_PATH = LIB_DIR / "libraglite_hip.so"
 SOURCES = [
     "api.hip", "api_ingest.hip", "api_keyword.hip", "api_retrieval.hip",  # the C ABI (host code only)
     "synth.hip", "scan.hip", "scan16.hip", "select.hip", "mask.hip", "score_gemm.hip", "hi_filter.hip",  # row and chunk search
-    "maxsim_stream.hip", "maxsim_generic.hip", "maxsim_gemm.hip", "maxsim_pp.hip",  # MaxSim
+    "maxsim_stream.hip", "maxsim_generic.hip", "maxsim_ragged.hip", "maxsim_gemm.hip", "maxsim_pp.hip",  # MaxSim
     "pool_norm.hip", "partition_sim.hip", "partition_dp.hip", "chunklet_dp.hip", "sentence_dp.hip",  # ingestion
     "attention_varlen.hip",  # the packed encoder's attention
     "encoder.hip",  # the native encoder forward for short packs

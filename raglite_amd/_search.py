@@ -12,7 +12,7 @@
     search_and_rerank_chunks(...)                                         (`_search.py:400-414`)
     search_and_rerank_chunks_batch(queries, ...) -> list of search_and_rerank_chunks's results: search, fusion, MaxSim rerank and
                                                     ordering of the whole batch in one device call
-    rerank_chunks_batch(queries, chunk_ids_per_query, ...) -> the MaxSim rerank of given lists, one launch per distinct nq
+    rerank_chunks_batch(queries, chunk_ids_per_query, ...) -> the MaxSim rerank of given lists, one launch whatever the queries' lengths
     retrieve_chunk_spans(chunk_ids, *, neighbors=(-1, 1), config=None) -> list[ChunkSpan]      (`_search.py:302-361`)
     retrieve_chunk_spans_batch(chunk_ids_per_query, ...) -> the same for ragged lists, one device call
     search_and_rerank_chunk_spans(...)                                    (`_search.py:417-433`)
@@ -37,7 +37,7 @@ from typing import Any, Callable, Sequence
 
 import numpy as np
 
-from raglite_amd import _embed, _keyword, _metadata, _ops
+from raglite_amd import _embed, _keyword, _metadata, _ops, _ragged
 from raglite_amd._config import DEFAULT_CHUNK_MAX_SIZE, HotPathConfig
 from raglite_amd._embed import embed_strings
 
@@ -1089,7 +1089,8 @@ class RankedResults:
 
 
 def _groups_by_nq(vecs: Sequence[np.ndarray]) -> list[list[int]]:
-    """The queries grouped by their number of token vectors, each group in query order (ColBERT's fixed query length gives one)."""
+    """The queries grouped by their number of token vectors, each group in query order: the calls of a ranker that takes no ragged
+    route (`MaxSimRanker._routes`), one per group."""
     groups: dict[int, list[int]] = {}
     for b, v in enumerate(vecs):
         groups.setdefault(int(v.shape[0]), []).append(b)
@@ -1102,7 +1103,13 @@ class MaxSimRanker:
     `rank(query=, docs=)` scores every doc as  sum_i max_j q_i . d_j  over the query's token vectors
     q_i and the doc's chunklet vectors d_j (GPU: `rl_maxsim_rerank`) and returns them best-first.
     `query_encoder(query: str) -> (nq, dim)` supplies the query's multi-vector representation.
+
+    `ragged`: a batch of queries of several lengths is ONE device call (`rl_maxsim_rerank_ragged`,
+    `rl_search_rerank_ragged`) instead of one per distinct length, and a query of more than 32 vectors is scored on an fp16-stored
+    index instead of raising.  Every query's score bits are those of the call for that query alone.  False: one call per length.
     """
+
+    ragged = True
 
     def __init__(self, index: GpuIndex, query_encoder: Callable[[str], np.ndarray]) -> None:
         self.index = index
@@ -1113,10 +1120,10 @@ class MaxSimRanker:
         self.query_batch_encoder: Callable[..., list | None] | None = None
 
     @classmethod
-    def from_embedder(cls, index: GpuIndex, embedder: Any, *, normalize: bool = True, max_vectors: int = 32) -> "MaxSimRanker":
+    def from_embedder(cls, index: GpuIndex, embedder: Any, *, normalize: bool = True, max_vectors: int | None = 32) -> "MaxSimRanker":
         """Query side from a token-level embedder (`raglite_amd.TorchTokenEmbedder`, or llama.cpp with pooling NONE):
         the query's token embeddings, L2-normalised like the stored chunklet vectors, at most `max_vectors` of them
-        (ColBERT's fixed query length; the first tokens are kept)."""
+        (the first tokens are kept; None: all of them -- nothing is padded, a query keeps its own length)."""
 
         def finish(m: np.ndarray) -> np.ndarray:
             m = m[:max_vectors]
@@ -1151,7 +1158,27 @@ class MaxSimRanker:
         qv = np.asarray(self.query_encoder(query), dtype=np.float32)
         qv = qv.reshape(1, *qv.shape) if qv.ndim == 2 else qv.reshape(1, 1, -1)
         cand = np.asarray(ordinals, dtype=np.int32).reshape(1, -1)
-        return np.asarray(self.index.index.maxsim_rerank(qv, cand))[0]
+        dev = self.index.index
+        if self.ragged and isinstance(dev, _ops.DeviceIndex) and dev.storage == "f16" and qv.shape[1] > 32:
+            return np.asarray(_ragged.maxsim_rerank_ragged(dev, [qv[0]], cand))[0]  # (`maxsim_rerank` stops at 32 vectors there)
+        return np.asarray(dev.maxsim_rerank(qv, cand))[0]
+
+    def _routes(self, vecs: Sequence[np.ndarray]) -> list[tuple[list[int], bool]]:
+        """How a batch is scored: (queries in query order, ragged?) per device call.  Queries of one length, a ranker with `ragged`
+        off and an index that is no `DeviceIndex`: one `maxsim_rerank` shape per distinct length, as ever.  Otherwise ONE ragged call
+        for every query of at most 32 vectors and, on an fp16-stored index, the longer ones too; on an fp32-stored index those keep
+        their per-length calls, whose kernel `score` takes for them as well (their last bits differ from a sum of slabs)."""
+        groups = _groups_by_nq(vecs)
+        dev = self.index.index
+        if not self.ragged or not isinstance(dev, _ops.DeviceIndex):
+            return [(g, False) for g in groups]
+        f16 = dev.storage == "f16"
+        if len(groups) == 1 and not (f16 and int(vecs[groups[0][0]].shape[0]) > 32):
+            return [(groups[0], False)]
+        ragged = [b for b, v in enumerate(vecs) if f16 or int(v.shape[0]) <= 32]
+        taken = set(ragged)
+        rest = [(g, False) for g in groups if g[0] not in taken]
+        return rest + ([(ragged, True)] if ragged else [])
 
     def _token_vectors(self, queries: Sequence[Any], query_token_vectors=None, mats: Sequence[Any] | None = None) -> list[np.ndarray]:
         """Each query's (nq, dim) float32 token vectors: `query_token_vectors[b]` when given; else, for a ranker made by `from_embedder`
@@ -1171,14 +1198,15 @@ class MaxSimRanker:
         return out
 
     def _score_and_order(self, vecs: Sequence[np.ndarray], ordinals: Sequence[Sequence[int]]):
-        """Per query (its candidates' scores in list order, their positions best first): one `rl_maxsim_rerank` and one
-        `rl_rerank_order` per distinct nq.  Short lists are padded with -1; short queries are NOT padded with zero vectors (that
-        could change the summation order and so the score bits)."""
+        """Per query (its candidates' scores in list order, their positions best first): one scoring call and one `rl_rerank_order`
+        per route (`_routes`: one `rl_maxsim_rerank_ragged` for a batch of mixed lengths, one `rl_maxsim_rerank` for a uniform one).
+        Short lists are padded with -1; short queries are NOT padded with zero vectors (that could change the summation order and so
+        the score bits): each keeps its own length."""
         lists = [np.asarray(o, dtype=np.int32).ravel() for o in ordinals]
         if len(lists) != len(vecs):
             raise ValueError("one list of candidates per query is required")
         out: list = [(np.zeros(0, np.float32), np.zeros(0, np.int32)) for _ in lists]
-        for group in _groups_by_nq(vecs):
+        for group, ragged in self._routes(vecs):
             n_cand = max(len(lists[b]) for b in group)
             if n_cand == 0:
                 continue
@@ -1187,19 +1215,23 @@ class MaxSimRanker:
             cand = np.full((len(group), n_cand), -1, dtype=np.int32)
             for i, b in enumerate(group):
                 cand[i, : len(lists[b])] = lists[b]
-            scores = np.asarray(self.index.index.maxsim_rerank(np.stack([vecs[b] for b in group]), cand))
+            if ragged:
+                scores = np.asarray(_ragged.maxsim_rerank_ragged(self.index.index, [vecs[b] for b in group], cand))
+            else:
+                scores = np.asarray(self.index.index.maxsim_rerank(np.stack([vecs[b] for b in group]), cand))
             _, _, pos, counts = _ops.rerank_order(scores, cand, n_cand)
             for i, b in enumerate(group):
                 out[b] = (scores[i, : len(lists[b])], pos[i, : int(counts[i])])
         return out
 
     def score_batch(self, queries: Sequence[str], ordinals: Sequence[Sequence[int]], *, query_token_vectors=None) -> list[np.ndarray]:
-        """`score(queries[b], ordinals[b])` for every b (ragged lists), one `rl_maxsim_rerank` per distinct nq."""
+        """`score(queries[b], ordinals[b])` for every b (ragged lists): one `rl_maxsim_rerank_ragged` for queries of mixed lengths,
+        one `rl_maxsim_rerank` where they all have the same (`_routes`)."""
         return [s for s, _ in self._score_and_order(self._token_vectors(queries, query_token_vectors), ordinals)]
 
     def rank_batch(self, queries: Sequence[str], docs_per_query: Sequence[Sequence[Any]], *, query_token_vectors=None) -> list[RankedResults]:
-        """`rank(query=queries[b], docs=docs_per_query[b])` for every b: the same `RankedResults`, from one `rl_maxsim_rerank` and one
-        `rl_rerank_order` per distinct nq instead of one call and one host sort per query."""
+        """`rank(query=queries[b], docs=docs_per_query[b])` for every b: the same `RankedResults`, from one scoring call and one
+        `rl_rerank_order` for the batch, whatever the queries' lengths (`_routes`), instead of one call and one host sort per query."""
         queries, docs_per_query = list(queries), [list(d) for d in docs_per_query]
         if len(queries) != len(docs_per_query):
             raise ValueError("one list of docs per query is required")
@@ -1311,8 +1343,8 @@ def rerank_chunks_batch(queries: Sequence[str], chunk_ids_per_query: Sequence[Se
                         index: GpuIndex | None = None, query_token_vectors=None) -> list[tuple[list[ChunkId], list[float]]]:
     """MaxSim-rerank a batch of (ragged) chunk id lists: element b is (ids best first, their MaxSim scores), the order
     `config.reranker.rank(queries[b], <those chunks' docs>)` gives.  `config.reranker` must be a `MaxSimRanker` over `index`; one
-    `rl_maxsim_rerank` and one `rl_rerank_order` per distinct query length.  `query_token_vectors`: one (nq, dim) matrix per query,
-    skips the ranker's query encoder."""
+    scoring call and one `rl_rerank_order` for the batch: `rl_maxsim_rerank_ragged` where the queries' lengths differ
+    (`MaxSimRanker._routes`).  `query_token_vectors`: one (nq, dim) matrix per query, of any lengths, skips the ranker's query encoder."""
     gi = index or _index_for(config)
     ranker = _device_ranker(config, gi)
     if ranker is None:
@@ -1337,9 +1369,11 @@ def search_and_rerank_chunks_batch(queries: Sequence[str], *, num_results: int =
     chunk ids, or as `chunk_lookup(ids)` per query when a lookup is given.  `search`: "hybrid" or "vector" (or those two functions).
 
     With `config.reranker` a `MaxSimRanker` over the searched index, the searches, the RRF fusion, the MaxSim scoring of every query's
-    `oversample * num_results` candidates and their ordering run on one stream in one device call per distinct query length
-    (`rl_search_rerank_per_query`), nothing is read back in between, and the best `num_results` are read back once.  Query token
-    vectors come from the ranker's `query_encoder`, one query at a time, or from `query_token_vectors` (one (nq, dim) matrix per query).
+    `oversample * num_results` candidates and their ordering run on one stream in one device call -- `rl_search_rerank_per_query`
+    where every query has the same number of token vectors, `rl_search_rerank_ragged` where they differ (`MaxSimRanker._routes`;
+    with `ranker.ragged` off, one call per distinct length) -- nothing is read back in between, and the best `num_results` are read
+    back once.  Query token vectors come from the ranker's `query_encoder`, one query at a time, or from `query_token_vectors` (one
+    (nq, dim) matrix per query, of any lengths).
     Without a reranker the batched search's results are returned truncated.  Any other reranker (a dict by language, a cross-encoder)
     is outside the device path: the batched search runs, then `rerank_chunks` per query.  `metadata_filter` and `query_vectors` as in
     `hybrid_search_batch`.  Raises where the loop would raise for some element, with its message."""
@@ -1389,6 +1423,17 @@ def _ids_of(gi: GpuIndex, out: list, group: Sequence[int], chunks, counts) -> No
         out[b] = [gi.chunk_ids[c] for c in chunks[i, : int(counts[i])].tolist()]
 
 
+def _rerank_calls(device_index: Any, ragged: bool):
+    """(search_rerank, search_rerank_spans, maxsim_rerank) of a route: the index's own calls, which take a (B, nq, dim) block, or the
+    ragged ones, which take a list of (nq_b, dim) matrices (looked up when called: `_ragged`'s functions stay replaceable)."""
+    if not ragged:
+        return (lambda *a, **kw: device_index.search_rerank(*a, **kw), lambda *a, **kw: device_index.search_rerank_spans(*a, **kw),
+                lambda *a, **kw: device_index.maxsim_rerank(*a, **kw))
+    return (lambda *a, **kw: _ragged.search_rerank_ragged(device_index, *a, **kw),
+            lambda *a, **kw: _ragged.search_rerank_spans_ragged(device_index, *a, **kw),
+            lambda *a, **kw: _ragged.maxsim_rerank_ragged(device_index, *a, **kw))
+
+
 def _hybrid_rerank_device(gi, cfg, ranker, queries, num_results, n_cand, metadata_filter, query_vectors, query_token_vectors,
                           spans: "_SpanRequest | None" = None) -> list:
     """The device path of search_and_rerank_chunks_batch over hybrid_search: its host decisions are hybrid_search_batch's.  With
@@ -1401,24 +1446,25 @@ def _hybrid_rerank_device(gi, cfg, ranker, queries, num_results, n_cand, metadat
         return out
     k = min(num_results, hp.k)
     vecs = ranker._token_vectors(queries, query_token_vectors, mats)  # noqa: SLF001
-    for group in _groups_by_nq(vecs):
+    for group, ragged in ranker._routes(vecs):  # noqa: SLF001
         qf, lim = _device_filters(hp.plan, group)
-        V = np.stack([vecs[b] for b in group])
+        V = [vecs[b] for b in group] if ragged else np.stack([vecs[b] for b in group])
+        pipeline, pipeline_spans, rerank = _rerank_calls(gi.index, ragged)
         terms = None if hp.term_ids is None else [hp.term_ids[b] for b in group]
         if hp.vector and spans is not None:
-            res = gi.index.search_rerank_spans(hp.Q[group], hp.num_hits, hp.n_each, hp.k, V, k, spans.table, spans.neighbors,
-                                               keyword=gi.keyword if hp.keyword else None, query_term_ids=terms, weights=(0.75, 0.25),
-                                               rrf_k=RRF_K, query_filters=qf, rank_limit=lim)
+            res = pipeline_spans(hp.Q[group], hp.num_hits, hp.n_each, hp.k, V, k, spans.table, spans.neighbors,
+                                 keyword=gi.keyword if hp.keyword else None, query_term_ids=terms, weights=(0.75, 0.25),
+                                 rrf_k=RRF_K, query_filters=qf, rank_limit=lim)
             _spans_of(gi, out, group, *res[2:6])
             continue
         if hp.vector:
-            _, chunks, counts = gi.index.search_rerank(hp.Q[group], hp.num_hits, hp.n_each, hp.k, V, k, keyword=gi.keyword if hp.keyword else None,
-                                                       query_term_ids=terms, weights=(0.75, 0.25), rrf_k=RRF_K, query_filters=qf,
-                                                       rank_limit=lim)
+            _, chunks, counts = pipeline(hp.Q[group], hp.num_hits, hp.n_each, hp.k, V, k, keyword=gi.keyword if hp.keyword else None,
+                                         query_term_ids=terms, weights=(0.75, 0.25), rrf_k=RRF_K, query_filters=qf,
+                                         rank_limit=lim)
         else:  # no vector results for any query: the keyword list alone, fused, scored and ordered by separate calls
             _, kw_chunks, _ = gi.keyword.search(terms, hp.n_each, query_filters=qf)
             _, fused, _ = _ops.rrf_fuse(kw_chunks[None], [0.25], rrf_k=RRF_K, k=hp.k)
-            _, chunks, _, counts = _ops.rerank_order(gi.index.maxsim_rerank(V, fused), fused, k)
+            _, chunks, _, counts = _ops.rerank_order(rerank(V, fused), fused, k)
         if spans is not None:  # (the ordered list is padded with -1 past its count)
             _spans_of(gi, out, group, *spans.table.chunk_spans(chunks, spans.neighbors)[:4])
         else:
@@ -1441,16 +1487,18 @@ def _vector_rerank_device(gi, cfg, ranker, queries, num_results, n_cand, metadat
     vecs = ranker._token_vectors([queries[b] for b in active],  # noqa: SLF001
                                  None if query_token_vectors is None else [query_token_vectors[b] for b in active],
                                  None if mats is None else [mats[b] for b in active])
-    for group in _groups_by_nq(vecs):
+    for group, ragged in ranker._routes(vecs):  # noqa: SLF001
         members = [active[i] for i in group]
         qf, lim = _device_filters(plan, members)
+        V = [vecs[i] for i in group] if ragged else np.stack([vecs[i] for i in group])
+        pipeline, pipeline_spans, _ = _rerank_calls(gi.index, ragged)
         if spans is not None:
-            res = gi.index.search_rerank_spans(Q[members], num_hits, n_cand, n_cand, np.stack([vecs[i] for i in group]), k, spans.table,
-                                               spans.neighbors, weights=(1.0,), rrf_k=RRF_K, query_filters=qf, rank_limit=lim)
+            res = pipeline_spans(Q[members], num_hits, n_cand, n_cand, V, k, spans.table, spans.neighbors, weights=(1.0,), rrf_k=RRF_K,
+                                 query_filters=qf, rank_limit=lim)
             _spans_of(gi, out, members, *res[2:6])
             continue
-        _, chunks, counts = gi.index.search_rerank(Q[members], num_hits, n_cand, n_cand, np.stack([vecs[i] for i in group]), k, weights=(1.0,),
-                                                   rrf_k=RRF_K, query_filters=qf, rank_limit=lim)
+        _, chunks, counts = pipeline(Q[members], num_hits, n_cand, n_cand, V, k, weights=(1.0,), rrf_k=RRF_K, query_filters=qf,
+                                     rank_limit=lim)
         _ids_of(gi, out, members, chunks, counts)
     return out
 
@@ -1560,11 +1608,11 @@ def search_and_rerank_chunk_spans_batch(queries: Sequence[str], *, num_results: 
                                         metadata_filter=None, index: GpuIndex | None = None, query_vectors=None,
                                         query_token_vectors=None) -> list[list[ChunkSpan]]:
     """`search_and_rerank_chunk_spans` for a batch: element b is what `search_and_rerank_chunk_spans(queries[b], search=hybrid_search |
-    vector_search, metadata_filter=<its filter>, ...)` returns with the same arguments.  The planning, the grouping by query length,
+    vector_search, metadata_filter=<its filter>, ...)` returns with the same arguments.  The planning, the routes by query length,
     the filters and the fallbacks are `search_and_rerank_chunks_batch`'s.  With `config.reranker` a `MaxSimRanker` over the searched
-    index, everything from the searches to the ordered spans runs on one stream in one device call per distinct query length
-    (`rl_search_rerank_spans_per_query`) and is read back once.  Otherwise the batched search runs, then the rerank path of
-    `search_and_rerank_chunks_batch`, then one `rl_chunk_spans` for the batch."""
+    index, everything from the searches to the ordered spans runs on one stream in one device call (`rl_search_rerank_spans_per_query`
+    for queries of one length, `rl_search_rerank_spans_ragged` for mixed lengths) and is read back once.  Otherwise the batched search
+    runs, then the rerank path of `search_and_rerank_chunks_batch`, then one `rl_chunk_spans` for the batch."""
     cfg = config or HotPathConfig()
     gi = index or _index_for(config)
     queries = list(queries)

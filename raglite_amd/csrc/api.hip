@@ -2470,9 +2470,78 @@ int maxsim_rerank_device(rl_index* idx, const float* d_q, int32_t n_queries, int
         st = launch_maxsim_generic(rows(idx), q, chunks(idx), d_c, n_cand, d_o, s);
     return st;
 }
+
+// A table of vectors per query, read on the host: from 0, strictly ascending (every query has a vector)
+int check_qv_off(const int64_t* qv_off, int32_t n_queries, const char* who) {
+    if (qv_off[0] != 0) return fail(RL_ERR_INVALID, std::string(who) + ": qv_off[0] must be 0");
+    for (int32_t b = 0; b < n_queries; ++b)
+        if (qv_off[b + 1] <= qv_off[b])
+            return fail(RL_ERR_INVALID, std::string(who) + ": query " + std::to_string(b) + " has no vectors (qv_off must ascend strictly)");
+    return RL_OK;
+}
+
+// The device half of rl_maxsim_rerank_ragged on device pointers (under idx->mu, after use_scratch): d_q [qv_off[n_queries] x dim], the
+// table on the host (the routes and the backstop's loop read it) and on the device (the kernel reads it), d_c / d_o [n_queries x n_cand].
+// One launch of maxsim_ragged_kernel where it takes the shape.  Elsewhere -- dim 128, whose kernel in rl_maxsim_rerank may follow the
+// index's arithmetic mode; the wide dims; any other dim of an fp32-stored index -- the backstop, which keeps the contract by
+// construction: maxsim_rerank_device per (query, slab of 32) into a scratch row, added to the result in slab order.  Correct and
+// unhurried: two to four launches per (query, slab).
+int maxsim_rerank_ragged_device(rl_index* idx, const float* d_q, const int64_t* h_qv_off, const int64_t* d_qv_off, int32_t n_queries,
+                                const int32_t* d_c, int32_t n_cand, float* d_o, hipStream_t s, const char* who) {
+    const int32_t dim = idx->dim;
+    if (idx->E16 && dim % 16)
+        return fail(RL_ERR_UNSUPPORTED, std::string(who) + ": MaxSim reranking on an fp16-stored index needs dim % 16 == 0");
+    if (dim != 128 && dim % 16 == 0 && dim <= 1024) {
+        const int64_t n_items = (int64_t)n_queries * n_cand;  // (ordinals that cannot be scored -> -inf, as in maxsim_rerank_device)
+        RL_TRY(idx->cand.reserve((size_t)n_items * sizeof(int32_t)));
+        RL_TRY(launch_sanitize_candidates(d_c, n_items, idx->n_chunks, idx->live_chunk_bits, idx->cand.as<int32_t>(), s));
+        const int st = launch_maxsim_ragged(rows(idx), d_q, d_qv_off, n_queries, chunks(idx), idx->cand.as<int32_t>(), n_cand, d_o, s);
+        if (st != RL_ERR_UNSUPPORTED) return st;  // (misaligned rows or vectors, more queries than a grid takes: the backstop)
+    }
+    RaggedScratch L;
+    RL_TRY(carve(idx->ragged, L, (size_t)n_cand));
+    for (int32_t b = 0; b < n_queries; ++b)
+        for (int64_t v0 = h_qv_off[b]; v0 < h_qv_off[b + 1]; v0 += 32) {
+            const int32_t nq = (int32_t)std::min<int64_t>(32, h_qv_off[b + 1] - v0);
+            RL_TRY(maxsim_rerank_device(idx, d_q + v0 * dim, 1, nq, d_c + (int64_t)b * n_cand, n_cand, L.slab, s));
+            RL_TRY(launch_slab_accumulate(d_o + (int64_t)b * n_cand, L.slab, n_cand, v0 != h_qv_off[b], s));
+        }
+    return RL_OK;
+}
 }  // namespace rl
 
 extern "C" {
+
+int rl_maxsim_rerank_ragged(rl_index* idx, const float* query_vecs, const int64_t* qv_off, int32_t n_queries, const int32_t* candidates,
+                            int32_t n_cand, float* out_scores, int mem, void* stream) {
+    const char* who = "rl_maxsim_rerank_ragged";
+    if (n_queries < 0 || n_cand < 0) return fail(RL_ERR_INVALID, std::string(who) + ": bad sizes");
+    RL_TRY(check_mem(mem, who));
+    if (n_queries == 0) return RL_OK;
+    if (!qv_off) return fail(RL_ERR_INVALID, std::string(who) + ": null qv_off");
+    RL_TRY(check_qv_off(qv_off, n_queries, who));
+    if (!idx) return fail(RL_ERR_INVALID, std::string(who) + ": null index");
+    if (n_cand == 0) return RL_OK;
+    if (!query_vecs || !candidates || !out_scores) return fail(RL_ERR_INVALID, std::string(who) + ": null argument");
+    if (idx->E16 && idx->dim % 16)
+        return fail(RL_ERR_UNSUPPORTED, std::string(who) + ": MaxSim reranking on an fp16-stored index needs dim % 16 == 0");
+    if (mem == RL_MEM_HOST) {  // -1 = "no chunk" (the padding of rl_search_chunks results) is allowed and scores -inf
+        for (int64_t i = 0; i < (int64_t)n_queries * n_cand; ++i)
+            if (candidates[i] < -1 || candidates[i] >= idx->n_chunks)
+                return fail(RL_ERR_INVALID, std::string(who) + ": candidate chunk ordinal out of range");
+    }
+    hipStream_t s = as_stream(stream);
+    std::lock_guard<std::mutex> lock(idx->mu);
+    RL_TRY(use_scratch(idx, s));
+    Staging st(mem, s);
+    const float* d_q; const int64_t* d_off; const int32_t* d_c; float* d_o;
+    RL_TRY(st.in(query_vecs, (size_t)qv_off[n_queries] * idx->dim, &d_q));
+    RL_TRY(st.in(qv_off, (size_t)n_queries + 1, &d_off, RL_MEM_HOST));
+    RL_TRY(st.in(candidates, (size_t)n_queries * n_cand, &d_c));
+    RL_TRY(st.out(out_scores, (size_t)n_queries * n_cand, &d_o));
+    RL_TRY(maxsim_rerank_ragged_device(idx, d_q, qv_off, d_off, n_queries, d_c, n_cand, d_o, s, who));
+    return st.finish();
+}
 
 int rl_maxsim_rerank(rl_index* idx, const float* query_vecs, int32_t n_queries, int32_t nq, const int32_t* candidates,
                      int32_t n_cand, float* out_scores, int mem, void* stream) {

@@ -251,8 +251,33 @@ namespace {
 struct RerankCall {
     HybridCall c;
     const float* d_v = nullptr;
+    const int64_t *qv_off = nullptr, *d_qv_off = nullptr;  // the ragged entries: each query's vectors, on the host and staged
     RerankCall(int mem, hipStream_t s) : c(mem, s) {}
 };
+
+// ... of the ragged entries (qv_off [B + 1], host memory, in place of nq): the same checks with the table's in front of the first HIP
+// call, no limit on a query's vectors, the table staged behind the vectors
+int search_rerank_ragged_begin(rl_index* idx, rl_keyword_index* kw, const float* queries, int32_t B, int32_t num_hits, int32_t n_each,
+                               const int64_t* q_off, const int32_t* q_terms, const uint32_t* chunk_filters, int32_t n_filters,
+                               const int32_t* query_filter, const int64_t* rank_limits, const double* weights, int32_t rrf_k, int32_t n_cand,
+                               const float* query_vecs, const int64_t* qv_off, int32_t k, bool outputs, int mem, hipStream_t s, const char* who,
+                               RerankCall* rc) {
+    if (B < 0) return fail(RL_ERR_INVALID, std::string(who) + ": n_queries must be >= 0");
+    if (n_cand < 1 || n_cand > RERANK_MAX_ENTRIES) return fail(RL_ERR_INVALID, std::string(who) + ": n_cand must be in [1, 4096]");
+    if (k < 1 || k > n_cand) return fail(RL_ERR_INVALID, std::string(who) + ": k must be in [1, n_cand]");
+    RL_TRY(check_query_filters(B, chunk_filters, n_filters, query_filter, rank_limits, who));
+    RL_TRY(check_mem(args_mem(mem), who));
+    if (B == 0) { rc->c.empty = true; return RL_OK; }
+    if (!qv_off) return fail(RL_ERR_INVALID, std::string(who) + ": null qv_off");
+    RL_TRY(check_qv_off(qv_off, B, who));
+    if (idx && idx->E16 && idx->dim % 16)
+        return fail(RL_ERR_UNSUPPORTED, std::string(who) + ": MaxSim reranking on an fp16-stored index needs dim % 16 == 0");
+    RL_TRY(hybrid_search_begin(idx, kw, queries, B, num_hits, n_each, q_off, q_terms, chunk_filters, query_filter ? n_filters : 0, query_filter,
+                               rank_limits, 0, weights, rrf_k, n_cand, query_vecs && outputs, mem, s, who, &rc->c));
+    rc->qv_off = qv_off;
+    RL_TRY(rc->c.st.in(query_vecs, (size_t)qv_off[B] * idx->dim, &rc->d_v));
+    return rc->c.st.in(qv_off, (size_t)B + 1, &rc->d_qv_off, RL_MEM_HOST);
+}
 
 // The checks of rl_search_rerank_per_query, the locks and the staging-in
 int search_rerank_begin(rl_index* idx, rl_keyword_index* kw, const float* queries, int32_t B, int32_t num_hits, int32_t n_each,
@@ -275,7 +300,7 @@ int search_rerank_begin(rl_index* idx, rl_keyword_index* kw, const float* querie
 // d_s [B x k], or nullptr: the scores stay in the index's scratch
 int search_rerank_device(rl_index* idx, rl_keyword_index* kw, const RerankCall& rc, int32_t B, int32_t num_hits, int32_t n_each,
                          const double* weights, int32_t rrf_k, int32_t n_cand, int32_t nq, int32_t k, float* d_s, int32_t* d_c, int32_t* d_n,
-                         hipStream_t s) {
+                         hipStream_t s, const char* who = "" /* the ragged entries: their name, for the rerank's errors */) {
     // index-owned scratch: the fused scores [B x n_cand] f64 (written, not read), the fused candidates [B x n_cand] int32, their
     // MaxSim scores [B x n_cand] f32, the fusion's counts [B] and the positions of the first k [B x k] int32 (written, not read);
     // without d_s the scores of the first k [B x k] f32 (written, not read)
@@ -283,7 +308,8 @@ int search_rerank_device(rl_index* idx, rl_keyword_index* kw, const RerankCall& 
     RL_TRY(carve(idx->rerank, L, B, n_cand, k, !d_s));
     if (!d_s) d_s = L.own_scores;
     RL_TRY(hybrid_search_device(idx, kw, rc.c, B, num_hits, n_each, weights, rrf_k, n_cand, L.fused_scores, L.fused, L.fused_counts, s));
-    RL_TRY(maxsim_rerank_device(idx, rc.d_v, B, nq, L.fused, n_cand, L.maxsim, s));
+    if (rc.qv_off) RL_TRY(maxsim_rerank_ragged_device(idx, rc.d_v, rc.qv_off, rc.d_qv_off, B, L.fused, n_cand, L.maxsim, s, who));
+    else RL_TRY(maxsim_rerank_device(idx, rc.d_v, B, nq, L.fused, n_cand, L.maxsim, s));
     return launch_rerank_order(L.maxsim, L.fused, B, n_cand, k, d_s, d_c, L.pos, d_n, s);
 }
 
@@ -344,6 +370,29 @@ int rl_search_rerank_per_query(rl_index* idx, rl_keyword_index* kw, const float*
     RL_TRY(st.out(out_chunks, n_out, &d_c));
     RL_TRY(st.out(out_counts, (size_t)B, &d_n));
     RL_TRY(search_rerank_device(idx, kw, rc, B, num_hits, n_each, weights, rrf_k, n_cand, nq, k, d_s, d_c, d_n, s));
+    return st.finish();
+}
+
+int rl_search_rerank_ragged(rl_index* idx, rl_keyword_index* kw, const float* queries, int32_t n_queries, int32_t num_hits, int32_t n_each,
+                            const int64_t* q_off, const int32_t* q_terms, const uint32_t* chunk_filters, int32_t n_filters,
+                            const int32_t* query_filter, const int64_t* rank_limits, const double* weights, int32_t rrf_k, int32_t n_cand,
+                            const float* query_vecs, const int64_t* qv_off, int32_t k, float* out_scores, int32_t* out_chunks,
+                            int32_t* out_counts, int mem, void* stream) {
+    const char* who = "rl_search_rerank_ragged";
+    const int32_t B = n_queries;
+    hipStream_t s = as_stream(stream);
+    RerankCall rc(mem, s);
+    RL_TRY(search_rerank_ragged_begin(idx, kw, queries, B, num_hits, n_each, q_off, q_terms, chunk_filters, n_filters, query_filter, rank_limits,
+                                      weights, rrf_k, n_cand, query_vecs, qv_off, k, out_scores && out_chunks && out_counts, mem, s, who, &rc));
+    if (rc.c.empty) return RL_OK;
+    Staging& st = rc.c.st;
+    const size_t n_out = (size_t)B * k;
+    float* d_s;
+    int32_t *d_c, *d_n;
+    RL_TRY(st.out(out_scores, n_out, &d_s));
+    RL_TRY(st.out(out_chunks, n_out, &d_c));
+    RL_TRY(st.out(out_counts, (size_t)B, &d_n));
+    RL_TRY(search_rerank_device(idx, kw, rc, B, num_hits, n_each, weights, rrf_k, n_cand, 0, k, d_s, d_c, d_n, s, who));
     return st.finish();
 }
 
@@ -444,6 +493,36 @@ int rl_search_rerank_spans_per_query(rl_index* idx, rl_keyword_index* kw, const 
     RL_TRY(st.out(out_top_counts, (size_t)B, &d_n));
     RL_TRY(span_outputs(st, out_chunks, out_span_len, out_span_scores, out_n_spans, out_n_chunks, n_out, (size_t)B, &o));
     RL_TRY(search_rerank_device(idx, kw, rc, B, num_hits, n_each, weights, rrf_k, n_cand, nq, k, nullptr, d_c, d_n, s));
+    RL_TRY(spans_device(table, d_c, B, k, offsets, n_off, o, s));
+    return st.finish();
+}
+
+int rl_search_rerank_spans_ragged(rl_index* idx, rl_keyword_index* kw, const float* queries, int32_t n_queries, int32_t num_hits,
+                                  int32_t n_each, const int64_t* q_off, const int32_t* q_terms, const uint32_t* chunk_filters,
+                                  int32_t n_filters, const int32_t* query_filter, const int64_t* rank_limits, const double* weights,
+                                  int32_t rrf_k, int32_t n_cand, const float* query_vecs, const int64_t* qv_off, int32_t k,
+                                  const rl_span_table* table, const int32_t* offsets, int32_t n_off, int32_t* out_top_chunks,
+                                  int32_t* out_top_counts, int32_t* out_chunks, int32_t* out_span_len, double* out_span_scores,
+                                  int32_t* out_n_spans, int32_t* out_n_chunks, int mem, void* stream) {
+    const char* who = "rl_search_rerank_spans_ragged";
+    const int32_t B = n_queries;
+    RL_TRY(check_span_args(table, B, k, offsets, n_off, args_mem(mem), who));  // (k * (1 + n_off) <= 4096)
+    if (idx && table->n_chunks != idx->n_chunks) return fail(RL_ERR_INVALID, std::string(who) + ": the span table covers another number of chunks");
+    hipStream_t s = as_stream(stream);
+    RerankCall rc(mem, s);
+    RL_TRY(search_rerank_ragged_begin(idx, kw, queries, B, num_hits, n_each, q_off, q_terms, chunk_filters, n_filters, query_filter, rank_limits,
+                                      weights, rrf_k, n_cand, query_vecs, qv_off, k,
+                                      out_top_chunks && out_top_counts && out_chunks && out_span_len && out_span_scores && out_n_spans && out_n_chunks,
+                                      mem, s, who, &rc));
+    if (rc.c.empty) return RL_OK;
+    Staging& st = rc.c.st;
+    const size_t n_top = (size_t)B * k, n_out = n_top * (1 + n_off);
+    int32_t *d_c, *d_n;
+    SpanPtrs o;
+    RL_TRY(st.out(out_top_chunks, n_top, &d_c));
+    RL_TRY(st.out(out_top_counts, (size_t)B, &d_n));
+    RL_TRY(span_outputs(st, out_chunks, out_span_len, out_span_scores, out_n_spans, out_n_chunks, n_out, (size_t)B, &o));
+    RL_TRY(search_rerank_device(idx, kw, rc, B, num_hits, n_each, weights, rrf_k, n_cand, 0, k, nullptr, d_c, d_n, s, who));
     RL_TRY(spans_device(table, d_c, B, k, offsets, n_off, o, s));
     return st.finish();
 }

@@ -658,5 +658,11 @@ int launch_sanitize_candidates(const int32_t* in, int64_t n, int64_t n_chunks, c
 // Rerank fast path: dim == 128, nq <= 32 (MFMA, direct fragment loads), fp32 or fp16 rows.
 int launch_maxsim_cand(const RowsRef& D, const QueryVecs& q, const ChunkMap& c, const int32_t* candidates, int32_t n_cand, float* out,
                        hipStream_t s);
+// maxsim_ragged.hip: the rerank where query b owns the vectors Q[qv_off[b] .. qv_off[b + 1]) (d_qv_off: device [n_queries + 1]), any number
+// of them, walked in slabs of 32: dim % 16 == 0 up to 1024, fp32 or fp16 rows; candidates / out [n_queries x n_cand].  RL_ERR_UNSUPPORTED elsewhere.
+int launch_maxsim_ragged(const RowsRef& D, const float* Q, const int64_t* d_qv_off, int32_t n_queries, const ChunkMap& c,
+                         const int32_t* candidates, int32_t n_cand, float* out, hipStream_t s);
+// out[i] = slab[i] (add false) or out[i] + slab[i]: how the ragged rerank's backstop sums a query's slabs, in slab order
+int launch_slab_accumulate(float* out, const float* slab, int64_t n, bool add, hipStream_t s);
 
 }  // namespace rl

@@ -150,6 +150,7 @@ struct rl_index {
     rl::Pool rankbuf;                     // rank cut (order-first-then-filter): histogram levels + tie counts
     rl::Pool hybrid;                      // rl_hybrid_search: the ranked lists the fusion reads, their scores and counts
     rl::Pool rerank;                      // rl_search_rerank_per_query: the fused candidates, their fused and MaxSim scores, positions
+    rl::Pool ragged;                      // rl_maxsim_rerank_ragged's backstop: one (query, slab)'s scores
     // HI plane (round 2): fp16(e * split_scale) rounded to nearest (toward zero until round 3), row-major [n_rows x dim] -- the hi halves of the fp16
     // split as a matrix of their own, 2 B per element: what the single-query search streams (search_rows_hi).
     rl::Image hiplane;
@@ -237,6 +238,11 @@ int search_chunks_device(rl_index* idx, const float* d_q, int32_t B, int32_t num
                          float* d_s, int32_t* d_c, int32_t* d_n, hipStream_t s);
 int maxsim_rerank_device(rl_index* idx, const float* d_q, int32_t n_queries, int32_t nq, const int32_t* d_c, int32_t n_cand, float* d_o,
                          hipStream_t s);
+// ... with a number of vectors per query: check_qv_off takes no lock and makes no HIP call (qv_off: HOST memory); the device half takes
+// the table on both sides
+int check_qv_off(const int64_t* qv_off, int32_t n_queries, const char* who);
+int maxsim_rerank_ragged_device(rl_index* idx, const float* d_q, const int64_t* h_qv_off, const int64_t* d_qv_off, int32_t n_queries,
+                                const int32_t* d_c, int32_t n_cand, float* d_o, hipStream_t s, const char* who);
 
 // api_keyword.hip, for the hybrid and rerank calls: check_host_q_off takes no lock; keyword_use_stream, then the other two, under kw->mu
 int keyword_use_stream(rl_keyword_index* kw, hipStream_t s);

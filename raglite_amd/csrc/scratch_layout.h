@@ -194,6 +194,14 @@ struct RerankScratch {  // search_rerank_device, pool `rerank`
     }
 };
 
+struct RaggedScratch {  // maxsim_rerank_ragged_device, pool `ragged`
+    float* slab;  // [n_cand] the backstop's scores of one (query, slab), summed into the result before the next one overwrites them
+    size_t lay(Carver c, size_t n_cand) {
+        slab = c.take<float>(n_cand);
+        return c.off;
+    }
+};
+
 // ---- native encoder forward (api_ingest.hip, encoder.hip) -------------------------------------------------------------------------------
 struct EncoderScratch {  // rl_encoder_forward, the handle's one block: reserved for RL_ENCODER_MAX_TOKENS rows, walked per call with the
                          // call's own `rows`, so that a call writes a prefix of the block and nothing behind it.  rl_encoder_forward_pack

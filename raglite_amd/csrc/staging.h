@@ -129,7 +129,7 @@ struct DevBuf {
 // keyed by their address, so the frame does not move).
 class Staging {
 public:
-    static constexpr int MAX_BUFFERS = 16;  // the largest caller, rl_search_rerank_spans_per_query, takes 12
+    static constexpr int MAX_BUFFERS = 16;  // the largest caller, rl_search_rerank_spans_ragged, takes 13
     Staging(int mem, hipStream_t s) : mem_(mem), s_(s) {}
     Staging(const Staging&) = delete;
     Staging& operator=(const Staging&) = delete;
