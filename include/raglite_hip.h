@@ -224,6 +224,42 @@ int rl_encoder_forward_pack(rl_encoder* enc, const int32_t* ids, const int32_t* 
 int rl_encoder_linear_pack(const void* x, int64_t M, int32_t K, const void* W, int32_t N, const void* bias, int32_t epilogue, int32_t dtype,
                            void* out16, float* part, int mem, void* stream);
 
+/* ---- the cross-encoder's head on the native forward (reranking) ----------------------------------------------------
+ * A BERT sequence classifier is the encoder above plus, on the FIRST token's row x of every sequence,
+ *     p = tanh(pooler_w x + pooler_b);   logit = head_w . p + head_b
+ * pooler_w [hidden x hidden] as nn.Linear keeps it, pooler_b [hidden], head_w [hidden] (the [1 x hidden] matrix), head_b [1], all in the
+ * 16-bit dtype.  Everything after the 16-bit loads is f32 and the logit is stored as f32: nothing is rounded to 16 bits on the way.  One
+ * workgroup per sequence, a fixed reduction tree that depends on `hidden` alone, no atomics: a sequence's logit bits depend neither on
+ * n_seqs, nor on its index, nor on where its row lies.  The row index seq_offsets[s] is clamped into [0, n_tokens - 1] (a bad offset
+ * gives a wrong number, never a read outside x); an empty sequence (seq_offsets[s] == seq_offsets[s + 1]) gives a quiet NaN.
+ *
+ * rl_encoder_head: the launch on its own, on the caller's buffers (no handle, no scratch, nothing allocated): x [n_tokens x hidden] in
+ *   `dtype`, seq_offsets int32[n_seqs + 1], out_logits f32[n_seqs], all on the device.  Checked before any HIP call: mem !=
+ *   RL_MEM_DEVICE (RL_ERR_UNSUPPORTED); n_seqs outside [0, 65535], n_tokens outside [0, 2^31), hidden not a positive multiple of 32
+ *   (RL_ERR_INVALID); hidden > 8192 (RL_ERR_UNSUPPORTED); an unknown dtype; then, with n_seqs > 0: n_tokens == 0, a null pointer, x or a
+ *   parameter not 16-byte aligned, seq_offsets or out_logits not 4-byte aligned (RL_ERR_INVALID).  n_seqs == 0 returns RL_OK and writes
+ *   nothing.
+ * rl_encoder_set_head: gives the handle its head; the four pointers are BORROWED like rl_encoder_create's, in the handle's dtype, 16-byte
+ *   aligned.  All four NULL clears the head.  RL_ERR_INVALID for some but not all NULL, a misaligned pointer, a null handle (looked at
+ *   last).  Not to be called while a call on the handle is running.
+ * rl_encoder_classify_workspace_bytes: host only; *bytes = the workspace rl_encoder_classify_pack needs for n_tokens rows and n_seqs
+ *   sequences: rl_encoder_pack_workspace_bytes(n_tokens) plus the final hidden states [n_tokens x hidden], from one walk of one layout;
+ *   monotone in both arguments (the logits are the caller's, so n_seqs adds nothing today).  RL_ERR_INVALID for n_tokens outside
+ *   [0, RL_ENCODER_MAX_PACK_TOKENS], n_seqs outside [0, 65535], a null `bytes`, a null handle (looked at last).
+ * rl_encoder_classify_pack: rl_encoder_forward_pack's arguments, checks and order, with out_logits f32[n_seqs] (4-byte aligned) in the
+ *   place of `out`: the trunk's 1 + 7 * layers launches, exactly rl_encoder_forward_pack's, write the final rows into the workspace, and
+ *   one launch of the head reads them: 2 + 7 * layers launches on `stream`, no allocation, no synchronisation; nothing behind
+ *   workspace_bytes >= rl_encoder_classify_workspace_bytes(n_tokens, n_seqs) or behind out_logits[n_seqs] is written.  After the
+ *   shared checks: a null or misaligned workspace (n_tokens > 0), a null handle, a handle without a head, a workspace that is too small
+ *   (RL_ERR_INVALID).  n_tokens == 0 returns RL_OK and writes nothing. */
+int rl_encoder_head(const void* x, const int32_t* seq_offsets, int32_t n_seqs, int64_t n_tokens, int32_t hidden, const void* pooler_w,
+                    const void* pooler_b, const void* head_w, const void* head_b, int32_t dtype, float* out_logits, int mem, void* stream);
+int rl_encoder_set_head(rl_encoder* enc, const void* pooler_w, const void* pooler_b, const void* head_w, const void* head_b);
+int rl_encoder_classify_workspace_bytes(const rl_encoder* enc, int64_t n_tokens, int32_t n_seqs, int64_t* bytes);
+int rl_encoder_classify_pack(rl_encoder* enc, const int32_t* ids, const int32_t* positions, const int32_t* type_ids,
+                             const int32_t* seq_offsets, int32_t n_seqs, int64_t n_tokens, int32_t max_len, float* out_logits,
+                             void* workspace, int64_t workspace_bytes, int mem, void* stream);
+
 /* ---- a5: query adapter -----------------------------------------------------------------------
  * Replaces src/raglite/_search.py:62  `(Q @ q).astype(q.dtype)`; out[b] = A @ q[b].
  *   A [dim x dim] f32, queries [B x dim] f32, out_f32 [B x dim] or NULL, out_f16 or NULL. */

@@ -78,6 +78,11 @@ _SIGNATURES = {
     "rl_encoder_forward_pack": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_i32, c_i64, c_i32, c_void_p, c_void_p, c_i64, c_int,
                                 c_void_p],
     "rl_encoder_linear_pack": [c_void_p, c_i64, c_i32, c_void_p, c_i32, c_void_p, c_i32, c_i32, c_void_p, c_void_p, c_int, c_void_p],
+    "rl_encoder_head": [c_void_p, c_void_p, c_i32, c_i64, c_i32, c_void_p, c_void_p, c_void_p, c_void_p, c_i32, c_void_p, c_int, c_void_p],
+    "rl_encoder_set_head": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
+    "rl_encoder_classify_workspace_bytes": [c_void_p, c_i64, c_i32, C.POINTER(c_i64)],
+    "rl_encoder_classify_pack": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_i32, c_i64, c_i32, c_void_p, c_void_p, c_i64, c_int,
+                                 c_void_p],
     "rl_adapter_apply": [c_void_p, c_void_p, c_i32, c_i32, c_void_p, c_void_p, c_int, c_void_p],
     "rl_adapter_apply_rows": [c_void_p, c_void_p, c_i32, c_i32, c_void_p, c_void_p, c_int, c_void_p],
     "rl_score_gemm": [c_void_p, c_i64, c_i32, c_void_p, c_i32, c_int, c_void_p, c_void_p, C.c_float, c_i32, c_i32, c_void_p, c_i64, c_void_p,

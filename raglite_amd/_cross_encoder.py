@@ -18,6 +18,10 @@ weights (`tests/test_host_logic.py`, `tests/test_gpu_parity.py`).  No checkpoint
 weights are random-initialised in the architecture's shape unless `load_hf_state_dict` is given the published ones,
 and the default tokenizer is the hashing stand-in; pass `tokenizer=` (anything with `encode(str) -> list[int]`, e.g. the
 model's WordPiece `tokenizers.Tokenizer` wrapped to return ids without special tokens) for real text.
+
+`forward="native"` sends the pairs through the native encoder and its head kernel instead (`rl_encoder_classify_pack`:
+one C call per pack of at most 8192 tokens), and `rank_batch` then reranks ALL queries of a batch in one forward per pack, every
+`RankedResults` equal to `rank`'s for that query: a pair's logit bits do not depend on the pack it sits in.
 """
 
 from __future__ import annotations
@@ -49,6 +53,9 @@ class CrossEncoderShape(EncoderShape):
     classifier: bool = True
 
 
+FORWARD_MODES = ("torch", "native")
+
+
 def truncate_pair(n_query: int, n_doc: int, budget: int) -> tuple[int, int]:
     """Token counts kept of (query, passage) when the pair exceeds `budget`: the `longest_first` strategy of the
     `tokenizers` library FlashRank truncates with -- drop one token at a time from the longer sequence, from the
@@ -72,13 +79,20 @@ class TorchCrossEncoderRanker:
 
     def __init__(self, shape: CrossEncoderShape | None = None, *, tokenizer: Any | None = None, device: str = "cuda",
                  dtype: Any | None = None, seed: int = 0, max_length: int | None = None, pairs_per_batch: int = 128,
-                 batching: str = "padded", pack_tokens: int = 16384) -> None:
+                 batching: str = "padded", pack_tokens: int = 16384, forward: str = "torch") -> None:
         """batching "padded" (default): length-sorted padded batches of `pairs_per_batch` pairs; "packed": the pairs in input order in
-        unpadded packs of at most `pack_tokens` tokens (`Encoder.forward_packed`; `pairs_per_batch` is ignored)."""
+        unpadded packs of at most `pack_tokens` tokens (`Encoder.forward_packed`; `pairs_per_batch` is ignored).
+        forward "torch" (default): the module's own forward; "native": on a GPU in bf16 / fp16 with a shape the native encoder takes,
+        the pairs in input order in packs of at most min(`pack_tokens`, 8192) tokens through `NativeEncoder.classify_rows`, whatever
+        `batching` says; where that does not apply (CPU, fp32, an unsupported width) the `batching` route, silently."""
         import torch
 
         if batching not in BATCHING_MODES:
             raise ValueError('batching must be "padded" or "packed"')
+        if forward not in FORWARD_MODES:
+            raise ValueError('forward must be "torch" or "native"')
+        self.forward = forward
+        self._native: Any | None = None  # the NativeEncoder, made on the first native forward
         if pack_tokens < 1:
             raise ValueError("pack_tokens must be >= 1")
         self.batching, self.pack_tokens = batching, int(pack_tokens)
@@ -114,11 +128,53 @@ class TorchCrossEncoderRanker:
             out.append(([self.shape.bos_id, *q_ids[:nq], self.shape.eos_id, *d_ids[:nd], self.shape.eos_id], nq + 2))
         return out
 
+    # ---- the native route -----------------------------------------------------------------
+    def _native_applies(self) -> bool:
+        """Does `forward="native"` hold for this ranker as it stands (its module's device and dtype are looked at on every call: a
+        `.to(...)` of the module changes the answer)?"""
+        if self.forward != "native":
+            return False
+        from raglite_amd._encoder import NativeEncoder
+
+        w = self.encoder.tok.weight
+        return NativeEncoder.supports_pack(self.shape, w.dtype, 1, w.device, classify=True)
+
+    def _native_encoder(self) -> Any:
+        if self._native is None:
+            from raglite_amd._encoder import NativeEncoder
+
+            self._native = NativeEncoder(self.encoder, self.shape)
+        return self._native
+
+    @property
+    def native(self) -> Any | None:
+        """The `NativeEncoder` behind `forward="native"` (its `pack_forwards` counts the forwards made), or None before the first one."""
+        return self._native
+
+    def _native_logits(self, pairs: Sequence[tuple[list[int], int]]):  # noqa: ANN202
+        """The logits of encoded pairs, in order: packs of consecutive pairs of at most min(pack_tokens, 8192) tokens, one
+        `classify_rows` each.  Where the cuts fall changes no bit: a pair's logit is a function of the pair alone."""
+        import torch
+
+        from raglite_amd._encoder import MAX_PACK_TOKENS
+
+        native = self._native_encoder()
+        parts = []
+        for lo, hi in pack_runs([len(p[0]) for p in pairs], min(self.pack_tokens, MAX_PACK_TOKENS)):
+            rows = [p[0] for p in pairs[lo:hi]]
+            types = [[0] * first + [1] * (len(r) - first) for r, (_, first) in zip(rows, pairs[lo:hi])]
+            parts.append(native.classify_rows(rows, types))
+        if not parts:
+            return torch.empty(0, dtype=torch.float32, device=self.device)
+        return parts[0] if len(parts) == 1 else torch.cat(parts)
+
     def logits(self, query: str, docs: Sequence[str]):  # noqa: ANN201
         """(len(docs),) float32 tensor of relevance logits on `self.device`."""
         import torch
 
         pairs = self.encode_pairs(query, docs)
+        if self._native_applies():
+            return self._native_logits(pairs)
         out = torch.empty(len(pairs), dtype=torch.float32, device=self.device)
         if self.batching == "packed":
             for lo, hi in pack_runs([len(p[0]) for p in pairs], self.pack_tokens):
@@ -164,3 +220,62 @@ class TorchCrossEncoderRanker:
         ids = list(doc_ids) if doc_ids is not None else list(range(len(docs)))
         return RankedResults(
             [Result(doc_id=ids[i], score=float(scores[i]), rank=r + 1, text=docs[i]) for r, i in enumerate(order)], query)
+
+    # ---- a batch of queries ----------------------------------------------------------------------------------
+    def logits_batch(self, queries: Sequence[str], docs_per_query: Sequence[Sequence[str]]) -> list:
+        """`logits(queries[b], docs_per_query[b])` for every b, with the same bits.  Native route: the pairs of ALL queries, in query
+        order and then doc order, cut into packs by `logits`' rule -- one forward per pack, not per query.  Otherwise the loop."""
+        queries, docs_per_query = list(queries), [list(d) for d in docs_per_query]
+        if len(queries) != len(docs_per_query):
+            raise ValueError("one list of docs per query is required")
+        if not self._native_applies():
+            return [self.logits(q, docs) for q, docs in zip(queries, docs_per_query)]
+        pairs, bounds = [], [0]
+        for q, docs in zip(queries, docs_per_query):
+            pairs += self.encode_pairs(q, docs)
+            bounds.append(len(pairs))
+        flat = self._native_logits(pairs)
+        return [flat[lo:hi] for lo, hi in zip(bounds, bounds[1:])]
+
+    def score_batch(self, queries: Sequence[str], docs_per_query: Sequence[Sequence[str]]) -> list:
+        """`score(queries[b], docs_per_query[b])` for every b: NumPy float32 vectors, the sigmoid taken by torch as in `score`."""
+        import torch
+
+        return [torch.sigmoid(z).cpu().numpy() for z in self.logits_batch(queries, docs_per_query)]
+
+    def rank_batch(self, queries: Sequence[str], docs_per_query: Sequence[Sequence[Any]],
+                   doc_ids_per_query: Sequence[Sequence[int] | None] | None = None) -> list:
+        """`rank(queries[b], docs_per_query[b], doc_ids_per_query[b])` for every b -- the same `doc_id`s in the same order with the same
+        score bits.  Native route: one forward per pack for the whole batch and one `rl_rerank_order` (ragged lists padded with candidate
+        -1), whose order is `rank`'s lexsort: score descending, NaN as -inf, equal scores in input order.  Otherwise the loop of `rank`."""
+        import numpy as np
+
+        from raglite_amd import _ops
+        from raglite_amd._search import RankedResults, Result
+
+        queries = list(queries)
+        docs_per_query = [[d if isinstance(d, str) else str(d) for d in docs] for docs in docs_per_query]
+        ids_per_query = [None] * len(queries) if doc_ids_per_query is None else [None if i is None else list(i) for i in doc_ids_per_query]
+        if len(queries) != len(docs_per_query) or len(queries) != len(ids_per_query):
+            raise ValueError("one list of docs (and of doc ids, where given) per query is required")
+        if not self._native_applies():
+            return [self.rank(q, docs, ids) for q, docs, ids in zip(queries, docs_per_query, ids_per_query)]
+        out = [RankedResults([], q) for q in queries]
+        n_cand = max((len(docs) for docs in docs_per_query), default=0)
+        if n_cand == 0:
+            return out
+        if n_cand > _ops.RERANK_MAX_ENTRIES:
+            raise ValueError(f"TorchCrossEncoderRanker: at most {_ops.RERANK_MAX_ENTRIES} docs per query can be ordered on the device")
+        scores = self.score_batch(queries, docs_per_query)
+        padded = np.zeros((len(queries), n_cand), dtype=np.float32)
+        cand = np.full((len(queries), n_cand), -1, dtype=np.int32)
+        for b, sc in enumerate(scores):
+            padded[b, : len(sc)] = sc
+            cand[b, : len(sc)] = np.arange(len(sc), dtype=np.int32)
+        _, _, pos, counts = _ops.rerank_order(padded, cand, n_cand)
+        pos, counts = np.asarray(pos), np.asarray(counts)
+        for b, (docs, ids, sc) in enumerate(zip(docs_per_query, ids_per_query, scores)):
+            ids = ids if ids is not None else list(range(len(docs)))
+            order = pos[b, : int(counts[b])].tolist()
+            out[b] = RankedResults([Result(doc_id=ids[i], score=float(sc[i]), rank=r + 1, text=docs[i]) for r, i in enumerate(order)], queries[b])
+        return out

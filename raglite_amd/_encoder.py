@@ -16,6 +16,7 @@ from raglite_amd._ops_frame import _Args, _Handle
 MAX_TOKENS = ENCODER_MAX_TOKENS
 MAX_PACK_TOKENS = ENCODER_MAX_PACK_TOKENS  # `forward_pack`: token blocks of MAX_TOKENS rows, a sequence's bits as in a call of its own
 HIDDEN_MAX, FFN_MAX = 8192, 32768
+_HEAD_PARAMS = ("pooler.weight", "pooler.bias", "head.weight", "head.bias")  # the order of rl_encoder_set_head
 _LAYER_PARAMS = ("qkv.weight", "qkv.bias", "out.weight", "out.bias", "ln1.weight", "ln1.bias", "up.weight", "up.bias", "down.weight",
                  "down.bias", "ln2.weight", "ln2.bias")  # the order of rl_encoder_create's layer_params
 
@@ -25,8 +26,8 @@ def _dtype_name(dtype: Any) -> str:
 
 
 class NativeEncoder(_Handle):
-    """`Encoder.forward_packed` without its classifier head, in HIP: `forward` returns the (n_tokens, hidden) rows in the module's
-    16-bit dtype.  The handle borrows the module's parameters; it is made on the first call and made again whenever a parameter's
+    """`Encoder.forward_packed` in HIP: `forward` returns the (n_tokens, hidden) rows in the module's 16-bit dtype (no classifier
+    head); for a `shape.classifier` module, `classify_rows` returns the head's float32 logits, one per sequence.  The handle borrows the module's parameters; it is made on the first call and made again whenever a parameter's
     `data_ptr()` or the dtype has changed (`.to(dtype)`, a `load_state_dict` that reallocates).  A parameter rewritten IN PLACE is
     simply read: the library keeps no copy."""
 
@@ -37,7 +38,7 @@ class NativeEncoder(_Handle):
         self._key: tuple | None = None
         self._held: list = []
         self._workspace: Any | None = None  # `forward_pack`'s scratch: a uint8 CUDA tensor, grown when a larger pack arrives
-        self.pack_forwards = 0  # `rl_encoder_forward_pack` calls made (what a batch of text queries should cost: one)
+        self.pack_forwards = 0  # `rl_encoder_forward_pack` / `rl_encoder_classify_pack` calls made (what a batch that fits a pack should cost: one)
         self._collect()
 
     def _collect(self) -> None:
@@ -47,13 +48,19 @@ class NativeEncoder(_Handle):
         names = ["tok.weight", "pos.weight", "typ.weight", "ln.weight", "ln.bias"]
         names += [f"layers.{i}.{n}" for i in range(self.shape.layers) for n in _LAYER_PARAMS]
         params = dict(self.module.named_parameters())
+        self._n_head = len(_HEAD_PARAMS) if getattr(self.shape, "classifier", False) else 0
+        names += list(_HEAD_PARAMS[: self._n_head])  # (behind the trunk's: `_ensure_handle` hands the trunk's to rl_encoder_create by position)
         self._params = [params[n] for n in names]
 
     @staticmethod
-    def supports(shape: Any, dtype: Any, n_tokens: int, device: Any = "cuda") -> bool:
-        """Does the native forward take a pack of `n_tokens` tokens of this shape, element type and device?"""
+    def supports(shape: Any, dtype: Any, n_tokens: int, device: Any = "cuda", classify: bool = False) -> bool:
+        """Does the native forward take a pack of `n_tokens` tokens of this shape, element type and device?  `classify`: the caller
+        wants the classifier head's logits (`classify_rows`), which needs a `shape.classifier`; without it the answer is about the rows,
+        whatever head the module has."""
         import torch
 
+        if classify and not getattr(shape, "classifier", False):
+            return False
         if torch.device(device).type != "cuda" or _dtype_name(dtype) not in ATTN_DTYPES:
             return False
         if shape.heads < 1 or shape.hidden % shape.heads or shape.hidden // shape.heads not in HEAD_DIMS:
@@ -63,13 +70,14 @@ class NativeEncoder(_Handle):
         return 1 <= n_tokens <= MAX_TOKENS
 
     @staticmethod
-    def supports_pack(shape: Any, dtype: Any, n_tokens: int, device: Any = "cuda") -> bool:
-        """Does `forward_pack` take a pack of `n_tokens` tokens of this shape, element type and device?  `supports` with the cap of
-        `MAX_PACK_TOKENS`."""
-        return 1 <= n_tokens <= MAX_PACK_TOKENS and NativeEncoder.supports(shape, dtype, 1, device)
+    def supports_pack(shape: Any, dtype: Any, n_tokens: int, device: Any = "cuda", classify: bool = False) -> bool:
+        """Does `forward_pack` (`classify`: `classify_rows`) take a pack of `n_tokens` tokens of this shape, element type and device?
+        `supports` with the cap of `MAX_PACK_TOKENS`."""
+        return 1 <= n_tokens <= MAX_PACK_TOKENS and NativeEncoder.supports(shape, dtype, 1, device, classify)
 
     def _ensure_handle(self) -> None:
-        if self.module.tok.weight is not self._params[0] or self.module.layers[-1].ln2.bias is not self._params[-1]:
+        last = self.module.head.bias if self._n_head else self.module.layers[-1].ln2.bias
+        if self.module.tok.weight is not self._params[0] or last is not self._params[-1]:
             self._collect()
         key =(self._params[0].dtype, *(p.data_ptr() for p in self._params))
         if key == self._key and self._handle:
@@ -81,11 +89,14 @@ class NativeEncoder(_Handle):
         name = _dtype_name(tensors[0].dtype)
         if name not in ATTN_DTYPES:
             raise ValueError("NativeEncoder: the encoder must be bfloat16 or float16")
-        layer_ptrs = (C.c_void_p * (len(tensors) - 5))(*(t.data_ptr() for t in tensors[5:]))
+        n_trunk = len(tensors) - self._n_head
+        layer_ptrs = (C.c_void_p * (n_trunk - 5))(*(t.data_ptr() for t in tensors[5:n_trunk]))
         h = C.c_void_p()
         check(lib().rl_encoder_create(C.byref(h), sh.vocab_size, sh.hidden, sh.layers, sh.heads, sh.ffn, sh.max_positions, sh.type_vocab,
                                       float(sh.layer_norm_eps), ATTN_DTYPES[name], *(t.data_ptr() for t in tensors[:5]), layer_ptrs))
         self._handle, self._key, self._held = h, key, tensors  # (the storages the handle reads stay alive with it)
+        if self._n_head:
+            check(lib().rl_encoder_set_head(h, *(t.data_ptr() for t in tensors[n_trunk:])))
 
     def close(self) -> None:
         super().close()
@@ -164,6 +175,56 @@ class NativeEncoder(_Handle):
                                             workspace.data_ptr(), int(workspace.numel()), MEM_DEVICE, a.stream))
         self.pack_forwards += 1
         return out
+
+    def classify_workspace_bytes(self, n_tokens: int, n_seqs: int) -> int:
+        """The device bytes `rl_encoder_classify_pack` needs for `n_tokens` rows in `n_seqs` sequences (host only once the handle exists)."""
+        a = _Args.on(MEM_DEVICE, self._params[0].device)
+        a.ensure_device()
+        self._ensure_handle()
+        n = C.c_int64()
+        check(lib().rl_encoder_classify_workspace_bytes(self._handle, int(n_tokens), int(n_seqs), C.byref(n)))
+        return n.value
+
+    def classify_pack_i32(self, ids: Any, positions: Any, seq_offsets: Any, type_ids: Any | None, n_seqs: int, n_tokens: int, max_len: int,
+                          out: Any | None = None, workspace: Any | None = None) -> Any:
+        """`forward_pack_i32` through the classifier head (`rl_encoder_classify_pack`): (n_seqs,) float32 logits.  `workspace`: at least
+        `classify_workspace_bytes(n_tokens, n_seqs)` bytes; None: the one kept on this object, which `forward_pack_i32` shares."""
+        import torch
+
+        if not self._n_head:
+            raise ValueError("NativeEncoder: classify needs an encoder with a classifier head (shape.classifier)")
+        dev = self._params[0].device
+        a = _Args.on(MEM_DEVICE, dev)
+        a.ensure_device()
+        self._ensure_handle()
+        for t in (ids, positions, seq_offsets, type_ids):
+            if t is not None and not (t.is_cuda and t.dtype == torch.int32 and t.is_contiguous()):
+                raise ValueError("NativeEncoder: ids, positions, seq_offsets and type_ids must be contiguous int32 CUDA tensors")
+        if ids.numel() < n_tokens or positions.numel() < n_tokens or seq_offsets.numel() < n_seqs + 1 or (type_ids is not None and type_ids.numel() < n_tokens):
+            raise ValueError("NativeEncoder: an argument is shorter than n_tokens / n_seqs + 1")
+        if workspace is None:
+            need = self.classify_workspace_bytes(n_tokens, n_seqs) if 0 <= n_tokens <= MAX_PACK_TOKENS and 0 <= n_seqs <= 65535 else 0
+            if self._workspace is None or self._workspace.device != dev or self._workspace.numel() < need:
+                self._workspace = torch.empty(need, dtype=torch.uint8, device=dev)
+            workspace = self._workspace
+        elif not (workspace.is_cuda and workspace.dtype == torch.uint8 and workspace.is_contiguous()):
+            raise ValueError("NativeEncoder: workspace must be a contiguous uint8 CUDA tensor")
+        if out is None:
+            out = torch.empty((n_seqs,), dtype=torch.float32, device=dev)
+        elif not (out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and out.numel() >= n_seqs):
+            raise ValueError("NativeEncoder: out must be a contiguous float32 CUDA tensor of at least n_seqs elements")
+        a.hold(ids, positions, seq_offsets, type_ids, out, workspace)
+        check(lib().rl_encoder_classify_pack(self._handle, ids.data_ptr(), positions.data_ptr(), type_ids.data_ptr() if type_ids is not None else None,
+                                             seq_offsets.data_ptr(), int(n_seqs), int(n_tokens), int(max_len), out.data_ptr(),
+                                             workspace.data_ptr(), int(workspace.numel()), MEM_DEVICE, a.stream))
+        self.pack_forwards += 1
+        return out
+
+    def classify_rows(self, rows: Sequence[Sequence[int]], type_rows: Sequence[Sequence[int]] | None = None) -> Any:
+        """The logits of token-id lists (each with its `[CLS]` / `[SEP]`s), (len(rows),) float32 on the device: ONE copy from pinned
+        memory, then the one C call.  A sequence's logit bits do not depend on what else is in `rows`."""
+        buf, typ, n, lens = self._upload_rows(rows, type_rows)
+        return self.classify_pack_i32(buf[:n], buf[n: 2 * n], buf[(3 if typ is not None else 2) * n:], typ, len(lens), n, max(lens))
 
     def forward_pack(self, ids: Any, seq_offsets: Any, lengths_host: Sequence[int], type_ids: Any | None = None) -> Any:
         """`forward` for a pack of up to `MAX_PACK_TOKENS` tokens: every sequence's rows are bit for bit the rows `forward` gives for
@@ -286,6 +347,29 @@ def encoder_linear_pack(x: Any, W: Any, bias: Any | None = None, epilogue: str =
     """`encoder_linear` for M up to `MAX_PACK_TOKENS` rows (`rl_encoder_linear_pack`): above `MAX_TOKENS` one workgroup per token block
     of 256 rows, every row with the bits `encoder_linear` gives it."""
     return _linear("rl_encoder_linear_pack", "encoder_linear_pack", x, W, bias, epilogue, out)
+
+
+def encoder_head(x: Any, seq_offsets: Any, pooler_w: Any, pooler_b: Any, head_w: Any, head_b: Any, *, out: Any | None = None) -> Any:
+    """The cross-encoder's head on its own (`rl_encoder_head`): x (n_tokens, hidden) final hidden states, seq_offsets int32 (n_seqs + 1) on
+    the device; pooler_w (hidden, hidden), pooler_b (hidden,), head_w (1, hidden) or (hidden,), head_b (1,), all of x's 16-bit dtype.
+    Returns (n_seqs,) float32: head_w . tanh(pooler_w x[first token] + pooler_b) + head_b, every step in f32; NaN for an empty sequence."""
+    import torch
+
+    if x.dim() != 2 or tuple(pooler_w.shape) != (x.shape[1], x.shape[1]) or tuple(pooler_b.shape) != (x.shape[1],) or head_w.numel() != x.shape[1] \
+            or head_b.numel() != 1:
+        raise ValueError("encoder_head: x must be (n_tokens, hidden), pooler_w (hidden, hidden), pooler_b (hidden,), head_w of hidden elements, head_b of one")
+    if not (seq_offsets.is_cuda and seq_offsets.dtype == torch.int32 and seq_offsets.is_contiguous() and seq_offsets.dim() == 1 and seq_offsets.numel() >= 1):
+        raise ValueError("encoder_head: seq_offsets must be a contiguous int32 CUDA tensor of n_seqs + 1 elements")
+    dt, a = _take("encoder_head", x.dtype, x, pooler_w, pooler_b, head_w, head_b)
+    n_seqs = int(seq_offsets.numel()) - 1
+    if out is None:
+        out = torch.empty((n_seqs,), dtype=torch.float32, device=x.device)
+    elif not (out.is_cuda and out.is_contiguous() and tuple(out.shape) == (n_seqs,) and out.dtype == torch.float32):
+        raise ValueError("encoder_head: out must be a contiguous float32 CUDA tensor (n_seqs,)")
+    a.hold(x, seq_offsets, pooler_w, pooler_b, head_w, head_b, out)
+    check(lib().rl_encoder_head(x.data_ptr(), seq_offsets.data_ptr(), n_seqs, int(x.shape[0]), int(x.shape[1]), pooler_w.data_ptr(),
+                                pooler_b.data_ptr(), head_w.data_ptr(), head_b.data_ptr(), dt, out.data_ptr(), MEM_DEVICE, a.stream))
+    return out
 
 
 def encoder_layer_norm(part: Any, bias: Any, resid: Any, ln_w: Any, ln_b: Any, eps: float, *, out: Any | None = None) -> Any:

@@ -1339,16 +1339,55 @@ def _device_ranker(cfg: Any, gi: GpuIndex) -> "MaxSimRanker | None":
     return reranker if isinstance(reranker, MaxSimRanker) and reranker.index is gi else None
 
 
+def _native_cross_encoder(cfg: Any) -> Any | None:
+    """`cfg.reranker` when it is ONE `TorchCrossEncoderRanker` with `forward == "native"` (not a dict by language): the case the
+    batched cross-encoder path covers."""
+    reranker = getattr(cfg, "reranker", None)
+    if reranker is None or isinstance(reranker, (dict, MaxSimRanker)):
+        return None
+    from raglite_amd._cross_encoder import TorchCrossEncoderRanker
+
+    return reranker if isinstance(reranker, TorchCrossEncoderRanker) and reranker.forward == "native" else None
+
+
+def _cross_encoder_rerank_batch(ranker: Any, queries: Sequence[str], found: Sequence[Sequence[Any]],
+                                chunk_lookup: Callable[[Sequence[ChunkId]], list[Any]] | None) -> tuple[list[list[Any]], list[RankedResults]]:
+    """`rerank_chunks` for every query with ONE `rank_batch`: per query the ids are resolved through `chunk_lookup` (once, as there),
+    `str(chunk)` is the doc, and the chunks come back best first; also the `RankedResults` (their `doc_id`s index the query's list)."""
+    resolved = []
+    for ids in found:
+        chunks = list(ids)
+        if chunks and all(isinstance(c, ChunkId) for c in chunks):
+            if chunk_lookup is None:
+                raise ValueError("chunk ids need a chunk_lookup callable (the reference's retrieve_chunks)")
+            chunks = chunk_lookup(chunks)
+        resolved.append(chunks)
+    ranked = ranker.rank_batch(queries, [[str(chunk) for chunk in chunks] for chunks in resolved])
+    return [[chunks[r.doc_id] for r in res.results] for chunks, res in zip(resolved, ranked)], ranked
+
+
 def rerank_chunks_batch(queries: Sequence[str], chunk_ids_per_query: Sequence[Sequence[ChunkId]], *, config: Any,
-                        index: GpuIndex | None = None, query_token_vectors=None) -> list[tuple[list[ChunkId], list[float]]]:
+                        index: GpuIndex | None = None, query_token_vectors=None,
+                        chunk_lookup: Callable[[Sequence[ChunkId]], list[Any]] | None = None) -> list[tuple[list[ChunkId], list[float]]]:
     """MaxSim-rerank a batch of (ragged) chunk id lists: element b is (ids best first, their MaxSim scores), the order
     `config.reranker.rank(queries[b], <those chunks' docs>)` gives.  `config.reranker` must be a `MaxSimRanker` over `index`; one
     scoring call and one `rl_rerank_order` for the batch: `rl_maxsim_rerank_ragged` where the queries' lengths differ
-    (`MaxSimRanker._routes`).  `query_token_vectors`: one (nq, dim) matrix per query, of any lengths, skips the ranker's query encoder."""
+    (`MaxSimRanker._routes`).  `query_token_vectors`: one (nq, dim) matrix per query, of any lengths, skips the ranker's query encoder.
+
+    Or `config.reranker` is a `TorchCrossEncoderRanker(forward="native")`, with a `chunk_lookup` for the ids' texts: element b is (ids
+    best first, their cross-encoder scores), from one `rank_batch` -- one native forward per pack of pairs, not per query (no index is
+    needed or looked at)."""
+    cross = _native_cross_encoder(config)
+    if cross is not None:
+        queries, id_lists = list(queries), [list(ids) for ids in chunk_ids_per_query]
+        if len(queries) != len(id_lists):
+            raise ValueError("one list of chunk ids per query is required")
+        _, ranked = _cross_encoder_rerank_batch(cross, queries, id_lists, chunk_lookup)
+        return [([ids[r.doc_id] for r in res.results], [r.score for r in res.results]) for ids, res in zip(id_lists, ranked)]
     gi = index or _index_for(config)
     ranker = _device_ranker(config, gi)
     if ranker is None:
-        raise ValueError("rerank_chunks_batch needs config.reranker to be a MaxSimRanker over the index")
+        raise ValueError("rerank_chunks_batch needs config.reranker to be a MaxSimRanker over the index, or a native cross-encoder")
     queries, id_lists = list(queries), [list(ids) for ids in chunk_ids_per_query]
     if len(queries) != len(id_lists):
         raise ValueError("one list of chunk ids per query is required")
@@ -1374,8 +1413,11 @@ def search_and_rerank_chunks_batch(queries: Sequence[str], *, num_results: int =
     with `ranker.ragged` off, one call per distinct length) -- nothing is read back in between, and the best `num_results` are read
     back once.  Query token vectors come from the ranker's `query_encoder`, one query at a time, or from `query_token_vectors` (one
     (nq, dim) matrix per query, of any lengths).
-    Without a reranker the batched search's results are returned truncated.  Any other reranker (a dict by language, a cross-encoder)
-    is outside the device path: the batched search runs, then `rerank_chunks` per query.  `metadata_filter` and `query_vectors` as in
+    Without a reranker the batched search's results are returned truncated.  With `config.reranker` ONE
+    `TorchCrossEncoderRanker(forward="native")` the batched search runs, then one `rank_batch` over all queries' found chunks: one native
+    forward per pack of (query, chunk) pairs instead of one rerank per query.  Any other reranker (a dict by language, a
+    cross-encoder with `forward="torch"`, anything with only `rank`) is outside the device path: the batched search runs, then
+    `rerank_chunks` per query.  `metadata_filter` and `query_vectors` as in
     `hybrid_search_batch`.  Raises where the loop would raise for some element, with its message."""
     cfg = config or HotPathConfig()
     gi = index or _index_for(config)
@@ -1394,6 +1436,9 @@ def search_and_rerank_chunks_batch(queries: Sequence[str], *, num_results: int =
         found = [ids for ids, _ in batch(queries, num_results=n_cand, metadata_filter=metadata_filter, config=cfg, index=gi,
                                          query_vectors=query_vectors)]
         if getattr(cfg, "reranker", None) and any(found):
+            cross = _native_cross_encoder(cfg)
+            if cross is not None:  # one rank_batch for all queries' found chunks: one native forward per pack
+                return [chunks[:num_results] for chunks in _cross_encoder_rerank_batch(cross, queries, found, chunk_lookup)[0]]
             return [rerank_chunks(q, ids, config=cfg, chunk_lookup=chunk_lookup)[:num_results] for q, ids in zip(queries, found)]
     elif kind == "hybrid":
         found = _hybrid_rerank_device(gi, cfg, ranker, queries, num_results, n_cand, metadata_filter, query_vectors, query_token_vectors)

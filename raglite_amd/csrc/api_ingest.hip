@@ -118,7 +118,7 @@ int rl_encoder_info(const rl_encoder* enc, int64_t n_tokens, int32_t* max_tokens
 // The handle comes after them, in the callers.
 static int check_forward_args(const char* who, int64_t cap, const char* cap_name, const int32_t* ids, const int32_t* positions,
                               const int32_t* type_ids, const int32_t* seq_offsets, int32_t n_seqs, int64_t n_tokens, int32_t max_len,
-                              const void* out, int mem) {
+                              const void* out, int mem, uintptr_t out_align = 16) {
     const std::string w(who);
     if (mem != RL_MEM_DEVICE) return fail(RL_ERR_UNSUPPORTED, w + ": device pointers only (mem must be RL_MEM_DEVICE)");
     if (n_seqs < 0 || n_tokens < 0 || max_len < 0) return fail(RL_ERR_INVALID, w + ": negative size");
@@ -126,8 +126,8 @@ static int check_forward_args(const char* who, int64_t cap, const char* cap_name
     if (n_tokens > cap) return fail(RL_ERR_UNSUPPORTED, w + ": n_tokens must be <= " + cap_name + " (" + std::to_string(cap) + ")");
     if (n_tokens > 0) {
         if (!ids || !positions || !seq_offsets || !out) return fail(RL_ERR_INVALID, w + ": null argument");
-        if (misaligned(ids, 4) || misaligned(positions, 4) || misaligned(type_ids, 4) || misaligned(seq_offsets, 4) || misaligned(out, 16))
-            return fail(RL_ERR_INVALID, w + ": the int32 arrays must be 4-byte and out 16-byte aligned");
+        if (misaligned(ids, 4) || misaligned(positions, 4) || misaligned(type_ids, 4) || misaligned(seq_offsets, 4) || misaligned(out, out_align))
+            return fail(RL_ERR_INVALID, w + ": the int32 arrays must be 4-byte and out " + std::to_string(out_align) + "-byte aligned");
     }
     return RL_OK;
 }
@@ -287,6 +287,76 @@ int rl_encoder_layer_norm(const float* part, int32_t slices, int64_t M, int32_t 
     if (misaligned(bias, 8) || misaligned(resid, 8) || misaligned(ln_w, 8) || misaligned(ln_b, 8) || misaligned(out, 8))
         return fail(RL_ERR_INVALID, "rl_encoder_layer_norm: bias, resid, ln_w, ln_b and out must be 8-byte aligned");
     return launch_encoder_ln(part, slices, (int32_t)M, hidden, bias, resid, ln_w, ln_b, eps, dtype, out, as_stream(stream));
+}
+
+// ---- the cross-encoder's head on the native forward (encoder_head.hip) ------------------------------------------------
+int rl_encoder_head(const void* x, const int32_t* seq_offsets, int32_t n_seqs, int64_t n_tokens, int32_t hidden, const void* pooler_w,
+                    const void* pooler_b, const void* head_w, const void* head_b, int32_t dtype, float* out_logits, int mem, void* stream) {
+    if (mem != RL_MEM_DEVICE) return fail(RL_ERR_UNSUPPORTED, "rl_encoder_head: device pointers only (mem must be RL_MEM_DEVICE)");
+    if (n_seqs < 0 || n_seqs > 65535) return fail(RL_ERR_INVALID, "rl_encoder_head: n_seqs must be in [0, 65535]");
+    if (n_tokens < 0 || n_tokens >= ((int64_t)1 << 31)) return fail(RL_ERR_INVALID, "rl_encoder_head: n_tokens must be in [0, 2^31)");
+    if (bad_width(hidden)) return fail(RL_ERR_INVALID, "rl_encoder_head: hidden must be a positive multiple of 32");
+    if (hidden > ENC_HIDDEN_MAX) return fail(RL_ERR_UNSUPPORTED, "rl_encoder_head: hidden must be <= 8192");
+    if (dtype != RL_ATTN_BF16 && dtype != RL_ATTN_F16) return fail(RL_ERR_INVALID, "rl_encoder_head: unknown dtype");
+    if (n_seqs == 0) return RL_OK;
+    if (n_tokens == 0) return fail(RL_ERR_INVALID, "rl_encoder_head: n_tokens must be >= 1 when there are sequences");
+    if (!x || !seq_offsets || !pooler_w || !pooler_b || !head_w || !head_b || !out_logits) return fail(RL_ERR_INVALID, "rl_encoder_head: null argument");
+    if (misaligned(x, 16) || misaligned(pooler_w, 16) || misaligned(pooler_b, 16) || misaligned(head_w, 16) || misaligned(head_b, 16))
+        return fail(RL_ERR_INVALID, "rl_encoder_head: x and the four parameters must be 16-byte aligned");
+    if (misaligned(seq_offsets, 4) || misaligned(out_logits, 4)) return fail(RL_ERR_INVALID, "rl_encoder_head: seq_offsets and out_logits must be 4-byte aligned");
+    return launch_encoder_head(x, seq_offsets, n_seqs, (int32_t)n_tokens, hidden, pooler_w, pooler_b, head_w, head_b, dtype, out_logits,
+                               as_stream(stream));
+}
+
+int rl_encoder_set_head(rl_encoder* enc, const void* pooler_w, const void* pooler_b, const void* head_w, const void* head_b) {
+    const int given = (pooler_w != nullptr) + (pooler_b != nullptr) + (head_w != nullptr) + (head_b != nullptr);
+    if (given != 0 && given != 4) return fail(RL_ERR_INVALID, "rl_encoder_set_head: give all four pointers, or none to clear the head");
+    if (misaligned(pooler_w, 16) || misaligned(pooler_b, 16) || misaligned(head_w, 16) || misaligned(head_b, 16))
+        return fail(RL_ERR_INVALID, "rl_encoder_set_head: every parameter must be 16-byte aligned");
+    if (!enc) return fail(RL_ERR_INVALID, "rl_encoder_set_head: null handle");
+    std::lock_guard<std::mutex> lock(enc->mu);
+    enc->pooler_w = pooler_w; enc->pooler_b = pooler_b; enc->head_w = head_w; enc->head_b = head_b;
+    return RL_OK;
+}
+
+static size_t classify_workspace_bytes(const rl_encoder* enc, int64_t n_tokens) {  // the one walk: rl_encoder_classify_pack takes its pointers from it
+    return EncoderClassifyScratch().lay(Carver(), (size_t)n_tokens, (size_t)enc->hidden, (size_t)enc->ffn, (size_t)enc->ksplit);
+}
+
+int rl_encoder_classify_workspace_bytes(const rl_encoder* enc, int64_t n_tokens, int32_t n_seqs, int64_t* bytes) {
+    if (n_tokens < 0 || n_tokens > RL_ENCODER_MAX_PACK_TOKENS)
+        return fail(RL_ERR_INVALID, "rl_encoder_classify_workspace_bytes: n_tokens must be in [0, RL_ENCODER_MAX_PACK_TOKENS]");
+    if (n_seqs < 0 || n_seqs > 65535) return fail(RL_ERR_INVALID, "rl_encoder_classify_workspace_bytes: n_seqs must be in [0, 65535]");
+    if (!bytes) return fail(RL_ERR_INVALID, "rl_encoder_classify_workspace_bytes: bytes is null");
+    if (!enc) return fail(RL_ERR_INVALID, "rl_encoder_classify_workspace_bytes: null handle");
+    *bytes = (int64_t)classify_workspace_bytes(enc, n_tokens);
+    return RL_OK;
+}
+
+int rl_encoder_classify_pack(rl_encoder* enc, const int32_t* ids, const int32_t* positions, const int32_t* type_ids,
+                             const int32_t* seq_offsets, int32_t n_seqs, int64_t n_tokens, int32_t max_len, float* out_logits,
+                             void* workspace, int64_t workspace_bytes, int mem, void* stream) {
+    RL_TRY(check_forward_args("rl_encoder_classify_pack", RL_ENCODER_MAX_PACK_TOKENS, "RL_ENCODER_MAX_PACK_TOKENS", ids, positions, type_ids,
+                              seq_offsets, n_seqs, n_tokens, max_len, out_logits, mem, 4));
+    if (n_tokens > 0) {
+        if (!workspace) return fail(RL_ERR_INVALID, "rl_encoder_classify_pack: workspace is null");
+        if (misaligned(workspace, 16)) return fail(RL_ERR_INVALID, "rl_encoder_classify_pack: workspace must be 16-byte aligned");
+    }
+    if (!enc) return fail(RL_ERR_INVALID, "rl_encoder_classify_pack: null handle");
+    const void *pw, *pb, *hw, *hb;
+    {
+        std::lock_guard<std::mutex> lock(enc->mu);
+        pw = enc->pooler_w; pb = enc->pooler_b; hw = enc->head_w; hb = enc->head_b;
+    }
+    if (!pw) return fail(RL_ERR_INVALID, "rl_encoder_classify_pack: the handle has no head (rl_encoder_set_head)");
+    if (n_tokens == 0) return RL_OK;
+    if (workspace_bytes < 0 || (uint64_t)workspace_bytes < (uint64_t)classify_workspace_bytes(enc, n_tokens))
+        return fail(RL_ERR_INVALID, "rl_encoder_classify_pack: workspace_bytes is less than rl_encoder_classify_workspace_bytes(n_tokens, n_seqs)");
+    EncoderClassifyScratch w;  // the trunk's scratch lies at the workspace's start: its launches get the block rl_encoder_forward_pack gives them
+    w.lay(Carver(workspace), (size_t)n_tokens, (size_t)enc->hidden, (size_t)enc->ffn, (size_t)enc->ksplit);
+    hipStream_t s = as_stream(stream);
+    RL_TRY(encoder_launches(enc, ids, positions, type_ids, seq_offsets, n_seqs, (int32_t)n_tokens, max_len, w.final_rows, workspace, s));
+    return launch_encoder_head(w.final_rows, seq_offsets, n_seqs, (int32_t)n_tokens, enc->hidden, pw, pb, hw, hb, enc->dtype, out_logits, s);
 }
 
 // ---- document-batched ingestion: similarities, chunk / chunklet / sentence partitions (kernels in partition_sim.hip, partition_dp.hip,

@@ -132,6 +132,10 @@ int launch_encoder_linear(const void* x, int32_t M, int32_t K, const void* W, in
 // out[r] = LN(part[0][r] + .. + part[ksplit - 1][r] + bias + resid[r])
 int launch_encoder_ln(const float* part, int32_t ksplit, int32_t M, int32_t hidden, const void* bias, const void* resid, const void* ln_w,
                       const void* ln_b, float eps, int32_t dtype, void* out, hipStream_t s);
+// encoder_head.hip: out_logits[s] = head_w . tanh(pooler_w x[clamp(seq_offsets[s])] + pooler_b) + head_b in f32, a quiet
+// NaN for an empty sequence; n_tokens >= 1, hidden a multiple of 32 and <= ENC_HIDDEN_MAX; arguments already checked
+int launch_encoder_head(const void* x, const int32_t* seq_offsets, int32_t n_seqs, int32_t n_tokens, int32_t hidden, const void* pooler_w,
+                        const void* pooler_b, const void* head_w, const void* head_b, int32_t dtype, float* out_logits, hipStream_t s);
 
 // scan.hip
 enum ScanMode { SCAN_RAW_DOT = 0, SCAN_COSINE = 1, SCAN_DOT = 2, SCAN_L2 = 3 };

@@ -217,7 +217,8 @@ struct rl_encoder {
     const void *tok = nullptr, *pos = nullptr, *typ = nullptr, *ln_w = nullptr, *ln_b = nullptr;  // borrowed, like everything in `layer`
     struct Layer { const void *qkv_w, *qkv_b, *out_w, *out_b, *ln1_w, *ln1_b, *up_w, *up_b, *down_w, *down_b, *ln2_w, *ln2_b; };
     std::vector<Layer> layer;
-    int32_t ksplit = 1;           // the larger of the out and down projections' K slices: what `part` of the scratch is sized by
+    const void *pooler_w = nullptr, *pooler_b = nullptr, *head_w = nullptr, *head_b = nullptr;  // rl_encoder_set_head: borrowed; all null = no head
+    int32_t ksplit = 1;          // the larger of the out and down projections' K slices: what `part` of the scratch is sized by
     std::mutex mu;
     rl::Pool scratch;             // rl::EncoderScratch over RL_ENCODER_MAX_TOKENS rows; every call walks a prefix of it
     rl::LastStream last_stream;

@@ -220,4 +220,15 @@ struct EncoderScratch {  // rl_encoder_forward, the handle's one block: reserved
     }
 };
 
+struct EncoderClassifyScratch {  // rl_encoder_classify_pack, over the caller's workspace: the pack's own scratch FIRST (so the trunk's
+                                 // launches see the block rl_encoder_forward_pack would give them), then the rows the trunk writes and the head reads
+    EncoderScratch trunk;
+    uint16_t* final_rows;  // [rows x hidden] the last layer's output
+    size_t lay(Carver c, size_t rows, size_t hidden, size_t ffn, size_t ksplit) {
+        c.off = trunk.lay(c, rows, hidden, ffn, ksplit);
+        final_rows = c.take<uint16_t>(rows * hidden);
+        return c.off;
+    }
+};
+
 }  // namespace rl
