@@ -1170,6 +1170,69 @@ int rl_partition_sentences(const uint32_t* codepoints, const void* probas, int p
                            const int64_t* doc_offsets, int64_t n, int64_t n_docs, int64_t min_len, int64_t max_len,
                            uint8_t* cut, double* objective, int32_t* status, int mem, void* stream);
 
+/* ---- WordPiece on the device: the cross-encoder's tokenizer --------------
+ * What the `tokenizers` library's BERT pipeline (BertNormalizer, BertPreTokenizer, WordPiece) does for
+ * many texts, on their UTF-32 code points: token ids equal to tok.encode(text, add_special_tokens =
+ * False).ids of the tokenizer the tables were probed from.  The library embeds neither Unicode data
+ * nor a vocabulary: rl_wordpiece_create takes (all HOST pointers, copied)
+ *   image        uint64[n_table]: the normalised image of a code point, three 21-bit fields from bit 0,
+ *                field = code point + 1, 0 = no further one; a code point >= n_table has the empty image
+ *   cls          uint8[n_table]: bits 0-1 the class of a code point where it occurs in an image (0 word
+ *                character, 1 white space, 2 punctuation -- a word of its own); bit 2 the context flag of
+ *                an input code point: its image may depend on its neighbours, so a text that holds one
+ *                gets status 1 and its ids are NOT the contract's (the caller tokenizes it elsewhere)
+ *   piece_cp     uint32: the vocabulary's pieces as UTF-32 back to back, the continuation prefix stripped
+ *   piece_off    int64[n_pieces + 1] into piece_cp;  piece_flags uint8[n_pieces]: bit 0 = a continuation;
+ *   piece_ids    int32[n_pieces] the token ids (>= 0).  Empty pieces and pieces longer than
+ *                max_word_chars can match nothing and are left out; of equal pieces the first stays
+ *   unk_id, max_word_chars (the model's max_input_chars_per_word; RL_ERR_UNSUPPORTED above 200)
+ *   hash_bits    0 or 64 = all; otherwise only that many low bits of the piece hash are used (tests
+ *                force collisions with it; results never depend on it: every hit compares code points)
+ * rl_wordpiece_encode takes codepoints uint32[n] (UTF-32) and text_off int64[n_texts + 1] (a CSR over
+ * them), host or device by `mem`; nothing carries across a text boundary.  Per text: expand through
+ * image; words are maximal runs of word characters and single punctuation symbols, white space is
+ * dropped; a word of more than max_word_chars normalised symbols is one unk_id; otherwise greedy
+ * longest match from the left, as a continuation behind the word's first piece, and one position
+ * without a match makes the whole word one unk_id.  It leaves ids int32[n_tokens], offsets
+ * int64[n_texts + 1] and status uint8[n_texts] in device memory the handle owns until its next encode
+ * (rl_wordpiece_device returns the pointers, rl_wordpiece_result copies them out; NULL skips one) and
+ * fills out_counts (HOST) = (n_tokens, n_words, unk words, texts with status 1, normalised symbols).
+ * Synchronises `stream`.  Each phase is its own launch; the only atomics are integer adds of the two
+ * counters; same bytes run to run and for host and device pointers.  Calls on one handle are
+ * serialised.  rl_wordpiece_info: out = (pieces kept, longest piece, table slots, device bytes held).
+ * RL_ERR_INVALID before any HIP call: a null handle or pointer, n_table outside [1, 0x110000], a
+ * malformed image or cls entry, piece_off that does not start at 0 or ascend, a negative id or size,
+ * hash_bits outside 0 .. 64, code points without a text, and for RL_MEM_HOST text_off that does not
+ * start at 0 / ascend / end at n.  RL_ERR_UNSUPPORTED: n >= 2^28 code points in one call.
+ *
+ * rl_wordpiece_pairs is a free function over ANY token lists (ids int32, tok_off int64[n_texts + 1]):
+ * for pair p with query text a = query_text[p] and doc text b = doc_text[p] (int32 indices),
+ *   (nq, nd) = the `longest_first` truncation of (tokens of a, tokens of b) to max_length - 3: one token
+ *              at a time from the longer list, from the doc on a tie
+ *   row p    = cls_id, a's first nq ids, sep_id, b's first nd ids, sep_id
+ *   type ids = 0 for the first nq + 2 tokens, then 1;  positions = position_offset + 0, 1, ...
+ *   out_seq_offsets int32[n_pairs + 1], *out_total (HOST) = the rows' tokens
+ * -- the four arrays rl_encoder_classify_pack takes.  With out_ids, out_positions and out_type_ids all
+ * NULL only the offsets and the total are computed (what a caller sizes the three by).  Synchronises
+ * `stream`.  RL_ERR_INVALID before any HIP call: bad mem, a negative size, max_length < 3, a null
+ * tok_off / out_seq_offsets / out_total / index list, one or two of the three outputs, and for
+ * RL_MEM_HOST tok_off that does not start at 0 or ascend, or an index outside [0, n_texts) (device
+ * callers: such a text counts as empty).  RL_ERR_UNSUPPORTED: 2^31 tokens or more in one call. */
+typedef struct rl_wordpiece rl_wordpiece;
+int rl_wordpiece_create(rl_wordpiece** out, const uint64_t* image, const uint8_t* cls, int64_t n_table, const uint32_t* piece_cp,
+                        const int64_t* piece_off, const uint8_t* piece_flags, const int32_t* piece_ids, int64_t n_pieces,
+                        int32_t unk_id, int32_t max_word_chars, int32_t hash_bits);
+int rl_wordpiece_destroy(rl_wordpiece* tok);
+int rl_wordpiece_info(rl_wordpiece* tok, int64_t out[4]);
+int rl_wordpiece_encode(rl_wordpiece* tok, const uint32_t* codepoints, const int64_t* text_off, int64_t n, int64_t n_texts,
+                        int64_t out_counts[5], int mem, void* stream);
+int rl_wordpiece_result(rl_wordpiece* tok, int32_t* ids, int64_t* offsets, uint8_t* status, int mem, void* stream);
+int rl_wordpiece_device(rl_wordpiece* tok, const int32_t** ids, const int64_t** offsets, const uint8_t** status);
+int rl_wordpiece_pairs(const int32_t* ids, const int64_t* tok_off, int64_t n_texts, const int32_t* query_text, const int32_t* doc_text,
+                       int64_t n_pairs, int32_t max_length, int32_t cls_id, int32_t sep_id, int32_t position_offset, int32_t* out_ids,
+                       int32_t* out_positions, int32_t* out_type_ids, int32_t* out_seq_offsets, int64_t* out_total, int mem,
+                       void* stream);
+
 /* What the last bound-filtered search on this index did (diagnostic; bench.py reports it next to every timed number that depends
  * on it).  The searches that rank on approximate scores and re-score what a rigorous bound cannot rule out -- rl_maxsim_topk_batch
  * over the HI image, rl_search_rows for B <= 16 over the HI plane, the fused top-k of B >= 96 -- keep per-query candidate lists of a

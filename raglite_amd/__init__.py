@@ -96,6 +96,7 @@ from raglite_amd._query_adapter import optimize_query_target_active_set, optimiz
 from raglite_amd._comm import Communicator
 from raglite_amd._attention import attention_varlen
 from raglite_amd._encoder import NativeEncoder
+from raglite_amd._wordpiece import DeviceWordPiece, WordPieceTables
 from raglite_amd._sharded import ShardedIndex, merge_topk_host, shard_bounds_by_chunk
 
 __all__ = [
@@ -144,5 +145,6 @@ __all__ = [
     "rerank_chunks", "search_and_rerank_chunks", "select_reranker", "set_language_detector", "set_device", "set_embedder_factory", "shard_bounds_by_chunk",
     "synth_fill", "topk", "vector_search",
     "attention_varlen", "embed_strings_batch", "NativeEncoder",
+    "DeviceWordPiece", "WordPieceTables",
 ]
 __version__ = "0.1.0"

@@ -83,6 +83,14 @@ _SIGNATURES = {
     "rl_encoder_classify_workspace_bytes": [c_void_p, c_i64, c_i32, C.POINTER(c_i64)],
     "rl_encoder_classify_pack": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_i32, c_i64, c_i32, c_void_p, c_void_p, c_i64, c_int,
                                  c_void_p],
+    "rl_wordpiece_create": [C.POINTER(c_void_p), c_void_p, c_void_p, c_i64, c_void_p, c_void_p, c_void_p, c_void_p, c_i64, c_i32, c_i32, c_i32],
+    "rl_wordpiece_destroy": [c_void_p],
+    "rl_wordpiece_info": [c_void_p, c_void_p],
+    "rl_wordpiece_encode": [c_void_p, c_void_p, c_void_p, c_i64, c_i64, c_void_p, c_int, c_void_p],
+    "rl_wordpiece_result": [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p],
+    "rl_wordpiece_device": [c_void_p, C.POINTER(c_void_p), C.POINTER(c_void_p), C.POINTER(c_void_p)],
+    "rl_wordpiece_pairs": [c_void_p, c_void_p, c_i64, c_void_p, c_void_p, c_i64, c_i32, c_i32, c_i32, c_i32, c_void_p, c_void_p, c_void_p,
+                           c_void_p, c_void_p, c_int, c_void_p],
     "rl_adapter_apply": [c_void_p, c_void_p, c_i32, c_i32, c_void_p, c_void_p, c_int, c_void_p],
     "rl_adapter_apply_rows": [c_void_p, c_void_p, c_i32, c_i32, c_void_p, c_void_p, c_int, c_void_p],
     "rl_score_gemm": [c_void_p, c_i64, c_i32, c_void_p, c_i32, c_int, c_void_p, c_void_p, C.c_float, c_i32, c_i32, c_void_p, c_i64, c_void_p,

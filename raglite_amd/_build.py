@@ -26,6 +26,7 @@ SOURCES = [
     "attention_varlen.hip",  # the packed encoder's attention
     "encoder.hip",  # the native encoder forward for short packs
     "encoder_head.hip",  # the cross-encoder's pooler + classifier head on its final rows
+    "wordpiece.hip",  # the cross-encoder's tokenizer: BERT WordPiece and pair assembly
     "adapter_fit.hip", "query_targets.hip",  # query adapter
     "keyword.hip", "keyword_build.hip", "keyword_analyze.hip",  # BM25
     "fuse.hip", "rerank.hip", "spans.hip", "metadata.hip",  # fusion, rerank order, spans, metadata filters

@@ -22,6 +22,10 @@ model's WordPiece `tokenizers.Tokenizer` wrapped to return ids without special t
 `forward="native"` sends the pairs through the native encoder and its head kernel instead (`rl_encoder_classify_pack`:
 one C call per pack of at most 8192 tokens), and `rank_batch` then reranks ALL queries of a batch in one forward per pack, every
 `RankedResults` equal to `rank`'s for that query: a pair's logit bits do not depend on the pack it sits in.
+
+With `tokenizer=DeviceWordPiece(tables)` on that route, the text itself goes to the device: the distinct strings of a
+call are tokenized once by the WordPiece kernels, the `[CLS] q [SEP] d [SEP]` rows are assembled there, and only the pairs' offsets
+come back before the forwards -- the same `doc_id`s, order and score bits as with the mirrored tokenizer wrapped as `encode`.
 """
 
 from __future__ import annotations
@@ -54,6 +58,11 @@ class CrossEncoderShape(EncoderShape):
 
 
 FORWARD_MODES = ("torch", "native")
+
+
+def _lengths(offsets: Any) -> list[int]:
+    """The lengths behind host offsets, as Python integers."""
+    return [int(b) - int(a) for a, b in zip(offsets[:-1], offsets[1:])]
 
 
 def truncate_pair(n_query: int, n_doc: int, budget: int) -> tuple[int, int]:
@@ -168,10 +177,36 @@ class TorchCrossEncoderRanker:
             return torch.empty(0, dtype=torch.float32, device=self.device)
         return parts[0] if len(parts) == 1 else torch.cat(parts)
 
+    def _device_pairs_apply(self) -> bool:
+        """Does text go to logits on the device?  Only with a tokenizer that assembles the pairs there
+        (`DeviceWordPiece.encode_pairs_device`) AND the native route; every other combination runs the code it ran before."""
+        return hasattr(self.tokenizer, "encode_pairs_device") and self._native_applies()
+
+    def _device_logits(self, queries: Sequence[str], docs_per_query: Sequence[Sequence[str]]):  # noqa: ANN202
+        """The logits of the pairs (query b, each of its docs), in query and then doc order: the distinct strings tokenized once and the
+        rows assembled on the device, the n_pairs + 1 offsets read back, the packs cut by `_native_logits`' rule and every pack a slice of
+        the four arrays with its offsets rebased."""
+        import torch
+
+        from raglite_amd._encoder import MAX_PACK_TOKENS
+
+        ids, positions, type_ids, seq, seq_host = self.tokenizer.encode_pairs_device(queries, docs_per_query, self.max_length, self.shape)
+        lens = _lengths(seq_host)
+        native = self._native_encoder()
+        parts = []
+        for lo, hi in pack_runs(lens, min(self.pack_tokens, MAX_PACK_TOKENS)):
+            t0, t1 = int(seq_host[lo]), int(seq_host[hi])
+            parts.append(native.classify_pack_i32(ids[t0:t1], positions[t0:t1], seq[lo: hi + 1] - t0, type_ids[t0:t1], hi - lo, t1 - t0, max(lens[lo:hi])))
+        if not parts:
+            return torch.empty(0, dtype=torch.float32, device=self.device)
+        return parts[0] if len(parts) == 1 else torch.cat(parts)
+
     def logits(self, query: str, docs: Sequence[str]):  # noqa: ANN201
         """(len(docs),) float32 tensor of relevance logits on `self.device`."""
         import torch
 
+        if self._device_pairs_apply():
+            return self._device_logits([query], [list(docs)])
         pairs = self.encode_pairs(query, docs)
         if self._native_applies():
             return self._native_logits(pairs)
@@ -230,6 +265,12 @@ class TorchCrossEncoderRanker:
             raise ValueError("one list of docs per query is required")
         if not self._native_applies():
             return [self.logits(q, docs) for q, docs in zip(queries, docs_per_query)]
+        if self._device_pairs_apply():
+            bounds = [0]
+            for docs in docs_per_query:
+                bounds.append(bounds[-1] + len(docs))
+            flat = self._device_logits(queries, docs_per_query)
+            return [flat[lo:hi] for lo, hi in zip(bounds, bounds[1:])]
         pairs, bounds = [], [0]
         for q, docs in zip(queries, docs_per_query):
             pairs += self.encode_pairs(q, docs)

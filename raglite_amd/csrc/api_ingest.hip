@@ -1,11 +1,12 @@
 // The ingestion entry points of the C ABI: pooling and normalising token embeddings, the packed encoder's attention, the native
-// encoder forward for short packs and for packs of several token blocks (the one handle here, rl_encoder) and the document-batched
-// splitters (include/raglite_hip.h for the contract of each).
+// encoder forward for short packs and for packs of several token blocks (rl_encoder), the document-batched splitters and the WordPiece
+// tokenizer that feeds the cross-encoder (rl_wordpiece) (include/raglite_hip.h for the contract of each).
 #include <cmath>
 #include <string>
 
 #include "handles.h"
 #include "staging.h"
+#include "wordpiece_table.h"
 
 using namespace rl;
 
@@ -532,6 +533,309 @@ int rl_partition_sentences(const uint32_t* codepoints, const void* probas, int p
     void* d_scr;
     RL_TRY(st.temp(sentence_dp_scratch_bytes(n, n_docs), &d_scr));
     RL_TRY(launch_sentence_dp(d_cp, d_p, probas_f64, d_k, d_off, n, n_docs, min_len, max_len, d_cut, d_obj, d_status, d_scr, s));
+    return st.finish();
+}
+
+}  // extern "C"
+
+// ---- WordPiece on the device: texts -> token ids -> [CLS] q [SEP] d [SEP] rows (kernels in wordpiece.hip) ---------------
+struct rl_wordpiece {
+    std::mutex mu;
+    int hash_bits = 0;
+    int64_t n_table = 0, n_pieces = 0, n_slots = 0, table_bytes = 0;
+    int32_t max_piece = 0, unk_id = 0, max_word_chars = 0;
+    rl::DevArray<uint64_t> image;      // [n_table]
+    rl::DevArray<uint8_t> cls;         // [n_table]
+    rl::DevArray<uint32_t> piece_cp;   // the kept pieces' code points, back to back
+    rl::DevArray<int32_t> piece_off;   // [n_pieces + 1]
+    rl::DevArray<uint8_t> piece_flags; // [n_pieces]
+    rl::DevArray<int32_t> piece_ids;   // [n_pieces]
+    rl::DevArray<int32_t> slots;       // [n_slots]
+    // what the last rl_wordpiece_encode left (nothing until then)
+    bool encoded = false;
+    int64_t n_texts = 0, n_tokens = 0;
+    // device arrays of a call, kept between calls with amortised capacity
+    rl::Pool count, scan_scratch, sym, kind, start, head, ftext_off, word_pos, tmp, tok_count, ids, offsets, status, counters;
+    rl::LastStream last_stream;
+    rl::WpTable table() const { return {piece_cp, piece_off, piece_flags, slots, n_slots, hash_bits}; }
+};
+
+namespace {
+
+constexpr int64_t WP_MAX_CODEPOINTS = int64_t(1) << 28;  // per call: the expansion's scan keeps two fields in one int64 (wordpiece.hip)
+
+// the exclusive scan of data [n] in place and its total, copied to *total_host (valid after the next synchronisation of `s`)
+int wp_scan(rl::Pool& scratch, int64_t* data, int64_t n, int64_t* total_host, hipStream_t s, const char* who) {
+    RL_TRY(reserve_amortised(scratch, kb_scan_scratch_items(n) * sizeof(int64_t), who));
+    const int64_t* total = nullptr;
+    RL_TRY(launch_kb_exclusive_scan(data, n, scratch.as<int64_t>(), &total, s));
+    RL_TRY(hip_status(hipMemcpyAsync(total_host, total, sizeof(int64_t), hipMemcpyDeviceToHost, s), who));
+    return RL_OK;
+}
+
+int check_text_off(const std::string& who, const char* name, const int64_t* off, int64_t n_texts, int64_t n, bool ends_at_n) {
+    if (off[0] != 0) return fail(RL_ERR_INVALID, who + ": " + name + " must start at 0");
+    for (int64_t t = 0; t < n_texts; ++t)
+        if (off[t + 1] < off[t]) return fail(RL_ERR_INVALID, who + ": " + name + " must be ascending");
+    if (ends_at_n && off[n_texts] != n) return fail(RL_ERR_INVALID, who + ": " + name + " must end at n");
+    return RL_OK;
+}
+
+template <class T>
+int wp_upload(rl::DevArray<T>& dst, const T* src, size_t count, const char* who) {
+    RL_TRY(dst.alloc(std::max<size_t>(count * sizeof(T), 16), who));
+    if (count) RL_TRY(hip_status(hipMemcpy(dst.p, src, count * sizeof(T), hipMemcpyHostToDevice), who));
+    return RL_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int rl_wordpiece_create(rl_wordpiece** out, const uint64_t* image, const uint8_t* cls, int64_t n_table, const uint32_t* piece_cp,
+                        const int64_t* piece_off, const uint8_t* piece_flags, const int32_t* piece_ids, int64_t n_pieces, int32_t unk_id,
+                        int32_t max_word_chars, int32_t hash_bits) {
+    const std::string who = "rl_wordpiece_create";
+    if (!out) return fail(RL_ERR_INVALID, who + ": out is null");
+    *out = nullptr;
+    if (!image) return fail(RL_ERR_INVALID, who + ": image is null");
+    if (!cls) return fail(RL_ERR_INVALID, who + ": cls is null");
+    if (n_table < 1 || n_table > 0x110000) return fail(RL_ERR_INVALID, who + ": n_table must be in [1, 0x110000]");
+    if (n_pieces < 0 || n_pieces >= (int64_t(1) << 31)) return fail(RL_ERR_INVALID, who + ": n_pieces must be in [0, 2^31)");
+    if (!piece_off) return fail(RL_ERR_INVALID, who + ": piece_off is null");
+    if (n_pieces > 0 && (!piece_cp || !piece_flags || !piece_ids)) return fail(RL_ERR_INVALID, who + ": piece_cp, piece_flags or piece_ids is null");
+    if (unk_id < 0) return fail(RL_ERR_INVALID, who + ": unk_id must be >= 0");
+    if (max_word_chars < 1) return fail(RL_ERR_INVALID, who + ": max_word_chars must be >= 1");
+    if (max_word_chars > WP_MAX_WORD_CHARS) return fail(RL_ERR_UNSUPPORTED, who + ": max_word_chars must be <= 200");
+    if (hash_bits < 0 || hash_bits > 64) return fail(RL_ERR_INVALID, who + ": hash_bits must be 0 .. 64");
+    if (piece_off[0] != 0) return fail(RL_ERR_INVALID, who + ": piece_off must start at 0");
+    for (int64_t i = 0; i < n_pieces; ++i) {
+        if (piece_off[i + 1] < piece_off[i]) return fail(RL_ERR_INVALID, who + ": piece_off must be ascending");
+        if (piece_ids[i] < 0) return fail(RL_ERR_INVALID, who + ": piece_ids must be >= 0");
+    }
+    if (piece_off[n_pieces] >= (int64_t(1) << 31)) return fail(RL_ERR_UNSUPPORTED, who + ": the pieces must hold fewer than 2^31 code points");
+    for (int64_t i = 0; i < n_table; ++i) {  // every field a code point + 1, no symbol behind an empty field, nothing above the fields
+        uint64_t e = image[i];
+        bool ended = false;
+        for (int j = 0; j < WP_IMAGE_MAX; ++j, e >>= 21) {
+            const uint64_t f = e & 0x1FFFFFull;
+            if (f > 0x110000ull || (ended && f)) return fail(RL_ERR_INVALID, who + ": malformed image entry");
+            ended |= f == 0;
+        }
+        if (e) return fail(RL_ERR_INVALID, who + ": malformed image entry");
+        if ((cls[i] & ~7u) || (cls[i] & 3u) == 3u) return fail(RL_ERR_INVALID, who + ": malformed cls entry");
+    }
+    // the pieces a word can match: 1 .. max_word_chars code points (a longer word is unk_id before any lookup)
+    std::vector<uint32_t> h_cp;
+    std::vector<int32_t> h_off{0}, h_ids;
+    std::vector<uint8_t> h_flags;
+    int32_t longest = 0;
+    for (int64_t i = 0; i < n_pieces; ++i) {
+        const int64_t b = piece_off[i], len = piece_off[i + 1] - b;
+        if (len < 1 || len > max_word_chars) continue;
+        h_cp.insert(h_cp.end(), piece_cp + b, piece_cp + b + len);
+        h_off.push_back((int32_t)h_cp.size());
+        h_ids.push_back(piece_ids[i]);
+        h_flags.push_back(piece_flags[i] & 1u);
+        longest = std::max(longest, (int32_t)len);
+    }
+    const int64_t kept = (int64_t)h_ids.size(), n_slots = wp_table_slots(kept);
+    std::vector<int32_t> h_slots((size_t)n_slots, WP_EMPTY);
+    const WpTable host{h_cp.data(), h_off.data(), h_flags.data(), h_slots.data(), n_slots, hash_bits == 64 ? 0 : hash_bits};
+    for (int64_t i = 0; i < kept; ++i) (void)wp_table_insert(host, h_slots.data(), (int32_t)i);  // (of equal pieces the first stays)
+    std::unique_ptr<rl_wordpiece> t(new rl_wordpiece());
+    t->hash_bits = host.hash_bits;
+    t->n_table = n_table; t->n_pieces = kept; t->n_slots = n_slots;
+    t->max_piece = longest; t->unk_id = unk_id; t->max_word_chars = max_word_chars;
+    const char* w = "rl_wordpiece_create";
+    RL_TRY(wp_upload(t->image, image, (size_t)n_table, w));
+    RL_TRY(wp_upload(t->cls, cls, (size_t)n_table, w));
+    RL_TRY(wp_upload(t->piece_cp, const_cast<const uint32_t*>(h_cp.data()), h_cp.size(), w));
+    RL_TRY(wp_upload(t->piece_off, const_cast<const int32_t*>(h_off.data()), h_off.size(), w));
+    RL_TRY(wp_upload(t->piece_flags, const_cast<const uint8_t*>(h_flags.data()), h_flags.size(), w));
+    RL_TRY(wp_upload(t->piece_ids, const_cast<const int32_t*>(h_ids.data()), h_ids.size(), w));
+    RL_TRY(wp_upload(t->slots, const_cast<const int32_t*>(h_slots.data()), h_slots.size(), w));
+    t->table_bytes = (int64_t)(t->image.cap + t->cls.cap + t->piece_cp.cap + t->piece_off.cap + t->piece_flags.cap + t->piece_ids.cap + t->slots.cap);
+    *out = t.release();
+    return RL_OK;
+}
+
+int rl_wordpiece_destroy(rl_wordpiece* tok) {
+    delete tok;
+    return RL_OK;
+}
+
+int rl_wordpiece_info(rl_wordpiece* tok, int64_t out[4]) {
+    if (!tok) return fail(RL_ERR_INVALID, "rl_wordpiece_info: null handle");
+    if (!out) return fail(RL_ERR_INVALID, "rl_wordpiece_info: out is null");
+    std::lock_guard<std::mutex> lock(tok->mu);
+    int64_t bytes = tok->table_bytes;
+    for (const rl::Pool* p : {&tok->count, &tok->scan_scratch, &tok->sym, &tok->kind, &tok->start, &tok->head, &tok->ftext_off, &tok->word_pos, &tok->tmp,
+                              &tok->tok_count, &tok->ids, &tok->offsets, &tok->status, &tok->counters})
+        bytes += (int64_t)p->cap;
+    out[0] = tok->n_pieces;
+    out[1] = tok->max_piece;
+    out[2] = tok->n_slots;
+    out[3] = bytes;
+    return RL_OK;
+}
+
+int rl_wordpiece_encode(rl_wordpiece* tok, const uint32_t* codepoints, const int64_t* text_off, int64_t n, int64_t n_texts, int64_t out_counts[5],
+                        int mem, void* stream) {
+    const char* who = "rl_wordpiece_encode";
+    const std::string w(who);
+    if (!tok) return fail(RL_ERR_INVALID, w + ": null handle");
+    if (n < 0 || n_texts < 0) return fail(RL_ERR_INVALID, w + ": negative size");
+    RL_TRY(check_mem(mem, who));
+    if (!text_off) return fail(RL_ERR_INVALID, w + ": text_off is null");
+    if (!out_counts) return fail(RL_ERR_INVALID, w + ": out_counts is null");
+    if (n > 0 && !codepoints) return fail(RL_ERR_INVALID, w + ": codepoints is null");
+    if (n > 0 && n_texts < 1) return fail(RL_ERR_INVALID, w + ": code points without a text");
+    if (n >= WP_MAX_CODEPOINTS) return fail(RL_ERR_UNSUPPORTED, w + ": n must be < 2^28 code points in one call");
+    if (mem == RL_MEM_HOST) RL_TRY(check_text_off(w, "text_off", text_off, n_texts, n, true));
+    hipStream_t s = as_stream(stream);
+    std::lock_guard<std::mutex> lock(tok->mu);
+    RL_TRY(tok->last_stream.use(s));
+    tok->encoded = false;
+    Staging st(mem, s);
+    const uint32_t* d_cp;
+    const int64_t* d_off;
+    RL_TRY(st.in(codepoints, (size_t)n, &d_cp));
+    RL_TRY(st.in(text_off, (size_t)n_texts + 1, &d_off));
+    // 1. expand
+    RL_TRY(reserve_amortised(tok->count, (size_t)(n + 1) * sizeof(int64_t), who));
+    RL_TRY(reserve_amortised(tok->counters, 2 * sizeof(unsigned long long), who));
+    unsigned long long* counters = tok->counters.as<unsigned long long>();
+    RL_TRY(hip_status(hipMemsetAsync(counters, 0, 2 * sizeof(unsigned long long), s), who));
+    int64_t* scan = tok->count.as<int64_t>();
+    RL_TRY(launch_wp_expand_count(d_cp, n, tok->image, tok->cls, tok->n_table, scan, s));
+    int64_t packed = 0, n_words = 0, n_tokens = 0;
+    RL_TRY(wp_scan(tok->scan_scratch, scan, n + 1, &packed, s, who));
+    RL_TRY(hip_status(hipStreamSynchronize(s), who));
+    const int64_t m = packed & ((int64_t(1) << 32) - 1);
+    const size_t m_items = std::max<size_t>((size_t)m, 16);
+    RL_TRY(reserve_amortised(tok->sym, m_items * sizeof(uint32_t), who));
+    RL_TRY(reserve_amortised(tok->kind, m_items, who));
+    RL_TRY(reserve_amortised(tok->start, m_items, who));
+    RL_TRY(reserve_amortised(tok->tmp, m_items * sizeof(int32_t), who));
+    RL_TRY(reserve_amortised(tok->ids, m_items * sizeof(int32_t), who));  // (a word has at most as many pieces as symbols)
+    RL_TRY(reserve_amortised(tok->head, (size_t)(m + 1) * sizeof(int64_t), who));
+    RL_TRY(reserve_amortised(tok->ftext_off, (size_t)(n_texts + 1) * sizeof(int64_t), who));
+    RL_TRY(reserve_amortised(tok->offsets, (size_t)(n_texts + 1) * sizeof(int64_t), who));
+    RL_TRY(reserve_amortised(tok->status, std::max<size_t>((size_t)n_texts, 16), who));
+    RL_TRY(hip_status(hipMemsetAsync(tok->start.p, 0, m_items, s), who));
+    RL_TRY(launch_wp_expand_write(d_cp, n, tok->image, tok->cls, tok->n_table, scan, m, tok->sym.as<uint32_t>(), tok->kind.as<uint8_t>(), s));
+    RL_TRY(launch_wp_texts(d_off, n_texts, n, scan, m, tok->ftext_off.as<int64_t>(), tok->start.as<uint8_t>(), tok->status.as<uint8_t>(), counters, s));
+    // 2. words
+    RL_TRY(launch_wp_heads(tok->kind.as<uint8_t>(), tok->start.as<uint8_t>(), m, tok->head.as<int64_t>(), s));
+    RL_TRY(wp_scan(tok->scan_scratch, tok->head.as<int64_t>(), m + 1, &n_words, s, who));
+    RL_TRY(hip_status(hipStreamSynchronize(s), who));
+    // 3. match, 4. emit
+    RL_TRY(reserve_amortised(tok->word_pos, std::max<size_t>((size_t)n_words, 2) * sizeof(int64_t), who));
+    RL_TRY(reserve_amortised(tok->tok_count, (size_t)(n_words + 1) * sizeof(int64_t), who));
+    RL_TRY(launch_wp_match(tok->sym.as<uint32_t>(), tok->kind.as<uint8_t>(), tok->start.as<uint8_t>(), tok->head.as<int64_t>(), m, n_words, tok->table(),
+                           tok->piece_ids, tok->max_piece, tok->unk_id, tok->max_word_chars, tok->word_pos.as<int64_t>(), tok->tmp.as<int32_t>(),
+                           tok->tok_count.as<int64_t>(), counters, s));
+    RL_TRY(wp_scan(tok->scan_scratch, tok->tok_count.as<int64_t>(), n_words + 1, &n_tokens, s, who));
+    RL_TRY(launch_wp_emit(tok->word_pos.as<int64_t>(), tok->tok_count.as<int64_t>(), n_words, tok->tmp.as<int32_t>(), m, m, tok->ids.as<int32_t>(), s));
+    RL_TRY(launch_wp_offsets(tok->ftext_off.as<int64_t>(), n_texts, tok->head.as<int64_t>(), m, tok->tok_count.as<int64_t>(), n_words,
+                             tok->offsets.as<int64_t>(), s));
+    unsigned long long h_counters[2] = {0, 0};
+    RL_TRY(hip_status(hipMemcpyAsync(h_counters, counters, sizeof(h_counters), hipMemcpyDeviceToHost, s), who));
+    RL_TRY(hip_status(hipStreamSynchronize(s), who));
+    st.drain();  // (the stream has been synchronised above)
+    tok->n_texts = n_texts;
+    tok->n_tokens = n_tokens;
+    tok->encoded = true;
+    out_counts[0] = n_tokens;
+    out_counts[1] = n_words;
+    out_counts[2] = (int64_t)h_counters[WP_COUNT_UNK];
+    out_counts[3] = (int64_t)h_counters[WP_COUNT_FLAGGED];
+    out_counts[4] = m;
+    return RL_OK;
+}
+
+int rl_wordpiece_result(rl_wordpiece* tok, int32_t* ids, int64_t* offsets, uint8_t* status, int mem, void* stream) {
+    const char* who = "rl_wordpiece_result";
+    if (!tok) return fail(RL_ERR_INVALID, std::string(who) + ": null handle");
+    RL_TRY(check_mem(mem, who));
+    hipStream_t s = as_stream(stream);
+    std::lock_guard<std::mutex> lock(tok->mu);
+    if (!tok->encoded) return fail(RL_ERR_INVALID, std::string(who) + ": no rl_wordpiece_encode before it");
+    RL_TRY(tok->last_stream.use(s));
+    const hipMemcpyKind kind = mem == RL_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
+    if (ids && tok->n_tokens) RL_TRY(hip_status(hipMemcpyAsync(ids, tok->ids.p, (size_t)tok->n_tokens * sizeof(int32_t), kind, s), who));
+    if (offsets) RL_TRY(hip_status(hipMemcpyAsync(offsets, tok->offsets.p, (size_t)(tok->n_texts + 1) * sizeof(int64_t), kind, s), who));
+    if (status && tok->n_texts) RL_TRY(hip_status(hipMemcpyAsync(status, tok->status.p, (size_t)tok->n_texts, kind, s), who));
+    RL_TRY(hip_status(hipStreamSynchronize(s), who));
+    return RL_OK;
+}
+
+int rl_wordpiece_device(rl_wordpiece* tok, const int32_t** ids, const int64_t** offsets, const uint8_t** status) {
+    const char* who = "rl_wordpiece_device";
+    if (!tok) return fail(RL_ERR_INVALID, std::string(who) + ": null handle");
+    std::lock_guard<std::mutex> lock(tok->mu);
+    if (!tok->encoded) return fail(RL_ERR_INVALID, std::string(who) + ": no rl_wordpiece_encode before it");
+    if (ids) *ids = tok->ids.as<int32_t>();
+    if (offsets) *offsets = tok->offsets.as<int64_t>();
+    if (status) *status = tok->status.as<uint8_t>();
+    return RL_OK;
+}
+
+int rl_wordpiece_pairs(const int32_t* ids, const int64_t* tok_off, int64_t n_texts, const int32_t* query_text, const int32_t* doc_text, int64_t n_pairs,
+                       int32_t max_length, int32_t cls_id, int32_t sep_id, int32_t position_offset, int32_t* out_ids, int32_t* out_positions,
+                       int32_t* out_type_ids, int32_t* out_seq_offsets, int64_t* out_total, int mem, void* stream) {
+    const char* who = "rl_wordpiece_pairs";
+    const std::string w(who);
+    RL_TRY(check_mem(mem, who));
+    if (n_texts < 0 || n_pairs < 0) return fail(RL_ERR_INVALID, w + ": negative size");
+    if (n_pairs >= (int64_t(1) << 31) / 3) return fail(RL_ERR_UNSUPPORTED, w + ": one call takes fewer than 2^31 tokens");
+    if (max_length < 3) return fail(RL_ERR_INVALID, w + ": max_length must be >= 3");
+    if (!tok_off) return fail(RL_ERR_INVALID, w + ": tok_off is null");
+    if (!out_seq_offsets) return fail(RL_ERR_INVALID, w + ": out_seq_offsets is null");
+    if (!out_total) return fail(RL_ERR_INVALID, w + ": out_total is null");
+    if (n_pairs > 0 && !query_text) return fail(RL_ERR_INVALID, w + ": query_text is null");
+    if (n_pairs > 0 && !doc_text) return fail(RL_ERR_INVALID, w + ": doc_text is null");
+    const int given = (out_ids != nullptr) + (out_positions != nullptr) + (out_type_ids != nullptr);
+    if (given != 0 && given != 3) return fail(RL_ERR_INVALID, w + ": give out_ids, out_positions and out_type_ids, or none of them for the sizes alone");
+    if (given && n_pairs > 0 && !ids) return fail(RL_ERR_INVALID, w + ": ids is null");
+    int64_t n_tokens = 0;
+    if (mem == RL_MEM_HOST) {
+        RL_TRY(check_text_off(w, "tok_off", tok_off, n_texts, 0, false));
+        n_tokens = tok_off[n_texts];
+        for (int64_t p = 0; p < n_pairs; ++p) {
+            if (query_text[p] < 0 || query_text[p] >= n_texts) return fail(RL_ERR_INVALID, w + ": query_text holds an index outside [0, n_texts)");
+            if (doc_text[p] < 0 || doc_text[p] >= n_texts) return fail(RL_ERR_INVALID, w + ": doc_text holds an index outside [0, n_texts)");
+        }
+    }
+    hipStream_t s = as_stream(stream);
+    Staging st(mem, s);
+    const int64_t* d_off; const int32_t* d_q; const int32_t* d_d; const int32_t* d_ids = ids;
+    RL_TRY(st.in(tok_off, (size_t)n_texts + 1, &d_off));
+    RL_TRY(st.in(query_text, (size_t)n_pairs, &d_q));
+    RL_TRY(st.in(doc_text, (size_t)n_pairs, &d_d));
+    if (given && n_pairs > 0) RL_TRY(st.in(ids, (size_t)n_tokens, &d_ids));
+    int64_t* d_len; int64_t* d_scr;
+    RL_TRY(st.temp((size_t)(n_pairs + 1) * sizeof(int64_t), &d_len));
+    RL_TRY(st.temp(kb_scan_scratch_items(n_pairs + 1) * sizeof(int64_t), &d_scr));
+    RL_TRY(launch_wp_pair_lengths(d_off, n_texts, d_q, d_d, n_pairs, max_length, d_len, s));
+    const int64_t* d_total = nullptr;
+    RL_TRY(launch_kb_exclusive_scan(d_len, n_pairs + 1, d_scr, &d_total, s));
+    int64_t total = 0;
+    RL_TRY(hip_status(hipMemcpyAsync(&total, d_total, sizeof(int64_t), hipMemcpyDeviceToHost, s), who));
+    RL_TRY(hip_status(hipStreamSynchronize(s), who));
+    if (total >= (int64_t(1) << 31)) return fail(RL_ERR_UNSUPPORTED, w + ": one call takes fewer than 2^31 tokens");
+    *out_total = total;
+    int32_t* d_so;
+    RL_TRY(st.out(out_seq_offsets, (size_t)n_pairs + 1, &d_so));
+    RL_TRY(launch_wp_pair_offsets(d_len, n_pairs, d_so, s));
+    if (given) {
+        int32_t *d_oi, *d_op, *d_ot;
+        RL_TRY(st.out(out_ids, (size_t)total, &d_oi));
+        RL_TRY(st.out(out_positions, (size_t)total, &d_op));
+        RL_TRY(st.out(out_type_ids, (size_t)total, &d_ot));
+        RL_TRY(launch_wp_pair_write(d_ids, d_off, n_texts, d_q, d_d, n_pairs, max_length, cls_id, sep_id, position_offset, d_len, total, d_oi, d_op, d_ot, s));
+    }
     return st.finish();
 }
 

@@ -434,6 +434,37 @@ int launch_ka_emit(const int64_t* tok_len, const int64_t* tok_slot, const uint64
 int launch_ka_offsets(const int64_t* ftext_off, int64_t n_texts, const int64_t* tok_idx, int64_t m, const int64_t* kept_scan, int64_t n_tok,
                       int64_t* offsets /* [n_texts + 1] */, hipStream_t s);
 
+// wordpiece.hip: texts -> BERT WordPiece ids (rl_wordpiece_encode drives these in this order; the scans between them are
+// launch_kb_exclusive_scan's), and the [CLS] q [SEP] d [SEP] rows of text pairs (rl_wordpiece_pairs).  cp [n] UTF-32; image [n_table]:
+// a code point's normalised image, WP_IMAGE_MAX fields of 21 bits (code point + 1; 0 ends it); cls [n_table]: bits 0-1 the class of a
+// SYMBOL of the normalised stream (0 word character, 1 white space, 2 punctuation), bit 2 the context flag of an INPUT code point.
+constexpr int WP_IMAGE_MAX = 3;
+constexpr int WP_COUNT_UNK = 0, WP_COUNT_FLAGGED = 1;  // counters [2]: words that became unk_id, texts with status 1 (zero on entry)
+struct WpTable;                                        // wordpiece_table.h
+// count [n + 1]: symbols per code point, + (context flag << 32); scanned, its last entry is (m, flagged code points) in the two fields
+int launch_wp_expand_count(const uint32_t* cp, int64_t n, const uint64_t* image, const uint8_t* cls, int64_t n_table, int64_t* count, hipStream_t s);
+int launch_wp_expand_write(const uint32_t* cp, int64_t n, const uint64_t* image, const uint8_t* cls, int64_t n_table, const int64_t* scan, int64_t m,
+                           uint32_t* sym, uint8_t* kind, hipStream_t s);
+// ftext_off [n_texts + 1]; start [m] (zero on entry): 1 where a text begins; status [n_texts]: 1 = holds a flagged code point
+int launch_wp_texts(const int64_t* text_off, int64_t n_texts, int64_t n, const int64_t* scan, int64_t m, int64_t* ftext_off, uint8_t* start,
+                    uint8_t* status, unsigned long long* counters, hipStream_t s);
+int launch_wp_heads(const uint8_t* kind, const uint8_t* start, int64_t m, int64_t* head /* [m + 1], to be scanned: word_idx */, hipStream_t s);
+// word_pos [n_words]; tmp [m]: the ids of word w from tmp[word_pos[w]] on; tok_count [n_words + 1]: to be scanned (tok_scan)
+int launch_wp_match(const uint32_t* sym, const uint8_t* kind, const uint8_t* start, const int64_t* word_idx, int64_t m, int64_t n_words,
+                    const WpTable& table, const int32_t* piece_ids, int32_t max_piece, int32_t unk_id, int32_t max_word_chars, int64_t* word_pos,
+                    int32_t* tmp, int64_t* tok_count, unsigned long long* counters, hipStream_t s);
+int launch_wp_emit(const int64_t* word_pos, const int64_t* tok_scan, int64_t n_words, const int32_t* tmp, int64_t m, int64_t n_tokens, int32_t* ids,
+                   hipStream_t s);
+int launch_wp_offsets(const int64_t* ftext_off, int64_t n_texts, const int64_t* word_idx, int64_t m, const int64_t* tok_scan, int64_t n_words,
+                      int64_t* offsets /* [n_texts + 1] */, hipStream_t s);
+// len [n_pairs + 1]: the row length of every pair, to be scanned (row_scan); then the int32 offsets and the three token arrays
+int launch_wp_pair_lengths(const int64_t* tok_off, int64_t n_texts, const int32_t* query_text, const int32_t* doc_text, int64_t n_pairs, int32_t max_length,
+                           int64_t* len, hipStream_t s);
+int launch_wp_pair_offsets(const int64_t* row_scan, int64_t n_pairs, int32_t* seq_offsets, hipStream_t s);
+int launch_wp_pair_write(const int32_t* ids, const int64_t* tok_off, int64_t n_texts, const int32_t* query_text, const int32_t* doc_text, int64_t n_pairs,
+                         int32_t max_length, int32_t cls_id, int32_t sep_id, int32_t position_offset, const int64_t* row_scan, int64_t total,
+                         int32_t* out_ids, int32_t* out_positions, int32_t* out_type_ids, hipStream_t s);
+
 // fuse.hip: weighted Reciprocal Rank Fusion of n_lists ranked lists per query (lists [n_lists x n_queries x len] int32, < 0 = padding)
 // -> the top k by (float64 score desc, first occurrence asc), bit for bit the reference's reciprocal_rank_fusion
 constexpr int32_t RRF_MAX_LISTS = 4;
