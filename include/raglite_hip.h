@@ -1233,6 +1233,75 @@ int rl_wordpiece_pairs(const int32_t* ids, const int64_t* tok_off, int64_t n_tex
                        int32_t* out_positions, int32_t* out_type_ids, int32_t* out_seq_offsets, int64_t* out_total, int mem,
                        void* stream);
 
+/* ---- SentencePiece Unigram on the device: the embedder's tokenizer --------
+ * What a SentencePieceProcessor over a UNIGRAM model (normaliser with a precompiled character map,
+ * add_dummy_prefix, remove_extra_whitespaces, escape_whitespaces; no byte fallback, no user-defined
+ * pieces) does for many texts, on their UTF-32 code points: ids equal to sp.encode(text) of the model the
+ * tables were read from.  The library embeds neither Unicode data nor a vocabulary: rl_sentencepiece_create
+ * takes (all HOST pointers, copied)
+ *   image_off    int32[n_table]: where the normalised image of a code point begins in image_pool; < 0 = the
+ *                code point is its own image (as is every code point >= n_table)
+ *   image_len    uint8[n_table]: bits 0-6 the image's length in code points (0: it vanishes); bit 7 the
+ *                trailing-set flag of an input code point: the normaliser may consume it together with its
+ *                predecessor, so a text that holds one gets status 1 and its ids are NOT the contract's
+ *                (the caller tokenizes it elsewhere)
+ *   image_pool   uint32[n_pool]: the images' code points back to back
+ *   piece_cp     uint32: the matchable (NORMAL) pieces as UTF-32 back to back;  piece_off int64[n_pieces + 1]
+ *   piece_ids    int32[n_pieces] SentencePiece ids (>= 0);  piece_scores float[n_pieces] as stored (finite)
+ *                Empty pieces match nothing and are left out; of equal pieces the first stays; a piece of
+ *                more than 64 code points is RL_ERR_UNSUPPORTED (one lane of a wave per start)
+ *   unk_id       the SentencePiece id of the unknown piece;  unk_score = float(min score) - 10.f
+ *   hash_bits    0 or 64 = all; otherwise only that many low bits of the piece hash are used (tests
+ *                force collisions with it; results never depend on it: every hit compares code points)
+ * rl_sentencepiece_encode takes codepoints uint32[n] (UTF-32) and text_off int64[n_texts + 1] (a CSR over
+ * them), host or device by `mem`; nothing carries across a text boundary.  Per text: expand through the
+ * images; U+0020 of the expanded stream is white space: leading and trailing runs go, inner runs become one
+ * U+2581, one U+2581 stands in front of a text that is not empty then.  Over these symbols s[0..n) the best
+ * path: best[0] = 0; for every start i ascending and every length l ascending up to the longest piece, a
+ * piece s[i:i+l] offers score + best[i] (ONE float32 addition) to position i + l, taken if the position has
+ * no predecessor or the sum is strictly greater; where no piece of length 1 matched at i, the unknown piece
+ * offers unk_score + best[i] to i + 1 after the pieces.  The sum is carried across the WHOLE text.
+ * Backtracked from n, a run of consecutive unknowns is one id.  raw_ids = 1: SentencePiece ids, the unknown
+ * piece unk_id; raw_ids = 0: the XLM-RoBERTa layout, every id + 1 and the unknown piece 3.  It leaves ids
+ * int32[n_tokens], offsets int64[n_texts + 1], status uint8[n_texts], the normalised symbols uint32[n_symbols]
+ * and their per-text offsets int64[n_texts + 1] in device memory the handle owns until its next encode
+ * (rl_sentencepiece_device returns the pointers, NULL skips one; rl_sentencepiece_result copies the first
+ * three out, NULL skips one) and fills out_counts (HOST) = (n_tokens, n_symbols, unknown ids, texts with
+ * status 1, the longest text in symbols).  Synchronises `stream`.  Each phase is its own launch; one text
+ * per wave in the search; no float atomics, the only atomics are integer adds and one integer maximum of
+ * the counters; same bytes run to run and for host and device pointers.  Calls on one handle are
+ * serialised.  rl_sentencepiece_info: out = (pieces kept, longest piece, table slots, device bytes held).
+ * RL_ERR_INVALID before any HIP call: a null handle or pointer, n_table outside [1, 0x110000], an image
+ * outside the pool, a pool entry that is no code point, piece_off that does not start at 0 or ascend, a
+ * negative id or size, a score that is not finite, hash_bits outside 0 .. 64, raw_ids outside {0, 1}, code
+ * points without a text, and for RL_MEM_HOST text_off that does not start at 0 / ascend / end at n.
+ * RL_ERR_UNSUPPORTED: n >= 2^25 code points or 2^31 symbols in one call.
+ *
+ * rl_sentencepiece_rows is a free function over ANY token lists (ids int32, tok_off int64[n_texts + 1]):
+ *   row t     = bos_id, the first min(tokens of t, max_len - 2) ids of text t, eos_id
+ *   positions = position_offset + 0, 1, ...
+ *   out_seq_offsets int32[n_texts + 1], *out_total (HOST) = the rows' tokens
+ * -- the arrays rl_encoder_forward / rl_encoder_forward_pack take.  With out_ids and out_positions both NULL
+ * only the offsets and the total are computed (what a caller sizes the two by).  Synchronises `stream`.
+ * RL_ERR_INVALID before any HIP call: bad mem, a negative size, max_len < 2, a null tok_off /
+ * out_seq_offsets / out_total, one of the two outputs without the other, null ids with outputs, and for
+ * RL_MEM_HOST tok_off that does not start at 0 or ascend.  RL_ERR_UNSUPPORTED: 2^31 tokens or more. */
+typedef struct rl_sentencepiece rl_sentencepiece;
+int rl_sentencepiece_create(rl_sentencepiece** out, const int32_t* image_off, const uint8_t* image_len, int64_t n_table,
+                            const uint32_t* image_pool, int64_t n_pool, const uint32_t* piece_cp, const int64_t* piece_off,
+                            const int32_t* piece_ids, const float* piece_scores, int64_t n_pieces, int32_t unk_id, float unk_score,
+                            int32_t hash_bits);
+int rl_sentencepiece_destroy(rl_sentencepiece* tok);
+int rl_sentencepiece_info(rl_sentencepiece* tok, int64_t out[4]);
+int rl_sentencepiece_encode(rl_sentencepiece* tok, const uint32_t* codepoints, const int64_t* text_off, int64_t n, int64_t n_texts,
+                            int32_t raw_ids, int64_t out_counts[5], int mem, void* stream);
+int rl_sentencepiece_result(rl_sentencepiece* tok, int32_t* ids, int64_t* offsets, uint8_t* status, int mem, void* stream);
+int rl_sentencepiece_device(rl_sentencepiece* tok, const int32_t** ids, const int64_t** offsets, const uint8_t** status,
+                            const uint32_t** symbols, const int64_t** symbol_offsets);
+int rl_sentencepiece_rows(const int32_t* ids, const int64_t* tok_off, int64_t n_texts, int32_t max_len, int32_t bos_id, int32_t eos_id,
+                          int32_t position_offset, int32_t* out_ids, int32_t* out_positions, int32_t* out_seq_offsets,
+                          int64_t* out_total, int mem, void* stream);
+
 /* What the last bound-filtered search on this index did (diagnostic; bench.py reports it next to every timed number that depends
  * on it).  The searches that rank on approximate scores and re-score what a rigorous bound cannot rule out -- rl_maxsim_topk_batch
  * over the HI image, rl_search_rows for B <= 16 over the HI plane, the fused top-k of B >= 96 -- keep per-query candidate lists of a

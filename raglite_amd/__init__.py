@@ -97,6 +97,7 @@ from raglite_amd._comm import Communicator
 from raglite_amd._attention import attention_varlen
 from raglite_amd._encoder import NativeEncoder
 from raglite_amd._wordpiece import DeviceWordPiece, WordPieceTables
+from raglite_amd._sentencepiece import DeviceSentencePiece, UnigramTables
 from raglite_amd._sharded import ShardedIndex, merge_topk_host, shard_bounds_by_chunk
 
 __all__ = [
@@ -146,5 +147,6 @@ __all__ = [
     "synth_fill", "topk", "vector_search",
     "attention_varlen", "embed_strings_batch", "NativeEncoder",
     "DeviceWordPiece", "WordPieceTables",
+    "DeviceSentencePiece", "UnigramTables",
 ]
 __version__ = "0.1.0"

@@ -91,6 +91,14 @@ _SIGNATURES = {
     "rl_wordpiece_device": [c_void_p, C.POINTER(c_void_p), C.POINTER(c_void_p), C.POINTER(c_void_p)],
     "rl_wordpiece_pairs": [c_void_p, c_void_p, c_i64, c_void_p, c_void_p, c_i64, c_i32, c_i32, c_i32, c_i32, c_void_p, c_void_p, c_void_p,
                            c_void_p, c_void_p, c_int, c_void_p],
+    "rl_sentencepiece_create": [C.POINTER(c_void_p), c_void_p, c_void_p, c_i64, c_void_p, c_i64, c_void_p, c_void_p, c_void_p, c_void_p, c_i64, c_i32,
+                                C.c_float, c_i32],
+    "rl_sentencepiece_destroy": [c_void_p],
+    "rl_sentencepiece_info": [c_void_p, c_void_p],
+    "rl_sentencepiece_encode": [c_void_p, c_void_p, c_void_p, c_i64, c_i64, c_i32, c_void_p, c_int, c_void_p],
+    "rl_sentencepiece_result": [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p],
+    "rl_sentencepiece_device": [c_void_p, C.POINTER(c_void_p), C.POINTER(c_void_p), C.POINTER(c_void_p), C.POINTER(c_void_p), C.POINTER(c_void_p)],
+    "rl_sentencepiece_rows": [c_void_p, c_void_p, c_i64, c_i32, c_i32, c_i32, c_i32, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p],
     "rl_adapter_apply": [c_void_p, c_void_p, c_i32, c_i32, c_void_p, c_void_p, c_int, c_void_p],
     "rl_adapter_apply_rows": [c_void_p, c_void_p, c_i32, c_i32, c_void_p, c_void_p, c_int, c_void_p],
     "rl_score_gemm": [c_void_p, c_i64, c_i32, c_void_p, c_i32, c_int, c_void_p, c_void_p, C.c_float, c_i32, c_i32, c_void_p, c_i64, c_void_p,

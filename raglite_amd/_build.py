@@ -27,6 +27,7 @@ SOURCES = [
     "encoder.hip",  # the native encoder forward for short packs
     "encoder_head.hip",  # the cross-encoder's pooler + classifier head on its final rows
     "wordpiece.hip",  # the cross-encoder's tokenizer: BERT WordPiece and pair assembly
+    "sentencepiece.hip",  # the embedder's tokenizer: SentencePiece Unigram and row assembly
     "adapter_fit.hip", "query_targets.hip",  # query adapter
     "keyword.hip", "keyword_build.hip", "keyword_analyze.hip",  # BM25
     "fuse.hip", "rerank.hip", "spans.hip", "metadata.hip",  # fusion, rerank order, spans, metadata filters

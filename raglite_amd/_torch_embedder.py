@@ -387,10 +387,17 @@ class TorchTokenEmbedder:
         self.embed_calls += 1
         single = isinstance(text, str)
         texts = [text] if single else list(text)
-        rows = []
-        for t in texts:
-            ids = self.tokenizer.encode(t)[: self.shape.n_ctx - 2]
-            rows.append([self.shape.bos_id, *ids, self.shape.eos_id])
+        dev = self._device_rows(texts)
+        if dev is not None:  # (the tokenizer assembled the rows on the device; only their offsets came back)
+            mats = self._embed_device_rows(*dev)
+            if mats is not None:
+                return mats[0] if single else mats
+            rows = self._rows_from_device(dev[0], dev[3])  # the padded route: the id lists it always took
+        else:
+            rows = []
+            for t in texts:
+                ids = self.tokenizer.encode(t)[: self.shape.n_ctx - 2]
+                rows.append([self.shape.bos_id, *ids, self.shape.eos_id])
         # Lengths stay on the HOST and the ids go up from pinned memory without blocking: nothing in this call waits for the device, so the
         # caller tokenises the next segment while the GPU is still in this one (a `.to(device)` from pageable memory and `int(tensor)`
         # each waited for the whole forward pass: 8 ms of idle GPU per 7.8 k-token segment)
@@ -413,6 +420,44 @@ class TorchTokenEmbedder:
             out = self.encoder(ids, lengths, all_full=min(lens) == T).float()
         mats = [out[i, : lens[i]] for i in range(len(rows))]
         return mats[0] if single else mats
+
+    def _device_rows(self, texts: Sequence[str]) -> tuple | None:
+        """(ids, positions, seq_offsets, seq_offsets_host) of the rows `<s> ids[: n_ctx - 2] </s>` from a tokenizer that assembles them
+        on the device (`DeviceSentencePiece.rows_device`), or None: every other tokenizer runs the code it ran before."""
+        if self.device.type != "cuda" or not hasattr(self.tokenizer, "rows_device") or not texts:
+            return None
+        return self.tokenizer.rows_device(texts, self.shape)
+
+    @staticmethod
+    def _rows_from_device(ids: Any, seq_host: Any) -> list[list[int]]:
+        flat = ids.cpu().tolist()
+        return [flat[int(a): int(b)] for a, b in zip(seq_host[:-1], seq_host[1:])]
+
+    def _embed_device_rows(self, ids: Any, positions: Any, seq: Any, seq_host: Any) -> list | None:
+        """`_embed_native`, then `_embed_packed`, on rows that are on the device already: the same decisions from the rows' offsets, the
+        same forwards on the same ids, so the same bits.  None where neither route applies (the padded batch)."""
+        import torch
+
+        from raglite_amd._encoder import NativeEncoder
+
+        lens = [int(b) - int(a) for a, b in zip(seq_host[:-1], seq_host[1:])]
+        n = int(seq_host[-1])
+        w = self.encoder.ln.weight
+        if self.short_forward == "native" and not self.shape.classifier and NativeEncoder.supports(self.shape, w.dtype, n, w.device):
+            if self._native is None or self._native.module is not self.encoder:
+                self._native = NativeEncoder(self.encoder, self.shape)
+            with torch.inference_mode():
+                out = self._native.forward_i32(ids, positions, seq, None, len(lens), n, max(lens)).float()
+            return list(torch.split(out, lens))
+        if self.batching != "packed":
+            return None
+        mats: list = []
+        for lo, hi in pack_runs(lens, self.pack_tokens):
+            t0, t1 = int(seq_host[lo]), int(seq_host[hi])
+            with torch.inference_mode():
+                out = self.encoder.forward_packed(ids[t0:t1].long(), seq[lo: hi + 1] - t0, lens[lo:hi]).float()
+            mats.extend(torch.split(out, lens[lo:hi]))
+        return mats
 
     def _embed_native(self, rows: list[list[int]]) -> list | None:
         """The strings of a call as one pack through the HIP forward, or None where it does not take them (too many tokens, a CPU,
@@ -445,8 +490,13 @@ class TorchTokenEmbedder:
         texts = list(texts)
         if not texts:
             return []
-        rows = [[self.shape.bos_id, *self.tokenizer.encode(t)[: self.shape.n_ctx - 2], self.shape.eos_id] for t in texts]
-        lens = [len(r) for r in rows]
+        dev = self._device_rows(texts)
+        if dev is not None:
+            ids, positions, seq, seq_host = dev
+            lens = [int(b) - int(a) for a, b in zip(seq_host[:-1], seq_host[1:])]
+        else:
+            rows = [[self.shape.bos_id, *self.tokenizer.encode(t)[: self.shape.n_ctx - 2], self.shape.eos_id] for t in texts]
+            lens = [len(r) for r in rows]
         w = self.encoder.ln.weight
         if max(lens) > MAX_TOKENS or not NativeEncoder.supports_pack(self.shape, w.dtype, min(sum(lens), MAX_PACK_TOKENS), w.device):
             return None
@@ -456,7 +506,12 @@ class TorchTokenEmbedder:
         mats: list = []
         for lo, hi in pack_runs(lens, MAX_PACK_TOKENS):
             with torch.inference_mode():
-                out = self._native.forward_pack_rows(rows[lo:hi]).float()
+                if dev is not None:
+                    t0, t1 = int(seq_host[lo]), int(seq_host[hi])
+                    out = self._native.forward_pack_i32(ids[t0:t1], positions[t0:t1], (seq[lo: hi + 1] - t0).contiguous(), None, hi - lo, t1 - t0,
+                                                        max(lens[lo:hi])).float()
+                else:
+                    out = self._native.forward_pack_rows(rows[lo:hi]).float()
             mats.extend(torch.split(out, lens[lo:hi]))
         return mats
 

@@ -840,3 +840,277 @@ int rl_wordpiece_pairs(const int32_t* ids, const int64_t* tok_off, int64_t n_tex
 }
 
 }  // extern "C"
+
+// ---- SentencePiece Unigram on the device: texts -> token ids -> bos ids eos rows (kernels in sentencepiece.hip) ----------
+namespace {
+
+constexpr int64_t SP_MAX_SYMBOLS = int64_t(1) << 31;     // per call: back-pointers and row offsets are int32
+constexpr int64_t SP_MAX_CODEPOINTS = int64_t(1) << 25;  // per call: times SP_MAX_IMAGE symbols each, the expansion's scan keeps its low field
+static_assert(SP_MAX_CODEPOINTS * rl::SP_MAX_IMAGE < (int64_t(1) << 32), "the symbol count of a call fits the scan's low field");
+
+const rl::Pool* const* sp_pools(const rl_sentencepiece* t, size_t* n) {
+    static thread_local const rl::Pool* pools[16];
+    const rl::Pool* all[] = {&t->count, &t->scan_scratch, &t->raw, &t->start, &t->rtext_off, &t->keep, &t->sym, &t->sym_off,
+                             &t->bp_start, &t->bp_id, &t->tmp, &t->tok_count, &t->ids, &t->offsets, &t->status, &t->counters};
+    *n = sizeof(all) / sizeof(all[0]);
+    for (size_t i = 0; i < *n; ++i) pools[i] = all[i];
+    return pools;
+}
+
+}  // namespace
+
+extern "C" {
+
+int rl_sentencepiece_create(rl_sentencepiece** out, const int32_t* image_off, const uint8_t* image_len, int64_t n_table, const uint32_t* image_pool,
+                            int64_t n_pool, const uint32_t* piece_cp, const int64_t* piece_off, const int32_t* piece_ids, const float* piece_scores,
+                            int64_t n_pieces, int32_t unk_id, float unk_score, int32_t hash_bits) {
+    const std::string who = "rl_sentencepiece_create";
+    if (!out) return fail(RL_ERR_INVALID, who + ": out is null");
+    *out = nullptr;
+    if (!image_off) return fail(RL_ERR_INVALID, who + ": image_off is null");
+    if (!image_len) return fail(RL_ERR_INVALID, who + ": image_len is null");
+    if (n_table < 1 || n_table > 0x110000) return fail(RL_ERR_INVALID, who + ": n_table must be in [1, 0x110000]");
+    if (n_pool < 0 || n_pool >= (int64_t(1) << 31)) return fail(RL_ERR_INVALID, who + ": n_pool must be in [0, 2^31)");
+    if (n_pool > 0 && !image_pool) return fail(RL_ERR_INVALID, who + ": image_pool is null");
+    if (n_pieces < 0 || n_pieces >= (int64_t(1) << 31)) return fail(RL_ERR_INVALID, who + ": n_pieces must be in [0, 2^31)");
+    if (!piece_off) return fail(RL_ERR_INVALID, who + ": piece_off is null");
+    if (n_pieces > 0 && (!piece_cp || !piece_ids || !piece_scores)) return fail(RL_ERR_INVALID, who + ": piece_cp, piece_ids or piece_scores is null");
+    if (unk_id < 0) return fail(RL_ERR_INVALID, who + ": unk_id must be >= 0");
+    if (!std::isfinite(unk_score)) return fail(RL_ERR_INVALID, who + ": unk_score must be finite");
+    if (hash_bits < 0 || hash_bits > 64) return fail(RL_ERR_INVALID, who + ": hash_bits must be 0 .. 64");
+    if (piece_off[0] != 0) return fail(RL_ERR_INVALID, who + ": piece_off must start at 0");
+    for (int64_t i = 0; i < n_pieces; ++i) {
+        if (piece_off[i + 1] < piece_off[i]) return fail(RL_ERR_INVALID, who + ": piece_off must be ascending");
+        if (piece_off[i + 1] - piece_off[i] > SP_MAX_PIECE) return fail(RL_ERR_UNSUPPORTED, who + ": a piece must have at most 64 code points");
+        if (piece_ids[i] < 0) return fail(RL_ERR_INVALID, who + ": piece_ids must be >= 0");
+        if (!std::isfinite(piece_scores[i])) return fail(RL_ERR_INVALID, who + ": piece_scores must be finite");
+    }
+    if (piece_off[n_pieces] >= (int64_t(1) << 31)) return fail(RL_ERR_UNSUPPORTED, who + ": the pieces must hold fewer than 2^31 code points");
+    for (int64_t i = 0; i < n_table; ++i) {  // an image lies inside the pool and holds code points
+        if (image_off[i] < 0) continue;
+        const int64_t len = image_len[i] & 0x7F;
+        if ((int64_t)image_off[i] + len > n_pool) return fail(RL_ERR_INVALID, who + ": malformed image entry");
+    }
+    for (int64_t i = 0; i < n_pool; ++i)
+        if (image_pool[i] >= 0x110000u) return fail(RL_ERR_INVALID, who + ": malformed image_pool entry");
+    // the pieces a span can match: at least one code point
+    std::vector<uint32_t> h_cp;
+    std::vector<int32_t> h_off{0}, h_ids;
+    std::vector<float> h_scores;
+    int32_t longest = 0;
+    for (int64_t i = 0; i < n_pieces; ++i) {
+        const int64_t b = piece_off[i], len = piece_off[i + 1] - b;
+        if (len < 1) continue;
+        h_cp.insert(h_cp.end(), piece_cp + b, piece_cp + b + len);
+        h_off.push_back((int32_t)h_cp.size());
+        h_ids.push_back(piece_ids[i]);
+        h_scores.push_back(piece_scores[i]);
+        longest = std::max(longest, (int32_t)len);
+    }
+    const int64_t kept = (int64_t)h_ids.size(), n_slots = wp_table_slots(kept);
+    std::vector<uint8_t> h_flags((size_t)kept, 0);
+    std::vector<int32_t> h_slots((size_t)n_slots, WP_EMPTY);
+    const WpTable host{h_cp.data(), h_off.data(), h_flags.data(), h_slots.data(), n_slots, hash_bits == 64 ? 0 : hash_bits};
+    for (int64_t i = 0; i < kept; ++i) (void)wp_table_insert(host, h_slots.data(), (int32_t)i);  // (of equal pieces the first stays)
+    std::unique_ptr<rl_sentencepiece> t(new rl_sentencepiece());
+    t->hash_bits = host.hash_bits;
+    t->n_table = n_table; t->n_pool = n_pool; t->n_pieces = kept; t->n_slots = n_slots;
+    t->longest = std::max(longest, 1); t->unk_id = unk_id; t->unk_score = unk_score;
+    const char* w = "rl_sentencepiece_create";
+    RL_TRY(wp_upload(t->image_off, image_off, (size_t)n_table, w));
+    RL_TRY(wp_upload(t->image_len, image_len, (size_t)n_table, w));
+    RL_TRY(wp_upload(t->image_pool, image_pool, (size_t)n_pool, w));
+    RL_TRY(wp_upload(t->piece_cp, const_cast<const uint32_t*>(h_cp.data()), h_cp.size(), w));
+    RL_TRY(wp_upload(t->piece_off, const_cast<const int32_t*>(h_off.data()), h_off.size(), w));
+    RL_TRY(wp_upload(t->piece_flags, const_cast<const uint8_t*>(h_flags.data()), h_flags.size(), w));
+    RL_TRY(wp_upload(t->piece_ids, const_cast<const int32_t*>(h_ids.data()), h_ids.size(), w));
+    RL_TRY(wp_upload(t->piece_scores, const_cast<const float*>(h_scores.data()), h_scores.size(), w));
+    RL_TRY(wp_upload(t->slots, const_cast<const int32_t*>(h_slots.data()), h_slots.size(), w));
+    t->table_bytes = (int64_t)(t->image_off.cap + t->image_len.cap + t->image_pool.cap + t->piece_cp.cap + t->piece_off.cap + t->piece_flags.cap +
+                               t->piece_ids.cap + t->piece_scores.cap + t->slots.cap);
+    *out = t.release();
+    return RL_OK;
+}
+
+int rl_sentencepiece_destroy(rl_sentencepiece* tok) {
+    delete tok;
+    return RL_OK;
+}
+
+int rl_sentencepiece_info(rl_sentencepiece* tok, int64_t out[4]) {
+    if (!tok) return fail(RL_ERR_INVALID, "rl_sentencepiece_info: null handle");
+    if (!out) return fail(RL_ERR_INVALID, "rl_sentencepiece_info: out is null");
+    std::lock_guard<std::mutex> lock(tok->mu);
+    int64_t bytes = tok->table_bytes;
+    size_t n_pools = 0;
+    const rl::Pool* const* pools = sp_pools(tok, &n_pools);
+    for (size_t i = 0; i < n_pools; ++i) bytes += (int64_t)pools[i]->cap;
+    out[0] = tok->n_pieces;
+    out[1] = tok->longest;
+    out[2] = tok->n_slots;
+    out[3] = bytes;
+    return RL_OK;
+}
+
+int rl_sentencepiece_encode(rl_sentencepiece* tok, const uint32_t* codepoints, const int64_t* text_off, int64_t n, int64_t n_texts, int32_t raw_ids,
+                            int64_t out_counts[5], int mem, void* stream) {
+    const char* who = "rl_sentencepiece_encode";
+    const std::string w(who);
+    if (!tok) return fail(RL_ERR_INVALID, w + ": null handle");
+    if (n < 0 || n_texts < 0) return fail(RL_ERR_INVALID, w + ": negative size");
+    RL_TRY(check_mem(mem, who));
+    if (raw_ids != 0 && raw_ids != 1) return fail(RL_ERR_INVALID, w + ": raw_ids must be 0 or 1");
+    if (!text_off) return fail(RL_ERR_INVALID, w + ": text_off is null");
+    if (!out_counts) return fail(RL_ERR_INVALID, w + ": out_counts is null");
+    if (n > 0 && !codepoints) return fail(RL_ERR_INVALID, w + ": codepoints is null");
+    if (n > 0 && n_texts < 1) return fail(RL_ERR_INVALID, w + ": code points without a text");
+    if (n >= SP_MAX_CODEPOINTS) return fail(RL_ERR_UNSUPPORTED, w + ": n must be < 2^25 code points in one call");
+    if (n_texts >= (int64_t(1) << 31) - 1) return fail(RL_ERR_UNSUPPORTED, w + ": n_texts must be < 2^31 - 1 in one call");
+    if (mem == RL_MEM_HOST) RL_TRY(check_text_off(w, "text_off", text_off, n_texts, n, true));
+    hipStream_t s = as_stream(stream);
+    std::lock_guard<std::mutex> lock(tok->mu);
+    RL_TRY(tok->last_stream.use(s));
+    tok->encoded = false;
+    Staging st(mem, s);
+    const uint32_t* d_cp;
+    const int64_t* d_off;
+    RL_TRY(st.in(codepoints, (size_t)n, &d_cp));
+    RL_TRY(st.in(text_off, (size_t)n_texts + 1, &d_off));
+    const rl::SpImage image = tok->image();
+    // 1. expand
+    RL_TRY(reserve_amortised(tok->count, (size_t)(n + 1) * sizeof(int64_t), who));
+    RL_TRY(reserve_amortised(tok->counters, SP_COUNTERS * sizeof(unsigned long long), who));
+    unsigned long long* counters = tok->counters.as<unsigned long long>();
+    RL_TRY(hip_status(hipMemsetAsync(counters, 0, SP_COUNTERS * sizeof(unsigned long long), s), who));
+    int64_t* scan = tok->count.as<int64_t>();
+    RL_TRY(launch_sp_expand_count(d_cp, n, image, scan, s));
+    int64_t packed = 0, m = 0, n_tokens = 0;
+    RL_TRY(wp_scan(tok->scan_scratch, scan, n + 1, &packed, s, who));
+    RL_TRY(hip_status(hipStreamSynchronize(s), who));
+    const int64_t m0 = packed & ((int64_t(1) << 32) - 1);  // (n < 2^25 code points of at most 127 symbols: the field cannot overflow)
+    if (m0 >= SP_MAX_SYMBOLS) return fail(RL_ERR_UNSUPPORTED, w + ": one call takes fewer than 2^31 symbols");
+    const size_t m0_items = std::max<size_t>((size_t)m0, 16);
+    RL_TRY(reserve_amortised(tok->raw, m0_items * sizeof(uint32_t), who));
+    RL_TRY(reserve_amortised(tok->start, m0_items + 1, who));
+    RL_TRY(reserve_amortised(tok->keep, (size_t)(m0 + 1) * sizeof(int64_t), who));
+    RL_TRY(reserve_amortised(tok->rtext_off, (size_t)(n_texts + 1) * sizeof(int64_t), who));
+    RL_TRY(reserve_amortised(tok->sym_off, (size_t)(n_texts + 1) * sizeof(int64_t), who));
+    RL_TRY(reserve_amortised(tok->tok_count, (size_t)(n_texts + 1) * sizeof(int64_t), who));
+    RL_TRY(reserve_amortised(tok->offsets, (size_t)(n_texts + 1) * sizeof(int64_t), who));
+    RL_TRY(reserve_amortised(tok->status, std::max<size_t>((size_t)n_texts, 16), who));
+    RL_TRY(hip_status(hipMemsetAsync(tok->start.p, 0, m0_items + 1, s), who));
+    RL_TRY(launch_sp_expand_write(d_cp, n, image, scan, m0, tok->raw.as<uint32_t>(), s));
+    RL_TRY(launch_sp_texts(d_off, n_texts, n, scan, m0, tok->rtext_off.as<int64_t>(), tok->start.as<uint8_t>(), tok->status.as<uint8_t>(), counters, s));
+    // 2. the white-space rule
+    RL_TRY(launch_sp_keep_count(tok->raw.as<uint32_t>(), tok->start.as<uint8_t>(), m0, tok->keep.as<int64_t>(), s));
+    RL_TRY(wp_scan(tok->scan_scratch, tok->keep.as<int64_t>(), m0 + 1, &m, s, who));
+    RL_TRY(hip_status(hipStreamSynchronize(s), who));
+    if (m >= SP_MAX_SYMBOLS) return fail(RL_ERR_UNSUPPORTED, w + ": one call takes fewer than 2^31 symbols");
+    const size_t m_items = std::max<size_t>((size_t)m, 16);
+    RL_TRY(reserve_amortised(tok->sym, m_items * sizeof(uint32_t), who));
+    RL_TRY(reserve_amortised(tok->bp_start, m_items * sizeof(int32_t), who));
+    RL_TRY(reserve_amortised(tok->bp_id, m_items * sizeof(int32_t), who));
+    RL_TRY(reserve_amortised(tok->tmp, m_items * sizeof(int32_t), who));
+    RL_TRY(reserve_amortised(tok->ids, m_items * sizeof(int32_t), who));  // (a text has at most as many ids as symbols)
+    RL_TRY(launch_sp_keep_write(tok->raw.as<uint32_t>(), tok->start.as<uint8_t>(), m0, tok->keep.as<int64_t>(), m, tok->rtext_off.as<int64_t>(), n_texts,
+                                tok->sym.as<uint32_t>(), tok->sym_off.as<int64_t>(), counters, s));
+    // 3. search, 4. emit
+    RL_TRY(launch_sp_viterbi(tok->sym.as<uint32_t>(), tok->sym_off.as<int64_t>(), n_texts, m, tok->table(), tok->longest, tok->unk_score,
+                             tok->bp_start.as<int32_t>(), tok->bp_id.as<int32_t>(), tok->tmp.as<int32_t>(), tok->tok_count.as<int64_t>(), counters, s));
+    RL_TRY(wp_scan(tok->scan_scratch, tok->tok_count.as<int64_t>(), n_texts + 1, &n_tokens, s, who));
+    RL_TRY(launch_sp_emit(tok->tmp.as<int32_t>(), tok->sym_off.as<int64_t>(), tok->tok_count.as<int64_t>(), n_texts, m, m, raw_ids ? 0 : 1,
+                          raw_ids ? tok->unk_id : 3, tok->ids.as<int32_t>(), tok->offsets.as<int64_t>(), s));
+    unsigned long long h_counters[SP_COUNTERS] = {0, 0, 0};
+    RL_TRY(hip_status(hipMemcpyAsync(h_counters, counters, sizeof(h_counters), hipMemcpyDeviceToHost, s), who));
+    RL_TRY(hip_status(hipStreamSynchronize(s), who));
+    st.drain();  // (the stream has been synchronised above)
+    tok->n_texts = n_texts;
+    tok->n_tokens = n_tokens;
+    tok->encoded = true;
+    out_counts[0] = n_tokens;
+    out_counts[1] = m;
+    out_counts[2] = (int64_t)h_counters[SP_COUNT_UNK];
+    out_counts[3] = (int64_t)h_counters[SP_COUNT_FLAGGED];
+    out_counts[4] = (int64_t)h_counters[SP_COUNT_LONGEST];
+    return RL_OK;
+}
+
+int rl_sentencepiece_result(rl_sentencepiece* tok, int32_t* ids, int64_t* offsets, uint8_t* status, int mem, void* stream) {
+    const char* who = "rl_sentencepiece_result";
+    if (!tok) return fail(RL_ERR_INVALID, std::string(who) + ": null handle");
+    RL_TRY(check_mem(mem, who));
+    hipStream_t s = as_stream(stream);
+    std::lock_guard<std::mutex> lock(tok->mu);
+    if (!tok->encoded) return fail(RL_ERR_INVALID, std::string(who) + ": no rl_sentencepiece_encode before it");
+    RL_TRY(tok->last_stream.use(s));
+    const hipMemcpyKind kind = mem == RL_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
+    if (ids && tok->n_tokens) RL_TRY(hip_status(hipMemcpyAsync(ids, tok->ids.p, (size_t)tok->n_tokens * sizeof(int32_t), kind, s), who));
+    if (offsets) RL_TRY(hip_status(hipMemcpyAsync(offsets, tok->offsets.p, (size_t)(tok->n_texts + 1) * sizeof(int64_t), kind, s), who));
+    if (status && tok->n_texts) RL_TRY(hip_status(hipMemcpyAsync(status, tok->status.p, (size_t)tok->n_texts, kind, s), who));
+    RL_TRY(hip_status(hipStreamSynchronize(s), who));
+    return RL_OK;
+}
+
+int rl_sentencepiece_device(rl_sentencepiece* tok, const int32_t** ids, const int64_t** offsets, const uint8_t** status, const uint32_t** symbols,
+                            const int64_t** symbol_offsets) {
+    const char* who = "rl_sentencepiece_device";
+    if (!tok) return fail(RL_ERR_INVALID, std::string(who) + ": null handle");
+    std::lock_guard<std::mutex> lock(tok->mu);
+    if (!tok->encoded) return fail(RL_ERR_INVALID, std::string(who) + ": no rl_sentencepiece_encode before it");
+    if (ids) *ids = tok->ids.as<int32_t>();
+    if (offsets) *offsets = tok->offsets.as<int64_t>();
+    if (status) *status = tok->status.as<uint8_t>();
+    if (symbols) *symbols = tok->sym.as<uint32_t>();
+    if (symbol_offsets) *symbol_offsets = tok->sym_off.as<int64_t>();
+    return RL_OK;
+}
+
+int rl_sentencepiece_rows(const int32_t* ids, const int64_t* tok_off, int64_t n_texts, int32_t max_len, int32_t bos_id, int32_t eos_id,
+                          int32_t position_offset, int32_t* out_ids, int32_t* out_positions, int32_t* out_seq_offsets, int64_t* out_total, int mem,
+                          void* stream) {
+    const char* who = "rl_sentencepiece_rows";
+    const std::string w(who);
+    RL_TRY(check_mem(mem, who));
+    if (n_texts < 0) return fail(RL_ERR_INVALID, w + ": negative size");
+    if (n_texts >= (int64_t(1) << 31) / 2) return fail(RL_ERR_UNSUPPORTED, w + ": one call takes fewer than 2^31 tokens");
+    if (max_len < 2) return fail(RL_ERR_INVALID, w + ": max_len must be >= 2");
+    if (!tok_off) return fail(RL_ERR_INVALID, w + ": tok_off is null");
+    if (!out_seq_offsets) return fail(RL_ERR_INVALID, w + ": out_seq_offsets is null");
+    if (!out_total) return fail(RL_ERR_INVALID, w + ": out_total is null");
+    const int given = (out_ids != nullptr) + (out_positions != nullptr);
+    if (given == 1) return fail(RL_ERR_INVALID, w + ": give out_ids and out_positions, or neither for the sizes alone");
+    if (given && n_texts > 0 && !ids) return fail(RL_ERR_INVALID, w + ": ids is null");
+    int64_t n_tokens = 0;
+    if (mem == RL_MEM_HOST) {
+        RL_TRY(check_text_off(w, "tok_off", tok_off, n_texts, 0, false));
+        n_tokens = tok_off[n_texts];
+    }
+    hipStream_t s = as_stream(stream);
+    Staging st(mem, s);
+    const int64_t* d_off; const int32_t* d_ids = ids;
+    RL_TRY(st.in(tok_off, (size_t)n_texts + 1, &d_off));
+    if (given && n_texts > 0) RL_TRY(st.in(ids, (size_t)n_tokens, &d_ids));
+    int64_t* d_len; int64_t* d_scr;
+    RL_TRY(st.temp((size_t)(n_texts + 1) * sizeof(int64_t), &d_len));
+    RL_TRY(st.temp(kb_scan_scratch_items(n_texts + 1) * sizeof(int64_t), &d_scr));
+    RL_TRY(launch_sp_row_lengths(d_off, n_texts, max_len, d_len, s));
+    const int64_t* d_total = nullptr;
+    RL_TRY(launch_kb_exclusive_scan(d_len, n_texts + 1, d_scr, &d_total, s));
+    int64_t total = 0;
+    RL_TRY(hip_status(hipMemcpyAsync(&total, d_total, sizeof(int64_t), hipMemcpyDeviceToHost, s), who));
+    RL_TRY(hip_status(hipStreamSynchronize(s), who));
+    if (total >= (int64_t(1) << 31)) return fail(RL_ERR_UNSUPPORTED, w + ": one call takes fewer than 2^31 tokens");
+    *out_total = total;
+    int32_t* d_so;
+    RL_TRY(st.out(out_seq_offsets, (size_t)n_texts + 1, &d_so));
+    RL_TRY(launch_sp_row_offsets(d_len, n_texts, d_so, s));
+    if (given) {
+        int32_t *d_oi, *d_op;
+        RL_TRY(st.out(out_ids, (size_t)total, &d_oi));
+        RL_TRY(st.out(out_positions, (size_t)total, &d_op));
+        RL_TRY(launch_sp_row_write(d_ids, d_off, n_texts, max_len, bos_id, eos_id, position_offset, d_len, total, d_oi, d_op, s));
+    }
+    return st.finish();
+}
+
+}  // extern "C"

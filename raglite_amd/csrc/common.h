@@ -465,6 +465,35 @@ int launch_wp_pair_write(const int32_t* ids, const int64_t* tok_off, int64_t n_t
                          int32_t max_length, int32_t cls_id, int32_t sep_id, int32_t position_offset, const int64_t* row_scan, int64_t total,
                          int32_t* out_ids, int32_t* out_positions, int32_t* out_type_ids, hipStream_t s);
 
+// sentencepiece.hip: texts -> SentencePiece Unigram ids (rl_sentencepiece_encode drives these in this order; the scans between them are
+// launch_kb_exclusive_scan's), and the bos ids eos rows of texts (rl_sentencepiece_rows).  cp [n] UTF-32; SpImage / SpTable:
+// sentencepiece_table.h.
+constexpr int SP_COUNT_UNK = 0, SP_COUNT_FLAGGED = 1, SP_COUNT_LONGEST = 2, SP_COUNTERS = 3;  // counters [3], zero on entry: unknown ids written,
+                                                                                             // texts with status 1, the longest text in symbols
+struct SpImage;
+struct SpTable;
+// count [n + 1]: symbols per code point, + (trailing-set flag << 32); scanned, its last entry is (m0, flagged code points) in the two fields
+int launch_sp_expand_count(const uint32_t* cp, int64_t n, const SpImage& im, int64_t* count, hipStream_t s);
+int launch_sp_expand_write(const uint32_t* cp, int64_t n, const SpImage& im, const int64_t* scan, int64_t m0, uint32_t* raw, hipStream_t s);
+// rtext_off [n_texts + 1]; start [m0] (zero on entry): 1 where a text begins; status [n_texts]: 1 = holds a flagged code point
+int launch_sp_texts(const int64_t* text_off, int64_t n_texts, int64_t n, const int64_t* scan, int64_t m0, int64_t* rtext_off, uint8_t* start,
+                    uint8_t* status, unsigned long long* counters, hipStream_t s);
+// keep [m0 + 1]: normalised symbols per expanded symbol (0, 1, 2), to be scanned; then sym [m] and sym_off [n_texts + 1]
+int launch_sp_keep_count(const uint32_t* raw, const uint8_t* start, int64_t m0, int64_t* keep, hipStream_t s);
+int launch_sp_keep_write(const uint32_t* raw, const uint8_t* start, int64_t m0, const int64_t* keep_scan, int64_t m, const int64_t* rtext_off,
+                         int64_t n_texts, uint32_t* sym, int64_t* sym_off, unsigned long long* counters, hipStream_t s);
+// one text per wave; bp_start, bp_id, tmp [m]; tok_count [n_texts + 1]: to be scanned (tok_scan); tmp holds every text's ids REVERSED
+int launch_sp_viterbi(const uint32_t* sym, const int64_t* sym_off, int64_t n_texts, int64_t m, const SpTable& table, int32_t longest, float unk_score,
+                      int32_t* bp_start, int32_t* bp_id, int32_t* tmp, int64_t* tok_count, unsigned long long* counters, hipStream_t s);
+// ids [n_tokens] = id + id_offset, the unknown piece unk_out; offsets [n_texts + 1] = tok_scan
+int launch_sp_emit(const int32_t* tmp, const int64_t* sym_off, const int64_t* tok_scan, int64_t n_texts, int64_t m, int64_t n_tokens, int32_t id_offset,
+                   int32_t unk_out, int32_t* ids, int64_t* offsets, hipStream_t s);
+// len [n_texts + 1]: the row length of every text, to be scanned (row_scan); then the int32 offsets and the two token arrays
+int launch_sp_row_lengths(const int64_t* tok_off, int64_t n_texts, int32_t max_len, int64_t* len, hipStream_t s);
+int launch_sp_row_offsets(const int64_t* row_scan, int64_t n_texts, int32_t* seq_offsets, hipStream_t s);
+int launch_sp_row_write(const int32_t* ids, const int64_t* tok_off, int64_t n_texts, int32_t max_len, int32_t bos_id, int32_t eos_id, int32_t position_offset,
+                        const int64_t* row_scan, int64_t total, int32_t* out_ids, int32_t* out_positions, hipStream_t s);
+
 // fuse.hip: weighted Reciprocal Rank Fusion of n_lists ranked lists per query (lists [n_lists x n_queries x len] int32, < 0 = padding)
 // -> the top k by (float64 score desc, first occurrence asc), bit for bit the reference's reciprocal_rank_fusion
 constexpr int32_t RRF_MAX_LISTS = 4;

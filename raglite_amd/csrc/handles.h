@@ -8,6 +8,7 @@
 #include <vector>
 
 #include "device_mem.h"
+#include "sentencepiece_table.h"
 
 namespace rl {
 
@@ -222,6 +223,32 @@ struct rl_encoder {
     std::mutex mu;
     rl::Pool scratch;             // rl::EncoderScratch over RL_ENCODER_MAX_TOKENS rows; every call walks a prefix of it
     rl::LastStream last_stream;
+};
+
+// ---- SentencePiece Unigram on the device (include/raglite_hip.h; kernels in sentencepiece.hip, entry points in api_ingest.hip) --------
+struct rl_sentencepiece {
+    std::mutex mu;
+    int hash_bits = 0;
+    int64_t n_table = 0, n_pool = 0, n_pieces = 0, n_slots = 0, table_bytes = 0;
+    int32_t longest = 0, unk_id = 0;
+    float unk_score = 0.f;
+    rl::DevArray<int32_t> image_off;    // [n_table]
+    rl::DevArray<uint8_t> image_len;    // [n_table]
+    rl::DevArray<uint32_t> image_pool;  // [n_pool]
+    rl::DevArray<uint32_t> piece_cp;    // the kept pieces' code points, back to back
+    rl::DevArray<int32_t> piece_off;    // [n_pieces + 1]
+    rl::DevArray<uint8_t> piece_flags;  // [n_pieces], all 0: no piece is a continuation
+    rl::DevArray<int32_t> piece_ids;    // [n_pieces]
+    rl::DevArray<float> piece_scores;   // [n_pieces]
+    rl::DevArray<int32_t> slots;        // [n_slots]
+    // what the last rl_sentencepiece_encode left (nothing until then)
+    bool encoded = false;
+    int64_t n_texts = 0, n_tokens = 0;
+    // device arrays of a call, kept between calls with amortised capacity
+    rl::Pool count, scan_scratch, raw, start, rtext_off, keep, sym, sym_off, bp_start, bp_id, tmp, tok_count, ids, offsets, status, counters;
+    rl::LastStream last_stream;
+    rl::SpImage image() const { return {image_off, image_len, image_pool, n_table, n_pool}; }
+    rl::SpTable table() const { return {{piece_cp, piece_off, piece_flags, slots, n_slots, hash_bits}, piece_scores, piece_ids}; }
 };
 
 namespace rl {
