@@ -633,7 +633,12 @@ int rl_maxsim_rerank_ragged(rl_index* index, const float* query_vecs, const int6
 /* ---- section 8e: shard merge --------------------------------------------------------------------
  * Merge `n_lists` per-shard top-k lists per query (as produced by an all-gather of each rank's
  * rl_search_rows / rl_maxsim_topk output with GLOBAL ids) into the global top-k by
- * (score desc, id asc).  in_* are [n_lists x n_queries x k_in]; out_* are [n_queries x k]. */
+ * (score desc, id asc).  in_* are [n_lists x n_queries x k_in]; out_* are [n_queries x k].
+ * An entry whose id is negative is padding and its score is ignored; slots past the real entries come back as (-inf, -1).
+ * n_lists * k_in <= 8192 and k <= 2048, else RL_ERR_UNSUPPORTED; k may exceed n_lists * k_in.
+ * The order is rl_topk's (below): one total order on the score's bits, so NaN ranks after -inf (ids ascending, written back as
+ * the one quiet NaN 0x7fc00000) and +0.0 ranks BEFORE -0.0 whatever the two ids are; only equal bit patterns tie and fall
+ * through to the id. */
 int rl_merge_topk(const float* in_scores, const int32_t* in_ids, int32_t n_lists, int32_t n_queries,
                   int32_t k_in, int32_t k, float* out_scores, int32_t* out_ids, int mem, void* stream);
 
@@ -666,7 +671,13 @@ int rl_allreduce_sum_u32(rl_comm* comm, uint32_t* buf, int64_t count, void* stre
 int rl_allgather_u32(rl_comm* comm, const uint32_t* local, int64_t count, uint32_t* out, void* stream);
 
 /* Generic exact top-k over a dense score matrix [n_queries x n] (row stride ld), the selection
- * stage used by every search above; exposed for tests and for callers that score elsewhere. */
+ * stage used by every search above; exposed for tests and for callers that score elsewhere.
+ * Order: (score desc, index asc) under ONE total order on the score's bits, the 32-bit key every selection kernel, the fused
+ * top-k and the shard merge share: +inf > finite > -inf > NaN, and +0.0 > -0.0.  So every +0.0 comes before every -0.0
+ * whatever their indices (the two compare equal in C; here they do not tie), every NaN comes last in index order and is
+ * written back as the quiet NaN 0x7fc00000 (a payload is not kept), and all other scores come back with their own bits.
+ * The host restatements (raglite_amd._sharded.merge_topk_host, oracle.topk_desc) follow the same rule.  No search produces
+ * -0.0 (a similarity is 1 - distance); the rerank order (rl_rerank_order) folds -0.0 into +0.0 on purpose and is not this. */
 int rl_topk(const float* scores, int32_t n_queries, int64_t n, int64_t ld, int32_t k,
             float* out_scores, int32_t* out_ids, int mem, void* stream);
 

@@ -321,12 +321,15 @@ def topk_desc(scores: np.ndarray, k: int) -> tuple[np.ndarray, np.ndarray]:
     """Exact top-k by (score descending, index ascending).  NaNs rank last.
 
     `ORDER BY dist LIMIT k` (`_search.py:77-79`) with the tie order SQL leaves unspecified
-    fixed to the lowest index; NaN ranks after -inf."""
+    fixed to the lowest index; NaN ranks after -inf.  Signed zeros: the device ranks by a total
+    order on the score's bits (`score_key`, csrc/common.h), in which +0.0 is larger than -0.0, so
+    every +0.0 comes before every -0.0 whatever their indices (include/raglite_hip.h, rl_topk)."""
     scores = np.asarray(scores)
     k = min(k, len(scores))
     nan = np.isnan(scores)
     key = np.where(nan, -np.inf, scores)
-    order = np.lexsort((np.arange(len(scores)), -key, nan))[:k]  # NaN strictly after -inf
+    neg_zero = (scores == 0) & np.signbit(scores)
+    order = np.lexsort((np.arange(len(scores)), neg_zero, -key, nan))[:k]  # NaN strictly after -inf
     return scores[order], order.astype(np.int64)
 
 
@@ -616,12 +619,12 @@ def maxsim_candidates(D, chunk_offsets, Q, cand, dtype=np.float64) -> np.ndarray
 
 def merge_topk(scores_list: list[np.ndarray], ids_list: list[np.ndarray], k: int):
     """Concatenate per-shard top-k lists (global ids) and take the global top-k by
-    (score desc, id asc): identical to the single-shard result."""
+    (score desc, id asc): identical to the single-shard result (+0.0 before -0.0, as `topk_desc`)."""
     s = np.concatenate(scores_list)
     i = np.concatenate(ids_list).astype(np.int64)
     nan = np.isnan(s)
     key = np.where(nan, -np.inf, s)
-    order = np.lexsort((i, -key, nan))[:k]
+    order = np.lexsort((i, (s == 0) & np.signbit(s), -key, nan))[:k]
     return s[order], i[order]
 
 

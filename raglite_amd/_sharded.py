@@ -39,11 +39,13 @@ def shard_bounds_by_chunk(chunk_offsets, world: int) -> list[tuple[int, int]]:
 
 def _merge_order(s: np.ndarray, i: np.ndarray, k: int) -> tuple[np.ndarray, np.ndarray]:
     """Positions of the k best entries of every row of s / i (shape (B, M); id -1 = padding) by (score desc, id asc),
-    NaN after -inf, padding last; and how many of them are real.  One lexsort over the whole batch."""
+    NaN after -inf, padding last; and how many of them are real.  One lexsort over the whole batch.  The device's key is a total
+    order on the score's bits (`score_key`, csrc/common.h): +0.0 ranks before -0.0 whatever the ids, so it does here."""
     pad = i < 0
     nan = np.isnan(s)
     key = np.where(nan | pad, -np.inf, s)
-    order = np.lexsort((i, -key, nan, pad), axis=-1)[:, :k]
+    neg_zero = (s == 0) & np.signbit(s) & ~pad
+    order = np.lexsort((i, neg_zero, -key, nan, pad), axis=-1)[:, :k]
     n_valid = np.minimum((~pad).sum(axis=1), k)
     return order, n_valid
 
@@ -138,14 +140,16 @@ def compose_hybrid_fuse(gathered, *, num_hits: int, n_each: int, keywords: bool,
 
 
 def merge_order_torch(s, i, k: int):
-    """`_merge_order` on torch tensors (any device, nothing synchronises with the host): three stable sorts, least significant
-    key first -- id asc, score desc, then (padding, NaN) last."""
+    """`_merge_order` on torch tensors (any device, nothing synchronises with the host): four stable sorts, least significant
+    key first -- id asc, +0.0 before -0.0, score desc, then (padding, NaN) last."""
     import torch
 
     pad = i < 0
     nan = torch.isnan(s)
     key = torch.where(nan | pad, torch.full_like(s, float("-inf")), s)
+    neg_zero = ((s == 0) & torch.signbit(s) & ~pad).to(torch.int32)
     idx = torch.argsort(i, dim=1, stable=True)
+    idx = idx.gather(1, torch.argsort(neg_zero.gather(1, idx), dim=1, stable=True))
     idx = idx.gather(1, torch.argsort(key.gather(1, idx), dim=1, descending=True, stable=True))
     cls = pad.to(torch.int32) * 2 + nan.to(torch.int32)
     idx = idx.gather(1, torch.argsort(cls.gather(1, idx), dim=1, stable=True))

@@ -75,6 +75,17 @@ def test_massive_ties_and_specials():
     s, i = _both(x, 9)
     assert i.tolist()[:3] == [3, 5, 8] and i.tolist()[-3:] == [4, 2, 6]
     assert np.isnan(s[-1]) and np.isnan(s[-2]) and np.isneginf(s[-3])
+    # the signed-zero rule (include/raglite_hip.h, rl_topk): the key orders the score's bits, +0.0 before -0.0 whatever the indices
+    assert i.tolist()[3:6] == [0, 1, 7] and s.view(np.uint32).tolist()[3:5] == [0x00000000, 0x80000000]
+    es, ei = oracle.topk_desc(x, 9)
+    assert np.array_equal(i, ei) and np.array_equal(np.isnan(s), np.isnan(es)) and np.array_equal(s.view(np.uint32)[:7], es.view(np.uint32)[:7])
+    x = np.array([-0.0, 1.0, 0.0, -0.0, np.nan, 0.0, -1.0, -0.0, 0.0], dtype=np.float32)  # every -0.0 has a +0.0 at a HIGHER index
+    s, i = _both(x, 9)
+    assert i.tolist() == [1, 2, 5, 8, 0, 3, 7, 6, 4]
+    assert s.view(np.uint32).tolist() == [0x3F800000, 0, 0, 0, 0x80000000, 0x80000000, 0x80000000, 0xBF800000, 0x7FC00000]
+    assert np.array_equal(oracle.topk_desc(x, 9)[1], i)
+    s, i = _both(x, 3)  # the cut falls inside the zeros
+    assert i.tolist() == [1, 2, 5] and s.view(np.uint32).tolist() == [0x3F800000, 0, 0]
     x = np.full(5000, -np.inf, dtype=np.float32)
     x[[7, 4999]] = [2.0, 3.0]
     s, i = _both(x, 10)
