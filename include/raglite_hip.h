@@ -1181,6 +1181,57 @@ int rl_partition_sentences(const uint32_t* codepoints, const void* probas, int p
                            const int64_t* doc_offsets, int64_t n, int64_t n_docs, int64_t min_len, int64_t max_len,
                            uint8_t* cut, double* objective, int32_t* status, int mem, void* stream);
 
+/* ---- Markdown block structure on the device ------------------------------
+ * What the two splitters read from markdown-it-py's `MarkdownIt().parse` (its `commonmark` block
+ * phase: code, fence, blockquote, hr, list, heading, lheading, paragraph), for many documents in one
+ * call, as two arrays per line.  Lines end at \n, \r\n or a lone \r.  The contract is exact or
+ * undecided: a document with status 0 has the library's tokens, token for token; a document with
+ * status 1 was given up and its rows are unspecified (parse it on the host).  A document is given up
+ * only where the parse meets: '<' as the first character of a line where block rules are tried (the
+ * html_block rule); '[' where a paragraph would start (the reference rule); a tab in a line's leading
+ * white space or behind a container marker; one of the other str.splitlines separators (U+000B,
+ * U+000C, U+001C-U+001E, U+0085, U+2028, U+2029); a block at nesting level 16 or deeper.  One
+ * document per wave, no atomics, the same bytes run to run and for host and device pointers.
+ *   codepoints   uint32[n] the characters (UTF-32)
+ *   doc_offsets  int64[n_docs + 1] CSR over the characters (starts at 0, ascends, ends at n)
+ *   first_open   uint8[n + n_docs], rows line_offsets[d] .. of document d: the first of these block
+ *                tokens that starts on the line: 0 none, 1 heading_open, 2 blockquote_open,
+ *                3 paragraph_open, 4 bullet_list_open, 5 ordered_list_open
+ *   heading_end  int32[n + n_docs]: map[1] of the heading that starts on the line, else 0
+ *   line_start   int64[n + n_docs] (nullable): the line's first character, an index into codepoints
+ *   line_offsets int64[n_docs + 1] CSR over the lines (str.splitlines lines; at most n + n_docs)
+ *   status       int32[n_docs]: 0 = decided, 1 = undecided
+ * RL_ERR_INVALID before any HIP call: n < 0, n > 0 with n_docs < 1 or a null codepoints /
+ * doc_offsets / first_open / heading_end / line_offsets / status, a document of 2^31 - 64 characters
+ * or more, and for RL_MEM_HOST offsets that do not start at 0 / ascend / end at n.  n == 0 returns
+ * RL_OK and writes nothing. */
+int rl_markdown_blocks(const uint32_t* codepoints, const int64_t* doc_offsets, int64_t n, int64_t n_docs,
+                       uint8_t* first_open, int32_t* heading_end, int64_t* line_start, int64_t* line_offsets,
+                       int32_t* status, int mem, void* stream);
+
+/* The known sentence boundaries of raglite_amd._sentences.markdown_sentence_boundaries, same bits,
+ * from rl_markdown_blocks' arrays (n_lines rows each, at least line_offsets[n_docs]): known f64[n] is
+ * NaN by default, 0 on a heading's lines, 1 on the character before a heading and on the first
+ * character behind it; where two headings write one character the later heading wins.  The
+ * characters of an undecided document are NaN.  What rl_partition_sentences takes as `known`.
+ * n == 0 returns RL_OK and writes nothing. */
+int rl_markdown_sentence_known(const int32_t* heading_end, const int64_t* line_start, const int64_t* line_offsets,
+                               const int32_t* status, const int64_t* doc_offsets, int64_t n, int64_t n_docs,
+                               int64_t n_lines, double* known, int mem, void* stream);
+
+/* The boundary probabilities of raglite_amd._chunklets.markdown_chunklet_boundaries, same bits, for
+ * documents that are the concatenation of their sentences: sentence i holds the characters
+ * [sentence_offsets[i], sentence_offsets[i + 1]) of codepoints (int64[n_sentences + 1]); doc_offsets
+ * int64[n_docs + 1] is the CSR over the sentences.  A sentence takes the first line that starts in it
+ * and bears a token: 1.0 heading, 0.75 blockquote, 0.5 paragraph, 0.25 either list, else 0; of a run
+ * of consecutive non-zero sentences only the first largest keeps its value.  The sentences of an
+ * undecided document get 0.  What rl_partition_chunklets takes as `boundary`.  n_sentences == 0
+ * returns RL_OK and writes nothing. */
+int rl_markdown_chunklet_boundary(const uint8_t* first_open, const int64_t* line_start, const int64_t* line_offsets,
+                                  const int32_t* status, const int64_t* sentence_offsets, const int64_t* doc_offsets,
+                                  int64_t n_sentences, int64_t n_docs, int64_t n_lines, double* boundary, int mem,
+                                  void* stream);
+
 /* ---- WordPiece on the device: the cross-encoder's tokenizer --------------
  * What the `tokenizers` library's BERT pipeline (BertNormalizer, BertPreTokenizer, WordPiece) does for
  * many texts, on their UTF-32 code points: token ids equal to tok.encode(text, add_special_tokens =

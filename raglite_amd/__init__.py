@@ -36,6 +36,7 @@ from raglite_amd._sentences import (
     whitespace_mask,
 )
 from raglite_amd._config import HotPathConfig
+from raglite_amd._markdown import MARKDOWN_OK, MARKDOWN_UNDECIDED, markdown_blocks_batch
 from raglite_amd._embed import (
     embed_strings,
     embed_strings_batch,
@@ -114,6 +115,7 @@ __all__ = [
     "markdown_chunklet_boundaries", "compute_num_statements",
     "split_sentences", "split_sentences_batch", "split_texts_batch", "partition_sentences", "sentence_dp", "sentence_partition",
     "markdown_sentence_boundaries", "whitespace_mask", "propagate_whitespace",
+    "markdown_blocks_batch", "MARKDOWN_OK", "MARKDOWN_UNDECIDED",
     "hybrid_search",
     "hybrid_search_batch",
     "keyword_search",

@@ -115,6 +115,10 @@ _SIGNATURES = {
     "rl_partition_chunklets": [c_void_p, c_void_p, c_void_p, c_void_p, c_i64, c_i64, c_i64, c_void_p, c_void_p, c_void_p, c_int, c_void_p],
     "rl_partition_sentences": [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_i64, c_i64, c_i64, c_i64, c_void_p, c_void_p, c_void_p, c_int,
                                c_void_p],
+    "rl_markdown_blocks": [c_void_p, c_void_p, c_i64, c_i64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p],
+    "rl_markdown_sentence_known": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_i64, c_i64, c_i64, c_void_p, c_int, c_void_p],
+    "rl_markdown_chunklet_boundary": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_i64, c_i64, c_i64, c_void_p, c_int,
+                                      c_void_p],
     "rl_chunk_best_rows": [c_void_p, c_void_p, c_i32, c_void_p, c_i32, c_void_p, c_int, c_void_p],
     "rl_gather_rows": [c_void_p, c_void_p, c_i64, c_void_p, c_int, c_void_p],
     "rl_query_targets": [c_void_p, c_void_p, c_i32, c_void_p, c_void_p, c_i32, c_double, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,

@@ -23,6 +23,7 @@ SOURCES = [
     "synth.hip", "scan.hip", "scan16.hip", "select.hip", "mask.hip", "score_gemm.hip", "hi_filter.hip",  # row and chunk search
     "maxsim_stream.hip", "maxsim_generic.hip", "maxsim_ragged.hip", "maxsim_gemm.hip", "maxsim_pp.hip",  # MaxSim
     "pool_norm.hip", "partition_sim.hip", "partition_dp.hip", "chunklet_dp.hip", "sentence_dp.hip",  # ingestion
+    "markdown.hip",  # the Markdown block structure the splitters read (the parser: markdown_blocks.h)
     "attention_varlen.hip",  # the packed encoder's attention
     "encoder.hip",  # the native encoder forward for short packs
     "encoder_head.hip",  # the cross-encoder's pooler + classifier head on its final rows

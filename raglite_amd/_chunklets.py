@@ -155,13 +155,18 @@ def _join(sentences: Sequence[str], cuts: Sequence[int]) -> list[str]:
 
 
 def split_chunklets_batch(documents: Sequence[Sequence[str]], max_size: int = 2048, *,
-                          boundary_probas: Sequence[Any] | None = None) -> list[list[str]]:
+                          boundary_probas: Sequence[Any] | None = None, markdown: str = "host") -> list[list[str]]:
     """`split_chunklets` for MANY documents in one `rl_partition_chunklets` call: the partition runs on the device; the host parses
     the Markdown, counts words and characters, and joins the strings.
 
     documents: a sequence of sentence lists; boundary_probas: optionally one float array per document that replaces the Markdown
-    parse.  One device call and one read-back (a byte per sentence, a word per document).  Returns per document what the reference
-    returns, `[""]` for a document without sentences."""
+    parse.  One device call and one read-back (a byte per sentence, a word per document).  markdown="host" (default):
+    `markdown_chunklet_boundaries` per document, with markdown-it; markdown="device": the Markdown block parse of the joined sentences
+    runs on the device too (`_markdown.py`), its boundary probabilities go to the partition on the device, and only the documents the
+    device parser gives up are parsed by markdown-it -- the same chunklets; an explicit boundary_probas still wins.  Returns per
+    document what the reference returns, `[""]` for a document without sentences."""
+    if markdown not in ("host", "device"):
+        raise ValueError('markdown must be "host" or "device"')
     docs = [d if isinstance(d, list) else list(d) for d in documents]
     if boundary_probas is not None and len(boundary_probas) != len(docs):
         raise ValueError("split_chunklets_batch: one boundary_probas array per document is required")
@@ -171,15 +176,21 @@ def split_chunklets_batch(documents: Sequence[Sequence[str]], max_size: int = 20
     cut = np.zeros(0, np.uint8)
     if n > 0:
         full = [d for d in range(len(docs)) if counts[d] > 0]
-        if boundary_probas is None:
+        lengths = np.fromiter((len(s) for d in docs for s in d), dtype=np.int64, count=n)
+        if boundary_probas is None and markdown == "device":
+            from raglite_amd import _markdown
+
+            boundary = _markdown.device_chunklet_boundary(docs, off, lengths, lambda d: markdown_chunklet_boundaries(docs[d]))
+        elif boundary_probas is None:
             boundary = np.concatenate([markdown_chunklet_boundaries(docs[d]) for d in full])
         else:
             boundary = np.concatenate([np.asarray(boundary_probas[d], dtype=np.float64).reshape(-1) for d in full])
         if len(boundary) != n:
             raise ValueError("split_chunklets_batch: a document's boundary_probas do not match its sentences")
         statements = np.concatenate([compute_num_statements(docs[d]) for d in full])
-        lengths = np.fromiter((len(s) for d in docs for s in d), dtype=np.int64, count=n)
         cut, _, status = _ops.partition_chunklets(boundary, statements, lengths, off, max_size, want_objective=False)
+        if not isinstance(cut, np.ndarray):  # the device route: one read-back
+            cut, status = cut.cpu().numpy(), status.cpu().numpy()
         bad = np.flatnonzero(status == CHUNKLETS_NOT_FINITE)
         if len(bad):
             raise ValueError(f"Non-finite chunklet boundary probabilities or statement counts detected. (document {int(bad[0])})")
@@ -237,11 +248,12 @@ def split_chunklets(sentences: list[str], boundary_cost: Callable[[np.ndarray], 
 
 
 def split_documents_batch(documents: Sequence[Sequence[str]], *, config: Any | None = None,
-                          embedder: Any | None = None, embed: str = "loop") -> list[tuple[list[str], list[Any]]]:
+                          embedder: Any | None = None, embed: str = "loop", markdown: str = "host") -> list[tuple[list[str], list[Any]]]:
     """Sentences -> chunklets -> chunklet embeddings -> chunks for MANY documents (`_insert.py:95-101`): `split_chunklets_batch`,
     the chunklet embeddings, `split_chunks_batch`.  embed="loop" (default): `embed_strings` one document at a time (as `_insert.py:96`
     does); embed="batch": `embed_strings_batch`, which shares encoder forwards and the pooling launch across documents.  Returns per
-    document (chunks, chunk_embeddings), ready for `GpuIndex.insert_chunks`."""
+    document (chunks, chunk_embeddings), ready for `GpuIndex.insert_chunks`.  markdown: where `split_chunklets_batch` parses the
+    Markdown."""
     from raglite_amd._chunking import split_chunks_batch
     from raglite_amd._config import HotPathConfig
     from raglite_amd._embed import embed_strings, embed_strings_batch
@@ -249,7 +261,7 @@ def split_documents_batch(documents: Sequence[Sequence[str]], *, config: Any | N
     if embed not in ("loop", "batch"):
         raise ValueError('embed must be "loop" or "batch"')
     config = config or HotPathConfig()
-    chunklets = split_chunklets_batch(documents, max_size=config.chunk_max_size)
+    chunklets = split_chunklets_batch(documents, max_size=config.chunk_max_size, markdown=markdown)
     if embed == "batch":
         embeddings = embed_strings_batch(chunklets, config=config, embedder=embedder)
     else:

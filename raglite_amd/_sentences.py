@@ -240,7 +240,7 @@ def _raise_for(status: int, d: int | None) -> None:
 
 
 def split_sentences_batch(documents: Sequence[str], min_len: int = 4, max_len: int | None = None, *, predicted_probas: Any,
-                          boundary_probas: Any | None = None) -> list[list[str]]:
+                          boundary_probas: Any | None = None, markdown: str = "host") -> list[list[str]]:
     """`split_sentences` for MANY documents in one `rl_partition_sentences` call and one read-back (a byte per character, a word per
     document).
 
@@ -248,8 +248,14 @@ def split_sentences_batch(documents: Sequence[str], min_len: int = 4, max_len: i
     stays float32, as the reference keeps the model's dtype; all documents of one call share a dtype).  boundary_probas: known
     boundaries that override the prediction where finite -- one array per document, a callable, or None for
     `markdown_sentence_boundaries` (the reference's default).  A document with `len(doc) <= min_len` comes back as `[doc]` without a
-    look at its probabilities (`_split_sentences.py:178`).  ValueError: a probability array of the wrong length, non-finite
-    probabilities, or no valid split under max_len (the reference's message), each naming the document."""
+    look at its probabilities (`_split_sentences.py:178`).  markdown="host" (default): `markdown_sentence_boundaries` per document,
+    with markdown-it; markdown="device": the Markdown block parse runs on the device too (`_markdown.py`; the code points are uploaded
+    once, the known boundaries go from `rl_markdown_sentence_known` to the partition on the device, and only the documents the
+    device parser gives up are parsed by markdown-it) -- the same sentences; an explicit boundary_probas still wins.  ValueError: a
+    probability array of the wrong length, non-finite probabilities, or no valid split under max_len (the reference's message), each
+    naming the document."""
+    if markdown not in ("host", "device"):
+        raise ValueError('markdown must be "host" or "device"')
     docs = list(documents)
     for name, source in (("predicted_probas", predicted_probas), ("boundary_probas", boundary_probas)):
         if source is not None and not callable(source) and len(source) != len(docs):
@@ -266,11 +272,18 @@ def split_sentences_batch(documents: Sequence[str], min_len: int = 4, max_len: i
     if len(dtypes) != 1:
         raise ValueError("split_sentences_batch: the predicted_probas of one call must share a dtype (float32 or float64)")
     dtype = dtypes.pop()
-    known = np.concatenate([_probas_of(known_source, d, docs[d], "boundary_probas").astype(np.float64, copy=False) for d in full])
     codepoints = codepoints_of("".join(docs[d] for d in full))
     off = np.concatenate(([0], np.cumsum([len(docs[d]) for d in full]))).astype(np.int64)
-    cut, _, status = _ops.partition_sentences(codepoints, np.concatenate(predicted).astype(dtype, copy=False), off, min_len, max_len,
-                                              known, want_objective=False)
+    probas = np.concatenate(predicted).astype(dtype, copy=False)
+    if markdown == "device" and boundary_probas is None:
+        from raglite_amd import _markdown
+
+        cp, known = _markdown.device_sentence_known(codepoints, off, lambda k: markdown_sentence_boundaries(docs[full[k]]))
+        cut, _, status = (x.cpu().numpy() if x is not None else None for x in _ops.partition_sentences(
+            cp, _markdown._upload(probas), off, min_len, max_len, known, want_objective=False))
+    else:
+        known = np.concatenate([_probas_of(known_source, d, docs[d], "boundary_probas").astype(np.float64, copy=False) for d in full])
+        cut, _, status = _ops.partition_sentences(codepoints, probas, off, min_len, max_len, known, want_objective=False)
     for k in np.flatnonzero(status >= SENTENCES_NOT_FINITE).tolist()[:1]:
         _raise_for(int(status[k]), full[k])
     for k, d in enumerate(full):
@@ -303,13 +316,14 @@ def split_sentences(doc: str, min_len: int = 4, max_len: int | None = None,
 
 
 def split_texts_batch(texts: Sequence[str], *, predicted_probas: Any, config: Any | None = None,
-                      embedder: Any | None = None) -> list[tuple[list[str], list[Any]]]:
+                      embedder: Any | None = None, markdown: str = "host") -> list[tuple[list[str], list[Any]]]:
     """Texts -> sentences -> chunklets -> chunklet embeddings -> chunks for MANY documents (`_insert.py:94-101`):
     `split_sentences_batch` with `max_len=config.chunk_max_size` (as `_insert.py:94` does), then `split_documents_batch`.  Returns per
-    text (chunks, chunk_embeddings), ready for `GpuIndex.insert_chunks`."""
+    text (chunks, chunk_embeddings), ready for `GpuIndex.insert_chunks`.  markdown: where both splitters parse the Markdown
+    (`split_sentences_batch`)."""
     from raglite_amd._chunklets import split_documents_batch
     from raglite_amd._config import HotPathConfig
 
     config = config or HotPathConfig()
-    sentences = split_sentences_batch(texts, max_len=config.chunk_max_size, predicted_probas=predicted_probas)
-    return split_documents_batch(sentences, config=config, embedder=embedder)
+    sentences = split_sentences_batch(texts, max_len=config.chunk_max_size, predicted_probas=predicted_probas, markdown=markdown)
+    return split_documents_batch(sentences, config=config, embedder=embedder, markdown=markdown)

@@ -536,6 +536,110 @@ int rl_partition_sentences(const uint32_t* codepoints, const void* probas, int p
     return st.finish();
 }
 
+// ---- Markdown block structure for the splitters (markdown.hip, markdown_blocks.h) --------------------------------------
+// The line offsets a host caller hands to the two derived entries: ascending from 0 and inside the per-line arrays.
+static int check_line_offsets(const char* who, const int64_t* off, int64_t n_docs, int64_t n_lines, int mem) {
+    if (mem != RL_MEM_HOST) return RL_OK;
+    const std::string w(who);
+    if (off[0] != 0) return fail(RL_ERR_INVALID, w + ": line_offsets must start at 0");
+    for (int64_t d = 0; d < n_docs; ++d)
+        if (off[d + 1] < off[d]) return fail(RL_ERR_INVALID, w + ": line_offsets must be ascending");
+    if (off[n_docs] > n_lines) return fail(RL_ERR_INVALID, w + ": line_offsets must end at or before n_lines");
+    return RL_OK;
+}
+
+int rl_markdown_blocks(const uint32_t* codepoints, const int64_t* doc_offsets, int64_t n, int64_t n_docs, uint8_t* first_open,
+                       int32_t* heading_end, int64_t* line_start, int64_t* line_offsets, int32_t* status, int mem, void* stream) {
+    if (n < 0) return fail(RL_ERR_INVALID, "rl_markdown_blocks: n must be >= 0");
+    RL_TRY(check_mem(mem, "rl_markdown_blocks"));
+    if (n == 0) return RL_OK;
+    if (n_docs < 1) return fail(RL_ERR_INVALID, "rl_markdown_blocks: n_docs must be >= 1");
+    if (!codepoints) return fail(RL_ERR_INVALID, "rl_markdown_blocks: codepoints is null");
+    if (!doc_offsets) return fail(RL_ERR_INVALID, "rl_markdown_blocks: doc_offsets is null");
+    if (!first_open || !heading_end) return fail(RL_ERR_INVALID, "rl_markdown_blocks: first_open or heading_end is null");
+    if (!line_offsets) return fail(RL_ERR_INVALID, "rl_markdown_blocks: line_offsets is null");
+    if (!status) return fail(RL_ERR_INVALID, "rl_markdown_blocks: status is null");
+    const int64_t doc_max = ((int64_t)1 << 31) - 64;  // positions are int32 (markdown.hip: MB_DOC_MAX)
+    if (n_docs == 1 && n >= doc_max) return fail(RL_ERR_INVALID, "rl_markdown_blocks: a document must be shorter than 2^31 characters");
+    RL_TRY(check_doc_offsets("rl_markdown_blocks", doc_offsets, n, n_docs, mem, doc_max));
+    hipStream_t s = as_stream(stream);
+    Staging st(mem, s);
+    const size_t rows = (size_t)n + (size_t)n_docs;
+    const uint32_t* d_cp; const int64_t* d_off;
+    RL_TRY(st.in(codepoints, (size_t)n, &d_cp));
+    RL_TRY(st.in(doc_offsets, (size_t)n_docs + 1, &d_off));
+    uint8_t* d_first; int32_t* d_end; int64_t* d_start; int64_t* d_loff; int32_t* d_status;
+    RL_TRY(st.out(first_open, rows, &d_first));
+    RL_TRY(st.out(heading_end, rows, &d_end));
+    RL_TRY(st.out(line_start, rows, &d_start));  // (optional)
+    RL_TRY(st.out(line_offsets, (size_t)n_docs + 1, &d_loff));
+    RL_TRY(st.out(status, (size_t)n_docs, &d_status));
+    void* d_scr;
+    RL_TRY(st.temp(markdown_blocks_scratch_bytes(n, n_docs), &d_scr));
+    RL_TRY(launch_markdown_blocks(d_cp, d_off, n, n_docs, d_first, d_end, d_start, d_loff, d_status, d_scr, s));
+    return st.finish();
+}
+
+int rl_markdown_sentence_known(const int32_t* heading_end, const int64_t* line_start, const int64_t* line_offsets, const int32_t* status,
+                               const int64_t* doc_offsets, int64_t n, int64_t n_docs, int64_t n_lines, double* known, int mem,
+                               void* stream) {
+    if (n < 0 || n_lines < 0) return fail(RL_ERR_INVALID, "rl_markdown_sentence_known: n and n_lines must be >= 0");
+    RL_TRY(check_mem(mem, "rl_markdown_sentence_known"));
+    if (n == 0) return RL_OK;
+    if (n_docs < 1) return fail(RL_ERR_INVALID, "rl_markdown_sentence_known: n_docs must be >= 1");
+    if (!heading_end || !line_start || !line_offsets || !status || !doc_offsets || !known)
+        return fail(RL_ERR_INVALID, "rl_markdown_sentence_known: null argument");
+    RL_TRY(check_doc_offsets("rl_markdown_sentence_known", doc_offsets, n, n_docs, mem, 0));
+    RL_TRY(check_line_offsets("rl_markdown_sentence_known", line_offsets, n_docs, n_lines, mem));
+    hipStream_t s = as_stream(stream);
+    Staging st(mem, s);
+    const int32_t* d_end; const int64_t* d_start; const int64_t* d_loff; const int32_t* d_status; const int64_t* d_off; double* d_known;
+    RL_TRY(st.in(heading_end, (size_t)n_lines, &d_end));
+    RL_TRY(st.in(line_start, (size_t)n_lines, &d_start));
+    RL_TRY(st.in(line_offsets, (size_t)n_docs + 1, &d_loff));
+    RL_TRY(st.in(status, (size_t)n_docs, &d_status));
+    RL_TRY(st.in(doc_offsets, (size_t)n_docs + 1, &d_off));
+    RL_TRY(st.out(known, (size_t)n, &d_known));
+    void* d_scr;
+    RL_TRY(st.temp(markdown_known_scratch_bytes(n_lines), &d_scr));
+    RL_TRY(launch_markdown_sentence_known(d_end, d_start, d_loff, d_status, d_off, n, n_docs, n_lines, d_known, d_scr, s));
+    return st.finish();
+}
+
+int rl_markdown_chunklet_boundary(const uint8_t* first_open, const int64_t* line_start, const int64_t* line_offsets, const int32_t* status,
+                                  const int64_t* sentence_offsets, const int64_t* doc_offsets, int64_t n_sentences, int64_t n_docs,
+                                  int64_t n_lines, double* boundary, int mem, void* stream) {
+    if (n_sentences < 0 || n_lines < 0) return fail(RL_ERR_INVALID, "rl_markdown_chunklet_boundary: n_sentences and n_lines must be >= 0");
+    RL_TRY(check_mem(mem, "rl_markdown_chunklet_boundary"));
+    if (n_sentences == 0) return RL_OK;
+    if (n_docs < 1) return fail(RL_ERR_INVALID, "rl_markdown_chunklet_boundary: n_docs must be >= 1");
+    if (!first_open || !line_start || !line_offsets || !status || !sentence_offsets || !doc_offsets || !boundary)
+        return fail(RL_ERR_INVALID, "rl_markdown_chunklet_boundary: null argument");
+    RL_TRY(check_doc_offsets("rl_markdown_chunklet_boundary", doc_offsets, n_sentences, n_docs, mem, 0));
+    RL_TRY(check_line_offsets("rl_markdown_chunklet_boundary", line_offsets, n_docs, n_lines, mem));
+    if (mem == RL_MEM_HOST) {
+        if (sentence_offsets[0] < 0) return fail(RL_ERR_INVALID, "rl_markdown_chunklet_boundary: sentence_offsets must be >= 0");
+        for (int64_t i = 0; i < n_sentences; ++i)
+            if (sentence_offsets[i + 1] < sentence_offsets[i])
+                return fail(RL_ERR_INVALID, "rl_markdown_chunklet_boundary: sentence_offsets must be ascending");
+    }
+    hipStream_t s = as_stream(stream);
+    Staging st(mem, s);
+    const uint8_t* d_first; const int64_t* d_start; const int64_t* d_loff; const int32_t* d_status; const int64_t* d_soff; const int64_t* d_off;
+    double* d_out;
+    RL_TRY(st.in(first_open, (size_t)n_lines, &d_first));
+    RL_TRY(st.in(line_start, (size_t)n_lines, &d_start));
+    RL_TRY(st.in(line_offsets, (size_t)n_docs + 1, &d_loff));
+    RL_TRY(st.in(status, (size_t)n_docs, &d_status));
+    RL_TRY(st.in(sentence_offsets, (size_t)n_sentences + 1, &d_soff));
+    RL_TRY(st.in(doc_offsets, (size_t)n_docs + 1, &d_off));
+    RL_TRY(st.out(boundary, (size_t)n_sentences, &d_out));
+    void* d_scr;
+    RL_TRY(st.temp(markdown_boundary_scratch_bytes(n_sentences), &d_scr));
+    RL_TRY(launch_markdown_chunklet_boundary(d_first, d_start, d_loff, d_status, d_soff, d_off, n_sentences, n_docs, n_lines, d_out, d_scr, s));
+    return st.finish();
+}
+
 }  // extern "C"
 
 // ---- WordPiece on the device: texts -> token ids -> [CLS] q [SEP] d [SEP] rows (kernels in wordpiece.hip) ---------------

@@ -583,6 +583,21 @@ int launch_sentence_dp(const uint32_t* codepoints, const void* probas, int proba
                        int64_t n, int64_t n_docs, int64_t min_len, int64_t max_len, uint8_t* cut, double* objective, int32_t* status,
                        void* scratch, hipStream_t s);
 
+// markdown.hip: the block structure `MarkdownIt().parse` gives the splitters, batched over documents (the parser: markdown_blocks.h).
+// first_open / heading_end / line_start have n + n_docs rows (a bound on the lines), line_off [n_docs + 1] says which are used;
+// line_start is optional.  The two derived launchers take per-line arrays of n_lines rows (at least line_off[n_docs]).
+size_t markdown_blocks_scratch_bytes(int64_t n, int64_t n_docs);
+int launch_markdown_blocks(const uint32_t* codepoints, const int64_t* doc_off, int64_t n, int64_t n_docs, uint8_t* first_open,
+                           int32_t* heading_end, int64_t* line_start, int64_t* line_off, int32_t* status, void* scratch, hipStream_t s);
+size_t markdown_known_scratch_bytes(int64_t n_lines);
+int launch_markdown_sentence_known(const int32_t* heading_end, const int64_t* line_start, const int64_t* line_off, const int32_t* status,
+                                   const int64_t* doc_off, int64_t n, int64_t n_docs, int64_t n_lines, double* known, void* scratch,
+                                   hipStream_t s);
+size_t markdown_boundary_scratch_bytes(int64_t n_sent);
+int launch_markdown_chunklet_boundary(const uint8_t* first_open, const int64_t* line_start, const int64_t* line_off, const int32_t* status,
+                                      const int64_t* sent_off, const int64_t* sent_doc_off, int64_t n_sent, int64_t n_docs,
+                                      int64_t n_lines, double* boundary, void* scratch, hipStream_t s);
+
 // maxsim*.hip
 // The launchers of this section take what they read and write as a few plain views (nothing owns memory; api.hip builds them from an index
 // in one place: rows(idx), image(idx), chunks(idx), on(idx, s, run_if) ...), then what is their own.

@@ -231,4 +231,33 @@ struct EncoderClassifyScratch {  // rl_encoder_classify_pack, over the caller's 
     }
 };
 
+// ---- Markdown block structure (markdown.hip) ----------------------------------------------------------------------------------------------
+struct MarkdownScratch {  // launch_markdown_blocks: n characters in n_docs documents have at most n + n_docs lines
+    int32_t *bm, *em, *ts, *sc;  // [lines] the line table: begin, end, first non-space character, indent
+    uint8_t* lazy;               // [lines] the quote frame that made the line a lazy continuation
+    int32_t* flags;              // [n_docs] undecided before the parse: a foreign line separator, a tab in a line's indent
+    int32_t* save;               // [save_entries x 4] the quotes' save stacks: (line, bm, ts, sc)
+    int64_t* scan;               // [scan_items] the scratch of the line counts' exclusive scan
+    size_t lay(Carver c, size_t n, size_t n_docs, size_t save_entries, size_t scan_items) {
+        const size_t lines = n + n_docs;
+        bm = c.take<int32_t>(lines);
+        em = c.take<int32_t>(lines);
+        ts = c.take<int32_t>(lines);
+        sc = c.take<int32_t>(lines);
+        lazy = c.take<uint8_t>(lines);
+        flags = c.take<int32_t>(n_docs);
+        save = c.take<int32_t>(save_entries * 4);
+        scan = c.take<int64_t>(scan_items);
+        return c.off;
+    }
+};
+struct MarkdownKnownScratch {  // launch_markdown_sentence_known: ONE take, cleared by a single memset
+    uint8_t *body, *behind;    // [lines] the line is a heading's; the line follows a heading's last
+    size_t lay(Carver c, size_t lines) {
+        body = c.take<uint8_t>(2 * lines);
+        behind = Carver::sub(body, lines);
+        return c.off;
+    }
+};
+
 }  // namespace rl
